@@ -5,10 +5,24 @@ decimator (hb11x8, hb15, hb23, hb47 -> 312.5 kHz) -> WFM mono demod, plus the 81
 2048-sample frame.  One "step" = one pass of that chain over one batch of `--superframes` super-frames
 (131072 samples each) already resident in HBM.
 
-  python bench.py [--gpus N --steps K --warmup W]           # N = 1
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   # N = 1
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # one rank per GPU
 
-The same JSON line carries, under "configs", the other BASELINE workloads timed with the same discipline (warm-up, barrier
+A plain run does only what the headline needs: set-up, warm-up (W steps, the untimed settle phase settle(), one untimed call
+after re-tuning the oscillator, W steps), exactly K timed steps, the outputs of the last timed step if --dump-outputs is given,
+and the JSON line (value, ms_per_step and the headline kernel's roofline from the HIP events of the timed steps).  Everything
+else, described below, runs with --full only.
+
+--dump-outputs DIR (rank 0): what a caller of the timed path receives after the last timed step, as float32 .npy files:
+  audio.npy             [1, n / 64, 2]   the channel's audio (pebblegpu_receiver_audio), (re, im)
+  spectrum_sample.npy   [1, 512, 8192]   512 of the call's 16 384 spectrum rows (pebblegpu_receiver_spectrum), picked with
+                                         np.random.default_rng(0) and sorted; all rows when the call has no more than 512
+The input is regenerated from fixed seeds, and the re-tune resets the oscillator's phase, so that how many steps settle() ran
+does not reach the outputs: runs with the same arguments dump the same arrays.
+
+With --full the same JSON line also carries the un-settled rate (the K steps right after the W warm-ups, before settle()), the
+spectrum kernel alone, the measured copy peak and socket power, the CPU baseline (unless --no-cpu-baseline) and, under
+"configs" (unless --headline-only), the other BASELINE workloads timed with the same discipline (warm-up, barrier
 + device sync, K steps, barrier + device sync, max over ranks), each with its own per-kernel HIP-event times and roofline:
   configs[2]        2.048 Msps shared stream -> 256 tuned USB channels: mixer + hb11x4,hb15,hb19,hb31 + FastFIR 2048/1025
                     (the full mixer -> decimate -> FastFIR -> demod chain the metric names); N = 1 only (a one-GPU config)
@@ -21,7 +35,7 @@ Channels / streams are independent: every rank owns its shard, no
 collectives are the control-plane barrier and the max-over-ranks of the elapsed time (gloo, CPU tensors) -- weak scaling.
 Rank 0 prints ONE JSON line.  With fewer devices than ranks the run exits non-zero instead of oversubscribing a GPU.
 
-The CPU baseline leg builds and runs oracle/cpu_baseline.cpp (the oracle's scalar fp64 restatement of the reference chain,
+The CPU baseline leg (--full) builds and runs oracle/cpu_baseline.cpp (the oracle's scalar fp64 restatement of the reference chain,
 -O3 -march=native, std::threads over the host's cores); it is the only place this file touches oracle/.
 """
 import argparse
@@ -256,6 +270,21 @@ def control_plane_rehearsal(args, rank, world, dist):
         dist.destroy_process_group()
 
 
+DUMP_SPECTRUM_ROWS = 512
+
+
+def dump_outputs(rx, out_dir):
+    """--dump-outputs: the last call's audio and a fixed, seeded sample of its spectrum rows as float32 .npy (about 20 MB at the
+    default --superframes 256); see the module docstring."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = rx.audio()  # complex64 [C, n / D]
+    np.save(os.path.join(out_dir, "audio.npy"), np.ascontiguousarray(a).view(np.float32).reshape(a.shape + (2,)))
+    s = rx.spectrum()  # float32 [streams, frames, bins]
+    if s.shape[1] > DUMP_SPECTRUM_ROWS:
+        s = s[:, np.sort(np.random.default_rng(0).choice(s.shape[1], DUMP_SPECTRUM_ROWS, replace=False))]
+    np.save(os.path.join(out_dir, "spectrum_sample.npy"), np.ascontiguousarray(s, dtype=np.float32))
+
+
 def kernel_lines(groups):
     """[(name, ms, algorithmic bytes)] -> per-kernel dict + the dominant kernel's roofline object"""
     ks = {}
@@ -472,8 +501,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--superframes", type=int, default=256, help="super-frames (131072 samples) per step per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip the configs[2..4] legs, the raw-int8 leg and the PCIe-inclusive rates")
+    ap.add_argument("--full", action="store_true",
+                    help="also the un-settled rate, the spectrum kernel alone, the copy peak, socket power, the CPU baseline, the configs[2..4] "
+                         "legs, the raw-int8 leg and the PCIe-inclusive rates (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's audio and a seeded sample of its spectrum rows to DIR/*.npy (float32; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the configs[2..4] legs, the raw-int8 leg and the PCIe-inclusive rates")
     ap.add_argument("--control-plane-only", action="store_true",
                     help="CPU rehearsal of the N>1 launch path (rendezvous, barriers, max-over-ranks, aggregation, shard ranges): "
                          "the GPU step is replaced by a rank-dependent sleep; used by tests/test_multirank_gloo.py")
@@ -511,7 +545,8 @@ def main():
     n = args.superframes * sf
     x = make_input(n, 1000 * (rank + 1))
     dbuf = P.DeviceBuffer.from_array(P.binding.to_f32_iq(x), device)  # inputs resident in HBM before timing
-    raw8 = np.clip(np.round(x.view(np.float32) * 128), -128, 127).astype(np.int8)  # the same samples as HackRF int8 pairs
+    raw_leg = args.full and not args.headline_only and world == 1
+    raw8 = np.clip(np.round(x.view(np.float32) * 128), -128, 127).astype(np.int8) if raw_leg else None  # the same samples as HackRF int8 pairs
     del x
 
     def barrier():
@@ -525,20 +560,25 @@ def main():
     for _ in range(args.warmup):
         step()
     rx.synchronize()
-    # the K steps right behind the driver's W warm-ups, before any settling: what the flags alone measure (inside the clocks' ramp)
-    elapsed_unsettled = timed_steps(step, barrier, args.steps, dist)
+    if args.full:
+        # the K steps right behind the driver's W warm-ups, before any settling: what the flags alone measure (inside the clocks' ramp)
+        elapsed_unsettled = timed_steps(step, barrier, args.steps, dist)
     settled = settle(step, rx.synchronize)  # untimed: the clocks' ramp after set-up is not the workload's rate
-    # untimed, for reference only: the dominant kernel alone on the device (per-kernel profiling keeps the whole call on one
-    # stream); in the timed steps the chain's first, memory-bound kernel runs beside it on a second stream
-    rx.set_profiling(True)
-    for _ in range(3):
-        rx.process_device(dbuf.ptr, n)
-    rx.synchronize()
-    alone_ms = rx.mean_ms(1, 3)
-    alone = {w: rx.mean_ms(w, 3) for w in (2, 3, 5)}
-    alone_names = {w: rx.kernel_name(w) for w in (2, 3, 5)}
-    alone_spec_name = rx.kernel_name(1)  # (with nothing beside it the library launches the transform's all-registers variant)
-    rx.set_profiling(False)
+    if args.full:
+        # untimed, for reference only: the dominant kernel alone on the device (per-kernel profiling keeps the whole call on one
+        # stream); in the timed steps the chain's first, memory-bound kernel runs beside it on a second stream
+        rx.set_profiling(True)
+        for _ in range(3):
+            rx.process_device(dbuf.ptr, n)
+        rx.synchronize()
+        alone_ms = rx.mean_ms(1, 3)
+        alone = {w: rx.mean_ms(w, 3) for w in (2, 3, 5)}
+        alone_names = {w: rx.kernel_name(w) for w in (2, 3, 5)}
+        alone_spec_name = rx.kernel_name(1)  # (with nothing beside it the library launches the transform's all-registers variant)
+        rx.set_profiling(False)
+    # re-tuning resets the oscillator's phase (Mixer::setFrequency); after this untimed call the chain's state no longer depends
+    # on how many steps settle() ran, so the timed steps compute the same from run to run
+    rx.set_mixer(0, MIX_HZ)
     rx.process_device(dbuf.ptr, n)
     rx.synchronize()
 
@@ -550,9 +590,11 @@ def main():
     k_ev = min(args.steps, 64)
     spec_ms = rx.mean_ms(1, k_ev)
     chain_ms = rx.mean_ms(0, k_ev) - spec_ms
+    if args.dump_outputs and rank == 0:
+        dump_outputs(rx, args.dump_outputs)
 
     extra, raw_line, pcie = {}, None, None
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         if world == 1:
             # the headline fed in the device's own sample format (2 B/sample in): normalizeIQ runs on the device
             rbuf = P.DeviceBuffer.from_array(raw8, device)
@@ -567,16 +609,16 @@ def main():
             pcie = pcie_inclusive(P, rx, n, device)
     del raw8
     rx_info = {"frames": n // NF}
-    power = socket_power(step, rx.synchronize) if (rank == 0 and world == 1 and not args.headline_only) else None
+    power = socket_power(step, rx.synchronize) if (args.full and rank == 0 and world == 1 and not args.headline_only) else None
     copy_gbps = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             copy_gbps = round(P.binding.probe_copy_gbps(16, 1 << 30, 10, device), 1)  # measured float4 streaming copy, read+write
         except Exception:
             copy_gbps = None
     rx.close()
     dbuf.free()
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         if world == 1:
             extra["configs[2]"] = run_bank(P, "configs[2]: 2.048 Msps shared stream -> 256 tuned USB channels, mixer + decimate + FastFIR 2048/1025 (300-3000 Hz), 8 super-frames per step",
                                            2_048_000, 256, [P.DM_USB], 8, rank, world, device, barrier, args, dist)
@@ -599,9 +641,14 @@ def main():
             "warmup": args.warmup,
             "settle_steps": settled,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "value_unsettled": round(aggregate_msps(n * args.steps, world, elapsed_unsettled), 2),
-            "ms_per_step_unsettled": round(elapsed_unsettled / args.steps * 1e3, 4),
-            "unsettled_note": "the same K steps timed right after the W warm-up steps, before the untimed settle phase (`value` is the settled rate)",
+        }
+        if args.full:
+            out.update({
+                "value_unsettled": round(aggregate_msps(n * args.steps, world, elapsed_unsettled), 2),
+                "ms_per_step_unsettled": round(elapsed_unsettled / args.steps * 1e3, 4),
+                "unsettled_note": "the same K steps timed right after the W warm-up steps, before the untimed settle phase (`value` is the settled rate)",
+            })
+        out.update({
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -610,17 +657,19 @@ def main():
             "config": {"workload": "configs[1]: 20 Msps int8-shape IQ (values k/128, resident in HBM as float2), 1 channel/GPU, mixer+decimate(D=64)+WFM mono demod + 8192-bin SignalSpectrum per 2048-sample frame",
                        "samples_per_step_per_gpu": n, "frames_per_buffer": NF, "spectrum_bins": BINS,
                        "parallelism": "independent channel per GPU, no collectives"},
-            "roofline": {"bound": "hbm", "kernel": "k_spectrum_t128", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "measured_copy_peak_GBs": copy_gbps,
-                         "socket_power": power,
-                         "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_ms": round(spec_ms, 4),
-                         "rest_of_chain_ms": round(chain_ms, 4),
-                         "co_scheduled": "the chain runs on a second stream beside this kernel (its first stage needs no LDS)",
-                         "avg_launch_ms_alone": round(float(alone_ms), 4), "kernel_alone": alone_spec_name,
+        })
+        roof = {"bound": "hbm", "kernel": "k_spectrum_t128", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src}
+        if args.full:
+            roof.update({"measured_copy_peak_GBs": copy_gbps, "socket_power": power})
+        roof.update({"algorithmic_bytes_per_launch": algo_bytes, "avg_launch_ms": round(spec_ms, 4),
+                     "rest_of_chain_ms": round(chain_ms, 4),
+                     "co_scheduled": "the chain runs on a second stream beside this kernel (its first stage needs no LDS)"})
+        if args.full:
+            roof.update({"avg_launch_ms_alone": round(float(alone_ms), 4), "kernel_alone": alone_spec_name,
                          "frac_alone": round(algo_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "chain_kernels_alone_ms": {alone_names[w]: round(alone[w], 4) for w in alone if alone_names[w]}},
-        }
+                         "chain_kernels_alone_ms": {alone_names[w]: round(alone[w], 4) for w in alone if alone_names[w]}})
+        out["roofline"] = roof
         if "configs[2]" in extra:
             c2 = extra["configs[2]"]
             # the one single-GPU workload that runs the whole chain the metric names (mixer -> decimate -> FastFIR -> demod), lifted
@@ -635,7 +684,7 @@ def main():
             out["pcie_inclusive"] = pcie
         if extra:
             out["configs"] = extra
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(1, 8, "configs[1] (20 Msps WFM mono + 8192-bin spectrum per frame; one channel per thread, as one channel per GPU)")
             if not args.headline_only:
                 for key, wl, what in (("configs[2]", 2, "the 256-channel bank"), ("configs[3] shard", 3, "the 512-channel shard, a 64-frame sample of its 2048-frame super-frame"),

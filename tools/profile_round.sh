@@ -9,9 +9,9 @@ mkdir -p $o
 set -e
 timeout -k 10 1000 python3 -m pytest tests -x -q -m gpu > $o/${tag}_gpu_tests.log 2>&1 || { tail -30 $o/${tag}_gpu_tests.log; exit 1; }
 tail -2 $o/${tag}_gpu_tests.log
-timeout -k 10 600 python3 bench.py > $o/${tag}_bench.json 2> $o/${tag}_bench.err
+timeout -k 10 600 python3 bench.py --full > $o/${tag}_bench.json 2> $o/${tag}_bench.err
 # per-kernel durations of the bench command
-rm -rf $o/${tag}_trace; rocprofv3 --kernel-trace --stats -d $o/${tag}_trace -- python3 bench.py --steps 20 --no-cpu-baseline > $o/${tag}_trace.log 2>&1
+rm -rf $o/${tag}_trace; rocprofv3 --kernel-trace --stats -d $o/${tag}_trace -- python3 bench.py --full --steps 20 --no-cpu-baseline > $o/${tag}_trace.log 2>&1
 python3 tools/kernel_stats.py $o/${tag}_trace $o/${tag}_kernel_stats.csv > /dev/null
 # HBM traffic of the headline workload, the configs[2] bank, the configs[3] shard and the configs[4] shard (separate FETCH_SIZE / WRITE_SIZE passes)
 export PMC_CALIBRATE=1
