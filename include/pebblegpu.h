@@ -217,6 +217,42 @@ const void *pebblegpu_receiver_audio(const pebblegpu_receiver *rx, uint64_t *sam
 const void *pebblegpu_receiver_spectrum(const pebblegpu_receiver *rx, uint64_t *frames_per_stream);
 /* the zoomed (hi-res) spectra of the last call: [channel][frames_per_channel][bins] float dB, -f..+f at the demodulator rate */
 const void *pebblegpu_receiver_zoom_spectrum(const pebblegpu_receiver *rx, uint64_t *frames_per_channel, uint32_t *bins);
+
+/* ------------------------------------------------------------------------------------------------
+ * Spectrum to display pixels: FFT::mapFFTToScreen (pebblelib/fft.cpp:400-534), the call SpectrumWidget makes for every plot and
+ * every waterfall row (through SignalSpectrum::mapFFTToScreen / mapFFTZoomedToScreen, application/signalspectrum.cpp:137-167).
+ * Each spectrum row of fftSize dB values becomes x_pixels plot heights in 0..y_pixels-1: bins are averaged in power where several
+ * fall on one pixel (the reference's window [previous pixel's bin, this pixel's bin), and only from pixel 2 on), repeated where one
+ * bin spans several pixels, -120 dB outside the spectrum.  The arithmetic is the reference's as an x86-64 build runs it (float where
+ * it is float, no contraction, truncating conversions); the per-pixel power sum may be added in another order and pow / log10 are
+ * the device's: an averaged pixel whose unrounded value lies within 1e-9 of an integer may come out one powerdB step away.
+ * Refused before anything is queued, leaving the handle usable (PEBBLEGPU_E_INVALID): x_pixels <= 0, y_pixels <= 0,
+ * max_db == min_db, a handle with no such spectrum or no call yet, a frame range beyond the last call.  Every other input the
+ * reference accepts is reproduced, start_freq >= stop_freq and ranges wholly outside the spectrum included.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct pebblegpu_screen_map {
+    uint32_t struct_size;           /* = sizeof(pebblegpu_screen_map) */
+    int32_t y_pixels;               /* plot height; 255 for the waterfall colour index (spectrumwidget.cpp:1285-1293) */
+    int32_t x_pixels;               /* plot width */
+    double max_db, min_db;          /* dB at the top / bottom of the plot */
+    int32_t start_freq, stop_freq;  /* Hz, relative to the spectrum's centre */
+    uint32_t reserved[4];
+} pebblegpu_screen_map;
+/* Maps frames first_frame + j * frame_step (j < n_frames) of every stream of the last call's unprocessed spectrum
+ * (pebblegpu_receiver_spectrum; sampleRate = the configured stream rate, fftSize = info.spectrum_bins) into the device buffer
+ * d_out: int32 [stream][n_frames][x_pixels].  Queued behind the call's display transform and ahead of the next call's, on the
+ * receiver's streams (default side-by-side calls and PEBBLEGPU_PIPELINE=1 alike); d_out holds the result after
+ * pebblegpu_receiver_synchronize.  A display that shows one frame maps the last one; a waterfall maps a stride. */
+int pebblegpu_receiver_map_spectrum(pebblegpu_receiver *rx, const pebblegpu_screen_map *map, uint32_t first_frame, uint32_t n_frames,
+                                    uint32_t frame_step, int32_t *d_out);
+/* The same on the zoomed spectra (pebblegpu_receiver_zoom_spectrum), per channel: int32 [channel][n_frames][x_pixels].  As
+ * SignalSpectrum::mapFFTZoomedToScreen (signalspectrum.cpp:151-167): quint16 span = hiResRate * zoom, start = -span/2 - offset,
+ * stop = span/2 - offset in int, hiResRate = info.demod_rate_int (the rate the zoomed transform ran at, receiver.cpp:221,644-646),
+ * offset = mode_offset[channel] (host array of n_channels; NULL: all 0).  A product hiResRate * zoom of 65536 or more does not fit
+ * the quint16 and the reference's conversion is undefined: as on x86-64 it is truncated to int32 and the low 16 bits are kept. */
+int pebblegpu_receiver_map_zoom_spectrum(pebblegpu_receiver *rx, int32_t y_pixels, int32_t x_pixels, double max_db, double min_db, double zoom,
+                                         const int32_t *mode_offset, uint32_t first_frame, uint32_t n_frames, uint32_t frame_step,
+                                         int32_t *d_out);
 /* Time of the last process call's kernels in ms, from HIP events on the library's stream.  which: 0 whole
  * call; 1 spectrum kernel; 2 mixer+first-decimator kernel; 3 remaining decimator stages; 4 FastFIR;
  * 5 demod.  A call whose chain runs beside its display transform records no end event of its own: which = 0
@@ -322,6 +358,12 @@ const void *pebblegpu_streambank_spectrum(const pebblegpu_streambank *sb, uint64
 /* which: 0 whole call, 1 band-pass kernel, 2 spectrum kernels */
 int pebblegpu_streambank_last_ms(const pebblegpu_streambank *sb, int which, float *ms);
 int pebblegpu_streambank_synchronize(pebblegpu_streambank *sb);
+/* FFT::mapFFTToScreen (see pebblegpu_screen_map above) of frames first_frame + j * frame_step (j < n_frames) of every stream of the
+ * last call's spectrum (sampleRate = the bank's sample_rate, fftSize = spectrum_bins; 65536 with the clamp lifted) into the device
+ * buffer d_out: int32 [stream][n_frames][x_pixels].  Queued behind the call's transform on the bank's stream; d_out holds the result
+ * after pebblegpu_streambank_synchronize. */
+int pebblegpu_streambank_map_spectrum(pebblegpu_streambank *sb, const pebblegpu_screen_map *map, uint32_t first_frame, uint32_t n_frames,
+                                      uint32_t frame_step, int32_t *d_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Stand-alone process steps with the reference's per-class call shapes, host buffers in and out.
@@ -406,6 +448,10 @@ int pebblegpu_spectrum_destroy(pebblegpu_spectrum *s);
 int pebblegpu_spectrum_bins(const pebblegpu_spectrum *s, uint32_t *bins);
 /* bool FFT::fftSpectrum(CPX *in, double *out, int numSamples), pebblelib/fft.h:38; *overload = return value */
 int pebblegpu_spectrum_process(pebblegpu_spectrum *s, const double *in, int n, double *out_db, int *overload);
+/* bool FFT::mapFFTToScreen(double *inBuf, ...), pebblelib/fft.h:53-56, with inBuf = the out of the last pebblegpu_spectrum_process
+ * (what SignalSpectrum always passes): that spectrum, exactly the floats the call handed out as doubles, mapped on the device into
+ * the host buffer out (x_pixels int32); sampleRate is the one the object was created with.  Blocks until out is written. */
+int pebblegpu_spectrum_map_to_screen(pebblegpu_spectrum *s, const pebblegpu_screen_map *map, int32_t *out);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,9 @@
 //   BandPassFilter::setBandPass / process       application/bandpassfilter.h    BandPassFilter
 //   CPX *Demod::processBlock(CPX*, int) / setDemodMode / setBandwidth
 //                                               application/demod.h:33-40       Demod
-//   FFT::fftParams / bool fftSpectrum(CPX*, double*, int)   pebblelib/fft.h:30-38   FFT
+//   FFT::fftParams / bool fftSpectrum(CPX*, double*, int) / bool mapFFTToScreen(...)   pebblelib/fft.h:30-56   FFT
+//   WindowFunction::WINDOWTYPE                  pebblelib/windowfunction.h:10-11   WindowFunction
+//   bool SignalSpectrum::mapFFTToScreen(...)    application/signalspectrum.cpp:137-149   Receiver::mapFFTToScreen
 //   void Receiver::processIQData(CPX*, quint16) application/receiver.cpp:758    Receiver::processIQData
 //   CB_ProcessIQData / CB_ProcessAudioData      pebblelib/device_interfaces.h:32,38   same std::function shapes
 //   FileSDRDevice (initialize / Cmd_Start pump) plugins/FileSDRDevice/filesdrdevice.cpp:24-33,226-289   FileSdrFeeder
@@ -251,7 +253,14 @@ private:
     DemodMode mode = dmAM;
 };
 
-// pebblelib/fft.h as SignalSpectrum uses it (factory + fftParams + fftSpectrum); window type is BLACKMANHARRIS
+// pebblelib/windowfunction.h:10-11: the window types FFT::fftParams takes, with the reference's numeric values
+class WindowFunction {
+public:
+    enum WINDOWTYPE { RECTANGULAR = 1, HANNING, WELCH, PARZEN, BARTLETT, HAMMING, BLACKMAN2, BLACKMAN3, BLACKMAN4, EXPONENTIAL, RIEMANN,
+                      BLACKMANHARRIS, BLACKMAN, NONE };
+};
+
+// pebblelib/fft.h as SignalSpectrum uses it (factory + fftParams + fftSpectrum + mapFFTToScreen); window type is BLACKMANHARRIS
 class FFT {
 public:
     explicit FFT(int device_ = 0) : device(device_) {}
@@ -266,6 +275,20 @@ public:
         bins = 0;
         if (h) pebblegpu_spectrum_bins(h, &bins);
     }
+    // the reference's five-argument form (fft.h:29-30, the call SignalSpectrum::setSampleRate makes, signalspectrum.cpp:58-59): the device
+    // transform windows with Blackman-Harris only -- any other type leaves no handle and lastStatus() = PEBBLEGPU_E_UNSUPPORTED
+    void fftParams(uint32_t fftSize, double dBCompensation, double sampleRate, int samplesPerBuffer, WindowFunction::WINDOWTYPE windowType)
+    {
+        if (windowType != WindowFunction::BLACKMANHARRIS) {
+            pebblegpu_spectrum_destroy(h);
+            h = nullptr;
+            bins = 0;
+            status = PEBBLEGPU_E_UNSUPPORTED;
+            std::fprintf(stderr, "pebblegpu: fftParams: window type %d is not implemented on the device (BLACKMANHARRIS only)\n", (int)windowType);
+            return;
+        }
+        fftParams(fftSize, dBCompensation, sampleRate, samplesPerBuffer);
+    }
     int getFFTSize() const { return (int)bins; }
     bool fftSpectrum(CPX *in, double *out, int numSamples)
     {
@@ -273,6 +296,25 @@ public:
         if (!h) return false;  // "if (!m_fftParamsSet) return false;"
         status = report("spectrum_process", pebblegpu_spectrum_process(h, reinterpret_cast<const double *>(in), numSamples, out, &ov));
         return ov != 0;
+    }
+    // bool FFT::mapFFTToScreen (fft.h:53-56, fft.cpp:411-534) on the device.  inBuf must be the out of this object's last fftSpectrum
+    // call -- what SignalSpectrum always passes (signalspectrum.cpp:146, :164): the library maps its own copy of that spectrum and does
+    // not read inBuf.  Returns false, as the reference does; outBuf receives xPixels values (untouched when the call is refused).
+    bool mapFFTToScreen(double * /*inBuf*/, int32_t yPixels, int32_t xPixels, double maxdB, double mindB, int32_t startFreq, int32_t stopFreq,
+                        int32_t *outBuf)
+    {
+        if (!h) return false;
+        pebblegpu_screen_map m;
+        std::memset(&m, 0, sizeof(m));
+        m.struct_size = sizeof(m);
+        m.y_pixels = yPixels;
+        m.x_pixels = xPixels;
+        m.max_db = maxdB;
+        m.min_db = mindB;
+        m.start_freq = startFreq;
+        m.stop_freq = stopFreq;
+        status = report("spectrum_map_to_screen", pebblegpu_spectrum_map_to_screen(h, &m, outBuf));
+        return false;
     }
     int lastStatus() const { return status; }
 
@@ -289,7 +331,7 @@ public:
     // audioOutRate: Key_AudioOutputSampleRate (receiver.cpp:203); 0 keeps the audio at the demod rate
     Receiver(uint32_t sampleRate, uint16_t framesPerBuffer, bool wfm, uint32_t spectrumBins, CB_ProcessAudioData audioCb,
              uint32_t fastfirFft = 0, uint32_t fastfirTaps = 0, int device = 0, uint32_t audioOutRate = 0)
-        : n(framesPerBuffer), cb(audioCb)
+        : n(framesPerBuffer), cb(audioCb), dev(device)
     {
         pebblegpu_config cfg;
         std::memset(&cfg, 0, sizeof(cfg));
@@ -313,7 +355,11 @@ public:
             demodRate = info.demod_rate_int;
         }
     }
-    ~Receiver() { pebblegpu_receiver_destroy(h); }
+    ~Receiver()
+    {
+        if (dPx) pebblegpu_free(dev, dPx);
+        pebblegpu_receiver_destroy(h);
+    }
     Receiver(const Receiver &) = delete;
     Receiver &operator=(const Receiver &) = delete;
     void mixerChanged(int f) { if (h) status = report("set_mixer_freq", pebblegpu_set_mixer_freq(h, 0, f)); }               // receiver.cpp:709
@@ -334,6 +380,34 @@ public:
         }
     }
     const std::vector<double> &unprocessedSpectrum() const { return spectrum; }  // SignalSpectrum::getUnprocessed
+    // bool SignalSpectrum::mapFFTToScreen(qint32 maxHeight, qint32 maxWidth, double maxdB, double mindB, qint32 startFreq,
+    // qint32 stopFreq, qint32 *outBuf), signalspectrum.cpp:137-149: the last frame's unprocessed spectrum mapped on the device
+    // (pebblegpu_receiver_map_spectrum), maxWidth values into outBuf.  Returns false, as the reference does.
+    bool mapFFTToScreen(int32_t maxHeight, int32_t maxWidth, double maxdB, double mindB, int32_t startFreq, int32_t stopFreq, int32_t *outBuf)
+    {
+        if (!h || !outBuf || maxWidth <= 0) return false;
+        uint64_t frames = 0;
+        pebblegpu_receiver_spectrum(h, &frames);
+        if ((size_t)maxWidth > pxCap) {
+            if (dPx) pebblegpu_free(dev, dPx);
+            dPx = nullptr;
+            pxCap = 0;
+            if ((status = report("malloc", pebblegpu_malloc(dev, sizeof(int32_t) * (size_t)maxWidth, &dPx))) != 0) return false;
+            pxCap = (size_t)maxWidth;
+        }
+        pebblegpu_screen_map m;
+        std::memset(&m, 0, sizeof(m));
+        m.struct_size = sizeof(m);
+        m.y_pixels = maxHeight;
+        m.x_pixels = maxWidth;
+        m.max_db = maxdB;
+        m.min_db = mindB;
+        m.start_freq = startFreq;
+        m.stop_freq = stopFreq;
+        status = report("receiver_map_spectrum", pebblegpu_receiver_map_spectrum(h, &m, frames ? (uint32_t)(frames - 1) : 0u, 1, 1, static_cast<int32_t *>(dPx)));
+        if (status == 0) status = report("memcpy_d2h", pebblegpu_memcpy_d2h(dev, outBuf, dPx, sizeof(int32_t) * (size_t)maxWidth));
+        return false;
+    }
     uint32_t demodSampleRate() const { return demodRate; }
     int lastStatus() const { return status; }
 
@@ -345,6 +419,9 @@ private:
     std::vector<double> spectrum;
     uint32_t demodRate = 0;
     int status = 0;
+    int dev;
+    void *dPx = nullptr;  // the mapped pixels on the device (mapFFTToScreen)
+    size_t pxCap = 0;
 };
 
 // Qt-free stand-in for plugins/FileSDRDevice: reads a RIFF/WAVE IQ recording (16-bit PCM stereo, /32767 as

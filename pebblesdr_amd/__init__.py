@@ -6,12 +6,12 @@ no CPU implementation here: importing works anywhere, but every compute call nee
 library and a HIP device and fails loudly otherwise.
 """
 from .binding import (  # noqa: F401
-    PebbleGpuError, load_library, library_path, ReceiverBank, StreamBank, DeviceBuffer,
+    PebbleGpuError, load_library, library_path, ReceiverBank, StreamBank, DeviceBuffer, ScreenMap, screen_map,
     DM_AM, DM_SAM, DM_FMN, DM_FMM, DM_FMS, DM_DSB, DM_LSB, DM_USB, DM_CWL, DM_CWU, DM_DIGL, DM_DIGU, DM_NONE,
 )
 from .steps import Mixer, Decimator, DownConvert, FastFIR, Demod, Spectrum  # noqa: F401
 
 __all__ = [
-    "PebbleGpuError", "load_library", "library_path", "ReceiverBank", "StreamBank", "DeviceBuffer",
+    "PebbleGpuError", "load_library", "library_path", "ReceiverBank", "StreamBank", "DeviceBuffer", "ScreenMap", "screen_map",
     "Mixer", "Decimator", "DownConvert", "FastFIR", "Demod", "Spectrum",
 ]

@@ -31,6 +31,8 @@ SYMBOLS = [
     "pebblegpu_demod_create", "pebblegpu_demod_destroy", "pebblegpu_demod_set_mode", "pebblegpu_demod_set_bandwidth",
     "pebblegpu_demod_process", "pebblegpu_demod_rds_groups", "pebblegpu_demod_rds_signal", "pebblegpu_demod_stereo_lock",
     "pebblegpu_spectrum_create", "pebblegpu_spectrum_destroy", "pebblegpu_spectrum_bins", "pebblegpu_spectrum_process",
+    "pebblegpu_receiver_map_spectrum", "pebblegpu_receiver_map_zoom_spectrum", "pebblegpu_streambank_map_spectrum",
+    "pebblegpu_spectrum_map_to_screen",
 ]
 
 
@@ -56,6 +58,39 @@ class StreamBankConfig(C.Structure):
         ("frame", C.c_uint32), ("spectrum_bins", C.c_uint32), ("fastfir_fft", C.c_uint32), ("fastfir_taps", C.c_uint32),
         ("max_frames", C.c_uint32), ("reserved", C.c_uint32 * 5),
     ]
+
+
+class ScreenMap(C.Structure):
+    """pebblegpu_screen_map: FFT::mapFFTToScreen's plot geometry (pebblelib/fft.cpp:411-419)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("y_pixels", C.c_int32), ("x_pixels", C.c_int32), ("max_db", C.c_double), ("min_db", C.c_double),
+        ("start_freq", C.c_int32), ("stop_freq", C.c_int32), ("reserved", C.c_uint32 * 4),
+    ]
+
+
+def screen_map(y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq):
+    m = ScreenMap()
+    m.struct_size = C.sizeof(ScreenMap)
+    m.y_pixels, m.x_pixels = int(y_pixels), int(x_pixels)
+    m.max_db, m.min_db = float(max_db), float(min_db)
+    m.start_freq, m.stop_freq = int(start_freq), int(stop_freq)
+    return m
+
+
+def _frame_range(frames, first_frame, n_frames, frame_step):
+    """None for first_frame maps the last frame; None for n_frames every frame from first_frame on at frame_step"""
+    if first_frame is None:
+        first_frame = frames - 1 if frames else 0
+    if n_frames is None:
+        n_frames = max(0, (frames - first_frame + frame_step - 1) // frame_step) if frame_step else 1
+    return int(first_frame), int(n_frames), int(frame_step)
+
+
+def _download_i32(L, device, p, shape):
+    out = np.empty(shape, dtype=np.int32)
+    if out.size:
+        check(L, L.pebblegpu_memcpy_d2h(device, out.ctypes.data_as(C.c_void_p), C.c_void_p(p), out.nbytes))
+    return out
 
 
 class Info(C.Structure):
@@ -164,6 +199,11 @@ def _declare(L):
     L.pebblegpu_spectrum_destroy.argtypes = [vp]
     L.pebblegpu_spectrum_bins.argtypes = [vp, C.POINTER(u32)]
     L.pebblegpu_spectrum_process.argtypes = [vp, dp, i32, dp, C.POINTER(i32)]
+    smp, ip = C.POINTER(ScreenMap), C.POINTER(C.c_int32)
+    L.pebblegpu_receiver_map_spectrum.argtypes = [vp, smp, u32, u32, u32, vp]
+    L.pebblegpu_receiver_map_zoom_spectrum.argtypes = [vp, C.c_int32, C.c_int32, dbl, dbl, dbl, ip, u32, u32, u32, vp]
+    L.pebblegpu_streambank_map_spectrum.argtypes = [vp, smp, u32, u32, u32, vp]
+    L.pebblegpu_spectrum_map_to_screen.argtypes = [vp, smp, ip]
     return L
 
 
@@ -426,6 +466,51 @@ class ReceiverBank:
             check(self.L, self.L.pebblegpu_memcpy_d2h(self.device, out.ctypes.data_as(C.c_void_p), C.c_void_p(p), out.nbytes))
         return out
 
+    def map_spectrum_device(self, d_out, y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq, first_frame, n_frames, frame_step=1):
+        """queue FFT::mapFFTToScreen of the last call's spectrum into the device buffer d_out (int32 [streams, n_frames, x_pixels])"""
+        m = screen_map(y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq)
+        check(self.L, self.L.pebblegpu_receiver_map_spectrum(self.h, C.byref(m), int(first_frame), int(n_frames), int(frame_step), C.c_void_p(d_out)))
+
+    def map_zoom_spectrum_device(self, d_out, y_pixels, x_pixels, max_db, min_db, zoom, mode_offset, first_frame, n_frames, frame_step=1):
+        """queue SignalSpectrum::mapFFTZoomedToScreen of the last call's zoomed spectra into d_out (int32 [channels, n_frames, x_pixels])"""
+        off = None
+        if mode_offset is not None:
+            off = np.ascontiguousarray(np.broadcast_to(np.asarray(mode_offset, dtype=np.int32), (self.n_channels,)))
+        check(self.L, self.L.pebblegpu_receiver_map_zoom_spectrum(self.h, int(y_pixels), int(x_pixels), float(max_db), float(min_db), float(zoom),
+                                                                  off.ctypes.data_as(C.POINTER(C.c_int32)) if off is not None else None,
+                                                                  int(first_frame), int(n_frames), int(frame_step), C.c_void_p(d_out)))
+
+    def map_spectrum(self, y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq, first_frame=None, n_frames=None, frame_step=1):
+        """FFT::mapFFTToScreen on the device -> int32 [streams, n_frames, x_pixels]; frames first_frame + j * frame_step of the
+        last call (default: its last frame only when first_frame is None, every frame from first_frame on otherwise)"""
+        n = C.c_uint64()
+        self.L.pebblegpu_receiver_spectrum(self.h, C.byref(n))
+        if first_frame is None and n_frames is None:
+            n_frames = 1
+        first_frame, n_frames, frame_step = _frame_range(int(n.value), first_frame, n_frames, frame_step)
+        buf = DeviceBuffer(4 * max(1, self.n_streams * n_frames * int(x_pixels)), self.device, self.L)
+        try:
+            self.map_spectrum_device(buf.ptr, y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq, first_frame, n_frames, frame_step)
+            self.synchronize()
+            return _download_i32(self.L, self.device, buf.ptr, (self.n_streams, n_frames, int(x_pixels)))
+        finally:
+            buf.free()
+
+    def map_zoom_spectrum(self, y_pixels, x_pixels, max_db, min_db, zoom=1.0, mode_offset=None, first_frame=None, n_frames=None, frame_step=1):
+        """SignalSpectrum::mapFFTZoomedToScreen per channel on the device -> int32 [channels, n_frames, x_pixels]"""
+        f, b = C.c_uint64(), C.c_uint32()
+        self.L.pebblegpu_receiver_zoom_spectrum(self.h, C.byref(f), C.byref(b))
+        if first_frame is None and n_frames is None:
+            n_frames = 1
+        first_frame, n_frames, frame_step = _frame_range(int(f.value), first_frame, n_frames, frame_step)
+        buf = DeviceBuffer(4 * max(1, self.n_channels * n_frames * int(x_pixels)), self.device, self.L)
+        try:
+            self.map_zoom_spectrum_device(buf.ptr, y_pixels, x_pixels, max_db, min_db, zoom, mode_offset, first_frame, n_frames, frame_step)
+            self.synchronize()
+            return _download_i32(self.L, self.device, buf.ptr, (self.n_channels, n_frames, int(x_pixels)))
+        finally:
+            buf.free()
+
     def process(self, iq):
         """iq: complex [streams, n] (or [n] for one stream).  Returns (audio [C, n/D], spectrum or None)."""
         iq = np.atleast_2d(np.asarray(iq))
@@ -520,6 +605,26 @@ class StreamBank:
         if out.size:
             check(self.L, self.L.pebblegpu_memcpy_d2h(self.device, out.ctypes.data_as(C.c_void_p), C.c_void_p(p), out.nbytes))
         return out
+
+    def map_spectrum_device(self, d_out, y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq, first_frame, n_frames, frame_step=1):
+        """queue FFT::mapFFTToScreen of the last call's spectrum into the device buffer d_out (int32 [streams, n_frames, x_pixels])"""
+        m = screen_map(y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq)
+        check(self.L, self.L.pebblegpu_streambank_map_spectrum(self.h, C.byref(m), int(first_frame), int(n_frames), int(frame_step), C.c_void_p(d_out)))
+
+    def map_spectrum(self, y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq, first_frame=None, n_frames=None, frame_step=1):
+        """FFT::mapFFTToScreen on the device -> int32 [streams, n_frames, x_pixels] (default: the last frame of each stream)"""
+        f, b = C.c_uint64(), C.c_uint32()
+        self.L.pebblegpu_streambank_spectrum(self.h, C.byref(f), C.byref(b))
+        if first_frame is None and n_frames is None:
+            n_frames = 1
+        first_frame, n_frames, frame_step = _frame_range(int(f.value), first_frame, n_frames, frame_step)
+        buf = DeviceBuffer(4 * max(1, self.n_streams * n_frames * int(x_pixels)), self.device, self.L)
+        try:
+            self.map_spectrum_device(buf.ptr, y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq, first_frame, n_frames, frame_step)
+            self.synchronize()
+            return _download_i32(self.L, self.device, buf.ptr, (self.n_streams, n_frames, int(x_pixels)))
+        finally:
+            buf.free()
 
     def process(self, iq, what=3):
         """iq: complex [streams, n] -> (filtered [S, n] or None, spectrum [S, frames, bins] or None)"""

@@ -1,6 +1,7 @@
 // pebblegpu_abi.hip -- extern "C" surface declared in include/pebblegpu.h (receiver bank + memory plumbing).
 #include <cmath>
 #include <new>
+#include <vector>
 #include "receiver.h"
 
 struct pebblegpu_receiver {
@@ -226,6 +227,34 @@ const void *pebblegpu_receiver_zoom_spectrum(const pebblegpu_receiver *h, uint64
     if (frames_per_channel) *frames_per_channel = h->rx.last_zoom_frames;
     if (bins) *bins = h->rx.zoom_bins;
     return h->rx.d_zoom;
+}
+static int screen_map_struct(const pebblegpu_screen_map *m)
+{
+    if (!m) return fail(PEBBLEGPU_E_INVALID, "null pebblegpu_screen_map");
+    if (m->struct_size != sizeof(pebblegpu_screen_map)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_screen_map size mismatch (ABI %d)", PEBBLEGPU_ABI_VERSION);
+    return 0;
+}
+int pebblegpu_receiver_map_spectrum(pebblegpu_receiver *h, const pebblegpu_screen_map *map, uint32_t first_frame, uint32_t n_frames,
+                                    uint32_t frame_step, int32_t *d_out)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    if (int rc = screen_map_struct(map)) return rc;
+    const int32_t edges[2] = {map->start_freq, map->stop_freq};
+    return h->rx.map_spectrum(false, edges, false, map->y_pixels, map->x_pixels, map->max_db, map->min_db, first_frame, n_frames, frame_step, d_out);
+}
+int pebblegpu_receiver_map_zoom_spectrum(pebblegpu_receiver *h, int32_t y_pixels, int32_t x_pixels, double max_db, double min_db, double zoom,
+                                         const int32_t *mode_offset, uint32_t first_frame, uint32_t n_frames, uint32_t frame_step,
+                                         int32_t *d_out)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    const uint32_t C = h->rx.C;
+    std::vector<int32_t> edges(2 * (size_t)C);
+    bool same = true;
+    for (uint32_t c = 0; c < C; c++) {
+        pg::zoom_span_edges(h->rx.demod_rate_int, zoom, mode_offset ? mode_offset[c] : 0, &edges[2 * c], &edges[2 * c + 1]);
+        same = same && edges[2 * c] == edges[0] && edges[2 * c + 1] == edges[1];
+    }
+    return h->rx.map_spectrum(true, edges.data(), !same, y_pixels, x_pixels, max_db, min_db, first_frame, n_frames, frame_step, d_out);
 }
 int pebblegpu_receiver_enable_signal_strength(pebblegpu_receiver *h, int on)
 {

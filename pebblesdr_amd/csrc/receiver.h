@@ -49,6 +49,16 @@ int run_gate_eval(hipStream_t s, const float4 *d_smeter, long long smeter_pitch,
 int run_gate_zero(hipStream_t s, float2 *audio, long long pitch, long long spf, const unsigned char *d_gate, int stride, uint32_t channels, int k);
 int run_signal_strength(hipStream_t s, const float *d_spec, long long stream_pitch, int bins, long long n_frames, const SmBins *d_bins,
                         float4 *d_out, long long out_pitch, uint32_t channels);
+// FFT::mapFFTToScreen (display.hip, kernels_display.h): rows = n_streams x n_frames of fft_size float dB, row (s, j) at
+// in + s * stream_pitch + j * frame_pitch, to out[(s * n_frames + j) * x_pixels + i].  edges: (startFreq, stopFreq), one pair for
+// every stream or (per_stream) one per stream
+int run_screen_map(hipStream_t s, const float *in, long long stream_pitch, long long frame_pitch, int n_streams, int n_frames, int32_t fft_size,
+                   double sample_rate, const int32_t *edges, bool per_stream, int32_t y_pixels, int32_t x_pixels, double max_db, double min_db,
+                   int32_t *out);
+// SignalSpectrum::mapFFTZoomedToScreen's (startFreq, stopFreq) for one channel
+void zoom_span_edges(uint32_t hires_rate, double zoom, int32_t mode_offset, int32_t *start, int32_t *stop);
+// the refusals every mapping shares (x_pixels, y_pixels, max_db == min_db); 0 when the request can be queued
+int check_screen_map(int32_t y_pixels, int32_t x_pixels, double max_db, double min_db);
 
 // ---- oscillator bank (Mixer state for C channels) ----
 struct OscBank {
@@ -490,6 +500,10 @@ public:
     int stereo_lock(uint32_t ch, int *lock, int *changed);
     int process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw = nullptr);
     int process_iq(const double *iq, uint16_t n, double *audio, uint32_t *n_audio, double *spectrum_db);
+    // FFT::mapFFTToScreen of frames first + j * step (j < n) of the last call's unprocessed spectrum (zoom = false) or zoomed spectra
+    // (zoom = true; edges per channel), queued behind that call's transform and ahead of the next call's: out [stream][n][x_pixels]
+    int map_spectrum(bool zoom, const int32_t *edges, bool per_stream, int32_t y_pixels, int32_t x_pixels, double max_db, double min_db,
+                     uint32_t first, uint32_t n, uint32_t step, int32_t *d_out);
     int sync();
     int close_timing();  // records the end event a side-by-side call left out (no-op otherwise)
     const char *kernel_name(int which) const;  // the kernels behind pebblegpu_receiver_last_ms's groups, as last run
@@ -558,6 +572,8 @@ private:
     hipEvent_t pipe_ev_ = nullptr;
     bool fuse_dec_ = false;           // the one-channel decimator inside the display transform's kernel (PEBBLEGPU_FUSE_DEC=1 at creation)
     hipEvent_t chain_end_ = nullptr;  // set when a two-stream call failed half-way: what was queued on the chain stream, for the main stream to wait on
+    hipStream_t zoom_stream_ = nullptr;  // where the last call's zoomed spectra were written (a map of them queues there)
+    hipEvent_t map_ev_ = nullptr;     // behind a map queued on the chain's stream: what a join waits for instead of the call's end
     std::vector<ChanCtl> ctl_;
     bool am_list_dirty_ = true, sm_dirty_ = true;
     long long pll_cap_ = 0;

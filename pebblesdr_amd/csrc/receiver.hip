@@ -122,6 +122,7 @@ Receiver::~Receiver()
         for (hipEvent_t e : {g.uploaded, g.done_main, g.done_chain}) if (e) (void)hipEventDestroy(e);
     }
     if (d_zoom) (void)hipFree(d_zoom);
+    if (map_ev_) (void)hipEventDestroy(map_ev_);
     agc_.release(); resamp_.release(); cond_.release(); anf_.release();
     if (d_audio_rs) (void)hipFree(d_audio_rs);
     if (h_gate_) (void)hipHostFree(h_gate_);
@@ -541,6 +542,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     if (zoom_bins) {  // SignalSpectrum::zoomed(m_sampleBuf, numStepSamples), receiver.cpp:884 / :942 (the update timer forced open)
         if (int rc = zoom_.run(cs, dec_.out().data(), dec_.out().pitch, nd / nf, d_zoom)) return rc;
         last_zoom_frames = (uint64_t)(nd / nf);
+        zoom_stream_ = cs;
     }
     if (!wfm) {
         if (int rc = ff_.run(cs, dec_.out(), nd, audio.data(), audio.pitch)) return rc;  // receiver.cpp:950
@@ -759,6 +761,37 @@ int Receiver::close_timing()
         PG_HIP(hipEventRecord(tm.ev[tm.open_slot][6], stream_));
         tm.end_ev[tm.open_slot] = tm.ev[tm.open_slot][6];
         tm.open_slot = -1;
+    }
+    return 0;
+}
+
+// The map is queued where the spectrum it reads was written (or where that stream has been joined): the main stream for the
+// unprocessed spectrum, the stream that ran the zoomed transform for the zoomed spectra.  The next call's transform of the same buffer
+// follows on that stream, so it cannot overwrite the rows before they are read; no host wait.
+int Receiver::map_spectrum(bool zoom, const int32_t *edges, bool per_stream, int32_t y_pixels, int32_t x_pixels, double max_db, double min_db,
+                           uint32_t first, uint32_t n, uint32_t step, int32_t *d_out)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (!d_out || !edges) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (int rc = check_screen_map(y_pixels, x_pixels, max_db, min_db)) return rc;
+    if (failed_) return fail(PEBBLEGPU_E_HIP, "an earlier call on this receiver failed half-way: its spectra are not defined");
+    const uint32_t fft = zoom ? zoom_bins : bins;
+    const uint64_t frames = zoom ? last_zoom_frames : last_spec_frames;
+    if (!fft) return fail(PEBBLEGPU_E_INVALID, zoom ? "the receiver computes no zoomed spectrum (hires_bins = 0)" : "the receiver computes no spectrum (spectrum_bins = 0)");
+    if (!frames) return fail(PEBBLEGPU_E_INVALID, "no call with a spectrum has been made yet");
+    if (n == 0 || (uint64_t)first + (uint64_t)(n - 1) * step >= frames)
+        return fail(PEBBLEGPU_E_INVALID, "frames %u + j * %u, j < %u, are not all within the last call's %llu", first, step, n, (unsigned long long)frames);
+    PG_HIP(hipSetDevice(device));
+    if (int rc = close_timing()) return rc;  // (a side-by-side call's time ends where it ended, not behind the map)
+    const int rows = zoom ? (int)C : (int)S;
+    const float *src = (zoom ? d_zoom : d_spec) + (long long)first * fft;
+    hipStream_t ms = zoom && zoom_stream_ ? zoom_stream_ : stream_;
+    if (int rc = run_screen_map(ms, src, (long long)frames * fft, (long long)step * fft, rows, (int)n, (int32_t)fft,
+                                zoom ? (double)demod_rate_int : fs, edges, per_stream, y_pixels, x_pixels, max_db, min_db, d_out)) return rc;
+    if (ms == chain_stream_ && chain_end_) {  // a join waits for the map too: the next call may write the zoomed spectra on the main stream
+        if (!map_ev_) PG_HIP(hipEventCreateWithFlags(&map_ev_, hipEventDisableTiming));
+        PG_HIP(hipEventRecord(map_ev_, chain_stream_));
+        chain_end_ = map_ev_;
     }
     return 0;
 }

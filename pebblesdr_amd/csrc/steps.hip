@@ -101,6 +101,9 @@ struct pebblegpu_spectrum : pg::StepBase {
     float *d_out = nullptr;
     std::vector<float> hs;
     int path = 0;  // 0: no call yet; 1: the frame-length kernels; 2: the general kernel (their previous-frame amplitudes are laid out differently)
+    double fs = 0;             // m_sampleRate (mapFFTToScreen's binsPerHz)
+    int32_t *d_px = nullptr;   // mapFFTToScreen's pixels
+    int32_t px_cap = 0;
 };
 
 extern "C" {
@@ -565,11 +568,11 @@ int pebblegpu_demod_rds_signal(pebblegpu_demod *d, double *data, uint32_t cap, u
 // ---------------- Spectrum ----------------
 int pebblegpu_spectrum_create(int device, uint32_t fft_size, double sample_rate, uint32_t samples_per_buffer, pebblegpu_spectrum **out)
 {
-    (void)sample_rate;  // only feeds the bin width in the reference (fft.cpp:81)
     if (!out || fft_size == 0) return fail(PEBBLEGPU_E_INVALID, "bad argument");  // "if (_fftSize == 0) return; //Error"
     if (int rc = step_device(device)) return rc;
     pebblegpu_spectrum *s = new (std::nothrow) pebblegpu_spectrum();
     if (!s) return fail(PEBBLEGPU_E_INVALID, "out of host memory");
+    s->fs = sample_rate;  // the bin width (fft.cpp:81) and mapFFTToScreen's binsPerHz (:424)
     int rc = s->open(device);
     if (!rc) rc = s->sp.init(1, samples_per_buffer, fft_size);
     if (!rc && hipMalloc((void **)&s->d_in, sizeof(float2) * samples_per_buffer) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
@@ -585,6 +588,7 @@ int pebblegpu_spectrum_destroy(pebblegpu_spectrum *s)
     s->sp.release();
     if (s->d_in) (void)hipFree(s->d_in);
     if (s->d_out) (void)hipFree(s->d_out);
+    if (s->d_px) (void)hipFree(s->d_px);
     delete s;
     return 0;
 }
@@ -618,6 +622,29 @@ int pebblegpu_spectrum_process(pebblegpu_spectrum *s, const double *in, int n, d
     PG_HIP(hipMemcpy(s->hs.data(), s->d_out, sizeof(float) * s->sp.bins, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < s->sp.bins; i++) out_db[i] = (double)s->hs[i];
     if (overload) *overload = ov;
+    return 0;
+}
+
+int pebblegpu_spectrum_map_to_screen(pebblegpu_spectrum *s, const pebblegpu_screen_map *map, int32_t *out)
+{
+    if (!s || !map || !out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (map->struct_size != sizeof(pebblegpu_screen_map)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_screen_map size mismatch");
+    if (int rc = pg::check_screen_map(map->y_pixels, map->x_pixels, map->max_db, map->min_db)) return rc;
+    if (!s->path) return fail(PEBBLEGPU_E_INVALID, "no fftSpectrum call yet: there is no spectrum to map");
+    PG_HIP(hipSetDevice(s->device));
+    if (map->x_pixels > s->px_cap) {
+        PG_HIP(hipStreamSynchronize(s->stream));
+        if (s->d_px) PG_HIP(hipFree(s->d_px));
+        s->d_px = nullptr;
+        s->px_cap = 0;
+        PG_HIP(hipMalloc((void **)&s->d_px, sizeof(int32_t) * (size_t)map->x_pixels));
+        s->px_cap = map->x_pixels;
+    }
+    const int32_t edges[2] = {map->start_freq, map->stop_freq};
+    if (int rc = pg::run_screen_map(s->stream, s->d_out, (long long)s->sp.bins, (long long)s->sp.bins, 1, 1, (int32_t)s->sp.bins, s->fs, edges, false,
+                                    map->y_pixels, map->x_pixels, map->max_db, map->min_db, s->d_px)) return rc;
+    PG_HIP(hipMemcpyAsync(out, s->d_px, sizeof(int32_t) * (size_t)map->x_pixels, hipMemcpyDeviceToHost, s->stream));
+    PG_HIP(hipStreamSynchronize(s->stream));
     return 0;
 }
 

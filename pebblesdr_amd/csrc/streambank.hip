@@ -161,6 +161,24 @@ int pebblegpu_streambank_last_ms(const pebblegpu_streambank *sb, int which, floa
     PG_HIP(hipEventElapsedTime(ms, sb->ev[a], sb->ev[b]));
     return 0;
 }
+int pebblegpu_streambank_map_spectrum(pebblegpu_streambank *sb, const pebblegpu_screen_map *map, uint32_t first_frame, uint32_t n_frames,
+                                      uint32_t frame_step, int32_t *d_out)
+{
+    if (!sb || !map || !d_out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (map->struct_size != sizeof(pebblegpu_screen_map)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_screen_map size mismatch");
+    if (int rc = pg::check_screen_map(map->y_pixels, map->x_pixels, map->max_db, map->min_db)) return rc;
+    if (!sb->last_frames) return fail(PEBBLEGPU_E_INVALID, "the last call computed no spectrum (or no call has been made yet)");
+    if (n_frames == 0 || (uint64_t)first_frame + (uint64_t)(n_frames - 1) * frame_step >= sb->last_frames)
+        return fail(PEBBLEGPU_E_INVALID, "frames %u + j * %u, j < %u, are not all within the last call's %llu", first_frame, frame_step, n_frames,
+                    (unsigned long long)sb->last_frames);
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    const long long bins = sb->sp.bins;
+    const int32_t edges[2] = {map->start_freq, map->stop_freq};
+    // on the bank's stream, behind the call's transform (and its join) and ahead of the next call's
+    return pg::run_screen_map(sb->stream, sb->d_spec + (long long)first_frame * bins, (long long)sb->last_frames * bins, (long long)frame_step * bins,
+                              (int)sb->cfg.n_streams, (int)n_frames, (int32_t)bins, sb->cfg.sample_rate, edges, false, map->y_pixels, map->x_pixels,
+                              map->max_db, map->min_db, d_out);
+}
 int pebblegpu_streambank_synchronize(pebblegpu_streambank *sb)
 {
     if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import check, load_library
+from .binding import check, load_library, screen_map
 
 _dp = C.POINTER(C.c_double)
 
@@ -200,3 +200,10 @@ class Spectrum(_Step):
         ov = C.c_int()
         check(self.L, self.L.pebblegpu_spectrum_process(self.h, x.ctypes.data_as(_dp), len(x), out.ctypes.data_as(_dp), C.byref(ov)))
         return out, bool(ov.value)
+
+    def mapFFTToScreen(self, yPixels, xPixels, maxdB, mindB, startFreq, stopFreq):
+        """FFT::mapFFTToScreen (pebblelib/fft.cpp:411-534) of the last fftSpectrum's spectrum, on the device -> int32 [xPixels]"""
+        m = screen_map(yPixels, xPixels, maxdB, mindB, startFreq, stopFreq)
+        out = np.empty(max(0, int(xPixels)), dtype=np.int32)
+        check(self.L, self.L.pebblegpu_spectrum_map_to_screen(self.h, C.byref(m), out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
