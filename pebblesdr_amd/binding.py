@@ -556,6 +556,7 @@ class StreamBank:
         cfg.fastfir_taps = fastfir_taps
         cfg.max_frames = max_frames
         self.h = C.c_void_p()
+        self.split32 = os.environ.get("PEBBLEGPU_BIG_SPLIT32") == "1"  # (the library reads its switches when the bank is created)
         check(self.L, self.L.pebblegpu_streambank_create(C.byref(cfg), C.byref(self.h)))
         self.device, self.n_streams, self.frame = device, n_streams, frame
 
@@ -586,7 +587,7 @@ class StreamBank:
 
     def spectrum_kernels(self):
         """label of the kernels behind last_ms(2)"""
-        return ("k_big_cols + k_big_rows" if os.environ.get("PEBBLEGPU_BIG_SPLIT32") == "1" else "k_big256_cols + k_big256_rows") if self.frame == 65536 else "k_spectrum"
+        return ("k_big_cols + k_big_rows" if self.split32 else "k_big256_cols + k_big256_rows") if self.frame == 65536 else "k_spectrum"
 
     def filtered(self):
         n, pitch = C.c_uint64(), C.c_uint64()

@@ -416,8 +416,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
     const float2 *y0_hist = y0_pending ? (const float2 *)(d_y0stage2[y0_cur] + fused_hy) : (const float2 *)y0b.data();
     const long long y0_hist_pitch = y0_pending ? (long long)fused_hy : y0b.pitch;
     // the oscillators' advance rides on the launch when the caller handed it over (banks whose oscillators live on the device)
-    static const int adv_mode = [] { const char *e = getenv("PEBBLEGPU_BANK_OSC_ADV"); return e ? atoi(e) : 1; }();  // 0: leave the oscillators to the tail launch (A/B)
-    const bool adv = adv_mode != 0 && oa != nullptr && oa->osc != nullptr && oa->osc_count == C;
+    const bool adv = tun.bank_osc_adv != 0 && oa != nullptr && oa->osc != nullptr && oa->osc_count == C;
     if (adv && !d_dyn[0]) {
         for (int i = 0; i < 2; i++) PG_HIP(hipMalloc((void **)&d_dyn[i], sizeof(OscDyn) * C));
     }
@@ -425,7 +424,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
     dyn_epoch_seen = osc.dyn_epoch;
     // One wave per SIMD pays the fewest warm-up blocks; two overlap what a lone wave leaves idle (measured on hb11 x 4, 15/19/31: 1200
     // clocks per block alone, 2075 for each of two) -- worth it once a chunk is long against its warm-up: from 128 outputs per chunk on
-    int waves = bank_waves;
+    int waves = tun.bank_waves;
     // (a receiver that runs two-stage calls keeps one wave per SIMD at every batch size: the previous call's band-pass needs the other
     // half of the register file beside it -- 0.2385 ms per configs[2] call of 32 super-frames against 0.2546, 0.875 against 0.905 at 128)
     if (waves == 0) waves = (!fin2.base && cdiv(len_out, 2 * std::max(1LL, 1024LL / g32)) >= 128) ? 2 : 1;
@@ -436,8 +435,8 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
     if (pairs_target < 1) pairs_target = 1;
     // a power of two (it divides the call's 2048 k outputs: the last chunk is a whole one), the nearest to the target above
     long long L = 16;
-    if (fused_L > 0) {
-        while (L * 2 <= fused_L) L *= 2;
+    if (tun.fused_l > 0) {
+        while (L * 2 <= tun.fused_l) L *= 2;
     } else {
         const long long want = cdiv(len_out, 2 * pairs_target);
         while (L < want && L < 2048) L *= 2;
@@ -446,18 +445,16 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
     while (2 * L <= warm) L *= 2;  // (only the first two chunks may reach in front of the call's start)
     const int S0 = first.stride, Sfs = cic ? S0 * wide_stride : S0;  // input samples per first-stage (hb11) output
     const long long pairs = cdiv(cdiv(len_out, L), 2);
-    static const int hist_split = [] { const char *e = getenv("PEBBLEGPU_BANK_HSPLIT"); return e ? atoi(e) : 4; }();
+    const int hist_split = tun.bank_hsplit;
     const unsigned n_wg = (unsigned)(8 * cdiv(pairs, 8) * cdiv(g32, 4) + cdiv(g32, 4) * hist_split);  // main workgroups, then the history waves'
-    static unsigned long long *d_clk = nullptr;  // diagnosis only: PEBBLEGPU_BANK_CLK=1 prints the waves' clock counts of every such launch
-    static size_t clk_cap = 0;
-    const char *eclk = getenv("PEBBLEGPU_BANK_CLK");
-    const bool want_clk = eclk && eclk[0] == '1';
-    if (want_clk && clk_cap < (size_t)n_wg * 16) {
+    if (tun.bank_clk && clk_cap < (size_t)n_wg * 16) {
         if (d_clk) (void)hipFree(d_clk);
+        d_clk = nullptr;
+        clk_cap = 0;
         PG_HIP(hipMalloc((void **)&d_clk, sizeof(unsigned long long) * n_wg * 16));
         clk_cap = (size_t)n_wg * 16;
     }
-    if (want_clk) PG_HIP(hipMemsetAsync(d_clk, 0, sizeof(unsigned long long) * n_wg * 16, s));
+    if (tun.bank_clk) PG_HIP(hipMemsetAsync(d_clk, 0, sizeof(unsigned long long) * n_wg * 16, s));
     auto common = [&](auto &bp) {
         bp.n_out = len_out;
         bp.out_pitch = fin.pitch;
@@ -476,7 +473,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
         bp.cic_s0 = cic ? S0 : 0;
         bp.state_in = had_state ? d_bank_state[bank_state_parity] : nullptr;
         bp.state_out = d_bank_state[bank_state_parity ^ 1];
-        bp.clk = want_clk ? d_clk : nullptr;
+        bp.clk = tun.bank_clk ? d_clk : nullptr;
         bp.dyn_in = adv && dyn_valid ? d_dyn[dyn_parity] : nullptr;
         bp.dyn_out = adv ? d_dyn[dyn_parity ^ 1] : nullptr;
         bp.osc_rw = adv ? oa->osc : nullptr;
@@ -499,17 +496,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
             bp.e[p] = (float)kE[p];
             bp.g[p] = p == 0 ? 0.5f * bank_taps.h[5] : bank_taps.h[5 + kE[p]];
         }
-        void *kern = bv->kern;
-        const char *edbg = getenv("PEBBLEGPU_BANK_DBG");  // timing experiments on the configs[2] instance (wrong results)
-        const int dbg = edbg ? atoi(edbg) : 0;
-        if (dbg && bv->t1 == 15 && bv->t2 == 19 && bv->t3 == 31)
-            kern = dbg == 1 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 1> : dbg == 2 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 2> : dbg == 3 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 3>
-                 : dbg == 4 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 4> : dbg == 8 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 8> : dbg == 16 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 16>
-                 : dbg == 128 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 128> : dbg == 256 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 256> : dbg == 512 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 512> : dbg == 32 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 32> : dbg == 64 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 64> : dbg == 96 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 96> : dbg == 31 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 31> : dbg == 100 ? (void *)k_mix_dec_mfma<4, 15, 19, 31, 0, 1> : kern;
-        if (dbg && bv->t1 == 19 && bv->t2 == 27 && bv->t3 == 59)
-            kern = dbg == 1 ? (void *)k_mix_dec_mfma<4, 19, 27, 59, 1> : dbg == 2 ? (void *)k_mix_dec_mfma<4, 19, 27, 59, 2> : dbg == 4 ? (void *)k_mix_dec_mfma<4, 19, 27, 59, 4>
-                 : dbg == 8 ? (void *)k_mix_dec_mfma<4, 19, 27, 59, 8> : dbg == 16 ? (void *)k_mix_dec_mfma<4, 19, 27, 59, 16> : dbg == 31 ? (void *)k_mix_dec_mfma<4, 19, 27, 59, 31> : kern;
-        if (int rc = launch_bank<4>(kern, n_wg, s, d_in, fin.data(), (const ChanOsc *)osc.d_osc, osc.inline_dyn, xh, xh_out, y0_hist, d_y0stage2[y0_cur ^ 1], mixed, bp, done_event)) return rc;
+        if (int rc = launch_bank<4>(bv->kern, n_wg, s, d_in, fin.data(), (const ChanOsc *)osc.d_osc, osc.inline_dyn, xh, xh_out, y0_hist, d_y0stage2[y0_cur ^ 1], mixed, bp, done_event)) return rc;
     } else {
         // CIC3 at stride S0 in the reference's merged form (decimator.cpp:719-737: output k = .125 (od_k + ev_{k-1} + 3 (od_{k-1} + ev_k)) of the
         // sample pairs (ev, od)_P = x[S0 P], x[S0 P + 1]) under the hb11 at stride 16: relative to sample S j, pair q = -11 .. 0 carries
@@ -531,42 +518,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
         if (int rc = launch_bank<12>(bv->kern, n_wg, s, d_in, fin.data(), (const ChanOsc *)osc.d_osc, osc.inline_dyn, xh, xh_out, y0_hist, d_y0stage2[y0_cur ^ 1], mixed, bp, done_event)) return rc;
     }
     done_recorded = done_event != nullptr;
-    if (want_clk) {
-        std::vector<unsigned long long> h((size_t)n_wg * 16);
-        PG_HIP(hipStreamSynchronize(s));
-        PG_HIP(hipMemcpy(h.data(), d_clk, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
-        std::vector<double> per, ghz;
-        std::vector<std::pair<double, size_t>> slow;
-        double mx = 0;
-        for (size_t w = 0; w < (size_t)n_wg * 4; w++)
-            if (h[4 * w + 2]) {
-                per.push_back((double)h[4 * w] / (double)h[4 * w + 2]);
-                ghz.push_back((double)h[4 * w] / ((double)h[4 * w + 1] * 10.0));
-                slow.push_back({per.back(), w});
-                if ((double)h[4 * w + 1] > mx) mx = (double)h[4 * w + 1];
-            }
-        std::sort(per.begin(), per.end());
-        std::sort(ghz.begin(), ghz.end());
-        std::sort(slow.begin(), slow.end());
-        if (!per.empty()) {
-            fprintf(stderr, "k_mix_dec_mfma: %zu waves, L %d, clocks per block min %.0f median %.0f max %.0f; shader clock median %.2f GHz; longest wave %.1f us\n", per.size(),
-                    (int)L, per.front(), per[per.size() / 2], per.back(), ghz[ghz.size() / 2], mx / 100.0);
-            fprintf(stderr, "   slowest (clocks per block : workgroup.wave pair):");
-            for (size_t i = slow.size() > 12 ? slow.size() - 12 : 0; i < slow.size(); i++)
-                fprintf(stderr, " %.0f:%zu.%zu p%llu", slow[i].first, slow[i].second / 4, slow[i].second % 4, h[4 * slow[i].second + 3]);
-            size_t over = 0;
-            for (double v : per) over += v > 1.25 * per[per.size() / 2];
-            fprintf(stderr, "\n   waves more than 25 %% over the median: %zu\n", over);
-            fprintf(stderr, "   workgroups with a wave more than 8 %% over the median:");
-            size_t last = (size_t)-1;
-            for (size_t w = 0; w < (size_t)n_wg * 4; w++)
-                if (h[4 * w + 2] && (double)h[4 * w] / (double)h[4 * w + 2] > 1.08 * per[per.size() / 2] && w / 4 != last) {
-                    fprintf(stderr, " %zu", w / 4);
-                    last = w / 4;
-                }
-            fprintf(stderr, "\n");
-        }
-    }
+    if (tun.bank_clk) { if (int rc = report_clk(s, n_wg, L)) return rc; }
     hist_parity ^= 1;
     bank_state_parity ^= 1;
     bank_state_valid = true;
@@ -583,6 +535,46 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
     return 0;
 }
 
+// Tuning::bank_clk: the clock counts k_mix_dec_mfma's waves left in d_clk (four per wave: shader clocks, 100 MHz ticks, blocks, pair)
+int DecimCore::report_clk(hipStream_t s, unsigned n_wg, long long L)
+{
+    std::vector<unsigned long long> h((size_t)n_wg * 16);
+    PG_HIP(hipStreamSynchronize(s));
+    PG_HIP(hipMemcpy(h.data(), d_clk, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    std::vector<double> per, ghz;
+    std::vector<std::pair<double, size_t>> slow;
+    double mx = 0;
+    for (size_t w = 0; w < (size_t)n_wg * 4; w++)
+        if (h[4 * w + 2]) {
+            per.push_back((double)h[4 * w] / (double)h[4 * w + 2]);
+            ghz.push_back((double)h[4 * w] / ((double)h[4 * w + 1] * 10.0));
+            slow.push_back({per.back(), w});
+            if ((double)h[4 * w + 1] > mx) mx = (double)h[4 * w + 1];
+        }
+    std::sort(per.begin(), per.end());
+    std::sort(ghz.begin(), ghz.end());
+    std::sort(slow.begin(), slow.end());
+    if (!per.empty()) {
+        fprintf(stderr, "k_mix_dec_mfma: %zu waves, L %d, clocks per block min %.0f median %.0f max %.0f; shader clock median %.2f GHz; longest wave %.1f us\n", per.size(),
+                (int)L, per.front(), per[per.size() / 2], per.back(), ghz[ghz.size() / 2], mx / 100.0);
+        fprintf(stderr, "   slowest (clocks per block : workgroup.wave pair):");
+        for (size_t i = slow.size() > 12 ? slow.size() - 12 : 0; i < slow.size(); i++)
+            fprintf(stderr, " %.0f:%zu.%zu p%llu", slow[i].first, slow[i].second / 4, slow[i].second % 4, h[4 * slow[i].second + 3]);
+        size_t over = 0;
+        for (double v : per) over += v > 1.25 * per[per.size() / 2];
+        fprintf(stderr, "\n   waves more than 25 %% over the median: %zu\n", over);
+        fprintf(stderr, "   workgroups with a wave more than 8 %% over the median:");
+        size_t last = (size_t)-1;
+        for (size_t w = 0; w < (size_t)n_wg * 4; w++)
+            if (h[4 * w + 2] && (double)h[4 * w] / (double)h[4 * w + 2] > 1.08 * per[per.size() / 2] && w / 4 != last) {
+                fprintf(stderr, " %zu", w / 4);
+                last = w / 4;
+            }
+        fprintf(stderr, "\n");
+    }
+    return 0;
+}
+
 // The first-stage history a k_mix_dec_mfma launch staged (d_y0stage) into the stage-0 head-room, where the other routes and a launch
 // without the halfbands' running sums look for it.  Not needed between two such launches: queued only when a call wants it.
 int DecimCore::flush_y0(hipStream_t s)
@@ -595,9 +587,10 @@ int DecimCore::flush_y0(hipStream_t s)
     return run_save_tails(s, jobs, C, nullptr);
 }
 
-int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in, int last_hist, float last_gain)
+int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in, int last_hist, float last_gain, const Tuning &t)
 {
     release();
+    tun = t;
     chain = c;
     C = channels;
     const size_t ns = chain.stages.size();
@@ -671,15 +664,13 @@ int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in,
     // hb11 x S, hb15, hb19, hb31 (PEBBLEGPU_BANK_DEC=0)
     {
         using FG = FusedDecGeom<15, 19, 31>;
-        const char *env = getenv("PEBBLEGPU_NO_FUSED_DEC");
-        const bool off = env && env[0] == '1';
+        const bool off = tun.no_fused_dec;
         const bool three2 = casc.nst == 3 && casc.stride[0] == 2 && casc.stride[1] == 2 && casc.stride[2] == 2;
         const bool hb_front = bank_front && C >= 16 && !wide && first.stride <= 16;
         const bool cic_front = fused_front && C >= 16 && wide_stride == 16;
         fused_all = hb_front && three2 && casc.ntaps[0] == 15 && casc.ntaps[1] == 19 && casc.ntaps[2] == 31 && !off;
-        const char *eb = getenv("PEBBLEGPU_BANK_DEC");
         bank_mfma = false;
-        if (three2 && (hb_front || cic_front) && !off && !(eb && eb[0] == '0'))
+        if (three2 && (hb_front || cic_front) && !off && tun.bank_dec)
             bank_mfma = bank_variant(cic_front ? 12 : 4, casc.ntaps[0], casc.ntaps[1], casc.ntaps[2], &fused_hy, &bank_nstate, &bank_minw);
         if (fused_all && !bank_mfma) fused_hy = FG::HY;
         if (fused_all || bank_mfma) {
@@ -703,9 +694,6 @@ int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in,
                 PG_HIP(hipMemset(d_y0stage2[i], 0, sizeof(float2) * ((size_t)fused_hy * C + 64)));
             }
             d_y0stage = d_y0stage2[0];
-            const char *ew = getenv("PEBBLEGPU_BANK_WAVES");
-            bank_waves = ew ? atoi(ew) : 0;  // 0: chosen per call
-            if (bank_waves < 0 || bank_waves > 4) bank_waves = 0;
             if (bank_mfma) {
                 for (int i = 0; i < 2; i++) {
                     PG_HIP(hipMalloc((void **)&d_bank_state[i], sizeof(float2) * (size_t)bank_nstate * C));
@@ -779,6 +767,9 @@ void DecimCore::release()
     if (d_ph_scratch) (void)hipFree(d_ph_scratch);
     d_ph_scratch = nullptr;
     ph_cap = 0;
+    if (d_clk) (void)hipFree(d_clk);
+    d_clk = nullptr;
+    clk_cap = 0;
 }
 int DecimCore::set_fuse_window(const float *d_window, const std::vector<float> &w)
 {
@@ -818,7 +809,6 @@ int DecimCore::fill_dec_fuse(hipStream_t s, DecFuse *df, const OscBank &osc, lon
     df->gain0 = first.gain;
     df->gain_last = casc.gain;
     df->mix_on = (int)o.mix_on;
-    { static const int dbg = [] { const char *e = getenv("PEBBLEGPU_FUSE_DBG"); return e ? atoi(e) : 0; }(); df->dbg = dbg; }
     if (!c0_valid || c0_inc != o.inc || c0_mix != (int)o.mix_on) {
         // (rare: the first such call and the first after a retune.)  The copy is queued on the call's main stream, which follows
         // everything earlier calls queued on either stream, and waited for: the host table is free to change afterwards
@@ -906,12 +896,6 @@ int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool s
         if (n / ((long long)first.stride * (fused_front ? wide_stride : 1)) > y0b.cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
         len_out = n / (long long)chain.total;
         const long long groups = cdiv(C, 64);
-        if (!fused_L) {
-            const char *e = getenv("PEBBLEGPU_FUSED_L");
-            fused_L = e ? atoi(e) : 0;
-            if (fused_L < 16) fused_L = -1;  // choose per call
-            fused_L &= ~15;
-        }
         if (bank_mfma && (unsigned long long)n * 8 < 0xFFF00000ull && (unsigned long long)C * (unsigned long long)fin.pitch * 8 < 0xFFF00000ull &&
             len_out >= 64 && (reinterpret_cast<uintptr_t>(d_in) & 7) == 0) {  // (its sample fetches and result stores carry 32-bit byte offsets)
             dyn_valid = had_dyn;
@@ -921,7 +905,7 @@ int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool s
         }
       if (int rc = flush_y0(s)) return rc;
       if (fused_all) {
-        long long L = fused_L > 0 ? fused_L : ((len_out * groups / 704 + 15) & ~15LL);  // ~700 four-wave workgroups (measured best on 256 CUs: 96 for configs[2]); every chunk pays a 21-block warm-up
+        long long L = tun.fused_l > 0 ? tun.fused_l : ((len_out * groups / 704 + 15) & ~15LL);  // ~700 four-wave workgroups (measured best on 256 CUs: 96 for configs[2]); every chunk pays a 21-block warm-up
         if (L < 32) L = 32;
         fused_p->n_out = len_out;
         fused_p->out_pitch = fin.pitch;
@@ -967,7 +951,7 @@ int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool s
             const RawSrc rs = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
             auto lean = !raw ? k_mix_hb11_lean<-1> : rs.fmt == 0 ? k_mix_hb11_lean<0> : rs.fmt == 1 ? k_mix_hb11_lean<1> : rs.fmt == 2 ? k_mix_hb11_lean<2>
                              : rs.fmt == 3 ? k_mix_hb11_lean<3> : k_mix_hb11_lean<4>;
-            static const bool edge_launch = [] { const char *e = getenv("PEBBLEGPU_LEAN_EDGE_LAUNCH"); return e && e[0] == '1'; }();  // A/B: the edges as a launch of their own
+            const bool edge_launch = tun.lean_edge_launch;  // A/B: the edges as a launch of their own
             launch(lean, dim3(cdiv(len0, 4LL * R * 64) + (edge_launch ? 0 : 1)), dim3(256), s, d_in, buf0.data(), len0, (const ChanOsc *)osc.d_osc,
                    osc.a_inf, bank_taps, first.gain, osc.inline_dyn, R, edge_launch ? -j_first : j_first, rs, (const float2 *)d_hist_mixed[hist_parity],
                    d_hist_mixed[hist_parity ^ 1]);
@@ -1062,8 +1046,7 @@ int DecimCore::enable_double_out()
     if (casc.nst == 0 || !fin.base) return fail(PEBBLEGPU_E_UNSUPPORTED, "a single-stage chain has no separate output buffer to double");
     if (fin2.base) return 0;
     if (int rc = fin2.alloc(fin.chans, fin.hist, fin.cap)) return rc;
-    const char *e = getenv("PEBBLEGPU_BANK_PIPE_BUFS");  // 2: the decimator waits for the consumer of the call before the last
-    if (e && e[0] == '2') return 0;
+    if (tun.bank_pipe_bufs2) return 0;  // the decimator waits for the consumer of the call before the last
     return fin3.alloc(fin.chans, fin.hist, fin.cap);
 }
 
@@ -1113,8 +1096,9 @@ int run_save_tails(hipStream_t s, const std::vector<TailJob> &jobs, uint32_t cha
 // ------------------------------------------------------------------------------------------------
 // FastFirCore
 // ------------------------------------------------------------------------------------------------
-int FastFirCore::init(uint32_t channels, uint32_t fft_size, uint32_t fir_size)
+int FastFirCore::init(uint32_t channels, uint32_t fft_size, uint32_t fir_size, const Tuning &t)
 {
+    tun = t;
     C = channels;
     fft_n = fft_size;
     taps = fir_size;
@@ -1145,9 +1129,8 @@ int FastFirCore::design(hipStream_t s, uint32_t ch, double lo, double hi, double
 }
 // k_fastfir_t128's grid: one-dimensional with the XCD-aware order (kernels_fastfir.h) unless PEBBLEGPU_FF_XCD=0 asks for (block, channel)
 struct FfGrid { dim3 grid; int nb, nchan; };
-static FfGrid ff_grid(long long nb, uint32_t channels)
+static FfGrid ff_grid(long long nb, uint32_t channels, bool xcd)
 {
-    static const bool xcd = [] { const char *e = getenv("PEBBLEGPU_FF_XCD"); return !(e && e[0] == '0'); }();
     const long long total = nb * (long long)channels;
     if (!xcd || total >= (1LL << 31) - 8) return FfGrid{dim3((unsigned)nb, channels), (int)nb, 0};
     return FfGrid{dim3((unsigned)(8 * ((total + 7) / 8))), (int)nb, (int)channels};
@@ -1161,8 +1144,8 @@ int FastFirCore::run(hipStream_t s, const HistBuf &in, long long n, float2 *out,
     const float2 *no_tail = nullptr;
     // (twiddles from the workgroup's LDS copy here: beside a bank's decimator -- two-stage calls -- the variant that reads them through the
     // vector cache measured 0.0833 ms per configs[2] call against 0.0820; alone, in the stream bank, it is the faster one: run_ext)
-    static const bool tw_lds = [] { const char *e = getenv("PEBBLEGPU_FF_TWLDS"); return !(e && e[0] == '0'); }();
-    const FfGrid fg = ff_grid(n / L, C);
+    const bool tw_lds = tun.ff_twlds != 0;
+    const FfGrid fg = ff_grid(n / L, C, tun.ff_xcd);
     if (fft_n == 2048 && !tw_lds) launch(k_fastfir_t128<false>, fg.grid, dim3(128), s, (const float2 *)in.data(), in.pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, no_tail, (float2 *)nullptr, fg.nb, fg.nchan);
     else if (fft_n == 2048) launch(k_fastfir_t128<true>, fg.grid, dim3(128), s, (const float2 *)in.data(), in.pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, no_tail, (float2 *)nullptr, fg.nb, fg.nchan);
     else if (fft_n == 4096) launch(k_fastfir<4096>, grid, block, s, (const float2 *)in.data(), in.pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw, overlap, no_tail);
@@ -1180,11 +1163,11 @@ int FastFirCore::run_ext(hipStream_t s, const float2 *in, long long in_pitch, fl
     const dim3 grid((unsigned)(n / L), C), block(256);
     const float2 *tail = d_tail;
     if (fft_n == 2048) {
-        static const size_t pad = [] { const char *e = getenv("PEBBLEGPU_FF_PADLDS"); return e ? (size_t)atol(e) : (size_t)0; }();  // A/B: extra LDS per workgroup (lowers its occupancy)
+        const size_t pad = tun.ff_padlds;  // A/B: extra LDS per workgroup (lowers its occupancy)
         // twiddles through the vector cache: without the 4.5 KB copy per workgroup eight workgroups fit a CU's LDS instead of six -- configs[4]'s
         // band-pass 0.222 / 0.227 -> 0.215 / 0.211 ms in alternating runs (PEBBLEGPU_FF_TWLDS=1 brings the copy back)
-        static const bool twg = [] { const char *e = getenv("PEBBLEGPU_FF_TWLDS"); return !(e && e[0] == '1'); }();
-        const FfGrid fg = ff_grid(n / L, C);
+        const bool twg = tun.ff_twlds != 1;
+        const FfGrid fg = ff_grid(n / L, C, tun.ff_xcd);
         if (twg) launch_lds(k_fastfir_t128<false>, fg.grid, dim3(128), pad, s, in, in_pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail, d_tail_next, fg.nb, fg.nchan);
         else launch_lds(k_fastfir_t128<true>, fg.grid, dim3(128), pad, s, in, in_pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail, d_tail_next, fg.nb, fg.nchan);
         if (d_tail_next) {  // the kernel's last block has written the next call's overlap into the caller's other buffer
@@ -1355,8 +1338,9 @@ int PllCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *ou
 // ------------------------------------------------------------------------------------------------
 // WfmCore
 // ------------------------------------------------------------------------------------------------
-int WfmCore::init(uint32_t channels, double demod_rate, long long max_n)
+int WfmCore::init(uint32_t channels, double demod_rate, long long max_n, const Tuning &t)
 {
+    tun = t;
     C = channels;
     rate = demod_rate;
     max_n_ = max_n;
@@ -1452,9 +1436,7 @@ int WfmCore::set_stereo(uint32_t ch, bool on)
         for (auto &q : z) { q.nco_freq = pd.nco_freq0; q.quiet = 1LL << 40; }
         PG_HIP(hipMemcpy(d_pilot, z.data(), sizeof(WfmPilotState) * C, hipMemcpyHostToDevice));
         // the RDS members, initialised with the rest of setSampleRate (demod_wfm.cpp:187-191)
-        const char *e = getenv("PEBBLEGPU_RDS");
-        rds_enabled = !(e && e[0] == '0');
-        if (rds_enabled) { if (int rc = rds.init(C, rate, max_n_)) return rc; }
+        if (tun.rds) { if (int rc = rds.init(C, rate, max_n_)) return rc; }
     }
     if (stereo[ch] != (unsigned char)on) stereo_dirty = true;
     stereo[ch] = on;
@@ -1927,8 +1909,9 @@ int ResampCore::run(hipStream_t s, const float2 *in, long long in_pitch, long lo
 // ------------------------------------------------------------------------------------------------
 // SpectrumCore
 // ------------------------------------------------------------------------------------------------
-int SpectrumCore::init(uint32_t streams, uint32_t frame, uint32_t fft_size)
+int SpectrumCore::init(uint32_t streams, uint32_t frame, uint32_t fft_size, const Tuning &t)
 {
+    tun = t;
     S = streams;
     nf = frame;
     bins = fft_size;
@@ -1960,9 +1943,8 @@ int SpectrumCore::init(uint32_t streams, uint32_t frame, uint32_t fft_size)
     // shared-frame kernels on the bench batch it wins at 2048 bins (0.098 vs 0.105 ms) and loses at 4096 (0.198 vs 0.185) and
     // 8192 (0.44 vs 0.28: its ZP workgroups each re-read the frame and store 4-byte bins ZP*4 bytes apart), so it runs where
     // it wins and where nothing else exists (16384, 32768).  PEBBLEGPU_SPECTRUM_PERQ=1 forces it everywhere (A/B runs).
-    { const char *e = getenv("PEBBLEGPU_SPECTRUM_W64"); use_w64 = e && e[0] == '1'; }  // the one-wave 8192-bin kernel (measured equal: opt-in)
-    const char *env = getenv("PEBBLEGPU_SPECTRUM_PERQ");
-    per_q = !big && !any && (bins == 2048 || bins > 8192 || (env && env[0] == '1'));
+    use_w64 = tun.spectrum_w64;  // the one-wave 8192-bin kernel (measured equal: opt-in)
+    per_q = !big && !any && (bins == 2048 || bins > 8192 || tun.spectrum_perq);
     std::vector<double> w;
     const double cg = design::blackman_harris(nf, w);
     std::vector<float> wf(nf);
@@ -1994,9 +1976,8 @@ int SpectrumCore::init(uint32_t streams, uint32_t frame, uint32_t fft_size)
         if (int rc = make_twiddles_t128(&d_tw128)) return rc;
     }
     if (bins == 8192 && !big && !per_q) {
-        const char *e1 = getenv("PEBBLEGPU_T128_STAGGER"), *e2 = getenv("PEBBLEGPU_T128_PADLDS");
-        stagger = e1 ? atoi(e1) : 3;  // measured on the bench batch: 0.300 ms as two 512-item workgroups per CU, 0.278 with the halves three intervals apart
-        pad_lds = e2 ? atoi(e2) : 0;
+        stagger = tun.t128_stagger;  // measured on the bench batch: 0.300 ms as two 512-item workgroups per CU, 0.278 with the halves three intervals apart
+        pad_lds = tun.t128_padlds;
         std::vector<float2> b2(4 * 16);
         for (int q = 0; q < 4; q++)
             for (int m = 0; m < 16; m++) {
@@ -2071,7 +2052,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
         // (one 64 MiB buffer reused by every batch), instead of a call-sized Y that went out to HBM and back
         // (28 B moved per 12 B of algorithmic traffic).
         const long long per_stream = (long long)F * kBigN;                       // Y points per stream
-        static const long long batch_mb = [] { const char *e = getenv("PEBBLEGPU_BIG_BATCH_MB"); return e ? atoll(e) : 0LL; }();  // 0: the whole call in one pair of launches (measured: 16 / 32 / 64 / 128 MiB batches 0.61 / 0.48 / 0.39 / 0.34 ms against 0.34 whole: the kernels are not bound by that traffic)
+        const long long batch_mb = tun.big_batch_mb;  // 0: the whole call in one pair of launches (measured: 16 / 32 / 64 / 128 MiB batches 0.61 / 0.48 / 0.39 / 0.34 ms against 0.34 whole: the kernels are not bound by that traffic)
         long long bs = batch_mb > 0 ? (batch_mb << 20) / (long long)sizeof(float2) / per_stream : (long long)S;    // streams per batch
         bs = bs < 1 ? 1 : (bs > (long long)S ? (long long)S : bs);
         const size_t need = (size_t)bs * (size_t)per_stream;
@@ -2091,8 +2072,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
         sp.out_pitch = F * (long long)bins;
         for (long long s0 = 0; s0 < (long long)S; s0 += bs) {
             const unsigned nb = (unsigned)((long long)S - s0 < bs ? (long long)S - s0 : bs);
-            static const bool split32 = [] { const char *e = getenv("PEBBLEGPU_BIG_SPLIT32"); return e && e[0] == '1'; }();  // A/B: the 32 x 2048 split
-            if (split32) {
+            if (tun.big_split32) {  // A/B: the 32 x 2048 split
                 launch(k_big_cols, dim3((unsigned)(F * 8), nb), dim3(256), s, d_in + s0 * in_pitch, (long long)in_pitch, d_Y, (const float *)d_window, (long long)F);
                 launch(k_big_rows, dim3((unsigned)(cdiv(F, G) * 8), nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch, (const float2 *)d_tw_nf,
                        (const float *)d_prev[parity] + s0 * kBigN, d_prev[parity ^ 1] + s0 * kBigN, sp);
@@ -2118,8 +2098,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
         sp.scale = scale;
         sp.out_pitch = F * (long long)bins;
         const long long chains = cdiv(F, Gq);
-        static const bool f_regs = [] { const char *e = getenv("PEBBLEGPU_SPECTRUM_FREGS"); return e && e[0] == '1'; }();
-        launch(f_regs ? k_spectrum_q128<true> : k_spectrum_q128<false>, dim3((unsigned)(8 * zp * cdiv(chains, 8)), S), dim3(128), s, d_in, d_out, (const float2 *)d_ftab, (const float2 *)d_tw128,
+        launch(tun.spectrum_fregs ? k_spectrum_q128<true> : k_spectrum_q128<false>, dim3((unsigned)(8 * zp * cdiv(chains, 8)), S), dim3(128), s, d_in, d_out, (const float2 *)d_ftab, (const float2 *)d_tw128,
                (const float *)d_prev[parity], d_prev[parity ^ 1], sp, zl);
         parity ^= 1;
         PG_HIP(hipGetLastError());

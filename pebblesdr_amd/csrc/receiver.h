@@ -18,6 +18,7 @@
 #include "common.h"
 #include "design.h"
 #include "params.h"
+#include "tuning.h"
 
 namespace pg {
 
@@ -124,13 +125,12 @@ struct DecimCore {
     float2 *d_y0stage = nullptr;                // [C][HY] the call's last first-stage outputs, copied into buf0's head-room by the tail refresh (k_mix_dec_fused: = d_y0stage2[0])
     float2 *d_y0stage2[2] = {nullptr, nullptr}; // k_mix_dec_mfma stages them alternately and reads the previous launch's directly (y0_cur: the one written last)
     int y0_cur = 0;
-    int fused_hy = 0, fused_L = 0;
+    int fused_hy = 0;
     // the same chain with its first stage on the matrix pipe, one wave per (32 channels, two chunks): k_mix_dec_mfma (kernels_bank_dec.h),
     // the default route of such a bank; PEBBLEGPU_BANK_DEC=0 keeps the four-wave pipeline above
     bool bank_mfma = false;
     int bank_nstate = 0, bank_minw = 2;          // running sums per channel of the chain's instance; waves per SIMD it admits
     int run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, bool had_state, const OscAdvance *oa);
-    int bank_waves = 0;                          // target waves per SIMD of a launch (PEBBLEGPU_BANK_WAVES, default 1)
     int xh_depth = 16;                           // samples of raw-input tail kept in d_xhist
     float2 *d_bank_state[2] = {nullptr, nullptr};  // [C][38] the halfbands' running sums where the last k_mix_dec_mfma call ended (ping-pong)
     int bank_state_parity = 0;
@@ -167,7 +167,11 @@ struct DecimCore {
     int run_beside_spectrum(hipStream_t s, const float2 *d_in, long long in_pitch, bool shared_input, long long n, const OscBank &osc, const RawSrc *raw);
     int hist_parity = 0;
     // last_hist: head-room of the final buffer (what the consumer looks back at); last_gain: folded into the final stage
-    int init(uint32_t channels, const design::Chain &c, long long max_in, int last_hist, float last_gain);
+    Tuning tun;                              // the owner's switches (init)
+    unsigned long long *d_clk = nullptr;     // Tuning::bank_clk: the waves' clock counts of the last k_mix_dec_mfma launch
+    size_t clk_cap = 0;
+    int report_clk(hipStream_t s, unsigned n_wg, long long L);  // waits for the launch, prints its clock counts on stderr
+    int init(uint32_t channels, const design::Chain &c, long long max_in, int last_hist, float last_gain, const Tuning &t);
     void release();
     // n must be a multiple of chain.total; any such n streams exactly (no minimum frame length)
     // oa (from OscBank::advance_job for this call, or nullptr): when the route's kernel can advance the oscillators itself it does, and
@@ -208,7 +212,8 @@ struct FastFirCore {
     uint32_t C = 0, fft_n = 2048, taps = 1025;
     float2 *d_H = nullptr, *d_tw = nullptr;
     float2 *d_tw128 = nullptr;   // 2048-point case: table of the two-wave transform (fft_t128.h)
-    int init(uint32_t channels, uint32_t fft_size, uint32_t fir_size);
+    Tuning tun;                  // the owner's switches (init)
+    int init(uint32_t channels, uint32_t fft_size, uint32_t fir_size, const Tuning &t);
     void release();
     long long block_len() const { return (long long)fft_n - (taps - 1); }
     // *ok = false (and H left alone) on the reference's "Filter Parameter error"
@@ -342,13 +347,13 @@ struct WfmCore {
     long long max_n_ = 0;
     int stereo_block = 2048;                  // samples per processDataStereo call in the reference (the owner's frame length)
     WfmPilotParams pilot;
-    RdsCore rds;                              // the RDS branch (PEBBLEGPU_RDS=0 leaves it out)
+    RdsCore rds;                              // the RDS branch (Tuning::rds = false leaves it out)
     // Demod_WFM::getStereoLock (demod_wfm.cpp:436-447): m_PilotLocked after the last block, and whether it differs from the value the
     // previous call of this function saw (m_LastPilotLocked starts as the opposite of m_PilotLocked: the first call reports a change)
     std::vector<char> stereo_ran, last_lock;
     int stereo_lock(hipStream_t s, uint32_t ch, int *lock, int *changed);
-    bool rds_enabled = true;
-    int init(uint32_t channels, double demod_rate, long long max_n);
+    Tuning tun;                               // the owner's switches (init)
+    int init(uint32_t channels, double demod_rate, long long max_n, const Tuning &t);
     void release();
     // more_tails / oa: the caller's other tail-refresh jobs and oscillator advance; when the single-kernel path runs it carries
     // them (and its own history copy) in extra workgroups of its launch and sets *carried -- the caller then skips its own
@@ -443,7 +448,8 @@ struct SpectrumCore {
     float2 *d_ftab = nullptr;         // [bins/nf][nf] window[n] * W_bins^{n q}: the one factor per point of k_spectrum_q128
     std::vector<float> h_window;      // host copy of the window (the decimator's taps against windowed samples)
     bool last_fullc = false;          // the last run used k_spectrum_t128's register-held twiddles (nothing ran beside it)
-    bool use_w64 = false;             // 8192 bins on k_spectrum_w64 (PEBBLEGPU_SPECTRUM_W64=1 when the core is created)
+    Tuning tun;                       // the owner's switches (init)
+    bool use_w64 = false;             // 8192 bins on k_spectrum_w64 (Tuning::spectrum_w64)
     int stagger = 0, pad_lds = 0;     // k_spectrum_t128: barrier intervals between the two halves of a 1024-item workgroup (0: 512-item workgroups)
     bool per_q = false;               // k_spectrum_q128 (one transform per 128-item workgroup) instead of the shared-frame kernels
     // 65536-sample frames / 65536 bins (four-step, kernels_spectrum.h): the [S][F][32][2048] intermediate
@@ -457,7 +463,7 @@ struct SpectrumCore {
     int any_M = 0, any_logM = 0, any_zp_log2 = 0;
     float2 *d_twM = nullptr;          // W_M^k, k < M / 2
     int run_any(hipStream_t s, const float2 *d_in, long long in_pitch, long long n_frames, float *d_out, int n_in, bool windowed);
-    int init(uint32_t streams, uint32_t frame, uint32_t fft_size);
+    int init(uint32_t streams, uint32_t frame, uint32_t fft_size, const Tuning &t);
     void release();
     int run(hipStream_t s, const float2 *d_in, long long in_pitch, long long n_frames, float *d_out, const RawSrc *raw = nullptr, const DecFuse *df = nullptr, bool nothing_beside = false);
     bool dec_ready() const { return !big && !per_q && bins == 8192 && !use_w64; }  // k_spectrum_t128<.., DEC> exists for this plan
@@ -562,7 +568,7 @@ private:
     // stream once it has also seen the transform's end event, and whatever next touches the main stream (the next call, a
     // synchronise) first waits for that end event.  Every event record costs the stream ~5 us, so none is spent on the fork/join.
     hipEvent_t spec_end_ = nullptr;   // pipelined calls: the last display transform queued on the main stream (for the chain's stream to wait on at a join)
-    bool pipeline_ = false;           // successive side-by-side calls overlap (PEBBLEGPU_PIPELINE=1 when the receiver is created)
+    Tuning tun_;                      // the switches, read when the receiver is created
     bool touched_ = true;             // a setter ran since the last call
     bool bank_pipe_ok_ = false;       // no display transform: the call's two stages (decimator | band-pass .. resampler) on the two streams, stage 2 beside the next call's stage 1
     hipEvent_t f_end_[3] = {nullptr, nullptr, nullptr};  // where stage 2 of the last three such calls ended
@@ -570,7 +576,6 @@ private:
     hipEvent_t d_end_prev_ = nullptr;           // where the last call ended, if that was a two-stage call (the next one is timed from there)
     hipEvent_t sync_ev_[4] = {nullptr, nullptr, nullptr, nullptr};  // stage 1 -> stage 2 hand-over events (no timing), a ring
     hipEvent_t pipe_ev_ = nullptr;
-    bool fuse_dec_ = false;           // the one-channel decimator inside the display transform's kernel (PEBBLEGPU_FUSE_DEC=1 at creation)
     hipEvent_t chain_end_ = nullptr;  // set when a two-stream call failed half-way: what was queued on the chain stream, for the main stream to wait on
     hipStream_t zoom_stream_ = nullptr;  // where the last call's zoomed spectra were written (a map of them queues there)
     hipEvent_t map_ev_ = nullptr;     // behind a map queued on the chain's stream: what a join waits for instead of the call's end

@@ -30,8 +30,7 @@ int Receiver::create(const pebblegpu_config *cfg)
     PG_HIP(hipSetDevice(device));
     PG_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     PG_HIP(hipStreamCreateWithFlags(&chain_stream_, hipStreamNonBlocking));
-    { const char *e = getenv("PEBBLEGPU_PIPELINE"); pipeline_ = e && e[0] == '1'; }
-    { const char *e = getenv("PEBBLEGPU_FUSE_DEC"); fuse_dec_ = e && e[0] == '1'; }
+    tun_ = read_tuning();
     for (auto &row : tm.ev)
         for (auto &e : row) PG_HIP(hipEventCreate(&e));
 
@@ -52,12 +51,12 @@ int Receiver::create(const pebblegpu_config *cfg)
     osc_.device_advance = true;  // (banks of more than kOscInline channels: no per-call copy of the oscillators' phases)
     // "Restore gain lost in decimation" 10^(2*stages/20) only on the narrow branch (receiver.cpp:935-938 vs :854-901)
     const float gain = wfm ? 1.f : (float)std::pow(10.0, (double)(chain.dec_by2 * 2) / 20.0);
-    if (int rc = dec_.init(C, chain, max_n, wfm ? 0 : (int)ff_taps - 1, gain)) return rc;
+    if (int rc = dec_.init(C, chain, max_n, wfm ? 0 : (int)ff_taps - 1, gain, tun_)) return rc;
     if (int rc = audio.alloc((int)C, 0, nd_max)) return rc;
     if (!wfm) {
         // Two-stage calls (the band-pass and everything behind it on the chain's stream, beside the NEXT call's decimator): needs the
-        // decimator's output twice (PEBBLEGPU_BANK_PIPELINE=0 when the receiver is created keeps every call on one stream)
-        { const char *e = getenv("PEBBLEGPU_BANK_PIPELINE"); bank_pipe_ok_ = !(e && e[0] == '0') && chain.stages.size() > 1 && !bins; }
+        // decimator's output twice (PEBBLEGPU_BANK_PIPELINE=0 keeps every call on one stream)
+        bank_pipe_ok_ = tun_.bank_pipeline && chain.stages.size() > 1 && !bins;
         if (bank_pipe_ok_) {
             if (int rc = dec_.enable_double_out()) return rc;
             // The second stage runs in what the decimator leaves idle: its stream has the lower priority, so that when a call's decimator
@@ -70,14 +69,14 @@ int Receiver::create(const pebblegpu_config *cfg)
             chain_stream_ = nullptr;
             PG_HIP(hipStreamCreateWithPriority(&chain_stream_, hipStreamNonBlocking, lo));
         }
-        if (int rc = ff_.init(C, ff_n, ff_taps)) return rc;
+        if (int rc = ff_.init(C, ff_n, ff_taps, tun_)) return rc;
         if (int rc = am_.init(C, (double)demod_rate_int, nd_max)) return rc;  // Demod_AM(m_inputSampleRate), demod.cpp:62
         // Demod_SAM / Demod_NFM objects also exist in every Receiver (demod.cpp:63-64); their buffers are allocated on first use
         pll_cap_ = nd_max;
         if (int rc = agc_.init(C, (double)demod_rate_int)) return rc;  // AGC(m_demodSampleRate, m_demodFrames), receiver.cpp:264
         if (int rc = anf_.init(C)) return rc;
     } else {
-        if (int rc = wfmc_.init(C, (double)demod_rate_int, nd_max)) return rc;  // Demod_WFM(m_inputWfmSampleRate), demod.cpp:65
+        if (int rc = wfmc_.init(C, (double)demod_rate_int, nd_max, tun_)) return rc;  // Demod_WFM(m_inputWfmSampleRate), demod.cpp:65
         wfmc_.stereo_block = (int)nf;  // the reference demodulates one accumulated frame per call (receiver.cpp:896)
     }
     if (int rc = cond_.init(S, nf, fs, max_n)) return rc;
@@ -93,15 +92,15 @@ int Receiver::create(const pebblegpu_config *cfg)
         }
     }
     if (bins) {
-        if (int rc = spec_.init(S, nf, bins)) return rc;
+        if (int rc = spec_.init(S, nf, bins, tun_)) return rc;
         bins = spec_.bins;
         PG_HIP(hipMalloc((void **)&d_spec, sizeof(float) * (size_t)(max_n / nf) * bins * S));
-        if (fuse_dec_ && spec_.dec_ready() && nf == 2048) { if (int rc = dec_.set_fuse_window(spec_.d_window, spec_.h_window)) return rc; }  // (opt-in) the decimator may run inside the transform's kernel
+        if (tun_.fuse_dec && spec_.dec_ready() && nf == 2048) { if (int rc = dec_.set_fuse_window(spec_.d_window, spec_.h_window)) return rc; }  // (opt-in) the decimator may run inside the transform's kernel
     }
     zoom_bins = cfg->hires_bins;
     if (zoom_bins) {  // m_fftHiRes->fftParams(m_numHiResSpectrumBins, maxDb, m_hiResSampleRate, numSamples, BLACKMANHARRIS), signalspectrum.cpp:59
         if (nd_max % nf != 0) return fail(PEBBLEGPU_E_UNSUPPORTED, "the zoomed spectrum needs whole frames at the demodulator rate");
-        if (int rc = zoom_.init(C, nf, zoom_bins)) return rc;
+        if (int rc = zoom_.init(C, nf, zoom_bins, tun_)) return rc;
         zoom_bins = zoom_.bins;
         PG_HIP(hipMalloc((void **)&d_zoom, sizeof(float) * (size_t)(nd_max / nf) * zoom_bins * C));
     }
@@ -388,7 +387,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     // its own instruction stream): the band-pass of the previous call fits beside it.  Results are complete after sync().
     const bool bank_pipe = bank_pipe_ok_ && with_chain && !with_spectrum && !profile_detail && squelch_db_ <= -120.0 && !bank_gate_ && !zoom_bins &&
                            !cond_.any && !cond_.dirty && dec_.double_out();
-    const bool plain = (side && pipeline_ && !touched_) || (bank_pipe && !touched_);
+    const bool plain = (side && tun_.pipeline && !touched_) || (bank_pipe && !touched_);
     auto join = [&]() -> int {
         if (chain_end_) PG_HIP(hipStreamWaitEvent(stream_, chain_end_, 0));
         if (spec_end_) PG_HIP(hipStreamWaitEvent(chain_stream_, spec_end_, 0));
@@ -449,8 +448,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         if (bank_pipe && last_reader && hipEventQuery(last_reader) != hipSuccess) {
             // the host is more than two calls ahead of the device: it waits here (PEBBLEGPU_BANK_PIPE_HOSTWAIT=0: a wait in the queue instead,
             // one more packet between this decimator and the last)
-            static const bool host_wait = [] { const char *e = getenv("PEBBLEGPU_BANK_PIPE_HOSTWAIT"); return !(e && e[0] == '0'); }();
-            if (host_wait) PG_HIP(hipEventSynchronize(last_reader));
+            if (tun_.bank_pipe_hostwait) PG_HIP(hipEventSynchronize(last_reader));
             else PG_HIP(hipStreamWaitEvent(stream_, last_reader, 0));
         }
     }
@@ -470,7 +468,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     // Opt-in (PEBBLEGPU_FUSE_DEC=1 when the receiver is created): measured slower -- the stages sit in the kernel's barrier intervals,
     // 0.297 ms against 0.247 beside the stand-alone first stage, the call 0.330 against 0.293
     dec_.want_lds_free = side;
-    const bool fuse_dec = fuse_dec_ && side && with_chain && !pipeline_ && S == 1 && spec_.dec_ready() && nf == 2048 && dec_.spectrum_can_run(osc_) && (!raw || !staged);
+    const bool fuse_dec = tun_.fuse_dec && side && with_chain && !tun_.pipeline && S == 1 && spec_.dec_ready() && nf == 2048 && dec_.spectrum_can_run(osc_) && (!raw || !staged);
     DecFuse df;
     if (fuse_dec) { if (int rc = dec_.fill_dec_fuse(stream_, &df, osc_, (long long)n)) return rc; }
     if (with_spectrum) {  // SignalSpectrum::unprocessed on the raw frame, receiver.cpp:826
@@ -508,9 +506,9 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
             if (int rc = osc_.advance_job(cs, n, &oa_pre)) return rc;
             have_oa = true;
         }
-        static const bool ext_ev = [] { const char *e = getenv("PEBBLEGPU_BANK_PIPE_EXTEV"); return e && e[0] == '1'; }();  // opt-in: measured 0.0695 / 0.0753 ms (configs[2] / configs[3] shard) against 0.0663 / 0.0774 without
+        // (PEBBLEGPU_BANK_PIPE_EXTEV=1, opt-in: measured 0.0695 / 0.0753 ms (configs[2] / configs[3] shard) against 0.0663 / 0.0774 without)
         dec_.done_event = nullptr;
-        if (bank_pipe && ext_ev) {  // the hand-over event of a two-stage call: completed by the bank kernel's own dispatch when that ends the first stage
+        if (bank_pipe && tun_.bank_pipe_extev) {  // the hand-over event of a two-stage call: completed by the bank kernel's own dispatch when that ends the first stage
             if (!sync_ev_[0]) for (hipEvent_t &e : sync_ev_) PG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             dec_.done_event = sync_ev_[tm.calls % 4];
         }
@@ -526,7 +524,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         const bool nothing_behind = jobs.empty() && oa_pre.osc == nullptr;
         if (int rc = run_save_tails(stream_, jobs, C, &oa_pre)) return rc;  // (no launch at all behind the bank kernel: nothing left to do)
         // (an event without timing for the hand-over: PEBBLEGPU_BANK_PIPE_TIMED_EV=1 records the call's timing event instead -- A/B)
-        static const bool timed_ev = [] { const char *e = getenv("PEBBLEGPU_BANK_PIPE_TIMED_EV"); return e && e[0] == '1'; }();
+        const bool timed_ev = tun_.bank_pipe_timed_ev;
         if (!sync_ev_[0]) for (hipEvent_t &e : sync_ev_) PG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         pipe_ev_ = timed_ev ? ev[1] : sync_ev_[tm.calls % 4];
         if (!(dec_.done_recorded && nothing_behind && !timed_ev)) PG_HIP(hipEventRecord(pipe_ev_, stream_));
@@ -535,8 +533,8 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         // (with two output buffers the next call's decimator becomes ready with the same event as this band-pass: a short nap lets its
         // one-wave-per-SIMD workgroups be placed before the band-pass fills the CUs -- placed behind them it ran 112 us instead of 65.
         // With three the next decimator is already running when this point is reached: no nap)
-        static const int nap_env = [] { const char *e = getenv("PEBBLEGPU_BANK_PIPE_NAP_US"); return e ? (int)(100.0 * atof(e)) : -1; }();
-        if (int rc = run_nap(cs, nap_env >= 0 ? (unsigned)nap_env : (rot3 ? 0u : 800u))) return rc;
+        const int nap = tun_.bank_pipe_nap;
+        if (int rc = run_nap(cs, nap >= 0 ? (unsigned)nap : (rot3 ? 0u : 800u))) return rc;
     }
     const long long nd = dec_.out_len();
     if (zoom_bins) {  // SignalSpectrum::zoomed(m_sampleBuf, numStepSamples), receiver.cpp:884 / :942 (the update timer forced open)
@@ -646,7 +644,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
             if (!found) out_reader_.push_back({(const void *)dec_.fin.base, ev[6]});
         }
         d_end_prev_ = ev[6];
-    } else if (side && pipeline_) {
+    } else if (side && tun_.pipeline) {
         // the call's two pipelines end separately: whoever needs both waits for both (sync(), the next call that is not plain)
         PG_HIP(hipEventRecord(ev[6], cs));
         chain_end_ = ev[6];
@@ -656,8 +654,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         // of the next call (the two swap roles): its first kernel then follows this call's last in queue order, where a wait
         // on an event from the other queue cost ~25 us of idle GPU per call
         if (!fuse_dec) PG_HIP(hipStreamWaitEvent(cs, ev[1], 0));
-        static const bool end_records = [] { const char *e = getenv("PEBBLEGPU_EVENTS"); return e && e[0] == 'f'; }();  // =full: an end record per call (A/B)
-        if (end_records) PG_HIP(hipEventRecord(ev[6], cs));
+        if (tun_.end_records) PG_HIP(hipEventRecord(ev[6], cs));
         else tm.open_slot = slot;  // (closed by the next call's start record, by sync() or by a timing query)
         std::swap(stream_, chain_stream_);
     } else {

@@ -59,6 +59,7 @@ struct pebblegpu_decimator : pg::StepBase {
     bool built = false;
     pg::OscBank osc;  // frequency 0: the oscillator is bypassed, the fused kernel only decimates
     pg::DecimCore dec;
+    pg::Tuning tun;   // read at create, handed to dec.init() by every build_chain
     float2 *d_in = nullptr;
 };
 // CDownConvert (pebblelib/downconvert.cpp): quadrature-oscillator mixer + a cascade of decimate-by-2 stages
@@ -173,6 +174,7 @@ int pebblegpu_decimator_create(int device, uint32_t sample_rate, uint32_t buffer
     if (!d) return fail(PEBBLEGPU_E_INVALID, "out of host memory");
     d->fs = sample_rate;
     d->cap = buffer_size;
+    d->tun = pg::read_tuning();
     int rc = d->open(device);
     if (!rc) rc = d->osc.init(1, (double)sample_rate);
     if (!rc && hipMalloc((void **)&d->d_in, sizeof(float2) * buffer_size) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
@@ -201,7 +203,7 @@ int pebblegpu_decimator_build_chain(pebblegpu_decimator *d, uint32_t sample_rate
     d->built = false;
     if (c.stages.empty()) { d->dec.release(); d->dec.chain = c; return 0; }  // "No decimation, just return" (decimator.cpp:155-160)
     if (c.stages.size() > (size_t)pg::kMaxStages) return fail(PEBBLEGPU_E_UNSUPPORTED, "chain too long");
-    if (int rc = d->dec.init(1, c, (long long)d->cap, 0, 1.0f)) return rc;
+    if (int rc = d->dec.init(1, c, (long long)d->cap, 0, 1.0f, d->tun)) return rc;
     d->built = true;
     return 0;
 }
@@ -391,7 +393,7 @@ int pebblegpu_fastfir_create(int device, uint32_t fft_size, uint32_t fir_size, p
     pebblegpu_fastfir *f = new (std::nothrow) pebblegpu_fastfir();
     if (!f) return fail(PEBBLEGPU_E_INVALID, "out of host memory");
     int rc = f->open(device);
-    if (!rc) rc = f->ff.init(1, fft_size ? fft_size : 2048, fir_size ? fir_size : 1025);
+    if (!rc) rc = f->ff.init(1, fft_size ? fft_size : 2048, fir_size ? fir_size : 1025, pg::read_tuning());
     if (!rc) {
         f->cap = 64 * f->ff.block_len();
         rc = f->in.alloc(1, (int)f->ff.taps - 1, f->cap);
@@ -473,7 +475,7 @@ int pebblegpu_demod_create(int device, uint32_t sample_rate, uint32_t wfm_sample
         rc = d->sam.set_list(d->stream, std::vector<int>(1, 0));
         if (!rc) rc = d->nfm.set_list(d->stream, std::vector<int>(1, 0));
     }
-    if (!rc && wfm_sample_rate) rc = d->wfm.init(1, (double)wfm_sample_rate, buffer_size);
+    if (!rc && wfm_sample_rate) rc = d->wfm.init(1, (double)wfm_sample_rate, buffer_size, pg::read_tuning());
     d->wfm.stereo_block = 0;  // a processBlock call is one block
     if (!rc && hipMalloc((void **)&d->d_in, sizeof(float2) * buffer_size) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
     if (!rc && hipMalloc((void **)&d->d_out, sizeof(float2) * buffer_size) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
@@ -574,7 +576,7 @@ int pebblegpu_spectrum_create(int device, uint32_t fft_size, double sample_rate,
     if (!s) return fail(PEBBLEGPU_E_INVALID, "out of host memory");
     s->fs = sample_rate;  // the bin width (fft.cpp:81) and mapFFTToScreen's binsPerHz (:424)
     int rc = s->open(device);
-    if (!rc) rc = s->sp.init(1, samples_per_buffer, fft_size);
+    if (!rc) rc = s->sp.init(1, samples_per_buffer, fft_size, pg::read_tuning());
     if (!rc && hipMalloc((void **)&s->d_in, sizeof(float2) * samples_per_buffer) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
     if (!rc && hipMalloc((void **)&s->d_out, sizeof(float) * s->sp.bins) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
     if (rc) { pebblegpu_spectrum_destroy(s); return rc; }

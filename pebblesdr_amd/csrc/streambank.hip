@@ -61,9 +61,10 @@ int pebblegpu_streambank_create(const pebblegpu_streambank_config *cfg, pebblegp
         PG_HIP(hipSetDevice(cfg->device));
         PG_HIP(hipStreamCreateWithFlags(&sb->stream, hipStreamNonBlocking));
         PG_HIP(hipStreamCreateWithFlags(&sb->stream2, hipStreamNonBlocking));
-        { const char *e = getenv("PEBBLEGPU_SB_SIDE"); sb->side_ok = e && e[0] == '1'; }  // opt-in: measured equal (below)
-        if (int r = sb->ff.init(S, sb->cfg.fastfir_fft, sb->cfg.fastfir_taps)) return r;
-        if (int r = sb->sp.init(S, cfg->frame, cfg->spectrum_bins)) return r;
+        const pg::Tuning tun = pg::read_tuning();
+        sb->side_ok = tun.sb_side;  // opt-in: measured equal (below)
+        if (int r = sb->ff.init(S, sb->cfg.fastfir_fft, sb->cfg.fastfir_taps, tun)) return r;
+        if (int r = sb->sp.init(S, cfg->frame, cfg->spectrum_bins, tun)) return r;
         if (cfg->frame % (uint64_t)sb->ff.block_len()) return fail(PEBBLEGPU_E_SIZE, "frame %u is not a multiple of the band-pass block %lld", cfg->frame, sb->ff.block_len());
         const size_t ov = sb->cfg.fastfir_taps - 1;
         PG_HIP(hipMalloc((void **)&sb->d_tail, sizeof(float2) * ov * S));

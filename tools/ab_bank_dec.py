@@ -17,9 +17,6 @@ VARIANTS = [
     ("k_mix_dec_mfma, 2 waves/SIMD", {"PEBBLEGPU_BANK_DEC": "1", "PEBBLEGPU_BANK_WAVES": "2"}),
     ("k_mix_dec_mfma, 3 waves/SIMD", {"PEBBLEGPU_BANK_DEC": "1", "PEBBLEGPU_BANK_WAVES": "3"}),
 ]
-if os.environ.get("AB_DBG"):  # timing experiments: parts of the kernel switched off (results wrong)
-    VARIANTS = [("mfma W1", {"PEBBLEGPU_BANK_DEC": "1", "PEBBLEGPU_BANK_WAVES": "1"})]
-DBG = os.environ.get("AB_DBG")
 KEYS = ("PEBBLEGPU_BANK_DEC", "PEBBLEGPU_BANK_WAVES", "PEBBLEGPU_FUSED_L")
 
 
@@ -37,8 +34,6 @@ def make(env, fs, C, k):
 
 def main():
     ks = [int(a) for a in sys.argv[1:]] or [8, 32]
-    if DBG:
-        os.environ["PEBBLEGPU_BANK_DBG"] = DBG
     fs, C = 2048000, 256
     for k in ks:
         rxs = [(name, make(env, fs, C, k)) for name, env in VARIANTS]

@@ -1,7 +1,7 @@
 import os, sys
 import numpy as np
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
-os.environ["PEBBLEGPU_BANK_CLK"] = "0"
+os.environ["PEBBLEGPU_BANK_CLK"] = "1"  # (read when the receiver is created: every launch of it prints its waves' clock counts)
 import pebblesdr_amd as P
 fs, C = 2400000, 32
 rx = P.ReceiverBank(fs, C, True, False, 0, max_superframes=1)
@@ -13,7 +13,6 @@ rng = np.random.default_rng(1)
 x = ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.05).astype(np.complex64)
 buf = P.DeviceBuffer.from_array(x.view(np.float32))
 rx.process_device(buf.ptr, n); rx.synchronize()
-os.environ["PEBBLEGPU_BANK_CLK"] = "1"
 for _ in range(2):
     rx.process_device(buf.ptr, n)
 rx.synchronize()
