@@ -173,6 +173,36 @@ int pebblegpu_receiver_rds_groups(pebblegpu_receiver *rx, uint32_t channel, pebb
  * frame of the channel (0 before its first dmFMS frame), *changed != 0 when that differs from what the previous call of this function
  * reported (the first call reports a change: m_LastPilotLocked starts as the opposite).  Waits for the receiver's queued work. */
 int pebblegpu_receiver_stereo_lock(pebblegpu_receiver *rx, uint32_t channel, int *pilot_lock, int *changed);
+/* The digital-modem hook between the noise filter and the AGC (application/receiver.cpp:977-980), with the Morse decoder
+ * (plugins/MorseDigitalModem, its default Goertzel path) per channel of a narrow receiver: Decimator to about 8 kHz
+ * (buildDecimationChain(demodRate, 1000, 8000)), a Goertzel bin of N samples at +-1000 Hz, GoertzelOOK's TH_PEAK threshold and
+ * Morse::stateMachine, on the device behind every call.  The library emits the reference's token per completed character (a leading 1,
+ * then 1 per dash and 0 per dot, at most 8 elements: MorseCode::tokenizeDotDash, morsecode.cpp:160-185) and a word-space event;
+ * the application renders text with MorseCode::tokenLookup ("*" when it returns nothing).  See DESIGN.md section 3. */
+typedef struct pebblegpu_morse_event {
+    uint64_t sample;  /* modem-rate samples since the modem was enabled, up to the one whose Goertzel result decided the event */
+    uint32_t token;   /* kind PEBBLEGPU_MORSE_CHAR: the token; PEBBLEGPU_MORSE_WORD_SPACE: 0 */
+    uint32_t kind;
+} pebblegpu_morse_event;
+#define PEBBLEGPU_MORSE_CHAR 0u
+#define PEBBLEGPU_MORSE_WORD_SPACE 1u
+/* what Morse::refreshOutput shows (morse.cpp:477-500): the WPM estimate (m_wpmSpeedCurrent; "?? est" when a flag is set), the
+ * out-of-range flags, the modem rate and N (Goertzel samples per result) */
+typedef struct pebblegpu_morse_report {
+    int32_t wpm, above_range, below_range;
+    uint32_t modem_rate, samples_per_result;
+} pebblegpu_morse_report;
+/* Receiver::setDigitalModem("Morse") + Morse::setSampleRate(m_demodSampleRate, m_demodFrames) (on != 0, also on a channel whose modem is
+ * already on): a fresh decoder in dmCWL whatever the channel's mode (morse.cpp:181; later pebblegpu_set_demod_mode calls are forwarded,
+ * receiver.cpp:653-654), starting from the channel's current WPM estimate (20 the first time); events decided before stay readable.
+ * on == 0 drops the decoder's state and its unread events.  Channels in dmNONE and calls closed by
+ * the squelch of a one-channel receiver leave the modem untouched.  Refused (PEBBLEGPU_E_UNSUPPORTED) by WFM receivers and together
+ * with a bank's per-channel squelch (by whichever of the two setters comes second).  Waits for the channel's queued modem work. */
+int pebblegpu_set_morse(pebblegpu_receiver *rx, uint32_t channel, int on);
+/* the channel's events since the last read, oldest first (*n <= cap; the rest stays).  None is lost however many calls run between
+ * two reads.  Waits for the receiver's queued modem work. */
+int pebblegpu_receiver_morse_events(pebblegpu_receiver *rx, uint32_t channel, pebblegpu_morse_event *ev, uint32_t cap, uint32_t *n);
+int pebblegpu_receiver_morse_status(pebblegpu_receiver *rx, uint32_t channel, pebblegpu_morse_report *st);
 /* AGC::setAgcMode(mode, threshold) (application/agc.cpp:53-82; Receiver::agcModeChanged/agcThresholdChanged).
  * agc_mode: the reference's AgcMode values.  With PEBBLEGPU_AGC_OFF the threshold is a manual gain slider in dB
  * (amplitude 10^((threshold/5)/20), integer division as written, agc.cpp:239-246; the constructor's OFF/1 is unit
@@ -452,6 +482,23 @@ int pebblegpu_spectrum_process(pebblegpu_spectrum *s, const double *in, int n, d
  * (what SignalSpectrum always passes): that spectrum, exactly the floats the call handed out as doubles, mapped on the device into
  * the host buffer out (x_pixels int32); sampleRate is the one the object was created with.  Blocks until out is written. */
 int pebblegpu_spectrum_map_to_screen(pebblegpu_spectrum *s, const pebblegpu_screen_map *map, int32_t *out);
+
+typedef struct pebblegpu_morse pebblegpu_morse;
+/* Morse (DigitalModemInterface) + setSampleRate(sample_rate, sample_count), morse.cpp:160-246: the decoder as above on one stream */
+int pebblegpu_morse_create(int device, uint32_t sample_rate, uint32_t sample_count, pebblegpu_morse **out);
+int pebblegpu_morse_destroy(pebblegpu_morse *m);
+int pebblegpu_morse_set_demod_mode(pebblegpu_morse *m, int mode);  /* Morse::setDemodMode, morse.cpp:337-341 */
+/* CPX *Morse::processBlock(CPX *in), morse.cpp:761-894: one frame of sample_count CPX; the reference returns in unchanged */
+int pebblegpu_morse_process(pebblegpu_morse *m, const double *in);
+int pebblegpu_morse_events(pebblegpu_morse *m, pebblegpu_morse_event *ev, uint32_t cap, uint32_t *n);
+int pebblegpu_morse_status(pebblegpu_morse *m, pebblegpu_morse_report *st);
+/* Morse::setSampleRate again (every powerOn of the reference): a fresh decoder in dmCWL, with new frames if sample_count changed, that
+ * starts from the current WPM estimate (the plugin object keeps m_wpmSpeedCurrent, morse.h:223).  Events decided before stay readable. */
+int pebblegpu_morse_set_sample_rate(pebblegpu_morse *m, uint32_t sample_rate, uint32_t sample_count);
+/* for parity checks: on != 0 makes every later process call also collect, per Goertzel result, m_power and the above-threshold decision
+ * (off by default: nothing is kept); pebblegpu_morse_results hands them out since its last call (*n <= cap; the rest stays) */
+int pebblegpu_morse_keep_results(pebblegpu_morse *m, int on);
+int pebblegpu_morse_results(pebblegpu_morse *m, double *power, uint8_t *tone, uint32_t cap, uint32_t *n);
 
 #ifdef __cplusplus
 }

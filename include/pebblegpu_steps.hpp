@@ -324,6 +324,57 @@ private:
     int device, status = 0;
 };
 
+// The Morse digital modem (plugins/MorseDigitalModem/morse.h), DigitalModemInterface's processing members.  Where the reference
+// appends text, the library hands out the tokens of MorseCode::tokenizeDotDash and word spaces: render them with the application's
+// MorseCode::tokenLookup(Morse::dotDash(token)) ("*" when it returns NULL) and " ".
+typedef pebblegpu_morse_event MorseEvent;
+typedef pebblegpu_morse_report MorseReport;
+class Morse {
+public:
+    explicit Morse(int device = 0) : dev(device) {}
+    ~Morse() { pebblegpu_morse_destroy(h); }
+    Morse(const Morse &) = delete;
+    Morse &operator=(const Morse &) = delete;
+    void setSampleRate(int sampleRate, int sampleCount)  // morse.cpp:160-246: a fresh decoder in dmCWL from the current WPM estimate
+    {
+        if (h) status = report("morse_set_sample_rate", pebblegpu_morse_set_sample_rate(h, (uint32_t)sampleRate, (uint32_t)sampleCount));
+        else status = report("morse_create", pebblegpu_morse_create(dev, (uint32_t)sampleRate, (uint32_t)sampleCount, &h));
+    }
+    void setDemodMode(DemodMode m) { if (h) status = report("morse_set_demod_mode", pebblegpu_morse_set_demod_mode(h, (int)m)); }
+    CPX *processBlock(CPX *in)  // morse.cpp:761-894: returns in unchanged
+    {
+        if (h) status = report("morse_process", pebblegpu_morse_process(h, reinterpret_cast<const double *>(in)));
+        return in;
+    }
+    // the events since the last call, oldest first
+    std::vector<MorseEvent> events()
+    {
+        std::vector<MorseEvent> out;
+        MorseEvent buf[256];
+        uint32_t got = 256;
+        while (h && got == 256) {
+            if ((status = report("morse_events", pebblegpu_morse_events(h, buf, 256, &got))) != 0) break;
+            out.insert(out.end(), buf, buf + got);
+        }
+        return out;
+    }
+    MorseReport getStatus() { MorseReport r{}; if (h) status = report("morse_status", pebblegpu_morse_status(h, &r)); return r; }  // refreshOutput
+    // the dot-dash string of a token (the inverse of MorseCode::tokenizeDotDash, morsecode.cpp:160-185), as tokenLookup takes it
+    static std::string dotDash(uint32_t token)
+    {
+        std::string s;
+        int top = 31;
+        while (top > 0 && !((token >> top) & 1u)) top--;
+        for (int b = top - 1; b >= 0; b--) s += ((token >> b) & 1u) ? '-' : '.';
+        return s;
+    }
+    int lastStatus() const { return status; }
+
+private:
+    pebblegpu_morse *h = nullptr;
+    int dev = 0, status = 0;
+};
+
 // The slice of application/receiver.cpp this library replaces: turnPowerOn's step construction and
 // processIQData's DSP for one tuned channel, audio delivered through the CB_ProcessAudioData-shaped callback.
 class Receiver {
@@ -368,6 +419,20 @@ public:
     // agcModeChanged / agcThresholdChanged -> AGC::setAgcMode(mode, threshold) (agc.cpp:53-82)
     void agcModeChanged(int agcMode, int threshold) { if (h) status = report("set_agc", pebblegpu_set_agc(h, 0, agcMode, threshold)); }
     void squelchChanged(double s) { if (h) status = report("set_squelch", pebblegpu_set_squelch(h, 0, s)); }                // receiver.cpp:704
+    // setDigitalModem("Morse") / setDigitalModem(NULL) (receiver.cpp:1085-1115) and the Morse decoder's output
+    void setMorse(bool on) { if (h) status = report("set_morse", pebblegpu_set_morse(h, 0, on ? 1 : 0)); }
+    std::vector<MorseEvent> morseEvents()
+    {
+        std::vector<MorseEvent> out;
+        MorseEvent buf[256];
+        uint32_t got = 256;
+        while (h && got == 256) {
+            if ((status = report("receiver_morse_events", pebblegpu_receiver_morse_events(h, 0, buf, 256, &got))) != 0) break;
+            out.insert(out.end(), buf, buf + got);
+        }
+        return out;
+    }
+    MorseReport morseStatus() { MorseReport r{}; if (h) status = report("receiver_morse_status", pebblegpu_receiver_morse_status(h, 0, &r)); return r; }
     // bound as the device plugin's CB_ProcessIQData, like receiver.cpp:135-138
     void processIQData(CPX *in, uint16_t numSamples)
     {

@@ -33,6 +33,10 @@ SYMBOLS = [
     "pebblegpu_spectrum_create", "pebblegpu_spectrum_destroy", "pebblegpu_spectrum_bins", "pebblegpu_spectrum_process",
     "pebblegpu_receiver_map_spectrum", "pebblegpu_receiver_map_zoom_spectrum", "pebblegpu_streambank_map_spectrum",
     "pebblegpu_spectrum_map_to_screen",
+    "pebblegpu_set_morse", "pebblegpu_receiver_morse_events", "pebblegpu_receiver_morse_status",
+    "pebblegpu_morse_create", "pebblegpu_morse_destroy", "pebblegpu_morse_set_demod_mode", "pebblegpu_morse_process",
+    "pebblegpu_morse_events", "pebblegpu_morse_status", "pebblegpu_morse_results", "pebblegpu_morse_set_sample_rate",
+    "pebblegpu_morse_keep_results",
 ]
 
 
@@ -91,6 +95,40 @@ def _download_i32(L, device, p, shape):
     if out.size:
         check(L, L.pebblegpu_memcpy_d2h(device, out.ctypes.data_as(C.c_void_p), C.c_void_p(p), out.nbytes))
     return out
+
+
+# pebblegpu_morse_event as a numpy record: (sample, token, kind); kind MORSE_CHAR carries the dot-dash token, MORSE_WORD_SPACE " "
+MORSE_EVENT = np.dtype([("sample", np.uint64), ("token", np.uint32), ("kind", np.uint32)])
+MORSE_CHAR, MORSE_WORD_SPACE = 0, 1
+
+
+class MorseReport(C.Structure):
+    """pebblegpu_morse_report: what Morse::refreshOutput shows (morse.cpp:477-500)"""
+    _fields_ = [("wpm", C.c_int32), ("above_range", C.c_int32), ("below_range", C.c_int32),
+                ("modem_rate", C.c_uint32), ("samples_per_result", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def morse_token_to_dotdash(token):
+    """The dot-dash string MorseCode::tokenLookup takes for a token (the inverse of tokenizeDotDash, morsecode.cpp:160-185)"""
+    token = int(token)
+    if token < 2:
+        return ""
+    n = token.bit_length() - 1
+    return "".join("-" if (token >> (n - 1 - i)) & 1 else "." for i in range(n))
+
+
+def _morse_events(L, fn, *args, cap=4096):
+    out = []
+    while True:
+        ev = np.zeros(cap, dtype=MORSE_EVENT)
+        n = C.c_uint32(0)
+        check(L, fn(*args, ev.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        out.append(ev[:n.value].copy())
+        if n.value < cap:
+            return np.concatenate(out)
 
 
 class Info(C.Structure):
@@ -204,6 +242,18 @@ def _declare(L):
     L.pebblegpu_receiver_map_zoom_spectrum.argtypes = [vp, C.c_int32, C.c_int32, dbl, dbl, dbl, ip, u32, u32, u32, vp]
     L.pebblegpu_streambank_map_spectrum.argtypes = [vp, smp, u32, u32, u32, vp]
     L.pebblegpu_spectrum_map_to_screen.argtypes = [vp, smp, ip]
+    L.pebblegpu_set_morse.argtypes = [vp, u32, i32]
+    L.pebblegpu_receiver_morse_events.argtypes = [vp, u32, vp, u32, C.POINTER(u32)]
+    L.pebblegpu_receiver_morse_status.argtypes = [vp, u32, C.POINTER(MorseReport)]
+    L.pebblegpu_morse_create.argtypes = [i32, u32, u32, C.POINTER(vp)]
+    L.pebblegpu_morse_destroy.argtypes = [vp]
+    L.pebblegpu_morse_set_demod_mode.argtypes = [vp, i32]
+    L.pebblegpu_morse_process.argtypes = [vp, dp]
+    L.pebblegpu_morse_events.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.pebblegpu_morse_status.argtypes = [vp, C.POINTER(MorseReport)]
+    L.pebblegpu_morse_results.argtypes = [vp, dp, vp, u32, C.POINTER(u32)]
+    L.pebblegpu_morse_set_sample_rate.argtypes = [vp, u32, u32]
+    L.pebblegpu_morse_keep_results.argtypes = [vp, i32]
     return L
 
 
@@ -369,6 +419,19 @@ class ReceiverBank:
         n = C.c_uint32(0)
         check(self.L, self.L.pebblegpu_receiver_rds_groups(self.h, ch, g.ctypes.data_as(C.c_void_p), chg.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return g[:n.value].copy(), chg[:n.value].astype(bool)
+
+    def set_morse(self, ch, on=True):
+        """Receiver::setDigitalModem("Morse") on a channel (on) or off: the Morse decoder behind the noise filter"""
+        check(self.L, self.L.pebblegpu_set_morse(self.h, ch, 1 if on else 0))
+
+    def morse_events(self, ch):
+        """the channel's Morse events since the last read -> MORSE_EVENT records (sample, token, kind), oldest first"""
+        return _morse_events(self.L, self.L.pebblegpu_receiver_morse_events, self.h, ch)
+
+    def morse_status(self, ch):
+        st = MorseReport()
+        check(self.L, self.L.pebblegpu_receiver_morse_status(self.h, ch, C.byref(st)))
+        return st.as_dict()
 
     def set_conditioners(self, stream, flags, iq_gain=1.0, iq_phase=0.0):
         check(self.L, self.L.pebblegpu_set_conditioners(self.h, stream, int(flags), float(iq_gain), float(iq_phase)))

@@ -301,4 +301,44 @@ struct SpectrumParams {
     long long out_pitch;     // floats between streams (= n_frames*bins)
 };
 
+// ---- the Morse digital modem (kernels_modem.h) ----
+constexpr uint32_t kMorseDotMagic = 1200000;  // MorseCode::c_uSecDotMagic, morsecode.h:58
+constexpr uint32_t kMorseWpmLow = 10, kMorseWpmHigh = 50, kMorseWpmVar = 2;  // morse.h:82-83, :169
+constexpr int kMorseMaxLen = 8;               // MorseCode::c_maxMorseLen, morsecode.h:51
+enum MorseRx { kMsIdle = 0, kMsMark = 1, kMsInterElement = 2, kMsWordSpace = 3 };  // DECODE_STATE, morse.h
+
+// one decided output of Morse::outputString: a character (the dot-dash token of morsecode.cpp:160-185) or the word space " "
+struct MorseEvent {
+    uint64_t sample;  // modem-rate samples since the modem was enabled, up to and including the one whose result decided it
+    uint32_t token;   // kind 0: leading 1, then 1 per dash and 0 per dot (oldest element first); kind 1: 0
+    uint32_t kind;    // 0 character, 1 word space
+};
+
+// the modem rate's constants: Goertzel::setFreq (goertzel.cpp:154-219) for +1000 Hz ([0]) and -1000 Hz moved up by the rate ([1])
+struct MorseParams {
+    double B[2], Cr[2], Ci[2], Dr[2], Di[2];
+    uint32_t N, rate;
+};
+
+// everything Morse, GoertzelOOK, Goertzel and the dot-dash threshold filter carry from one sample to the next, per channel
+struct MorseState {
+    double s1r, s1i, s2r, s2i;        // Goertzel m_s1, m_s2
+    double peak, minp;                // GoertzelOOK m_peakPower, m_minPower
+    double peak_avg, min_avg;         // ... their DecayMovingAverage filters' m_movingAvg
+    double sma[8];                    // m_dotDashThresholdFilter: SimpleMovingAverage(8), movingavgfilter.cpp:66-130
+    double sma_sum, sma_avg;
+    uint64_t abs;                     // modem samples since enabled
+    uint64_t n_events;                // events appended to the channel's log since enabled
+    uint32_t count;                   // Goertzel m_nCount
+    uint32_t neg;                     // the tone sits at -1000 Hz (CWL / LSB): MorseParams [1]
+    uint32_t nres, first_end;         // this call's results and the call index of the first one's last sample (k_morse_goertzel -> k_morse_decide)
+    int32_t last_tone, sma_primed, sma_idx;
+    int32_t state, last_state, mark_handled, dd_len;
+    uint32_t dd_bits;                 // m_dotDashBuf as a token without its leading 1
+    uint32_t clk;                     // SampleClock m_clock
+    uint32_t tone_end, usec_mark, usec_space, usec_last_mark, usec_last_space;
+    uint32_t ddt, element, chr, word, spike, fade, dot, dash, shortest;
+    int32_t wpm, above, below;
+};
+
 }  // namespace pg

@@ -170,6 +170,23 @@ int pebblegpu_set_demod_mode(pebblegpu_receiver *h, uint32_t channel, int mode)
     return h->rx.set_mode(channel, mode);
 }
 
+int pebblegpu_set_morse(pebblegpu_receiver *h, uint32_t channel, int on)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.set_morse(channel, on != 0);
+}
+int pebblegpu_receiver_morse_events(pebblegpu_receiver *h, uint32_t channel, pebblegpu_morse_event *ev, uint32_t cap, uint32_t *n)
+{
+    if (!h || !n) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    static_assert(sizeof(pebblegpu_morse_event) == sizeof(pg::MorseEvent), "event layout");
+    return h->rx.morse_events(channel, reinterpret_cast<pg::MorseEvent *>(ev), ev ? cap : 0, n);
+}
+int pebblegpu_receiver_morse_status(pebblegpu_receiver *h, uint32_t channel, pebblegpu_morse_report *st)
+{
+    if (!h || !st) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    static_assert(sizeof(pebblegpu_morse_report) == sizeof(pg::MorseStatus), "status layout");
+    return h->rx.morse_status(channel, reinterpret_cast<pg::MorseStatus *>(st));
+}
 int pebblegpu_receiver_rds_groups(pebblegpu_receiver *h, uint32_t channel, pebblegpu_rds_group *groups, uint8_t *changed, uint32_t cap, uint32_t *n)
 {
     if (!h || !n) return fail(PEBBLEGPU_E_INVALID, "null argument");

@@ -312,6 +312,46 @@ struct RdsCore {
     int signal(hipStream_t s, uint32_t ch, double *data, uint32_t cap_out, uint32_t *n_out);  // m_RdsData of the last call
 };
 
+// ---- the Morse digital modem behind the noise filter (plugins/MorseDigitalModem, Goertzel path; morse.hip, kernels_modem.h) ----
+struct MorseStatus { int32_t wpm, above, below; uint32_t rate, samples_per_result; };  // what Morse::refreshOutput shows (morse.cpp:477-500)
+struct MorseCore {
+    uint32_t C = 0, in_rate = 0;
+    design::Chain chain;                       // Decimator::buildDecimationChain(demodRate, 1000, 8000), morse.cpp:193
+    MorseParams pp = {};
+    long long cap_in = 0, rpitch = 0;          // input samples per call at most; results per channel row
+    int log_cap = 0;                           // events per channel the device log holds
+    std::vector<float *> d_taps;               // per stage
+    std::vector<float2 *> d_hist, d_out;       // per stage: [C][kMaxTaps] the input's tail of the last call; [C][out_pitch] the output
+    std::vector<long long> out_pitch;
+    double *d_power = nullptr;                 // [C][rpitch] this call's Goertzel powers
+    unsigned char *d_tone = nullptr;           // [C][rpitch] ... and decisions (stand-alone step only)
+    MorseState *d_state = nullptr;             // [C]
+    MorseEvent *d_log = nullptr;               // [C][log_cap] ring
+    int *d_list = nullptr;                     // the channels the modem runs for (on, and not in dmNONE)
+    std::vector<int> list;
+    std::vector<unsigned char> on, tune_only;
+    std::vector<int32_t> wpm;                  // where the next enable starts: m_wpmSpeedCurrent outlives setSampleRate (morse.h:223)
+    struct Host { uint64_t seen = 0; std::vector<MorseEvent> q; };
+    std::vector<Host> host;
+    std::vector<MorseState> h_state;
+    std::vector<MorseEvent> h_log;
+    long long since_drain = 0;                 // results queued since the log was last drained (each adds at most one event)
+    hipEvent_t done = nullptr;                 // behind the last decide launch
+    bool recorded = false;
+    int n_on = 0;
+    bool any() const { return n_on > 0; }
+    int init(uint32_t channels, uint32_t demod_rate, long long max_n, bool keep_tone);
+    void release();
+    int check(long long n) const;              // refusals for a call of n input samples (before anything is queued)
+    int enable(uint32_t ch, bool on, int mode);  // setDigitalModem + setSampleRate (on), drop the state (off); synchronous
+    int set_mode(uint32_t ch, int mode);       // Morse::setDemodMode (and dmNONE leaves the channel out); synchronous
+    int run(hipStream_t s, const float2 *in, long long in_pitch, long long n);
+    int drain();                               // waits for the last call, moves every channel's new events to the host
+    int events(uint32_t ch, MorseEvent *ev, uint32_t cap, uint32_t *n);
+    int status(uint32_t ch, MorseStatus *st);
+    int upload_list();
+};
+
 struct WfmCore {
     uint32_t C = 0;
     double rate = 0;
@@ -504,6 +544,10 @@ public:
     // dmFMS channels of a WFM bank: what Demod::fmStereo took from the RDS group queue since the last call (waits for queued work)
     int rds_groups(uint32_t ch, RdsGroup *g, unsigned char *changed, uint32_t cap, uint32_t *n);
     int stereo_lock(uint32_t ch, int *lock, int *changed);
+    // the digital-modem hook between the noise filter and the AGC (receiver.cpp:977-980): the Morse decoder per channel
+    int set_morse(uint32_t ch, bool on);
+    int morse_events(uint32_t ch, MorseEvent *ev, uint32_t cap, uint32_t *n);
+    int morse_status(uint32_t ch, MorseStatus *st);
     int process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw = nullptr);
     int process_iq(const double *iq, uint16_t n, double *audio, uint32_t *n_audio, double *spectrum_db);
     // FFT::mapFFTToScreen of frames first + j * step (j < n) of the last call's unprocessed spectrum (zoom = false) or zoomed spectra
@@ -591,6 +635,7 @@ private:
     AgcCore agc_;
     ConditionCore cond_;
     AnfCore anf_;
+    MorseCore morse_;
     ResampCore resamp_;
     SpectrumCore spec_, zoom_;
     float2 *d_stage_in_ = nullptr;

@@ -123,6 +123,7 @@ Receiver::~Receiver()
     if (d_zoom) (void)hipFree(d_zoom);
     if (map_ev_) (void)hipEventDestroy(map_ev_);
     agc_.release(); resamp_.release(); cond_.release(); anf_.release();
+    morse_.release();
     if (d_audio_rs) (void)hipFree(d_audio_rs);
     if (h_gate_) (void)hipHostFree(h_gate_);
     if (d_squelch) (void)hipFree(d_squelch);
@@ -170,7 +171,52 @@ int Receiver::set_mode(uint32_t ch, int mode)
         agc_.set_muted(ch, mode == PEBBLEGPU_DM_NONE);
         anf_.set_muted(ch, mode == PEBBLEGPU_DM_NONE);
     }
+    // m_iDigitalModem->setDemodMode(_demodMode), receiver.cpp:653-654 (the dmNONE return, :968-971, leaves the channel's modem alone)
+    if (morse_.C) {
+        PG_HIP(hipSetDevice(device));
+        if (int rc = morse_.set_mode(ch, mode)) return rc;
+    }
     return 0;
+}
+
+int Receiver::set_morse(uint32_t ch, bool on)
+{
+    if (ch >= C) return fail(PEBBLEGPU_E_INVALID, "channel %u out of range", ch);
+    if (wfm) return fail(PEBBLEGPU_E_UNSUPPORTED, "the digital-modem hook is on the narrow branch (receiver.cpp:977-980): a WFM receiver has none");
+    std::lock_guard<std::mutex> g(mu_);
+    if (on && bank_gate_)
+        return fail(PEBBLEGPU_E_UNSUPPORTED, "the per-channel squelch of a bank and the Morse modem do not run together (DESIGN.md section 7)");
+    PG_HIP(hipSetDevice(device));
+    if (!morse_.C) {
+        if (!on) return 0;
+        const long long per_sf = (long long)(superframe / chain.total);
+        int rc = morse_.init(C, demod_rate_int, (long long)max_sf * per_sf, false);
+        if (!rc) rc = morse_.check(per_sf);  // every call is a whole number of super-frames: one passing is all passing
+        if (rc) { morse_.release(); return rc; }
+    }
+    touched_ = true;
+    return morse_.enable(ch, on, ctl_[ch].mode);  // Receiver::setDigitalModem -> Morse::setSampleRate(m_demodSampleRate, m_demodFrames)
+}
+
+// (the getters take the receiver's lock like the setters: a host may read them from another thread than the one that calls process,
+// whose calls drain the same logs when they could wrap)
+int Receiver::morse_events(uint32_t ch, MorseEvent *ev, uint32_t cap, uint32_t *n)
+{
+    if (n) *n = 0;
+    if (ch >= C) return fail(PEBBLEGPU_E_INVALID, "channel %u out of range", ch);
+    std::lock_guard<std::mutex> g(mu_);
+    if (!morse_.C) return 0;
+    PG_HIP(hipSetDevice(device));
+    return morse_.events(ch, ev, cap, n);
+}
+
+int Receiver::morse_status(uint32_t ch, MorseStatus *st)
+{
+    if (ch >= C) return fail(PEBBLEGPU_E_INVALID, "channel %u out of range", ch);
+    std::lock_guard<std::mutex> g(mu_);
+    if (!morse_.C) return fail(PEBBLEGPU_E_INVALID, "the Morse modem of channel %u is off", ch);
+    PG_HIP(hipSetDevice(device));
+    return morse_.status(ch, st);
 }
 
 int Receiver::enable_smeter(bool on)
@@ -212,10 +258,16 @@ int Receiver::set_squelch(uint32_t ch, double squelch_db)
             if (squelch_db <= -120.0) return 0;  // "never closes": nothing to set up
             return fail(PEBBLEGPU_E_UNSUPPORTED, "the per-channel gate of a bank is built for the narrow branch (a WFM receiver gates as one channel, one super-frame per call)");
         }
+        const char *both = "the per-channel squelch of a bank and the Morse modem do not run together (DESIGN.md section 7)";
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            if (squelch_db > -120.0 && morse_.any()) return fail(PEBBLEGPU_E_UNSUPPORTED, "%s", both);
+        }
         if (squelch_db > -120.0) {
             if (int rc = enable_smeter(true)) return rc;
         }
         std::lock_guard<std::mutex> g(mu_);
+        if (squelch_db > -120.0 && morse_.any()) return fail(PEBBLEGPU_E_UNSUPPORTED, "%s", both);  // (a set_morse between the two locks)
         touched_ = true;  // the next call joins its two pipelines before the change is applied
         PG_HIP(hipSetDevice(device));
         if (squelch_.empty()) squelch_.assign(C, -120.f);
@@ -591,6 +643,8 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
             if (ctl_[ch].mode == PEBBLEGPU_DM_NONE) PG_HIP(hipMemsetAsync(audio.data((int)ch), 0, sizeof(float2) * (size_t)nd, cs));
     } else if (!wfm) {
         if (int rc = anf_.run(cs, audio.data(), audio.pitch, nd)) return rc;  // NoiseFilter::ProcessBlock, receiver.cpp:974
+        // m_iDigitalModem->processBlock, receiver.cpp:979-980: the Morse modem reads the rows before the AGC overwrites them
+        if (morse_.any()) { if (int rc = morse_.run(cs, audio.data(), audio.pitch, nd)) return rc; }
         if (int rc = agc_.run(cs, audio.data(), audio.pitch, nd)) return rc;  // AGC::processBlock, receiver.cpp:983
         // Demod::processBlock, receiver.cpp:987: AM channels are demodulated in place; every other narrow mode returns its input
         am_.defer_tail = bank_pipe;  // (a two-stage call's tail launch carries the AM demodulator's history refresh: one launch fewer)

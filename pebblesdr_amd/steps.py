@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import check, load_library, screen_map
+from .binding import MorseReport, _morse_events, check, load_library, screen_map
 
 _dp = C.POINTER(C.c_double)
 
@@ -207,3 +207,48 @@ class Spectrum(_Step):
         out = np.empty(max(0, int(xPixels)), dtype=np.int32)
         check(self.L, self.L.pebblegpu_spectrum_map_to_screen(self.h, C.byref(m), out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
+
+
+class Morse(_Step):
+    """The Morse digital modem (plugins/MorseDigitalModem, DigitalModemInterface): Morse() + setSampleRate(sampleRate, sampleCount)"""
+    _destroy = "pebblegpu_morse_destroy"
+
+    def __init__(self, sample_rate, sample_count, device=0, lib=None, keep_results=False):
+        self.L = lib or load_library()
+        self.n = int(sample_count)
+        self.h = C.c_void_p()
+        check(self.L, self.L.pebblegpu_morse_create(device, int(sample_rate), self.n, C.byref(self.h)))
+        if keep_results:
+            check(self.L, self.L.pebblegpu_morse_keep_results(self.h, 1))
+
+    def setSampleRate(self, sample_rate, sample_count):
+        """Morse::setSampleRate again: a fresh decoder in dmCWL from the current WPM estimate"""
+        check(self.L, self.L.pebblegpu_morse_set_sample_rate(self.h, int(sample_rate), int(sample_count)))
+        self.n = int(sample_count)
+
+    def setDemodMode(self, mode):
+        check(self.L, self.L.pebblegpu_morse_set_demod_mode(self.h, int(mode)))
+
+    def processBlock(self, x):
+        """one frame of sampleCount samples; returns `in` unchanged, as the reference does"""
+        xs = _c128(x)
+        assert len(xs) == self.n, "processBlock takes frames of %d samples" % self.n
+        check(self.L, self.L.pebblegpu_morse_process(self.h, xs.ctypes.data_as(_dp)))
+        return x
+
+    def events(self):
+        """events since the last read -> MORSE_EVENT records (sample, token, kind)"""
+        return _morse_events(self.L, self.L.pebblegpu_morse_events, self.h)
+
+    def status(self):
+        st = MorseReport()
+        check(self.L, self.L.pebblegpu_morse_status(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def results(self, cap=1 << 20):
+        """per Goertzel result since the last read: (m_power, above-threshold decision); needs keep_results"""
+        p = np.zeros(cap, dtype=np.float64)
+        t = np.zeros(cap, dtype=np.uint8)
+        n = C.c_uint32(0)
+        check(self.L, self.L.pebblegpu_morse_results(self.h, p.ctypes.data_as(_dp), t.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        return p[:n.value].copy(), t[:n.value].astype(bool)
