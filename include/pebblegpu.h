@@ -247,6 +247,32 @@ const void *pebblegpu_receiver_audio(const pebblegpu_receiver *rx, uint64_t *sam
 const void *pebblegpu_receiver_spectrum(const pebblegpu_receiver *rx, uint64_t *frames_per_stream);
 /* the zoomed (hi-res) spectra of the last call: [channel][frames_per_channel][bins] float dB, -f..+f at the demodulator rate */
 const void *pebblegpu_receiver_zoom_spectrum(const pebblegpu_receiver *rx, uint64_t *frames_per_channel, uint32_t *bins);
+/* SignalSpectrum::setUpdatesPerSec (application/signalspectrum.cpp:124-135; SpectrumWidget::updatesPerSecChanged calls it): the gate
+ * in front of SignalSpectrum::unprocessed and ::zoomed (:63-113).  Open by default (PEBBLEGPU_SPECTRUM_EVERY_FRAME: every frame gets a
+ * spectrum, as before this setter existed).  0: no unprocessed and no zoomed spectrum is computed (m_updatesPerSec == 0).  A rate > 0:
+ * the reference's rule with its wall clock replaced by the stream's own sample clock, so that the selection does not depend on how fast
+ * or in what call sizes the host feeds the library: period_ms = 1000 / updates_per_sec (integer division); frames are numbered from the
+ * handle's creation, across calls; the frame that starts the timer gets no spectrum; after that frame f gets one iff
+ * (f - f_last) * frames_per_buffer * 1000 / sample_rate >= period_ms (integer arithmetic, the rate in whole Hz) and then becomes f_last.
+ * Changing the rate changes the period only, the timer runs on: coming from the default it counts from the last frame of the previous
+ * call (or is started by the first frame), coming from 0 it has kept its f_last.  The zoomed spectrum has a timer of its own with the
+ * same period over the decimated frames of each channel (frames_per_buffer * 1000 / info.demod_rate_int per frame).
+ * With a gate set:
+ *   - the frame list is worked out on the host before anything is queued (no read-back, no synchronisation);
+ *   - pebblegpu_receiver_spectrum / _zoom_spectrum return the COMPUTED rows only, compact: [stream][n_selected][bins], the frame count
+ *     they report is n_selected (possibly 0); pebblegpu_receiver_spectrum_frames says which frames they are; the map functions and the
+ *     S-meter index these rows (after a call that made no unprocessed spectrum pebblegpu_receiver_map_spectrum maps the latest one made
+ *     before it, as frame 0: what the display still shows); a frame's spectrum is averaged with the previous COMPUTED frame's (m_fftAmplitude, fft.cpp:378-386),
+ *     across calls;
+ *   - the squelch reads avgDb of the latest computed spectrum at or before the super-frame's last raw frame, from an earlier call if
+ *     need be (getUnprocessed(), receiver.cpp:891-897, 959-965); before the first spectrum the gate stays open;
+ *   - audio is the same on every route. */
+#define PEBBLEGPU_SPECTRUM_EVERY_FRAME (-1)
+int pebblegpu_set_spectrum_updates(pebblegpu_receiver *rx, int updates_per_sec);
+/* which frames of the last call got an unprocessed (zoomed != 0: a zoomed) spectrum: indices relative to the call's first frame,
+ * ascending, row i of the spectrum buffer belongs to idx[i].  *n entries are written (every frame of the call without a gate);
+ * PEBBLEGPU_E_SIZE when cap is too small.  Known the moment the process call returns. */
+int pebblegpu_receiver_spectrum_frames(const pebblegpu_receiver *rx, int zoomed, uint32_t *idx, uint32_t cap, uint32_t *n);
 
 /* ------------------------------------------------------------------------------------------------
  * Spectrum to display pixels: FFT::mapFFTToScreen (pebblelib/fft.cpp:400-534), the call SpectrumWidget makes for every plot and
@@ -321,7 +347,8 @@ int pebblegpu_set_noise_filter(pebblegpu_receiver *rx, uint32_t channel, int on)
  * frame's unprocessed spectrum, per channel: float4 (peakDb, avgDb, snrDb, floorDb) at [channel * pitch + frame].  The
  * band window is the channel's band-pass (+-100 kHz in a WFM bank) around its mixer frequency.  avgDb is the value the
  * reference's squelch compares with m_squelchDb (receiver.cpp:893-897, 962-965); see pebblegpu_set_squelch.
- * Needs spectrum_bins != 0.  The reference's 10-per-second update timer is forced open: every frame is measured. */
+ * Needs spectrum_bins != 0.  The reference's 10-per-second update timer is open by default: every frame is measured.  With
+ * pebblegpu_set_spectrum_updates: one float4 per COMPUTED row, indexed like the rows. */
 int pebblegpu_receiver_enable_signal_strength(pebblegpu_receiver *rx, int on);
 const void *pebblegpu_receiver_signal_strength(const pebblegpu_receiver *rx, uint64_t *frames, uint64_t *pitch_frames);
 /* Squelch (Receiver::squelchChanged, receiver.cpp:704-707; the gate at :893-897 for WFM and :962-965 otherwise).  Once a
@@ -351,6 +378,12 @@ int pebblegpu_receiver_synchronize(pebblegpu_receiver *rx);
  * spectrum_db (may be NULL) receives this frame's dB spectrum (bins doubles). */
 int pebblegpu_process_iq(pebblegpu_receiver *rx, const double *iq, uint16_t n, double *audio,
                          uint32_t *n_audio, double *spectrum_db);
+/* The same for a host that has called pebblegpu_set_spectrum_updates: *spectrum_updated (may be NULL) is 1 when this frame got a
+ * spectrum -- spectrum_db was written -- and 0 when the update timer skipped it: spectrum_db is then left untouched, so a host that
+ * passes the same buffer every frame keeps the last computed spectrum in it, as SignalSpectrum::getUnprocessed does.  Without a gate
+ * every frame reports 1 (when spectrum_db was asked for).  pebblegpu_process_iq itself leaves spectrum_db untouched in the same way. */
+int pebblegpu_process_iq_updates(pebblegpu_receiver *rx, const double *iq, uint16_t n, double *audio,
+                                 uint32_t *n_audio, double *spectrum_db, uint32_t *spectrum_updated);
 
 /* ------------------------------------------------------------------------------------------------
  * Stream bank: S independent full-rate IQ streams, each through the overlap-save band-pass

@@ -438,13 +438,18 @@ public:
     {
         if (!h) return;
         uint32_t na = 0;
-        status = report("process_iq", pebblegpu_process_iq(h, reinterpret_cast<const double *>(in), numSamples, reinterpret_cast<double *>(audio.data()), &na,
-                                                          spectrum.empty() ? nullptr : spectrum.data()));
+        // (behind setUpdatesPerSec a frame the timer skips leaves `spectrum` as it is: the last computed one, as getUnprocessed() holds it)
+        status = report("process_iq", pebblegpu_process_iq_updates(h, reinterpret_cast<const double *>(in), numSamples, reinterpret_cast<double *>(audio.data()), &na,
+                                                                  spectrum.empty() ? nullptr : spectrum.data(), &specUpdated));
         if (status == 0 && na > 0 && cb) {
             for (uint32_t off = 0; off < na; off += n) cb(audio.data() + off, (uint16_t)((na - off) < n ? (na - off) : n));  // processAudioData, receiver.cpp:1007
         }
     }
     const std::vector<double> &unprocessedSpectrum() const { return spectrum; }  // SignalSpectrum::getUnprocessed
+    // SignalSpectrum::setUpdatesPerSec (signalspectrum.cpp:124-135; bound to SpectrumWidget::updatesPerSecChanged): spectra per second
+    // on the stream's sample clock, 0 for none; PEBBLEGPU_SPECTRUM_EVERY_FRAME (the library's default) for one per frame
+    void setUpdatesPerSec(int updatesPerSec) { if (h) status = report("set_spectrum_updates", pebblegpu_set_spectrum_updates(h, updatesPerSec)); }
+    bool spectrumUpdated() const { return specUpdated != 0; }  // the last processIQData made a spectrum (newFftData would have been emitted)
     // bool SignalSpectrum::mapFFTToScreen(qint32 maxHeight, qint32 maxWidth, double maxdB, double mindB, qint32 startFreq,
     // qint32 stopFreq, qint32 *outBuf), signalspectrum.cpp:137-149: the last frame's unprocessed spectrum mapped on the device
     // (pebblegpu_receiver_map_spectrum), maxWidth values into outBuf.  Returns false, as the reference does.
@@ -482,6 +487,7 @@ private:
     CB_ProcessAudioData cb;
     std::vector<CPX> audio;
     std::vector<double> spectrum;
+    uint32_t specUpdated = 0;
     uint32_t demodRate = 0;
     int status = 0;
     int dev;

@@ -7,7 +7,7 @@ library and a HIP device and fails loudly otherwise.
 """
 from .binding import (  # noqa: F401
     PebbleGpuError, load_library, library_path, ReceiverBank, StreamBank, DeviceBuffer, ScreenMap, screen_map,
-    MORSE_EVENT, MORSE_CHAR, MORSE_WORD_SPACE, morse_token_to_dotdash,
+    MORSE_EVENT, MORSE_CHAR, MORSE_WORD_SPACE, morse_token_to_dotdash, SPECTRUM_EVERY_FRAME,
     DM_AM, DM_SAM, DM_FMN, DM_FMM, DM_FMS, DM_DSB, DM_LSB, DM_USB, DM_CWL, DM_CWU, DM_DIGL, DM_DIGU, DM_NONE,
 )
 from .steps import Mixer, Decimator, DownConvert, FastFIR, Demod, Spectrum, Morse  # noqa: F401

@@ -37,7 +37,10 @@ SYMBOLS = [
     "pebblegpu_morse_create", "pebblegpu_morse_destroy", "pebblegpu_morse_set_demod_mode", "pebblegpu_morse_process",
     "pebblegpu_morse_events", "pebblegpu_morse_status", "pebblegpu_morse_results", "pebblegpu_morse_set_sample_rate",
     "pebblegpu_morse_keep_results",
+    "pebblegpu_set_spectrum_updates", "pebblegpu_receiver_spectrum_frames", "pebblegpu_process_iq_updates",
 ]
+
+SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
 
 
 class PebbleGpuError(RuntimeError):
@@ -190,6 +193,9 @@ def _declare(L):
     L.pebblegpu_receiver_signal_strength.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.pebblegpu_receiver_synchronize.argtypes = [vp]
     L.pebblegpu_process_iq.argtypes = [vp, dp, C.c_uint16, dp, C.POINTER(u32), dp]
+    L.pebblegpu_process_iq_updates.argtypes = [vp, dp, C.c_uint16, dp, C.POINTER(u32), dp, C.POINTER(u32)]
+    L.pebblegpu_set_spectrum_updates.argtypes = [vp, i32]
+    L.pebblegpu_receiver_spectrum_frames.argtypes = [vp, i32, C.POINTER(u32), u32, C.POINTER(u32)]
     L.pebblegpu_streambank_create.argtypes = [C.POINTER(StreamBankConfig), C.POINTER(vp)]
     L.pebblegpu_streambank_destroy.argtypes = [vp]
     L.pebblegpu_streambank_set_bandpass.argtypes = [vp, u32, dbl, dbl]
@@ -446,6 +452,22 @@ class ReceiverBank:
     def set_agc(self, ch, agc_mode, threshold):
         check(self.L, self.L.pebblegpu_set_agc(self.h, ch, int(agc_mode), int(threshold)))
 
+    def set_spectrum_updates(self, updates_per_sec):
+        """SignalSpectrum::setUpdatesPerSec on the stream's sample clock: -1 every frame (default), 0 none, else spectra per second"""
+        check(self.L, self.L.pebblegpu_set_spectrum_updates(self.h, int(updates_per_sec)))
+
+    def spectrum_frames(self, zoomed=False):
+        """-> uint32 [n]: which frames of the last call (relative to its first) the rows of spectrum() / zoom_spectrum() belong to"""
+        f = C.c_uint64()
+        if zoomed:
+            self.L.pebblegpu_receiver_zoom_spectrum(self.h, C.byref(f), None)
+        else:
+            self.L.pebblegpu_receiver_spectrum(self.h, C.byref(f))
+        idx = np.zeros(max(1, int(f.value)), dtype=np.uint32)
+        n = C.c_uint32()
+        check(self.L, self.L.pebblegpu_receiver_spectrum_frames(self.h, 1 if zoomed else 0, idx.ctypes.data_as(C.POINTER(C.c_uint32)), len(idx), C.byref(n)))
+        return idx[: n.value].copy()
+
     def process_device(self, dptr, n_samples):
         check(self.L, self.L.pebblegpu_receiver_process(self.h, C.c_void_p(dptr), int(n_samples)))
 
@@ -478,7 +500,7 @@ class ReceiverBank:
         p = self.L.pebblegpu_receiver_signal_strength(self.h, C.byref(f), C.byref(pitch))
         self.synchronize()
         out = np.empty((self.n_channels, int(f.value), 4), dtype=np.float32)
-        for c in range(self.n_channels):
+        for c in range(self.n_channels if out.size else 0):
             check(self.L, self.L.pebblegpu_memcpy_d2h(self.device, out[c].ctypes.data_as(C.c_void_p), C.c_void_p(p + c * int(pitch.value) * 16), out[c].nbytes))
         return out
 
@@ -516,7 +538,8 @@ class ReceiverBank:
         frames = int(n.value)
         self.synchronize()
         out = np.empty((self.n_streams, frames, self.bins), dtype=np.float32)
-        check(self.L, self.L.pebblegpu_memcpy_d2h(self.device, out.ctypes.data_as(C.c_void_p), C.c_void_p(p), out.nbytes))
+        if out.size:  # (a gated call may have computed no row)
+            check(self.L, self.L.pebblegpu_memcpy_d2h(self.device, out.ctypes.data_as(C.c_void_p), C.c_void_p(p), out.nbytes))
         return out
 
     def zoom_spectrum(self):
@@ -598,6 +621,18 @@ class ReceiverBank:
         check(self.L, self.L.pebblegpu_process_iq(self.h, x.ctypes.data_as(dp), len(x), audio.ctypes.data_as(dp), C.byref(n_audio),
                                                  spec.ctypes.data_as(dp) if spec is not None else None))
         return audio[: n_audio.value].copy(), spec
+
+    def process_iq_updates(self, frame, spectrum):
+        """pebblegpu_process_iq_updates: `spectrum` (float64 [bins]) is the host's own buffer, overwritten only when the frame got a
+        spectrum.  -> (audio complex128 [n_audio], updated)"""
+        x = np.ascontiguousarray(frame, dtype=np.complex128)
+        dp = C.POINTER(C.c_double)
+        assert spectrum.dtype == np.float64 and spectrum.flags.c_contiguous and spectrum.size == self.bins
+        audio = np.empty(max(self.nf, self.superframe // self.D), dtype=np.complex128)
+        n_audio, upd = C.c_uint32(), C.c_uint32()
+        check(self.L, self.L.pebblegpu_process_iq_updates(self.h, x.ctypes.data_as(dp), len(x), audio.ctypes.data_as(dp), C.byref(n_audio),
+                                                         spectrum.ctypes.data_as(dp), C.byref(upd)))
+        return audio[: n_audio.value].copy(), bool(upd.value)
 
 
 class StreamBank:

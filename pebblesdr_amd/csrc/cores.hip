@@ -1567,6 +1567,22 @@ int run_gate_eval(hipStream_t s, const float4 *d_smeter, long long smeter_pitch,
     PG_HIP(hipGetLastError());
     return 0;
 }
+// rows[j], j < k: the compact S-meter row super-frame j reads, kGateRowCarried or kGateRowNone (k_gate_eval_rows)
+int run_gate_eval_rows(hipStream_t s, const float4 *d_smeter, long long smeter_pitch, const float4 *d_carried, const int *rows, int k, const float *d_squelch,
+                       unsigned char *d_gate, int stride, uint32_t channels)
+{
+    for (int j0 = 0; j0 < k; j0 += kListMax) {
+        GateRows gr;
+        memset(&gr, 0, sizeof(gr));
+        gr.n = k - j0 < kListMax ? k - j0 : kListMax;
+        gr.j0 = j0;
+        for (int j = 0; j < gr.n; j++) gr.row[j] = rows[j0 + j];
+        launch(k_gate_eval_rows, dim3((unsigned)((channels * (unsigned)gr.n + 255) / 256)), dim3(256), s, d_smeter, smeter_pitch, d_carried, d_squelch, d_gate, stride,
+               (int)channels, gr);
+    }
+    PG_HIP(hipGetLastError());
+    return 0;
+}
 int run_gate_zero(hipStream_t s, float2 *audio, long long pitch, long long spf, const unsigned char *d_gate, int stride, uint32_t channels, int k)
 {
     launch(k_gate_zero, dim3((unsigned)((spf + 1023) / 1024), channels, (unsigned)k), dim3(256), s, audio, pitch, spf, d_gate, stride);
@@ -2001,6 +2017,12 @@ void SpectrumCore::release()
     void *p[] = {d_window, d_btab, d_prev[0], d_prev[1], d_tw_nf, d_Y, d_btab128, d_tw128, d_ftab, d_twM};
     d_twM = nullptr;
     for (void *q : p) if (q) (void)hipFree(q);
+    if (list_owned) {
+        if (d_list_ftab) (void)hipFree(d_list_ftab);
+        if (d_list_tw128) (void)hipFree(d_list_tw128);
+    }
+    d_list_ftab = d_list_tw128 = nullptr;
+    list_owned = false;
     d_ftab = nullptr;
     d_window = nullptr; d_btab = nullptr; d_prev[0] = d_prev[1] = nullptr; d_tw_nf = nullptr; d_Y = nullptr; d_btab128 = d_tw128 = nullptr;
     y_cap = 0;
@@ -2200,6 +2222,76 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
     if (bins == 2048) launch(k_spectrum_1to1, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_tw_nf, pin, pout, sp);
     else if (bins == 4096) launch(k_spectrum<2>, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab, (const float2 *)d_tw_nf, pin, pout, sp);
     else return fail(PEBBLEGPU_E_UNSUPPORTED, "no spectrum kernel for %u bins", bins);
+    parity ^= 1;
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// The tables of k_spectrum_list_q128 for a plan whose own kernels use others (4096 and 8192 bins); synchronous, once, from the setter
+int SpectrumCore::init_list()
+{
+    if (big) return fail(PEBBLEGPU_E_UNSUPPORTED, "the 65536-point spectrum has no frame-list transform");
+    if (any || d_list_ftab) return 0;
+    if (per_q) {  // k_spectrum_q128's own
+        d_list_ftab = d_ftab;
+        d_list_tw128 = d_tw128;
+        return 0;
+    }
+    const uint32_t zp = bins / nf;
+    std::vector<float2> ft((size_t)zp * nf);
+    for (uint32_t q = 0; q < zp; q++)
+        for (uint32_t n = 0; n < nf; n++) {
+            const double a = -design::kTwoPi * (double)(((uint64_t)n * q) % bins) / (double)bins;
+            ft[(size_t)q * nf + n] = make_float2((float)((double)h_window[n] * std::cos(a)), (float)((double)h_window[n] * std::sin(a)));
+        }
+    PG_HIP(hipMalloc((void **)&d_list_ftab, sizeof(float2) * ft.size()));
+    PG_HIP(hipMemcpy(d_list_ftab, ft.data(), sizeof(float2) * ft.size(), hipMemcpyHostToDevice));
+    list_owned = true;
+    if (int rc = make_twiddles_t128(&d_list_tw128)) return rc;
+    return 0;
+}
+// FFT::fftSpectrum of the listed frames only (ascending, relative to d_in's first frame), rows compact in d_out: [stream][n_sel][bins]
+int SpectrumCore::run_list(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw)
+{
+    if (n_sel <= 0) return 0;  // nothing is queued and the carried amplitudes stay
+    if (big) return fail(PEBBLEGPU_E_UNSUPPORTED, "the 65536-point spectrum has no frame-list transform");
+    if (any && raw) return fail(PEBBLEGPU_E_INVALID, "the general display transform takes float2 input");
+    if (!any && !d_list_ftab) return fail(PEBBLEGPU_E_INVALID, "the frame-list transform was not set up");
+    SpectrumParams sp;
+    sp.in_pitch = in_pitch;
+    sp.n_frames = n_sel;
+    sp.frames_per_group = 1;
+    sp.scale = scale;
+    sp.out_pitch = n_sel * (long long)bins;
+    const RawSrc rs = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
+    const float *pin = d_prev[parity];
+    float *pout = d_prev[parity ^ 1];
+    for (long long r0 = 0; r0 < n_sel; r0 += kListMax) {
+        FrameList fl;
+        memset(&fl, 0, sizeof(fl));
+        fl.n = (int)(n_sel - r0 < kListMax ? n_sel - r0 : kListMax);
+        fl.row0 = (int)r0;
+        fl.pred = r0 ? (long long)idx[r0 - 1] : -1;
+        fl.last = r0 + fl.n == n_sel ? 1 : 0;
+        for (int i = 0; i < fl.n; i++) fl.idx[i] = idx[r0 + i];
+        if (any) {
+            AnySpecParams ap;
+            ap.n_in = (int)nf;
+            ap.frame = (int)nf;
+            ap.M = any_M;
+            ap.logM = any_logM;
+            ap.zp_log2 = any_zp_log2;
+            ap.windowed = 1;
+            launch_lds(k_spectrum_list_any, dim3((unsigned)fl.n << any_zp_log2, S), dim3(256), sizeof(float2) * (size_t)any_M, s, d_in, d_out, (const float *)d_window,
+                       (const float2 *)d_twM, pin, pout, sp, ap, fl);
+        } else {
+            int zl = 0;
+            while (((uint32_t)nf << zl) < bins) zl++;
+            const dim3 grid((unsigned)fl.n << zl, S), block(128);
+            if (raw) launch(k_spectrum_list_q128<true>, grid, block, s, d_in, d_out, (const float2 *)d_list_ftab, (const float2 *)d_list_tw128, pin, pout, sp, zl, fl, rs);
+            else launch(k_spectrum_list_q128<false>, grid, block, s, d_in, d_out, (const float2 *)d_list_ftab, (const float2 *)d_list_tw128, pin, pout, sp, zl, fl, rs);
+        }
+    }
     parity ^= 1;
     PG_HIP(hipGetLastError());
     return 0;

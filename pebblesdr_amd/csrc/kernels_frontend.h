@@ -843,6 +843,21 @@ static __global__ __launch_bounds__(256) void k_gate_eval(const float4 *__restri
     const int c = i / k, j = i % k;
     open[(long long)c * stride + j] = smeter[(long long)c * smeter_pitch + (long long)(j + 1) * frames_per_sf - 1].y < squelch_db[c] ? 0 : 1;
 }
+// The same under the spectrum's update timer: the super-frame reads the latest COMPUTED spectrum at or before its last raw frame -- a
+// compact S-meter row of this call (rows.row[j] >= 0), the row carried from an earlier call (carried[c]), or none yet: the gate stays open
+static __global__ __launch_bounds__(256) void k_gate_eval_rows(const float4 *__restrict__ smeter, long long smeter_pitch, const float4 *__restrict__ carried,
+                                                               const float *__restrict__ squelch_db, unsigned char *__restrict__ open, int stride, int n_chan,
+                                                               GateRows rows)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_chan * rows.n) return;
+    const int c = i / rows.n, j = i % rows.n;
+    const int r = rows.row[j];
+    unsigned char o = 1;
+    if (r >= 0) o = smeter[(long long)c * smeter_pitch + r].y < squelch_db[c] ? 0 : 1;
+    else if (r == kGateRowCarried) o = carried[c].y < squelch_db[c] ? 0 : 1;
+    open[(long long)c * stride + rows.j0 + j] = o;
+}
 static __global__ __launch_bounds__(256) void k_gate_zero(float2 *__restrict__ audio, long long pitch, long long spf, const unsigned char *__restrict__ open, int stride)
 {
     const int c = blockIdx.y, j = blockIdx.z;

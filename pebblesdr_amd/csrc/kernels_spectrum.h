@@ -1210,6 +1210,33 @@ struct AnySpecParams {
     int zp_log2;     // bins = M << zp_log2
     int windowed;    // multiply by window[n] (numSamples == samplesPerBuffer)
 };
+// one frame x into buf (M points of LDS, 256 work-items): window, pre-twiddle W_bins^{n q}, bit-reversed load, log2 M radix-2 passes;
+// ends behind a barrier with X[ZP k + q] in buf[k] (shared by k_spectrum_any and k_spectrum_list_any)
+__device__ __forceinline__ void any_transform(float2 *buf, const float2 *__restrict__ x, const float *__restrict__ window, const float2 *__restrict__ twM,
+                                              const AnySpecParams &ap, int q, int tid)
+{
+    const int M = ap.M, logM = ap.logM, bins = M << ap.zp_log2;
+    for (int i = tid; i < M; i += 256) {
+        float2 v = make_float2(0.f, 0.f);
+        if (i < ap.n_in) {
+            v = x[i];
+            if (ap.windowed) v = cscale(v, window[i]);
+            if (q) v = cmul(cis_cycles(-(double)(((long long)i * q) & (bins - 1)) / (double)bins), v);
+        }
+        buf[__brev((unsigned)i) >> (32 - logM)] = v;
+    }
+    __syncthreads();
+    for (int st = 1; st <= logM; st++) {
+        const int half = 1 << (st - 1);
+        for (int b = tid; b < (M >> 1); b += 256) {
+            const int j = b & (half - 1), i0 = ((b >> (st - 1)) << st) + j, i1 = i0 + half;
+            const float2 t = cmul(twM[j << (logM - st)], buf[i1]), a = buf[i0];
+            buf[i0] = cadd(a, t);
+            buf[i1] = csub(a, t);
+        }
+        __syncthreads();
+    }
+}
 static __global__ __launch_bounds__(256) void k_spectrum_any(const float2 *__restrict__ in, float *__restrict__ out, const float *__restrict__ window,
                                                             const float2 *__restrict__ twM, const float *__restrict__ prev_in, float *__restrict__ prev_out,
                                                             SpectrumParams sp, AnySpecParams ap)
@@ -1218,7 +1245,7 @@ static __global__ __launch_bounds__(256) void k_spectrum_any(const float2 *__res
     constexpr int EMAX = 64;  // M / 256 <= 64 points per work-item
     const int tid = threadIdx.x, s = blockIdx.y;
     const int ZP = 1 << ap.zp_log2, q = blockIdx.x & (ZP - 1);
-    const int M = ap.M, logM = ap.logM, bins = M << ap.zp_log2;
+    const int M = ap.M, bins = M << ap.zp_log2;
     const int E = M >= 256 ? M >> 8 : 1;
     const int G = sp.frames_per_group;
     const long long f0 = (long long)(blockIdx.x >> ap.zp_log2) * G;
@@ -1235,27 +1262,7 @@ static __global__ __launch_bounds__(256) void k_spectrum_any(const float2 *__res
                 if (m < E && tid + 256 * m < M) pa[m] = prev_in[(long long)s * bins + ((tid + 256 * m) << ap.zp_log2) + q];
             continue;
         }
-        const float2 *x = in + (long long)s * sp.in_pitch + f * ap.frame;
-        for (int i = tid; i < M; i += 256) {
-            float2 v = make_float2(0.f, 0.f);
-            if (i < ap.n_in) {
-                v = x[i];
-                if (ap.windowed) v = cscale(v, window[i]);
-                if (q) v = cmul(cis_cycles(-(double)(((long long)i * q) & (bins - 1)) / (double)bins), v);
-            }
-            buf[__brev((unsigned)i) >> (32 - logM)] = v;
-        }
-        __syncthreads();
-        for (int st = 1; st <= logM; st++) {
-            const int half = 1 << (st - 1);
-            for (int b = tid; b < (M >> 1); b += 256) {
-                const int j = b & (half - 1), i0 = ((b >> (st - 1)) << st) + j, i1 = i0 + half;
-                const float2 t = cmul(twM[j << (logM - st)], buf[i1]), a = buf[i0];
-                buf[i0] = cadd(a, t);
-                buf[i1] = csub(a, t);
-            }
-            __syncthreads();
-        }
+        any_transform(buf, in + (long long)s * sp.in_pitch + f * ap.frame, window, twM, ap, q, tid);
         float *yf = out + (long long)s * sp.out_pitch + f * (long long)bins;
 #pragma unroll
         for (int m = 0; m < EMAX; m++) {
@@ -1275,6 +1282,123 @@ static __global__ __launch_bounds__(256) void k_spectrum_any(const float2 *__res
 #pragma unroll
             for (int m = 0; m < EMAX; m++)
                 if (m < E && tid + 256 * m < M) prev_out[(long long)s * bins + ((tid + 256 * m) << ap.zp_log2) + q] = pa[m];
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The display transform over a frame LIST: the frames SignalSpectrum's update timer lets through (signalspectrum.cpp:63-113), a
+// handful per call and far apart -- often fewer than there are CUs.  The chain kernels above walk consecutive frames and take
+// |X_prev| from the frame in front; here the frame in front is the previous LISTED frame (fft.cpp:378-386 averages with
+// m_fftAmplitude, the last frame that was transformed), or the carried buffer for the call's first.
+// One workgroup per (listed frame, q, stream).  It recomputes its predecessor's amplitudes instead of reading them from a scratch row:
+// the transforms of a list stay independent (no ordering between workgroups, no second launch, no buffer sized by the list), and
+// twice the arithmetic of a dozen transforms on 256 CUs is microseconds beside a call that streams hundreds of megabytes.
+// Rows come out compact, [stream][n_selected][bins]; the call's last listed frame leaves its amplitudes in the carried buffer.
+//   k_spectrum_list_q128: 2048-sample frames, bins = ZP * 2048 (ZP = 1 .. 16) -- k_spectrum_q128's transform (fft2048_t128, the
+//     per-point factor table F[q][n] = w[n] W_bins^{n q}); RAW: the frames are read in the device's own sample format (RawSrc).
+//     grid (n * ZP, S), block 128.
+//   k_spectrum_list_any: every other frame length -- k_spectrum_any's transform.  grid (n * ZP, S), block 256, LDS M * 8 bytes.
+// ------------------------------------------------------------------------------------------------
+template <bool RAW>
+static __global__ __launch_bounds__(128, 4) void k_spectrum_list_q128(const float2 *__restrict__ in, float *__restrict__ out,
+                                                                      const float2 *__restrict__ ftab, const float2 *__restrict__ tw128,
+                                                                      const float *__restrict__ prev_in, float *__restrict__ prev_out,
+                                                                      SpectrumParams sp, int zp_log2, FrameList fl, RawSrc raw)
+{
+    constexpr int NF = 2048, E = 16;
+    __shared__ float2 lds[FftLds<NF>::kSlots];
+    const int t0 = threadIdx.x, s = blockIdx.y;
+    const int ZP = 1 << zp_log2, BINS = NF << zp_log2;
+    const int q = blockIdx.x & (ZP - 1), li = blockIdx.x >> zp_log2;
+    if (li >= fl.n) return;  // workgroup-uniform
+    const float db_off = 6.02059991327962f * __builtin_amdgcn_logf(0.5f * sp.scale);
+    float pa[E];
+#pragma unroll
+    for (int m = 0; m < E; m++) pa[m] = 0.f;
+    for (int it = -1; it < 1; it++) {
+        const long long f = it < 0 ? (li > 0 ? (long long)fl.idx[li - 1] : fl.pred) : (long long)fl.idx[li];
+        int t = t0;
+        opaque(t);
+        if (f < 0) {  // the call's first listed frame pairs with the carried amplitudes (zeros before the first spectrum)
+            const float *pp = prev_in + (long long)s * BINS + (t << zp_log2) + q;
+#pragma unroll
+            for (int m = 0; m < E; m++) pa[m] = pp[(128 * m) << zp_log2];
+            continue;
+        }
+        float2 v[E];
+        {
+            const long long base = (long long)s * sp.in_pitch + f * NF + t;
+            const float2 *fp = ftab + q * NF + t;
+#pragma unroll
+            for (int m = 0; m < E; m++) v[m] = RAW ? raw_load(raw, base + 128 * m) : in[base + 128 * m];
+#pragma unroll
+            for (int m = 0; m < E; m++) v[m] = cmul(fp[128 * m], v[m]);
+        }
+        fft2048_t128(v, lds, tw128, t, [] { __syncthreads(); });
+        float mag[E];
+#pragma unroll
+        for (int m = 0; m < E; m++) mag[m] = __builtin_amdgcn_sqrtf(v[m].x * v[m].x + v[m].y * v[m].y);
+        if (it < 0) {
+#pragma unroll
+            for (int m = 0; m < E; m++) pa[m] = mag[m];
+            continue;
+        }
+        float *yp = out + (long long)s * sp.out_pitch + (long long)(fl.row0 + li) * BINS + ((t << zp_log2) + q);
+#pragma unroll
+        for (int m = 0; m < E; m++) {
+            const int u = m < 8 ? ((128 * m + 1024) << zp_log2) : ((128 * (m - 8)) << zp_log2);  // unfold, fft.cpp:207-213
+            yp[u] = fminf(fmaxf(fmaf(6.02059991327962f, __builtin_amdgcn_logf(mag[m] + pa[m]), db_off), -120.f), 0.f);
+        }
+        if (fl.last && li == fl.n - 1) {
+            float *pp = prev_out + (long long)s * BINS + (t << zp_log2) + q;
+#pragma unroll
+            for (int m = 0; m < E; m++) pp[(128 * m) << zp_log2] = mag[m];
+        }
+    }
+}
+
+static __global__ __launch_bounds__(256) void k_spectrum_list_any(const float2 *__restrict__ in, float *__restrict__ out, const float *__restrict__ window,
+                                                                 const float2 *__restrict__ twM, const float *__restrict__ prev_in, float *__restrict__ prev_out,
+                                                                 SpectrumParams sp, AnySpecParams ap, FrameList fl)
+{
+    HIP_DYNAMIC_SHARED(float2, buf)
+    constexpr int EMAX = 64;  // M / 256 <= 64 points per work-item
+    const int tid = threadIdx.x, s = blockIdx.y;
+    const int ZP = 1 << ap.zp_log2, q = blockIdx.x & (ZP - 1), li = blockIdx.x >> ap.zp_log2;
+    if (li >= fl.n) return;  // workgroup-uniform
+    const int M = ap.M, bins = M << ap.zp_log2;
+    const int E = M >= 256 ? M >> 8 : 1;
+    const float db_off = 6.02059991327962f * __builtin_amdgcn_logf(0.5f * sp.scale);
+    float pa[EMAX];
+#pragma unroll
+    for (int m = 0; m < EMAX; m++) pa[m] = 0.f;
+    for (int it = -1; it < 1; it++) {
+        const long long f = it < 0 ? (li > 0 ? (long long)fl.idx[li - 1] : fl.pred) : (long long)fl.idx[li];
+        if (f < 0) {
+#pragma unroll
+            for (int m = 0; m < EMAX; m++)
+                if (m < E && tid + 256 * m < M) pa[m] = prev_in[(long long)s * bins + ((tid + 256 * m) << ap.zp_log2) + q];
+            continue;
+        }
+        any_transform(buf, in + (long long)s * sp.in_pitch + f * ap.frame, window, twM, ap, q, tid);
+        float *yf = out + (long long)s * sp.out_pitch + (long long)(fl.row0 + li) * bins;
+        const bool keep = it >= 0 && fl.last && li == fl.n - 1;
+#pragma unroll
+        for (int m = 0; m < EMAX; m++) {
+            const int k = tid + 256 * m;
+            if (m < E && k < M) {
+                const float2 z = buf[k];
+                const float mag = __builtin_amdgcn_sqrtf(z.x * z.x + z.y * z.y);
+                const float a = mag + pa[m];
+                pa[m] = mag;
+                if (it >= 0) {
+                    const int u = (((k << ap.zp_log2) + q) + (bins >> 1)) & (bins - 1);  // unfold, fft.cpp:207-213
+                    yf[u] = fminf(fmaxf(fmaf(6.02059991327962f, __builtin_amdgcn_logf(a), db_off), -120.f), 0.f);
+                    if (keep) prev_out[(long long)s * bins + (k << ap.zp_log2) + q] = mag;
+                }
+            }
         }
         __syncthreads();
     }

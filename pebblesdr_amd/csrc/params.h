@@ -301,6 +301,25 @@ struct SpectrumParams {
     long long out_pitch;     // floats between streams (= n_frames*bins)
 };
 
+// The frames of a gated call (SignalSpectrum's update timer, signalspectrum.cpp:63-113): a short list of far-apart frames, worked out
+// by the host before anything is queued and carried in the kernel arguments (k_spectrum_list_*); longer lists take several launches.
+constexpr int kListMax = 64;
+struct FrameList {
+    int n;                   // listed frames of this launch
+    int row0;                // output row of idx[0] (rows are compact: [stream][n_selected][bins])
+    long long pred;          // the listed frame in front of idx[0], whose amplitudes pair with idx[0]'s; -1: the carried buffer
+    int last;                // != 0: idx[n - 1] is the call's last listed frame: its amplitudes go to the carried buffer
+    int pad_;
+    uint32_t idx[kListMax];  // frame numbers relative to the call's first frame, ascending
+};
+// the squelch gate of a bank under the update timer: per super-frame the compact row of the latest computed spectrum at or before the
+// super-frame's last raw frame (k_gate_eval_rows); kGateRowCarried: the row carried from an earlier call; kGateRowNone: no spectrum yet
+constexpr int kGateRowCarried = -1, kGateRowNone = -2;
+struct GateRows {
+    int n, j0;               // super-frames j0 .. j0 + n - 1 of the call
+    int row[kListMax];
+};
+
 // ---- the Morse digital modem (kernels_modem.h) ----
 constexpr uint32_t kMorseDotMagic = 1200000;  // MorseCode::c_uSecDotMagic, morsecode.h:58
 constexpr uint32_t kMorseWpmLow = 10, kMorseWpmHigh = 50, kMorseWpmVar = 2;  // morse.h:82-83, :169

@@ -343,5 +343,21 @@ int pebblegpu_process_iq(pebblegpu_receiver *h, const double *iq, uint16_t n, do
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
     return h->rx.process_iq(iq, n, audio, n_audio, spectrum_db);
 }
+int pebblegpu_process_iq_updates(pebblegpu_receiver *h, const double *iq, uint16_t n, double *audio, uint32_t *n_audio,
+                                 double *spectrum_db, uint32_t *spectrum_updated)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.process_iq(iq, n, audio, n_audio, spectrum_db, spectrum_updated);
+}
+int pebblegpu_set_spectrum_updates(pebblegpu_receiver *h, int updates_per_sec)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.set_spectrum_updates(updates_per_sec);
+}
+int pebblegpu_receiver_spectrum_frames(const pebblegpu_receiver *h, int zoomed, uint32_t *idx, uint32_t cap, uint32_t *n)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.spectrum_frames(zoomed != 0, idx, cap, n);
+}
 
 }  // extern "C"

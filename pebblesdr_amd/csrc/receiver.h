@@ -47,6 +47,8 @@ int fill_tail_jobs(TailJobs &tj, const std::vector<TailJob> &jobs, const OscAdva
 int run_normalize_iq(int fmt, int order, double gain, const void *d_src, long long n, float2 *d_dst, hipStream_t s, bool wait, const float *final_scale = nullptr);
 int run_gate_eval(hipStream_t s, const float4 *d_smeter, long long smeter_pitch, int frames_per_sf, int k, const float *d_squelch, unsigned char *d_gate,
                   int stride, uint32_t channels);
+int run_gate_eval_rows(hipStream_t s, const float4 *d_smeter, long long smeter_pitch, const float4 *d_carried, const int *rows, int k, const float *d_squelch,
+                       unsigned char *d_gate, int stride, uint32_t channels);
 int run_gate_zero(hipStream_t s, float2 *audio, long long pitch, long long spf, const unsigned char *d_gate, int stride, uint32_t channels, int k);
 int run_signal_strength(hipStream_t s, const float *d_spec, long long stream_pitch, int bins, long long n_frames, const SmBins *d_bins,
                         float4 *d_out, long long out_pitch, uint32_t channels);
@@ -506,6 +508,11 @@ struct SpectrumCore {
     int init(uint32_t streams, uint32_t frame, uint32_t fft_size, const Tuning &t);
     void release();
     int run(hipStream_t s, const float2 *d_in, long long in_pitch, long long n_frames, float *d_out, const RawSrc *raw = nullptr, const DecFuse *df = nullptr, bool nothing_beside = false);
+    // the transform over a frame list (the update timer's selection, k_spectrum_list_*): rows compact, |X_prev| = the previous listed frame
+    float2 *d_list_ftab = nullptr, *d_list_tw128 = nullptr;  // k_spectrum_list_q128's tables (k_spectrum_q128's own where that kernel is the plan's)
+    bool list_owned = false;
+    int init_list();
+    int run_list(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw = nullptr);
     bool dec_ready() const { return !big && !per_q && bins == 8192 && !use_w64; }  // k_spectrum_t128<.., DEC> exists for this plan
     bool raw_ready() const { return !big && !per_q && bins == 8192; }  // k_spectrum_t128 converts in its loads
 };
@@ -524,9 +531,27 @@ struct Timers {
     hipEvent_t *slot() { return ev[calls % kRing]; }
 };
 
+// SignalSpectrum's update timer (m_spectrumTimer / m_hiResTimer, signalspectrum.cpp:63-113) on the stream's own sample clock: frames are
+// numbered from the handle's creation, the first one starts the timer and gets no spectrum, after that frame f gets one iff
+// (f - f_last) * frame_len * 1000 / rate >= period_ms in integer arithmetic, and then becomes f_last.  Host only: the list is known
+// before anything is queued.
+struct UpdateTimer {
+    bool started = false;
+    uint64_t next = 0;    // number of the next frame of the stream
+    uint64_t f_last = 0;  // the frame that last restarted the timer
+    // the n frames of a call; the selected ones, relative to the call's first frame, are appended to *sel.
+    // ups -1: every frame gets a spectrum and restarts the timer (nothing is appended); 0: none does (m_updatesPerSec == 0)
+    void advance(int ups, uint64_t period_ms, uint64_t n, uint64_t frame_len, uint64_t rate, std::vector<uint32_t> *sel);
+};
+
 class Receiver {
 public:
     int create(const pebblegpu_config *cfg);
+    // SignalSpectrum::setUpdatesPerSec (signalspectrum.cpp:124-135); PEBBLEGPU_SPECTRUM_EVERY_FRAME (-1, the default): no gate
+    int set_spectrum_updates(int updates_per_sec);
+    // which frames of the last call got an unprocessed (zoomed) spectrum, relative to the call's first frame
+    int spectrum_frames(bool zoomed, uint32_t *idx, uint32_t cap, uint32_t *n) const;
+    bool gated() const { return spec_ups_ != -1; }
     ~Receiver();
     int set_mixer(uint32_t ch, double f);
     int set_bandpass(uint32_t ch, double lo, double hi);
@@ -549,7 +574,8 @@ public:
     int morse_events(uint32_t ch, MorseEvent *ev, uint32_t cap, uint32_t *n);
     int morse_status(uint32_t ch, MorseStatus *st);
     int process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw = nullptr);
-    int process_iq(const double *iq, uint16_t n, double *audio, uint32_t *n_audio, double *spectrum_db);
+    // spectrum_updated (may be null): whether this frame got a spectrum (always, without the update timer)
+    int process_iq(const double *iq, uint16_t n, double *audio, uint32_t *n_audio, double *spectrum_db, uint32_t *spectrum_updated = nullptr);
     // FFT::mapFFTToScreen of frames first + j * step (j < n) of the last call's unprocessed spectrum (zoom = false) or zoomed spectra
     // (zoom = true; edges per channel), queued behind that call's transform and ahead of the next call's: out [stream][n][x_pixels]
     int map_spectrum(bool zoom, const int32_t *edges, bool per_stream, int32_t y_pixels, int32_t x_pixels, double max_db, double min_db,
@@ -573,6 +599,17 @@ public:
     uint32_t zoom_bins = 0;
     float *d_zoom = nullptr;          // [C][max_sf * superframe / (D * nf)][zoom_bins]
     uint64_t last_zoom_frames = 0;
+    // the update timer (set_spectrum_updates): -1 no gate; with a gate last_spec_frames / last_zoom_frames count the COMPUTED rows of
+    // the last call (compact in d_spec / d_zoom) and sel_spec_ / sel_zoom_ say which frames they are
+    int spec_ups_ = -1;
+    uint64_t spec_period_ms_ = 100;   // 1000 / m_updatesPerSec of the last rate above 0 (the reference's default: 10 per second)
+    UpdateTimer ut_spec_, ut_zoom_;
+    std::vector<uint32_t> sel_spec_, sel_zoom_;
+    // what the S-meter and the squelch read between two updates (getUnprocessed(), receiver.cpp:891-897, 959-965): the latest computed
+    // row per stream, carried across calls, and its S-meter per channel (refreshed with the channel's current band at every call)
+    float *d_spec_carry = nullptr;    // [S][bins]
+    float4 *d_sm_carry = nullptr;     // [C]
+    bool have_carry_ = false;
     // SignalStrength::fdEstimate per frame (S-meter): enabled on request, needs the spectrum
     bool smeter_on = false;
     float4 *d_smeter = nullptr;       // [C][max frames]

@@ -129,6 +129,8 @@ Receiver::~Receiver()
     if (d_squelch) (void)hipFree(d_squelch);
     if (d_gate) (void)hipFree(d_gate);
     if (d_raw_stage_) (void)hipFree(d_raw_stage_);
+    if (d_spec_carry) (void)hipFree(d_spec_carry);
+    if (d_sm_carry) (void)hipFree(d_sm_carry);
     if (d_smeter) (void)hipFree(d_smeter);
     if (d_sm_bins) (void)hipFree(d_sm_bins);
     audio.release();
@@ -217,6 +219,72 @@ int Receiver::morse_status(uint32_t ch, MorseStatus *st)
     if (!morse_.C) return fail(PEBBLEGPU_E_INVALID, "the Morse modem of channel %u is off", ch);
     PG_HIP(hipSetDevice(device));
     return morse_.status(ch, st);
+}
+
+void UpdateTimer::advance(int ups, uint64_t period_ms, uint64_t n, uint64_t frame_len, uint64_t rate, std::vector<uint32_t> *sel)
+{
+    const uint64_t first = next, end = next + n;
+    next = end;
+    if (n == 0) return;
+    if (ups < 0) {  // no gate: every frame is transformed and restarts the timer
+        started = true;
+        f_last = end - 1;
+        return;
+    }
+    uint64_t f = first;
+    if (!started) {  // "First time": the frame starts the timer and gets no spectrum (signalspectrum.cpp:65-68)
+        started = true;
+        f_last = f++;
+    }
+    if (ups == 0) return;  // m_updatesPerSec == 0: the timer runs on, nothing is made
+    // floor(d * frame_len * 1000 / rate) >= period_ms  <=>  d >= ceil(period_ms * rate / (frame_len * 1000)); a frame never pairs with itself
+    const uint64_t per = frame_len * 1000u;
+    uint64_t d_min = (period_ms * rate + per - 1) / per;
+    if (d_min < 1) d_min = 1;
+    for (f = std::max(f, f_last + d_min); f < end; f = f_last + d_min) {
+        sel->push_back((uint32_t)(f - first));
+        f_last = f;
+    }
+}
+
+int Receiver::set_spectrum_updates(int ups)
+{
+    if (ups < -1) return fail(PEBBLEGPU_E_INVALID, "updates per second: -1 (every frame), 0 (none) or a rate");
+    std::lock_guard<std::mutex> g(mu_);
+    PG_HIP(hipSetDevice(device));
+    if (ups != -1) {
+        if (bins) { if (int rc = spec_.init_list()) return rc; }
+        if (zoom_bins) { if (int rc = zoom_.init_list()) return rc; }
+        if (bins && !d_spec_carry) {
+            PG_HIP(hipMalloc((void **)&d_spec_carry, sizeof(float) * (size_t)bins * S));
+            PG_HIP(hipMalloc((void **)&d_sm_carry, sizeof(float4) * C));
+        }
+        if (spec_ups_ == -1 && bins && last_spec_frames) {
+            // so far every frame had a spectrum: the one the S-meter and the squelch go on reading is the last call's last
+            if (int rc = sync()) return rc;
+            PG_HIP(hipMemcpy2D(d_spec_carry, sizeof(float) * bins, d_spec + (last_spec_frames - 1) * bins, sizeof(float) * last_spec_frames * bins,
+                               sizeof(float) * bins, S, hipMemcpyDeviceToDevice));
+            have_carry_ = true;
+        }
+    }
+    if (ups > 0) spec_period_ms_ = (uint64_t)(1000 / ups);  // integer division, as the reference computes it
+    spec_ups_ = ups;
+    touched_ = true;  // the next call joins its two pipelines first
+    return 0;
+}
+int Receiver::spectrum_frames(bool zoomed, uint32_t *idx, uint32_t cap, uint32_t *n) const
+{
+    if (!n) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    *n = 0;
+    if (zoomed ? !zoom_bins : !bins) return fail(PEBBLEGPU_E_INVALID, zoomed ? "the receiver computes no zoomed spectrum (hires_bins = 0)" : "the receiver computes no spectrum (spectrum_bins = 0)");
+    const uint64_t rows = zoomed ? last_zoom_frames : last_spec_frames;
+    const std::vector<uint32_t> &sel = zoomed ? sel_zoom_ : sel_spec_;
+    if (rows > cap) return fail(PEBBLEGPU_E_SIZE, "%llu frames do not fit %u entries", (unsigned long long)rows, cap);
+    if (rows && !idx) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    // (without the gate every frame of the call has its row)
+    for (uint64_t i = 0; i < rows; i++) idx[i] = gated() && sel.size() == rows ? sel[i] : (uint32_t)i;
+    *n = (uint32_t)rows;
+    return 0;
 }
 
 int Receiver::enable_smeter(bool on)
@@ -418,7 +486,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         return fail(PEBBLEGPU_E_SIZE, "spectrum needs whole frames of %u samples within capacity", nf);
     // caller mistakes around the squelch gate are refused HERE, before anything is queued: they leave the handle usable (a failure
     // behind this point has kernels in flight and histories half advanced, and closes the handle)
-    if (with_chain && squelch_db_ > -120.0 && !with_spectrum && !last_spec_frames)
+    if (with_chain && squelch_db_ > -120.0 && !with_spectrum && !last_spec_frames && !gated())  // (under the update timer the gate stays open until the first spectrum)
         return fail(PEBBLEGPU_E_INVALID, "the squelch gate needs a spectrum: none has been computed yet");
     if (with_chain && !wfm && bank_gate_ && !with_spectrum && !(squelch_db_ > -120.0) && !(C == 1 && ctl_[0].mode == PEBBLEGPU_DM_NONE))
         return fail(PEBBLEGPU_E_INVALID, "the squelch gate of a bank reads the spectra of the same call: create the bank with spectrum_bins");
@@ -520,10 +588,32 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     // Opt-in (PEBBLEGPU_FUSE_DEC=1 when the receiver is created): measured slower -- the stages sit in the kernel's barrier intervals,
     // 0.297 ms against 0.247 beside the stand-alone first stage, the call 0.330 against 0.293
     dec_.want_lds_free = side;
-    const bool fuse_dec = tun_.fuse_dec && side && with_chain && !tun_.pipeline && S == 1 && spec_.dec_ready() && nf == 2048 && dec_.spectrum_can_run(osc_) && (!raw || !staged);
+    const bool fuse_dec = tun_.fuse_dec && !gated() && side && with_chain && !tun_.pipeline && S == 1 && spec_.dec_ready() && nf == 2048 && dec_.spectrum_can_run(osc_) && (!raw || !staged);
     DecFuse df;
     if (fuse_dec) { if (int rc = dec_.fill_dec_fuse(stream_, &df, osc_, (long long)n)) return rc; }
-    if (with_spectrum) {  // SignalSpectrum::unprocessed on the raw frame, receiver.cpp:826
+    const bool carry_before = have_carry_;  // a computed spectrum from before this call exists (what its first super-frames' squelch reads)
+    // the carried row's S-meter with the channels' current bands (before this call's rows replace the row)
+    auto measure_carry = [&](hipStream_t st) -> int {
+        if (!(gated() && smeter_on && have_carry_)) return 0;
+        return run_signal_strength(st, d_spec_carry, (long long)bins, (int)bins, 1, d_sm_bins, d_sm_carry, 1, C);
+    };
+    if (with_spectrum && gated()) {
+        // SignalSpectrum::unprocessed behind its update timer (signalspectrum.cpp:63-86): the host has the frame list before anything is
+        // queued; the transform runs over that list alone, rows compact, |X_prev| from listed frame to listed frame
+        sel_spec_.clear();
+        ut_spec_.advance(spec_ups_, spec_period_ms_, n / nf, nf, (uint64_t)fs, &sel_spec_);
+        const long long ns = (long long)sel_spec_.size();
+        if (int rc = measure_carry(stream_)) return rc;
+        if (int rc = spec_.run_list(stream_, d_iq, in_pitch, sel_spec_.data(), ns, d_spec, raw)) return rc;
+        last_spec_frames = (uint64_t)ns;
+        if (ns) {
+            if (smeter_on) { if (int rc = run_signal_strength(stream_, d_spec, ns * (long long)bins, (int)bins, ns, d_sm_bins, d_smeter, smeter_pitch, C)) return rc; }
+            PG_HIP(hipMemcpy2DAsync(d_spec_carry, sizeof(float) * bins, d_spec + (ns - 1) * (long long)bins, sizeof(float) * (size_t)ns * bins, sizeof(float) * bins, S,
+                                    hipMemcpyDeviceToDevice, stream_));
+            have_carry_ = true;
+        }
+    } else if (with_spectrum) {  // SignalSpectrum::unprocessed on the raw frame, receiver.cpp:826
+        ut_spec_.advance(-1, 0, n / nf, nf, (uint64_t)fs, nullptr);  // (every frame restarts the timer a later set_spectrum_updates goes on from)
         // (a call whose chain follows on the same stream, or that has none, leaves the GPU to the transform: its all-registers variant)
         if (int rc = spec_.run(stream_, d_iq, in_pitch, (long long)(n / nf), d_spec, raw, fuse_dec ? &df : nullptr, !side)) return rc;
         last_spec_frames = n / nf;
@@ -589,9 +679,17 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         if (int rc = run_nap(cs, nap >= 0 ? (unsigned)nap : (rot3 ? 0u : 800u))) return rc;
     }
     const long long nd = dec_.out_len();
-    if (zoom_bins) {  // SignalSpectrum::zoomed(m_sampleBuf, numStepSamples), receiver.cpp:884 / :942 (the update timer forced open)
-        if (int rc = zoom_.run(cs, dec_.out().data(), dec_.out().pitch, nd / nf, d_zoom)) return rc;
-        last_zoom_frames = (uint64_t)(nd / nf);
+    if (zoom_bins) {  // SignalSpectrum::zoomed(m_sampleBuf, numStepSamples), receiver.cpp:884 / :942 (its update timer: open by default)
+        if (gated()) {  // m_hiResTimer: the same period, counted in decimated frames at the demodulator rate (signalspectrum.cpp:94-100)
+            sel_zoom_.clear();
+            ut_zoom_.advance(spec_ups_, spec_period_ms_, (uint64_t)(nd / nf), nf, demod_rate_int, &sel_zoom_);
+            if (int rc = zoom_.run_list(cs, dec_.out().data(), dec_.out().pitch, sel_zoom_.data(), (long long)sel_zoom_.size(), d_zoom)) return rc;
+            last_zoom_frames = (uint64_t)sel_zoom_.size();
+        } else {
+            ut_zoom_.advance(-1, 0, (uint64_t)(nd / nf), nf, demod_rate_int, nullptr);
+            if (int rc = zoom_.run(cs, dec_.out().data(), dec_.out().pitch, nd / nf, d_zoom)) return rc;
+            last_zoom_frames = (uint64_t)(nd / nf);
+        }
         zoom_stream_ = cs;
     }
     if (!wfm) {
@@ -601,7 +699,21 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     // Squelch, receiver.cpp:893-897 / :962-965: below the threshold the reference returns here -- nothing behind the gate
     // runs or changes state, and no audio leaves the call.
     bool gate_closed = false, tails_carried = false;
-    if (squelch_db_ > -120.0) {
+    if (squelch_db_ > -120.0 && gated()) {
+        // the latest computed spectrum: a row of this call, else the carried one (m_unprocessedSpectrum between two updates).  Before the
+        // first spectrum the reference compares against an uninitialised buffer (signalspectrum.cpp:13): the gate stays open
+        const float4 *src = nullptr;
+        if (with_spectrum && last_spec_frames) src = d_smeter + (last_spec_frames - 1);
+        else if (have_carry_) {
+            if (!with_spectrum) { if (int rc = measure_carry(cs)) return rc; }
+            src = d_sm_carry;
+        }
+        if (src) {
+            PG_HIP(hipMemcpyAsync(h_gate_, src, sizeof(float4), hipMemcpyDeviceToHost, cs));
+            PG_HIP(hipStreamSynchronize(cs));
+            gate_closed = (double)h_gate_->y < squelch_db_;  // m_avgDb < m_squelchDb
+        }
+    } else if (squelch_db_ > -120.0) {
         if (!last_spec_frames) return fail(PEBBLEGPU_E_INVALID, "the squelch gate needs a spectrum: none has been computed yet");
         PG_HIP(hipMemcpyAsync(h_gate_, d_smeter + (last_spec_frames - 1), sizeof(float4), hipMemcpyDeviceToHost, cs));
         PG_HIP(hipStreamSynchronize(cs));
@@ -627,7 +739,17 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         if (!with_spectrum) return fail(PEBBLEGPU_E_INVALID, "the squelch gate of a bank reads the spectra of the same call: create the bank with spectrum_bins");
         const int k = (int)(n / superframe);
         const long long spf = nd / k;
-        if (int rc = run_gate_eval(cs, d_smeter, smeter_pitch, (int)(superframe / nf), k, d_squelch, d_gate, (int)max_sf, C)) return rc;
+        if (gated()) {
+            // per super-frame the latest computed spectrum at or before its last raw frame: a compact row of this call, the carried row, or none yet
+            const uint64_t fps = superframe / nf;
+            std::vector<int> rows((size_t)k);
+            size_t r = 0;
+            for (int j = 0; j < k; j++) {
+                while (r < sel_spec_.size() && (uint64_t)sel_spec_[r] <= (uint64_t)(j + 1) * fps - 1) r++;
+                rows[(size_t)j] = r ? (int)r - 1 : (carry_before ? kGateRowCarried : kGateRowNone);
+            }
+            if (int rc = run_gate_eval_rows(cs, d_smeter, smeter_pitch, d_sm_carry, rows.data(), k, d_squelch, d_gate, (int)max_sf, C)) return rc;
+        } else if (int rc = run_gate_eval(cs, d_smeter, smeter_pitch, (int)(superframe / nf), k, d_squelch, d_gate, (int)max_sf, C)) return rc;
         for (int j = 0; j < k; j++) {
             const Gate gate{d_gate, (int)max_sf, j};
             float2 *seg = audio.data() + (long long)j * spf;
@@ -797,7 +919,7 @@ int Receiver::process_ingested(uint32_t slot, int fmt, int order, double gain, u
 const char *Receiver::kernel_name(int which) const
 {
     switch (which) {
-    case 1: return !bins ? "" : spec_.big ? "k_big256_cols + k_big256_rows" : spec_.per_q ? "k_spectrum_q128" : bins == 8192 ? (spec_.use_w64 ? "k_spectrum_w64" : spec_.last_fullc ? "k_spectrum_t128 (twiddles held)" : "k_spectrum_t128") : bins == 4096 ? "k_spectrum<2>" : "k_spectrum_1to1";
+    case 1: return !bins ? "" : gated() ? (spec_.any ? "k_spectrum_list_any" : "k_spectrum_list_q128") : spec_.big ? "k_big256_cols + k_big256_rows" : spec_.per_q ? "k_spectrum_q128" : bins == 8192 ? (spec_.use_w64 ? "k_spectrum_w64" : spec_.last_fullc ? "k_spectrum_t128 (twiddles held)" : "k_spectrum_t128") : bins == 4096 ? "k_spectrum<2>" : "k_spectrum_1to1";
     case 2: return dec_.front_name;
     case 3: return dec_.rest_name;
     case 4: return wfm ? "" : ff_n == 2048 ? "k_fastfir_t128" : "k_fastfir";
@@ -827,7 +949,10 @@ int Receiver::map_spectrum(bool zoom, const int32_t *edges, bool per_stream, int
     if (int rc = check_screen_map(y_pixels, x_pixels, max_db, min_db)) return rc;
     if (failed_) return fail(PEBBLEGPU_E_HIP, "an earlier call on this receiver failed half-way: its spectra are not defined");
     const uint32_t fft = zoom ? zoom_bins : bins;
-    const uint64_t frames = zoom ? last_zoom_frames : last_spec_frames;
+    uint64_t frames = zoom ? last_zoom_frames : last_spec_frames;
+    // behind the update timer a call may have made no spectrum: the display then maps the one it still holds (m_unprocessedSpectrum), as row 0
+    const bool carried = !zoom && gated() && !frames && have_carry_;
+    if (carried) frames = 1;
     if (!fft) return fail(PEBBLEGPU_E_INVALID, zoom ? "the receiver computes no zoomed spectrum (hires_bins = 0)" : "the receiver computes no spectrum (spectrum_bins = 0)");
     if (!frames) return fail(PEBBLEGPU_E_INVALID, "no call with a spectrum has been made yet");
     if (n == 0 || (uint64_t)first + (uint64_t)(n - 1) * step >= frames)
@@ -835,7 +960,7 @@ int Receiver::map_spectrum(bool zoom, const int32_t *edges, bool per_stream, int
     PG_HIP(hipSetDevice(device));
     if (int rc = close_timing()) return rc;  // (a side-by-side call's time ends where it ended, not behind the map)
     const int rows = zoom ? (int)C : (int)S;
-    const float *src = (zoom ? d_zoom : d_spec) + (long long)first * fft;
+    const float *src = carried ? d_spec_carry : (zoom ? d_zoom : d_spec) + (long long)first * fft;
     hipStream_t ms = zoom && zoom_stream_ ? zoom_stream_ : stream_;
     if (int rc = run_screen_map(ms, src, (long long)frames * fft, (long long)step * fft, rows, (int)n, (int32_t)fft,
                                 zoom ? (double)demod_rate_int : fs, edges, per_stream, y_pixels, x_pixels, max_db, min_db, d_out)) return rc;
@@ -858,7 +983,7 @@ int Receiver::sync()
 
 // CB_ProcessIQData shape: one frame in; audio appears once a whole super-frame has been collected, exactly where
 // the reference stops returning early (receiver.cpp:922-931).
-int Receiver::process_iq(const double *iq, uint16_t n, double *audio_out, uint32_t *n_audio, double *spectrum_db)
+int Receiver::process_iq(const double *iq, uint16_t n, double *audio_out, uint32_t *n_audio, double *spectrum_db, uint32_t *spectrum_updated)
 {
     if (!iq || !n_audio) return fail(PEBBLEGPU_E_INVALID, "null argument");
     if (n != nf) return fail(PEBBLEGPU_E_SIZE, "process_iq takes frames of %u samples", nf);
@@ -872,10 +997,15 @@ int Receiver::process_iq(const double *iq, uint16_t n, double *audio_out, uint32
     float2 *dst = d_stage_in_ + acc_frames_ * nf;
     PG_HIP(hipMemcpy(dst, h_frame_.data(), sizeof(float2) * nf, hipMemcpyHostToDevice));
     *n_audio = 0;
-    if ((spectrum_db || squelch_db_ > -120.0) && bins) {  // the gate reads the latest frame's spectrum, wanted by the host or not
+    if (spectrum_updated) *spectrum_updated = 0;
+    if ((spectrum_db || squelch_db_ > -120.0 || gated()) && bins) {  // the gate reads the latest frame's spectrum, wanted by the host or not (and the update timer counts every frame)
         if (int rc = process(dst, nf, true, false)) return rc;
+        if (spectrum_updated) *spectrum_updated = last_spec_frames ? 1u : 0u;
+    } else if (bins) {
+        std::lock_guard<std::mutex> g(mu_);
+        ut_spec_.advance(-1, 0, 1, nf, (uint64_t)fs, nullptr);
     }
-    if (spectrum_db && bins) {
+    if (spectrum_db && bins && last_spec_frames) {  // (under the update timer only a frame that got a spectrum hands one out)
         if (int rc = sync()) return rc;
         h_out_.resize(bins);
         PG_HIP(hipMemcpy(h_out_.data(), d_spec, sizeof(float) * bins, hipMemcpyDeviceToHost));
