@@ -15,7 +15,7 @@
  *   - process_* calls are single-caller per handle (the reference calls processIQData from one
  *     consumer thread, pebblelib/producerconsumer.cpp:101-109); setters may be called from another
  *     thread and take effect at the next process call (= frame boundary).
- *   - ASYNCHRONY: pebblegpu_receiver_process / _process_raw and pebblegpu_streambank_process only QUEUE their kernels on
+ *   - ASYNCHRONY: pebblegpu_receiver_process / _process_raw and pebblegpu_streambank_process / _process_raw only QUEUE their kernels on
  *     streams private to the handle and return.  The device buffers behind pebblegpu_receiver_audio / _spectrum /
  *     _signal_strength and pebblegpu_streambank_filtered / _spectrum hold the call's results, and the call's INPUT buffer
  *     may be overwritten, only after pebblegpu_receiver_synchronize / pebblegpu_streambank_synchronize (or any of
@@ -421,6 +421,33 @@ const void *pebblegpu_streambank_spectrum(const pebblegpu_streambank *sb, uint64
 /* which: 0 whole call, 1 band-pass kernel, 2 spectrum kernels */
 int pebblegpu_streambank_last_ms(const pebblegpu_streambank *sb, int which, float *ms);
 int pebblegpu_streambank_synchronize(pebblegpu_streambank *sb);
+/* pebblegpu_streambank_process on streams still in the device's sample format: d_raw is [stream][n_samples] IQ pairs of `format`
+ * (pebblegpu_iq_format; row pitch n_samples pairs), converted as DeviceInterfaceBase::normalizeIQ does (format / iq_order / gain as in
+ * pebblegpu_receiver_process_raw; gain 0 is silence).  Results equal pebblegpu_streambank_process on the same samples converted on the
+ * host, bit for bit, and raw and float2 calls may alternate on one bank: the band-pass's overlap carries converted samples.
+ * With 65536-sample frames and 65536 bins, or 2048-sample frames and 8192 bins, and the 2048-point band-pass, both kernels convert in
+ * their own loads and no float2 copy of the streams exists; every other geometry is converted by one pass into a library-owned
+ * float2 buffer first (allocated on the first such call).  pebblegpu_streambank_kernel_name tells which.
+ * d_raw must be aligned to PEBBLEGPU_RAW_ALIGN bytes (the kernels read it with loads of up to 32 bytes).  Refused before anything is
+ * queued, leaving the handle usable: unknown format or order (PEBBLEGPU_E_INVALID), n_samples not a multiple of the frame or above the
+ * capacity (PEBBLEGPU_E_SIZE), a misaligned d_raw (PEBBLEGPU_E_INVALID). */
+#define PEBBLEGPU_RAW_ALIGN 32
+int pebblegpu_streambank_process_raw(pebblegpu_streambank *sb, int format, int iq_order, double gain, const void *d_raw, uint64_t n_samples,
+                                     uint32_t what);
+/* The library's pinned double buffer for a stream bank, same contract as pebblegpu_receiver_ingest_* above:
+ * acquire(slot, bytes) hands out the slot's pinned host buffer (after waiting for the call that last read the slot), the host writes
+ * [stream][n_samples] raw pairs into it, submit(slot, bytes) queues the upload, process_ingested runs pebblegpu_streambank_process_raw
+ * on the uploaded samples behind the upload -- while the host fills the other slot.  Refused: a slot submitted again without an
+ * acquire while its call is in flight (PEBBLEGPU_E_INVALID), more bytes than acquired, or a format whose n_streams * n_samples pairs
+ * do not fit the submitted bytes (PEBBLEGPU_E_SIZE). */
+int pebblegpu_streambank_ingest_acquire(pebblegpu_streambank *sb, uint32_t slot, uint64_t bytes, void **host_ptr);
+int pebblegpu_streambank_ingest_submit(pebblegpu_streambank *sb, uint32_t slot, uint64_t bytes);
+int pebblegpu_streambank_process_ingested(pebblegpu_streambank *sb, uint32_t slot, int format, int iq_order, double gain, uint64_t n_samples,
+                                          uint32_t what);
+/* which: 1 band-pass, 2 display transform -> the kernel route the LAST call took ("" when the call did not ask for it), stable names
+ * as pebblegpu_receiver_kernel_name: e.g. "k_fastfir_t128 (raw s8)" for converting loads against "k_normalize_iq + k_fastfir_t128"
+ * for a staged raw call and "k_fastfir_t128" for float2 input */
+const char *pebblegpu_streambank_kernel_name(const pebblegpu_streambank *sb, int which);
 /* FFT::mapFFTToScreen (see pebblegpu_screen_map above) of frames first_frame + j * frame_step (j < n_frames) of every stream of the
  * last call's spectrum (sampleRate = the bank's sample_rate, fftSize = spectrum_bins; 65536 with the clamp lifted) into the device
  * buffer d_out: int32 [stream][n_frames][x_pixels].  Queued behind the call's transform on the bank's stream; d_out holds the result

@@ -21,6 +21,8 @@ SYMBOLS = [
     "pebblegpu_streambank_create", "pebblegpu_streambank_destroy", "pebblegpu_streambank_set_bandpass",
     "pebblegpu_streambank_process", "pebblegpu_streambank_filtered", "pebblegpu_streambank_spectrum",
     "pebblegpu_streambank_last_ms", "pebblegpu_streambank_synchronize",
+    "pebblegpu_streambank_process_raw", "pebblegpu_streambank_ingest_acquire", "pebblegpu_streambank_ingest_submit",
+    "pebblegpu_streambank_process_ingested", "pebblegpu_streambank_kernel_name",
     "pebblegpu_mixer_create", "pebblegpu_mixer_destroy", "pebblegpu_mixer_set_frequency", "pebblegpu_mixer_process",
     "pebblegpu_decimator_create", "pebblegpu_decimator_destroy", "pebblegpu_decimator_build_chain",
     "pebblegpu_decimator_dec_by2_stages", "pebblegpu_decimator_process",
@@ -206,6 +208,12 @@ def _declare(L):
     L.pebblegpu_streambank_spectrum.argtypes = [vp, C.POINTER(u64), C.POINTER(u32)]
     L.pebblegpu_streambank_last_ms.argtypes = [vp, i32, C.POINTER(C.c_float)]
     L.pebblegpu_streambank_synchronize.argtypes = [vp]
+    L.pebblegpu_streambank_process_raw.argtypes = [vp, i32, i32, dbl, vp, u64, u32]
+    L.pebblegpu_streambank_ingest_acquire.argtypes = [vp, u32, u64, C.POINTER(vp)]
+    L.pebblegpu_streambank_ingest_submit.argtypes = [vp, u32, u64]
+    L.pebblegpu_streambank_process_ingested.argtypes = [vp, u32, i32, i32, dbl, u64, u32]
+    L.pebblegpu_streambank_kernel_name.restype = C.c_char_p
+    L.pebblegpu_streambank_kernel_name.argtypes = [vp, i32]
     # stand-alone steps
     L.pebblegpu_mixer_create.argtypes = [i32, u32, u32, C.POINTER(vp)]
     L.pebblegpu_mixer_destroy.argtypes = [vp]
@@ -674,6 +682,27 @@ class StreamBank:
 
     def process_device(self, dptr, n_samples, what=3):
         check(self.L, self.L.pebblegpu_streambank_process(self.h, C.c_void_p(dptr), int(n_samples), int(what)))
+
+    def process_raw_device(self, dptr, n_samples, fmt, iq_order=0, gain=1.0, what=3):
+        """[streams, n_samples] raw device-format IQ pairs (pebblegpu_iq_format) already on the device, 32-byte aligned"""
+        check(self.L, self.L.pebblegpu_streambank_process_raw(self.h, int(fmt), int(iq_order), float(gain), C.c_void_p(dptr), int(n_samples), int(what)))
+
+    def ingest_acquire(self, slot, nbytes, dtype=np.int8):
+        """the slot's pinned host buffer as a numpy array (valid until the slot is acquired again with a larger size)"""
+        p = C.c_void_p()
+        check(self.L, self.L.pebblegpu_streambank_ingest_acquire(self.h, int(slot), int(nbytes), C.byref(p)))
+        n = int(nbytes) // np.dtype(dtype).itemsize
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(n,))
+
+    def ingest_submit(self, slot, nbytes):
+        check(self.L, self.L.pebblegpu_streambank_ingest_submit(self.h, int(slot), int(nbytes)))
+
+    def process_ingested(self, slot, n_samples, fmt, iq_order=0, gain=1.0, what=3):
+        check(self.L, self.L.pebblegpu_streambank_process_ingested(self.h, int(slot), int(fmt), int(iq_order), float(gain), int(n_samples), int(what)))
+
+    def kernel_name(self, which):
+        """the kernel route the last call took: which 1 band-pass, 2 display transform"""
+        return (self.L.pebblegpu_streambank_kernel_name(self.h, int(which)) or b"").decode()
 
     def synchronize(self):
         check(self.L, self.L.pebblegpu_streambank_synchronize(self.h))

@@ -293,17 +293,92 @@ void OscBank::advance(uint64_t n)
 
 int run_normalize_iq(int fmt, int order, double gain, const void *d_src, long long n, float2 *d_dst, hipStream_t s, bool wait, const float *final_scale)
 {
-    double scale = gain;
-    if (final_scale != nullptr) scale = (double)*final_scale;  // the caller has already folded the format's constant in (a gain of 0 included)
-    else if (fmt == 0 || fmt == 1) scale *= 1 / 128.0;   // deviceinterfacebase.cpp:651,689
-    else if (fmt == 2) scale *= 1 / 32768.0;             // :729
-    else if (fmt == 4) scale *= 1 / 32767.0;             // wavfile.cpp:299-300
+    // (a final_scale: the caller has already folded the format's constant in, a gain of 0 included)
+    const float scale = final_scale != nullptr ? *final_scale : raw_scale(fmt, gain);
     long long blocks = (n + 255) / 256;
     if (blocks > 256 * 8) blocks = 256 * 8;
-    launch(k_normalize_iq, dim3((unsigned)blocks), dim3(256), s, d_src, d_dst, n, fmt, order, (float)scale);
+    launch(k_normalize_iq, dim3((unsigned)blocks), dim3(256), s, d_src, d_dst, n, fmt, order, scale);
     PG_HIP(hipGetLastError());
     if (wait) PG_HIP(hipStreamSynchronize(s));
     return 0;
+}
+
+// ---- IngestRing (ingest.h) ----
+int IngestRing::acquire(int device, uint32_t s, uint64_t bytes, void **host_ptr)
+{
+    if (s > 1 || !host_ptr || bytes == 0) return fail(PEBBLEGPU_E_INVALID, "ingest slot is 0 or 1, bytes > 0");
+    PG_HIP(hipSetDevice(device));
+    IngestSlot &g = slot[s];
+    if (g.in_flight) {  // the call that read this slot's device copy (and the upload before it) must be over before the host refills it
+        PG_HIP(hipEventSynchronize(g.done_main));
+        PG_HIP(hipEventSynchronize(g.done_chain));
+        g.in_flight = false;
+    }
+    if (!copy_stream) PG_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    if (!g.uploaded) {
+        PG_HIP(hipEventCreateWithFlags(&g.uploaded, hipEventDisableTiming));
+        PG_HIP(hipEventCreateWithFlags(&g.done_main, hipEventDisableTiming));
+        PG_HIP(hipEventCreateWithFlags(&g.done_chain, hipEventDisableTiming));
+    }
+    if (g.cap < bytes) {
+        PG_HIP(hipStreamSynchronize(copy_stream));
+        if (g.h) (void)hipHostFree(g.h);
+        if (g.d) (void)hipFree(g.d);
+        g.h = g.d = nullptr;
+        g.cap = 0;
+        PG_HIP(hipHostMalloc(&g.h, bytes));
+        PG_HIP(hipMalloc(&g.d, bytes));
+        g.cap = bytes;
+    }
+    g.submitted = 0;
+    *host_ptr = g.h;
+    return 0;
+}
+int IngestRing::submit(int device, uint32_t s, uint64_t bytes)
+{
+    if (s > 1) return fail(PEBBLEGPU_E_INVALID, "ingest slot is 0 or 1");
+    IngestSlot &g = slot[s];
+    if (!g.h || bytes == 0 || bytes > g.cap) return fail(PEBBLEGPU_E_SIZE, "%llu bytes do not fit the slot acquired (%zu)", (unsigned long long)bytes, g.cap);
+    if (g.in_flight) return fail(PEBBLEGPU_E_INVALID, "the slot's previous call is still in flight: acquire it again first");
+    PG_HIP(hipSetDevice(device));
+    PG_HIP(hipMemcpyAsync(g.d, g.h, bytes, hipMemcpyHostToDevice, copy_stream));
+    PG_HIP(hipEventRecord(g.uploaded, copy_stream));
+    g.submitted = bytes;
+    return 0;
+}
+int IngestRing::check(uint32_t s, int fmt, uint64_t pairs, uint64_t n_for_message, IngestSlot **out)
+{
+    if (s > 1) return fail(PEBBLEGPU_E_INVALID, "ingest slot is 0 or 1");
+    IngestSlot &g = slot[s];
+    if (fmt < 0 || fmt > 4) return fail(PEBBLEGPU_E_INVALID, "unknown sample format %d", fmt);
+    if (!g.submitted || pairs * kRawPairBytes[fmt] > g.submitted)
+        return fail(PEBBLEGPU_E_SIZE, "the slot holds %zu submitted bytes; %llu samples of this format need more", g.submitted, (unsigned long long)n_for_message);
+    *out = &g;
+    return 0;
+}
+int IngestRing::wait_upload(IngestSlot &g, hipStream_t main, hipStream_t chain)
+{
+    PG_HIP(hipStreamWaitEvent(main, g.uploaded, 0));
+    PG_HIP(hipStreamWaitEvent(chain, g.uploaded, 0));
+    return 0;
+}
+int IngestRing::mark_in_flight(IngestSlot &g, hipStream_t main, hipStream_t chain)
+{
+    PG_HIP(hipEventRecord(g.done_main, main));
+    PG_HIP(hipEventRecord(g.done_chain, chain));
+    g.in_flight = true;
+    return 0;
+}
+void IngestRing::release()
+{
+    if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+    copy_stream = nullptr;
+    for (IngestSlot &g : slot) {
+        if (g.h) (void)hipHostFree(g.h);
+        if (g.d) (void)hipFree(g.d);
+        for (hipEvent_t e : {g.uploaded, g.done_main, g.done_chain}) if (e) (void)hipEventDestroy(e);
+        g = IngestSlot();
+    }
 }
 
 // streaming-copy probe: the chip's practical HBM ceiling next to which the kernels are priced
@@ -1153,8 +1228,9 @@ int FastFirCore::run(hipStream_t s, const HistBuf &in, long long n, float2 *out,
     PG_HIP(hipGetLastError());
     return 0;
 }
-int FastFirCore::run_ext(hipStream_t s, const float2 *in, long long in_pitch, float2 *d_tail, long long n, float2 *out, long long out_pitch, float2 *d_tail_next)
+int FastFirCore::run_ext(hipStream_t s, const float2 *in, long long in_pitch, float2 *d_tail, long long n, float2 *out, long long out_pitch, float2 *d_tail_next, const RawSrc *raw)
 {
+    if (raw && !(raw_ready() && d_tail && d_tail_next)) return fail(PEBBLEGPU_E_INVALID, "raw-format input reached a band-pass kernel that has no converting loads");
     const int overlap = (int)taps - 1;
     const long long L = block_len();
     if (n % L != 0) return fail(PEBBLEGPU_E_SIZE, "FastFIR input %lld is not a multiple of its block %lld", n, L);
@@ -1168,7 +1244,17 @@ int FastFirCore::run_ext(hipStream_t s, const float2 *in, long long in_pitch, fl
         // band-pass 0.222 / 0.227 -> 0.215 / 0.211 ms in alternating runs (PEBBLEGPU_FF_TWLDS=1 brings the copy back)
         const bool twg = tun.ff_twlds != 1;
         const FfGrid fg = ff_grid(n / L, C, tun.ff_xcd);
-        if (twg) launch_lds(k_fastfir_t128<false>, fg.grid, dim3(128), pad, s, in, in_pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail, d_tail_next, fg.nb, fg.nchan);
+        if (raw) {  // the stream bank's raw calls: converted in the loads (twiddles through the vector cache, as the float2 default below)
+            auto go = [&](auto kern) { launch_lds(kern, fg.grid, dim3(128), pad, s, in_pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail, d_tail_next, fg.nb, fg.nchan, *raw); };
+            switch (raw->fmt) {
+            case 0: go(k_fastfir_t128_raw<0>); break;
+            case 1: go(k_fastfir_t128_raw<1>); break;
+            case 2: go(k_fastfir_t128_raw<2>); break;
+            case 3: go(k_fastfir_t128_raw<3>); break;
+            default: go(k_fastfir_t128_raw<4>); break;
+            }
+        }
+        else if (twg) launch_lds(k_fastfir_t128<false>, fg.grid, dim3(128), pad, s, in, in_pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail, d_tail_next, fg.nb, fg.nchan);
         else launch_lds(k_fastfir_t128<true>, fg.grid, dim3(128), pad, s, in, in_pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail, d_tail_next, fg.nb, fg.nchan);
         if (d_tail_next) {  // the kernel's last block has written the next call's overlap into the caller's other buffer
             PG_HIP(hipGetLastError());
@@ -2059,7 +2145,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
 {
     if (df && !dec_ready()) return fail(PEBBLEGPU_E_INVALID, "the decimator was handed to a display transform that cannot run it");
     last_fullc = nothing_beside && !df && dec_ready();
-    if (raw && !raw_ready()) return fail(PEBBLEGPU_E_INVALID, "raw-format input reached a spectrum kernel that has no converting loads");
+    if (raw && !(raw_ready() || raw_ready_big())) return fail(PEBBLEGPU_E_INVALID, "raw-format input reached a spectrum kernel that has no converting loads");
     if (any) {
         if (raw || df) return fail(PEBBLEGPU_E_INVALID, "the general display transform takes float2 input and runs no decimator");
         return run_any(s, d_in, in_pitch, F, d_out, (int)nf, true);
@@ -2099,6 +2185,20 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
                 launch(k_big_rows, dim3((unsigned)(cdiv(F, G) * 8), nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch, (const float2 *)d_tw_nf,
                        (const float *)d_prev[parity] + s0 * kBigN, d_prev[parity ^ 1] + s0 * kBigN, sp);
             } else {
+                if (raw) {  // (the stream offset is in IQ pairs of the raw format: the kernel gets the batch's base)
+                    RawSrc rs = *raw;
+                    rs.base = static_cast<const char *>(raw->base) + (size_t)(s0 * in_pitch) * kRawPairBytes[raw->fmt];
+                    const bool b8 = raw->fmt == 0 || raw->fmt == 1;  // 8-bit pairs: the paired tile order (kernels_spectrum.h)
+                    const dim3 grid(b8 ? (unsigned)(16 * cdiv(F, 2)) : (unsigned)(F * 8), nb);
+                    auto go = [&](auto kern) { launch(kern, grid, dim3(256), s, (long long)in_pitch, d_Y, (const float *)d_window, (long long)F, rs); };
+                    switch (raw->fmt) {
+                    case 0: go(k_big256_cols_raw<0>); break;
+                    case 1: go(k_big256_cols_raw<1>); break;
+                    case 2: go(k_big256_cols_raw<2>); break;
+                    case 3: go(k_big256_cols_raw<3>); break;
+                    default: go(k_big256_cols_raw<4>); break;
+                    }
+                } else
                 launch(k_big256_cols, dim3((unsigned)(F * 8), nb), dim3(256), s, d_in + s0 * in_pitch, (long long)in_pitch, d_Y, (const float *)d_window, (long long)F);
                 launch(k_big256_rows, dim3((unsigned)(cdiv(F, G) * 8), nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch,
                        (const float *)d_prev[parity] + s0 * kBigN, d_prev[parity ^ 1] + s0 * kBigN, sp);

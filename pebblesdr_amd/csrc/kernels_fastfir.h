@@ -14,6 +14,7 @@
 #pragma once
 #include "fft_lds.h"
 #include "fft_t128.h"
+#include "params.h"
 
 namespace pg {
 
@@ -122,6 +123,78 @@ static __global__ __launch_bounds__(128) void k_fastfir_t128(const float2 *__res
         v[m] = make_float2(p.x, -p.y);                // conj: IFFT(z) = conj(FFT(conj(z))), unscaled (1/N is in the taps)
     }
     fft2048_t128(v, lds, tw_lds, t, [] { __syncthreads(); });  // (the forward transform ends behind a barrier: the image is free)
+    float2 *y = out + (long long)c * out_pitch + b * L;
+#pragma unroll
+    for (int m = 0; m < E; m++) {
+        const int i = t + 128 * m;
+        if (i >= overlap) y[i - overlap] = make_float2(v[m].x, -v[m].y);
+    }
+}
+
+// k_fastfir_t128 for the stream bank's raw calls: the new samples are read in the device's own sample format (RawSrc,
+// pebblegpu_iq_format FMT; `in_pitch` counts IQ pairs) and converted in the load, point by point in the same t + 128 m layout -- a wave
+// instruction fetches 64 adjacent pairs (128 bytes of int8 pairs, 256 of int16): as many load instructions as the float2 kernel issues,
+// for a quarter or half of the bytes, and no exchange in front of the transform.  raw_load1 rounds the product with the scale on its
+// own: the first butterfly ADDS converted samples, and a fused multiply-add there would differ from the float2 route in the last bit.
+// The overlap of block 0 still comes from the float2 `tail` (never null here: it lies in front of the caller's buffer), and `tail_out`
+// receives CONVERTED samples, so raw and float2 calls continue each other exactly.  Twiddles through the vector cache, as the stream
+// bank's float2 default.  A kernel of its own rather than a parameter of the one above: written as one body with two entry points,
+// k_fastfir_t128<false> came out at 126 registers instead of 96, and the receivers run that instance.
+template <int FMT>
+static __global__ __launch_bounds__(128) void k_fastfir_t128_raw(long long in_pitch, float2 *__restrict__ out, long long out_pitch,
+                                                                 const float2 *__restrict__ H, const float2 *__restrict__ tw128,
+                                                                 int overlap /* taps-1 */, const float2 *__restrict__ tail,
+                                                                 float2 *__restrict__ tail_out /* or null, as above */,
+                                                                 int nb, int nchan, RawSrc raw)
+{
+    constexpr int N = 2048, E = 16;
+    __shared__ float2 lds[FftLds<N>::kSlots];
+    const int t = threadIdx.x;
+    const int L = N - overlap;
+    int c;
+    long long b;
+    if (nchan > 0) {  // the XCD-ordered one-dimensional grid, as above
+        const long long total = (long long)nb * nchan, per = (total + 7) >> 3;
+        const long long q = (long long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
+        if ((long long)(blockIdx.x >> 3) >= per || q >= total) return;  // (uniform: the whole workgroup)
+        c = (int)(q / nb);
+        b = q - (long long)c * nb;
+    } else {
+        c = blockIdx.y;
+        b = blockIdx.x;
+        nb = (int)gridDim.x;
+    }
+    const long long x0 = (long long)c * in_pitch + b * L - overlap;  // first sample of [overlap | new]
+    const float2 *h = H + (long long)c * N;
+    float2 v[E];
+    if (b == 0) {
+        const float2 *tl = tail + (long long)c * overlap;
+#pragma unroll
+        for (int m = 0; m < E; m++) {
+            const int i = t + 128 * m;
+            if (i < overlap) v[m] = tl[i];
+            else v[m] = raw_load1<FMT>(raw, x0 + i);  // (x0 + i >= c * in_pitch: nothing in front of the row is read)
+        }
+    } else {
+#pragma unroll
+        for (int m = 0; m < E; m++) v[m] = raw_load1<FMT>(raw, x0 + t + 128 * m);
+    }
+    if (tail_out != nullptr && b == (long long)nb - 1) {
+        float2 *to = tail_out + (long long)c * overlap;
+#pragma unroll
+        for (int m = 0; m < E; m++) {
+            const int i = t + 128 * m;
+            if (i >= L) to[i - L] = v[m];
+        }
+    }
+    __syncthreads();
+    fft2048_t128(v, lds, tw128, t, [] { __syncthreads(); });
+#pragma unroll
+    for (int m = 0; m < E; m++) {
+        const float2 p = cmul(h[t + 128 * m], v[m]);
+        v[m] = make_float2(p.x, -p.y);
+    }
+    fft2048_t128(v, lds, tw128, t, [] { __syncthreads(); });
     float2 *y = out + (long long)c * out_pitch + b * L;
 #pragma unroll
     for (int m = 0; m < E; m++) {

@@ -1055,17 +1055,37 @@ static __global__ __launch_bounds__(256, 2) void k_big_rows(const float2 *__rest
 constexpr int kBig256 = 256;
 
 // grid (frames * 8, S), block 256.  Y layout: [stream][frame][k1][n2]
-static __global__ __launch_bounds__(256, 2) void k_big256_cols(const float2 *__restrict__ in, long long in_pitch, float2 *__restrict__ Y,
-                                                               const float *__restrict__ window, long long n_frames)
+//
+// FMT >= 0 (k_big256_cols_raw, the stream bank's raw calls): the frames are read in the device's own sample format (RawSrc,
+// pebblegpu_iq_format FMT; `in_pitch` counts IQ pairs) and converted in the load.  The tile stays 32 columns: 256-byte row segments of
+// float pairs, whole 128-byte lines of int16 pairs.  Of 8-bit pairs a row segment is HALF a line (64 bytes), and with tile =
+// blockIdx.x & 7 the workgroup that wants the other half sits on another XCD, behind another L2: both would fetch the whole line.  So
+// the 8-bit instances deal the tiles differently -- grid (8 * 2 * ceil(frames / 2), S): an XCD takes ONE pair of tiles (one run of
+// lines) of every second frame, the two halves in consecutive workgroups of that XCD, and the second finds the line in its L2.
+template <int FMT>
+__device__ __forceinline__ void big256_cols_body(const float2 *__restrict__ in, long long in_pitch, float2 *__restrict__ Y,
+                                                 const float *__restrict__ window, long long n_frames, const RawSrc &raw)
 {
     __shared__ float2 T[256 * 32];   // [cc * 16 + b][column]
     __shared__ float2 tw[256];       // W_256^m
     const int t = threadIdx.x, c = t & 31, j = t >> 5;
     const int s = blockIdx.y;
-    const long long f = blockIdx.x >> 3;
-    const int n2 = ((blockIdx.x & 7) << 5) + c;
+    long long f;
+    int tile;
+    if (FMT == 0 || FMT == 1) {
+        const int xcd = blockIdx.x & 7;
+        const long long k = blockIdx.x >> 3;
+        tile = ((xcd & 3) << 1) | (int)(k & 1);
+        f = ((k >> 1) << 1) | (xcd >> 2);
+        if (f >= n_frames) return;  // (uniform: an odd number of frames leaves the last pair half empty)
+    } else {
+        f = blockIdx.x >> 3;
+        tile = blockIdx.x & 7;
+    }
+    const int n2 = (tile << 5) + c;
     tw[t] = cis_cycles(-(double)t / 256.0);
-    const float2 *x = in + (long long)s * in_pitch + f * kBigN + n2;
+    const long long x0 = (long long)s * in_pitch + f * kBigN + n2;
+    const float2 *x = FMT >= 0 ? nullptr : in + x0;  // (the raw instances have no float2 input)
     const float *w = window + n2;
     float2 u[2][16];
 #pragma unroll
@@ -1073,7 +1093,8 @@ static __global__ __launch_bounds__(256, 2) void k_big256_cols(const float2 *__r
 #pragma unroll
         for (int a = 0; a < 16; a++) {
             const int n1 = 16 * a + j + 8 * h;
-            u[h][a] = cscale(x[(long long)kBig256 * n1], w[kBig256 * n1]);
+            if (FMT >= 0) u[h][a] = cscale(raw_load1<FMT < 0 ? 0 : FMT>(raw, x0 + (long long)kBig256 * n1), w[kBig256 * n1]);
+            else u[h][a] = cscale(x[(long long)kBig256 * n1], w[kBig256 * n1]);
         }
     __syncthreads();  // (the twiddle table)
 #pragma unroll
@@ -1104,6 +1125,17 @@ static __global__ __launch_bounds__(256, 2) void k_big256_cols(const float2 *__r
             ph = cmul(w16, ph);
         }
     }
+}
+static __global__ __launch_bounds__(256, 2) void k_big256_cols(const float2 *__restrict__ in, long long in_pitch, float2 *__restrict__ Y,
+                                                               const float *__restrict__ window, long long n_frames)
+{
+    big256_cols_body<-1>(in, in_pitch, Y, window, n_frames, RawSrc{nullptr, 0, 0, 0.f, 0});
+}
+template <int FMT>
+static __global__ __launch_bounds__(256, 2) void k_big256_cols_raw(long long in_pitch, float2 *__restrict__ Y, const float *__restrict__ window,
+                                                                   long long n_frames, RawSrc raw)
+{
+    big256_cols_body<FMT>(nullptr, in_pitch, Y, window, n_frames, raw);
 }
 
 // grid (ceil(n_frames / G) * 8, S), block 256: rows k1 = 32 (blockIdx.x & 7) + 16 pass + (t >> 4), sixteen work-items per row

@@ -159,6 +159,18 @@ struct RawSrc {
     float scale;
     int pad_;
 };
+
+// the format's constant folded into the gain (deviceinterfacebase.cpp:651,689,729; wavfile.cpp:299-300), rounded once to float
+inline float raw_scale(int fmt, double gain)
+{
+    double scale = gain;
+    if (fmt == 0 || fmt == 1) scale *= 1 / 128.0;
+    else if (fmt == 2) scale *= 1 / 32768.0;
+    else if (fmt == 4) scale *= 1 / 32767.0;
+    return (float)scale;
+}
+constexpr size_t kRawPairBytes[5] = {2, 2, 4, 8, 4};  // bytes per IQ pair: CPX8, CPXU8, CPX16, CPXFLOAT, WAV PCM16
+
 __device__ __forceinline__ float2 raw_load(const RawSrc &r, long long i)
 {
     float a, b;
@@ -177,6 +189,30 @@ __device__ __forceinline__ float2 raw_load(const RawSrc &r, long long i)
     }
     a *= r.scale;
     b *= r.scale;
+    return make_float2((r.order & 1) == 0 ? a : b, (r.order == 1 || r.order == 2) ? a : b);
+}
+
+// raw_load with the sample format a template constant, for kernels whose first use of a converted sample is an addition (the band-pass's
+// first butterfly): the product with the scale is rounded on its own (__fmul_rn is never contracted into a fused multiply-add), so
+// the sample is bit for bit what k_normalize_iq writes
+template <int FMT>
+__device__ __forceinline__ float2 raw_load1(const RawSrc &r, long long i)
+{
+    float a, b;
+    if (FMT == 0 || FMT == 1) {  // (the pair as ONE 2-byte load: char2 / uchar2 came out as two byte loads)
+        const unsigned w = reinterpret_cast<const unsigned short *>(r.base)[i];
+        a = FMT == 0 ? (float)((int)(w << 24) >> 24) : (float)(w & 0xFFu) - 128.0f;
+        b = FMT == 0 ? (float)((int)(w << 16) >> 24) : (float)(w >> 8) - 128.0f;
+    } else if (FMT == 2 || FMT == 4) {
+        const unsigned w = reinterpret_cast<const unsigned *>(r.base)[i];
+        a = (float)((int)(w << 16) >> 16);
+        b = (float)((int)w >> 16);
+    } else {
+        const float2 v = reinterpret_cast<const float2 *>(r.base)[i];
+        a = v.x; b = v.y;
+    }
+    a = __fmul_rn(a, r.scale);
+    b = __fmul_rn(b, r.scale);
     return make_float2((r.order & 1) == 0 ? a : b, (r.order == 1 || r.order == 2) ? a : b);
 }
 

@@ -17,6 +17,7 @@
 #include "../../include/pebblegpu.h"
 #include "common.h"
 #include "design.h"
+#include "ingest.h"
 #include "params.h"
 #include "tuning.h"
 
@@ -225,7 +226,11 @@ struct FastFirCore {
     // caller-owned rows without head-room; d_tail [C][taps-1] carries the overlap between calls and is refreshed here
     // d_tail_next (2048-point plan only): a second [C][taps-1] buffer that receives the next call's overlap straight from the
     // kernel (the caller alternates the two) instead of a copy launched behind it
-    int run_ext(hipStream_t s, const float2 *in, long long in_pitch, float2 *d_tail, long long n, float2 *out, long long out_pitch, float2 *d_tail_next = nullptr);
+    // raw (2048-point plan with both tail buffers only): the rows are still in the device's sample format (`in` unused, in_pitch in IQ
+    // pairs) and converted in the kernel's loads; the overlap buffers stay float2 and hold converted samples
+    int run_ext(hipStream_t s, const float2 *in, long long in_pitch, float2 *d_tail, long long n, float2 *out, long long out_pitch, float2 *d_tail_next = nullptr,
+                const RawSrc *raw = nullptr);
+    bool raw_ready() const { return fft_n == 2048; }  // k_fastfir_t128_raw exists for this plan
 };
 
 // ---- Demod_AM ----
@@ -514,7 +519,8 @@ struct SpectrumCore {
     int init_list();
     int run_list(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw = nullptr);
     bool dec_ready() const { return !big && !per_q && bins == 8192 && !use_w64; }  // k_spectrum_t128<.., DEC> exists for this plan
-    bool raw_ready() const { return !big && !per_q && bins == 8192; }  // k_spectrum_t128 converts in its loads
+    bool raw_ready() const { return !big && !any && !per_q && bins == 8192; }  // k_spectrum_t128 converts in its loads (2048-sample frames only)
+    bool raw_ready_big() const { return big && !tun.big_split32; }      // k_big256_cols_raw converts in its loads (the stream bank's raw calls)
 };
 
 // HIP events around each kernel group, kept for the last kRing calls so a caller can run calls back to back
@@ -677,13 +683,7 @@ private:
     SpectrumCore spec_, zoom_;
     float2 *d_stage_in_ = nullptr;
     float2 *d_raw_stage_ = nullptr;   // process_raw: the normalised copy of a raw device-format call (allocated on first use)
-    struct IngestSlot {
-        void *h = nullptr, *d = nullptr;      // pinned host buffer and its device twin
-        size_t cap = 0, submitted = 0;
-        hipEvent_t uploaded = nullptr, done_main = nullptr, done_chain = nullptr;
-        bool in_flight = false;               // a call that reads the device twin has been queued and not waited for
-    } ingest_[2];
-    hipStream_t copy_stream_ = nullptr;
+    IngestRing ingest_;               // the pinned double buffer of ingest_acquire / _submit / process_ingested (ingest.h)
     std::vector<float> h_frame_, h_out_;
     uint64_t acc_frames_ = 0;
 };

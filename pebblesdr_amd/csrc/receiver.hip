@@ -113,13 +113,8 @@ Receiver::~Receiver()
     if (chain_stream_) (void)hipStreamSynchronize(chain_stream_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     osc_.release(); dec_.release(); ff_.release(); am_.release(); nfm_.release(); sam_.release(); wfmc_.release(); spec_.release(); zoom_.release();
-    if (copy_stream_) { (void)hipStreamSynchronize(copy_stream_); (void)hipStreamDestroy(copy_stream_); }
     for (hipEvent_t e : sync_ev_) if (e) (void)hipEventDestroy(e);
-    for (IngestSlot &g : ingest_) {
-        if (g.h) (void)hipHostFree(g.h);
-        if (g.d) (void)hipFree(g.d);
-        for (hipEvent_t e : {g.uploaded, g.done_main, g.done_chain}) if (e) (void)hipEventDestroy(e);
-    }
+    ingest_.release();
     if (d_zoom) (void)hipFree(d_zoom);
     if (map_ev_) (void)hipEventDestroy(map_ev_);
     agc_.release(); resamp_.release(); cond_.release(); anf_.release();
@@ -846,74 +841,22 @@ int Receiver::process_raw(int fmt, int order, double gain, const void *d_raw, ui
     if (!d_raw || n == 0) return fail(PEBBLEGPU_E_INVALID, "null input or zero samples");
     if (fmt < 0 || fmt > 4 || order < 0 || order > 3) return fail(PEBBLEGPU_E_INVALID, "unknown sample format %d / IQ order %d", fmt, order);
     if (n > (uint64_t)max_sf * superframe) return fail(PEBBLEGPU_E_SIZE, "%llu samples exceed this object's capacity", (unsigned long long)n);
-    double scale = gain;
-    if (fmt == 0 || fmt == 1) scale *= 1 / 128.0;        // deviceinterfacebase.cpp:651,689
-    else if (fmt == 2) scale *= 1 / 32768.0;             // :729
-    else if (fmt == 4) scale *= 1 / 32767.0;             // wavfile.cpp:299-300
-    const RawSrc raw{d_raw, fmt, order, (float)scale, 0};
+    const RawSrc raw{d_raw, fmt, order, raw_scale(fmt, gain), 0};
     return process(nullptr, n, bins != 0, true, &raw);
 }
 
-// ---- host ingest: pinned double buffer (the library owns the pinned host buffers; the producer side of
-// plugins/HackRFDevice/hackrfdevice.cpp:533-566 writes into them instead of into its own ring) ----
-int Receiver::ingest_acquire(uint32_t slot, uint64_t bytes, void **host_ptr)
-{
-    if (slot > 1 || !host_ptr || bytes == 0) return fail(PEBBLEGPU_E_INVALID, "ingest slot is 0 or 1, bytes > 0");
-    PG_HIP(hipSetDevice(device));
-    IngestSlot &g = ingest_[slot];
-    if (g.in_flight) {  // the call that read this slot's device copy (and the upload before it) must be over before the host refills it
-        PG_HIP(hipEventSynchronize(g.done_main));
-        PG_HIP(hipEventSynchronize(g.done_chain));
-        g.in_flight = false;
-    }
-    if (!copy_stream_) PG_HIP(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
-    if (!g.uploaded) {
-        PG_HIP(hipEventCreateWithFlags(&g.uploaded, hipEventDisableTiming));
-        PG_HIP(hipEventCreateWithFlags(&g.done_main, hipEventDisableTiming));
-        PG_HIP(hipEventCreateWithFlags(&g.done_chain, hipEventDisableTiming));
-    }
-    if (g.cap < bytes) {
-        PG_HIP(hipStreamSynchronize(copy_stream_));
-        if (g.h) (void)hipHostFree(g.h);
-        if (g.d) (void)hipFree(g.d);
-        g.h = g.d = nullptr;
-        g.cap = 0;
-        PG_HIP(hipHostMalloc(&g.h, bytes));
-        PG_HIP(hipMalloc(&g.d, bytes));
-        g.cap = bytes;
-    }
-    g.submitted = 0;
-    *host_ptr = g.h;
-    return 0;
-}
-int Receiver::ingest_submit(uint32_t slot, uint64_t bytes)
-{
-    if (slot > 1) return fail(PEBBLEGPU_E_INVALID, "ingest slot is 0 or 1");
-    IngestSlot &g = ingest_[slot];
-    if (!g.h || bytes == 0 || bytes > g.cap) return fail(PEBBLEGPU_E_SIZE, "%llu bytes do not fit the slot acquired (%zu)", (unsigned long long)bytes, g.cap);
-    if (g.in_flight) return fail(PEBBLEGPU_E_INVALID, "the slot's previous call is still in flight: acquire it again first");
-    PG_HIP(hipSetDevice(device));
-    PG_HIP(hipMemcpyAsync(g.d, g.h, bytes, hipMemcpyHostToDevice, copy_stream_));
-    PG_HIP(hipEventRecord(g.uploaded, copy_stream_));
-    g.submitted = bytes;
-    return 0;
-}
+// ---- host ingest: the pinned double buffer (ingest.h) ----
+int Receiver::ingest_acquire(uint32_t slot, uint64_t bytes, void **host_ptr) { return ingest_.acquire(device, slot, bytes, host_ptr); }
+int Receiver::ingest_submit(uint32_t slot, uint64_t bytes) { return ingest_.submit(device, slot, bytes); }
 int Receiver::process_ingested(uint32_t slot, int fmt, int order, double gain, uint64_t n)
 {
-    if (slot > 1) return fail(PEBBLEGPU_E_INVALID, "ingest slot is 0 or 1");
-    IngestSlot &g = ingest_[slot];
-    if (fmt < 0 || fmt > 4) return fail(PEBBLEGPU_E_INVALID, "unknown sample format %d", fmt);
-    static const size_t kPair[5] = {2, 2, 4, 8, 4};  // bytes per IQ pair: CPX8, CPXU8, CPX16, CPXFLOAT, WAV PCM16
-    if (!g.submitted || (uint64_t)S * n * kPair[fmt] > g.submitted) return fail(PEBBLEGPU_E_SIZE, "the slot holds %zu submitted bytes; %llu samples of this format need more", g.submitted, (unsigned long long)n);
+    IngestSlot *g = nullptr;
+    if (int rc = ingest_.check(slot, fmt, (uint64_t)S * n, n, &g)) return rc;
     PG_HIP(hipSetDevice(device));
     // both of the call's streams read the raw samples (the display transform and the chain's first stage convert in their own loads)
-    PG_HIP(hipStreamWaitEvent(stream_, g.uploaded, 0));
-    PG_HIP(hipStreamWaitEvent(chain_stream_, g.uploaded, 0));
-    if (int rc = process_raw(fmt, order, gain, g.d, n)) return rc;
-    PG_HIP(hipEventRecord(g.done_main, stream_));
-    PG_HIP(hipEventRecord(g.done_chain, chain_stream_));
-    g.in_flight = true;
-    return 0;
+    if (int rc = ingest_.wait_upload(*g, stream_, chain_stream_)) return rc;
+    if (int rc = process_raw(fmt, order, gain, g->d, n)) return rc;
+    return ingest_.mark_in_flight(*g, stream_, chain_stream_);
 }
 
 const char *Receiver::kernel_name(int which) const

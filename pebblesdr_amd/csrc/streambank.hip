@@ -16,7 +16,14 @@ struct pebblegpu_streambank {
     uint64_t cap = 0, last_n = 0, last_frames = 0;
     hipEvent_t ev[4] = {};
     bool timed = false;
+    float2 *d_raw_stage = nullptr;   // raw calls of a geometry without converting loads: the normalised copy (allocated on first use)
+    pg::IngestRing ingest;           // the pinned double buffer of pebblegpu_streambank_ingest_* (ingest.h)
+    int last_fmt = -1;               // the last call's route, for pebblegpu_streambank_kernel_name: -1 float2 input, else the raw format
+    bool last_staged = false, last_bp = false, last_sp = false;
 };
+
+// every kernel a raw call would run converts in its own loads (else the call is staged through k_normalize_iq as a whole)
+static bool sb_converts(const pebblegpu_streambank *sb) { return sb->ff.raw_ready() && (sb->sp.raw_ready() || sb->sp.raw_ready_big()); }
 
 extern "C" {
 
@@ -34,7 +41,8 @@ int pebblegpu_streambank_destroy(pebblegpu_streambank *sb)
     }
     sb->ff.release();
     sb->sp.release();
-    void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec};
+    sb->ingest.release();
+    void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec, sb->d_raw_stage};
     for (void *q : p) if (q) (void)hipFree(q);
     for (hipEvent_t e : sb->ev) if (e) (void)hipEventDestroy(e);
     delete sb;
@@ -94,13 +102,16 @@ int pebblegpu_streambank_set_bandpass(pebblegpu_streambank *sb, uint32_t stream,
     return 0;
 }
 
-int pebblegpu_streambank_process(pebblegpu_streambank *sb, const void *d_iq, uint64_t n, uint32_t what)
+// the checks every process call makes before anything is queued
+static int sb_check_n(const pebblegpu_streambank *sb, uint64_t n)
 {
-    if (!sb || (!d_iq && n)) return fail(PEBBLEGPU_E_INVALID, "null argument");
     if (n % sb->cfg.frame) return fail(PEBBLEGPU_E_SIZE, "n_samples %llu is not a multiple of the frame %u", (unsigned long long)n, sb->cfg.frame);
     if (n > sb->cap) return fail(PEBBLEGPU_E_SIZE, "n_samples %llu above the capacity %llu", (unsigned long long)n, (unsigned long long)sb->cap);
-    PG_HIP(hipSetDevice(sb->cfg.device));
-    const float2 *in = static_cast<const float2 *>(d_iq);
+    return 0;
+}
+// one call: float2 rows `in`, or (raw != nullptr) rows still in the device's sample format that the kernels convert in their loads
+static int sb_run(pebblegpu_streambank *sb, const float2 *in, const pg::RawSrc *raw, uint64_t n, uint32_t what)
+{
     sb->last_n = 0;
     sb->last_frames = 0;
     if (n == 0) return 0;
@@ -115,16 +126,18 @@ int pebblegpu_streambank_process(pebblegpu_streambank *sb, const void *d_iq, uin
     sb->side = side;
     hipStream_t fs = side ? sb->stream2 : sb->stream;
     if (side) PG_HIP(hipStreamWaitEvent(fs, sb->ev[0], 0));
+    sb->last_bp = (what & 1u) != 0;
+    sb->last_sp = (what & 2u) != 0;
     if (what & 1u) {
         float2 *next = sb->ff.fft_n == 2048 ? sb->d_tail_alt : nullptr;
-        if (int rc = sb->ff.run_ext(fs, in, (long long)n, sb->d_tail, (long long)n, sb->d_filt, (long long)n, next)) return rc;
+        if (int rc = sb->ff.run_ext(fs, in, (long long)n, sb->d_tail, (long long)n, sb->d_filt, (long long)n, next, raw)) return rc;
         if (next) std::swap(sb->d_tail, sb->d_tail_alt);
         sb->last_n = n;
     }
     PG_HIP(hipEventRecord(sb->ev[1], fs));
     if (what & 2u) {
         const long long F = (long long)(n / sb->cfg.frame);
-        if (int rc = sb->sp.run(sb->stream, in, (long long)n, F, sb->d_spec, nullptr, nullptr, !side)) return rc;
+        if (int rc = sb->sp.run(sb->stream, in, (long long)n, F, sb->d_spec, raw, nullptr, !side)) return rc;
         sb->last_frames = (uint64_t)F;
     }
     if (side) {
@@ -134,6 +147,104 @@ int pebblegpu_streambank_process(pebblegpu_streambank *sb, const void *d_iq, uin
     PG_HIP(hipEventRecord(sb->ev[2], sb->stream));
     sb->timed = true;
     return 0;
+}
+
+int pebblegpu_streambank_process(pebblegpu_streambank *sb, const void *d_iq, uint64_t n, uint32_t what)
+{
+    if (!sb || (!d_iq && n)) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (int rc = sb_check_n(sb, n)) return rc;
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    sb->last_fmt = -1;
+    sb->last_staged = false;
+    return sb_run(sb, static_cast<const float2 *>(d_iq), nullptr, n, what);
+}
+
+// the argument checks of a raw call, before anything is queued
+static int sb_check_raw(const pebblegpu_streambank *sb, int fmt, int order, const void *d_raw, uint64_t n)
+{
+    if (!d_raw && n) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (fmt < 0 || fmt > 4 || order < 0 || order > 3) return fail(PEBBLEGPU_E_INVALID, "unknown sample format %d / IQ order %d", fmt, order);
+    if (int rc = sb_check_n(sb, n)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_raw) % PEBBLEGPU_RAW_ALIGN) return fail(PEBBLEGPU_E_INVALID, "d_raw must be aligned to %d bytes", PEBBLEGPU_RAW_ALIGN);
+    return 0;
+}
+// a raw call behind its checks.  Where every kernel converts in its loads no float2 copy of the streams exists; every other geometry is
+// staged as a whole: k_normalize_iq on the bank's stream into a float2 buffer of the bank's capacity, then the ordinary call.
+// Either way the band-pass's overlap buffers hold CONVERTED samples, so raw and float2 calls continue each other.
+static int sb_run_raw(pebblegpu_streambank *sb, int fmt, int order, double gain, const void *d_raw, uint64_t n, uint32_t what)
+{
+    const pg::RawSrc raw{d_raw, fmt, order, pg::raw_scale(fmt, gain), 0};
+    sb->last_fmt = fmt;
+    sb->last_staged = !sb_converts(sb);
+    if (!sb->last_staged || n == 0) return sb_run(sb, nullptr, &raw, n, what);
+    const size_t S = sb->cfg.n_streams;
+    if (!sb->d_raw_stage) PG_HIP(hipMalloc((void **)&sb->d_raw_stage, sizeof(float2) * S * sb->cap));
+    // (the rows of d_raw are n pairs apart, so S * n pairs are one run; the side stream forks behind it, at the call's start event)
+    if (int rc = pg::run_normalize_iq(fmt, order, 1.0, d_raw, (long long)(S * n), sb->d_raw_stage, sb->stream, false, &raw.scale)) return rc;
+    return sb_run(sb, sb->d_raw_stage, nullptr, n, what);
+}
+
+int pebblegpu_streambank_process_raw(pebblegpu_streambank *sb, int format, int iq_order, double gain, const void *d_raw, uint64_t n, uint32_t what)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (int rc = sb_check_raw(sb, format, iq_order, d_raw, n)) return rc;
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    return sb_run_raw(sb, format, iq_order, gain, d_raw, n, what);
+}
+
+int pebblegpu_streambank_ingest_acquire(pebblegpu_streambank *sb, uint32_t slot, uint64_t bytes, void **host_ptr)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return sb->ingest.acquire(sb->cfg.device, slot, bytes, host_ptr);
+}
+int pebblegpu_streambank_ingest_submit(pebblegpu_streambank *sb, uint32_t slot, uint64_t bytes)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return sb->ingest.submit(sb->cfg.device, slot, bytes);
+}
+int pebblegpu_streambank_process_ingested(pebblegpu_streambank *sb, uint32_t slot, int format, int iq_order, double gain, uint64_t n, uint32_t what)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    pg::IngestSlot *g = nullptr;
+    if (int rc = sb->ingest.check(slot, format, (uint64_t)sb->cfg.n_streams * n, n, &g)) return rc;
+    if (int rc = sb_check_raw(sb, format, iq_order, g->d, n)) return rc;
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    // both streams may read the raw samples (PEBBLEGPU_SB_SIDE=1: the band-pass runs on the second one)
+    if (int rc = sb->ingest.wait_upload(*g, sb->stream, sb->stream2)) return rc;
+    if (int rc = sb_run_raw(sb, format, iq_order, gain, g->d, n, what)) return rc;
+    return sb->ingest.mark_in_flight(*g, sb->stream, sb->stream2);
+}
+
+const char *pebblegpu_streambank_kernel_name(const pebblegpu_streambank *sb, int which)
+{
+    if (!sb || !sb->timed) return "";
+    static const char *const kFf[6] = {"k_fastfir_t128", "k_fastfir_t128 (raw s8)", "k_fastfir_t128 (raw u8)", "k_fastfir_t128 (raw s16)",
+                                       "k_fastfir_t128 (raw f32)", "k_fastfir_t128 (raw wav16)"};
+    static const char *const kBig[6] = {"k_big256_cols + k_big256_rows", "k_big256_cols (raw s8) + k_big256_rows", "k_big256_cols (raw u8) + k_big256_rows",
+                                        "k_big256_cols (raw s16) + k_big256_rows", "k_big256_cols (raw f32) + k_big256_rows",
+                                        "k_big256_cols (raw wav16) + k_big256_rows"};
+    static const char *const kT128[6] = {"k_spectrum_t128", "k_spectrum_t128 (raw s8)", "k_spectrum_t128 (raw u8)", "k_spectrum_t128 (raw s16)",
+                                         "k_spectrum_t128 (raw f32)", "k_spectrum_t128 (raw wav16)"};
+    static const char *const kW64[6] = {"k_spectrum_w64", "k_spectrum_w64 (raw s8)", "k_spectrum_w64 (raw u8)", "k_spectrum_w64 (raw s16)",
+                                        "k_spectrum_w64 (raw f32)", "k_spectrum_w64 (raw wav16)"};
+    const int r = sb->last_fmt >= 0 && !sb->last_staged ? sb->last_fmt + 1 : 0;  // 0: the float2 instances
+    const pg::SpectrumCore &sp = sb->sp;
+    if (which == 1) {
+        if (!sb->last_bp) return "";
+        if (sb->ff.fft_n == 2048) return sb->last_staged ? "k_normalize_iq + k_fastfir_t128" : kFf[r];
+        return sb->last_staged ? "k_normalize_iq + k_fastfir" : "k_fastfir";
+    }
+    if (which == 2) {
+        if (!sb->last_sp) return "";
+        if (sp.big && sp.tun.big_split32) return sb->last_staged ? "k_normalize_iq + k_big_cols + k_big_rows" : "k_big_cols + k_big_rows";
+        if (sp.big) return sb->last_staged ? "k_normalize_iq + k_big256_cols + k_big256_rows" : kBig[r];
+        if (sp.any) return sb->last_staged ? "k_normalize_iq + k_spectrum_any" : "k_spectrum_any";
+        if (sp.per_q) return sb->last_staged ? "k_normalize_iq + k_spectrum_q128" : "k_spectrum_q128";
+        if (sp.bins == 8192) return sb->last_staged ? (sp.use_w64 ? "k_normalize_iq + k_spectrum_w64" : "k_normalize_iq + k_spectrum_t128") : sp.use_w64 ? kW64[r] : kT128[r];
+        if (sp.bins == 4096) return sb->last_staged ? "k_normalize_iq + k_spectrum<2>" : "k_spectrum<2>";
+        return sb->last_staged ? "k_normalize_iq + k_spectrum_1to1" : "k_spectrum_1to1";
+    }
+    return "";
 }
 
 const void *pebblegpu_streambank_filtered(const pebblegpu_streambank *sb, uint64_t *n, uint64_t *pitch)
