@@ -366,6 +366,69 @@ const void *pebblegpu_receiver_signal_strength(const pebblegpu_receiver *rx, uin
  *     for several super-frames per call: a threshold above -120 is PEBBLEGPU_E_UNSUPPORTED (-120 and below, "never closes", is
  *     accepted and does nothing). */
 int pebblegpu_set_squelch(pebblegpu_receiver *rx, uint32_t channel, double squelch_db);
+/* ------------------------------------------------------------------------------------------------
+ * Test bench on the batched device path: the generator at the head of Receiver::processIQData (application/receiver.cpp:797-798,
+ * TestBench::genSweep then TestBench::genNoise, application/testbench.cpp:518-544 -> NCO::genSweep / NCO::genNoise,
+ * pebblelib/nco.cpp:87-212) and taps at the points where the reference hands the signal to its scope (displayData, receiver.cpp:803,
+ * 945, 953, 992) and to the digital modem (:979-980).  Everything is off by default; with both generators off and no tap set a call is
+ * what it was before these entry points existed.  Batched path only: pebblegpu_process_iq, whose `in` is a host CPX * the host can
+ * inject into and display itself, refuses a call while a generator or a tap is on (PEBBLEGPU_E_UNSUPPORTED).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct pebblegpu_sweep {            /* NCO::initSweep (nco.cpp:119-137) + what TestBench::genSweep passes (testbench.cpp:518-526) */
+    uint32_t struct_size;                   /* = sizeof(pebblegpu_sweep) */
+    int32_t  sweep_type;                    /* NCO::SweepType, nco.h:52: 0 SINGLE, 1 REPEAT, 2 REPEAT_REVERSE */
+    double   start_hz, stop_hz, rate_hz_per_s;
+    double   pulse_width_s, pulse_period_s; /* width <= 0: no pulse modulation (nco.cpp:149) */
+    double   amplitude;                     /* m_signalAmplitude, linear (m_ampMax * dBToAmplitude(dB), testbench.cpp:563) */
+    int32_t  mix;                           /* genMixBox (testbench.cpp:521): 1 add to the input, 0 replace it */
+    uint32_t reserved[3];
+} pebblegpu_sweep;
+/* What the library makes of a sweep, on the host, no device needed: leg_samples = samples from the start frequency until the frequency
+ * reaches the stop frequency (nco.cpp:188-189; 0: never -- rate <= 0 keeps the frequency, nco.cpp:181); pulse_period_samples /
+ * pulse_on_samples = the reference's serial pulse timer (m_sweepPulseTimer += 1 / fs, reset once it exceeds the period, amplitude 0
+ * while it exceeds the width, nco.cpp:149-156) run once in double as the reference runs it: of every pulse_period_samples samples the
+ * first pulse_on_samples and the last one carry the signal (0, 0: no pulse modulation).  Refused: legs shorter than 64 samples and
+ * pulse periods of 2^28 samples or more (PEBBLEGPU_E_UNSUPPORTED; the setter runs the timer's sum once, one addition per sample of a period), non-finite values, an unknown type (PEBBLEGPU_E_INVALID). */
+int pebblegpu_sweep_plan(double sample_rate, const pebblegpu_sweep *s, uint64_t *leg_samples, uint64_t *pulse_period_samples,
+                         uint64_t *pulse_on_samples);
+/* TestBench::reset() + the generator switch of a receiver (s == NULL: sweep off).  Every call of either setter restarts the sweep at
+ * start_hz with phase 0 and pulse timer 0 and the noise counter at 0.  From then on sample i of every stream gets
+ * amp_i * (cos phi_i, sin phi_i): phi advances by f * 2 pi / fs per sample and f by rate / fs, with the three SweepType behaviours where f
+ * reaches the stop frequency (nco.cpp:188-207).  The phase is evaluated in double from a closed form per sweep leg (DESIGN.md section
+ * 4) instead of the reference's serial sum: they differ by the serial sum's own rounding (1e-7 rad over 2^18 samples at the rates
+ * tested).  The sample is formed in double -- input + sweep + noise -- and rounded to float once.  The sweep is the same on every stream
+ * of a receiver with independent streams.
+ * A call with a generator on is staged: the caller's buffer is never written; raw formats are converted into the library's staging
+ * buffer and generated into there, float2 input is read, summed and written into that buffer by the generator's own kernel.  Such a
+ * call is never raw-fused and never pipelined with the calls around it (the staging buffer is shared by successive calls, as with
+ * pebblegpu_set_conditioners); its chain may still run beside its own display transform, with the kernels of the same call without a
+ * generator: its audio is bit for bit that of a receiver fed the summed stream.  pebblegpu_receiver_kernel_name(rx, 2) starts with
+ * "k_testbench + ". */
+int pebblegpu_set_testbench_sweep(pebblegpu_receiver *rx, const pebblegpu_sweep *s);
+/* TestBench::genNoise -> NCO::genNoise (nco.cpp:87-116), always mixed (testbench.cpp:542); amplitude = m_noiseAmplitude, linear; <= 0:
+ * off.  The reference draws from rand(); the library keeps the method (Knop's polar form, u = 1 - 2 r / 2147483647 with 31-bit r, s >= 1
+ * or s == 0 rejected, sqrt(-2 ln s / s), in double) and makes r a pure function of (seed, stream, sample number since the last setter,
+ * attempt, which of the two): splitmix64's finaliser, see DESIGN.md section 4 and tests/testbench_ref.py.  At most 32 attempts per
+ * sample; a sample whose 32 attempts all fail (4e-22) gets no noise.  Streams of one receiver get different noise. */
+int pebblegpu_set_testbench_noise(pebblegpu_receiver *rx, double amplitude, uint64_t seed);
+/* Taps: the float2 signal of the whole call at a point of the chain, copied into a library-owned buffer (allocated when the point is
+ * first enabled) by a copy queued on the call's stream at that point.  Valid after pebblegpu_receiver_synchronize until the next call.
+ *   RAW_IQ      [stream][n_samples] at the stream rate: the streams after the generator, before the conditioners (receiver.cpp:803)
+ *   POST_MIXER  [channel][n_samples / D] at the demodulator rate: the decimated frames after the gain restore, what zoomed() sees
+ *               (receiver.cpp:942-945; on a WFM receiver m_sampleBuf at :884)
+ *   POST_BP     [channel][n_samples / D]: the band-pass output (receiver.cpp:953)
+ *   MODEM       [channel][n_samples / D]: after NoiseFilter::ProcessBlock, the frame m_iDigitalModem->processBlock receives (:974-980)
+ *   POST_DEMOD  [channel][n_samples / D]: the demodulator output before the resampler (receiver.cpp:992)
+ * Channels in dmNONE leave their MODEM and POST_DEMOD rows zero (the reference returns before, :968-971).  A tap changes no value and
+ * no kernel of the call; a receiver without a display transform runs a call with taps on one stream instead of as two overlapping
+ * stages.  Refused (PEBBLEGPU_E_UNSUPPORTED, nothing changed): POST_BP, MODEM and POST_DEMOD on a WFM receiver (it has no such
+ * points); MODEM or POST_DEMOD together with a squelch threshold above -120, by whichever setter comes second (a closed gate ends the
+ * call before those points).  mask: 1 << point or'ed; 0 switches every tap off. */
+enum { PEBBLEGPU_TAP_RAW_IQ = 1, PEBBLEGPU_TAP_POST_MIXER = 2, PEBBLEGPU_TAP_POST_BP = 3, PEBBLEGPU_TAP_POST_DEMOD = 4,   /* TB_RAW_IQ .., receiver.h:113-116 */
+       PEBBLEGPU_TAP_MODEM = 16 };                                                                                        /* receiver.cpp:979-980 */
+int pebblegpu_receiver_set_taps(pebblegpu_receiver *rx, uint32_t mask);
+/* the tap's row 0 after the last call (NULL: the point is off, or the last call did not reach it); row r starts *pitch_samples float2 further */
+const void *pebblegpu_receiver_tap(const pebblegpu_receiver *rx, int point, uint64_t *samples_per_row, uint64_t *pitch_samples, double *rate);
 /* waits until every process call made on this handle has finished: its outputs are then valid and its input may be reused */
 int pebblegpu_receiver_synchronize(pebblegpu_receiver *rx);
 
@@ -559,6 +622,26 @@ int pebblegpu_morse_set_sample_rate(pebblegpu_morse *m, uint32_t sample_rate, ui
  * (off by default: nothing is kept); pebblegpu_morse_results hands them out since its last call (*n <= cap; the rest stays) */
 int pebblegpu_morse_keep_results(pebblegpu_morse *m, int on);
 int pebblegpu_morse_results(pebblegpu_morse *m, double *power, uint8_t *tone, uint32_t cap, uint32_t *n);
+
+typedef struct pebblegpu_siggen pebblegpu_siggen;
+/* The test bench's generator as a stand-alone step: NCO::NCO(sampleRate, bufSize) (nco.cpp:4-25) with initSweep / genSweep / genNoise,
+ * the same kernel a receiver runs, on one stream of the caller's.  frames_per_buffer: the frame pebblegpu_siggen_generate expects most
+ * often (its staging grows on demand). */
+int pebblegpu_siggen_create(int device, double sample_rate, uint32_t frames_per_buffer, pebblegpu_siggen **out);
+int pebblegpu_siggen_destroy(pebblegpu_siggen *g);
+/* as pebblegpu_set_testbench_sweep / _noise: each call is TestBench::reset() */
+int pebblegpu_siggen_set_sweep(pebblegpu_siggen *g, const pebblegpu_sweep *s);
+int pebblegpu_siggen_set_noise(pebblegpu_siggen *g, double amplitude, uint64_t seed);
+/* which stream of a receiver's noise this generator makes (default 0); does not reset */
+int pebblegpu_siggen_set_stream(pebblegpu_siggen *g, uint32_t stream);
+/* the next n samples into d_iq (device float2, in place: mixed with what is there, or replacing it); queues and returns */
+int pebblegpu_siggen_generate_device(pebblegpu_siggen *g, void *d_iq, uint64_t n);
+int pebblegpu_siggen_synchronize(pebblegpu_siggen *g);
+/* TestBench::genSweep(n, iq) then TestBench::genNoise(n, iq) on a host frame of n CPX, in place; results are float-rounded */
+int pebblegpu_siggen_generate(pebblegpu_siggen *g, double *iq, uint32_t n);
+/* for parity checks: the accepted 31-bit draws (r [n][2]) and the accepted attempt's number (attempt [n]; 32: none) of noise samples
+ * first_sample .. first_sample + n - 1 of the generator's stream with its current seed, computed on the device; host arrays */
+int pebblegpu_siggen_noise_draws(pebblegpu_siggen *g, uint64_t first_sample, uint32_t n, uint32_t *r, uint8_t *attempt);
 
 #ifdef __cplusplus
 }

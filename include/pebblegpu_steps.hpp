@@ -18,6 +18,7 @@
 //   bool SignalSpectrum::mapFFTToScreen(...)    application/signalspectrum.cpp:137-149   Receiver::mapFFTToScreen
 //   void Receiver::processIQData(CPX*, quint16) application/receiver.cpp:758    Receiver::processIQData
 //   CB_ProcessIQData / CB_ProcessAudioData      pebblelib/device_interfaces.h:32,38   same std::function shapes
+//   void TestBench::genSweep(int, CPX*) / genNoise(int, CPX*)   application/testbench.h; NCO::initSweep pebblelib/nco.h:52-57   TestBench
 //   FileSDRDevice (initialize / Cmd_Start pump) plugins/FileSDRDevice/filesdrdevice.cpp:24-33,226-289   FileSdrFeeder
 //
 // Error behaviour follows the reference: no exceptions across step calls; a failing call logs to stderr (the
@@ -375,6 +376,64 @@ private:
     int dev = 0, status = 0;
 };
 
+// The members of TestBench that Receiver::processIQData calls (application/receiver.cpp:797-798; testbench.cpp:518-544) over the
+// library's generator, with NCO::initSweep's signature (pebblelib/nco.h:52-55) for the set-up the reference's dialog does.  The two
+// calls stay separate, as in the reference: one generator object each, so the sweep's phase and the noise counter advance with their own
+// calls.  Results are float-rounded (the library's kernels work on float2).
+class TestBench {
+public:
+    enum SweepType { SINGLE, REPEAT, REPEAT_REVERSE };  // NCO::SweepType, nco.h:52
+    TestBench(uint32_t sampleRate, uint32_t bufferSize, int device = 0)
+    {
+        status = report("siggen_create", pebblegpu_siggen_create(device, (double)sampleRate, bufferSize, &sweepGen));
+        if (status == 0) status = report("siggen_create", pebblegpu_siggen_create(device, (double)sampleRate, bufferSize, &noiseGen));
+        std::memset(&sw, 0, sizeof(sw));
+        sw.struct_size = sizeof(sw);
+        sw.amplitude = 1.0;
+        sw.mix = 1;
+    }
+    ~TestBench()
+    {
+        pebblegpu_siggen_destroy(sweepGen);
+        pebblegpu_siggen_destroy(noiseGen);
+    }
+    TestBench(const TestBench &) = delete;
+    TestBench &operator=(const TestBench &) = delete;
+    // NCO::initSweep (nco.cpp:119-137) as TestBench::reset calls it (testbench.cpp:557-558): restarts the sweep
+    void initSweep(double sweepStartFreq, double sweepStopFreq, double sweepRate, double pulseWidth, double pulsePeriod, SweepType sweepType = SINGLE)
+    {
+        sw.start_hz = sweepStartFreq;
+        sw.stop_hz = sweepStopFreq;
+        sw.rate_hz_per_s = sweepRate;
+        sw.pulse_width_s = pulseWidth;
+        sw.pulse_period_s = pulsePeriod;
+        sw.sweep_type = (int32_t)sweepType;
+        sweepOn = true;
+        apply();
+    }
+    void setSignalAmplitude(double a) { sw.amplitude = a; if (sweepOn) apply(); }  // m_signalAmplitude (linear), testbench.cpp:563
+    void setMix(bool mix) { sw.mix = mix ? 1 : 0; if (sweepOn) apply(); }          // genMixBox, testbench.cpp:521
+    void setSweepOn(bool on) { sweepOn = on; if (sweepGen) status = report("siggen_set_sweep", pebblegpu_siggen_set_sweep(sweepGen, on ? &sw : nullptr)); }
+    // m_noiseOn + m_noiseAmplitude (linear, testbench.cpp:566); amplitude <= 0: off
+    void setNoise(double amplitude, uint64_t seed = 0) { if (noiseGen) status = report("siggen_set_noise", pebblegpu_siggen_set_noise(noiseGen, amplitude, seed)); }
+    void genSweep(int length, CPX *pBuf)  // testbench.cpp:518-526
+    {
+        if (sweepGen && sweepOn && length > 0) status = report("siggen_generate", pebblegpu_siggen_generate(sweepGen, reinterpret_cast<double *>(pBuf), (uint32_t)length));
+    }
+    void genNoise(int length, CPX *pBuf)  // testbench.cpp:537-544
+    {
+        if (noiseGen && length > 0) status = report("siggen_generate", pebblegpu_siggen_generate(noiseGen, reinterpret_cast<double *>(pBuf), (uint32_t)length));
+    }
+    int lastStatus() const { return status; }
+
+private:
+    void apply() { if (sweepGen) status = report("siggen_set_sweep", pebblegpu_siggen_set_sweep(sweepGen, &sw)); }
+    pebblegpu_siggen *sweepGen = nullptr, *noiseGen = nullptr;
+    pebblegpu_sweep sw;
+    bool sweepOn = false;
+    int status = 0;
+};
+
 // The slice of application/receiver.cpp this library replaces: turnPowerOn's step construction and
 // processIQData's DSP for one tuned channel, audio delivered through the CB_ProcessAudioData-shaped callback.
 class Receiver {
@@ -404,10 +463,12 @@ public:
             audio.resize((size_t)(info.superframe / info.total_decimation) + framesPerBuffer);
             spectrum.resize(info.spectrum_bins);
             demodRate = info.demod_rate_int;
+            superframe = info.superframe;
         }
     }
     ~Receiver()
     {
+        if (dIn) pebblegpu_free(dev, dIn);
         if (dPx) pebblegpu_free(dev, dPx);
         pebblegpu_receiver_destroy(h);
     }
@@ -433,10 +494,24 @@ public:
         return out;
     }
     MorseReport morseStatus() { MorseReport r{}; if (h) status = report("receiver_morse_status", pebblegpu_receiver_morse_status(h, 0, &r)); return r; }
+    // The test bench (receiver.cpp:797-803, 945, 953, 979-980, 992).  The generator and the taps live on the library's batched device
+    // path: while one of them is on, processIQData collects a super-frame of frames, runs it as one pebblegpu_receiver_process call and
+    // hands every tapped point to displayData frame by frame (numSamples, frame, sample rate, point -- TestBench::displayData's
+    // arguments) before the audio callback; the unprocessed spectrum is then the super-frame's last frame's.  A host DigitalModemInterface
+    // plugin binds its processBlock to PEBBLEGPU_TAP_MODEM here.
+    typedef std::function<void(int, CPX *, double, int)> CB_DisplayData;
+    void setTestBenchSweep(const pebblegpu_sweep *s) { if (h) status = report("set_testbench_sweep", pebblegpu_set_testbench_sweep(h, s)); if (status == 0) tbSweep = s != nullptr; }
+    void setTestBenchNoise(double amplitude, uint64_t seed) { if (h) status = report("set_testbench_noise", pebblegpu_set_testbench_noise(h, amplitude, seed)); if (status == 0) tbNoise = amplitude > 0; }
+    void setTaps(uint32_t mask, CB_DisplayData displayData)
+    {
+        if (h) status = report("receiver_set_taps", pebblegpu_receiver_set_taps(h, mask));
+        if (status == 0) { tapMask = mask; display = displayData; }
+    }
     // bound as the device plugin's CB_ProcessIQData, like receiver.cpp:135-138
     void processIQData(CPX *in, uint16_t numSamples)
     {
         if (!h) return;
+        if (tbSweep || tbNoise || tapMask) { processBatched(in, numSamples); return; }
         uint32_t na = 0;
         // (behind setUpdatesPerSec a frame the timer skips leaves `spectrum` as it is: the last computed one, as getUnprocessed() holds it)
         status = report("process_iq", pebblegpu_process_iq_updates(h, reinterpret_cast<const double *>(in), numSamples, reinterpret_cast<double *>(audio.data()), &na,
@@ -482,8 +557,63 @@ public:
     int lastStatus() const { return status; }
 
 private:
+    void processBatched(CPX *in, uint16_t numSamples)
+    {
+        if (numSamples != n || !superframe) { status = report("process_iq", PEBBLEGPU_E_SIZE); return; }
+        if (!dIn && (status = report("malloc", pebblegpu_malloc(dev, sizeof(float) * 2 * (size_t)superframe, &dIn))) != 0) return;
+        staged.resize(2 * (size_t)superframe);
+        for (size_t i = 0; i < (size_t)n; i++) {
+            staged[2 * (filled + i)] = (float)in[i].real();
+            staged[2 * (filled + i) + 1] = (float)in[i].imag();
+        }
+        filled += n;
+        if (filled < superframe) return;
+        filled = 0;
+        if ((status = report("memcpy_h2d", pebblegpu_memcpy_h2d(dev, dIn, staged.data(), sizeof(float) * staged.size()))) != 0) return;
+        if ((status = report("receiver_process", pebblegpu_receiver_process(h, dIn, superframe))) != 0) return;
+        if ((status = report("receiver_synchronize", pebblegpu_receiver_synchronize(h))) != 0) return;
+        static const int points[5] = {PEBBLEGPU_TAP_RAW_IQ, PEBBLEGPU_TAP_POST_MIXER, PEBBLEGPU_TAP_POST_BP, PEBBLEGPU_TAP_MODEM, PEBBLEGPU_TAP_POST_DEMOD};
+        for (int pt : points) {
+            uint64_t rows = 0, pitch = 0;
+            double rate = 0;
+            const void *p = (tapMask >> pt & 1u) ? pebblegpu_receiver_tap(h, pt, &rows, &pitch, &rate) : nullptr;
+            if (!p || !display) continue;
+            fetch(p, (size_t)rows);
+            for (size_t off = 0; off + n <= (size_t)rows; off += n) display((int)n, frames.data() + off, rate, pt);
+        }
+        if (!spectrum.empty()) {
+            uint64_t nfr = 0;
+            const void *p = pebblegpu_receiver_spectrum(h, &nfr);
+            specUpdated = nfr ? 1u : 0u;
+            if (p && nfr) {
+                stagedSpec.resize(spectrum.size());
+                if ((status = report("memcpy_d2h", pebblegpu_memcpy_d2h(dev, stagedSpec.data(), static_cast<const float *>(p) + (nfr - 1) * spectrum.size(), sizeof(float) * spectrum.size()))) != 0) return;
+                for (size_t i = 0; i < spectrum.size(); i++) spectrum[i] = (double)stagedSpec[i];
+            }
+        }
+        uint64_t na = 0;
+        const void *pa = pebblegpu_receiver_audio(h, &na, nullptr);
+        if (!pa || !na || !cb) return;
+        fetch(pa, (size_t)na);
+        for (size_t off = 0; off < (size_t)na; off += n) cb(frames.data() + off, (uint16_t)((na - off) < n ? (na - off) : n));  // processAudioData, receiver.cpp:1007
+    }
+    void fetch(const void *dSrc, size_t count)  // device float2 row -> frames (CPX)
+    {
+        staged.resize(2 * count > staged.size() ? 2 * count : staged.size());
+        frames.resize(count);
+        if ((status = report("memcpy_d2h", pebblegpu_memcpy_d2h(dev, staged.data(), dSrc, sizeof(float) * 2 * count))) != 0) { frames.assign(count, CPX(0, 0)); return; }
+        for (size_t i = 0; i < count; i++) frames[i] = CPX(staged[2 * i], staged[2 * i + 1]);
+    }
     pebblegpu_receiver *h = nullptr;
     uint16_t n;
+    bool tbSweep = false, tbNoise = false;
+    uint32_t tapMask = 0;
+    CB_DisplayData display;
+    uint64_t superframe = 0;
+    size_t filled = 0;
+    void *dIn = nullptr;
+    std::vector<float> staged, stagedSpec;
+    std::vector<CPX> frames;
     CB_ProcessAudioData cb;
     std::vector<CPX> audio;
     std::vector<double> spectrum;

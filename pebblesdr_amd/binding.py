@@ -40,6 +40,9 @@ SYMBOLS = [
     "pebblegpu_morse_events", "pebblegpu_morse_status", "pebblegpu_morse_results", "pebblegpu_morse_set_sample_rate",
     "pebblegpu_morse_keep_results",
     "pebblegpu_set_spectrum_updates", "pebblegpu_receiver_spectrum_frames", "pebblegpu_process_iq_updates",
+    "pebblegpu_sweep_plan", "pebblegpu_set_testbench_sweep", "pebblegpu_set_testbench_noise", "pebblegpu_receiver_set_taps", "pebblegpu_receiver_tap",
+    "pebblegpu_siggen_create", "pebblegpu_siggen_destroy", "pebblegpu_siggen_set_sweep", "pebblegpu_siggen_set_noise", "pebblegpu_siggen_set_stream",
+    "pebblegpu_siggen_generate_device", "pebblegpu_siggen_synchronize", "pebblegpu_siggen_generate", "pebblegpu_siggen_noise_draws",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
@@ -84,6 +87,37 @@ def screen_map(y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq):
     m.max_db, m.min_db = float(max_db), float(min_db)
     m.start_freq, m.stop_freq = int(start_freq), int(stop_freq)
     return m
+
+
+class Sweep(C.Structure):
+    """pebblegpu_sweep: NCO::initSweep's arguments + the amplitude and mix switch TestBench::genSweep passes"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("sweep_type", C.c_int32), ("start_hz", C.c_double), ("stop_hz", C.c_double), ("rate_hz_per_s", C.c_double),
+        ("pulse_width_s", C.c_double), ("pulse_period_s", C.c_double), ("amplitude", C.c_double), ("mix", C.c_int32), ("reserved", C.c_uint32 * 3),
+    ]
+
+
+SWEEP_SINGLE, SWEEP_REPEAT, SWEEP_REPEAT_REVERSE = 0, 1, 2  # NCO::SweepType
+TAP_RAW_IQ, TAP_POST_MIXER, TAP_POST_BP, TAP_POST_DEMOD, TAP_MODEM = 1, 2, 3, 4, 16  # PEBBLEGPU_TAP_*
+
+
+def sweep(start_hz, stop_hz, rate_hz_per_s, amplitude=1.0, sweep_type=SWEEP_REPEAT, pulse_width_s=0.0, pulse_period_s=0.0, mix=True):
+    s = Sweep()
+    s.struct_size = C.sizeof(Sweep)
+    s.sweep_type = int(sweep_type)
+    s.start_hz, s.stop_hz, s.rate_hz_per_s = float(start_hz), float(stop_hz), float(rate_hz_per_s)
+    s.pulse_width_s, s.pulse_period_s = float(pulse_width_s), float(pulse_period_s)
+    s.amplitude = float(amplitude)
+    s.mix = 1 if mix else 0
+    return s
+
+
+def sweep_plan(sample_rate, s, lib=None):
+    """what the library makes of a sweep, on the host (no device): (leg_samples, pulse_period_samples, pulse_on_samples)"""
+    L = lib or load_library()
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(L, L.pebblegpu_sweep_plan(float(sample_rate), C.byref(s), C.byref(a), C.byref(b), C.byref(c)))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def _frame_range(frames, first_frame, n_frames, frame_step):
@@ -268,6 +302,22 @@ def _declare(L):
     L.pebblegpu_morse_results.argtypes = [vp, dp, vp, u32, C.POINTER(u32)]
     L.pebblegpu_morse_set_sample_rate.argtypes = [vp, u32, u32]
     L.pebblegpu_morse_keep_results.argtypes = [vp, i32]
+    swp, u64p = C.POINTER(Sweep), C.POINTER(u64)
+    L.pebblegpu_sweep_plan.argtypes = [dbl, swp, u64p, u64p, u64p]
+    L.pebblegpu_set_testbench_sweep.argtypes = [vp, swp]
+    L.pebblegpu_set_testbench_noise.argtypes = [vp, dbl, u64]
+    L.pebblegpu_receiver_set_taps.argtypes = [vp, u32]
+    L.pebblegpu_receiver_tap.restype = vp
+    L.pebblegpu_receiver_tap.argtypes = [vp, i32, u64p, u64p, dp]
+    L.pebblegpu_siggen_create.argtypes = [i32, dbl, u32, C.POINTER(vp)]
+    L.pebblegpu_siggen_destroy.argtypes = [vp]
+    L.pebblegpu_siggen_set_sweep.argtypes = [vp, swp]
+    L.pebblegpu_siggen_set_noise.argtypes = [vp, dbl, u64]
+    L.pebblegpu_siggen_set_stream.argtypes = [vp, u32]
+    L.pebblegpu_siggen_generate_device.argtypes = [vp, vp, u64]
+    L.pebblegpu_siggen_synchronize.argtypes = [vp]
+    L.pebblegpu_siggen_generate.argtypes = [vp, dp, u32]
+    L.pebblegpu_siggen_noise_draws.argtypes = [vp, u64, u32, vp, vp]
     return L
 
 
@@ -446,6 +496,34 @@ class ReceiverBank:
         st = MorseReport()
         check(self.L, self.L.pebblegpu_receiver_morse_status(self.h, ch, C.byref(st)))
         return st.as_dict()
+
+    def set_testbench_sweep(self, s):
+        """TestBench::reset + the sweep generator at the head of the chain; s: a Sweep (see sweep()), None switches it off"""
+        check(self.L, self.L.pebblegpu_set_testbench_sweep(self.h, C.byref(s) if s is not None else None))
+
+    def set_testbench_noise(self, amplitude, seed=0):
+        """NCO::genNoise at the head of the chain, always mixed; amplitude <= 0 switches it off"""
+        check(self.L, self.L.pebblegpu_set_testbench_noise(self.h, float(amplitude), int(seed)))
+
+    def set_taps(self, points):
+        """points: iterable of TAP_* (empty: every tap off)"""
+        mask = 0
+        for p in points:
+            mask |= 1 << int(p)
+        check(self.L, self.L.pebblegpu_receiver_set_taps(self.h, mask))
+
+    def tap(self, point):
+        """-> (complex64 [rows, n] of the last call at that point, rate in Hz); None when the point is off or was not reached"""
+        n, pitch, rate = C.c_uint64(), C.c_uint64(), C.c_double()
+        p = self.L.pebblegpu_receiver_tap(self.h, int(point), C.byref(n), C.byref(pitch), C.byref(rate))
+        if not p:
+            return None
+        self.synchronize()
+        rows = self.n_streams if int(point) == TAP_RAW_IQ else self.n_channels
+        out = np.empty((rows, int(n.value)), dtype=np.complex64)
+        for r in range(rows):
+            check(self.L, self.L.pebblegpu_memcpy_d2h(self.device, out[r].ctypes.data_as(C.c_void_p), C.c_void_p(p + r * int(pitch.value) * 8), out[r].nbytes))
+        return out, rate.value
 
     def set_conditioners(self, stream, flags, iq_gain=1.0, iq_phase=0.0):
         check(self.L, self.L.pebblegpu_set_conditioners(self.h, stream, int(flags), float(iq_gain), float(iq_phase)))
@@ -641,6 +719,56 @@ class ReceiverBank:
         check(self.L, self.L.pebblegpu_process_iq_updates(self.h, x.ctypes.data_as(dp), len(x), audio.ctypes.data_as(dp), C.byref(n_audio),
                                                          spectrum.ctypes.data_as(dp), C.byref(upd)))
         return audio[: n_audio.value].copy(), bool(upd.value)
+
+
+class SigGen:
+    """The test bench's generator as a stand-alone step (pebblegpu_siggen_*): NCO::genSweep + NCO::genNoise on one stream"""
+
+    def __init__(self, sample_rate, frames_per_buffer=2048, device=0, lib=None):
+        self.L = lib or load_library()
+        self.h = C.c_void_p()
+        check(self.L, self.L.pebblegpu_siggen_create(device, float(sample_rate), int(frames_per_buffer), C.byref(self.h)))
+        self.device = device
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.pebblegpu_siggen_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_sweep(self, s):
+        check(self.L, self.L.pebblegpu_siggen_set_sweep(self.h, C.byref(s) if s is not None else None))
+
+    def set_noise(self, amplitude, seed=0):
+        check(self.L, self.L.pebblegpu_siggen_set_noise(self.h, float(amplitude), int(seed)))
+
+    def set_stream(self, stream):
+        check(self.L, self.L.pebblegpu_siggen_set_stream(self.h, int(stream)))
+
+    def generate_device(self, dptr, n):
+        """the next n samples into the device float2 buffer at dptr, in place; queued"""
+        check(self.L, self.L.pebblegpu_siggen_generate_device(self.h, C.c_void_p(dptr), int(n)))
+
+    def synchronize(self):
+        check(self.L, self.L.pebblegpu_siggen_synchronize(self.h))
+
+    def generate(self, frame):
+        """TestBench::genSweep + genNoise on a host frame (complex128, modified in place and returned)"""
+        assert frame.dtype == np.complex128 and frame.flags.c_contiguous
+        check(self.L, self.L.pebblegpu_siggen_generate(self.h, frame.ctypes.data_as(C.POINTER(C.c_double)), len(frame)))
+        return frame
+
+    def noise_draws(self, first_sample, n):
+        """-> (uint32 [n, 2] accepted draws, uint8 [n] accepted attempt) of the generator's stream and seed, from the device"""
+        r = np.zeros((n, 2), dtype=np.uint32)
+        a = np.zeros(n, dtype=np.uint8)
+        check(self.L, self.L.pebblegpu_siggen_noise_draws(self.h, int(first_sample), int(n), r.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p)))
+        return r, a
 
 
 class StreamBank:

@@ -1,0 +1,379 @@
+// kernels_testbench.h -- the test bench's signal generator on the device (TestBenchCore, receiver.h):
+// NCO::genSweep (pebblelib/nco.cpp:140-212) and NCO::genNoise (:87-116) as TestBench::genSweep / genNoise call them at the head of
+// Receiver::processIQData (application/testbench.cpp:518-544, application/receiver.cpp:797-798), in ONE pass over the streams.
+//
+// Sweep.  The reference accumulates the phase serially (m_sweepAcc += m_sweepFreq * m_sweepFreqNorm, m_sweepFreq += m_sweepRateInc per
+// sample, fmod once per call).  Here every sample evaluates the closed form of its sweep leg, in double and in TURNS (phase / 2 pi, so
+// that the reduction before the sincos is an exact subtraction):
+//     turns(k) = turns0 + (f0 * j + inc * j (j - 1) / 2) / fs,   j = k - k0,
+// with (k0, turns0, f0, inc) from the call's leg table, which the host writes relative to the CALL's first sample (indexing from the
+// stream's first sample would lose the low bits of j^2).  A leg ends where the reference's frequency reaches the stop frequency
+// (nco.cpp:188-207); SINGLE then holds (inc = 0), REPEAT starts over, REPEAT_REVERSE runs back.
+// Pulse modulation (nco.cpp:149-156) is a serial double accumulation of 1 / fs whose edges depend on rounding: the host runs it once
+// (TestBenchCore::set_sweep) and the kernel gates by (absolute sample number mod period).
+//
+// Noise.  The Knop polar method of the reference with its rand() replaced by a counter-based draw: a pure function of
+// (seed, stream, absolute sample number, attempt, which of the two), so a sample's noise depends neither on call sizes nor on the lane
+// that makes it.  tests/testbench_ref.py restates the function; the integers are reproduced exactly.
+#pragma once
+#include "common.h"
+#include "receiver.h"
+
+namespace pg {
+
+// ---- the counter-based draw ----
+__host__ __device__ __forceinline__ unsigned long long tb_mix64(unsigned long long z)  // the splitmix64 finaliser
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+constexpr unsigned long long kTbGolden = 0x9E3779B97F4A7C15ull;
+__host__ __device__ __forceinline__ unsigned long long tb_stream_key(unsigned long long seed, unsigned stream)
+{
+    return tb_mix64(seed + kTbGolden * (unsigned long long)(stream + 1u));
+}
+// attempt a of sample n: 64 bits, the two 31-bit draws are bits 63..33 and 31..1
+__device__ __forceinline__ unsigned long long tb_draw(unsigned long long key, unsigned long long n, int a)
+{
+    return tb_mix64(tb_mix64(key ^ n) + kTbGolden * (unsigned long long)(a + 1));
+}
+// NCO::genNoise's loop body for one sample (nco.cpp:98-107), amplitude 1: at most kTbNoiseAttempts attempts (an attempt is accepted
+// with probability pi / 4; all of them failing, 0.215^32 = 4e-22 per sample, leaves the sample without noise).  *att: the accepted
+// attempt's number, kTbNoiseAttempts when none was
+__device__ __forceinline__ double2 tb_noise(unsigned long long key, unsigned long long n, unsigned *r1, unsigned *r2, int *att)
+{
+    for (int a = 0; a < kTbNoiseAttempts; a++) {
+        const unsigned long long h = tb_draw(key, n, a);
+        const unsigned ra = (unsigned)(h >> 33), rb = (unsigned)(h >> 1) & 0x7FFFFFFFu;
+        const double u1 = 1.0 - 2.0 * (double)ra / 2147483647.0;
+        const double u2 = 1.0 - 2.0 * (double)rb / 2147483647.0;
+        const double s = __dadd_rn(__dmul_rn(u1, u1), __dmul_rn(u2, u2));  // (no contraction: the acceptance test sees the reference's s)
+        if (s >= 1.0 || s == 0.0) continue;
+        const double rad = sqrt(-2.0 * log(s) / s);
+        *r1 = ra; *r2 = rb; *att = a;
+        return make_double2(u1 * rad, u2 * rad);
+    }
+    *r1 = 0; *r2 = 0; *att = kTbNoiseAttempts;
+    return make_double2(0.0, 0.0);
+}
+
+// the last leg that starts at or before call-relative sample k (legs[0].k0 == 0), by bisection.  Called with a wave-uniform k (the first
+// sample of the wave's stretch), so the table is read through scalar loads, once per wave and step instead of once per sample
+__device__ __forceinline__ int tb_find_leg(const SweepLeg *__restrict__ legs, int n_legs, unsigned long long k)
+{
+    int lo = 0, hi = n_legs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (legs[mid].k0 <= k) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+__device__ __forceinline__ unsigned long long tb_uniform(unsigned long long v)  // the first active lane's value, in scalar registers
+{
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (unsigned long long)hi << 32 | lo;
+}
+
+// one output sample: `in` + sweep + noise, formed in double and rounded to float once.  leg: a leg at or before the sample's (the wave's
+// first sample's leg); the sample's own is at most a few entries further (a wave spans 128 samples, a whole leg at least kTbMinLeg)
+__device__ __forceinline__ float2 tb_sample(const TbParams &p, const SweepLeg *__restrict__ legs, int leg, unsigned long long noise_key, long long k, float2 in)
+{
+    double re = (double)in.x, im = (double)in.y;
+    const unsigned long long n_abs = p.n0 + (unsigned long long)k;
+    if (p.sweep_on) {
+        double amp = p.amp;
+        if (p.pulse_period) {  // on while the reference's timer is <= the width: its first pulse_on increments, and the one that resets it
+            const unsigned long long m = n_abs % p.pulse_period;
+            if (m >= p.pulse_on && m != p.pulse_period - 1) amp = 0.0;
+        }
+        while (leg + 1 < p.n_legs && legs[leg + 1].k0 <= (unsigned long long)k) leg++;
+        const SweepLeg lg = legs[leg];
+        const unsigned long long j = (unsigned long long)k - lg.k0;
+        const unsigned long long tri = (j & 1) ? j * ((j - 1) >> 1) : (j >> 1) * (j - 1);
+        double t = lg.turns0 + (lg.f0 * (double)j + lg.inc * (double)tri) * p.fs_inv;  // (j < 2^26: the host splits longer pieces, tri is exact)
+        t -= rint(t);
+        double s, c;
+        sincospi(2.0 * t, &s, &c);
+        if (p.mix) { re += amp * c; im += amp * s; }
+        else { re = amp * c; im = amp * s; }
+    }
+    if (p.noise_on) {
+        unsigned r1, r2;
+        int att;
+        const double2 g = tb_noise(noise_key, n_abs, &r1, &r2, &att);
+        re += p.noise_amp * g.x;
+        im += p.noise_amp * g.y;
+    }
+    return make_float2((float)re, (float)im);
+}
+
+// in == nullptr: silence in (a generator that replaces, or a stand-alone buffer that is only written); in may equal out.
+// One work-item makes two neighbouring samples per step (16-byte accesses) when the rows allow it (vec: pointers 16-byte aligned, even
+// pitches), else one.  grid (x, streams)
+static __global__ __launch_bounds__(256) void k_testbench(const float2 *in, float2 *out, long long in_pitch, long long out_pitch, long long n, int vec,
+                                                          TbParams p, const SweepLeg *__restrict__ legs)
+{
+    const unsigned s = blockIdx.y;
+    const unsigned long long key = tb_stream_key(p.seed, p.stream0 + s);
+    const float2 *src = in ? in + (long long)s * in_pitch : nullptr;
+    float2 *dst = out + (long long)s * out_pitch;
+    const long long step = (long long)gridDim.x * 256;
+    if (vec) {
+        const long long pairs = n >> 1;
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < pairs; q += step) {
+            const int leg = p.sweep_on ? tb_find_leg(legs, p.n_legs, tb_uniform(2ull * (unsigned long long)(q - (threadIdx.x & 63)))) : 0;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (src) v = reinterpret_cast<const float4 *>(src)[q];
+            const float2 a = tb_sample(p, legs, leg, key, 2 * q, make_float2(v.x, v.y));
+            const float2 b = tb_sample(p, legs, leg, key, 2 * q + 1, make_float2(v.z, v.w));
+            reinterpret_cast<float4 *>(dst)[q] = make_float4(a.x, a.y, b.x, b.y);
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) dst[n - 1] = tb_sample(p, legs, p.sweep_on ? tb_find_leg(legs, p.n_legs, (unsigned long long)(n - 1)) : 0, key, n - 1, src ? src[n - 1] : make_float2(0.f, 0.f));
+    } else {
+        for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += step) {
+            const int leg = p.sweep_on ? tb_find_leg(legs, p.n_legs, tb_uniform((unsigned long long)(k - (threadIdx.x & 63)))) : 0;
+            dst[k] = tb_sample(p, legs, leg, key, k, src ? src[k] : make_float2(0.f, 0.f));
+        }
+    }
+}
+
+// the accepted draws of samples first .. first + n - 1 of one stream (parity checks against the restatement): r [n][2], attempt [n]
+static __global__ __launch_bounds__(256) void k_testbench_draws(unsigned long long seed, unsigned stream, unsigned long long first, int n,
+                                                                unsigned *__restrict__ r, unsigned char *__restrict__ attempt)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    unsigned r1, r2;
+    int att;
+    (void)tb_noise(tb_stream_key(seed, stream), first + (unsigned long long)i, &r1, &r2, &att);
+    r[2 * i] = r1;
+    r[2 * i + 1] = r2;
+    attempt[i] = (unsigned char)att;
+}
+
+// ---- host side ----
+// (definitions with external linkage: EXACTLY ONE translation unit, steps.hip, includes this header; receiver.hip and the rest see the
+// declarations in receiver.h)
+
+// NCO::initSweep + the serial pulse timer of NCO::genSweep, run once: no device needed
+int tb_plan_sweep(double fs, const pebblegpu_sweep *s, TbSweepPlan *plan)
+{
+    if (!s || !plan) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (s->struct_size != sizeof(pebblegpu_sweep)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_sweep size mismatch (ABI %d)", PEBBLEGPU_ABI_VERSION);
+    if (!(fs > 0) || s->sweep_type < 0 || s->sweep_type > 2) return fail(PEBBLEGPU_E_INVALID, "bad sample rate or sweep type");
+    if (!std::isfinite(s->start_hz) || !std::isfinite(s->stop_hz) || !std::isfinite(s->rate_hz_per_s) || !std::isfinite(s->amplitude) ||
+        !std::isfinite(s->pulse_width_s) || !std::isfinite(s->pulse_period_s))
+        return fail(PEBBLEGPU_E_INVALID, "sweep parameters must be finite");
+    TbSweepPlan pl;
+    pl.inc = s->rate_hz_per_s / fs;  // m_sweepRateInc
+    pl.leg = 0;                      // 0: the leg never ends
+    if (pl.inc > 0) {
+        // the frequency after j steps reaches the stop frequency at j = ceil(|stop - start| / inc); the test comes after a step, so j >= 1
+        const double q = std::ceil(std::fabs(s->stop_hz - s->start_hz) / pl.inc);
+        if (q < 9.0e18) {  // (else: not reached within a 64-bit sample count)
+            pl.leg = q < 1.0 ? 1ull : (unsigned long long)q;
+            if (pl.leg < (unsigned long long)kTbMinLeg)
+                return fail(PEBBLEGPU_E_UNSUPPORTED, "sweep legs of %llu samples: the leg table is built for %d or more (DESIGN.md section 7)", pl.leg, kTbMinLeg);
+        }
+    } else {
+        pl.inc = 0.0;  // "if (m_sweepRateInc > 0)", nco.cpp:181: the frequency never moves
+    }
+    pl.pulse_period = pl.pulse_on = 0;
+    if (s->pulse_width_s > 0.0) {
+        // m_sweepPulseTimer += 1 / fs until it exceeds the period (then it is reset: the pattern repeats); the first increment that leaves it
+        // above the width starts the gap
+        const double dt = 1.0 / fs;
+        // (the sum below is run here, under the owner's lock: 2^28 additions are a fraction of a second; the reference's 0.5 s is 1e7 samples at 20 Msps)
+        if (!(s->pulse_period_s * fs < (double)kTbMaxPulsePeriod)) return fail(PEBBLEGPU_E_UNSUPPORTED, "pulse periods of 2^28 samples or more are not built");
+        double t = 0.0;
+        unsigned long long i = 0, first_off = 0;
+        do {
+            t += dt;
+            i++;
+            if (!first_off && t > s->pulse_width_s) first_off = i;
+        } while (!(t > s->pulse_period_s));
+        pl.pulse_period = i;
+        // samples 0 .. pulse_on - 1 of a period are on, and its last (the increment that resets the timer leaves 0, which is never above a width > 0)
+        pl.pulse_on = first_off ? first_off - 1 : i;
+    }
+    *plan = pl;
+    return 0;
+}
+
+int TestBenchCore::init(double sample_rate, uint32_t streams)
+{
+    fs = sample_rate;
+    S = streams;
+    return 0;
+}
+
+void TestBenchCore::release()
+{
+    for (int i = 0; i < 2; i++) {
+        if (d_legs[i]) (void)hipFree(d_legs[i]);
+        if (h_legs[i]) (void)hipHostFree(h_legs[i]);
+        if (h_done[i]) (void)hipEventDestroy(h_done[i]);
+        d_legs[i] = nullptr; h_legs[i] = nullptr; h_done[i] = nullptr;
+    }
+    leg_cap = 0;
+}
+
+// TestBench::reset(): the sweep restarts at the start frequency with phase 0 and pulse timer 0, the noise counter at 0
+void TestBenchCore::reset()
+{
+    n_abs = 0;
+    turns = 0.0;
+    leg_pos = 0;
+    if (sweep_on) {
+        start = sw.start_hz;
+        stop = sw.stop_hz;
+        up = start < stop;  // m_sweepUp
+        f_leg = start;
+        inc = up ? plan.inc : -plan.inc;
+        leg_len = plan.leg;
+    }
+}
+
+int TestBenchCore::set_sweep(const pebblegpu_sweep *s)
+{
+    if (!s) {
+        sweep_on = false;
+        reset();
+        return 0;
+    }
+    TbSweepPlan pl;
+    if (int rc = tb_plan_sweep(fs, s, &pl)) return rc;
+    sw = *s;
+    plan = pl;
+    sweep_on = true;
+    reset();
+    return 0;
+}
+
+int TestBenchCore::set_noise(double amplitude, uint64_t seed_)
+{
+    if (!std::isfinite(amplitude)) return fail(PEBBLEGPU_E_INVALID, "the noise amplitude must be finite");
+    noise_on = amplitude > 0.0;
+    noise_amp = noise_on ? amplitude : 0.0;
+    seed = seed_;
+    reset();
+    return 0;
+}
+
+// the legs of the next n samples, relative to the call's first; advances the carried (phase, frequency, leg, direction)
+int TestBenchCore::build_legs(long long n, std::vector<SweepLeg> &legs)
+{
+    legs.clear();
+    unsigned long long k = 0;
+    while (k < (unsigned long long)n) {
+        const unsigned long long left = (unsigned long long)n - k;
+        // (a piece is at most kTbMaxPiece samples: j (j - 1) / 2 stays exact in the kernel's double, however slow the sweep and long the call)
+        const unsigned long long len = std::min(leg_len ? std::min(left, leg_len - leg_pos) : left, kTbMaxPiece);
+        const double f0 = f_leg + inc * (double)leg_pos;
+        legs.push_back(SweepLeg{k, turns, f0, inc});
+        // the phase where the piece ends, as the kernel would evaluate it one sample further (long double: the carry is made once per piece)
+        const long double tri = (long double)len * (long double)(len - 1) / 2.0L;
+        long double t = (long double)turns + ((long double)f0 * (long double)len + (long double)inc * tri) / (long double)fs;
+        t -= floorl(t);
+        turns = (double)t;
+        if (turns >= 1.0) turns = 0.0;
+        k += len;
+        leg_pos += len;
+        if (leg_len && leg_pos == leg_len) {  // reached end of sweep (nco.cpp:188-207)
+            leg_pos = 0;
+            switch (sw.sweep_type) {
+            case 0:  // SINGLE: m_sweepRateInc = 0, the frequency stays where the last step left it
+                f_leg = f_leg + inc * (double)leg_len;
+                inc = 0.0;
+                leg_len = 0;
+                break;
+            case 1:  // REPEAT
+                break;
+            default:  // REPEAT_REVERSE: swap start and stop, reverse
+                std::swap(start, stop);
+                up = !up;
+                inc = -inc;
+                f_leg = start;
+                break;
+            }
+        }
+    }
+    return 0;
+}
+
+// in (may be nullptr: silence) -> out (may be in), `streams` rows of n samples; the carried state moves on by n samples
+int TestBenchCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, uint32_t streams, uint32_t stream0)
+{
+    if (!any() || n <= 0) return 0;
+    TbParams p;
+    memset(&p, 0, sizeof(p));
+    p.fs_inv = 1.0 / fs;
+    p.n0 = n_abs;
+    p.seed = seed;
+    p.stream0 = stream0;
+    p.noise_on = noise_on ? 1 : 0;
+    p.noise_amp = noise_amp;
+    const int slot = parity;
+    if (sweep_on) {
+        p.sweep_on = 1;
+        p.mix = sw.mix != 0;
+        p.amp = sw.amplitude;
+        p.pulse_period = plan.pulse_period;
+        p.pulse_on = plan.pulse_on;
+        if (int rc = build_legs(n, legs_)) return rc;
+        if (legs_.size() > leg_cap) {  // (a call longer, or legs shorter, than any before: both tables grow; rare)
+            PG_HIP(hipStreamSynchronize(s));
+            const size_t cap = legs_.size() + legs_.size() / 2 + 8;
+            for (int i = 0; i < 2; i++) {
+                if (h_done[i]) PG_HIP(hipEventSynchronize(h_done[i]));
+                if (d_legs[i]) PG_HIP(hipFree(d_legs[i]));
+                if (h_legs[i]) PG_HIP(hipHostFree(h_legs[i]));
+                d_legs[i] = nullptr; h_legs[i] = nullptr;
+                PG_HIP(hipMalloc((void **)&d_legs[i], sizeof(SweepLeg) * cap));
+                PG_HIP(hipHostMalloc((void **)&h_legs[i], sizeof(SweepLeg) * cap));
+                if (!h_done[i]) PG_HIP(hipEventCreateWithFlags(&h_done[i], hipEventDisableTiming));
+            }
+            leg_cap = cap;
+            used[0] = used[1] = false;
+        }
+        if (used[slot]) PG_HIP(hipEventSynchronize(h_done[slot]));  // the upload two calls back has left the pinned slot
+        memcpy(h_legs[slot], legs_.data(), sizeof(SweepLeg) * legs_.size());
+        PG_HIP(hipMemcpyAsync(d_legs[slot], h_legs[slot], sizeof(SweepLeg) * legs_.size(), hipMemcpyHostToDevice, s));
+        PG_HIP(hipEventRecord(h_done[slot], s));
+        used[slot] = true;
+        parity ^= 1;
+        p.n_legs = (int)legs_.size();
+    }
+    const bool mix_in = in != nullptr && !(sweep_on && !sw.mix);  // a generator that replaces never reads the input
+    const float2 *src = mix_in ? in : nullptr;
+    const int vec = ((reinterpret_cast<uintptr_t>(out) | (src ? reinterpret_cast<uintptr_t>(src) : 0)) & 15) == 0 && (streams == 1 || ((in_pitch | out_pitch) & 1) == 0);
+    const long long items = vec ? (n + 1) / 2 : n;
+    long long blocks = (items + 255) / 256;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    launch(k_testbench, dim3((unsigned)blocks, streams), dim3(256), s, src, out, in_pitch, out_pitch, n, vec, p, (const SweepLeg *)(sweep_on ? d_legs[slot] : nullptr));
+    PG_HIP(hipGetLastError());
+    n_abs += (unsigned long long)n;
+    return 0;
+}
+
+int TestBenchCore::draws(hipStream_t s, uint32_t stream, uint64_t first, uint32_t n, uint32_t *r, uint8_t *attempt)
+{
+    if (!n) return 0;
+    unsigned *d_r = nullptr;
+    unsigned char *d_a = nullptr;
+    PG_HIP(hipMalloc((void **)&d_r, sizeof(unsigned) * 2 * (size_t)n));
+    if (hipMalloc((void **)&d_a, n) != hipSuccess) { (void)hipFree(d_r); return fail(PEBBLEGPU_E_HIP, "hipMalloc failed"); }
+    launch(k_testbench_draws, dim3((n + 255) / 256), dim3(256), s, (unsigned long long)seed, stream, (unsigned long long)first, (int)n, d_r, d_a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(r, d_r, sizeof(unsigned) * 2 * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(attempt, d_a, n, hipMemcpyDeviceToHost);
+    (void)hipFree(d_r);
+    (void)hipFree(d_a);
+    if (e != hipSuccess) return fail(PEBBLEGPU_E_HIP, "noise draws: %s", hipGetErrorString(e));
+    return 0;
+}
+
+}  // namespace pg

@@ -164,6 +164,26 @@ int pebblegpu_set_squelch(pebblegpu_receiver *h, uint32_t channel, double squelc
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
     return h->rx.set_squelch(channel, squelch_db);
 }
+int pebblegpu_set_testbench_sweep(pebblegpu_receiver *h, const pebblegpu_sweep *s)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.set_testbench_sweep(s);
+}
+int pebblegpu_set_testbench_noise(pebblegpu_receiver *h, double amplitude, uint64_t seed)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.set_testbench_noise(amplitude, seed);
+}
+int pebblegpu_receiver_set_taps(pebblegpu_receiver *h, uint32_t mask)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.set_taps(mask);
+}
+const void *pebblegpu_receiver_tap(const pebblegpu_receiver *h, int point, uint64_t *samples_per_row, uint64_t *pitch_samples, double *rate)
+{
+    if (!h) return nullptr;
+    return h->rx.tap(point, samples_per_row, pitch_samples, rate);
+}
 int pebblegpu_set_demod_mode(pebblegpu_receiver *h, uint32_t channel, int mode)
 {
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");

@@ -468,6 +468,50 @@ struct AnfCore {
     int run(hipStream_t s, float2 *buf, long long pitch, long long n, Gate gate = Gate{nullptr, 0, 0});
 };
 
+// ---- the test bench's generator: NCO::genSweep + NCO::genNoise at the head of the chain (receiver.cpp:797-798; kernels_testbench.h) ----
+constexpr int kTbNoiseAttempts = 32;  // polar-method attempts per sample at most (all failing: the sample gets no noise)
+constexpr int kTbMinLeg = 64;         // shortest sweep leg, in samples, the per-call leg table is built for
+constexpr unsigned long long kTbMaxPiece = 1ull << 26;        // longest stretch one leg-table entry covers (longer ones are split on the host)
+constexpr unsigned long long kTbMaxPulsePeriod = 1ull << 28;  // pulse periods from here on are refused (the setter runs the timer's serial sum once)
+struct SweepLeg { unsigned long long k0; double turns0, f0, inc; };  // from call-relative sample k0 on: phase (turns) and frequency there, Hz per sample
+struct TbParams {                     // k_testbench's argument block
+    double fs_inv, amp, noise_amp;
+    unsigned long long n0, seed;      // absolute number of the call's first sample (pulse timer, noise counter)
+    unsigned long long pulse_period, pulse_on;  // 0: no pulse modulation
+    unsigned stream0;
+    int n_legs, sweep_on, mix, noise_on;
+};
+struct TbSweepPlan { double inc = 0; unsigned long long leg = 0, pulse_period = 0, pulse_on = 0; };
+int tb_plan_sweep(double fs, const pebblegpu_sweep *s, TbSweepPlan *plan);  // host only: leg length and the pulse timer's period / width in samples
+struct TestBenchCore {
+    double fs = 0;
+    uint32_t S = 1;
+    bool sweep_on = false, noise_on = false;
+    pebblegpu_sweep sw = {};
+    TbSweepPlan plan;
+    double noise_amp = 0;
+    uint64_t seed = 0;
+    // carried from call to call: samples since the last setter, phase in turns, and where the sweep stands in its leg
+    unsigned long long n_abs = 0, leg_pos = 0, leg_len = 0;
+    double turns = 0, f_leg = 0, inc = 0, start = 0, stop = 0;
+    bool up = true;
+    std::vector<SweepLeg> legs_;
+    SweepLeg *d_legs[2] = {nullptr, nullptr}, *h_legs[2] = {nullptr, nullptr};  // the call's leg table, ping-pong (pinned staging: no host wait per call)
+    hipEvent_t h_done[2] = {nullptr, nullptr};
+    bool used[2] = {false, false};
+    size_t leg_cap = 0;
+    int parity = 0;
+    bool any() const { return sweep_on || noise_on; }
+    int init(double sample_rate, uint32_t streams);
+    void release();
+    void reset();                                        // TestBench::reset
+    int set_sweep(const pebblegpu_sweep *s);             // nullptr: off
+    int set_noise(double amplitude, uint64_t seed);      // amplitude <= 0: off
+    int build_legs(long long n, std::vector<SweepLeg> &legs);
+    int run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, uint32_t streams, uint32_t stream0);
+    int draws(hipStream_t s, uint32_t stream, uint64_t first, uint32_t n, uint32_t *r, uint8_t *attempt);
+};
+
 // ---- CFractResampler (complex), pebblelib/fractresampler.cpp ----
 struct ResampCore {
     uint32_t C = 0, nf = 0;
@@ -579,6 +623,12 @@ public:
     int set_morse(uint32_t ch, bool on);
     int morse_events(uint32_t ch, MorseEvent *ev, uint32_t cap, uint32_t *n);
     int morse_status(uint32_t ch, MorseStatus *st);
+    // the test bench on the batched path: the generator at the head of the chain (TestBench::genSweep / genNoise, receiver.cpp:797-798) and
+    // copies of the signal at the reference's displayData points (:803, :945, :953, :992) and at the digital-modem hook (:979-980)
+    int set_testbench_sweep(const pebblegpu_sweep *s);
+    int set_testbench_noise(double amplitude, uint64_t seed);
+    int set_taps(uint32_t mask);
+    const float2 *tap(int point, uint64_t *n_per_row, uint64_t *pitch, double *rate) const;
     int process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw = nullptr);
     // spectrum_updated (may be null): whether this frame got a spectrum (always, without the update timer)
     int process_iq(const double *iq, uint16_t n, double *audio, uint32_t *n_audio, double *spectrum_db, uint32_t *spectrum_updated = nullptr);
@@ -679,6 +729,16 @@ private:
     ConditionCore cond_;
     AnfCore anf_;
     MorseCore morse_;
+    TestBenchCore tb_;
+    bool last_tb_ = false;            // the last call ran the generator (kernel_name)
+    // taps: one buffer per enabled point (allocated when the point is first enabled), filled by a copy queued on the stream that has
+    // just produced the signal; index = the point's number (PEBBLEGPU_TAP_*)
+    static constexpr int kTapPoints = 17;
+    static constexpr uint32_t kTapsBehindGate = 1u << PEBBLEGPU_TAP_MODEM | 1u << PEBBLEGPU_TAP_POST_DEMOD;  // points a closed squelch gate never reaches
+    uint32_t taps_ = 0;
+    float2 *d_tap_[kTapPoints] = {};
+    uint64_t tap_n_[kTapPoints] = {};
+    int copy_tap(hipStream_t s, int point, const float2 *src, long long src_pitch, long long n, uint32_t rows);
     ResampCore resamp_;
     SpectrumCore spec_, zoom_;
     float2 *d_stage_in_ = nullptr;

@@ -1,6 +1,7 @@
 // receiver.hip -- the receiver bank: Receiver::processIQData's DSP (application/receiver.cpp:826-987)
 // for C tuned channels, composed from the device cores in the reference's step order.
 #include <cmath>
+#include <map>
 #include "receiver.h"
 
 namespace pg {
@@ -80,6 +81,7 @@ int Receiver::create(const pebblegpu_config *cfg)
         wfmc_.stereo_block = (int)nf;  // the reference demodulates one accumulated frame per call (receiver.cpp:896)
     }
     if (int rc = cond_.init(S, nf, fs, max_n)) return rc;
+    if (int rc = tb_.init(fs, S)) return rc;
     audio_rate = cfg->audio_rate;
     if (audio_rate) {
         // resampRate = (m_demodSampleRate*1.0) / (m_audioOutRate*1.0), the int members (receiver.cpp:901,994)
@@ -119,6 +121,8 @@ Receiver::~Receiver()
     if (map_ev_) (void)hipEventDestroy(map_ev_);
     agc_.release(); resamp_.release(); cond_.release(); anf_.release();
     morse_.release();
+    tb_.release();
+    for (float2 *p : d_tap_) if (p) (void)hipFree(p);
     if (d_audio_rs) (void)hipFree(d_audio_rs);
     if (h_gate_) (void)hipHostFree(h_gate_);
     if (d_squelch) (void)hipFree(d_squelch);
@@ -315,6 +319,11 @@ int Receiver::stereo_lock(uint32_t ch, int *lock, int *changed)
 int Receiver::set_squelch(uint32_t ch, double squelch_db)
 {
     if (ch >= C) return fail(PEBBLEGPU_E_INVALID, "channel %u of %u", ch, C);
+    if (squelch_db > -120.0) {
+        std::lock_guard<std::mutex> g(mu_);
+        if (taps_ & kTapsBehindGate)
+            return fail(PEBBLEGPU_E_UNSUPPORTED, "a squelch gate ends the call before the modem hook and the demodulator: their taps are on (pebblegpu_receiver_set_taps)");
+    }
     if (C != 1 || max_sf != 1) {
         // a bank, or calls of several super-frames: per-channel thresholds, the decision per (channel, super-frame) on the device
         if (wfm) {
@@ -354,6 +363,62 @@ int Receiver::set_squelch(uint32_t ch, double squelch_db)
         PG_HIP(hipHostMalloc((void **)&h_gate_, sizeof(float4)));
     }
     squelch_db_ = squelch_db;
+    return 0;
+}
+
+// TestBench::reset() + the generator switches (testbench.cpp:550-566): the next call starts the sweep and the noise counter afresh
+int Receiver::set_testbench_sweep(const pebblegpu_sweep *s)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (int rc = tb_.set_sweep(s)) return rc;
+    touched_ = true;  // the next call joins its two pipelines before the change is applied
+    return 0;
+}
+
+int Receiver::set_testbench_noise(double amplitude, uint64_t seed)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (int rc = tb_.set_noise(amplitude, seed)) return rc;
+    touched_ = true;
+    return 0;
+}
+
+int Receiver::set_taps(uint32_t mask)
+{
+    const uint32_t known = 1u << PEBBLEGPU_TAP_RAW_IQ | 1u << PEBBLEGPU_TAP_POST_MIXER | 1u << PEBBLEGPU_TAP_POST_BP | 1u << PEBBLEGPU_TAP_POST_DEMOD | 1u << PEBBLEGPU_TAP_MODEM;
+    if (mask & ~known) return fail(PEBBLEGPU_E_INVALID, "tap mask %#x names a point that does not exist", mask);
+    if (wfm && (mask & (kTapsBehindGate | 1u << PEBBLEGPU_TAP_POST_BP)))
+        return fail(PEBBLEGPU_E_UNSUPPORTED, "the WFM branch has no band-pass, modem hook or post-demodulator display point (receiver.cpp:854-901)");
+    std::lock_guard<std::mutex> g(mu_);
+    if ((mask & kTapsBehindGate) && (squelch_db_ > -120.0 || bank_gate_))
+        return fail(PEBBLEGPU_E_UNSUPPORTED, "a squelch gate ends the call before the modem hook and the demodulator: no tap there while a threshold is set");
+    PG_HIP(hipSetDevice(device));
+    const size_t max_n = (size_t)max_sf * superframe;
+    for (int pt = 0; pt < kTapPoints; pt++) {
+        if (!(mask >> pt & 1u)) continue;
+        if (!d_tap_[pt]) PG_HIP(hipMalloc((void **)&d_tap_[pt], sizeof(float2) * (pt == PEBBLEGPU_TAP_RAW_IQ ? (size_t)S * max_n : (size_t)C * (max_n / chain.total))));
+        if (!(taps_ >> pt & 1u)) tap_n_[pt] = 0;  // (nothing of this point yet)
+    }
+    taps_ = mask;
+    touched_ = true;  // the next call joins its two pipelines first
+    return 0;
+}
+
+const float2 *Receiver::tap(int point, uint64_t *n_per_row, uint64_t *pitch, double *rate) const
+{
+    if (point < 0 || point >= kTapPoints || !(taps_ >> point & 1u) || !tap_n_[point]) return nullptr;
+    if (n_per_row) *n_per_row = tap_n_[point];
+    if (pitch) *pitch = tap_n_[point];  // rows are compact
+    if (rate) *rate = point == PEBBLEGPU_TAP_RAW_IQ ? fs : (double)demod_rate_int;
+    return d_tap_[point];
+}
+
+// rows of n samples at src (pitched) -> the point's buffer, compact, behind whatever `s` has queued
+int Receiver::copy_tap(hipStream_t s, int point, const float2 *src, long long src_pitch, long long n, uint32_t rows)
+{
+    if (!(taps_ >> point & 1u)) return 0;
+    PG_HIP(hipMemcpy2DAsync(d_tap_[point], sizeof(float2) * (size_t)n, src, sizeof(float2) * (size_t)src_pitch, sizeof(float2) * (size_t)n, rows, hipMemcpyDeviceToDevice, s));
+    tap_n_[point] = (uint64_t)n;
     return 0;
 }
 
@@ -495,14 +560,18 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     // call's transform instead of on an idle GPU.  Results are complete after sync() (the contract of include/pebblegpu.h).
     // Anything else -- a control change to apply, a call of another shape -- first orders the two queues behind each other.
     const bool was_touched = touched_;
+    for (uint64_t &tn : tap_n_) tn = 0;  // a tap holds the last call's signal: a point this call does not reach reads as "nothing" (NULL), never as an older call's
     // Two-stage calls of a receiver without a display transform: mixer + decimator (and the refresh of their histories) on the main
     // stream, band-pass, noise filter, AGC, demodulators and resampler on the chain's stream behind an event -- the decimator of the next
     // call does not wait for them (it writes the other output buffer; it does wait for the band-pass of the call before the last, which
     // read that buffer).  The decimator of a bank leaves the vector units idle two thirds of the time (one wave per SIMD, bound by
     // its own instruction stream): the band-pass of the previous call fits beside it.  Results are complete after sync().
     const bool bank_pipe = bank_pipe_ok_ && with_chain && !with_spectrum && !profile_detail && squelch_db_ <= -120.0 && !bank_gate_ && !zoom_bins &&
-                           !cond_.any && !cond_.dirty && dec_.double_out();
-    const bool plain = (side && tun_.pipeline && !touched_) || (bank_pipe && !touched_);
+                           !cond_.any && !cond_.dirty && !tb_.any() && !taps_ && dec_.double_out();
+    // (a call with the test bench's generator on is staged through a buffer successive calls share, as a conditioned call is: it may run its
+    // chain beside its own display transform -- the kernels of the same call without a generator, so that injecting on the device and
+    // feeding the summed stream give the same audio bit for bit -- but never pipelined with its neighbours, and never raw-fused)
+    const bool plain = ((side && tun_.pipeline && !touched_) || (bank_pipe && !touched_)) && !tb_.any();
     auto join = [&]() -> int {
         if (chain_end_) PG_HIP(hipStreamWaitEvent(stream_, chain_end_, 0));
         if (spec_end_) PG_HIP(hipStreamWaitEvent(chain_stream_, spec_end_, 0));
@@ -519,7 +588,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         // and the one-channel first stage beside it) there is no float2 copy of the stream at all; otherwise normalizeIQ runs
         // as its own pass into a staging buffer and the call goes on from there.
         dec_.want_lds_free = side;
-        const bool fused = side && S == 1 && spec_.raw_ready() && dec_.raw_ready(osc_);
+        const bool fused = side && S == 1 && spec_.raw_ready() && dec_.raw_ready(osc_) && !tb_.any();
         staged = !fused;
         if (!fused) {
             if (plain && !bank_pipe) { if (int rc = join()) return rc; }  // the staging buffer is shared by successive calls (two-stage calls: only their first stage touches it)
@@ -531,6 +600,16 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         }
     }
     long long in_pitch = (long long)n;
+    // TestBench::genSweep + genNoise, receiver.cpp:797-798: into the library's staging buffer (a raw call has been converted into it above:
+    // generated in place; float2 input is read from the caller's buffer, which is never written)
+    last_tb_ = tb_.any();
+    if (last_tb_) {
+        if (!d_raw_stage_) PG_HIP(hipMalloc((void **)&d_raw_stage_, sizeof(float2) * (size_t)S * max_sf * superframe));
+        if (int rc = tb_.run(stream_, d_iq, in_pitch, d_raw_stage_, in_pitch, (long long)n, S, 0)) return rc;
+        d_iq = d_raw_stage_;
+        staged = true;
+    }
+    const float2 *tap_iq = d_iq;  // displayData(.., TB_RAW_IQ), receiver.cpp:803: before the conditioners
     // DCRemoval, IQBalance, NoiseBlanker 1/2 on the raw streams, ahead of the spectrum and the mixer (receiver.cpp:814-823)
     if (int rc = cond_.run(stream_, d_iq, in_pitch, (long long)n, &d_iq, &in_pitch)) return rc;
     hipEvent_t *ev = tm.slot();
@@ -618,6 +697,11 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         }
     }
     // (every record is a ~5 us bubble in the stream: a call with no display transform does without the one behind it)
+    if (taps_ >> PEBBLEGPU_TAP_RAW_IQ & 1u) {  // (behind the display transform on its stream: the chain's start does not wait for the copy)
+        if (raw) { if (int rc = run_normalize_iq(raw->fmt, raw->order, 1.0, raw->base, (long long)(S * n), d_tap_[PEBBLEGPU_TAP_RAW_IQ], stream_, false, &raw->scale)) return rc; }
+        else PG_HIP(hipMemcpyAsync(d_tap_[PEBBLEGPU_TAP_RAW_IQ], tap_iq, sizeof(float2) * (size_t)S * n, hipMemcpyDeviceToDevice, stream_));
+        tap_n_[PEBBLEGPU_TAP_RAW_IQ] = n;
+    }
     const bool mid = with_spectrum || profile_detail || side;
     if (mid) PG_HIP(hipEventRecord(ev[1], stream_));
     tm.detailed[(tm.calls - 1) % Timers::kRing] = profile_detail;
@@ -674,6 +758,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         if (int rc = run_nap(cs, nap >= 0 ? (unsigned)nap : (rot3 ? 0u : 800u))) return rc;
     }
     const long long nd = dec_.out_len();
+    if (int rc = copy_tap(cs, PEBBLEGPU_TAP_POST_MIXER, dec_.out().data(), dec_.out().pitch, nd, C)) return rc;  // receiver.cpp:945 (WFM: m_sampleBuf, :884)
     if (zoom_bins) {  // SignalSpectrum::zoomed(m_sampleBuf, numStepSamples), receiver.cpp:884 / :942 (its update timer: open by default)
         if (gated()) {  // m_hiResTimer: the same period, counted in decimated frames at the demodulator rate (signalspectrum.cpp:94-100)
             sel_zoom_.clear();
@@ -690,6 +775,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     if (!wfm) {
         if (int rc = ff_.run(cs, dec_.out(), nd, audio.data(), audio.pitch)) return rc;  // receiver.cpp:950
         if (profile_detail) PG_HIP(hipEventRecord(ev[4], cs));
+        if (int rc = copy_tap(cs, PEBBLEGPU_TAP_POST_BP, audio.data(), audio.pitch, nd, C)) return rc;  // receiver.cpp:953
     }
     // Squelch, receiver.cpp:893-897 / :962-965: below the threshold the reference returns here -- nothing behind the gate
     // runs or changes state, and no audio leaves the call.
@@ -726,6 +812,11 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         last_audio_n = 0;
         gate_closed = true;
         if (profile_detail) { if (wfm) PG_HIP(hipEventRecord(ev[4], cs)); }
+        for (int pt : {PEBBLEGPU_TAP_MODEM, PEBBLEGPU_TAP_POST_DEMOD}) {  // "Tune only mode" returns before both points: their rows read zero
+            if (!(taps_ >> pt & 1u)) continue;
+            PG_HIP(hipMemsetAsync(d_tap_[pt], 0, sizeof(float2) * (size_t)nd * C, cs));
+            tap_n_[pt] = (uint64_t)nd;
+        }
     } else if (!wfm && bank_gate_) {
         // Per-channel squelch of a bank: the decision is made on the device from the S-meter of each super-frame's last raw frame
         // (no read-back, no stream synchronisation); everything behind the band-pass then runs one super-frame at a time and
@@ -760,6 +851,11 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
             if (ctl_[ch].mode == PEBBLEGPU_DM_NONE) PG_HIP(hipMemsetAsync(audio.data((int)ch), 0, sizeof(float2) * (size_t)nd, cs));
     } else if (!wfm) {
         if (int rc = anf_.run(cs, audio.data(), audio.pitch, nd)) return rc;  // NoiseFilter::ProcessBlock, receiver.cpp:974
+        if (taps_ >> PEBBLEGPU_TAP_MODEM & 1u) {  // the frame m_iDigitalModem->processBlock receives (a dmNONE channel's call has returned before, :968-971)
+            if (int rc = copy_tap(cs, PEBBLEGPU_TAP_MODEM, audio.data(), audio.pitch, nd, C)) return rc;
+            for (uint32_t ch = 0; ch < C; ch++)
+                if (ctl_[ch].mode == PEBBLEGPU_DM_NONE) PG_HIP(hipMemsetAsync(d_tap_[PEBBLEGPU_TAP_MODEM] + (size_t)ch * nd, 0, sizeof(float2) * (size_t)nd, cs));
+        }
         // m_iDigitalModem->processBlock, receiver.cpp:979-980: the Morse modem reads the rows before the AGC overwrites them
         if (morse_.any()) { if (int rc = morse_.run(cs, audio.data(), audio.pitch, nd)) return rc; }
         if (int rc = agc_.run(cs, audio.data(), audio.pitch, nd)) return rc;  // AGC::processBlock, receiver.cpp:983
@@ -770,6 +866,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         if (nfm_.C) { if (int rc = nfm_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd)) return rc; }
         for (uint32_t ch = 0; ch < C; ch++)  // clearCPX(m_audioBuf, ...) of the bank's tune-only channels
             if (ctl_[ch].mode == PEBBLEGPU_DM_NONE) PG_HIP(hipMemsetAsync(audio.data((int)ch), 0, sizeof(float2) * (size_t)nd, cs));
+        if (int rc = copy_tap(cs, PEBBLEGPU_TAP_POST_DEMOD, audio.data(), audio.pitch, nd, C)) return rc;  // receiver.cpp:992, before the resampler
     } else {
         if (profile_detail) PG_HIP(hipEventRecord(ev[4], cs));
         // (the call's tail refresh rides on the demodulator's launch: it is the last kernel of the call, run on an idle GPU)
@@ -859,11 +956,25 @@ int Receiver::process_ingested(uint32_t slot, int fmt, int order, double gain, u
     return ingest_.mark_in_flight(*g, stream_, chain_stream_);
 }
 
+// "k_testbench + <front kernel>": one string per front-kernel name, kept for the life of the process like the literals the other groups
+// return (the set of names is small and fixed)
+static const char *testbench_label(const char *front)
+{
+    static std::mutex mu;
+    static std::map<std::string, std::string> labels;
+    std::lock_guard<std::mutex> g(mu);
+    auto it = labels.find(front);
+    if (it == labels.end()) it = labels.emplace(front, std::string("k_testbench + ") + front).first;
+    return it->second.c_str();
+}
+
 const char *Receiver::kernel_name(int which) const
 {
     switch (which) {
     case 1: return !bins ? "" : gated() ? (spec_.any ? "k_spectrum_list_any" : "k_spectrum_list_q128") : spec_.big ? "k_big256_cols + k_big256_rows" : spec_.per_q ? "k_spectrum_q128" : bins == 8192 ? (spec_.use_w64 ? "k_spectrum_w64" : spec_.last_fullc ? "k_spectrum_t128 (twiddles held)" : "k_spectrum_t128") : bins == 4096 ? "k_spectrum<2>" : "k_spectrum_1to1";
-    case 2: return dec_.front_name;
+    case 2:
+        if (!last_tb_) return dec_.front_name;
+        return testbench_label(dec_.front_name);
     case 3: return dec_.rest_name;
     case 4: return wfm ? "" : ff_n == 2048 ? "k_fastfir_t128" : "k_fastfir";
     case 5: return wfm ? (wfmc_.fused ? "k_wfm_fir" : "k_iir_scan + k_discrim + k_fir_dec") : "k_anf/k_agc/k_iir_scan/k_pll_demod + k_fir_dec (listed channels only)";
@@ -933,6 +1044,8 @@ int Receiver::process_iq(const double *iq, uint16_t n, double *audio_out, uint32
     if (S != 1) return fail(PEBBLEGPU_E_UNSUPPORTED, "process_iq feeds one stream; this bank has %u", S);
     if (cond_.any || cond_.dirty)
         return fail(PEBBLEGPU_E_UNSUPPORTED, "the input conditioners run on the batched device path (pebblegpu_receiver_process) only");
+    if (tb_.any() || taps_)  // (here `iq` is a host CPX *: the host injects and displays itself)
+        return fail(PEBBLEGPU_E_UNSUPPORTED, "the test bench's generator and taps run on the batched device path (pebblegpu_receiver_process) only");
     PG_HIP(hipSetDevice(device));
     if (!d_stage_in_) PG_HIP(hipMalloc((void **)&d_stage_in_, sizeof(float2) * superframe));
     h_frame_.resize((size_t)nf * 2);

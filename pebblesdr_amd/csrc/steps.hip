@@ -3,6 +3,7 @@
 #include <cmath>
 #include <new>
 #include "receiver.h"
+#include "kernels_testbench.h"
 
 namespace pg {
 int run_mixer(hipStream_t s, const float2 *d_in, float2 *d_out, long long n, const OscBank &osc);
@@ -95,6 +96,13 @@ struct pebblegpu_demod : pg::StepBase {
     pg::PllCore nfm, sam;
     pg::WfmCore wfm;
     float2 *d_in = nullptr, *d_out = nullptr;
+};
+// the test bench's generator (NCO::genSweep / genNoise) on one stream of the caller's
+struct pebblegpu_siggen : pg::StepBase {
+    pg::TestBenchCore tb;
+    uint32_t noise_stream = 0;
+    float2 *d_buf = nullptr;
+    size_t cap = 0;
 };
 struct pebblegpu_spectrum : pg::StepBase {
     pg::SpectrumCore sp;
@@ -648,6 +656,95 @@ int pebblegpu_spectrum_map_to_screen(pebblegpu_spectrum *s, const pebblegpu_scre
     PG_HIP(hipMemcpyAsync(out, s->d_px, sizeof(int32_t) * (size_t)map->x_pixels, hipMemcpyDeviceToHost, s->stream));
     PG_HIP(hipStreamSynchronize(s->stream));
     return 0;
+}
+
+// ---------------- test-bench generator ----------------
+int pebblegpu_sweep_plan(double sample_rate, const pebblegpu_sweep *s, uint64_t *leg_samples, uint64_t *pulse_period_samples, uint64_t *pulse_on_samples)
+{
+    pg::TbSweepPlan pl;
+    if (int rc = pg::tb_plan_sweep(sample_rate, s, &pl)) return rc;
+    if (leg_samples) *leg_samples = pl.leg;
+    if (pulse_period_samples) *pulse_period_samples = pl.pulse_period;
+    if (pulse_on_samples) *pulse_on_samples = pl.pulse_on;
+    return 0;
+}
+int pebblegpu_siggen_destroy(pebblegpu_siggen *g)
+{
+    if (!g) return 0;
+    g->close_stream();
+    g->tb.release();
+    if (g->d_buf) (void)hipFree(g->d_buf);
+    delete g;
+    return 0;
+}
+int pebblegpu_siggen_create(int device, double sample_rate, uint32_t frames_per_buffer, pebblegpu_siggen **out)
+{
+    if (!out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (int rc = step_device(device)) return rc;
+    if (!(sample_rate > 0) || !std::isfinite(sample_rate) || frames_per_buffer == 0) return fail(PEBBLEGPU_E_INVALID, "bad sample rate or buffer size");
+    pebblegpu_siggen *g = new (std::nothrow) pebblegpu_siggen();
+    if (!g) return fail(PEBBLEGPU_E_INVALID, "out of host memory");
+    int rc = g->open(device);
+    if (!rc) rc = g->tb.init(sample_rate, 1);
+    if (!rc && hipMalloc((void **)&g->d_buf, sizeof(float2) * frames_per_buffer) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
+    if (rc) { pebblegpu_siggen_destroy(g); return rc; }
+    g->cap = frames_per_buffer;
+    *out = g;
+    return 0;
+}
+int pebblegpu_siggen_set_sweep(pebblegpu_siggen *g, const pebblegpu_sweep *s)
+{
+    if (!g) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return g->tb.set_sweep(s);
+}
+int pebblegpu_siggen_set_noise(pebblegpu_siggen *g, double amplitude, uint64_t seed)
+{
+    if (!g) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return g->tb.set_noise(amplitude, seed);
+}
+int pebblegpu_siggen_set_stream(pebblegpu_siggen *g, uint32_t stream)
+{
+    if (!g) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    g->noise_stream = stream;
+    return 0;
+}
+int pebblegpu_siggen_generate_device(pebblegpu_siggen *g, void *d_iq, uint64_t n)
+{
+    if (!g || !d_iq) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (n == 0 || n > (uint64_t)1 << 40) return fail(PEBBLEGPU_E_SIZE, "bad sample count");
+    PG_HIP(hipSetDevice(g->device));
+    return g->tb.run(g->stream, (const float2 *)d_iq, (long long)n, (float2 *)d_iq, (long long)n, (long long)n, 1, g->noise_stream);
+}
+int pebblegpu_siggen_synchronize(pebblegpu_siggen *g)
+{
+    if (!g) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    PG_HIP(hipSetDevice(g->device));
+    PG_HIP(hipStreamSynchronize(g->stream));
+    return 0;
+}
+int pebblegpu_siggen_generate(pebblegpu_siggen *g, double *iq, uint32_t n)
+{
+    if (!g || !iq) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (n == 0) return fail(PEBBLEGPU_E_SIZE, "bad sample count");
+    if (!g->tb.any()) return 0;  // both generators off: the frame stays as it is (testbench.cpp:522-523, 539-540)
+    PG_HIP(hipSetDevice(g->device));
+    if (n > g->cap) {
+        PG_HIP(hipStreamSynchronize(g->stream));
+        PG_HIP(hipFree(g->d_buf));
+        g->d_buf = nullptr;
+        g->cap = 0;
+        PG_HIP(hipMalloc((void **)&g->d_buf, sizeof(float2) * n));
+        g->cap = n;
+    }
+    if (int rc = g->up(g->d_buf, iq, n)) return rc;
+    if (int rc = g->tb.run(g->stream, g->d_buf, n, g->d_buf, n, n, 1, g->noise_stream)) return rc;
+    return g->down(iq, g->d_buf, n);
+}
+int pebblegpu_siggen_noise_draws(pebblegpu_siggen *g, uint64_t first_sample, uint32_t n, uint32_t *r, uint8_t *attempt)
+{
+    if (!g || !r || !attempt) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    PG_HIP(hipSetDevice(g->device));
+    return g->tb.draws(g->stream, g->noise_stream, first_sample, n, r, attempt);
 }
 
 }  // extern "C"
