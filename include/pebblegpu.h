@@ -478,7 +478,8 @@ int pebblegpu_streambank_destroy(pebblegpu_streambank *sb);
 int pebblegpu_streambank_set_bandpass(pebblegpu_streambank *sb, uint32_t stream, double lo, double hi);
 /* d_iq: [stream][n_samples] float2, n_samples a multiple of frame.  what: bit 0 band-pass, bit 1 spectrum */
 int pebblegpu_streambank_process(pebblegpu_streambank *sb, const void *d_iq, uint64_t n_samples, uint32_t what);
-/* filtered [stream][n_samples] float2 (row pitch returned); spectrum [stream][frames][bins] float dB */
+/* filtered [stream][n_samples] float2 (row pitch returned); spectrum [stream][frames][bins] float dB (under an update gate, below:
+ * the computed frames only) */
 const void *pebblegpu_streambank_filtered(const pebblegpu_streambank *sb, uint64_t *samples_per_stream, uint64_t *pitch_samples);
 const void *pebblegpu_streambank_spectrum(const pebblegpu_streambank *sb, uint64_t *frames_per_stream, uint32_t *bins);
 /* which: 0 whole call, 1 band-pass kernel, 2 spectrum kernels */
@@ -517,6 +518,30 @@ const char *pebblegpu_streambank_kernel_name(const pebblegpu_streambank *sb, int
  * after pebblegpu_streambank_synchronize. */
 int pebblegpu_streambank_map_spectrum(pebblegpu_streambank *sb, const pebblegpu_screen_map *map, uint32_t first_frame, uint32_t n_frames,
                                       uint32_t frame_step, int32_t *d_out);
+/* The spectrum's update gate for a stream bank: pebblegpu_set_spectrum_updates (above; its comment is the specification) with ONE
+ * timer per bank on the bank's sample clock -- all streams share it, so all select the same frames; the rate of the rule is
+ * sample_rate rounded to the nearest whole Hz, frames_per_buffer is `frame`.  PEBBLEGPU_SPECTRUM_EVERY_FRAME (-1, the default): every
+ * frame, exactly as without this setter; 0: no spectrum; a negative rate other than -1 is PEBBLEGPU_E_INVALID.  Changing the rate
+ * changes the period only, the timer runs on.  With a gate set:
+ *   - the frame list is worked out on the host before anything is queued (no read-back, no synchronisation), for every process call:
+ *     pebblegpu_streambank_process, _process_raw and _process_ingested (raw and float2 results stay equal bit for bit);
+ *   - pebblegpu_streambank_spectrum returns the COMPUTED rows only, compact: [stream][n_selected][bins]; the frame count it reports is
+ *     n_selected and may be 0; a row is averaged with the previous COMPUTED row's amplitudes (fft.cpp:378-386), across calls; a call
+ *     that selects nothing launches no transform and leaves those amplitudes alone;
+ *   - pebblegpu_streambank_map_spectrum indexes the compact rows; after a call that asked for the spectrum (bit 1) and selected nothing it
+ *     maps the latest row computed before it, as frame 0 with n_frames = 1 (refused before any row has been computed); after a call
+ *     without bit 1 it is refused, gate or no gate;
+ *   - pebblegpu_streambank_last_ms(sb, 2) is valid (nothing elapsed when nothing ran), pebblegpu_streambank_kernel_name(sb, 2) names the
+ *     frame-list kernels ("k_big256_cols_list + k_big256_rows", "k_spectrum_list_q128", "k_spectrum_list_any", with " (raw ...)" or
+ *     "k_normalize_iq + " as for the every-frame kernels) and is "" after a call that selected nothing;
+ *   - the band-pass output is the same on every route, bit for bit.
+ * A call WITHOUT bit 1 of `what` advances the sample clock by its frames and nothing else: it selects no frame and neither starts nor
+ * restarts the timer (under the default as well: a later gate counts from the last frame that did get a spectrum). */
+int pebblegpu_streambank_set_spectrum_updates(pebblegpu_streambank *sb, int updates_per_sec);
+/* which frames of the last call got a spectrum: indices relative to the call's first frame, ascending, row i of the spectrum buffer
+ * belongs to idx[i].  Without a gate every frame of the last call (none when it did not ask for the spectrum); *n = 0 before any call;
+ * PEBBLEGPU_E_SIZE when cap is too small.  Known the moment the process call returns. */
+int pebblegpu_streambank_spectrum_frames(const pebblegpu_streambank *sb, uint32_t *idx, uint32_t cap, uint32_t *n);
 
 /* ------------------------------------------------------------------------------------------------
  * Stand-alone process steps with the reference's per-class call shapes, host buffers in and out.

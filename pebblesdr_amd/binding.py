@@ -40,6 +40,7 @@ SYMBOLS = [
     "pebblegpu_morse_events", "pebblegpu_morse_status", "pebblegpu_morse_results", "pebblegpu_morse_set_sample_rate",
     "pebblegpu_morse_keep_results",
     "pebblegpu_set_spectrum_updates", "pebblegpu_receiver_spectrum_frames", "pebblegpu_process_iq_updates",
+    "pebblegpu_streambank_set_spectrum_updates", "pebblegpu_streambank_spectrum_frames",
     "pebblegpu_sweep_plan", "pebblegpu_set_testbench_sweep", "pebblegpu_set_testbench_noise", "pebblegpu_receiver_set_taps", "pebblegpu_receiver_tap",
     "pebblegpu_siggen_create", "pebblegpu_siggen_destroy", "pebblegpu_siggen_set_sweep", "pebblegpu_siggen_set_noise", "pebblegpu_siggen_set_stream",
     "pebblegpu_siggen_generate_device", "pebblegpu_siggen_synchronize", "pebblegpu_siggen_generate", "pebblegpu_siggen_noise_draws",
@@ -232,6 +233,8 @@ def _declare(L):
     L.pebblegpu_process_iq_updates.argtypes = [vp, dp, C.c_uint16, dp, C.POINTER(u32), dp, C.POINTER(u32)]
     L.pebblegpu_set_spectrum_updates.argtypes = [vp, i32]
     L.pebblegpu_receiver_spectrum_frames.argtypes = [vp, i32, C.POINTER(u32), u32, C.POINTER(u32)]
+    L.pebblegpu_streambank_set_spectrum_updates.argtypes = [vp, i32]
+    L.pebblegpu_streambank_spectrum_frames.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(u32)]
     L.pebblegpu_streambank_create.argtypes = [C.POINTER(StreamBankConfig), C.POINTER(vp)]
     L.pebblegpu_streambank_destroy.argtypes = [vp]
     L.pebblegpu_streambank_set_bandpass.argtypes = [vp, u32, dbl, dbl]
@@ -808,6 +811,19 @@ class StreamBank:
     def set_bandpass(self, stream, lo, hi):
         check(self.L, self.L.pebblegpu_streambank_set_bandpass(self.h, stream, float(lo), float(hi)))
 
+    def set_spectrum_updates(self, updates_per_sec):
+        """SignalSpectrum::setUpdatesPerSec on the bank's sample clock: -1 every frame (default), 0 none, else spectra per second"""
+        check(self.L, self.L.pebblegpu_streambank_set_spectrum_updates(self.h, int(updates_per_sec)))
+
+    def spectrum_frames(self):
+        """-> uint32 [n]: which frames of the last call (relative to its first) the rows of spectrum() belong to"""
+        f = C.c_uint64()
+        self.L.pebblegpu_streambank_spectrum(self.h, C.byref(f), None)
+        idx = np.zeros(max(1, int(f.value)), dtype=np.uint32)
+        n = C.c_uint32()
+        check(self.L, self.L.pebblegpu_streambank_spectrum_frames(self.h, idx.ctypes.data_as(C.POINTER(C.c_uint32)), len(idx), C.byref(n)))
+        return idx[: n.value].copy()
+
     def process_device(self, dptr, n_samples, what=3):
         check(self.L, self.L.pebblegpu_streambank_process(self.h, C.c_void_p(dptr), int(n_samples), int(what)))
 
@@ -868,7 +884,8 @@ class StreamBank:
         check(self.L, self.L.pebblegpu_streambank_map_spectrum(self.h, C.byref(m), int(first_frame), int(n_frames), int(frame_step), C.c_void_p(d_out)))
 
     def map_spectrum(self, y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq, first_frame=None, n_frames=None, frame_step=1):
-        """FFT::mapFFTToScreen on the device -> int32 [streams, n_frames, x_pixels] (default: the last frame of each stream)"""
+        """FFT::mapFFTToScreen on the device -> int32 [streams, n_frames, x_pixels] (default: the last frame of each stream; under an
+        update gate the frames are the compact rows, and after a call that selected none the latest row made before it is frame 0)"""
         f, b = C.c_uint64(), C.c_uint32()
         self.L.pebblegpu_streambank_spectrum(self.h, C.byref(f), C.byref(b))
         if first_frame is None and n_frames is None:
@@ -883,7 +900,8 @@ class StreamBank:
             buf.free()
 
     def process(self, iq, what=3):
-        """iq: complex [streams, n] -> (filtered [S, n] or None, spectrum [S, frames, bins] or None)"""
+        """iq: complex [streams, n] -> (filtered [S, n] or None, spectrum [S, frames, bins] or None); under an update gate
+        (set_spectrum_updates) frames counts the computed rows only, spectrum_frames() says which they are"""
         iq = np.atleast_2d(np.asarray(iq))
         assert iq.shape[0] == self.n_streams
         buf = DeviceBuffer.from_array(to_f32_iq(iq), self.device, self.L)

@@ -2330,8 +2330,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
 // The tables of k_spectrum_list_q128 for a plan whose own kernels use others (4096 and 8192 bins); synchronous, once, from the setter
 int SpectrumCore::init_list()
 {
-    if (big) return fail(PEBBLEGPU_E_UNSUPPORTED, "the 65536-point spectrum has no frame-list transform");
-    if (any || d_list_ftab) return 0;
+    if (big || any || d_list_ftab) return 0;  // (the 65536-point listed transform needs no table of its own)
     if (per_q) {  // k_spectrum_q128's own
         d_list_ftab = d_ftab;
         d_list_tw128 = d_tw128;
@@ -2350,11 +2349,71 @@ int SpectrumCore::init_list()
     if (int rc = make_twiddles_t128(&d_list_tw128)) return rc;
     return 0;
 }
+// The 65536-point transform of the listed frames: pass A reads the listed frames and leaves COMPACT rows in Y ([stream][n_sel][k1][n2],
+// k_big256_cols_list, kListMax frames per launch), pass B is run()'s k_big256_rows over those n_sel rows -- its chains take a row's
+// predecessor from the row in front or from the carried amplitudes, and the last row leaves its own there.  Y, the stream batches and
+// the chain length follow run()'s rules with n_sel in place of the call's frame count.  Under PEBBLEGPU_BIG_SPLIT32 these kernels run
+// all the same.
+int SpectrumCore::run_list_big(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw)
+{
+    if (raw && !raw_ready_big()) return fail(PEBBLEGPU_E_INVALID, "raw-format input reached a spectrum kernel that has no converting loads");
+    const long long per_stream = n_sel * kBigN;  // Y points per stream
+    const long long batch_mb = tun.big_batch_mb;
+    long long bs = batch_mb > 0 ? (batch_mb << 20) / (long long)sizeof(float2) / per_stream : (long long)S;  // streams per batch
+    bs = bs < 1 ? 1 : (bs > (long long)S ? (long long)S : bs);
+    const size_t need = (size_t)bs * (size_t)per_stream;
+    if (need > y_cap) {
+        PG_HIP(hipStreamSynchronize(s));
+        if (d_Y) (void)hipFree(d_Y);
+        d_Y = nullptr;
+        y_cap = 0;
+        PG_HIP(hipMalloc((void **)&d_Y, sizeof(float2) * need));
+        y_cap = need;
+    }
+    long long G = (n_sel * bs * 8) / 512;
+    G = G < 1 ? 1 : (G > 16 ? 16 : G);
+    SpectrumParams sp;
+    sp.in_pitch = in_pitch;
+    sp.n_frames = n_sel;
+    sp.frames_per_group = (int)G;
+    sp.scale = scale;
+    sp.out_pitch = n_sel * (long long)bins;
+    const bool b8 = raw && (raw->fmt == 0 || raw->fmt == 1);  // 8-bit pairs: the paired tile order (kernels_spectrum.h)
+    for (long long s0 = 0; s0 < (long long)S; s0 += bs) {
+        const unsigned nb = (unsigned)((long long)S - s0 < bs ? (long long)S - s0 : bs);
+        RawSrc rs = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
+        if (raw) rs.base = static_cast<const char *>(raw->base) + (size_t)(s0 * in_pitch) * kRawPairBytes[raw->fmt];
+        const float2 *in0 = raw ? nullptr : d_in + s0 * in_pitch;
+        for (long long r0 = 0; r0 < n_sel; r0 += kListMax) {
+            FrameList fl;
+            memset(&fl, 0, sizeof(fl));
+            fl.n = (int)(n_sel - r0 < kListMax ? n_sel - r0 : kListMax);
+            fl.row0 = (int)r0;
+            fl.pred = -1;  // (pass B finds the predecessors)
+            for (int i = 0; i < fl.n; i++) fl.idx[i] = idx[r0 + i];
+            const dim3 grid(b8 ? (unsigned)(16 * cdiv(fl.n, 2)) : (unsigned)(fl.n * 8), nb);
+            auto go = [&](auto kern) { launch(kern, grid, dim3(256), s, in0, (long long)in_pitch, d_Y, (const float *)d_window, (long long)n_sel, fl, rs); };
+            switch (raw ? raw->fmt : -1) {
+            case -1: go(k_big256_cols_list<-1>); break;
+            case 0: go(k_big256_cols_list<0>); break;
+            case 1: go(k_big256_cols_list<1>); break;
+            case 2: go(k_big256_cols_list<2>); break;
+            case 3: go(k_big256_cols_list<3>); break;
+            default: go(k_big256_cols_list<4>); break;
+            }
+        }
+        launch(k_big256_rows, dim3((unsigned)(cdiv(n_sel, G) * 8), nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch,
+               (const float *)d_prev[parity] + s0 * kBigN, d_prev[parity ^ 1] + s0 * kBigN, sp);
+    }
+    parity ^= 1;
+    PG_HIP(hipGetLastError());
+    return 0;
+}
 // FFT::fftSpectrum of the listed frames only (ascending, relative to d_in's first frame), rows compact in d_out: [stream][n_sel][bins]
 int SpectrumCore::run_list(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw)
 {
     if (n_sel <= 0) return 0;  // nothing is queued and the carried amplitudes stay
-    if (big) return fail(PEBBLEGPU_E_UNSUPPORTED, "the 65536-point spectrum has no frame-list transform");
+    if (big) return run_list_big(s, d_in, in_pitch, idx, n_sel, d_out, raw);
     if (any && raw) return fail(PEBBLEGPU_E_INVALID, "the general display transform takes float2 input");
     if (!any && !d_list_ftab) return fail(PEBBLEGPU_E_INVALID, "the frame-list transform was not set up");
     SpectrumParams sp;

@@ -1062,9 +1062,23 @@ constexpr int kBig256 = 256;
 // blockIdx.x & 7 the workgroup that wants the other half sits on another XCD, behind another L2: both would fetch the whole line.  So
 // the 8-bit instances deal the tiles differently -- grid (8 * 2 * ceil(frames / 2), S): an XCD takes ONE pair of tiles (one run of
 // lines) of every second frame, the two halves in consecutive workgroups of that XCD, and the second finds the line in its L2.
-template <int FMT>
+//
+// `rows` says which frame of the call's input workgroup-frame f READS and which row of Y (of rows.n per stream) it WRITES: one and the
+// same for the every-frame kernels (BigRowsAll), a listed frame and its compact row for k_big256_cols_list below (BigRowsList).
+struct BigRowsAll {
+    long long n;
+    __device__ __forceinline__ long long src(long long f) const { return f; }
+    __device__ __forceinline__ long long dst(long long f) const { return f; }
+};
+struct BigRowsList {
+    const FrameList &fl;
+    long long n;
+    __device__ __forceinline__ long long src(long long i) const { return (long long)fl.idx[i]; }
+    __device__ __forceinline__ long long dst(long long i) const { return fl.row0 + i; }
+};
+template <int FMT, class ROWS>
 __device__ __forceinline__ void big256_cols_body(const float2 *__restrict__ in, long long in_pitch, float2 *__restrict__ Y,
-                                                 const float *__restrict__ window, long long n_frames, const RawSrc &raw)
+                                                 const float *__restrict__ window, long long n_frames, const RawSrc &raw, const ROWS &rows)
 {
     __shared__ float2 T[256 * 32];   // [cc * 16 + b][column]
     __shared__ float2 tw[256];       // W_256^m
@@ -1084,7 +1098,7 @@ __device__ __forceinline__ void big256_cols_body(const float2 *__restrict__ in, 
     }
     const int n2 = (tile << 5) + c;
     tw[t] = cis_cycles(-(double)t / 256.0);
-    const long long x0 = (long long)s * in_pitch + f * kBigN + n2;
+    const long long x0 = (long long)s * in_pitch + rows.src(f) * kBigN + n2;
     const float2 *x = FMT >= 0 ? nullptr : in + x0;  // (the raw instances have no float2 input)
     const float *w = window + n2;
     float2 u[2][16];
@@ -1110,7 +1124,7 @@ __device__ __forceinline__ void big256_cols_body(const float2 *__restrict__ in, 
     __syncthreads();
     // W_N^{n2 k1}, k1 = cc + 16 d: exact phasors for cc = j, j + 8 and for 16, then a power series over d
     const float2 w16 = cis_cycles(-(double)(16 * n2) / (double)kBigN);
-    float2 *y = Y + ((long long)s * n_frames + f) * kBigN + n2;
+    float2 *y = Y + ((long long)s * rows.n + rows.dst(f)) * kBigN + n2;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const int cc = j + 8 * h;
@@ -1129,13 +1143,24 @@ __device__ __forceinline__ void big256_cols_body(const float2 *__restrict__ in, 
 static __global__ __launch_bounds__(256, 2) void k_big256_cols(const float2 *__restrict__ in, long long in_pitch, float2 *__restrict__ Y,
                                                                const float *__restrict__ window, long long n_frames)
 {
-    big256_cols_body<-1>(in, in_pitch, Y, window, n_frames, RawSrc{nullptr, 0, 0, 0.f, 0});
+    big256_cols_body<-1>(in, in_pitch, Y, window, n_frames, RawSrc{nullptr, 0, 0, 0.f, 0}, BigRowsAll{n_frames});
 }
 template <int FMT>
 static __global__ __launch_bounds__(256, 2) void k_big256_cols_raw(long long in_pitch, float2 *__restrict__ Y, const float *__restrict__ window,
                                                                    long long n_frames, RawSrc raw)
 {
-    big256_cols_body<FMT>(nullptr, in_pitch, Y, window, n_frames, raw);
+    big256_cols_body<FMT>(nullptr, in_pitch, Y, window, n_frames, raw, BigRowsAll{n_frames});
+}
+// Pass A over a frame LIST (the stream bank's update gate; FrameList, "The display transform over a frame LIST" below): workgroups are
+// dealt over the launch's fl.n listed frames exactly as k_big256_cols / _raw deal them over a call's frames -- grid (fl.n * 8, S), or
+// (8 * 2 * ceil(fl.n / 2), S) for the 8-bit formats, whose paired tile order then runs over COMPACT rows: the two tiles of one source
+// frame in consecutive workgroups of one XCD.  Listed frame i is read at frame fl.idx[i] of the call's input and written to compact
+// row fl.row0 + i of Y, [stream][n_rows][k1][n2]; pass B is k_big256_rows on that Y with n_frames = n_rows.  FMT -1: float2 input.
+template <int FMT>
+static __global__ __launch_bounds__(256, 2) void k_big256_cols_list(const float2 *__restrict__ in, long long in_pitch, float2 *__restrict__ Y,
+                                                                    const float *__restrict__ window, long long n_rows, FrameList fl, RawSrc raw)
+{
+    big256_cols_body<FMT>(in, in_pitch, Y, window, (long long)fl.n, raw, BigRowsList{fl, n_rows});
 }
 
 // grid (ceil(n_frames / G) * 8, S), block 256: rows k1 = 32 (blockIdx.x & 7) + 16 pass + (t >> 4), sixteen work-items per row

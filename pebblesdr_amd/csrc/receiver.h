@@ -562,6 +562,7 @@ struct SpectrumCore {
     bool list_owned = false;
     int init_list();
     int run_list(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw = nullptr);
+    int run_list_big(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw);  // 65536 points
     bool dec_ready() const { return !big && !per_q && bins == 8192 && !use_w64; }  // k_spectrum_t128<.., DEC> exists for this plan
     bool raw_ready() const { return !big && !any && !per_q && bins == 8192; }  // k_spectrum_t128 converts in its loads (2048-sample frames only)
     bool raw_ready_big() const { return big && !tun.big_split32; }      // k_big256_cols_raw converts in its loads (the stream bank's raw calls)

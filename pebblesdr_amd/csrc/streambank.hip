@@ -1,5 +1,6 @@
 // streambank.hip -- S full-rate streams through CFastFIR + fftSpectrum (include/pebblegpu.h, "Stream bank").
 #include <new>
+#include <cmath>
 #include "receiver.h"
 
 using pg::fail;
@@ -20,6 +21,14 @@ struct pebblegpu_streambank {
     pg::IngestRing ingest;           // the pinned double buffer of pebblegpu_streambank_ingest_* (ingest.h)
     int last_fmt = -1;               // the last call's route, for pebblegpu_streambank_kernel_name: -1 float2 input, else the raw format
     bool last_staged = false, last_bp = false, last_sp = false;
+    // the spectrum's update gate (pebblegpu_streambank_set_spectrum_updates): one timer on the bank's sample clock, all streams select
+    // the same frames.  With a gate last_frames counts the COMPUTED rows of the last call, d_spec holds them compact.
+    int ups = -1;
+    uint64_t period_ms = 100;        // 1000 / updates_per_sec of the last rate above 0 (the reference's default: 10 per second)
+    pg::UpdateTimer ut;
+    std::vector<uint32_t> sel;       // the last call's selection, relative to its first frame
+    bool last_listed = false;        // the last call's transform went through the frame-list kernels (or, sel empty, through none)
+    uint64_t spec_rows = 0;          // rows per stream of what d_spec holds (the last call that computed any): its last row is the latest spectrum
 };
 
 // every kernel a raw call would run converts in its own loads (else the call is staged through k_normalize_iq as a whole)
@@ -102,6 +111,28 @@ int pebblegpu_streambank_set_bandpass(pebblegpu_streambank *sb, uint32_t stream,
     return 0;
 }
 
+int pebblegpu_streambank_set_spectrum_updates(pebblegpu_streambank *sb, int updates_per_sec)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (updates_per_sec < -1) return fail(PEBBLEGPU_E_INVALID, "updates per second: -1 (every frame), 0 (none) or a rate");
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    if (updates_per_sec != -1) { if (int rc = sb->sp.init_list()) return rc; }
+    if (updates_per_sec > 0) sb->period_ms = (uint64_t)(1000 / updates_per_sec);  // integer division, as the reference computes it
+    sb->ups = updates_per_sec;
+    return 0;
+}
+int pebblegpu_streambank_spectrum_frames(const pebblegpu_streambank *sb, uint32_t *idx, uint32_t cap, uint32_t *n)
+{
+    if (!sb || !n) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    *n = 0;
+    const uint64_t rows = sb->last_frames;
+    if (rows > cap) return fail(PEBBLEGPU_E_SIZE, "%llu frames do not fit %u entries", (unsigned long long)rows, cap);
+    if (rows && !idx) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    for (uint64_t i = 0; i < rows; i++) idx[i] = sb->last_listed ? sb->sel[i] : (uint32_t)i;  // (without the gate every frame of the call has its row)
+    *n = (uint32_t)rows;
+    return 0;
+}
+
 // the checks every process call makes before anything is queued
 static int sb_check_n(const pebblegpu_streambank *sb, uint64_t n)
 {
@@ -115,6 +146,13 @@ static int sb_run(pebblegpu_streambank *sb, const float2 *in, const pg::RawSrc *
     sb->last_n = 0;
     sb->last_frames = 0;
     if (n == 0) return 0;
+    // The update timer, on the host before anything is queued.  A call without the spectrum advances the sample clock and nothing else:
+    // it selects no frame and neither starts nor restarts the timer.
+    const uint64_t F = n / sb->cfg.frame;
+    sb->sel.clear();
+    sb->last_listed = (what & 2u) && sb->ups != -1;
+    if (what & 2u) sb->ut.advance(sb->ups, sb->period_ms, F, sb->cfg.frame, (uint64_t)std::llround(sb->cfg.sample_rate), &sb->sel);
+    else sb->ut.next += F;
     PG_HIP(hipEventRecord(sb->ev[0], sb->stream));
     // Both asked for: the band-pass (bound by its two transforms per block: vector units + LDS) and the display transform (the 65536-point
     // one is bound by what it moves through HBM) read the same input and share nothing else.  Side by side on two streams (fork at the
@@ -135,11 +173,14 @@ static int sb_run(pebblegpu_streambank *sb, const float2 *in, const pg::RawSrc *
         sb->last_n = n;
     }
     PG_HIP(hipEventRecord(sb->ev[1], fs));
-    if (what & 2u) {
-        const long long F = (long long)(n / sb->cfg.frame);
-        if (int rc = sb->sp.run(sb->stream, in, (long long)n, F, sb->d_spec, raw, nullptr, !side)) return rc;
-        sb->last_frames = (uint64_t)F;
+    if (sb->last_listed) {  // the listed frames only, rows compact (an empty list queues nothing and leaves d_spec and the carried amplitudes alone)
+        if (int rc = sb->sp.run_list(sb->stream, in, (long long)n, sb->sel.data(), (long long)sb->sel.size(), sb->d_spec, raw)) return rc;
+        sb->last_frames = sb->sel.size();
+    } else if (what & 2u) {
+        if (int rc = sb->sp.run(sb->stream, in, (long long)n, (long long)F, sb->d_spec, raw, nullptr, !side)) return rc;
+        sb->last_frames = F;
     }
+    if (sb->last_frames) sb->spec_rows = sb->last_frames;
     if (side) {
         PG_HIP(hipEventRecord(sb->ev[3], sb->stream));       // where the transform ended
         PG_HIP(hipStreamWaitEvent(sb->stream, sb->ev[1], 0));  // join
@@ -234,6 +275,17 @@ const char *pebblegpu_streambank_kernel_name(const pebblegpu_streambank *sb, int
         if (sb->ff.fft_n == 2048) return sb->last_staged ? "k_normalize_iq + k_fastfir_t128" : kFf[r];
         return sb->last_staged ? "k_normalize_iq + k_fastfir" : "k_fastfir";
     }
+    if (which == 2 && sb->last_sp && sb->last_listed) {  // a gated call: the frame-list kernels, or none
+        static const char *const kBigL[6] = {"k_big256_cols_list + k_big256_rows", "k_big256_cols_list (raw s8) + k_big256_rows",
+                                             "k_big256_cols_list (raw u8) + k_big256_rows", "k_big256_cols_list (raw s16) + k_big256_rows",
+                                             "k_big256_cols_list (raw f32) + k_big256_rows", "k_big256_cols_list (raw wav16) + k_big256_rows"};
+        static const char *const kQ128L[6] = {"k_spectrum_list_q128", "k_spectrum_list_q128 (raw s8)", "k_spectrum_list_q128 (raw u8)",
+                                              "k_spectrum_list_q128 (raw s16)", "k_spectrum_list_q128 (raw f32)", "k_spectrum_list_q128 (raw wav16)"};
+        if (!sb->last_frames) return "";
+        if (sp.big) return sb->last_staged ? "k_normalize_iq + k_big256_cols_list + k_big256_rows" : kBigL[r];
+        if (sp.any) return sb->last_staged ? "k_normalize_iq + k_spectrum_list_any" : "k_spectrum_list_any";
+        return sb->last_staged ? "k_normalize_iq + k_spectrum_list_q128" : kQ128L[r];
+    }
     if (which == 2) {
         if (!sb->last_sp) return "";
         if (sp.big && sp.tun.big_split32) return sb->last_staged ? "k_normalize_iq + k_big_cols + k_big_rows" : "k_big_cols + k_big_rows";
@@ -279,15 +331,20 @@ int pebblegpu_streambank_map_spectrum(pebblegpu_streambank *sb, const pebblegpu_
     if (!sb || !map || !d_out) return fail(PEBBLEGPU_E_INVALID, "null argument");
     if (map->struct_size != sizeof(pebblegpu_screen_map)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_screen_map size mismatch");
     if (int rc = pg::check_screen_map(map->y_pixels, map->x_pixels, map->max_db, map->min_db)) return rc;
-    if (!sb->last_frames) return fail(PEBBLEGPU_E_INVALID, "the last call computed no spectrum (or no call has been made yet)");
-    if (n_frames == 0 || (uint64_t)first_frame + (uint64_t)(n_frames - 1) * frame_step >= sb->last_frames)
+    // a gated call that asked for the spectrum and selected nothing left d_spec alone: the latest row computed before it (the last of
+    // the spec_rows it holds) is mapped as frame 0 -- what the display still shows
+    const bool latest = !sb->last_frames && sb->last_sp && sb->last_listed && sb->spec_rows;
+    const uint64_t rows = latest ? 1 : sb->last_frames, pitch_rows = latest ? sb->spec_rows : sb->last_frames;
+    if (!rows) return fail(PEBBLEGPU_E_INVALID, "the last call computed no spectrum (or no call has been made yet)");
+    if (n_frames == 0 || (uint64_t)first_frame + (uint64_t)(n_frames - 1) * frame_step >= rows)
         return fail(PEBBLEGPU_E_INVALID, "frames %u + j * %u, j < %u, are not all within the last call's %llu", first_frame, frame_step, n_frames,
-                    (unsigned long long)sb->last_frames);
+                    (unsigned long long)rows);
     PG_HIP(hipSetDevice(sb->cfg.device));
     const long long bins = sb->sp.bins;
     const int32_t edges[2] = {map->start_freq, map->stop_freq};
+    if (latest) first_frame = (uint32_t)(sb->spec_rows - 1);
     // on the bank's stream, behind the call's transform (and its join) and ahead of the next call's
-    return pg::run_screen_map(sb->stream, sb->d_spec + (long long)first_frame * bins, (long long)sb->last_frames * bins, (long long)frame_step * bins,
+    return pg::run_screen_map(sb->stream, sb->d_spec + (long long)first_frame * bins, (long long)pitch_rows * bins, (long long)frame_step * bins,
                               (int)sb->cfg.n_streams, (int)n_frames, (int32_t)bins, sb->cfg.sample_rate, edges, false, map->y_pixels, map->x_pixels,
                               map->max_db, map->min_db, d_out);
 }
