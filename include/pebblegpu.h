@@ -411,6 +411,53 @@ int pebblegpu_set_testbench_sweep(pebblegpu_receiver *rx, const pebblegpu_sweep 
  * attempt, which of the two): splitmix64's finaliser, see DESIGN.md section 4 and tests/testbench_ref.py.  At most 32 attempts per
  * sample; a sample whose 32 attempts all fail (4e-22) gets no noise.  Streams of one receiver get different noise. */
 int pebblegpu_set_testbench_noise(pebblegpu_receiver *rx, double amplitude, uint64_t seed);
+/* Keyed Morse stations: the reference's plugins/MorseGenDevice, a bank of MorseGen objects (morsegen.cpp:33-328) summed at the head of
+ * the chain (morsegendevice.cpp:1008-1063), here in the test bench's generator pass.  A station sends its tokens over and over: a token
+ * is MorseCode's (a leading 1, then 1 per dash and 0 per dot, below 0x200: genToken shifts nine bits, morsegen.cpp:244), 0 is a word
+ * space (' ', genText :226).  The application keeps MorseCode::asciiLookup, as it keeps tokenLookup on the decoder's side.
+ * With msTcw = 1200 / wpm (integer, MorseCode::wpmToTcwMs), samplesPerTcw = (quint32)(msTcw / (1000.0 / fs)) and rise = fall =
+ * (quint32)(ms_rise / (1000 / fs)) (morsegen.cpp:45-58), a dot is rise + (samplesPerTcw - rise) + fall samples and a dash
+ * rise + (3 samplesPerTcw - rise) + fall (:59-67).  Inside a mark the carrier starts at phase 0 at the mark's first sample and advances
+ * by 2 pi f / fs per sample (:90-142: it restarts at every dot and dash); the envelope rises as ampInc (i + 1) over the rise samples
+ * (ampInc = amplitude / rise), holds at amplitude, and falls as amplitude - ampInc (i + 1), so that the last fall sample is 0.
+ * samplesPerTcw zeros come between two marks of one character only (genDot / genDash :272-275), 3 samplesPerTcw zeros behind every
+ * token (genChar), 7 samplesPerTcw - 3 zeros for a word space (the reference's "- 3" is in samples, :84) in addition to the character
+ * space before it; the text starts over from its first token with nothing in between (nextOutputSample :204-207).
+ * The library evaluates phase and ramps in closed form (phase in turns, reduced exactly; a lane makes a short run of samples from one
+ * sincos and rotations in double): they differ from the reference's serial sums by those sums' own rounding.  DESIGN.md section 4.
+ * Not built: the per-sample random fade (morsegendevice.cpp:1016-1021, libc's unseeded rand()), presets and the UI. */
+#define PEBBLEGPU_MORSE_MAX_STATIONS 256    /* stations a receiver or a generator takes at most */
+typedef struct pebblegpu_morse_station {    /* MorseGen::setParams + setTextOut (morsegen.cpp:33, 163) */
+    uint32_t struct_size;                   /* = sizeof(pebblegpu_morse_station) */
+    uint32_t wpm;
+    uint32_t ms_rise;                       /* m_msRiseFall; 0: hard keying */
+    uint32_t n_tokens;
+    double   frequency_hz, amplitude;       /* amplitude linear: DB::dBToAmplitude(dbAmplitude), morsegen.cpp:40 */
+    const uint16_t *tokens;                 /* n_tokens of them; copied by the setter */
+    uint32_t reserved[2];
+} pebblegpu_morse_station;
+/* What the library makes of a station, on the host, no device needed: the lengths above in samples (dot_samples / dash_samples: the
+ * whole mark buffers, rise and fall included) and period_samples, one pass through the text.  PEBBLEGPU_E_INVALID: a null or mis-sized
+ * struct, non-finite values, |frequency| >= fs / 2, n_tokens == 0, a token of 0x200 or more.  PEBBLEGPU_E_UNSUPPORTED: wpm 0, msTcw or
+ * samplesPerTcw 0, samplesPerTcw <= rise (a dot of less than one sample at full level: the reference's unsigned subtraction wraps), a
+ * mark of 2^26 samples or more, a period of 2^40 samples or more.  Any of the output pointers may be NULL. */
+int pebblegpu_morse_station_plan(double sample_rate, const pebblegpu_morse_station *st, uint64_t *samples_per_tcw, uint64_t *rise_samples,
+                                 uint64_t *dot_samples, uint64_t *dash_samples, uint64_t *period_samples);
+/* For parity checks, on the host, no device needed: the mark table the library builds for a call of n samples that begins first_sample
+ * samples after the station was set -- for every mark that intersects the call, (start relative to the call's first sample) * 2 +
+ * (1: dash), ascending; a mark that began before the call has a negative start.  *n_marks: how many there are (PEBBLEGPU_E_SIZE when
+ * more than cap; more than 2^22 in one call: PEBBLEGPU_E_UNSUPPORTED, as the generating call itself). */
+int pebblegpu_morse_station_marks(double sample_rate, const pebblegpu_morse_station *st, uint64_t first_sample, uint64_t n, int64_t *marks,
+                                  uint32_t cap, uint32_t *n_marks);
+/* Replaces the receiver's whole set of stations (n_stations == 0: off; more than PEBBLEGPU_MORSE_MAX_STATIONS: PEBBLEGPU_E_INVALID) and
+ * starts every station at its first token with the next sample.  It does not restart the sweep or the noise counter, and the two setters
+ * above do not restart the stations.  mix = 1 adds the stations to the input; mix = 0: the caller's input is not read.  With the sweep
+ * on as well the input is dropped when either says "replace"; sweep, stations and noise are summed in double and rounded to float once.
+ * The stations are the same on every stream of a receiver with independent streams (their sum is formed once per sample position).  A
+ * call with stations on is staged exactly as a call with the sweep on (see pebblegpu_set_testbench_sweep);
+ * pebblegpu_receiver_kernel_name(rx, 2) then starts with "k_morsegen + " (the kernel that also makes the call's sweep and noise).  A
+ * refused call leaves the set as it was. */
+int pebblegpu_set_testbench_morse(pebblegpu_receiver *rx, const pebblegpu_morse_station *stations, uint32_t n_stations, int mix);
 /* Taps: the float2 signal of the whole call at a point of the chain, copied into a library-owned buffer (allocated when the point is
  * first enabled) by a copy queued on the call's stream at that point.  Valid after pebblegpu_receiver_synchronize until the next call.
  *   RAW_IQ      [stream][n_samples] at the stream rate: the streams after the generator, before the conditioners (receiver.cpp:803)
@@ -657,6 +704,8 @@ int pebblegpu_siggen_destroy(pebblegpu_siggen *g);
 /* as pebblegpu_set_testbench_sweep / _noise: each call is TestBench::reset() */
 int pebblegpu_siggen_set_sweep(pebblegpu_siggen *g, const pebblegpu_sweep *s);
 int pebblegpu_siggen_set_noise(pebblegpu_siggen *g, double amplitude, uint64_t seed);
+/* as pebblegpu_set_testbench_morse: replaces the set and restarts the stations only; generate then makes sweep + stations + noise */
+int pebblegpu_siggen_set_morse(pebblegpu_siggen *g, const pebblegpu_morse_station *stations, uint32_t n_stations, int mix);
 /* which stream of a receiver's noise this generator makes (default 0); does not reset */
 int pebblegpu_siggen_set_stream(pebblegpu_siggen *g, uint32_t stream);
 /* the next n samples into d_iq (device float2, in place: mixed with what is there, or replacing it); queues and returns */

@@ -19,12 +19,14 @@
 //   void Receiver::processIQData(CPX*, quint16) application/receiver.cpp:758    Receiver::processIQData
 //   CB_ProcessIQData / CB_ProcessAudioData      pebblelib/device_interfaces.h:32,38   same std::function shapes
 //   void TestBench::genSweep(int, CPX*) / genNoise(int, CPX*)   application/testbench.h; NCO::initSweep pebblelib/nco.h:52-57   TestBench
+//   void MorseGen::setParams(double, double, quint32, quint32) / setTextOut / nextOutputSample   plugins/MorseGenDevice/morsegen.h   MorseGen
 //   FileSDRDevice (initialize / Cmd_Start pump) plugins/FileSDRDevice/filesdrdevice.cpp:24-33,226-289   FileSdrFeeder
 //
 // Error behaviour follows the reference: no exceptions across step calls; a failing call logs to stderr (the
 // reference uses qDebug) and returns the input pointer / zero count; lastStatus() exposes the C status code.
 #ifndef PEBBLEGPU_STEPS_HPP
 #define PEBBLEGPU_STEPS_HPP
+#include <cmath>
 #include <complex>
 #include <cstdint>
 #include <cstdio>
@@ -434,6 +436,60 @@ private:
     int status = 0;
 };
 
+// The reference's Morse sender (plugins/MorseGenDevice/morsegen.h) over the library's generator: one station per object.  setParams has
+// the reference's signature (dbAmplitude in dB: m_amplitude = 10^(dB/20), morsegen.cpp:40); the text is handed over as MorseCode tokens
+// (the application keeps MorseCode::asciiLookup; 0 stands for ' '); generate() ADDS the next n samples to out -- the reference's
+// per-sample loop "out[i] = ... + m_morseGenN->nextOutputSample()" (morsegendevice.cpp:1013-1061) as one call per station.  As with the
+// reference, setParams and setTextOut each start the text over.  Results are float-rounded (the library's kernels work on float2).
+class MorseGen {
+public:
+    explicit MorseGen(double sampleRate, int device = 0)
+    {
+        status = report("siggen_create", pebblegpu_siggen_create(device, sampleRate, 2048, &gen));
+        std::memset(&st, 0, sizeof(st));
+        st.struct_size = sizeof(st);
+    }
+    ~MorseGen() { pebblegpu_siggen_destroy(gen); }
+    MorseGen(const MorseGen &) = delete;
+    MorseGen &operator=(const MorseGen &) = delete;
+    void setParams(double frequency, double dbAmplitude, uint32_t wpm, uint32_t msRise)  // morsegen.cpp:33-160
+    {
+        st.frequency_hz = frequency;
+        st.amplitude = std::pow(10.0, dbAmplitude / 20.0);  // DB::dBToAmplitude
+        st.wpm = wpm;
+        st.ms_rise = msRise;
+        apply();
+    }
+    void setTextOut(const std::vector<uint16_t> &tokensOut)  // morsegen.cpp:163-180
+    {
+        tokens = tokensOut;
+        apply();
+    }
+    bool hasOutputSamples() const { return !tokens.empty(); }  // the text repeats: always, once there is one
+    void generate(CPX *out, uint32_t n)
+    {
+        if (gen && on && n > 0) status = report("siggen_generate", pebblegpu_siggen_generate(gen, reinterpret_cast<double *>(out), n));
+    }
+    int lastStatus() const { return status; }
+
+private:
+    void apply()
+    {
+        if (!gen) return;
+        on = false;
+        if (tokens.empty() || st.wpm == 0) { status = report("siggen_set_morse", pebblegpu_siggen_set_morse(gen, nullptr, 0, 1)); return; }  // nothing to send yet
+        st.tokens = tokens.data();
+        st.n_tokens = (uint32_t)tokens.size();
+        status = report("siggen_set_morse", pebblegpu_siggen_set_morse(gen, &st, 1, 1));
+        on = status == 0;
+    }
+    pebblegpu_siggen *gen = nullptr;
+    pebblegpu_morse_station st;
+    std::vector<uint16_t> tokens;
+    bool on = false;
+    int status = 0;
+};
+
 // The slice of application/receiver.cpp this library replaces: turnPowerOn's step construction and
 // processIQData's DSP for one tuned channel, audio delivered through the CB_ProcessAudioData-shaped callback.
 class Receiver {
@@ -502,6 +558,12 @@ public:
     typedef std::function<void(int, CPX *, double, int)> CB_DisplayData;
     void setTestBenchSweep(const pebblegpu_sweep *s) { if (h) status = report("set_testbench_sweep", pebblegpu_set_testbench_sweep(h, s)); if (status == 0) tbSweep = s != nullptr; }
     void setTestBenchNoise(double amplitude, uint64_t seed) { if (h) status = report("set_testbench_noise", pebblegpu_set_testbench_noise(h, amplitude, seed)); if (status == 0) tbNoise = amplitude > 0; }
+    // MorseGen stations summed into the input on the device (pebblegpu_set_testbench_morse): n == 0 switches them off
+    void setMorseStations(const pebblegpu_morse_station *stations, uint32_t n, bool mix = true)
+    {
+        if (h) status = report("set_testbench_morse", pebblegpu_set_testbench_morse(h, stations, n, mix ? 1 : 0));
+        if (status == 0) tbMorse = n > 0;
+    }
     void setTaps(uint32_t mask, CB_DisplayData displayData)
     {
         if (h) status = report("receiver_set_taps", pebblegpu_receiver_set_taps(h, mask));
@@ -511,7 +573,7 @@ public:
     void processIQData(CPX *in, uint16_t numSamples)
     {
         if (!h) return;
-        if (tbSweep || tbNoise || tapMask) { processBatched(in, numSamples); return; }
+        if (tbSweep || tbNoise || tbMorse || tapMask) { processBatched(in, numSamples); return; }
         uint32_t na = 0;
         // (behind setUpdatesPerSec a frame the timer skips leaves `spectrum` as it is: the last computed one, as getUnprocessed() holds it)
         status = report("process_iq", pebblegpu_process_iq_updates(h, reinterpret_cast<const double *>(in), numSamples, reinterpret_cast<double *>(audio.data()), &na,
@@ -606,7 +668,7 @@ private:
     }
     pebblegpu_receiver *h = nullptr;
     uint16_t n;
-    bool tbSweep = false, tbNoise = false;
+    bool tbSweep = false, tbNoise = false, tbMorse = false;
     uint32_t tapMask = 0;
     CB_DisplayData display;
     uint64_t superframe = 0;

@@ -11,11 +11,12 @@ from .binding import (  # noqa: F401
     DM_AM, DM_SAM, DM_FMN, DM_FMM, DM_FMS, DM_DSB, DM_LSB, DM_USB, DM_CWL, DM_CWU, DM_DIGL, DM_DIGU, DM_NONE,
     SigGen, Sweep, sweep, sweep_plan, SWEEP_SINGLE, SWEEP_REPEAT, SWEEP_REPEAT_REVERSE,
     TAP_RAW_IQ, TAP_POST_MIXER, TAP_POST_BP, TAP_POST_DEMOD, TAP_MODEM,
+    MorseStation, morse_station, morse_station_plan, morse_station_marks, MORSE_MAX_STATIONS,
 )
 from .steps import Mixer, Decimator, DownConvert, FastFIR, Demod, Spectrum, Morse  # noqa: F401
 
 __all__ = [
     "PebbleGpuError", "load_library", "library_path", "ReceiverBank", "StreamBank", "DeviceBuffer", "ScreenMap", "screen_map",
     "Mixer", "Decimator", "DownConvert", "FastFIR", "Demod", "Spectrum", "Morse", "morse_token_to_dotdash",
-    "SigGen", "Sweep", "sweep", "sweep_plan",
+    "SigGen", "Sweep", "sweep", "sweep_plan", "MorseStation", "morse_station", "morse_station_plan",
 ]

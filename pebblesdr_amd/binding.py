@@ -44,6 +44,7 @@ SYMBOLS = [
     "pebblegpu_sweep_plan", "pebblegpu_set_testbench_sweep", "pebblegpu_set_testbench_noise", "pebblegpu_receiver_set_taps", "pebblegpu_receiver_tap",
     "pebblegpu_siggen_create", "pebblegpu_siggen_destroy", "pebblegpu_siggen_set_sweep", "pebblegpu_siggen_set_noise", "pebblegpu_siggen_set_stream",
     "pebblegpu_siggen_generate_device", "pebblegpu_siggen_synchronize", "pebblegpu_siggen_generate", "pebblegpu_siggen_noise_draws",
+    "pebblegpu_morse_station_plan", "pebblegpu_morse_station_marks", "pebblegpu_set_testbench_morse", "pebblegpu_siggen_set_morse",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
@@ -119,6 +120,61 @@ def sweep_plan(sample_rate, s, lib=None):
     a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     check(L, L.pebblegpu_sweep_plan(float(sample_rate), C.byref(s), C.byref(a), C.byref(b), C.byref(c)))
     return int(a.value), int(b.value), int(c.value)
+
+
+MORSE_MAX_STATIONS = 256  # PEBBLEGPU_MORSE_MAX_STATIONS
+
+
+class MorseStation(C.Structure):
+    """pebblegpu_morse_station: MorseGen::setParams' arguments (amplitude linear) and the text as MorseCode tokens (0: a word space)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("wpm", C.c_uint32), ("ms_rise", C.c_uint32), ("n_tokens", C.c_uint32),
+        ("frequency_hz", C.c_double), ("amplitude", C.c_double), ("tokens", C.POINTER(C.c_uint16)), ("reserved", C.c_uint32 * 2),
+    ]
+
+
+def morse_station(frequency_hz, amplitude, wpm, ms_rise, tokens):
+    """tokens: MorseCode tokens (a leading 1, then 1 per dash and 0 per dot; 0: a word space).  The struct keeps its token array alive."""
+    st = MorseStation()
+    st.struct_size = C.sizeof(MorseStation)
+    st.wpm, st.ms_rise = int(wpm), int(ms_rise)
+    st.frequency_hz, st.amplitude = float(frequency_hz), float(amplitude)
+    toks = [int(t) for t in tokens]
+    st._tokens = (C.c_uint16 * max(1, len(toks)))(*toks)
+    st.tokens = C.cast(st._tokens, C.POINTER(C.c_uint16))
+    st.n_tokens = len(toks)
+    return st
+
+
+def _station_array(stations):
+    stations = list(stations or [])
+    arr = (MorseStation * max(1, len(stations)))()
+    for i, st in enumerate(stations):
+        C.memmove(C.byref(arr[i]), C.byref(st), C.sizeof(MorseStation))
+    return arr, len(stations), stations  # (the third keeps the token arrays alive over the call)
+
+
+def morse_station_plan(sample_rate, st, lib=None):
+    """what the library makes of a station, on the host (no device): (samples_per_tcw, rise_samples, dot_samples, dash_samples, period_samples)"""
+    L = lib or load_library()
+    v = [C.c_uint64() for _ in range(5)]
+    check(L, L.pebblegpu_morse_station_plan(float(sample_rate), C.byref(st), *[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
+def morse_station_marks(sample_rate, st, first_sample, n, lib=None):
+    """the library's mark table for a call of n samples that begins first_sample samples after the station was set, on the host:
+    [(start relative to the call's first sample, is_dash)]"""
+    L = lib or load_library()
+    cap, cnt = 4096, C.c_uint32()
+    while True:
+        buf = (C.c_int64 * cap)()
+        rc = L.pebblegpu_morse_station_marks(float(sample_rate), C.byref(st), int(first_sample), int(n), buf, cap, C.byref(cnt))
+        if rc == -5 and cnt.value > cap:  # PEBBLEGPU_E_SIZE
+            cap = cnt.value
+            continue
+        check(L, rc)
+        return [(int(v) >> 1, bool(int(v) & 1)) for v in buf[:cnt.value]]
 
 
 def _frame_range(frames, first_frame, n_frames, frame_step):
@@ -309,6 +365,11 @@ def _declare(L):
     L.pebblegpu_sweep_plan.argtypes = [dbl, swp, u64p, u64p, u64p]
     L.pebblegpu_set_testbench_sweep.argtypes = [vp, swp]
     L.pebblegpu_set_testbench_noise.argtypes = [vp, dbl, u64]
+    msp = C.POINTER(MorseStation)
+    L.pebblegpu_morse_station_plan.argtypes = [dbl, msp, u64p, u64p, u64p, u64p, u64p]
+    L.pebblegpu_morse_station_marks.argtypes = [dbl, msp, u64, u64, C.POINTER(C.c_int64), u32, C.POINTER(u32)]
+    L.pebblegpu_set_testbench_morse.argtypes = [vp, msp, u32, i32]
+    L.pebblegpu_siggen_set_morse.argtypes = [vp, msp, u32, i32]
     L.pebblegpu_receiver_set_taps.argtypes = [vp, u32]
     L.pebblegpu_receiver_tap.restype = vp
     L.pebblegpu_receiver_tap.argtypes = [vp, i32, u64p, u64p, dp]
@@ -503,6 +564,11 @@ class ReceiverBank:
     def set_testbench_sweep(self, s):
         """TestBench::reset + the sweep generator at the head of the chain; s: a Sweep (see sweep()), None switches it off"""
         check(self.L, self.L.pebblegpu_set_testbench_sweep(self.h, C.byref(s) if s is not None else None))
+
+    def set_testbench_morse(self, stations, mix=True):
+        """MorseGen stations at the head of the chain (see morse_station()); replaces the set and restarts it, None or [] switches it off"""
+        arr, n, _keep = _station_array(stations)
+        check(self.L, self.L.pebblegpu_set_testbench_morse(self.h, arr, n, 1 if mix else 0))
 
     def set_testbench_noise(self, amplitude, seed=0):
         """NCO::genNoise at the head of the chain, always mixed; amplitude <= 0 switches it off"""
@@ -749,6 +815,10 @@ class SigGen:
 
     def set_noise(self, amplitude, seed=0):
         check(self.L, self.L.pebblegpu_siggen_set_noise(self.h, float(amplitude), int(seed)))
+
+    def set_morse(self, stations, mix=True):
+        arr, n, _keep = _station_array(stations)
+        check(self.L, self.L.pebblegpu_siggen_set_morse(self.h, arr, n, 1 if mix else 0))
 
     def set_stream(self, stream):
         check(self.L, self.L.pebblegpu_siggen_set_stream(self.h, int(stream)))

@@ -78,7 +78,10 @@ __device__ __forceinline__ unsigned long long tb_uniform(unsigned long long v)  
 
 // one output sample: `in` + sweep + noise, formed in double and rounded to float once.  leg: a leg at or before the sample's (the wave's
 // first sample's leg); the sample's own is at most a few entries further (a wave spans 128 samples, a whole leg at least kTbMinLeg)
-__device__ __forceinline__ float2 tb_sample(const TbParams &p, const SweepLeg *__restrict__ legs, int leg, unsigned long long noise_key, long long k, float2 in)
+// kAdd (k_morsegen): `add`, the stations' sum at this sample, goes in between the sweep and the noise
+template <bool kAdd = false>
+__device__ __forceinline__ float2 tb_sample(const TbParams &p, const SweepLeg *__restrict__ legs, int leg, unsigned long long noise_key, long long k, float2 in,
+                                            double2 add = make_double2(0.0, 0.0))
 {
     double re = (double)in.x, im = (double)in.y;
     const unsigned long long n_abs = p.n0 + (unsigned long long)k;
@@ -99,6 +102,7 @@ __device__ __forceinline__ float2 tb_sample(const TbParams &p, const SweepLeg *_
         if (p.mix) { re += amp * c; im += amp * s; }
         else { re = amp * c; im = amp * s; }
     }
+    if (kAdd) { re += add.x; im += add.y; }
     if (p.noise_on) {
         unsigned r1, r2;
         int att;
@@ -135,6 +139,102 @@ static __global__ __launch_bounds__(256) void k_testbench(const float2 *in, floa
         for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += step) {
             const int leg = p.sweep_on ? tb_find_leg(legs, p.n_legs, tb_uniform((unsigned long long)(k - (threadIdx.x & 63)))) : 0;
             dst[k] = tb_sample(p, legs, leg, key, k, src ? src[k] : make_float2(0.f, 0.f));
+        }
+    }
+}
+
+// ---- keyed Morse stations (MorseGen, plugins/MorseGenDevice/morsegen.cpp) ----
+// the envelope at sample i of a mark of L samples (morsegen.cpp:95-117): ampInc (i + 1) over the rise, m_amplitude, then m_amplitude - ampInc (i + 1)
+// over the fall; 0 outside the mark
+__device__ __forceinline__ double morse_env(const MorseStationDev &h, long long L, long long i)
+{
+    if ((unsigned long long)i >= (unsigned long long)L) return 0.0;
+    const long long fall0 = L - (long long)h.rise;
+    return i < (long long)h.rise ? h.inc * (double)(i + 1) : i < fall0 ? h.amp : h.amp - h.inc * (double)(i - fall0 + 1);
+}
+
+// the stations' sum at the lane's kMorseRun consecutive samples a .. a + kMorseRun - 1 (call-relative).  [w0, w1) is the wave's stretch: the
+// station loop, the bisection and the marks it visits are wave-uniform (scalar loads); a station whose stretch lies wholly in a gap costs
+// the bisection and nothing else.  Inside a mark the lane takes the carrier at its first sample from one sincospi -- the phase in turns,
+// (a - start) * f / fs with the product's rounding error recovered by an fma, so the reduction is exact -- and the following ones by
+// rotating with exp(j 2 pi f / fs) in double (kMorseRun - 1 rotations: 1e-16 each).
+__device__ __forceinline__ void morse_sum(const MorseStationDev *__restrict__ st, const long long *__restrict__ marks, int n_st, long long w0, long long w1, long long a,
+                                          double2 (&acc)[kMorseRun])
+{
+    for (int i = 0; i < n_st; i++) {
+        const MorseStationDev h = st[i];
+        if (!h.count) continue;
+        const long long *__restrict__ m = marks + h.first;
+        // the last mark that starts at or before w0 (marks do not overlap: no earlier one reaches into the stretch), else the first
+        int lo = 0, hi = (int)h.count - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if ((m[mid] >> 1) <= w0) lo = mid;
+            else hi = mid - 1;
+        }
+        for (int j = lo; j < (int)h.count; j++) {
+            const long long enc = m[j], start = enc >> 1;
+            if (start >= w1) break;
+            const long long L = (enc & 1) ? (long long)h.dash : (long long)h.dot;
+            if (start + L <= w0) continue;
+            const long long i0 = a - start;  // (|i0| < 2^26 + 64 kMorseRun: exact in a double)
+            if (i0 + kMorseRun <= 0 || i0 >= L) continue;
+            const double x = (double)i0;
+            double t = x * h.tps;
+            const double t_lo = fma(x, h.tps, -t);
+            t = (t - rint(t)) + t_lo;
+            double s, c;
+            sincospi(2.0 * t, &s, &c);
+#pragma unroll
+            for (int r = 0; r < kMorseRun; r++) {
+                const double e = morse_env(h, L, i0 + r);
+                acc[r].x += e * c;
+                acc[r].y += e * s;
+                const double c1 = c * h.rot_c - s * h.rot_s;
+                s = c * h.rot_s + s * h.rot_c;
+                c = c1;
+            }
+        }
+    }
+}
+
+// k_testbench with stations: in + sweep + stations + noise in ONE pass over the streams.  A work-item makes kMorseRun neighbouring samples
+// per step, of every stream: the stations' sum is formed once per sample position and added to each stream.  grid (x); in == nullptr:
+// silence in; in may equal out; vec as k_testbench's (16-byte accesses, two samples each)
+static __global__ __launch_bounds__(256) void k_morsegen(const float2 *in, float2 *out, long long in_pitch, long long out_pitch, long long n, int streams, int vec,
+                                                         TbParams p, const SweepLeg *__restrict__ legs, const MorseStationDev *__restrict__ st,
+                                                         const long long *__restrict__ marks, int n_st)
+{
+    const long long runs = (n + kMorseRun - 1) / kMorseRun;
+    const long long step = (long long)gridDim.x * 256;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x;; q += step) {
+        const long long q0 = (long long)tb_uniform((unsigned long long)(q - (threadIdx.x & 63)));
+        if (q0 >= runs) break;
+        const long long w0 = q0 * kMorseRun, w1 = min(n, w0 + 64ll * kMorseRun), a = q * kMorseRun;
+        double2 acc[kMorseRun];
+#pragma unroll
+        for (int r = 0; r < kMorseRun; r++) acc[r] = make_double2(0.0, 0.0);
+        morse_sum(st, marks, n_st, w0, w1, a, acc);
+        if (a >= n) continue;
+        const int leg = p.sweep_on ? tb_find_leg(legs, p.n_legs, (unsigned long long)w0) : 0;
+        for (int s = 0; s < streams; s++) {
+            const unsigned long long key = tb_stream_key(p.seed, p.stream0 + (unsigned)s);
+            const float2 *src = in ? in + (long long)s * in_pitch : nullptr;
+            float2 *dst = out + (long long)s * out_pitch;
+#pragma unroll
+            for (int r = 0; r < kMorseRun; r += 2) {
+                const long long k = a + r;
+                if (vec && k + 1 < n) {
+                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (src) v = *reinterpret_cast<const float4 *>(src + k);
+                    const float2 y0 = tb_sample<true>(p, legs, leg, key, k, make_float2(v.x, v.y), acc[r]);
+                    const float2 y1 = tb_sample<true>(p, legs, leg, key, k + 1, make_float2(v.z, v.w), acc[r + 1]);
+                    *reinterpret_cast<float4 *>(dst + k) = make_float4(y0.x, y0.y, y1.x, y1.y);
+                } else {
+                    if (k < n) dst[k] = tb_sample<true>(p, legs, leg, key, k, src ? src[k] : make_float2(0.f, 0.f), acc[r]);
+                    if (k + 1 < n) dst[k + 1] = tb_sample<true>(p, legs, leg, key, k + 1, src ? src[k + 1] : make_float2(0.f, 0.f), acc[r + 1]);
+                }
+            }
         }
     }
 }
@@ -202,6 +302,120 @@ int tb_plan_sweep(double fs, const pebblegpu_sweep *s, TbSweepPlan *plan)
     return 0;
 }
 
+// MorseGen::setParams' sizes (morsegen.cpp:45-87) and one pass through the text: no device needed
+int tb_plan_morse(double fs, const pebblegpu_morse_station *st, MorsePlan *plan)
+{
+    if (!st || !plan) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (st->struct_size != sizeof(pebblegpu_morse_station)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_morse_station size mismatch (ABI %d)", PEBBLEGPU_ABI_VERSION);
+    if (!(fs > 0) || !std::isfinite(fs)) return fail(PEBBLEGPU_E_INVALID, "bad sample rate");
+    if (!std::isfinite(st->frequency_hz) || !std::isfinite(st->amplitude)) return fail(PEBBLEGPU_E_INVALID, "station parameters must be finite");
+    if (!(std::fabs(st->frequency_hz) < fs / 2)) return fail(PEBBLEGPU_E_INVALID, "station frequency %g Hz is outside +-fs/2", st->frequency_hz);
+    if (st->n_tokens == 0 || !st->tokens) return fail(PEBBLEGPU_E_INVALID, "a station needs at least one token");
+    for (uint32_t i = 0; i < st->n_tokens; i++)
+        if (st->tokens[i] >= 0x200) return fail(PEBBLEGPU_E_INVALID, "token %#x has more than nine bits (morsegen.cpp:244)", (unsigned)st->tokens[i]);
+    if (st->wpm == 0) return fail(PEBBLEGPU_E_UNSUPPORTED, "0 words per minute");
+    const uint32_t ms_tcw = 1200u / st->wpm;  // MorseCode::wpmToTcwMs
+    const double spt_d = (double)ms_tcw / (1000.0 / fs), rise_d = (double)st->ms_rise / (1000.0 / fs);  // morsegen.cpp:47, 55-56
+    if (ms_tcw == 0 || !(spt_d >= 1.0)) return fail(PEBBLEGPU_E_UNSUPPORTED, "%u words per minute at %g Hz: no sample per Tcw", st->wpm, fs);
+    if (!(3.0 * spt_d + rise_d < (double)kMorseMaxMark)) return fail(PEBBLEGPU_E_UNSUPPORTED, "marks of 2^26 samples or more are not built");
+    MorsePlan pl;
+    pl.spt = (unsigned long long)spt_d;
+    pl.rise = (unsigned long long)rise_d;
+    // m_numSamplesDot = samplesPerTcw - (rise + fall) / 2 (:58-59) is unsigned: below one sample the reference wraps
+    if (pl.spt <= pl.rise) return fail(PEBBLEGPU_E_UNSUPPORTED, "a rise of %llu samples leaves no dot at %llu samples per Tcw", pl.rise, pl.spt);
+    pl.dot = 2 * pl.rise + (pl.spt - pl.rise);       // :61
+    pl.dash = 2 * pl.rise + (3 * pl.spt - pl.rise);  // :66-67
+    if (pl.dash >= kMorseMaxMark) return fail(PEBBLEGPU_E_UNSUPPORTED, "marks of 2^26 samples or more are not built");
+    pl.period = 0;
+    for (uint32_t i = 0; i < st->n_tokens; i++) {
+        const unsigned tok = st->tokens[i];
+        if (!tok) { pl.period += 7 * pl.spt - 3; continue; }  // genWord, :84
+        int top = 8;
+        while (!((tok >> top) & 1u)) top--;
+        for (int b = top - 1; b >= 0; b--) pl.period += (b < top - 1 ? pl.spt : 0) + (((tok >> b) & 1u) ? pl.dash : pl.dot);  // genDot / genDash
+        pl.period += 3 * pl.spt;  // genChar
+        if (pl.period >= kMorseMaxPeriod) break;
+    }
+    if (pl.period >= kMorseMaxPeriod) return fail(PEBBLEGPU_E_UNSUPPORTED, "texts of 2^40 samples or more are not built");
+    *plan = pl;
+    return 0;
+}
+
+// the plan, the kernel's constants and where the marks of one pass start (genToken :236-267 over the tokens, in order)
+int tb_morse_station(double fs, const pebblegpu_morse_station *st, MorseStationHost *out)
+{
+    MorseStationHost h;
+    if (int rc = tb_plan_morse(fs, st, &h.plan)) return rc;
+    const MorsePlan &pl = h.plan;
+    h.dev.tps = st->frequency_hz / fs;
+    h.dev.amp = st->amplitude;
+    h.dev.inc = pl.rise ? st->amplitude / (double)pl.rise : 0.0;  // ampInc, :95 (never used with hard keying)
+    h.dev.rot_c = (double)cosl(2.0L * 3.14159265358979323846264338327950288L * (long double)h.dev.tps);
+    h.dev.rot_s = (double)sinl(2.0L * 3.14159265358979323846264338327950288L * (long double)h.dev.tps);
+    h.dev.rise = (unsigned)pl.rise;
+    h.dev.dot = (unsigned)pl.dot;
+    h.dev.dash = (unsigned)pl.dash;
+    unsigned long long at = 0;
+    for (uint32_t i = 0; i < st->n_tokens; i++) {
+        const unsigned tok = st->tokens[i];
+        if (!tok) { at += 7 * pl.spt - 3; continue; }
+        int top = 8;
+        while (!((tok >> top) & 1u)) top--;
+        for (int b = top - 1; b >= 0; b--) {
+            if (b < top - 1) at += pl.spt;  // the element space: between two marks of one character only (:272-275)
+            const bool dash = (tok >> b) & 1u;
+            h.mark_off.push_back(at);
+            h.mark_dash.push_back(dash ? 1 : 0);
+            at += dash ? pl.dash : pl.dot;
+        }
+        at += 3 * pl.spt;
+    }
+    h.pos = 0;
+    *out = std::move(h);
+    return 0;
+}
+
+void tb_morse_marks(const MorseStationHost &st, unsigned long long n, std::vector<long long> &marks)
+{
+    if (st.mark_off.empty()) return;
+    const long long period = (long long)st.plan.period;
+    // pass by pass: `base` is where a pass starts relative to the call's first sample (the first one at -pos)
+    for (long long base = -(long long)st.pos; base < (long long)n; base += period) {
+        // the first mark of the pass that ends behind the call's first sample (every mark ends inside its pass: a character space follows)
+        size_t j = 0;
+        if (base < 0) {
+            const unsigned long long from = (unsigned long long)(-base);
+            j = (size_t)(std::upper_bound(st.mark_off.begin(), st.mark_off.end(), from) - st.mark_off.begin());
+            if (j > 0 && st.mark_off[j - 1] + (st.mark_dash[j - 1] ? st.plan.dash : st.plan.dot) > from) j--;
+        }
+        for (; j < st.mark_off.size(); j++) {
+            const long long start = base + (long long)st.mark_off[j];
+            if (start >= (long long)n) return;
+            marks.push_back(start * 2 + st.mark_dash[j]);
+            if (marks.size() > kMorseMaxCallMarks) return;
+        }
+    }
+}
+
+int TestBenchCore::set_morse(const pebblegpu_morse_station *st, uint32_t n, int mix)
+{
+    if (n > PEBBLEGPU_MORSE_MAX_STATIONS) return fail(PEBBLEGPU_E_INVALID, "%u stations: at most %d", n, PEBBLEGPU_MORSE_MAX_STATIONS);
+    if (n && !st) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    std::vector<MorseStationHost> next(n);
+    for (uint32_t i = 0; i < n; i++)
+        if (int rc = tb_morse_station(fs, &st[i], &next[i])) return rc;
+    stations.swap(next);  // every station at its first token; the sweep and the noise counter stay where they are
+    morse_mix = mix != 0;
+    return 0;
+}
+
+int TestBenchCore::ensure_events()
+{
+    for (int i = 0; i < 2; i++)
+        if (!h_done[i]) PG_HIP(hipEventCreateWithFlags(&h_done[i], hipEventDisableTiming));
+    return 0;
+}
+
 int TestBenchCore::init(double sample_rate, uint32_t streams)
 {
     fs = sample_rate;
@@ -215,9 +429,13 @@ void TestBenchCore::release()
         if (d_legs[i]) (void)hipFree(d_legs[i]);
         if (h_legs[i]) (void)hipHostFree(h_legs[i]);
         if (h_done[i]) (void)hipEventDestroy(h_done[i]);
+        if (d_morse[i]) (void)hipFree(d_morse[i]);
+        if (h_morse[i]) (void)hipHostFree(h_morse[i]);
         d_legs[i] = nullptr; h_legs[i] = nullptr; h_done[i] = nullptr;
+        d_morse[i] = nullptr; h_morse[i] = nullptr;
     }
     leg_cap = 0;
+    morse_cap = 0;
 }
 
 // TestBench::reset(): the sweep restarts at the start frequency with phase 0 and pulse timer 0, the noise counter at 0
@@ -316,6 +534,18 @@ int TestBenchCore::run(hipStream_t s, const float2 *in, long long in_pitch, floa
     p.noise_on = noise_on ? 1 : 0;
     p.noise_amp = noise_amp;
     const int slot = parity;
+    const bool table = sweep_on || morse_on();  // the call uploads a table through pinned slot `slot`
+    size_t n_marks = 0;
+    if (morse_on()) {  // (first: a call too long for the mark table is refused before anything moves)
+        marks_.clear();
+        for (MorseStationHost &st : stations) {
+            st.dev.first = (unsigned)marks_.size();
+            tb_morse_marks(st, (unsigned long long)n, marks_);
+            if (marks_.size() > kMorseMaxCallMarks) return fail(PEBBLEGPU_E_UNSUPPORTED, "more than 2^22 marks in one call: make shorter calls");
+            st.dev.count = (unsigned)marks_.size() - st.dev.first;
+        }
+        n_marks = marks_.size();
+    }
     if (sweep_on) {
         p.sweep_on = 1;
         p.mix = sw.mix != 0;
@@ -326,34 +556,71 @@ int TestBenchCore::run(hipStream_t s, const float2 *in, long long in_pitch, floa
         if (legs_.size() > leg_cap) {  // (a call longer, or legs shorter, than any before: both tables grow; rare)
             PG_HIP(hipStreamSynchronize(s));
             const size_t cap = legs_.size() + legs_.size() / 2 + 8;
+            if (int rc = ensure_events()) return rc;
             for (int i = 0; i < 2; i++) {
-                if (h_done[i]) PG_HIP(hipEventSynchronize(h_done[i]));
+                PG_HIP(hipEventSynchronize(h_done[i]));
                 if (d_legs[i]) PG_HIP(hipFree(d_legs[i]));
                 if (h_legs[i]) PG_HIP(hipHostFree(h_legs[i]));
                 d_legs[i] = nullptr; h_legs[i] = nullptr;
                 PG_HIP(hipMalloc((void **)&d_legs[i], sizeof(SweepLeg) * cap));
                 PG_HIP(hipHostMalloc((void **)&h_legs[i], sizeof(SweepLeg) * cap));
-                if (!h_done[i]) PG_HIP(hipEventCreateWithFlags(&h_done[i], hipEventDisableTiming));
             }
             leg_cap = cap;
             used[0] = used[1] = false;
         }
-        if (used[slot]) PG_HIP(hipEventSynchronize(h_done[slot]));  // the upload two calls back has left the pinned slot
+    }
+    const size_t morse_bytes = sizeof(MorseStationDev) * stations.size() + sizeof(long long) * n_marks;
+    if (morse_on() && morse_bytes > morse_cap) {  // (more stations, or more marks in a call, than any before; rare)
+        PG_HIP(hipStreamSynchronize(s));
+        const size_t cap = morse_bytes + morse_bytes / 2 + 256;
+        if (int rc = ensure_events()) return rc;
+        for (int i = 0; i < 2; i++) {
+            PG_HIP(hipEventSynchronize(h_done[i]));
+            if (d_morse[i]) PG_HIP(hipFree(d_morse[i]));
+            if (h_morse[i]) PG_HIP(hipHostFree(h_morse[i]));
+            d_morse[i] = nullptr; h_morse[i] = nullptr;
+            morse_cap = 0;
+            PG_HIP(hipMalloc((void **)&d_morse[i], cap));
+            PG_HIP(hipHostMalloc((void **)&h_morse[i], cap));
+        }
+        morse_cap = cap;
+        used[0] = used[1] = false;
+    }
+    if (table && used[slot]) PG_HIP(hipEventSynchronize(h_done[slot]));  // the upload two calls back has left the pinned slot
+    if (sweep_on) {
         memcpy(h_legs[slot], legs_.data(), sizeof(SweepLeg) * legs_.size());
         PG_HIP(hipMemcpyAsync(d_legs[slot], h_legs[slot], sizeof(SweepLeg) * legs_.size(), hipMemcpyHostToDevice, s));
+        p.n_legs = (int)legs_.size();
+    }
+    if (morse_on()) {
+        MorseStationDev *hd = reinterpret_cast<MorseStationDev *>(h_morse[slot]);
+        for (size_t i = 0; i < stations.size(); i++) hd[i] = stations[i].dev;
+        if (n_marks) memcpy(h_morse[slot] + sizeof(MorseStationDev) * stations.size(), marks_.data(), sizeof(long long) * n_marks);
+        PG_HIP(hipMemcpyAsync(d_morse[slot], h_morse[slot], morse_bytes, hipMemcpyHostToDevice, s));
+    }
+    if (table) {
         PG_HIP(hipEventRecord(h_done[slot], s));
         used[slot] = true;
         parity ^= 1;
-        p.n_legs = (int)legs_.size();
     }
-    const bool mix_in = in != nullptr && !(sweep_on && !sw.mix);  // a generator that replaces never reads the input
+    const bool mix_in = in != nullptr && !(sweep_on && !sw.mix) && !(morse_on() && !morse_mix);  // a generator that replaces never reads the input
     const float2 *src = mix_in ? in : nullptr;
     const int vec = ((reinterpret_cast<uintptr_t>(out) | (src ? reinterpret_cast<uintptr_t>(src) : 0)) & 15) == 0 && (streams == 1 || ((in_pitch | out_pitch) & 1) == 0);
-    const long long items = vec ? (n + 1) / 2 : n;
-    long long blocks = (items + 255) / 256;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    launch(k_testbench, dim3((unsigned)blocks, streams), dim3(256), s, src, out, in_pitch, out_pitch, n, vec, p, (const SweepLeg *)(sweep_on ? d_legs[slot] : nullptr));
-    PG_HIP(hipGetLastError());
+    if (morse_on()) {
+        const long long runs = (n + kMorseRun - 1) / kMorseRun;
+        long long blocks = (runs + 255) / 256;
+        if (blocks > 256 * 8) blocks = 256 * 8;
+        launch(k_morsegen, dim3((unsigned)blocks), dim3(256), s, src, out, in_pitch, out_pitch, n, (int)streams, vec, p, (const SweepLeg *)(sweep_on ? d_legs[slot] : nullptr),
+               (const MorseStationDev *)d_morse[slot], (const long long *)(d_morse[slot] + sizeof(MorseStationDev) * stations.size()), (int)stations.size());
+        PG_HIP(hipGetLastError());
+        for (MorseStationHost &st : stations) st.pos = (st.pos + (unsigned long long)n) % st.plan.period;
+    } else {
+        const long long items = vec ? (n + 1) / 2 : n;
+        long long blocks = (items + 255) / 256;
+        if (blocks > 256 * 8) blocks = 256 * 8;
+        launch(k_testbench, dim3((unsigned)blocks, streams), dim3(256), s, src, out, in_pitch, out_pitch, n, vec, p, (const SweepLeg *)(sweep_on ? d_legs[slot] : nullptr));
+        PG_HIP(hipGetLastError());
+    }
     n_abs += (unsigned long long)n;
     return 0;
 }

@@ -169,6 +169,11 @@ int pebblegpu_set_testbench_sweep(pebblegpu_receiver *h, const pebblegpu_sweep *
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
     return h->rx.set_testbench_sweep(s);
 }
+int pebblegpu_set_testbench_morse(pebblegpu_receiver *h, const pebblegpu_morse_station *stations, uint32_t n_stations, int mix)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.set_testbench_morse(stations, n_stations, mix);
+}
 int pebblegpu_set_testbench_noise(pebblegpu_receiver *h, double amplitude, uint64_t seed)
 {
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");

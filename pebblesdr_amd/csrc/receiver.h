@@ -483,10 +483,45 @@ struct TbParams {                     // k_testbench's argument block
 };
 struct TbSweepPlan { double inc = 0; unsigned long long leg = 0, pulse_period = 0, pulse_on = 0; };
 int tb_plan_sweep(double fs, const pebblegpu_sweep *s, TbSweepPlan *plan);  // host only: leg length and the pulse timer's period / width in samples
+// Keyed Morse stations (MorseGen, plugins/MorseGenDevice/morsegen.cpp:33-328).  Per call the host lists, station by station, the marks that
+// intersect the call: (start relative to the call's first sample) * 2 + (1: dash), ascending; a mark that began in an earlier call has a
+// negative start.  The call's table is one block: n stations' MorseStationDev, then all marks.
+constexpr unsigned long long kMorseMaxMark = 1ull << 26;    // marks from here on are refused (the phase's product stays far inside a double)
+constexpr unsigned long long kMorseMaxPeriod = 1ull << 40;  // one pass through a text
+constexpr size_t kMorseMaxCallMarks = (size_t)1 << 22;      // marks of all stations in one call (a call of days of Morse is refused)
+constexpr int kMorseRun = 8;                                // consecutive samples one lane makes from one sincospi (k_morsegen)
+struct MorsePlan { unsigned long long spt = 0, rise = 0, dot = 0, dash = 0, period = 0; };  // samplesPerTcw, rise = fall, mark buffers, one pass
+int tb_plan_morse(double fs, const pebblegpu_morse_station *st, MorsePlan *plan);  // host only
+struct MorseStationDev {
+    double tps, amp, inc, rot_c, rot_s;  // turns per sample (f / fs), m_amplitude, ampInc (0 with hard keying), exp(j 2 pi f / fs)
+    unsigned rise, dot, dash;            // samples: rise = fall, the dot's and the dash's whole buffer
+    unsigned first, count;               // this call's marks: marks[first .. first + count)
+    unsigned pad;
+};
+struct MorseStationHost {
+    MorsePlan plan;
+    MorseStationDev dev = {};
+    std::vector<unsigned long long> mark_off;  // one pass: where each mark starts ...
+    std::vector<unsigned char> mark_dash;      // ... and which it is
+    unsigned long long pos = 0;                // where in its pass the station stands at the next sample
+};
+// the marks of `st` that intersect the next n samples, appended to `marks` (encoded as above); does not move the station
+void tb_morse_marks(const MorseStationHost &st, unsigned long long n, std::vector<long long> &marks);
+int tb_morse_station(double fs, const pebblegpu_morse_station *st, MorseStationHost *out);  // plan + one pass's marks; host only
+
 struct TestBenchCore {
     double fs = 0;
     uint32_t S = 1;
     bool sweep_on = false, noise_on = false;
+    // stations: set_morse replaces them and restarts them; reset() (the sweep's and the noise's setters) leaves them alone
+    std::vector<MorseStationHost> stations;
+    bool morse_mix = true;
+    std::vector<long long> marks_;
+    unsigned char *d_morse[2] = {nullptr, nullptr}, *h_morse[2] = {nullptr, nullptr};  // the call's station table, ping-pong like the legs
+    size_t morse_cap = 0;
+    bool morse_on() const { return !stations.empty(); }
+    int set_morse(const pebblegpu_morse_station *st, uint32_t n, int mix);  // n == 0: off
+    int ensure_events();
     pebblegpu_sweep sw = {};
     TbSweepPlan plan;
     double noise_amp = 0;
@@ -501,7 +536,7 @@ struct TestBenchCore {
     bool used[2] = {false, false};
     size_t leg_cap = 0;
     int parity = 0;
-    bool any() const { return sweep_on || noise_on; }
+    bool any() const { return sweep_on || noise_on || morse_on(); }
     int init(double sample_rate, uint32_t streams);
     void release();
     void reset();                                        // TestBench::reset
@@ -628,6 +663,7 @@ public:
     // copies of the signal at the reference's displayData points (:803, :945, :953, :992) and at the digital-modem hook (:979-980)
     int set_testbench_sweep(const pebblegpu_sweep *s);
     int set_testbench_noise(double amplitude, uint64_t seed);
+    int set_testbench_morse(const pebblegpu_morse_station *stations, uint32_t n_stations, int mix);
     int set_taps(uint32_t mask);
     const float2 *tap(int point, uint64_t *n_per_row, uint64_t *pitch, double *rate) const;
     int process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw = nullptr);
@@ -732,6 +768,7 @@ private:
     MorseCore morse_;
     TestBenchCore tb_;
     bool last_tb_ = false;            // the last call ran the generator (kernel_name)
+    bool last_tb_morse_ = false;      // ... with stations on: k_morsegen instead of k_testbench
     // taps: one buffer per enabled point (allocated when the point is first enabled), filled by a copy queued on the stream that has
     // just produced the signal; index = the point's number (PEBBLEGPU_TAP_*)
     static constexpr int kTapPoints = 17;

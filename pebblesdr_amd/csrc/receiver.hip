@@ -383,6 +383,15 @@ int Receiver::set_testbench_noise(double amplitude, uint64_t seed)
     return 0;
 }
 
+// MorseGen stations (plugins/MorseGenDevice): replaces the set and restarts the stations; the sweep and the noise counter stay where they are
+int Receiver::set_testbench_morse(const pebblegpu_morse_station *stations, uint32_t n_stations, int mix)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (int rc = tb_.set_morse(stations, n_stations, mix)) return rc;
+    touched_ = true;
+    return 0;
+}
+
 int Receiver::set_taps(uint32_t mask)
 {
     const uint32_t known = 1u << PEBBLEGPU_TAP_RAW_IQ | 1u << PEBBLEGPU_TAP_POST_MIXER | 1u << PEBBLEGPU_TAP_POST_BP | 1u << PEBBLEGPU_TAP_POST_DEMOD | 1u << PEBBLEGPU_TAP_MODEM;
@@ -603,6 +612,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     // TestBench::genSweep + genNoise, receiver.cpp:797-798: into the library's staging buffer (a raw call has been converted into it above:
     // generated in place; float2 input is read from the caller's buffer, which is never written)
     last_tb_ = tb_.any();
+    last_tb_morse_ = tb_.morse_on();
     if (last_tb_) {
         if (!d_raw_stage_) PG_HIP(hipMalloc((void **)&d_raw_stage_, sizeof(float2) * (size_t)S * max_sf * superframe));
         if (int rc = tb_.run(stream_, d_iq, in_pitch, d_raw_stage_, in_pitch, (long long)n, S, 0)) return rc;
@@ -958,13 +968,14 @@ int Receiver::process_ingested(uint32_t slot, int fmt, int order, double gain, u
 
 // "k_testbench + <front kernel>": one string per front-kernel name, kept for the life of the process like the literals the other groups
 // return (the set of names is small and fixed)
-static const char *testbench_label(const char *front)
+// (with stations on the generator's kernel is k_morsegen)
+static const char *testbench_label(const char *front, bool morse)
 {
     static std::mutex mu;
-    static std::map<std::string, std::string> labels;
+    static std::map<std::string, std::string> labels[2];
     std::lock_guard<std::mutex> g(mu);
-    auto it = labels.find(front);
-    if (it == labels.end()) it = labels.emplace(front, std::string("k_testbench + ") + front).first;
+    auto it = labels[morse].find(front);
+    if (it == labels[morse].end()) it = labels[morse].emplace(front, std::string(morse ? "k_morsegen + " : "k_testbench + ") + front).first;
     return it->second.c_str();
 }
 
@@ -974,7 +985,7 @@ const char *Receiver::kernel_name(int which) const
     case 1: return !bins ? "" : gated() ? (spec_.any ? "k_spectrum_list_any" : "k_spectrum_list_q128") : spec_.big ? "k_big256_cols + k_big256_rows" : spec_.per_q ? "k_spectrum_q128" : bins == 8192 ? (spec_.use_w64 ? "k_spectrum_w64" : spec_.last_fullc ? "k_spectrum_t128 (twiddles held)" : "k_spectrum_t128") : bins == 4096 ? "k_spectrum<2>" : "k_spectrum_1to1";
     case 2:
         if (!last_tb_) return dec_.front_name;
-        return testbench_label(dec_.front_name);
+        return testbench_label(dec_.front_name, last_tb_morse_);
     case 3: return dec_.rest_name;
     case 4: return wfm ? "" : ff_n == 2048 ? "k_fastfir_t128" : "k_fastfir";
     case 5: return wfm ? (wfmc_.fused ? "k_wfm_fir" : "k_iir_scan + k_discrim + k_fir_dec") : "k_anf/k_agc/k_iir_scan/k_pll_demod + k_fir_dec (listed channels only)";

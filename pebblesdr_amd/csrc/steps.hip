@@ -97,7 +97,7 @@ struct pebblegpu_demod : pg::StepBase {
     pg::WfmCore wfm;
     float2 *d_in = nullptr, *d_out = nullptr;
 };
-// the test bench's generator (NCO::genSweep / genNoise) on one stream of the caller's
+// the test bench's generator (NCO::genSweep / genNoise, MorseGen stations) on one stream of the caller's
 struct pebblegpu_siggen : pg::StepBase {
     pg::TestBenchCore tb;
     uint32_t noise_stream = 0;
@@ -668,6 +668,33 @@ int pebblegpu_sweep_plan(double sample_rate, const pebblegpu_sweep *s, uint64_t 
     if (pulse_on_samples) *pulse_on_samples = pl.pulse_on;
     return 0;
 }
+int pebblegpu_morse_station_plan(double sample_rate, const pebblegpu_morse_station *st, uint64_t *samples_per_tcw, uint64_t *rise_samples,
+                                 uint64_t *dot_samples, uint64_t *dash_samples, uint64_t *period_samples)
+{
+    pg::MorsePlan pl;
+    if (int rc = pg::tb_plan_morse(sample_rate, st, &pl)) return rc;
+    if (samples_per_tcw) *samples_per_tcw = pl.spt;
+    if (rise_samples) *rise_samples = pl.rise;
+    if (dot_samples) *dot_samples = pl.dot;
+    if (dash_samples) *dash_samples = pl.dash;
+    if (period_samples) *period_samples = pl.period;
+    return 0;
+}
+int pebblegpu_morse_station_marks(double sample_rate, const pebblegpu_morse_station *st, uint64_t first_sample, uint64_t n, int64_t *marks, uint32_t cap,
+                                  uint32_t *n_marks)
+{
+    if (!n_marks || (cap && !marks)) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    pg::MorseStationHost h;
+    if (int rc = pg::tb_morse_station(sample_rate, st, &h)) return rc;
+    h.pos = first_sample % h.plan.period;
+    std::vector<long long> m;
+    pg::tb_morse_marks(h, n, m);
+    if (m.size() > pg::kMorseMaxCallMarks) return fail(PEBBLEGPU_E_UNSUPPORTED, "more than 2^22 marks in one call: make shorter calls");
+    *n_marks = (uint32_t)m.size();
+    if (m.size() > cap) return fail(PEBBLEGPU_E_SIZE, "%zu marks, room for %u", m.size(), cap);
+    for (size_t i = 0; i < m.size(); i++) marks[i] = (int64_t)m[i];
+    return 0;
+}
 int pebblegpu_siggen_destroy(pebblegpu_siggen *g)
 {
     if (!g) return 0;
@@ -702,6 +729,11 @@ int pebblegpu_siggen_set_noise(pebblegpu_siggen *g, double amplitude, uint64_t s
     if (!g) return fail(PEBBLEGPU_E_INVALID, "null handle");
     return g->tb.set_noise(amplitude, seed);
 }
+int pebblegpu_siggen_set_morse(pebblegpu_siggen *g, const pebblegpu_morse_station *stations, uint32_t n_stations, int mix)
+{
+    if (!g) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return g->tb.set_morse(stations, n_stations, mix);
+}
 int pebblegpu_siggen_set_stream(pebblegpu_siggen *g, uint32_t stream)
 {
     if (!g) return fail(PEBBLEGPU_E_INVALID, "null handle");
@@ -726,7 +758,7 @@ int pebblegpu_siggen_generate(pebblegpu_siggen *g, double *iq, uint32_t n)
 {
     if (!g || !iq) return fail(PEBBLEGPU_E_INVALID, "null argument");
     if (n == 0) return fail(PEBBLEGPU_E_SIZE, "bad sample count");
-    if (!g->tb.any()) return 0;  // both generators off: the frame stays as it is (testbench.cpp:522-523, 539-540)
+    if (!g->tb.any()) return 0;  // every generator off: the frame stays as it is (testbench.cpp:522-523, 539-540)
     PG_HIP(hipSetDevice(g->device));
     if (n > g->cap) {
         PG_HIP(hipStreamSynchronize(g->stream));
