@@ -14,8 +14,20 @@ _SO = os.path.join(_HERE, "libpebble_oracle.so")
 AM, SAM, FMN, FMM, FMS, DSB, LSB, USB, CWL, CWU, DIGL, DIGU, NONE = range(13)
 
 
+def build_ref(force=False):
+    """Build oracle/_ref/ref_driver, the reference's own DSP classes behind a command line (oracle/ref_build/).  Returns its
+    path, or None where there is no reference tree to build it from (then tests/test_reference_pins.py uses its fixtures)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_pebble_build_ref", os.path.join(_HERE, "ref_build", "build_ref.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.build_ref(force=force)
+
+
 def build(force=False):
-    """Compile the oracle with gcc (a few hundred ms).  Safe to call repeatedly."""
+    """Compile the oracle with gcc (a few hundred ms), and the reference driver where a reference tree exists.  Safe to call
+    repeatedly."""
+    build_ref(force=force)
     src = [os.path.join(_HERE, f) for f in ("pebble_oracle.c", "pebble_oracle.h", "hb_taps.h")]
     if (not force) and os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(s) for s in src):
         return _SO
@@ -293,7 +305,7 @@ class Spectrum:
     def process(self, x):
         x = _c128(x)
         out = np.empty(self.bins, dtype=np.float64)
-        lib().po_spectrum_process(self.h, _ptr(x), len(x), _ptr(out))
+        self.overload = bool(lib().po_spectrum_process(self.h, _ptr(x), len(x), _ptr(out)))  # FFT::getOverload after this frame
         return out
 
 

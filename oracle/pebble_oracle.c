@@ -398,6 +398,7 @@ struct po_spectrum {
     double *time, *freq; /* m_timeDomain / unfolded */
     double *prev_power, *prev_amp; /* m_fftPower / m_fftAmplitude (zero-initialised here; the
                                       reference leaves them uninitialised, fft.cpp:107-115) */
+    int overload;        /* m_isOverload: a member, false at construction (fft.cpp:26), rewritten by whole buffers only */
 };
 
 po_spectrum *po_spectrum_new(uint32_t fft_size, uint32_t samples_per_buffer, int window_type, int lift_clamp)
@@ -447,11 +448,11 @@ static double po_clip_db(double db) { return db < -120.0 ? -120.0 : (db > 0.0 ? 
  * forward FFT, m_unfoldInOrder (fft.cpp:207-213), calcPowerAverages (fft.cpp:324-399). */
 int po_spectrum_process(po_spectrum *s, const double *in, uint32_t n, double *out_db)
 {
-    int overload = 0;
     uint32_t N = s->fft_size;
     if (s->window_type == 0 && n == s->spb) {
+        s->overload = 0; /* fft.cpp:135 */
         for (uint32_t i = 0; i < s->spb; i++) {
-            if (fabs(in[2 * i]) > 0.9 || fabs(in[2 * i + 1]) > 0.9) overload = 1;
+            if (fabs(in[2 * i]) > 0.9 || fabs(in[2 * i + 1]) > 0.9) s->overload = 1;
             /* in[i] * windowCpx[i] with windowCpx = (w, 0): full complex product */
             double w = s->window[i];
             s->time[2 * i] = in[2 * i] * w - in[2 * i + 1] * 0.0;
@@ -459,6 +460,8 @@ int po_spectrum_process(po_spectrum *s, const double *in, uint32_t n, double *ou
         }
         for (uint32_t i = s->spb; i < N; i++) { s->time[2 * i] = 0; s->time[2 * i + 1] = 0; }
     } else {
+        /* fft.cpp:147-153: no overload test on this branch; the flag of the last whole buffer stands (pinned by
+         * tests/test_reference_pins.py, spectrum_overload_then_short) */
         memset(s->time, 0, (size_t)N * 2 * sizeof(double));
         memcpy(s->time, in, (size_t)(n < N ? n : N) * 2 * sizeof(double));
     }
@@ -478,7 +481,7 @@ int po_spectrum_process(po_spectrum *s, const double *in, uint32_t n, double *ou
         double db = (bin_amp == 0) ? -120.0 : 20 * log10(bin_amp); /* amplitudeTodB, db.h:44-48 */
         out_db[i] = po_clip_db(db);
     }
-    return overload;
+    return s->overload;
 }
 
 /* ------------------------------------------------------------------------------------------------

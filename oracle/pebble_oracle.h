@@ -5,15 +5,19 @@
  * "port" CPU baseline that bench.py times.  Nothing under pebblesdr_amd/ or include/ may include,
  * link or call it; only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg do.
  *
- * PARITY PINNING STATUS: the reference (Qt5 + Apple Accelerate, macOS/Windows only) cannot be
- * built in this image without writing stand-in Qt/vDSP headers, which the build rules forbid, so
- * there is no oracle/_ref.  The reference ships no tests and no golden vectors.
- * The oracle is pinned by (1) the one worked known-answer table the reference holds
+ * PARITY PINNING STATUS: the reference's DSP classes (Qt5 + Apple Accelerate, macOS/Windows only) are built
+ * unmodified against stand-in Qt/vDSP headers into oracle/_ref/ref_driver (oracle/ref_build/), and
+ * tests/test_reference_pins.py compares every time-domain stage below with them on the same fp64 input: mixer,
+ * decimator, CDownConvert, FastFIR, CFir, CIir, resampler, spectrum, AGC, blankers, ANF, IQBalance, DCRemoval,
+ * fdEstimate -- all bit for bit (DESIGN.md section 3 has the table).  Not pinned that way: the two vDSP primitives
+ * (the stand-in is our code), FastFIR at 8192/4097 and the demodulators (demod.h needs a uic-generated header).
+ * The reference ships no tests and no golden vectors.
+ * The oracle is also pinned by (1) the one worked known-answer table the reference holds
  * (pebblelib/fft.cpp:363-369, -10 dB tone -> spectrum peak per FFT size), (2) the outputs of
  * the reference itself recorded when it was executed at survey time (chain
  * tables, tap counts, oscillator fixed point, FastFIR pass-band gain, spectrum peaks), and
  * (3) closed-form / independent-implementation cross-checks (numpy.fft, scipy.signal).  Stages with
- * none of these say "parity unpinned" in their tests.
+ * none of these and no reference pin say "parity unpinned" in their tests.
  *
  * Every function cites the reference file:line it restates (paths relative to /root/reference).
  * Complex buffers are interleaved (re, im) doubles == CPX = std::complex<double> (pebblelib/cpx.h:96).
@@ -52,8 +56,8 @@ void po_decimator_stage(const po_decimator *d, int i, int *ntaps, uint32_t *stri
 /* Decimator::process (vDSP path): returns number of output samples (decimator.cpp:152-226) */
 uint32_t po_decimator_process(po_decimator *d, const double *in, double *out, uint32_t n);
 
-/* ---- CDownConvert: pebblelib/downconvert.cpp:63-535, filtercoef.h (the alternate mixer + decimator; "parity unpinned": the
- * reference's tests hold no vector for it -- pinned only by the thresholds its own comments work out, downconvert.cpp:124-134) ---- */
+/* ---- CDownConvert: pebblelib/downconvert.cpp:63-535, filtercoef.h (the alternate mixer + decimator; pinned to the
+ * reference binary by tests/test_reference_pins.py, downconvert_*, and by the thresholds its own comments work out, downconvert.cpp:124-134) ---- */
 typedef struct po_downconvert po_downconvert;
 po_downconvert *po_downconvert_new(void);
 void po_downconvert_free(po_downconvert *d);
@@ -89,7 +93,7 @@ void po_spectrum_free(po_spectrum *s);
 uint32_t po_spectrum_bins(const po_spectrum *s);
 double po_spectrum_coherent_gain(const po_spectrum *s);
 const double *po_spectrum_window(const po_spectrum *s);
-/* returns overload flag; out has bins doubles (dB amplitude, -f..+f) */
+/* returns the overload flag (m_isOverload: rewritten by whole buffers only, kept by shorter calls); out has bins doubles (dB amplitude, -f..+f) */
 int po_spectrum_process(po_spectrum *s, const double *in, uint32_t n, double *out_db);
 
 /* ---- CFir: pebblelib/fir.cpp:106-132, 246-337, 494-512 ---- */
@@ -174,7 +178,7 @@ void po_demod_wfm_process_mono(po_demod_wfm *d, const double *in, double *out, i
  * setters below are used; audio out is the caller's. */
 /* ------------------------------------------------------------------------------------------------
  * AGC -- application/agc.{h,cpp}.  modes: 0 AGC_OFF, 1 ACG_FAST, 2 AGC_MED, 3 AGC_SLOW, 4 AGC_LONG
- * (agc.h enum AgcMode).  Parity unpinned: the reference holds no recorded values for this class.
+ * (agc.h enum AgcMode).  Pinned to the reference binary: tests/test_reference_pins.py, agc_*.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct po_agc po_agc;
 po_agc *po_agc_new(double sample_rate);                       /* AGC::AGC, agc.cpp:15-32 */
@@ -183,8 +187,8 @@ void po_agc_set_mode(po_agc *a, int mode, int threshold);     /* setAgcMode + se
 void po_agc_process(po_agc *a, const double *in, double *out, int n); /* processBlock, agc.cpp:84-235 */
 
 /* ------------------------------------------------------------------------------------------------
- * CFractResampler (complex version) -- pebblelib/fractresampler.cpp:87-195.  Parity unpinned (no
- * recorded values in the reference).
+ * CFractResampler (complex version) -- pebblelib/fractresampler.cpp:87-195.  Pinned to the reference
+ * binary: tests/test_reference_pins.py, resampler_*.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct po_resampler po_resampler;
 po_resampler *po_resampler_new(int max_input);                /* Init, fractresampler.cpp:87-140 */
@@ -194,8 +198,8 @@ int po_resampler_process(po_resampler *r, int n, double rate, const double *in, 
 double po_resampler_time(const po_resampler *r);              /* m_FloatTime, for tests */
 
 /* ------------------------------------------------------------------------------------------------
- * Pre-chain conditioners and the noise filter (all default-off in the reference; parity unpinned: no
- * recorded values).  DCRemoval is po_iir_init_hp(10, 0.7071, fs) + po_iir_process_cpx (dcremoval.cpp:3-19).
+ * Pre-chain conditioners and the noise filter (all default-off in the reference; pinned to the reference
+ * binary: tests/test_reference_pins.py, nb*, anf, iqbalance, dcremoval_*, fdestimate).  DCRemoval is po_iir_init_hp(10, 0.7071, fs) + po_iir_process_cpx (dcremoval.cpp:3-19).
  * ---------------------------------------------------------------------------------------------- */
 /* IQBalance::ProcessBlock, application/iqbalance.cpp:65-86 (t1, t2 restart at zero every block) */
 void po_iq_balance(double gain_factor, double phase_factor, const double *in, double *out, int n);

@@ -1,0 +1,335 @@
+/* ref_driver -- runs the reference's own DSP classes (compiled unmodified from the reference tree) on a file of
+ * float64 input and writes what they produce.  It restates no arithmetic: constructors and methods only.
+ *
+ *   ref_driver STAGE IN OUT [numbers...]
+ *
+ * IN:  raw float64, interleaved (re, im) unless the stage says otherwise.
+ * OUT: raw float64 records, each [count, count values]; complex values are interleaved.
+ * The stages and their arguments are listed in main(); tests/reference_cases.py is the other end of this interface.
+ *
+ * Private members are read (coefficients, clocks, chain tables) by compiling this one file with the access
+ * keywords opened; the reference's sources are compiled as they are.
+ */
+#include <cmath>
+#include <complex>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <string>
+#include <vector>
+#include "qt_standins.h"
+
+#define private public
+#define protected public
+#include "cpx.h"
+#include "mixer.h"
+#include "decimator.h"
+#include "downconvert.h"
+#include "fastfir.h"
+#include "fft.h"
+#include "fftaccelerate.h"
+#include "fftooura.h"
+#include "fir.h"
+#include "iir.h"
+#include "fractresampler.h"
+#include "global.h"
+#include "agc.h"
+#include "noiseblanker.h"
+#include "noisefilter.h"
+#include "dcremoval.h"
+#include "iqbalance.h"
+#include "signalstrength.h"
+#undef private
+#undef protected
+
+Global *global = nullptr;
+/* what moc would generate for the one signal the driven classes declare */
+void SignalStrength::newSignalStrength(double, double, double, double, double) {}
+
+static std::vector<double> g_in;
+static FILE *g_out;
+static std::vector<double> g_arg;
+
+static void rec(const double *v, size_t n)
+{
+    double c = double(n);
+    fwrite(&c, sizeof c, 1, g_out);
+    if (n)
+        fwrite(v, sizeof(double), n, g_out);
+}
+static void rec1(double v) { rec(&v, 1); }
+static void rec_cpx(const CPX *v, size_t n) { rec(reinterpret_cast<const double *>(v), 2 * n); }
+static CPX *in_cpx() { return reinterpret_cast<CPX *>(g_in.data()); }
+static size_t in_len() { return g_in.size() / 2; }
+static double arg(size_t i)
+{
+    if (i >= g_arg.size()) {
+        fprintf(stderr, "ref_driver: missing argument %zu\n", i);
+        exit(2);
+    }
+    return g_arg[i];
+}
+
+/* mixer FS N F0 [RETUNE_FRAME F1]: one record per frame */
+static void st_mixer()
+{
+    quint32 n = quint32(arg(1));
+    Mixer m(quint32(arg(0)), n);
+    m.setFrequency(arg(2));
+    for (size_t f = 0; f * n + n <= in_len(); f++) {
+        if (g_arg.size() > 4 && f == size_t(arg(3)))
+            m.setFrequency(arg(4));
+        rec_cpx(m.processBlock(in_cpx() + f * n), n);
+    }
+}
+
+/* decimator FS BW N PLAIN: records: rate, decBy2Stages, chain (taps, stride pairs), then one record per frame.
+ * PLAIN=1 runs the chain through HalfbandFilter::process (no vDSP) */
+static void st_decimator()
+{
+    quint32 n = quint32(arg(2));
+    Decimator d(quint32(arg(0)), n);
+    if (arg(3) != 0)
+        d.m_useVdsp = false;
+    rec1(d.buildDecimationChain(quint32(arg(0)), quint32(arg(1))));
+    rec1(d.decBy2Stages());
+    std::vector<double> chain;
+    for (int i = 0; i < d.m_decimationChain.length(); i++) {
+        HalfbandFilter *h = d.m_decimationChain[i];
+        chain.push_back(h->m_useCIC3 ? 0 : h->m_numTaps);
+        chain.push_back(h->m_decimate);
+    }
+    rec(chain.data(), chain.size());
+    std::vector<CPX> out(n + 16);
+    for (size_t f = 0; f * n + n <= in_len(); f++) {
+        quint32 k = d.process(in_cpx() + f * n, out.data(), n);
+        rec_cpx(out.data(), k);
+    }
+    if (arg(3) != 0)
+        d.m_useVdsp = true; /* the destructor frees what the constructor made */
+}
+
+/* downconvert INRATE MAXBW SIMPLE (LEN FREQ CWOFFSET)...: records: rate, then one record per call; the setters are
+ * called before a call whose frequency or offset differs from the call before */
+static void st_downconvert()
+{
+    CDownConvert d;
+    double rate = arg(2) != 0 ? d.SetDataRateSimple(arg(0), arg(1)) : d.SetDataRate(arg(0), arg(1));
+    rec1(rate);
+    size_t pos = 0;
+    double pf = 0, pc = 0;
+    for (size_t c = 0; 3 + 3 * c + 2 < g_arg.size(); c++) {
+        int n = int(g_arg[3 + 3 * c]);
+        double f = g_arg[4 + 3 * c], cw = g_arg[5 + 3 * c];
+        if (c == 0 || f != pf || cw != pc) {
+            d.SetCwOffset(cw);
+            d.SetFrequency(f);
+        }
+        pf = f;
+        pc = cw;
+        std::vector<CPX> work(in_cpx() + pos, in_cpx() + pos + n), out(n + 16); /* ProcessData mixes its input in place */
+        int k = d.ProcessData(n, work.data(), out.data());
+        rec_cpx(out.data(), k);
+        pos += n;
+    }
+}
+
+/* fastfir LO HI OFFSET FS N: records: H (2048 complex), then one record per block */
+static void st_fastfir()
+{
+    CFastFIR f;
+    int n = int(arg(4));
+    f.SetupParameters(arg(0), arg(1), arg(2), arg(3));
+    rec_cpx(f.m_pFilterCoef, f.m_Fft->getFFTSize());
+    std::vector<CPX> out(in_len() + 4 * 8192);
+    for (size_t b = 0; b * n + n <= in_len(); b++) {
+        int k = f.ProcessData(n, in_cpx() + b * n, out.data());
+        rec_cpx(out.data(), k);
+    }
+}
+
+/* fir NTAPS SCALE ASTOP FPASS FSTOP FS: records: tap count, taps, filtered input */
+static void st_fir()
+{
+    CFir f;
+    int nt = f.InitLPFilter(int(arg(0)), arg(1), arg(2), arg(3), arg(4), arg(5));
+    rec1(nt);
+    rec(f.m_Coef, nt);
+    std::vector<CPX> out(in_len());
+    f.ProcessFilter(int(in_len()), in_cpx(), out.data());
+    rec_cpx(out.data(), out.size());
+}
+
+/* iir KIND(0 LP, 1 HP) F0 Q FS: records: (b0 b1 b2 a1 a2), filtered input */
+static void st_iir()
+{
+    CIir q;
+    if (arg(0) == 0)
+        q.InitLP(arg(1), arg(2), arg(3));
+    else
+        q.InitHP(arg(1), arg(2), arg(3));
+    double c[5] = {q.m_B0, q.m_B1, q.m_B2, q.m_A1, q.m_A2};
+    rec(c, 5);
+    std::vector<CPX> out(in_len());
+    q.ProcessFilter(int(in_len()), in_cpx(), out.data());
+    rec_cpx(out.data(), out.size());
+}
+
+/* resampler MAXIN RATE N: per frame two records: output, m_FloatTime */
+static void st_resampler()
+{
+    CFractResampler r;
+    int n = int(arg(2));
+    r.Init(int(arg(0)));
+    std::vector<CPX> out(size_t(n / arg(1)) + 16);
+    for (size_t f = 0; f * n + n <= in_len(); f++) {
+        int k = r.Resample(n, arg(1), in_cpx() + f * n, out.data());
+        rec_cpx(out.data(), k);
+        rec1(r.m_FloatTime);
+    }
+}
+
+/* spectrum FFTSIZE SPB FS OOURA LEN...: per frame two records: dB bins, overload flag.  The previous-frame
+ * buffers are uninitialised in the reference; they are zeroed here so that frame 0 is defined */
+static void st_spectrum()
+{
+    FFT *f = arg(3) != 0 ? static_cast<FFT *>(new FFTOoura()) : FFT::factory("ref_driver");
+    f->fftParams(quint32(arg(0)), 0, arg(2), int(arg(1)), WindowFunction::BLACKMANHARRIS);
+    int bins = f->getFFTSize();
+    memset(f->m_fftPower, 0, bins * sizeof(double));
+    memset(f->m_fftAmplitude, 0, bins * sizeof(double));
+    memset(f->m_fftPhase, 0, bins * sizeof(double));
+    std::vector<double> out(bins);
+    size_t pos = 0;
+    for (size_t i = 4; i < g_arg.size(); i++) {
+        int n = int(g_arg[i]);
+        bool over = f->fftSpectrum(in_cpx() + pos, out.data(), n);
+        pos += n;
+        rec(out.data(), bins);
+        rec1(over ? 1 : 0);
+    }
+    delete f;
+}
+
+/* agc FS N (MODE THRESHOLD)...: one block per pair, setAgcMode when the pair changes; one record per block */
+static void st_agc()
+{
+    quint32 n = quint32(arg(1));
+    AGC a(quint32(arg(0)), n);
+    double pm = -1, pt = -1;
+    for (size_t b = 0; 2 + 2 * b + 1 < g_arg.size(); b++) {
+        double m = g_arg[2 + 2 * b], t = g_arg[3 + 2 * b];
+        if (m != pm || t != pt)
+            a.setAgcMode(AGC::AgcMode(int(m)), int(t));
+        pm = m;
+        pt = t;
+        rec_cpx(a.processBlock(in_cpx() + b * n), n);
+    }
+}
+
+/* nb WHICH(1|2) FS N ON...: one block per flag; the setter is called when the flag changes; one record per block */
+static void st_nb()
+{
+    quint32 n = quint32(arg(2));
+    NoiseBlanker nb(quint32(arg(1)), n);
+    int which = int(arg(0)), prev = 0;
+    for (size_t b = 0; 3 + b < g_arg.size(); b++) {
+        int on = int(g_arg[3 + b]);
+        if (on != prev) {
+            if (which == 1)
+                nb.setNbEnabled(on != 0);
+            else
+                nb.setNb2Enabled(on != 0);
+        }
+        prev = on;
+        CPX *o = which == 1 ? nb.ProcessBlock(in_cpx() + b * n) : nb.ProcessBlock2(in_cpx() + b * n);
+        rec_cpx(o, n);
+    }
+}
+
+/* anf FS N: one record per block */
+static void st_anf()
+{
+    quint32 n = quint32(arg(1));
+    NoiseFilter nf(quint32(arg(0)), n);
+    nf.enableStep(true);
+    for (size_t b = 0; b * n + n <= in_len(); b++)
+        rec_cpx(nf.ProcessBlock(in_cpx() + b * n), n);
+}
+
+/* iqbalance FS N GAIN PHASE: one record per block */
+static void st_iqbalance()
+{
+    quint32 n = quint32(arg(1));
+    IQBalance q(quint32(arg(0)), n);
+    q.enableStep(true);
+    q.setAutomatic(false);
+    q.setGainFactor(arg(2));
+    q.setPhaseFactor(arg(3));
+    for (size_t b = 0; b * n + n <= in_len(); b++)
+        rec_cpx(q.ProcessBlock(in_cpx() + b * n), n);
+}
+
+/* dcremoval FS N: one record per block */
+static void st_dcremoval()
+{
+    quint32 n = quint32(arg(1));
+    DCRemoval d(quint32(arg(0)), n);
+    d.enableStep(true);
+    for (size_t b = 0; b * n + n <= in_len(); b++)
+        rec_cpx(d.process(in_cpx() + b * n, n), n);
+}
+
+/* fdestimate FS N RATE MIXER (LO HI)...: IN is one dB spectrum (real doubles); one record (peak, avg, snr, floor,
+ * returned value) per band */
+static void st_fdestimate()
+{
+    SignalStrength s(quint32(arg(0)), quint32(arg(1)));
+    for (size_t b = 0; 4 + 2 * b + 1 < g_arg.size(); b++) {
+        double r = s.fdEstimate(g_in.data(), int(g_in.size()), quint32(arg(2)), float(g_arg[4 + 2 * b]), float(g_arg[5 + 2 * b]), arg(3));
+        double v[5] = {s.peakDb(), s.avgDb(), s.snrDb(), s.floorDb(), r};
+        rec(v, 5);
+    }
+}
+
+int main(int argc, char **argv)
+{
+    static const struct { const char *name; void (*fn)(); } stages[] = {
+        {"mixer", st_mixer}, {"decimator", st_decimator}, {"downconvert", st_downconvert}, {"fastfir", st_fastfir},
+        {"fir", st_fir}, {"iir", st_iir}, {"resampler", st_resampler}, {"spectrum", st_spectrum}, {"agc", st_agc},
+        {"nb", st_nb}, {"anf", st_anf}, {"iqbalance", st_iqbalance}, {"dcremoval", st_dcremoval}, {"fdestimate", st_fdestimate}};
+    if (argc < 4) {
+        fprintf(stderr, "usage: ref_driver STAGE IN OUT [numbers...]\n");
+        return 2;
+    }
+    FILE *fi = fopen(argv[2], "rb");
+    if (!fi) {
+        perror(argv[2]);
+        return 2;
+    }
+    fseek(fi, 0, SEEK_END);
+    long bytes = ftell(fi);
+    fseek(fi, 0, SEEK_SET);
+    g_in.resize(size_t(bytes) / sizeof(double) + 2);
+    if (bytes && fread(g_in.data(), 1, size_t(bytes), fi) != size_t(bytes)) {
+        perror("read");
+        return 2;
+    }
+    g_in.resize(size_t(bytes) / sizeof(double));
+    fclose(fi);
+    for (int i = 4; i < argc; i++)
+        g_arg.push_back(strtod(argv[i], nullptr));
+    g_out = fopen(argv[3], "wb");
+    if (!g_out) {
+        perror(argv[3]);
+        return 2;
+    }
+    for (const auto &s : stages)
+        if (!strcmp(argv[1], s.name)) {
+            s.fn();
+            return fclose(g_out) ? 2 : 0;
+        }
+    fprintf(stderr, "ref_driver: unknown stage %s\n", argv[1]);
+    return 2;
+}

@@ -1,0 +1,2 @@
+/* stand-in: see qt_standins.h */
+#include "qt_standins.h"

@@ -280,15 +280,22 @@ M2 m2_mul(const M2 &x, const M2 &y)
 {
     return M2{x.a * y.a + x.b * y.c, x.a * y.b + x.b * y.d, x.c * y.a + x.d * y.c, x.c * y.b + x.d * y.d};
 }
+// Squared in long double and rounded once: a biquad whose poles lie at 1 - 2e-6 (DCRemoval's 10 Hz high-pass at 20 Msps) has
+// M^256 = [[257, -256], [256, -255]] minus terms of 1e-3; squaring in double leaves 8e-10 in those entries (129^2 - 128^2 cancels
+// from 1.6e4), and a scan that multiplies direct-form-2 states of 5e8 by them puts 4e-7 of drift into the filter's output.
 M2 m2_pow(M2 x, uint64_t e)
 {
-    M2 r{1, 0, 0, 1};
+    long double r[4] = {1, 0, 0, 1}, b[4] = {x.a, x.b, x.c, x.d};
+    auto mul = [](const long double *p, const long double *q, long double *o) {
+        const long double t[4] = {p[0] * q[0] + p[1] * q[2], p[0] * q[1] + p[1] * q[3], p[2] * q[0] + p[3] * q[2], p[2] * q[1] + p[3] * q[3]};
+        for (int i = 0; i < 4; i++) o[i] = t[i];
+    };
     while (e) {
-        if (e & 1) r = m2_mul(r, x);
-        x = m2_mul(x, x);
+        if (e & 1) mul(r, b, r);
+        mul(b, b, b);
         e >>= 1;
     }
-    return r;
+    return M2{(double)r[0], (double)r[1], (double)r[2], (double)r[3]};
 }
 double spectral_radius(const M2 &x)
 {

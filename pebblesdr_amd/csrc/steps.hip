@@ -109,6 +109,7 @@ struct pebblegpu_spectrum : pg::StepBase {
     float2 *d_in = nullptr;
     float *d_out = nullptr;
     std::vector<float> hs;
+    int overload = 0;  // m_isOverload: a member, rewritten by whole buffers only (fft.cpp:26,135-140)
     int path = 0;  // 0: no call yet; 1: the frame-length kernels; 2: the general kernel (their previous-frame amplitudes are laid out differently)
     double fs = 0;             // m_sampleRate (mapFFTToScreen's binsPerHz)
     int32_t *d_px = nullptr;   // mapFFTToScreen's pixels
@@ -614,13 +615,18 @@ int pebblegpu_spectrum_process(pebblegpu_spectrum *s, const double *in, int n, d
     if (n <= 0 || (uint32_t)n > s->sp.nf)
         return fail(PEBBLEGPU_E_SIZE, "numSamples %d is not in 1..samplesPerBuffer (%u)", n, s->sp.nf);
     PG_HIP(hipSetDevice(s->device));
-    int ov = 0;  // m_isOverload: any |re| or |im| above m_overLimit = 0.9 (fft.cpp:137-140), flagged on the host copy
-    for (int i = 0; i < 2 * n; i++) if (std::fabs(in[i]) > 0.9) { ov = 1; break; }
-    if (int rc = s->up(s->d_in, in, (size_t)n)) return rc;
     const int path = ((uint32_t)n == s->sp.nf && !s->sp.any) ? 1 : 2;
     if (s->path && s->path != path)
         return fail(PEBBLEGPU_E_UNSUPPORTED, "one spectrum object takes either whole buffers of %u samples or shorter ones (its previous-frame average is kept per kernel family): create a second object", s->sp.nf);
     s->path = path;
+    // m_isOverload: any |re| or |im| above m_overLimit = 0.9, tested on whole buffers only (fft.cpp:133-140), flagged on the host copy (a refused call, above, leaves it alone);
+    // a shorter call takes the other branch of m_applyWindow, which tests nothing and leaves the member as it was
+    if ((uint32_t)n == s->sp.nf) {
+        s->overload = 0;
+        for (int i = 0; i < 2 * n; i++) if (std::fabs(in[i]) > 0.9) { s->overload = 1; break; }
+    }
+    const int ov = s->overload;
+    if (int rc = s->up(s->d_in, in, (size_t)n)) return rc;
     if ((uint32_t)n == s->sp.nf) {
         if (int rc = s->sp.run(s->stream, s->d_in, n, 1, s->d_out, nullptr, nullptr, true)) return rc;  // (a step on its own stream: nothing beside it)
     } else {

@@ -1,0 +1,416 @@
+"""The cases of tests/test_reference_pins.py: for each, the input recipe, the reference driver's command line
+(oracle/ref_build/ref_driver.cpp) and the oracle's counterpart, both returning the same list of records.
+
+Shared by the test module and tools/record_reference_pins.py, which writes the fixtures tests/golden/refpin_*.npy.
+
+A record is (kind, float64 array); complex samples are stored interleaved.  kind:
+  "x"  compared exactly (counts, chain tables, flags, and every record of a case whose bar is 0)
+  "v"  values: relative RMS error <= the case's bar
+  "d"  decibels: max |difference| <= the case's dB bar
+"""
+import json
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+from tests.signals import lcg_noise, tones
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+BINARY = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
+TAIL = 512  # values of a case's last record kept in its fixture (256 complex samples)
+
+# The ceilings the bars may never exceed: four orders under the 1e-5 / 0.1 dB the oracle is used to judge.
+MAX_BAR = 1e-9
+MAX_BAR_DB = 1e-6
+
+
+def _il(z):
+    """complex -> interleaved float64"""
+    return np.ascontiguousarray(z, dtype=np.complex128).view(np.float64).copy()
+
+
+def run_driver(stage, x, args):
+    """-> list of float64 arrays, the driver's records.  A binary that does not run is an error."""
+    with tempfile.TemporaryDirectory() as d:
+        fi, fo = os.path.join(d, "in.f64"), os.path.join(d, "out.f64")
+        (np.ascontiguousarray(x, dtype=np.float64) if np.isrealobj(x) else _il(x)).tofile(fi)
+        p = subprocess.run([BINARY, stage, fi, fo] + [repr(float(a)) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                           text=True, timeout=120)
+        assert p.returncode == 0, "ref_driver %s failed (%d): %s" % (stage, p.returncode, p.stdout[-500:])
+        raw = np.fromfile(fo, dtype=np.float64)
+    out, pos = [], 0
+    while pos < len(raw):
+        n = int(raw[pos])
+        out.append(raw[pos + 1:pos + 1 + n].copy())
+        pos += 1 + n
+    assert pos == len(raw)
+    return out
+
+
+def compress(records):
+    """what a fixture holds of a list of records: every length; short records (counts, state scalars, chain tables, taps) whole;
+    the last TAIL values of the last long record and the last 16 of the long ones before it"""
+    records = [np.asarray(r, dtype=np.float64) for r in records]
+    big = [i for i, r in enumerate(records) if len(r) > 160]
+    parts = []
+    for i, r in enumerate(records):
+        k = len(r) if len(r) <= 160 else (TAIL if i == big[-1] else 16)
+        parts += [np.array([len(r), k], dtype=np.float64), r[len(r) - k:]]
+    return np.concatenate(parts) if parts else np.zeros(0)
+
+
+def expand(flat):
+    """fixture -> [(full length, tail)]"""
+    out, pos = [], 0
+    while pos < len(flat):
+        n, k = int(flat[pos]), int(flat[pos + 1])
+        out.append((n, flat[pos + 2:pos + 2 + k]))
+        pos += 2 + k
+    return out
+
+
+def record_error(kind, got, want):
+    """-> the error of one record in the unit of its kind (0.0 when identical)"""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    if got.size == 0 or np.array_equal(got, want):
+        return 0.0
+    if kind == "d":
+        return float(np.abs(got - want).max())
+    den = float(np.sqrt(np.mean(want ** 2)))
+    num = float(np.sqrt(np.mean((got - want) ** 2)))
+    return num / den if den > 0 else float("inf")
+
+
+class Case:
+    def __init__(self, name, stage, args, make_input, oracle, bar=0.0, bar_db=0.0):
+        self.name, self.stage, self.args, self.make_input, self.oracle = name, stage, list(args), make_input, oracle
+        self.bar, self.bar_db = bar, bar_db
+        assert bar <= MAX_BAR and bar_db <= MAX_BAR_DB
+
+    @property
+    def fixture(self):
+        return os.path.join(GOLD, "refpin_%s.npy" % self.name)
+
+    def reference(self, x):
+        return run_driver(self.stage, x, self.args)
+
+    def allowed(self, kind):
+        return 0.0 if kind == "x" else (self.bar_db if kind == "d" else self.bar)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# inputs (seeds and tones written here; regenerated, never stored)
+# ---------------------------------------------------------------------------------------------------------------
+def _wide(fs, n, seed):
+    return tones(fs, n, [(0.3, 0.0586 * fs), (0.1, -0.146 * fs), (0.05, 0.0012 * fs)]) + lcg_noise(n, seed, 1e-3)
+
+
+def _audio(fs, n, seed):
+    return tones(fs, n, [(0.3, 1000.0), (0.2, -2200.0), (0.1, 4500.0), (0.05, 12000.0)]) + lcg_noise(n, seed, 1e-2)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# oracle counterparts: each returns [(kind, array)] in the driver's record order
+# ---------------------------------------------------------------------------------------------------------------
+def _mixer(fs, n, f0, retune=None):
+    def run(O, x):
+        m = O.Mixer(fs)
+        m.set_frequency(f0)
+        out = []
+        for f in range(len(x) // n):
+            if retune and f == retune[0]:
+                m.set_frequency(retune[1])
+            out.append(("v", _il(m.process(x[f * n:(f + 1) * n]))))
+        return out
+    return run
+
+
+def _decimator(fs, bw, n):
+    def run(O, x):
+        d = O.Decimator(fs, bw)
+        out = [("x", np.array([d.rate])), ("x", np.array([float(d.dec_by2_stages)])),
+               ("x", np.array([v for c in d.chain() for v in c], dtype=np.float64))]
+        for f in range(len(x) // n):
+            out.append(("v", _il(d.process(x[f * n:(f + 1) * n]))))
+        return out
+    return run
+
+
+def _downconvert(fs, bw, simple, calls):
+    def run(O, x):
+        d = O.DownConvert()
+        out = [("x", np.array([d.set_data_rate(fs, bw, simple)]))]
+        pos, prev = 0, None
+        for ln, f, cw in calls:
+            if prev != (f, cw):
+                d.set_cw_offset(cw)
+                d.set_frequency(f)
+            prev = (f, cw)
+            out.append(("v", _il(d.process(x[pos:pos + ln]))))
+            pos += ln
+        return out
+    return run
+
+
+def _fastfir(lo, hi, fs, n):
+    def run(O, x):
+        f = O.FastFIR(2048, 1025)
+        f.setup(lo, hi, 0.0, fs)
+        out = [("v", _il(f.coef()))]
+        for b in range(len(x) // n):
+            out.append(("v", _il(f.process(x[b * n:(b + 1) * n]))))
+        return out
+    return run
+
+
+def _fir(ntaps, scale, astop, fpass, fstop, fs):
+    def run(O, x):
+        f = O.Fir()
+        nt = f.init_lp(ntaps, scale, astop, fpass, fstop, fs)
+        return [("x", np.array([float(nt)])), ("v", f.taps()), ("v", _il(f.process(x)))]
+    return run
+
+
+def _iir(kind, f0, q, fs, n=None):
+    def run(O, x):
+        f = O.Iir(kind, f0, q, fs)
+        if n is None:
+            return [("v", np.array(f.coeffs())), ("v", _il(f.process(x)))]
+        return [("v", _il(f.process(x[b * n:(b + 1) * n]))) for b in range(len(x) // n)]
+    return run
+
+
+def _resampler(maxin, rate, n):
+    def run(O, x):
+        r = O.Resampler(maxin)
+        out = []
+        for f in range(len(x) // n):
+            out.append(("v", _il(r.process(x[f * n:(f + 1) * n], rate))))
+            out.append(("v", np.array([r.float_time])))
+        return out
+    return run
+
+
+def _spectrum(bins, spb, lens):
+    def run(O, x):
+        s = O.Spectrum(bins, spb)
+        out, pos = [], 0
+        for ln in lens:
+            out.append(("d", s.process(x[pos:pos + ln])))
+            out.append(("x", np.array([float(s.overload)])))
+            pos += ln
+        return out
+    return run
+
+
+def _agc(fs, n, plan):
+    def run(O, x):
+        a = O.Agc(fs)
+        out, prev = [], None
+        for b, mt in enumerate(plan):
+            if mt != prev:
+                a.set_mode(*mt)
+            prev = mt
+            out.append(("v", _il(a.process(x[b * n:(b + 1) * n]))))
+        return out
+    return run
+
+
+def _nb(which, n, plan):
+    def run(O, x):
+        nb = O.NoiseBlanker()
+        out, prev = [], 0
+        for b, on in enumerate(plan):
+            if on and not prev:
+                nb.enable(which)
+            prev = on
+            blk = x[b * n:(b + 1) * n]
+            out.append(("v", _il(nb.process(blk, which) if on else blk)))  # disabled: the reference hands its input back
+        return out
+    return run
+
+
+def _anf(n):
+    def run(O, x):
+        a = O.Anf()
+        return [("v", _il(a.process(x[b * n:(b + 1) * n]))) for b in range(len(x) // n)]
+    return run
+
+
+def _iqbalance(n, gain, phase):
+    def run(O, x):
+        return [("v", _il(O.iq_balance(x[b * n:(b + 1) * n], gain, phase))) for b in range(len(x) // n)]
+    return run
+
+
+def _fdestimate(rate, mixer, bands):
+    def run(O, sp):
+        out = []
+        for lo, hi in bands:
+            v = O.fd_estimate(sp, rate, lo, hi, mixer)
+            out.append(("v", np.array([v[0], v[1], v[2], v[3], v[1]])))
+        return out
+    return run
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the table of cases
+# ---------------------------------------------------------------------------------------------------------------
+def _levels(fs, n, nblocks, seed):
+    """AGC input over about 2 s (the modes differ by decay constants of 100 ms .. 2 s, so nothing shorter tells them apart): a tone
+    whose level starts in silence, steps to between the two knees (0.0316 and 0.1 for thresholds 30 and 20), under both, up by 30 dB
+    (attack; the peak-window rescan runs at every step down), is held for a second so that the decay average charges (its rise takes
+    0.3 of the mode's decay time), then drops by 9.5 dB to a level above both knees, where the decay average alone sets the gain until
+    the end: the tail a fixture keeps lies there."""
+    m = n * nblocks
+    t = np.arange(m) / float(fs)
+    env = np.full(m, 0.2)
+    for t0, t1, v in ((0.0, 0.05, 0.001), (0.05, 0.15, 0.06), (0.15, 0.25, 0.02), (0.25, 1.25, 0.6)):
+        env[(t >= t0) & (t < t1)] = v
+    return env * tones(fs, m, [(1.0, 1000.0), (0.1, -2200.0)]) + lcg_noise(m, seed, 1e-3)
+
+
+def _spiky(fs, n, seed):
+    x = tones(fs, n, [(0.05, 101e3), (0.02, -250e3)]) + lcg_noise(n, seed, 1e-3) + 0.01
+    x[5000 % n] += 2.0
+    x[3000:3003] += 1.5j
+    x[n - 1000] -= 3.0
+    return x
+
+
+def _toggled(fs, n, seed):
+    """three blocks for a blanker that is on, off, on: the level drops to a quarter for the third block, and 150 samples before its end
+    comes a spike of 0.19.  The average a blanker keeps has a time constant of 1000 samples: restarted from zero by the setter it
+    stands near 0.043 there (the spike is over 3.3 times that and is blanked), carried over from the first block it would stand near
+    0.072 (the spike would pass).  So the reset shows in the last 256 samples, the part of the output a fixture keeps."""
+    x = tones(fs, 3 * n, [(1.0, 101e3)]) * np.repeat([0.2, 0.2, 0.05], n) + lcg_noise(3 * n, seed, 1e-3) + 0.001
+    x[3 * n - 150] = 0.19
+    return x
+
+
+def _spectrum_input(n, seed, hot_frame=None, spb=2048):
+    x = tones(2048000, n, [(10 ** (-10 / 20) * 0.9, 0.2305 * 2048000), (0.01, 0.4871 * 2048000), (0.003, -0.31 * 2048000)]) \
+        + lcg_noise(n, seed, 1e-3)
+    if hot_frame is not None:
+        x[hot_frame * spb + 17] = 0.95 + 0.1j  # one sample over the 0.9 overload limit
+    return x
+
+
+def _dc_calls(D, f0, fs):
+    # the call lengths of the device test, quartered where the first stage is a generic halfband: the reference copies a call
+    # into a buffer of 32768 samples there (downconvert.cpp:60,345) and writes past it on a longer one
+    q = 4 if D == 64 else 1
+    lens = [D * 600 // q, D * 256 // q, D * 1024 // q, D * 300 // q]
+    return [(lens[0], f0, 0.0), (lens[1], f0, 0.0), (lens[2], f0 + 0.01 * fs / D, 700.0), (lens[3], 0.0, 0.0)]
+
+
+def _dc_input(fs, D, f0, n):
+    return tones(fs, n, [(0.3, f0 + 0.02 * fs / D), (0.2, f0 - 0.05 * fs / D), (0.3, f0 + 0.37 * fs), (0.1, 0.013 * fs / D)]) \
+        + lcg_noise(n, 4, 1e-3)
+
+
+def _build_cases():
+    C = []
+    fs, n = 2048000, 2048
+    # Mixer::processBlock
+    C.append(Case("mixer_100k", "mixer", [fs, n, 100e3], lambda: _wide(fs, 4 * n, 11), _mixer(fs, n, 100e3)))
+    C.append(Case("mixer_retune", "mixer", [fs, n, 100e3, 2, -250e3], lambda: _wide(fs, 4 * n, 12), _mixer(fs, n, 100e3, (2, -250e3))))
+    C.append(Case("mixer_zero", "mixer", [fs, n, 0.0], lambda: _wide(fs, 2 * n, 13), _mixer(fs, n, 0.0)))
+    # Decimator: chain builder and cascade (vDSP path, combined stages), then once through HalfbandFilter::process
+    for dfs, bw, dn, frames in ((2048000, 30000, 2048, 4), (2048000, 200000, 2048, 4), (20000000, 200000, 2048, 4),
+                                (100000000, 30000, 49152, 2), (100000000, 30000, 2048, 1), (20000000, 30000, 2048, 1)):
+        C.append(Case("decimator_%d_%d_%d" % (dfs, bw, dn), "decimator", [dfs, bw, dn, 0],
+                      lambda dfs=dfs, dn=dn, frames=frames: _wide(dfs, frames * dn, 21), _decimator(dfs, bw, dn)))
+    C.append(Case("decimator_plain_2048000_30000", "decimator", [2048000, 30000, 2048, 1], lambda: _wide(2048000, 4 * 2048, 21),
+                  _decimator(2048000, 30000, 2048)))
+    # CDownConvert: the four cases of test_downconvert_step_against_the_oracle
+    for dfs, bw, simple, stages in ((2048000.0, 15000.0, False, 5), (10e6, 15000.0, False, 7), (20e6, 200000.0, True, 6), (250000.0, 48000.0, False, 0)):
+        D, f0 = 1 << stages, 0.11 * dfs
+        calls = _dc_calls(D, f0, dfs)
+        C.append(Case("downconvert_%d_%d" % (dfs, bw), "downconvert", [dfs, bw, int(simple)] + [v for c in calls for v in c],
+                      lambda dfs=dfs, D=D, f0=f0, calls=calls: _dc_input(dfs, D, f0, sum(c[0] for c in calls)),
+                      _downconvert(dfs, bw, simple, calls)))
+    # CFastFIR 2048/1025 at 64 kHz: H and three blocks
+    for lo, hi in ((300, 3000), (-5000, 5000), (-3000, -300), (1000, 1500)):
+        C.append(Case("fastfir_%d_%d" % (lo, hi), "fastfir", [lo, hi, 0, 64000, 2048], lambda: _audio(64000, 3 * 2048, 31),
+                      _fastfir(float(lo), float(hi), 64000.0, 2048)))
+    # CFir Kaiser low-pass (the demodulators' audio filters) and CIir LP / HP
+    for nm, a in (("am10k_64k", (0, 1.0, 50.0, 10000.0, 10000.0 * 1.8, 64000.0)), ("nfm_64k", (0, 1.0, 50.0, 3000.0, 1.6 * 3000.0, 64000.0)),
+                  ("sam_64k", (0, 1.0, 40.0, 4500.0, 5500.0, 64000.0)), ("wfm_256k", (0, 1.0, 60.0, 15000.0, 21000.0, 256000.0)),
+                  ("wfm_312k5", (0, 1.0, 60.0, 15000.0, 21000.0, 312500.0))):
+        C.append(Case("fir_" + nm, "fir", a, lambda a=a: _audio(a[5], 4096, 41), _fir(*a)))
+    for nm, kind, a in (("lp_15k_256k", "lp", (15000.0, 0.7071, 256000.0)), ("hp_10_64k", "hp", (10.0, 0.7071, 64000.0)),
+                        ("lp_15k_312k5", "lp", (15000.0, 0.7071, 312500.0))):
+        C.append(Case("iir_" + nm, "iir", [0 if kind == "lp" else 1] + list(a), lambda a=a: _audio(a[2], 4096, 42) + 0.01, _iir(kind, *a)))
+    # CFractResampler (complex)
+    for out_rate in (11025, 48000):
+        C.append(Case("resampler_%d" % out_rate, "resampler", [4096, 64000.0 / out_rate, 2048], lambda: _audio(64000, 6 * 2048, 51),
+                      _resampler(4096, 64000.0 / out_rate, 2048)))
+    # FFT::fftParams / fftSpectrum with the Blackman-Harris window
+    for bins in (2048, 4096, 8192):
+        C.append(Case("spectrum_%d" % bins, "spectrum", [bins, 2048, 2048000, 0, 2048, 2048, 2048], lambda: _spectrum_input(3 * 2048, 61),
+                      _spectrum(bins, 2048, [2048] * 3)))
+    C.append(Case("spectrum_short_buffer", "spectrum", [4096, 2048, 2048000, 0, 2048, 1500, 2048], lambda: _spectrum_input(2048 + 1500 + 2048, 62),
+                  _spectrum(4096, 2048, [2048, 1500, 2048])))
+    C.append(Case("spectrum_overload_then_short", "spectrum", [2048, 2048, 2048000, 0, 2048, 2048, 1000, 2048],
+                  lambda: _spectrum_input(3 * 2048 + 1000, 63, hot_frame=1), _spectrum(2048, 2048, [2048, 2048, 1000, 2048])))
+    C.append(Case("spectrum_ooura_4096", "spectrum", [4096, 2048, 2048000, 1, 2048, 2048, 2048], lambda: _spectrum_input(3 * 2048, 61),
+                  _spectrum(4096, 2048, [2048] * 3), bar_db=OOURA_BAR_DB))
+    # AGC: five modes x two thresholds x two rates over 16 blocks of 8192 (2 s at 64 kHz); a change of mode and threshold between blocks,
+    # just behind the drop, so that the new decay constant and the new knee both show in what follows
+    an, ab = 8192, 16
+    for afs in (64000, 48828):
+        for mode, mname in ((0, "off"), (1, "fast"), (2, "med"), (3, "slow"), (4, "long")):
+            for thr in (20, 30):
+                plan = [(mode, thr)] * ab
+                C.append(Case("agc_%s_%d_%d" % (mname, thr, afs), "agc", [afs, an] + [v for p in plan for v in p],
+                              lambda afs=afs: _levels(afs, an, ab, 71), _agc(afs, an, plan)))
+    plan = [(2, 30)] * 10 + [(3, 20)] * 6
+    C.append(Case("agc_med_to_slow", "agc", [64000, an] + [v for p in plan for v in p], lambda: _levels(64000, an, ab, 72), _agc(64000, an, plan)))
+    # conditioners: spikes and a DC offset, 3 blocks with state carried; each blanker disabled then enabled again
+    bn = 8192
+    for which in (1, 2):
+        C.append(Case("nb%d" % which, "nb", [which, fs, bn, 1, 1, 1], lambda: _spiky(fs, 3 * bn, 81), _nb(which, bn, [1, 1, 1])))
+        C.append(Case("nb%d_off_on" % which, "nb", [which, fs, 2048, 1, 0, 1], lambda: _toggled(fs, 2048, 82), _nb(which, 2048, [1, 0, 1])))
+    C.append(Case("anf", "anf", [64000, 2048], lambda: tones(64000, 3 * 2048, [(0.05, 1000.0), (0.03, 2200.0)]) + lcg_noise(3 * 2048, 5, 1e-2),
+                  _anf(2048)))
+    C.append(Case("iqbalance", "iqbalance", [fs, bn, 1.02, 0.03], lambda: _spiky(fs, 3 * bn, 83), _iqbalance(bn, 1.02, 0.03)))
+    for dfs in (2048000, 20000000):
+        C.append(Case("dcremoval_%d" % dfs, "dcremoval", [dfs, bn], lambda dfs=dfs: _spiky(dfs, 3 * bn, 84),
+                      _iir("hp", 10.0, 0.7071, float(dfs), n=bn)))
+    # SignalStrength::fdEstimate: two bands over one spectrum
+    bands = [(-4000.0, 4000.0), (300.0, 3000.0)]
+    C.append(Case("fdestimate", "fdestimate", [2048000, 2048, 2048000, 100000.0] + [v for b in bands for v in b], _fd_spectrum,
+                  _fdestimate(2048000, 100000.0, bands)))
+    return C
+
+
+def _fd_spectrum():
+    """a dB spectrum of 4096 bins: a ragged floor near -100 dB and a ragged plateau around the mixer's bin"""
+    from tests.signals import lcg_uniform
+    u = lcg_uniform(4096, 91)
+    sp = -100.0 + 6.0 * u
+    sp[2248 - 3:2248 + 4] = -30.0 - 3.0 * u[:7]
+    return sp
+
+
+# Every stage comes out bit for bit against the reference binary and is asserted equal (bar 0).  The one bar is for the cross-check
+# of the spectrum through the reference's in-tree Ooura transform, a different FFT: measured 1.01e-10 dB on the CPU, times ten.
+OOURA_BAR_DB = 1.1e-9
+
+CASES = None
+
+
+def cases():
+    global CASES
+    if CASES is None:
+        CASES = _build_cases()
+    return CASES
+
+
+def chains_table():
+    return json.load(open(os.path.join(GOLD, "chains.json")))

@@ -6,7 +6,8 @@ The reference has no test suite and no golden files.  What
       (SURVEY.md section 10): chain tables, stage counts, tap counts, oscillator fixed point, FastFIR gain;
   (3) closed forms and independent implementations (numpy.fft, scipy.signal) for everything else.
 Stages pinned only by (3) say "parity unpinned" below: they are checked for self-consistency, not against
-reference output.
+reference output.  Since then tests/test_reference_pins.py compares the time-domain stages with the reference's own
+code, compiled with stand-ins; the docstrings below point at its cases.
 """
 import json
 import os
@@ -75,7 +76,7 @@ def test_decimator_is_frame_invariant(oracle_mod):
 
 
 def test_decimator_matches_scipy_polyphase(oracle_mod):
-    """parity unpinned (no reference vector): each halfband stage is y[n] = sum_p x[nS+p-(T-1)] h[p]; check the
+    """(parity with the reference binary: tests/test_reference_pins.py, decimator_*)  Each halfband stage is y[n] = sum_p x[nS+p-(T-1)] h[p]; check the
     cascade against scipy.signal.lfilter + slicing in fp64."""
     O = oracle_mod
     import re
@@ -151,7 +152,7 @@ def test_fastfir_known_answers(oracle_mod):
 
 
 def test_fastfir_equals_direct_convolution(oracle_mod):
-    """parity unpinned beyond the known answers: overlap-save must equal y[n] = sum_k h[k] x[n-k] with h = IFFT(H)*N... i.e.
+    """(parity with the reference binary: tests/test_reference_pins.py, fastfir_*)  Overlap-save must equal y[n] = sum_k h[k] x[n-k] with h = IFFT(H)*N... i.e.
     the designed taps; checked with scipy in fp64."""
     O = oracle_mod
     f = O.FastFIR()
@@ -179,7 +180,8 @@ def test_cfir_tap_counts_match_survey(oracle_mod):
 
 
 def test_cfir_and_ciir_match_scipy(oracle_mod):
-    """parity unpinned: CFir's circular delay line and CIir's DF2 against scipy.signal.lfilter."""
+    """(parity with the reference binary: tests/test_reference_pins.py, fir_* and iir_*)  CFir's circular delay line and CIir's DF2
+    against scipy.signal.lfilter."""
     O = oracle_mod
     x = lcg_noise(5000, 5, 1.0)
     f = O.Fir()
@@ -565,7 +567,7 @@ def test_downconvert_stage_limits_are_the_reference_comments(oracle_mod):
 
 
 def test_downconvert_against_independent_filters(oracle_mod):
-    """parity unpinned (the reference holds no vector for CDownConvert): the restatement against an independent model -- the
+    """(parity with the reference binary: tests/test_reference_pins.py, downconvert_*)  The restatement against an independent model -- the
     oscillator in closed form (a_0 = 1, a_{n+1} = a_n (1.95 - a_n^2), phase (n + 1) inc: the recurrence of downconvert.cpp:288-293
     started from m_Osc1 = 1), every stage as a plain convolution at stride 2: the CIC3 as (1 3 3 1) / 8 ending on the pair's ODD sample
     (:524-526), the fixed 11-tap class with its table as it stands (:429-489), the generic class with tap 0 counted twice

@@ -576,6 +576,40 @@ def test_spectrum_step_with_fewer_samples_than_the_buffer(gpu_lib, oracle_mod, n
             sp.fftSpectrum(x[:nf])  # the same object with a whole buffer: refused, loudly
 
 
+def test_spectrum_step_overload_flag_is_a_member_that_whole_buffers_rewrite(gpu_lib, oracle_mod):
+    """FFT::m_isOverload is cleared and set on the whole-buffer branch of m_applyWindow only (fft.cpp:133-140); a shorter call tests
+    nothing and returns the member as it stands (pinned to the reference binary by tests/test_reference_pins.py, case
+    spectrum_overload_then_short).  An object that only ever sees short calls therefore never reports an overload."""
+    import pebblesdr_amd as P
+    hot = np.full(1500, 0.95 + 0j)
+    ref = oracle_mod.Spectrum(2048, 2048)
+    sp = P.Spectrum(2048, 2.048e6, 2048)
+    for _ in range(2):
+        ref.process(hot)
+        _, ov = sp.fftSpectrum(hot)
+        assert ov == ref.overload == False  # noqa: E712
+    whole = P.Spectrum(2048, 2.048e6, 2048)
+    ref = oracle_mod.Spectrum(2048, 2048)
+    for fr, want in ((np.full(2048, 0.95 + 0j), True), (np.full(2048, 0.5 + 0j), False)):
+        ref.process(fr)
+        _, ov = whole.fftSpectrum(fr)
+        assert ov == ref.overload == want
+    with pytest.raises(P.PebbleGpuError):
+        whole.fftSpectrum(hot)  # refused (an object of whole buffers): the member stays as the last whole buffer left it
+    ref.process(np.full(2048, 0.5 + 0j))
+    _, ov = whole.fftSpectrum(np.full(2048, 0.5 + 0j))
+    assert ov == ref.overload == False  # noqa: E712
+    # 4096-sample buffers into 8192 bins go through the general kernel, which takes whole and shorter calls on one object: the
+    # sequence of the reference pin -- a hot whole buffer, then a short call that keeps True, a cool whole one, a hot short one
+    ref = oracle_mod.Spectrum(8192, 4096)
+    sp = P.Spectrum(8192, 2.048e6, 4096)
+    for fr, want in ((np.full(4096, 0.95 + 0j), True), (np.full(1000, 0.5 + 0j), True), (np.full(4096, 0.5 + 0j), False),
+                     (np.full(1000, 0.95 + 0j), False)):
+        ref.process(fr)
+        _, ov = sp.fftSpectrum(fr)
+        assert ov == ref.overload == want
+
+
 def test_receiver_with_4096_sample_frames(gpu_lib, oracle_mod):
     """A receiver created with framesPerBuffer = 4096 (settings.cpp:57): the display transform of every 4096-sample frame at 8192
     bins and the AM chain, against an oracle receiver of the same frame length."""
@@ -2360,8 +2394,8 @@ def test_downconvert_step_against_the_oracle(gpu_lib, oracle_mod, fs, bw, simple
     restatement -- the quadrature oscillator with its amplitude transient and its phase carried across calls AND across a retune
     (SetFrequency keeps m_Osc1; there is no "frequency 0" exit), the CIC3 ending on the pair's odd sample, the fixed 11-tap
     halfband, the generic halfband with tap 0 counted twice -- four calls of unequal length (the first inside the transient), a retune
-    and a CW offset before the third, frequency 0 for the fourth.  Oracle: parity unpinned (tests/test_oracle_pins.py pins its stage
-    limits to the reference's comments and checks it against an independent model)."""
+    and a CW offset before the third, frequency 0 for the fourth.  Oracle: held to the reference's own CDownConvert on these four
+    chains by tests/test_reference_pins.py (downconvert_*); tests/test_oracle_pins.py pins its stage limits to the reference's comments."""
     import pebblesdr_amd as P
     D = 1 << len(chain)
     lens = [D * 600, D * 256, D * 1024, D * 300]
