@@ -496,6 +496,85 @@ int pebblegpu_process_iq_updates(pebblegpu_receiver *rx, const double *iq, uint1
                                  uint32_t *n_audio, double *spectrum_db, uint32_t *spectrum_updated);
 
 /* ------------------------------------------------------------------------------------------------
+ * Multibank: ONE process and ONE consumer thread drive a bank whose channels are sharded across several devices (what a host
+ * behind the reference's plugin surface is: Receiver::turnPowerOn builds one chain, application/receiver.cpp:116-281, and
+ * processIQData is called from one thread).  Shard g of G owns the global channels [g*C/G, (g+1)*C/G) in integer arithmetic
+ * (4096 over 8: 512 each; 5 over 2: [0,2) and [2,5)); pebblegpu_multibank_plan is that rule, on the host, no device needed.
+ * Each shard is an ordinary pebblegpu_receiver created on device_ids[g] with the caller's configuration and the shard's channel
+ * count (cfg->n_channels is the total C, cfg->device is ignored; with shared_input = 0 the streams are split by the same ranges), so
+ * every sample goes through exactly the kernels a single-device bank runs, and nothing is exchanged between devices.
+ *   - A device may appear more than once in device_ids: {0, 0} is two shards on one device.  That is a TEST RIG for machines with
+ *     one GPU -- two shards on one device share it and run slower than one bank of the same channels -- not a configuration to run.
+ *   - PEBBLEGPU_MULTIBANK_SPECTRUM_SHARD0: shards 1.. are created with spectrum_bins = hires_bins = 0 (with a shared stream every
+ *     shard's display transform would compute the same rows).  What reads the spectrum (S-meter, squelch) then works on shard 0 and
+ *     is refused on the others exactly as on a single bank without one.  Without the flag every shard has its spectrum.
+ *   - Setters and read-outs are not duplicated: pebblegpu_multibank_shard hands out the shard's receiver handle, BORROWED, and every
+ *     pebblegpu_set_* and pebblegpu_receiver_* read-out works on (rx, channel - first_channel); pebblegpu_multibank_locate does the
+ *     arithmetic.  As on a single receiver, setters may be called from another thread and take effect at the next call.  A borrowed
+ *     handle must NOT be passed to pebblegpu_receiver_destroy, nor to any process / ingest entry point (pebblegpu_receiver_process,
+ *     _process_raw, _ingest_acquire, _ingest_submit, _process_ingested, pebblegpu_process_iq, _process_iq_updates): those belong to
+ *     the multibank; it is valid until pebblegpu_multibank_destroy.  Outputs stay sharded: each shard's audio is on its device.
+ *   - create checks its arguments before any device is touched (PEBBLEGPU_E_INVALID: a null pointer, a struct_size mismatch,
+ *     n_shards 0 or above PEBBLEGPU_MULTIBANK_MAX_SHARDS, n_channels < n_shards, unknown flag bits), then probes the devices
+ *     (PEBBLEGPU_E_NO_DEVICE with none, PEBBLEGPU_E_INVALID for an ordinal out of range).
+ *   - Every shard has a persistent host worker thread (created by create, joined by destroy -- hence the cap of 16: a node has 8
+ *     devices).  A process call posts its job to all workers and returns when ALL HAVE QUEUED their shard's call, not when the
+ *     calls have run: the ASYNCHRONY rules above hold unchanged, with pebblegpu_multibank_synchronize in the place of
+ *     pebblegpu_receiver_synchronize.  Process calls are single-caller per multibank handle.
+ *   - The common checks are made once, before any worker is asked -- null pointers, the state of an ingest slot, n_samples a whole
+ *     number of super-frames (PEBBLEGPU_E_SIZE) and at most max_superframes -- and a refusal there leaves every shard untouched and
+ *     the handle usable.  A failing shard's error text is carried to the calling thread's pebblegpu_last_error() and the call
+ *     returns the first failing shard's code.  If a shard refuses or fails AFTER others have queued, the shards' streams no longer
+ *     agree: the multibank is failed, later process calls return PEBBLEGPU_E_HIP with a text that says so, and only
+ *     pebblegpu_multibank_synchronize and _destroy (and the read-outs of the shards) still work.
+ *   - destroy waits for every shard's queued work, stops the workers, then destroys the shards; it may be called right behind a
+ *     queued call.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct pebblegpu_multibank pebblegpu_multibank;
+#define PEBBLEGPU_MULTIBANK_MAX_SHARDS 16
+#define PEBBLEGPU_MULTIBANK_SPECTRUM_SHARD0 1u   /* flags bit 0 */
+/* first[g], count[g] for g < n_shards: contiguous, covering [0, n_channels), none empty.  PEBBLEGPU_E_INVALID: a null pointer,
+ * n_shards 0 or above 16, n_channels < n_shards. */
+int pebblegpu_multibank_plan(uint32_t n_channels, uint32_t n_shards, uint32_t *first, uint32_t *count);
+int pebblegpu_multibank_create(const pebblegpu_config *cfg, const int32_t *device_ids, uint32_t n_shards,
+                               uint32_t flags, pebblegpu_multibank **out);
+int pebblegpu_multibank_destroy(pebblegpu_multibank *mb);
+int pebblegpu_multibank_shards(const pebblegpu_multibank *mb, uint32_t *n_shards);
+/* shard g: a BORROWED receiver handle (see above), its device, its first global channel and its channel count; any of the four
+ * output pointers may be NULL */
+int pebblegpu_multibank_shard(pebblegpu_multibank *mb, uint32_t g, pebblegpu_receiver **rx, int32_t *device,
+                              uint32_t *first_channel, uint32_t *n_channels);
+/* global channel -> (shard, channel within the shard); PEBBLEGPU_E_INVALID for a channel out of range */
+int pebblegpu_multibank_locate(const pebblegpu_multibank *mb, uint32_t channel, uint32_t *shard, uint32_t *local_channel);
+/* Device-resident input: d_iq / d_raw is an array of n_shards device pointers; entry g is resident on shard g's device and holds what
+ * that shard reads, as pebblegpu_receiver_process / _process_raw take it -- the whole stream for a shared stream (with {0, 0} both
+ * entries may be the same pointer), the shard's rows [stream][time] for independent streams.  A host that keeps its samples on one
+ * device distributes them itself.  The inputs are never modified and may be overwritten after pebblegpu_multibank_synchronize. */
+int pebblegpu_multibank_process(pebblegpu_multibank *mb, const void *const *d_iq, uint64_t n_samples);
+int pebblegpu_multibank_process_raw(pebblegpu_multibank *mb, int format, int iq_order, double gain,
+                                    const void *const *d_raw, uint64_t n_samples);
+/* Host ingest, the path a one-process host really has (samples arrive from a radio in host memory): two pinned slots owned by the
+ * multibank, readable by every device, with the contract of pebblegpu_receiver_ingest_* above.
+ *   acquire  -- blocks until every shard's last call that read the slot's device twin is over, then hands out the slot's buffer;
+ *   submit   -- queues one upload per shard, on that shard's copy stream, into that shard's device twin: all `bytes` for a shared
+ *               stream; for independent streams the buffer is [stream][time] in n_channels equal rows and each shard is sent its
+ *               rows only (bytes must then be n_channels * n_samples pairs exactly);
+ *   process_ingested -- pebblegpu_receiver_process_raw per shard on its twin, ordered behind that shard's upload on the device, no
+ *               host synchronisation.  Refused, with every shard untouched: a slot nothing was submitted to or too small for the
+ *               format (PEBBLEGPU_E_SIZE), a slot whose samples have been processed and that has not been acquired since
+ *               (PEBBLEGPU_E_INVALID).
+ * Copies from host memory per shard, not peer copies from an ingest device: the same code runs on one device and on eight, it
+ * depends on no peer-access state, and the traffic is small. */
+int pebblegpu_multibank_ingest_acquire(pebblegpu_multibank *mb, uint32_t slot, uint64_t bytes, void **host_ptr);
+int pebblegpu_multibank_ingest_submit(pebblegpu_multibank *mb, uint32_t slot, uint64_t bytes);
+int pebblegpu_multibank_process_ingested(pebblegpu_multibank *mb, uint32_t slot, int format, int iq_order,
+                                         double gain, uint64_t n_samples);
+/* waits until every call made on this handle has finished on every shard */
+int pebblegpu_multibank_synchronize(pebblegpu_multibank *mb);
+/* the maximum over the shards of pebblegpu_receiver_last_ms(rx, 0, ..): the slowest shard bounds the call */
+int pebblegpu_multibank_last_ms(const pebblegpu_multibank *mb, float *max_over_shards);
+
+/* ------------------------------------------------------------------------------------------------
  * Stream bank: S independent full-rate IQ streams, each through the overlap-save band-pass
  * (CFastFIR::ProcessData, pebblelib/fastfir.cpp:281-334, one filter per stream) and the display
  * transform (FFT::fftSpectrum, pebblelib/fft.cpp:317-374) at the stream rate -- the two transforms of

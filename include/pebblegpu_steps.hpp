@@ -687,6 +687,61 @@ private:
     size_t pxCap = 0;
 };
 
+// A bank whose channels are sharded across devices, driven by this one process and one consumer thread (pebblegpu_multibank_*): the
+// shape a Qt host needs to use more than one GPU.  Channels are global; the control slots are routed to
+// the shard that owns the channel.  The config's n_channels is the total, its device is ignored.
+class MultiBank {
+public:
+    MultiBank(const pebblegpu_config &config, const std::vector<int> &devices, uint32_t flags = 0)
+    {
+        std::vector<int32_t> ids(devices.begin(), devices.end());
+        pebblegpu_config cfg = config;
+        cfg.struct_size = sizeof(cfg);
+        status = report("multibank_create", pebblegpu_multibank_create(&cfg, ids.data(), (uint32_t)ids.size(), flags, &h));
+    }
+    ~MultiBank() { pebblegpu_multibank_destroy(h); }
+    MultiBank(const MultiBank &) = delete;
+    MultiBank &operator=(const MultiBank &) = delete;
+    uint32_t shards() const { uint32_t g = 0; if (h) pebblegpu_multibank_shards(h, &g); return g; }
+    // shard g's receiver handle, BORROWED: for every pebblegpu_set_* and pebblegpu_receiver_* read-out with channels local to the shard,
+    // never for pebblegpu_receiver_destroy or a process / ingest entry point
+    pebblegpu_receiver *shard(uint32_t g, int32_t *device = nullptr, uint32_t *firstChannel = nullptr, uint32_t *nChannels = nullptr)
+    {
+        pebblegpu_receiver *rx = nullptr;
+        if (h) status = report("multibank_shard", pebblegpu_multibank_shard(h, g, &rx, device, firstChannel, nChannels));
+        return rx;
+    }
+    void setMixer(uint32_t channel, double f) { uint32_t c; if (pebblegpu_receiver *rx = at(channel, &c)) status = report("set_mixer_freq", pebblegpu_set_mixer_freq(rx, c, f)); }
+    void setBandPass(uint32_t channel, double lo, double hi) { uint32_t c; if (pebblegpu_receiver *rx = at(channel, &c)) status = report("set_bandpass", pebblegpu_set_bandpass(rx, c, lo, hi)); }
+    void setDemodMode(uint32_t channel, DemodMode m) { uint32_t c; if (pebblegpu_receiver *rx = at(channel, &c)) status = report("set_demod_mode", pebblegpu_set_demod_mode(rx, c, (int)m)); }
+    // dIq[g]: float2 input on shard g's device; queue and return (results after synchronize())
+    int process(const std::vector<const void *> &dIq, uint64_t n) { return status = h && dIq.size() == shards() ? report("multibank_process", pebblegpu_multibank_process(h, dIq.data(), n)) : PEBBLEGPU_E_INVALID; }
+    int processRaw(int format, int iqOrder, double gain, const std::vector<const void *> &dRaw, uint64_t n)
+    {
+        return status = h && dRaw.size() == shards() ? report("multibank_process_raw", pebblegpu_multibank_process_raw(h, format, iqOrder, gain, dRaw.data(), n)) : PEBBLEGPU_E_INVALID;
+    }
+    // the pinned slots: acquire, fill, submit, processIngested, slot ^= 1
+    void *ingestAcquire(uint32_t slot, uint64_t bytes) { void *p = nullptr; if (h) status = report("multibank_ingest_acquire", pebblegpu_multibank_ingest_acquire(h, slot, bytes, &p)); return p; }
+    int ingestSubmit(uint32_t slot, uint64_t bytes) { return status = h ? report("multibank_ingest_submit", pebblegpu_multibank_ingest_submit(h, slot, bytes)) : PEBBLEGPU_E_INVALID; }
+    int processIngested(uint32_t slot, int format, int iqOrder, double gain, uint64_t n)
+    {
+        return status = h ? report("multibank_process_ingested", pebblegpu_multibank_process_ingested(h, slot, format, iqOrder, gain, n)) : PEBBLEGPU_E_INVALID;
+    }
+    int synchronize() { return status = h ? report("multibank_synchronize", pebblegpu_multibank_synchronize(h)) : PEBBLEGPU_E_INVALID; }
+    int lastStatus() const { return status; }
+    pebblegpu_multibank *handle() { return h; }
+
+private:
+    pebblegpu_receiver *at(uint32_t channel, uint32_t *local)
+    {
+        uint32_t g = 0;
+        if (!h || (status = report("multibank_locate", pebblegpu_multibank_locate(h, channel, &g, local))) != 0) return nullptr;
+        return shard(g);
+    }
+    pebblegpu_multibank *h = nullptr;
+    int status = 0;
+};
+
 // Qt-free stand-in for plugins/FileSDRDevice: reads a RIFF/WAVE IQ recording (16-bit PCM stereo, /32767 as
 // wavfile.cpp:299-300, or float32 stereo) and pumps framesPerBuffer-sized CPX frames into the callback the host bound
 // with initialize().  start() runs the whole file synchronously (the reference paces it in real time through

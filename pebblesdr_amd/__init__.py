@@ -12,6 +12,7 @@ from .binding import (  # noqa: F401
     SigGen, Sweep, sweep, sweep_plan, SWEEP_SINGLE, SWEEP_REPEAT, SWEEP_REPEAT_REVERSE,
     TAP_RAW_IQ, TAP_POST_MIXER, TAP_POST_BP, TAP_POST_DEMOD, TAP_MODEM,
     MorseStation, morse_station, morse_station_plan, morse_station_marks, MORSE_MAX_STATIONS,
+    MultiBank, multibank_plan, MULTIBANK_MAX_SHARDS, MULTIBANK_SPECTRUM_SHARD0,
 )
 from .steps import Mixer, Decimator, DownConvert, FastFIR, Demod, Spectrum, Morse  # noqa: F401
 
@@ -19,4 +20,5 @@ __all__ = [
     "PebbleGpuError", "load_library", "library_path", "ReceiverBank", "StreamBank", "DeviceBuffer", "ScreenMap", "screen_map",
     "Mixer", "Decimator", "DownConvert", "FastFIR", "Demod", "Spectrum", "Morse", "morse_token_to_dotdash",
     "SigGen", "Sweep", "sweep", "sweep_plan", "MorseStation", "morse_station", "morse_station_plan",
+    "MultiBank", "multibank_plan",
 ]

@@ -45,6 +45,9 @@ SYMBOLS = [
     "pebblegpu_siggen_create", "pebblegpu_siggen_destroy", "pebblegpu_siggen_set_sweep", "pebblegpu_siggen_set_noise", "pebblegpu_siggen_set_stream",
     "pebblegpu_siggen_generate_device", "pebblegpu_siggen_synchronize", "pebblegpu_siggen_generate", "pebblegpu_siggen_noise_draws",
     "pebblegpu_morse_station_plan", "pebblegpu_morse_station_marks", "pebblegpu_set_testbench_morse", "pebblegpu_siggen_set_morse",
+    "pebblegpu_multibank_plan", "pebblegpu_multibank_create", "pebblegpu_multibank_destroy", "pebblegpu_multibank_shards", "pebblegpu_multibank_shard",
+    "pebblegpu_multibank_locate", "pebblegpu_multibank_process", "pebblegpu_multibank_process_raw", "pebblegpu_multibank_ingest_acquire",
+    "pebblegpu_multibank_ingest_submit", "pebblegpu_multibank_process_ingested", "pebblegpu_multibank_synchronize", "pebblegpu_multibank_last_ms",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
@@ -382,6 +385,20 @@ def _declare(L):
     L.pebblegpu_siggen_synchronize.argtypes = [vp]
     L.pebblegpu_siggen_generate.argtypes = [vp, dp, u32]
     L.pebblegpu_siggen_noise_draws.argtypes = [vp, u64, u32, vp, vp]
+    u32p, vpp = C.POINTER(u32), C.POINTER(vp)
+    L.pebblegpu_multibank_plan.argtypes = [u32, u32, u32p, u32p]
+    L.pebblegpu_multibank_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_int32), u32, u32, vpp]
+    L.pebblegpu_multibank_destroy.argtypes = [vp]
+    L.pebblegpu_multibank_shards.argtypes = [vp, u32p]
+    L.pebblegpu_multibank_shard.argtypes = [vp, u32, vpp, C.POINTER(C.c_int32), u32p, u32p]
+    L.pebblegpu_multibank_locate.argtypes = [vp, u32, u32p, u32p]
+    L.pebblegpu_multibank_process.argtypes = [vp, vpp, u64]
+    L.pebblegpu_multibank_process_raw.argtypes = [vp, i32, i32, dbl, vpp, u64]
+    L.pebblegpu_multibank_ingest_acquire.argtypes = [vp, u32, u64, vpp]
+    L.pebblegpu_multibank_ingest_submit.argtypes = [vp, u32, u64]
+    L.pebblegpu_multibank_process_ingested.argtypes = [vp, u32, i32, i32, dbl, u64]
+    L.pebblegpu_multibank_synchronize.argtypes = [vp]
+    L.pebblegpu_multibank_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     return L
 
 
@@ -499,6 +516,9 @@ class ReceiverBank:
         cfg.hires_bins = hires_bins
         self.h = C.c_void_p()
         check(self.L, self.L.pebblegpu_receiver_create(C.byref(cfg), C.byref(self.h)))
+        self._read_info(device, n_channels, frames_per_buffer)
+
+    def _read_info(self, device, n_channels, frames_per_buffer):
         self.device = device
         self.n_channels = n_channels
         self.nf = frames_per_buffer
@@ -513,9 +533,20 @@ class ReceiverBank:
     def chain(self):
         return [(int(self.info.stage_taps[i]), int(self.info.stage_stride[i])) for i in range(self.info.chain_len)]
 
+    @classmethod
+    def borrowed(cls, handle, device, n_channels, frames_per_buffer, lib=None):
+        """a view over a receiver handle somebody else owns (a MultiBank's shard): every setter and read-out, but close() leaves the handle alone"""
+        self = cls.__new__(cls)
+        self.L = lib or load_library()
+        self._borrowed = True
+        self.h = C.c_void_p(handle)
+        self._read_info(device, n_channels, frames_per_buffer)
+        return self
+
     def close(self):
         if getattr(self, "h", None) and self.h.value:
-            self.L.pebblegpu_receiver_destroy(self.h)
+            if not getattr(self, "_borrowed", False):
+                self.L.pebblegpu_receiver_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -982,3 +1013,158 @@ class StreamBank:
         finally:
             buf.free()
         return y, s
+
+
+MULTIBANK_MAX_SHARDS = 16       # PEBBLEGPU_MULTIBANK_MAX_SHARDS
+MULTIBANK_SPECTRUM_SHARD0 = 1   # PEBBLEGPU_MULTIBANK_SPECTRUM_SHARD0
+
+
+def multibank_plan(n_channels, n_shards, lib=None):
+    """pebblegpu_multibank_plan, on the host (no device): [(first, count)] -- shard g owns the channels [g*C/G, (g+1)*C/G)"""
+    L = lib or load_library()
+    first, count = (C.c_uint32 * MULTIBANK_MAX_SHARDS)(), (C.c_uint32 * MULTIBANK_MAX_SHARDS)()
+    check(L, L.pebblegpu_multibank_plan(int(n_channels), int(n_shards), first, count))
+    return [(int(first[g]), int(count[g])) for g in range(int(n_shards))]
+
+
+class MultiBank:
+    """A bank's channels sharded across devices, driven from this one process (pebblegpu_multibank_*).  device_ids may repeat a
+    device ([0, 0]: two shards on one GPU, a test rig).  Channels are global; shard(g) is a ReceiverBank view of shard g."""
+
+    def __init__(self, sample_rate, n_channels, device_ids, flags=0, shared_input=True, wfm=False, spectrum_bins=0,
+                 frames_per_buffer=2048, fastfir_fft=0, fastfir_taps=0, max_superframes=1, lib=None, audio_rate=0, hires_bins=0):
+        self.L = lib or load_library()
+        cfg = Config()
+        cfg.struct_size = C.sizeof(Config)
+        cfg.sample_rate = float(sample_rate)
+        cfg.frames_per_buffer = frames_per_buffer
+        cfg.n_channels = n_channels
+        cfg.shared_input = 1 if shared_input else 0
+        cfg.wfm = 1 if wfm else 0
+        cfg.spectrum_bins = spectrum_bins
+        cfg.fastfir_fft = fastfir_fft
+        cfg.fastfir_taps = fastfir_taps
+        cfg.max_superframes = max_superframes
+        cfg.audio_rate = audio_rate
+        cfg.hires_bins = hires_bins
+        ids = [int(d) for d in device_ids]
+        arr = (C.c_int32 * max(1, len(ids)))(*ids)
+        self.h = C.c_void_p()
+        check(self.L, self.L.pebblegpu_multibank_create(C.byref(cfg), arr, len(ids), int(flags), C.byref(self.h)))
+        self.n_channels, self.shared_input, self.nf = n_channels, bool(shared_input), frames_per_buffer
+        g = C.c_uint32()
+        check(self.L, self.L.pebblegpu_multibank_shards(self.h, C.byref(g)))
+        self.n_shards = int(g.value)
+        self.shards, self.ranges, self.devices = [], [], []
+        for k in range(self.n_shards):
+            rx, dev, first, cnt = C.c_void_p(), C.c_int32(), C.c_uint32(), C.c_uint32()
+            check(self.L, self.L.pebblegpu_multibank_shard(self.h, k, C.byref(rx), C.byref(dev), C.byref(first), C.byref(cnt)))
+            self.shards.append(ReceiverBank.borrowed(rx.value, int(dev.value), int(cnt.value), frames_per_buffer, self.L))
+            self.ranges.append((int(first.value), int(cnt.value)))
+            self.devices.append(int(dev.value))
+        self.superframe = self.shards[0].superframe
+        self.D = self.shards[0].D
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            for s in self.shards:
+                s.close()  # (views: they only forget the handle)
+            self.L.pebblegpu_multibank_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def shard(self, g):
+        """the ReceiverBank view of shard g (channels local to the shard; it does not own the handle)"""
+        return self.shards[g]
+
+    def locate(self, ch):
+        """global channel -> (shard, channel within the shard)"""
+        g, c = C.c_uint32(), C.c_uint32()
+        check(self.L, self.L.pebblegpu_multibank_locate(self.h, int(ch), C.byref(g), C.byref(c)))
+        return int(g.value), int(c.value)
+
+    def _at(self, ch):
+        g, c = self.locate(ch)
+        return self.shards[g], c
+
+    def set_mixer(self, ch, f):
+        s, c = self._at(ch)
+        s.set_mixer(c, f)
+
+    def set_bandpass(self, ch, lo, hi):
+        s, c = self._at(ch)
+        s.set_bandpass(c, lo, hi)
+
+    def set_mode(self, ch, mode):
+        s, c = self._at(ch)
+        s.set_mode(c, mode)
+
+    def set_morse(self, ch, on=True):
+        s, c = self._at(ch)
+        s.set_morse(c, on)
+
+    def morse_events(self, ch):
+        s, c = self._at(ch)
+        return s.morse_events(c)
+
+    def morse_status(self, ch):
+        s, c = self._at(ch)
+        return s.morse_status(c)
+
+    def _ptrs(self, dptrs):
+        assert len(dptrs) == self.n_shards, "one device pointer per shard"
+        return (C.c_void_p * self.n_shards)(*[C.c_void_p(int(p)) for p in dptrs])
+
+    def process_device(self, dptrs, n_samples):
+        """dptrs[g]: float2 input resident on shard g's device (the whole shared stream, or the shard's rows)"""
+        check(self.L, self.L.pebblegpu_multibank_process(self.h, self._ptrs(dptrs), int(n_samples)))
+
+    def process_raw_device(self, dptrs, n_samples, fmt, iq_order=0, gain=1.0):
+        check(self.L, self.L.pebblegpu_multibank_process_raw(self.h, int(fmt), int(iq_order), float(gain), self._ptrs(dptrs), int(n_samples)))
+
+    def ingest_buffer(self, slot, nbytes, dtype=np.int8):
+        """the multibank's pinned host slot as a numpy array: [n] pairs of a shared stream, [C][n] pairs of independent streams"""
+        p = C.c_void_p()
+        check(self.L, self.L.pebblegpu_multibank_ingest_acquire(self.h, int(slot), int(nbytes), C.byref(p)))
+        n = int(nbytes) // np.dtype(dtype).itemsize
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(n,))
+
+    def ingest_submit(self, slot, nbytes):
+        check(self.L, self.L.pebblegpu_multibank_ingest_submit(self.h, int(slot), int(nbytes)))
+
+    def process_ingested(self, slot, n_samples, fmt, iq_order=0, gain=1.0):
+        check(self.L, self.L.pebblegpu_multibank_process_ingested(self.h, int(slot), int(fmt), int(iq_order), float(gain), int(n_samples)))
+
+    def synchronize(self):
+        check(self.L, self.L.pebblegpu_multibank_synchronize(self.h))
+
+    def last_ms(self):
+        """the slowest shard's time of the last call (pebblegpu_receiver_last_ms(rx, 0) maximised over the shards)"""
+        ms = C.c_float()
+        check(self.L, self.L.pebblegpu_multibank_last_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def audio(self):
+        """-> complex64 [C, n] of the last call: the shards' rows concatenated in global channel order"""
+        self.synchronize()
+        return np.concatenate([s.audio() for s in self.shards], axis=0)
+
+    def process(self, iq):
+        """iq: host complex [n] (shared stream) or [C, n] (independent streams), uploaded per shard.  -> audio [C, n/D]"""
+        iq = np.atleast_2d(np.asarray(iq))
+        assert iq.shape[0] == (1 if self.shared_input else self.n_channels), "expected %d streams" % (1 if self.shared_input else self.n_channels)
+        bufs = []
+        try:
+            for g, (first, cnt) in enumerate(self.ranges):
+                rows = iq if self.shared_input else iq[first:first + cnt]
+                bufs.append(DeviceBuffer.from_array(to_f32_iq(rows), self.devices[g], self.L))
+            self.process_device([b.ptr for b in bufs], iq.shape[1])
+            return self.audio()
+        finally:
+            for b in bufs:
+                b.free()

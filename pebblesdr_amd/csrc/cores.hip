@@ -369,6 +369,44 @@ int IngestRing::mark_in_flight(IngestSlot &g, hipStream_t main, hipStream_t chai
     g.in_flight = true;
     return 0;
 }
+int IngestRing::wait_free(uint32_t s)
+{
+    if (s > 1) return fail(PEBBLEGPU_E_INVALID, "ingest slot is 0 or 1");
+    IngestSlot &g = slot[s];
+    if (g.in_flight) {
+        PG_HIP(hipEventSynchronize(g.done_main));
+        PG_HIP(hipEventSynchronize(g.done_chain));
+        g.in_flight = false;
+    }
+    if (copy_stream) PG_HIP(hipStreamSynchronize(copy_stream));  // (an upload nobody processed: the host buffer is about to be refilled)
+    g.submitted = 0;
+    return 0;
+}
+int IngestRing::submit_from(int device, uint32_t s, const void *h_src, uint64_t bytes)
+{
+    if (s > 1 || !h_src || bytes == 0) return fail(PEBBLEGPU_E_INVALID, "ingest slot is 0 or 1, a host buffer, bytes > 0");
+    IngestSlot &g = slot[s];
+    if (g.in_flight) return fail(PEBBLEGPU_E_INVALID, "the slot's previous call is still in flight: acquire it again first");
+    PG_HIP(hipSetDevice(device));
+    if (!copy_stream) PG_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    if (!g.uploaded) {
+        PG_HIP(hipEventCreateWithFlags(&g.uploaded, hipEventDisableTiming));
+        PG_HIP(hipEventCreateWithFlags(&g.done_main, hipEventDisableTiming));
+        PG_HIP(hipEventCreateWithFlags(&g.done_chain, hipEventDisableTiming));
+    }
+    if (g.cap < bytes) {
+        PG_HIP(hipStreamSynchronize(copy_stream));
+        if (g.d) (void)hipFree(g.d);
+        g.d = nullptr;
+        g.cap = 0;
+        PG_HIP(hipMalloc(&g.d, bytes));
+        g.cap = bytes;
+    }
+    PG_HIP(hipMemcpyAsync(g.d, h_src, bytes, hipMemcpyHostToDevice, copy_stream));
+    PG_HIP(hipEventRecord(g.uploaded, copy_stream));
+    g.submitted = bytes;
+    return 0;
+}
 void IngestRing::release()
 {
     if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }

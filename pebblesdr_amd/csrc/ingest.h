@@ -25,6 +25,12 @@ struct IngestRing {
     // both of a call's streams read the raw samples: they wait for the upload, and the slot is free again when both are past the call
     int wait_upload(IngestSlot &g, hipStream_t main, hipStream_t chain);
     int mark_in_flight(IngestSlot &g, hipStream_t main, hipStream_t chain);
+    // A ring fed from a pinned host buffer that somebody else owns (the multibank's slots, shared by every shard: multibank.hip).  Such a
+    // ring has device twins only (slot.h stays null) and is never handed to acquire / submit:
+    //   wait_free   -- blocks until the last call that read the slot's twin, and any upload still queued, is over
+    //   submit_from -- queues the upload of `bytes` from h_src (pinned, readable by this device) into the twin (grown on demand)
+    int wait_free(uint32_t s);
+    int submit_from(int device, uint32_t s, const void *h_src, uint64_t bytes);
     void release();  // (the owner has synchronised its own streams)
 };
 

@@ -4,10 +4,6 @@
 #include <vector>
 #include "receiver.h"
 
-struct pebblegpu_receiver {
-    pg::Receiver rx;
-};
-
 using pg::fail;
 namespace pg {
 int probe_copy(int lane_bytes, size_t bytes, int iters, float *gbps);

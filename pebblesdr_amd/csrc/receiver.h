@@ -651,6 +651,13 @@ public:
     int ingest_acquire(uint32_t slot, uint64_t bytes, void **host_ptr);
     int ingest_submit(uint32_t slot, uint64_t bytes);
     int process_ingested(uint32_t slot, int fmt, int order, double gain, uint64_t n);
+    // The same three steps for an owner of several receivers that share ONE pinned host buffer (the multibank's slots, multibank.hip):
+    // the receiver keeps only the slot's device twin (a second ring, so that the two ways in never mix).  ingest_wait blocks until the
+    // last call that read the twin is over; ingest_upload queues the copy of `bytes` from h_src on the copy stream; process_uploaded
+    // is process_raw on the twin, ordered behind that copy on the device.
+    int ingest_wait(uint32_t slot);
+    int ingest_upload(uint32_t slot, const void *h_src, uint64_t bytes);
+    int process_uploaded(uint32_t slot, int fmt, int order, double gain, uint64_t n);
     int set_squelch(uint32_t ch, double squelch_db);   // Receiver::squelchChanged, receiver.cpp:704-707
     // dmFMS channels of a WFM bank: what Demod::fmStereo took from the RDS group queue since the last call (waits for queued work)
     int rds_groups(uint32_t ch, RdsGroup *g, unsigned char *changed, uint32_t cap, uint32_t *n);
@@ -782,8 +789,14 @@ private:
     float2 *d_stage_in_ = nullptr;
     float2 *d_raw_stage_ = nullptr;   // process_raw: the normalised copy of a raw device-format call (allocated on first use)
     IngestRing ingest_;               // the pinned double buffer of ingest_acquire / _submit / process_ingested (ingest.h)
+    IngestRing ext_ingest_;           // device twins of somebody else's pinned slots (ingest_wait / _upload / process_uploaded)
     std::vector<float> h_frame_, h_out_;
     uint64_t acc_frames_ = 0;
 };
 
 }  // namespace pg
+
+// the handle of include/pebblegpu.h (pebblegpu_abi.hip has its entry points; multibank.hip owns one per shard)
+struct pebblegpu_receiver {
+    pg::Receiver rx;
+};

@@ -117,6 +117,7 @@ Receiver::~Receiver()
     osc_.release(); dec_.release(); ff_.release(); am_.release(); nfm_.release(); sam_.release(); wfmc_.release(); spec_.release(); zoom_.release();
     for (hipEvent_t e : sync_ev_) if (e) (void)hipEventDestroy(e);
     ingest_.release();
+    ext_ingest_.release();
     if (d_zoom) (void)hipFree(d_zoom);
     if (map_ev_) (void)hipEventDestroy(map_ev_);
     agc_.release(); resamp_.release(); cond_.release(); anf_.release();
@@ -964,6 +965,22 @@ int Receiver::process_ingested(uint32_t slot, int fmt, int order, double gain, u
     if (int rc = ingest_.wait_upload(*g, stream_, chain_stream_)) return rc;
     if (int rc = process_raw(fmt, order, gain, g->d, n)) return rc;
     return ingest_.mark_in_flight(*g, stream_, chain_stream_);
+}
+// the twins of an outside owner's pinned slots (the multibank): same order of steps on the second ring
+int Receiver::ingest_wait(uint32_t slot)
+{
+    PG_HIP(hipSetDevice(device));
+    return ext_ingest_.wait_free(slot);
+}
+int Receiver::ingest_upload(uint32_t slot, const void *h_src, uint64_t bytes) { return ext_ingest_.submit_from(device, slot, h_src, bytes); }
+int Receiver::process_uploaded(uint32_t slot, int fmt, int order, double gain, uint64_t n)
+{
+    IngestSlot *g = nullptr;
+    if (int rc = ext_ingest_.check(slot, fmt, (uint64_t)S * n, n, &g)) return rc;
+    PG_HIP(hipSetDevice(device));
+    if (int rc = ext_ingest_.wait_upload(*g, stream_, chain_stream_)) return rc;
+    if (int rc = process_raw(fmt, order, gain, g->d, n)) return rc;
+    return ext_ingest_.mark_in_flight(*g, stream_, chain_stream_);
 }
 
 // "k_testbench + <front kernel>": one string per front-kernel name, kept for the life of the process like the literals the other groups
