@@ -514,6 +514,8 @@ int pebblegpu_process_iq_updates(pebblegpu_receiver *rx, const double *iq, uint1
  *     handle must NOT be passed to pebblegpu_receiver_destroy, nor to any process / ingest entry point (pebblegpu_receiver_process,
  *     _process_raw, _ingest_acquire, _ingest_submit, _process_ingested, pebblegpu_process_iq, _process_iq_updates): those belong to
  *     the multibank; it is valid until pebblegpu_multibank_destroy.  Outputs stay sharded: each shard's audio is on its device.
+ *     The audio blocks and recorded IQ (pebblegpu_receiver_audio_out_*, pebblegpu_set_audio_level, pebblegpu_receiver_record_*, below)
+ *     are such setters and read-outs: they work per shard on the borrowed handle, and there is no multibank call for them.
  *   - create checks its arguments before any device is touched (PEBBLEGPU_E_INVALID: a null pointer, a struct_size mismatch,
  *     n_shards 0 or above PEBBLEGPU_MULTIBANK_MAX_SHARDS, n_channels < n_shards, unknown flag bits), then probes the devices
  *     (PEBBLEGPU_E_NO_DEVICE with none, PEBBLEGPU_E_INVALID for an ordinal out of range).
@@ -795,6 +797,90 @@ int pebblegpu_siggen_generate(pebblegpu_siggen *g, double *iq, uint32_t n);
 /* for parity checks: the accepted 31-bit draws (r [n][2]) and the accepted attempt's number (attempt [n]; 32: none) of noise samples
  * first_sample .. first_sample + n - 1 of the generator's stream with its current seed, computed on the device; host arrays */
 int pebblegpu_siggen_noise_draws(pebblegpu_siggen *g, uint64_t first_sample, uint32_t n, uint32_t *r, uint8_t *attempt);
+
+/* ------------------------------------------------------------------------------------------------
+ * Host egress: the audio output stage and IQ recording through pinned slots.
+ * The two steps the reference ends its chain with, as ONE mechanism -- the ingest slots in the other direction: a small packing
+ * kernel is queued behind the process call on the call's own stream, its output travels on a copy stream into a ring of pinned host
+ * slots, and the host waits for one slot's event, never for the device.  Without a ring the only way to a call's audio is
+ * pebblegpu_receiver_audio + pebblegpu_receiver_synchronize / pebblegpu_memcpy_d2h, which drain the device after every call.
+ *
+ * Audio output: Receiver::processAudioData -> Audio::SendToOutput(in, n, m_gain, m_mute) (application/receiver.cpp:1029-1035; the sample
+ * rule is pebblelib/audiopa.cpp:304-343, the same clip in pebblelib/audioqt.cpp:169-211), per selected channel:
+ *     g = gain / 100.f;  t = a * g (ONE fp32 multiply: the reference's float(double(a) * double(g)), whose double product is exact);
+ *     if (t > 0.9999f) t = 0.9999f; else if (t < -0.9999f) t = -0.9999f;        written interleaved L (real), R (imaginary)
+ * The reference writes nothing when muted; a muted channel's row is zeros here.  NaN inputs: unpinned.  The source is the buffer
+ * pebblegpu_receiver_audio reports -- the resampled audio when audio_rate is set, so the count can differ from call to call and is no
+ * multiple of anything.  The reference's sound device takes floats: the two PCM16 formats are the library's own combination of that
+ * clipped value with WavFile::WriteSamples' rule, (int16_t)((double)t * 32767), truncating (pebblelib/wavfile.cpp:387-388; the product
+ * in double -- an fp32 product can round up to the next integer).
+ *
+ * ONE block per process call, always: call indices are 0-based from open and contiguous; a call that yields no audio (a one-channel
+ * receiver's closed squelch, tune-only) gives a block with samples_per_channel == 0.  A FULL RING DROPS, IT DOES NOT REFUSE: when the
+ * next slot has not been released as a call is queued, the call runs unchanged, its block is dropped and counted (the reference's
+ * producer drops a frame the same way when no buffer is free; chain state never depends on the reader).  "Free" is host-side
+ * bookkeeping only, so what is delivered and what is dropped does not depend on the device's timing.  n_slots: 2..8; 4 cover the
+ * documented run-ahead of three calls.  Opening a ring changes no call's route or kernels (pebblegpu_receiver_kernel_name reports the
+ * same strings): it adds one launch and one event to the call, and nothing the next call queues waits for the copy.  One reader, which
+ * may run on another thread than the process calls; pebblegpu_process_iq / _process_iq_updates return their audio themselves and are
+ * refused with PEBBLEGPU_E_UNSUPPORTED while a ring is open.  On the shard handles of a multibank (pebblegpu_multibank_shard) these
+ * are setters and read-outs like any other: every shard has its own rings.
+ * ---------------------------------------------------------------------------------------------- */
+typedef enum {
+    PEBBLEGPU_AUDIO_F32 = 0,      /* AudioPA::SendToOutput: float L, R interleaved, 8 bytes per sample */
+    PEBBLEGPU_AUDIO_S16 = 1,      /* the same clipped value through WavFile::WriteSamples' rule, L, R, 4 bytes */
+    PEBBLEGPU_AUDIO_S16_MONO = 2  /* left only, 2 bytes */
+} pebblegpu_audio_format;
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(pebblegpu_audio_block), set by the caller */
+    uint32_t format;               /* pebblegpu_audio_format (a recording block: PEBBLEGPU_AUDIO_S16, left = I, right = Q) */
+    uint64_t call_index;           /* which process call since open */
+    const void *host;              /* pinned host memory: row r at host + r * pitch_bytes; NULL: no block (see _next) */
+    uint64_t samples_per_channel;  /* may be 0 */
+    uint64_t pitch_bytes;          /* a multiple of 16 */
+    uint32_t n_channels;           /* rows: the selected channels (a recording block: the streams) */
+    uint32_t dropped_before;       /* blocks dropped between the previous queued block and this one */
+} pebblegpu_audio_block;
+/* channels: row r of every block is channel channels[r] -- a subset, in any order; NULL: all n_channels of the receiver, in order
+ * (n_channels is then ignored).  Duplicates, channels out of range, n_slots outside 2..8, an unknown format and a second open are
+ * PEBBLEGPU_E_INVALID and leave the handle as it was. */
+int pebblegpu_receiver_audio_out_open(pebblegpu_receiver *rx, int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots);
+/* waits for the handle's queued work, frees the ring (blocks not read are lost, and pointers handed out by _next become invalid).  A
+ * reader that is inside _next on another thread is waited for (every copy is complete by then, so its wait ends); it returns
+ * PEBBLEGPU_E_INVALID or its block, and must not touch the block after close returns */
+int pebblegpu_receiver_audio_out_close(pebblegpu_receiver *rx);
+/* Receiver::m_gain (the UI's 0..100; larger values amplify) and m_mute; defaults 100, 0.  gain must be finite and >= 0.  Takes effect at
+ * the next process call like every setter (that call first waits for the calls before it: the rows' table is shared); kept while the
+ * ring is closed. */
+int pebblegpu_set_audio_level(pebblegpu_receiver *rx, uint32_t channel, float gain, int mute);
+/* the oldest block not handed out yet.  wait != 0: blocks on that slot's event only.  b->host == NULL (and PEBBLEGPU_OK) when nothing
+ * is queued, or with wait == 0 when the copy has not completed.  The memory stays valid until the block is released. */
+int pebblegpu_receiver_audio_out_next(pebblegpu_receiver *rx, int wait, pebblegpu_audio_block *b);
+/* gives the slot back: call_index must be the oldest handed-out block that has not been released, anything else is PEBBLEGPU_E_INVALID */
+int pebblegpu_receiver_audio_out_release(pebblegpu_receiver *rx, uint64_t call_index);
+int pebblegpu_receiver_audio_out_dropped(const pebblegpu_receiver *rx, uint64_t *blocks);   /* blocks dropped since open */
+/* the host twin of the packing kernel (the same inline function; no device): n samples of interleaved float L, R -> out in `format` */
+int pebblegpu_audio_out_convert(int format, float gain, int mute, const float *lr, uint64_t n, void *out);
+
+/* IQ recording: if (m_isRecording) m_recordingFile.WriteSamples(nextStep, numSamples) (application/receiver.cpp:800-801), right behind
+ * the test bench's injection: per call and stream the samples PEBBLEGPU_TAP_RAW_IQ shows -- after the generator, before the
+ * conditioners (receiver.cpp:800-803) -- as PCM16 pairs, left = I, right = Q: the format PEBBLEGPU_IQ_WAV16 ingests.  Conversion:
+ * (int16_t)((double)v * 32767), truncating (pebblelib/wavfile.cpp:377-396); where the reference's is undefined, |v * 32767| >= 32768,
+ * the value saturates to +-32767; NaN gives 0.  A second ring of the same type, with the same block, drop and reader rules
+ * (n_channels = streams, samples_per_channel = the call's n_samples, 4 bytes per sample).  On raw calls (pebblegpu_receiver_process_raw /
+ * _process_ingested, multibank calls) with the test bench's generator off the kernel converts from the raw pairs itself, with
+ * pebblegpu_normalize_iq's loader and scale, whether the call's own kernels convert in their loads (one channel beside the 8192-bin
+ * transform: no float2 copy of the stream exists at all) or the call stages a converted copy for itself; the recording makes no
+ * float2 copy of its own.  With the generator on, what the chain saw exists only in the buffer the generator wrote, and the kernel
+ * reads that.  The kernel sits where the RAW_IQ tap's copy sits, and as with a tap a receiver without a
+ * display transform runs its calls on ONE stream while a recording ring is open: recording is a diagnostic path, the audio ring is
+ * the throughput path and has no such cost. */
+int pebblegpu_receiver_record_open(pebblegpu_receiver *rx, uint32_t n_slots);
+int pebblegpu_receiver_record_close(pebblegpu_receiver *rx);
+int pebblegpu_receiver_record_next(pebblegpu_receiver *rx, int wait, pebblegpu_audio_block *b);
+int pebblegpu_receiver_record_release(pebblegpu_receiver *rx, uint64_t call_index);
+/* host twin: n IQ samples of interleaved float I, Q -> n PCM16 pairs */
+int pebblegpu_iq_record_convert(const float *iq, uint64_t n, int16_t *out);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,10 @@ SYMBOLS = [
     "pebblegpu_multibank_plan", "pebblegpu_multibank_create", "pebblegpu_multibank_destroy", "pebblegpu_multibank_shards", "pebblegpu_multibank_shard",
     "pebblegpu_multibank_locate", "pebblegpu_multibank_process", "pebblegpu_multibank_process_raw", "pebblegpu_multibank_ingest_acquire",
     "pebblegpu_multibank_ingest_submit", "pebblegpu_multibank_process_ingested", "pebblegpu_multibank_synchronize", "pebblegpu_multibank_last_ms",
+    "pebblegpu_receiver_audio_out_open", "pebblegpu_receiver_audio_out_close", "pebblegpu_set_audio_level", "pebblegpu_receiver_audio_out_next",
+    "pebblegpu_receiver_audio_out_release", "pebblegpu_receiver_audio_out_dropped", "pebblegpu_audio_out_convert",
+    "pebblegpu_receiver_record_open", "pebblegpu_receiver_record_close", "pebblegpu_receiver_record_next", "pebblegpu_receiver_record_release",
+    "pebblegpu_iq_record_convert",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
@@ -239,6 +243,55 @@ class Info(C.Structure):
     ]
 
 
+AUDIO_F32, AUDIO_S16, AUDIO_S16_MONO = range(3)  # pebblegpu_audio_format
+_AUDIO_DTYPE = {AUDIO_F32: (np.float32, 2), AUDIO_S16: (np.int16, 2), AUDIO_S16_MONO: (np.int16, 1)}  # element type, elements per sample
+
+
+class AudioBlock(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_uint32), ("call_index", C.c_uint64), ("host", C.c_void_p),
+                ("samples_per_channel", C.c_uint64), ("pitch_bytes", C.c_uint64), ("n_channels", C.c_uint32), ("dropped_before", C.c_uint32)]
+
+
+def _block_array(b):
+    """a copy of the block's rows: [rows, samples, 2] (float32 or int16), [rows, samples] for the mono format"""
+    dt, per = _AUDIO_DTYPE[int(b.format)]
+    rows, n, pitch = int(b.n_channels), int(b.samples_per_channel), int(b.pitch_bytes)
+    out = np.zeros((rows, n, per), dtype=dt)
+    if n:
+        raw = np.ctypeslib.as_array(C.cast(b.host, C.POINTER(C.c_uint8)), shape=(rows * pitch,)).reshape(rows, pitch)
+        out = raw[:, : n * per * np.dtype(dt).itemsize].copy().view(dt).reshape(rows, n, per)
+    return out[:, :, 0] if per == 1 else out
+
+
+def audio_out_convert(fmt, gain, mute, lr, lib=None):
+    """the host twin of the audio packing kernel: lr float32 [n, 2] (or complex64 [n]) -> [n, 2] float32 / int16, [n] int16 for the mono format"""
+    L = lib or load_library()
+    lr = np.ascontiguousarray(lr)
+    if np.iscomplexobj(lr):
+        lr = lr.astype(np.complex64).view(np.float32)
+    lr = np.ascontiguousarray(lr, dtype=np.float32).reshape(-1, 2)
+    n = lr.shape[0]
+    if int(fmt) not in _AUDIO_DTYPE:
+        out = np.zeros(1, dtype=np.float32)  # (the call refuses the format itself)
+    else:
+        dt, per = _AUDIO_DTYPE[int(fmt)]
+        out = np.zeros((n, per), dtype=dt)
+    check(L, L.pebblegpu_audio_out_convert(int(fmt), float(gain), 1 if mute else 0, lr.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p)))
+    return out[:, 0] if out.shape[1] == 1 else out
+
+
+def iq_record_convert(iq, lib=None):
+    """the host twin of the recording kernel: float32 [n, 2] (or complex64 [n]) -> int16 [n, 2], left = I, right = Q"""
+    L = lib or load_library()
+    iq = np.ascontiguousarray(iq)
+    if np.iscomplexobj(iq):
+        iq = iq.astype(np.complex64).view(np.float32)
+    iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1, 2)
+    out = np.zeros(iq.shape, dtype=np.int16)
+    check(L, L.pebblegpu_iq_record_convert(iq.ctypes.data_as(C.c_void_p), iq.shape[0], out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def library_path():
     return os.path.join(_HERE, _LIBNAME)
 
@@ -399,6 +452,19 @@ def _declare(L):
     L.pebblegpu_multibank_process_ingested.argtypes = [vp, u32, i32, i32, dbl, u64]
     L.pebblegpu_multibank_synchronize.argtypes = [vp]
     L.pebblegpu_multibank_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    blk = C.POINTER(AudioBlock)
+    L.pebblegpu_receiver_audio_out_open.argtypes = [vp, i32, u32p, u32, u32]
+    L.pebblegpu_receiver_audio_out_close.argtypes = [vp]
+    L.pebblegpu_set_audio_level.argtypes = [vp, u32, C.c_float, i32]
+    L.pebblegpu_receiver_audio_out_next.argtypes = [vp, i32, blk]
+    L.pebblegpu_receiver_audio_out_release.argtypes = [vp, u64]
+    L.pebblegpu_receiver_audio_out_dropped.argtypes = [vp, C.POINTER(u64)]
+    L.pebblegpu_audio_out_convert.argtypes = [i32, C.c_float, i32, vp, u64, vp]
+    L.pebblegpu_receiver_record_open.argtypes = [vp, u32]
+    L.pebblegpu_receiver_record_close.argtypes = [vp]
+    L.pebblegpu_receiver_record_next.argtypes = [vp, i32, blk]
+    L.pebblegpu_receiver_record_release.argtypes = [vp, u64]
+    L.pebblegpu_iq_record_convert.argtypes = [vp, u64, vp]
     return L
 
 
@@ -676,6 +742,55 @@ class ReceiverBank:
 
     def synchronize(self):
         check(self.L, self.L.pebblegpu_receiver_synchronize(self.h))
+
+    # ---- host egress: the audio output stage and IQ recording through pinned slots ----
+    def audio_out_open(self, fmt=AUDIO_F32, channels=None, n_slots=4):
+        """channels: row r of every block is channel channels[r] (None: all, in order)"""
+        if channels is None:
+            check(self.L, self.L.pebblegpu_receiver_audio_out_open(self.h, int(fmt), None, 0, int(n_slots)))
+        else:
+            arr = (C.c_uint32 * max(1, len(channels)))(*[int(c) for c in channels])
+            check(self.L, self.L.pebblegpu_receiver_audio_out_open(self.h, int(fmt), arr, len(channels), int(n_slots)))
+
+    def audio_out_close(self):
+        check(self.L, self.L.pebblegpu_receiver_audio_out_close(self.h))
+
+    def set_audio_level(self, ch, gain=100.0, mute=False):
+        """Receiver::m_gain (the UI's 0..100) and m_mute of one channel; takes effect at the next call"""
+        check(self.L, self.L.pebblegpu_set_audio_level(self.h, int(ch), float(gain), 1 if mute else 0))
+
+    def _egress_next(self, fn, wait):
+        b = AudioBlock()
+        b.struct_size = C.sizeof(AudioBlock)
+        check(self.L, fn(self.h, 1 if wait else 0, C.byref(b)))
+        if not b.host:
+            return None
+        return int(b.call_index), int(b.dropped_before), _block_array(b)
+
+    def audio_out_next(self, wait=True):
+        """-> (call_index, dropped_before, copy of the block's rows) or None; the block stays taken until audio_out_release(call_index)"""
+        return self._egress_next(self.L.pebblegpu_receiver_audio_out_next, wait)
+
+    def audio_out_release(self, call_index):
+        check(self.L, self.L.pebblegpu_receiver_audio_out_release(self.h, int(call_index)))
+
+    def audio_out_dropped(self):
+        n = C.c_uint64()
+        check(self.L, self.L.pebblegpu_receiver_audio_out_dropped(self.h, C.byref(n)))
+        return int(n.value)
+
+    def record_open(self, n_slots=4):
+        check(self.L, self.L.pebblegpu_receiver_record_open(self.h, int(n_slots)))
+
+    def record_close(self):
+        check(self.L, self.L.pebblegpu_receiver_record_close(self.h))
+
+    def record_next(self, wait=True):
+        """-> (call_index, dropped_before, int16 [streams, n, 2]) or None"""
+        return self._egress_next(self.L.pebblegpu_receiver_record_next, wait)
+
+    def record_release(self, call_index):
+        check(self.L, self.L.pebblegpu_receiver_record_release(self.h, int(call_index)))
 
     def enable_signal_strength(self, on=True):
         check(self.L, self.L.pebblegpu_receiver_enable_signal_strength(self.h, 1 if on else 0))

@@ -1,0 +1,119 @@
+// egress.h -- host egress: ingest.h in the other direction.  A ring of pinned host slots that a small packing kernel, queued behind a
+// process call on the call's own stream, fills through a device staging twin and a copy stream; the host waits for ONE slot's
+// "copied" event, never for the device.  Two users, both in Receiver (egress.hip):
+//   the audio output stage -- Receiver::processAudioData -> Audio::SendToOutput(in, n, m_gain, m_mute), application/receiver.cpp:1029-1035;
+//                             the sample rule is pebblelib/audiopa.cpp:304-343 (the same clip in pebblelib/audioqt.cpp:169-211)
+//   IQ recording           -- if (m_isRecording) m_recordingFile.WriteSamples(nextStep, numSamples), application/receiver.cpp:800-801;
+//                             the conversion is pebblelib/wavfile.cpp:377-396
+// Per call: the packing kernel writes the next slot's twin on the stream where the call's last writer ran, an event is recorded
+// there, the copy stream waits for it, copies device -> pinned host and records the slot's event.  Nothing the next call queues waits
+// for that copy.  One block per process call, always (a call without audio yields a block of 0 samples); call indices count from
+// open().  A slot is free once the reader has released it -- host-side bookkeeping only, so what is delivered and what is dropped
+// does not depend on the device's timing.  A call that finds the next slot taken runs unchanged and its block is dropped and
+// counted: the reference's producer drops a frame the same way when no buffer is free, and chain state never depends on the reader.
+// Slots: 2..8; 4 cover the documented run-ahead of three calls (a two-stage call returns once the call three before it has completed).
+#pragma once
+#include <condition_variable>
+#include <mutex>
+#include "common.h"
+
+namespace pg {
+
+// ---- the sample rules, shared by the kernels and the host twins (pebblegpu_audio_out_convert / pebblegpu_iq_record_convert) ----
+constexpr float kAudioMaxOutput = 0.9999f;  // const float maxOutput = 0.9999, audiopa.cpp:315
+
+// out[i] *= (gain / 100); temp = out[i].real(); clip (audiopa.cpp:323-330), g = gain / 100.f.  The reference multiplies in double and
+// narrows: float(double(a) * double(g)); the double product of two floats is exact, so that is ONE fp32 multiply, rounded on its own
+__host__ __device__ inline float audio_out_sample(float a, float g)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    float t = __fmul_rn(a, g);  // (never contracted into anything)
+#else
+    float t = a * g;
+#endif
+    if (t > kAudioMaxOutput) t = kAudioMaxOutput;
+    else if (t < -kAudioMaxOutput) t = -kAudioMaxOutput;
+    return t;
+}
+// pcmData.left = value * 32767 (wavfile.cpp:387-388) on the clipped value: the product in double (an fp32 product can round up to the
+// next integer and then truncates differently), the conversion truncates.  |t| <= 0.9999: always in range
+__host__ __device__ inline int16_t audio_out_s16(float t) { return (int16_t)((double)t * 32767); }
+// the same conversion on an unclipped IQ sample: where the reference's is undefined (|v * 32767| >= 32768) the value saturates to
+// +-32767; NaN gives 0
+__host__ __device__ inline int16_t iq_record_s16(float v)
+{
+    double d = (double)v * 32767;
+    if (!(d == d)) return 0;
+    if (d > 32767.0) d = 32767.0;
+    else if (d < -32767.0) d = -32767.0;
+    return (int16_t)d;
+}
+
+constexpr int kAudioFormats = 3;
+constexpr uint32_t kAudioBytes[kAudioFormats] = {8, 4, 2};  // per sample and row: F32 L, R; S16 L, R; S16 left only
+constexpr uint32_t kEgressMinSlots = 2, kEgressMaxSlots = 8;
+
+// one selected row of the audio ring, as the packing kernel reads it (refreshed at call boundaries)
+struct EgressRow {
+    float g;        // gain / 100.f
+    int mute;
+    int src;        // row of the receiver's audio buffer
+    int pad_;
+};
+
+struct EgressSlot {
+    void *h = nullptr, *d = nullptr;   // pinned host buffer and its device staging twin
+    hipEvent_t packed = nullptr;       // behind the packing kernel, on the call's stream (no timing)
+    hipEvent_t copied = nullptr;       // behind the copy, on the copy stream (no timing)
+    uint64_t call = 0, samples = 0, pitch_bytes = 0;
+    uint32_t dropped_before = 0;
+    bool queued = false;               // holds a block that has not been released
+    bool handed = false;               // ... and next() has handed it out
+    bool has_copy = false;             // a copy was queued for it (a block of 0 samples has none)
+};
+
+struct EgressBlock {
+    uint64_t call = 0, samples = 0, pitch_bytes = 0;
+    const void *host = nullptr;
+    uint32_t dropped_before = 0, rows = 0, format = 0;
+};
+
+struct EgressRing {
+    std::mutex mu;                     // the ring's bookkeeping; never held while waiting for an event
+    std::condition_variable cv;        // close() waits here for a reader that is inside its event wait
+    bool open = false, reader_waiting = false;
+    uint32_t n_slots = 0, rows = 0, bytes_per_sample = 0, format = 0;  // format: what the blocks report (pebblegpu_audio_format)
+    uint64_t max_samples = 0, slot_bytes = 0;
+    EgressSlot slot[kEgressMaxSlots];
+    hipStream_t copy_stream = nullptr;
+    uint64_t calls = 0;                // process calls since open(): the next block's index
+    uint64_t head = 0, tail = 0;       // slot sequence numbers: [tail, head) are queued, oldest first
+    uint64_t read = 0;                 // ... and [tail, read) of them have been handed out
+    uint64_t dropped = 0;
+    uint32_t dropped_run = 0;          // blocks dropped since the last one that was queued
+
+    static uint64_t row_pitch(uint64_t samples, uint32_t bytes_per_sample) { return (samples * bytes_per_sample + 15) & ~(uint64_t)15; }
+    // allocates n_slots x (pinned buffer, twin, two events) for `rows` rows of at most max_samples; the caller has set the device
+    int open_ring(uint32_t slots, uint32_t n_rows, uint32_t bps, uint64_t max_n, uint32_t fmt);
+    void release();                    // (the owner has synchronised its streams)
+    // close: the owner has synchronised its streams (every slot's event is complete); waits until a reader on another thread has left
+    // its event wait, then frees the ring -- the events are never destroyed under a waiting reader
+    void close_ring();
+    // The producer's side, from a process call.  begin(): the slot the call's block goes to, or nullptr when the ring is full (the block
+    // is dropped and counted); the call index advances either way.  commit(): an event on `s` behind the packing kernel, the copy of
+    // rows * pitch bytes on the copy stream behind it, the slot's event; with samples == 0 nothing is queued at all.
+    EgressSlot *begin();
+    int commit(EgressSlot *g, hipStream_t s, uint64_t samples);
+    // The reader's side.  next(): the oldest block not handed out yet; wait != 0 blocks on that slot's event only; host == nullptr
+    // when nothing is queued or (wait == 0) the copy has not completed.  finish(): takes the oldest unreleased block.
+    int next(int device, int wait, EgressBlock *b);
+    int finish(uint64_t call_index);
+};
+
+// rows x n float2 audio samples (row r at audio + tab[r].src * pitch) -> dst [rows][dst_pitch bytes] in `format`
+int run_audio_pack(hipStream_t s, const float2 *audio, long long pitch, long long n, const EgressRow *d_tab, uint32_t rows, int format, void *dst,
+                   uint64_t dst_pitch);
+// rows x n IQ samples (float2 rows of `pitch`, or raw device-format pairs converted as k_normalize_iq converts them) -> PCM16 pairs
+int run_iq_record(hipStream_t s, const float2 *iq, long long pitch, const struct RawSrc *raw, long long n, uint32_t rows, void *dst, uint64_t dst_pitch);
+
+}  // namespace pg

@@ -1,0 +1,420 @@
+// egress.hip -- the egress ring (egress.h), its two packing kernels and the receiver's audio output stage and IQ recording.
+#include "receiver.h"
+
+namespace pg {
+
+// ---- kernels ----
+// Audio::SendToOutput (audiopa.cpp:304-343) for the selected rows of a call's audio buffer, one launch per call: a work-item takes four
+// samples -- two 16-byte loads where the source row is 16-byte aligned, one or two 16-byte stores (8 for the mono format); the ragged
+// end of a row and unaligned rows (a resampled buffer's odd pitch) go sample by sample.  Destination rows are 16-byte aligned by
+// construction (EgressRing::row_pitch).  FMT: 0 float L, R; 1 PCM16 L, R; 2 PCM16 left only
+template <int FMT>
+static __global__ __launch_bounds__(256) void k_audio_pack(const float2 *__restrict__ audio, long long pitch, long long n, const EgressRow *__restrict__ tab,
+                                                            unsigned char *__restrict__ dst, unsigned long long dst_pitch)
+{
+    const EgressRow r = tab[blockIdx.y];
+    const float2 *src = audio + (long long)r.src * pitch;
+    unsigned char *out = dst + (unsigned long long)blockIdx.y * dst_pitch;
+    const bool vec = (reinterpret_cast<unsigned long long>(src) & 15ull) == 0;
+    for (long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (long long)gridDim.x * 1024) {
+        const int m = n - i0 >= 4 ? 4 : (int)(n - i0);
+        float2 v[4];
+        if (r.mute) {
+            for (int k = 0; k < 4; k++) v[k] = make_float2(0.f, 0.f);
+        } else if (vec && m == 4) {
+            const float4 a = reinterpret_cast<const float4 *>(src + i0)[0], b = reinterpret_cast<const float4 *>(src + i0)[1];
+            v[0] = make_float2(a.x, a.y); v[1] = make_float2(a.z, a.w); v[2] = make_float2(b.x, b.y); v[3] = make_float2(b.z, b.w);
+        } else {
+            for (int k = 0; k < 4; k++) v[k] = k < m ? src[i0 + k] : make_float2(0.f, 0.f);
+        }
+        if (!r.mute)  // (a muted row is zeros whatever the samples are, NaN included)
+            for (int k = 0; k < 4; k++) v[k] = make_float2(audio_out_sample(v[k].x, r.g), audio_out_sample(v[k].y, r.g));
+        if (FMT == 0) {
+            float2 *o = reinterpret_cast<float2 *>(out) + i0;
+            if (m == 4) {
+                reinterpret_cast<float4 *>(o)[0] = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
+                reinterpret_cast<float4 *>(o)[1] = make_float4(v[2].x, v[2].y, v[3].x, v[3].y);
+            } else {
+                for (int k = 0; k < m; k++) o[k] = v[k];
+            }
+        } else if (FMT == 1) {
+            short2 q[4];
+            for (int k = 0; k < 4; k++) q[k] = make_short2(audio_out_s16(v[k].x), audio_out_s16(v[k].y));
+            short2 *o = reinterpret_cast<short2 *>(out) + i0;
+            if (m == 4) {
+                uint4 w;
+                memcpy(&w, q, 16);
+                *reinterpret_cast<uint4 *>(o) = w;
+            } else {
+                for (int k = 0; k < m; k++) o[k] = q[k];
+            }
+        } else {
+            short q[4];
+            for (int k = 0; k < 4; k++) q[k] = audio_out_s16(v[k].x);
+            short *o = reinterpret_cast<short *>(out) + i0;
+            if (m == 4) {
+                uint2 w;
+                memcpy(&w, q, 8);
+                *reinterpret_cast<uint2 *>(o) = w;
+            } else {
+                for (int k = 0; k < m; k++) o[k] = q[k];
+            }
+        }
+    }
+}
+
+// WavFile::WriteSamples' conversion (wavfile.cpp:386-388) of the streams a call's chain saw, left = I, right = Q.  RAW: the samples are
+// still in the device's format and converted here exactly as k_normalize_iq converts them (raw_load: the same loader, the same scale)
+template <bool RAW>
+static __global__ __launch_bounds__(256) void k_iq_record(const float2 *__restrict__ iq, long long pitch, RawSrc raw, long long n, unsigned char *__restrict__ dst,
+                                                           unsigned long long dst_pitch)
+{
+    const long long row = blockIdx.y;
+    const float2 *src = RAW ? nullptr : iq + row * pitch;
+    short2 *out = reinterpret_cast<short2 *>(dst + (unsigned long long)row * dst_pitch);
+    const bool vec = !RAW && (reinterpret_cast<unsigned long long>(src) & 15ull) == 0;
+    for (long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (long long)gridDim.x * 1024) {
+        const int m = n - i0 >= 4 ? 4 : (int)(n - i0);
+        float2 v[4];
+        if (vec && m == 4) {
+            const float4 a = reinterpret_cast<const float4 *>(src + i0)[0], b = reinterpret_cast<const float4 *>(src + i0)[1];
+            v[0] = make_float2(a.x, a.y); v[1] = make_float2(a.z, a.w); v[2] = make_float2(b.x, b.y); v[3] = make_float2(b.z, b.w);
+        } else {
+            for (int k = 0; k < 4; k++) {
+                if (k >= m) v[k] = make_float2(0.f, 0.f);
+                else if (RAW) v[k] = raw_load(raw, row * n + i0 + k);  // (streams are stream-major: row r starts at pair r * n)
+                else v[k] = src[i0 + k];
+            }
+        }
+        short2 q[4];
+        for (int k = 0; k < 4; k++) q[k] = make_short2(iq_record_s16(v[k].x), iq_record_s16(v[k].y));
+        if (m == 4) {
+            uint4 w;
+            memcpy(&w, q, 16);
+            *reinterpret_cast<uint4 *>(out + i0) = w;
+        } else {
+            for (int k = 0; k < m; k++) out[i0 + k] = q[k];
+        }
+    }
+}
+
+static unsigned pack_blocks(long long n)
+{
+    long long b = (n + 1023) / 1024;
+    return (unsigned)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
+}
+
+int run_audio_pack(hipStream_t s, const float2 *audio, long long pitch, long long n, const EgressRow *d_tab, uint32_t rows, int format, void *dst,
+                   uint64_t dst_pitch)
+{
+    if (n <= 0 || rows == 0) return 0;
+    const dim3 grid(pack_blocks(n), rows);
+    unsigned char *o = (unsigned char *)dst;
+    if (format == PEBBLEGPU_AUDIO_F32) launch(k_audio_pack<0>, grid, dim3(256), s, audio, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
+    else if (format == PEBBLEGPU_AUDIO_S16) launch(k_audio_pack<1>, grid, dim3(256), s, audio, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
+    else launch(k_audio_pack<2>, grid, dim3(256), s, audio, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int run_iq_record(hipStream_t s, const float2 *iq, long long pitch, const RawSrc *raw, long long n, uint32_t rows, void *dst, uint64_t dst_pitch)
+{
+    if (n <= 0 || rows == 0) return 0;
+    const dim3 grid(pack_blocks(n), rows);
+    unsigned char *o = (unsigned char *)dst;
+    if (raw) launch(k_iq_record<true>, grid, dim3(256), s, (const float2 *)nullptr, 0LL, *raw, n, o, (unsigned long long)dst_pitch);
+    else launch(k_iq_record<false>, grid, dim3(256), s, iq, pitch, RawSrc{nullptr, 0, 0, 0.f, 0}, n, o, (unsigned long long)dst_pitch);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- EgressRing ----
+int EgressRing::open_ring(uint32_t slots, uint32_t n_rows, uint32_t bps, uint64_t max_n, uint32_t fmt)
+{
+    format = fmt;
+    n_slots = slots;
+    rows = n_rows;
+    bytes_per_sample = bps;
+    max_samples = max_n;
+    slot_bytes = (uint64_t)n_rows * row_pitch(max_n, bps);
+    if (!copy_stream) PG_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    for (uint32_t i = 0; i < n_slots; i++) {
+        EgressSlot &g = slot[i];
+        g = EgressSlot{};
+        PG_HIP(hipHostMalloc(&g.h, slot_bytes, hipHostMallocDefault));
+        PG_HIP(hipMalloc(&g.d, slot_bytes));
+        PG_HIP(hipEventCreateWithFlags(&g.packed, hipEventDisableTiming));
+        PG_HIP(hipEventCreateWithFlags(&g.copied, hipEventDisableTiming));
+    }
+    calls = head = tail = read = dropped = 0;
+    dropped_run = 0;
+    open = true;
+    return 0;
+}
+
+void EgressRing::release()
+{
+    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+    for (EgressSlot &g : slot) {
+        if (g.h) (void)hipHostFree(g.h);
+        if (g.d) (void)hipFree(g.d);
+        if (g.packed) (void)hipEventDestroy(g.packed);
+        if (g.copied) (void)hipEventDestroy(g.copied);
+        g = EgressSlot{};
+    }
+    if (copy_stream) (void)hipStreamDestroy(copy_stream);
+    copy_stream = nullptr;
+    open = false;
+    n_slots = 0;
+}
+
+void EgressRing::close_ring()
+{
+    std::unique_lock<std::mutex> lk(mu);
+    open = false;  // (a reader that comes back from its wait finds the ring closed and leaves without touching a slot)
+    cv.wait(lk, [this] { return !reader_waiting; });
+    release();
+}
+
+EgressSlot *EgressRing::begin()
+{
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t call = calls++;
+    if (head - tail >= n_slots) {  // the reader has not released the next slot: this call's block is dropped
+        dropped++;
+        dropped_run++;
+        return nullptr;
+    }
+    EgressSlot &g = slot[head % n_slots];  // (not visible to the reader until commit() moves `head`)
+    g.call = call;
+    g.dropped_before = dropped_run;
+    dropped_run = 0;
+    return &g;
+}
+
+int EgressRing::commit(EgressSlot *g, hipStream_t s, uint64_t samples)
+{
+    g->samples = samples;
+    g->pitch_bytes = row_pitch(samples, bytes_per_sample);
+    g->has_copy = samples != 0;
+    if (g->has_copy) {
+        PG_HIP(hipEventRecord(g->packed, s));
+        PG_HIP(hipStreamWaitEvent(copy_stream, g->packed, 0));
+        PG_HIP(hipMemcpyAsync(g->h, g->d, (size_t)(rows * g->pitch_bytes), hipMemcpyDeviceToHost, copy_stream));
+        PG_HIP(hipEventRecord(g->copied, copy_stream));
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    g->queued = true;
+    g->handed = false;
+    head++;
+    return 0;
+}
+
+int EgressRing::next(int device, int wait, EgressBlock *b)
+{
+    *b = EgressBlock{};
+    std::unique_lock<std::mutex> lk(mu);
+    if (!open) return fail(PEBBLEGPU_E_INVALID, "the ring is not open");
+    b->rows = rows;
+    b->format = format;
+    if (read == head) return 0;  // nothing queued
+    EgressSlot &g = slot[read % n_slots];
+    if (g.has_copy) {
+        const hipEvent_t ev = g.copied;
+        const uint64_t seq = read;
+        reader_waiting = true;
+        lk.unlock();  // the wait is on this slot's event alone, and not under the lock: the process thread goes on queueing
+        hipError_t q = hipSetDevice(device);
+        if (q == hipSuccess) q = wait ? hipEventSynchronize(ev) : hipEventQuery(ev);
+        lk.lock();
+        reader_waiting = false;
+        cv.notify_all();
+        if (q == hipErrorNotReady) return 0;
+        PG_HIP(q);
+        if (!open || read != seq) return fail(PEBBLEGPU_E_INVALID, "the ring was closed, or read by a second reader, during the wait");
+    }
+    g.handed = true;
+    read++;
+    b->call = g.call;
+    b->samples = g.samples;
+    b->pitch_bytes = g.pitch_bytes;
+    b->host = g.h;
+    b->dropped_before = g.dropped_before;
+    b->rows = rows;
+    b->format = format;
+    return 0;
+}
+
+int EgressRing::finish(uint64_t call_index)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    if (!open) return fail(PEBBLEGPU_E_INVALID, "the ring is not open");
+    if (tail == read) return fail(PEBBLEGPU_E_INVALID, "no block has been handed out that is still unreleased");
+    EgressSlot &g = slot[tail % n_slots];
+    if (g.call != call_index)
+        return fail(PEBBLEGPU_E_INVALID, "blocks are released oldest first: call %llu is next, not %llu", (unsigned long long)g.call, (unsigned long long)call_index);
+    g.queued = g.handed = false;
+    tail++;
+    return 0;
+}
+
+// ---- the receiver's two rings ----
+static int check_slots(uint32_t n_slots)
+{
+    if (n_slots < kEgressMinSlots || n_slots > kEgressMaxSlots)
+        return fail(PEBBLEGPU_E_INVALID, "n_slots %u: a ring has %u..%u slots", n_slots, kEgressMinSlots, kEgressMaxSlots);
+    return 0;
+}
+
+int Receiver::audio_out_open(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots)
+{
+    if (format < 0 || format >= kAudioFormats) return fail(PEBBLEGPU_E_INVALID, "unknown audio format %d", format);
+    if (int rc = check_slots(n_slots)) return rc;
+    if (channels && n_channels == 0) return fail(PEBBLEGPU_E_INVALID, "an empty channel list");
+    std::vector<uint32_t> sel;
+    if (!channels) {
+        for (uint32_t c = 0; c < C; c++) sel.push_back(c);
+    } else {
+        std::vector<char> seen(C, 0);
+        for (uint32_t i = 0; i < n_channels; i++) {
+            if (channels[i] >= C) return fail(PEBBLEGPU_E_INVALID, "channel %u out of range", channels[i]);
+            if (seen[channels[i]]) return fail(PEBBLEGPU_E_INVALID, "channel %u is listed twice", channels[i]);
+            seen[channels[i]] = 1;
+            sel.push_back(channels[i]);
+        }
+    }
+    std::lock_guard<std::mutex> g(mu_);
+    if (aout_.open) return fail(PEBBLEGPU_E_INVALID, "the audio ring is already open");
+    PG_HIP(hipSetDevice(device));
+    const uint64_t max_n = audio_rate ? (uint64_t)rs_pitch : (uint64_t)audio.cap;
+    if (!d_aout_tab_) PG_HIP(hipMalloc((void **)&d_aout_tab_, sizeof(EgressRow) * C));
+    std::lock_guard<std::mutex> lk(aout_.mu);
+    if (int rc = aout_.open_ring(n_slots, (uint32_t)sel.size(), kAudioBytes[format], max_n, (uint32_t)format)) {
+        aout_.release();
+        return rc;
+    }
+    aout_format_ = format;
+    aout_sel_ = sel;
+    aout_tab_dirty_ = true;
+    return 0;
+}
+
+int Receiver::audio_out_close()
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (!aout_.open) return fail(PEBBLEGPU_E_INVALID, "the audio ring is not open");
+    if (int rc = sync()) return rc;
+    aout_.close_ring();
+    return 0;
+}
+
+int Receiver::set_audio_level(uint32_t ch, float gain, int mute)
+{
+    if (ch >= C) return fail(PEBBLEGPU_E_INVALID, "channel %u out of range", ch);
+    if (!(gain >= 0.f) || !(gain <= 3.402823466e38f)) return fail(PEBBLEGPU_E_INVALID, "gain must be finite and >= 0");
+    std::lock_guard<std::mutex> g(mu_);
+    if (levels_.size() != C) levels_.assign(C, Level{});
+    levels_[ch].gain = gain;
+    levels_[ch].mute = mute != 0;
+    aout_tab_dirty_ = true;
+    return 0;
+}
+
+// the rows' table for the coming call.  Rare (open, a level change): both streams are drained first, since the packing kernel of an
+// earlier call may still be reading the table -- the route the call then takes is the one it would have taken anyway
+int Receiver::upload_audio_table()
+{
+    if (levels_.size() != C) levels_.assign(C, Level{});
+    std::vector<EgressRow> tab(aout_sel_.size());
+    for (size_t r = 0; r < tab.size(); r++) {
+        const Level &l = levels_[aout_sel_[r]];
+        tab[r] = EgressRow{l.gain / 100.f, l.mute ? 1 : 0, (int)aout_sel_[r], 0};  // gain / 100, audiopa.cpp:323
+    }
+    PG_HIP(hipStreamSynchronize(stream_));
+    PG_HIP(hipStreamSynchronize(chain_stream_));
+    PG_HIP(hipMemcpy(d_aout_tab_, tab.data(), sizeof(EgressRow) * tab.size(), hipMemcpyHostToDevice));
+    aout_tab_dirty_ = false;
+    return 0;
+}
+
+// behind the last writer of the call's audio buffer, on its stream: one launch, one event; n == 0 (closed squelch, tune-only): nothing
+int Receiver::queue_audio_block(hipStream_t s, uint64_t n)
+{
+    EgressSlot *g = aout_.begin();
+    if (!g) return 0;
+    if (int rc = run_audio_pack(s, audio_ptr(), audio_pitch(), (long long)n, d_aout_tab_, aout_.rows, aout_format_, g->d, EgressRing::row_pitch(n, aout_.bytes_per_sample)))
+        return rc;
+    return aout_.commit(g, s, n);
+}
+
+// where the RAW_IQ tap's copy sits: behind the generator, ahead of the conditioners, on the main stream
+int Receiver::queue_record_block(hipStream_t s, const float2 *iq, const RawSrc *raw, uint64_t n)
+{
+    EgressSlot *g = rec_.begin();
+    if (!g) return 0;
+    if (int rc = run_iq_record(s, iq, (long long)n, raw, (long long)n, S, g->d, EgressRing::row_pitch(n, 4))) return rc;
+    return rec_.commit(g, s, n);
+}
+
+static void fill_block(pebblegpu_audio_block *b, const EgressBlock &e)
+{
+    b->format = e.format;
+    b->call_index = e.call;
+    b->host = e.host;
+    b->samples_per_channel = e.host ? e.samples : 0;
+    b->pitch_bytes = e.host ? e.pitch_bytes : 0;
+    b->n_channels = e.rows;
+    b->dropped_before = e.host ? e.dropped_before : 0;
+}
+
+int Receiver::audio_out_next(int wait, pebblegpu_audio_block *b)
+{
+    EgressBlock e;
+    if (int rc = aout_.next(device, wait, &e)) return rc;
+    fill_block(b, e);
+    return 0;
+}
+int Receiver::audio_out_release(uint64_t call_index) { return aout_.finish(call_index); }
+int Receiver::audio_out_dropped(uint64_t *blocks)
+{
+    std::lock_guard<std::mutex> lk(aout_.mu);
+    if (!aout_.open) return fail(PEBBLEGPU_E_INVALID, "the audio ring is not open");
+    *blocks = aout_.dropped;
+    return 0;
+}
+
+int Receiver::record_open(uint32_t n_slots)
+{
+    if (int rc = check_slots(n_slots)) return rc;
+    std::lock_guard<std::mutex> g(mu_);
+    if (rec_.open) return fail(PEBBLEGPU_E_INVALID, "the recording ring is already open");
+    PG_HIP(hipSetDevice(device));
+    std::lock_guard<std::mutex> lk(rec_.mu);
+    if (int rc = rec_.open_ring(n_slots, S, 4, (uint64_t)max_sf * superframe, PEBBLEGPU_AUDIO_S16)) {
+        rec_.release();
+        return rc;
+    }
+    touched_ = true;  // the next call joins its two pipelines first (it runs on one stream from here on, as with a tap)
+    return 0;
+}
+
+int Receiver::record_close()
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (!rec_.open) return fail(PEBBLEGPU_E_INVALID, "the recording ring is not open");
+    if (int rc = sync()) return rc;
+    rec_.close_ring();
+    touched_ = true;
+    return 0;
+}
+
+int Receiver::record_next(int wait, pebblegpu_audio_block *b)
+{
+    EgressBlock e;
+    if (int rc = rec_.next(device, wait, &e)) return rc;
+    fill_block(b, e);
+    return 0;
+}
+int Receiver::record_release(uint64_t call_index) { return rec_.finish(call_index); }
+
+}  // namespace pg

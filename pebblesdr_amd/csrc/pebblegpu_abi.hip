@@ -381,4 +381,90 @@ int pebblegpu_receiver_spectrum_frames(const pebblegpu_receiver *h, int zoomed, 
     return h->rx.spectrum_frames(zoomed != 0, idx, cap, n);
 }
 
+// ---- host egress (egress.h, egress.hip) ----
+static int block_struct(const pebblegpu_audio_block *b)
+{
+    if (!b) return fail(PEBBLEGPU_E_INVALID, "null pebblegpu_audio_block");
+    if (b->struct_size != sizeof(pebblegpu_audio_block)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_audio_block size mismatch (ABI %d)", PEBBLEGPU_ABI_VERSION);
+    return 0;
+}
+int pebblegpu_receiver_audio_out_open(pebblegpu_receiver *h, int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.audio_out_open(format, channels, n_channels, n_slots);
+}
+int pebblegpu_receiver_audio_out_close(pebblegpu_receiver *h)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.audio_out_close();
+}
+int pebblegpu_set_audio_level(pebblegpu_receiver *h, uint32_t channel, float gain, int mute)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.set_audio_level(channel, gain, mute);
+}
+int pebblegpu_receiver_audio_out_next(pebblegpu_receiver *h, int wait, pebblegpu_audio_block *b)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    if (int rc = block_struct(b)) return rc;
+    return h->rx.audio_out_next(wait, b);
+}
+int pebblegpu_receiver_audio_out_release(pebblegpu_receiver *h, uint64_t call_index)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.audio_out_release(call_index);
+}
+int pebblegpu_receiver_audio_out_dropped(const pebblegpu_receiver *h, uint64_t *blocks)
+{
+    if (!h || !blocks) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return const_cast<pebblegpu_receiver *>(h)->rx.audio_out_dropped(blocks);
+}
+int pebblegpu_audio_out_convert(int format, float gain, int mute, const float *lr, uint64_t n, void *out)
+{
+    if (format < 0 || format >= pg::kAudioFormats) return fail(PEBBLEGPU_E_INVALID, "unknown audio format %d", format);
+    if (!(gain >= 0.f) || !(gain <= 3.402823466e38f)) return fail(PEBBLEGPU_E_INVALID, "gain must be finite and >= 0");
+    if (n && (!lr || !out)) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    const float g = gain / 100.f;
+    for (uint64_t i = 0; i < n; i++) {
+        const float l = mute ? 0.f : pg::audio_out_sample(lr[2 * i], g), r = mute ? 0.f : pg::audio_out_sample(lr[2 * i + 1], g);
+        if (format == PEBBLEGPU_AUDIO_F32) {
+            ((float *)out)[2 * i] = l;
+            ((float *)out)[2 * i + 1] = r;
+        } else if (format == PEBBLEGPU_AUDIO_S16) {
+            ((int16_t *)out)[2 * i] = pg::audio_out_s16(l);
+            ((int16_t *)out)[2 * i + 1] = pg::audio_out_s16(r);
+        } else {
+            ((int16_t *)out)[i] = pg::audio_out_s16(l);
+        }
+    }
+    return 0;
+}
+int pebblegpu_receiver_record_open(pebblegpu_receiver *h, uint32_t n_slots)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.record_open(n_slots);
+}
+int pebblegpu_receiver_record_close(pebblegpu_receiver *h)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.record_close();
+}
+int pebblegpu_receiver_record_next(pebblegpu_receiver *h, int wait, pebblegpu_audio_block *b)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    if (int rc = block_struct(b)) return rc;
+    return h->rx.record_next(wait, b);
+}
+int pebblegpu_receiver_record_release(pebblegpu_receiver *h, uint64_t call_index)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.record_release(call_index);
+}
+int pebblegpu_iq_record_convert(const float *iq, uint64_t n, int16_t *out)
+{
+    if (n && (!iq || !out)) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    for (uint64_t i = 0; i < 2 * n; i++) out[i] = pg::iq_record_s16(iq[i]);
+    return 0;
+}
+
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include "../../include/pebblegpu.h"
 #include "common.h"
 #include "design.h"
+#include "egress.h"
 #include "ingest.h"
 #include "params.h"
 #include "tuning.h"
@@ -680,6 +681,19 @@ public:
     // (zoom = true; edges per channel), queued behind that call's transform and ahead of the next call's: out [stream][n][x_pixels]
     int map_spectrum(bool zoom, const int32_t *edges, bool per_stream, int32_t y_pixels, int32_t x_pixels, double max_db, double min_db,
                      uint32_t first, uint32_t n, uint32_t step, int32_t *d_out);
+    // host egress (egress.h): the audio output stage (Audio::SendToOutput, receiver.cpp:1029-1035) and IQ recording (receiver.cpp:800-801),
+    // each a ring of pinned slots filled behind the call; open / close / the level setter take the handle's lock, the reader's
+    // next / release take the ring's own
+    int audio_out_open(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots);
+    int audio_out_close();
+    int set_audio_level(uint32_t ch, float gain, int mute);  // Receiver::m_gain (0..100), m_mute
+    int audio_out_next(int wait, pebblegpu_audio_block *b);
+    int audio_out_release(uint64_t call_index);
+    int audio_out_dropped(uint64_t *blocks);
+    int record_open(uint32_t n_slots);
+    int record_close();
+    int record_next(int wait, pebblegpu_audio_block *b);
+    int record_release(uint64_t call_index);
     int sync();
     int close_timing();  // records the end event a side-by-side call left out (no-op otherwise)
     const char *kernel_name(int which) const;  // the kernels behind pebblegpu_receiver_last_ms's groups, as last run
@@ -792,6 +806,16 @@ private:
     IngestRing ext_ingest_;           // device twins of somebody else's pinned slots (ingest_wait / _upload / process_uploaded)
     std::vector<float> h_frame_, h_out_;
     uint64_t acc_frames_ = 0;
+    EgressRing aout_, rec_;           // the audio output ring and the recording ring (egress.h); closed: a call queues nothing for them
+    int aout_format_ = 0;
+    std::vector<uint32_t> aout_sel_;  // row r of a block is channel aout_sel_[r]
+    struct Level { float gain = 100.f; bool mute = false; };  // Receiver::m_gain / m_mute defaults
+    std::vector<Level> levels_;       // per channel (kept while the ring is closed)
+    EgressRow *d_aout_tab_ = nullptr; // [C] the selected rows' (g, mute, source row)
+    bool aout_tab_dirty_ = false;
+    int upload_audio_table();
+    int queue_audio_block(hipStream_t s, uint64_t n);
+    int queue_record_block(hipStream_t s, const float2 *iq, const RawSrc *raw, uint64_t n);
 };
 
 }  // namespace pg

@@ -118,6 +118,9 @@ Receiver::~Receiver()
     for (hipEvent_t e : sync_ev_) if (e) (void)hipEventDestroy(e);
     ingest_.release();
     ext_ingest_.release();
+    aout_.release();
+    rec_.release();
+    if (d_aout_tab_) (void)hipFree(d_aout_tab_);
     if (d_zoom) (void)hipFree(d_zoom);
     if (map_ev_) (void)hipEventDestroy(map_ev_);
     agc_.release(); resamp_.release(); cond_.release(); anf_.release();
@@ -577,7 +580,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     // read that buffer).  The decimator of a bank leaves the vector units idle two thirds of the time (one wave per SIMD, bound by
     // its own instruction stream): the band-pass of the previous call fits beside it.  Results are complete after sync().
     const bool bank_pipe = bank_pipe_ok_ && with_chain && !with_spectrum && !profile_detail && squelch_db_ <= -120.0 && !bank_gate_ && !zoom_bins &&
-                           !cond_.any && !cond_.dirty && !tb_.any() && !taps_ && dec_.double_out();
+                           !cond_.any && !cond_.dirty && !tb_.any() && !taps_ && !rec_.open && dec_.double_out();
     // (a call with the test bench's generator on is staged through a buffer successive calls share, as a conditioned call is: it may run its
     // chain beside its own display transform -- the kernels of the same call without a generator, so that injecting on the device and
     // feeding the summed stream give the same audio bit for bit -- but never pipelined with its neighbours, and never raw-fused)
@@ -592,7 +595,12 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     if (int rc = apply_controls(plain ? chain_stream_ : stream_)) return rc;
     touched_ = false;
     if (int rc = cond_.apply(stream_)) return rc;
+    if (aout_.open && aout_tab_dirty_) { if (int rc = upload_audio_table()) return rc; }
     bool staged = false;  // a conversion pass was queued in front of the call
+    // recording (egress.h): with the generator off a raw call is recorded from the raw samples themselves, whichever way the chain takes
+    // them in (the same loader and scale as the conversion pass: the same values, and the recording needs no float2 copy of its own)
+    const RawSrc rec_raw = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
+    const bool rec_from_raw = raw != nullptr && !tb_.any();
     if (raw) {
         // Raw device-format input: when the call's first kernels convert in their own loads (the 8192-bin display transform
         // and the one-channel first stage beside it) there is no float2 copy of the stream at all; otherwise normalizeIQ runs
@@ -713,6 +721,8 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         else PG_HIP(hipMemcpyAsync(d_tap_[PEBBLEGPU_TAP_RAW_IQ], tap_iq, sizeof(float2) * (size_t)S * n, hipMemcpyDeviceToDevice, stream_));
         tap_n_[PEBBLEGPU_TAP_RAW_IQ] = n;
     }
+    // WavFile::WriteSamples(nextStep, numSamples), receiver.cpp:800-801: the same samples, at the same place in the queue
+    if (rec_.open && with_chain) { if (int rc = queue_record_block(stream_, tap_iq, rec_from_raw ? &rec_raw : nullptr, n)) return rc; }
     const bool mid = with_spectrum || profile_detail || side;
     if (mid) PG_HIP(hipEventRecord(ev[1], stream_));
     tm.detailed[(tm.calls - 1) % Timers::kRing] = profile_detail;
@@ -895,6 +905,9 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
             last_audio_n = (uint64_t)n_rs;
         }
     }
+    // Audio::SendToOutput, receiver.cpp:1029-1035: behind the last writer of the audio buffer on whichever stream that was (the
+    // resampler, the demodulators, the gate's clears); the next call's writers follow on the same stream or behind its end
+    if (aout_.open) { if (int rc = queue_audio_block(cs, last_audio_n)) return rc; }
     if (profile_detail) PG_HIP(hipEventRecord(ev[5], cs));
     if (bank_pipe) {
         std::vector<TailJob> jobs;
@@ -1074,6 +1087,8 @@ int Receiver::process_iq(const double *iq, uint16_t n, double *audio_out, uint32
         return fail(PEBBLEGPU_E_UNSUPPORTED, "the input conditioners run on the batched device path (pebblegpu_receiver_process) only");
     if (tb_.any() || taps_)  // (here `iq` is a host CPX *: the host injects and displays itself)
         return fail(PEBBLEGPU_E_UNSUPPORTED, "the test bench's generator and taps run on the batched device path (pebblegpu_receiver_process) only");
+    if (aout_.open || rec_.open)  // (this entry point returns its audio itself, and the host holds the frame it passes in)
+        return fail(PEBBLEGPU_E_UNSUPPORTED, "the audio and recording rings follow the batched device path (pebblegpu_receiver_process) only: close them first");
     PG_HIP(hipSetDevice(device));
     if (!d_stage_in_) PG_HIP(hipMalloc((void **)&d_stage_in_, sizeof(float2) * superframe));
     h_frame_.resize((size_t)nf * 2);
