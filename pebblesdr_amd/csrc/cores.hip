@@ -8,6 +8,7 @@
 #include "kernels_fastfir.h"
 #include "kernels_frontend.h"
 #include <algorithm>
+#include "bank_geom.h"
 #include "kernels_fused_dec.h"
 #include "kernels_bank_dec.h"
 #include "kernels_spectrum.h"
@@ -535,31 +536,12 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
     }
     if (osc.dyn_epoch != dyn_epoch_seen) dyn_valid = false;
     dyn_epoch_seen = osc.dyn_epoch;
-    // One wave per SIMD pays the fewest warm-up blocks; two overlap what a lone wave leaves idle (measured on hb11 x 4, 15/19/31: 1200
-    // clocks per block alone, 2075 for each of two) -- worth it once a chunk is long against its warm-up: from 128 outputs per chunk on
-    int waves = tun.bank_waves;
-    // (a receiver that runs two-stage calls keeps one wave per SIMD at every batch size: the previous call's band-pass needs the other
-    // half of the register file beside it -- 0.2385 ms per configs[2] call of 32 super-frames against 0.2546, 0.875 against 0.905 at 128)
-    if (waves == 0) waves = (!fin2.base && cdiv(len_out, 2 * std::max(1LL, 1024LL / g32)) >= 128) ? 2 : 1;
-    if (waves > bv->minw) waves = bv->minw;  // (the instances with the longest halfbands need more than half a SIMD's registers)
-    long long pairs_target = 1024LL * waves / g32;
-    if (cic) pairs_target /= 2;  // (twelve pairs of lines per output instead of one window: the blocks are bound by what they fetch, and every chunk
-                                 // fetches its 30 warm-up blocks again -- measured on configs[3]: 0.081 ms at 1024 waves, 0.075 at 512, 0.12 at 256)
-    if (pairs_target < 1) pairs_target = 1;
-    // a power of two (it divides the call's 2048 k outputs: the last chunk is a whole one), the nearest to the target above
-    long long L = 16;
-    if (tun.fused_l > 0) {
-        while (L * 2 <= tun.fused_l) L *= 2;
-    } else {
-        const long long want = cdiv(len_out, 2 * pairs_target);
-        while (L < want && L < 2048) L *= 2;
-    }
-    while (len_out % L != 0 && L > 16) L /= 2;
-    while (2 * L <= warm) L *= 2;  // (only the first two chunks may reach in front of the call's start)
+    // waves per SIMD, outputs per chunk, chunk pairs and workgroups: bank_geom.h
+    const BankGeom geo = bank_geometry(len_out, C, cic, warm, bv->minw, fin2.base != nullptr, tun.bank_waves, tun.fused_l, tun.bank_hsplit);
+    const long long L = geo.L;
     const int S0 = first.stride, Sfs = cic ? S0 * wide_stride : S0;  // input samples per first-stage (hb11) output
-    const long long pairs = cdiv(cdiv(len_out, L), 2);
     const int hist_split = tun.bank_hsplit;
-    const unsigned n_wg = (unsigned)(8 * cdiv(pairs, 8) * cdiv(g32, 4) + cdiv(g32, 4) * hist_split);  // main workgroups, then the history waves'
+    const unsigned n_wg = geo.n_wg;
     if (tun.bank_clk && clk_cap < (size_t)n_wg * 16) {
         if (d_clk) (void)hipFree(d_clk);
         d_clk = nullptr;

@@ -1744,9 +1744,10 @@ def test_configs3_shard_over_three_calls(gpu_lib, oracle_mod):
 @pytest.mark.parametrize("fs,C", [(1024000, 3), (2400000, 17), (3200000, 1), (5000000, 17), (8000000, 3), (10000000, 1), (10000000, 17),
                                   (16000000, 3), (25000000, 17), (40000000, 1), (40000000, 3)])
 def test_chain_sweep_over_rates_and_bank_sizes(gpu_lib, oracle_mod, fs, C):
-    """Every first-stage form the ladder of decimator.cpp:74-146 produces between 1 and 40 Msps -- hb11 merged 2/4/8/16 times
+    """First-stage forms the ladder of decimator.cpp:74-146 produces between 1 and 40 Msps -- hb11 merged 2/4/8/16 times
     (LDS-tiled for few channels, in registers for a bank, the stride-16 one peeled off the cascade) and CIC3 merged 1/2/3 times
-    in front of hb11 x 16 (the fused register front end) -- for one channel, a few and a ragged bank off one shared stream: USB
+    in front of hb11 x 16 (the fused register front end) -- on the routes one channel and a few channels take, and a one-group
+    bank on some of them (the banks' own kernel, every instance and stride of it: tests/test_bank_decimator_gpu.py): USB
     audio of the first and last channel against Mixer -> Decimator -> gain restore -> FastFIR restated by the oracle, three
     calls.  The oracle is fed whole super-frames so that none of its stages sees fewer samples than taps."""
     import pebblesdr_amd as P
