@@ -882,6 +882,91 @@ int pebblegpu_receiver_record_release(pebblegpu_receiver *rx, uint64_t call_inde
 /* host twin: n IQ samples of interleaved float I, Q -> n PCM16 pairs */
 int pebblegpu_iq_record_convert(const float *iq, uint64_t n, int16_t *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Host egress for a stream bank: the band-passed IQ of selected streams and the display rows of the spectra a call computed, through
+ * the same rings of pinned slots (above).  Without a ring the only way to a call's results is
+ * pebblegpu_streambank_filtered / _spectrum / _map_spectrum + pebblegpu_streambank_synchronize + pebblegpu_memcpy_d2h, which drain the
+ * device after every call; with the rings a host runs a bank from pinned slots in (pebblegpu_streambank_ingest_*) to pinned slots out
+ * with no synchronize in its loop and a reader on another thread.
+ *
+ * Both rings follow the audio ring's rules word for word.  ONE block per accepted process call (_process, _process_raw,
+ * _process_ingested), always: indices are 0-based from the ring's open and contiguous; a call that does not run the ring's producer
+ * (`what` without bit 0 for the IQ ring, without bit 1 for the display ring, n_samples == 0) gives a block of 0 samples / 0 rows and
+ * queues no copy; a refused call gives no block and does not advance the index.  A FULL RING DROPS, IT NEVER REFUSES AND NEVER STALLS:
+ * the call runs unchanged, its block is dropped and counted (_dropped, dropped_before); "free" is host bookkeeping only, so what is
+ * delivered does not depend on the device's timing, and the band-pass overlap, the spectrum's carried amplitudes and the update timer
+ * never depend on the reader.  The packing kernel is queued on the bank's stream behind the call's end (behind the join when
+ * PEBBLEGPU_SB_SIDE=1 put the band-pass on the second stream), ahead of the next call's kernels, which overwrite the buffers it reads;
+ * the copy travels on the ring's own stream, and nothing the next call queues waits for it.  An open ring changes no route
+ * (pebblegpu_streambank_kernel_name reports the same strings) and leaves pebblegpu_streambank_filtered / _spectrum / _map_spectrum /
+ * _spectrum_frames unchanged: it adds one launch and one event per ring to a call, however many streams are selected (the selection is
+ * a table on the device, written at open), and no float2 copy of anything.  One reader per ring, which may run on another thread;
+ * _next(wait) blocks on that slot's event only; _release takes the oldest handed-out block; n_slots: 2..8.
+ *
+ * Refused at open with PEBBLEGPU_E_INVALID, leaving the handle as it was: duplicate or out-of-range streams (or an empty list), n_slots
+ * outside 2..8, an unknown format, a second open of the same ring; for the display ring also a map the mappings refuse (x_pixels or
+ * y_pixels <= 0, max_db == min_db), a missing map for the two mapped formats, and a bank created with spectrum_bins == 0.  With
+ * PEBBLEGPU_E_SIZE: a ring whose slots would pin more than 1 GiB of host memory in total (pinned memory is a resource of the whole
+ * machine: select fewer streams, a smaller max_rows, or set the update gate).  _close waits for the bank's queued work, then for a
+ * reader that is inside _next on another thread, then frees the ring; pebblegpu_streambank_destroy closes open rings.
+ * ---------------------------------------------------------------------------------------------- */
+/* The IQ ring.  streams: row r of every block is stream streams[r] -- a subset in any order; NULL: all streams, in order (n_streams is
+ * then ignored).  format: PEBBLEGPU_AUDIO_F32 -- the float2 rows of pebblegpu_streambank_filtered verbatim, I then Q (no gain and no
+ * clip: this is not the audio stage); PEBBLEGPU_AUDIO_S16 -- PCM16 pairs by the recording ring's rule, WavFile::WriteSamples
+ * (pebblelib/wavfile.cpp:377-396): (int16_t)((double)v * 32767), truncating, saturating to +-32767 where the reference's conversion is
+ * undefined, NaN -> 0; pebblegpu_iq_record_convert is its host twin.  PEBBLEGPU_AUDIO_S16_MONO is refused.  Blocks: n_channels = the
+ * selected streams, samples_per_channel = the call's n_samples. */
+int pebblegpu_streambank_iq_out_open(pebblegpu_streambank *sb, int format, const uint32_t *streams, uint32_t n_streams, uint32_t n_slots);
+int pebblegpu_streambank_iq_out_close(pebblegpu_streambank *sb);
+int pebblegpu_streambank_iq_out_next(pebblegpu_streambank *sb, int wait, pebblegpu_audio_block *b);
+int pebblegpu_streambank_iq_out_release(pebblegpu_streambank *sb, uint64_t call_index);
+int pebblegpu_streambank_iq_out_dropped(const pebblegpu_streambank *sb, uint64_t *blocks);
+
+/* The display ring.  The rows of a block are the spectrum rows ITS call computed for each selected stream: every frame of the call
+ * without an update gate, the gate's selection (which may be empty) with pebblegpu_streambank_set_spectrum_updates, none for a call
+ * without bit 1 of `what`.  A block never repeats a row of an earlier call: after a call that selected nothing the display keeps
+ * showing what the host already has, and the block has 0 rows.  max_rows (0, or more than the bank's max_frames: max_frames) sizes the
+ * slots; a call that computed more rows delivers the LAST max_rows of them (the latest row is what a display shows) and first_row
+ * says where they start: max_rows = 1 is "the latest spectrum of every call".
+ *   PEBBLEGPU_DISPLAY_DB_F32            the float dB rows of pebblegpu_streambank_spectrum, verbatim; map is ignored and may be NULL
+ *   PEBBLEGPU_DISPLAY_PIXELS_I32        FFT::mapFFTToScreen (pebblelib/fft.cpp:400-534) of each row with map: the values
+ *                                       pebblegpu_streambank_map_spectrum writes, bit for bit (one computation, see pebblegpu_screen_map)
+ *   PEBBLEGPU_DISPLAY_WATERFALL_ARGB32  SpectrumWidget::drawWaterfall (application/spectrumwidget.cpp:1098-1118) on those pixels: pixel
+ *                                       value v becomes m_spectrumColors[255 - v] as 0xFFRRGGBB -- QColor::setRgb (alpha 255) in QRgb
+ *                                       layout.  Requires map->y_pixels == 255, the value every waterfall call site passes
+ *                                       (spectrumwidget.cpp:1285-1293, 1302-1349); anything else is PEBBLEGPU_E_INVALID
+ * The palette is the constructor's loop (spectrumwidget.cpp:97-113), integer arithmetic as written, with one deviation: the reference
+ * allocates 255 entries, writes entry 255 and reads it for v = 0, both out of bounds; the library's table has 256 entries with entry
+ * 255 = what the loop computes for i = 255. */
+typedef enum {
+    PEBBLEGPU_DISPLAY_DB_F32 = 0,
+    PEBBLEGPU_DISPLAY_PIXELS_I32 = 1,
+    PEBBLEGPU_DISPLAY_WATERFALL_ARGB32 = 2
+} pebblegpu_display_format;
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(pebblegpu_display_block), set by the caller */
+    uint32_t format;               /* pebblegpu_display_format */
+    uint64_t call_index;           /* which process call since open */
+    const void *host;              /* row j of selected stream r at host + r * stream_pitch_bytes + j * row_pitch_bytes; NULL: no block */
+    uint32_t rows_per_stream;      /* may be 0 */
+    uint32_t first_row;            /* index, among the rows the call computed, of the block's row 0 */
+    uint32_t row_elems;            /* bins (DB_F32) or x_pixels; 4 bytes each */
+    uint32_t n_streams;            /* the selected streams */
+    uint32_t dropped_before;       /* blocks dropped between the previous queued block and this one */
+    uint32_t reserved;
+    uint64_t row_pitch_bytes;      /* a multiple of 16 (x_pixels need not be a multiple of 4) */
+    uint64_t stream_pitch_bytes;   /* rows_per_stream * row_pitch_bytes */
+} pebblegpu_display_block;
+int pebblegpu_streambank_display_open(pebblegpu_streambank *sb, int format, const pebblegpu_screen_map *map, const uint32_t *streams,
+                                      uint32_t n_streams, uint32_t max_rows, uint32_t n_slots);
+int pebblegpu_streambank_display_close(pebblegpu_streambank *sb);
+int pebblegpu_streambank_display_next(pebblegpu_streambank *sb, int wait, pebblegpu_display_block *b);
+int pebblegpu_streambank_display_release(pebblegpu_streambank *sb, uint64_t call_index);
+int pebblegpu_streambank_display_dropped(const pebblegpu_streambank *sb, uint64_t *blocks);
+/* host twin of the waterfall's colour rule (the same inline function the packing kernel runs; no device): n pixel values -> n
+ * 0xFFRRGGBB words.  A pixel outside 0..255 is PEBBLEGPU_E_INVALID. */
+int pebblegpu_waterfall_colors(const int32_t *pixels, uint64_t n, uint32_t *argb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ from .binding import (  # noqa: F401
     MorseStation, morse_station, morse_station_plan, morse_station_marks, MORSE_MAX_STATIONS,
     MultiBank, multibank_plan, MULTIBANK_MAX_SHARDS, MULTIBANK_SPECTRUM_SHARD0,
     AUDIO_F32, AUDIO_S16, AUDIO_S16_MONO, AudioBlock, audio_out_convert, iq_record_convert,
+    DISPLAY_DB_F32, DISPLAY_PIXELS_I32, DISPLAY_WATERFALL_ARGB32, DisplayBlock, waterfall_colors,
 )
 from .steps import Mixer, Decimator, DownConvert, FastFIR, Demod, Spectrum, Morse  # noqa: F401
 
@@ -21,5 +22,5 @@ __all__ = [
     "PebbleGpuError", "load_library", "library_path", "ReceiverBank", "StreamBank", "DeviceBuffer", "ScreenMap", "screen_map",
     "Mixer", "Decimator", "DownConvert", "FastFIR", "Demod", "Spectrum", "Morse", "morse_token_to_dotdash",
     "SigGen", "Sweep", "sweep", "sweep_plan", "MorseStation", "morse_station", "morse_station_plan",
-    "MultiBank", "multibank_plan", "audio_out_convert", "iq_record_convert",
+    "MultiBank", "multibank_plan", "audio_out_convert", "iq_record_convert", "DisplayBlock", "waterfall_colors",
 ]

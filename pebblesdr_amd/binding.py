@@ -52,6 +52,10 @@ SYMBOLS = [
     "pebblegpu_receiver_audio_out_release", "pebblegpu_receiver_audio_out_dropped", "pebblegpu_audio_out_convert",
     "pebblegpu_receiver_record_open", "pebblegpu_receiver_record_close", "pebblegpu_receiver_record_next", "pebblegpu_receiver_record_release",
     "pebblegpu_iq_record_convert",
+    "pebblegpu_streambank_iq_out_open", "pebblegpu_streambank_iq_out_close", "pebblegpu_streambank_iq_out_next", "pebblegpu_streambank_iq_out_release",
+    "pebblegpu_streambank_iq_out_dropped",
+    "pebblegpu_streambank_display_open", "pebblegpu_streambank_display_close", "pebblegpu_streambank_display_next",
+    "pebblegpu_streambank_display_release", "pebblegpu_streambank_display_dropped", "pebblegpu_waterfall_colors",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
@@ -263,6 +267,37 @@ def _block_array(b):
     return out[:, :, 0] if per == 1 else out
 
 
+DISPLAY_DB_F32, DISPLAY_PIXELS_I32, DISPLAY_WATERFALL_ARGB32 = range(3)  # pebblegpu_display_format
+_DISPLAY_DTYPE = {DISPLAY_DB_F32: np.float32, DISPLAY_PIXELS_I32: np.int32, DISPLAY_WATERFALL_ARGB32: np.uint32}
+
+
+class DisplayBlock(C.Structure):
+    """pebblegpu_display_block: the display rows one stream-bank call computed, in pinned host memory"""
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_uint32), ("call_index", C.c_uint64), ("host", C.c_void_p),
+                ("rows_per_stream", C.c_uint32), ("first_row", C.c_uint32), ("row_elems", C.c_uint32), ("n_streams", C.c_uint32),
+                ("dropped_before", C.c_uint32), ("reserved", C.c_uint32), ("row_pitch_bytes", C.c_uint64), ("stream_pitch_bytes", C.c_uint64)]
+
+
+def _display_array(b):
+    """a copy of the block's rows: [streams, rows, row_elems] float32 (dB), int32 (pixels) or uint32 (0xFFRRGGBB)"""
+    dt = _DISPLAY_DTYPE[int(b.format)]
+    S, R, E = int(b.n_streams), int(b.rows_per_stream), int(b.row_elems)
+    if not R:
+        return np.zeros((S, 0, E), dtype=dt)
+    sp, rp = int(b.stream_pitch_bytes), int(b.row_pitch_bytes)
+    raw = np.ctypeslib.as_array(C.cast(b.host, C.POINTER(C.c_uint8)), shape=(S * sp,)).reshape(S, sp)[:, : R * rp].reshape(S, R, rp)
+    return raw[:, :, : 4 * E].copy().view(dt).reshape(S, R, E)
+
+
+def waterfall_colors(pixels, lib=None):
+    """the host twin of the waterfall's colour rule (SpectrumWidget::drawWaterfall): int32 pixel values 0..255 -> uint32 0xFFRRGGBB, same shape"""
+    L = lib or load_library()
+    px = np.ascontiguousarray(pixels, dtype=np.int32)
+    out = np.zeros(px.shape, dtype=np.uint32)
+    check(L, L.pebblegpu_waterfall_colors(px.ctypes.data_as(C.c_void_p), px.size, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def audio_out_convert(fmt, gain, mute, lr, lib=None):
     """the host twin of the audio packing kernel: lr float32 [n, 2] (or complex64 [n]) -> [n, 2] float32 / int16, [n] int16 for the mono format"""
     L = lib or load_library()
@@ -465,6 +500,18 @@ def _declare(L):
     L.pebblegpu_receiver_record_next.argtypes = [vp, i32, blk]
     L.pebblegpu_receiver_record_release.argtypes = [vp, u64]
     L.pebblegpu_iq_record_convert.argtypes = [vp, u64, vp]
+    dblk = C.POINTER(DisplayBlock)
+    L.pebblegpu_streambank_iq_out_open.argtypes = [vp, i32, u32p, u32, u32]
+    L.pebblegpu_streambank_iq_out_close.argtypes = [vp]
+    L.pebblegpu_streambank_iq_out_next.argtypes = [vp, i32, blk]
+    L.pebblegpu_streambank_iq_out_release.argtypes = [vp, u64]
+    L.pebblegpu_streambank_iq_out_dropped.argtypes = [vp, C.POINTER(u64)]
+    L.pebblegpu_streambank_display_open.argtypes = [vp, i32, smp, u32p, u32, u32, u32]
+    L.pebblegpu_streambank_display_close.argtypes = [vp]
+    L.pebblegpu_streambank_display_next.argtypes = [vp, i32, dblk]
+    L.pebblegpu_streambank_display_release.argtypes = [vp, u64]
+    L.pebblegpu_streambank_display_dropped.argtypes = [vp, C.POINTER(u64)]
+    L.pebblegpu_waterfall_colors.argtypes = [vp, u64, vp]
     return L
 
 
@@ -1114,6 +1161,63 @@ class StreamBank:
             return _download_i32(self.L, self.device, buf.ptr, (self.n_streams, n_frames, int(x_pixels)))
         finally:
             buf.free()
+
+    # ---- host egress: band-passed IQ and display rows through pinned slots ----
+    def _stream_list(self, streams):
+        if streams is None:
+            return None, 0
+        return (C.c_uint32 * max(1, len(streams)))(*[int(c) for c in streams]), len(streams)
+
+    def iq_out_open(self, fmt=AUDIO_F32, streams=None, n_slots=4):
+        """streams: row r of every block is stream streams[r] (None: all, in order); fmt AUDIO_F32 (verbatim) or AUDIO_S16"""
+        arr, n = self._stream_list(streams)
+        check(self.L, self.L.pebblegpu_streambank_iq_out_open(self.h, int(fmt), arr, n, int(n_slots)))
+
+    def iq_out_close(self):
+        check(self.L, self.L.pebblegpu_streambank_iq_out_close(self.h))
+
+    def iq_out_next(self, wait=True):
+        """-> (call_index, dropped_before, copy of the rows: [streams, n, 2] float32 or int16) or None; taken until iq_out_release(call_index)"""
+        b = AudioBlock()
+        b.struct_size = C.sizeof(AudioBlock)
+        check(self.L, self.L.pebblegpu_streambank_iq_out_next(self.h, 1 if wait else 0, C.byref(b)))
+        if not b.host:
+            return None
+        return int(b.call_index), int(b.dropped_before), _block_array(b)
+
+    def iq_out_release(self, call_index):
+        check(self.L, self.L.pebblegpu_streambank_iq_out_release(self.h, int(call_index)))
+
+    def iq_out_dropped(self):
+        n = C.c_uint64()
+        check(self.L, self.L.pebblegpu_streambank_iq_out_dropped(self.h, C.byref(n)))
+        return int(n.value)
+
+    def display_open(self, fmt=DISPLAY_DB_F32, screen=None, streams=None, max_rows=0, n_slots=4):
+        """screen: a ScreenMap (screen_map(...)) for the two mapped formats; max_rows 0: the bank's max_frames"""
+        arr, n = self._stream_list(streams)
+        check(self.L, self.L.pebblegpu_streambank_display_open(self.h, int(fmt), C.byref(screen) if screen is not None else None, arr, n,
+                                                               int(max_rows), int(n_slots)))
+
+    def display_close(self):
+        check(self.L, self.L.pebblegpu_streambank_display_close(self.h))
+
+    def display_next(self, wait=True):
+        """-> (call_index, dropped_before, first_row, copy of the rows [streams, rows, row_elems]) or None; taken until display_release(call_index)"""
+        b = DisplayBlock()
+        b.struct_size = C.sizeof(DisplayBlock)
+        check(self.L, self.L.pebblegpu_streambank_display_next(self.h, 1 if wait else 0, C.byref(b)))
+        if not b.host:
+            return None
+        return int(b.call_index), int(b.dropped_before), int(b.first_row), _display_array(b)
+
+    def display_release(self, call_index):
+        check(self.L, self.L.pebblegpu_streambank_display_release(self.h, int(call_index)))
+
+    def display_dropped(self):
+        n = C.c_uint64()
+        check(self.L, self.L.pebblegpu_streambank_display_dropped(self.h, C.byref(n)))
+        return int(n.value)
 
     def process(self, iq, what=3):
         """iq: complex [streams, n] -> (filtered [S, n] or None, spectrum [S, frames, bins] or None); under an update gate

@@ -1,6 +1,7 @@
 // egress.h -- host egress: ingest.h in the other direction.  A ring of pinned host slots that a small packing kernel, queued behind a
 // process call on the call's own stream, fills through a device staging twin and a copy stream; the host waits for ONE slot's
-// "copied" event, never for the device.  Two users, both in Receiver (egress.hip):
+// "copied" event, never for the device.  Two users in Receiver (egress.hip), two in the stream bank (streambank.hip: the band-passed IQ
+// of selected streams and the display rows of a call's spectra; the ring itself knows neither):
 //   the audio output stage -- Receiver::processAudioData -> Audio::SendToOutput(in, n, m_gain, m_mute), application/receiver.cpp:1029-1035;
 //                             the sample rule is pebblelib/audiopa.cpp:304-343 (the same clip in pebblelib/audioqt.cpp:169-211)
 //   IQ recording           -- if (m_isRecording) m_recordingFile.WriteSamples(nextStep, numSamples), application/receiver.cpp:800-801;
@@ -67,6 +68,7 @@ struct EgressSlot {
     hipEvent_t copied = nullptr;       // behind the copy, on the copy stream (no timing)
     uint64_t call = 0, samples = 0, pitch_bytes = 0;
     uint32_t dropped_before = 0;
+    uint32_t aux = 0;                  // the owner's own word about the block, set before commit() (the display ring: first_row)
     bool queued = false;               // holds a block that has not been released
     bool handed = false;               // ... and next() has handed it out
     bool has_copy = false;             // a copy was queued for it (a block of 0 samples has none)
@@ -75,7 +77,7 @@ struct EgressSlot {
 struct EgressBlock {
     uint64_t call = 0, samples = 0, pitch_bytes = 0;
     const void *host = nullptr;
-    uint32_t dropped_before = 0, rows = 0, format = 0;
+    uint32_t dropped_before = 0, rows = 0, format = 0, aux = 0;
 };
 
 struct EgressRing {
@@ -115,5 +117,9 @@ int run_audio_pack(hipStream_t s, const float2 *audio, long long pitch, long lon
                    uint64_t dst_pitch);
 // rows x n IQ samples (float2 rows of `pitch`, or raw device-format pairs converted as k_normalize_iq converts them) -> PCM16 pairs
 int run_iq_record(hipStream_t s, const float2 *iq, long long pitch, const struct RawSrc *raw, long long n, uint32_t rows, void *dst, uint64_t dst_pitch);
+// rows x n band-passed samples (row r at iq + tab[r] * pitch: the stream bank's selection) -> dst [rows][dst_pitch bytes]: the float2
+// rows verbatim (PEBBLEGPU_AUDIO_F32) or PCM16 pairs by iq_record_s16 (PEBBLEGPU_AUDIO_S16)
+int run_iq_pack(hipStream_t s, const float2 *iq, long long pitch, long long n, const uint32_t *d_tab, uint32_t rows, int format, void *dst, uint64_t dst_pitch);
+int check_egress_slots(uint32_t n_slots);
 
 }  // namespace pg

@@ -98,6 +98,41 @@ static __global__ __launch_bounds__(256) void k_iq_record(const float2 *__restri
     }
 }
 
+// The stream bank's IQ ring: k_iq_record with a row table.  Selected rows of the band-pass output (row r of the block is stream tab[r])
+// as they are (S16 false: two 16-byte loads, two 16-byte stores per work-item) or through iq_record_s16 (four pairs, one 16-byte
+// store).  A call's n is a multiple of the band-pass block, so rows are 16-byte aligned on both sides; anything else goes sample by
+// sample like k_iq_record's ragged end.
+template <bool S16>
+static __global__ __launch_bounds__(256) void k_iq_pack(const float2 *__restrict__ iq, long long pitch, long long n, const uint32_t *__restrict__ tab,
+                                                         unsigned char *__restrict__ dst, unsigned long long dst_pitch)
+{
+    const float2 *src = iq + (long long)tab[blockIdx.y] * pitch;
+    unsigned char *out = dst + (unsigned long long)blockIdx.y * dst_pitch;
+    const bool vec = (reinterpret_cast<unsigned long long>(src) & 15ull) == 0;
+    for (long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (long long)gridDim.x * 1024) {
+        if (vec && n - i0 >= 4) {
+            const float4 a = reinterpret_cast<const float4 *>(src + i0)[0], b = reinterpret_cast<const float4 *>(src + i0)[1];
+            if (!S16) {
+                float4 *o = reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(out) + i0);
+                o[0] = a;
+                o[1] = b;
+            } else {
+                const short2 q0 = make_short2(iq_record_s16(a.x), iq_record_s16(a.y)), q1 = make_short2(iq_record_s16(a.z), iq_record_s16(a.w));
+                const short2 q2 = make_short2(iq_record_s16(b.x), iq_record_s16(b.y)), q3 = make_short2(iq_record_s16(b.z), iq_record_s16(b.w));
+                uint4 w;
+                memcpy(&w.x, &q0, 4); memcpy(&w.y, &q1, 4); memcpy(&w.z, &q2, 4); memcpy(&w.w, &q3, 4);
+                *reinterpret_cast<uint4 *>(reinterpret_cast<short2 *>(out) + i0) = w;
+            }
+        } else {  // (no registers indexed by a run-time count: that would cost the kernel LDS)
+            for (long long i = i0; i < n && i < i0 + 4; i++) {
+                const float2 v = src[i];
+                if (!S16) reinterpret_cast<float2 *>(out)[i] = v;
+                else reinterpret_cast<short2 *>(out)[i] = make_short2(iq_record_s16(v.x), iq_record_s16(v.y));
+            }
+        }
+    }
+}
+
 static unsigned pack_blocks(long long n)
 {
     long long b = (n + 1023) / 1024;
@@ -124,6 +159,17 @@ int run_iq_record(hipStream_t s, const float2 *iq, long long pitch, const RawSrc
     unsigned char *o = (unsigned char *)dst;
     if (raw) launch(k_iq_record<true>, grid, dim3(256), s, (const float2 *)nullptr, 0LL, *raw, n, o, (unsigned long long)dst_pitch);
     else launch(k_iq_record<false>, grid, dim3(256), s, iq, pitch, RawSrc{nullptr, 0, 0, 0.f, 0}, n, o, (unsigned long long)dst_pitch);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int run_iq_pack(hipStream_t s, const float2 *iq, long long pitch, long long n, const uint32_t *d_tab, uint32_t rows, int format, void *dst, uint64_t dst_pitch)
+{
+    if (n <= 0 || rows == 0) return 0;
+    const dim3 grid(pack_blocks(n), rows);
+    unsigned char *o = (unsigned char *)dst;
+    if (format == PEBBLEGPU_AUDIO_F32) launch(k_iq_pack<false>, grid, dim3(256), s, iq, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
+    else launch(k_iq_pack<true>, grid, dim3(256), s, iq, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
     PG_HIP(hipGetLastError());
     return 0;
 }
@@ -240,6 +286,7 @@ int EgressRing::next(int device, int wait, EgressBlock *b)
     b->pitch_bytes = g.pitch_bytes;
     b->host = g.h;
     b->dropped_before = g.dropped_before;
+    b->aux = g.aux;
     b->rows = rows;
     b->format = format;
     return 0;
@@ -259,7 +306,7 @@ int EgressRing::finish(uint64_t call_index)
 }
 
 // ---- the receiver's two rings ----
-static int check_slots(uint32_t n_slots)
+int check_egress_slots(uint32_t n_slots)
 {
     if (n_slots < kEgressMinSlots || n_slots > kEgressMaxSlots)
         return fail(PEBBLEGPU_E_INVALID, "n_slots %u: a ring has %u..%u slots", n_slots, kEgressMinSlots, kEgressMaxSlots);
@@ -269,7 +316,7 @@ static int check_slots(uint32_t n_slots)
 int Receiver::audio_out_open(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots)
 {
     if (format < 0 || format >= kAudioFormats) return fail(PEBBLEGPU_E_INVALID, "unknown audio format %d", format);
-    if (int rc = check_slots(n_slots)) return rc;
+    if (int rc = check_egress_slots(n_slots)) return rc;
     if (channels && n_channels == 0) return fail(PEBBLEGPU_E_INVALID, "an empty channel list");
     std::vector<uint32_t> sel;
     if (!channels) {
@@ -385,7 +432,7 @@ int Receiver::audio_out_dropped(uint64_t *blocks)
 
 int Receiver::record_open(uint32_t n_slots)
 {
-    if (int rc = check_slots(n_slots)) return rc;
+    if (int rc = check_egress_slots(n_slots)) return rc;
     std::lock_guard<std::mutex> g(mu_);
     if (rec_.open) return fail(PEBBLEGPU_E_INVALID, "the recording ring is already open");
     PG_HIP(hipSetDevice(device));

@@ -26,6 +26,8 @@
 #include <climits>
 #include "common.h"
 
+struct pebblegpu_screen_map;  // include/pebblegpu.h
+
 namespace pg {
 
 constexpr int kMapMaxGeom = 64;  // per-stream geometries carried in one launch's arguments (zoomed spectra with per-channel offsets)
@@ -94,6 +96,31 @@ __host__ __device__ inline int32_t map_y(float y_scale, int32_t power_db, int32_
     return y < 0 ? 0 : (y > y_pixels - 1 ? y_pixels - 1 : y);  // qBound(0, y, yPixels - 1)
 }
 
+// powerdB of pixel i of the dB row x (fft.cpp:470-527), for the G lanes that own the pixel: every lane of the group calls it with the
+// same arguments and gets the same value.  Shared by k_screen_map and the display ring's packing kernel (k_display_map), so a block's
+// pixels and pebblegpu_*_map_spectrum's are one computation.
+template <int G>
+__device__ inline int32_t map_power_db(const float *__restrict__ x, const MapGeom &g, const MapShared &sh, int32_t i, int lane)
+{
+#pragma clang fp contract(off)
+    const bool averaged = g.bins_to_plot > sh.x_pixels;
+    const int32_t bin = map_bin(g, averaged, i);
+    if (bin < 0 || bin >= sh.fft_size) return kMinDb;
+    const int32_t last = i == 0 ? -1 : map_bin(g, averaged, i - 1);
+    if (averaged && last > 0 && bin != last + 1) {
+        // bins [last, bin): 1 <= last, bin < fft_size, and last <= bin (the per-pixel bin never decreases)
+        const int32_t skipped = bin - last;
+        double acc = 0.0;
+        for (int32_t k = lane; k < skipped; k += G) acc += exp10((double)x[last + k] / 10.0);  // DB::dBToPower
+#pragma unroll
+        for (int m = G / 2; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, G);
+        const double p = acc / (double)skipped;
+        const double db = p == 0.0 ? (double)kMinDb : 10.0 * log10(p);  // DB::powerTodB
+        return x86_trunc(db - sh.max_db);
+    }
+    return x86_trunc((double)x[bin] - sh.max_db);
+}
+
 // rows = streams x frames: row (s, j) reads in + s * stream_pitch + j * frame_pitch and writes out + (s * n_frames + j) * x_pixels
 template <int G>
 static __global__ __launch_bounds__(256) void k_screen_map(const float *__restrict__ in, long long stream_pitch, long long frame_pitch,
@@ -110,28 +137,73 @@ static __global__ __launch_bounds__(256) void k_screen_map(const float *__restri
         const int s = (int)(row / n_frames), j = (int)(row - (long long)s * n_frames);
         const MapGeom g = geoms.g[geoms.n == 1 ? 0 : s];
         const float *x = in + (long long)s * stream_pitch + (long long)j * frame_pitch;
-        const bool averaged = g.bins_to_plot > sh.x_pixels;
-        const int32_t bin = map_bin(g, averaged, i);
-        int32_t power_db;
-        if (bin < 0 || bin >= sh.fft_size) {
-            power_db = kMinDb;
-        } else {
-            const int32_t last = i == 0 ? -1 : map_bin(g, averaged, i - 1);
-            if (averaged && last > 0 && bin != last + 1) {
-                // bins [last, bin): 1 <= last, bin < fft_size, and last <= bin (the per-pixel bin never decreases)
-                const int32_t skipped = bin - last;
-                double acc = 0.0;
-                for (int32_t k = lane; k < skipped; k += G) acc += exp10((double)x[last + k] / 10.0);  // DB::dBToPower
-#pragma unroll
-                for (int m = G / 2; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, G);
-                const double p = acc / (double)skipped;
-                const double db = p == 0.0 ? (double)kMinDb : 10.0 * log10(p);  // DB::powerTodB
-                power_db = x86_trunc(db - sh.max_db);
-            } else {
-                power_db = x86_trunc((double)x[bin] - sh.max_db);
-            }
-        }
+        const int32_t power_db = map_power_db<G>(x, g, sh, i, lane);
         if (lane == 0) out[row * sh.x_pixels + i] = map_y(sh.y_scale, power_db, sh.y_pixels);
+    }
+}
+
+// ---- the waterfall's colours ----
+// SpectrumWidget's palette (application/spectrumwidget.cpp:97-113), the constructor's loop in its own integer arithmetic, entry i as
+// QColor::setRgb(r, g, b) leaves it: alpha 255, QRgb layout 0xFFRRGGBB.  The reference allocates 255 entries, writes entry 255 and
+// reads it for a pixel value of 0, both out of bounds; here the table has 256 entries and entry 255 is what the loop computes for it.
+__host__ __device__ inline uint32_t waterfall_palette(int i)
+{
+    int r, g, b;
+    if (i < 43) { r = 0; g = 0; b = 255 * i / 43; }
+    else if (i < 87) { r = 0; g = 255 * (i - 43) / 43; b = 255; }
+    else if (i < 120) { r = 0; g = 255; b = 255 - (255 * (i - 87) / 32); }
+    else if (i < 154) { r = 255 * (i - 120) / 33; g = 255; b = 0; }
+    else if (i < 217) { r = 255; g = 255 - (255 * (i - 154) / 62); b = 0; }
+    else { r = 255; g = 0; b = 128 * (i - 217) / 38; }
+    return 0xFF000000u | ((uint32_t)r << 16) | ((uint32_t)g << 8) | (uint32_t)b;
+}
+// SpectrumWidget::drawWaterfall, spectrumwidget.cpp:1111-1113: plotColor = m_spectrumColors[255 - _fftMap[i]]; v in 0..255
+__host__ __device__ inline uint32_t waterfall_color(int32_t v) { return waterfall_palette(255 - v); }
+
+// ---- the display ring's packing kernels (streambank.hip) ----
+// what a display ring fixes at open: the format, the selection's table on the device, the plot geometry and its lane group
+struct DisplayPack {
+    int format = 0;                  // pebblegpu_display_format
+    uint32_t n_streams = 0;          // selected streams: rows of d_tab
+    uint32_t *d_tab = nullptr;       // d_tab[r] = the stream of block row r
+    uint32_t row_elems = 0;          // bins (DB_F32) or x_pixels
+    uint64_t row_pitch_bytes = 0;    // row_elems * 4 rounded up to 16
+    int group = 1;                   // the lane group run_screen_map picks for geom
+    MapGeom geom;
+    MapShared sh;                    // (DB_F32: fft_size only)
+};
+// fills everything but n_streams and d_tab from the format and (mapped formats) the checked map
+void display_pack_plan(DisplayPack *p, int32_t bins, double sample_rate, const ::pebblegpu_screen_map *map);
+// rows first_row .. first_row + n_rows - 1 of spec ([stream][pitch_rows][bins]) -> dst [selected][n_rows][row_pitch_bytes]; one launch
+int run_display_pack(hipStream_t s, const DisplayPack &p, const float *spec, long long pitch_rows, int first_row, int n_rows, void *dst);
+int waterfall_colors(const int32_t *pixels, uint64_t n, uint32_t *argb);
+
+// Rows first_row .. first_row + n_rows - 1 of the selected streams of a compact spectrum buffer ([stream][pitch_rows][bins] float dB,
+// tab[r] = the stream of block row r) into a block: row j of selected stream r at out + r * out_stream_pitch + j * out_row_pitch
+// (bytes, multiples of 16).  ARGB false: FFT::mapFFTToScreen pixels, as k_screen_map writes them; true: drawWaterfall's colour of
+// each pixel, with no int32 intermediate.  One geometry for all rows; G is the lane group run_screen_map picks for it, so the
+// reduction adds in the same order.
+template <int G, bool ARGB>
+static __global__ __launch_bounds__(256) void k_display_map(const float *__restrict__ in, long long stream_pitch, long long frame_pitch, int first_row,
+                                                            int n_rows, long long n_items, MapGeom g, MapShared sh, const uint32_t *__restrict__ tab,
+                                                            unsigned char *__restrict__ out, unsigned long long out_row_pitch,
+                                                            unsigned long long out_stream_pitch)
+{
+#pragma clang fp contract(off)
+    constexpr int kGroups = 256 / G;
+    const int lane = (int)threadIdx.x % G;
+    const long long stride = (long long)gridDim.x * kGroups;
+    for (long long item = (long long)blockIdx.x * kGroups + (int)threadIdx.x / G; item < n_items; item += stride) {
+        const long long row = item / sh.x_pixels;
+        const int32_t i = (int32_t)(item - row * sh.x_pixels);
+        const int r = (int)(row / n_rows), j = (int)(row - (long long)r * n_rows);
+        const float *x = in + (long long)tab[r] * stream_pitch + (long long)(first_row + j) * frame_pitch;
+        const int32_t y = map_y(sh.y_scale, map_power_db<G>(x, g, sh, i, lane), sh.y_pixels);
+        if (lane == 0) {
+            unsigned char *o = out + (unsigned long long)r * out_stream_pitch + (unsigned long long)j * out_row_pitch;
+            if (ARGB) reinterpret_cast<uint32_t *>(o)[i] = waterfall_color(y);
+            else reinterpret_cast<int32_t *>(o)[i] = y;
+        }
     }
 }
 

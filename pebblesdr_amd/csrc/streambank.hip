@@ -1,6 +1,7 @@
 // streambank.hip -- S full-rate streams through CFastFIR + fftSpectrum (include/pebblegpu.h, "Stream bank").
 #include <new>
 #include <cmath>
+#include "kernels_display.h"
 #include "receiver.h"
 
 using pg::fail;
@@ -29,7 +30,99 @@ struct pebblegpu_streambank {
     std::vector<uint32_t> sel;       // the last call's selection, relative to its first frame
     bool last_listed = false;        // the last call's transform went through the frame-list kernels (or, sel empty, through none)
     uint64_t spec_rows = 0;          // rows per stream of what d_spec holds (the last call that computed any): its last row is the latest spectrum
+    // host egress (egress.h): the band-passed IQ of selected streams and the display rows of a call's spectra, one block per call each
+    pg::EgressRing iq_ring, disp_ring;
+    uint32_t *d_iq_tab = nullptr;    // d_iq_tab[r] = the stream of block row r (written at open)
+    int iq_fmt = 0;
+    pg::DisplayPack disp;            // format, selection table, plot geometry of the display ring
+    uint32_t disp_max_rows = 0;
 };
+
+constexpr uint64_t kMaxRingBytes = 1ull << 30;  // pinned host memory one ring may hold, all slots together
+
+// a ring's selection: `streams` checked against the bank (NULL: all, in order)
+static int sb_selection(const pebblegpu_streambank *sb, const uint32_t *streams, uint32_t n_streams, std::vector<uint32_t> *sel)
+{
+    const uint32_t S = sb->cfg.n_streams;
+    if (!streams) {
+        for (uint32_t c = 0; c < S; c++) sel->push_back(c);
+        return 0;
+    }
+    if (n_streams == 0) return fail(PEBBLEGPU_E_INVALID, "an empty stream list");
+    std::vector<char> seen(S, 0);
+    for (uint32_t i = 0; i < n_streams; i++) {
+        if (streams[i] >= S) return fail(PEBBLEGPU_E_INVALID, "stream %u out of range", streams[i]);
+        if (seen[streams[i]]) return fail(PEBBLEGPU_E_INVALID, "stream %u is listed twice", streams[i]);
+        seen[streams[i]] = 1;
+        sel->push_back(streams[i]);
+    }
+    return 0;
+}
+
+// allocates the ring and the selection's table; on failure everything it made is freed again and the handle is as it was
+static int sb_open_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, uint32_t **d_tab, const std::vector<uint32_t> &sel, uint32_t n_slots, uint32_t bps,
+                        uint64_t max_n, uint32_t fmt)
+{
+    const uint64_t slot = (uint64_t)sel.size() * pg::EgressRing::row_pitch(max_n, bps);
+    if (slot * n_slots > kMaxRingBytes)
+        return fail(PEBBLEGPU_E_SIZE, "%u slots of %llu bytes: a ring pins at most %llu bytes of host memory", n_slots, (unsigned long long)slot,
+                    (unsigned long long)kMaxRingBytes);
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    auto body = [&]() -> int {
+        PG_HIP(hipMalloc((void **)d_tab, sizeof(uint32_t) * sel.size()));
+        PG_HIP(hipMemcpy(*d_tab, sel.data(), sizeof(uint32_t) * sel.size(), hipMemcpyHostToDevice));
+        if (int rc = ring.open_ring(n_slots, (uint32_t)sel.size(), bps, max_n, fmt)) return rc;
+        for (uint32_t i = 0; i < n_slots; i++) PG_HIP(hipMemset(ring.slot[i].d, 0, ring.slot_bytes));  // (the padding of a row is never written)
+        return 0;
+    };
+    std::lock_guard<std::mutex> lk(ring.mu);
+    const int rc = body();
+    if (rc) {
+        ring.release();
+        if (*d_tab) (void)hipFree(*d_tab);
+        *d_tab = nullptr;
+    }
+    return rc;
+}
+
+static int sb_close_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, uint32_t **d_tab)
+{
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    PG_HIP(hipStreamSynchronize(sb->stream));
+    PG_HIP(hipStreamSynchronize(sb->stream2));
+    ring.close_ring();
+    if (*d_tab) (void)hipFree(*d_tab);
+    *d_tab = nullptr;
+    return 0;
+}
+
+// The blocks of an accepted call, behind its end on the bank's stream (behind the join of a side-by-side call) and so ahead of the
+// next call's kernels, which overwrite d_filt and d_spec: one launch and one event per open ring; a call that did not run a ring's
+// producer gives that ring a block of 0 samples / 0 rows and queues nothing.
+static int sb_queue_blocks(pebblegpu_streambank *sb, uint64_t n, uint32_t what)
+{
+    if (sb->iq_ring.open) {
+        if (pg::EgressSlot *g = sb->iq_ring.begin()) {
+            const uint64_t m = (what & 1u) ? n : 0;
+            if (int rc = pg::run_iq_pack(sb->stream, sb->d_filt, (long long)n, (long long)m, sb->d_iq_tab, sb->iq_ring.rows, sb->iq_fmt, g->d,
+                                         pg::EgressRing::row_pitch(m, sb->iq_ring.bytes_per_sample)))
+                return rc;
+            g->aux = 0;
+            if (int rc = sb->iq_ring.commit(g, sb->stream, m)) return rc;
+        }
+    }
+    if (sb->disp_ring.open) {
+        if (pg::EgressSlot *g = sb->disp_ring.begin()) {
+            // the rows THIS call computed (under a gate d_spec is compact: last_frames rows per stream); the last max_rows of them
+            const uint64_t computed = n ? sb->last_frames : 0, k = std::min<uint64_t>(computed, sb->disp_max_rows), first = computed - k;
+            if (int rc = pg::run_display_pack(sb->stream, sb->disp, sb->d_spec, (long long)computed, (int)first, (int)k, g->d)) return rc;
+            g->aux = (uint32_t)first;
+            if (int rc = sb->disp_ring.commit(g, sb->stream, k * (sb->disp.row_pitch_bytes / 4))) return rc;  // (a "sample" is 4 bytes of a row)
+        }
+    }
+    return 0;
+}
+
 
 // every kernel a raw call would run converts in its own loads (else the call is staged through k_normalize_iq as a whole)
 static bool sb_converts(const pebblegpu_streambank *sb) { return sb->ff.raw_ready() && (sb->sp.raw_ready() || sb->sp.raw_ready_big()); }
@@ -40,6 +133,10 @@ int pebblegpu_streambank_destroy(pebblegpu_streambank *sb)
 {
     if (!sb) return 0;
     (void)hipSetDevice(sb->cfg.device);
+    if (sb->stream2) (void)hipStreamSynchronize(sb->stream2);
+    if (sb->stream) (void)hipStreamSynchronize(sb->stream);
+    if (sb->iq_ring.open) sb->iq_ring.close_ring();  // (waits for a reader that is inside _next)
+    if (sb->disp_ring.open) sb->disp_ring.close_ring();
     if (sb->stream2) {
         (void)hipStreamSynchronize(sb->stream2);
         (void)hipStreamDestroy(sb->stream2);
@@ -51,7 +148,7 @@ int pebblegpu_streambank_destroy(pebblegpu_streambank *sb)
     sb->ff.release();
     sb->sp.release();
     sb->ingest.release();
-    void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec, sb->d_raw_stage};
+    void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec, sb->d_raw_stage, sb->d_iq_tab, sb->disp.d_tab};
     for (void *q : p) if (q) (void)hipFree(q);
     for (hipEvent_t e : sb->ev) if (e) (void)hipEventDestroy(e);
     delete sb;
@@ -145,7 +242,7 @@ static int sb_run(pebblegpu_streambank *sb, const float2 *in, const pg::RawSrc *
 {
     sb->last_n = 0;
     sb->last_frames = 0;
-    if (n == 0) return 0;
+    if (n == 0) return sb_queue_blocks(sb, 0, what);
     // The update timer, on the host before anything is queued.  A call without the spectrum advances the sample clock and nothing else:
     // it selects no frame and neither starts nor restarts the timer.
     const uint64_t F = n / sb->cfg.frame;
@@ -187,7 +284,7 @@ static int sb_run(pebblegpu_streambank *sb, const float2 *in, const pg::RawSrc *
     }
     PG_HIP(hipEventRecord(sb->ev[2], sb->stream));
     sb->timed = true;
-    return 0;
+    return sb_queue_blocks(sb, n, what);
 }
 
 int pebblegpu_streambank_process(pebblegpu_streambank *sb, const void *d_iq, uint64_t n, uint32_t what)
@@ -355,6 +452,131 @@ int pebblegpu_streambank_synchronize(pebblegpu_streambank *sb)
     PG_HIP(hipStreamSynchronize(sb->stream));
     PG_HIP(hipStreamSynchronize(sb->stream2));
     return 0;
+}
+
+// ---- host egress: the IQ ring ----
+int pebblegpu_streambank_iq_out_open(pebblegpu_streambank *sb, int format, const uint32_t *streams, uint32_t n_streams, uint32_t n_slots)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (format != PEBBLEGPU_AUDIO_F32 && format != PEBBLEGPU_AUDIO_S16)
+        return fail(PEBBLEGPU_E_INVALID, "IQ format %d: PEBBLEGPU_AUDIO_F32 or PEBBLEGPU_AUDIO_S16", format);
+    if (int rc = pg::check_egress_slots(n_slots)) return rc;
+    std::vector<uint32_t> sel;
+    if (int rc = sb_selection(sb, streams, n_streams, &sel)) return rc;
+    if (sb->iq_ring.open) return fail(PEBBLEGPU_E_INVALID, "the IQ ring is already open");
+    if (int rc = sb_open_ring(sb, sb->iq_ring, &sb->d_iq_tab, sel, n_slots, pg::kAudioBytes[format], sb->cap, (uint32_t)format)) return rc;
+    sb->iq_fmt = format;
+    return 0;
+}
+int pebblegpu_streambank_iq_out_close(pebblegpu_streambank *sb)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (!sb->iq_ring.open) return fail(PEBBLEGPU_E_INVALID, "the IQ ring is not open");
+    return sb_close_ring(sb, sb->iq_ring, &sb->d_iq_tab);
+}
+int pebblegpu_streambank_iq_out_next(pebblegpu_streambank *sb, int wait, pebblegpu_audio_block *b)
+{
+    if (!sb || !b) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (b->struct_size != sizeof(pebblegpu_audio_block)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_audio_block size mismatch");
+    pg::EgressBlock e;
+    if (int rc = sb->iq_ring.next(sb->cfg.device, wait, &e)) return rc;
+    b->format = e.format;
+    b->call_index = e.call;
+    b->host = e.host;
+    b->samples_per_channel = e.host ? e.samples : 0;
+    b->pitch_bytes = e.host ? e.pitch_bytes : 0;
+    b->n_channels = e.rows;
+    b->dropped_before = e.host ? e.dropped_before : 0;
+    return 0;
+}
+int pebblegpu_streambank_iq_out_release(pebblegpu_streambank *sb, uint64_t call_index)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return sb->iq_ring.finish(call_index);
+}
+static int sb_dropped(pg::EgressRing &ring, uint64_t *blocks)
+{
+    std::lock_guard<std::mutex> lk(ring.mu);
+    if (!ring.open) return fail(PEBBLEGPU_E_INVALID, "the ring is not open");
+    *blocks = ring.dropped;
+    return 0;
+}
+int pebblegpu_streambank_iq_out_dropped(const pebblegpu_streambank *sb, uint64_t *blocks)
+{
+    if (!sb || !blocks) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return sb_dropped(const_cast<pebblegpu_streambank *>(sb)->iq_ring, blocks);
+}
+
+// ---- host egress: the display ring ----
+int pebblegpu_streambank_display_open(pebblegpu_streambank *sb, int format, const pebblegpu_screen_map *map, const uint32_t *streams, uint32_t n_streams,
+                                      uint32_t max_rows, uint32_t n_slots)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (format != PEBBLEGPU_DISPLAY_DB_F32 && format != PEBBLEGPU_DISPLAY_PIXELS_I32 && format != PEBBLEGPU_DISPLAY_WATERFALL_ARGB32)
+        return fail(PEBBLEGPU_E_INVALID, "unknown display format %d", format);
+    if (int rc = pg::check_egress_slots(n_slots)) return rc;
+    if (!sb->cfg.spectrum_bins) return fail(PEBBLEGPU_E_INVALID, "the bank was created without a spectrum (spectrum_bins 0)");
+    if (format != PEBBLEGPU_DISPLAY_DB_F32) {
+        if (!map) return fail(PEBBLEGPU_E_INVALID, "display format %d needs a pebblegpu_screen_map", format);
+        if (map->struct_size != sizeof(pebblegpu_screen_map)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_screen_map size mismatch");
+        if (int rc = pg::check_screen_map(map->y_pixels, map->x_pixels, map->max_db, map->min_db)) return rc;
+        if (format == PEBBLEGPU_DISPLAY_WATERFALL_ARGB32 && map->y_pixels != 255)
+            return fail(PEBBLEGPU_E_INVALID, "the waterfall's palette is indexed by pixels of a 255-pixel plot, not %d (spectrumwidget.cpp:1285-1293)", map->y_pixels);
+    }
+    std::vector<uint32_t> sel;
+    if (int rc = sb_selection(sb, streams, n_streams, &sel)) return rc;
+    if (sb->disp_ring.open) return fail(PEBBLEGPU_E_INVALID, "the display ring is already open");
+    pg::DisplayPack plan;
+    plan.format = format;
+    plan.n_streams = (uint32_t)sel.size();
+    pg::display_pack_plan(&plan, (int32_t)sb->sp.bins, sb->cfg.sample_rate, map);
+    const uint32_t rows = max_rows && max_rows < sb->cfg.max_frames ? max_rows : sb->cfg.max_frames;  // (no call computes more than max_frames)
+    if (int rc = sb_open_ring(sb, sb->disp_ring, &plan.d_tab, sel, n_slots, 4, (uint64_t)rows * (plan.row_pitch_bytes / 4), (uint32_t)format)) return rc;
+    sb->disp = plan;
+    sb->disp_max_rows = rows;
+    return 0;
+}
+int pebblegpu_streambank_display_close(pebblegpu_streambank *sb)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (!sb->disp_ring.open) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    return sb_close_ring(sb, sb->disp_ring, &sb->disp.d_tab);
+}
+int pebblegpu_streambank_display_next(pebblegpu_streambank *sb, int wait, pebblegpu_display_block *b)
+{
+    if (!sb || !b) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (b->struct_size != sizeof(pebblegpu_display_block)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_display_block size mismatch");
+    pg::EgressBlock e;
+    if (int rc = sb->disp_ring.next(sb->cfg.device, wait, &e)) return rc;
+    // (disp is written at open only, and a reader has no business in _next before open has returned)
+    const uint64_t row_pitch = sb->disp.row_pitch_bytes;
+    b->format = e.format;
+    b->call_index = e.call;
+    b->host = e.host;
+    b->rows_per_stream = e.host && row_pitch ? (uint32_t)(e.pitch_bytes / row_pitch) : 0;
+    b->first_row = e.host ? e.aux : 0;
+    b->row_elems = sb->disp.row_elems;
+    b->n_streams = e.rows;
+    b->dropped_before = e.host ? e.dropped_before : 0;
+    b->reserved = 0;
+    b->row_pitch_bytes = row_pitch;
+    b->stream_pitch_bytes = e.host ? e.pitch_bytes : 0;
+    return 0;
+}
+int pebblegpu_streambank_display_release(pebblegpu_streambank *sb, uint64_t call_index)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return sb->disp_ring.finish(call_index);
+}
+int pebblegpu_streambank_display_dropped(const pebblegpu_streambank *sb, uint64_t *blocks)
+{
+    if (!sb || !blocks) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return sb_dropped(const_cast<pebblegpu_streambank *>(sb)->disp_ring, blocks);
+}
+int pebblegpu_waterfall_colors(const int32_t *pixels, uint64_t n, uint32_t *argb)
+{
+    if (n && (!pixels || !argb)) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return pg::waterfall_colors(pixels, n, argb);
 }
 
 }  // extern "C"
