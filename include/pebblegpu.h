@@ -967,6 +967,76 @@ int pebblegpu_streambank_display_dropped(const pebblegpu_streambank *sb, uint64_
  * 0xFFRRGGBB words.  A pixel outside 0..255 is PEBBLEGPU_E_INVALID. */
 int pebblegpu_waterfall_colors(const int32_t *pixels, uint64_t n, uint32_t *argb);
 
+/* ------------------------------------------------------------------------------------------------
+ * The receiver's display ring: what SpectrumWidget::newFftData (application/spectrumwidget.cpp:1169-1357) draws from, through the same
+ * pinned slots as the audio.  Without it a host that wants a call's display rows calls pebblegpu_receiver_map_spectrum /
+ * _map_zoom_spectrum, pebblegpu_receiver_synchronize and pebblegpu_memcpy_d2h, which drain the device after every call and throw away
+ * the run-ahead the audio ring keeps.  A block has ONE OR TWO PANES -- newFftData's top and bottom panel -- and each pane names
+ *   source    PEBBLEGPU_PANE_SPECTRUM: the unprocessed spectrum (pebblegpu_receiver_spectrum), rows per STREAM;
+ *             PEBBLEGPU_PANE_ZOOM: the zoomed spectra (pebblegpu_receiver_zoom_spectrum), rows per CHANNEL
+ *   format    pebblegpu_display_format, as for the stream bank's ring; DB_F32 ignores the geometry
+ *   geometry  unprocessed source: `map` as pebblegpu_receiver_map_spectrum takes it (the top panel's zoomed-in range around the mixer is
+ *             a start_freq / stop_freq pair).  Zoomed source: map.y_pixels, x_pixels, max_db, min_db with `zoom` and `mode_offset`
+ *             (host array of the receiver's n_channels entries, indexed by channel; NULL: all 0) as pebblegpu_receiver_map_zoom_spectrum
+ *             takes them: the edges are SignalSpectrum::mapFFTZoomedToScreen's, per channel; map.start_freq / stop_freq are ignored
+ *   rows      row r of the pane is stream / channel rows[r] of its source -- a subset in any order; NULL: all of them, in order
+ *   max_rows  0, or more than a call can compute: every row a call can compute
+ * Pixels are pebblegpu_receiver_map_spectrum's / _map_zoom_spectrum's bit for bit (one computation, and each row's lanes add in the
+ * order the map functions use for it); colours are pebblegpu_waterfall_colors of those pixels.
+ *
+ * The rules are the stream bank's display ring, word for word.  ONE block per accepted process call (_process, _process_raw,
+ * _process_ingested, multibank calls through the shard handles: every shard has its own ring), indices 0-based from open and
+ * contiguous; one slot holds all panes of a call (one copy, one event) and _next fills all the panes' blocks for the same call_index.
+ * A pane holds the rows ITS CALL computed: every frame without a gate; the gate's selection under pebblegpu_set_spectrum_updates,
+ * possibly 0 rows (the two sources have timers of their own, so the panes' row counts differ); 0 rows for a call that ran no such
+ * transform.  A block never repeats an earlier call's row: the row pebblegpu_receiver_map_spectrum maps "as frame 0" after a call that
+ * made none is for the pull interface only.  More rows than max_rows: the LAST max_rows, first_row says where they start.  A FULL
+ * RING DROPS AND COUNTS, it never refuses and never stalls; "free" is host bookkeeping only.  One reader, possibly on another thread;
+ * n_slots 2..8.  Opening the ring changes no call's route (pebblegpu_receiver_kernel_name reports the same strings, the audio has the
+ * same bits): per call it adds one launch where both sources are complete on one stream (a call that joins its streams, a receiver
+ * without side-by-side calls), one per pane on the stream that wrote its source otherwise (PEBBLEGPU_PIPELINE=1), however many
+ * channels are selected -- selection and per-channel geometry are a table on the device, written at open and at _set_pane -- and
+ * nothing the next call queues waits for the copy.  pebblegpu_process_iq / _process_iq_updates are refused with
+ * PEBBLEGPU_E_UNSUPPORTED while the ring is open.  _close waits for queued work, then for a reader inside _next;
+ * pebblegpu_receiver_destroy closes an open ring.
+ *
+ * Refused at open with PEBBLEGPU_E_INVALID, leaving the handle as it was: n_panes outside 1..2, an unknown source or format, a source
+ * the receiver does not compute (spectrum_bins == 0 / hires_bins == 0), a duplicate, out-of-range or empty selection, n_slots outside
+ * 2..8, a second open, a geometry the mappings refuse (x_pixels or y_pixels <= 0, max_db == min_db), a waterfall pane with
+ * y_pixels != 255, a non-finite zoom.  With PEBBLEGPU_E_SIZE: slots that would pin more than 1 GiB of host memory in total.
+ * ---------------------------------------------------------------------------------------------- */
+typedef enum {
+    PEBBLEGPU_PANE_SPECTRUM = 0,
+    PEBBLEGPU_PANE_ZOOM = 1
+} pebblegpu_pane_source;
+typedef struct pebblegpu_display_pane {
+    uint32_t struct_size;          /* = sizeof(pebblegpu_display_pane) */
+    uint32_t source;               /* pebblegpu_pane_source */
+    uint32_t format;               /* pebblegpu_display_format */
+    uint32_t max_rows;
+    pebblegpu_screen_map map;      /* struct_size set; ignored by DB_F32 */
+    double zoom;                   /* zoomed source only */
+    const int32_t *mode_offset;    /* zoomed source only: [n_channels] or NULL */
+    const uint32_t *rows;          /* [n_rows] or NULL: all */
+    uint32_t n_rows;
+    uint32_t reserved[5];
+} pebblegpu_display_pane;
+#define PEBBLEGPU_DISPLAY_MAX_PANES 2
+int pebblegpu_receiver_display_open(pebblegpu_receiver *rx, const pebblegpu_display_pane *panes, uint32_t n_panes, uint32_t n_slots);
+int pebblegpu_receiver_display_close(pebblegpu_receiver *rx);
+/* blocks: n_panes pebblegpu_display_block, struct_size set in each; blocks[p] is pane p of the same call (n_streams = the pane's selected
+ * rows).  blocks[0].host == NULL (and PEBBLEGPU_OK): nothing queued, or (wait == 0) not copied yet.  A pane of 0 rows has a host pointer
+ * all the same. */
+int pebblegpu_receiver_display_next(pebblegpu_receiver *rx, int wait, pebblegpu_display_block *blocks);
+int pebblegpu_receiver_display_release(pebblegpu_receiver *rx, uint64_t call_index);
+int pebblegpu_receiver_display_dropped(const pebblegpu_receiver *rx, uint64_t *blocks);
+/* A pane's plot geometry -- map, zoom, mode offsets: what a resize, a dB-range or a zoom change does in the GUI.  `geometry` is a whole
+ * pane description (the one passed to _open with its map, zoom or mode_offset changed): source and format must be the pane's own
+ * (anything else is PEBBLEGPU_E_INVALID), rows, n_rows and max_rows are not read -- the pane keeps its selection and its max_rows.
+ * Takes effect at the next process call like every setter (that call first waits for the calls before it: the table is shared).  A
+ * row wider than the slots were sized for at open is PEBBLEGPU_E_SIZE; the refusals of _open apply to the new geometry. */
+int pebblegpu_receiver_display_set_pane(pebblegpu_receiver *rx, uint32_t pane, const pebblegpu_display_pane *geometry);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,8 @@ SYMBOLS = [
     "pebblegpu_streambank_iq_out_dropped",
     "pebblegpu_streambank_display_open", "pebblegpu_streambank_display_close", "pebblegpu_streambank_display_next",
     "pebblegpu_streambank_display_release", "pebblegpu_streambank_display_dropped", "pebblegpu_waterfall_colors",
+    "pebblegpu_receiver_display_open", "pebblegpu_receiver_display_close", "pebblegpu_receiver_display_next",
+    "pebblegpu_receiver_display_release", "pebblegpu_receiver_display_dropped", "pebblegpu_receiver_display_set_pane",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
@@ -289,6 +291,35 @@ def _display_array(b):
     return raw[:, :, : 4 * E].copy().view(dt).reshape(S, R, E)
 
 
+PANE_SPECTRUM, PANE_ZOOM = range(2)  # pebblegpu_pane_source
+DISPLAY_MAX_PANES = 2                 # PEBBLEGPU_DISPLAY_MAX_PANES
+
+
+class DisplayPane(C.Structure):
+    """pebblegpu_display_pane: one pane of the receiver's display ring (display_pane(...) fills one and keeps its arrays alive)"""
+    _fields_ = [("struct_size", C.c_uint32), ("source", C.c_uint32), ("format", C.c_uint32), ("max_rows", C.c_uint32), ("map", ScreenMap),
+                ("zoom", C.c_double), ("mode_offset", C.POINTER(C.c_int32)), ("rows", C.POINTER(C.c_uint32)), ("n_rows", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
+
+
+def display_pane(source, fmt, screen=None, zoom=1.0, mode_offset=None, rows=None, max_rows=0):
+    """screen: a ScreenMap for the two mapped formats (a zoomed pane reads y_pixels, x_pixels, max_db, min_db of it); mode_offset: one int per
+    channel of the receiver (zoomed panes; None: all 0); rows: the selected streams / channels in block order (None: all)"""
+    p = DisplayPane()
+    p.struct_size = C.sizeof(DisplayPane)
+    p.source, p.format, p.max_rows, p.zoom = int(source), int(fmt), int(max_rows), float(zoom)
+    if screen is not None:
+        p.map = screen
+    if mode_offset is not None:
+        p._off = (C.c_int32 * max(1, len(mode_offset)))(*[int(v) for v in mode_offset])
+        p.mode_offset = C.cast(p._off, C.POINTER(C.c_int32))
+    if rows is not None:
+        p._rows = (C.c_uint32 * max(1, len(rows)))(*[int(v) for v in rows])
+        p.rows = C.cast(p._rows, C.POINTER(C.c_uint32))
+        p.n_rows = len(rows)
+    return p
+
+
 def waterfall_colors(pixels, lib=None):
     """the host twin of the waterfall's colour rule (SpectrumWidget::drawWaterfall): int32 pixel values 0..255 -> uint32 0xFFRRGGBB, same shape"""
     L = lib or load_library()
@@ -512,6 +543,13 @@ def _declare(L):
     L.pebblegpu_streambank_display_release.argtypes = [vp, u64]
     L.pebblegpu_streambank_display_dropped.argtypes = [vp, C.POINTER(u64)]
     L.pebblegpu_waterfall_colors.argtypes = [vp, u64, vp]
+    dpane = C.POINTER(DisplayPane)
+    L.pebblegpu_receiver_display_open.argtypes = [vp, dpane, u32, u32]
+    L.pebblegpu_receiver_display_close.argtypes = [vp]
+    L.pebblegpu_receiver_display_next.argtypes = [vp, i32, dblk]
+    L.pebblegpu_receiver_display_release.argtypes = [vp, u64]
+    L.pebblegpu_receiver_display_dropped.argtypes = [vp, C.POINTER(u64)]
+    L.pebblegpu_receiver_display_set_pane.argtypes = [vp, u32, dpane]
     return L
 
 
@@ -838,6 +876,40 @@ class ReceiverBank:
 
     def record_release(self, call_index):
         check(self.L, self.L.pebblegpu_receiver_record_release(self.h, int(call_index)))
+
+    # ---- host egress: the display ring (one or two panes per block) ----
+    def display_open(self, panes, n_slots=4):
+        """panes: one or two display_pane(...) -- SpectrumWidget::newFftData's top and bottom panel"""
+        arr = (DisplayPane * max(1, len(panes)))(*panes)
+        check(self.L, self.L.pebblegpu_receiver_display_open(self.h, arr, len(panes), int(n_slots)))
+        self._display_panes = len(panes)
+
+    def display_close(self):
+        check(self.L, self.L.pebblegpu_receiver_display_close(self.h))
+
+    def display_set_pane(self, pane, geometry):
+        """a pane's plot geometry (map, zoom, mode offsets) from the next call on; geometry: a display_pane(...) with the pane's source and format"""
+        check(self.L, self.L.pebblegpu_receiver_display_set_pane(self.h, int(pane), C.byref(geometry)))
+
+    def display_next(self, wait=True):
+        """-> (call_index, dropped_before, [(first_row, copy of the pane's rows [selected, rows, row_elems]) per pane]) or None; taken until
+        display_release(call_index)"""
+        n = getattr(self, "_display_panes", 1)
+        b = (DisplayBlock * DISPLAY_MAX_PANES)()
+        for k in range(DISPLAY_MAX_PANES):
+            b[k].struct_size = C.sizeof(DisplayBlock)
+        check(self.L, self.L.pebblegpu_receiver_display_next(self.h, 1 if wait else 0, b))
+        if not b[0].host:
+            return None
+        return int(b[0].call_index), int(b[0].dropped_before), [(int(b[k].first_row), _display_array(b[k])) for k in range(n)]
+
+    def display_release(self, call_index):
+        check(self.L, self.L.pebblegpu_receiver_display_release(self.h, int(call_index)))
+
+    def display_dropped(self):
+        n = C.c_uint64()
+        check(self.L, self.L.pebblegpu_receiver_display_dropped(self.h, C.byref(n)))
+        return int(n.value)
 
     def enable_signal_strength(self, on=True):
         check(self.L, self.L.pebblegpu_receiver_enable_signal_strength(self.h, 1 if on else 0))

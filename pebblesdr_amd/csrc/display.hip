@@ -1,6 +1,8 @@
 // display.hip -- launcher of k_screen_map (FFT::mapFFTToScreen, kernels_display.h) for the receiver, the stream bank and the
-// stand-alone spectrum step, and of the stream bank's display-ring packing kernels.
+// stand-alone spectrum step, and of the stream bank's display-ring packing kernels; the receiver's display ring (k_display_panes).
 #include <algorithm>
+#include <cmath>
+#include <new>
 #include "kernels_display.h"
 #include "receiver.h"
 
@@ -23,6 +25,35 @@ static int map_lane_group(float bpp)
     return G;
 }
 
+// one chunk of run_screen_map: the geometries of streams s0 .. s0 + ns - 1 into g (per_stream; else the one geometry every stream uses)
+// and the lane group of the chunk's launch: the widest averaged pixel sizes it
+static int map_chunk_plan(int32_t fft_size, double sample_rate, const int32_t *edges, bool per_stream, int s0, int ns, int32_t x_pixels, MapGeom *g)
+{
+    const int n = per_stream ? ns : 1;
+    float bpp = 0.0f;
+    for (int k = 0; k < n; k++) {
+        const int32_t *e = edges + 2 * (per_stream ? s0 + k : 0);
+        g[k] = map_geom(fft_size, sample_rate, e[0], e[1], x_pixels);
+        if (g[k].bins_to_plot > x_pixels) bpp = std::max(bpp, g[k].bins_per_pixel);
+    }
+    return map_lane_group(bpp);
+}
+
+// what run_screen_map below does with each stream's rows, as a table: the receiver's display ring packs with it (k_display_panes)
+void map_row_plan(int32_t fft_size, double sample_rate, const int32_t *edges, bool per_stream, int n_streams, int32_t x_pixels, MapGeom *geoms, int *groups)
+{
+    const int chunk = per_stream ? kMapMaxGeom : n_streams;
+    for (int s0 = 0; s0 < n_streams; s0 += chunk) {
+        const int ns = std::min(chunk, n_streams - s0);
+        MapGeom g[kMapMaxGeom];
+        const int G = map_chunk_plan(fft_size, sample_rate, edges, per_stream, s0, ns, x_pixels, g);
+        for (int k = 0; k < ns; k++) {
+            geoms[s0 + k] = g[per_stream ? k : 0];
+            groups[s0 + k] = G;
+        }
+    }
+}
+
 int run_screen_map(hipStream_t s, const float *in, long long stream_pitch, long long frame_pitch, int n_streams, int n_frames, int32_t fft_size,
                    double sample_rate, const int32_t *edges, bool per_stream, int32_t y_pixels, int32_t x_pixels, double max_db, double min_db,
                    int32_t *out)
@@ -40,13 +71,7 @@ int run_screen_map(hipStream_t s, const float *in, long long stream_pitch, long 
         MapGeoms geoms;
         memset(&geoms, 0, sizeof(geoms));
         geoms.n = per_stream ? ns : 1;
-        float bpp = 0.0f;  // the widest pixel of the launch sizes its lane groups
-        for (int k = 0; k < geoms.n; k++) {
-            const int32_t *e = edges + 2 * (per_stream ? s0 + k : 0);
-            geoms.g[k] = map_geom(fft_size, sample_rate, e[0], e[1], x_pixels);
-            if (geoms.g[k].bins_to_plot > x_pixels) bpp = std::max(bpp, geoms.g[k].bins_per_pixel);
-        }
-        const int G = map_lane_group(bpp);
+        const int G = map_chunk_plan(fft_size, sample_rate, edges, per_stream, s0, ns, x_pixels, geoms.g);
         const long long n_items = (long long)ns * n_frames * x_pixels;
         const float *rin = in + (long long)s0 * stream_pitch;
         int32_t *rout = out + (long long)s0 * n_frames * x_pixels;
@@ -142,6 +167,28 @@ int run_display_pack(hipStream_t s, const DisplayPack &p, const float *spec, lon
     return 0;
 }
 
+int run_display_panes(hipStream_t s, const DisplayPaneArgs *panes, int n_panes)
+{
+    DisplayPaneArgs a[2];
+    int n = 0;
+    for (int k = 0; k < n_panes && k < 2; k++)
+        if (panes[k].total_rows > 0) a[n++] = panes[k];
+    if (!n) return 0;
+    if (n == 1) {
+        a[1] = a[0];
+        a[1].total_rows = 0;
+    }
+    unsigned gx = 1;
+    long long gy = 1;
+    for (int k = 0; k < n; k++) {
+        gx = std::max(gx, a[k].x_blocks);
+        gy = std::max(gy, a[k].total_rows);
+    }
+    launch(k_display_panes, dim3(gx, (unsigned)std::min<long long>(gy, 4096), (unsigned)n), dim3(256), s, a[0], a[1]);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
 // the host twin of the waterfall's colour rule (no device)
 int waterfall_colors(const int32_t *pixels, uint64_t n, uint32_t *argb)
 {
@@ -168,6 +215,326 @@ void zoom_span_edges(uint32_t hires_rate, double zoom, int32_t mode_offset, int3
     const uint16_t span = (uint16_t)(uint32_t)x86_trunc((double)hires_rate * zoom);
     *start = (int32_t)((uint32_t)(-(int32_t)span / 2) - (uint32_t)mode_offset);  // (int arithmetic that wraps as on x86-64)
     *stop = (int32_t)((uint32_t)((int32_t)span / 2) - (uint32_t)mode_offset);
+}
+
+// ---- the receiver's display ring: one or two panes per block (include/pebblegpu.h, "The receiver's display ring") ----
+// One EgressRing whose "row" is a whole slot: the panes of a call lie behind one another in it, compact, so one copy and one event carry
+// them all; what each pane of a slot holds is kept beside the ring (written between begin() and commit(), read behind next(): the
+// ring's lock orders the two).
+constexpr uint64_t kMaxDisplayRingBytes = 1ull << 30;  // pinned host memory the ring may hold, all slots together (the stream bank's limit)
+
+struct DisplayRing {
+    struct Pane {
+        uint32_t source = 0, format = 0, max_rows = 0;
+        std::vector<uint32_t> sel;       // row r of the pane is stream / channel sel[r]
+        uint32_t row_elems = 0;          // bins (DB_F32) or x_pixels
+        uint64_t row_pitch = 0;          // bytes, a multiple of 16
+        uint64_t cap_pitch = 0;          // ... what the slots were sized for at open
+        MapShared sh{};
+        unsigned x_blocks = 1;
+        std::vector<DisplayRow> tab;     // the device table's host copy
+        DisplayRow *d_tab = nullptr;
+    };
+    struct SlotPane { uint32_t rows, first_row, row_elems; uint64_t row_pitch, offset; };
+    EgressRing ring;
+    uint32_t n_panes = 0;                // 0: closed
+    uint32_t fmt[PEBBLEGPU_DISPLAY_MAX_PANES] = {}, n_sel[PEBBLEGPU_DISPLAY_MAX_PANES] = {};  // fixed at open (what the reader may look at)
+    Pane pane[PEBBLEGPU_DISPLAY_MAX_PANES];
+    SlotPane info[kEgressMaxSlots][PEBBLEGPU_DISPLAY_MAX_PANES] = {};
+    hipEvent_t packed2[kEgressMaxSlots] = {};  // behind the first pane's launch when the two panes are packed on different streams
+    bool dirty = false;                  // a table changed: uploaded at the next call's boundary
+
+    void free_device()
+    {
+        for (Pane &p : pane) {
+            if (p.d_tab) (void)hipFree(p.d_tab);
+            p.d_tab = nullptr;
+        }
+        for (hipEvent_t &e : packed2) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+};
+
+// a pane's request checked against the receiver and turned into its table and launch geometry (no device call)
+static int plan_pane(const Receiver &rx, const pebblegpu_display_pane *p, DisplayRing::Pane *out)
+{
+    if (p->struct_size != sizeof(pebblegpu_display_pane)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_display_pane size mismatch");
+    if (p->source != PEBBLEGPU_PANE_SPECTRUM && p->source != PEBBLEGPU_PANE_ZOOM) return fail(PEBBLEGPU_E_INVALID, "unknown pane source %u", p->source);
+    if (p->format != PEBBLEGPU_DISPLAY_DB_F32 && p->format != PEBBLEGPU_DISPLAY_PIXELS_I32 && p->format != PEBBLEGPU_DISPLAY_WATERFALL_ARGB32)
+        return fail(PEBBLEGPU_E_INVALID, "unknown display format %u", p->format);
+    const bool zoom = p->source == PEBBLEGPU_PANE_ZOOM;
+    const uint32_t fft = zoom ? rx.zoom_bins : rx.bins, n_src = zoom ? rx.C : rx.S;
+    if (!fft) return fail(PEBBLEGPU_E_INVALID, zoom ? "the receiver computes no zoomed spectrum (hires_bins = 0)" : "the receiver computes no spectrum (spectrum_bins = 0)");
+    out->source = p->source;
+    out->format = p->format;
+    out->sel.clear();
+    if (!p->rows) {
+        for (uint32_t c = 0; c < n_src; c++) out->sel.push_back(c);
+    } else {
+        if (p->n_rows == 0) return fail(PEBBLEGPU_E_INVALID, "an empty row selection");
+        std::vector<char> seen(n_src, 0);
+        for (uint32_t i = 0; i < p->n_rows; i++) {
+            if (p->rows[i] >= n_src) return fail(PEBBLEGPU_E_INVALID, "%s %u out of range", zoom ? "channel" : "stream", p->rows[i]);
+            if (seen[p->rows[i]]) return fail(PEBBLEGPU_E_INVALID, "%s %u is listed twice", zoom ? "channel" : "stream", p->rows[i]);
+            seen[p->rows[i]] = 1;
+            out->sel.push_back(p->rows[i]);
+        }
+    }
+    // no call computes more rows than its capacity holds frames (the zoomed transform: decimated frames)
+    const uint64_t cap = (uint64_t)rx.max_sf * rx.superframe, maxr = std::max<uint64_t>(1, zoom ? cap / ((uint64_t)rx.chain.total * rx.nf) : cap / rx.nf);
+    out->max_rows = (uint32_t)(p->max_rows && p->max_rows < maxr ? p->max_rows : maxr);
+    memset(&out->sh, 0, sizeof(out->sh));
+    out->sh.fft_size = (int32_t)fft;
+    out->tab.assign(out->sel.size(), DisplayRow{});
+    for (size_t r = 0; r < out->sel.size(); r++) {
+        out->tab[r].src = out->sel[r];
+        out->tab[r].group = 1;
+    }
+    if (p->format == PEBBLEGPU_DISPLAY_DB_F32) {
+        if (fft % 4) return fail(PEBBLEGPU_E_UNSUPPORTED, "%u bins: display rows are copied in 16-byte vectors", fft);
+        out->row_elems = fft;
+        out->x_blocks = std::min<unsigned>((fft / 4 + 255) / 256, 16);
+    } else {
+        const pebblegpu_screen_map &m = p->map;
+        if (m.struct_size != sizeof(pebblegpu_screen_map)) return fail(PEBBLEGPU_E_INVALID, "display format %u needs a pebblegpu_screen_map (struct_size set)", p->format);
+        if (int rc = check_screen_map(m.y_pixels, m.x_pixels, m.max_db, m.min_db)) return rc;
+        if (p->format == PEBBLEGPU_DISPLAY_WATERFALL_ARGB32 && m.y_pixels != 255)
+            return fail(PEBBLEGPU_E_INVALID, "the waterfall's palette is indexed by pixels of a 255-pixel plot, not %d (spectrumwidget.cpp:1285-1293)", m.y_pixels);
+        if (zoom && !std::isfinite(p->zoom)) return fail(PEBBLEGPU_E_INVALID, "zoom must be finite");
+        // the edges and the per_stream decision of pebblegpu_receiver_map_spectrum / _map_zoom_spectrum, then run_screen_map's plan for every row
+        std::vector<int32_t> edges(2 * (size_t)n_src);
+        bool same = true;
+        if (zoom) {
+            for (uint32_t c = 0; c < n_src; c++) {
+                zoom_span_edges(rx.demod_rate_int, p->zoom, p->mode_offset ? p->mode_offset[c] : 0, &edges[2 * c], &edges[2 * c + 1]);
+                same = same && edges[2 * c] == edges[0] && edges[2 * c + 1] == edges[1];
+            }
+        } else {
+            edges[0] = m.start_freq;
+            edges[1] = m.stop_freq;
+        }
+        std::vector<MapGeom> geoms(n_src);
+        std::vector<int> groups(n_src);
+        map_row_plan((int32_t)fft, zoom ? (double)rx.demod_rate_int : rx.fs, edges.data(), zoom && !same, (int)n_src, m.x_pixels, geoms.data(), groups.data());
+        int gmax = 1;
+        for (size_t r = 0; r < out->sel.size(); r++) {
+            out->tab[r].geom = geoms[out->sel[r]];
+            out->tab[r].group = groups[out->sel[r]];
+            gmax = std::max(gmax, groups[out->sel[r]]);
+        }
+        out->sh.x_pixels = m.x_pixels;
+        out->sh.y_pixels = m.y_pixels;
+        out->sh.y_scale = map_y_scale(m.y_pixels, m.max_db, m.min_db);
+        out->sh.max_db = m.max_db;
+        out->row_elems = (uint32_t)m.x_pixels;
+        const long long per_wg = 256 / gmax;
+        out->x_blocks = (unsigned)std::min<long long>(((long long)m.x_pixels + per_wg - 1) / per_wg, 64);
+    }
+    out->row_pitch = ((uint64_t)out->row_elems * 4 + 15) & ~(uint64_t)15;
+    return 0;
+}
+
+int Receiver::display_open(const pebblegpu_display_pane *panes, uint32_t n_panes, uint32_t n_slots)
+{
+    if (!panes) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (n_panes < 1 || n_panes > PEBBLEGPU_DISPLAY_MAX_PANES) return fail(PEBBLEGPU_E_INVALID, "n_panes %u: a block has 1..%d panes", n_panes, PEBBLEGPU_DISPLAY_MAX_PANES);
+    if (int rc = check_egress_slots(n_slots)) return rc;
+    DisplayRing::Pane plan[PEBBLEGPU_DISPLAY_MAX_PANES];
+    uint64_t slot_bytes = 0;
+    for (uint32_t k = 0; k < n_panes; k++) {
+        if (int rc = plan_pane(*this, &panes[k], &plan[k])) return rc;
+        plan[k].cap_pitch = plan[k].row_pitch;
+        const uint64_t rows = (uint64_t)plan[k].sel.size() * plan[k].max_rows;
+        if (rows > kMaxDisplayRingBytes / plan[k].row_pitch) slot_bytes = kMaxDisplayRingBytes + 1;  // (and no overflow)
+        else slot_bytes += rows * plan[k].row_pitch;
+    }
+    std::lock_guard<std::mutex> g(mu_);
+    if (disp_open_) return fail(PEBBLEGPU_E_INVALID, "the display ring is already open");
+    if (slot_bytes > kMaxDisplayRingBytes || slot_bytes * n_slots > kMaxDisplayRingBytes)
+        return fail(PEBBLEGPU_E_SIZE, "%u slots of %llu bytes: a ring pins at most %llu bytes of host memory", n_slots, (unsigned long long)slot_bytes,
+                    (unsigned long long)kMaxDisplayRingBytes);
+    PG_HIP(hipSetDevice(device));
+    if (!disp_) disp_ = new (std::nothrow) DisplayRing();
+    if (!disp_) return fail(PEBBLEGPU_E_INVALID, "out of host memory");
+    DisplayRing &d = *disp_;
+    std::lock_guard<std::mutex> lk(d.ring.mu);
+    auto body = [&]() -> int {
+        for (uint32_t k = 0; k < n_panes; k++) PG_HIP(hipMalloc((void **)&plan[k].d_tab, sizeof(DisplayRow) * plan[k].tab.size()));
+        if (int rc = d.ring.open_ring(n_slots, 1, 4, slot_bytes / 4, 0)) return rc;
+        for (uint32_t i = 0; i < n_slots; i++) {
+            PG_HIP(hipMemset(d.ring.slot[i].d, 0, d.ring.slot_bytes));  // (the padding of a row is never written)
+            PG_HIP(hipEventCreateWithFlags(&d.packed2[i], hipEventDisableTiming));
+        }
+        PG_HIP(hipStreamSynchronize(nullptr));  // (the clears are over before a packing kernel on the receiver's own streams can run)
+        return 0;
+    };
+    if (int rc = body()) {
+        d.ring.release();
+        for (uint32_t k = 0; k < n_panes; k++) if (plan[k].d_tab) (void)hipFree(plan[k].d_tab);
+        d.free_device();
+        return rc;
+    }
+    for (uint32_t k = 0; k < n_panes; k++) {
+        d.pane[k] = plan[k];
+        d.fmt[k] = plan[k].format;
+        d.n_sel[k] = (uint32_t)plan[k].sel.size();
+    }
+    d.n_panes = n_panes;
+    d.dirty = true;
+    disp_open_ = true;
+    return 0;
+}
+
+int Receiver::display_close()
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (!disp_open_) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    if (int rc = sync()) return rc;
+    disp_->ring.close_ring();  // (waits for a reader that is inside _next)
+    disp_->n_panes = 0;
+    disp_->free_device();
+    disp_open_ = false;
+    return 0;
+}
+
+// ~Receiver, behind the synchronisation of both streams
+void Receiver::display_destroy()
+{
+    if (!disp_) return;
+    if (disp_->ring.open) disp_->ring.close_ring();
+    else disp_->ring.release();
+    disp_->free_device();
+    delete disp_;
+    disp_ = nullptr;
+    disp_open_ = false;
+}
+
+int Receiver::display_set_pane(uint32_t pane, const pebblegpu_display_pane *p)
+{
+    if (!p) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(mu_);
+    if (!disp_open_) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    if (pane >= disp_->n_panes) return fail(PEBBLEGPU_E_INVALID, "pane %u: the ring has %u", pane, disp_->n_panes);
+    DisplayRing::Pane &cur = disp_->pane[pane];
+    if (p->source != cur.source || p->format != cur.format)
+        return fail(PEBBLEGPU_E_INVALID, "a pane keeps the source and the format it was opened with: close and open the ring to change them");
+    pebblegpu_display_pane q = *p;  // ... and its selection and max_rows
+    q.rows = cur.sel.data();
+    q.n_rows = (uint32_t)cur.sel.size();
+    q.max_rows = cur.max_rows;
+    DisplayRing::Pane next;
+    if (int rc = plan_pane(*this, &q, &next)) return rc;
+    if (next.row_pitch > cur.cap_pitch)
+        return fail(PEBBLEGPU_E_SIZE, "rows of %llu bytes: the slots were sized for %llu at open", (unsigned long long)next.row_pitch, (unsigned long long)cur.cap_pitch);
+    next.cap_pitch = cur.cap_pitch;
+    next.d_tab = cur.d_tab;
+    cur = next;
+    disp_->dirty = true;
+    return 0;
+}
+
+// the panes' tables for the coming call.  Rare (open, set_pane): both streams are drained first, since the packing kernel of an earlier
+// call may still be reading a table -- as the audio ring's table is refreshed
+int Receiver::upload_display_tables()
+{
+    if (!disp_->dirty) return 0;
+    PG_HIP(hipStreamSynchronize(stream_));
+    PG_HIP(hipStreamSynchronize(chain_stream_));
+    for (uint32_t k = 0; k < disp_->n_panes; k++) {
+        const DisplayRing::Pane &p = disp_->pane[k];
+        PG_HIP(hipMemcpy(p.d_tab, p.tab.data(), sizeof(DisplayRow) * p.tab.size(), hipMemcpyHostToDevice));
+    }
+    disp_->dirty = false;
+    return 0;
+}
+
+// The block of an accepted call.  spec_rows / zoom_rows: the rows THIS call computed (compact in d_spec / d_zoom), complete on spec_s /
+// zoom_s -- where Receiver::map_spectrum would queue its map, and where the next call's transform of the same buffer follows.  Both
+// panes on one stream: one launch; else one per pane, and the slot's copy waits for both.
+int Receiver::queue_display_block(hipStream_t spec_s, uint64_t spec_rows, hipStream_t zoom_s, uint64_t zoom_rows)
+{
+    DisplayRing &d = *disp_;
+    EgressSlot *g = d.ring.begin();
+    if (!g) return 0;
+    const int si = (int)(g - d.ring.slot);
+    DisplayPaneArgs a[PEBBLEGPU_DISPLAY_MAX_PANES];
+    hipStream_t st[PEBBLEGPU_DISPLAY_MAX_PANES] = {};
+    uint64_t off = 0;
+    for (uint32_t k = 0; k < d.n_panes; k++) {
+        const DisplayRing::Pane &p = d.pane[k];
+        const bool zoom = p.source == PEBBLEGPU_PANE_ZOOM;
+        const uint64_t computed = zoom ? zoom_rows : spec_rows, n = std::min<uint64_t>(computed, p.max_rows), first = computed - n;
+        d.info[si][k] = DisplayRing::SlotPane{(uint32_t)n, (uint32_t)first, p.row_elems, p.row_pitch, off};
+        DisplayPaneArgs &q = a[k];
+        q.in = zoom ? d_zoom : d_spec;
+        q.stream_pitch = (long long)computed * p.sh.fft_size;
+        q.first_row = (int)first;
+        q.n_rows = (int)n;
+        q.total_rows = (long long)p.sel.size() * (long long)n;
+        q.tab = p.d_tab;
+        q.format = (int)p.format;
+        q.x_blocks = p.x_blocks;
+        q.sh = p.sh;
+        q.out = (unsigned char *)g->d + off;
+        q.out_row_pitch = p.row_pitch;
+        st[k] = zoom ? zoom_s : spec_s;
+        off += (uint64_t)q.total_rows * p.row_pitch;
+    }
+    g->aux = (uint32_t)si;
+    hipStream_t last = st[0];
+    if (d.n_panes == 2 && st[0] != st[1] && a[0].total_rows && a[1].total_rows) {
+        if (int rc = run_display_panes(st[0], &a[0], 1)) return rc;
+        PG_HIP(hipEventRecord(d.packed2[si], st[0]));
+        PG_HIP(hipStreamWaitEvent(d.ring.copy_stream, d.packed2[si], 0));
+        if (int rc = run_display_panes(st[1], &a[1], 1)) return rc;
+        last = st[1];
+    } else {
+        if (d.n_panes == 2 && !a[0].total_rows) last = st[1];
+        if (int rc = run_display_panes(last, a, (int)d.n_panes)) return rc;
+    }
+    return d.ring.commit(g, last, off / 4);  // (a "sample" is 4 bytes; 0: nothing is queued at all)
+}
+
+int Receiver::display_next(int wait, pebblegpu_display_block *b)
+{
+    if (!b) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    const uint32_t n = disp_ ? disp_->n_panes : 0;
+    if (!n) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    for (uint32_t k = 0; k < n; k++)
+        if (b[k].struct_size != sizeof(pebblegpu_display_block)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_display_block size mismatch (pane %u)", k);
+    EgressBlock e;
+    if (int rc = disp_->ring.next(device, wait, &e)) return rc;
+    for (uint32_t k = 0; k < n; k++) {
+        pebblegpu_display_block &o = b[k];
+        const DisplayRing::SlotPane z{}, &q = e.host ? disp_->info[e.aux % kEgressMaxSlots][k] : z;
+        o.format = disp_->fmt[k];
+        o.call_index = e.call;
+        o.host = e.host ? (const unsigned char *)e.host + q.offset : nullptr;
+        o.rows_per_stream = q.rows;
+        o.first_row = q.first_row;
+        o.row_elems = q.row_elems;
+        o.n_streams = disp_->n_sel[k];
+        o.dropped_before = e.host ? e.dropped_before : 0;
+        o.reserved = 0;
+        o.row_pitch_bytes = q.row_pitch;
+        o.stream_pitch_bytes = (uint64_t)q.rows * q.row_pitch;
+    }
+    return 0;
+}
+int Receiver::display_release(uint64_t call_index)
+{
+    if (!disp_) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    return disp_->ring.finish(call_index);
+}
+int Receiver::display_dropped(uint64_t *blocks)
+{
+    if (!disp_) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    std::lock_guard<std::mutex> lk(disp_->ring.mu);
+    if (!disp_->ring.open) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    *blocks = disp_->ring.dropped;
+    return 0;
 }
 
 }  // namespace pg

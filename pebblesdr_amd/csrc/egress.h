@@ -1,7 +1,8 @@
 // egress.h -- host egress: ingest.h in the other direction.  A ring of pinned host slots that a small packing kernel, queued behind a
 // process call on the call's own stream, fills through a device staging twin and a copy stream; the host waits for ONE slot's
 // "copied" event, never for the device.  Two users in Receiver (egress.hip), two in the stream bank (streambank.hip: the band-passed IQ
-// of selected streams and the display rows of a call's spectra; the ring itself knows neither):
+// of selected streams and the display rows of a call's spectra; the ring itself knows neither), and the receiver's display ring
+// (display.hip: one or two panes per slot, the ring's one "row" being the whole slot):
 //   the audio output stage -- Receiver::processAudioData -> Audio::SendToOutput(in, n, m_gain, m_mute), application/receiver.cpp:1029-1035;
 //                             the sample rule is pebblelib/audiopa.cpp:304-343 (the same clip in pebblelib/audioqt.cpp:169-211)
 //   IQ recording           -- if (m_isRecording) m_recordingFile.WriteSamples(nextStep, numSamples), application/receiver.cpp:800-801;

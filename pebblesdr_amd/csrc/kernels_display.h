@@ -207,4 +207,81 @@ static __global__ __launch_bounds__(256) void k_display_map(const float *__restr
     }
 }
 
+// ---- the receiver's display ring (egress.hip): one or two panes per block, per-row geometry from a table on the device ----
+// k_display_map carries ONE geometry by value; a zoomed pane needs one per channel, for any number of channels, and run_screen_map's
+// answer -- a launch per kMapMaxGeom streams -- would make the ring's launches grow with the bank.  Here the geometry lives in device
+// memory, one entry per block row, written at open and at set_pane (call boundaries, like the audio ring's EgressRow table), together
+// with the source row (the selection) and the lane group run_screen_map gives THAT row, so the reduction adds in the same order.
+struct DisplayRow {
+    MapGeom geom;
+    uint32_t src;    // the stream / channel of this block row
+    int32_t group;   // lanes per pixel, a power of two <= 64
+    uint32_t pad_[2];
+};
+// one pane of one call, by value
+struct DisplayPaneArgs {
+    const float *in;                 // [source row][pitch rows][fft_size] float dB
+    long long stream_pitch;          // floats between two source rows
+    int first_row, n_rows;           // rows first_row .. first_row + n_rows - 1 of each selected source row
+    long long total_rows;            // selected rows x n_rows
+    const DisplayRow *tab;
+    int format;                      // pebblegpu_display_format
+    unsigned x_blocks;               // workgroups along x this pane uses (the grid has the larger of the two panes')
+    MapShared sh;
+    unsigned char *out;              // [selected][n_rows][out_row_pitch bytes]
+    unsigned long long out_row_pitch;
+};
+
+template <int G>
+__device__ inline void display_map_row(const float *__restrict__ x, const MapGeom &g, const MapShared &sh, bool argb, unsigned char *__restrict__ o, unsigned x_blocks)
+{
+#pragma clang fp contract(off)
+    constexpr int kGroups = 256 / G;
+    const int lane = (int)threadIdx.x % G;
+    for (int32_t i = (int32_t)blockIdx.x * kGroups + (int)threadIdx.x / G; i < sh.x_pixels; i += (int32_t)x_blocks * kGroups) {
+        const int32_t y = map_y(sh.y_scale, map_power_db<G>(x, g, sh, i, lane), sh.y_pixels);
+        if (lane == 0) {
+            if (argb) reinterpret_cast<uint32_t *>(o)[i] = waterfall_color(y);
+            else reinterpret_cast<int32_t *>(o)[i] = y;
+        }
+    }
+}
+
+// grid (x, rows, panes): a workgroup takes whole block rows (strided over grid.y), so the row's lane group is uniform in it.  DB_F32 is
+// k_display_rows' 16-byte gather (rows are powers of two >= 2048 floats: 16-byte aligned on both sides); the mapped formats run
+// map_power_db<G> / map_y / waterfall_color, the one computation of k_screen_map and k_display_map.
+static __global__ __launch_bounds__(256) void k_display_panes(DisplayPaneArgs p0, DisplayPaneArgs p1)
+{
+    const DisplayPaneArgs &p = blockIdx.z ? p1 : p0;
+    if (blockIdx.x >= p.x_blocks) return;
+    for (long long row = blockIdx.y; row < p.total_rows; row += gridDim.y) {
+        const int r = (int)(row / p.n_rows), j = (int)(row - (long long)r * p.n_rows);
+        const DisplayRow e = p.tab[r];
+        const float *x = p.in + (long long)e.src * p.stream_pitch + (long long)(p.first_row + j) * p.sh.fft_size;
+        unsigned char *o = p.out + (unsigned long long)row * p.out_row_pitch;
+        if (p.format == 0) {  // PEBBLEGPU_DISPLAY_DB_F32
+            const float4 *xv = reinterpret_cast<const float4 *>(x);
+            float4 *ov = reinterpret_cast<float4 *>(o);
+            for (int k = (int)(blockIdx.x * 256 + threadIdx.x); k < p.sh.fft_size / 4; k += (int)p.x_blocks * 256) ov[k] = xv[k];
+            continue;
+        }
+        const bool argb = p.format == 2;  // PEBBLEGPU_DISPLAY_WATERFALL_ARGB32
+        switch (e.group) {
+        case 1: display_map_row<1>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
+        case 2: display_map_row<2>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
+        case 4: display_map_row<4>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
+        case 8: display_map_row<8>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
+        case 16: display_map_row<16>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
+        case 32: display_map_row<32>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
+        default: display_map_row<64>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
+        }
+    }
+}
+
+// the lane group run_screen_map gives each of n_streams rows: per chunk of kMapMaxGeom streams by the chunk's widest averaged pixel
+// (per_stream), one for all otherwise.  geoms / groups: n_streams entries each
+void map_row_plan(int32_t fft_size, double sample_rate, const int32_t *edges, bool per_stream, int n_streams, int32_t x_pixels, MapGeom *geoms, int *groups);
+// up to two panes in one launch on `s` (n_panes 1 or 2; a pane of 0 rows is left out, none left: no launch)
+int run_display_panes(hipStream_t s, const DisplayPaneArgs *panes, int n_panes);
+
 }  // namespace pg

@@ -460,6 +460,36 @@ int pebblegpu_receiver_record_release(pebblegpu_receiver *h, uint64_t call_index
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
     return h->rx.record_release(call_index);
 }
+int pebblegpu_receiver_display_open(pebblegpu_receiver *h, const pebblegpu_display_pane *panes, uint32_t n_panes, uint32_t n_slots)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.display_open(panes, n_panes, n_slots);
+}
+int pebblegpu_receiver_display_close(pebblegpu_receiver *h)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.display_close();
+}
+int pebblegpu_receiver_display_next(pebblegpu_receiver *h, int wait, pebblegpu_display_block *blocks)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.display_next(wait, blocks);
+}
+int pebblegpu_receiver_display_release(pebblegpu_receiver *h, uint64_t call_index)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.display_release(call_index);
+}
+int pebblegpu_receiver_display_dropped(const pebblegpu_receiver *h, uint64_t *blocks)
+{
+    if (!h || !blocks) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return const_cast<pebblegpu_receiver *>(h)->rx.display_dropped(blocks);
+}
+int pebblegpu_receiver_display_set_pane(pebblegpu_receiver *h, uint32_t pane, const pebblegpu_display_pane *geometry)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.display_set_pane(pane, geometry);
+}
 int pebblegpu_iq_record_convert(const float *iq, uint64_t n, int16_t *out)
 {
     if (n && (!iq || !out)) return fail(PEBBLEGPU_E_INVALID, "null argument");

@@ -694,6 +694,13 @@ public:
     int record_close();
     int record_next(int wait, pebblegpu_audio_block *b);
     int record_release(uint64_t call_index);
+    // the display ring (display.hip): the rows a call's display transforms computed, one or two panes per block, through the same slots
+    int display_open(const pebblegpu_display_pane *panes, uint32_t n_panes, uint32_t n_slots);
+    int display_close();
+    int display_set_pane(uint32_t pane, const pebblegpu_display_pane *p);
+    int display_next(int wait, pebblegpu_display_block *blocks);
+    int display_release(uint64_t call_index);
+    int display_dropped(uint64_t *blocks);
     int sync();
     int close_timing();  // records the end event a side-by-side call left out (no-op otherwise)
     const char *kernel_name(int which) const;  // the kernels behind pebblegpu_receiver_last_ms's groups, as last run
@@ -816,6 +823,11 @@ private:
     int upload_audio_table();
     int queue_audio_block(hipStream_t s, uint64_t n);
     int queue_record_block(hipStream_t s, const float2 *iq, const RawSrc *raw, uint64_t n);
+    struct DisplayRing *disp_ = nullptr;  // allocated at the first open, kept until the receiver goes (a reader may hold it)
+    bool disp_open_ = false;          // (under mu_: what a process call looks at)
+    int upload_display_tables();
+    int queue_display_block(hipStream_t spec_s, uint64_t spec_rows, hipStream_t zoom_s, uint64_t zoom_rows);
+    void display_destroy();
 };
 
 }  // namespace pg

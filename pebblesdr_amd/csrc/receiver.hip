@@ -120,6 +120,7 @@ Receiver::~Receiver()
     ext_ingest_.release();
     aout_.release();
     rec_.release();
+    display_destroy();  // (closes an open display ring: waits for a reader that is inside _next)
     if (d_aout_tab_) (void)hipFree(d_aout_tab_);
     if (d_zoom) (void)hipFree(d_zoom);
     if (map_ev_) (void)hipEventDestroy(map_ev_);
@@ -596,6 +597,8 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     touched_ = false;
     if (int rc = cond_.apply(stream_)) return rc;
     if (aout_.open && aout_tab_dirty_) { if (int rc = upload_audio_table()) return rc; }
+    if (disp_open_) { if (int rc = upload_display_tables()) return rc; }  // (only after open or set_pane)
+    uint64_t disp_spec_rows = 0, disp_zoom_rows = 0;  // the display ring's block: the rows THIS call computes (never a carried one)
     bool staged = false;  // a conversion pass was queued in front of the call
     // recording (egress.h): with the generator off a raw call is recorded from the raw samples themselves, whichever way the chain takes
     // them in (the same loader and scale as the conversion pass: the same values, and the recording needs no float2 copy of its own)
@@ -715,6 +718,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
             if (int rc = run_signal_strength(stream_, d_spec, F * (long long)bins, (int)bins, F, d_sm_bins, d_smeter, smeter_pitch, C)) return rc;
         }
     }
+    if (with_spectrum) disp_spec_rows = last_spec_frames;
     // (every record is a ~5 us bubble in the stream: a call with no display transform does without the one behind it)
     if (taps_ >> PEBBLEGPU_TAP_RAW_IQ & 1u) {  // (behind the display transform on its stream: the chain's start does not wait for the copy)
         if (raw) { if (int rc = run_normalize_iq(raw->fmt, raw->order, 1.0, raw->base, (long long)(S * n), d_tap_[PEBBLEGPU_TAP_RAW_IQ], stream_, false, &raw->scale)) return rc; }
@@ -792,6 +796,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
             last_zoom_frames = (uint64_t)(nd / nf);
         }
         zoom_stream_ = cs;
+        disp_zoom_rows = last_zoom_frames;
     }
     if (!wfm) {
         if (int rc = ff_.run(cs, dec_.out(), nd, audio.data(), audio.pitch)) return rc;  // receiver.cpp:950
@@ -922,6 +927,20 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         if (!have_oa) { if (int rc = osc_.advance_job(cs, n, &oa)) return rc; }
         if (int rc = run_save_tails(cs, jobs, C, &oa)) return rc;
     }
+    // The display ring's block, where Receiver::map_spectrum would queue a map of each source: the zoomed spectra on the stream that wrote
+    // them, the unprocessed spectrum on the main stream -- one stream, and one launch for both panes, unless the call's two pipelines end
+    // separately (PEBBLEGPU_PIPELINE=1).  A call that joins its streams does so first.  Ahead of the call's end record, so that whoever
+    // waits for the call (sync(), a join, the next call's transform on the same stream) waits for the launch too
+    bool joined = false;
+    if (disp_open_) {
+        hipStream_t spec_s = stream_;
+        if (side && !tun_.pipeline) {
+            if (!fuse_dec) PG_HIP(hipStreamWaitEvent(cs, ev[1], 0));
+            joined = true;
+            spec_s = cs;
+        }
+        if (int rc = queue_display_block(spec_s, disp_spec_rows, cs, disp_zoom_rows)) return rc;
+    }
     if (!bank_pipe) d_end_prev_ = nullptr;
     if (bank_pipe) {
         PG_HIP(hipEventRecord(ev[6], cs));
@@ -945,7 +964,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         // join: the call has ended once both pipelines have, and it ends on the chain's stream.  That stream is the main stream
         // of the next call (the two swap roles): its first kernel then follows this call's last in queue order, where a wait
         // on an event from the other queue cost ~25 us of idle GPU per call
-        if (!fuse_dec) PG_HIP(hipStreamWaitEvent(cs, ev[1], 0));
+        if (!fuse_dec && !joined) PG_HIP(hipStreamWaitEvent(cs, ev[1], 0));
         if (tun_.end_records) PG_HIP(hipEventRecord(ev[6], cs));
         else tm.open_slot = slot;  // (closed by the next call's start record, by sync() or by a timing query)
         std::swap(stream_, chain_stream_);
@@ -1087,8 +1106,8 @@ int Receiver::process_iq(const double *iq, uint16_t n, double *audio_out, uint32
         return fail(PEBBLEGPU_E_UNSUPPORTED, "the input conditioners run on the batched device path (pebblegpu_receiver_process) only");
     if (tb_.any() || taps_)  // (here `iq` is a host CPX *: the host injects and displays itself)
         return fail(PEBBLEGPU_E_UNSUPPORTED, "the test bench's generator and taps run on the batched device path (pebblegpu_receiver_process) only");
-    if (aout_.open || rec_.open)  // (this entry point returns its audio itself, and the host holds the frame it passes in)
-        return fail(PEBBLEGPU_E_UNSUPPORTED, "the audio and recording rings follow the batched device path (pebblegpu_receiver_process) only: close them first");
+    if (aout_.open || rec_.open || disp_open_)  // (this entry point returns its audio and its spectrum itself, and the host holds the frame it passes in)
+        return fail(PEBBLEGPU_E_UNSUPPORTED, "the audio, recording and display rings follow the batched device path (pebblegpu_receiver_process) only: close them first");
     PG_HIP(hipSetDevice(device));
     if (!d_stage_in_) PG_HIP(hipMalloc((void **)&d_stage_in_, sizeof(float2) * superframe));
     h_frame_.resize((size_t)nf * 2);
