@@ -513,7 +513,7 @@ static int launch_bank(void *kern, unsigned n_wg, hipStream_t s, const float2 *d
 }
 
 // the call's decimator as one launch of k_mix_dec_mfma (the caller has checked the sizes)
-int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, bool had_state, const OscAdvance *oa)
+int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, bool had_state, const OscAdvance *oa, hipEvent_t done_event, DecimDone *done)
 {
     const bool cic = fused_front;
     const HistBuf &y0b = cic ? buf1 : buf0;
@@ -612,7 +612,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
         for (int p = 0; p < 12; p++) bp.e[p] = 0.5f * (float)(bp.oa[p] - bp.ob[p]);
         if (int rc = launch_bank<12>(bv->kern, n_wg, s, d_in, fin.data(), (const ChanOsc *)osc.d_osc, osc.inline_dyn, xh, xh_out, y0_hist, d_y0stage2[y0_cur ^ 1], mixed, bp, done_event)) return rc;
     }
-    done_recorded = done_event != nullptr;
+    done->done_recorded = done_event != nullptr;
     if (tun.bank_clk) { if (int rc = report_clk(s, n_wg, L)) return rc; }
     hist_parity ^= 1;
     bank_state_parity ^= 1;
@@ -624,7 +624,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
     y0_cur ^= 1;
     y0_pending = true;
     // (with dyn_in the launch advanced the device blocks too; without, the caller's tail launch does and the next call finds dyn_out current)
-    osc_advanced = adv && dyn_valid;
+    done->osc_advanced = adv && dyn_valid;
     if (adv) dyn_parity ^= 1;
     dyn_valid = adv;
     return 0;
@@ -968,20 +968,21 @@ int DecimCore::run_beside_spectrum(hipStream_t s, const float2 *d_in, long long 
     return 0;
 }
 int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool shared_input, long long n, const OscBank &osc,
-                   hipEvent_t after_first, const RawSrc *raw, const OscAdvance *oa)
+                   hipEvent_t after_first, const RawSrc *raw, const OscAdvance *oa, DecimCall call, DecimDone *done)
 {
-    if (raw && !raw_ready(osc)) return fail(PEBBLEGPU_E_INVALID, "raw-format input reached a decimator path that has no converting loads");
+    DecimDone unread;
+    if (!done) done = &unread;
+    *done = DecimDone{};
+    if (raw && !raw_ready(osc, call.lds_free)) return fail(PEBBLEGPU_E_INVALID, "raw-format input reached a decimator path that has no converting loads");
     if (n <= 0 || n % (long long)chain.total != 0)
         return fail(PEBBLEGPU_E_SIZE, "%lld samples is not a multiple of the decimation %u", n, chain.total);
     len0 = n / first.stride;
     // successive calls write successive output buffers (tail_job_out carries the consumer's look-back into the next one's head-room)
-    if (fin3.base && rotate3) { std::swap(fin, fin2); std::swap(fin2, fin3); }  // (fin, fin2, fin3) <- (fin2, fin3, fin)
+    if (fin3.base && call.rotate3) { std::swap(fin, fin2); std::swap(fin2, fin3); }  // (fin, fin2, fin3) <- (fin2, fin3, fin)
     else if (fin2.base) std::swap(fin, fin2);  // (either way the call writes what was fin2, whose head-room the last call's consumer filled)
     const HistBuf *src = &buf0;
     last_fused = false;
     last_mfma = false;
-    osc_advanced = false;
-    done_recorded = false;
     const bool had_bank_state = bank_state_valid;
     bank_state_valid = false;  // (set again below when this call takes the matrix-pipe route)
     const bool had_dyn = dyn_valid;
@@ -994,7 +995,7 @@ int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool s
         if (bank_mfma && (unsigned long long)n * 8 < 0xFFF00000ull && (unsigned long long)C * (unsigned long long)fin.pitch * 8 < 0xFFF00000ull &&
             len_out >= 64 && (reinterpret_cast<uintptr_t>(d_in) & 7) == 0) {  // (its sample fetches and result stores carry 32-bit byte offsets)
             dyn_valid = had_dyn;
-            if (int rc = run_bank_mfma(s, d_in, n, osc, had_bank_state, oa)) return rc;
+            if (int rc = run_bank_mfma(s, d_in, n, osc, had_bank_state, oa, call.done_event, done)) return rc;
             if (after_first) PG_HIP(hipEventRecord(after_first, s));
             return 0;
         }
@@ -1038,7 +1039,7 @@ int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool s
         src = &buf1;
     } else {
         if (len0 > buf0.cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
-        if (bank_front && C == 1 && want_lds_free && !osc.any_transient()) {
+        if (bank_front && C == 1 && call.lds_free && !osc.any_transient()) {
             // beside the spectrum kernel: the lean one-channel kernel for every output inside the call, and the general one
             // (a handful of lanes) for the first outputs, whose windows reach back into the mixed history, and the new history
             const int R = 8;
@@ -1055,7 +1056,7 @@ int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool s
                 launch(raw ? k_mix_hb11_bank<false, false, true> : k_mix_hb11_bank<false, false, false>, dim3(len0 / (4LL * R * 64) != 0 ? 2 : 1, 1), dim3(256), s, d_in, in_pitch,
                        (int)shared_input, buf0.data(), buf0.pitch, len0, (const ChanOsc *)osc.d_osc, (const float2 *)d_hist_mixed[hist_parity], d_hist_mixed[hist_parity ^ 1],
                        (int)kMaxTaps, (const float *)osc.d_amp, osc.a_inf, bank_taps, first.gain, osc.inline_dyn, 0, (int)C, R, j_first, rs);
-        } else if (bank_front && (C >= 16 ? shared_input : want_lds_free)) {
+        } else if (bank_front && (C >= 16 ? shared_input : call.lds_free)) {
  // a bank off one shared stream: lanes = channels, windows in registers (k_mix_hb11_bank)
             int cl_log2 = 0;
             while ((1u << cl_log2) < C && cl_log2 < 6) cl_log2++;
@@ -1338,9 +1339,9 @@ int AmCore::set_list(hipStream_t s, const std::vector<int> &am_channels)
     }
     return 0;
 }
-int AmCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate)
+int AmCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate, bool defer_tail)
 {
-    last_n = 0;
+    deferred_n = 0;
     if (list.empty()) return 0;
     if (n > tmp.cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
     if (n < tmp.hist) return fail(PEBBLEGPU_E_SIZE, "AM demod needs at least %d samples per call", tmp.hist);
@@ -1352,8 +1353,8 @@ int AmCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out
            (int)nsub, -1, (const int *)d_list, gate);
     launch(k_fir_dec, dim3(cdiv(n, 256), na), dim3(256), s, (const float2 *)tmp.data(), tmp.pitch, out, out_pitch, n, 1,
            (const float *)d_taps, (const float *)nullptr, (int)kMaxTaps, (const int *)d_ntaps, 0, 1.0f, 0, (const int *)d_list, gate);
-    last_n = n;
-    if (!defer_tail) launch(k_save_tail, dim3(cdiv(tmp.hist, 256), na), dim3(256), s, tmp.data(), tmp.pitch, n, tmp.hist, (const int *)d_list, gate);
+    if (defer_tail) deferred_n = n;
+    else launch(k_save_tail, dim3(cdiv(tmp.hist, 256), na), dim3(256), s, tmp.data(), tmp.pitch, n, tmp.hist, (const int *)d_list, gate);
     PG_HIP(hipGetLastError());
     return 0;
 }

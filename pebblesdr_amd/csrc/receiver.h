@@ -8,13 +8,15 @@
 //   WfmCore     <- Demod_WFM (mono)            (application/demod/demod_wfm.cpp)
 //   SpectrumCore<- FFT::fftSpectrum            (pebblelib/fft.cpp)
 // Receiver composes them the way Receiver::processIQData does; the stand-alone steps (steps.hip) wrap one
-// core each behind the reference's per-class call shapes.
+// core each behind the reference's per-class call shapes.  What one call asks of a core travels in that call's arguments
+// (DecimCall / DecimDone, AmCore::run's defer_tail); the route of a Receiver call is planned once, in call_route.h.
 #pragma once
 #include <algorithm>
 #include <complex>
 #include <mutex>
 #include <vector>
 #include "../../include/pebblegpu.h"
+#include "call_route.h"
 #include "common.h"
 #include "design.h"
 #include "egress.h"
@@ -105,6 +107,17 @@ struct OscBank {
 // ---- Mixer + Decimator ----
 bool bank_variant(int np, int t1, int t2, int t3, int *hy, int *nstate, int *minw);  // a k_mix_dec_mfma instance exists for this front and triple
 
+// what one DecimCore::run call is asked for, and what it reports back
+struct DecimCall {
+    bool lds_free = false;            // the first kernel should leave LDS alone (it runs beside the display transform)
+    bool rotate3 = true;              // this call rotates three output buffers (ignored without fin3)
+    hipEvent_t done_event = nullptr;  // an event to complete WITH the call's last launch when that is the bank kernel
+};
+struct DecimDone {
+    bool osc_advanced = false;        // the route's kernel advanced the oscillators itself
+    bool done_recorded = false;       // DecimCall::done_event was completed (else the caller records it)
+};
+
 struct DecimCore {
     design::Chain chain;
     uint32_t C = 0;
@@ -118,7 +131,6 @@ struct DecimCore {
     bool fused_front = false;        // merged CIC3 + wide halfband in one kernel (k_mix_cic_hb): nothing is written at the CIC rate
     FrontTaps wide_fir;              // the wide stage's taps as kernel arguments (fused_front)
     bool bank_front = false;         // hb11 first stage in registers (k_mix_hb11_bank): a >= 16-channel bank off a shared stream, or one channel when asked
-    bool want_lds_free = false;      // set per call by the owner: the first kernel should leave LDS alone (it runs beside the display transform)
     bool front_is_lds_free() const { return C == 1 && (fused_front || bank_front); }
     FrontTaps bank_taps;
     // the whole decimator in one kernel (k_mix_dec_fused): a >= 16-channel bank off one shared stream whose chain is hb11 x S
@@ -134,7 +146,7 @@ struct DecimCore {
     // the default route of such a bank; PEBBLEGPU_BANK_DEC=0 keeps the four-wave pipeline above
     bool bank_mfma = false;
     int bank_nstate = 0, bank_minw = 2;          // running sums per channel of the chain's instance; waves per SIMD it admits
-    int run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, bool had_state, const OscAdvance *oa);
+    int run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, bool had_state, const OscAdvance *oa, hipEvent_t done_event, DecimDone *done);
     int xh_depth = 16;                           // samples of raw-input tail kept in d_xhist
     float2 *d_bank_state[2] = {nullptr, nullptr};  // [C][38] the halfbands' running sums where the last k_mix_dec_mfma call ended (ping-pong)
     int bank_state_parity = 0;
@@ -164,7 +176,9 @@ struct DecimCore {
     size_t ph_cap = 0;
     int set_fuse_window(const float *d_window, const std::vector<float> &w);  // the owner's display transform uses this window
     bool shape_for_spectrum() const;               // the chain is the one the kernel is built for
-    bool spectrum_can_run(const OscBank &osc) const { return shape_for_spectrum() && fuse_window && want_lds_free && !osc.any_transient(); }
+    bool fuse_shape() const { return shape_for_spectrum() && fuse_window; }  // ... and the owner's transform has handed over its window
+    // lds_free: the call asks for a first kernel that leaves LDS alone (DecimCall::lds_free)
+    bool spectrum_can_run(const OscBank &osc, bool lds_free) const { return fuse_shape() && lds_free && !osc.any_transient(); }
     // fills the kernel's parameter block for a call of n samples (before the transform is launched)
     int fill_dec_fuse(hipStream_t s, DecFuse *df, const OscBank &osc, long long n);
     // what is left for the chain's stream in such a call: the mixed-sample history for a later general call (two workgroups)
@@ -179,10 +193,9 @@ struct DecimCore {
     void release();
     // n must be a multiple of chain.total; any such n streams exactly (no minimum frame length)
     // oa (from OscBank::advance_job for this call, or nullptr): when the route's kernel can advance the oscillators itself it does, and
-    // osc_advanced says so (the caller then leaves the advance out of its tail launch)
+    // DecimDone::osc_advanced says so (the caller then leaves the advance out of its tail launch)
     int run(hipStream_t s, const float2 *d_in, long long in_pitch, bool shared_input, long long n, const OscBank &osc,
-            hipEvent_t after_first = nullptr, const RawSrc *raw = nullptr, const OscAdvance *oa = nullptr);
-    bool osc_advanced = false;
+            hipEvent_t after_first = nullptr, const RawSrc *raw = nullptr, const OscAdvance *oa = nullptr, DecimCall call = DecimCall{}, DecimDone *done = nullptr);
     bool last_mfma = false;                 // the last run() was a k_mix_dec_mfma launch
     int flush_y0(hipStream_t s);
     OscDyn *d_dyn[2] = {nullptr, nullptr};  // [C] the oscillators' per-call fields as k_mix_dec_mfma hands them from call to call (ping-pong)
@@ -191,14 +204,12 @@ struct DecimCore {
     uint64_t dyn_epoch_seen = 0;
     bool y0_pending = false;                // d_y0stage holds first-stage history the stage-0 head-room has not received yet (copied when a call needs it there)
     // the first kernels this call would run read raw device-format samples themselves (k_mix_hb11_lean + its edge launch)
-    bool raw_ready(const OscBank &osc) const { return bank_front && C == 1 && want_lds_free && !osc.any_transient() && !(fused_all || bank_mfma); }
+    bool raw_front() const { return bank_front && C == 1 && !(fused_all || bank_mfma); }  // those kernels exist for this chain
+    bool raw_ready(const OscBank &osc, bool lds_free) const { return raw_front() && lds_free && !osc.any_transient(); }
     void tail_jobs(std::vector<TailJob> &jobs) const;  // after run(): what must be refreshed before the next call
     // Two output buffers, written by alternate calls, so that whatever reads a call's output (the band-pass) may run on another stream
     // beside the NEXT call's decimator: the consumer's look-back (the head-room) is carried from the buffer just written into the other
     // one's head-room.  tail_jobs() = tail_jobs_dec() (the decimator's own histories: its stream) + tail_job_out() (the consumer's stream)
-    hipEvent_t done_event = nullptr;         // set by the caller before run(): an event to complete WITH the call's last launch when that is the bank kernel ...
-    bool done_recorded = false;              // ... and whether run() did so (else the caller records it)
-    bool rotate3 = true;                     // this call rotates three output buffers (set by the caller before run(); ignored without fin3)
     // a call of this many input samples is "long": chunks of 128 outputs or more, where two output buffers do as well as three
     bool long_call(long long n) const { const long long lo = n / (long long)chain.total; return (lo + 2 * std::max(1LL, 1024LL / ((C + 31) / 32)) - 1) / (2 * std::max(1LL, 1024LL / ((C + 31) / 32))) >= 128; }
     HistBuf fin2, fin3;                      // fin: this call's; fin2: the next call's (its head-room filled by this call's consumer); fin3: a third, written by the call after that,
@@ -249,12 +260,11 @@ struct AmCore {
     int set_bandwidth(hipStream_t s, uint32_t ch, double bw);   // Demod_AM::setBandwidth, demod_am.cpp:17-21
     int set_list(hipStream_t s, const std::vector<int> &am_channels);
     // in/out rows may be the same buffer (the scan reads `in`, the FIR writes `out`)
-    int run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate = Gate{nullptr, 0, 0});
     // defer_tail: run() leaves the refresh of tmp's head-room to the caller's tail launch (tail_jobs: every row, also those of channels
     // that are not AM -- harmless; not for gated calls, whose closed channels keep their history)
-    bool defer_tail = false;
-    long long last_n = 0;
-    void tail_jobs(std::vector<TailJob> &jobs) const { if (defer_tail && !list.empty() && last_n > 0) jobs.push_back(TailJob{tmp.data(), tmp.pitch, last_n, tmp.hist, 0, nullptr, 0}); }
+    int run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate = Gate{nullptr, 0, 0}, bool defer_tail = false);
+    long long deferred_n = 0;       // samples of the last run() whose tail refresh was left to the caller (0: none)
+    void tail_jobs(std::vector<TailJob> &jobs) const { if (!list.empty() && deferred_n > 0) jobs.push_back(TailJob{tmp.data(), tmp.pitch, deferred_n, tmp.hist, 0, nullptr, 0}); }
 };
 
 // ---- Demod_NFM / Demod_SAM (PLL demodulators) ----
@@ -760,6 +770,54 @@ private:
         bool bp_valid = false, bp_dirty = false, am_dirty = true;
     };
     int apply_controls(hipStream_t osc_stream);
+    // One process call (receiver.hip): its route is planned once (call_route.h) from call_facts(), then its stages are queued in order.
+    // What the stages hand to one another lives in one Call on the stack of process().
+    struct Call {
+        uint64_t n = 0;
+        bool with_spectrum = false, with_chain = false;
+        CallRoute rt;
+        hipEvent_t *ev = nullptr;         // the call's timing slot (Timers::slot) ...
+        int slot = 0;                     // ... and its number
+        hipStream_t cs = nullptr;         // where the chain is being queued (the chain's stream from the fork or the hand-over on)
+        const float2 *d_iq = nullptr;     // the input as the next stage reads it ...
+        long long in_pitch = 0;           // ... and its row pitch
+        const float2 *tap_iq = nullptr;   // the input before the conditioners (raw-IQ tap, recording)
+        const RawSrc *raw = nullptr;      // raw source while the call's kernels convert in their own loads (null once staged)
+        RawSrc rec_raw = {nullptr, 0, 0, 0.f, 0};  // what the recording ring reads of a raw call
+        bool rec_from_raw = false;
+        OscAdvance oa_pre = {};           // the oscillators' advance offered to the decimator (cleared when its kernel carried it)
+        bool have_oa = false;
+        DecFuse df;                       // the in-transform decimator's parameter block (CallRoute::fuse_dec)
+        bool carry_before = false;        // a computed spectrum from before this call exists
+        uint64_t disp_spec_rows = 0, disp_zoom_rows = 0;  // the display ring's block: the rows THIS call computes (never a carried one)
+        long long nd = 0;                 // decimated samples per channel
+        bool gate_closed = false;         // the call ends behind the band-pass: squelch read-back below the threshold, or tune-only mode
+        bool tails_carried = false;       // the WFM kernel's launch carried the call's tail refresh
+    };
+    int refuse_call(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw) const;
+    CallFacts call_facts(uint64_t n, bool with_spectrum, bool with_chain, bool raw) const;
+    int join_and_apply(Call &c);
+    int stage_input(Call &c);
+    int start_call(Call &c);
+    int run_display_transform(Call &c);
+    int tap_and_record_input(Call &c);
+    int end_without_chain(Call &c);
+    int run_decimator(Call &c);
+    int run_zoomed_transform(Call &c);
+    int bandpass_and_gate(Call &c);
+    int tail_closed(Call &c);
+    int tail_bank_gated(Call &c);
+    int tail_narrow(Call &c);
+    int tail_wfm(Call &c);
+    int finish_chain(Call &c);
+    int end_call(Call &c);
+    int join_streams();
+    int raw_stage(float2 **p);
+    int handover_event(hipEvent_t *e);
+    int read_gate(hipStream_t cs, const float4 *src, bool *closed);
+    int clear_tune_only_rows(hipStream_t cs, float2 *row0, long long pitch, long long n);
+    int measure_carry(hipStream_t st);
+    int process_slot(IngestRing &ring, uint32_t slot, int fmt, int order, double gain, uint64_t n);
     std::mutex mu_;
     hipStream_t stream_ = nullptr;
     // The display transform is arithmetic-bound and the front of the chain memory-bound: when the chain's first kernel

@@ -547,10 +547,11 @@ int Receiver::apply_controls(hipStream_t osc_stream)
     return 0;
 }
 
-int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw)
+// ---- one process call: its refusals, its route (call_route.h), then its stages in queue order ----
+
+// caller mistakes that leave the handle usable: refused before anything is queued
+int Receiver::refuse_call(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw) const
 {
-    std::lock_guard<std::mutex> g(mu_);
-    PG_HIP(hipSetDevice(device));
     if (failed_) return fail(PEBBLEGPU_E_HIP, "an earlier call on this receiver failed half-way (its filter histories no longer match its oscillators): destroy it");
     if ((!d_iq && !raw) || n == 0) return fail(PEBBLEGPU_E_INVALID, "null input or zero samples");
     if (with_chain && (n % superframe != 0 || n / superframe > max_sf))
@@ -564,143 +565,187 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
         return fail(PEBBLEGPU_E_INVALID, "the squelch gate needs a spectrum: none has been computed yet");
     if (with_chain && !wfm && bank_gate_ && !with_spectrum && !(squelch_db_ > -120.0) && !(C == 1 && ctl_[0].mode == PEBBLEGPU_DM_NONE))
         return fail(PEBBLEGPU_E_INVALID, "the squelch gate of a bank reads the spectra of the same call: create the bank with spectrum_bins");
-    // side by side: the chain goes to its own stream while the display transform keeps the arithmetic units busy (only when
-    // the chain's first kernel needs no LDS -- the transform's workgroups leave none -- and nothing downstream reads the
-    // spectrum or a conditioned copy of the input)
-    const bool side = with_spectrum && with_chain && !profile_detail && squelch_db_ <= -120.0 && !bank_gate_ && dec_.front_is_lds_free() && !cond_.any && !cond_.dirty;
-    // Pipelined calls: the display transforms of successive calls follow one another on the main stream and the chains on the
-    // chain's stream -- neither waits for the other's previous call (they share nothing: the transform carries its previous
-    // amplitudes, the chain its histories and oscillators), so a call's short, LDS-hungry tail kernels run beside the NEXT
-    // call's transform instead of on an idle GPU.  Results are complete after sync() (the contract of include/pebblegpu.h).
-    // Anything else -- a control change to apply, a call of another shape -- first orders the two queues behind each other.
-    const bool was_touched = touched_;
+    return 0;
+}
+
+// what plan_call_route() reads, as the handle stands before anything of the call is queued
+CallFacts Receiver::call_facts(uint64_t n, bool with_spectrum, bool with_chain, bool raw) const
+{
+    CallFacts f;
+    f.with_spectrum = with_spectrum;
+    f.with_chain = with_chain;
+    f.raw = raw;
+    f.n = n;
+    f.C = C;
+    f.S = S;
+    f.nf = nf;
+    f.zoom_bins = zoom_bins;
+    f.wfm = wfm;
+    f.bank_pipe_ok = bank_pipe_ok_;
+    f.profiling = profile_detail;
+    f.squelch_set = squelch_db_ > -120.0;
+    f.bank_gate = bank_gate_;
+    f.gated = gated();
+    f.touched = touched_;
+    f.cond_any = cond_.any;
+    f.cond_dirty = cond_.dirty;
+    f.generator = tb_.any();
+    f.taps = taps_ != 0;
+    f.recording = rec_.open;
+    f.ch0_tune_only = ctl_[0].mode == PEBBLEGPU_DM_NONE;
+    f.dec_lds_free_front = dec_.front_is_lds_free();
+    f.dec_raw_front = dec_.raw_front();
+    f.dec_double_out = dec_.double_out();
+    f.dec_triple_out = dec_.fin3.base != nullptr;
+    f.dec_long_call = dec_.long_call((long long)n);
+    f.dec_fuse_shape = dec_.fuse_shape();
+    f.osc_transient = osc_.any_transient();
+    f.spec_raw_ready = spec_.raw_ready();
+    f.spec_dec_ready = spec_.dec_ready();
+    f.pipeline = tun_.pipeline;
+    f.fuse_dec = tun_.fuse_dec;
+    f.bank_pipe_extev = tun_.bank_pipe_extev;
+    f.bank_pipe_timed_ev = tun_.bank_pipe_timed_ev;
+    return f;
+}
+
+int Receiver::join_streams()
+{
+    if (chain_end_) PG_HIP(hipStreamWaitEvent(stream_, chain_end_, 0));
+    if (spec_end_) PG_HIP(hipStreamWaitEvent(chain_stream_, spec_end_, 0));
+    chain_end_ = spec_end_ = nullptr;
+    return 0;
+}
+
+// the staging buffer of raw and generated calls (allocated on first use)
+int Receiver::raw_stage(float2 **p)
+{
+    if (!d_raw_stage_) PG_HIP(hipMalloc((void **)&d_raw_stage_, sizeof(float2) * (size_t)S * max_sf * superframe));
+    *p = d_raw_stage_;
+    return 0;
+}
+
+// this call's stage 1 -> stage 2 hand-over event (no timing; the ring is created on first use)
+int Receiver::handover_event(hipEvent_t *e)
+{
+    if (!sync_ev_[0]) for (hipEvent_t &ne : sync_ev_) PG_HIP(hipEventCreateWithFlags(&ne, hipEventDisableTiming));
+    *e = sync_ev_[tm.calls % 4];
+    return 0;
+}
+
+// the one-value squelch gate: the host reads one S-meter value back behind whatever `cs` has queued
+int Receiver::read_gate(hipStream_t cs, const float4 *src, bool *closed)
+{
+    PG_HIP(hipMemcpyAsync(h_gate_, src, sizeof(float4), hipMemcpyDeviceToHost, cs));
+    PG_HIP(hipStreamSynchronize(cs));
+    *closed = (double)h_gate_->y < squelch_db_;  // m_avgDb < m_squelchDb
+    return 0;
+}
+
+// clearCPX(m_audioBuf, ...) of a bank's tune-only channels: rows of n samples, `pitch` apart
+int Receiver::clear_tune_only_rows(hipStream_t cs, float2 *row0, long long pitch, long long n)
+{
+    for (uint32_t ch = 0; ch < C; ch++)
+        if (ctl_[ch].mode == PEBBLEGPU_DM_NONE) PG_HIP(hipMemsetAsync(row0 + (long long)ch * pitch, 0, sizeof(float2) * (size_t)n, cs));
+    return 0;
+}
+
+// the carried row's S-meter with the channels' current bands (before this call's rows replace the row)
+int Receiver::measure_carry(hipStream_t st)
+{
+    if (!(gated() && smeter_on && have_carry_)) return 0;
+    return run_signal_strength(st, d_spec_carry, (long long)bins, (int)bins, 1, d_sm_bins, d_sm_carry, 1, C);
+}
+
+// join (unless the call is pipelined with its neighbours), apply the controls, upload the tables
+int Receiver::join_and_apply(Call &c)
+{
     for (uint64_t &tn : tap_n_) tn = 0;  // a tap holds the last call's signal: a point this call does not reach reads as "nothing" (NULL), never as an older call's
-    // Two-stage calls of a receiver without a display transform: mixer + decimator (and the refresh of their histories) on the main
-    // stream, band-pass, noise filter, AGC, demodulators and resampler on the chain's stream behind an event -- the decimator of the next
-    // call does not wait for them (it writes the other output buffer; it does wait for the band-pass of the call before the last, which
-    // read that buffer).  The decimator of a bank leaves the vector units idle two thirds of the time (one wave per SIMD, bound by
-    // its own instruction stream): the band-pass of the previous call fits beside it.  Results are complete after sync().
-    const bool bank_pipe = bank_pipe_ok_ && with_chain && !with_spectrum && !profile_detail && squelch_db_ <= -120.0 && !bank_gate_ && !zoom_bins &&
-                           !cond_.any && !cond_.dirty && !tb_.any() && !taps_ && !rec_.open && dec_.double_out();
-    // (a call with the test bench's generator on is staged through a buffer successive calls share, as a conditioned call is: it may run its
-    // chain beside its own display transform -- the kernels of the same call without a generator, so that injecting on the device and
-    // feeding the summed stream give the same audio bit for bit -- but never pipelined with its neighbours, and never raw-fused)
-    const bool plain = ((side && tun_.pipeline && !touched_) || (bank_pipe && !touched_)) && !tb_.any();
-    auto join = [&]() -> int {
-        if (chain_end_) PG_HIP(hipStreamWaitEvent(stream_, chain_end_, 0));
-        if (spec_end_) PG_HIP(hipStreamWaitEvent(chain_stream_, spec_end_, 0));
-        chain_end_ = spec_end_ = nullptr;
-        return 0;
-    };
-    if (!plain) { if (int rc = join()) return rc; }
-    if (int rc = apply_controls(plain ? chain_stream_ : stream_)) return rc;
+    if (!c.rt.plain) { if (int rc = join_streams()) return rc; }
+    if (int rc = apply_controls(c.rt.plain ? chain_stream_ : stream_)) return rc;
     touched_ = false;
     if (int rc = cond_.apply(stream_)) return rc;
     if (aout_.open && aout_tab_dirty_) { if (int rc = upload_audio_table()) return rc; }
     if (disp_open_) { if (int rc = upload_display_tables()) return rc; }  // (only after open or set_pane)
-    uint64_t disp_spec_rows = 0, disp_zoom_rows = 0;  // the display ring's block: the rows THIS call computes (never a carried one)
-    bool staged = false;  // a conversion pass was queued in front of the call
-    // recording (egress.h): with the generator off a raw call is recorded from the raw samples themselves, whichever way the chain takes
-    // them in (the same loader and scale as the conversion pass: the same values, and the recording needs no float2 copy of its own)
-    const RawSrc rec_raw = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
-    const bool rec_from_raw = raw != nullptr && !tb_.any();
-    if (raw) {
-        // Raw device-format input: when the call's first kernels convert in their own loads (the 8192-bin display transform
-        // and the one-channel first stage beside it) there is no float2 copy of the stream at all; otherwise normalizeIQ runs
-        // as its own pass into a staging buffer and the call goes on from there.
-        dec_.want_lds_free = side;
-        const bool fused = side && S == 1 && spec_.raw_ready() && dec_.raw_ready(osc_) && !tb_.any();
-        staged = !fused;
-        if (!fused) {
-            if (plain && !bank_pipe) { if (int rc = join()) return rc; }  // the staging buffer is shared by successive calls (two-stage calls: only their first stage touches it)
-            if (!d_raw_stage_) PG_HIP(hipMalloc((void **)&d_raw_stage_, sizeof(float2) * (size_t)S * max_sf * superframe));
-            // streams are stream-major in both layouts, so one pass over S * n pairs converts them all
-            if (int rc = run_normalize_iq(raw->fmt, raw->order, 1.0, raw->base, (long long)(S * n), d_raw_stage_, stream_, false, &raw->scale)) return rc;
-            d_iq = d_raw_stage_;
-            raw = nullptr;
-        }
+    return 0;
+}
+
+// the input as the call's kernels read it: raw conversion, generator, conditioners
+int Receiver::stage_input(Call &c)
+{
+    if (c.raw && !c.rt.raw_fused) {
+        if (c.rt.plain && !c.rt.bank_pipe) { if (int rc = join_streams()) return rc; }  // the staging buffer is shared by successive calls (two-stage calls: only their first stage touches it)
+        float2 *stage = nullptr;
+        if (int rc = raw_stage(&stage)) return rc;
+        // streams are stream-major in both layouts, so one pass over S * n pairs converts them all
+        if (int rc = run_normalize_iq(c.raw->fmt, c.raw->order, 1.0, c.raw->base, (long long)(S * c.n), stage, stream_, false, &c.raw->scale)) return rc;
+        c.d_iq = stage;
+        c.raw = nullptr;
     }
-    long long in_pitch = (long long)n;
+    c.in_pitch = (long long)c.n;
     // TestBench::genSweep + genNoise, receiver.cpp:797-798: into the library's staging buffer (a raw call has been converted into it above:
     // generated in place; float2 input is read from the caller's buffer, which is never written)
     last_tb_ = tb_.any();
     last_tb_morse_ = tb_.morse_on();
     if (last_tb_) {
-        if (!d_raw_stage_) PG_HIP(hipMalloc((void **)&d_raw_stage_, sizeof(float2) * (size_t)S * max_sf * superframe));
-        if (int rc = tb_.run(stream_, d_iq, in_pitch, d_raw_stage_, in_pitch, (long long)n, S, 0)) return rc;
-        d_iq = d_raw_stage_;
-        staged = true;
+        float2 *stage = nullptr;
+        if (int rc = raw_stage(&stage)) return rc;
+        if (int rc = tb_.run(stream_, c.d_iq, c.in_pitch, stage, c.in_pitch, (long long)c.n, S, 0)) return rc;
+        c.d_iq = stage;
     }
-    const float2 *tap_iq = d_iq;  // displayData(.., TB_RAW_IQ), receiver.cpp:803: before the conditioners
+    c.tap_iq = c.d_iq;  // displayData(.., TB_RAW_IQ), receiver.cpp:803: before the conditioners
     // DCRemoval, IQBalance, NoiseBlanker 1/2 on the raw streams, ahead of the spectrum and the mixer (receiver.cpp:814-823)
-    if (int rc = cond_.run(stream_, d_iq, in_pitch, (long long)n, &d_iq, &in_pitch)) return rc;
-    hipEvent_t *ev = tm.slot();
-    const int slot = (int)(tm.calls % Timers::kRing);
+    return cond_.run(stream_, c.d_iq, c.in_pitch, (long long)c.n, &c.d_iq, &c.in_pitch);
+}
+
+// the call's timing slot, its start record, the fork, and the wait for the last reader of the output buffer it writes
+int Receiver::start_call(Call &c)
+{
+    c.ev = tm.slot();
+    c.slot = (int)(tm.calls % Timers::kRing);
     tm.calls++;
     // Every event record is a packet of its own in the queue (~6 us of idle GPU between two kernels).  A side-by-side call therefore
     // records no end event: it ends where the next call's start event is recorded (same queue, nothing in between), or where
     // sync() / a timing query closes it (close_timing).
-    hipEvent_t start = ev[0];
-    if (bank_pipe && plain && d_end_prev_) start = d_end_prev_;  // (back to back, a two-stage call is timed from where the previous one ended: one queue packet less)
-    else PG_HIP(hipEventRecord(ev[0], stream_));
-    tm.start_ev[slot] = start;
+    hipEvent_t start = c.ev[0];
+    if (c.rt.bank_pipe && c.rt.plain && d_end_prev_) start = d_end_prev_;  // (back to back, a two-stage call is timed from where the previous one ended: one queue packet less)
+    else PG_HIP(hipEventRecord(c.ev[0], stream_));
+    tm.start_ev[c.slot] = start;
     if (tm.open_slot >= 0) {
         tm.end_ev[tm.open_slot] = start;
         tm.open_slot = -1;
     }
-    tm.end_ev[slot] = ev[6];
-    hipStream_t cs = side ? chain_stream_ : stream_;
-    if (side) {
+    tm.end_ev[c.slot] = c.ev[6];
+    c.cs = c.rt.side ? chain_stream_ : stream_;
+    if (c.rt.side) {
         PG_HIP(hipStreamWaitEvent(chain_stream_, start, 0));  // fork: the input is ready where the call starts
     }
     // the output buffer this call writes was read three (two) calls ago (a wait is a queue packet: none when the host can see that it is over)
-    // three output buffers in rotation for short calls, two for long ones (chunks of 128 outputs or more: 0.917 / 0.923 ms per configs[2]
-    // call of 128 super-frames with two against 0.950-0.989 with three, the same at 32, 0.0775 against 0.0658 at 8)
-    const bool rot3 = bank_pipe && dec_.fin3.base && !dec_.long_call((long long)n);
-    dec_.rotate3 = rot3;
-    {
-        hipEvent_t last_reader = nullptr;  // where the second stage that last read the buffer this call writes (dec_.fin2) ended
-        for (const auto &pr : out_reader_) if (pr.first == (const void *)dec_.fin2.base) last_reader = pr.second;
-        if (bank_pipe && last_reader && hipEventQuery(last_reader) != hipSuccess) {
-            // the host is more than two calls ahead of the device: it waits here (PEBBLEGPU_BANK_PIPE_HOSTWAIT=0: a wait in the queue instead,
-            // one more packet between this decimator and the last)
-            if (tun_.bank_pipe_hostwait) PG_HIP(hipEventSynchronize(last_reader));
-            else PG_HIP(hipStreamWaitEvent(stream_, last_reader, 0));
-        }
+    hipEvent_t last_reader = nullptr;  // where the second stage that last read the buffer this call writes (dec_.fin2) ended
+    for (const auto &pr : out_reader_) if (pr.first == (const void *)dec_.fin2.base) last_reader = pr.second;
+    if (c.rt.bank_pipe && last_reader && hipEventQuery(last_reader) != hipSuccess) {
+        // the host is more than two calls ahead of the device: it waits here (PEBBLEGPU_BANK_PIPE_HOSTWAIT=0: a wait in the queue instead,
+        // one more packet between this decimator and the last)
+        if (tun_.bank_pipe_hostwait) PG_HIP(hipEventSynchronize(last_reader));
+        else PG_HIP(hipStreamWaitEvent(stream_, last_reader, 0));
     }
-    // From here on a failing step leaves kernels queued (on the chain stream too) and histories half advanced: whatever the
-    // exit, join the two streams so later work is ordered behind what was queued, and refuse further calls on the handle.
-    struct Guard {
-        Receiver *r; hipEvent_t *ev; hipStream_t cs; bool side, armed;
-        ~Guard()
-        {
-            if (!armed) return;
-            r->failed_ = true;
-            if (side && hipEventRecord(ev[6], cs) == hipSuccess) r->chain_end_ = ev[6];
-        }
-    } guard{this, ev, bank_pipe ? chain_stream_ : cs, side || bank_pipe, true};
-    // One channel through hb11 x 8, hb15, hb23, hb47 beside the 8192-bin transform: the transform's workgroups can compute the decimator
-    // from the frames they hold (k_spectrum_t128<.., DEC>): the stream crosses HBM once, nothing is written at the intermediate rates.
-    // Opt-in (PEBBLEGPU_FUSE_DEC=1 when the receiver is created): measured slower -- the stages sit in the kernel's barrier intervals,
-    // 0.297 ms against 0.247 beside the stand-alone first stage, the call 0.330 against 0.293
-    dec_.want_lds_free = side;
-    const bool fuse_dec = tun_.fuse_dec && !gated() && side && with_chain && !tun_.pipeline && S == 1 && spec_.dec_ready() && nf == 2048 && dec_.spectrum_can_run(osc_) && (!raw || !staged);
-    DecFuse df;
-    if (fuse_dec) { if (int rc = dec_.fill_dec_fuse(stream_, &df, osc_, (long long)n)) return rc; }
-    const bool carry_before = have_carry_;  // a computed spectrum from before this call exists (what its first super-frames' squelch reads)
-    // the carried row's S-meter with the channels' current bands (before this call's rows replace the row)
-    auto measure_carry = [&](hipStream_t st) -> int {
-        if (!(gated() && smeter_on && have_carry_)) return 0;
-        return run_signal_strength(st, d_spec_carry, (long long)bins, (int)bins, 1, d_sm_bins, d_sm_carry, 1, C);
-    };
-    if (with_spectrum && gated()) {
+    return 0;
+}
+
+// the display transform, its S-meter and the carried row
+int Receiver::run_display_transform(Call &c)
+{
+    if (c.rt.fuse_dec) { if (int rc = dec_.fill_dec_fuse(stream_, &c.df, osc_, (long long)c.n)) return rc; }
+    c.carry_before = have_carry_;  // a computed spectrum from before this call exists (what its first super-frames' squelch reads)
+    const uint64_t n = c.n;
+    if (c.with_spectrum && gated()) {
         // SignalSpectrum::unprocessed behind its update timer (signalspectrum.cpp:63-86): the host has the frame list before anything is
         // queued; the transform runs over that list alone, rows compact, |X_prev| from listed frame to listed frame
         sel_spec_.clear();
         ut_spec_.advance(spec_ups_, spec_period_ms_, n / nf, nf, (uint64_t)fs, &sel_spec_);
         const long long ns = (long long)sel_spec_.size();
         if (int rc = measure_carry(stream_)) return rc;
-        if (int rc = spec_.run_list(stream_, d_iq, in_pitch, sel_spec_.data(), ns, d_spec, raw)) return rc;
+        if (int rc = spec_.run_list(stream_, c.d_iq, c.in_pitch, sel_spec_.data(), ns, d_spec, c.raw)) return rc;
         last_spec_frames = (uint64_t)ns;
         if (ns) {
             if (smeter_on) { if (int rc = run_signal_strength(stream_, d_spec, ns * (long long)bins, (int)bins, ns, d_sm_bins, d_smeter, smeter_pitch, C)) return rc; }
@@ -708,225 +753,268 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
                                     hipMemcpyDeviceToDevice, stream_));
             have_carry_ = true;
         }
-    } else if (with_spectrum) {  // SignalSpectrum::unprocessed on the raw frame, receiver.cpp:826
+    } else if (c.with_spectrum) {  // SignalSpectrum::unprocessed on the raw frame, receiver.cpp:826
         ut_spec_.advance(-1, 0, n / nf, nf, (uint64_t)fs, nullptr);  // (every frame restarts the timer a later set_spectrum_updates goes on from)
         // (a call whose chain follows on the same stream, or that has none, leaves the GPU to the transform: its all-registers variant)
-        if (int rc = spec_.run(stream_, d_iq, in_pitch, (long long)(n / nf), d_spec, raw, fuse_dec ? &df : nullptr, !side)) return rc;
+        if (int rc = spec_.run(stream_, c.d_iq, c.in_pitch, (long long)(n / nf), d_spec, c.raw, c.rt.fuse_dec ? &c.df : nullptr, !c.rt.side)) return rc;
         last_spec_frames = n / nf;
         if (smeter_on) {
             const long long F = (long long)(n / nf);
             if (int rc = run_signal_strength(stream_, d_spec, F * (long long)bins, (int)bins, F, d_sm_bins, d_smeter, smeter_pitch, C)) return rc;
         }
     }
-    if (with_spectrum) disp_spec_rows = last_spec_frames;
-    // (every record is a ~5 us bubble in the stream: a call with no display transform does without the one behind it)
+    if (c.with_spectrum) c.disp_spec_rows = last_spec_frames;
+    return 0;
+}
+
+// the raw-IQ tap, the record block and the record behind the display transform
+int Receiver::tap_and_record_input(Call &c)
+{
+    const uint64_t n = c.n;
     if (taps_ >> PEBBLEGPU_TAP_RAW_IQ & 1u) {  // (behind the display transform on its stream: the chain's start does not wait for the copy)
-        if (raw) { if (int rc = run_normalize_iq(raw->fmt, raw->order, 1.0, raw->base, (long long)(S * n), d_tap_[PEBBLEGPU_TAP_RAW_IQ], stream_, false, &raw->scale)) return rc; }
-        else PG_HIP(hipMemcpyAsync(d_tap_[PEBBLEGPU_TAP_RAW_IQ], tap_iq, sizeof(float2) * (size_t)S * n, hipMemcpyDeviceToDevice, stream_));
+        if (c.raw) { if (int rc = run_normalize_iq(c.raw->fmt, c.raw->order, 1.0, c.raw->base, (long long)(S * n), d_tap_[PEBBLEGPU_TAP_RAW_IQ], stream_, false, &c.raw->scale)) return rc; }
+        else PG_HIP(hipMemcpyAsync(d_tap_[PEBBLEGPU_TAP_RAW_IQ], c.tap_iq, sizeof(float2) * (size_t)S * n, hipMemcpyDeviceToDevice, stream_));
         tap_n_[PEBBLEGPU_TAP_RAW_IQ] = n;
     }
     // WavFile::WriteSamples(nextStep, numSamples), receiver.cpp:800-801: the same samples, at the same place in the queue
-    if (rec_.open && with_chain) { if (int rc = queue_record_block(stream_, tap_iq, rec_from_raw ? &rec_raw : nullptr, n)) return rc; }
-    const bool mid = with_spectrum || profile_detail || side;
-    if (mid) PG_HIP(hipEventRecord(ev[1], stream_));
+    if (rec_.open && c.with_chain) { if (int rc = queue_record_block(stream_, c.tap_iq, c.rec_from_raw ? &c.rec_raw : nullptr, n)) return rc; }
+    if (c.rt.mid) PG_HIP(hipEventRecord(c.ev[1], stream_));
     tm.detailed[(tm.calls - 1) % Timers::kRing] = profile_detail;
-    tm.has_mid[(tm.calls - 1) % Timers::kRing] = mid;
-    if (!with_chain) {
-        if (profile_detail) for (int i = 2; i <= 5; i++) PG_HIP(hipEventRecord(ev[i], stream_));
-        PG_HIP(hipEventRecord(ev[6], stream_));
-        guard.armed = false;
-        return 0;
-    }
-    // Mixer::processBlock + Decimator::process, receiver.cpp:867-868 / :910-911
-    dec_.want_lds_free = side;
+    tm.has_mid[(tm.calls - 1) % Timers::kRing] = c.rt.mid;
+    return 0;
+}
+
+// the end of a call that has no chain
+int Receiver::end_without_chain(Call &c)
+{
+    if (profile_detail) for (int i = 2; i <= 5; i++) PG_HIP(hipEventRecord(c.ev[i], stream_));
+    PG_HIP(hipEventRecord(c.ev[6], stream_));
+    return 0;
+}
+
+// Mixer::processBlock + Decimator::process, receiver.cpp:867-868 / :910-911, and for two-stage calls the hand-over to the chain's stream
+int Receiver::run_decimator(Call &c)
+{
+    const CallRoute &rt = c.rt;
+    const uint64_t n = c.n;
     // an event record costs the stream a ~5 us bubble: per-kernel events only when asked for (set_profiling)
-    OscAdvance oa_pre;
-    memset(&oa_pre, 0, sizeof(oa_pre));
-    bool have_oa = false;
-    if (fuse_dec) {
-        if (int rc = dec_.run_beside_spectrum(cs, d_iq, in_pitch, shared_input, (long long)n, osc_, raw)) return rc;
-        PG_HIP(hipStreamWaitEvent(cs, ev[1], 0));  // everything behind the decimator reads what the transform's kernel wrote
+    memset(&c.oa_pre, 0, sizeof(c.oa_pre));
+    c.have_oa = false;
+    DecimDone done;
+    if (rt.fuse_dec) {
+        if (int rc = dec_.run_beside_spectrum(c.cs, c.d_iq, c.in_pitch, shared_input, (long long)n, osc_, c.raw)) return rc;
+        PG_HIP(hipStreamWaitEvent(c.cs, c.ev[1], 0));  // everything behind the decimator reads what the transform's kernel wrote
     } else {
-        // (the oscillators' advance is offered to the decimator: the bank kernel carries it in its own launch, DecimCore::osc_advanced)
+        // (the oscillators' advance is offered to the decimator: the bank kernel carries it in its own launch, DecimDone::osc_advanced)
         if (!wfm) {
-            if (int rc = osc_.advance_job(cs, n, &oa_pre)) return rc;
-            have_oa = true;
+            if (int rc = osc_.advance_job(c.cs, n, &c.oa_pre)) return rc;
+            c.have_oa = true;
         }
+        DecimCall dc;
+        dc.lds_free = rt.side;
+        dc.rotate3 = rt.rot3;
         // (PEBBLEGPU_BANK_PIPE_EXTEV=1, opt-in: measured 0.0695 / 0.0753 ms (configs[2] / configs[3] shard) against 0.0663 / 0.0774 without)
-        dec_.done_event = nullptr;
-        if (bank_pipe && tun_.bank_pipe_extev) {  // the hand-over event of a two-stage call: completed by the bank kernel's own dispatch when that ends the first stage
-            if (!sync_ev_[0]) for (hipEvent_t &e : sync_ev_) PG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            dec_.done_event = sync_ev_[tm.calls % 4];
-        }
-        if (int rc = dec_.run(cs, d_iq, in_pitch, shared_input, (long long)n, osc_, profile_detail ? ev[2] : nullptr, raw, have_oa ? &oa_pre : nullptr)) return rc;
-        dec_.done_event = nullptr;
-        if (have_oa && dec_.osc_advanced) memset(&oa_pre, 0, sizeof(oa_pre));
+        // the hand-over event of a two-stage call: completed by the bank kernel's own dispatch when that ends the first stage
+        if (rt.done_in_kernel) { if (int rc = handover_event(&dc.done_event)) return rc; }
+        if (int rc = dec_.run(c.cs, c.d_iq, c.in_pitch, shared_input, (long long)n, osc_, profile_detail ? c.ev[2] : nullptr, c.raw, c.have_oa ? &c.oa_pre : nullptr, dc, &done)) return rc;
+        if (c.have_oa && done.osc_advanced) memset(&c.oa_pre, 0, sizeof(c.oa_pre));
     }
-    if (profile_detail) PG_HIP(hipEventRecord(ev[3], cs));
-    if (bank_pipe) {
+    if (profile_detail) PG_HIP(hipEventRecord(c.ev[3], c.cs));
+    if (rt.bank_pipe) {
         // the decimator's own histories and the oscillators' phases stay on its stream; the rest of the call moves over
         std::vector<TailJob> jobs;
         dec_.tail_jobs_dec(jobs);
-        const bool nothing_behind = jobs.empty() && oa_pre.osc == nullptr;
-        if (int rc = run_save_tails(stream_, jobs, C, &oa_pre)) return rc;  // (no launch at all behind the bank kernel: nothing left to do)
+        const bool nothing_behind = jobs.empty() && c.oa_pre.osc == nullptr;
+        if (int rc = run_save_tails(stream_, jobs, C, &c.oa_pre)) return rc;  // (no launch at all behind the bank kernel: nothing left to do)
         // (an event without timing for the hand-over: PEBBLEGPU_BANK_PIPE_TIMED_EV=1 records the call's timing event instead -- A/B)
-        const bool timed_ev = tun_.bank_pipe_timed_ev;
-        if (!sync_ev_[0]) for (hipEvent_t &e : sync_ev_) PG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        pipe_ev_ = timed_ev ? ev[1] : sync_ev_[tm.calls % 4];
-        if (!(dec_.done_recorded && nothing_behind && !timed_ev)) PG_HIP(hipEventRecord(pipe_ev_, stream_));
-        cs = chain_stream_;
-        PG_HIP(hipStreamWaitEvent(cs, pipe_ev_, 0));
+        hipEvent_t sync_ev = nullptr;
+        if (int rc = handover_event(&sync_ev)) return rc;
+        pipe_ev_ = rt.timed_handover ? c.ev[1] : sync_ev;
+        if (!(done.done_recorded && nothing_behind && !rt.timed_handover)) PG_HIP(hipEventRecord(pipe_ev_, stream_));
+        c.cs = chain_stream_;
+        PG_HIP(hipStreamWaitEvent(c.cs, pipe_ev_, 0));
         // (with two output buffers the next call's decimator becomes ready with the same event as this band-pass: a short nap lets its
         // one-wave-per-SIMD workgroups be placed before the band-pass fills the CUs -- placed behind them it ran 112 us instead of 65.
         // With three the next decimator is already running when this point is reached: no nap)
         const int nap = tun_.bank_pipe_nap;
-        if (int rc = run_nap(cs, nap >= 0 ? (unsigned)nap : (rot3 ? 0u : 800u))) return rc;
+        if (int rc = run_nap(c.cs, nap >= 0 ? (unsigned)nap : (rt.rot3 ? 0u : 800u))) return rc;
     }
-    const long long nd = dec_.out_len();
-    if (int rc = copy_tap(cs, PEBBLEGPU_TAP_POST_MIXER, dec_.out().data(), dec_.out().pitch, nd, C)) return rc;  // receiver.cpp:945 (WFM: m_sampleBuf, :884)
-    if (zoom_bins) {  // SignalSpectrum::zoomed(m_sampleBuf, numStepSamples), receiver.cpp:884 / :942 (its update timer: open by default)
-        if (gated()) {  // m_hiResTimer: the same period, counted in decimated frames at the demodulator rate (signalspectrum.cpp:94-100)
-            sel_zoom_.clear();
-            ut_zoom_.advance(spec_ups_, spec_period_ms_, (uint64_t)(nd / nf), nf, demod_rate_int, &sel_zoom_);
-            if (int rc = zoom_.run_list(cs, dec_.out().data(), dec_.out().pitch, sel_zoom_.data(), (long long)sel_zoom_.size(), d_zoom)) return rc;
-            last_zoom_frames = (uint64_t)sel_zoom_.size();
-        } else {
-            ut_zoom_.advance(-1, 0, (uint64_t)(nd / nf), nf, demod_rate_int, nullptr);
-            if (int rc = zoom_.run(cs, dec_.out().data(), dec_.out().pitch, nd / nf, d_zoom)) return rc;
-            last_zoom_frames = (uint64_t)(nd / nf);
-        }
-        zoom_stream_ = cs;
-        disp_zoom_rows = last_zoom_frames;
+    c.nd = dec_.out_len();
+    return copy_tap(c.cs, PEBBLEGPU_TAP_POST_MIXER, dec_.out().data(), dec_.out().pitch, c.nd, C);  // receiver.cpp:945 (WFM: m_sampleBuf, :884)
+}
+
+// SignalSpectrum::zoomed(m_sampleBuf, numStepSamples), receiver.cpp:884 / :942 (its update timer: open by default)
+int Receiver::run_zoomed_transform(Call &c)
+{
+    if (!zoom_bins) return 0;
+    const long long nd = c.nd;
+    if (gated()) {  // m_hiResTimer: the same period, counted in decimated frames at the demodulator rate (signalspectrum.cpp:94-100)
+        sel_zoom_.clear();
+        ut_zoom_.advance(spec_ups_, spec_period_ms_, (uint64_t)(nd / nf), nf, demod_rate_int, &sel_zoom_);
+        if (int rc = zoom_.run_list(c.cs, dec_.out().data(), dec_.out().pitch, sel_zoom_.data(), (long long)sel_zoom_.size(), d_zoom)) return rc;
+        last_zoom_frames = (uint64_t)sel_zoom_.size();
+    } else {
+        ut_zoom_.advance(-1, 0, (uint64_t)(nd / nf), nf, demod_rate_int, nullptr);
+        if (int rc = zoom_.run(c.cs, dec_.out().data(), dec_.out().pitch, nd / nf, d_zoom)) return rc;
+        last_zoom_frames = (uint64_t)(nd / nf);
     }
+    zoom_stream_ = c.cs;
+    c.disp_zoom_rows = last_zoom_frames;
+    return 0;
+}
+
+// the band-pass, and whether the call ends behind it (c.gate_closed): the squelch gate's read-back, or tune-only mode
+int Receiver::bandpass_and_gate(Call &c)
+{
+    hipStream_t cs = c.cs;
     if (!wfm) {
-        if (int rc = ff_.run(cs, dec_.out(), nd, audio.data(), audio.pitch)) return rc;  // receiver.cpp:950
-        if (profile_detail) PG_HIP(hipEventRecord(ev[4], cs));
-        if (int rc = copy_tap(cs, PEBBLEGPU_TAP_POST_BP, audio.data(), audio.pitch, nd, C)) return rc;  // receiver.cpp:953
+        if (int rc = ff_.run(cs, dec_.out(), c.nd, audio.data(), audio.pitch)) return rc;  // receiver.cpp:950
+        if (profile_detail) PG_HIP(hipEventRecord(c.ev[4], cs));
+        if (int rc = copy_tap(cs, PEBBLEGPU_TAP_POST_BP, audio.data(), audio.pitch, c.nd, C)) return rc;  // receiver.cpp:953
     }
     // Squelch, receiver.cpp:893-897 / :962-965: below the threshold the reference returns here -- nothing behind the gate
     // runs or changes state, and no audio leaves the call.
-    bool gate_closed = false, tails_carried = false;
-    if (squelch_db_ > -120.0 && gated()) {
-        // the latest computed spectrum: a row of this call, else the carried one (m_unprocessedSpectrum between two updates).  Before the
-        // first spectrum the reference compares against an uninitialised buffer (signalspectrum.cpp:13): the gate stays open
+    bool gate_closed = false;
+    if (squelch_db_ > -120.0) {
         const float4 *src = nullptr;
-        if (with_spectrum && last_spec_frames) src = d_smeter + (last_spec_frames - 1);
+        if (!gated()) src = d_smeter + (last_spec_frames - 1);  // (refuse_call: a call without a spectrum of its own follows one that had one)
+        // under the update timer the latest computed spectrum: a row of this call, else the carried one (m_unprocessedSpectrum between two
+        // updates).  Before the first spectrum the reference compares against an uninitialised buffer (signalspectrum.cpp:13): the gate stays open
+        else if (c.with_spectrum && last_spec_frames) src = d_smeter + (last_spec_frames - 1);
         else if (have_carry_) {
-            if (!with_spectrum) { if (int rc = measure_carry(cs)) return rc; }
+            if (!c.with_spectrum) { if (int rc = measure_carry(cs)) return rc; }
             src = d_sm_carry;
         }
-        if (src) {
-            PG_HIP(hipMemcpyAsync(h_gate_, src, sizeof(float4), hipMemcpyDeviceToHost, cs));
-            PG_HIP(hipStreamSynchronize(cs));
-            gate_closed = (double)h_gate_->y < squelch_db_;  // m_avgDb < m_squelchDb
-        }
-    } else if (squelch_db_ > -120.0) {
-        if (!last_spec_frames) return fail(PEBBLEGPU_E_INVALID, "the squelch gate needs a spectrum: none has been computed yet");
-        PG_HIP(hipMemcpyAsync(h_gate_, d_smeter + (last_spec_frames - 1), sizeof(float4), hipMemcpyDeviceToHost, cs));
-        PG_HIP(hipStreamSynchronize(cs));
-        gate_closed = (double)h_gate_->y < squelch_db_;  // m_avgDb < m_squelchDb
+        if (src) { if (int rc = read_gate(cs, src, &gate_closed)) return rc; }
     }
+    if (gate_closed) squelched_calls++;
     // dmNONE, "Tune only mode, no demod or output" (receiver.cpp:968-971): for the reference's own shape (one channel) the call
     // ends here like a closed gate -- nothing behind the band-pass runs or changes state, no audio leaves; in a bank the
     // tune-only channels sit out the noise filter, AGC and demodulators (muted lists) and their audio rows are cleared
-    bool tune_only = false;
-    if (!wfm && !gate_closed) {
-        if (C == 1) tune_only = ctl_[0].mode == PEBBLEGPU_DM_NONE;
+    c.gate_closed = gate_closed || c.rt.tune_only;
+    return 0;
+}
+
+// a closed gate, or tune-only mode: nothing behind the band-pass runs
+int Receiver::tail_closed(Call &c)
+{
+    last_audio_n = 0;
+    if (profile_detail) { if (wfm) PG_HIP(hipEventRecord(c.ev[4], c.cs)); }
+    for (int pt : {PEBBLEGPU_TAP_MODEM, PEBBLEGPU_TAP_POST_DEMOD}) {  // "Tune only mode" returns before both points: their rows read zero
+        if (!(taps_ >> pt & 1u)) continue;
+        PG_HIP(hipMemsetAsync(d_tap_[pt], 0, sizeof(float2) * (size_t)c.nd * C, c.cs));
+        tap_n_[pt] = (uint64_t)c.nd;
     }
-    if (gate_closed || tune_only) {
-        if (gate_closed) squelched_calls++;
-        last_audio_n = 0;
-        gate_closed = true;
-        if (profile_detail) { if (wfm) PG_HIP(hipEventRecord(ev[4], cs)); }
-        for (int pt : {PEBBLEGPU_TAP_MODEM, PEBBLEGPU_TAP_POST_DEMOD}) {  // "Tune only mode" returns before both points: their rows read zero
-            if (!(taps_ >> pt & 1u)) continue;
-            PG_HIP(hipMemsetAsync(d_tap_[pt], 0, sizeof(float2) * (size_t)nd * C, cs));
-            tap_n_[pt] = (uint64_t)nd;
-        }
-    } else if (!wfm && bank_gate_) {
-        // Per-channel squelch of a bank: the decision is made on the device from the S-meter of each super-frame's last raw frame
-        // (no read-back, no stream synchronisation); everything behind the band-pass then runs one super-frame at a time and
-        // leaves a closed channel alone -- no output, no state change: the reference's early return (receiver.cpp:962-965) per
-        // channel.  A closed (channel, super-frame) reads as silence in the bank's audio rows.
-        if (!with_spectrum) return fail(PEBBLEGPU_E_INVALID, "the squelch gate of a bank reads the spectra of the same call: create the bank with spectrum_bins");
-        const int k = (int)(n / superframe);
-        const long long spf = nd / k;
-        if (gated()) {
-            // per super-frame the latest computed spectrum at or before its last raw frame: a compact row of this call, the carried row, or none yet
-            const uint64_t fps = superframe / nf;
-            std::vector<int> rows((size_t)k);
-            size_t r = 0;
-            for (int j = 0; j < k; j++) {
-                while (r < sel_spec_.size() && (uint64_t)sel_spec_[r] <= (uint64_t)(j + 1) * fps - 1) r++;
-                rows[(size_t)j] = r ? (int)r - 1 : (carry_before ? kGateRowCarried : kGateRowNone);
-            }
-            if (int rc = run_gate_eval_rows(cs, d_smeter, smeter_pitch, d_sm_carry, rows.data(), k, d_squelch, d_gate, (int)max_sf, C)) return rc;
-        } else if (int rc = run_gate_eval(cs, d_smeter, smeter_pitch, (int)(superframe / nf), k, d_squelch, d_gate, (int)max_sf, C)) return rc;
+    return 0;
+}
+
+// Per-channel squelch of a bank: the decision is made on the device from the S-meter of each super-frame's last raw frame
+// (no read-back, no stream synchronisation); everything behind the band-pass then runs one super-frame at a time and
+// leaves a closed channel alone -- no output, no state change: the reference's early return (receiver.cpp:962-965) per
+// channel.  A closed (channel, super-frame) reads as silence in the bank's audio rows.
+int Receiver::tail_bank_gated(Call &c)
+{
+    hipStream_t cs = c.cs;
+    const long long nd = c.nd;
+    if (!c.with_spectrum) return fail(PEBBLEGPU_E_INVALID, "the squelch gate of a bank reads the spectra of the same call: create the bank with spectrum_bins");
+    const int k = (int)(c.n / superframe);
+    const long long spf = nd / k;
+    if (gated()) {
+        // per super-frame the latest computed spectrum at or before its last raw frame: a compact row of this call, the carried row, or none yet
+        const uint64_t fps = superframe / nf;
+        std::vector<int> rows((size_t)k);
+        size_t r = 0;
         for (int j = 0; j < k; j++) {
-            const Gate gate{d_gate, (int)max_sf, j};
-            float2 *seg = audio.data() + (long long)j * spf;
-            if (int rc = anf_.run(cs, seg, audio.pitch, spf, gate)) return rc;
-            if (int rc = agc_.run(cs, seg, audio.pitch, spf, gate)) return rc;
-            am_.defer_tail = false;
-            if (int rc = am_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate)) return rc;
-            if (sam_.C) { if (int rc = sam_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate)) return rc; }
-            if (nfm_.C) { if (int rc = nfm_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate)) return rc; }
+            while (r < sel_spec_.size() && (uint64_t)sel_spec_[r] <= (uint64_t)(j + 1) * fps - 1) r++;
+            rows[(size_t)j] = r ? (int)r - 1 : (c.carry_before ? kGateRowCarried : kGateRowNone);
         }
-        if (int rc = run_gate_zero(cs, audio.data(), audio.pitch, spf, d_gate, (int)max_sf, C, k)) return rc;
-        for (uint32_t ch = 0; ch < C; ch++)
-            if (ctl_[ch].mode == PEBBLEGPU_DM_NONE) PG_HIP(hipMemsetAsync(audio.data((int)ch), 0, sizeof(float2) * (size_t)nd, cs));
-    } else if (!wfm) {
-        if (int rc = anf_.run(cs, audio.data(), audio.pitch, nd)) return rc;  // NoiseFilter::ProcessBlock, receiver.cpp:974
-        if (taps_ >> PEBBLEGPU_TAP_MODEM & 1u) {  // the frame m_iDigitalModem->processBlock receives (a dmNONE channel's call has returned before, :968-971)
-            if (int rc = copy_tap(cs, PEBBLEGPU_TAP_MODEM, audio.data(), audio.pitch, nd, C)) return rc;
-            for (uint32_t ch = 0; ch < C; ch++)
-                if (ctl_[ch].mode == PEBBLEGPU_DM_NONE) PG_HIP(hipMemsetAsync(d_tap_[PEBBLEGPU_TAP_MODEM] + (size_t)ch * nd, 0, sizeof(float2) * (size_t)nd, cs));
-        }
-        // m_iDigitalModem->processBlock, receiver.cpp:979-980: the Morse modem reads the rows before the AGC overwrites them
-        if (morse_.any()) { if (int rc = morse_.run(cs, audio.data(), audio.pitch, nd)) return rc; }
-        if (int rc = agc_.run(cs, audio.data(), audio.pitch, nd)) return rc;  // AGC::processBlock, receiver.cpp:983
-        // Demod::processBlock, receiver.cpp:987: AM channels are demodulated in place; every other narrow mode returns its input
-        am_.defer_tail = bank_pipe;  // (a two-stage call's tail launch carries the AM demodulator's history refresh: one launch fewer)
-        if (int rc = am_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd)) return rc;
-        if (sam_.C) { if (int rc = sam_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd)) return rc; }
-        if (nfm_.C) { if (int rc = nfm_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd)) return rc; }
-        for (uint32_t ch = 0; ch < C; ch++)  // clearCPX(m_audioBuf, ...) of the bank's tune-only channels
-            if (ctl_[ch].mode == PEBBLEGPU_DM_NONE) PG_HIP(hipMemsetAsync(audio.data((int)ch), 0, sizeof(float2) * (size_t)nd, cs));
-        if (int rc = copy_tap(cs, PEBBLEGPU_TAP_POST_DEMOD, audio.data(), audio.pitch, nd, C)) return rc;  // receiver.cpp:992, before the resampler
-    } else {
-        if (profile_detail) PG_HIP(hipEventRecord(ev[4], cs));
-        // (the call's tail refresh rides on the demodulator's launch: it is the last kernel of the call, run on an idle GPU)
-        std::vector<TailJob> jobs;
-        dec_.tail_jobs(jobs);
-        OscAdvance oa;
-        if (int rc = osc_.advance_job(cs, n, &oa)) return rc;
-        if (int rc = wfmc_.run(cs, dec_.out().data(), dec_.out().pitch, audio.data(), audio.pitch, nd, &jobs, &oa, &tails_carried)) return rc;  // receiver.cpp:896
+        if (int rc = run_gate_eval_rows(cs, d_smeter, smeter_pitch, d_sm_carry, rows.data(), k, d_squelch, d_gate, (int)max_sf, C)) return rc;
+    } else if (int rc = run_gate_eval(cs, d_smeter, smeter_pitch, (int)(superframe / nf), k, d_squelch, d_gate, (int)max_sf, C)) return rc;
+    for (int j = 0; j < k; j++) {
+        const Gate gate{d_gate, (int)max_sf, j};
+        float2 *seg = audio.data() + (long long)j * spf;
+        if (int rc = anf_.run(cs, seg, audio.pitch, spf, gate)) return rc;
+        if (int rc = agc_.run(cs, seg, audio.pitch, spf, gate)) return rc;
+        if (int rc = am_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate, false)) return rc;
+        if (sam_.C) { if (int rc = sam_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate)) return rc; }
+        if (nfm_.C) { if (int rc = nfm_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate)) return rc; }
     }
-    if (!gate_closed) {
-        last_audio_n = (uint64_t)nd;
+    if (int rc = run_gate_zero(cs, audio.data(), audio.pitch, spf, d_gate, (int)max_sf, C, k)) return rc;
+    return clear_tune_only_rows(cs, audio.data(), audio.pitch, nd);
+}
+
+// noise filter, modem hook, AGC and demodulators of the narrow branch (receiver.cpp:974-992)
+int Receiver::tail_narrow(Call &c)
+{
+    hipStream_t cs = c.cs;
+    const long long nd = c.nd;
+    if (int rc = anf_.run(cs, audio.data(), audio.pitch, nd)) return rc;  // NoiseFilter::ProcessBlock, receiver.cpp:974
+    if (taps_ >> PEBBLEGPU_TAP_MODEM & 1u) {  // the frame m_iDigitalModem->processBlock receives (a dmNONE channel's call has returned before, :968-971)
+        if (int rc = copy_tap(cs, PEBBLEGPU_TAP_MODEM, audio.data(), audio.pitch, nd, C)) return rc;
+        if (int rc = clear_tune_only_rows(cs, d_tap_[PEBBLEGPU_TAP_MODEM], nd, nd)) return rc;
+    }
+    // m_iDigitalModem->processBlock, receiver.cpp:979-980: the Morse modem reads the rows before the AGC overwrites them
+    if (morse_.any()) { if (int rc = morse_.run(cs, audio.data(), audio.pitch, nd)) return rc; }
+    if (int rc = agc_.run(cs, audio.data(), audio.pitch, nd)) return rc;  // AGC::processBlock, receiver.cpp:983
+    // Demod::processBlock, receiver.cpp:987: AM channels are demodulated in place; every other narrow mode returns its input
+    // (a two-stage call's tail launch carries the AM demodulator's history refresh: one launch fewer)
+    if (int rc = am_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd, Gate{nullptr, 0, 0}, c.rt.bank_pipe)) return rc;
+    if (sam_.C) { if (int rc = sam_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd)) return rc; }
+    if (nfm_.C) { if (int rc = nfm_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd)) return rc; }
+    if (int rc = clear_tune_only_rows(cs, audio.data(), audio.pitch, nd)) return rc;
+    return copy_tap(cs, PEBBLEGPU_TAP_POST_DEMOD, audio.data(), audio.pitch, nd, C);  // receiver.cpp:992, before the resampler
+}
+
+// Demod_WFM, receiver.cpp:896
+int Receiver::tail_wfm(Call &c)
+{
+    if (profile_detail) PG_HIP(hipEventRecord(c.ev[4], c.cs));
+    // (the call's tail refresh rides on the demodulator's launch: it is the last kernel of the call, run on an idle GPU)
+    std::vector<TailJob> jobs;
+    dec_.tail_jobs(jobs);
+    OscAdvance oa;
+    if (int rc = osc_.advance_job(c.cs, c.n, &oa)) return rc;
+    return wfmc_.run(c.cs, dec_.out().data(), dec_.out().pitch, audio.data(), audio.pitch, c.nd, &jobs, &oa, &c.tails_carried);
+}
+
+// resampler, the audio ring's block, and the refresh of every history head-room for the next call
+int Receiver::finish_chain(Call &c)
+{
+    hipStream_t cs = c.cs;
+    if (!c.gate_closed) {
+        last_audio_n = (uint64_t)c.nd;
         if (audio_rate) {  // CFractResampler::Resample into the audio buffer, receiver.cpp:1000-1001
             long long n_rs = 0;
-            if (int rc = resamp_.run(cs, audio.data(), audio.pitch, nd, d_audio_rs, rs_pitch, &n_rs)) return rc;
+            if (int rc = resamp_.run(cs, audio.data(), audio.pitch, c.nd, d_audio_rs, rs_pitch, &n_rs)) return rc;
             last_audio_n = (uint64_t)n_rs;
         }
     }
     // Audio::SendToOutput, receiver.cpp:1029-1035: behind the last writer of the audio buffer on whichever stream that was (the
     // resampler, the demodulators, the gate's clears); the next call's writers follow on the same stream or behind its end
     if (aout_.open) { if (int rc = queue_audio_block(cs, last_audio_n)) return rc; }
-    if (profile_detail) PG_HIP(hipEventRecord(ev[5], cs));
-    if (bank_pipe) {
+    if (profile_detail) PG_HIP(hipEventRecord(c.ev[5], cs));
+    if (c.rt.bank_pipe) {
         std::vector<TailJob> jobs;
         dec_.tail_job_out(jobs);
         am_.tail_jobs(jobs);
         if (int rc = run_save_tails(cs, jobs, C, nullptr)) return rc;
-    } else if (!tails_carried) {  // one launch refreshes every history head-room for the next call
+    } else if (!c.tails_carried) {  // one launch refreshes every history head-room for the next call
         std::vector<TailJob> jobs;
         dec_.tail_jobs(jobs);
-        if (wfm && !gate_closed) wfmc_.tail_jobs(jobs);  // a gated super-frame never reached the demodulator: its history stays
-        OscAdvance oa = oa_pre;
-        if (!have_oa) { if (int rc = osc_.advance_job(cs, n, &oa)) return rc; }
+        if (wfm && !c.gate_closed) wfmc_.tail_jobs(jobs);  // a gated super-frame never reached the demodulator: its history stays
+        OscAdvance oa = c.oa_pre;
+        if (!c.have_oa) { if (int rc = osc_.advance_job(cs, c.n, &oa)) return rc; }
         if (int rc = run_save_tails(cs, jobs, C, &oa)) return rc;
     }
+    return 0;
+}
+
+// the display ring's block and the call's end
+int Receiver::end_call(Call &c)
+{
+    const CallRoute &rt = c.rt;
+    hipStream_t cs = c.cs;
+    hipEvent_t *ev = c.ev;
     // The display ring's block, where Receiver::map_spectrum would queue a map of each source: the zoomed spectra on the stream that wrote
     // them, the unprocessed spectrum on the main stream -- one stream, and one launch for both panes, unless the call's two pipelines end
     // separately (PEBBLEGPU_PIPELINE=1).  A call that joins its streams does so first.  Ahead of the call's end record, so that whoever
@@ -934,15 +1022,15 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     bool joined = false;
     if (disp_open_) {
         hipStream_t spec_s = stream_;
-        if (side && !tun_.pipeline) {
-            if (!fuse_dec) PG_HIP(hipStreamWaitEvent(cs, ev[1], 0));
+        if (rt.side && !tun_.pipeline) {
+            if (!rt.fuse_dec) PG_HIP(hipStreamWaitEvent(cs, ev[1], 0));
             joined = true;
             spec_s = cs;
         }
-        if (int rc = queue_display_block(spec_s, disp_spec_rows, cs, disp_zoom_rows)) return rc;
+        if (int rc = queue_display_block(spec_s, c.disp_spec_rows, cs, c.disp_zoom_rows)) return rc;
     }
-    if (!bank_pipe) d_end_prev_ = nullptr;
-    if (bank_pipe) {
+    if (!rt.bank_pipe) d_end_prev_ = nullptr;
+    if (rt.bank_pipe) {
         PG_HIP(hipEventRecord(ev[6], cs));
         chain_end_ = ev[6];   // for whoever needs both stages over: sync(), a call after a setter, a call of another shape
         spec_end_ = pipe_ev_;
@@ -955,23 +1043,72 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
             if (!found) out_reader_.push_back({(const void *)dec_.fin.base, ev[6]});
         }
         d_end_prev_ = ev[6];
-    } else if (side && tun_.pipeline) {
+    } else if (rt.side && tun_.pipeline) {
         // the call's two pipelines end separately: whoever needs both waits for both (sync(), the next call that is not plain)
         PG_HIP(hipEventRecord(ev[6], cs));
         chain_end_ = ev[6];
         spec_end_ = ev[1];
-    } else if (side) {
+    } else if (rt.side) {
         // join: the call has ended once both pipelines have, and it ends on the chain's stream.  That stream is the main stream
         // of the next call (the two swap roles): its first kernel then follows this call's last in queue order, where a wait
         // on an event from the other queue cost ~25 us of idle GPU per call
-        if (!fuse_dec && !joined) PG_HIP(hipStreamWaitEvent(cs, ev[1], 0));
+        if (!rt.fuse_dec && !joined) PG_HIP(hipStreamWaitEvent(cs, ev[1], 0));
         if (tun_.end_records) PG_HIP(hipEventRecord(ev[6], cs));
-        else tm.open_slot = slot;  // (closed by the next call's start record, by sync() or by a timing query)
+        else tm.open_slot = c.slot;  // (closed by the next call's start record, by sync() or by a timing query)
         std::swap(stream_, chain_stream_);
     } else {
         PG_HIP(hipEventRecord(ev[6], stream_));
     }
-    osc_.advance(n);
+    osc_.advance(c.n);
+    return 0;
+}
+
+int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    PG_HIP(hipSetDevice(device));
+    if (int rc = refuse_call(d_iq, n, with_spectrum, with_chain, raw)) return rc;
+    Call c;
+    c.rt = plan_call_route(call_facts(n, with_spectrum, with_chain, raw != nullptr));
+    c.n = n;
+    c.with_spectrum = with_spectrum;
+    c.with_chain = with_chain;
+    c.d_iq = d_iq;
+    c.raw = raw;
+    // recording (egress.h): with the generator off a raw call is recorded from the raw samples themselves, whichever way the chain takes
+    // them in (the same loader and scale as the conversion pass: the same values, and the recording needs no float2 copy of its own)
+    c.rec_raw = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
+    c.rec_from_raw = raw != nullptr && !tb_.any();
+    if (int rc = join_and_apply(c)) return rc;
+    if (int rc = stage_input(c)) return rc;
+    if (int rc = start_call(c)) return rc;
+    // From here on a failing step leaves kernels queued (on the chain stream too) and histories half advanced: whatever the
+    // exit, join the two streams so later work is ordered behind what was queued, and refuse further calls on the handle.
+    struct Guard {
+        Receiver *r; hipEvent_t *ev; hipStream_t cs; bool side, armed;
+        ~Guard()
+        {
+            if (!armed) return;
+            r->failed_ = true;
+            if (side && hipEventRecord(ev[6], cs) == hipSuccess) r->chain_end_ = ev[6];
+        }
+    } guard{this, c.ev, c.rt.bank_pipe ? chain_stream_ : c.cs, c.rt.side || c.rt.bank_pipe, true};
+    if (int rc = run_display_transform(c)) return rc;
+    if (int rc = tap_and_record_input(c)) return rc;
+    if (!with_chain) {
+        if (int rc = end_without_chain(c)) return rc;
+        guard.armed = false;
+        return 0;
+    }
+    if (int rc = run_decimator(c)) return rc;
+    if (int rc = run_zoomed_transform(c)) return rc;
+    if (int rc = bandpass_and_gate(c)) return rc;
+    if (c.gate_closed) { if (int rc = tail_closed(c)) return rc; }
+    else if (c.rt.tail == CallTail::BankGated) { if (int rc = tail_bank_gated(c)) return rc; }
+    else if (c.rt.tail == CallTail::Narrow) { if (int rc = tail_narrow(c)) return rc; }
+    else if (int rc = tail_wfm(c)) return rc;
+    if (int rc = finish_chain(c)) return rc;
+    if (int rc = end_call(c)) return rc;
     guard.armed = false;
     return 0;
 }
@@ -988,16 +1125,18 @@ int Receiver::process_raw(int fmt, int order, double gain, const void *d_raw, ui
 // ---- host ingest: the pinned double buffer (ingest.h) ----
 int Receiver::ingest_acquire(uint32_t slot, uint64_t bytes, void **host_ptr) { return ingest_.acquire(device, slot, bytes, host_ptr); }
 int Receiver::ingest_submit(uint32_t slot, uint64_t bytes) { return ingest_.submit(device, slot, bytes); }
-int Receiver::process_ingested(uint32_t slot, int fmt, int order, double gain, uint64_t n)
+// a raw call on a slot of `ring`, ordered behind the slot's upload on the device
+int Receiver::process_slot(IngestRing &ring, uint32_t slot, int fmt, int order, double gain, uint64_t n)
 {
     IngestSlot *g = nullptr;
-    if (int rc = ingest_.check(slot, fmt, (uint64_t)S * n, n, &g)) return rc;
+    if (int rc = ring.check(slot, fmt, (uint64_t)S * n, n, &g)) return rc;
     PG_HIP(hipSetDevice(device));
     // both of the call's streams read the raw samples (the display transform and the chain's first stage convert in their own loads)
-    if (int rc = ingest_.wait_upload(*g, stream_, chain_stream_)) return rc;
+    if (int rc = ring.wait_upload(*g, stream_, chain_stream_)) return rc;
     if (int rc = process_raw(fmt, order, gain, g->d, n)) return rc;
-    return ingest_.mark_in_flight(*g, stream_, chain_stream_);
+    return ring.mark_in_flight(*g, stream_, chain_stream_);
 }
+int Receiver::process_ingested(uint32_t slot, int fmt, int order, double gain, uint64_t n) { return process_slot(ingest_, slot, fmt, order, gain, n); }
 // the twins of an outside owner's pinned slots (the multibank): same order of steps on the second ring
 int Receiver::ingest_wait(uint32_t slot)
 {
@@ -1005,15 +1144,7 @@ int Receiver::ingest_wait(uint32_t slot)
     return ext_ingest_.wait_free(slot);
 }
 int Receiver::ingest_upload(uint32_t slot, const void *h_src, uint64_t bytes) { return ext_ingest_.submit_from(device, slot, h_src, bytes); }
-int Receiver::process_uploaded(uint32_t slot, int fmt, int order, double gain, uint64_t n)
-{
-    IngestSlot *g = nullptr;
-    if (int rc = ext_ingest_.check(slot, fmt, (uint64_t)S * n, n, &g)) return rc;
-    PG_HIP(hipSetDevice(device));
-    if (int rc = ext_ingest_.wait_upload(*g, stream_, chain_stream_)) return rc;
-    if (int rc = process_raw(fmt, order, gain, g->d, n)) return rc;
-    return ext_ingest_.mark_in_flight(*g, stream_, chain_stream_);
-}
+int Receiver::process_uploaded(uint32_t slot, int fmt, int order, double gain, uint64_t n) { return process_slot(ext_ingest_, slot, fmt, order, gain, n); }
 
 // "k_testbench + <front kernel>": one string per front-kernel name, kept for the life of the process like the literals the other groups
 // return (the set of names is small and fixed)
