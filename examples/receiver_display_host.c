@@ -6,6 +6,9 @@
  * threads talk through two counters on the host: the reader asks for block k once call k has been queued, and the producer stays at
  * most N_SLOTS calls ahead of the reader, so nothing is dropped (a host that would rather lose a line than wait leaves that out and
  * reads dropped_before).  Half-way the "user" changes the plot's dB range: pebblegpu_receiver_display_set_pane.
+ * With --auto both dB boxes are on "Auto" (the reference's default, SpectrumWidget::recalcScale): pebblegpu_receiver_display_set_auto_scale
+ * after the open -- a host flag, no wait -- the range of every block is printed from its trailer (pebblegpu_receiver_display_scale), and
+ * half-way the "user" moves the LO instead: pebblegpu_receiver_display_rescale, the next call's first spectrum gives the new range.
  * Exit status 0 on success; otherwise the failing call and pebblegpu_last_error() on stderr.
  * Build: gcc -O2 -Wall -pthread -Iinclude examples/receiver_display_host.c -Lpebblesdr_amd -lpebblegpu -Wl,-rpath,$PWD/pebblesdr_amd -lm */
 #include <math.h>
@@ -28,6 +31,7 @@ static int taken = 0;       /* calls whose blocks the reader has released */
 static int reader_rc = 0;
 static uint32_t audio_sum = 0, plot_sum = 0, line_sum = 0;
 static uint64_t audio_samples = 0, plots = 0, lines = 0;
+static int auto_scale = 0;  /* --auto */
 
 static int read_call(uint64_t call)
 {
@@ -57,6 +61,12 @@ static int read_call(uint64_t call)
         const uint32_t *line = (const uint32_t *)((const char *)d[1].host + j * d[1].row_pitch_bytes);
         for (uint32_t i = 0; i < d[1].row_elems; i++) line_sum = line_sum * 31u + line[i];
         lines++;
+    }
+    if (auto_scale) {                                             /* the range this block was mapped with (one channel: one entry) */
+        pebblegpu_display_scale sc;
+        uint32_t n_sc = 0;
+        CHECK(pebblegpu_receiver_display_scale(rx, call, &sc, 1, &n_sc));
+        printf("call %llu: %d .. %d dB%s\n", (unsigned long long)call, sc.min_db, sc.max_db, sc.peak_power > 0.0 ? " (recalculated)" : "");
     }
     CHECK(pebblegpu_receiver_display_release(rx, call));
     return 0;
@@ -94,8 +104,9 @@ static void plot_geometry(pebblegpu_screen_map *m, int32_t y, int32_t x, double 
     m->stop_freq = stop;
 }
 
-int main(void)
+int main(int argc, char **argv)
 {
+    auto_scale = argc > 1 && !strcmp(argv[1], "--auto");
     pebblegpu_config cfg;
     memset(&cfg, 0, sizeof cfg);
     cfg.struct_size = sizeof cfg;
@@ -125,6 +136,7 @@ int main(void)
     pane[1].max_rows = 1;
     plot_geometry(&pane[1].map, 255, BOTTOM_X, 0.0, -10000000, 10000000);
     CHECK(pebblegpu_receiver_display_open(rx, pane, 2, N_SLOTS));
+    if (auto_scale) CHECK(pebblegpu_receiver_display_set_auto_scale(rx, PEBBLEGPU_AUTO_SCALE_MAX | PEBBLEGPU_AUTO_SCALE_MIN));
 
     pthread_t th;
     if (pthread_create(&th, NULL, reader, NULL)) { fprintf(stderr, "pthread_create failed\n"); return 1; }
@@ -140,7 +152,9 @@ int main(void)
         rc = reader_rc;
         pthread_mutex_unlock(&mu);
         if (rc) break;
-        if (call == N_CALLS / 2) {                                /* the user drags the plot's top down to -20 dB: from this call on */
+        if (call == N_CALLS / 2 && auto_scale) {                  /* the user moves the LO: m_scaleNeedsRecalc (a host flag, no wait) */
+            CHECK(pebblegpu_receiver_display_rescale(rx));
+        } else if (call == N_CALLS / 2) {                         /* the user drags the plot's top down to -20 dB: from this call on */
             plot_geometry(&pane[0].map, 400, TOP_X, -20.0, 0, 0);
             CHECK(pebblegpu_receiver_display_set_pane(rx, 0, &pane[0]));
         }

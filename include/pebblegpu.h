@@ -1037,6 +1037,69 @@ int pebblegpu_receiver_display_dropped(const pebblegpu_receiver *rx, uint64_t *b
  * row wider than the slots were sized for at open is PEBBLEGPU_E_SIZE; the refusals of _open apply to the new geometry. */
 int pebblegpu_receiver_display_set_pane(pebblegpu_receiver *rx, uint32_t pane, const pebblegpu_display_pane *geometry);
 
+/* ------------------------------------------------------------------------------------------------
+ * Auto-scale: SpectrumWidget::recalcScale (application/spectrumwidget.cpp:693-734), the plot range the reference draws with by default
+ * (AutoScaleMax / AutoScaleMin are both true, application/settings.cpp:70-71), computed on the device so that a display ring's pixels
+ * and colours follow the signal without the host pulling dB rows.  The rule, for one unprocessed-spectrum row of `bins` float dB values
+ * (each widened to double):
+ *   pwr_i = pow(10, dB_i / 10.0) (DB::dBToPower);  total = sum pwr_i;  peak = max pwr_i (from 0);  avg = total / bins
+ *   min_db = qBound(-120, ((int)(powerTodB(avg)  - 10) / 5) * 5, -70)      powerTodB(0) = -120, else 10 log10; (int) truncates; C division
+ *   max_db = qBound( -50, ((int)(powerTodB(peak) + 10) / 5) * 5,   0)
+ * The host twin (pebblegpu_auto_scale_row) is the reference's serial loop; the device (k_scale_stats: one 256-lane workgroup per row, a
+ * fixed reduction order, no atomics -- the same bits on every run) adds in another order, so avg_power agrees to ~bins * 2^-53 relative
+ * and a row whose powerTodB(avg) - 10 or powerTodB(peak) + 10 lies within that of an integer may come out 5 dB away.
+ *
+ * Pull interface: the scale of frames first_frame + j * frame_step (j < n_frames) of the LAST call's unprocessed spectrum, every
+ * stream, into the device buffer d_out [stream][n_frames]; queued where pebblegpu_*_map_spectrum queues its map, results complete
+ * after _synchronize; the same frame rules and refusals.
+ *
+ * The rings.  _display_set_auto_scale(flags) is maxDbChanged / minDbChanged with or without "Auto" (spectrumwidget.cpp:933-966);
+ * _display_rescale is m_scaleNeedsRecalc = true (power-on :239, an LO change :562).  Both are HOST FLAGS consumed when the next call is
+ * queued: they never wait for earlier calls (pebblegpu_receiver_display_set_pane does).
+ *   - A flag that goes on requests a recalc; until it has happened the pane's own map.max_db / min_db hold for that end of the range
+ *     (m_fullScaleDb / m_baseScaleDb).  A flag that goes off returns its end to the pane's map from the next call on.
+ *   - The recalc happens in the first call after the request that computes at least one unprocessed-spectrum row, on that call's FIRST
+ *     computed row of every stream ("wait for next fft to have new data", :1184-1187); a call under the update gate that computes none
+ *     leaves it pending.  The new range maps every row of that call's block and of later blocks, in every mapped pane: a zoomed row takes
+ *     the range of its channel's stream (stream 0 off a shared input) -- m_plotMaxDb / m_plotMinDb are the widget's.  DB_F32 panes ignore
+ *     the range as they ignore the geometry.  The stream bank: stream s's rows are mapped with stream s's range.
+ *   - Cost: one launch (k_scale_stats, a workgroup per stream) in the recalc call, ahead of the packing launch -- and, where that call's
+ *     two pipelines end on different streams (PEBBLEGPU_PIPELINE=1), two event records and two waits that order the table's write against
+ *     the other stream -- and nothing in any other call: the packing kernels read the range once per row from a table on the device, and
+ *     a call that computed no row queues nothing, as before.  With flags 0 blocks, launches and pebblegpu_*_kernel_name strings are
+ *     exactly as without this interface.
+ *   - While a flag is on every block THAT HAS ROWS carries, behind its rows and inside the slot's one copy, the ranges it was mapped with:
+ *     one pebblegpu_display_scale per selected stream (a receiver: per selected row of pane 0, by the row's stream), read with
+ *     _display_scale for a block that is currently handed out (PEBBLEGPU_E_INVALID for any other call_index, for a block queued while the
+ *     flags were 0 and for a block without a row of any pane: it maps nothing, the ranges of the last block with rows still hold).
+ *     An end whose flag is off reports the pane's (pane 0's; the stream bank: the map's) own value, truncated to int.  avg_power /
+ *     peak_power are those of the recalc in the block's own call and 0 in every other block.
+ * Refused with PEBBLEGPU_E_INVALID, the handle left as it was: no open ring; unknown flag bits; a receiver without an unprocessed spectrum
+ * (spectrum_bins == 0); a stream bank ring in DB_F32 (nothing is mapped); MAX alone with a mapped pane whose fixed min_db >= -50, MIN
+ * alone with one whose fixed max_db <= -70 (the range could come out empty or upside down), and a later _set_pane that would create either.
+ * "Alone" is judged twice: by the flags, and by the ends the table supplies at that moment -- a flag whose recalc is still pending leaves
+ * its end to the pane, so with MAX in use and MIN just requested a fixed min_db >= -50 is refused until the recalc has landed.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t max_db, min_db;        /* m_plotMaxDb, m_plotMinDb */
+    double avg_power, peak_power;  /* avgPwr, peakPwr of the row the range came from */
+} pebblegpu_display_scale;
+#define PEBBLEGPU_AUTO_SCALE_MAX 1
+#define PEBBLEGPU_AUTO_SCALE_MIN 2
+/* host twin (no device): recalcScale's loop over one row, serial as the reference */
+int pebblegpu_auto_scale_row(const float *db, uint32_t bins, pebblegpu_display_scale *out);
+int pebblegpu_receiver_spectrum_scale(pebblegpu_receiver *rx, uint32_t first_frame, uint32_t n_frames, uint32_t frame_step,
+                                      pebblegpu_display_scale *d_out);
+int pebblegpu_streambank_spectrum_scale(pebblegpu_streambank *sb, uint32_t first_frame, uint32_t n_frames, uint32_t frame_step,
+                                        pebblegpu_display_scale *d_out);
+int pebblegpu_receiver_display_set_auto_scale(pebblegpu_receiver *rx, uint32_t flags);
+int pebblegpu_receiver_display_rescale(pebblegpu_receiver *rx);
+/* out: cap entries; *n = the entries written */
+int pebblegpu_receiver_display_scale(pebblegpu_receiver *rx, uint64_t call_index, pebblegpu_display_scale *out, uint32_t cap, uint32_t *n);
+int pebblegpu_streambank_display_set_auto_scale(pebblegpu_streambank *sb, uint32_t flags);
+int pebblegpu_streambank_display_rescale(pebblegpu_streambank *sb);
+int pebblegpu_streambank_display_scale(pebblegpu_streambank *sb, uint64_t call_index, pebblegpu_display_scale *out, uint32_t cap, uint32_t *n);
+
 #ifdef __cplusplus
 }
 #endif

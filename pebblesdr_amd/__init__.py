@@ -16,6 +16,7 @@ from .binding import (  # noqa: F401
     AUDIO_F32, AUDIO_S16, AUDIO_S16_MONO, AudioBlock, audio_out_convert, iq_record_convert,
     DISPLAY_DB_F32, DISPLAY_PIXELS_I32, DISPLAY_WATERFALL_ARGB32, DisplayBlock, waterfall_colors,
     PANE_SPECTRUM, PANE_ZOOM, DisplayPane, display_pane,
+    AUTO_SCALE_MAX, AUTO_SCALE_MIN, DisplayScale, DISPLAY_SCALE, auto_scale_row,
 )
 from .steps import Mixer, Decimator, DownConvert, FastFIR, Demod, Spectrum, Morse  # noqa: F401
 
@@ -25,4 +26,5 @@ __all__ = [
     "SigGen", "Sweep", "sweep", "sweep_plan", "MorseStation", "morse_station", "morse_station_plan",
     "MultiBank", "multibank_plan", "audio_out_convert", "iq_record_convert", "DisplayBlock", "waterfall_colors",
     "PANE_SPECTRUM", "PANE_ZOOM", "DisplayPane", "display_pane",
+    "AUTO_SCALE_MAX", "AUTO_SCALE_MIN", "DisplayScale", "DISPLAY_SCALE", "auto_scale_row",
 ]

@@ -58,6 +58,9 @@ SYMBOLS = [
     "pebblegpu_streambank_display_release", "pebblegpu_streambank_display_dropped", "pebblegpu_waterfall_colors",
     "pebblegpu_receiver_display_open", "pebblegpu_receiver_display_close", "pebblegpu_receiver_display_next",
     "pebblegpu_receiver_display_release", "pebblegpu_receiver_display_dropped", "pebblegpu_receiver_display_set_pane",
+    "pebblegpu_auto_scale_row", "pebblegpu_receiver_spectrum_scale", "pebblegpu_streambank_spectrum_scale",
+    "pebblegpu_receiver_display_set_auto_scale", "pebblegpu_receiver_display_rescale", "pebblegpu_receiver_display_scale",
+    "pebblegpu_streambank_display_set_auto_scale", "pebblegpu_streambank_display_rescale", "pebblegpu_streambank_display_scale",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
@@ -320,6 +323,51 @@ def display_pane(source, fmt, screen=None, zoom=1.0, mode_offset=None, rows=None
     return p
 
 
+AUTO_SCALE_MAX, AUTO_SCALE_MIN = 1, 2  # PEBBLEGPU_AUTO_SCALE_*
+
+
+class DisplayScale(C.Structure):
+    """pebblegpu_display_scale: the plot range SpectrumWidget::recalcScale gives one spectrum row, and the powers it came from"""
+    _fields_ = [("max_db", C.c_int32), ("min_db", C.c_int32), ("avg_power", C.c_double), ("peak_power", C.c_double)]
+
+
+# the same 24 bytes as a numpy record (what the pull functions and display_scale() return)
+DISPLAY_SCALE = np.dtype([("max_db", np.int32), ("min_db", np.int32), ("avg_power", np.float64), ("peak_power", np.float64)])
+
+
+def auto_scale_row(db, lib=None):
+    """host twin of the auto-scale rule (no device): one row of float dB -> (max_db, min_db, avg_power, peak_power)"""
+    L = lib or load_library()
+    row = np.ascontiguousarray(db, dtype=np.float32).reshape(-1)
+    out = DisplayScale()
+    check(L, L.pebblegpu_auto_scale_row(row.ctypes.data_as(C.c_void_p), row.size, C.byref(out)))
+    return int(out.max_db), int(out.min_db), float(out.avg_power), float(out.peak_power)
+
+
+def _pull_scale(obj, fn, frames, first_frame, n_frames, frame_step):
+    """the pull functions' shared body: queue, synchronise, download -> DISPLAY_SCALE [streams, n_frames]"""
+    if first_frame is None and n_frames is None:
+        n_frames = 1
+    first_frame, n_frames, frame_step = _frame_range(frames, first_frame, n_frames, frame_step)
+    out = np.zeros((obj.n_streams, n_frames), dtype=DISPLAY_SCALE)
+    buf = DeviceBuffer(max(1, out.nbytes), obj.device, obj.L)
+    try:
+        check(obj.L, fn(obj.h, first_frame, n_frames, frame_step, C.c_void_p(buf.ptr)))
+        obj.synchronize()
+        if out.size:
+            check(obj.L, obj.L.pebblegpu_memcpy_d2h(obj.device, out.ctypes.data_as(C.c_void_p), C.c_void_p(buf.ptr), out.nbytes))
+        return out
+    finally:
+        buf.free()
+
+
+def _ring_scale(L, fn, h, call_index, cap):
+    out = np.zeros(max(1, int(cap)), dtype=DISPLAY_SCALE)
+    n = C.c_uint32()
+    check(L, fn(h, int(call_index), out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)))
+    return out[: n.value].copy()
+
+
 def waterfall_colors(pixels, lib=None):
     """the host twin of the waterfall's colour rule (SpectrumWidget::drawWaterfall): int32 pixel values 0..255 -> uint32 0xFFRRGGBB, same shape"""
     L = lib or load_library()
@@ -550,6 +598,13 @@ def _declare(L):
     L.pebblegpu_receiver_display_release.argtypes = [vp, u64]
     L.pebblegpu_receiver_display_dropped.argtypes = [vp, C.POINTER(u64)]
     L.pebblegpu_receiver_display_set_pane.argtypes = [vp, u32, dpane]
+    L.pebblegpu_auto_scale_row.argtypes = [vp, u32, C.POINTER(DisplayScale)]
+    L.pebblegpu_receiver_spectrum_scale.argtypes = [vp, u32, u32, u32, vp]
+    L.pebblegpu_streambank_spectrum_scale.argtypes = [vp, u32, u32, u32, vp]
+    for who in ("receiver", "streambank"):
+        getattr(L, "pebblegpu_%s_display_set_auto_scale" % who).argtypes = [vp, u32]
+        getattr(L, "pebblegpu_%s_display_rescale" % who).argtypes = [vp]
+        getattr(L, "pebblegpu_%s_display_scale" % who).argtypes = [vp, u64, vp, u32, C.POINTER(u32)]
     return L
 
 
@@ -905,6 +960,26 @@ class ReceiverBank:
 
     def display_release(self, call_index):
         check(self.L, self.L.pebblegpu_receiver_display_release(self.h, int(call_index)))
+
+    # ---- auto-scale (SpectrumWidget::recalcScale) ----
+    def spectrum_scale(self, first_frame=None, n_frames=None, frame_step=1):
+        """the auto-scale range of frames first_frame + j * frame_step of the last call's spectrum -> DISPLAY_SCALE [streams, n_frames]
+        (default: the last frame only)"""
+        n = C.c_uint64()
+        self.L.pebblegpu_receiver_spectrum(self.h, C.byref(n))
+        return _pull_scale(self, self.L.pebblegpu_receiver_spectrum_scale, int(n.value), first_frame, n_frames, frame_step)
+
+    def display_set_auto_scale(self, flags):
+        """AUTO_SCALE_MAX | AUTO_SCALE_MIN: "Auto" in the max / min dB box; a host flag, consumed by the next call (no wait)"""
+        check(self.L, self.L.pebblegpu_receiver_display_set_auto_scale(self.h, int(flags)))
+
+    def display_rescale(self):
+        """m_scaleNeedsRecalc = true (an LO change): the next call that computes a spectrum row recomputes the range"""
+        check(self.L, self.L.pebblegpu_receiver_display_rescale(self.h))
+
+    def display_scale(self, call_index, cap=4096):
+        """the ranges the handed-out block of call_index was mapped with -> DISPLAY_SCALE [pane 0's selected rows]"""
+        return _ring_scale(self.L, self.L.pebblegpu_receiver_display_scale, self.h, call_index, cap)
 
     def display_dropped(self):
         n = C.c_uint64()
@@ -1285,6 +1360,24 @@ class StreamBank:
 
     def display_release(self, call_index):
         check(self.L, self.L.pebblegpu_streambank_display_release(self.h, int(call_index)))
+
+    # ---- auto-scale (SpectrumWidget::recalcScale) ----
+    def spectrum_scale(self, first_frame=None, n_frames=None, frame_step=1):
+        """the auto-scale range of frames first_frame + j * frame_step of the last call's spectrum -> DISPLAY_SCALE [streams, n_frames]"""
+        f = C.c_uint64()
+        self.L.pebblegpu_streambank_spectrum(self.h, C.byref(f), None)
+        return _pull_scale(self, self.L.pebblegpu_streambank_spectrum_scale, int(f.value), first_frame, n_frames, frame_step)
+
+    def display_set_auto_scale(self, flags):
+        """AUTO_SCALE_MAX | AUTO_SCALE_MIN; a host flag, consumed by the next call (no wait)"""
+        check(self.L, self.L.pebblegpu_streambank_display_set_auto_scale(self.h, int(flags)))
+
+    def display_rescale(self):
+        check(self.L, self.L.pebblegpu_streambank_display_rescale(self.h))
+
+    def display_scale(self, call_index, cap=4096):
+        """the ranges the handed-out block of call_index was mapped with -> DISPLAY_SCALE [selected streams]"""
+        return _ring_scale(self.L, self.L.pebblegpu_streambank_display_scale, self.h, call_index, cap)
 
     def display_dropped(self):
         n = C.c_uint64()

@@ -25,6 +25,7 @@ struct CallFacts {
     bool taps = false;            // some tap point is enabled
     bool recording = false;       // the recording ring is open
     bool ch0_tune_only = false;   // channel 0 is in DM_NONE
+    bool scale_pending = false;   // the display ring has an auto-scale flag on and a recalc requested (m_scaleNeedsRecalc)
     // what the cores can do
     bool dec_lds_free_front = false;  // the decimator's first kernel can leave LDS alone (DecimCore::front_is_lds_free)
     bool dec_raw_front = false;       // ... and has a variant that converts raw samples in its loads (DecimCore::raw_front)
@@ -52,6 +53,8 @@ struct CallRoute {
     bool done_in_kernel = false;  // the hand-over event is offered to the bank kernel's own dispatch (Tuning::bank_pipe_extev)
     bool timed_handover = false;  // the hand-over records the call's timing event instead of one without timing (Tuning::bank_pipe_timed_ev)
     CallTail tail = CallTail::Narrow;
+    bool rescale = false;    // the display ring's recalc stage: k_scale_stats on the call's first computed spectrum row, ahead of the packing
+                             // launch (a gated call that computes no row leaves the request pending: the timer's selection is made later)
     bool tune_only = false;  // one channel in DM_NONE: the call ends behind the band-pass like a closed gate (a gate closed by the
                              // squelch read-back is a run-time fact and not part of the route)
 };
@@ -99,6 +102,9 @@ inline CallRoute plan_call_route(const CallFacts &f)
     r.done_in_kernel = r.bank_pipe && f.bank_pipe_extev;
     r.timed_handover = r.bank_pipe && f.bank_pipe_timed_ev;
     r.tail = f.wfm ? CallTail::Wfm : f.bank_gate ? CallTail::BankGated : CallTail::Narrow;
+    // SpectrumWidget::recalcScale runs on "the next fft that has new data" (spectrumwidget.cpp:1184-1187): one more launch in this call,
+    // none in any other
+    r.rescale = f.scale_pending && f.with_spectrum;
     // dmNONE, "Tune only mode, no demod or output" (receiver.cpp:968-971): for the reference's own shape (one channel) the call
     // ends behind the band-pass; in a bank the tune-only channels sit out the noise filter, AGC and demodulators and their rows are cleared
     r.tune_only = !f.wfm && f.C == 1 && f.ch0_tune_only;

@@ -107,17 +107,49 @@ static __global__ __launch_bounds__(256) void k_display_rows(const float *__rest
 
 template <int G>
 static void launch_display_map(hipStream_t s, const DisplayPack &p, const float *in, long long stream_pitch, int first_row, int n_rows, unsigned char *out,
-                               unsigned long long stream_bytes)
+                               unsigned long long stream_bytes, const ScaleUse &su)
 {
     constexpr long long kGroups = 256 / G;
     const long long n_items = (long long)p.n_streams * n_rows * p.sh.x_pixels;
     const dim3 grid((unsigned)std::min<long long>((n_items + kGroups - 1) / kGroups, 1LL << 20));
     if (p.format == PEBBLEGPU_DISPLAY_WATERFALL_ARGB32)
         launch(k_display_map<G, true>, grid, dim3(256), s, in, stream_pitch, (long long)p.sh.fft_size, first_row, n_rows, n_items, p.geom, p.sh, p.d_tab, out,
-               (unsigned long long)p.row_pitch_bytes, stream_bytes);
+               (unsigned long long)p.row_pitch_bytes, stream_bytes, su);
     else
         launch(k_display_map<G, false>, grid, dim3(256), s, in, stream_pitch, (long long)p.sh.fft_size, first_row, n_rows, n_items, p.geom, p.sh, p.d_tab, out,
-               (unsigned long long)p.row_pitch_bytes, stream_bytes);
+               (unsigned long long)p.row_pitch_bytes, stream_bytes, su);
+}
+
+int run_scale_stats(hipStream_t s, const float *in, long long stream_pitch, long long frame_pitch, int n_streams, int n_frames, int bins, ScaleEntry *out)
+{
+    if (n_streams <= 0 || n_frames <= 0) return 0;
+    if (bins < 4 || bins % 4) return fail(PEBBLEGPU_E_UNSUPPORTED, "%d bins: spectrum rows are read in 16-byte vectors", bins);
+    launch(k_scale_stats, dim3((unsigned)((long long)n_streams * n_frames)), dim3(256), s, in, stream_pitch, frame_pitch, n_frames, bins, out);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// SpectrumWidget::recalcScale on the host: the loop of spectrumwidget.cpp:705-710 as written, one bin after the other
+ScaleEntry auto_scale_row(const float *db, uint32_t bins)
+{
+#pragma clang fp contract(off)
+    double total = 0.0, peak = 0.0;
+    for (uint32_t i = 0; i < bins; i++) {
+        const double pwr = std::pow(10, (double)db[i] / 10.0);  // DB::dBToPower
+        total += pwr;
+        if (pwr > peak) peak = pwr;
+    }
+    return auto_scale_finish(total, peak, (int32_t)bins);
+}
+
+int check_auto_scale(uint32_t flags, double fixed_max_db, double fixed_min_db)
+{
+    if (flags & ~(uint32_t)(PEBBLEGPU_AUTO_SCALE_MAX | PEBBLEGPU_AUTO_SCALE_MIN)) return fail(PEBBLEGPU_E_INVALID, "unknown auto-scale flags 0x%x", flags);
+    if (flags == PEBBLEGPU_AUTO_SCALE_MAX && fixed_min_db >= (double)kAutoMaxDbLimit)
+        return fail(PEBBLEGPU_E_INVALID, "auto-scaled max_db may come out %d: a fixed min_db of %g leaves no range", kAutoMaxDbLimit, fixed_min_db);
+    if (flags == PEBBLEGPU_AUTO_SCALE_MIN && fixed_max_db <= (double)kAutoMinDbLimit)
+        return fail(PEBBLEGPU_E_INVALID, "auto-scaled min_db may come out %d: a fixed max_db of %g leaves no range", kAutoMinDbLimit, fixed_max_db);
+    return 0;
 }
 
 void display_pack_plan(DisplayPack *p, int32_t bins, double sample_rate, const pebblegpu_screen_map *map)
@@ -133,6 +165,7 @@ void display_pack_plan(DisplayPack *p, int32_t bins, double sample_rate, const p
         p->sh.y_pixels = map->y_pixels;
         p->sh.y_scale = map_y_scale(map->y_pixels, map->max_db, map->min_db);
         p->sh.max_db = map->max_db;
+        p->min_db = map->min_db;
         p->geom = map_geom(bins, sample_rate, map->start_freq, map->stop_freq, map->x_pixels);
         p->group = map_lane_group(p->geom.bins_to_plot > map->x_pixels ? p->geom.bins_per_pixel : 0.0f);  // as run_screen_map sizes it
         p->row_elems = (uint32_t)map->x_pixels;
@@ -140,7 +173,7 @@ void display_pack_plan(DisplayPack *p, int32_t bins, double sample_rate, const p
     p->row_pitch_bytes = ((uint64_t)p->row_elems * 4 + 15) & ~(uint64_t)15;
 }
 
-int run_display_pack(hipStream_t s, const DisplayPack &p, const float *spec, long long pitch_rows, int first_row, int n_rows, void *dst)
+int run_display_pack(hipStream_t s, const DisplayPack &p, const float *spec, long long pitch_rows, int first_row, int n_rows, void *dst, const ScaleUse &su)
 {
     if (n_rows <= 0 || p.n_streams == 0) return 0;
     const long long bins = p.sh.fft_size, stream_pitch = pitch_rows * bins;
@@ -154,20 +187,20 @@ int run_display_pack(hipStream_t s, const DisplayPack &p, const float *spec, lon
                (unsigned long long)p.row_pitch_bytes, stream_bytes);
     } else {
         switch (p.group) {
-        case 1: launch_display_map<1>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes); break;
-        case 2: launch_display_map<2>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes); break;
-        case 4: launch_display_map<4>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes); break;
-        case 8: launch_display_map<8>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes); break;
-        case 16: launch_display_map<16>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes); break;
-        case 32: launch_display_map<32>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes); break;
-        default: launch_display_map<64>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes); break;
+        case 1: launch_display_map<1>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes, su); break;
+        case 2: launch_display_map<2>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes, su); break;
+        case 4: launch_display_map<4>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes, su); break;
+        case 8: launch_display_map<8>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes, su); break;
+        case 16: launch_display_map<16>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes, su); break;
+        case 32: launch_display_map<32>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes, su); break;
+        default: launch_display_map<64>(s, p, spec, stream_pitch, first_row, n_rows, out, stream_bytes, su); break;
         }
     }
     PG_HIP(hipGetLastError());
     return 0;
 }
 
-int run_display_panes(hipStream_t s, const DisplayPaneArgs *panes, int n_panes)
+int run_display_panes(hipStream_t s, const DisplayPaneArgs *panes, int n_panes, const ScaleUse &su, const DisplayRow *trailer_tab)
 {
     DisplayPaneArgs a[2];
     int n = 0;
@@ -184,7 +217,7 @@ int run_display_panes(hipStream_t s, const DisplayPaneArgs *panes, int n_panes)
         gx = std::max(gx, a[k].x_blocks);
         gy = std::max(gy, a[k].total_rows);
     }
-    launch(k_display_panes, dim3(gx, (unsigned)std::min<long long>(gy, 4096), (unsigned)n), dim3(256), s, a[0], a[1]);
+    launch(k_display_panes, dim3(gx, (unsigned)std::min<long long>(gy, 4096), (unsigned)n), dim3(256), s, a[0], a[1], su, trailer_tab);
     PG_HIP(hipGetLastError());
     return 0;
 }
@@ -231,6 +264,7 @@ struct DisplayRing {
         uint64_t row_pitch = 0;          // bytes, a multiple of 16
         uint64_t cap_pitch = 0;          // ... what the slots were sized for at open
         MapShared sh{};
+        double min_db = 0;               // the map's lower end (sh has the upper one)
         unsigned x_blocks = 1;
         std::vector<DisplayRow> tab;     // the device table's host copy
         DisplayRow *d_tab = nullptr;
@@ -243,9 +277,27 @@ struct DisplayRing {
     SlotPane info[kEgressMaxSlots][PEBBLEGPU_DISPLAY_MAX_PANES] = {};
     hipEvent_t packed2[kEgressMaxSlots] = {};  // behind the first pane's launch when the two panes are packed on different streams
     bool dirty = false;                  // a table changed: uploaded at the next call's boundary
+    // auto-scale (SpectrumWidget::recalcScale): host flags consumed when the next call is queued -- never a wait
+    uint32_t scale_flags = 0;            // PEBBLEGPU_AUTO_SCALE_* as last set
+    uint32_t scale_live = 0;             // ... those whose end of the range a recalc has computed since the flag went on
+    bool scale_pending = false;          // m_scaleNeedsRecalc
+    ScaleEntry *d_scale = nullptr;       // [streams] the ranges, written by k_scale_stats in a recalc call
+    hipEvent_t scale_ev = nullptr;       // behind that launch, for the panes packed on the other stream (the recalc call only)
+    hipEvent_t scale_rd_ev = nullptr;    // ... and in front of it: behind everything queued on the other stream so far (the table's readers there)
+    uint64_t trailer_cap = 0;            // bytes of a slot kept for the trailer
+    struct SlotScale { bool on; uint32_t n; uint64_t offset; };
+    SlotScale scale_info[kEgressMaxSlots] = {};
 
     void free_device()
     {
+        if (d_scale) (void)hipFree(d_scale);
+        d_scale = nullptr;
+        if (scale_ev) (void)hipEventDestroy(scale_ev);
+        scale_ev = nullptr;
+        if (scale_rd_ev) (void)hipEventDestroy(scale_rd_ev);
+        scale_rd_ev = nullptr;
+        scale_flags = scale_live = 0;
+        scale_pending = false;
         for (Pane &p : pane) {
             if (p.d_tab) (void)hipFree(p.d_tab);
             p.d_tab = nullptr;
@@ -291,6 +343,7 @@ static int plan_pane(const Receiver &rx, const pebblegpu_display_pane *p, Displa
     for (size_t r = 0; r < out->sel.size(); r++) {
         out->tab[r].src = out->sel[r];
         out->tab[r].group = 1;
+        out->tab[r].scale_src = zoom ? (rx.shared_input ? 0u : out->sel[r]) : out->sel[r];  // m_plotMaxDb / m_plotMinDb are the widget's: the zoomed panel takes its stream's range
     }
     if (p->format == PEBBLEGPU_DISPLAY_DB_F32) {
         if (fft % 4) return fail(PEBBLEGPU_E_UNSUPPORTED, "%u bins: display rows are copied in 16-byte vectors", fft);
@@ -328,6 +381,7 @@ static int plan_pane(const Receiver &rx, const pebblegpu_display_pane *p, Displa
         out->sh.y_pixels = m.y_pixels;
         out->sh.y_scale = map_y_scale(m.y_pixels, m.max_db, m.min_db);
         out->sh.max_db = m.max_db;
+        out->min_db = m.min_db;
         out->row_elems = (uint32_t)m.x_pixels;
         const long long per_wg = 256 / gmax;
         out->x_blocks = (unsigned)std::min<long long>(((long long)m.x_pixels + per_wg - 1) / per_wg, 64);
@@ -350,6 +404,8 @@ int Receiver::display_open(const pebblegpu_display_pane *panes, uint32_t n_panes
         if (rows > kMaxDisplayRingBytes / plan[k].row_pitch) slot_bytes = kMaxDisplayRingBytes + 1;  // (and no overflow)
         else slot_bytes += rows * plan[k].row_pitch;
     }
+    const uint64_t trailer_cap = ((uint64_t)plan[0].sel.size() * sizeof(ScaleEntry) + 15) & ~(uint64_t)15;  // room behind the panes for the auto-scale trailer
+    if (slot_bytes <= kMaxDisplayRingBytes) slot_bytes += trailer_cap;
     std::lock_guard<std::mutex> g(mu_);
     if (disp_open_) return fail(PEBBLEGPU_E_INVALID, "the display ring is already open");
     if (slot_bytes > kMaxDisplayRingBytes || slot_bytes * n_slots > kMaxDisplayRingBytes)
@@ -362,7 +418,13 @@ int Receiver::display_open(const pebblegpu_display_pane *panes, uint32_t n_panes
     std::lock_guard<std::mutex> lk(d.ring.mu);
     auto body = [&]() -> int {
         for (uint32_t k = 0; k < n_panes; k++) PG_HIP(hipMalloc((void **)&plan[k].d_tab, sizeof(DisplayRow) * plan[k].tab.size()));
-        if (int rc = d.ring.open_ring(n_slots, 1, 4, slot_bytes / 4, 0)) return rc;
+        // the auto-scale trailer holds pane 0's selected rows; the ranges' table one entry per stream
+        d.trailer_cap = trailer_cap;
+        PG_HIP(hipMalloc((void **)&d.d_scale, sizeof(ScaleEntry) * S));
+        PG_HIP(hipMemset(d.d_scale, 0, sizeof(ScaleEntry) * S));
+        PG_HIP(hipEventCreateWithFlags(&d.scale_ev, hipEventDisableTiming));
+        PG_HIP(hipEventCreateWithFlags(&d.scale_rd_ev, hipEventDisableTiming));
+        if (int rc = d.ring.open_ring(n_slots, 1, 4, (slot_bytes - trailer_cap) / 4, 0, trailer_cap)) return rc;
         for (uint32_t i = 0; i < n_slots; i++) {
             PG_HIP(hipMemset(d.ring.slot[i].d, 0, d.ring.slot_bytes));  // (the padding of a row is never written)
             PG_HIP(hipEventCreateWithFlags(&d.packed2[i], hipEventDisableTiming));
@@ -428,6 +490,10 @@ int Receiver::display_set_pane(uint32_t pane, const pebblegpu_display_pane *p)
     if (int rc = plan_pane(*this, &q, &next)) return rc;
     if (next.row_pitch > cur.cap_pitch)
         return fail(PEBBLEGPU_E_SIZE, "rows of %llu bytes: the slots were sized for %llu at open", (unsigned long long)next.row_pitch, (unsigned long long)cur.cap_pitch);
+    if (next.format != PEBBLEGPU_DISPLAY_DB_F32) {  // (against the flags, and against the ends the table supplies until a pending recalc lands)
+        if (int rc = check_auto_scale(disp_->scale_flags, next.sh.max_db, next.min_db)) return rc;
+        if (int rc = check_auto_scale(disp_->scale_flags & disp_->scale_live, next.sh.max_db, next.min_db)) return rc;
+    }
     next.cap_pitch = cur.cap_pitch;
     next.d_tab = cur.d_tab;
     cur = next;
@@ -453,9 +519,31 @@ int Receiver::upload_display_tables()
 // The block of an accepted call.  spec_rows / zoom_rows: the rows THIS call computed (compact in d_spec / d_zoom), complete on spec_s /
 // zoom_s -- where Receiver::map_spectrum would queue its map, and where the next call's transform of the same buffer follows.  Both
 // panes on one stream: one launch; else one per pane, and the slot's copy waits for both.
-int Receiver::queue_display_block(hipStream_t spec_s, uint64_t spec_rows, hipStream_t zoom_s, uint64_t zoom_rows)
+int Receiver::queue_display_block(hipStream_t spec_s, uint64_t spec_rows, hipStream_t zoom_s, uint64_t zoom_rows, bool rescale)
 {
     DisplayRing &d = *disp_;
+    // SpectrumWidget::recalcScale on this call's first computed row of every stream (spectrumwidget.cpp:1184-1187: "wait for next fft to
+    // have new data" -- a call that computed none leaves the request pending).  Whether the block is delivered or dropped: what later
+    // blocks look like never depends on the reader
+    const bool recalc = rescale && d.scale_flags && d.scale_pending && spec_rows > 0;
+    if (recalc) {
+        // The table's readers are the packing launches of earlier calls.  Those on spec_s precede the write in stream order.  A call whose two
+        // pipelines are not joined (PEBBLEGPU_PIPELINE=1) may have zoomed-pane launches of ANY earlier call still queued on the other stream,
+        // which the main stream never waits for: the write waits for everything queued there so far, and that stream -- this call's zoomed
+        // pane and every later one -- is ordered behind the write.  Two records and two waits, in the recalc call only
+        const bool two = zoom_s != spec_s;
+        if (two) {
+            PG_HIP(hipEventRecord(d.scale_rd_ev, zoom_s));
+            PG_HIP(hipStreamWaitEvent(spec_s, d.scale_rd_ev, 0));
+        }
+        if (int rc = run_scale_stats(spec_s, d_spec, (long long)spec_rows * bins, 0, (int)S, 1, (int)bins, d.d_scale)) return rc;
+        if (two) {
+            PG_HIP(hipEventRecord(d.scale_ev, spec_s));
+            PG_HIP(hipStreamWaitEvent(zoom_s, d.scale_ev, 0));
+        }
+        d.scale_live = d.scale_flags;
+        d.scale_pending = false;
+    }
     EgressSlot *g = d.ring.begin();
     if (!g) return 0;
     const int si = (int)(g - d.ring.slot);
@@ -479,22 +567,110 @@ int Receiver::queue_display_block(hipStream_t spec_s, uint64_t spec_rows, hipStr
         q.sh = p.sh;
         q.out = (unsigned char *)g->d + off;
         q.out_row_pitch = p.row_pitch;
+        q.min_db = p.min_db;
         st[k] = zoom ? zoom_s : spec_s;
         off += (uint64_t)q.total_rows * p.row_pitch;
     }
     g->aux = (uint32_t)si;
+    // auto-scale: the ranges by value in the launch, the ranges used into a trailer behind the panes (inside the one copy).  A block
+    // without a row of any pane stays what it was: nothing queued, no trailer
+    ScaleUse su, su_rest;
+    uint64_t trailer = 0;
+    d.scale_info[si] = DisplayRing::SlotScale{false, 0, 0};
+    if (d.scale_flags && off) {
+        su.tab = d.d_scale;
+        su.use = d.scale_flags & d.scale_live;
+        su.refreshed = recalc ? 1u : 0u;
+        su_rest = su;
+        su.trailer = reinterpret_cast<ScaleEntry *>((unsigned char *)g->d + off);
+        su.n_trailer = (uint32_t)d.pane[0].sel.size();
+        su.fixed_max = d.pane[0].sh.max_db;
+        su.fixed_min = d.pane[0].min_db;
+        d.scale_info[si] = DisplayRing::SlotScale{true, su.n_trailer, off};
+        trailer = d.trailer_cap;
+    }
     hipStream_t last = st[0];
     if (d.n_panes == 2 && st[0] != st[1] && a[0].total_rows && a[1].total_rows) {
-        if (int rc = run_display_panes(st[0], &a[0], 1)) return rc;
+        if (int rc = run_display_panes(st[0], &a[0], 1, su, d.pane[0].d_tab)) return rc;
         PG_HIP(hipEventRecord(d.packed2[si], st[0]));
         PG_HIP(hipStreamWaitEvent(d.ring.copy_stream, d.packed2[si], 0));
-        if (int rc = run_display_panes(st[1], &a[1], 1)) return rc;
+        if (int rc = run_display_panes(st[1], &a[1], 1, su_rest, nullptr)) return rc;
         last = st[1];
     } else {
         if (d.n_panes == 2 && !a[0].total_rows) last = st[1];
-        if (int rc = run_display_panes(last, a, (int)d.n_panes)) return rc;
+        if (int rc = run_display_panes(last, a, (int)d.n_panes, su, d.pane[0].d_tab)) return rc;
     }
-    return d.ring.commit(g, last, off / 4);  // (a "sample" is 4 bytes; 0: nothing is queued at all)
+    return d.ring.commit(g, last, off / 4, trailer);  // (a "sample" is 4 bytes; 0: nothing is queued at all)
+}
+
+// ---- auto-scale: the pull function and the ring's flags ----
+bool Receiver::display_scale_pending() const { return disp_open_ && disp_->scale_flags && disp_->scale_pending; }
+
+int Receiver::spectrum_scale(uint32_t first, uint32_t n, uint32_t step, pebblegpu_display_scale *d_out)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (!d_out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (failed_) return fail(PEBBLEGPU_E_HIP, "an earlier call on this receiver failed half-way: its spectra are not defined");
+    if (!bins) return fail(PEBBLEGPU_E_INVALID, "the receiver computes no spectrum (spectrum_bins = 0)");
+    uint64_t frames = last_spec_frames;
+    const bool carried = gated() && !frames && have_carry_;  // as pebblegpu_receiver_map_spectrum: the spectrum the display still holds, as row 0
+    if (carried) frames = 1;
+    if (!frames) return fail(PEBBLEGPU_E_INVALID, "no call with a spectrum has been made yet");
+    if (n == 0 || (uint64_t)first + (uint64_t)(n - 1) * step >= frames)
+        return fail(PEBBLEGPU_E_INVALID, "frames %u + j * %u, j < %u, are not all within the last call's %llu", first, step, n, (unsigned long long)frames);
+    PG_HIP(hipSetDevice(device));
+    if (int rc = close_timing()) return rc;
+    const float *src = carried ? d_spec_carry : d_spec + (long long)first * bins;
+    return run_scale_stats(stream_, src, (long long)frames * bins, (long long)step * bins, (int)S, (int)n, (int)bins, reinterpret_cast<ScaleEntry *>(d_out));
+}
+
+int Receiver::display_set_auto_scale(uint32_t flags)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (!disp_open_) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    if (!bins) return fail(PEBBLEGPU_E_INVALID, "the range comes from the unprocessed spectrum: the receiver computes none (spectrum_bins = 0)");
+    DisplayRing &d = *disp_;
+    if (int rc = check_auto_scale(flags, 0.0, -120.0)) return rc;  // (the flag bits)
+    // (the one-flag refusals hold for the flags and for the ends the table supplies until the recalc lands: flags & live)
+    for (uint32_t k = 0; k < d.n_panes; k++)
+        if (d.pane[k].format != PEBBLEGPU_DISPLAY_DB_F32) {
+            if (int rc = check_auto_scale(flags, d.pane[k].sh.max_db, d.pane[k].min_db)) return rc;
+            if (int rc = check_auto_scale(flags & d.scale_live, d.pane[k].sh.max_db, d.pane[k].min_db)) return rc;
+        }
+    if (flags & ~d.scale_flags) d.scale_pending = true;  // maxDbChanged / minDbChanged with "Auto": m_scaleNeedsRecalc = true (spectrumwidget.cpp:942, :960)
+    d.scale_live &= flags;                               // a flag that goes off returns its end to the pane's map (m_plotMaxDb = db)
+    d.scale_flags = flags;
+    if (!flags) d.scale_pending = false;
+    return 0;
+}
+int Receiver::display_rescale()
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (!disp_open_) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    disp_->scale_pending = disp_->scale_flags != 0;  // (recalcScale returns at once with neither flag on)
+    return 0;
+}
+int Receiver::display_scale(uint64_t call_index, pebblegpu_display_scale *out, uint32_t cap, uint32_t *n)
+{
+    if (!n) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    *n = 0;
+    if (!disp_) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    DisplayRing &d = *disp_;
+    std::lock_guard<std::mutex> lk(d.ring.mu);
+    if (!d.ring.open) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    for (uint64_t q = d.ring.tail; q < d.ring.read; q++) {
+        const uint32_t si = (uint32_t)(q % d.ring.n_slots);
+        const EgressSlot &g = d.ring.slot[si];
+        if (g.call != call_index) continue;
+        const DisplayRing::SlotScale &z = d.scale_info[si];
+        if (!z.on) return fail(PEBBLEGPU_E_INVALID, "the block of call %llu carries no ranges: no auto-scale flag was on when it was queued, or it has no rows", (unsigned long long)call_index);
+        if (z.n > cap) return fail(PEBBLEGPU_E_SIZE, "%u ranges do not fit %u entries", z.n, cap);
+        if (z.n && !out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+        memcpy(out, (const unsigned char *)g.h + z.offset, sizeof(pebblegpu_display_scale) * z.n);
+        *n = z.n;
+        return 0;
+    }
+    return fail(PEBBLEGPU_E_INVALID, "call %llu is not handed out", (unsigned long long)call_index);
 }
 
 int Receiver::display_next(int wait, pebblegpu_display_block *b)

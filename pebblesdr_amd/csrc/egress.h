@@ -97,7 +97,8 @@ struct EgressRing {
 
     static uint64_t row_pitch(uint64_t samples, uint32_t bytes_per_sample) { return (samples * bytes_per_sample + 15) & ~(uint64_t)15; }
     // allocates n_slots x (pinned buffer, twin, two events) for `rows` rows of at most max_samples; the caller has set the device
-    int open_ring(uint32_t slots, uint32_t n_rows, uint32_t bps, uint64_t max_n, uint32_t fmt);
+    // extra_bytes: room behind the rows for the owner's trailer (commit's extra_bytes)
+    int open_ring(uint32_t slots, uint32_t n_rows, uint32_t bps, uint64_t max_n, uint32_t fmt, uint64_t extra_bytes = 0);
     void release();                    // (the owner has synchronised its streams)
     // close: the owner has synchronised its streams (every slot's event is complete); waits until a reader on another thread has left
     // its event wait, then frees the ring -- the events are never destroyed under a waiting reader
@@ -106,7 +107,8 @@ struct EgressRing {
     // is dropped and counted); the call index advances either way.  commit(): an event on `s` behind the packing kernel, the copy of
     // rows * pitch bytes on the copy stream behind it, the slot's event; with samples == 0 nothing is queued at all.
     EgressSlot *begin();
-    int commit(EgressSlot *g, hipStream_t s, uint64_t samples);
+    // extra_bytes (a multiple of 16): a trailer the packing launch wrote at rows * pitch, inside the one copy
+    int commit(EgressSlot *g, hipStream_t s, uint64_t samples, uint64_t extra_bytes = 0);
     // The reader's side.  next(): the oldest block not handed out yet; wait != 0 blocks on that slot's event only; host == nullptr
     // when nothing is queued or (wait == 0) the copy has not completed.  finish(): takes the oldest unreleased block.
     int next(int device, int wait, EgressBlock *b);

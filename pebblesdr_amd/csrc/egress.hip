@@ -175,14 +175,14 @@ int run_iq_pack(hipStream_t s, const float2 *iq, long long pitch, long long n, c
 }
 
 // ---- EgressRing ----
-int EgressRing::open_ring(uint32_t slots, uint32_t n_rows, uint32_t bps, uint64_t max_n, uint32_t fmt)
+int EgressRing::open_ring(uint32_t slots, uint32_t n_rows, uint32_t bps, uint64_t max_n, uint32_t fmt, uint64_t extra_bytes)
 {
     format = fmt;
     n_slots = slots;
     rows = n_rows;
     bytes_per_sample = bps;
     max_samples = max_n;
-    slot_bytes = (uint64_t)n_rows * row_pitch(max_n, bps);
+    slot_bytes = (uint64_t)n_rows * row_pitch(max_n, bps) + extra_bytes;
     if (!copy_stream) PG_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
     for (uint32_t i = 0; i < n_slots; i++) {
         EgressSlot &g = slot[i];
@@ -238,15 +238,15 @@ EgressSlot *EgressRing::begin()
     return &g;
 }
 
-int EgressRing::commit(EgressSlot *g, hipStream_t s, uint64_t samples)
+int EgressRing::commit(EgressSlot *g, hipStream_t s, uint64_t samples, uint64_t extra_bytes)
 {
     g->samples = samples;
     g->pitch_bytes = row_pitch(samples, bytes_per_sample);
-    g->has_copy = samples != 0;
+    g->has_copy = samples != 0 || extra_bytes != 0;
     if (g->has_copy) {
         PG_HIP(hipEventRecord(g->packed, s));
         PG_HIP(hipStreamWaitEvent(copy_stream, g->packed, 0));
-        PG_HIP(hipMemcpyAsync(g->h, g->d, (size_t)(rows * g->pitch_bytes), hipMemcpyDeviceToHost, copy_stream));
+        PG_HIP(hipMemcpyAsync(g->h, g->d, (size_t)(rows * g->pitch_bytes + extra_bytes), hipMemcpyDeviceToHost, copy_stream));
         PG_HIP(hipEventRecord(g->copied, copy_stream));
     }
     std::lock_guard<std::mutex> lk(mu);

@@ -65,8 +65,10 @@ inline MapGeom map_geom(int32_t fft_size, double sample_rate, int32_t start_freq
     return g;
 }
 
-inline float map_y_scale(int32_t y_pixels, double max_db, double min_db)
+// (a double division, correctly rounded on the device too: the packing kernels of a ring with auto-scale on call it per row and get the host's bits)
+__host__ __device__ inline float map_y_scale(int32_t y_pixels, double max_db, double min_db)
 {
+#pragma clang fp contract(off)
     const double db_range = max_db - min_db;
     return (float)(-y_pixels / db_range);
 }
@@ -142,6 +144,116 @@ static __global__ __launch_bounds__(256) void k_screen_map(const float *__restri
     }
 }
 
+// ---- SpectrumWidget::recalcScale (application/spectrumwidget.cpp:693-734): the plot range of AutoScaleMax / AutoScaleMin ----
+// (both default true, application/settings.cpp:70-71).  One spectrum row of `bins` dB values, each widened to double:
+//   pwr_i   = pow(10, dB_i / 10.0)                               DB::dBToPower, db.h:72-75                            (:706)
+//   total  += pwr_i; if (pwr_i > peak) peak = pwr_i  (peak starts at 0);  avg = total / bins                          (:707-711)
+//   newAvg  = (int)(powerTodB(avg) - 10)       powerTodB(0) = -120, else 10 * log10 (db.h:78-82); double -> int truncates   (:715)
+//   newAvg  = (newAvg / 5) * 5                 C int division, toward zero                                            (:716)
+//   min_db  = qBound(-120, newAvg, -70)        m_minDbScaleLimit, spectrumwidget.h:154                                (:717)
+//   newPeak = (int)(powerTodB(peak) + 10); (newPeak / 5) * 5; max_db = qBound(-50, newPeak, 0)   m_maxDbScaleLimit, :153   (:723-725)
+// The range comes from the unprocessed spectrum and applies to every pane (m_plotMaxDb / m_plotMinDb are the widget's).
+constexpr int kAutoMinDbLimit = -70, kAutoMaxDbLimit = -50;
+struct ScaleEntry {  // = pebblegpu_display_scale
+    int32_t max_db, min_db;
+    double avg_power, peak_power;
+};
+__host__ __device__ inline ScaleEntry auto_scale_finish(double total, double peak, int32_t bins)
+{
+#pragma clang fp contract(off)
+    ScaleEntry e;
+    e.avg_power = total / (double)bins;
+    e.peak_power = peak;
+    int32_t a = x86_trunc((e.avg_power == 0.0 ? (double)kMinDb : 10.0 * log10(e.avg_power)) - 10.0);
+    a = (a / 5) * 5;
+    e.min_db = a > kAutoMinDbLimit ? kAutoMinDbLimit : (a < kMinDb ? kMinDb : a);  // qBound(lo, v, hi) = max(lo, min(hi, v))
+    int32_t p = x86_trunc((peak == 0.0 ? (double)kMinDb : 10.0 * log10(peak)) + 10.0);
+    p = (p / 5) * 5;
+    e.max_db = p > 0 ? 0 : (p < kAutoMaxDbLimit ? kAutoMaxDbLimit : p);
+    return e;
+}
+
+// One 256-lane workgroup per row (grid = rows; row = s * n_frames + j reads in + s * stream_pitch + j * frame_pitch and writes out[row]).
+// Rows are powers of two >= 2048 floats and 16-byte aligned (as the DB_F32 gather relies on): float4 loads, bins / 1024 per lane.  Each
+// lane keeps a double sum and a double peak; xor-shuffle tree inside the wave, then the four waves' values through LDS, added in wave
+// order by lane 0 -- no atomics, one fixed order, the same bits on every run.  Lane 0 finishes the integer rule.  A 65536-bin row is
+// 256 KiB for one workgroup: the kernel runs when a recalc is pending or the pull function asks, never per call.
+static __global__ __launch_bounds__(256) void k_scale_stats(const float *__restrict__ in, long long stream_pitch, long long frame_pitch, int n_frames,
+                                                            int bins, ScaleEntry *__restrict__ out)
+{
+#pragma clang fp contract(off)
+    const long long row = blockIdx.x;
+    const long long s = row / n_frames, j = row - s * n_frames;
+    const float4 *x = reinterpret_cast<const float4 *>(in + s * stream_pitch + j * frame_pitch);
+    double sum = 0.0, peak = 0.0;
+    for (int k = (int)threadIdx.x; k < bins / 4; k += 256) {
+        const float4 v = x[k];
+        const double p0 = exp10((double)v.x / 10.0), p1 = exp10((double)v.y / 10.0), p2 = exp10((double)v.z / 10.0), p3 = exp10((double)v.w / 10.0);
+        sum += p0; sum += p1; sum += p2; sum += p3;
+        if (p0 > peak) peak = p0;
+        if (p1 > peak) peak = p1;
+        if (p2 > peak) peak = p2;
+        if (p3 > peak) peak = p3;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        sum += __shfl_xor(sum, m, 64);
+        const double o = __shfl_xor(peak, m, 64);
+        if (o > peak) peak = o;
+    }
+    __shared__ double w_sum[4], w_peak[4];
+    if ((threadIdx.x & 63) == 0) {
+        w_sum[threadIdx.x >> 6] = sum;
+        w_peak[threadIdx.x >> 6] = peak;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = w_sum[0], pk = w_peak[0];
+        for (int w = 1; w < 4; w++) {
+            total += w_sum[w];
+            if (w_peak[w] > pk) pk = w_peak[w];
+        }
+        out[row] = auto_scale_finish(total, pk, bins);
+    }
+}
+// the launch; rows = n_streams x n_frames
+int run_scale_stats(hipStream_t s, const float *in, long long stream_pitch, long long frame_pitch, int n_streams, int n_frames, int bins, ScaleEntry *out);
+// the host twin of one row, serial as the reference (no device)
+ScaleEntry auto_scale_row(const float *db, uint32_t bins);
+// the refusals a flag word shares: unknown bits; MAX alone against a fixed min_db >= -50 / MIN alone against a fixed max_db <= -70 (a range
+// that could come out empty or upside down: the reference would divide by zero or flip the plot)
+int check_auto_scale(uint32_t flags, double fixed_max_db, double fixed_min_db);
+
+// A ring's ranges on the device: tab[stream] is the stream's range as the last recalc left it; `use` (the AUTO_SCALE bits whose end of the
+// range has been computed since the flag went on) says which ends the packing kernel takes from it, the others stay the pane's map's.
+// Carried by value in the packing launch: flags never wait for earlier calls.  use == 0: the kernels run exactly as without the table.
+struct ScaleUse {
+    const ScaleEntry *tab = nullptr;
+    uint32_t use = 0;
+    uint32_t refreshed = 0;           // this call's launch was preceded by the recalc: the trailer carries avg_power / peak_power
+    ScaleEntry *trailer = nullptr;    // [n_trailer] the ranges used, per selected stream (nullptr: none)
+    uint32_t n_trailer = 0;
+    double fixed_max = 0, fixed_min = 0;  // the trailer's pane's own range
+};
+// max_db / y_scale of a row whose range is stream `src`'s
+__device__ inline void scale_row_shared(const ScaleUse &u, uint32_t src, double fixed_min, MapShared *sh)
+{
+    const ScaleEntry e = u.tab[src];
+    const double mx = (u.use & 1u) ? (double)e.max_db : sh->max_db, mn = (u.use & 2u) ? (double)e.min_db : fixed_min;
+    sh->max_db = mx;
+    sh->y_scale = map_y_scale(sh->y_pixels, mx, mn);
+}
+__device__ inline void scale_write_trailer(const ScaleUse &u, uint32_t r, uint32_t src)
+{
+    const ScaleEntry e = u.tab[src];
+    ScaleEntry o;
+    o.max_db = (u.use & 1u) ? e.max_db : (int32_t)u.fixed_max;
+    o.min_db = (u.use & 2u) ? e.min_db : (int32_t)u.fixed_min;
+    o.avg_power = u.refreshed ? e.avg_power : 0.0;
+    o.peak_power = u.refreshed ? e.peak_power : 0.0;
+    u.trailer[r] = o;
+}
+
 // ---- the waterfall's colours ----
 // SpectrumWidget's palette (application/spectrumwidget.cpp:97-113), the constructor's loop in its own integer arithmetic, entry i as
 // QColor::setRgb(r, g, b) leaves it: alpha 255, QRgb layout 0xFFRRGGBB.  The reference allocates 255 entries, writes entry 255 and
@@ -171,11 +283,13 @@ struct DisplayPack {
     int group = 1;                   // the lane group run_screen_map picks for geom
     MapGeom geom;
     MapShared sh;                    // (DB_F32: fft_size only)
+    double min_db = 0;               // the map's lower end (auto-scale with one flag on)
 };
 // fills everything but n_streams and d_tab from the format and (mapped formats) the checked map
 void display_pack_plan(DisplayPack *p, int32_t bins, double sample_rate, const ::pebblegpu_screen_map *map);
 // rows first_row .. first_row + n_rows - 1 of spec ([stream][pitch_rows][bins]) -> dst [selected][n_rows][row_pitch_bytes]; one launch
-int run_display_pack(hipStream_t s, const DisplayPack &p, const float *spec, long long pitch_rows, int first_row, int n_rows, void *dst);
+// su: the ring's ranges (ScaleUse{}: none, the launch as without auto-scale)
+int run_display_pack(hipStream_t s, const DisplayPack &p, const float *spec, long long pitch_rows, int first_row, int n_rows, void *dst, const ScaleUse &su = ScaleUse{});
 int waterfall_colors(const int32_t *pixels, uint64_t n, uint32_t *argb);
 
 // Rows first_row .. first_row + n_rows - 1 of the selected streams of a compact spectrum buffer ([stream][pitch_rows][bins] float dB,
@@ -187,18 +301,45 @@ template <int G, bool ARGB>
 static __global__ __launch_bounds__(256) void k_display_map(const float *__restrict__ in, long long stream_pitch, long long frame_pitch, int first_row,
                                                             int n_rows, long long n_items, MapGeom g, MapShared sh, const uint32_t *__restrict__ tab,
                                                             unsigned char *__restrict__ out, unsigned long long out_row_pitch,
-                                                            unsigned long long out_stream_pitch)
+                                                            unsigned long long out_stream_pitch, ScaleUse su)
 {
 #pragma clang fp contract(off)
     constexpr int kGroups = 256 / G;
     const int lane = (int)threadIdx.x % G;
     const long long stride = (long long)gridDim.x * kGroups;
-    for (long long item = (long long)blockIdx.x * kGroups + (int)threadIdx.x / G; item < n_items; item += stride) {
+    // auto-scale: stream tab[r]'s range from the ring's table; the ranges used go into the slot's trailer (first workgroup).  The range of
+    // a row -- a table read and a double division -- is made once per row a workgroup's kGroups consecutive items touch (at most kGroups
+    // rows), by its first lanes, and handed to the items through LDS; su is uniform, so are the barriers
+    __shared__ float row_y_scale[kGroups];
+    __shared__ double row_max_db[kGroups];
+    if (su.trailer && blockIdx.x == 0)
+        for (uint32_t r = threadIdx.x; r < su.n_trailer; r += 256) scale_write_trailer(su, r, tab[r]);
+    for (long long base = (long long)blockIdx.x * kGroups; base < n_items; base += stride) {
+        const long long item = base + (int)threadIdx.x / G;
+        const long long row0 = base / sh.x_pixels;
+        if (su.use) {
+            const long long last = base + kGroups - 1 < n_items ? base + kGroups - 1 : n_items - 1;
+            const int rows_here = (int)(last / sh.x_pixels - row0) + 1;
+            __syncthreads();  // (the previous round's readers)
+            if ((int)threadIdx.x < rows_here) {
+                MapShared t = sh;
+                scale_row_shared(su, tab[(row0 + (int)threadIdx.x) / n_rows], su.fixed_min, &t);
+                row_y_scale[threadIdx.x] = t.y_scale;
+                row_max_db[threadIdx.x] = t.max_db;
+            }
+            __syncthreads();
+        }
+        if (item >= n_items) continue;
         const long long row = item / sh.x_pixels;
         const int32_t i = (int32_t)(item - row * sh.x_pixels);
         const int r = (int)(row / n_rows), j = (int)(row - (long long)r * n_rows);
         const float *x = in + (long long)tab[r] * stream_pitch + (long long)(first_row + j) * frame_pitch;
-        const int32_t y = map_y(sh.y_scale, map_power_db<G>(x, g, sh, i, lane), sh.y_pixels);
+        MapShared rs = sh;
+        if (su.use) {
+            rs.y_scale = row_y_scale[row - row0];
+            rs.max_db = row_max_db[row - row0];
+        }
+        const int32_t y = map_y(rs.y_scale, map_power_db<G>(x, g, rs, i, lane), rs.y_pixels);
         if (lane == 0) {
             unsigned char *o = out + (unsigned long long)r * out_stream_pitch + (unsigned long long)j * out_row_pitch;
             if (ARGB) reinterpret_cast<uint32_t *>(o)[i] = waterfall_color(y);
@@ -216,7 +357,8 @@ struct DisplayRow {
     MapGeom geom;
     uint32_t src;    // the stream / channel of this block row
     int32_t group;   // lanes per pixel, a power of two <= 64
-    uint32_t pad_[2];
+    uint32_t scale_src;  // auto-scale: the stream whose range maps this row (a zoomed row: its channel's stream, 0 off a shared input)
+    uint32_t pad_;
 };
 // one pane of one call, by value
 struct DisplayPaneArgs {
@@ -230,6 +372,7 @@ struct DisplayPaneArgs {
     MapShared sh;
     unsigned char *out;              // [selected][n_rows][out_row_pitch bytes]
     unsigned long long out_row_pitch;
+    double min_db;                   // the pane's own lower end (auto-scale with one flag: the other end stays the pane's)
 };
 
 template <int G>
@@ -250,8 +393,12 @@ __device__ inline void display_map_row(const float *__restrict__ x, const MapGeo
 // grid (x, rows, panes): a workgroup takes whole block rows (strided over grid.y), so the row's lane group is uniform in it.  DB_F32 is
 // k_display_rows' 16-byte gather (rows are powers of two >= 2048 floats: 16-byte aligned on both sides); the mapped formats run
 // map_power_db<G> / map_y / waterfall_color, the one computation of k_screen_map and k_display_map.
-static __global__ __launch_bounds__(256) void k_display_panes(DisplayPaneArgs p0, DisplayPaneArgs p1)
+// su (auto-scale, ScaleUse): use != 0 takes each mapped row's range from the ring's table, once per row; the workgroup (0, 0, 0) copies
+// the ranges used into the slot's trailer (trailer_tab: the table of the pane the trailer speaks for).  DB_F32 panes ignore the range.
+static __global__ __launch_bounds__(256) void k_display_panes(DisplayPaneArgs p0, DisplayPaneArgs p1, ScaleUse su, const DisplayRow *__restrict__ trailer_tab)
 {
+    if (su.trailer && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
+        for (uint32_t r = threadIdx.x; r < su.n_trailer; r += 256) scale_write_trailer(su, r, trailer_tab[r].scale_src);
     const DisplayPaneArgs &p = blockIdx.z ? p1 : p0;
     if (blockIdx.x >= p.x_blocks) return;
     for (long long row = blockIdx.y; row < p.total_rows; row += gridDim.y) {
@@ -266,14 +413,16 @@ static __global__ __launch_bounds__(256) void k_display_panes(DisplayPaneArgs p0
             continue;
         }
         const bool argb = p.format == 2;  // PEBBLEGPU_DISPLAY_WATERFALL_ARGB32
+        MapShared sh = p.sh;
+        if (su.use) scale_row_shared(su, e.scale_src, p.min_db, &sh);
         switch (e.group) {
-        case 1: display_map_row<1>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
-        case 2: display_map_row<2>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
-        case 4: display_map_row<4>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
-        case 8: display_map_row<8>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
-        case 16: display_map_row<16>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
-        case 32: display_map_row<32>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
-        default: display_map_row<64>(x, e.geom, p.sh, argb, o, p.x_blocks); break;
+        case 1: display_map_row<1>(x, e.geom, sh, argb, o, p.x_blocks); break;
+        case 2: display_map_row<2>(x, e.geom, sh, argb, o, p.x_blocks); break;
+        case 4: display_map_row<4>(x, e.geom, sh, argb, o, p.x_blocks); break;
+        case 8: display_map_row<8>(x, e.geom, sh, argb, o, p.x_blocks); break;
+        case 16: display_map_row<16>(x, e.geom, sh, argb, o, p.x_blocks); break;
+        case 32: display_map_row<32>(x, e.geom, sh, argb, o, p.x_blocks); break;
+        default: display_map_row<64>(x, e.geom, sh, argb, o, p.x_blocks); break;
         }
     }
 }
@@ -282,6 +431,7 @@ static __global__ __launch_bounds__(256) void k_display_panes(DisplayPaneArgs p0
 // (per_stream), one for all otherwise.  geoms / groups: n_streams entries each
 void map_row_plan(int32_t fft_size, double sample_rate, const int32_t *edges, bool per_stream, int n_streams, int32_t x_pixels, MapGeom *geoms, int *groups);
 // up to two panes in one launch on `s` (n_panes 1 or 2; a pane of 0 rows is left out, none left: no launch)
-int run_display_panes(hipStream_t s, const DisplayPaneArgs *panes, int n_panes);
+// su / trailer_tab (auto-scale): the ranges' table and where the launch's first workgroup writes the trailer
+int run_display_panes(hipStream_t s, const DisplayPaneArgs *panes, int n_panes, const ScaleUse &su = ScaleUse{}, const DisplayRow *trailer_tab = nullptr);
 
 }  // namespace pg

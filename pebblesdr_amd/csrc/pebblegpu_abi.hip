@@ -490,6 +490,26 @@ int pebblegpu_receiver_display_set_pane(pebblegpu_receiver *h, uint32_t pane, co
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
     return h->rx.display_set_pane(pane, geometry);
 }
+int pebblegpu_receiver_spectrum_scale(pebblegpu_receiver *h, uint32_t first_frame, uint32_t n_frames, uint32_t frame_step, pebblegpu_display_scale *d_out)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.spectrum_scale(first_frame, n_frames, frame_step, d_out);
+}
+int pebblegpu_receiver_display_set_auto_scale(pebblegpu_receiver *h, uint32_t flags)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.display_set_auto_scale(flags);
+}
+int pebblegpu_receiver_display_rescale(pebblegpu_receiver *h)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.display_rescale();
+}
+int pebblegpu_receiver_display_scale(pebblegpu_receiver *h, uint64_t call_index, pebblegpu_display_scale *out, uint32_t cap, uint32_t *n)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.display_scale(call_index, out, cap, n);
+}
 int pebblegpu_iq_record_convert(const float *iq, uint64_t n, int16_t *out)
 {
     if (n && (!iq || !out)) return fail(PEBBLEGPU_E_INVALID, "null argument");

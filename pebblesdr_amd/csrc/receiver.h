@@ -711,6 +711,13 @@ public:
     int display_next(int wait, pebblegpu_display_block *blocks);
     int display_release(uint64_t call_index);
     int display_dropped(uint64_t *blocks);
+    // SpectrumWidget's auto-scale (recalcScale, spectrumwidget.cpp:693-734; kernels_display.h): the pull function -- the scale of frames
+    // first + j * step of the last call's unprocessed spectrum, d_out [stream][n], queued where map_spectrum queues -- and the ring's
+    // flags: host state consumed when the next call is queued, never a wait
+    int spectrum_scale(uint32_t first, uint32_t n, uint32_t step, pebblegpu_display_scale *d_out);
+    int display_set_auto_scale(uint32_t flags);
+    int display_rescale();
+    int display_scale(uint64_t call_index, pebblegpu_display_scale *out, uint32_t cap, uint32_t *n);
     int sync();
     int close_timing();  // records the end event a side-by-side call left out (no-op otherwise)
     const char *kernel_name(int which) const;  // the kernels behind pebblegpu_receiver_last_ms's groups, as last run
@@ -884,7 +891,8 @@ private:
     struct DisplayRing *disp_ = nullptr;  // allocated at the first open, kept until the receiver goes (a reader may hold it)
     bool disp_open_ = false;          // (under mu_: what a process call looks at)
     int upload_display_tables();
-    int queue_display_block(hipStream_t spec_s, uint64_t spec_rows, hipStream_t zoom_s, uint64_t zoom_rows);
+    int queue_display_block(hipStream_t spec_s, uint64_t spec_rows, hipStream_t zoom_s, uint64_t zoom_rows, bool rescale);
+    bool display_scale_pending() const;  // the ring is open with an auto-scale flag on and a recalc requested (CallFacts::scale_pending)
     void display_destroy();
 };
 

@@ -593,6 +593,7 @@ CallFacts Receiver::call_facts(uint64_t n, bool with_spectrum, bool with_chain, 
     f.taps = taps_ != 0;
     f.recording = rec_.open;
     f.ch0_tune_only = ctl_[0].mode == PEBBLEGPU_DM_NONE;
+    f.scale_pending = display_scale_pending();
     f.dec_lds_free_front = dec_.front_is_lds_free();
     f.dec_raw_front = dec_.raw_front();
     f.dec_double_out = dec_.double_out();
@@ -1027,7 +1028,7 @@ int Receiver::end_call(Call &c)
             joined = true;
             spec_s = cs;
         }
-        if (int rc = queue_display_block(spec_s, c.disp_spec_rows, cs, c.disp_zoom_rows)) return rc;
+        if (int rc = queue_display_block(spec_s, c.disp_spec_rows, cs, c.disp_zoom_rows, rt.rescale)) return rc;
     }
     if (!rt.bank_pipe) d_end_prev_ = nullptr;
     if (rt.bank_pipe) {

@@ -36,6 +36,12 @@ struct pebblegpu_streambank {
     int iq_fmt = 0;
     pg::DisplayPack disp;            // format, selection table, plot geometry of the display ring
     uint32_t disp_max_rows = 0;
+    // the display ring's auto-scale (SpectrumWidget::recalcScale, kernels_display.h): host flags consumed when the next call is queued
+    uint32_t scale_flags = 0, scale_live = 0;  // PEBBLEGPU_AUTO_SCALE_* as last set; those whose end a recalc has computed since
+    bool scale_pending = false;      // m_scaleNeedsRecalc
+    pg::ScaleEntry *d_scale = nullptr;  // [n_streams] the ranges (allocated with the ring)
+    uint64_t trailer_bytes = 0;      // per slot, behind the rows
+    bool slot_scaled[pg::kEgressMaxSlots] = {};  // the slot's block carries a trailer
 };
 
 constexpr uint64_t kMaxRingBytes = 1ull << 30;  // pinned host memory one ring may hold, all slots together
@@ -61,9 +67,9 @@ static int sb_selection(const pebblegpu_streambank *sb, const uint32_t *streams,
 
 // allocates the ring and the selection's table; on failure everything it made is freed again and the handle is as it was
 static int sb_open_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, uint32_t **d_tab, const std::vector<uint32_t> &sel, uint32_t n_slots, uint32_t bps,
-                        uint64_t max_n, uint32_t fmt)
+                        uint64_t max_n, uint32_t fmt, uint64_t extra_bytes = 0)
 {
-    const uint64_t slot = (uint64_t)sel.size() * pg::EgressRing::row_pitch(max_n, bps);
+    const uint64_t slot = (uint64_t)sel.size() * pg::EgressRing::row_pitch(max_n, bps) + extra_bytes;
     if (slot * n_slots > kMaxRingBytes)
         return fail(PEBBLEGPU_E_SIZE, "%u slots of %llu bytes: a ring pins at most %llu bytes of host memory", n_slots, (unsigned long long)slot,
                     (unsigned long long)kMaxRingBytes);
@@ -71,7 +77,7 @@ static int sb_open_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, uint32_t
     auto body = [&]() -> int {
         PG_HIP(hipMalloc((void **)d_tab, sizeof(uint32_t) * sel.size()));
         PG_HIP(hipMemcpy(*d_tab, sel.data(), sizeof(uint32_t) * sel.size(), hipMemcpyHostToDevice));
-        if (int rc = ring.open_ring(n_slots, (uint32_t)sel.size(), bps, max_n, fmt)) return rc;
+        if (int rc = ring.open_ring(n_slots, (uint32_t)sel.size(), bps, max_n, fmt, extra_bytes)) return rc;
         for (uint32_t i = 0; i < n_slots; i++) PG_HIP(hipMemset(ring.slot[i].d, 0, ring.slot_bytes));  // (the padding of a row is never written)
         return 0;
     };
@@ -112,12 +118,34 @@ static int sb_queue_blocks(pebblegpu_streambank *sb, uint64_t n, uint32_t what)
         }
     }
     if (sb->disp_ring.open) {
+        // SpectrumWidget::recalcScale on this call's first computed row of every stream; a call that computed none leaves the request
+        // pending.  Delivered or dropped: what later blocks look like never depends on the reader.  One stream orders everything
+        const bool recalc = sb->scale_flags && sb->scale_pending && n && sb->last_frames;
+        if (recalc) {
+            const long long bins = sb->sp.bins;
+            if (int rc = pg::run_scale_stats(sb->stream, sb->d_spec, (long long)sb->last_frames * bins, 0, (int)sb->cfg.n_streams, 1, (int)bins, sb->d_scale)) return rc;
+            sb->scale_live = sb->scale_flags;
+            sb->scale_pending = false;
+        }
         if (pg::EgressSlot *g = sb->disp_ring.begin()) {
             // the rows THIS call computed (under a gate d_spec is compact: last_frames rows per stream); the last max_rows of them
             const uint64_t computed = n ? sb->last_frames : 0, k = std::min<uint64_t>(computed, sb->disp_max_rows), first = computed - k;
-            if (int rc = pg::run_display_pack(sb->stream, sb->disp, sb->d_spec, (long long)computed, (int)first, (int)k, g->d)) return rc;
+            // auto-scale: the ranges by value in the launch, the ranges used into a trailer behind the rows (inside the one copy)
+            pg::ScaleUse su;
+            const uint64_t samples = k * (sb->disp.row_pitch_bytes / 4);  // (a "sample" is 4 bytes of a row)
+            if (sb->scale_flags && k) {  // (a block without rows stays what it was: nothing queued, no trailer)
+                su.tab = sb->d_scale;
+                su.use = sb->scale_flags & sb->scale_live;
+                su.refreshed = recalc ? 1u : 0u;
+                su.trailer = reinterpret_cast<pg::ScaleEntry *>((unsigned char *)g->d + sb->disp_ring.rows * pg::EgressRing::row_pitch(samples, 4));
+                su.n_trailer = sb->disp_ring.rows;
+                su.fixed_max = sb->disp.sh.max_db;
+                su.fixed_min = sb->disp.min_db;
+            }
+            sb->slot_scaled[g - sb->disp_ring.slot] = su.trailer != nullptr;
+            if (int rc = pg::run_display_pack(sb->stream, sb->disp, sb->d_spec, (long long)computed, (int)first, (int)k, g->d, su)) return rc;
             g->aux = (uint32_t)first;
-            if (int rc = sb->disp_ring.commit(g, sb->stream, k * (sb->disp.row_pitch_bytes / 4))) return rc;  // (a "sample" is 4 bytes of a row)
+            if (int rc = sb->disp_ring.commit(g, sb->stream, samples, su.trailer ? sb->trailer_bytes : 0)) return rc;
         }
     }
     return 0;
@@ -148,7 +176,7 @@ int pebblegpu_streambank_destroy(pebblegpu_streambank *sb)
     sb->ff.release();
     sb->sp.release();
     sb->ingest.release();
-    void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec, sb->d_raw_stage, sb->d_iq_tab, sb->disp.d_tab};
+    void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec, sb->d_raw_stage, sb->d_iq_tab, sb->disp.d_tab, sb->d_scale};
     for (void *q : p) if (q) (void)hipFree(q);
     for (hipEvent_t e : sb->ev) if (e) (void)hipEventDestroy(e);
     delete sb;
@@ -531,9 +559,19 @@ int pebblegpu_streambank_display_open(pebblegpu_streambank *sb, int format, cons
     plan.n_streams = (uint32_t)sel.size();
     pg::display_pack_plan(&plan, (int32_t)sb->sp.bins, sb->cfg.sample_rate, map);
     const uint32_t rows = max_rows && max_rows < sb->cfg.max_frames ? max_rows : sb->cfg.max_frames;  // (no call computes more than max_frames)
-    if (int rc = sb_open_ring(sb, sb->disp_ring, &plan.d_tab, sel, n_slots, 4, (uint64_t)rows * (plan.row_pitch_bytes / 4), (uint32_t)format)) return rc;
+    // (room behind the rows for the auto-scale trailer, and the ranges' table: one entry per stream of the bank)
+    const uint64_t trailer = ((uint64_t)sel.size() * sizeof(pg::ScaleEntry) + 15) & ~(uint64_t)15;
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    if (!sb->d_scale) {
+        PG_HIP(hipMalloc((void **)&sb->d_scale, sizeof(pg::ScaleEntry) * sb->cfg.n_streams));
+        PG_HIP(hipMemset(sb->d_scale, 0, sizeof(pg::ScaleEntry) * sb->cfg.n_streams));
+    }
+    if (int rc = sb_open_ring(sb, sb->disp_ring, &plan.d_tab, sel, n_slots, 4, (uint64_t)rows * (plan.row_pitch_bytes / 4), (uint32_t)format, trailer)) return rc;
     sb->disp = plan;
     sb->disp_max_rows = rows;
+    sb->trailer_bytes = trailer;
+    sb->scale_flags = sb->scale_live = 0;
+    sb->scale_pending = false;
     return 0;
 }
 int pebblegpu_streambank_display_close(pebblegpu_streambank *sb)
@@ -572,6 +610,74 @@ int pebblegpu_streambank_display_dropped(const pebblegpu_streambank *sb, uint64_
 {
     if (!sb || !blocks) return fail(PEBBLEGPU_E_INVALID, "null argument");
     return sb_dropped(const_cast<pebblegpu_streambank *>(sb)->disp_ring, blocks);
+}
+int pebblegpu_auto_scale_row(const float *db, uint32_t bins, pebblegpu_display_scale *out)
+{
+    if (!db || !out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (!bins) return fail(PEBBLEGPU_E_INVALID, "a row of 0 bins");
+    const pg::ScaleEntry e = pg::auto_scale_row(db, bins);
+    out->max_db = e.max_db;
+    out->min_db = e.min_db;
+    out->avg_power = e.avg_power;
+    out->peak_power = e.peak_power;
+    return 0;
+}
+int pebblegpu_streambank_spectrum_scale(pebblegpu_streambank *sb, uint32_t first_frame, uint32_t n_frames, uint32_t frame_step, pebblegpu_display_scale *d_out)
+{
+    if (!sb || !d_out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    // (the frame rules of pebblegpu_streambank_map_spectrum, the latest row after a gated call that selected nothing included)
+    const bool latest = !sb->last_frames && sb->last_sp && sb->last_listed && sb->spec_rows;
+    const uint64_t rows = latest ? 1 : sb->last_frames, pitch_rows = latest ? sb->spec_rows : sb->last_frames;
+    if (!rows) return fail(PEBBLEGPU_E_INVALID, "the last call computed no spectrum (or no call has been made yet)");
+    if (n_frames == 0 || (uint64_t)first_frame + (uint64_t)(n_frames - 1) * frame_step >= rows)
+        return fail(PEBBLEGPU_E_INVALID, "frames %u + j * %u, j < %u, are not all within the last call's %llu", first_frame, frame_step, n_frames,
+                    (unsigned long long)rows);
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    const long long bins = sb->sp.bins;
+    if (latest) first_frame = (uint32_t)(sb->spec_rows - 1);
+    return pg::run_scale_stats(sb->stream, sb->d_spec + (long long)first_frame * bins, (long long)pitch_rows * bins, (long long)frame_step * bins,
+                               (int)sb->cfg.n_streams, (int)n_frames, (int)bins, reinterpret_cast<pg::ScaleEntry *>(d_out));
+}
+int pebblegpu_streambank_display_set_auto_scale(pebblegpu_streambank *sb, uint32_t flags)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (!sb->disp_ring.open) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    if (int rc = pg::check_auto_scale(flags, 0.0, -120.0)) return rc;  // (the flag bits)
+    if (sb->disp.format == PEBBLEGPU_DISPLAY_DB_F32) return fail(PEBBLEGPU_E_INVALID, "a DB_F32 ring maps nothing: there is no range to scale");
+    if (int rc = pg::check_auto_scale(flags, sb->disp.sh.max_db, sb->disp.min_db)) return rc;
+    if (int rc = pg::check_auto_scale(flags & sb->scale_live, sb->disp.sh.max_db, sb->disp.min_db)) return rc;  // (the ends the table supplies until the recalc lands)
+    if (flags & ~sb->scale_flags) sb->scale_pending = true;  // "Auto" chosen: m_scaleNeedsRecalc = true (spectrumwidget.cpp:942, :960)
+    sb->scale_live &= flags;                                 // a flag that goes off returns its end to the map (m_plotMaxDb = db)
+    sb->scale_flags = flags;
+    if (!flags) sb->scale_pending = false;
+    return 0;
+}
+int pebblegpu_streambank_display_rescale(pebblegpu_streambank *sb)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (!sb->disp_ring.open) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    sb->scale_pending = sb->scale_flags != 0;  // (recalcScale returns at once with neither flag on)
+    return 0;
+}
+int pebblegpu_streambank_display_scale(pebblegpu_streambank *sb, uint64_t call_index, pebblegpu_display_scale *out, uint32_t cap, uint32_t *n)
+{
+    if (!sb || !n) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    *n = 0;
+    pg::EgressRing &ring = sb->disp_ring;
+    std::lock_guard<std::mutex> lk(ring.mu);
+    if (!ring.open) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
+    for (uint64_t q = ring.tail; q < ring.read; q++) {
+        const uint32_t si = (uint32_t)(q % ring.n_slots);
+        const pg::EgressSlot &g = ring.slot[si];
+        if (g.call != call_index) continue;
+        if (!sb->slot_scaled[si]) return fail(PEBBLEGPU_E_INVALID, "the block of call %llu carries no ranges: no auto-scale flag was on when it was queued, or it has no rows", (unsigned long long)call_index);
+        if (ring.rows > cap) return fail(PEBBLEGPU_E_SIZE, "%u ranges do not fit %u entries", ring.rows, cap);
+        if (!out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+        memcpy(out, (const unsigned char *)g.h + ring.rows * g.pitch_bytes, sizeof(pebblegpu_display_scale) * ring.rows);
+        *n = ring.rows;
+        return 0;
+    }
+    return fail(PEBBLEGPU_E_INVALID, "call %llu is not handed out", (unsigned long long)call_index);
 }
 int pebblegpu_waterfall_colors(const int32_t *pixels, uint64_t n, uint32_t *argb)
 {

@@ -2,7 +2,7 @@
 pebblegpu_streambank_display_*) beside the only way there was before them.  Not the bench line (bench.py measures configs[1]); the
 figures go into profiles/streambank_egress.json, DESIGN.md section 5 and the README.
 
-    bench_streambank_egress.py [--calls 100] [--repeats 5] [--streams 128] [--frames 4] [--out profiles/streambank_egress.json]
+    bench_streambank_egress.py [--calls 100] [--repeats 5] [--streams 128] [--frames 4] [--only PREFIX,...] [--out profiles/streambank_egress.json]
 
 Shape: a BASELINE configs[4] shard -- 128 streams x 4 frames of 65536 samples per call, 65536 bins, int8 pairs fed through the pinned
 ingest slots.  One process, one device visit.  The variants run alternately, --repeats times each; one measurement is a host clock
@@ -15,6 +15,11 @@ around --calls calls ending in a synchronise, after a warm-up:
                  memcpy_d2h of the pixels
     B_f32, B_s16 the IQ ring, 8 streams selected, 4 slots; the host takes and releases the block of the call 3 calls back
     C_pixels, C_waterfall   the display ring over all streams, max_rows = 1, 1024 pixels
+    C_waterfall_auto        the same with pebblegpu_streambank_display_set_auto_scale(MAX | MIN), the recalc done in the warm-up: every
+                            stream's row mapped with its own range from the table
+    C_waterfall_auto_rescale  ... and pebblegpu_streambank_display_rescale() before EVERY call: k_scale_stats over 128 rows of 65536 bins
+                            in each call
+--only runs the variants whose names start with one of the prefixes (the auto-scale figures: --only D,C_display_ring_waterfall).
 
 Reported per variant: ms per call (median over the repeats, and their min / max), bytes per call, for the rings bytes per call over ms
 per call in GB/s, the host's own time per call inside the process calls and inside next + release, and pebblegpu_streambank_last_ms
@@ -40,6 +45,7 @@ ap.add_argument("--calls", type=int, default=100)
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--streams", type=int, default=128)
 ap.add_argument("--frames", type=int, default=4)
+ap.add_argument("--only", default="")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 FS, S, F, N65, SLOTS, XP = 200e6, args.streams, args.frames, 65536, 4, 1024
@@ -115,7 +121,7 @@ def variant_a_pixels():
     return timed(body)
 
 
-def variant_ring(open_, close, nxt, release, dropped, blk):
+def variant_ring(open_, close, nxt, release, dropped, blk, pre=None):
     open_()
     queued = {"n": 0}
 
@@ -127,6 +133,8 @@ def variant_ring(open_, close, nxt, release, dropped, blk):
         state["take_s"] += time.perf_counter() - t
 
     def body():
+        if pre:
+            pre()
         call()
         queued["n"] += 1
         if queued["n"] > SLOTS - 1:  # lagging by SLOTS - 1 calls
@@ -153,21 +161,30 @@ def iq_ring(fmt):
                         L.pebblegpu_streambank_iq_out_release, sb.iq_out_dropped, ablk)
 
 
-def display_ring(fmt):
-    return variant_ring(lambda: sb.display_open(fmt, screen, None, 1, SLOTS), sb.display_close, L.pebblegpu_streambank_display_next,
-                        L.pebblegpu_streambank_display_release, sb.display_dropped, dblk)
+def display_ring(fmt, flags=0, rescale=False):
+    def open_():
+        sb.display_open(fmt, screen, None, 1, SLOTS)
+        if flags:
+            sb.display_set_auto_scale(flags)
+    return variant_ring(open_, sb.display_close, L.pebblegpu_streambank_display_next, L.pebblegpu_streambank_display_release, sb.display_dropped, dblk,
+                        sb.display_rescale if rescale else None)
 
 
 variants = {"D_calls_alone": lambda: timed(call), "A_iq_sync_memcpy_d2h": variant_a_iq, "A_pixels_map_sync_memcpy_d2h": variant_a_pixels,
             "B_iq_ring_f32": lambda: iq_ring(P.AUDIO_F32), "B_iq_ring_s16": lambda: iq_ring(P.AUDIO_S16),
-            "C_display_ring_pixels": lambda: display_ring(P.DISPLAY_PIXELS_I32), "C_display_ring_waterfall": lambda: display_ring(P.DISPLAY_WATERFALL_ARGB32)}
+            "C_display_ring_pixels": lambda: display_ring(P.DISPLAY_PIXELS_I32), "C_display_ring_waterfall": lambda: display_ring(P.DISPLAY_WATERFALL_ARGB32),
+            "C_display_ring_waterfall_auto": lambda: display_ring(P.DISPLAY_WATERFALL_ARGB32, 3),
+            "C_display_ring_waterfall_auto_rescale": lambda: display_ring(P.DISPLAY_WATERFALL_ARGB32, 3, True)}
+if args.only:
+    variants = {v: fn for v, fn in variants.items() if v.startswith(tuple(args.only.split(",")))}
 ms = {v: [] for v in variants}
 for _ in range(args.repeats):  # alternating: what drifts during the run drifts for all of them
     for v, fn in variants.items():
         state["variant"] = v
         ms[v].append(fn())
 nbytes = {"D_calls_alone": 0, "A_iq_sync_memcpy_d2h": rows_host.nbytes, "A_pixels_map_sync_memcpy_d2h": px_host.nbytes,
-          "B_iq_ring_f32": len(SEL) * n * 8, "B_iq_ring_s16": len(SEL) * n * 4, "C_display_ring_pixels": S * XP * 4, "C_display_ring_waterfall": S * XP * 4}
+          "B_iq_ring_f32": len(SEL) * n * 8, "B_iq_ring_s16": len(SEL) * n * 4, "C_display_ring_pixels": S * XP * 4, "C_display_ring_waterfall": S * XP * 4,
+          "C_display_ring_waterfall_auto": S * XP * 4 + S * 24, "C_display_ring_waterfall_auto_rescale": S * XP * 4 + S * 24}
 result = {
     "workload": "configs[4] shard: %d streams x %d frames of 65536 (65536 bins), int8 pairs through the ingest slots; %d calls per measurement, %d repeats, "
                 "variants alternating" % (S, F, args.calls, args.repeats),
