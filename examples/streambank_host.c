@@ -5,6 +5,8 @@
  * two threads talk through two counters on the host: the reader asks for block k once call k has been queued (_next returns no
  * block, rather than waiting, while no call has queued one), and the producer stays at most N_SLOTS calls ahead of the reader, so
  * nothing is dropped (a host that would rather lose a line than wait leaves that out and reads dropped_before).
+ * The two recorded streams carry a squelch threshold each; the S-meter runs on the device and every IQ block brings, in a trailer inside
+ * its one copy, the values and the decision per (stream, frame): the reader prints which streams were open and would skip closed frames.
  * Exit status 0 on success; otherwise the failing call and pebblegpu_last_error() on stderr.
  * Build: gcc -O2 -Wall -pthread -Iinclude examples/streambank_host.c -Lpebblesdr_amd -lpebblegpu -Wl,-rpath,$PWD/pebblesdr_amd -lm */
 #include <math.h>
@@ -29,6 +31,7 @@ static int taken = 0;       /* calls whose two blocks the reader has released */
 static int reader_rc = 0;
 static uint32_t iq_sum = 0, line_sum = 0;
 static uint64_t iq_samples = 0, lines = 0;
+static const uint32_t recorded[2] = {5, 2};                  /* row 0 of every IQ block is stream 5, row 1 stream 2 */
 
 static int read_call(uint64_t call)
 {
@@ -45,6 +48,17 @@ static int read_call(uint64_t call)
         for (uint64_t i = 0; i < 2 * a.samples_per_channel; i++) iq_sum = iq_sum * 31u + (uint16_t)row[i];
     }
     iq_samples += a.samples_per_channel;
+    pebblegpu_stream_gate gate[2 * FRAMES_PER_CALL];         /* entry r * frames + j: selected stream r, frame j of the call */
+    uint32_t frames = 0;
+    CHECK(pebblegpu_streambank_iq_out_gate(sb, a.call_index, gate, 2 * FRAMES_PER_CALL, &frames));
+    printf("block %llu:", (unsigned long long)call);
+    for (uint32_t r = 0; r < a.n_channels && frames; r++) {
+        uint32_t open = 0;
+        for (uint32_t j = 0; j < frames; j++) open += gate[r * frames + j].open;
+        printf("  stream %u open in %u of %u frames (avg %.1f dB, snr %.1f dB)", recorded[r], open, frames, gate[r * frames + frames - 1].avg_db,
+               gate[r * frames + frames - 1].snr_db);
+    }
+    printf("\n");
     CHECK(pebblegpu_streambank_iq_out_release(sb, a.call_index));
     CHECK(pebblegpu_streambank_display_next(sb, 1, &d));
     if (!d.host || d.call_index != call || d.dropped_before) { fprintf(stderr, "display block %llu missing\n", (unsigned long long)call); return 1; }
@@ -91,7 +105,8 @@ int main(void)
     CHECK(pebblegpu_streambank_create(&cfg, &sb));
     for (uint32_t s = 0; s < N_STREAMS; s++) CHECK(pebblegpu_streambank_set_bandpass(sb, s, -60e3, 60e3));
 
-    const uint32_t recorded[2] = {5, 2};                     /* row 0 of every IQ block is stream 5, row 1 stream 2 */
+    CHECK(pebblegpu_streambank_set_squelch(sb, 5, -20.0));   /* above what the tone averages over the pass band: closed, zeros in the block */
+    CHECK(pebblegpu_streambank_set_squelch(sb, 2, -60.0));   /* (a threshold above -120 turns the S-meter on) */
     CHECK(pebblegpu_streambank_iq_out_open(sb, PEBBLEGPU_AUDIO_S16, recorded, 2, N_SLOTS));
     pebblegpu_screen_map map;
     memset(&map, 0, sizeof map);

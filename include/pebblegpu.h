@@ -1100,6 +1100,68 @@ int pebblegpu_streambank_display_set_auto_scale(pebblegpu_streambank *sb, uint32
 int pebblegpu_streambank_display_rescale(pebblegpu_streambank *sb);
 int pebblegpu_streambank_display_scale(pebblegpu_streambank *sb, uint64_t call_index, pebblegpu_display_scale *out, uint32_t cap, uint32_t *n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Stream bank: per-stream S-meter and squelch-gated IQ blocks.  The reference's order in Receiver::processIQData is band-pass, then
+ * SignalStrength::fdEstimate (application/signalstrength.cpp:287-380) on the unprocessed spectrum over the band-pass window, then the
+ * squelch return (application/receiver.cpp:950-965); the bank runs the last two on the device, so a host that watches many streams
+ * neither pulls dB rows nor ships the IQ of streams that carry nothing.
+ *
+ * The rule, for one row of `bins` float dB values (each widened to double): binWidth = sample_rate / bins (INTEGER division);
+ *   mixerBin = qBound(0, (int)(bins / 2 + mixer_freq / binWidth), bins);   lo / hi = qBound(0, (int)(mixerBin + bp_lo|bp_hi / binWidth), bins)
+ *   bpBins = hi - lo;   noiseLow = qBound(0, lo - bpBins, bins);   noiseHigh = qBound(0, hi + bpBins, bins)
+ *   over i in [noiseLow, min(noiseHigh, bins - 1)]: pwr = pow(10, dB_i / 10.0); lo <= i <= hi: total += pwr, peak = max; else noise += pwr
+ *   peakDb = clip(powerTodB(peak)); avgDb = clip(powerTodB(total / bpBins)); floorDb = clip(powerTodB(noise / noiseBins));
+ *   snrDb = bound(0, 10 log10(peak / noiseAvg), 120), 0 when either is 0.      powerTodB(0) = -120; clip bounds to -120..0
+ * bpBins == 0 gives avgDb 0 (x / 0 = inf) and, with no noise bin, NaN floorDb and snrDb -- as the reference computes them.
+ * pebblegpu_signal_strength_row is the host twin (no device): the reference's serial loop; out = (peakDb, avgDb, snrDb, floorDb).
+ * PEBBLEGPU_E_INVALID for a NULL argument, 0 bins, or sample_rate < bins (the integer bin width would be 0).  The device
+ * (k_stream_strength: one 256-lane workgroup per row, a fixed reduction order, no atomics -- the same bits on every run) adds in another
+ * order: the four values agree with the twin's on the same row to ~1e-4 dB.
+ *
+ * _enable_signal_strength(sb, on): from the next call on every call that computes unprocessed-spectrum rows queues ONE more launch behind
+ * its end (behind the join with PEBBLEGPU_SB_SIDE=1), whether or not a ring is open; a call that computes no row launches nothing.
+ * Stream s's window is its own band-pass (lo, hi) as float -- what the last ACCEPTED pebblegpu_streambank_set_bandpass left; (-1, 1),
+ * CFastFIR's constructor state, before the first -- around mixer frequency 0 at the bank's sample_rate rounded to whole Hz.  Needs
+ * spectrum_bins != 0 and a bin width of at least 1 Hz (else PEBBLEGPU_E_INVALID).  Off cannot be chosen while a stream's squelch is above
+ * -120 (PEBBLEGPU_E_INVALID).  With the S-meter off a call queues exactly what it queued before this interface existed.
+ * _signal_strength(sb, &rows_per_stream, &pitch): a device pointer to float4 [stream][pitch] (peakDb, avgDb, snrDb, floorDb), one entry per
+ * row the LAST call computed, indexed like pebblegpu_streambank_spectrum -- under the update gate the computed rows only, possibly none;
+ * complete after pebblegpu_streambank_synchronize.  NULL and 0 rows while the S-meter is off.
+ *
+ * _set_squelch(sb, stream, squelch_db): one threshold per stream, narrowed to float; -120 and below never closes (the default).  A
+ * threshold above -120 turns the S-meter on (and is refused where that is).  PEBBLEGPU_E_INVALID: stream out of range, a non-finite value.
+ * The setters are HOST STATE consumed when the next call is queued: tables are uploaded in stream order from pinned staging, no call waits
+ * for the calls before it.  The decision is per (stream, frame of cfg.frame samples -- processIQData's buffer), made on the device with
+ * no read-back: closed = avgDb < squelch_db on the float the S-meter reported.  The row frame f reads (getUnprocessed(), receiver.cpp:959-965):
+ * its own when the call computed one for f; else the latest computed at or before f, carried from an earlier call if need be (a call
+ * without bit 1 of `what` reads the carried one); before any row exists (since the S-meter went on) the gate is open.
+ * What the gate suppresses is what lies behind the band-pass: the IQ ring.  A closed (stream, frame) is zeros in the block (0.0f pairs in
+ * F32, 0 pairs in S16), an open one bit for bit what the ring delivered before.  pebblegpu_streambank_filtered is in FRONT of the gate, as
+ * the band-pass is in the reference: its bits, the overlap and the spectrum never depend on a threshold.  The rows go through the gated
+ * instance of the packing kernel only while some threshold is above -120.
+ *
+ * The trailer.  While the S-meter is on every IQ block THAT HAS SAMPLES carries, behind its rows and inside the slot's one copy, one
+ * pebblegpu_stream_gate per (selected stream r, frame j of the call), entry r * n_frames + j: the values the frame's decision read, `open`,
+ * and `row` -- the computed-row index of this call they came from, PEBBLEGPU_GATE_ROW_CARRIED (an earlier call's) or
+ * PEBBLEGPU_GATE_ROW_NONE (none yet: values 0, open 1).  _iq_out_gate reads it for a block that is currently handed out (out: cap entries;
+ * *n_frames = the call's frames): PEBBLEGPU_E_INVALID for any other call_index and for a block queued while the S-meter was off or without
+ * samples, PEBBLEGPU_E_SIZE when n_selected * n_frames entries do not fit cap.  Every IQ ring reserves n_selected * max_frames entries per
+ * slot at open (counted in the 1 GiB limit) whether or not the S-meter is on: 24 bytes per (stream, frame) of pinned memory that an
+ * S-meter that stays off never copies.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct pebblegpu_stream_gate {
+    float peak_db, avg_db, snr_db, floor_db;
+    uint32_t open;                 /* 0: the frame is zeros in the block */
+    uint32_t row;
+} pebblegpu_stream_gate;
+#define PEBBLEGPU_GATE_ROW_CARRIED 0xFFFFFFFEu
+#define PEBBLEGPU_GATE_ROW_NONE 0xFFFFFFFFu
+int pebblegpu_signal_strength_row(const float *db, uint32_t bins, uint32_t sample_rate, float bp_lo, float bp_hi, double mixer_freq, float out[4]);
+int pebblegpu_streambank_enable_signal_strength(pebblegpu_streambank *sb, int on);
+const void *pebblegpu_streambank_signal_strength(const pebblegpu_streambank *sb, uint64_t *rows_per_stream, uint64_t *pitch);
+int pebblegpu_streambank_set_squelch(pebblegpu_streambank *sb, uint32_t stream, double squelch_db);
+int pebblegpu_streambank_iq_out_gate(pebblegpu_streambank *sb, uint64_t call_index, pebblegpu_stream_gate *out, uint32_t cap, uint32_t *n_frames);
+
 #ifdef __cplusplus
 }
 #endif

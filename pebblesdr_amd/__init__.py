@@ -17,6 +17,7 @@ from .binding import (  # noqa: F401
     DISPLAY_DB_F32, DISPLAY_PIXELS_I32, DISPLAY_WATERFALL_ARGB32, DisplayBlock, waterfall_colors,
     PANE_SPECTRUM, PANE_ZOOM, DisplayPane, display_pane,
     AUTO_SCALE_MAX, AUTO_SCALE_MIN, DisplayScale, DISPLAY_SCALE, auto_scale_row,
+    StreamGateEntry, STREAM_GATE, GATE_ROW_CARRIED, GATE_ROW_NONE, signal_strength_row,
 )
 from .steps import Mixer, Decimator, DownConvert, FastFIR, Demod, Spectrum, Morse  # noqa: F401
 
@@ -27,4 +28,5 @@ __all__ = [
     "MultiBank", "multibank_plan", "audio_out_convert", "iq_record_convert", "DisplayBlock", "waterfall_colors",
     "PANE_SPECTRUM", "PANE_ZOOM", "DisplayPane", "display_pane",
     "AUTO_SCALE_MAX", "AUTO_SCALE_MIN", "DisplayScale", "DISPLAY_SCALE", "auto_scale_row",
+    "StreamGateEntry", "STREAM_GATE", "GATE_ROW_CARRIED", "GATE_ROW_NONE", "signal_strength_row",
 ]

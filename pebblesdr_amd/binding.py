@@ -61,6 +61,8 @@ SYMBOLS = [
     "pebblegpu_auto_scale_row", "pebblegpu_receiver_spectrum_scale", "pebblegpu_streambank_spectrum_scale",
     "pebblegpu_receiver_display_set_auto_scale", "pebblegpu_receiver_display_rescale", "pebblegpu_receiver_display_scale",
     "pebblegpu_streambank_display_set_auto_scale", "pebblegpu_streambank_display_rescale", "pebblegpu_streambank_display_scale",
+    "pebblegpu_signal_strength_row", "pebblegpu_streambank_enable_signal_strength", "pebblegpu_streambank_signal_strength",
+    "pebblegpu_streambank_set_squelch", "pebblegpu_streambank_iq_out_gate",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
@@ -344,6 +346,27 @@ def auto_scale_row(db, lib=None):
     return int(out.max_db), int(out.min_db), float(out.avg_power), float(out.peak_power)
 
 
+class StreamGateEntry(C.Structure):
+    """pebblegpu_stream_gate: one (selected stream, frame) of a stream-bank IQ block's trailer"""
+    _fields_ = [("peak_db", C.c_float), ("avg_db", C.c_float), ("snr_db", C.c_float), ("floor_db", C.c_float), ("open", C.c_uint32), ("row", C.c_uint32)]
+
+
+# the same 24 bytes as a numpy record (what StreamBank.iq_out_gate returns)
+STREAM_GATE = np.dtype([("peak_db", np.float32), ("avg_db", np.float32), ("snr_db", np.float32), ("floor_db", np.float32),
+                        ("open", np.uint32), ("row", np.uint32)])
+GATE_ROW_CARRIED, GATE_ROW_NONE = 0xFFFFFFFE, 0xFFFFFFFF  # PEBBLEGPU_GATE_ROW_*
+
+
+def signal_strength_row(db, sample_rate, bp_lo, bp_hi, mixer_freq=0.0, lib=None):
+    """host twin of the S-meter rule (SignalStrength::fdEstimate, no device): one row of float dB -> float32 [4] (peakDb, avgDb, snrDb, floorDb)"""
+    L = lib or load_library()
+    row = np.ascontiguousarray(db, dtype=np.float32).reshape(-1)
+    out = np.zeros(4, dtype=np.float32)
+    check(L, L.pebblegpu_signal_strength_row(row.ctypes.data_as(C.c_void_p), row.size, int(sample_rate), float(bp_lo), float(bp_hi), float(mixer_freq),
+                                             out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def _pull_scale(obj, fn, frames, first_frame, n_frames, frame_step):
     """the pull functions' shared body: queue, synchronise, download -> DISPLAY_SCALE [streams, n_frames]"""
     if first_frame is None and n_frames is None:
@@ -601,6 +624,12 @@ def _declare(L):
     L.pebblegpu_auto_scale_row.argtypes = [vp, u32, C.POINTER(DisplayScale)]
     L.pebblegpu_receiver_spectrum_scale.argtypes = [vp, u32, u32, u32, vp]
     L.pebblegpu_streambank_spectrum_scale.argtypes = [vp, u32, u32, u32, vp]
+    L.pebblegpu_signal_strength_row.argtypes = [vp, u32, u32, C.c_float, C.c_float, dbl, vp]
+    L.pebblegpu_streambank_enable_signal_strength.argtypes = [vp, i32]
+    L.pebblegpu_streambank_signal_strength.restype = vp
+    L.pebblegpu_streambank_signal_strength.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.pebblegpu_streambank_set_squelch.argtypes = [vp, u32, dbl]
+    L.pebblegpu_streambank_iq_out_gate.argtypes = [vp, u64, vp, u32, C.POINTER(u32)]
     for who in ("receiver", "streambank"):
         getattr(L, "pebblegpu_%s_display_set_auto_scale" % who).argtypes = [vp, u32]
         getattr(L, "pebblegpu_%s_display_rescale" % who).argtypes = [vp]
@@ -1319,6 +1348,7 @@ class StreamBank:
         """streams: row r of every block is stream streams[r] (None: all, in order); fmt AUDIO_F32 (verbatim) or AUDIO_S16"""
         arr, n = self._stream_list(streams)
         check(self.L, self.L.pebblegpu_streambank_iq_out_open(self.h, int(fmt), arr, n, int(n_slots)))
+        self._iq_rows = self.n_streams if streams is None else len(streams)
 
     def iq_out_close(self):
         check(self.L, self.L.pebblegpu_streambank_iq_out_close(self.h))
@@ -1339,6 +1369,35 @@ class StreamBank:
         n = C.c_uint64()
         check(self.L, self.L.pebblegpu_streambank_iq_out_dropped(self.h, C.byref(n)))
         return int(n.value)
+
+    # ---- S-meter and squelch (SignalStrength::fdEstimate, receiver.cpp:959-965) ----
+    def enable_signal_strength(self, on=True):
+        """host state, consumed by the next call (no wait): one more launch per call that computes spectrum rows"""
+        check(self.L, self.L.pebblegpu_streambank_enable_signal_strength(self.h, 1 if on else 0))
+
+    def signal_strength(self):
+        """-> float32 [streams, rows, 4] (peakDb, avgDb, snrDb, floorDb): one entry per spectrum row the last call computed"""
+        rows, pitch = C.c_uint64(), C.c_uint64()
+        p = self.L.pebblegpu_streambank_signal_strength(self.h, C.byref(rows), C.byref(pitch))
+        self.synchronize()
+        full = np.zeros((self.n_streams, int(pitch.value), 4), dtype=np.float32)
+        if int(rows.value):
+            check(self.L, self.L.pebblegpu_memcpy_d2h(self.device, full.ctypes.data_as(C.c_void_p), C.c_void_p(p), full.nbytes))
+        return full[:, : int(rows.value)].copy()
+
+    def set_squelch(self, stream, squelch_db):
+        """closed = avgDb < squelch_db per (stream, frame): a closed frame is zeros in the IQ ring's block; -120 and below never closes"""
+        check(self.L, self.L.pebblegpu_streambank_set_squelch(self.h, int(stream), float(squelch_db)))
+
+    def iq_out_gate(self, call_index, cap=1 << 16):
+        """the gate trailer of the handed-out IQ block of call_index -> STREAM_GATE [selected streams, frames]"""
+        out = np.zeros(max(1, int(cap)), dtype=STREAM_GATE)
+        n = C.c_uint32()
+        check(self.L, self.L.pebblegpu_streambank_iq_out_gate(self.h, int(call_index), out.ctypes.data_as(C.c_void_p), int(cap), C.byref(n)))
+        frames = int(n.value)
+        if not frames:
+            return out[:0].reshape(0, 0)
+        return out.reshape(-1)[: (len(out) // frames) * frames].reshape(-1, frames)[: self._iq_rows].copy()
 
     def display_open(self, fmt=DISPLAY_DB_F32, screen=None, streams=None, max_rows=0, n_slots=4):
         """screen: a ScreenMap (screen_map(...)) for the two mapped formats; max_rows 0: the bank's max_frames"""

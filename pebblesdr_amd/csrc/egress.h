@@ -120,9 +120,19 @@ int run_audio_pack(hipStream_t s, const float2 *audio, long long pitch, long lon
                    uint64_t dst_pitch);
 // rows x n IQ samples (float2 rows of `pitch`, or raw device-format pairs converted as k_normalize_iq converts them) -> PCM16 pairs
 int run_iq_record(hipStream_t s, const float2 *iq, long long pitch, const struct RawSrc *raw, long long n, uint32_t rows, void *dst, uint64_t dst_pitch);
+// = pebblegpu_stream_gate: one (selected stream, frame) of a stream-bank IQ block's trailer, and the gated packing kernel's table
+struct StreamGate {
+    float peak_db, avg_db, snr_db, floor_db;
+    uint32_t open, row;
+};
+constexpr uint32_t kStreamGateCarried = 0xFFFFFFFEu, kStreamGateNone = 0xFFFFFFFFu;
+
 // rows x n band-passed samples (row r at iq + tab[r] * pitch: the stream bank's selection) -> dst [rows][dst_pitch bytes]: the float2
 // rows verbatim (PEBBLEGPU_AUDIO_F32) or PCM16 pairs by iq_record_s16 (PEBBLEGPU_AUDIO_S16)
-int run_iq_pack(hipStream_t s, const float2 *iq, long long pitch, long long n, const uint32_t *d_tab, uint32_t rows, int format, void *dst, uint64_t dst_pitch);
+// gate != nullptr: the gated instance -- frame f (of `frame` samples, n_frames = n / frame) of block row r is zeros where
+// gate[r * n_frames + f].open == 0 and what the ungated instance writes everywhere else
+int run_iq_pack(hipStream_t s, const float2 *iq, long long pitch, long long n, const uint32_t *d_tab, uint32_t rows, int format, void *dst, uint64_t dst_pitch,
+                const StreamGate *gate = nullptr, long long frame = 0);
 int check_egress_slots(uint32_t n_slots);
 
 }  // namespace pg

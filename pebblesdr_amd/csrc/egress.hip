@@ -102,16 +102,25 @@ static __global__ __launch_bounds__(256) void k_iq_record(const float2 *__restri
 // as they are (S16 false: two 16-byte loads, two 16-byte stores per work-item) or through iq_record_s16 (four pairs, one 16-byte
 // store).  A call's n is a multiple of the band-pass block, so rows are 16-byte aligned on both sides; anything else goes sample by
 // sample like k_iq_record's ragged end.
-template <bool S16>
-static __global__ __launch_bounds__(256) void k_iq_pack(const float2 *__restrict__ iq, long long pitch, long long n, const uint32_t *__restrict__ tab,
-                                                         unsigned char *__restrict__ dst, unsigned long long dst_pitch)
+// GATED (the bank's squelch): the samples of frame f of row r are replaced by zeros where gate[r * n_frames + f].open == 0 -- 0.0f pairs,
+// which iq_record_s16 turns into 0 pairs; an open frame goes through the same loads, conversions and stores as without the gate.
+template <bool S16, bool GATED>
+__device__ __forceinline__ void iq_pack_body(const float2 *__restrict__ iq, long long pitch, long long n, const uint32_t *__restrict__ tab,
+                                             unsigned char *__restrict__ dst, unsigned long long dst_pitch, const StreamGate *__restrict__ gate, long long frame)
 {
     const float2 *src = iq + (long long)tab[blockIdx.y] * pitch;
     unsigned char *out = dst + (unsigned long long)blockIdx.y * dst_pitch;
-    const bool vec = (reinterpret_cast<unsigned long long>(src) & 15ull) == 0;
+    const bool vec = (reinterpret_cast<unsigned long long>(src) & 15ull) == 0 && (!GATED || (frame & 3) == 0);  // (four samples, one frame)
+    const StreamGate *g = GATED ? gate + (long long)blockIdx.y * (n / frame) : nullptr;
     for (long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (long long)gridDim.x * 1024) {
         if (vec && n - i0 >= 4) {
-            const float4 a = reinterpret_cast<const float4 *>(src + i0)[0], b = reinterpret_cast<const float4 *>(src + i0)[1];
+            float4 a, b;
+            if (GATED && !g[i0 / frame].open) {
+                a = b = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                a = reinterpret_cast<const float4 *>(src + i0)[0];
+                b = reinterpret_cast<const float4 *>(src + i0)[1];
+            }
             if (!S16) {
                 float4 *o = reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(out) + i0);
                 o[0] = a;
@@ -125,12 +134,26 @@ static __global__ __launch_bounds__(256) void k_iq_pack(const float2 *__restrict
             }
         } else {  // (no registers indexed by a run-time count: that would cost the kernel LDS)
             for (long long i = i0; i < n && i < i0 + 4; i++) {
-                const float2 v = src[i];
+                const float2 v = (GATED && !g[i / frame].open) ? make_float2(0.f, 0.f) : src[i];
                 if (!S16) reinterpret_cast<float2 *>(out)[i] = v;
                 else reinterpret_cast<short2 *>(out)[i] = make_short2(iq_record_s16(v.x), iq_record_s16(v.y));
             }
         }
     }
+}
+
+template <bool S16>
+static __global__ __launch_bounds__(256) void k_iq_pack(const float2 *__restrict__ iq, long long pitch, long long n, const uint32_t *__restrict__ tab,
+                                                         unsigned char *__restrict__ dst, unsigned long long dst_pitch)
+{
+    iq_pack_body<S16, false>(iq, pitch, n, tab, dst, dst_pitch, nullptr, 1);
+}
+template <bool S16>
+static __global__ __launch_bounds__(256) void k_iq_pack_gated(const float2 *__restrict__ iq, long long pitch, long long n, const uint32_t *__restrict__ tab,
+                                                               unsigned char *__restrict__ dst, unsigned long long dst_pitch,
+                                                               const StreamGate *__restrict__ gate, long long frame)
+{
+    iq_pack_body<S16, true>(iq, pitch, n, tab, dst, dst_pitch, gate, frame);
 }
 
 static unsigned pack_blocks(long long n)
@@ -163,13 +186,21 @@ int run_iq_record(hipStream_t s, const float2 *iq, long long pitch, const RawSrc
     return 0;
 }
 
-int run_iq_pack(hipStream_t s, const float2 *iq, long long pitch, long long n, const uint32_t *d_tab, uint32_t rows, int format, void *dst, uint64_t dst_pitch)
+int run_iq_pack(hipStream_t s, const float2 *iq, long long pitch, long long n, const uint32_t *d_tab, uint32_t rows, int format, void *dst, uint64_t dst_pitch,
+                const StreamGate *gate, long long frame)
 {
     if (n <= 0 || rows == 0) return 0;
     const dim3 grid(pack_blocks(n), rows);
     unsigned char *o = (unsigned char *)dst;
-    if (format == PEBBLEGPU_AUDIO_F32) launch(k_iq_pack<false>, grid, dim3(256), s, iq, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
-    else launch(k_iq_pack<true>, grid, dim3(256), s, iq, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
+    if (gate) {
+        if (frame <= 0 || n % frame) return fail(PEBBLEGPU_E_INVALID, "a gated block of %lld samples in frames of %lld", n, frame);
+        if (format == PEBBLEGPU_AUDIO_F32) launch(k_iq_pack_gated<false>, grid, dim3(256), s, iq, pitch, n, d_tab, o, (unsigned long long)dst_pitch, gate, frame);
+        else launch(k_iq_pack_gated<true>, grid, dim3(256), s, iq, pitch, n, d_tab, o, (unsigned long long)dst_pitch, gate, frame);
+    } else if (format == PEBBLEGPU_AUDIO_F32) {
+        launch(k_iq_pack<false>, grid, dim3(256), s, iq, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
+    } else {
+        launch(k_iq_pack<true>, grid, dim3(256), s, iq, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
+    }
     PG_HIP(hipGetLastError());
     return 0;
 }

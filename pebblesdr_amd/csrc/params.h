@@ -309,6 +309,23 @@ struct Gate {
 
 // fdEstimate's bin windows for one channel: noise [nlo, nhi] around the band-pass [lo, hi]; stream = which spectrum it reads
 struct SmBins { int nlo, lo, hi, nhi, bp_bins, stream, pad_[2]; };
+// ... as the reference works them out (signalstrength.cpp:313-337): integer bin width sample_rate / bins (the caller makes sure it is not 0),
+// truncating conversions, qBound(0, ., bins)
+inline SmBins strength_windows(uint32_t bins, uint32_t sample_rate, float bp_lo, float bp_hi, double mixer_freq, int stream)
+{
+    const int nb = (int)bins;
+    const double bin_width = (double)(sample_rate / bins);
+    auto qb = [nb](int v) { return v < 0 ? 0 : (v > nb ? nb : v); };
+    const int mixer_bin = qb((int)(nb / 2 + (mixer_freq / bin_width)));
+    SmBins b{};
+    b.lo = qb((int)(mixer_bin + (bp_lo / bin_width)));
+    b.hi = qb((int)(mixer_bin + (bp_hi / bin_width)));
+    b.bp_bins = b.hi - b.lo;
+    b.nlo = qb(b.lo - b.bp_bins);
+    b.nhi = qb(b.hi + b.bp_bins);
+    b.stream = stream;
+    return b;
+}
 
 // k_spectrum_t128<.., DEC = true>: the one-channel mixer + decimator hb11 x 8, hb15, hb23, hb47 (20 Msps -> 312.5 kHz; the halfbands'
 // coefficients are literals of the kernel, hb_const.h) computed by the

@@ -490,21 +490,11 @@ int Receiver::apply_controls(hipStream_t osc_stream)
 {
     if (int rc = osc_.upload(osc_stream)) return rc;
     if (smeter_on && sm_dirty_) {
-        // bin indices of fdEstimate (signalstrength.cpp:313-337): integer bin width, truncating conversions, qBound
+        // bin indices of fdEstimate (strength_windows, params.h)
         std::vector<SmBins> hb(C);
-        const int nb = (int)bins;
-        const double bin_width = (double)((uint32_t)fs / (uint32_t)nb);
-        auto qb = [nb](int v) { return v < 0 ? 0 : (v > nb ? nb : v); };
         for (uint32_t ch = 0; ch < C; ch++) {
             const float lo = wfm ? -100000.f : (float)ctl_[ch].lo, hi = wfm ? 100000.f : (float)ctl_[ch].hi;  // receiver.cpp:891-892,959-960
-            const int mixer_bin = qb((int)(nb / 2 + (osc_.ctl[ch].freq / bin_width)));
-            SmBins &b = hb[ch];
-            b.lo = qb((int)(mixer_bin + (lo / bin_width)));
-            b.hi = qb((int)(mixer_bin + (hi / bin_width)));
-            b.bp_bins = b.hi - b.lo;
-            b.nlo = qb(b.lo - b.bp_bins);
-            b.nhi = qb(b.hi + b.bp_bins);
-            b.stream = shared_input ? 0 : (int)ch;
+            hb[ch] = strength_windows((uint32_t)bins, (uint32_t)fs, lo, hi, osc_.ctl[ch].freq, shared_input ? 0 : (int)ch);
         }
         PG_HIP(hipMemcpyAsync(d_sm_bins, hb.data(), sizeof(SmBins) * C, hipMemcpyHostToDevice, stream_));
         PG_HIP(hipStreamSynchronize(stream_));

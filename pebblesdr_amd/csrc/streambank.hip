@@ -2,6 +2,7 @@
 #include <new>
 #include <cmath>
 #include "kernels_display.h"
+#include "kernels_strength.h"
 #include "receiver.h"
 
 using pg::fail;
@@ -42,8 +43,30 @@ struct pebblegpu_streambank {
     pg::ScaleEntry *d_scale = nullptr;  // [n_streams] the ranges (allocated with the ring)
     uint64_t trailer_bytes = 0;      // per slot, behind the rows
     bool slot_scaled[pg::kEgressMaxSlots] = {};  // the slot's block carries a trailer
+    // the S-meter and the squelch (kernels_strength.h): host state consumed when the next call is queued, like the auto-scale flags
+    bool sm_on = false;
+    std::vector<float> bp_lo, bp_hi;     // per stream, as the last accepted set_bandpass left them (CFastFIR's constructor state: -1, 1)
+    std::vector<float> squelch;          // per stream; -120 and below never closes
+    uint32_t n_squelch = 0;              // thresholds above -120: while there are any the IQ ring packs through the gated instance
+    bool win_dirty = true, sq_dirty = true;
+    pg::SmBins *d_win = nullptr;         // [n_streams] fdEstimate's windows
+    float *d_squelch = nullptr;          // [n_streams]
+    float4 *d_smeter = nullptr;          // [n_streams][max_frames]: one entry per row the last call computed
+    float4 *d_carry[2] = {};             // [n_streams] each: the last computed entry per stream.  A call that computes rows writes the other
+    int carry_cur = 0;                   // one, so its own gate still reads what earlier calls left; then they swap
+    bool have_row = false;               // d_carry[carry_cur] holds a row (computed since the S-meter went on)
+    uint64_t sm_rows = 0;                // entries per stream the last call wrote
+    // table uploads that never wait for earlier calls: pinned staging slots, each reused once the copy queued from it has completed
+    static constexpr int kStage = 4;
+    void *h_stage[kStage] = {};
+    hipEvent_t stage_ev[kStage] = {};
+    int stage_next = 0;
+    uint64_t gate_bytes = 0;             // per IQ slot, behind the rows: room for n_selected * max_frames entries
+    bool slot_gated[pg::kEgressMaxSlots] = {};      // the IQ slot's block carries the gate trailer ...
+    uint32_t slot_frames[pg::kEgressMaxSlots] = {}; // ... of this many frames per selected stream
 };
 
+static_assert(sizeof(pg::StreamGate) == sizeof(pebblegpu_stream_gate) && sizeof(pebblegpu_stream_gate) == 24, "the IQ block trailer's entry");
 constexpr uint64_t kMaxRingBytes = 1ull << 30;  // pinned host memory one ring may hold, all slots together
 
 // a ring's selection: `streams` checked against the bank (NULL: all, in order)
@@ -102,20 +125,102 @@ static int sb_close_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, uint32_
     return 0;
 }
 
+// `bytes` of host table `src` to d_dst, in stream order on the bank's stream: behind the kernels of earlier calls that read the table,
+// ahead of this call's.  The host copies into a pinned staging slot and goes on; it waits only if the copy queued from that slot
+// kStage uploads ago has not completed.
+static int sb_upload(pebblegpu_streambank *sb, void *d_dst, const void *src, size_t bytes)
+{
+    const int i = sb->stage_next;
+    sb->stage_next = (i + 1) % pebblegpu_streambank::kStage;
+    PG_HIP(hipEventSynchronize(sb->stage_ev[i]));
+    memcpy(sb->h_stage[i], src, bytes);
+    PG_HIP(hipMemcpyAsync(d_dst, sb->h_stage[i], bytes, hipMemcpyHostToDevice, sb->stream));
+    PG_HIP(hipEventRecord(sb->stage_ev[i], sb->stream));
+    return 0;
+}
+
+// fdEstimate on every row the call computed: one launch behind the call's end, none when it computed no row
+static int sb_queue_strength(pebblegpu_streambank *sb, uint64_t rows)
+{
+    sb->sm_rows = 0;
+    if (!rows) return 0;
+    const uint32_t S = sb->cfg.n_streams;
+    const int bins = (int)sb->sp.bins;
+    if (sb->win_dirty) {
+        std::vector<pg::SmBins> w(S);
+        for (uint32_t s = 0; s < S; s++)
+            w[s] = pg::strength_windows((uint32_t)bins, (uint32_t)std::llround(sb->cfg.sample_rate), sb->bp_lo[s], sb->bp_hi[s], 0.0, (int)s);
+        if (int rc = sb_upload(sb, sb->d_win, w.data(), sizeof(pg::SmBins) * S)) return rc;
+        sb->win_dirty = false;
+    }
+    pg::launch(pg::k_stream_strength, dim3((unsigned)(S * rows)), dim3(256), sb->stream, sb->d_spec, (long long)rows * bins, bins, (int)rows, sb->d_win,
+               sb->d_smeter, (long long)sb->cfg.max_frames, sb->d_carry[sb->carry_cur ^ 1]);
+    PG_HIP(hipGetLastError());
+    sb->sm_rows = rows;
+    return 0;
+}
+
+// The gate of an IQ block of F frames into its trailer: per frame the S-meter row it reads (receiver.cpp:959-965, getUnprocessed()) -- its
+// own when the call computed one for it, else the latest at or before it, carried from an earlier call if need be, none before any exists
+static int sb_queue_gate(pebblegpu_streambank *sb, uint32_t F, uint32_t what, pg::StreamGate *gate)
+{
+    if (sb->sq_dirty) {
+        if (int rc = sb_upload(sb, sb->d_squelch, sb->squelch.data(), sizeof(float) * sb->cfg.n_streams)) return rc;
+        sb->sq_dirty = false;
+    }
+    const int before = sb->have_row ? pg::kGateRowCarried : pg::kGateRowNone;
+    const bool every = (what & 2u) && !sb->last_listed && sb->sm_rows;
+    size_t k = 0;  // listed frames at or before the current one
+    for (uint32_t j0 = 0; j0 < F; j0 += pg::kListMax) {
+        pg::GateRows gr;
+        gr.j0 = (int)j0;
+        gr.n = (int)std::min<uint32_t>(pg::kListMax, F - j0);
+        for (int j = 0; j < gr.n; j++) {
+            const uint32_t f = j0 + (uint32_t)j;
+            if (every) { gr.row[j] = (int)f; continue; }
+            while (sb->sm_rows && k < sb->sel.size() && sb->sel[k] <= f) k++;
+            gr.row[j] = k ? (int)k - 1 : before;
+        }
+        const unsigned items = sb->iq_ring.rows * (unsigned)gr.n;
+        pg::launch(pg::k_stream_gate_eval, dim3((items + 255) / 256), dim3(256), sb->stream, sb->d_smeter, (long long)sb->cfg.max_frames,
+                   sb->d_carry[sb->carry_cur], sb->d_squelch, sb->d_iq_tab, (int)sb->iq_ring.rows, (int)F, gate, gr);
+    }
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
 // The blocks of an accepted call, behind its end on the bank's stream (behind the join of a side-by-side call) and so ahead of the
 // next call's kernels, which overwrite d_filt and d_spec: one launch and one event per open ring; a call that did not run a ring's
 // producer gives that ring a block of 0 samples / 0 rows and queues nothing.
 static int sb_queue_blocks(pebblegpu_streambank *sb, uint64_t n, uint32_t what)
 {
+    if (sb->sm_on) {
+        if (int rc = sb_queue_strength(sb, n ? sb->last_frames : 0)) return rc;
+    }
     if (sb->iq_ring.open) {
         if (pg::EgressSlot *g = sb->iq_ring.begin()) {
-            const uint64_t m = (what & 1u) ? n : 0;
-            if (int rc = pg::run_iq_pack(sb->stream, sb->d_filt, (long long)n, (long long)m, sb->d_iq_tab, sb->iq_ring.rows, sb->iq_fmt, g->d,
-                                         pg::EgressRing::row_pitch(m, sb->iq_ring.bytes_per_sample)))
+            const uint64_t m = (what & 1u) ? n : 0, pitch = pg::EgressRing::row_pitch(m, sb->iq_ring.bytes_per_sample);
+            // S-meter on: the gate per (selected stream, frame) into a trailer behind the rows, inside the one copy; the rows go through the
+            // gated instance only while some threshold can close (else the launch is the one a bank without S-meter queues)
+            pg::StreamGate *gate = nullptr;
+            const uint32_t F = (uint32_t)(m / sb->cfg.frame);
+            if (sb->sm_on && m) {
+                gate = reinterpret_cast<pg::StreamGate *>((unsigned char *)g->d + sb->iq_ring.rows * pitch);
+                if (int rc = sb_queue_gate(sb, F, what, gate)) return rc;
+            }
+            sb->slot_gated[g - sb->iq_ring.slot] = gate != nullptr;
+            sb->slot_frames[g - sb->iq_ring.slot] = F;
+            if (int rc = pg::run_iq_pack(sb->stream, sb->d_filt, (long long)n, (long long)m, sb->d_iq_tab, sb->iq_ring.rows, sb->iq_fmt, g->d, pitch,
+                                         sb->n_squelch ? gate : nullptr, (long long)sb->cfg.frame))
                 return rc;
             g->aux = 0;
-            if (int rc = sb->iq_ring.commit(g, sb->stream, m)) return rc;
+            const uint64_t extra = gate ? ((uint64_t)sb->iq_ring.rows * F * sizeof(pg::StreamGate) + 15) & ~(uint64_t)15 : 0;
+            if (int rc = sb->iq_ring.commit(g, sb->stream, m, extra)) return rc;
         }
+    }
+    if (sb->sm_rows) {  // this call's last entry is what later calls carry
+        sb->carry_cur ^= 1;
+        sb->have_row = true;
     }
     if (sb->disp_ring.open) {
         // SpectrumWidget::recalcScale on this call's first computed row of every stream; a call that computed none leaves the request
@@ -176,8 +281,11 @@ int pebblegpu_streambank_destroy(pebblegpu_streambank *sb)
     sb->ff.release();
     sb->sp.release();
     sb->ingest.release();
-    void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec, sb->d_raw_stage, sb->d_iq_tab, sb->disp.d_tab, sb->d_scale};
+    void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec, sb->d_raw_stage, sb->d_iq_tab, sb->disp.d_tab, sb->d_scale,
+                 sb->d_win, sb->d_squelch, sb->d_smeter, sb->d_carry[0], sb->d_carry[1]};
     for (void *q : p) if (q) (void)hipFree(q);
+    for (void *q : sb->h_stage) if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : sb->stage_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sb->ev) if (e) (void)hipEventDestroy(e);
     delete sb;
     return 0;
@@ -198,6 +306,9 @@ int pebblegpu_streambank_create(const pebblegpu_streambank_config *cfg, pebblegp
     if (!sb->cfg.fastfir_taps) sb->cfg.fastfir_taps = 1025;
     const uint32_t S = cfg->n_streams;
     sb->cap = (uint64_t)cfg->frame * cfg->max_frames;
+    sb->bp_lo.assign(cfg->n_streams, -1.f);
+    sb->bp_hi.assign(cfg->n_streams, 1.f);
+    sb->squelch.assign(cfg->n_streams, -120.f);
     int rc = 0;
     auto body = [&]() -> int {
         PG_HIP(hipSetDevice(cfg->device));
@@ -233,6 +344,9 @@ int pebblegpu_streambank_set_bandpass(pebblegpu_streambank *sb, uint32_t stream,
     bool ok = false;
     if (int rc = sb->ff.design(sb->stream, stream, lo, hi, 0.0, sb->cfg.sample_rate, &ok)) return rc;
     if (!ok) return fail(PEBBLEGPU_E_FILTER_PARAM, "Filter Parameter error (lo %g hi %g rate %g)", lo, hi, sb->cfg.sample_rate);
+    sb->bp_lo[stream] = (float)lo;  // the S-meter's window (fdEstimate takes floats)
+    sb->bp_hi[stream] = (float)hi;
+    sb->win_dirty = true;
     return 0;
 }
 
@@ -492,8 +606,12 @@ int pebblegpu_streambank_iq_out_open(pebblegpu_streambank *sb, int format, const
     std::vector<uint32_t> sel;
     if (int rc = sb_selection(sb, streams, n_streams, &sel)) return rc;
     if (sb->iq_ring.open) return fail(PEBBLEGPU_E_INVALID, "the IQ ring is already open");
-    if (int rc = sb_open_ring(sb, sb->iq_ring, &sb->d_iq_tab, sel, n_slots, pg::kAudioBytes[format], sb->cap, (uint32_t)format)) return rc;
+    // (room behind the rows for the gate trailer, reserved whether or not the S-meter is on: a slot's size is fixed here)
+    const uint64_t trailer = ((uint64_t)sel.size() * sb->cfg.max_frames * sizeof(pg::StreamGate) + 15) & ~(uint64_t)15;
+    if (int rc = sb_open_ring(sb, sb->iq_ring, &sb->d_iq_tab, sel, n_slots, pg::kAudioBytes[format], sb->cap, (uint32_t)format, trailer)) return rc;
     sb->iq_fmt = format;
+    sb->gate_bytes = trailer;
+    for (bool &b : sb->slot_gated) b = false;
     return 0;
 }
 int pebblegpu_streambank_iq_out_close(pebblegpu_streambank *sb)
@@ -675,6 +793,111 @@ int pebblegpu_streambank_display_scale(pebblegpu_streambank *sb, uint64_t call_i
         if (!out) return fail(PEBBLEGPU_E_INVALID, "null argument");
         memcpy(out, (const unsigned char *)g.h + ring.rows * g.pitch_bytes, sizeof(pebblegpu_display_scale) * ring.rows);
         *n = ring.rows;
+        return 0;
+    }
+    return fail(PEBBLEGPU_E_INVALID, "call %llu is not handed out", (unsigned long long)call_index);
+}
+// ---- the S-meter and the squelch ----
+int pebblegpu_signal_strength_row(const float *db, uint32_t bins, uint32_t sample_rate, float bp_lo, float bp_hi, double mixer_freq, float out[4])
+{
+#pragma clang fp contract(off)
+    if (!db || !out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (!bins || bins > 0x7FFFFFFFu) return fail(PEBBLEGPU_E_INVALID, "a row of %u bins", bins);
+    if (sample_rate / bins == 0) return fail(PEBBLEGPU_E_INVALID, "sample rate %u below %u bins: the reference's integer bin width is 0", sample_rate, bins);
+    // the loop of signalstrength.cpp:339-353 as written, one bin after the other
+    const pg::SmBins b = pg::strength_windows(bins, sample_rate, bp_lo, bp_hi, mixer_freq, 0);
+    double total = 0.0, peak = 0.0, noise = 0.0;
+    int nn = 0;
+    for (int i = 0; i < (int)bins; i++) {
+        if (i < b.nlo) continue;
+        const double pwr = std::pow(10, (double)db[i] / 10.0);  // DB::dBToPower
+        if (i >= b.lo && i <= b.hi) {
+            total += pwr;
+            if (pwr > peak) peak = pwr;
+        } else if (i >= b.nlo && i <= b.nhi) {
+            noise += pwr;
+            nn++;
+        }
+        if (i >= b.nhi) break;
+    }
+    const float4 r = pg::strength_finish(total, peak, noise, nn, b.bp_bins);
+    out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
+    return 0;
+}
+int pebblegpu_streambank_enable_signal_strength(pebblegpu_streambank *sb, int on)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (!on) {
+        if (sb->n_squelch) return fail(PEBBLEGPU_E_INVALID, "%u streams have a squelch threshold above -120: the squelch reads the S-meter", sb->n_squelch);
+        sb->sm_on = false;
+        sb->sm_rows = 0;
+        return 0;
+    }
+    if (sb->sm_on) return 0;
+    const uint32_t S = sb->cfg.n_streams, bins = (uint32_t)sb->sp.bins;
+    if (!sb->cfg.spectrum_bins || !bins) return fail(PEBBLEGPU_E_INVALID, "the bank was created without a spectrum (spectrum_bins 0)");
+    if (bins % 4) return fail(PEBBLEGPU_E_UNSUPPORTED, "%u bins: spectrum rows are read in 16-byte vectors", bins);
+    const long long rate = std::llround(sb->cfg.sample_rate);
+    if (rate > 0xFFFFFFFFLL || (uint32_t)rate / bins == 0)
+        return fail(PEBBLEGPU_E_INVALID, "sample rate %g with %u bins: the reference's integer bin width would be 0 (or the rate does not fit 32 bits)", sb->cfg.sample_rate, bins);
+    PG_HIP(hipSetDevice(sb->cfg.device));
+    if (!sb->d_smeter) {  // (kept until destroy; nothing here waits for queued calls)
+        const size_t stage = std::max(sizeof(pg::SmBins), sizeof(float)) * S;
+        for (int i = 0; i < pebblegpu_streambank::kStage; i++) {
+            if (!sb->h_stage[i]) PG_HIP(hipHostMalloc(&sb->h_stage[i], stage, hipHostMallocDefault));
+            if (!sb->stage_ev[i]) PG_HIP(hipEventCreateWithFlags(&sb->stage_ev[i], hipEventDisableTiming));
+        }
+        if (!sb->d_win) PG_HIP(hipMalloc((void **)&sb->d_win, sizeof(pg::SmBins) * S));
+        if (!sb->d_squelch) PG_HIP(hipMalloc((void **)&sb->d_squelch, sizeof(float) * S));
+        for (float4 *&c : sb->d_carry) if (!c) PG_HIP(hipMalloc((void **)&c, sizeof(float4) * S));
+        PG_HIP(hipMalloc((void **)&sb->d_smeter, sizeof(float4) * (size_t)S * sb->cfg.max_frames));
+    }
+    sb->sm_on = true;
+    sb->win_dirty = sb->sq_dirty = true;
+    sb->have_row = false;  // rows computed while the S-meter was off are not carried
+    sb->sm_rows = 0;
+    return 0;
+}
+const void *pebblegpu_streambank_signal_strength(const pebblegpu_streambank *sb, uint64_t *rows_per_stream, uint64_t *pitch)
+{
+    if (rows_per_stream) *rows_per_stream = 0;
+    if (pitch) *pitch = 0;
+    if (!sb || !sb->sm_on) return nullptr;
+    if (rows_per_stream) *rows_per_stream = sb->sm_rows;
+    if (pitch) *pitch = sb->cfg.max_frames;
+    return sb->d_smeter;
+}
+int pebblegpu_streambank_set_squelch(pebblegpu_streambank *sb, uint32_t stream, double squelch_db)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (stream >= sb->cfg.n_streams) return fail(PEBBLEGPU_E_INVALID, "stream %u out of range", stream);
+    if (!std::isfinite(squelch_db)) return fail(PEBBLEGPU_E_INVALID, "the squelch threshold must be finite");
+    const float v = (float)squelch_db;  // (what the device compares the S-meter's float with)
+    if (v > -120.f) {
+        if (int rc = pebblegpu_streambank_enable_signal_strength(sb, 1)) return rc;
+    }
+    sb->n_squelch += (v > -120.f ? 1u : 0u) - (sb->squelch[stream] > -120.f ? 1u : 0u);
+    sb->squelch[stream] = v;
+    sb->sq_dirty = true;
+    return 0;
+}
+int pebblegpu_streambank_iq_out_gate(pebblegpu_streambank *sb, uint64_t call_index, pebblegpu_stream_gate *out, uint32_t cap, uint32_t *n_frames)
+{
+    if (!sb || !n_frames) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    *n_frames = 0;
+    pg::EgressRing &ring = sb->iq_ring;
+    std::lock_guard<std::mutex> lk(ring.mu);
+    if (!ring.open) return fail(PEBBLEGPU_E_INVALID, "the IQ ring is not open");
+    for (uint64_t q = ring.tail; q < ring.read; q++) {
+        const uint32_t si = (uint32_t)(q % ring.n_slots);
+        const pg::EgressSlot &g = ring.slot[si];
+        if (g.call != call_index) continue;
+        if (!sb->slot_gated[si]) return fail(PEBBLEGPU_E_INVALID, "the block of call %llu carries no gate: the S-meter was off when it was queued, or it has no samples", (unsigned long long)call_index);
+        const uint64_t entries = (uint64_t)ring.rows * sb->slot_frames[si];
+        if (entries > cap) return fail(PEBBLEGPU_E_SIZE, "%llu gate entries do not fit %u", (unsigned long long)entries, cap);
+        if (!out) return fail(PEBBLEGPU_E_INVALID, "null argument");
+        memcpy(out, (const unsigned char *)g.h + ring.rows * g.pitch_bytes, sizeof(pebblegpu_stream_gate) * entries);
+        *n_frames = sb->slot_frames[si];
         return 0;
     }
     return fail(PEBBLEGPU_E_INVALID, "call %llu is not handed out", (unsigned long long)call_index);
