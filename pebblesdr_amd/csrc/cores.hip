@@ -9,6 +9,7 @@
 #include "kernels_frontend.h"
 #include <algorithm>
 #include "bank_geom.h"
+#include "spectrum_geom.h"
 #include "kernels_fused_dec.h"
 #include "kernels_bank_dec.h"
 #include "kernels_spectrum.h"
@@ -2143,10 +2144,8 @@ int SpectrumCore::run_any(hipStream_t s, const float2 *d_in, long long in_pitch,
     SpectrumParams sp;
     sp.in_pitch = in_pitch;
     sp.n_frames = F;
-    const int zp = 1 << any_zp_log2;
-    long long G = (F * (long long)S * zp) / 1024;  // every chain recomputes one frame: chains as long as leaves about a thousand workgroups
-    G = G < 1 ? 1 : (G > 32 ? 32 : G);
-    sp.frames_per_group = (int)G;
+    const SpectrumGeom geo = spectrum_geometry(SpecFamily::any, F, S, bins, nf, S);  // chain length and workgroups: spectrum_geom.h
+    sp.frames_per_group = geo.G;
     sp.scale = scale;
     sp.out_pitch = F * (long long)bins;
     AnySpecParams ap;
@@ -2156,7 +2155,7 @@ int SpectrumCore::run_any(hipStream_t s, const float2 *d_in, long long in_pitch,
     ap.logM = any_logM;
     ap.zp_log2 = any_zp_log2;
     ap.windowed = windowed ? 1 : 0;
-    launch_lds(k_spectrum_any, dim3((unsigned)(cdiv(F, G) * zp), S), dim3(256), sizeof(float2) * (size_t)any_M, s, d_in, d_out, (const float *)d_window, (const float2 *)d_twM,
+    launch_lds(k_spectrum_any, dim3(geo.wgs, S), dim3(256), sizeof(float2) * (size_t)any_M, s, d_in, d_out, (const float *)d_window, (const float2 *)d_twM,
                (const float *)d_prev[parity], d_prev[parity ^ 1], sp, ap);
     parity ^= 1;
     PG_HIP(hipGetLastError());
@@ -2193,17 +2192,16 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
             PG_HIP(hipMalloc((void **)&d_Y, sizeof(float2) * need));
             y_cap = need;
         }
-        // a chain that does not start at frame 0 recomputes one frame: prefer chains as long as keeps >= 512 workgroups
-        long long G = (F * bs * 8) / 512;
-        G = G < 1 ? 1 : (G > 16 ? 16 : G);
-        sp.frames_per_group = (int)G;
+        // a chain that does not start at frame 0 recomputes one frame: chains sized by the batch (spectrum_geom.h)
+        const SpectrumGeom geo = spectrum_geometry(SpecFamily::big, F, S, bins, nf, bs);
+        sp.frames_per_group = geo.G;
         sp.scale = scale;
         sp.out_pitch = F * (long long)bins;
         for (long long s0 = 0; s0 < (long long)S; s0 += bs) {
             const unsigned nb = (unsigned)((long long)S - s0 < bs ? (long long)S - s0 : bs);
             if (tun.big_split32) {  // A/B: the 32 x 2048 split
                 launch(k_big_cols, dim3((unsigned)(F * 8), nb), dim3(256), s, d_in + s0 * in_pitch, (long long)in_pitch, d_Y, (const float *)d_window, (long long)F);
-                launch(k_big_rows, dim3((unsigned)(cdiv(F, G) * 8), nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch, (const float2 *)d_tw_nf,
+                launch(k_big_rows, dim3(geo.wgs, nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch, (const float2 *)d_tw_nf,
                        (const float *)d_prev[parity] + s0 * kBigN, d_prev[parity ^ 1] + s0 * kBigN, sp);
             } else {
                 if (raw) {  // (the stream offset is in IQ pairs of the raw format: the kernel gets the batch's base)
@@ -2221,7 +2219,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
                     }
                 } else
                 launch(k_big256_cols, dim3((unsigned)(F * 8), nb), dim3(256), s, d_in + s0 * in_pitch, (long long)in_pitch, d_Y, (const float *)d_window, (long long)F);
-                launch(k_big256_rows, dim3((unsigned)(cdiv(F, G) * 8), nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch,
+                launch(k_big256_rows, dim3(geo.wgs, nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch,
                        (const float *)d_prev[parity] + s0 * kBigN, d_prev[parity ^ 1] + s0 * kBigN, sp);
             }
         }
@@ -2230,18 +2228,15 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
         return 0;
     }
     if (per_q) {
-        // one (chain, q) per 128-item workgroup, eight workgroups per CU: aim at 2048 resident workgroups; every chain
-        // recomputes one frame, so chains are as long as that allows
+        // one (chain, q) per 128-item workgroup, in stretches of eight chains (spectrum_geom.h)
         const int zp = (int)(bins / nf);
         int zl = 0;
         while ((1 << zl) < zp) zl++;
-        long long Gq = (F * (long long)S * zp) / 2048;
-        Gq = Gq < 1 ? 1 : (Gq > 32 ? 32 : Gq);
-        sp.frames_per_group = (int)Gq;
+        const SpectrumGeom geo = spectrum_geometry(SpecFamily::q128, F, S, bins, nf, S);
+        sp.frames_per_group = geo.G;
         sp.scale = scale;
         sp.out_pitch = F * (long long)bins;
-        const long long chains = cdiv(F, Gq);
-        launch(tun.spectrum_fregs ? k_spectrum_q128<true> : k_spectrum_q128<false>, dim3((unsigned)(8 * zp * cdiv(chains, 8)), S), dim3(128), s, d_in, d_out, (const float2 *)d_ftab, (const float2 *)d_tw128,
+        launch(tun.spectrum_fregs ? k_spectrum_q128<true> : k_spectrum_q128<false>, dim3(geo.wgs, S), dim3(128), s, d_in, d_out, (const float2 *)d_ftab, (const float2 *)d_tw128,
                (const float *)d_prev[parity], d_prev[parity ^ 1], sp, zl);
         parity ^= 1;
         PG_HIP(hipGetLastError());
@@ -2250,13 +2245,12 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
     if (bins == 8192 && use_w64) {
         // one-wave transforms (fft_w64.h), one frame chain per 256-item workgroup, two workgroups per CU: chains as long as
         // keeps every workgroup resident at once (every chain recomputes one frame)
-        long long Gw = cdiv(F * (long long)S, 512);
-        Gw = Gw < 1 ? 1 : (Gw > 32 ? 32 : Gw);
-        sp.frames_per_group = (int)Gw;
+        const SpectrumGeom geo = spectrum_geometry(SpecFamily::w64, F, S, bins, nf, S);
+        sp.frames_per_group = geo.G;
         sp.scale = scale;
         sp.out_pitch = F * (long long)bins;
         const RawSrc rs = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
-        const dim3 grid((unsigned)cdiv(F, Gw), S), block(256);
+        const dim3 grid(geo.wgs, S), block(256);
         auto go = [&](auto kern) { launch(kern, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab, (const float *)d_prev[parity], d_prev[parity ^ 1], sp, rs); };
         switch (raw ? raw->fmt : -1) {
         case -1: go(k_spectrum_w64<-1>); break;
@@ -2271,11 +2265,10 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
         return 0;
     }
     if (bins == 8192) {
-        // two-wave transforms, one frame chain per 512-thread workgroup; all workgroups resident at once (2 per CU on 256
-        // CUs) when the batch allows: every chain recomputes one frame, so longer chains also mean less repeated work
-        long long G8 = (F * (long long)S) / 512;
-        G8 = G8 < 1 ? 1 : (G8 > 32 ? 32 : G8);
-        sp.frames_per_group = (int)G8;
+        // two-wave transforms, one frame chain per 512 work-items, two chains per workgroup but for the T128_STAGGER=0 launch (spectrum_geom.h)
+        const bool one_chain = !df && !last_fullc && !raw && stagger <= 0;
+        const SpectrumGeom geo = spectrum_geometry(one_chain ? SpecFamily::t128_one : SpecFamily::t128, F, S, bins, nf, S);
+        sp.frames_per_group = geo.G;
         sp.scale = scale;
         sp.out_pitch = F * (long long)bins;
         const RawSrc rs = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
@@ -2285,7 +2278,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
         memset(&none, 0, sizeof(none));
         const DecFuse &dfv = df ? *df : none;
         if (df) {  // the one-channel decimator rides in the transform's workgroups (two chains per workgroup, every sample format)
-            const dim3 grid(cdiv(cdiv(F, G8), 2), S), block(1024);
+            const dim3 grid(geo.wgs, S), block(1024);
             const int st = stagger > 0 ? stagger : 3;
             auto go = [&](auto kern) { launch(kern, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, st, rs, dfv); };
             switch (raw ? raw->fmt : -1) {
@@ -2299,7 +2292,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
         } else if (last_fullc) {
             // nothing is to run beside this launch: pass C's fifteen twiddles per work-item formed once and held (126 registers: four such
             // waves fill a SIMD's register file) -- 0.200 ms for the bench batch against 0.224
-            const dim3 grid(cdiv(cdiv(F, G8), 2), S), block(1024);
+            const dim3 grid(geo.wgs, S), block(1024);
             const int st = stagger > 0 ? stagger : 3;
             auto go = [&](auto kern) { launch(kern, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, st, rs, dfv); };
             switch (raw ? raw->fmt : -1) {
@@ -2311,7 +2304,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
             default: go(k_spectrum_t128<2, 4, false, true>); break;
             }
         } else if (raw) {  // raw-format frames take the two-chain kernel (one instantiation per sample format)
-            const dim3 grid(cdiv(cdiv(F, G8), 2), S), block(1024);
+            const dim3 grid(geo.wgs, S), block(1024);
             const int st = stagger > 0 ? stagger : 7;
             auto go = [&](auto kern) { launch(kern, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, st, rs, dfv); };
             switch (raw->fmt) {
@@ -2322,22 +2315,20 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
             default: go(k_spectrum_t128<2, 4>); break;
             }
         } else if (stagger > 0)  // two chains per 1024-item workgroup, the second `stagger` barrier intervals behind the first
-            launch(k_spectrum_t128<2, -1>, dim3(cdiv(cdiv(F, G8), 2), S), dim3(1024), s, d_in, d_out, (const float *)d_window,
+            launch(k_spectrum_t128<2, -1>, dim3(geo.wgs, S), dim3(1024), s, d_in, d_out, (const float *)d_window,
                    (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, stagger, rs, dfv);
         else
-            launch_lds(k_spectrum_t128<1, -1>, dim3(cdiv(F, G8), S), dim3(512), (size_t)pad_lds, s, d_in, d_out, (const float *)d_window,
+            launch_lds(k_spectrum_t128<1, -1>, dim3(geo.wgs, S), dim3(512), (size_t)pad_lds, s, d_in, d_out, (const float *)d_window,
                        (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, 0, rs, dfv);
         parity ^= 1;
         PG_HIP(hipGetLastError());
         return 0;
     }
-    const int groups = 4 / (int)(bins / nf);  // wave groups (frames in flight) per workgroup
-    long long G = (F * (long long)S) / (1024 * groups);  // aim for ~1024 workgroups; each group recomputes one extra frame
-    G = G < 1 ? 1 : (G > 16 ? 16 : G);
-    sp.frames_per_group = (int)G;
+    const SpectrumGeom geo = spectrum_geometry(SpecFamily::waves, F, S, bins, nf, S);  // 4 / ZP wave groups (frames in flight) per workgroup
+    sp.frames_per_group = geo.G;
     sp.scale = scale;
     sp.out_pitch = F * (long long)bins;
-    const dim3 grid(cdiv(F, G * groups), S), block(256);
+    const dim3 grid(geo.wgs, S), block(256);
     const float *pin = d_prev[parity];
     float *pout = d_prev[parity ^ 1];
     if (bins == 2048) launch(k_spectrum_1to1, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_tw_nf, pin, pout, sp);
@@ -2391,12 +2382,11 @@ int SpectrumCore::run_list_big(hipStream_t s, const float2 *d_in, long long in_p
         PG_HIP(hipMalloc((void **)&d_Y, sizeof(float2) * need));
         y_cap = need;
     }
-    long long G = (n_sel * bs * 8) / 512;
-    G = G < 1 ? 1 : (G > 16 ? 16 : G);
+    const SpectrumGeom geo = spectrum_geometry(SpecFamily::big, n_sel, S, bins, nf, bs);
     SpectrumParams sp;
     sp.in_pitch = in_pitch;
     sp.n_frames = n_sel;
-    sp.frames_per_group = (int)G;
+    sp.frames_per_group = geo.G;
     sp.scale = scale;
     sp.out_pitch = n_sel * (long long)bins;
     const bool b8 = raw && (raw->fmt == 0 || raw->fmt == 1);  // 8-bit pairs: the paired tile order (kernels_spectrum.h)
@@ -2423,7 +2413,7 @@ int SpectrumCore::run_list_big(hipStream_t s, const float2 *d_in, long long in_p
             default: go(k_big256_cols_list<4>); break;
             }
         }
-        launch(k_big256_rows, dim3((unsigned)(cdiv(n_sel, G) * 8), nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch,
+        launch(k_big256_rows, dim3(geo.wgs, nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch,
                (const float *)d_prev[parity] + s0 * kBigN, d_prev[parity ^ 1] + s0 * kBigN, sp);
     }
     parity ^= 1;
