@@ -106,8 +106,9 @@ typedef struct {
     uint32_t wfm;                /* 0: narrow branch (protect 30 kHz + FastFIR, receiver.cpp:903-993)
                                     1: WFM branch (protect 200 kHz, no band-pass, receiver.cpp:854-901) */
     uint32_t spectrum_bins;      /* 0: no spectrum; else FFT size (settings.cpp:59 default 4096) */
-    uint32_t fastfir_fft;        /* 0 -> 2048 (fastfir.cpp:65) */
-    uint32_t fastfir_taps;       /* 0 -> 1025 (fastfir.cpp:66) */
+    uint32_t fastfir_fft;        /* 0 -> 2048 (fastfir.cpp:65); 2048, 4096 or 8192 */
+    uint32_t fastfir_taps;       /* 0 -> 1025 (fastfir.cpp:66); 2 .. fastfir_fft/2 + 1, else PEBBLEGPU_E_INVALID: the overlap
+                                    (taps-1) may not exceed the block (fft - overlap) */
     uint32_t max_superframes;    /* capacity of one process call, in super-frames (>=1) */
     uint32_t audio_rate;         /* 0: audio stays at the demod rate (resampRate == 1, receiver.cpp:1002-1003); else
                                     Key_AudioOutputSampleRate (receiver.cpp:203, default 11025): the audio buffer is
@@ -594,8 +595,9 @@ typedef struct pebblegpu_streambank_config {
     uint32_t n_streams;
     uint32_t frame;          /* samples per spectrum frame */
     uint32_t spectrum_bins;
-    uint32_t fastfir_fft;    /* 0 -> 2048 */
-    uint32_t fastfir_taps;   /* 0 -> 1025 */
+    uint32_t fastfir_fft;    /* 0 -> 2048; 2048, 4096 or 8192 */
+    uint32_t fastfir_taps;   /* 0 -> 1025; 2 .. fastfir_fft/2 + 1, else PEBBLEGPU_E_INVALID (overlap taps-1 <= block fft-overlap);
+                                frame must be a multiple of the block */
     uint32_t max_frames;     /* capacity per call, frames per stream */
     uint32_t reserved[5];
 } pebblegpu_streambank_config;
@@ -619,7 +621,8 @@ int pebblegpu_streambank_synchronize(pebblegpu_streambank *sb);
  * host, bit for bit, and raw and float2 calls may alternate on one bank: the band-pass's overlap carries converted samples.
  * With 65536-sample frames and 65536 bins, or 2048-sample frames and 8192 bins, and the 2048-point band-pass, both kernels convert in
  * their own loads and no float2 copy of the streams exists; every other geometry is converted by one pass into a library-owned
- * float2 buffer first (allocated on the first such call).  pebblegpu_streambank_kernel_name tells which.
+ * float2 buffer first (allocated on the first such call).  Only the kernels the call asks for count (`what`): a band-pass-only call
+ * on the 2048-point band-pass converts in its loads whatever the display geometry.  pebblegpu_streambank_kernel_name tells which.
  * d_raw must be aligned to PEBBLEGPU_RAW_ALIGN bytes (the kernels read it with loads of up to 32 bytes).  Refused before anything is
  * queued, leaving the handle usable: unknown format or order (PEBBLEGPU_E_INVALID), n_samples not a multiple of the frame or above the
  * capacity (PEBBLEGPU_E_SIZE), a misaligned d_raw (PEBBLEGPU_E_INVALID). */
@@ -722,7 +725,9 @@ int pebblegpu_downconvert_process_device(pebblegpu_downconvert *d, const void *d
 int pebblegpu_downconvert_synchronize(pebblegpu_downconvert *d);
 
 typedef struct pebblegpu_fastfir pebblegpu_fastfir;
-/* CFastFIR::CFastFIR, fastfir.cpp:77-145 (fft/fir sizes are #defines there; 0,0 -> 2048,1025) */
+/* CFastFIR::CFastFIR, fastfir.cpp:77-145 (fft/fir sizes are #defines there; 0,0 -> 2048,1025).  fft_size 2048, 4096 or 8192;
+ * fir_size 2 .. fft_size/2 + 1, else PEBBLEGPU_E_INVALID: with a longer filter the overlap (fir_size-1) exceeds the block
+ * (fft_size - overlap), where the reference's own bookkeeping no longer computes the convolution */
 int pebblegpu_fastfir_create(int device, uint32_t fft_size, uint32_t fir_size, pebblegpu_fastfir **out);
 int pebblegpu_fastfir_destroy(pebblegpu_fastfir *f);
 /* void CFastFIR::SetupParameters(FLoCut, FHiCut, Offset, SampleRate), pebblelib/fastfir.h:57 */

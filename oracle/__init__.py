@@ -619,7 +619,9 @@ class Receiver:
     def __init__(self, fs, frames_per_buffer=2048, spectrum_bins=4096, fastfir_fft=2048, fastfir_taps=1025):
         self.n = frames_per_buffer
         self.bins = max(2048, spectrum_bins) if spectrum_bins else 0
-        self.cap = max(frames_per_buffer, fastfir_fft)
+        # what one frame can deliver: the band-pass holds back up to a block and then releases it with the frame's own samples (the C
+        # side's buffers are this size, po_receiver_new): 2048/513 (L = 1536) hands out 3072 samples on every third 2048-sample frame
+        self.cap = frames_per_buffer + fastfir_fft
         self.h = lib().po_receiver_new(int(fs), frames_per_buffer, spectrum_bins, fastfir_fft, fastfir_taps)
 
     def __del__(self):

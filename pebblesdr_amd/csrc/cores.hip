@@ -1200,7 +1200,9 @@ int FastFirCore::init(uint32_t channels, uint32_t fft_size, uint32_t fir_size, c
     fft_n = fft_size;
     taps = fir_size;
     if (!(fft_n == 2048 || fft_n == 4096 || fft_n == 8192)) return fail(PEBBLEGPU_E_UNSUPPORTED, "FastFIR FFT size %u not built", fft_n);
-    if (taps < 2 || taps > fft_n) return fail(PEBBLEGPU_E_INVALID, "FastFIR taps must be in [2, fft size]");
+    // overlap = taps-1 <= L = fft-overlap: one block back always reaches the whole overlap.  Longer filters have no reference semantics
+    // (CFastFIR refills only the last L samples of m_pFFTOverlapBuf per block) and cost more than the next FFT size with the same taps
+    if (taps < 2 || taps > fft_n / 2 + 1) return fail(PEBBLEGPU_E_INVALID, "FastFIR taps must be in [2, fft/2 + 1] (got %u for fft %u)", taps, fft_n);
     PG_HIP(hipMalloc((void **)&d_H, sizeof(float2) * (size_t)fft_n * C));
     PG_HIP(hipMemset(d_H, 0, sizeof(float2) * (size_t)fft_n * C));
     if (fft_n == 2048) { if (int rc = make_twiddles_t128(&d_tw128)) return rc; }
@@ -1256,8 +1258,8 @@ int FastFirCore::run_ext(hipStream_t s, const float2 *in, long long in_pitch, fl
     const int overlap = (int)taps - 1;
     const long long L = block_len();
     if (n % L != 0) return fail(PEBBLEGPU_E_SIZE, "FastFIR input %lld is not a multiple of its block %lld", n, L);
-    if (n < overlap) return fail(PEBBLEGPU_E_SIZE, "FastFIR input %lld is shorter than its overlap %d", n, overlap);
     if (n == 0) return 0;
+    // (init: overlap <= L <= n, so only block 0 reaches in front of its row -- served from d_tail -- and the row holds a whole overlap for the next call)
     const dim3 grid((unsigned)(n / L), C), block(256);
     const float2 *tail = d_tail;
     if (fft_n == 2048) {

@@ -9,6 +9,9 @@
 // exactly m_pFFTOverlapBuf (zero before the first call, fastfir.cpp:104-105).  A caller-owned buffer
 // without head-room passes `tail` instead ([channel][taps-1], refreshed by the host side after the call).
 //
+// taps-1 <= L (FastFirCore::init refuses longer filters): block b >= 1 starts at b L - (taps-1) >= 0, inside its own row, so with `tail`
+// only block 0 looks in front of the row, and it takes those samples from `tail`.
+//
 // Bound: HBM.  Algorithmic bytes per demod-rate sample: 8 read + 8 written (+ H once per block: with
 // taps-1 = N/2 the overlap doubles the read to 16 B unless L2 serves the second touch).
 #pragma once
@@ -173,7 +176,7 @@ static __global__ __launch_bounds__(128) void k_fastfir_t128_raw(long long in_pi
         for (int m = 0; m < E; m++) {
             const int i = t + 128 * m;
             if (i < overlap) v[m] = tl[i];
-            else v[m] = raw_load1<FMT>(raw, x0 + i);  // (x0 + i >= c * in_pitch: nothing in front of the row is read)
+            else v[m] = raw_load1<FMT>(raw, x0 + i);  // (i >= overlap: x0 + i >= c * in_pitch.  Blocks b >= 1 below rest on overlap <= L: b L - overlap >= 0)
         }
     } else {
 #pragma unroll

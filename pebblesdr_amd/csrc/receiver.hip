@@ -28,6 +28,8 @@ int Receiver::create(const pebblegpu_config *cfg)
     max_sf = cfg->max_superframes ? cfg->max_superframes : 1;
     if (C == 0 || fs <= 0 || fs > 4.0e9 || fs != std::floor(fs)) return fail(PEBBLEGPU_E_INVALID, "bad channel count or sample rate");
     if (nf < 256 || nf > 65535) return fail(PEBBLEGPU_E_INVALID, "frames_per_buffer must be 256..65535 (quint16, device_interfaces.h:32)");
+    // FastFirCore::init's rule, here in front of everything that is created: the super-frame below is computed from these sizes
+    if (!wfm && (ff_taps < 2 || ff_taps > ff_n / 2 + 1)) return fail(PEBBLEGPU_E_INVALID, "FastFIR taps must be in [2, fft/2 + 1] (got %u for fft %u)", ff_taps, ff_n);
     PG_HIP(hipSetDevice(device));
     PG_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     PG_HIP(hipStreamCreateWithFlags(&chain_stream_, hipStreamNonBlocking));
@@ -39,7 +41,6 @@ int Receiver::create(const pebblegpu_config *cfg)
     if (chain.stages.empty() || chain.stages.size() > (size_t)kMaxStages)
         return fail(PEBBLEGPU_E_UNSUPPORTED, "sample rate %.0f yields no decimation chain; not built", fs);
     demod_rate_int = (uint32_t)(int)chain.rate;  // int members, receiver.h:165-166
-    if (!wfm && (ff_taps < 2 || ff_taps > ff_n)) return fail(PEBBLEGPU_E_INVALID, "FastFIR taps must be in [2, fft size]");
     const long long L = wfm ? (long long)nf : (long long)ff_n - ((long long)ff_taps - 1);
     superframe = (uint64_t)chain.total * (uint64_t)lcm_ll(nf, L);
     const long long max_n = (long long)max_sf * (long long)superframe;

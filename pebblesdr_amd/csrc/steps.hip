@@ -448,14 +448,10 @@ int pebblegpu_fastfir_process(pebblegpu_fastfir *f, int n, const double *in, dou
         if (int rc = f->up(f->in.data(), f->pend.data() + done * 2, (size_t)take)) return rc;
         if (int rc = f->ff.run(f->stream, f->in, take, f->d_out, take)) return rc;
         if (int rc = f->down(out + (size_t)(*n_out) * 2, f->d_out, (size_t)take)) return rc;
-        // overlap for the next block = last taps-1 inputs (m_pFFTOverlapBuf)
+        // overlap for the next block = last taps-1 inputs (m_pFFTOverlapBuf); take >= L >= taps-1 (FastFirCore::init), so source and
+        // destination never overlap
         const int hist = f->in.hist;
-        if (take >= hist) {
-            PG_HIP(hipMemcpyAsync(f->in.data() - hist, f->in.data() + take - hist, sizeof(float2) * hist, hipMemcpyDeviceToDevice, f->stream));
-        } else {  // FIR longer than one block: shift what is kept, then append
-            PG_HIP(hipMemcpyAsync(f->in.data() - hist, f->in.data() - hist + take, sizeof(float2) * (hist - take), hipMemcpyDeviceToDevice, f->stream));
-            PG_HIP(hipMemcpyAsync(f->in.data() - take, f->in.data(), sizeof(float2) * take, hipMemcpyDeviceToDevice, f->stream));
-        }
+        PG_HIP(hipMemcpyAsync(f->in.data() - hist, f->in.data() + take - hist, sizeof(float2) * hist, hipMemcpyDeviceToDevice, f->stream));
         PG_HIP(hipStreamSynchronize(f->stream));
         done += take;
         *n_out += (int)take;

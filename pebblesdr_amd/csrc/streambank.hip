@@ -257,8 +257,12 @@ static int sb_queue_blocks(pebblegpu_streambank *sb, uint64_t n, uint32_t what)
 }
 
 
-// every kernel a raw call would run converts in its own loads (else the call is staged through k_normalize_iq as a whole)
-static bool sb_converts(const pebblegpu_streambank *sb) { return sb->ff.raw_ready() && (sb->sp.raw_ready() || sb->sp.raw_ready_big()); }
+// every kernel THIS raw call would run converts in its own loads (else the call is staged through k_normalize_iq as a whole): a call that
+// asks for the band-pass alone does not depend on the display transform's kernels, and the other way round
+static bool sb_converts(const pebblegpu_streambank *sb, uint32_t what)
+{
+    return (!(what & 1u) || sb->ff.raw_ready()) && (!(what & 2u) || sb->sp.raw_ready() || sb->sp.raw_ready_big());
+}
 
 extern "C" {
 
@@ -455,7 +459,7 @@ static int sb_run_raw(pebblegpu_streambank *sb, int fmt, int order, double gain,
 {
     const pg::RawSrc raw{d_raw, fmt, order, pg::raw_scale(fmt, gain), 0};
     sb->last_fmt = fmt;
-    sb->last_staged = !sb_converts(sb);
+    sb->last_staged = !sb_converts(sb, what);
     if (!sb->last_staged || n == 0) return sb_run(sb, nullptr, &raw, n, what);
     const size_t S = sb->cfg.n_streams;
     if (!sb->d_raw_stage) PG_HIP(hipMalloc((void **)&sb->d_raw_stage, sizeof(float2) * S * sb->cap));

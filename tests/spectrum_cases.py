@@ -51,8 +51,9 @@ ROWS = [
          "an odd number of chains: the last workgroup's second chain wholly dead, the last live chain one frame"),
     _row("t128-s8", "t128", "k_spectrum_t128 (raw s8)", 2048, 8192, 4, 257, 2, 129, 1, 1, "the same in the converting-loads instance", fmt=0),
     _row("any-1024-8192", "any", "k_spectrum_any", 1024, 8192, 3, 87, 2, 44, 1, 0, "ZP = 8"),
-    # (a frame of 3000 samples is no multiple of the band-pass's default block of 1024: 1049 taps make it 1000; the band-pass never runs)
-    _row("any-3000-4096", "any", "k_spectrum_any", 3000, 4096, 4, 513, 2, 257, 1, 0, "a frame that is no power of two (M = 4096)", taps=1049),
+    # (a frame of 3000 samples is no multiple of the band-pass's default block of 1024: 549 taps make it 1500 -- overlap 548, two blocks a
+    # frame; the band-pass never runs)
+    _row("any-3000-4096", "any", "k_spectrum_any", 3000, 4096, 4, 513, 2, 257, 1, 0, "a frame that is no power of two (M = 4096)", taps=549),
     _row("any-4096-16384", "any", "k_spectrum_any", 4096, 16384, 2, 257, 2, 129, 1, 0, "ZP = 4"),
     _row("big", "big", "k_big256_cols + k_big256_rows", 65536, 65536, 16, 9, 2, 5, 1, 0, "five chains per stream, the last ragged", chunk=2),
     _row("big-listed-s8", "big", "k_big256_cols_list (raw s8) + k_big256_rows", 65536, 65536, 16, 19, 2, 5, 1, 0,
