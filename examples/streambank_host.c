@@ -104,6 +104,8 @@ int main(void)
     cfg.max_frames = FRAMES_PER_CALL;
     CHECK(pebblegpu_streambank_create(&cfg, &sb));
     for (uint32_t s = 0; s < N_STREAMS; s++) CHECK(pebblegpu_streambank_set_bandpass(sb, s, -60e3, 60e3));
+    /* real front ends: DCRemoval and the first noise blanker ahead of both transforms, on every stream (a host flag, no wait) */
+    for (uint32_t s = 0; s < N_STREAMS; s++) CHECK(pebblegpu_streambank_set_conditioners(sb, s, PEBBLEGPU_COND_DC | PEBBLEGPU_COND_NB1, 1.0, 0.0));
 
     CHECK(pebblegpu_streambank_set_squelch(sb, 5, -20.0));   /* above what the tone averages over the pass band: closed, zeros in the block */
     CHECK(pebblegpu_streambank_set_squelch(sb, 2, -60.0));   /* (a threshold above -120 turns the S-meter on) */

@@ -1167,6 +1167,51 @@ const void *pebblegpu_streambank_signal_strength(const pebblegpu_streambank *sb,
 int pebblegpu_streambank_set_squelch(pebblegpu_streambank *sb, uint32_t stream, double squelch_db);
 int pebblegpu_streambank_iq_out_gate(pebblegpu_streambank *sb, uint64_t call_index, pebblegpu_stream_gate *out, uint32_t cap, uint32_t *n_frames);
 
+/* ------------------------------------------------------------------------------------------------
+ * Stream bank: input conditioners.  The four steps Receiver::processIQData runs ahead of both of the bank's transforms
+ * (application/receiver.cpp:814-823): DCRemoval, IQBalance, NoiseBlanker::ProcessBlock, NoiseBlanker::ProcessBlock2 -- in that order,
+ * per stream, all default-off.  flags: PEBBLEGPU_COND_* or'ed, as for pebblegpu_set_conditioners.
+ *
+ * _set_conditioners(sb, stream, flags, iq_gain, iq_phase) is HOST STATE consumed when the next call is queued: it touches no device
+ * memory and makes no device or stream synchronisation (the receivers' setter does; a bank runs from pinned slots with no synchronise in
+ * its loop).  The next conditioned call uploads the table from pinned staging in stream order.  Switching NB1 on resets its magnitude
+ * average and spike count, switching NB2 on its two averages (setNbEnabled / setNb2Enabled, noiseblanker.cpp:20-37), on the device, in
+ * stream order ahead of that call; NB1's delay line and the DC filter's state carry on.  A blanker that is off leaves its state alone (its
+ * averages start at 1, the constructor's value).  PEBBLEGPU_E_INVALID, handle usable afterwards: a NULL handle, a stream out of range,
+ * flags outside 0..15, a non-finite gain or phase.
+ *
+ * While ANY stream has a flag set every call with n > 0 conditions its samples first, whatever `what` asks for: the state advances with
+ * the sample stream.  The caller's input is never written: the first pass over it is out of place, into a float2 buffer the bank owns
+ * ([n_streams][capacity], allocated by the first conditioned call together with the state; a second one when NB1 is on, shared with the
+ * normalised copy of staged raw calls); streams with flags 0 are copied by that pass, bit for bit.  The band-pass, the display transform
+ * and with them the S-meter, the squelch gate, _map_spectrum and both rings read the conditioned rows.  A raw call is staged:
+ * k_normalize_iq, the conditioners, the float2 kernels (pebblegpu_streambank_kernel_name: "k_normalize_iq + k_condition + <the float2
+ * route>"; a float2 call: "k_condition + <route>"); raw and float2 calls still continue each other.  pebblegpu_streambank_last_ms which 0
+ * and 1 include the conditioners.  With no flag ever set, or all cleared again, a call queues exactly what it queued before this
+ * interface existed: the same routes, names and bits.
+ * IQBalance restarts its adaptive terms every cfg.frame samples (the reference's numSamples).
+ *
+ * _conditioned(sb, &samples_per_stream, &pitch_samples): a device pointer to float2 [stream][pitch], the rows the LAST call's transforms
+ * read; valid until the next call, complete after pebblegpu_streambank_synchronize.  NULL and 0 when the last call conditioned nothing.
+ *
+ * The kernels (csrc/kernels_condition.h) are parallel in time: a stream's call is cut into chunks of 2048 samples, one workgroup each.
+ * Per stage: every chunk's contribution from a zero entry state, a fixed-order scan of those per stream, then every chunk again from its
+ * true entry state.  Every reduction has a fixed order: the same call sequence gives the same bits.  Against the serial form:
+ *   DC removal: fp64 state as there; a chunk's entry state is M^2048 applied to the one before plus the chunk's zero-state end state
+ *     instead of 2048 sequential steps -- another fp64 rounding order, far below the float the samples are stored in.  No warm-up; the
+ *     state carried between calls is the last chunk's end state.
+ *   NB1 / NB2 magnitude averages, a <- (float)(0.999 a + 0.001 mag): every run of 8 samples takes its entry value from the fp64
+ *     recurrence (rounded to float once) and then rounds per step as the reference does.  The serial float chain drifts from the exact
+ *     recurrence by about 2e-6 relative, this form by at most 8 roundings: the averages agree to the last bits, NOT bit for bit, and a
+ *     blanker decision mag > 3.3 avg that lies within those bits can fall the other way.  So can the same samples cut into other calls.
+ *   NB2's complex average (pole 0.75, fp64 in the reference too): entry values from the same scan; its value is used rounded to float.
+ *   NB1's spike count: exact (maps on the 8 counts, composed in order).  Its output is the input two samples earlier (DelayLine(8, 2));
+ *     the two samples in front of a call are carried state.
+ *   IQBalance: the reference's arithmetic step by step, one workgroup per (stream, frame).
+ * ---------------------------------------------------------------------------------------------- */
+int pebblegpu_streambank_set_conditioners(pebblegpu_streambank *sb, uint32_t stream, int flags, double iq_gain, double iq_phase);
+const void *pebblegpu_streambank_conditioned(const pebblegpu_streambank *sb, uint64_t *samples_per_stream, uint64_t *pitch_samples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ from .binding import (  # noqa: F401
     PANE_SPECTRUM, PANE_ZOOM, DisplayPane, display_pane,
     AUTO_SCALE_MAX, AUTO_SCALE_MIN, DisplayScale, DISPLAY_SCALE, auto_scale_row,
     StreamGateEntry, STREAM_GATE, GATE_ROW_CARRIED, GATE_ROW_NONE, signal_strength_row,
+    COND_DC, COND_IQBALANCE, COND_NB1, COND_NB2,
 )
 from .steps import Mixer, Decimator, DownConvert, FastFIR, Demod, Spectrum, Morse  # noqa: F401
 

@@ -63,9 +63,11 @@ SYMBOLS = [
     "pebblegpu_streambank_display_set_auto_scale", "pebblegpu_streambank_display_rescale", "pebblegpu_streambank_display_scale",
     "pebblegpu_signal_strength_row", "pebblegpu_streambank_enable_signal_strength", "pebblegpu_streambank_signal_strength",
     "pebblegpu_streambank_set_squelch", "pebblegpu_streambank_iq_out_gate",
+    "pebblegpu_streambank_set_conditioners", "pebblegpu_streambank_conditioned",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
+COND_DC, COND_IQBALANCE, COND_NB1, COND_NB2 = 1, 2, 4, 8  # PEBBLEGPU_COND_*
 
 
 class PebbleGpuError(RuntimeError):
@@ -630,6 +632,9 @@ def _declare(L):
     L.pebblegpu_streambank_signal_strength.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.pebblegpu_streambank_set_squelch.argtypes = [vp, u32, dbl]
     L.pebblegpu_streambank_iq_out_gate.argtypes = [vp, u64, vp, u32, C.POINTER(u32)]
+    L.pebblegpu_streambank_set_conditioners.argtypes = [vp, u32, C.c_int, dbl, dbl]
+    L.pebblegpu_streambank_conditioned.restype = vp
+    L.pebblegpu_streambank_conditioned.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     for who in ("receiver", "streambank"):
         getattr(L, "pebblegpu_%s_display_set_auto_scale" % who).argtypes = [vp, u32]
         getattr(L, "pebblegpu_%s_display_rescale" % who).argtypes = [vp]
@@ -1388,6 +1393,22 @@ class StreamBank:
     def set_squelch(self, stream, squelch_db):
         """closed = avgDb < squelch_db per (stream, frame): a closed frame is zeros in the IQ ring's block; -120 and below never closes"""
         check(self.L, self.L.pebblegpu_streambank_set_squelch(self.h, int(stream), float(squelch_db)))
+
+    # ---- input conditioners (receiver.cpp:814-823: DCRemoval, IQBalance, NB1, NB2) ----
+    def set_conditioners(self, stream, flags, iq_gain=1.0, iq_phase=0.0):
+        """flags: COND_* or'ed; a host flag, consumed by the next call (no wait).  While any stream has one set every call conditions first"""
+        check(self.L, self.L.pebblegpu_streambank_set_conditioners(self.h, int(stream), int(flags), float(iq_gain), float(iq_phase)))
+
+    def conditioned(self):
+        """-> complex64 [streams, n]: the rows the last call's transforms read, or None when it conditioned nothing"""
+        n, pitch = C.c_uint64(), C.c_uint64()
+        p = self.L.pebblegpu_streambank_conditioned(self.h, C.byref(n), C.byref(pitch))
+        if not p or not int(n.value):
+            return None
+        self.synchronize()
+        out = np.empty((self.n_streams, int(pitch.value)), dtype=np.complex64)
+        check(self.L, self.L.pebblegpu_memcpy_d2h(self.device, out.ctypes.data_as(C.c_void_p), C.c_void_p(p), out.nbytes))
+        return out[:, : int(n.value)]
 
     def iq_out_gate(self, call_index, cap=1 << 16):
         """the gate trailer of the handed-out IQ block of call_index -> STREAM_GATE [selected streams, frames]"""

@@ -3,7 +3,10 @@
 #include <cmath>
 #include "kernels_display.h"
 #include "kernels_strength.h"
+#include "kernels_condition.h"
 #include "receiver.h"
+#include "design.h"
+#include <string>
 
 using pg::fail;
 
@@ -17,7 +20,7 @@ struct pebblegpu_streambank {
     float2 *d_tail = nullptr, *d_tail_alt = nullptr, *d_filt = nullptr;  // (the two overlap buffers swap after every band-pass call)
     float *d_spec = nullptr;
     uint64_t cap = 0, last_n = 0, last_frames = 0;
-    hipEvent_t ev[4] = {};
+    hipEvent_t ev[5] = {};           // (ev[4]: behind the conditioners, where a side-by-side call forks)
     bool timed = false;
     float2 *d_raw_stage = nullptr;   // raw calls of a geometry without converting loads: the normalised copy (allocated on first use)
     pg::IngestRing ingest;           // the pinned double buffer of pebblegpu_streambank_ingest_* (ingest.h)
@@ -61,6 +64,29 @@ struct pebblegpu_streambank {
     void *h_stage[kStage] = {};
     hipEvent_t stage_ev[kStage] = {};
     int stage_next = 0;
+    // the input conditioners (kernels_condition.h): host flags consumed when the next call is queued; the setter touches no device state
+    struct CondHost { int flags = 0, reset = 0; double gain = 1.0, phase = 0.0; };
+    std::vector<CondHost> cond;          // per stream
+    uint32_t n_cond = 0;                 // streams with a flag set: while there are any every call conditions its samples first
+    bool cond_dirty = false;             // a setter changed something since the last upload
+    bool cond_ready = false;             // the state block holds the constructors' values (written on the stream by the first conditioned call)
+    int cond_mask = 0;                   // the flags of all streams or'ed, as last uploaded
+    pg::ScanParams<1> cond_dc;           // DCRemoval's high-pass
+    pg::CondAvg cond_mag{}, cond_cpx{};  // the blankers' averages
+    double cond_m[4] = {};               // the high-pass's transition matrix on (w1, w1 - w2) to the power of a chunk
+    float2 *d_cond[2] = {};              // [n_streams][capacity] each; d_cond[1] IS d_raw_stage (allocated on first use, either way)
+    pg::CondPar *d_cond_par = nullptr;
+    pg::CondState *d_cond_state = nullptr;
+    double *d_cond_sum = nullptr, *d_cond_entry = nullptr;  // [n_streams][chunks][4]
+    unsigned *d_cond_map = nullptr;      // [n_streams][chunks]
+    int *d_cond_count = nullptr;         // [n_streams][chunks]
+    float2 *d_cond_prev = nullptr;       // [n_streams][2]
+    void *h_cond[kStage] = {};           // pinned staging of the parameter table, reused like h_stage
+    hipEvent_t cond_ev[kStage] = {};
+    int cond_next = 0;
+    const float2 *last_cond = nullptr;   // the rows the last call's transforms read, if it conditioned any
+    uint64_t last_cond_n = 0;
+    std::string name_buf[3];             // pebblegpu_streambank_kernel_name of a conditioned call
     uint64_t gate_bytes = 0;             // per IQ slot, behind the rows: room for n_selected * max_frames entries
     bool slot_gated[pg::kEgressMaxSlots] = {};      // the IQ slot's block carries the gate trailer ...
     uint32_t slot_frames[pg::kEgressMaxSlots] = {}; // ... of this many frames per selected stream
@@ -264,6 +290,124 @@ static bool sb_converts(const pebblegpu_streambank *sb, uint32_t what)
     return (!(what & 1u) || sb->ff.raw_ready()) && (!(what & 2u) || sb->sp.raw_ready() || sb->sp.raw_ready_big());
 }
 
+
+// The conditioners of one call, queued on the bank's stream: *in (the caller's rows, or with `owned` the normalised copy of a raw call in
+// d_cond[1]; rows n apart) becomes the bank-owned rows the call's transforms read.  The caller's rows are never written: the first pass
+// over them is out of place.  DC removal, IQ balance and NB2 may run in place on rows the bank owns; NB1 never (its output is its input
+// two samples earlier), it goes from one of the two buffers to the other.
+static int sb_condition(pebblegpu_streambank *sb, const float2 **in, bool owned, uint64_t n)
+{
+    const uint32_t S = sb->cfg.n_streams;
+    const size_t ncmax = (size_t)((sb->cap + pg::kCondChunk - 1) / pg::kCondChunk);
+    if (!sb->cond_ready) {  // first use: the design, the state and the scans' scratch
+        const pg::design::Biquad h = pg::design::biquad_highpass(10, 0.7071, sb->cfg.sample_rate);  // DCRemoval ctor, dcremoval.cpp:5-9
+        const double c[5] = {h.b0, h.b1, h.b2, h.a1, h.a2};
+        pg::fill_scan_section(sb->cond_dc.sec[0], pg::kBiquadDf2, c);
+        // the chunk-to-chunk transition on (w1, w1 - w2) (k_cond_dc_combine): -a1 - a2 - 1 is 1e-11 at 20 Msps, formed in long double
+        const double a12 = (double)(-(long double)h.a1 - (long double)h.a2), a121 = (double)(-(long double)h.a1 - (long double)h.a2 - 1.0L);
+        const pg::design::M2 m = pg::design::m2_pow(pg::design::M2{a12, h.a2, a121, h.a2}, (uint64_t)pg::kCondChunk);
+        sb->cond_m[0] = m.a; sb->cond_m[1] = m.b; sb->cond_m[2] = m.c; sb->cond_m[3] = m.d;
+        auto avg = [](pg::CondAvg &a, double d, double g) {
+            a.d = d;
+            a.g = g;
+            for (int k = 0; k < 6; k++) a.P[k] = std::pow(d, (double)(pg::kSeg << k));
+            a.chunk = std::pow(d, (double)pg::kCondChunk);
+        };
+        avg(sb->cond_mag, 0.999, 0.001);
+        avg(sb->cond_cpx, 0.75, 0.25);
+        if (!sb->d_cond_par) PG_HIP(hipMalloc((void **)&sb->d_cond_par, sizeof(pg::CondPar) * S));
+        if (!sb->d_cond_state) PG_HIP(hipMalloc((void **)&sb->d_cond_state, sizeof(pg::CondState) * S));
+        if (!sb->d_cond_sum) PG_HIP(hipMalloc((void **)&sb->d_cond_sum, sizeof(double) * 4 * ncmax * S));
+        if (!sb->d_cond_entry) PG_HIP(hipMalloc((void **)&sb->d_cond_entry, sizeof(double) * 4 * ncmax * S));
+        if (!sb->d_cond_map) PG_HIP(hipMalloc((void **)&sb->d_cond_map, sizeof(unsigned) * ncmax * S));
+        if (!sb->d_cond_count) PG_HIP(hipMalloc((void **)&sb->d_cond_count, sizeof(int) * ncmax * S));
+        if (!sb->d_cond_prev) PG_HIP(hipMalloc((void **)&sb->d_cond_prev, sizeof(float2) * 2 * S));
+        for (int i = 0; i < pebblegpu_streambank::kStage; i++) {
+            if (!sb->h_cond[i]) PG_HIP(hipHostMalloc(&sb->h_cond[i], sizeof(pg::CondPar) * S, hipHostMallocDefault));
+            if (!sb->cond_ev[i]) PG_HIP(hipEventCreateWithFlags(&sb->cond_ev[i], hipEventDisableTiming));
+        }
+    }
+    hipStream_t st = sb->stream;
+    if (sb->cond_dirty || !sb->cond_ready) {
+        // the table in stream order: behind the kernels of earlier calls that read it, ahead of this call's.  The host waits only if the
+        // copy queued from this pinned slot kStage uploads ago has not completed.
+        const int i = sb->cond_next;
+        sb->cond_next = (i + 1) % pebblegpu_streambank::kStage;
+        PG_HIP(hipEventSynchronize(sb->cond_ev[i]));
+        pg::CondPar *t = static_cast<pg::CondPar *>(sb->h_cond[i]);
+        sb->cond_mask = 0;
+        for (uint32_t s = 0; s < S; s++) {
+            const auto &h = sb->cond[s];
+            t[s] = pg::CondPar{h.flags, h.reset, h.gain, h.phase};
+            sb->cond_mask |= h.flags;
+        }
+        PG_HIP(hipMemcpyAsync(sb->d_cond_par, t, sizeof(pg::CondPar) * S, hipMemcpyHostToDevice, st));
+        PG_HIP(hipEventRecord(sb->cond_ev[i], st));
+        pg::launch(pg::k_cond_reset, dim3((S + 63) / 64), dim3(64), st, sb->d_cond_state, (const pg::CondPar *)sb->d_cond_par, (int)S, sb->cond_ready ? 0 : 1);
+        PG_HIP(hipGetLastError());
+        for (auto &h : sb->cond) h.reset = 0;
+        sb->cond_dirty = false;
+        sb->cond_ready = true;
+    }
+    const int mask = sb->cond_mask;
+    auto buffer = [&](int i) -> int {
+        if (sb->d_cond[i]) return 0;
+        if (i == 1 && sb->d_raw_stage) { sb->d_cond[1] = sb->d_raw_stage; return 0; }
+        PG_HIP(hipMalloc((void **)&sb->d_cond[i], sizeof(float2) * (size_t)S * sb->cap));
+        if (i == 1) sb->d_raw_stage = sb->d_cond[1];
+        return 0;
+    };
+    const long long N = (long long)n;
+    const int nc = (int)((n + pg::kCondChunk - 1) / pg::kCondChunk);
+    const dim3 all((unsigned)nc, S), but_last((unsigned)(nc - 1), S), per_stream(S), wave(64);
+    const pg::CondPar *par = sb->d_cond_par;
+    const float2 *cur = *in;
+    bool mine = owned;
+    if (mask & 3) {  // DC removal; IQ balance alone needs rows it may write, and gets them from the same pass (it copies a stream without DC)
+        if (!mine) { if (int rc = buffer(0)) return rc; }
+        float2 *dst = mine ? const_cast<float2 *>(cur) : sb->d_cond[0];
+        if (mask & 1) {
+            if (nc > 1) pg::launch(pg::k_cond_dc_sum, but_last, wave, st, cur, N, sb->cond_dc, par, sb->d_cond_sum, nc);
+            pg::launch(pg::k_cond_dc_combine, per_stream, wave, st, (const double *)sb->d_cond_sum, sb->d_cond_entry, (const pg::CondState *)sb->d_cond_state, par,
+                       sb->cond_m[0], sb->cond_m[1], sb->cond_m[2], sb->cond_m[3], nc);
+        }
+        if ((mask & 1) || !mine)
+            pg::launch(pg::k_cond_dc_apply, all, wave, st, cur, N, dst, N, N, sb->cond_dc, par, (const double *)sb->d_cond_entry, sb->d_cond_state, nc);
+        cur = dst;
+        mine = true;
+    }
+    if (mask & 2) pg::launch(pg::k_cond_iq, dim3((unsigned)(n / sb->cfg.frame), S), wave, st, const_cast<float2 *>(cur), N, (int)sb->cfg.frame, par);
+    if (mask & 4) {
+        const int to = cur == sb->d_cond[0] ? 1 : 0;
+        if (int rc = buffer(to)) return rc;
+        float2 *dst = sb->d_cond[to];
+        if (nc > 1) pg::launch(pg::k_cond_nb_sum<1>, but_last, wave, st, cur, N, sb->cond_mag, sb->cond_cpx, par, sb->d_cond_sum, nc);
+        pg::launch(pg::k_cond_nb_combine<1>, per_stream, wave, st, (const double *)sb->d_cond_sum, sb->d_cond_entry, (const pg::CondState *)sb->d_cond_state, par,
+                   sb->cond_mag.chunk, sb->cond_cpx.chunk, nc);
+        if (nc > 1) pg::launch(pg::k_cond_nb1_map, but_last, wave, st, cur, N, sb->cond_mag, par, (const double *)sb->d_cond_entry, sb->d_cond_map, nc);
+        pg::launch(pg::k_cond_nb1_map_combine, per_stream, wave, st, (const unsigned *)sb->d_cond_map, sb->d_cond_count, sb->d_cond_prev, sb->d_cond_state, par, cur,
+                   N, N, nc);
+        pg::launch(pg::k_cond_nb1_apply, all, wave, st, cur, N, dst, N, N, sb->cond_mag, par, (const double *)sb->d_cond_entry, (const int *)sb->d_cond_count,
+                   (const float2 *)sb->d_cond_prev, sb->d_cond_state, nc);
+        cur = dst;
+        mine = true;
+    }
+    if (mask & 8) {
+        if (!mine) { if (int rc = buffer(0)) return rc; }
+        float2 *dst = mine ? const_cast<float2 *>(cur) : sb->d_cond[0];
+        if (nc > 1) pg::launch(pg::k_cond_nb_sum<2>, but_last, wave, st, cur, N, sb->cond_mag, sb->cond_cpx, par, sb->d_cond_sum, nc);
+        pg::launch(pg::k_cond_nb_combine<2>, per_stream, wave, st, (const double *)sb->d_cond_sum, sb->d_cond_entry, (const pg::CondState *)sb->d_cond_state, par,
+                   sb->cond_mag.chunk, sb->cond_cpx.chunk, nc);
+        pg::launch(pg::k_cond_nb2_apply, all, wave, st, cur, N, dst, N, N, sb->cond_mag, sb->cond_cpx, par, (const double *)sb->d_cond_entry, sb->d_cond_state, nc);
+        cur = dst;
+    }
+    PG_HIP(hipGetLastError());
+    *in = cur;
+    sb->last_cond = cur;
+    sb->last_cond_n = n;
+    return 0;
+}
+
 extern "C" {
 
 int pebblegpu_streambank_destroy(pebblegpu_streambank *sb)
@@ -286,10 +430,14 @@ int pebblegpu_streambank_destroy(pebblegpu_streambank *sb)
     sb->sp.release();
     sb->ingest.release();
     void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec, sb->d_raw_stage, sb->d_iq_tab, sb->disp.d_tab, sb->d_scale,
-                 sb->d_win, sb->d_squelch, sb->d_smeter, sb->d_carry[0], sb->d_carry[1]};
+                 sb->d_win, sb->d_squelch, sb->d_smeter, sb->d_carry[0], sb->d_carry[1],
+                 sb->d_cond[0], sb->d_cond_par, sb->d_cond_state, sb->d_cond_sum, sb->d_cond_entry, sb->d_cond_map, sb->d_cond_count,
+                 sb->d_cond_prev};  // (d_cond[1] is d_raw_stage)
     for (void *q : p) if (q) (void)hipFree(q);
     for (void *q : sb->h_stage) if (q) (void)hipHostFree(q);
     for (hipEvent_t e : sb->stage_ev) if (e) (void)hipEventDestroy(e);
+    for (void *q : sb->h_cond) if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : sb->cond_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sb->ev) if (e) (void)hipEventDestroy(e);
     delete sb;
     return 0;
@@ -313,6 +461,7 @@ int pebblegpu_streambank_create(const pebblegpu_streambank_config *cfg, pebblegp
     sb->bp_lo.assign(cfg->n_streams, -1.f);
     sb->bp_hi.assign(cfg->n_streams, 1.f);
     sb->squelch.assign(cfg->n_streams, -120.f);
+    sb->cond.assign(cfg->n_streams, pebblegpu_streambank::CondHost());
     int rc = 0;
     auto body = [&]() -> int {
         PG_HIP(hipSetDevice(cfg->device));
@@ -384,10 +533,13 @@ static int sb_check_n(const pebblegpu_streambank *sb, uint64_t n)
     return 0;
 }
 // one call: float2 rows `in`, or (raw != nullptr) rows still in the device's sample format that the kernels convert in their loads
-static int sb_run(pebblegpu_streambank *sb, const float2 *in, const pg::RawSrc *raw, uint64_t n, uint32_t what)
+// (owned: `in` is the bank's own normalised copy, which the conditioners may write)
+static int sb_run(pebblegpu_streambank *sb, const float2 *in, const pg::RawSrc *raw, uint64_t n, uint32_t what, bool owned = false)
 {
     sb->last_n = 0;
     sb->last_frames = 0;
+    sb->last_cond = nullptr;
+    sb->last_cond_n = 0;
     if (n == 0) return sb_queue_blocks(sb, 0, what);
     // The update timer, on the host before anything is queued.  A call without the spectrum advances the sample clock and nothing else:
     // it selects no frame and neither starts nor restarts the timer.
@@ -397,6 +549,12 @@ static int sb_run(pebblegpu_streambank *sb, const float2 *in, const pg::RawSrc *
     if (what & 2u) sb->ut.advance(sb->ups, sb->period_ms, F, sb->cfg.frame, (uint64_t)std::llround(sb->cfg.sample_rate), &sb->sel);
     else sb->ut.next += F;
     PG_HIP(hipEventRecord(sb->ev[0], sb->stream));
+    // While any stream has a conditioner flag set every call conditions its samples first, whatever it asks for: the state advances
+    // with the sample stream (receiver.cpp:814-823 run ahead of everything else)
+    const bool conditioned = sb->n_cond != 0;
+    if (conditioned) {
+        if (int rc = sb_condition(sb, &in, owned, n)) return rc;
+    }
     // Both asked for: the band-pass (bound by its two transforms per block: vector units + LDS) and the display transform (the 65536-point
     // one is bound by what it moves through HBM) read the same input and share nothing else.  Side by side on two streams (fork at the
     // call's start event, join at its end; PEBBLEGPU_SB_SIDE=1 when the bank is created) they do NOT overlap: 0.4345 / 0.4368 ms per
@@ -406,7 +564,8 @@ static int sb_run(pebblegpu_streambank *sb, const float2 *in, const pg::RawSrc *
     const bool side = sb->side_ok && (what & 3u) == 3u;
     sb->side = side;
     hipStream_t fs = side ? sb->stream2 : sb->stream;
-    if (side) PG_HIP(hipStreamWaitEvent(fs, sb->ev[0], 0));
+    if (side && conditioned) PG_HIP(hipEventRecord(sb->ev[4], sb->stream));
+    if (side) PG_HIP(hipStreamWaitEvent(fs, sb->ev[conditioned ? 4 : 0], 0));
     sb->last_bp = (what & 1u) != 0;
     sb->last_sp = (what & 2u) != 0;
     if (what & 1u) {
@@ -459,13 +618,14 @@ static int sb_run_raw(pebblegpu_streambank *sb, int fmt, int order, double gain,
 {
     const pg::RawSrc raw{d_raw, fmt, order, pg::raw_scale(fmt, gain), 0};
     sb->last_fmt = fmt;
-    sb->last_staged = !sb_converts(sb, what);
+    sb->last_staged = !sb_converts(sb, what) || (sb->n_cond && n);  // (the conditioners read and write float2 rows)
     if (!sb->last_staged || n == 0) return sb_run(sb, nullptr, &raw, n, what);
     const size_t S = sb->cfg.n_streams;
     if (!sb->d_raw_stage) PG_HIP(hipMalloc((void **)&sb->d_raw_stage, sizeof(float2) * S * sb->cap));
+    sb->d_cond[1] = sb->d_raw_stage;
     // (the rows of d_raw are n pairs apart, so S * n pairs are one run; the side stream forks behind it, at the call's start event)
     if (int rc = pg::run_normalize_iq(fmt, order, 1.0, d_raw, (long long)(S * n), sb->d_raw_stage, sb->stream, false, &raw.scale)) return rc;
-    return sb_run(sb, sb->d_raw_stage, nullptr, n, what);
+    return sb_run(sb, sb->d_raw_stage, nullptr, n, what, true);
 }
 
 int pebblegpu_streambank_process_raw(pebblegpu_streambank *sb, int format, int iq_order, double gain, const void *d_raw, uint64_t n, uint32_t what)
@@ -499,9 +659,9 @@ int pebblegpu_streambank_process_ingested(pebblegpu_streambank *sb, uint32_t slo
     return sb->ingest.mark_in_flight(*g, sb->stream, sb->stream2);
 }
 
-const char *pebblegpu_streambank_kernel_name(const pebblegpu_streambank *sb, int which)
+// the route of a call: last_fmt -1 float2 input, else the raw format; last_staged: through k_normalize_iq as a whole
+static const char *sb_route_name(const pebblegpu_streambank *sb, int which, int last_fmt, bool last_staged)
 {
-    if (!sb || !sb->timed) return "";
     static const char *const kFf[6] = {"k_fastfir_t128", "k_fastfir_t128 (raw s8)", "k_fastfir_t128 (raw u8)", "k_fastfir_t128 (raw s16)",
                                        "k_fastfir_t128 (raw f32)", "k_fastfir_t128 (raw wav16)"};
     static const char *const kBig[6] = {"k_big256_cols + k_big256_rows", "k_big256_cols (raw s8) + k_big256_rows", "k_big256_cols (raw u8) + k_big256_rows",
@@ -511,12 +671,12 @@ const char *pebblegpu_streambank_kernel_name(const pebblegpu_streambank *sb, int
                                          "k_spectrum_t128 (raw f32)", "k_spectrum_t128 (raw wav16)"};
     static const char *const kW64[6] = {"k_spectrum_w64", "k_spectrum_w64 (raw s8)", "k_spectrum_w64 (raw u8)", "k_spectrum_w64 (raw s16)",
                                         "k_spectrum_w64 (raw f32)", "k_spectrum_w64 (raw wav16)"};
-    const int r = sb->last_fmt >= 0 && !sb->last_staged ? sb->last_fmt + 1 : 0;  // 0: the float2 instances
+    const int r = last_fmt >= 0 && !last_staged ? last_fmt + 1 : 0;  // 0: the float2 instances
     const pg::SpectrumCore &sp = sb->sp;
     if (which == 1) {
         if (!sb->last_bp) return "";
-        if (sb->ff.fft_n == 2048) return sb->last_staged ? "k_normalize_iq + k_fastfir_t128" : kFf[r];
-        return sb->last_staged ? "k_normalize_iq + k_fastfir" : "k_fastfir";
+        if (sb->ff.fft_n == 2048) return last_staged ? "k_normalize_iq + k_fastfir_t128" : kFf[r];
+        return last_staged ? "k_normalize_iq + k_fastfir" : "k_fastfir";
     }
     if (which == 2 && sb->last_sp && sb->last_listed) {  // a gated call: the frame-list kernels, or none
         static const char *const kBigL[6] = {"k_big256_cols_list + k_big256_rows", "k_big256_cols_list (raw s8) + k_big256_rows",
@@ -525,21 +685,60 @@ const char *pebblegpu_streambank_kernel_name(const pebblegpu_streambank *sb, int
         static const char *const kQ128L[6] = {"k_spectrum_list_q128", "k_spectrum_list_q128 (raw s8)", "k_spectrum_list_q128 (raw u8)",
                                               "k_spectrum_list_q128 (raw s16)", "k_spectrum_list_q128 (raw f32)", "k_spectrum_list_q128 (raw wav16)"};
         if (!sb->last_frames) return "";
-        if (sp.big) return sb->last_staged ? "k_normalize_iq + k_big256_cols_list + k_big256_rows" : kBigL[r];
-        if (sp.any) return sb->last_staged ? "k_normalize_iq + k_spectrum_list_any" : "k_spectrum_list_any";
-        return sb->last_staged ? "k_normalize_iq + k_spectrum_list_q128" : kQ128L[r];
+        if (sp.big) return last_staged ? "k_normalize_iq + k_big256_cols_list + k_big256_rows" : kBigL[r];
+        if (sp.any) return last_staged ? "k_normalize_iq + k_spectrum_list_any" : "k_spectrum_list_any";
+        return last_staged ? "k_normalize_iq + k_spectrum_list_q128" : kQ128L[r];
     }
     if (which == 2) {
         if (!sb->last_sp) return "";
-        if (sp.big && sp.tun.big_split32) return sb->last_staged ? "k_normalize_iq + k_big_cols + k_big_rows" : "k_big_cols + k_big_rows";
-        if (sp.big) return sb->last_staged ? "k_normalize_iq + k_big256_cols + k_big256_rows" : kBig[r];
-        if (sp.any) return sb->last_staged ? "k_normalize_iq + k_spectrum_any" : "k_spectrum_any";
-        if (sp.per_q) return sb->last_staged ? "k_normalize_iq + k_spectrum_q128" : "k_spectrum_q128";
-        if (sp.bins == 8192) return sb->last_staged ? (sp.use_w64 ? "k_normalize_iq + k_spectrum_w64" : "k_normalize_iq + k_spectrum_t128") : sp.use_w64 ? kW64[r] : kT128[r];
-        if (sp.bins == 4096) return sb->last_staged ? "k_normalize_iq + k_spectrum<2>" : "k_spectrum<2>";
-        return sb->last_staged ? "k_normalize_iq + k_spectrum_1to1" : "k_spectrum_1to1";
+        if (sp.big && sp.tun.big_split32) return last_staged ? "k_normalize_iq + k_big_cols + k_big_rows" : "k_big_cols + k_big_rows";
+        if (sp.big) return last_staged ? "k_normalize_iq + k_big256_cols + k_big256_rows" : kBig[r];
+        if (sp.any) return last_staged ? "k_normalize_iq + k_spectrum_any" : "k_spectrum_any";
+        if (sp.per_q) return last_staged ? "k_normalize_iq + k_spectrum_q128" : "k_spectrum_q128";
+        if (sp.bins == 8192) return last_staged ? (sp.use_w64 ? "k_normalize_iq + k_spectrum_w64" : "k_normalize_iq + k_spectrum_t128") : sp.use_w64 ? kW64[r] : kT128[r];
+        if (sp.bins == 4096) return last_staged ? "k_normalize_iq + k_spectrum<2>" : "k_spectrum<2>";
+        return last_staged ? "k_normalize_iq + k_spectrum_1to1" : "k_spectrum_1to1";
     }
     return "";
+}
+
+const char *pebblegpu_streambank_kernel_name(const pebblegpu_streambank *sb, int which)
+{
+    if (!sb || !sb->timed) return "";
+    if (!sb->last_cond) return sb_route_name(sb, which, sb->last_fmt, sb->last_staged);
+    // a conditioned call: [k_normalize_iq +] k_condition + the float2 instances
+    if (which < 1 || which > 2) return "";
+    const char *base = sb_route_name(sb, which, -1, false);
+    if (!*base) return "";
+    std::string &b = const_cast<pebblegpu_streambank *>(sb)->name_buf[which];
+    b = std::string(sb->last_fmt >= 0 ? "k_normalize_iq + " : "") + "k_condition + " + base;
+    return b.c_str();
+}
+
+const void *pebblegpu_streambank_conditioned(const pebblegpu_streambank *sb, uint64_t *samples_per_stream, uint64_t *pitch_samples)
+{
+    if (samples_per_stream) *samples_per_stream = 0;
+    if (pitch_samples) *pitch_samples = 0;
+    if (!sb || !sb->last_cond) return nullptr;
+    if (samples_per_stream) *samples_per_stream = sb->last_cond_n;
+    if (pitch_samples) *pitch_samples = sb->last_cond_n;
+    return sb->last_cond;
+}
+int pebblegpu_streambank_set_conditioners(pebblegpu_streambank *sb, uint32_t stream, int flags, double iq_gain, double iq_phase)
+{
+    if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (stream >= sb->cfg.n_streams) return fail(PEBBLEGPU_E_INVALID, "stream %u out of range", stream);
+    if (flags < 0 || flags > 15) return fail(PEBBLEGPU_E_INVALID, "conditioner flags %d: PEBBLEGPU_COND_* or'ed, 0..15", flags);
+    if (!std::isfinite(iq_gain) || !std::isfinite(iq_phase)) return fail(PEBBLEGPU_E_INVALID, "the IQ gain and phase factors must be finite");
+    // host state only: the next call uploads the table and resets what was switched on, in stream order
+    auto &h = sb->cond[stream];
+    h.reset |= (flags & ~h.flags) & (PEBBLEGPU_COND_NB1 | PEBBLEGPU_COND_NB2);  // setNbEnabled(true) / setNb2Enabled(true), noiseblanker.cpp:20-37
+    sb->n_cond += (flags ? 1u : 0u) - (h.flags ? 1u : 0u);
+    h.flags = flags;
+    h.gain = iq_gain;
+    h.phase = iq_phase;
+    sb->cond_dirty = true;
+    return 0;
 }
 
 const void *pebblegpu_streambank_filtered(const pebblegpu_streambank *sb, uint64_t *n, uint64_t *pitch)
