@@ -113,7 +113,8 @@ typedef struct {
     uint32_t audio_rate;         /* 0: audio stays at the demod rate (resampRate == 1, receiver.cpp:1002-1003); else
                                     Key_AudioOutputSampleRate (receiver.cpp:203, default 11025): the audio buffer is
                                     CFractResampler::Resample(n, demodRate / audio_rate, ...) of the demodulated frames
-                                    (receiver.cpp:994-1001, pebblelib/fractresampler.cpp:149-195) */
+                                    (receiver.cpp:994-1001, pebblelib/fractresampler.cpp:149-195).  Rates above the demod rate
+                                    (upsampling) are accepted: the audio rows hold n * audio_rate / demodRate + frames + 8 samples */
     uint32_t hires_bins;         /* 0: no zoomed spectrum (m_useHiRes off); else the bin count of SignalSpectrum::zoomed
                                     (application/signalspectrum.cpp:89-113; settings.cpp:61 default 2048): fftSpectrum, BlackmanHarris
                                     over frames_per_buffer samples, of every DECIMATED frame of every channel -- m_sampleBuf at the

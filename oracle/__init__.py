@@ -666,6 +666,9 @@ class Receiver:
 
     def set_audio_rate(self, rate):
         lib().po_receiver_set_audio_rate(self.h, int(rate))
+        if rate:  # upsampling: a frame's block comes out longer than it went in, and process() must have room for it
+            dt = min(self.demod_rate(False), self.demod_rate(True)) / float(rate)
+            self.cap = max(self.cap, int(self.cap / dt) + 4)
 
     def process(self, frame, want_spectrum=True):
         """one frame -> (audio ndarray (possibly empty), spectrum ndarray or None)"""

@@ -70,18 +70,6 @@ void fill_scan_section(ScanSection &s, int type, const double *c)
     }
 }
 
-// how many kSub-sample sub-chunks of zero-state warm-up make radius^samples < tol; -1 if more than 8
-int scan_warm_subchunks(const ScanSection *secs, int nsec, double tol)
-{
-    double r = 0;
-    for (int i = 0; i < nsec; i++) r = std::fmax(r, design::spectral_radius(section_matrix(secs[i])));
-    if (r <= 0) return 1;
-    if (r >= 1) return -1;
-    const double need = std::log(tol) / std::log(r) * 1.5 + 64;  // margin for the non-normal transient
-    const int subs = (int)std::ceil(need / kSub);
-    return subs <= 8 ? (subs < 1 ? 1 : subs) : -1;
-}
-
 int make_twiddles(int n, float2 **d_tw)
 {
     // per-pass tables in the layout fft_lds.h reads (fft_tw_off)
@@ -1464,9 +1452,6 @@ int WfmCore::init(uint32_t channels, double demod_rate, long long max_n, const T
     const design::Biquad br = design::biquad_notch(19000.0, 5, rate);    // demod_wfm.cpp:178
     const double brc[5] = {br.b0, br.b1, br.b2, br.a1, br.a2};
     fill_scan_section(dn.sec[1], kBiquadDf2, brc);
-    // samples are stored fp32 (eps 6e-8): a start-up residue below 1e-10 of the state is invisible
-    warm_lp = scan_warm_subchunks(lp.sec, 1, 1e-10);
-    warm_dn = scan_warm_subchunks(dn.sec, 2, 1e-10);
     const std::vector<double> h = design::fir_lowpass(0, 1.0, 60.0, 15000.0, 1.4 * 15000.0, rate);  // demod_wfm.cpp:175
     ntaps = (int)h.size();
     std::vector<float> hf(kMaxTaps, 0.f);

@@ -297,14 +297,6 @@ M2 m2_pow(M2 x, uint64_t e)
     }
     return M2{(double)r[0], (double)r[1], (double)r[2], (double)r[3]};
 }
-double spectral_radius(const M2 &x)
-{
-    const double tr = x.a + x.d, det = x.a * x.d - x.b * x.c, disc = tr * tr / 4 - det;
-    if (disc < 0) return std::sqrt(det);
-    const double r = std::sqrt(disc);
-    return std::fmax(std::fabs(tr / 2 + r), std::fabs(tr / 2 - r));
-}
-
 bool cascade_impulse(const std::vector<double> &fir_prefix, const double *one_pole_avg_a, const std::vector<Biquad> &biquads, double tol,
                      int max_len, std::vector<double> &h)
 {

@@ -100,7 +100,6 @@ bool cascade_impulse(const std::vector<double> &fir_prefix, const double *one_po
 struct M2 { double a, b, c, d; };
 M2 m2_mul(const M2 &x, const M2 &y);
 M2 m2_pow(M2 x, uint64_t e);
-double spectral_radius(const M2 &x);
 
 }  // namespace design
 }  // namespace pg

@@ -7,9 +7,13 @@
 // precomputed transition powers M^(kSeg*2^k), and each lane re-runs its samples from its true entry state.
 // Recurrence arithmetic is fp64 (the DC-block pole 0.9999 needs it); samples are stored fp32.
 //
-// Across workgroups a long single-channel stream is cut into chunks; a chunk that does not start at
-// the call boundary warms up on `warm_sub` preceding sub-chunks from a zero state (host picks warm_sub
-// so the pole radius^samples < 1e-13, else it selects the exact sequential mode, warm_sub < 0).
+// Every launch in the library runs k_iir_scan in its exact sequential mode: grid.x = 1, sub_per_block = all of the call's
+// sub-chunks, warm_sub = -1 -- ONE workgroup per channel walks the call sub-chunk by sub-chunk and carries the true state, read
+// from and written back to the same slot (AmCore::run, WfmCore::run's sequential path, the pre-chain DC removal).  The
+// last sub-chunk of a call may be ragged (nv < kSub: lanes past the end run zero steps and write nothing; the carried state is the
+// one after the last valid sample, held by lane (nv - 1) / kSeg).  The kernel's parameters also describe a mode that cuts a call
+// into chunks across workgroups, each warming up on `warm_sub` preceding sub-chunks from a zero state; nothing launches it (the
+// AM DC block's 0.9999 pole forbids it, and the fast-pole WFM cascades are folded into k_wfm_fir instead) and no test reaches it.
 #pragma once
 #include "params.h"
 #include "tail_refresh.h"

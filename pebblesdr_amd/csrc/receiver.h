@@ -39,7 +39,6 @@ struct HistBuf {
 };
 
 void fill_scan_section(ScanSection &s, int type, const double *c);
-int scan_warm_subchunks(const ScanSection *secs, int nsec, double tol);
 int make_twiddles(int n, float2 **d_tw);
 int make_twiddles_t128(float2 **d_tw);
 int make_twiddles_t128q(float2 **d_tw);  // four tables, the pruned transform's per-work-item factor folded in (k_spectrum_t128)
@@ -379,7 +378,7 @@ struct WfmCore {
     bool lp_on = false;
     ScanParams<1> lp;
     ScanParams<2> dn;
-    int warm_lp = -1, warm_dn = -1, parity = 0;
+    int parity = 0;
     double *d_lp_state[2] = {nullptr, nullptr}, *d_dn_state[2] = {nullptr, nullptr};
     bool fused = false;             // single-kernel FIR-ised path (k_wfm_fir); else the multi-kernel sequential fallback
     int L4 = 0, Llp = 1;            // fused: combined audio response (padded to 16) and low-pass response lengths

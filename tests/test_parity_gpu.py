@@ -207,8 +207,9 @@ def test_sam_pll_demod_step(gpu_lib, oracle_mod):
 
 @pytest.mark.parametrize("fsw", [256000, 312500, 390625])
 def test_wfm_mono_demod_step(gpu_lib, oracle_mod, fsw):
-    """processDataMono at the three WFM rates SURVEY.md 8(a-3) lists; the last call is long enough to run the
-    chunk-parallel (warm-up) scan path across several workgroups, with a ragged tail."""
+    """processDataMono at the three WFM rates SURVEY.md 8(a-3) lists.  All three run the one-kernel path (k_wfm_fir, no scan at
+    all); the last call spans twenty of its 1024-output workgroups with a ragged last one.  The sequential path, the Llp == 1
+    branch and the short-call history merge are in tests/test_demod_geometry_gpu.py."""
     import pebblesdr_amd as P
     n = 2048
     tw = np.arange(15 * n) / fsw
