@@ -1473,6 +1473,10 @@ int WfmCore::init(uint32_t channels, double demod_rate, long long max_n, const T
             std::vector<float> hlf(hl.begin(), hl.end()), haf(ha.begin(), ha.end());
             PG_HIP(hipMalloc((void **)&d_h, sizeof(float) * (L4 + 16)));
             PG_HIP(hipMemcpy(d_h, haf.data(), sizeof(float) * (L4 + 16), hipMemcpyHostToDevice));
+            std::vector<float> hm((size_t)wfm_mx_table_floats(L4));
+            wfm_mx_fill_taps(haf.data(), L4, hm.data());
+            PG_HIP(hipMalloc((void **)&d_hm, sizeof(float) * hm.size()));
+            PG_HIP(hipMemcpy(d_hm, hm.data(), sizeof(float) * hm.size(), hipMemcpyHostToDevice));
             PG_HIP(hipMalloc((void **)&d_hlp, sizeof(float) * Llp));
             PG_HIP(hipMemcpy(d_hlp, hlf.data(), sizeof(float) * Llp, hipMemcpyHostToDevice));
             for (int i = 0; i < 2; i++) {
@@ -1496,7 +1500,7 @@ int WfmCore::init(uint32_t channels, double demod_rate, long long max_n, const T
 void WfmCore::release()
 {
     a.release(); b.release(); c.release();
-    void *p[] = {d_taps, d_lp_state[0], d_lp_state[1], d_dn_state[0], d_dn_state[1], d_h, d_hlp, d_xtail[0], d_xtail[1], d_stereo, d_pilot, d_hilb, d_stereo_list};
+    void *p[] = {d_taps, d_lp_state[0], d_lp_state[1], d_dn_state[0], d_dn_state[1], d_h, d_hm, d_hlp, d_xtail[0], d_xtail[1], d_stereo, d_pilot, d_hilb, d_stereo_list};
     d_stereo = nullptr;
     d_pilot = nullptr;
     d_hilb = nullptr;
@@ -1506,7 +1510,7 @@ void WfmCore::release()
     for (void *q : p) if (q) (void)hipFree(q);
     d_taps = nullptr;
     d_lp_state[0] = d_lp_state[1] = d_dn_state[0] = d_dn_state[1] = nullptr;
-    d_h = nullptr; d_hlp = nullptr; d_xtail[0] = d_xtail[1] = nullptr;
+    d_h = nullptr; d_hm = nullptr; d_hlp = nullptr; d_xtail[0] = d_xtail[1] = nullptr;
 }
 int WfmCore::set_stereo(uint32_t ch, bool on)
 {
@@ -1602,7 +1606,7 @@ int WfmCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *ou
             }
         }
         launch_lds(k_wfm_fir, dim3(groups + extra, C), dim3(512), wfm_fir_lds_bytes(L4, Llp), s, in, in_pitch, (const float2 *)d_xtail[parity],
-                   out, out_pitch, n, wp, (const float *)d_h, (const float *)d_hlp, (const unsigned char *)d_stereo, groups, tj);
+                   out, out_pitch, n, wp, (const float *)d_hm, (const float *)d_hlp, (const unsigned char *)d_stereo, groups, tj);
         PG_HIP(hipGetLastError());
         if (n < Lx) {
             PG_HIP(hipMemcpy2DAsync(nt, sizeof(float2) * Lx, d_xtail[parity] + n, sizeof(float2) * Lx, sizeof(float2) * (Lx - n), C, hipMemcpyDeviceToDevice, s));

@@ -17,6 +17,7 @@
 #pragma once
 #include "params.h"
 #include "tail_refresh.h"
+#include "wfm_fir_geom.h"
 
 namespace pg {
 
@@ -156,12 +157,12 @@ static __global__ __launch_bounds__(64) void k_iir_scan(const float2 *__restrict
 // the previous call's last Lx input samples (`xtail`) -- and all outputs are computed independently: no scans, no
 // warm-up runs, no sequential carries.  (The scan kernels above remain for slow poles: AM's DC block, other rates.)
 //
-// One workgroup per kWfmOutB = 1024 outputs.  x -> LDS (one pad slot per 8 samples); low-pass (fp32, Llp taps): each
-// work-item owns 8 consecutive outputs and slides a register window over the padded samples -> LDS; discriminator ->
-// LDS as fp32 in blocks of 4; audio FIR: each work-item owns 4 consecutive outputs, slides a two-block window through
-// the history (one 16-byte LDS read per 4 taps against 16 FMAs), multiplies in fp32 and folds every 16-tap partial
-// sum into an fp64 accumulator (fp64 FMA runs at a fraction of the fp32 rate here; the fold keeps the rounding of a
-// 600..1500-tap sum at the 1e-7 level).
+// One workgroup per kWfmOutB = 1024 outputs.  x -> LDS as a plane of real and a plane of imaginary parts; low-pass (fp32, Llp
+// taps) on each plane and the audio FIR: banded-Toeplitz matrix products on the fp32 matrix instruction (phases 2 and 4 below,
+// wfm_fir_geom.h); discriminator between them -> LDS as fp32.  The audio FIR folds every 16-term fp32 partial sum into an
+// fp64 accumulator (fp64 FMA runs at a fraction of the fp32 rate here; the fold keeps the rounding of a 600..1500-tap sum at
+// the 1e-7 level).  wfm_fir_lds_bytes still counts the layout of the plain-FMA kernel (padded 8-byte samples); the planes fit
+// inside it (wfm_fir_db_offset, wfm_fir_lp_offset), and it decides which rates take this path.
 constexpr int kWfmOutB = 1024;    // outputs per workgroup
 constexpr int kWfmIrMax = 1536;   // longest combined audio response (taps, multiple of 16) that fits the LDS budget
 constexpr int kWfmLpMax = 64;     // longest low-pass response
@@ -181,7 +182,7 @@ __host__ __device__ inline size_t wfm_fir_lds_bytes(int L4, int Llp)
 // xtail: [channel][L4 + Llp] input samples preceding in[0] (zeros before the first call)
 static __global__ __launch_bounds__(512) void k_wfm_fir(const float2 *__restrict__ in, long long in_pitch, const float2 *__restrict__ xtail,
                                                         float2 *__restrict__ out, long long out_pitch, long long n, WfmFirParams wp,
-                                                        const float *__restrict__ h, const float *__restrict__ hlp,
+                                                        const float *__restrict__ hm /* the audio response as wfm_mx_fill_taps lays it out */, const float *__restrict__ hlp,
                                                         const unsigned char *__restrict__ no_prefilter /* [channel] or null: dmFMS, see WfmCore */,
                                                         int n_fir_groups, TailJobs tails /* run by the workgroups behind the first n_fir_groups: the call's tail refresh rides on this launch */)
 {
@@ -192,112 +193,125 @@ static __global__ __launch_bounds__(512) void k_wfm_fir(const float2 *__restrict
     HIP_DYNAMIC_SHARED(float2, dyn)
     const int L4 = wp.L4, Llp = wp.Llp;
     const int ND = kWfmOutB + L4, NL = (ND + 1 + 7) & ~7, NX = NL + Llp - 1, Lx = L4 + Llp;
-    float2 *xs = dyn;                                                    // NX samples, position j + j/8
-    float2 *lpb = xs + (NX + NX / 8 + 1);                                // NL (+1)
-    float *db = reinterpret_cast<float *>(lpb + NL + 1);                 // ND
-    __shared__ float hl[kWfmLpMax];
+    // LDS, as floats from `dyn`: the samples as two planes xr, xi of NXp = NX rounded up to 4 (inside what wfm_fir_lds_bytes counts
+    // for NX padded 8-byte samples); the low-passed samples as two planes lr, li of NL directly in front of db; db (ND) on a 16-byte
+    // boundary -- every matrix operand of phases 2 and 4 is one aligned 16-byte read, a wave's 64 of them 1024 contiguous bytes.
+    const int NXp = wfm_lp_plane(NX);
+    float *xr = reinterpret_cast<float *>(dyn), *xi = xr + NXp;
+    float *lr = xr + wfm_fir_lp_offset(kWfmOutB, L4, Llp), *li = lr + NL;
+    float *db = xr + wfm_fir_db_offset(kWfmOutB, L4, Llp);
+    __shared__ __attribute__((aligned(16))) float hl[kWfmLpMax];
     const int tid = threadIdx.x, c = blockIdx.y;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;  // (wave-uniform: the matrix loops' counters stay scalar)
     const long long s = (long long)blockIdx.x * kWfmOutB;
     const float2 *x = in + (long long)c * in_pitch;
     const float2 *xt = xtail + (long long)c * Lx;
     const bool raw_iq = no_prefilter != nullptr && no_prefilter[c] != 0;  // processDataStereo has no 75 kHz low-pass: the identity response
     if (tid < kWfmLpMax) hl[tid] = tid < Llp ? (raw_iq ? (tid == 0 ? 1.f : 0.f) : hlp[tid]) : 0.f;
-    // ---- 1. input samples x0 .. x0+NX-1, x0 = s - L4 - Llp (history from the tail, nothing past n) ----
+    // ---- 1. input samples x0 .. x0+NX-1, x0 = s - L4 - Llp (history from the tail, nothing past n), zeros up to NXp ----
     const long long x0 = s - Lx;
-    for (int j = tid; j < NX; j += 512) {
+    for (int j = tid; j < NXp; j += 512) {
         const long long g = x0 + j;
         float2 v = make_float2(0.f, 0.f);
-        if (g < 0) v = xt[Lx + g];
-        else if (g < n) v = x[g];
-        xs[j + (j >> 3)] = v;
+        if (j < NX) {
+            if (g < 0) v = xt[Lx + g];
+            else if (g < n) v = x[g];
+        }
+        xr[j] = v.x;
+        xi[j] = v.y;
     }
     __syncthreads();
-    // ---- 2. low-pass: lpb[k] = sum_m hlp[m] * xs[k + Llp - 1 - m], k < NL.  Work-item: outputs 8a .. 8a+7; with the
-    //         pad its 9-slot stride spreads a wave's 8-byte reads over all banks. ----
-    for (int a8 = tid * 8; a8 < NL; a8 += 512 * 8) {
-        float2 w[8], acc[8];
+    typedef float v4f_t __attribute__((ext_vector_type(4)));
+    const v4f_t zero4 = {0.f, 0.f, 0.f, 0.f};
+    auto chain = [](const float4 &a, const float4 &b, v4f_t c) {
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, c, 0, 0, 0);
+    };
+    // ---- 2. low-pass: l[o] = sum_m hlp[m] * x[o + Llp - 1 - m], o < NL, on both planes, as the banded-Toeplitz product of phase 4
+    //         (wfm_fir_geom.h): a job is 256 outputs of one plane, K = Llp + 15 in groups of 16, one fp32 chain per job.  The A
+    //         operands (at most 20 taps per lane) stay in registers for all jobs. ----
+    {
+        float4 ta[kWfmLpGroupsMax];
 #pragma unroll
-        for (int r = 0; r < 8; r++) {
-            acc[r] = make_float2(0.f, 0.f);
-            const int j = a8 + r + Llp - 1;
-            w[r] = xs[j + (j >> 3)];  // tap 0 operands: w[r] = x for output a8 + r
-        }
-        for (int m = 0; m < Llp; m++) {
-            const float t = hl[m];
+        for (int g = 0; g < kWfmLpGroupsMax; g++) {
+            float t4[4];
 #pragma unroll
-            for (int r = 0; r < 8; r++) {
-                acc[r].x = fmaf(t, w[r].x, acc[r].x);
-                acc[r].y = fmaf(t, w[r].y, acc[r].y);
+            for (int j = 0; j < 4; j++) {
+                const int m = Llp - 1 + (lane & 15) - wfm_mx_k(g, lane, j);  // wfm_lp_tap: hl holds zeros from Llp on
+                t4[j] = m >= 0 && m < kWfmLpMax ? hl[m] : 0.f;
             }
-#pragma unroll
-            for (int r = 7; r > 0; r--) w[r] = w[r - 1];
-            const int j = a8 + Llp - 2 - m;  // next tap's operand of output a8 (may run below 0 on the last turn)
-            w[0] = j >= 0 ? xs[j + (j >> 3)] : make_float2(0.f, 0.f);
+            ta[g] = make_float4(t4[0], t4[1], t4[2], t4[3]);
         }
+        const int Glp = wfm_lp_groups(Llp), jobs = wfm_lp_jobs(NL);
+        for (int job = wave; job < jobs; job += 8) {
+            const int t = job >> 1;
+            const float *xp = (job & 1) ? xi : xr;
+            v4f_t acc = zero4;
 #pragma unroll
-        for (int r = 0; r < 8; r++) lpb[a8 + r] = acc[r];
+            for (int g = 0; g < kWfmLpGroupsMax; g++)
+                if (g < Glp) {
+                    const int idx = wfm_lp_x(t, g, lane, 0);
+                    const bool ok = idx < NXp;  // (both multiples of 4) the last tile's columns reach past the samples: zeros
+                    float4 b = *reinterpret_cast<const float4 *>(xp + (ok ? idx : 0));
+                    if (!ok) b = make_float4(0.f, 0.f, 0.f, 0.f);
+                    acc = chain(ta[g], b, acc);
+                }
+            const int o = wfm_mx_out(t, lane, 0);  // four consecutive outputs
+            if (o < NL) *reinterpret_cast<float4 *>(((job & 1) ? li : lr) + o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        }
     }
     __syncthreads();
     // ---- 3. discriminator d[s - L4 + i], i < ND (demod_wfm.cpp:217) ----
     for (int i = tid; i < ND; i += 512) {
-        const float2 c0 = lpb[i + 1], c1 = lpb[i];
+        const float2 c0 = make_float2(lr[i + 1], li[i + 1]), c1 = make_float2(lr[i], li[i]);
         db[i] = wp.gain * atan2f(c1.x * c0.y - c0.x * c1.y, c1.x * c0.x + c1.y * c0.y);
     }
     __syncthreads();
-    // ---- 4. y[s + 4 tid + r] = sum_p h[p] * d[s + 4 tid + r - p] ----
-    //         Taps are fetched 16 at a time, one chunk (64 FMAs per work-item) ahead of their use, with VECTOR loads of
-    //         a lane-invariant address: scalar loads share the LDS wait counter and return out of order, which would
-    //         force a full wait at every LDS read; taps parked in LDS cost four 16-byte broadcast reads per chunk and per
-    //         wave (measured: 0.027 -> 0.040 ms).  The next history block is read from LDS one group ahead.
-    //         The workgroup's two halves split the taps: work-items 0..255 run p in [0, L4/2) rounded to 16, 256..511 the rest, and
-    //         the halves' fp64 partial sums meet in LDS (this kernel runs on an otherwise idle GPU behind the display transform:
-    //         its own serial length is the call's time).
-    const int half = tid >> 8, ot = tid & 255;
-    const int p_split = ((L4 >> 1) + 15) & ~15;
-    const int p_lo = half ? p_split : 0, p_hi = half ? L4 : p_split;
-    const float4 *blk = reinterpret_cast<const float4 *>(db) + ot + (L4 >> 2) - (p_lo >> 2);
-    float4 cur = blk[0], nxt = blk[-1];
+    // ---- 4. y[s + o] = sum_p h[p] * db[L4 + o - p] as a banded-Toeplitz product on the fp32 matrix instruction (wfm_fir_geom.h has
+    //         the index arithmetic): o = 256 cg + 16 a + b, Y[b][a] = sum_k A[b][k] B[k][a] with A[b][k] = h[L4 + b - k] from the
+    //         table `hm` and B[k][a] = db[256 cg + 16 a + k], k < L4 + 16 in groups of 16.  Wave w: column group w & 3, K half
+    //         w >> 2.  Per group and lane one 16-byte tap load (vector memory, coalesced), one 16-byte LDS read (a wave reads 1024
+    //         contiguous bytes) and four v_mfma_f32_16x16x4_f32 that start from C = 0: bit for bit a 16-term fmaf chain, folded
+    //         into fp64 as the plain-FMA loop this replaces folded every 16 taps (the rounding of a 600..1500-tap sum stays at the
+    //         1e-7 level).  Four groups per turn of the loop: four independent chains with their loads in flight together (a
+    //         fetch-ahead written here comes out of the compiler as a load at the point of use; two groups per turn measured the
+    //         same 7 us at the benchmark's rate).  The K halves' fp64 partial sums meet in LDS (this kernel runs on an otherwise
+    //         idle GPU behind the display transform: its own serial length is the call's time).
+    const int cg = wave & (kWfmMxColGroups - 1), kh = wave >> 2;
+    const int G = wfm_mx_groups(L4), g_lo = wfm_mx_half_begin(G, kh), g_hi = wfm_mx_half_begin(G, kh + 1);
+    const float4 *bp = reinterpret_cast<const float4 *>(db + wfm_mx_db(cg, g_lo, lane, 0));  // 4 float4 per group; the last index read is ND - 1
+    const float4 *ap = reinterpret_cast<const float4 *>(hm) + g_lo * 64 + lane;              // 64 float4 per group
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    int vz = 0;
-    opaque(vz);  // a zero the compiler must treat as per-lane: keeps the tap loads on the vector memory path
-    const float4 *hv = reinterpret_cast<const float4 *>(h) + vz;  // (16-byte loads: four per chunk)
-    float4 hn[4];
+    int g = g_lo;
+    for (; g + 3 < g_hi; g += 4, ap += 256, bp += 16) {
+        const float4 t0 = ap[0], t1 = ap[64], t2 = ap[128], t3 = ap[192];
+        const float4 b0 = bp[0], b1 = bp[4], b2 = bp[8], b3 = bp[12];
+        const v4f_t c0 = chain(t0, b0, zero4), c1 = chain(t1, b1, zero4), c2 = chain(t2, b2, zero4), c3 = chain(t3, b3, zero4);
 #pragma unroll
-    for (int u = 0; u < 4; u++) hn[u] = hv[(p_lo >> 2) + u];
-    for (int p0 = p_lo; p0 < p_hi; p0 += 16) {  // L4 is a multiple of 16; h carries 16 zeros past it
-        float ht[16];
-#pragma unroll
-        for (int u = 0; u < 4; u++) { ht[4 * u] = hn[u].x; ht[4 * u + 1] = hn[u].y; ht[4 * u + 2] = hn[u].z; ht[4 * u + 3] = hn[u].w; }
-#pragma unroll
-        for (int u = 0; u < 4; u++) hn[u] = hv[((p0 + 16) >> 2) + u];
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            blk -= 1;
-            const float4 prev = nxt;
-            nxt = blk[-1];  // on the very last group this reads the 16 bytes in front of db (the end of lpb): in bounds, unused
-            const float h0 = ht[4 * g], h1 = ht[4 * g + 1], h2 = ht[4 * g + 2], h3 = ht[4 * g + 3];
-            a0 = fmaf(h0, cur.x, a0); a1 = fmaf(h0, cur.y, a1); a2 = fmaf(h0, cur.z, a2); a3 = fmaf(h0, cur.w, a3);
-            a0 = fmaf(h1, prev.w, a0); a1 = fmaf(h1, cur.x, a1); a2 = fmaf(h1, cur.y, a2); a3 = fmaf(h1, cur.z, a3);
-            a0 = fmaf(h2, prev.z, a0); a1 = fmaf(h2, prev.w, a1); a2 = fmaf(h2, cur.x, a2); a3 = fmaf(h2, cur.y, a3);
-            a0 = fmaf(h3, prev.y, a0); a1 = fmaf(h3, prev.z, a1); a2 = fmaf(h3, prev.w, a2); a3 = fmaf(h3, cur.x, a3);
-            cur = prev;
-        }
-        acc[0] += (double)a0; acc[1] += (double)a1; acc[2] += (double)a2; acc[3] += (double)a3;
+        for (int r = 0; r < 4; r++) acc[r] += ((double)c0[r] + (double)c1[r]) + ((double)c2[r] + (double)c3[r]);
     }
-    // the second half's sums through LDS (xs is free: every work-item is past the low-pass), added in the first half
+    for (; g < g_hi; g++, ap += 64, bp += 4) {  // the groups a half has beyond a multiple of four
+        const v4f_t c0 = chain(ap[0], bp[0], zero4);
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc[r] += (double)c0[r];
+    }
+    // the second half's sums through LDS (the sample planes are free: every work-item is past the low-pass), added in the first half
     __syncthreads();
-    double *part = reinterpret_cast<double *>(xs);
-    if (half) {
+    double *part = reinterpret_cast<double *>(xr);
+    const int ot = tid & 255;
+    if (kh) {
 #pragma unroll
         for (int r = 0; r < 4; r++) part[r * 256 + ot] = acc[r];
     }
     __syncthreads();
-    if (half) return;
-    float2 *y = out + (long long)c * out_pitch + s + 4 * ot;
+    if (kh) return;
+    const int o = wfm_mx_out(cg, lane, 0);  // this lane's four results: outputs o .. o + 3
+    float2 *y = out + (long long)c * out_pitch + s + o;
 #pragma unroll
     for (int r = 0; r < 4; r++)
-        if (s + 4 * ot + r < n) {
+        if (s + o + r < n) {
             const float v = (float)(acc[r] + part[r * 256 + ot]);
             y[r] = make_float2(v, v);  // mono: left = right (demod_wfm.cpp:229-230)
         }

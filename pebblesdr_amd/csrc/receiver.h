@@ -382,7 +382,8 @@ struct WfmCore {
     double *d_lp_state[2] = {nullptr, nullptr}, *d_dn_state[2] = {nullptr, nullptr};
     bool fused = false;             // single-kernel FIR-ised path (k_wfm_fir); else the multi-kernel sequential fallback
     int L4 = 0, Llp = 1;            // fused: combined audio response (padded to 16) and low-pass response lengths
-    float *d_h = nullptr;           // [L4 + 16]
+    float *d_h = nullptr;           // [L4 + 16]  (k_wfm_lmr_fir)
+    float *d_hm = nullptr;          // [wfm_mx_table_floats(L4)]: the same response in the order k_wfm_fir's matrix operand walks (wfm_fir_geom.h)
     float *d_hlp = nullptr;         // [Llp]
     float2 *d_xtail[2] = {nullptr, nullptr};  // [C][L4 + Llp] input history, ping-pong
     const float2 *deferred_in = nullptr;      // set by run(): the history copy is left to tail_jobs()
