@@ -131,7 +131,8 @@ typedef struct {
     uint32_t demod_rate_int;     /* the int the Receiver stores and designs filters with (receiver.h:165-166) */
     uint32_t dec_by2_stages;     /* Decimator::decBy2Stages() */
     uint32_t total_decimation;   /* D */
-    uint32_t chain_len;          /* merged stages */
+    uint32_t chain_len;          /* merged stages; 0 where no design fits the rate (below 75 kHz narrow, below 500 kHz WFM): the
+                                    reference's "No decimation" (decimator.cpp:155-160), D = 1, the demodulator at the input rate */
     uint32_t stage_taps[16];     /* 0 => CIC3 */
     uint32_t stage_stride[16];
     uint64_t superframe;         /* input samples per super-frame = D * frames_per_buffer */

@@ -36,6 +36,9 @@ struct CallFacts {
     bool spec_raw_ready = false, spec_dec_ready = false;  // SpectrumCore::raw_ready / dec_ready
     // the Tuning fields that take part
     bool pipeline = false, fuse_dec = false, bank_pipe_extev = false, bank_pipe_timed_ev = false;
+    // a receiver without a decimator (an empty chain); the defaults leave every other receiver's routes as they are
+    bool dec_mix_in_consumer = false;  // the chain is empty and the band-pass has a variant that mixes in its loads (DecimCore::mix_in_consumer_ready)
+    bool tap_post_mixer = false;       // the POST_MIXER tap is on: the mixed rows must exist
 };
 
 enum class CallTail { Narrow, BankGated, Wfm };
@@ -57,6 +60,7 @@ struct CallRoute {
                              // launch (a gated call that computes no row leaves the request pending: the timer's selection is made later)
     bool tune_only = false;  // one channel in DM_NONE: the call ends behind the band-pass like a closed gate (a gate closed by the
                              // squelch read-back is a run-time fact and not part of the route)
+    bool mix_in_bandpass = false;  // an empty chain: no mixer launch, the band-pass rotates the stream's samples in its own loads
 };
 
 inline CallRoute plan_call_route(const CallFacts &f)
@@ -108,6 +112,9 @@ inline CallRoute plan_call_route(const CallFacts &f)
     // dmNONE, "Tune only mode, no demod or output" (receiver.cpp:968-971): for the reference's own shape (one channel) the call
     // ends behind the band-pass; in a bank the tune-only channels sit out the noise filter, AGC and demodulators and their rows are cleared
     r.tune_only = !f.wfm && f.C == 1 && f.ch0_tune_only;
+    // A receiver without a decimator: the mixer inside the band-pass's first loads (k_fastfir_t128_mix), unless something reads the
+    // mixed rows -- the zoomed transform, the POST_MIXER tap, the per-kernel events of a profiled call -- or the bank's gate is on
+    r.mix_in_bandpass = f.dec_mix_in_consumer && f.with_chain && !f.wfm && !f.zoom_bins && !f.tap_post_mixer && !f.bank_gate && !f.profiling;
     return r;
 }
 

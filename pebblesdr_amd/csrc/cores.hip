@@ -442,7 +442,7 @@ int probe_copy(int lane_bytes, size_t bytes, int iters, float *gbps)
 int run_mixer(hipStream_t s, const float2 *d_in, float2 *d_out, long long n, const OscBank &osc)
 {
     launch(k_mixer, dim3(cdiv(n, 1024), osc.C), dim3(256), s, d_in, n, 0, d_out, n, n, (const ChanOsc *)osc.d_osc,
-           (const float *)osc.d_amp, osc.a_inf);
+           (const float *)osc.d_amp, osc.a_inf, osc.inline_dyn);
     PG_HIP(hipGetLastError());
     return 0;
 }
@@ -678,6 +678,16 @@ int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in,
     chain = c;
     C = channels;
     const size_t ns = chain.stages.size();
+    if (ns == 0) {
+        // "No decimation, just return" (decimator.cpp:155-160): the mixer alone, into the row the consumer reads (its look-back in front)
+        zero_stage = true;
+        memset(&first, 0, sizeof(first));
+        first.stride = 1;
+        first.gain = last_gain;
+        memset(&casc, 0, sizeof(casc));
+        ovl_len = last_hist;
+        return buf0.alloc((int)C, last_hist, max_in);
+    }
     if (ns - 1 > (size_t)kMaxCascade) return fail(PEBBLEGPU_E_UNSUPPORTED, "decimation chain has %zu stages; at most %d are built", ns, kMaxCascade + 1);
     const design::Stage &s0 = chain.stages[0];
     memset(&first, 0, sizeof(first));
@@ -816,6 +826,13 @@ void DecimCore::release()
 {
     delete fused_p;
     fused_p = nullptr;
+    zero_stage = false;
+    for (int i = 0; i < 2; i++) {
+        if (d_ovl[i]) (void)hipFree(d_ovl[i]);
+        d_ovl[i] = nullptr;
+    }
+    ovl_pending = last_in_consumer = false;
+    ovl_parity = 0;
     for (int i = 0; i < 2; i++) {
         if (d_xhist[i]) (void)hipFree(d_xhist[i]);
         d_xhist[i] = nullptr;
@@ -966,6 +983,39 @@ int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool s
     if (n <= 0 || n % (long long)chain.total != 0)
         return fail(PEBBLEGPU_E_SIZE, "%lld samples is not a multiple of the decimation %u", n, chain.total);
     len0 = n / first.stride;
+    if (zero_stage) {
+        if (n > buf0.cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
+        last_in_consumer = call.mix_in_consumer;
+        if (call.mix_in_consumer) {
+            if (!mix_in_consumer_ready()) return fail(PEBBLEGPU_E_INVALID, "the consumer's overlap rows were not enabled");
+            // nothing to launch: the consumer reads the stream.  Its block 0 looks back at the previous call's mixed samples -- its own
+            // row, or the head-room a k_mixer call's tail job refreshed
+            mix_tail.tail = ovl_pending ? d_ovl[ovl_parity] : buf0.base + (buf0.hist - ovl_len);
+            mix_tail.tail_pitch = ovl_pending ? (long long)ovl_len : buf0.pitch;
+            mix_tail.tail_out = d_ovl[ovl_parity ^ 1];
+            ovl_parity ^= 1;
+            ovl_pending = true;
+            len_out = n;
+            front_name = "k_fastfir_t128 (mixing)";
+            rest_name = "";
+            if (after_first) PG_HIP(hipEventRecord(after_first, s));
+            return 0;
+        }
+        if (ovl_pending) {  // the first k_mixer call behind calls that mixed in the band-pass: their overlap row becomes the head-room
+            std::vector<TailJob> jobs;
+            jobs.push_back(TailJob{d_ovl[ovl_parity], (long long)ovl_len, (long long)ovl_len, ovl_len, 0, buf0.base + (buf0.hist - ovl_len), buf0.pitch});
+            if (int rc = run_save_tails(s, jobs, C, nullptr)) return rc;
+            ovl_pending = false;
+        }
+        launch(k_mixer, dim3(cdiv(n, 1024), C), dim3(256), s, d_in, in_pitch, (int)shared_input, buf0.data(), buf0.pitch, n, (const ChanOsc *)osc.d_osc,
+               (const float *)osc.d_amp, osc.a_inf, osc.inline_dyn);
+        PG_HIP(hipGetLastError());
+        len_out = n;
+        front_name = "k_mixer";
+        rest_name = "";
+        if (after_first) PG_HIP(hipEventRecord(after_first, s));
+        return 0;
+    }
     // successive calls write successive output buffers (tail_job_out carries the consumer's look-back into the next one's head-room)
     if (fin3.base && call.rotate3) { std::swap(fin, fin2); std::swap(fin2, fin3); }  // (fin, fin2, fin3) <- (fin2, fin3, fin)
     else if (fin2.base) std::swap(fin, fin2);  // (either way the call writes what was fin2, whose head-room the last call's consumer filled)
@@ -1112,7 +1162,8 @@ void DecimCore::tail_jobs_dec(std::vector<TailJob> &jobs) const
 }
 void DecimCore::tail_job_out(std::vector<TailJob> &jobs) const
 {
-    if (casc.nst == 0) {  // a single stage: its buffer is the output
+    if (casc.nst == 0) {  // a single stage (or none: the mixer's row): its buffer is the output
+        if (last_in_consumer) return;  // (the consumer mixed in its own loads and kept its overlap itself: buf0 was not written)
         if (!fused_front && buf0.hist > 0) jobs.push_back(TailJob{buf0.data(), buf0.pitch, len0, buf0.hist, 0, nullptr, 0});
         return;
     }
@@ -1125,6 +1176,16 @@ void DecimCore::tail_jobs(std::vector<TailJob> &jobs) const
 {
     tail_jobs_dec(jobs);
     tail_job_out(jobs);
+}
+int DecimCore::enable_mix_in_consumer()
+{
+    if (!zero_stage || buf0.hist <= 0) return fail(PEBBLEGPU_E_UNSUPPORTED, "only the consumer of an empty chain mixes in its own loads");
+    if (d_ovl[0]) return 0;
+    for (int i = 0; i < 2; i++) {
+        PG_HIP(hipMalloc((void **)&d_ovl[i], sizeof(float2) * (size_t)ovl_len * C));
+        PG_HIP(hipMemset(d_ovl[i], 0, sizeof(float2) * (size_t)ovl_len * C));
+    }
+    return 0;
 }
 int DecimCore::enable_double_out()
 {
@@ -1237,6 +1298,19 @@ int FastFirCore::run(hipStream_t s, const HistBuf &in, long long n, float2 *out,
     else if (fft_n == 2048) launch(k_fastfir_t128<true>, fg.grid, dim3(128), s, (const float2 *)in.data(), in.pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, no_tail, (float2 *)nullptr, fg.nb, fg.nchan);
     else if (fft_n == 4096) launch(k_fastfir<4096>, grid, block, s, (const float2 *)in.data(), in.pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw, overlap, no_tail);
     else launch(k_fastfir<8192>, grid, block, s, (const float2 *)in.data(), in.pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw, overlap, no_tail);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+int FastFirCore::run_mixing(hipStream_t s, const float2 *in, long long in_pitch, bool shared_input, long long n, float2 *out, long long out_pitch,
+                            const OscBank &osc, const float2 *tail, long long tail_pitch, float2 *tail_out)
+{
+    if (!mix_ready() || !tail || !tail_out) return fail(PEBBLEGPU_E_INVALID, "the mixing band-pass is the 2048-point plan with both overlap rows");
+    const int overlap = (int)taps - 1;
+    const long long L = block_len();
+    if (n <= 0 || n % L != 0) return fail(PEBBLEGPU_E_SIZE, "FastFIR input %lld is not a multiple of its block %lld", n, L);
+    const FfGrid fg = ff_grid(n / L, C, tun.ff_xcd);
+    launch(k_fastfir_t128_mix, fg.grid, dim3(128), s, in, in_pitch, (int)shared_input, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail,
+           tail_pitch, tail_out, fg.nb, fg.nchan, (const ChanOsc *)osc.d_osc, (const float *)osc.d_amp, osc.a_inf, osc.inline_dyn);
     PG_HIP(hipGetLastError());
     return 0;
 }

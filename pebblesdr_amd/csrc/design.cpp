@@ -34,6 +34,14 @@ Chain build_chain(uint32_t fs_in, uint32_t protect_bw, uint32_t fs_out_min)
 
 const double *halfband_taps(int design) { return pebble_hb_designs[design].h; }
 
+uint64_t superframe_len(const Chain &c, uint32_t frame, uint32_t fastfir_fft, uint32_t fastfir_taps, bool wfm)
+{
+    const uint64_t L = wfm ? (uint64_t)frame : (uint64_t)fastfir_fft - ((uint64_t)fastfir_taps - 1);
+    uint64_t x = frame, y = L;
+    while (y) { const uint64_t t = x % y; x = y; y = t; }
+    return (uint64_t)c.total * ((uint64_t)frame / x * L);
+}
+
 DcChain downconvert_chain(double in_rate, double max_bw, bool simple)
 {
     DcChain c;

@@ -26,6 +26,10 @@ struct Chain {
 // Decimator::buildDecimationChain, pebblelib/decimator.cpp:64-149
 Chain build_chain(uint32_t fs_in, uint32_t protect_bw, uint32_t fs_out_min);
 const double *halfband_taps(int design);  // length = ntaps of that design
+// The shortest call a receiver's chain streams exactly: whole input frames (frames_per_buffer) and, on the narrow branch, whole
+// overlap-save blocks L = fft - (taps - 1) at the demodulator rate -- total * lcm(frame, L); a WFM receiver demodulates frame by frame:
+// total * frame.  An empty chain (total = 1: no design fits the rate, decimator.cpp:155-160) leaves lcm(frame, L) narrow, frame WFM.
+uint64_t superframe_len(const Chain &c, uint32_t frame, uint32_t fastfir_fft, uint32_t fastfir_taps, bool wfm);
 
 // CDownConvert::SetDataRate / SetDataRateSimple (pebblelib/downconvert.cpp:139-237): the decimate-by-2 stages from the input rate down,
 // each an index into the stage table (dc_taps.inc: 0 = CIC3, 1 = the fixed 11-tap halfband, 2.. = hb15 .. hb51); returns the output rate

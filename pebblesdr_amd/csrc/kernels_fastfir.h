@@ -17,6 +17,7 @@
 #pragma once
 #include "fft_lds.h"
 #include "fft_t128.h"
+#include "mixer_osc.h"
 #include "params.h"
 
 namespace pg {
@@ -183,6 +184,79 @@ static __global__ __launch_bounds__(128) void k_fastfir_t128_raw(long long in_pi
         for (int m = 0; m < E; m++) v[m] = raw_load1<FMT>(raw, x0 + t + 128 * m);
     }
     if (tail_out != nullptr && b == (long long)nb - 1) {
+        float2 *to = tail_out + (long long)c * overlap;
+#pragma unroll
+        for (int m = 0; m < E; m++) {
+            const int i = t + 128 * m;
+            if (i >= L) to[i - L] = v[m];
+        }
+    }
+    __syncthreads();
+    fft2048_t128(v, lds, tw128, t, [] { __syncthreads(); });
+#pragma unroll
+    for (int m = 0; m < E; m++) {
+        const float2 p = cmul(h[t + 128 * m], v[m]);
+        v[m] = make_float2(p.x, -p.y);
+    }
+    fft2048_t128(v, lds, tw128, t, [] { __syncthreads(); });
+    float2 *y = out + (long long)c * out_pitch + b * L;
+#pragma unroll
+    for (int m = 0; m < E; m++) {
+        const int i = t + 128 * m;
+        if (i >= overlap) y[i - overlap] = make_float2(v[m].x, -v[m].y);
+    }
+}
+
+// k_fastfir_t128 for a receiver without a decimator (an empty chain: 48 kHz narrow): the band-pass reads the INPUT stream and rotates
+// every sample by its channel's oscillator on the way into the registers (mixer_osc, the value k_mixer multiplies by), so the mixed
+// row is neither written nor read back -- per channel one write where mixer + band-pass make four crossings (mixer write, band-pass
+// read with its 2x overlap, band-pass write); a shared stream stays in cache.  Blocks behind the first recompute their overlap from the
+// stream with the call's oscillator (the frequency cannot change inside a call).  Block 0's overlap are MIXED samples of the previous
+// call -- mixed at the old frequency after a retune, as m_pFFTOverlapBuf holds them: `tail` [c][tail_pitch], and the last block leaves
+// the next call's in `tail_out` [c][overlap] (a different buffer).  Sample s of the call sits at in[s] of its stream.
+static __global__ __launch_bounds__(128) void k_fastfir_t128_mix(const float2 *__restrict__ in, long long in_pitch, int shared_input,
+                                                                 float2 *__restrict__ out, long long out_pitch,
+                                                                 const float2 *__restrict__ H, const float2 *__restrict__ tw128,
+                                                                 int overlap /* taps-1 */, const float2 *__restrict__ tail, long long tail_pitch,
+                                                                 float2 *__restrict__ tail_out, int nb, int nchan,
+                                                                 const ChanOsc *__restrict__ osc, const float *__restrict__ amp_tab, float a_inf,
+                                                                 OscDynInline dyn)
+{
+    constexpr int N = 2048, E = 16;
+    __shared__ float2 lds[FftLds<N>::kSlots];
+    const int t = threadIdx.x;
+    const int L = N - overlap;
+    int c;
+    long long b;
+    if (nchan > 0) {  // the XCD-ordered one-dimensional grid, as above
+        const long long total = (long long)nb * nchan, per = (total + 7) >> 3;
+        const long long q = (long long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
+        if ((long long)(blockIdx.x >> 3) >= per || q >= total) return;  // (uniform: the whole workgroup)
+        c = (int)(q / nb);
+        b = q - (long long)c * nb;
+    } else {
+        c = blockIdx.y;
+        b = blockIdx.x;
+        nb = (int)gridDim.x;
+    }
+    const ChanOsc *o = &osc[c];
+    const double phase0 = dyn.use ? dyn.d[c].phase0 : o->phase0;
+    const uint32_t n0 = dyn.use ? dyn.d[c].n0 : o->n0;
+    const bool mix = (dyn.use ? dyn.d[c].mix_on : o->mix_on) != 0;
+    const float2 *x = in + (shared_input ? 0 : (long long)c * in_pitch);
+    const long long s0 = b * L - overlap;  // the call's sample under point 0 of [overlap | new]: negative in block 0 only (overlap <= L)
+    const float2 *h = H + (long long)c * N;
+    const float2 *tl = tail + (long long)c * tail_pitch;
+    float2 v[E];
+#pragma unroll
+    for (int m = 0; m < E; m++) {
+        const int i = t + 128 * m;
+        const long long s = s0 + i;
+        if (s < 0) v[m] = tl[i];  // (s < 0: b == 0 and i < overlap)
+        else if (mix) v[m] = cmul(mixer_osc(o, phase0, n0, amp_tab, a_inf, s), x[s]);
+        else v[m] = x[s];         // frequency 0: Mixer::processBlock returns its input (mixer.cpp:51-53)
+    }
+    if (b == (long long)nb - 1) {
         float2 *to = tail_out + (long long)c * overlap;
 #pragma unroll
         for (int m = 0; m < E; m++) {

@@ -10,24 +10,18 @@
 // Bound: HBM.  Algorithmic bytes: 8 B read per input sample per stream + 8/stride B written per
 // channel for the first stage; later stages (8 + 8/stride) B per their own input sample.
 #pragma once
+#include "mixer_osc.h"
 #include "params.h"
 #include "tail_refresh.h"
 
 namespace pg {
 
-
-__device__ __forceinline__ float osc_amp(const float *__restrict__ amp_tab, float a_inf, uint32_t n0, long long i)
-{
-    unsigned long long k = (unsigned long long)n0 + (unsigned long long)i;
-    return k < (unsigned long long)kAmpTab ? amp_tab[k] : a_inf;
-}
-
 // Stand-alone mixer (Mixer::processBlock shape): out[c][i] = osc_c(i) * in[s(c)][i].
-// grid (ceil(n/(256*4)), C); each work-item does 4 consecutive samples from one accurate phasor.
+// grid (ceil(n/(256*4)), C); each work-item does 4 consecutive samples: one aligned group of mixer_osc (mixer_osc.h).
 static __global__ __launch_bounds__(256) void k_mixer(const float2 *__restrict__ in, long long in_pitch, int shared_input,
                                                 float2 *__restrict__ out, long long out_pitch, long long n,
                                                 const ChanOsc *__restrict__ osc, const float *__restrict__ amp_tab,
-                                                float a_inf)
+                                                float a_inf, OscDynInline dyn)
 {
     const int c = blockIdx.y;
     const ChanOsc *o = &osc[c];
@@ -35,16 +29,17 @@ static __global__ __launch_bounds__(256) void k_mixer(const float2 *__restrict__
     float2 *y = out + (long long)c * out_pitch;
     const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i0 >= n) return;
-    if (!o->mix_on) {
+    // (a small bank's per-call fields travel in the kernel arguments, like every other front kernel's)
+    const double phase0 = dyn.use ? dyn.d[c].phase0 : o->phase0;
+    const uint32_t n0 = dyn.use ? dyn.d[c].n0 : o->n0;
+    const bool mix = (dyn.use ? dyn.d[c].mix_on : o->mix_on) != 0;
+    if (!mix) {
         for (int d = 0; d < 4 && i0 + d < n; d++) y[i0 + d] = x[i0 + d];
         return;
     }
-    const float2 p0 = cis_cycles(o->phase0 + (double)(i0 + 1) * o->inc);
-    for (int d = 0; d < 4 && i0 + d < n; d++) {
-        const float2 ph = cmul(p0, o->step[d]);
-        const float a = osc_amp(amp_tab, a_inf, o->n0, i0 + d);
-        y[i0 + d] = cmul(cscale(ph, a), x[i0 + d]);
-    }
+#pragma unroll
+    for (int d = 0; d < 4; d++)
+        if (i0 + d < n) y[i0 + d] = cmul(mixer_osc(o, phase0, n0, amp_tab, a_inf, i0 + d), x[i0 + d]);
 }
 
 // Fused mixer + first decimation stage, LDS-tiled.  A workgroup produces 256 consecutive outputs:

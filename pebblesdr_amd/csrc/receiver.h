@@ -111,6 +111,7 @@ struct DecimCall {
     bool lds_free = false;            // the first kernel should leave LDS alone (it runs beside the display transform)
     bool rotate3 = true;              // this call rotates three output buffers (ignored without fin3)
     hipEvent_t done_event = nullptr;  // an event to complete WITH the call's last launch when that is the bank kernel
+    bool mix_in_consumer = false;     // an empty chain only: the consumer (the band-pass) rotates the samples in its own loads
 };
 struct DecimDone {
     bool osc_advanced = false;        // the route's kernel advanced the oscillators itself
@@ -130,7 +131,24 @@ struct DecimCore {
     bool fused_front = false;        // merged CIC3 + wide halfband in one kernel (k_mix_cic_hb): nothing is written at the CIC rate
     FrontTaps wide_fir;              // the wide stage's taps as kernel arguments (fused_front)
     bool bank_front = false;         // hb11 first stage in registers (k_mix_hb11_bank): a >= 16-channel bank off a shared stream, or one channel when asked
-    bool front_is_lds_free() const { return C == 1 && (fused_front || bank_front); }
+    // An empty chain (no halfband design fits the rate: 48 kHz narrow, WFM below 500 kHz): run() is the stand-alone mixer (k_mixer) into
+    // buf0, which is then out() -- head-room = the consumer's look-back, refreshed by tail_job_out() like a single stage's.  No first
+    // stage means no register front, no raw-converting loads, no decimator inside the transform and no second output buffer.
+    bool zero_stage = false;
+    bool front_is_lds_free() const { return zero_stage || (C == 1 && (fused_front || bank_front)); }
+    // ... and its consumer may mix in its own loads (DecimCall::mix_in_consumer; k_fastfir_t128_mix): run() then launches nothing and
+    // hands out where block 0's overlap of MIXED samples lies and where the consumer's last block leaves the next call's (mix_tail).
+    // Hand-over between the two routes, in both directions, at the switch only: such a call behind a k_mixer call reads its overlap
+    // straight from buf0's head-room (that call's tail job has refreshed it); a k_mixer call behind such a call first copies the
+    // consumer's row into the head-room (ovl_pending).
+    struct MixTail { const float2 *tail = nullptr; long long tail_pitch = 0; float2 *tail_out = nullptr; };
+    MixTail mix_tail;                              // of the last run() with DecimCall::mix_in_consumer
+    float2 *d_ovl[2] = {nullptr, nullptr};         // [C][ovl_len] the consumer's overlap rows, written by alternate calls
+    int ovl_len = 0, ovl_parity = 0;
+    bool ovl_pending = false;                      // d_ovl[ovl_parity] is newer than buf0's head-room
+    bool last_in_consumer = false;                 // the last run() left the mixing to the consumer: buf0 was not written
+    int enable_mix_in_consumer();                  // after init(), zero-stage only: allocates the rows (last_hist samples each)
+    bool mix_in_consumer_ready() const { return d_ovl[0] != nullptr; }
     FrontTaps bank_taps;
     // the whole decimator in one kernel (k_mix_dec_fused): a >= 16-channel bank off one shared stream whose chain is hb11 x S
     // followed by hb15, hb19, hb31; calls inside an oscillator transient take the two-kernel route (both keep each other's history)
@@ -242,6 +260,11 @@ struct FastFirCore {
     int run_ext(hipStream_t s, const float2 *in, long long in_pitch, float2 *d_tail, long long n, float2 *out, long long out_pitch, float2 *d_tail_next = nullptr,
                 const RawSrc *raw = nullptr);
     bool raw_ready() const { return fft_n == 2048; }  // k_fastfir_t128_raw exists for this plan
+    // the band-pass of a receiver without a decimator, mixing in its loads (k_fastfir_t128_mix): in = the input stream(s), n samples per
+    // row; tail [C][tail_pitch] block 0's overlap of mixed samples, tail_out [C][taps-1] receives the next call's
+    bool mix_ready() const { return fft_n == 2048; }
+    int run_mixing(hipStream_t s, const float2 *in, long long in_pitch, bool shared_input, long long n, float2 *out, long long out_pitch,
+                   const OscBank &osc, const float2 *tail, long long tail_pitch, float2 *tail_out);
 };
 
 // ---- Demod_AM ----

@@ -6,13 +6,6 @@
 
 namespace pg {
 
-static long long lcm_ll(long long a, long long b)
-{
-    long long x = a, y = b;
-    while (y) { long long t = x % y; x = y; y = t; }
-    return a / x * b;
-}
-
 int Receiver::create(const pebblegpu_config *cfg)
 {
     device = cfg->device;
@@ -38,11 +31,12 @@ int Receiver::create(const pebblegpu_config *cfg)
         for (auto &e : row) PG_HIP(hipEventCreate(&e));
 
     chain = design::build_chain((uint32_t)fs, wfm ? 200000u : 30000u, 0);  // receiver.cpp:195,213
-    if (chain.stages.empty() || chain.stages.size() > (size_t)kMaxStages)
-        return fail(PEBBLEGPU_E_UNSUPPORTED, "sample rate %.0f yields no decimation chain; not built", fs);
+    // An empty chain is the reference's own case at its default rate (48000: no design has fs >= 30000 / wPass) and for WFM below 500 kHz:
+    // Decimator::process copies (decimator.cpp:155-160), total = 1, no gain to restore, the demodulator runs at the input rate
+    if (chain.stages.size() > (size_t)kMaxStages)
+        return fail(PEBBLEGPU_E_UNSUPPORTED, "sample rate %.0f yields a decimation chain of %zu stages; at most %d are built", fs, chain.stages.size(), kMaxStages);
     demod_rate_int = (uint32_t)(int)chain.rate;  // int members, receiver.h:165-166
-    const long long L = wfm ? (long long)nf : (long long)ff_n - ((long long)ff_taps - 1);
-    superframe = (uint64_t)chain.total * (uint64_t)lcm_ll(nf, L);
+    superframe = design::superframe_len(chain, nf, ff_n, ff_taps, wfm);
     const long long max_n = (long long)max_sf * (long long)superframe;
     const long long nd_max = max_n / chain.total;
 
@@ -72,6 +66,8 @@ int Receiver::create(const pebblegpu_config *cfg)
             PG_HIP(hipStreamCreateWithPriority(&chain_stream_, hipStreamNonBlocking, lo));
         }
         if (int rc = ff_.init(C, ff_n, ff_taps, tun_)) return rc;
+        // an empty chain under the 2048-point band-pass: the band-pass may mix in its own loads (PEBBLEGPU_NO_FUSED_DEC=1 keeps k_mixer)
+        if (dec_.zero_stage && ff_.mix_ready() && !tun_.no_fused_dec) { if (int rc = dec_.enable_mix_in_consumer()) return rc; }
         if (int rc = am_.init(C, (double)demod_rate_int, nd_max)) return rc;  // Demod_AM(m_inputSampleRate), demod.cpp:62
         // Demod_SAM / Demod_NFM objects also exist in every Receiver (demod.cpp:63-64); their buffers are allocated on first use
         pll_cap_ = nd_max;
@@ -598,6 +594,8 @@ CallFacts Receiver::call_facts(uint64_t n, bool with_spectrum, bool with_chain, 
     f.fuse_dec = tun_.fuse_dec;
     f.bank_pipe_extev = tun_.bank_pipe_extev;
     f.bank_pipe_timed_ev = tun_.bank_pipe_timed_ev;
+    f.dec_mix_in_consumer = dec_.mix_in_consumer_ready();
+    f.tap_post_mixer = (taps_ >> PEBBLEGPU_TAP_POST_MIXER & 1u) != 0;
     return f;
 }
 
@@ -805,6 +803,7 @@ int Receiver::run_decimator(Call &c)
         DecimCall dc;
         dc.lds_free = rt.side;
         dc.rotate3 = rt.rot3;
+        dc.mix_in_consumer = rt.mix_in_bandpass;
         // (PEBBLEGPU_BANK_PIPE_EXTEV=1, opt-in: measured 0.0695 / 0.0753 ms (configs[2] / configs[3] shard) against 0.0663 / 0.0774 without)
         // the hand-over event of a two-stage call: completed by the bank kernel's own dispatch when that ends the first stage
         if (rt.done_in_kernel) { if (int rc = handover_event(&dc.done_event)) return rc; }
@@ -832,6 +831,7 @@ int Receiver::run_decimator(Call &c)
         if (int rc = run_nap(c.cs, nap >= 0 ? (unsigned)nap : (rt.rot3 ? 0u : 800u))) return rc;
     }
     c.nd = dec_.out_len();
+    if (rt.mix_in_bandpass) return 0;  // (no mixed rows: the route is taken only while nothing reads them)
     return copy_tap(c.cs, PEBBLEGPU_TAP_POST_MIXER, dec_.out().data(), dec_.out().pitch, c.nd, C);  // receiver.cpp:945 (WFM: m_sampleBuf, :884)
 }
 
@@ -860,7 +860,10 @@ int Receiver::bandpass_and_gate(Call &c)
 {
     hipStream_t cs = c.cs;
     if (!wfm) {
-        if (int rc = ff_.run(cs, dec_.out(), c.nd, audio.data(), audio.pitch)) return rc;  // receiver.cpp:950
+        if (c.rt.mix_in_bandpass) {  // Mixer::processBlock inside the band-pass's loads (an empty chain: the stream is at the demodulator rate)
+            const DecimCore::MixTail &mt = dec_.mix_tail;
+            if (int rc = ff_.run_mixing(cs, c.d_iq, c.in_pitch, shared_input, c.nd, audio.data(), audio.pitch, osc_, mt.tail, mt.tail_pitch, mt.tail_out)) return rc;
+        } else if (int rc = ff_.run(cs, dec_.out(), c.nd, audio.data(), audio.pitch)) return rc;  // receiver.cpp:950
         if (profile_detail) PG_HIP(hipEventRecord(c.ev[4], cs));
         if (int rc = copy_tap(cs, PEBBLEGPU_TAP_POST_BP, audio.data(), audio.pitch, c.nd, C)) return rc;  // receiver.cpp:953
     }
@@ -1159,7 +1162,7 @@ const char *Receiver::kernel_name(int which) const
         if (!last_tb_) return dec_.front_name;
         return testbench_label(dec_.front_name, last_tb_morse_);
     case 3: return dec_.rest_name;
-    case 4: return wfm ? "" : ff_n == 2048 ? "k_fastfir_t128" : "k_fastfir";
+    case 4: return wfm ? "" : dec_.last_in_consumer ? "k_fastfir_t128 (mixing)" : ff_n == 2048 ? "k_fastfir_t128" : "k_fastfir";
     case 5: return wfm ? (wfmc_.fused ? "k_wfm_fir" : "k_iir_scan + k_discrim + k_fir_dec") : "k_anf/k_agc/k_iir_scan/k_pll_demod + k_fir_dec (listed channels only)";
     default: return "";
     }

@@ -20,7 +20,7 @@ struct Tuning {
     // stream bank
     bool sb_side = false;             // SB_SIDE=1: the band-pass on a second stream beside the display transform
     // DecimCore
-    bool no_fused_dec = false;        // NO_FUSED_DEC=1: banks take the two-kernel decimator
+    bool no_fused_dec = false;        // NO_FUSED_DEC=1: banks take the two-kernel decimator; an empty chain takes k_mixer + k_fastfir_t128, not the mixing band-pass
     bool bank_dec = true;             // BANK_DEC=0: banks take k_mix_dec_fused where it exists instead of k_mix_dec_mfma
     int bank_waves = 0;               // BANK_WAVES=<1..4>: waves per SIMD k_mix_dec_mfma's chunks are sized for (0: by call length)
     int bank_osc_adv = 1;             // BANK_OSC_ADV=0: the oscillators' advance stays in the tail launch
