@@ -1238,6 +1238,15 @@ int run_save_tails(hipStream_t s, const std::vector<TailJob> &jobs, uint32_t cha
     PG_HIP(hipGetLastError());
     return 0;
 }
+int run_save_tails_listed(hipStream_t s, const std::vector<TailJob> &jobs, const int *d_list, int n_list)
+{
+    if (jobs.empty() || n_list <= 0) return 0;
+    TailJobs tj;
+    if (int rc = fill_tail_jobs(tj, jobs, nullptr)) return rc;
+    launch(k_save_tails_listed, dim3(1, (unsigned)n_list, (unsigned)jobs.size()), dim3(256), s, tj, d_list);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
 
 // ------------------------------------------------------------------------------------------------
 // FastFirCore
@@ -1580,6 +1589,7 @@ void WfmCore::release()
     d_hilb = nullptr;
     d_stereo_list = nullptr;
     lm.release();
+    lm_pending = 0;
     rds.release();
     for (void *q : p) if (q) (void)hipFree(q);
     d_taps = nullptr;
@@ -1699,11 +1709,24 @@ int WfmCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *ou
                    (const int *)d_stereo_list, n_stereo);
             launch(k_wfm_lmr_fir, dim3(cdiv(n, 256), n_stereo), dim3(256), s, (const float2 *)lm.data(), lm.pitch, (const float *)d_h, L4, out, out_pitch, n,
                    (const WfmPilotState *)d_pilot, (const int *)d_stereo_list);
+            // ALL rows, unlike the RDS rows (RdsCore::run): `lm` is what a channel adds to the input of the audio filter the reference
+            // shares between processDataMono and processDataStereo (m_LPFilter, demod_wfm.cpp:359-361), and a channel in dmFMM adds
+            // nothing.  The memset above zeroes [0, n) of every row, k_wfm_pilot writes the listed ones only, so an unlisted row's
+            // refresh shifts n zeros into its head-room: the (L - R) part it left with rings out of the filter while it is away, as
+            // in the reference.  A row never holds stale data, whatever the call lengths: [0, n) is rewritten on every call.
             std::vector<TailJob> lj(1, TailJob{lm.data(), lm.pitch, n, lm.hist, 0, nullptr, 0});
             if (int rc = run_save_tails(s, lj, C)) return rc;
             PG_HIP(hipGetLastError());
             // the RDS branch (demod_wfm.cpp:296-357) runs whether the pilot is locked or not
             if (int rc = rds.run(s, in, in_pitch, n, (const double *)d_hilb, (const int *)d_stereo_list, n_stereo, stereo_block)) return rc;
+            lm_pending = lm.hist;
+        } else if (lm_pending > 0) {
+            // the last dmFMS channel has left: the same n zeros go into every row, as they would with another channel still listed
+            const long long m = n < lm.cap ? n : lm.cap;
+            PG_HIP(hipMemset2DAsync(lm.data(), sizeof(float2) * (size_t)lm.pitch, 0, sizeof(float2) * (size_t)m, C, s));
+            std::vector<TailJob> lj(1, TailJob{lm.data(), lm.pitch, m, lm.hist, 0, nullptr, 0});
+            if (int rc = run_save_tails(s, lj, C)) return rc;
+            lm_pending -= m < lm_pending ? m : lm_pending;
         }
         return 0;
     }

@@ -878,4 +878,11 @@ static __global__ __launch_bounds__(256) void k_save_tails(TailJobs jobs)
     save_tails_block(jobs, (int)blockIdx.z, (int)blockIdx.y, (int)threadIdx.x);
 }
 
+// the same for the rows of the listed channels only (grid y = entries of the list): the rows of a channel the call's kernels did
+// not fill keep their head-room as it is
+static __global__ __launch_bounds__(256) void k_save_tails_listed(TailJobs jobs, const int *__restrict__ chan_list)
+{
+    save_tails_block(jobs, (int)blockIdx.z, chan_list[blockIdx.y], (int)threadIdx.x);
+}
+
 }  // namespace pg

@@ -128,7 +128,10 @@ int RdsCore::run(hipStream_t s, const float2 *in, long long in_pitch, long long 
     launch(k_rds_bits, dim3((unsigned)cdiv_ll(n_list, 64)), dim3(64), s, (const double *)d_data, (long long)(cap / D + 2), len, q, d_state, d_log, in, in_pitch, n,
            d_list, n_list);
     jobs.push_back(TailJob{mag.data(), mag.pitch, len, mag.hist, 0, nullptr, 0});
-    if (int rc = run_save_tails(s, jobs, C)) return rc;
+    // listed channels only: the kernels above filled no other row, and a refresh of an unlisted row would copy positions [n - hist, n)
+    // of whatever its last dmFMS call left there -- with calls of changing length, or n < hist, not the history the channel went away
+    // with (the reference's delay lines stand still while a channel is in another mode)
+    if (int rc = run_save_tails_listed(s, jobs, d_list, n_list)) return rc;
     PG_HIP(hipGetLastError());
     last_len = len;
     return 0;

@@ -43,6 +43,8 @@ int make_twiddles(int n, float2 **d_tw);
 int make_twiddles_t128(float2 **d_tw);
 int make_twiddles_t128q(float2 **d_tw);  // four tables, the pruned transform's per-work-item factor folded in (k_spectrum_t128)
 int run_save_tails(hipStream_t s, const std::vector<TailJob> &jobs, uint32_t channels, const OscAdvance *oa = nullptr);
+// the rows of the channels in d_list (device memory, n_list entries) only: for buffers that only those channels' kernels fill
+int run_save_tails_listed(hipStream_t s, const std::vector<TailJob> &jobs, const int *d_list, int n_list);
 int run_nap(hipStream_t s, unsigned ticks_100mhz);  // one sleeping wave (k_nap)
 int run_fir_dec(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n_out, int stride,
                 const float *d_taps, int ntaps, uint32_t channels);
@@ -421,6 +423,7 @@ struct WfmCore {
     // pilot band-pass and the PLL serially per dmFMS channel and leaves the (L - R) contribution of the blocks that end locked in `lm`;
     // k_wfm_lmr_fir sends it through the audio response and adds / subtracts it.  Allocated when a channel first asks for dmFMS.
     HistBuf lm;                               // [C] rows, .x = lmr, head-room = the audio response's look-back
+    long long lm_pending = 0;                 // head-room samples that may still be non-zero once no channel is in dmFMS (run() flushes them)
     struct WfmPilotState *d_pilot = nullptr;  // [C]
     double *d_hilb = nullptr;                 // [2][61]
     int *d_stereo_list = nullptr;             // the dmFMS channels

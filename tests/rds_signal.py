@@ -44,14 +44,18 @@ def make_groups(n, seed=1, pi=0x54A8):
     return out
 
 
-def rds_baseband(groups, fs, n, lead_bits=40, seed=2):
+def rds_baseband(groups, fs, n, lead_bits=40, seed=2, alter=None):
     """biphase baseband of the differentially coded bit stream at rate fs, n samples, unit amplitude: a data bit is one cycle of a
-    sine at the bit rate (the shaped biphase symbol is close to that), its sign the differentially coded bit"""
+    sine at the bit rate (the shaped biphase symbol is close to that), its sign the differentially coded bit.  alter: a function
+    that is handed the bit stream in front of the differential coder (int64 array: lead_bits, then 104 per group) and returns the
+    stream to send -- transmission errors, noise instead of groups"""
     rng = np.random.default_rng(seed)
     bits = list(rng.integers(0, 2, lead_bits))
     for g in groups:
         bits += group_bits(*g)
     bits = np.array(bits, dtype=np.int64)
+    if alter is not None:
+        bits = np.asarray(alter(bits.copy()), dtype=np.int64)
     diff = np.bitwise_xor.accumulate(bits)                           # e[n] = d[n] xor e[n-1]
     t = np.arange(n) / fs * (57000.0 / 48.0)                         # time in bit periods
     k = np.floor(t).astype(np.int64)
@@ -59,7 +63,8 @@ def rds_baseband(groups, fs, n, lead_bits=40, seed=2):
     return sym * np.sin(2.0 * np.pi * (t - k))
 
 
-def fm_multiplex(groups, fs, n, rds_level=0.08, pilot_level=0.09, audio_level=0.35, subcarrier_offset_hz=0.0, seed=3, deviation=75000.0):
+def fm_multiplex(groups, fs, n, rds_level=0.08, pilot_level=0.09, audio_level=0.35, subcarrier_offset_hz=0.0, seed=3, deviation=75000.0,
+                 alter=None, lead_bits=40):
     """complex FM signal at rate fs carrying left/right tones, the 19 kHz pilot, the 38 kHz difference signal and the RDS subcarrier
     (3 x pilot + subcarrier_offset_hz)"""
     rng = np.random.default_rng(seed)
@@ -69,6 +74,6 @@ def fm_multiplex(groups, fs, n, rds_level=0.08, pilot_level=0.09, audio_level=0.
     pilot_phase = 2 * np.pi * 19000.0 * t
     m = audio_level * 0.5 * (left + right) + pilot_level * np.sin(pilot_phase) \
         + audio_level * 0.5 * (left - right) * np.sin(2 * pilot_phase) \
-        + rds_level * rds_baseband(groups, fs, n) * np.cos(3 * pilot_phase + 2 * np.pi * subcarrier_offset_hz * t)
+        + rds_level * rds_baseband(groups, fs, n, lead_bits=lead_bits, alter=alter) * np.cos(3 * pilot_phase + 2 * np.pi * subcarrier_offset_hz * t)
     phase = 2 * np.pi * deviation * np.cumsum(m) / fs
     return np.exp(1j * phase)
