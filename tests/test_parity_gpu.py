@@ -1750,7 +1750,9 @@ def test_chain_sweep_over_rates_and_bank_sizes(gpu_lib, oracle_mod, fs, C):
     in front of hb11 x 16 (the fused register front end) -- on the routes one channel and a few channels take, and a one-group
     bank on some of them (the banks' own kernel, every instance and stride of it: tests/test_bank_decimator_gpu.py): USB
     audio of the first and last channel against Mixer -> Decimator -> gain restore -> FastFIR restated by the oracle, three
-    calls.  The oracle is fed whole super-frames so that none of its stages sees fewer samples than taps."""
+    calls.  The oracle is fed whole super-frames so that none of its stages sees fewer samples than taps.  The banks of 17 here sit
+    on halfband triples that k_mix_dec_mfma has an instance for; a bank on another triple ((15,23,59) at 1.4 and 2.8 Msps, (15,19,31)
+    behind a CIC3 at 16 Msps, ...) or behind hb11 x 32 stays on the general route in steady state too: tests/decim_cases.py."""
     import pebblesdr_amd as P
     rx = P.ReceiverBank(fs, C, True, False, 0, max_superframes=1)
     chain = rx.chain()
@@ -1768,8 +1770,8 @@ def test_chain_sweep_over_rates_and_bank_sizes(gpu_lib, oracle_mod, fs, C):
         names.append(rx.kernel_name(2))
     g = np.concatenate(g, axis=1)
     if C >= 16:
-        # every bank of >= 16 channels whose chain is [cic3 x S0,] hb11 x S + three halfbands runs its whole decimator in one kernel
-        # once the oscillators have settled
+        # the banks of >= 16 channels of this table ([cic3 x S0,] hb11 x S + a halfband triple with a matrix instance) run their whole
+        # decimator in one kernel once the oscillators have settled
         assert names[1] == "k_mix_dec_mfma" and names[2] == "k_mix_dec_mfma", (names, chain)
     for c in sorted({0, C - 1}):
         mix = oracle_mod.Mixer(fs); mix.set_frequency(fcs[c])
