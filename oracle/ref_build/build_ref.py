@@ -20,7 +20,7 @@ DEFAULT_REFERENCE = "/root/reference"
 ENV = "PEBBLE_REFERENCE_DIR"
 
 PEBBLELIB = ["cpx", "mixer", "decimator", "downconvert", "fastfir", "fft", "fftaccelerate", "fftooura", "fftcute", "windowfunction", "fir",
-             "iir", "fractresampler", "delayline", "perform", "db"]
+             "iir", "fractresampler", "delayline", "perform", "db", "goertzel", "firfilter", "movingavgfilter", "sampleclock"]
 APPLICATION = ["processstep", "agc", "noiseblanker", "noisefilter", "dcremoval", "iqbalance", "signalstrength"]
 FLAGS = ["-std=c++14", "-O2", "-ffp-contract=off", "-DPEBBLELIB_LIBRARY", "-DUSE_FFTACCELERATE", "-w"]
 
@@ -65,8 +65,9 @@ def build_ref(force=False):
         return BINARY
     obj_dir = os.path.join(OUT, "obj")
     os.makedirs(obj_dir, exist_ok=True)
-    # the second standins path lies one level below the directory that holds fftw-3.3.4/, as the reference's fftw.h looks it up
-    inc = ["-I" + STANDINS, "-I" + os.path.join(STANDINS, "QtCore"), "-I" + os.path.join(ref, "pebblelib"),
+    # forward/ holds the stand-ins named like a directory of standins/ ("QtCore") and comes first, so that the name finds the file;
+    # the third path lies one level below the directory that holds fftw-3.3.4/, as the reference's fftw.h looks it up
+    inc = ["-I" + os.path.join(STANDINS, "forward"), "-I" + STANDINS, "-I" + os.path.join(STANDINS, "QtCore"), "-I" + os.path.join(ref, "pebblelib"),
            "-I" + os.path.join(ref, "application")]
     jobs = [(n, os.path.join(ref, "pebblelib", n + ".cpp"), os.path.join(obj_dir, n + ".o"), inc) for n in PEBBLELIB]
     jobs += [(n, os.path.join(ref, "application", n + ".cpp"), os.path.join(obj_dir, n + ".o"), inc) for n in APPLICATION]

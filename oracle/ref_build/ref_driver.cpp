@@ -40,6 +40,9 @@
 #include "dcremoval.h"
 #include "iqbalance.h"
 #include "signalstrength.h"
+#include "goertzel.h"
+#include "movingavgfilter.h"
+#include "sampleclock.h"
 #undef private
 #undef protected
 
@@ -293,12 +296,68 @@ static void st_fdestimate()
     }
 }
 
+/* goertzel RATE FRAMES N FREQ [SWITCH_AT FREQ2]: GoertzelOOK the way the Morse modem drives it (morse.cpp:228-232, :345-373,
+ * :861-866): constructed, its rate set, TH_PEAK (the constructor's own choice, said again), setFreq(freq, N, jitterCount), then
+ * processSample(CPX, ...) on every sample;
+ * setFreq again before sample SWITCH_AT (Morse::setDemodMode on a running modem).  Records: powers, decisions, peak powers, one
+ * value per result, then the samples left in the block under way */
+static void st_goertzel()
+{
+    quint32 rate = quint32(arg(0)), n = quint32(arg(2));
+    GoertzelOOK g(rate, quint32(arg(1)));
+    g.setTargetSampleRate(rate);
+    g.setThresholdType(GoertzelOOK::TH_PEAK);
+    int jitter = int(rate * .005 / n);
+    g.setFreq(int(arg(3)), n, jitter);
+    std::vector<double> pw, above, peak;
+    for (size_t i = 0; i < in_len(); i++) {
+        if (g_arg.size() > 5 && i == size_t(arg(4)))
+            g.setFreq(int(arg(5)), n, jitter);
+        double p = 0, pk = 0;
+        bool a = false;
+        if (g.processSample(in_cpx()[i], p, a, pk)) {
+            pw.push_back(p);
+            above.push_back(a ? 1 : 0);
+            peak.push_back(pk);
+        }
+    }
+    rec(pw.data(), pw.size());
+    rec(above.data(), above.size());
+    rec(peak.data(), peak.size());
+    rec1(g.m_mainTone.m_nCount);
+}
+
+/* sampleclock RATE (EARLIER LATER)...: one record, SampleClock::uSecDelta of every pair; IN is not read */
+static void st_sampleclock()
+{
+    SampleClock c(quint32(arg(0)));
+    c.reset();
+    std::vector<double> out;
+    for (size_t i = 1; i + 1 < g_arg.size(); i += 2)
+        out.push_back(c.uSecDelta(quint32(g_arg[i]), quint32(g_arg[i + 1])));
+    rec(out.data(), out.size());
+}
+
+/* movingavg LEN RESET_AT: IN is real doubles; MovingAvgFilter(LEN)::newSample of each, reset() before sample RESET_AT; one record */
+static void st_movingavg()
+{
+    MovingAvgFilter f(quint32(arg(0)));
+    std::vector<double> out;
+    for (size_t i = 0; i < g_in.size(); i++) {
+        if (i == size_t(arg(1)))
+            f.reset();
+        out.push_back(f.newSample(g_in[i]));
+    }
+    rec(out.data(), out.size());
+}
+
 int main(int argc, char **argv)
 {
     static const struct { const char *name; void (*fn)(); } stages[] = {
         {"mixer", st_mixer}, {"decimator", st_decimator}, {"downconvert", st_downconvert}, {"fastfir", st_fastfir},
         {"fir", st_fir}, {"iir", st_iir}, {"resampler", st_resampler}, {"spectrum", st_spectrum}, {"agc", st_agc},
-        {"nb", st_nb}, {"anf", st_anf}, {"iqbalance", st_iqbalance}, {"dcremoval", st_dcremoval}, {"fdestimate", st_fdestimate}};
+        {"nb", st_nb}, {"anf", st_anf}, {"iqbalance", st_iqbalance}, {"dcremoval", st_dcremoval}, {"fdestimate", st_fdestimate},
+        {"goertzel", st_goertzel}, {"sampleclock", st_sampleclock}, {"movingavg", st_movingavg}};
     if (argc < 4) {
         fprintf(stderr, "usage: ref_driver STAGE IN OUT [numbers...]\n");
         return 2;

@@ -50,11 +50,16 @@ int MorseCore::init(uint32_t channels, uint32_t demod_rate, long long max_n, boo
         const double k = nfq * pp.N;
         const double A = design::kTwoPi * k / pp.N;
         pp.B[q] = 2 * std::cos(A);
-        pp.Cr[q] = std::cos(A);
-        pp.Ci[q] = -std::sin(A);
+        // c_C = exp(-c_j * c_A), c_D = exp(-c_j * c_A * (N - 1)) with pebblelib's c_j = {6.123233995736766e-17, 1} (cpx.h:158), not {0, 1}:
+        // the modulus is exp(-6.1e-17 A (N - 1)), up to 3e-14 under 1
+        const double cj_re = 6.123233995736766e-17;
+        const double eC = std::exp(-cj_re * A);
+        pp.Cr[q] = eC * std::cos(A);
+        pp.Ci[q] = -(eC * std::sin(A));
         const double AD = A * ((double)pp.N - 1.0);
-        pp.Dr[q] = std::cos(AD);
-        pp.Di[q] = -std::sin(AD);
+        const double eD = std::exp((-cj_re * A) * ((double)pp.N - 1.0));
+        pp.Dr[q] = eD * std::cos(AD);
+        pp.Di[q] = -(eD * std::sin(AD));
     }
     long long len = max_n;
     for (const design::Stage &st : chain.stages) {
@@ -199,7 +204,8 @@ int MorseCore::run(hipStream_t s, const float2 *in, long long in_pitch, long lon
         tj.in[j] = x; tj.in_pitch[j] = xp; tj.n[j] = len; tj.hist[j] = d_hist[j]; tj.keep[j] = st.ntaps - 1;
         x = d_out[j]; xp = out_pitch[j]; len = n_out;
     }
-    launch(k_morse_tails, dim3((unsigned)chain.stages.size(), nl), dim3(64), s, tj, kMaxTaps, (const int *)d_list);
+    if (!chain.stages.empty())  // a demodulator rate of 8000 Hz or less has no stage, and a grid of no blocks is no launch
+        launch(k_morse_tails, dim3((unsigned)chain.stages.size(), nl), dim3(64), s, tj, kMaxTaps, (const int *)d_list);
     launch(k_morse_goertzel, dim3(nl), dim3(64), s, x, xp, m, pp, d_state, d_power, rpitch, (const int *)d_list);
     launch(k_morse_decide, dim3((unsigned)cdiv_ll(nl, 64)), dim3(64), s, (const double *)d_power, rpitch, m, pp.N, pp.rate, d_state, d_log, log_cap,
            d_tone, (const int *)d_list, nl);
@@ -280,6 +286,13 @@ struct pebblegpu_morse {
 // Morse::setSampleRate(sample_rate, sample_count) on the step: everything new but the WPM estimate the plugin object keeps (wpm < 0: 20)
 static int morse_open(pebblegpu_morse *m, uint32_t sample_rate, uint32_t sample_count, int32_t wpm)
 {
+    {   // what init or check refuses is refused before the handle is touched: the decoder that runs keeps running as it was
+        pg::MorseCore probe;
+        int rc = probe.init(1, sample_rate, sample_count, true);
+        if (!rc) rc = probe.check(sample_count);
+        probe.release();
+        if (rc) return rc;
+    }
     m->core.release();
     if (m->d_in) (void)hipFree(m->d_in);
     m->d_in = nullptr;

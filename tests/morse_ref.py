@@ -47,10 +47,20 @@ def goertzel_coeffs(freq, n, rate):
     k = nf * n
     a = TWOPI * k / n
     b = 2 * math.cos(a)
-    c = complex(math.cos(a), -math.sin(a))           # exp(-c_j * c_A)
-    ad = a * (float(n) - 1.0)
-    d = complex(math.cos(ad), -math.sin(ad))         # exp(-c_j * c_A * (N - 1))
+    c = _exp_minus_cj(a, 1.0)                        # exp(-c_j * c_A)
+    d = _exp_minus_cj(a, float(n) - 1.0)             # exp(-c_j * c_A * ((double)N - 1.0))
     return b, c, d
+
+
+CJ_RE = 6.123233995736766e-17                        # pebblelib/cpx.h:158: const CPX c_j = {6.123233995736766e-17, 1}, not {0, 1}
+
+
+def _exp_minus_cj(a, k):
+    """std::exp((-c_j * a) * k): complex times double scales both parts, twice; exp(re) * (cos(im), sin(im)).  With c_j's real part the
+    modulus is exp(-6.1e-17 a k), not 1: up to 3e-14 under it at N = 80 (found by tests/test_reference_pins.py's Goertzel cases)"""
+    re, im = (-CJ_RE * a) * k, (-1.0 * a) * k
+    e = math.exp(re)
+    return complex(e * math.cos(im), e * math.sin(im))
 
 
 def usec_delta(earlier, later, rate):
@@ -66,9 +76,9 @@ class MorseRef:
     def __init__(self, demod_rate, frames, wpm=20):
         self.frames = frames
         self.dec = oracle.Decimator(int(demod_rate), 1000, 8000)
-        self.rate = int(self.dec.rate)
-        self.n = best_n(self.rate)
-        self.mode = DM_CWL                            # morse.cpp:181: dmCWL whatever the receiver's mode
+        self.rate = self.modem_rate_of(self.dec.rate)
+        self.n = self.best_n_of(self.rate)
+        self.mode = DM_CWL                           # morse.cpp:181: dmCWL whatever the receiver's mode
         # GoertzelOOK ctor, goertzel.cpp:351-373, and Goertzel's running sums
         self.s1 = self.s2 = 0j
         self.count = 0
@@ -87,6 +97,13 @@ class MorseRef:
         self.dd = []
         self.below = self.above = False
         self.init(wpm)
+
+    # the two roundings of setSampleRate, as methods so that tests/morse_cases.py's deliberately wrong models can get them wrong
+    def modem_rate_of(self, chain_rate):
+        return int(chain_rate)                        # int actualModemRate, morse.cpp:191-192
+
+    def best_n_of(self, rate):
+        return best_n(rate)
 
     def set_sample_rate(self, demod_rate, frames):
         """setSampleRate again (morse.cpp:160-246): a new Decimator, GoertzelOOK and threshold filter, dmCWL, init from the plugin

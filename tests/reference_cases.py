@@ -57,7 +57,7 @@ def compress(records):
     big = [i for i, r in enumerate(records) if len(r) > 160]
     parts = []
     for i, r in enumerate(records):
-        k = len(r) if len(r) <= 160 else (TAIL if i == big[-1] else 16)
+        k = len(r) if len(r) <= 160 else min(len(r), TAIL if i == big[-1] else 16)
         parts += [np.array([len(r), k], dtype=np.float64), r[len(r) - k:]]
     return np.concatenate(parts) if parts else np.zeros(0)
 
@@ -257,6 +257,73 @@ def _fdestimate(rate, mixer, bands):
     return run
 
 
+# ---- the Morse restatement (tests/morse_ref.py): its Goertzel, TH_PEAK, clock and threshold-filter arithmetic.  Morse::stateMachine,
+# updateThresholds and findBestGoertzelN live in the Qt plugin, not in pebblelib: they stay pinned by hand (tests/test_morse_host.py)
+def _morse_goertzel(rate, n, freq, switch_at, freq2):
+    def run(O, x):
+        from tests import morse_ref as M
+
+        class Rec(M.MorseRef):
+            peaks = None
+
+            def th_peak(self, p):
+                tone = super().th_peak(p)
+                self.peaks.append(self.peak)
+                return tone
+
+        r = Rec(rate, 1)                      # at 8000 Hz and below the modem's decimator has no stage: the modem rate is the rate
+        r.peaks = []
+        assert (r.rate, r.n) == (rate, n)
+        mode = {-1000: M.DM_CWL, 1000: M.DM_CWU}
+        r.set_demod_mode(mode[freq])
+        r.process_modem(x[:switch_at])
+        r.set_demod_mode(mode[freq2])
+        r.process_modem(x[switch_at:])
+        return [("v", np.array(r.powers)), ("x", np.array(r.tones, dtype=np.float64)), ("v", np.array(r.peaks)),
+                ("x", np.array([float(r.count)]))]
+    return run
+
+
+def _morse_clock(rate, pairs):
+    def run(O, x):
+        from tests import morse_ref as M
+        return [("x", np.array([float(M.usec_delta(a, b, rate)) for a, b in pairs]))]
+    return run
+
+
+def _morse_sma(reset_at):
+    def run(O, x):
+        from tests import morse_ref as M
+        r = M.MorseRef(8000, 1)
+        out = []
+        for i, v in enumerate(x):
+            if i == reset_at or i == 0:
+                r.sma, r.sma_i = None, 0      # MovingAvgFilter::reset, as MorseRef.init does it
+            out.append(r.sma_sample(v))
+        return [("v", np.array(out))]
+    return run
+
+
+def _morse_keyed(rate, n, freq, switch_at, seed):
+    from tests import morse_ref as M
+    out = lcg_noise(n, seed, 2e-3)
+    for text, f, start in (("TEST", freq, 0), ("EE", -freq, switch_at)):
+        env = M.keying(text, 25, rate)[:n - start]
+        t = (np.arange(len(env)) + start) / float(rate)
+        out[start:start + len(env)] += 0.05 * env * np.exp(2j * np.pi * f * t)
+    return out
+
+
+def _clock_pairs(n):
+    """(earlier, later) clock pairs: marks and spaces of a few to a few thousand results, earlier >= later (0 by definition), and
+    spans whose microseconds pass 2^32 (the quint64 is cut to quint32)"""
+    pairs = [(0, 0), (5, 5), (7, 3), (0, 1), (0, n - 1), (0, n), (0, n + 1)]
+    pairs += [(k * 37, k * 37 + k * n) for k in range(1, 40)]
+    pairs += [(11, 11 + k * n + (k % n)) for k in (3, 13, 127, 1021, 8191)]
+    pairs += [(1, 40000000), (0, 4294967295), (123456, 3123456789)]
+    return pairs
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # the table of cases
 # ---------------------------------------------------------------------------------------------------------------
@@ -386,7 +453,29 @@ def _build_cases():
     bands = [(-4000.0, 4000.0), (300.0, 3000.0)]
     C.append(Case("fdestimate", "fdestimate", [2048000, 2048, 2048000, 100000.0] + [v for b in bands for v in b], _fd_spectrum,
                   _fdestimate(2048000, 100000.0, bands)))
+    # the Morse modem's pebblelib classes at its four modem rates (no stage; 6000; 4687 of 4687.5; 7812 of 7812.5), both tones, the
+    # tone moved to the other side on a running filter (Morse::setDemodMode): GoertzelOOK TH_PEAK, SampleClock, MovingAvgFilter(8)
+    from tests import morse_ref as M
+    for mrate in (8000, 6000, 4687, 7812):
+        mn = M.best_n(mrate)
+        total = int(2.6 * mrate)
+        sw = int(1.7 * mrate) + 7             # inside a block, not on its boundary
+        for freq in (-1000, 1000):
+            C.append(Case("morse_goertzel_%d_%s" % (mrate, "cwl" if freq < 0 else "cwu"), "goertzel", [mrate, 2048, mn, freq, sw, -freq],
+                          lambda mrate=mrate, freq=freq, total=total, sw=sw: _morse_keyed(mrate, total, freq, sw, 95),
+                          _morse_goertzel(mrate, mn, freq, sw, -freq), bar=MORSE_POWER_BAR))
+        pairs = _clock_pairs(mn)
+        C.append(Case("morse_clock_%d" % mrate, "sampleclock", [mrate] + [v for p in pairs for v in p], lambda: np.zeros(0),
+                      _morse_clock(mrate, pairs)))
+    C.append(Case("morse_threshold_filter", "movingavg", [8, 21], _sma_input, _morse_sma(21)))
     return C
+
+
+def _sma_input():
+    """dot-dash thresholds as updateThresholds feeds them: whole microseconds, (dash + dot) / 2 for speeds of 10 to 50 WPM"""
+    from tests.signals import lcg_uniform
+    u = lcg_uniform(40, 97)
+    return np.floor(2 * 1200000 / (10 + 40 * u))
 
 
 def _fd_spectrum():
@@ -401,6 +490,8 @@ def _fd_spectrum():
 # Every stage comes out bit for bit against the reference binary and is asserted equal (bar 0).  The one bar is for the cross-check
 # of the spectrum through the reference's in-tree Ooura transform, a different FFT: measured 1.01e-10 dB on the CPU, times ten.
 OOURA_BAR_DB = 1.1e-9
+# The Goertzel powers and peak averages of the Morse restatement against the reference's GoertzelOOK: measured bit for bit as well
+MORSE_POWER_BAR = 0.0
 
 CASES = None
 

@@ -13,7 +13,10 @@ WHAT IS PINNED.  The Accelerate stand-in is this project's code (plain loops, le
 so these tests pin the reference's code AROUND the DFT and the strided FIR, not those two primitives: the window, scaling,
 unfold and dB averaging of the spectrum, the filter designs, the overlap-save bookkeeping of FastFIR, the decimator's chain
 selection, delay lines and short-frame fallback, and every serial fp64 stage whole (mixer, CDownConvert, CFir, CIir, the
-resampler, AGC, the blankers, ANF, IQBalance, DCRemoval, fdEstimate).  The two primitives are cross-checked once each through
+resampler, AGC, the blankers, ANF, IQBalance, DCRemoval, fdEstimate).  The Morse restatement (tests/morse_ref.py) is held to the
+pebblelib classes the modem is made of, driven the way morse.cpp:160-246 and :761-894 drive them: GoertzelOOK with TH_PEAK at the four
+modem rates of tests/morse_cases.py and both tones, the tone moved on a running filter (powers, decisions, peak averages, the count
+left in the block), SampleClock::uSecDelta, MovingAvgFilter(8).  The two primitives are cross-checked once each through
 reference code that does not use the stand-in: the decimator through HalfbandFilter::process (decimator.cpp:661-685) and the
 spectrum through the in-tree Ooura transform (magnitudes only: FastFIR is mirrored on that back end).
 
@@ -21,11 +24,15 @@ MEASURED (CPU, both sides fp64, same libm, contraction off): every case is bit f
   spectrum through Ooura against the oracle: max 1.01e-10 dB, bar 1.1e-9 dB (ten times; the ceiling is 1e-6 dB).
 No bar may exceed 1e-9 relative RMS or 1e-6 dB (reference_cases.MAX_BAR, MAX_BAR_DB).
 
-NOT PINNED: the two vDSP primitives themselves; CFastFIR at 8192/4097 (its sizes are #defines inside fastfir.cpp, so the
+NOT PINNED: Morse::stateMachine, updateThresholds and findBestGoertzelN, which live in the Qt plugin (plugins/MorseDigitalModem), not
+in pebblelib: they stay pinned by hand-worked numbers (tests/test_morse_host.py); the two vDSP primitives themselves; CFastFIR at 8192/4097 (its sizes are #defines inside fastfir.cpp, so the
 variant cannot be built from the unmodified source); the demodulators (demod.h needs the uic-generated ui_data-band.h).
 
 FOUND BY THESE PINS: FFT::m_isOverload is a member that only whole buffers rewrite; the oracle returned 0 for a short
 frame after an overloaded whole one (case spectrum_overload_then_short).  Fixed in the oracle and in the device's spectrum step.
+pebblelib's c_j is {6.123233995736766e-17, 1} (cpx.h:158), so Goertzel's c_C and c_D have a modulus of exp(-6.1e-17 A (N - 1)), up to
+3e-14 under 1; the Morse restatement had {0, 1} and its powers came out 5e-14 off (cases morse_goertzel_*).  Fixed in the restatement and
+in MorseCore::init's coefficients; bit for bit since.
 """
 import os
 
@@ -80,7 +87,7 @@ def test_reference_pin(oracle_mod, name):
 def test_every_stage_of_the_table_has_a_case():
     stages = {c.stage for c in R.cases()}
     assert stages == {"mixer", "decimator", "downconvert", "fastfir", "fir", "iir", "resampler", "spectrum", "agc", "nb", "anf",
-                      "iqbalance", "dcremoval", "fdestimate"}
+                      "iqbalance", "dcremoval", "fdestimate", "goertzel", "sampleclock", "movingavg"}
     assert all(c.bar <= R.MAX_BAR and c.bar_db <= R.MAX_BAR_DB for c in R.cases())
     assert all(os.path.getsize(c.fixture) < 16384 for c in R.cases())
 
