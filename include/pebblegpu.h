@@ -76,6 +76,11 @@ int pebblegpu_device_synchronize(int device);
 /* Streaming-copy probe (read + write GB/s of a plain device copy with 16- or 8-byte lanes): the measured HBM ceiling
  * the bench quotes next to the 8 TB/s datasheet peak. */
 int pebblegpu_probe_copy_gbps(int device, int lane_bytes, size_t bytes, int iters, float *gbps);
+/* Diagnostic: the bytes of device memory and of pinned host memory that THIS library holds in THIS process right now, over all
+ * devices and handles (what pebblegpu_malloc handed to the host is the host's and is not counted).  Either pointer may be NULL.
+ * Every handle's destroy brings both back to what they were before its create: a leak check that does not read the device's free
+ * memory, which other processes on the same device change. */
+int pebblegpu_live_bytes(uint64_t *device, uint64_t *pinned);
 /* Ingest on the device: DeviceInterfaceBase::normalizeIQ (pebblelib/deviceinterfacebase.cpp:648-838) and
  * WavFile::ReadSamples' PCM16 scaling (wavfile.cpp:299-300).  d_src holds n_samples raw IQ pairs, d_dst receives float2.
  * gain = m_userIQGain * m_normalizeIQGain; iq_order = DeviceInterface::IQOrder (device_interfaces.h:140-145). */

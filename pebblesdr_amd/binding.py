@@ -13,7 +13,7 @@ _LIBNAME = "libpebblegpu.so"
 SYMBOLS = [
     "pebblegpu_last_error", "pebblegpu_abi_version", "pebblegpu_device_count",
     "pebblegpu_malloc", "pebblegpu_free", "pebblegpu_memcpy_h2d", "pebblegpu_memcpy_d2h", "pebblegpu_memset",
-    "pebblegpu_device_synchronize", "pebblegpu_probe_copy_gbps", "pebblegpu_normalize_iq",
+    "pebblegpu_device_synchronize", "pebblegpu_probe_copy_gbps", "pebblegpu_live_bytes", "pebblegpu_normalize_iq",
     "pebblegpu_receiver_create", "pebblegpu_receiver_destroy", "pebblegpu_receiver_info",
     "pebblegpu_set_mixer_freq", "pebblegpu_set_bandpass", "pebblegpu_set_demod_mode", "pebblegpu_receiver_rds_groups", "pebblegpu_receiver_stereo_lock", "pebblegpu_set_agc", "pebblegpu_set_conditioners", "pebblegpu_set_noise_filter", "pebblegpu_set_squelch", "pebblegpu_receiver_process_raw",
     "pebblegpu_receiver_process", "pebblegpu_receiver_audio", "pebblegpu_receiver_spectrum", "pebblegpu_receiver_zoom_spectrum",
@@ -450,6 +450,7 @@ def _declare(L):
     L.pebblegpu_device_synchronize.argtypes = [i32]
     L.pebblegpu_normalize_iq.argtypes = [i32, i32, i32, dbl, vp, u64, vp]
     L.pebblegpu_probe_copy_gbps.argtypes = [i32, i32, C.c_size_t, i32, C.POINTER(C.c_float)]
+    L.pebblegpu_live_bytes.argtypes = [C.POINTER(u64), C.POINTER(u64)]
     L.pebblegpu_receiver_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
     L.pebblegpu_receiver_destroy.argtypes = [vp]
     L.pebblegpu_receiver_info.argtypes = [vp, C.POINTER(Info)]
@@ -667,6 +668,14 @@ def probe_copy_gbps(lane_bytes=16, nbytes=1 << 30, iters=10, device=0, lib=None)
     g = C.c_float()
     check(L, L.pebblegpu_probe_copy_gbps(device, lane_bytes, nbytes, iters, C.byref(g)))
     return g.value
+
+
+def live_bytes(lib=None):
+    """(device bytes, pinned host bytes) this library holds in this process right now"""
+    L = lib or load_library()
+    d, p = C.c_uint64(), C.c_uint64()
+    check(L, L.pebblegpu_live_bytes(C.byref(d), C.byref(p)))
+    return d.value, p.value
 
 
 IQ_S8, IQ_U8, IQ_S16, IQ_F32, IQ_WAV16 = range(5)

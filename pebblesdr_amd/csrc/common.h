@@ -25,15 +25,16 @@ int fail(int code, const char *fmt, ...);
             return pg::fail(-3, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// kernel launch through a function pointer: the name may be a template-id with commas
+// kernel launch through a function pointer: the name may be a template-id with commas.  Arguments are converted to the kernel's
+// parameter types here, so an owning buffer (devmem.h) may be passed where its pointer is meant.
 template <class... KA, class... A>
-inline void launch(void (*kernel)(KA...), dim3 grid, dim3 block, hipStream_t stream, A... args)
+inline void launch(void (*kernel)(KA...), dim3 grid, dim3 block, hipStream_t stream, const A &...args)
 {
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<KA>(args)...);
 }
 
 template <class... KA, class... A>
-inline void launch_lds(void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, A... args)
+inline void launch_lds(void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const A &...args)
 {
     hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, static_cast<KA>(args)...);
 }

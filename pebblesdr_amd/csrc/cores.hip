@@ -41,15 +41,7 @@ int HistBuf::alloc(int channels, int hist_len, long long capacity)
     cap = capacity;
     chans = channels;
     pitch = (hist + capacity + 1) & ~1LL;
-    const size_t bytes = (size_t)pitch * channels * sizeof(float2);
-    PG_HIP(hipMalloc((void **)&base, bytes));
-    PG_HIP(hipMemset(base, 0, bytes));
-    return 0;
-}
-void HistBuf::release()
-{
-    if (base) (void)hipFree(base);
-    base = nullptr;
+    return base.alloc_zero((size_t)pitch * channels);
 }
 
 static design::M2 section_matrix(const ScanSection &s)
@@ -70,7 +62,7 @@ void fill_scan_section(ScanSection &s, int type, const double *c)
     }
 }
 
-int make_twiddles(int n, float2 **d_tw)
+int make_twiddles(int n, DevBuf<float2> &tw)
 {
     // per-pass tables in the layout fft_lds.h reads (fft_tw_off)
     if (!(n == 2048 || n == 4096 || n == 8192)) return fail(PEBBLEGPU_E_UNSUPPORTED, "no FFT plan for %d points", n);
@@ -89,12 +81,10 @@ int make_twiddles(int n, float2 **d_tw)
         }
         P *= R;
     }
-    PG_HIP(hipMalloc((void **)d_tw, sizeof(float2) * h.size()));
-    PG_HIP(hipMemcpy(*d_tw, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice));
-    return 0;
+    return tw.upload(h.data(), h.size());
 }
 
-int make_twiddles_t128(float2 **d_tw)
+int make_twiddles_t128(DevBuf<float2> &tw)
 {
     // fft_t128.h: pass B W^{16k}, W^{32k}, W^{64k} (k < 16); pass C W^{k}, W^{2k}, W^{4k}, W^{8k} (k < 128); W = exp(-2 pi i / 2048)
     std::vector<float2> t2((size_t)kTw128Count);
@@ -106,14 +96,12 @@ int make_twiddles_t128(float2 **d_tw)
         for (int e = 0; e < 3; e++) t2[kTw128B + e * 16 + k] = W((long long)(16 * k) << e);
     for (int k = 0; k < 128; k++)
         for (int e = 0; e < 4; e++) t2[kTw128C + e * 128 + k] = W((long long)k << e);
-    PG_HIP(hipMalloc((void **)d_tw, sizeof(float2) * t2.size()));
-    PG_HIP(hipMemcpy(*d_tw, t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice));
-    return 0;
+    return tw.upload(t2.data(), t2.size());
 }
 
 // k_spectrum_t128 (8192 bins = four transforms x[n] W_8192^{n q} of a 2048-sample frame): one such table per q with the per-work-item
 // part of that factor, W_8192^{t q}, folded in -- pass B's entries times W_8192^{16 q << e}, pass C's times W_8192^{q << e}
-int make_twiddles_t128q(float2 **d_tw)
+int make_twiddles_t128q(DevBuf<float2> &tw)
 {
     std::vector<float2> t2((size_t)4 * kTw128Count);
     auto W = [](long long idx) {
@@ -127,9 +115,7 @@ int make_twiddles_t128q(float2 **d_tw)
         for (int k = 0; k < 128; k++)
             for (int e = 0; e < 4; e++) t[kTw128C + e * 128 + k] = W((long long)(4 * k + q) << e);
     }
-    PG_HIP(hipMalloc((void **)d_tw, sizeof(float2) * t2.size()));
-    PG_HIP(hipMemcpy(*d_tw, t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice));
-    return 0;
+    return tw.upload(t2.data(), t2.size());
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -143,31 +129,24 @@ int OscBank::init(uint32_t channels, double sample_rate)
     ctl.assign(C, Ctl());
     h_osc.assign(C, ChanOsc());
     for (int i = 0; i < 2; i++) {
-        PG_HIP(hipHostMalloc((void **)&h_dyn[i], sizeof(Dyn) * C, 0));
+        PG_TRY(h_dyn[i].alloc(C));
         PG_HIP(hipEventCreate(&h_done[i]));
     }
-    PG_HIP(hipMalloc((void **)&d_osc, sizeof(ChanOsc) * C));
-    PG_HIP(hipMemset(d_osc, 0, sizeof(ChanOsc) * C));
+    PG_TRY(d_osc.alloc_zero(C));
     std::vector<float> amp(kAmpTab);
     design::mixer_amplitudes(amp.data(), kAmpTab, &a_inf);
-    PG_HIP(hipMalloc((void **)&d_amp, sizeof(float) * kAmpTab));
-    PG_HIP(hipMemcpy(d_amp, amp.data(), sizeof(float) * kAmpTab, hipMemcpyHostToDevice));
-    return 0;
+    return d_amp.upload(amp.data(), kAmpTab);
 }
 void OscBank::release()
 {
     for (int i = 0; i < 2; i++) {
-        if (h_dyn[i]) (void)hipHostFree(h_dyn[i]);
         if (h_done[i]) (void)hipEventDestroy(h_done[i]);
-        h_dyn[i] = nullptr;
         h_done[i] = nullptr;
+        h_dyn[i].release();
     }
-    if (d_osc) (void)hipFree(d_osc);
-    if (d_amp) (void)hipFree(d_amp);
-    if (d_adv) (void)hipFree(d_adv);
-    d_adv = nullptr;
-    d_osc = nullptr;
-    d_amp = nullptr;
+    d_osc.release();
+    d_amp.release();
+    d_adv.release();
 }
 void OscBank::retune(uint32_t ch, double f)
 {
@@ -244,7 +223,7 @@ int OscBank::advance_job(hipStream_t s, uint64_t n, OscAdvance *oa)
     memset(oa, 0, sizeof(*oa));
     dev_dyn_valid = false;
     if (!device_advance || C <= (uint32_t)kOscInline) return 0;
-    if (!d_adv) PG_HIP(hipMalloc((void **)&d_adv, sizeof(double) * C));
+    if (!d_adv) PG_TRY(d_adv.alloc(C));
     if (adv_stale || adv_n != n) {  // (rare: a retune or another call length)
         std::vector<double> a(C);
         for (uint32_t ch = 0; ch < C; ch++) {
@@ -312,12 +291,9 @@ int IngestRing::acquire(int device, uint32_t s, uint64_t bytes, void **host_ptr)
     }
     if (g.cap < bytes) {
         PG_HIP(hipStreamSynchronize(copy_stream));
-        if (g.h) (void)hipHostFree(g.h);
-        if (g.d) (void)hipFree(g.d);
-        g.h = g.d = nullptr;
         g.cap = 0;
-        PG_HIP(hipHostMalloc(&g.h, bytes));
-        PG_HIP(hipMalloc(&g.d, bytes));
+        PG_TRY(g.h.alloc(bytes));
+        PG_TRY(g.d.alloc(bytes));
         g.cap = bytes;
     }
     g.submitted = 0;
@@ -386,10 +362,8 @@ int IngestRing::submit_from(int device, uint32_t s, const void *h_src, uint64_t 
     }
     if (g.cap < bytes) {
         PG_HIP(hipStreamSynchronize(copy_stream));
-        if (g.d) (void)hipFree(g.d);
-        g.d = nullptr;
         g.cap = 0;
-        PG_HIP(hipMalloc(&g.d, bytes));
+        PG_TRY(g.d.alloc(bytes));
         g.cap = bytes;
     }
     PG_HIP(hipMemcpyAsync(g.d, h_src, bytes, hipMemcpyHostToDevice, copy_stream));
@@ -402,8 +376,6 @@ void IngestRing::release()
     if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
     copy_stream = nullptr;
     for (IngestSlot &g : slot) {
-        if (g.h) (void)hipHostFree(g.h);
-        if (g.d) (void)hipFree(g.d);
         for (hipEvent_t e : {g.uploaded, g.done_main, g.done_chain}) if (e) (void)hipEventDestroy(e);
         g = IngestSlot();
     }
@@ -414,25 +386,24 @@ int probe_copy(int lane_bytes, size_t bytes, int iters, float *gbps)
 {
     hipStream_t s;
     hipEvent_t e0, e1;
-    void *a = nullptr, *b = nullptr;
+    DevBuf<unsigned char> a, b;
     PG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     PG_HIP(hipEventCreate(&e0));
     PG_HIP(hipEventCreate(&e1));
-    PG_HIP(hipMalloc(&a, bytes));
-    PG_HIP(hipMalloc(&b, bytes));
+    PG_TRY(a.alloc(bytes));
+    PG_TRY(b.alloc(bytes));
     PG_HIP(hipMemsetAsync(a, 1, bytes, s));
     const dim3 grid(256 * 8), block(256);
     for (int it = -1; it < iters; it++) {
         if (it == 0) PG_HIP(hipEventRecord(e0, s));
-        if (lane_bytes == 16) launch(k_probe_copy16, grid, block, s, (const float4 *)a, (float4 *)b, (long long)(bytes / 16));
-        else launch(k_probe_copy8, grid, block, s, (const float2 *)a, (float2 *)b, (long long)(bytes / 8));
+        if (lane_bytes == 16) launch(k_probe_copy16, grid, block, s, (const float4 *)a.get(), (float4 *)b.get(), (long long)(bytes / 16));
+        else launch(k_probe_copy8, grid, block, s, (const float2 *)a.get(), (float2 *)b.get(), (long long)(bytes / 8));
     }
     PG_HIP(hipEventRecord(e1, s));
     PG_HIP(hipEventSynchronize(e1));
     float ms = 0;
     PG_HIP(hipEventElapsedTime(&ms, e0, e1));
     *gbps = (float)(2.0 * (double)bytes * iters / (ms * 1e-3) / 1e9);  // read + write
-    (void)hipFree(a); (void)hipFree(b);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     (void)hipStreamDestroy(s);
     return 0;
@@ -521,7 +492,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
     // the oscillators' advance rides on the launch when the caller handed it over (banks whose oscillators live on the device)
     const bool adv = tun.bank_osc_adv != 0 && oa != nullptr && oa->osc != nullptr && oa->osc_count == C;
     if (adv && !d_dyn[0]) {
-        for (int i = 0; i < 2; i++) PG_HIP(hipMalloc((void **)&d_dyn[i], sizeof(OscDyn) * C));
+        for (int i = 0; i < 2; i++) PG_TRY(d_dyn[i].alloc(C));
     }
     if (osc.dyn_epoch != dyn_epoch_seen) dyn_valid = false;
     dyn_epoch_seen = osc.dyn_epoch;
@@ -531,13 +502,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
     const int S0 = first.stride, Sfs = cic ? S0 * wide_stride : S0;  // input samples per first-stage (hb11) output
     const int hist_split = tun.bank_hsplit;
     const unsigned n_wg = geo.n_wg;
-    if (tun.bank_clk && clk_cap < (size_t)n_wg * 16) {
-        if (d_clk) (void)hipFree(d_clk);
-        d_clk = nullptr;
-        clk_cap = 0;
-        PG_HIP(hipMalloc((void **)&d_clk, sizeof(unsigned long long) * n_wg * 16));
-        clk_cap = (size_t)n_wg * 16;
-    }
+    if (tun.bank_clk) PG_TRY(d_clk.grow(s, (size_t)n_wg * 16));
     if (tun.bank_clk) PG_HIP(hipMemsetAsync(d_clk, 0, sizeof(unsigned long long) * n_wg * 16, s));
     auto common = [&](auto &bp) {
         bp.n_out = len_out;
@@ -711,8 +676,7 @@ int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in,
         wide_stride = (int)w.stride;
         std::vector<float> wt(kMaxTaps, 0.f);
         for (int p = 0; p < w.ntaps; p++) wt[p] = (float)design::halfband_taps(w.design)[p];
-        PG_HIP(hipMalloc((void **)&d_wide_taps, sizeof(float) * kMaxTaps));
-        PG_HIP(hipMemcpy(d_wide_taps, wt.data(), sizeof(float) * kMaxTaps, hipMemcpyHostToDevice));
+        PG_TRY(d_wide_taps.upload(wt.data(), kMaxTaps));
         kfirst = 2;
         fused_front = first.cic3 != 0 && w.ntaps == kFrontT1;  // k_mix_cic_hb is built for the hb11 the ladder always picks here
         memset(&wide_fir, 0, sizeof(wide_fir));
@@ -779,20 +743,11 @@ int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in,
                 fused_p->gain0 = first.gain;
                 fused_p->gain = casc.gain;
             }
-            for (int i = 0; i < 2; i++) {
-                PG_HIP(hipMalloc((void **)&d_xhist[i], sizeof(float2) * xh_depth));
-                PG_HIP(hipMemset(d_xhist[i], 0, sizeof(float2) * xh_depth));
-            }
-            for (int i = 0; i < 2; i++) {  // (64 entries of slack: the kernel requests a block ahead of what it uses)
-                PG_HIP(hipMalloc((void **)&d_y0stage2[i], sizeof(float2) * ((size_t)fused_hy * C + 64)));
-                PG_HIP(hipMemset(d_y0stage2[i], 0, sizeof(float2) * ((size_t)fused_hy * C + 64)));
-            }
+            for (int i = 0; i < 2; i++) PG_TRY(d_xhist[i].alloc_zero(xh_depth));
+            for (int i = 0; i < 2; i++) PG_TRY(d_y0stage2[i].alloc_zero((size_t)fused_hy * C + 64));  // (64 entries of slack: the kernel requests a block ahead of what it uses)
             d_y0stage = d_y0stage2[0];
             if (bank_mfma) {
-                for (int i = 0; i < 2; i++) {
-                    PG_HIP(hipMalloc((void **)&d_bank_state[i], sizeof(float2) * (size_t)bank_nstate * C));
-                    PG_HIP(hipMemset(d_bank_state[i], 0, sizeof(float2) * (size_t)bank_nstate * C));
-                }
+                for (int i = 0; i < 2; i++) PG_TRY(d_bank_state[i].alloc_zero((size_t)bank_nstate * C));
             }
             bank_state_valid = false;
         }
@@ -812,13 +767,8 @@ int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in,
         }
     }
     for (int i = 0; i < 2; i++) {
-        PG_HIP(hipMalloc((void **)&d_hist_mixed[i], sizeof(float2) * kMaxTaps * C));
-        PG_HIP(hipMemset(d_hist_mixed[i], 0, sizeof(float2) * kMaxTaps * C));
-        if (C == 1) {
-            PG_HIP(hipMalloc((void **)&d_xtail_w[i], sizeof(float2) * 2048));
-            PG_HIP(hipMemset(d_xtail_w[i], 0, sizeof(float2) * 2048));
-        }
-
+        PG_TRY(d_hist_mixed[i].alloc_zero((size_t)kMaxTaps * C));
+        if (C == 1) PG_TRY(d_xtail_w[i].alloc_zero(2048));
     }
     return 0;
 }
@@ -827,50 +777,23 @@ void DecimCore::release()
     delete fused_p;
     fused_p = nullptr;
     zero_stage = false;
-    for (int i = 0; i < 2; i++) {
-        if (d_ovl[i]) (void)hipFree(d_ovl[i]);
-        d_ovl[i] = nullptr;
-    }
     ovl_pending = last_in_consumer = false;
     ovl_parity = 0;
-    for (int i = 0; i < 2; i++) {
-        if (d_xhist[i]) (void)hipFree(d_xhist[i]);
-        d_xhist[i] = nullptr;
-    }
-    for (int i = 0; i < 2; i++) {
-        if (d_y0stage2[i]) (void)hipFree(d_y0stage2[i]);
-        d_y0stage2[i] = nullptr;
-    }
     d_y0stage = nullptr;
     for (int i = 0; i < 2; i++) {
-        if (d_bank_state[i]) (void)hipFree(d_bank_state[i]);
-        d_bank_state[i] = nullptr;
+        d_ovl[i].release();
+        d_xhist[i].release();
+        d_y0stage2[i].release();
+        d_bank_state[i].release();
+        d_dyn[i].release();
+        d_hist_mixed[i].release();
+        d_xtail_w[i].release();
     }
-    for (int i = 0; i < 2; i++) {
-        if (d_dyn[i]) (void)hipFree(d_dyn[i]);
-        d_dyn[i] = nullptr;
-    }
-    buf0.release();
-    buf1.release();
-    fin.release();
-    fin2.release();
-    fin3.release();
-    if (d_wide_taps) (void)hipFree(d_wide_taps);
-    d_wide_taps = nullptr;
-    for (int i = 0; i < 2; i++) {
-        if (d_hist_mixed[i]) (void)hipFree(d_hist_mixed[i]);
-        d_hist_mixed[i] = nullptr;
-        if (d_xtail_w[i]) (void)hipFree(d_xtail_w[i]);
-        d_xtail_w[i] = nullptr;
-    }
-    if (d_c0tab) (void)hipFree(d_c0tab);
-    d_c0tab = nullptr;
-    if (d_ph_scratch) (void)hipFree(d_ph_scratch);
-    d_ph_scratch = nullptr;
-    ph_cap = 0;
-    if (d_clk) (void)hipFree(d_clk);
-    d_clk = nullptr;
-    clk_cap = 0;
+    for (HistBuf *b : {&buf0, &buf1, &fin, &fin2, &fin3}) b->release();
+    d_wide_taps.release();
+    d_c0tab.release();
+    d_ph_scratch.release();
+    d_clk.release();
 }
 int DecimCore::set_fuse_window(const float *d_window, const std::vector<float> &w)
 {
@@ -883,7 +806,7 @@ int DecimCore::set_fuse_window(const float *d_window, const std::vector<float> &
     h_r0 = t;
     h_c0.assign(t.size(), make_float2(0.f, 0.f));
     c0_valid = false;
-    if (!d_c0tab) PG_HIP(hipMalloc((void **)&d_c0tab, sizeof(float2) * t.size()));
+    if (!d_c0tab) PG_TRY(d_c0tab.alloc(t.size()));
     fuse_window = d_window;
     return 0;
 }
@@ -934,14 +857,7 @@ int DecimCore::fill_dec_fuse(hipStream_t s, DecFuse *df, const OscBank &osc, lon
     df->c0tab = d_c0tab;
     {
         // one 2 KiB row per frame chain of the transform's launch (chains of at most 32 frames, at least 512 of them)
-        const size_t need = (size_t)(n / 2048 + 1024) * 256;
-        if (need > ph_cap) {
-            if (d_ph_scratch) (void)hipFree(d_ph_scratch);
-            d_ph_scratch = nullptr;
-            ph_cap = 0;
-            PG_HIP(hipMalloc((void **)&d_ph_scratch, sizeof(float2) * need));
-            ph_cap = need;
-        }
+        PG_TRY(d_ph_scratch.grow(s, (size_t)(n / 2048 + 1024) * 256));
         df->ph_scratch = d_ph_scratch;
     }
     return 0;
@@ -1181,10 +1097,7 @@ int DecimCore::enable_mix_in_consumer()
 {
     if (!zero_stage || buf0.hist <= 0) return fail(PEBBLEGPU_E_UNSUPPORTED, "only the consumer of an empty chain mixes in its own loads");
     if (d_ovl[0]) return 0;
-    for (int i = 0; i < 2; i++) {
-        PG_HIP(hipMalloc((void **)&d_ovl[i], sizeof(float2) * (size_t)ovl_len * C));
-        PG_HIP(hipMemset(d_ovl[i], 0, sizeof(float2) * (size_t)ovl_len * C));
-    }
+    for (int i = 0; i < 2; i++) PG_TRY(d_ovl[i].alloc_zero((size_t)ovl_len * C));
     return 0;
 }
 int DecimCore::enable_double_out()
@@ -1261,17 +1174,9 @@ int FastFirCore::init(uint32_t channels, uint32_t fft_size, uint32_t fir_size, c
     // overlap = taps-1 <= L = fft-overlap: one block back always reaches the whole overlap.  Longer filters have no reference semantics
     // (CFastFIR refills only the last L samples of m_pFFTOverlapBuf per block) and cost more than the next FFT size with the same taps
     if (taps < 2 || taps > fft_n / 2 + 1) return fail(PEBBLEGPU_E_INVALID, "FastFIR taps must be in [2, fft/2 + 1] (got %u for fft %u)", taps, fft_n);
-    PG_HIP(hipMalloc((void **)&d_H, sizeof(float2) * (size_t)fft_n * C));
-    PG_HIP(hipMemset(d_H, 0, sizeof(float2) * (size_t)fft_n * C));
-    if (fft_n == 2048) { if (int rc = make_twiddles_t128(&d_tw128)) return rc; }
-    return make_twiddles((int)fft_n, &d_tw);
-}
-void FastFirCore::release()
-{
-    if (d_H) (void)hipFree(d_H);
-    if (d_tw) (void)hipFree(d_tw);
-    if (d_tw128) (void)hipFree(d_tw128);
-    d_H = d_tw = d_tw128 = nullptr;
+    PG_TRY(d_H.alloc_zero((size_t)fft_n * C));
+    if (fft_n == 2048) { if (int rc = make_twiddles_t128(d_tw128)) return rc; }
+    return make_twiddles((int)fft_n, d_tw);
 }
 int FastFirCore::design(hipStream_t s, uint32_t ch, double lo, double hi, double offset, double rate, bool *ok)
 {
@@ -1341,13 +1246,7 @@ int FastFirCore::run_ext(hipStream_t s, const float2 *in, long long in_pitch, fl
         const FfGrid fg = ff_grid(n / L, C, tun.ff_xcd);
         if (raw) {  // the stream bank's raw calls: converted in the loads (twiddles through the vector cache, as the float2 default below)
             auto go = [&](auto kern) { launch_lds(kern, fg.grid, dim3(128), pad, s, in_pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail, d_tail_next, fg.nb, fg.nchan, *raw); };
-            switch (raw->fmt) {
-            case 0: go(k_fastfir_t128_raw<0>); break;
-            case 1: go(k_fastfir_t128_raw<1>); break;
-            case 2: go(k_fastfir_t128_raw<2>); break;
-            case 3: go(k_fastfir_t128_raw<3>); break;
-            default: go(k_fastfir_t128_raw<4>); break;
-            }
+            with_raw_fmt(raw->fmt, [&](auto F) { go(k_fastfir_t128_raw<F.value>); });
         }
         else if (twg) launch_lds(k_fastfir_t128<false>, fg.grid, dim3(128), pad, s, in, in_pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail, d_tail_next, fg.nb, fg.nchan);
         else launch_lds(k_fastfir_t128<true>, fg.grid, dim3(128), pad, s, in, in_pitch, out, out_pitch, (const float2 *)d_H, (const float2 *)d_tw128, overlap, tail, d_tail_next, fg.nb, fg.nchan);
@@ -1373,23 +1272,13 @@ int AmCore::init(uint32_t channels, double demod_rate, long long max_n)
     C = channels;
     rate = demod_rate;
     if (int rc = tmp.alloc((int)C, kMaxTaps, max_n)) return rc;
-    PG_HIP(hipMalloc((void **)&d_taps, sizeof(float) * kMaxTaps * C));
-    PG_HIP(hipMemset(d_taps, 0, sizeof(float) * kMaxTaps * C));
-    PG_HIP(hipMalloc((void **)&d_ntaps, sizeof(int) * C));
-    PG_HIP(hipMemset(d_ntaps, 0, sizeof(int) * C));
-    PG_HIP(hipMalloc((void **)&d_list, sizeof(int) * C));
-    PG_HIP(hipMalloc((void **)&d_state, sizeof(double) * 4 * C));
-    PG_HIP(hipMemset(d_state, 0, sizeof(double) * 4 * C));
+    PG_TRY(d_taps.alloc_zero((size_t)kMaxTaps * C));
+    PG_TRY(d_ntaps.alloc_zero(C));
+    PG_TRY(d_list.alloc(C));
+    PG_TRY(d_state.alloc_zero((size_t)4 * C));
     const double alpha = (double)0.9999f;  // DC_ALPHA is a float literal, demod_am.cpp:36
     fill_scan_section(scan.sec[0], kOnePoleDiff, &alpha);
     return 0;
-}
-void AmCore::release()
-{
-    tmp.release();
-    void *p[] = {d_taps, d_ntaps, d_list, d_state};
-    for (void *q : p) if (q) (void)hipFree(q);
-    d_taps = nullptr; d_ntaps = nullptr; d_list = nullptr; d_state = nullptr;
 }
 int AmCore::set_bandwidth(hipStream_t s, uint32_t ch, double bw)
 {
@@ -1473,24 +1362,11 @@ int PllCore::init(uint32_t channels, double demod_rate, long long max_n, int whi
     // k_fir_dec computes sum_p x[i-(T-1)+p] h[p]; CFir computes sum_k coef[k] x[i-k]: store the taps reversed
     std::vector<float> ri(kMaxTaps, 0.f), rq(kMaxTaps, 0.f);
     for (int p = 0; p < ntaps; p++) { ri[p] = hi[ntaps - 1 - p]; rq[p] = hq[ntaps - 1 - p]; }
-    PG_HIP(hipMalloc((void **)&d_taps_i, sizeof(float) * kMaxTaps));
-    PG_HIP(hipMalloc((void **)&d_taps_q, sizeof(float) * kMaxTaps));
-    PG_HIP(hipMemcpy(d_taps_i, ri.data(), sizeof(float) * kMaxTaps, hipMemcpyHostToDevice));
-    PG_HIP(hipMemcpy(d_taps_q, rq.data(), sizeof(float) * kMaxTaps, hipMemcpyHostToDevice));
+    PG_TRY(d_taps_i.upload(ri.data(), kMaxTaps));
+    PG_TRY(d_taps_q.upload(rq.data(), kMaxTaps));
     if (int rc = tmp.alloc((int)C, kMaxTaps, max_n)) return rc;
-    PG_HIP(hipMalloc((void **)&d_state, sizeof(PllState) * C));
-    PG_HIP(hipMemset(d_state, 0, sizeof(PllState) * C));
-    PG_HIP(hipMalloc((void **)&d_list, sizeof(int) * C));
-    return 0;
-}
-void PllCore::release()
-{
-    tmp.release();
-    void *p[] = {d_taps_i, d_taps_q, d_state, d_list};
-    for (void *q : p) if (q) (void)hipFree(q);
-    d_taps_i = d_taps_q = nullptr;
-    d_state = nullptr;
-    d_list = nullptr;
+    PG_TRY(d_state.alloc_zero(C));
+    return d_list.alloc(C);
 }
 int PllCore::set_list(hipStream_t s, const std::vector<int> &channels)
 {
@@ -1539,8 +1415,7 @@ int WfmCore::init(uint32_t channels, double demod_rate, long long max_n, const T
     ntaps = (int)h.size();
     std::vector<float> hf(kMaxTaps, 0.f);
     for (size_t i = 0; i < h.size(); i++) hf[i] = (float)h[i];
-    PG_HIP(hipMalloc((void **)&d_taps, sizeof(float) * kMaxTaps));
-    PG_HIP(hipMemcpy(d_taps, hf.data(), sizeof(float) * kMaxTaps, hipMemcpyHostToDevice));
+    PG_TRY(d_taps.upload(hf.data(), kMaxTaps));
     // One kernel with no carried state when the cascades decay fast enough to be folded into FIRs (they do at every rate
     // the WFM chain produces: pole radii <= ~0.97); otherwise the exact sequential multi-kernel path below.
     {
@@ -1554,18 +1429,12 @@ int WfmCore::init(uint32_t channels, double demod_rate, long long max_n, const T
             Llp = (int)hl.size();
             ha.resize((size_t)L4 + 16, 0.0);  // the kernel fetches its taps one chunk of 16 ahead
             std::vector<float> hlf(hl.begin(), hl.end()), haf(ha.begin(), ha.end());
-            PG_HIP(hipMalloc((void **)&d_h, sizeof(float) * (L4 + 16)));
-            PG_HIP(hipMemcpy(d_h, haf.data(), sizeof(float) * (L4 + 16), hipMemcpyHostToDevice));
+            PG_TRY(d_h.upload(haf.data(), (size_t)L4 + 16));
             std::vector<float> hm((size_t)wfm_mx_table_floats(L4));
             wfm_mx_fill_taps(haf.data(), L4, hm.data());
-            PG_HIP(hipMalloc((void **)&d_hm, sizeof(float) * hm.size()));
-            PG_HIP(hipMemcpy(d_hm, hm.data(), sizeof(float) * hm.size(), hipMemcpyHostToDevice));
-            PG_HIP(hipMalloc((void **)&d_hlp, sizeof(float) * Llp));
-            PG_HIP(hipMemcpy(d_hlp, hlf.data(), sizeof(float) * Llp, hipMemcpyHostToDevice));
-            for (int i = 0; i < 2; i++) {
-                PG_HIP(hipMalloc((void **)&d_xtail[i], sizeof(float2) * (size_t)(L4 + Llp) * C));
-                PG_HIP(hipMemset(d_xtail[i], 0, sizeof(float2) * (size_t)(L4 + Llp) * C));
-            }
+            PG_TRY(d_hm.upload(hm.data(), hm.size()));
+            PG_TRY(d_hlp.upload(hlf.data(), (size_t)Llp));
+            for (int i = 0; i < 2; i++) PG_TRY(d_xtail[i].alloc_zero((size_t)(L4 + Llp) * C));
             return 0;
         }
     }
@@ -1573,28 +1442,10 @@ int WfmCore::init(uint32_t channels, double demod_rate, long long max_n, const T
     if (int rc = b.alloc((int)C, kMaxTaps, max_n)) return rc;
     if (int rc = c.alloc((int)C, 0, max_n)) return rc;
     for (int i = 0; i < 2; i++) {
-        PG_HIP(hipMalloc((void **)&d_lp_state[i], sizeof(double) * 4 * C));
-        PG_HIP(hipMemset(d_lp_state[i], 0, sizeof(double) * 4 * C));
-        PG_HIP(hipMalloc((void **)&d_dn_state[i], sizeof(double) * 8 * C));
-        PG_HIP(hipMemset(d_dn_state[i], 0, sizeof(double) * 8 * C));
+        PG_TRY(d_lp_state[i].alloc_zero((size_t)4 * C));
+        PG_TRY(d_dn_state[i].alloc_zero((size_t)8 * C));
     }
     return 0;
-}
-void WfmCore::release()
-{
-    a.release(); b.release(); c.release();
-    void *p[] = {d_taps, d_lp_state[0], d_lp_state[1], d_dn_state[0], d_dn_state[1], d_h, d_hm, d_hlp, d_xtail[0], d_xtail[1], d_stereo, d_pilot, d_hilb, d_stereo_list};
-    d_stereo = nullptr;
-    d_pilot = nullptr;
-    d_hilb = nullptr;
-    d_stereo_list = nullptr;
-    lm.release();
-    lm_pending = 0;
-    rds.release();
-    for (void *q : p) if (q) (void)hipFree(q);
-    d_taps = nullptr;
-    d_lp_state[0] = d_lp_state[1] = d_dn_state[0] = d_dn_state[1] = nullptr;
-    d_h = nullptr; d_hm = nullptr; d_hlp = nullptr; d_xtail[0] = d_xtail[1] = nullptr;
 }
 int WfmCore::set_stereo(uint32_t ch, bool on)
 {
@@ -1607,17 +1458,15 @@ int WfmCore::set_stereo(uint32_t ch, bool on)
         pilot.nco_lo = pd.nco_lo; pilot.nco_hi = pd.nco_hi; pilot.alpha = pd.alpha; pilot.beta = pd.beta;
         pilot.err_alpha = pd.err_alpha; pilot.phase_adjust = pd.phase_adjust;
         pilot.L4 = L4;
-        PG_HIP(hipMalloc((void **)&d_hilb, sizeof(double) * 122));
-        PG_HIP(hipMemcpy(d_hilb, pd.hilb, sizeof(double) * 122, hipMemcpyHostToDevice));
-        PG_HIP(hipMalloc((void **)&d_pilot, sizeof(WfmPilotState) * C));
-        PG_HIP(hipMalloc((void **)&d_stereo_list, sizeof(int) * C));
+        PG_TRY(d_hilb.upload(pd.hilb, 122));
+        PG_TRY(d_stereo_list.alloc(C));
         if (int rc = lm.alloc((int)C, L4 + 16, max_n_)) return rc;
         // initPilotPll (demod_wfm.cpp:371-386), once per object as in the reference: a channel that leaves dmFMS and comes back finds its
         // loop where it left it (its lock average still high: it stays dropped)
         std::vector<WfmPilotState> z(C);
         memset(z.data(), 0, sizeof(WfmPilotState) * C);
         for (auto &q : z) { q.nco_freq = pd.nco_freq0; q.quiet = 1LL << 40; }
-        PG_HIP(hipMemcpy(d_pilot, z.data(), sizeof(WfmPilotState) * C, hipMemcpyHostToDevice));
+        PG_TRY(d_pilot.upload(z.data(), C));
         // the RDS members, initialised with the rest of setSampleRate (demod_wfm.cpp:187-191)
         if (tun.rds) { if (int rc = rds.init(C, rate, max_n_)) return rc; }
     }
@@ -1648,7 +1497,7 @@ int WfmCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *ou
     if (n < kMaxTaps) return fail(PEBBLEGPU_E_SIZE, "WFM demod needs at least %d samples per call", kMaxTaps);
     last_n = n;
     if (stereo_dirty) {  // (rare: a mode change)
-        if (!d_stereo) PG_HIP(hipMalloc((void **)&d_stereo, C));
+        if (!d_stereo) PG_TRY(d_stereo.alloc(C));
         PG_HIP(hipMemcpyAsync(d_stereo, stereo.data(), C, hipMemcpyHostToDevice, s));
         std::vector<int> list;
         for (uint32_t ch = 0; ch < C; ch++) if (stereo[ch]) list.push_back((int)ch);
@@ -1803,21 +1652,13 @@ int AgcCore::init(uint32_t channels, double demod_rate)
     C = channels;
     rate = demod_rate;
     host.assign(C, Host());
-    PG_HIP(hipMalloc((void **)&d_state, sizeof(AgcState) * C));
-    PG_HIP(hipMemset(d_state, 0, sizeof(AgcState) * C));
-    PG_HIP(hipMalloc((void **)&d_list, sizeof(int) * C));
+    PG_TRY(d_state.alloc_zero(C));
+    PG_TRY(d_list.alloc(C));
     std::vector<AgcState> init(1);
     memset(&init[0], 0, sizeof(AgcState));
     init[0].manual_gain = 1.0;  // AGC::AGC -> setAgcMode(AGC_OFF, 1): dBToAmplitude(1 / 5) = 1 (agc.cpp:29,241-245)
     for (uint32_t c = 0; c < C; c++) PG_HIP(hipMemcpy(d_state + c, &init[0], offsetof(AgcState, sig), hipMemcpyHostToDevice));
     return 0;
-}
-void AgcCore::release()
-{
-    if (d_state) (void)hipFree(d_state);
-    if (d_list) (void)hipFree(d_list);
-    d_state = nullptr;
-    d_list = nullptr;
 }
 int AgcCore::set_mode(uint32_t ch, int mode, int threshold)
 {
@@ -1910,27 +1751,19 @@ int ConditionCore::init(uint32_t streams, uint32_t frame, double sample_rate, lo
     fill_scan_section(dc.sec[0], kBiquadDf2, c);
     return 0;
 }
-void ConditionCore::release()
-{
-    void *p[] = {d_buf, d_dc_state, d_dc_list, d_iq, d_nb};
-    for (void *q : p) if (q) (void)hipFree(q);
-    d_buf = nullptr; d_dc_state = nullptr; d_dc_list = nullptr; d_iq = nullptr; d_nb = nullptr;
-}
 int ConditionCore::set(uint32_t stream, int flags, double gain, double phase)
 {
     if (stream >= S || flags < 0 || flags > 15) return fail(PEBBLEGPU_E_INVALID, "bad stream or conditioner flags");
     Host &h = host[stream];
     if (!d_buf) {  // first use: the conditioned copy and the per-stream state
-        PG_HIP(hipMalloc((void **)&d_buf, sizeof(float2) * (size_t)cap * S));
-        PG_HIP(hipMalloc((void **)&d_dc_state, sizeof(double) * 4 * S));
-        PG_HIP(hipMemset(d_dc_state, 0, sizeof(double) * 4 * S));
-        PG_HIP(hipMalloc((void **)&d_dc_list, sizeof(int) * S));
-        PG_HIP(hipMalloc((void **)&d_iq, sizeof(double2) * S));
-        PG_HIP(hipMalloc((void **)&d_nb, sizeof(NbState) * S));
+        PG_TRY(d_buf.alloc((size_t)cap * S));
+        PG_TRY(d_dc_state.alloc_zero((size_t)4 * S));
+        PG_TRY(d_dc_list.alloc(S));
+        PG_TRY(d_iq.alloc(S));
         std::vector<NbState> nb(S);
         memset(nb.data(), 0, sizeof(NbState) * S);
         for (auto &b : nb) { b.nb_avg_mag = 1; b.nb2_avg_mag = 1; }  // NoiseBlanker ctor, noiseblanker.cpp:9-15
-        PG_HIP(hipMemcpy(d_nb, nb.data(), sizeof(NbState) * S, hipMemcpyHostToDevice));
+        PG_TRY(d_nb.upload(nb.data(), S));
     }
     // setNbEnabled(true) / setNb2Enabled(true) reset their averages (noiseblanker.cpp:20-37)
     const int turned_on = flags & ~h.flags;
@@ -1996,20 +1829,12 @@ int AnfCore::init(uint32_t channels)
     on.assign(C, 0);
     return 0;
 }
-void AnfCore::release()
-{
-    if (d_state) (void)hipFree(d_state);
-    if (d_list) (void)hipFree(d_list);
-    d_state = nullptr;
-    d_list = nullptr;
-}
 int AnfCore::set(uint32_t ch, bool enable)
 {
     if (ch >= C) return fail(PEBBLEGPU_E_INVALID, "channel %u out of range", ch);
     if (!d_state) {
-        PG_HIP(hipMalloc((void **)&d_state, sizeof(AnfState) * C));
-        PG_HIP(hipMemset(d_state, 0, sizeof(AnfState) * C));  // new CPX[] coefficients and the delay line start at zero
-        PG_HIP(hipMalloc((void **)&d_list, sizeof(int) * C));
+        PG_TRY(d_state.alloc_zero(C));  // new CPX[] coefficients and the delay line start at zero
+        PG_TRY(d_list.alloc(C));
     }
     on[ch] = enable ? 1 : 0;
     dirty = true;
@@ -2051,29 +1876,20 @@ int ResampCore::init(uint32_t channels, uint32_t frame, double rate, uint32_t fr
         const double fi = (design::kTwoPi / 2.0) * (double)(i - kSincLength / 2) / (double)kSincPeriodPts;
         t[i] = (float)(i != kSincLength / 2 ? window * std::sin(fi) / fi : 1.0);
     }
-    PG_HIP(hipMalloc((void **)&d_sinc, sizeof(float) * kSincLength));
-    PG_HIP(hipMemcpy(d_sinc, t.data(), sizeof(float) * kSincLength, hipMemcpyHostToDevice));
+    PG_TRY(d_sinc.upload(t.data(), (size_t)kSincLength));
     for (int i = 0; i < 2; i++) {
-        PG_HIP(hipMalloc((void **)&d_hist[i], sizeof(float2) * kSincPeriods * C));
-        PG_HIP(hipMemset(d_hist[i], 0, sizeof(float2) * kSincPeriods * C));  // Init zeroes m_pInputBuf
-        PG_HIP(hipHostMalloc((void **)&h_frames[i], sizeof(ResampFrame) * max_frames));
+        PG_TRY(d_hist[i].alloc_zero((size_t)kSincPeriods * C));  // Init zeroes m_pInputBuf
+        PG_TRY(h_frames[i].alloc(max_frames));
         PG_HIP(hipEventCreateWithFlags(&h_done[i], hipEventDisableTiming));
     }
-    PG_HIP(hipMalloc((void **)&d_frames, sizeof(ResampFrame) * max_frames));
-    return 0;
+    return d_frames.alloc(max_frames);
 }
 void ResampCore::release()
 {
-    if (d_sinc) (void)hipFree(d_sinc);
-    if (d_frames) (void)hipFree(d_frames);
-    for (int i = 0; i < 2; i++) {
-        if (d_hist[i]) (void)hipFree(d_hist[i]);
-        if (h_frames[i]) (void)hipHostFree(h_frames[i]);
-        if (h_done[i]) (void)hipEventDestroy(h_done[i]);
-        d_hist[i] = nullptr; h_frames[i] = nullptr; h_done[i] = nullptr;
+    for (hipEvent_t &e : h_done) {  // (the memory goes with the object)
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
     }
-    d_sinc = nullptr;
-    d_frames = nullptr;
 }
 int ResampCore::run(hipStream_t s, const float2 *in, long long in_pitch, long long n, float2 *out, long long out_pitch, long long *n_out)
 {
@@ -2121,6 +1937,18 @@ int ResampCore::run(hipStream_t s, const float2 *in, long long in_pitch, long lo
 // ------------------------------------------------------------------------------------------------
 // SpectrumCore
 // ------------------------------------------------------------------------------------------------
+// [bins/nf][nf] w[n] * W_bins^{n q}: the one factor per point of k_spectrum_q128 and k_spectrum_list_q128
+static std::vector<float2> factor_table(const std::vector<double> &w, uint32_t nf, uint32_t bins)
+{
+    const uint32_t zp = bins / nf;
+    std::vector<float2> ft((size_t)zp * nf);
+    for (uint32_t q = 0; q < zp; q++)
+        for (uint32_t n = 0; n < nf; n++) {
+            const double a = -design::kTwoPi * (double)(((uint64_t)n * q) % bins) / (double)bins;
+            ft[(size_t)q * nf + n] = make_float2((float)(w[n] * std::cos(a)), (float)(w[n] * std::sin(a)));
+        }
+    return ft;
+}
 int SpectrumCore::init(uint32_t streams, uint32_t frame, uint32_t fft_size, const Tuning &t)
 {
     tun = t;
@@ -2147,8 +1975,7 @@ int SpectrumCore::init(uint32_t streams, uint32_t frame, uint32_t fft_size, cons
             any_M = M; any_logM = lg; any_zp_log2 = zl;
             std::vector<float2> tw((size_t)M / 2);
             for (int k = 0; k < M / 2; k++) tw[k] = make_float2((float)std::cos(-design::kTwoPi * k / M), (float)std::sin(-design::kTwoPi * k / M));
-            PG_HIP(hipMalloc((void **)&d_twM, sizeof(float2) * tw.size()));
-            PG_HIP(hipMemcpy(d_twM, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
+            PG_TRY(d_twM.upload(tw.data(), tw.size()));
         }
     }
     // One transform per 128-item workgroup (k_spectrum_q128) serves every power-of-two zero-padding; measured against the
@@ -2161,8 +1988,7 @@ int SpectrumCore::init(uint32_t streams, uint32_t frame, uint32_t fft_size, cons
     const double cg = design::blackman_harris(nf, w);
     std::vector<float> wf(nf);
     for (uint32_t i = 0; i < nf; i++) wf[i] = (float)w[i];
-    PG_HIP(hipMalloc((void **)&d_window, sizeof(float) * nf));
-    PG_HIP(hipMemcpy(d_window, wf.data(), sizeof(float) * nf, hipMemcpyHostToDevice));
+    PG_TRY(d_window.upload(wf.data(), nf));
     h_window = wf;
     // btab[q][m] = exp(-2*pi*i*(64*m*q)/bins): the wave-uniform factor of the pruned-FFT pre-twiddle W_bins^{n q},
     // n = lane + 64 m (the per-lane factor W_bins^{lane q} is computed in the kernel)
@@ -2174,18 +2000,11 @@ int SpectrumCore::init(uint32_t streams, uint32_t frame, uint32_t fft_size, cons
             const double a = -design::kTwoPi * (double)k / (double)bins;
             bt[(size_t)q * 32 + m] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
-    PG_HIP(hipMalloc((void **)&d_btab, sizeof(float2) * bt.size()));
-    PG_HIP(hipMemcpy(d_btab, bt.data(), sizeof(float2) * bt.size(), hipMemcpyHostToDevice));
+    PG_TRY(d_btab.upload(bt.data(), bt.size()));
     if (per_q) {
-        std::vector<float2> ft((size_t)zp * nf);
-        for (uint32_t q = 0; q < zp; q++)
-            for (uint32_t n = 0; n < nf; n++) {
-                const double a = -design::kTwoPi * (double)(((uint64_t)n * q) % bins) / (double)bins;
-                ft[(size_t)q * nf + n] = make_float2((float)(w[n] * std::cos(a)), (float)(w[n] * std::sin(a)));
-            }
-        PG_HIP(hipMalloc((void **)&d_ftab, sizeof(float2) * ft.size()));
-        PG_HIP(hipMemcpy(d_ftab, ft.data(), sizeof(float2) * ft.size(), hipMemcpyHostToDevice));
-        if (int rc = make_twiddles_t128(&d_tw128)) return rc;
+        const std::vector<float2> ft = factor_table(w, nf, bins);
+        PG_TRY(d_ftab.upload(ft.data(), ft.size()));
+        if (int rc = make_twiddles_t128(d_tw128)) return rc;
     }
     if (bins == 8192 && !big && !per_q) {
         stagger = tun.t128_stagger;  // measured on the bench batch: 0.300 ms as two 512-item workgroups per CU, 0.278 with the halves three intervals apart
@@ -2196,32 +2015,24 @@ int SpectrumCore::init(uint32_t streams, uint32_t frame, uint32_t fft_size, cons
                 const double a = -design::kTwoPi * (double)((128 * m * q) % 8192) / 8192.0;
                 b2[q * 16 + m] = make_float2((float)std::cos(a), (float)std::sin(a));
             }
-        PG_HIP(hipMalloc((void **)&d_btab128, sizeof(float2) * b2.size()));
-        PG_HIP(hipMemcpy(d_btab128, b2.data(), sizeof(float2) * b2.size(), hipMemcpyHostToDevice));
-        if (int rc = make_twiddles_t128q(&d_tw128)) return rc;  // (k_spectrum_t128's own: one table per q)
+        PG_TRY(d_btab128.upload(b2.data(), b2.size()));
+        if (int rc = make_twiddles_t128q(d_tw128)) return rc;  // (k_spectrum_t128's own: one table per q)
     }
     scale = (float)(1.0 / (cg * (double)nf));  // /coherentGain then /maxBinPower, fft.cpp:347,355
-    if (int rc = make_twiddles(2048, &d_tw_nf)) return rc;
-    for (int i = 0; i < 2; i++) {
-        PG_HIP(hipMalloc((void **)&d_prev[i], sizeof(float) * (size_t)bins * S));
-        PG_HIP(hipMemset(d_prev[i], 0, sizeof(float) * (size_t)bins * S));  // the reference leaves these uninitialised (fft.cpp:107-115)
-    }
+    if (int rc = make_twiddles(2048, d_tw_nf)) return rc;
+    for (int i = 0; i < 2; i++) PG_TRY(d_prev[i].alloc_zero((size_t)bins * S));  // the reference leaves these uninitialised (fft.cpp:107-115)
     return 0;
 }
-void SpectrumCore::release()
+// The 65536-point transform's intermediate Y (8 bytes per point, written by pass A, read by pass B) for a call of per_stream points per
+// stream: streams are processed in batches (*bs streams each) whose Y fits well inside the 256 MiB Infinity Cache together with the
+// batch's own input and output (one buffer reused by every batch), instead of a call-sized Y that went out to HBM and back (28 B moved
+// per 12 B of algorithmic traffic).
+int SpectrumCore::size_Y(hipStream_t s, long long per_stream, long long *bs)
 {
-    void *p[] = {d_window, d_btab, d_prev[0], d_prev[1], d_tw_nf, d_Y, d_btab128, d_tw128, d_ftab, d_twM};
-    d_twM = nullptr;
-    for (void *q : p) if (q) (void)hipFree(q);
-    if (list_owned) {
-        if (d_list_ftab) (void)hipFree(d_list_ftab);
-        if (d_list_tw128) (void)hipFree(d_list_tw128);
-    }
-    d_list_ftab = d_list_tw128 = nullptr;
-    list_owned = false;
-    d_ftab = nullptr;
-    d_window = nullptr; d_btab = nullptr; d_prev[0] = d_prev[1] = nullptr; d_tw_nf = nullptr; d_Y = nullptr; d_btab128 = d_tw128 = nullptr;
-    y_cap = 0;
+    const long long batch_mb = tun.big_batch_mb;  // 0: the whole call in one pair of launches (measured: 16 / 32 / 64 / 128 MiB batches 0.61 / 0.48 / 0.39 / 0.34 ms against 0.34 whole: the kernels are not bound by that traffic)
+    long long b = batch_mb > 0 ? (batch_mb << 20) / (long long)sizeof(float2) / per_stream : (long long)S;  // streams per batch
+    *bs = b = b < 1 ? 1 : (b > (long long)S ? (long long)S : b);
+    return d_Y.grow(s, (size_t)b * (size_t)per_stream);
 }
 // FFT::fftSpectrum for any frame length (and for fewer samples than samplesPerBuffer: copied, zero-padded, not windowed, fft.cpp:129-157)
 int SpectrumCore::run_any(hipStream_t s, const float2 *d_in, long long in_pitch, long long F, float *d_out, int n_in, bool windowed)
@@ -2263,23 +2074,8 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
     sp.n_frames = F;
     if (big) {
         if (F == 0) return 0;
-        // The four-step intermediate Y (8 bytes per point, written by pass A, read by pass B) is kept on the die: streams are
-        // processed in batches whose Y fits well inside the 256 MiB Infinity Cache together with the batch's own input and output
-        // (one 64 MiB buffer reused by every batch), instead of a call-sized Y that went out to HBM and back
-        // (28 B moved per 12 B of algorithmic traffic).
-        const long long per_stream = (long long)F * kBigN;                       // Y points per stream
-        const long long batch_mb = tun.big_batch_mb;  // 0: the whole call in one pair of launches (measured: 16 / 32 / 64 / 128 MiB batches 0.61 / 0.48 / 0.39 / 0.34 ms against 0.34 whole: the kernels are not bound by that traffic)
-        long long bs = batch_mb > 0 ? (batch_mb << 20) / (long long)sizeof(float2) / per_stream : (long long)S;    // streams per batch
-        bs = bs < 1 ? 1 : (bs > (long long)S ? (long long)S : bs);
-        const size_t need = (size_t)bs * (size_t)per_stream;
-        if (need > y_cap) {
-            PG_HIP(hipStreamSynchronize(s));
-            if (d_Y) (void)hipFree(d_Y);
-            d_Y = nullptr;
-            y_cap = 0;
-            PG_HIP(hipMalloc((void **)&d_Y, sizeof(float2) * need));
-            y_cap = need;
-        }
+        long long bs = 0;  // streams per batch
+        PG_TRY(size_Y(s, (long long)F * kBigN, &bs));
         // a chain that does not start at frame 0 recomputes one frame: chains sized by the batch (spectrum_geom.h)
         const SpectrumGeom geo = spectrum_geometry(SpecFamily::big, F, S, bins, nf, bs);
         sp.frames_per_group = geo.G;
@@ -2298,13 +2094,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
                     const bool b8 = raw->fmt == 0 || raw->fmt == 1;  // 8-bit pairs: the paired tile order (kernels_spectrum.h)
                     const dim3 grid(b8 ? (unsigned)(16 * cdiv(F, 2)) : (unsigned)(F * 8), nb);
                     auto go = [&](auto kern) { launch(kern, grid, dim3(256), s, (long long)in_pitch, d_Y, (const float *)d_window, (long long)F, rs); };
-                    switch (raw->fmt) {
-                    case 0: go(k_big256_cols_raw<0>); break;
-                    case 1: go(k_big256_cols_raw<1>); break;
-                    case 2: go(k_big256_cols_raw<2>); break;
-                    case 3: go(k_big256_cols_raw<3>); break;
-                    default: go(k_big256_cols_raw<4>); break;
-                    }
+                    with_raw_fmt(raw->fmt, [&](auto F) { go(k_big256_cols_raw<F.value>); });
                 } else
                 launch(k_big256_cols, dim3((unsigned)(F * 8), nb), dim3(256), s, d_in + s0 * in_pitch, (long long)in_pitch, d_Y, (const float *)d_window, (long long)F);
                 launch(k_big256_rows, dim3(geo.wgs, nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch,
@@ -2340,14 +2130,7 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
         const RawSrc rs = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
         const dim3 grid(geo.wgs, S), block(256);
         auto go = [&](auto kern) { launch(kern, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab, (const float *)d_prev[parity], d_prev[parity ^ 1], sp, rs); };
-        switch (raw ? raw->fmt : -1) {
-        case -1: go(k_spectrum_w64<-1>); break;
-        case 0: go(k_spectrum_w64<0>); break;
-        case 1: go(k_spectrum_w64<1>); break;
-        case 2: go(k_spectrum_w64<2>); break;
-        case 3: go(k_spectrum_w64<3>); break;
-        default: go(k_spectrum_w64<4>); break;
-        }
+        with_sample_fmt(raw, [&](auto F) { go(k_spectrum_w64<F.value>); });
         parity ^= 1;
         PG_HIP(hipGetLastError());
         return 0;
@@ -2365,46 +2148,20 @@ int SpectrumCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lon
         DecFuse none;
         memset(&none, 0, sizeof(none));
         const DecFuse &dfv = df ? *df : none;
-        if (df) {  // the one-channel decimator rides in the transform's workgroups (two chains per workgroup, every sample format)
-            const dim3 grid(geo.wgs, S), block(1024);
-            const int st = stagger > 0 ? stagger : 3;
-            auto go = [&](auto kern) { launch(kern, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, st, rs, dfv); };
-            switch (raw ? raw->fmt : -1) {
-            case -1: go(k_spectrum_t128<2, -1, true>); break;
-            case 0: go(k_spectrum_t128<2, 0, true>); break;
-            case 1: go(k_spectrum_t128<2, 1, true>); break;
-            case 2: go(k_spectrum_t128<2, 2, true>); break;
-            case 3: go(k_spectrum_t128<2, 3, true>); break;
-            default: go(k_spectrum_t128<2, 4, true>); break;
-            }
-        } else if (last_fullc) {
+        // two chains per 1024-item workgroup, the second `st` barrier intervals behind the first
+        auto go = [&](auto kern, int st) {
+            launch(kern, dim3(geo.wgs, S), dim3(1024), s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, st, rs, dfv);
+        };
+        if (df)  // the one-channel decimator rides in the transform's workgroups (every sample format)
+            with_sample_fmt(raw, [&](auto F) { go(k_spectrum_t128<2, F.value, true>, stagger > 0 ? stagger : 3); });
+        else if (last_fullc)
             // nothing is to run beside this launch: pass C's fifteen twiddles per work-item formed once and held (126 registers: four such
             // waves fill a SIMD's register file) -- 0.200 ms for the bench batch against 0.224
-            const dim3 grid(geo.wgs, S), block(1024);
-            const int st = stagger > 0 ? stagger : 3;
-            auto go = [&](auto kern) { launch(kern, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, st, rs, dfv); };
-            switch (raw ? raw->fmt : -1) {
-            case -1: go(k_spectrum_t128<2, -1, false, true>); break;
-            case 0: go(k_spectrum_t128<2, 0, false, true>); break;
-            case 1: go(k_spectrum_t128<2, 1, false, true>); break;
-            case 2: go(k_spectrum_t128<2, 2, false, true>); break;
-            case 3: go(k_spectrum_t128<2, 3, false, true>); break;
-            default: go(k_spectrum_t128<2, 4, false, true>); break;
-            }
-        } else if (raw) {  // raw-format frames take the two-chain kernel (one instantiation per sample format)
-            const dim3 grid(geo.wgs, S), block(1024);
-            const int st = stagger > 0 ? stagger : 7;
-            auto go = [&](auto kern) { launch(kern, grid, block, s, d_in, d_out, (const float *)d_window, (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, st, rs, dfv); };
-            switch (raw->fmt) {
-            case 0: go(k_spectrum_t128<2, 0>); break;
-            case 1: go(k_spectrum_t128<2, 1>); break;
-            case 2: go(k_spectrum_t128<2, 2>); break;
-            case 3: go(k_spectrum_t128<2, 3>); break;
-            default: go(k_spectrum_t128<2, 4>); break;
-            }
-        } else if (stagger > 0)  // two chains per 1024-item workgroup, the second `stagger` barrier intervals behind the first
-            launch(k_spectrum_t128<2, -1>, dim3(geo.wgs, S), dim3(1024), s, d_in, d_out, (const float *)d_window,
-                   (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, stagger, rs, dfv);
+            with_sample_fmt(raw, [&](auto F) { go(k_spectrum_t128<2, F.value, false, true>, stagger > 0 ? stagger : 3); });
+        else if (raw)  // raw-format frames take the two-chain kernel (one instantiation per sample format)
+            with_raw_fmt(raw->fmt, [&](auto F) { go(k_spectrum_t128<2, F.value>, stagger > 0 ? stagger : 7); });
+        else if (stagger > 0)
+            go(k_spectrum_t128<2, -1>, stagger);
         else
             launch_lds(k_spectrum_t128<1, -1>, dim3(geo.wgs, S), dim3(512), (size_t)pad_lds, s, d_in, d_out, (const float *)d_window,
                        (const float2 *)d_btab128, (const float2 *)d_tw128, pin, pout, sp, 0, rs, dfv);
@@ -2436,17 +2193,11 @@ int SpectrumCore::init_list()
         d_list_tw128 = d_tw128;
         return 0;
     }
-    const uint32_t zp = bins / nf;
-    std::vector<float2> ft((size_t)zp * nf);
-    for (uint32_t q = 0; q < zp; q++)
-        for (uint32_t n = 0; n < nf; n++) {
-            const double a = -design::kTwoPi * (double)(((uint64_t)n * q) % bins) / (double)bins;
-            ft[(size_t)q * nf + n] = make_float2((float)((double)h_window[n] * std::cos(a)), (float)((double)h_window[n] * std::sin(a)));
-        }
-    PG_HIP(hipMalloc((void **)&d_list_ftab, sizeof(float2) * ft.size()));
-    PG_HIP(hipMemcpy(d_list_ftab, ft.data(), sizeof(float2) * ft.size(), hipMemcpyHostToDevice));
-    list_owned = true;
-    if (int rc = make_twiddles_t128(&d_list_tw128)) return rc;
+    const std::vector<float2> ft = factor_table(std::vector<double>(h_window.begin(), h_window.end()), nf, bins);
+    PG_TRY(own_list_ftab.upload(ft.data(), ft.size()));
+    PG_TRY(make_twiddles_t128(own_list_tw128));
+    d_list_ftab = own_list_ftab;
+    d_list_tw128 = own_list_tw128;
     return 0;
 }
 // The 65536-point transform of the listed frames: pass A reads the listed frames and leaves COMPACT rows in Y ([stream][n_sel][k1][n2],
@@ -2457,19 +2208,8 @@ int SpectrumCore::init_list()
 int SpectrumCore::run_list_big(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw)
 {
     if (raw && !raw_ready_big()) return fail(PEBBLEGPU_E_INVALID, "raw-format input reached a spectrum kernel that has no converting loads");
-    const long long per_stream = n_sel * kBigN;  // Y points per stream
-    const long long batch_mb = tun.big_batch_mb;
-    long long bs = batch_mb > 0 ? (batch_mb << 20) / (long long)sizeof(float2) / per_stream : (long long)S;  // streams per batch
-    bs = bs < 1 ? 1 : (bs > (long long)S ? (long long)S : bs);
-    const size_t need = (size_t)bs * (size_t)per_stream;
-    if (need > y_cap) {
-        PG_HIP(hipStreamSynchronize(s));
-        if (d_Y) (void)hipFree(d_Y);
-        d_Y = nullptr;
-        y_cap = 0;
-        PG_HIP(hipMalloc((void **)&d_Y, sizeof(float2) * need));
-        y_cap = need;
-    }
+    long long bs = 0;  // streams per batch
+    PG_TRY(size_Y(s, n_sel * kBigN, &bs));
     const SpectrumGeom geo = spectrum_geometry(SpecFamily::big, n_sel, S, bins, nf, bs);
     SpectrumParams sp;
     sp.in_pitch = in_pitch;
@@ -2492,14 +2232,7 @@ int SpectrumCore::run_list_big(hipStream_t s, const float2 *d_in, long long in_p
             for (int i = 0; i < fl.n; i++) fl.idx[i] = idx[r0 + i];
             const dim3 grid(b8 ? (unsigned)(16 * cdiv(fl.n, 2)) : (unsigned)(fl.n * 8), nb);
             auto go = [&](auto kern) { launch(kern, grid, dim3(256), s, in0, (long long)in_pitch, d_Y, (const float *)d_window, (long long)n_sel, fl, rs); };
-            switch (raw ? raw->fmt : -1) {
-            case -1: go(k_big256_cols_list<-1>); break;
-            case 0: go(k_big256_cols_list<0>); break;
-            case 1: go(k_big256_cols_list<1>); break;
-            case 2: go(k_big256_cols_list<2>); break;
-            case 3: go(k_big256_cols_list<3>); break;
-            default: go(k_big256_cols_list<4>); break;
-            }
+            with_sample_fmt(raw, [&](auto F) { go(k_big256_cols_list<F.value>); });
         }
         launch(k_big256_rows, dim3(geo.wgs, nb), dim3(256), s, (const float2 *)d_Y, d_out + s0 * sp.out_pitch,
                (const float *)d_prev[parity] + s0 * kBigN, d_prev[parity ^ 1] + s0 * kBigN, sp);

@@ -267,7 +267,7 @@ struct DisplayRing {
         double min_db = 0;               // the map's lower end (sh has the upper one)
         unsigned x_blocks = 1;
         std::vector<DisplayRow> tab;     // the device table's host copy
-        DisplayRow *d_tab = nullptr;
+        DevBuf<DisplayRow> d_tab;
     };
     struct SlotPane { uint32_t rows, first_row, row_elems; uint64_t row_pitch, offset; };
     EgressRing ring;
@@ -281,7 +281,7 @@ struct DisplayRing {
     uint32_t scale_flags = 0;            // PEBBLEGPU_AUTO_SCALE_* as last set
     uint32_t scale_live = 0;             // ... those whose end of the range a recalc has computed since the flag went on
     bool scale_pending = false;          // m_scaleNeedsRecalc
-    ScaleEntry *d_scale = nullptr;       // [streams] the ranges, written by k_scale_stats in a recalc call
+    DevBuf<ScaleEntry> d_scale;          // [streams] the ranges, written by k_scale_stats in a recalc call
     hipEvent_t scale_ev = nullptr;       // behind that launch, for the panes packed on the other stream (the recalc call only)
     hipEvent_t scale_rd_ev = nullptr;    // ... and in front of it: behind everything queued on the other stream so far (the table's readers there)
     uint64_t trailer_cap = 0;            // bytes of a slot kept for the trailer
@@ -290,18 +290,14 @@ struct DisplayRing {
 
     void free_device()
     {
-        if (d_scale) (void)hipFree(d_scale);
-        d_scale = nullptr;
+        d_scale.release();
         if (scale_ev) (void)hipEventDestroy(scale_ev);
         scale_ev = nullptr;
         if (scale_rd_ev) (void)hipEventDestroy(scale_rd_ev);
         scale_rd_ev = nullptr;
         scale_flags = scale_live = 0;
         scale_pending = false;
-        for (Pane &p : pane) {
-            if (p.d_tab) (void)hipFree(p.d_tab);
-            p.d_tab = nullptr;
-        }
+        for (Pane &p : pane) p.d_tab.release();
         for (hipEvent_t &e : packed2) {
             if (e) (void)hipEventDestroy(e);
             e = nullptr;
@@ -417,11 +413,10 @@ int Receiver::display_open(const pebblegpu_display_pane *panes, uint32_t n_panes
     DisplayRing &d = *disp_;
     std::lock_guard<std::mutex> lk(d.ring.mu);
     auto body = [&]() -> int {
-        for (uint32_t k = 0; k < n_panes; k++) PG_HIP(hipMalloc((void **)&plan[k].d_tab, sizeof(DisplayRow) * plan[k].tab.size()));
+        for (uint32_t k = 0; k < n_panes; k++) PG_TRY(plan[k].d_tab.alloc(plan[k].tab.size()));
         // the auto-scale trailer holds pane 0's selected rows; the ranges' table one entry per stream
         d.trailer_cap = trailer_cap;
-        PG_HIP(hipMalloc((void **)&d.d_scale, sizeof(ScaleEntry) * S));
-        PG_HIP(hipMemset(d.d_scale, 0, sizeof(ScaleEntry) * S));
+        PG_TRY(d.d_scale.alloc_zero(S));
         PG_HIP(hipEventCreateWithFlags(&d.scale_ev, hipEventDisableTiming));
         PG_HIP(hipEventCreateWithFlags(&d.scale_rd_ev, hipEventDisableTiming));
         if (int rc = d.ring.open_ring(n_slots, 1, 4, (slot_bytes - trailer_cap) / 4, 0, trailer_cap)) return rc;
@@ -434,14 +429,13 @@ int Receiver::display_open(const pebblegpu_display_pane *panes, uint32_t n_panes
     };
     if (int rc = body()) {
         d.ring.release();
-        for (uint32_t k = 0; k < n_panes; k++) if (plan[k].d_tab) (void)hipFree(plan[k].d_tab);
         d.free_device();
-        return rc;
+        return rc;  // (the planned panes' tables go with `plan`)
     }
     for (uint32_t k = 0; k < n_panes; k++) {
-        d.pane[k] = plan[k];
         d.fmt[k] = plan[k].format;
         d.n_sel[k] = (uint32_t)plan[k].sel.size();
+        d.pane[k] = std::move(plan[k]);
     }
     d.n_panes = n_panes;
     d.dirty = true;
@@ -495,8 +489,8 @@ int Receiver::display_set_pane(uint32_t pane, const pebblegpu_display_pane *p)
         if (int rc = check_auto_scale(disp_->scale_flags & disp_->scale_live, next.sh.max_db, next.min_db)) return rc;
     }
     next.cap_pitch = cur.cap_pitch;
-    next.d_tab = cur.d_tab;
-    cur = next;
+    next.d_tab = std::move(cur.d_tab);
+    cur = std::move(next);
     disp_->dirty = true;
     return 0;
 }

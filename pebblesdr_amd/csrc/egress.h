@@ -18,6 +18,7 @@
 #include <condition_variable>
 #include <mutex>
 #include "common.h"
+#include "devmem.h"
 
 namespace pg {
 
@@ -64,7 +65,8 @@ struct EgressRow {
 };
 
 struct EgressSlot {
-    void *h = nullptr, *d = nullptr;   // pinned host buffer and its device staging twin
+    PinnedBuf<unsigned char> h;        // pinned host buffer ...
+    DevBuf<unsigned char> d;           // ... and its device staging twin
     hipEvent_t packed = nullptr;       // behind the packing kernel, on the call's stream (no timing)
     hipEvent_t copied = nullptr;       // behind the copy, on the copy stream (no timing)
     uint64_t call = 0, samples = 0, pitch_bytes = 0;

@@ -218,8 +218,8 @@ int EgressRing::open_ring(uint32_t slots, uint32_t n_rows, uint32_t bps, uint64_
     for (uint32_t i = 0; i < n_slots; i++) {
         EgressSlot &g = slot[i];
         g = EgressSlot{};
-        PG_HIP(hipHostMalloc(&g.h, slot_bytes, hipHostMallocDefault));
-        PG_HIP(hipMalloc(&g.d, slot_bytes));
+        PG_TRY(g.h.alloc(slot_bytes));
+        PG_TRY(g.d.alloc(slot_bytes));
         PG_HIP(hipEventCreateWithFlags(&g.packed, hipEventDisableTiming));
         PG_HIP(hipEventCreateWithFlags(&g.copied, hipEventDisableTiming));
     }
@@ -233,8 +233,6 @@ void EgressRing::release()
 {
     if (copy_stream) (void)hipStreamSynchronize(copy_stream);
     for (EgressSlot &g : slot) {
-        if (g.h) (void)hipHostFree(g.h);
-        if (g.d) (void)hipFree(g.d);
         if (g.packed) (void)hipEventDestroy(g.packed);
         if (g.copied) (void)hipEventDestroy(g.copied);
         g = EgressSlot{};
@@ -365,7 +363,7 @@ int Receiver::audio_out_open(int format, const uint32_t *channels, uint32_t n_ch
     if (aout_.open) return fail(PEBBLEGPU_E_INVALID, "the audio ring is already open");
     PG_HIP(hipSetDevice(device));
     const uint64_t max_n = audio_rate ? (uint64_t)rs_pitch : (uint64_t)audio.cap;
-    if (!d_aout_tab_) PG_HIP(hipMalloc((void **)&d_aout_tab_, sizeof(EgressRow) * C));
+    if (!d_aout_tab_) PG_TRY(d_aout_tab_.alloc(C));
     std::lock_guard<std::mutex> lk(aout_.mu);
     if (int rc = aout_.open_ring(n_slots, (uint32_t)sel.size(), kAudioBytes[format], max_n, (uint32_t)format)) {
         aout_.release();

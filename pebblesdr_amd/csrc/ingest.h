@@ -3,11 +3,13 @@
 // one while the call that reads the other's device twin is still queued.  Shared by Receiver and the stream bank (cores.hip).
 #pragma once
 #include "common.h"
+#include "devmem.h"
 
 namespace pg {
 
 struct IngestSlot {
-    void *h = nullptr, *d = nullptr;      // pinned host buffer and its device twin
+    PinnedBuf<unsigned char> h;           // pinned host buffer ...
+    DevBuf<unsigned char> d;              // ... and its device twin
     size_t cap = 0, submitted = 0;
     hipEvent_t uploaded = nullptr, done_main = nullptr, done_chain = nullptr;
     bool in_flight = false;               // a call that reads the device twin has been queued and not waited for

@@ -277,7 +277,7 @@ __host__ __device__ inline uint32_t waterfall_color(int32_t v) { return waterfal
 struct DisplayPack {
     int format = 0;                  // pebblegpu_display_format
     uint32_t n_streams = 0;          // selected streams: rows of d_tab
-    uint32_t *d_tab = nullptr;       // d_tab[r] = the stream of block row r
+    uint32_t *d_tab = nullptr;       // a view of the owner's table: d_tab[r] = the stream of block row r
     uint32_t row_elems = 0;          // bins (DB_F32) or x_pixels
     uint64_t row_pitch_bytes = 0;    // row_elems * 4 rounded up to 16
     int group = 1;                   // the lane group run_screen_map picks for geom

@@ -425,17 +425,10 @@ int TestBenchCore::init(double sample_rate, uint32_t streams)
 
 void TestBenchCore::release()
 {
-    for (int i = 0; i < 2; i++) {
-        if (d_legs[i]) (void)hipFree(d_legs[i]);
-        if (h_legs[i]) (void)hipHostFree(h_legs[i]);
-        if (h_done[i]) (void)hipEventDestroy(h_done[i]);
-        if (d_morse[i]) (void)hipFree(d_morse[i]);
-        if (h_morse[i]) (void)hipHostFree(h_morse[i]);
-        d_legs[i] = nullptr; h_legs[i] = nullptr; h_done[i] = nullptr;
-        d_morse[i] = nullptr; h_morse[i] = nullptr;
+    for (hipEvent_t &e : h_done) {  // (the tables go with the object)
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
     }
-    leg_cap = 0;
-    morse_cap = 0;
 }
 
 // TestBench::reset(): the sweep restarts at the start frequency with phase 0 and pulse timer 0, the noise counter at 0
@@ -559,11 +552,9 @@ int TestBenchCore::run(hipStream_t s, const float2 *in, long long in_pitch, floa
             if (int rc = ensure_events()) return rc;
             for (int i = 0; i < 2; i++) {
                 PG_HIP(hipEventSynchronize(h_done[i]));
-                if (d_legs[i]) PG_HIP(hipFree(d_legs[i]));
-                if (h_legs[i]) PG_HIP(hipHostFree(h_legs[i]));
-                d_legs[i] = nullptr; h_legs[i] = nullptr;
-                PG_HIP(hipMalloc((void **)&d_legs[i], sizeof(SweepLeg) * cap));
-                PG_HIP(hipHostMalloc((void **)&h_legs[i], sizeof(SweepLeg) * cap));
+                leg_cap = 0;
+                PG_TRY(d_legs[i].alloc(cap));
+                PG_TRY(h_legs[i].alloc(cap));
             }
             leg_cap = cap;
             used[0] = used[1] = false;
@@ -576,12 +567,9 @@ int TestBenchCore::run(hipStream_t s, const float2 *in, long long in_pitch, floa
         if (int rc = ensure_events()) return rc;
         for (int i = 0; i < 2; i++) {
             PG_HIP(hipEventSynchronize(h_done[i]));
-            if (d_morse[i]) PG_HIP(hipFree(d_morse[i]));
-            if (h_morse[i]) PG_HIP(hipHostFree(h_morse[i]));
-            d_morse[i] = nullptr; h_morse[i] = nullptr;
             morse_cap = 0;
-            PG_HIP(hipMalloc((void **)&d_morse[i], cap));
-            PG_HIP(hipHostMalloc((void **)&h_morse[i], cap));
+            PG_TRY(d_morse[i].alloc(cap));
+            PG_TRY(h_morse[i].alloc(cap));
         }
         morse_cap = cap;
         used[0] = used[1] = false;
@@ -593,7 +581,7 @@ int TestBenchCore::run(hipStream_t s, const float2 *in, long long in_pitch, floa
         p.n_legs = (int)legs_.size();
     }
     if (morse_on()) {
-        MorseStationDev *hd = reinterpret_cast<MorseStationDev *>(h_morse[slot]);
+        MorseStationDev *hd = reinterpret_cast<MorseStationDev *>(h_morse[slot].get());
         for (size_t i = 0; i < stations.size(); i++) hd[i] = stations[i].dev;
         if (n_marks) memcpy(h_morse[slot] + sizeof(MorseStationDev) * stations.size(), marks_.data(), sizeof(long long) * n_marks);
         PG_HIP(hipMemcpyAsync(d_morse[slot], h_morse[slot], morse_bytes, hipMemcpyHostToDevice, s));
@@ -610,15 +598,15 @@ int TestBenchCore::run(hipStream_t s, const float2 *in, long long in_pitch, floa
         const long long runs = (n + kMorseRun - 1) / kMorseRun;
         long long blocks = (runs + 255) / 256;
         if (blocks > 256 * 8) blocks = 256 * 8;
-        launch(k_morsegen, dim3((unsigned)blocks), dim3(256), s, src, out, in_pitch, out_pitch, n, (int)streams, vec, p, (const SweepLeg *)(sweep_on ? d_legs[slot] : nullptr),
-               (const MorseStationDev *)d_morse[slot], (const long long *)(d_morse[slot] + sizeof(MorseStationDev) * stations.size()), (int)stations.size());
+        launch(k_morsegen, dim3((unsigned)blocks), dim3(256), s, src, out, in_pitch, out_pitch, n, (int)streams, vec, p, (const SweepLeg *)(sweep_on ? d_legs[slot].get() : nullptr),
+               (const MorseStationDev *)d_morse[slot].get(), (const long long *)(d_morse[slot] + sizeof(MorseStationDev) * stations.size()), (int)stations.size());
         PG_HIP(hipGetLastError());
         for (MorseStationHost &st : stations) st.pos = (st.pos + (unsigned long long)n) % st.plan.period;
     } else {
         const long long items = vec ? (n + 1) / 2 : n;
         long long blocks = (items + 255) / 256;
         if (blocks > 256 * 8) blocks = 256 * 8;
-        launch(k_testbench, dim3((unsigned)blocks, streams), dim3(256), s, src, out, in_pitch, out_pitch, n, vec, p, (const SweepLeg *)(sweep_on ? d_legs[slot] : nullptr));
+        launch(k_testbench, dim3((unsigned)blocks, streams), dim3(256), s, src, out, in_pitch, out_pitch, n, vec, p, (const SweepLeg *)(sweep_on ? d_legs[slot].get() : nullptr));
         PG_HIP(hipGetLastError());
     }
     n_abs += (unsigned long long)n;
@@ -628,17 +616,15 @@ int TestBenchCore::run(hipStream_t s, const float2 *in, long long in_pitch, floa
 int TestBenchCore::draws(hipStream_t s, uint32_t stream, uint64_t first, uint32_t n, uint32_t *r, uint8_t *attempt)
 {
     if (!n) return 0;
-    unsigned *d_r = nullptr;
-    unsigned char *d_a = nullptr;
-    PG_HIP(hipMalloc((void **)&d_r, sizeof(unsigned) * 2 * (size_t)n));
-    if (hipMalloc((void **)&d_a, n) != hipSuccess) { (void)hipFree(d_r); return fail(PEBBLEGPU_E_HIP, "hipMalloc failed"); }
+    DevBuf<unsigned> d_r;
+    DevBuf<unsigned char> d_a;
+    PG_TRY(d_r.alloc(2 * (size_t)n));
+    PG_TRY(d_a.alloc(n));
     launch(k_testbench_draws, dim3((n + 255) / 256), dim3(256), s, (unsigned long long)seed, stream, (unsigned long long)first, (int)n, d_r, d_a);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipMemcpy(r, d_r, sizeof(unsigned) * 2 * (size_t)n, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(attempt, d_a, n, hipMemcpyDeviceToHost);
-    (void)hipFree(d_r);
-    (void)hipFree(d_a);
     if (e != hipSuccess) return fail(PEBBLEGPU_E_HIP, "noise draws: %s", hipGetErrorString(e));
     return 0;
 }

@@ -66,29 +66,26 @@ int MorseCore::init(uint32_t channels, uint32_t demod_rate, long long max_n, boo
         if (st.ntaps < 1 || st.ntaps > kMaxTaps) return fail(PEBBLEGPU_E_UNSUPPORTED, "modem stage of %d taps", st.ntaps);
         std::vector<float> h(kMaxTaps, 0.f);
         for (int p = 0; p < st.ntaps; p++) h[p] = (float)design::halfband_taps(st.design)[p];
-        float *t = nullptr;
-        PG_HIP(hipMalloc((void **)&t, sizeof(float) * kMaxTaps));
-        d_taps.push_back(t);
-        PG_HIP(hipMemcpy(t, h.data(), sizeof(float) * kMaxTaps, hipMemcpyHostToDevice));
-        float2 *hb = nullptr;
-        PG_HIP(hipMalloc((void **)&hb, sizeof(float2) * kMaxTaps * C));
-        d_hist.push_back(hb);
-        PG_HIP(hipMemset(hb, 0, sizeof(float2) * kMaxTaps * C));
+        DevBuf<float> t;
+        PG_TRY(t.upload(h.data(), kMaxTaps));
+        d_taps.push_back(std::move(t));
+        DevBuf<float2> hb;
+        PG_TRY(hb.alloc_zero((size_t)kMaxTaps * C));
+        d_hist.push_back(std::move(hb));
         len /= st.stride;
         const long long pitch = (len + 1) & ~1LL;
-        float2 *o = nullptr;
-        PG_HIP(hipMalloc((void **)&o, sizeof(float2) * (size_t)pitch * C));
-        d_out.push_back(o);
+        DevBuf<float2> o;
+        PG_TRY(o.alloc((size_t)pitch * C));
+        d_out.push_back(std::move(o));
         out_pitch.push_back(pitch);
     }
     rpitch = len / pp.N + 2;
     log_cap = (int)std::max<long long>(1024, 2 * rpitch);
-    PG_HIP(hipMalloc((void **)&d_power, sizeof(double) * (size_t)rpitch * C));
-    if (keep_tone) PG_HIP(hipMalloc((void **)&d_tone, (size_t)rpitch * C));
-    PG_HIP(hipMalloc((void **)&d_state, sizeof(MorseState) * C));
-    PG_HIP(hipMemset(d_state, 0, sizeof(MorseState) * C));
-    PG_HIP(hipMalloc((void **)&d_log, sizeof(MorseEvent) * (size_t)log_cap * C));
-    PG_HIP(hipMalloc((void **)&d_list, sizeof(int) * C));
+    PG_TRY(d_power.alloc((size_t)rpitch * C));
+    if (keep_tone) PG_TRY(d_tone.alloc((size_t)rpitch * C));
+    PG_TRY(d_state.alloc_zero(C));
+    PG_TRY(d_log.alloc((size_t)log_cap * C));
+    PG_TRY(d_list.alloc(C));
     PG_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
     on.assign(C, 0);
     tune_only.assign(C, 0);
@@ -99,13 +96,8 @@ int MorseCore::init(uint32_t channels, uint32_t demod_rate, long long max_n, boo
 
 void MorseCore::release()
 {
-    for (float *t : d_taps) if (t) (void)hipFree(t);
-    for (float2 *b : d_hist) if (b) (void)hipFree(b);
-    for (float2 *b : d_out) if (b) (void)hipFree(b);
     d_taps.clear(); d_hist.clear(); d_out.clear(); out_pitch.clear();
-    void *p[] = {d_power, d_tone, d_state, d_log, d_list};
-    for (void *q : p) if (q) (void)hipFree(q);
-    d_power = nullptr; d_tone = nullptr; d_state = nullptr; d_log = nullptr; d_list = nullptr;
+    d_power.release(); d_tone.release(); d_state.release(); d_log.release(); d_list.release();
     if (done) (void)hipEventDestroy(done);
     done = nullptr;
     C = 0;
@@ -160,7 +152,7 @@ int MorseCore::enable(uint32_t ch, bool en, int mode)
         const MorseState s = fresh_state(wpm[ch]);
         PG_HIP(hipMemcpy(d_state + ch, &s, sizeof(s), hipMemcpyHostToDevice));
         float2 z[kMaxTaps] = {};
-        for (float2 *hb : d_hist) PG_HIP(hipMemcpy(hb + (size_t)ch * kMaxTaps, z, sizeof(z), hipMemcpyHostToDevice));
+        for (const DevBuf<float2> &hb : d_hist) PG_HIP(hipMemcpy(hb + (size_t)ch * kMaxTaps, z, sizeof(z), hipMemcpyHostToDevice));
         if (!on[ch]) host[ch] = Host();
         host[ch].seen = 0;  // the new decoder's log count starts at 0
     }
@@ -275,7 +267,7 @@ struct pebblegpu_morse {
     hipStream_t stream = nullptr;
     uint32_t count = 0;
     pg::MorseCore core;
-    float2 *d_in = nullptr;
+    pg::DevBuf<float2> d_in;
     std::vector<float> hf;
     std::vector<pg::MorseEvent> carried;  // events of the decoder a setSampleRate replaced, not read yet (handed out first)
     bool keep = false;                // pebblegpu_morse_keep_results: collect the parity read-out
@@ -294,14 +286,13 @@ static int morse_open(pebblegpu_morse *m, uint32_t sample_rate, uint32_t sample_
         if (rc) return rc;
     }
     m->core.release();
-    if (m->d_in) (void)hipFree(m->d_in);
-    m->d_in = nullptr;
+    m->d_in.release();
     m->count = sample_count;
     m->pw.clear();
     m->tone.clear();
     if (int rc = m->core.init(1, sample_rate, sample_count, true)) return rc;
     if (int rc = m->core.check(sample_count)) return rc;
-    PG_HIP(hipMalloc((void **)&m->d_in, sizeof(float2) * sample_count));
+    PG_TRY(m->d_in.alloc(sample_count));
     if (wpm >= 0) m->core.wpm[0] = wpm;
     return m->core.enable(0, true, PEBBLEGPU_DM_CWL);
 }
@@ -314,7 +305,6 @@ int pebblegpu_morse_destroy(pebblegpu_morse *m)
     (void)hipSetDevice(m->device);
     if (m->stream) { (void)hipStreamSynchronize(m->stream); (void)hipStreamDestroy(m->stream); }
     m->core.release();
-    if (m->d_in) (void)hipFree(m->d_in);
     delete m;
     return 0;
 }

@@ -26,7 +26,7 @@ struct Job {
 };
 
 struct HostSlot {
-    void *h = nullptr;       // pinned, portable: every device reads it
+    pg::PortableBuf<unsigned char> h;  // pinned, portable: every device reads it
     uint64_t cap = 0;
     uint64_t submitted = 0;  // bytes of the last submit (0: nothing to process)
     bool in_flight = false;  // a process_ingested call has been queued on it and the slot has not been acquired since
@@ -79,7 +79,7 @@ int pebblegpu_multibank::run_job(uint32_t g, const Job &j)
         const HostSlot &s = slot[j.slot];
         if (shared) return rx.ingest_upload(j.slot, s.h, j.n);
         const uint64_t row = j.n / cfg.n_channels;
-        return rx.ingest_upload(j.slot, (const char *)s.h + row * first[g], row * count[g]);
+        return rx.ingest_upload(j.slot, (const char *)s.h.get() + row * first[g], row * count[g]);
     }
     case JOB_PROCESS_UPLOADED: return rx.process_uploaded(j.slot, j.fmt, j.order, j.gain, j.n);
     case JOB_SYNC: return rx.sync();
@@ -239,9 +239,7 @@ int pebblegpu_multibank_destroy(pebblegpu_multibank *mb)
     (void)mb->post(j);  // every shard's queued work first,
     mb->stop_workers();  // then the workers,
     for (uint32_t g = 0; g < mb->G; g++) (void)pebblegpu_receiver_destroy(mb->shard[g]);  // then the shards (and their device twins)
-    for (HostSlot &s : mb->slot)
-        if (s.h) (void)hipHostFree(s.h);
-    delete mb;
+    delete mb;  // (and the pinned slots)
     return 0;
 }
 
@@ -319,10 +317,8 @@ int pebblegpu_multibank_ingest_acquire(pebblegpu_multibank *mb, uint32_t slot, u
     s.submitted = 0;
     if (s.cap < bytes) {
         PG_HIP(hipSetDevice(mb->device[0]));
-        if (s.h) (void)hipHostFree(s.h);
-        s.h = nullptr;
         s.cap = 0;
-        PG_HIP(hipHostMalloc(&s.h, bytes, hipHostMallocPortable));  // portable: pinned for every device, not only the current one
+        PG_TRY(s.h.alloc(bytes));
         s.cap = bytes;
     }
     *host_ptr = s.h;

@@ -1,5 +1,6 @@
 // params.h -- plain structs shared by the host objects and the kernels (passed by value or uploaded).
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace pg {
@@ -159,6 +160,27 @@ struct RawSrc {
     float scale;
     int pad_;
 };
+
+// The raw sample format as a compile-time constant: f(std::integral_constant<int, F>) for the runtime fmt, so that one generic lambda
+// picks a kernel's instance per format (0..4: pebblegpu_iq_format; anything else takes 4's place).  with_sample_fmt also knows -1,
+// "the samples are float2 already" (no RawSrc).
+template <class Fn>
+inline void with_raw_fmt(int fmt, Fn &&f)
+{
+    switch (fmt) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+template <class Fn>
+inline void with_sample_fmt(const RawSrc *raw, Fn &&f)
+{
+    if (!raw) f(std::integral_constant<int, -1>{});
+    else with_raw_fmt(raw->fmt, f);
+}
 
 // the format's constant folded into the gain (deviceinterfacebase.cpp:651,689,729; wavfile.cpp:299-300), rounded once to float
 inline float raw_scale(int fmt, double gain)

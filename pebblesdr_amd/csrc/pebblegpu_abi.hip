@@ -80,6 +80,13 @@ int pebblegpu_probe_copy_gbps(int device, int lane_bytes, size_t bytes, int iter
     return pg::probe_copy(lane_bytes, bytes & ~(size_t)4095, iters, gbps);
 }
 
+int pebblegpu_live_bytes(uint64_t *device, uint64_t *pinned)
+{
+    if (device) *device = pg::g_live_device.load();
+    if (pinned) *pinned = pg::g_live_pinned.load();
+    return 0;
+}
+
 int pebblegpu_normalize_iq(int device, int format, int iq_order, double gain, const void *d_src, uint64_t n_samples, void *d_dst)
 {
     if (!d_src || !d_dst || format < 0 || format > PEBBLEGPU_IQ_WAV16 || iq_order < 0 || iq_order > 3 || n_samples == 0)

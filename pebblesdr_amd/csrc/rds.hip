@@ -8,13 +8,6 @@ namespace pg {
 
 static long long cdiv_ll(long long a, long long b) { return (a + b - 1) / b; }
 
-static int upload(double **d, const std::vector<double> &h)
-{
-    PG_HIP(hipMalloc((void **)d, sizeof(double) * h.size()));
-    PG_HIP(hipMemcpy(*d, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
-    return 0;
-}
-
 int RdsCore::init(uint32_t channels, double demod_rate, long long max_n)
 {
     C = channels;
@@ -40,45 +33,29 @@ int RdsCore::init(uint32_t channels, double demod_rate, long long max_n)
             h.assign(des.lp.rbegin(), des.lp.rend());
         }
         if ((int)h.size() > kMaxTaps) return fail(PEBBLEGPU_E_UNSUPPORTED, "RDS stage of %zu taps", h.size());
-        double *t = nullptr;
-        if (int rc = upload(&t, h)) return rc;
-        d_taps.push_back(t);
+        DevBuf<double> t;
+        PG_TRY(t.upload(h.data(), h.size()));
+        d_taps.push_back(std::move(t));
         ntaps.push_back((int)h.size());
         newest.push_back(nw);
         HistBuf b;
         if (int rc = b.alloc((int)C, 2 * ((int)h.size() + 1), 2 * (len + 2))) return rc;  // rows of double2 in 8-byte units
-        st.push_back(b);
+        st.push_back(std::move(b));
         if (j < nst) len /= 2;
     }
     const long long out_cap = len + 2;
     if (int rc = mag.alloc((int)C, pp.mtaps + 2, out_cap)) return rc;
-    PG_HIP(hipMalloc((void **)&d_lp, sizeof(double2) * (size_t)out_cap * C));
-    PG_HIP(hipMalloc((void **)&d_data, sizeof(double) * (size_t)out_cap * C));
-    PG_HIP(hipMemset(d_data, 0, sizeof(double) * (size_t)out_cap * C));
-    PG_HIP(hipMalloc((void **)&d_state, sizeof(RdsState) * C));
-    PG_HIP(hipMemset(d_state, 0, sizeof(RdsState) * C));  // initRds, :524-537 (and m_RdsLastData, which the reference never sets)
-    PG_HIP(hipMalloc((void **)&d_log, sizeof(RdsEvent) * (size_t)pp.log_cap * C));
-    PG_HIP(hipMemset(d_log, 0, sizeof(RdsEvent) * (size_t)pp.log_cap * C));
+    PG_TRY(d_lp.alloc((size_t)out_cap * C));
+    PG_TRY(d_data.alloc_zero((size_t)out_cap * C));
+    PG_TRY(d_state.alloc_zero(C));  // initRds, :524-537 (and m_RdsLastData, which the reference never sets)
+    PG_TRY(d_log.alloc_zero((size_t)pp.log_cap * C));
     std::vector<double> amp(kRdsAmpTab);
     design::oscillator_amplitudes(amp.data(), kRdsAmpTab);
-    if (int rc = upload(&d_amp, amp)) return rc;
-    if (int rc = upload(&d_matched, des.matched)) return rc;
+    PG_TRY(d_amp.upload(amp.data(), amp.size()));
+    PG_TRY(d_matched.upload(des.matched.data(), des.matched.size()));
     host.assign(C, Host());
     on = true;
     return 0;
-}
-
-void RdsCore::release()
-{
-    raw.release(); mag.release();
-    for (auto &b : st) b.release();
-    st.clear();
-    void *p[] = {d_lp, d_data, d_state, d_log, d_amp, d_matched, d_lptaps};
-    for (void *q : p) if (q) (void)hipFree(q);
-    for (double *t : d_taps) if (t) (void)hipFree(t);
-    d_taps.clear(); ntaps.clear(); newest.clear();
-    d_lp = nullptr; d_data = nullptr; d_state = nullptr; d_log = nullptr; d_amp = d_matched = d_lptaps = nullptr;
-    on = false;
 }
 
 int RdsCore::check(long long n, int block) const

@@ -18,6 +18,7 @@
 #include "../../include/pebblegpu.h"
 #include "call_route.h"
 #include "common.h"
+#include "devmem.h"
 #include "design.h"
 #include "egress.h"
 #include "ingest.h"
@@ -27,21 +28,22 @@
 namespace pg {
 
 // [channel][hist | data] complex buffer; data(c) points at the first new sample, data(c)[-hist..-1] is history.
+// Move-only: it owns `base`.
 struct HistBuf {
-    float2 *base = nullptr;
+    DevBuf<float2> base;
     long long pitch = 0;  // samples per channel row (hist + capacity, even)
     int hist = 0;
     long long cap = 0;
     int chans = 0;
     float2 *data(int c = 0) const { return base + (long long)c * pitch + hist; }
     int alloc(int channels, int hist_len, long long capacity);
-    void release();
+    void release() { base.release(); }
 };
 
 void fill_scan_section(ScanSection &s, int type, const double *c);
-int make_twiddles(int n, float2 **d_tw);
-int make_twiddles_t128(float2 **d_tw);
-int make_twiddles_t128q(float2 **d_tw);  // four tables, the pruned transform's per-work-item factor folded in (k_spectrum_t128)
+int make_twiddles(int n, DevBuf<float2> &tw);
+int make_twiddles_t128(DevBuf<float2> &tw);
+int make_twiddles_t128q(DevBuf<float2> &tw);  // four tables, the pruned transform's per-work-item factor folded in (k_spectrum_t128)
 int run_save_tails(hipStream_t s, const std::vector<TailJob> &jobs, uint32_t channels, const OscAdvance *oa = nullptr);
 // the rows of the channels in d_list (device memory, n_list entries) only: for buffers that only those channels' kernels fill
 int run_save_tails_listed(hipStream_t s, const std::vector<TailJob> &jobs, const int *d_list, int n_list);
@@ -78,11 +80,11 @@ struct OscBank {
     struct Dyn { double phase0; uint32_t n0, mix_on; };
     OscDynInline inline_dyn = {};             // filled by upload() when allow_inline and C <= kOscInline
     bool allow_inline = false;                // set by owners whose kernels take OscDynInline
-    Dyn *h_dyn[2] = {nullptr, nullptr};       // pinned staging of the per-call fields, ping-pong: no host sync per call
+    PinnedBuf<Dyn> h_dyn[2];                  // pinned staging of the per-call fields, ping-pong: no host sync per call
     hipEvent_t h_done[2] = {nullptr, nullptr};
     int h_idx = 0;
-    ChanOsc *d_osc = nullptr;
-    float *d_amp = nullptr;
+    DevBuf<ChanOsc> d_osc;
+    DevBuf<float> d_amp;
     float a_inf = 0;
     // Banks too large for kernel-argument transport (C > kOscInline): with device_advance set by the owner, the per-call fields
     // are advanced ON the device at the end of each call (k_save_tails, OscAdvance) instead of being copied up before the next;
@@ -90,7 +92,7 @@ struct OscBank {
     // length, rebuilt (long double, as advance() computes) when the length or a frequency changes.
     bool device_advance = false;
     bool dev_dyn_valid = false;    // the device blocks hold the per-call fields of the coming call
-    double *d_adv = nullptr;
+    DevBuf<double> d_adv;
     uint64_t adv_n = 0;
     bool adv_stale = true;
     uint64_t dyn_epoch = 0;        // counts host writes of the device blocks' per-call fields (a retune's block, the per-call upload)
@@ -145,20 +147,20 @@ struct DecimCore {
     // consumer's row into the head-room (ovl_pending).
     struct MixTail { const float2 *tail = nullptr; long long tail_pitch = 0; float2 *tail_out = nullptr; };
     MixTail mix_tail;                              // of the last run() with DecimCall::mix_in_consumer
-    float2 *d_ovl[2] = {nullptr, nullptr};         // [C][ovl_len] the consumer's overlap rows, written by alternate calls
+    DevBuf<float2> d_ovl[2];                       // [C][ovl_len] the consumer's overlap rows, written by alternate calls
     int ovl_len = 0, ovl_parity = 0;
     bool ovl_pending = false;                      // d_ovl[ovl_parity] is newer than buf0's head-room
     bool last_in_consumer = false;                 // the last run() left the mixing to the consumer: buf0 was not written
     int enable_mix_in_consumer();                  // after init(), zero-stage only: allocates the rows (last_hist samples each)
-    bool mix_in_consumer_ready() const { return d_ovl[0] != nullptr; }
+    bool mix_in_consumer_ready() const { return d_ovl[0].get() != nullptr; }
     FrontTaps bank_taps;
     // the whole decimator in one kernel (k_mix_dec_fused): a >= 16-channel bank off one shared stream whose chain is hb11 x S
     // followed by hb15, hb19, hb31; calls inside an oscillator transient take the two-kernel route (both keep each other's history)
     bool fused_all = false, last_fused = false;
     struct FusedDecParams *fused_p = nullptr;   // host copy of the kernel's parameter block
-    float2 *d_xhist[2] = {nullptr, nullptr};    // [16] raw input tail of the previous call, ping-pong with hist_parity
-    float2 *d_y0stage = nullptr;                // [C][HY] the call's last first-stage outputs, copied into buf0's head-room by the tail refresh (k_mix_dec_fused: = d_y0stage2[0])
-    float2 *d_y0stage2[2] = {nullptr, nullptr}; // k_mix_dec_mfma stages them alternately and reads the previous launch's directly (y0_cur: the one written last)
+    DevBuf<float2> d_xhist[2];                  // [16] raw input tail of the previous call, ping-pong with hist_parity
+    float2 *d_y0stage = nullptr;                // a view of d_y0stage2[.]: [C][HY] the call's last first-stage outputs, copied into buf0's head-room by the tail refresh (k_mix_dec_fused: = d_y0stage2[0])
+    DevBuf<float2> d_y0stage2[2];               // k_mix_dec_mfma stages them alternately and reads the previous launch's directly (y0_cur: the one written last)
     int y0_cur = 0;
     int fused_hy = 0;
     // the same chain with its first stage on the matrix pipe, one wave per (32 channels, two chunks): k_mix_dec_mfma (kernels_bank_dec.h),
@@ -167,32 +169,31 @@ struct DecimCore {
     int bank_nstate = 0, bank_minw = 2;          // running sums per channel of the chain's instance; waves per SIMD it admits
     int run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, bool had_state, const OscAdvance *oa, hipEvent_t done_event, DecimDone *done);
     int xh_depth = 16;                           // samples of raw-input tail kept in d_xhist
-    float2 *d_bank_state[2] = {nullptr, nullptr};  // [C][38] the halfbands' running sums where the last k_mix_dec_mfma call ended (ping-pong)
+    DevBuf<float2> d_bank_state[2];                // [C][38] the halfbands' running sums where the last k_mix_dec_mfma call ended (ping-pong)
     int bank_state_parity = 0;
     bool bank_state_valid = false;               // the previous call took that route (else the next one warms up from the first-stage history)
     int wide_taps = 0, wide_stride = 1;
-    float *d_wide_taps = nullptr;
+    DevBuf<float> d_wide_taps;
     HistBuf buf1;
     long long len1 = 0;
     long long len0 = 0, len_out = 0; // lengths produced by the last run
     const char *front_name = "";     // the kernel the last run() used for the mixer + first stage (bench / profiling labels)
     const char *rest_name = "";      // ... and for the remaining stages
-    float2 *d_hist_mixed[2] = {nullptr, nullptr};  // [C][kMaxTaps]: mixed-sample history of stage 0 (read one, write the other)
+    DevBuf<float2> d_hist_mixed[2];                // [C][kMaxTaps]: mixed-sample history of stage 0 (read one, write the other)
     // One channel through hb11 x 8, hb15, hb23, hb47 beside an 8192-bin display transform: k_spectrum_t128<.., DEC> computes the whole
     // decimator from the frames it holds in LDS (DecFuse, kernels_spectrum.h).  Its look-back is the previous call's last frame, kept
     // WINDOWED (the transform's workgroups park windowed frames): written by that kernel, or by k_window_tail behind a call that took
     // the general kernels, so either route can follow the other.
-    float2 *d_xtail_w[2] = {nullptr, nullptr};     // [2048] ping-pong
+    DevBuf<float2> d_xtail_w[2];                   // [2048] ping-pong
     int xtail_parity = 0;
-    const float *fuse_window = nullptr;            // the display transform's window (set by the owner; nullptr: never fused)
-    float2 *d_c0tab = nullptr;                     // [7][256] first-stage taps over that window times the oscillator's step per tap (DecFuse::c0tab)
+    const float *fuse_window = nullptr;            // a view of the display transform's window, SpectrumCore::d_window (set by the owner; nullptr: never fused)
+    DevBuf<float2> d_c0tab;                        // [7][256] first-stage taps over that window times the oscillator's step per tap (DecFuse::c0tab)
     std::vector<float> h_r0;                       // ... the real part of it: h0[d] / w[n]
     std::vector<float2> h_c0;
     bool c0_valid = false;
     double c0_inc = 0;
     int c0_mix = 0;
-    float2 *d_ph_scratch = nullptr;                // DecFuse::ph_scratch
-    size_t ph_cap = 0;
+    DevBuf<float2> d_ph_scratch;                   // DecFuse::ph_scratch (grows)
     int set_fuse_window(const float *d_window, const std::vector<float> &w);  // the owner's display transform uses this window
     bool shape_for_spectrum() const;               // the chain is the one the kernel is built for
     bool fuse_shape() const { return shape_for_spectrum() && fuse_window; }  // ... and the owner's transform has handed over its window
@@ -205,8 +206,7 @@ struct DecimCore {
     int hist_parity = 0;
     // last_hist: head-room of the final buffer (what the consumer looks back at); last_gain: folded into the final stage
     Tuning tun;                              // the owner's switches (init)
-    unsigned long long *d_clk = nullptr;     // Tuning::bank_clk: the waves' clock counts of the last k_mix_dec_mfma launch
-    size_t clk_cap = 0;
+    DevBuf<unsigned long long> d_clk;        // Tuning::bank_clk: the waves' clock counts of the last k_mix_dec_mfma launch
     int report_clk(hipStream_t s, unsigned n_wg, long long L);  // waits for the launch, prints its clock counts on stderr
     int init(uint32_t channels, const design::Chain &c, long long max_in, int last_hist, float last_gain, const Tuning &t);
     void release();
@@ -217,7 +217,7 @@ struct DecimCore {
             hipEvent_t after_first = nullptr, const RawSrc *raw = nullptr, const OscAdvance *oa = nullptr, DecimCall call = DecimCall{}, DecimDone *done = nullptr);
     bool last_mfma = false;                 // the last run() was a k_mix_dec_mfma launch
     int flush_y0(hipStream_t s);
-    OscDyn *d_dyn[2] = {nullptr, nullptr};  // [C] the oscillators' per-call fields as k_mix_dec_mfma hands them from call to call (ping-pong)
+    DevBuf<OscDyn> d_dyn[2];                // [C] the oscillators' per-call fields as k_mix_dec_mfma hands them from call to call (ping-pong)
     int dyn_parity = 0;
     bool dyn_valid = false;                 // d_dyn[dyn_parity] holds this call's fields (the previous call was such a launch and nothing was uploaded since)
     uint64_t dyn_epoch_seen = 0;
@@ -234,7 +234,7 @@ struct DecimCore {
     HistBuf fin2, fin3;                      // fin: this call's; fin2: the next call's (its head-room filled by this call's consumer); fin3: a third, written by the call after that,
                                              // so that a call's decimator waits for the consumer of the call THREE back (long over) instead of two (often still running)
     int enable_double_out();                 // after init(); fails for a single-stage chain (its output is the first stage's buffer)
-    bool double_out() const { return fin2.base != nullptr; }
+    bool double_out() const { return fin2.base.get() != nullptr; }
     void tail_jobs_dec(std::vector<TailJob> &jobs) const;
     void tail_job_out(std::vector<TailJob> &jobs) const;
     const HistBuf &out() const { return casc.nst > 0 ? fin : buf0; }
@@ -244,11 +244,10 @@ struct DecimCore {
 // ---- CFastFIR ----
 struct FastFirCore {
     uint32_t C = 0, fft_n = 2048, taps = 1025;
-    float2 *d_H = nullptr, *d_tw = nullptr;
-    float2 *d_tw128 = nullptr;   // 2048-point case: table of the two-wave transform (fft_t128.h)
+    DevBuf<float2> d_H, d_tw;
+    DevBuf<float2> d_tw128;      // 2048-point case: table of the two-wave transform (fft_t128.h)
     Tuning tun;                  // the owner's switches (init)
     int init(uint32_t channels, uint32_t fft_size, uint32_t fir_size, const Tuning &t);
-    void release();
     long long block_len() const { return (long long)fft_n - (taps - 1); }
     // *ok = false (and H left alone) on the reference's "Filter Parameter error"
     int design(hipStream_t s, uint32_t ch, double lo, double hi, double offset, double rate, bool *ok);
@@ -274,13 +273,12 @@ struct AmCore {
     uint32_t C = 0;
     double rate = 0;
     HistBuf tmp;                    // DC-blocked magnitude, head-room for the audio FIR
-    float *d_taps = nullptr;        // [C][kMaxTaps]
-    int *d_ntaps = nullptr, *d_list = nullptr;
-    double *d_state = nullptr;      // [C][1][2][2]
+    DevBuf<float> d_taps;           // [C][kMaxTaps]
+    DevBuf<int> d_ntaps, d_list;
+    DevBuf<double> d_state;         // [C][1][2][2]
     ScanParams<1> scan;
     std::vector<int> list;
     int init(uint32_t channels, double demod_rate, long long max_n);
-    void release();
     int set_bandwidth(hipStream_t s, uint32_t ch, double bw);   // Demod_AM::setBandwidth, demod_am.cpp:17-21
     int set_list(hipStream_t s, const std::vector<int> &am_channels);
     // in/out rows may be the same buffer (the scan reads `in`, the FIR writes `out`)
@@ -298,12 +296,11 @@ struct PllCore {
     int mode = 0, ntaps = 0;        // 0 NFM, 1 SAM
     PllParams pp;
     HistBuf tmp;                    // PLL output, head-room for the CFir
-    float *d_taps_i = nullptr, *d_taps_q = nullptr;
-    PllState *d_state = nullptr;
-    int *d_list = nullptr;
+    DevBuf<float> d_taps_i, d_taps_q;
+    DevBuf<PllState> d_state;
+    DevBuf<int> d_list;
     std::vector<int> list;
     int init(uint32_t channels, double demod_rate, long long max_n, int which);
-    void release();
     int set_list(hipStream_t s, const std::vector<int> &channels);
     int run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate = Gate{nullptr, 0, 0});
 };
@@ -325,12 +322,12 @@ struct RdsCore {
     RdsParams pp{};
     HistBuf raw, mag;                // rows of double
     std::vector<HistBuf> st;         // rows of double2: st[j] the input of stage j, st[nst] the low-pass's input
-    double2 *d_lp = nullptr;         // [C][cap / D]
-    double *d_data = nullptr;        // [C][cap / D] m_RdsData of the last call
-    RdsState *d_state = nullptr;
-    RdsEvent *d_log = nullptr;       // [C][log_cap]
-    double *d_amp = nullptr, *d_matched = nullptr, *d_lptaps = nullptr;
-    std::vector<double *> d_taps;    // per stage, oldest sample first
+    DevBuf<double2> d_lp;            // [C][cap / D]
+    DevBuf<double> d_data;           // [C][cap / D] m_RdsData of the last call
+    DevBuf<RdsState> d_state;
+    DevBuf<RdsEvent> d_log;          // [C][log_cap]
+    DevBuf<double> d_amp, d_matched;
+    std::vector<DevBuf<double>> d_taps;  // per stage, oldest sample first
     std::vector<int> ntaps, newest;
     long long last_len = 0;
     struct Host {                    // m_RdsGroupQueue and its consumer
@@ -345,7 +342,6 @@ struct RdsCore {
     };
     std::vector<Host> host;
     int init(uint32_t channels, double demod_rate, long long max_n);
-    void release();
     // queues the branch for the listed channels; block: demodulator-rate samples per processDataStereo call of the reference
     int check(long long n, int block) const;   // the sizes run() accepts (the owner asks before it queues anything of the call)
     int run(hipStream_t s, const float2 *in, long long in_pitch, long long n, const double *d_hilb, const int *d_list, int n_list, int block);
@@ -362,14 +358,14 @@ struct MorseCore {
     MorseParams pp = {};
     long long cap_in = 0, rpitch = 0;          // input samples per call at most; results per channel row
     int log_cap = 0;                           // events per channel the device log holds
-    std::vector<float *> d_taps;               // per stage
-    std::vector<float2 *> d_hist, d_out;       // per stage: [C][kMaxTaps] the input's tail of the last call; [C][out_pitch] the output
+    std::vector<DevBuf<float>> d_taps;         // per stage
+    std::vector<DevBuf<float2>> d_hist, d_out; // per stage: [C][kMaxTaps] the input's tail of the last call; [C][out_pitch] the output
     std::vector<long long> out_pitch;
-    double *d_power = nullptr;                 // [C][rpitch] this call's Goertzel powers
-    unsigned char *d_tone = nullptr;           // [C][rpitch] ... and decisions (stand-alone step only)
-    MorseState *d_state = nullptr;             // [C]
-    MorseEvent *d_log = nullptr;               // [C][log_cap] ring
-    int *d_list = nullptr;                     // the channels the modem runs for (on, and not in dmNONE)
+    DevBuf<double> d_power;                    // [C][rpitch] this call's Goertzel powers
+    DevBuf<unsigned char> d_tone;              // [C][rpitch] ... and decisions (stand-alone step only)
+    DevBuf<MorseState> d_state;                // [C]
+    DevBuf<MorseEvent> d_log;                  // [C][log_cap] ring
+    DevBuf<int> d_list;                        // the channels the modem runs for (on, and not in dmNONE)
     std::vector<int> list;
     std::vector<unsigned char> on, tune_only;
     std::vector<int32_t> wpm;                  // where the next enable starts: m_wpmSpeedCurrent outlives setSampleRate (morse.h:223)
@@ -398,25 +394,25 @@ struct WfmCore {
     uint32_t C = 0;
     double rate = 0;
     HistBuf a, b, c;                // low-passed IQ (hist 1), discriminator (hist FIR), FIR out
-    float *d_taps = nullptr;
+    DevBuf<float> d_taps;
     int ntaps = 0;
     bool lp_on = false;
     ScanParams<1> lp;
     ScanParams<2> dn;
     int parity = 0;
-    double *d_lp_state[2] = {nullptr, nullptr}, *d_dn_state[2] = {nullptr, nullptr};
+    DevBuf<double> d_lp_state[2], d_dn_state[2];
     bool fused = false;             // single-kernel FIR-ised path (k_wfm_fir); else the multi-kernel sequential fallback
     int L4 = 0, Llp = 1;            // fused: combined audio response (padded to 16) and low-pass response lengths
-    float *d_h = nullptr;           // [L4 + 16]  (k_wfm_lmr_fir)
-    float *d_hm = nullptr;          // [wfm_mx_table_floats(L4)]: the same response in the order k_wfm_fir's matrix operand walks (wfm_fir_geom.h)
-    float *d_hlp = nullptr;         // [Llp]
-    float2 *d_xtail[2] = {nullptr, nullptr};  // [C][L4 + Llp] input history, ping-pong
-    const float2 *deferred_in = nullptr;      // set by run(): the history copy is left to tail_jobs()
+    DevBuf<float> d_h;              // [L4 + 16]  (k_wfm_lmr_fir)
+    DevBuf<float> d_hm;             // [wfm_mx_table_floats(L4)]: the same response in the order k_wfm_fir's matrix operand walks (wfm_fir_geom.h)
+    DevBuf<float> d_hlp;            // [Llp]
+    DevBuf<float2> d_xtail[2];                // [C][L4 + Llp] input history, ping-pong
+    const float2 *deferred_in = nullptr;      // a view of the caller's input rows, set by run(): the history copy is left to tail_jobs()
     long long deferred_pitch = 0;
     // dmFMS as the reference delivers it: processDataStereo's pilot PLL does not hold lock, so the block
     // copies the discriminator output to both channels -- processDataMono without its 75 kHz pre-filter (demod_wfm.cpp:255-293)
     std::vector<unsigned char> stereo;        // per channel: 1 = dmFMS
-    unsigned char *d_stereo = nullptr;        // device copy, uploaded by run() when dirty; null until a channel asks for it
+    DevBuf<unsigned char> d_stereo;           // device copy, uploaded by run() when dirty; null until a channel asks for it
     bool stereo_dirty = false;
     int set_stereo(uint32_t ch, bool on);
     // ... and before it drops out (at most the first blocks of a stream): k_wfm_pilot runs the discriminator, the Hilbert pair, the
@@ -424,9 +420,9 @@ struct WfmCore {
     // k_wfm_lmr_fir sends it through the audio response and adds / subtracts it.  Allocated when a channel first asks for dmFMS.
     HistBuf lm;                               // [C] rows, .x = lmr, head-room = the audio response's look-back
     long long lm_pending = 0;                 // head-room samples that may still be non-zero once no channel is in dmFMS (run() flushes them)
-    struct WfmPilotState *d_pilot = nullptr;  // [C]
-    double *d_hilb = nullptr;                 // [2][61]
-    int *d_stereo_list = nullptr;             // the dmFMS channels
+    DevBuf<struct WfmPilotState> d_pilot;     // [C]
+    DevBuf<double> d_hilb;                    // [2][61]
+    DevBuf<int> d_stereo_list;                // the dmFMS channels
     int n_stereo = 0;
     long long max_n_ = 0;
     int stereo_block = 2048;                  // samples per processDataStereo call in the reference (the owner's frame length)
@@ -438,7 +434,6 @@ struct WfmCore {
     int stereo_lock(hipStream_t s, uint32_t ch, int *lock, int *changed);
     Tuning tun;                               // the owner's switches (init)
     int init(uint32_t channels, double demod_rate, long long max_n, const Tuning &t);
-    void release();
     // more_tails / oa: the caller's other tail-refresh jobs and oscillator advance; when the single-kernel path runs it carries
     // them (and its own history copy) in extra workgroups of its launch and sets *carried -- the caller then skips its own
     // tail-refresh launch (one launch and ~5 us fewer on the call's critical path)
@@ -452,13 +447,12 @@ struct WfmCore {
 struct AgcCore {
     uint32_t C = 0;
     double rate = 0;
-    struct AgcState *d_state = nullptr;
-    int *d_list = nullptr;
+    DevBuf<struct AgcState> d_state;
+    DevBuf<int> d_list;
     std::vector<int> list;          // channels the kernel visits: every mode but OFF-with-unit-gain
     struct Host { int mode = 0, threshold = 1, use_hang = 0, thr = 0, decay = 0; double slope = 0, sample_rate = 100.0, manual = 1.0; bool dirty = false; };
     std::vector<Host> host;
     int init(uint32_t channels, double demod_rate);
-    void release();
     int set_mode(uint32_t ch, int mode, int threshold);      // AGC::setAgcMode, agc.cpp:53-82
     std::vector<char> muted;        // channels the owner keeps out of the list (dmNONE: the reference returns before the AGC)
     void set_muted(uint32_t ch, bool m) { if (muted.size() != C) muted.assign(C, 0); if ((muted[ch] != 0) != m) { muted[ch] = m; list_dirty = true; } }
@@ -475,16 +469,15 @@ struct ConditionCore {
     struct Host { int flags = 0; double gain = 1, phase = 0; };
     std::vector<Host> host;
     bool any = false, dirty = false;
-    float2 *d_buf = nullptr;          // [S][cap] conditioned copy of the input (allocated on first enable)
-    double *d_dc_state = nullptr;     // [S][1][2][2]
-    int *d_dc_list = nullptr;
+    DevBuf<float2> d_buf;             // [S][cap] conditioned copy of the input (allocated on first enable)
+    DevBuf<double> d_dc_state;        // [S][1][2][2]
+    DevBuf<int> d_dc_list;
     std::vector<int> dc_list;
-    double2 *d_iq = nullptr;          // [S] (gain, phase), gain < 0: off
-    struct NbState *d_nb = nullptr;   // [S]
+    DevBuf<double2> d_iq;             // [S] (gain, phase), gain < 0: off
+    DevBuf<struct NbState> d_nb;      // [S]
     ScanParams<1> dc;
     bool iq_any = false, nb_any = false;
     int init(uint32_t streams, uint32_t frame, double sample_rate, long long max_n);
-    void release();
     int set(uint32_t stream, int flags, double gain, double phase);
     int apply(hipStream_t s);
     // copies d_in to the internal buffer and runs the enabled steps on it; *out = what the rest of the call should read
@@ -492,14 +485,13 @@ struct ConditionCore {
 };
 struct AnfCore {
     uint32_t C = 0;
-    struct AnfState *d_state = nullptr;
-    int *d_list = nullptr;
+    DevBuf<struct AnfState> d_state;
+    DevBuf<int> d_list;
     std::vector<int> list;
     std::vector<char> on, muted;   // muted: dmNONE channels (the reference returns before the noise filter)
     bool dirty = false;
     void set_muted(uint32_t ch, bool m) { if (muted.size() != C) muted.assign(C, 0); if ((muted[ch] != 0) != m) { muted[ch] = m; dirty = true; } }
     int init(uint32_t channels);
-    void release();
     int set(uint32_t ch, bool enable);
     int apply(hipStream_t s);
     int run(hipStream_t s, float2 *buf, long long pitch, long long n, Gate gate = Gate{nullptr, 0, 0});
@@ -554,7 +546,8 @@ struct TestBenchCore {
     std::vector<MorseStationHost> stations;
     bool morse_mix = true;
     std::vector<long long> marks_;
-    unsigned char *d_morse[2] = {nullptr, nullptr}, *h_morse[2] = {nullptr, nullptr};  // the call's station table, ping-pong like the legs
+    DevBuf<unsigned char> d_morse[2];
+    PinnedBuf<unsigned char> h_morse[2];  // the call's station table, ping-pong like the legs
     size_t morse_cap = 0;
     bool morse_on() const { return !stations.empty(); }
     int set_morse(const pebblegpu_morse_station *st, uint32_t n, int mix);  // n == 0: off
@@ -568,7 +561,8 @@ struct TestBenchCore {
     double turns = 0, f_leg = 0, inc = 0, start = 0, stop = 0;
     bool up = true;
     std::vector<SweepLeg> legs_;
-    SweepLeg *d_legs[2] = {nullptr, nullptr}, *h_legs[2] = {nullptr, nullptr};  // the call's leg table, ping-pong (pinned staging: no host wait per call)
+    DevBuf<SweepLeg> d_legs[2];
+    PinnedBuf<SweepLeg> h_legs[2];  // the call's leg table, ping-pong (pinned staging: no host wait per call)
     hipEvent_t h_done[2] = {nullptr, nullptr};
     bool used[2] = {false, false};
     size_t leg_cap = 0;
@@ -588,9 +582,10 @@ struct TestBenchCore {
 struct ResampCore {
     uint32_t C = 0, nf = 0;
     double dt = 1.0, float_time = 0.0;     // Rate = input rate / output rate; m_FloatTime
-    float *d_sinc = nullptr;
-    float2 *d_hist[2] = {nullptr, nullptr};  // [C][28] last inputs of the previous call, ping-pong
-    struct ResampFrame *d_frames = nullptr, *h_frames[2] = {nullptr, nullptr};
+    DevBuf<float> d_sinc;
+    DevBuf<float2> d_hist[2];                // [C][28] last inputs of the previous call, ping-pong
+    DevBuf<struct ResampFrame> d_frames;
+    PinnedBuf<struct ResampFrame> h_frames[2];
     hipEvent_t h_done[2] = {nullptr, nullptr};
     int parity = 0, pin = 0;
     uint32_t max_frames = 0;
@@ -604,11 +599,11 @@ struct ResampCore {
 // ---- FFT::fftSpectrum ----
 struct SpectrumCore {
     uint32_t S = 0, nf = 2048, bins = 0;
-    float *d_prev[2] = {nullptr, nullptr};
-    float *d_window = nullptr;
-    float2 *d_btab = nullptr, *d_tw_nf = nullptr;  // btab: [bins/nf][32] wave-uniform pre-twiddle factors
-    float2 *d_btab128 = nullptr, *d_tw128 = nullptr;  // the same for the two-wave transform (fft_t128.h), 8192 bins
-    float2 *d_ftab = nullptr;         // [bins/nf][nf] window[n] * W_bins^{n q}: the one factor per point of k_spectrum_q128
+    DevBuf<float> d_prev[2];
+    DevBuf<float> d_window;
+    DevBuf<float2> d_btab, d_tw_nf;                // btab: [bins/nf][32] wave-uniform pre-twiddle factors
+    DevBuf<float2> d_btab128, d_tw128;                // the same for the two-wave transform (fft_t128.h), 8192 bins
+    DevBuf<float2> d_ftab;            // [bins/nf][nf] window[n] * W_bins^{n q}: the one factor per point of k_spectrum_q128
     std::vector<float> h_window;      // host copy of the window (the decimator's taps against windowed samples)
     bool last_fullc = false;          // the last run used k_spectrum_t128's register-held twiddles (nothing ran beside it)
     Tuning tun;                       // the owner's switches (init)
@@ -617,21 +612,20 @@ struct SpectrumCore {
     bool per_q = false;               // k_spectrum_q128 (one transform per 128-item workgroup) instead of the shared-frame kernels
     // 65536-sample frames / 65536 bins (four-step, kernels_spectrum.h): the [S][F][32][2048] intermediate
     bool big = false;
-    float2 *d_Y = nullptr;
-    size_t y_cap = 0;
+    DevBuf<float2> d_Y;               // (grows)
     float scale = 0;
     int parity = 0;
     // any other frame length, and frames shorter than samplesPerBuffer (un-windowed): k_spectrum_any
     bool any = false;                 // the frame length / bin count has none of the kernels above: every call takes the general kernel
     int any_M = 0, any_logM = 0, any_zp_log2 = 0;
-    float2 *d_twM = nullptr;          // W_M^k, k < M / 2
+    DevBuf<float2> d_twM;             // W_M^k, k < M / 2
     int run_any(hipStream_t s, const float2 *d_in, long long in_pitch, long long n_frames, float *d_out, int n_in, bool windowed);
     int init(uint32_t streams, uint32_t frame, uint32_t fft_size, const Tuning &t);
-    void release();
+    int size_Y(hipStream_t s, long long per_stream, long long *bs);  // the stream batch of a 65536-point call; grows d_Y to hold one
     int run(hipStream_t s, const float2 *d_in, long long in_pitch, long long n_frames, float *d_out, const RawSrc *raw = nullptr, const DecFuse *df = nullptr, bool nothing_beside = false);
     // the transform over a frame list (the update timer's selection, k_spectrum_list_*): rows compact, |X_prev| = the previous listed frame
-    float2 *d_list_ftab = nullptr, *d_list_tw128 = nullptr;  // k_spectrum_list_q128's tables (k_spectrum_q128's own where that kernel is the plan's)
-    bool list_owned = false;
+    const float2 *d_list_ftab = nullptr, *d_list_tw128 = nullptr;  // views: k_spectrum_list_q128's tables -- d_ftab / d_tw128 where k_spectrum_q128 is the plan's, else the two below
+    DevBuf<float2> own_list_ftab, own_list_tw128;
     int init_list();
     int run_list(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw = nullptr);
     int run_list_big(hipStream_t s, const float2 *d_in, long long in_pitch, const uint32_t *idx, long long n_sel, float *d_out, const RawSrc *raw);  // 65536 points
@@ -758,10 +752,10 @@ public:
     uint64_t last_audio_n = 0, last_spec_frames = 0;
     Timers tm;
     HistBuf audio;   // [C][k*nf]
-    float *d_spec = nullptr;
+    DevBuf<float> d_spec;
     // SignalSpectrum::zoomed (signalspectrum.cpp:89-113): the display transform of every decimated frame of every channel
     uint32_t zoom_bins = 0;
-    float *d_zoom = nullptr;          // [C][max_sf * superframe / (D * nf)][zoom_bins]
+    DevBuf<float> d_zoom;             // [C][max_sf * superframe / (D * nf)][zoom_bins]
     uint64_t last_zoom_frames = 0;
     // the update timer (set_spectrum_updates): -1 no gate; with a gate last_spec_frames / last_zoom_frames count the COMPUTED rows of
     // the last call (compact in d_spec / d_zoom) and sel_spec_ / sel_zoom_ say which frames they are
@@ -771,29 +765,29 @@ public:
     std::vector<uint32_t> sel_spec_, sel_zoom_;
     // what the S-meter and the squelch read between two updates (getUnprocessed(), receiver.cpp:891-897, 959-965): the latest computed
     // row per stream, carried across calls, and its S-meter per channel (refreshed with the channel's current band at every call)
-    float *d_spec_carry = nullptr;    // [S][bins]
-    float4 *d_sm_carry = nullptr;     // [C]
+    DevBuf<float> d_spec_carry;       // [S][bins]
+    DevBuf<float4> d_sm_carry;        // [C]
     bool have_carry_ = false;
     // SignalStrength::fdEstimate per frame (S-meter): enabled on request, needs the spectrum
     bool smeter_on = false;
-    float4 *d_smeter = nullptr;       // [C][max frames]
-    SmBins *d_sm_bins = nullptr;
+    DevBuf<float4> d_smeter;          // [C][max frames]
+    DevBuf<SmBins> d_sm_bins;
     long long smeter_pitch = 0;
     int enable_smeter(bool on);
     double squelch_db_ = -120.0;      // DB::minDb: the gate never closes (receiverwidget.cpp:82); the one-channel, one-super-frame shape
     // banks (or calls of several super-frames): a per-channel threshold, decided on the device per (channel, super-frame)
     std::vector<float> squelch_;      // per channel, -120 = never closes
     bool bank_gate_ = false, squelch_dirty_ = false;
-    float *d_squelch = nullptr;
-    unsigned char *d_gate = nullptr;  // [C][max_sf]
-    float4 *h_gate_ = nullptr;        // pinned: the S-meter value the gate reads back
+    DevBuf<float> d_squelch;
+    DevBuf<unsigned char> d_gate;     // [C][max_sf]
+    PinnedBuf<float4> h_gate_;        // pinned: the S-meter value the gate reads back
     uint64_t squelched_calls = 0;
     bool failed_ = false;             // a process call failed after it had started queueing work: the handle is refused from then on
     bool profile_detail = false;      // record the per-kernel events too (pebblegpu_receiver_set_profiling)
     uint32_t audio_rate = 0;          // 0: audio stays at the demod rate (the resampRate == 1 branch, receiver.cpp:1000-1003)
-    float2 *d_audio_rs = nullptr;     // [C][rs_pitch] resampled audio
+    DevBuf<float2> d_audio_rs;        // [C][rs_pitch] resampled audio
     long long rs_pitch = 0;
-    const float2 *audio_ptr() const { return audio_rate ? d_audio_rs : audio.data(0); }
+    const float2 *audio_ptr() const { return audio_rate ? d_audio_rs.get() : audio.data(0); }
     long long audio_pitch() const { return audio_rate ? rs_pitch : audio.pitch; }
 
 private:
@@ -893,13 +887,13 @@ private:
     static constexpr int kTapPoints = 17;
     static constexpr uint32_t kTapsBehindGate = 1u << PEBBLEGPU_TAP_MODEM | 1u << PEBBLEGPU_TAP_POST_DEMOD;  // points a closed squelch gate never reaches
     uint32_t taps_ = 0;
-    float2 *d_tap_[kTapPoints] = {};
+    DevBuf<float2> d_tap_[kTapPoints];
     uint64_t tap_n_[kTapPoints] = {};
     int copy_tap(hipStream_t s, int point, const float2 *src, long long src_pitch, long long n, uint32_t rows);
     ResampCore resamp_;
     SpectrumCore spec_, zoom_;
-    float2 *d_stage_in_ = nullptr;
-    float2 *d_raw_stage_ = nullptr;   // process_raw: the normalised copy of a raw device-format call (allocated on first use)
+    DevBuf<float2> d_stage_in_;
+    DevBuf<float2> d_raw_stage_;      // process_raw: the normalised copy of a raw device-format call (allocated on first use)
     IngestRing ingest_;               // the pinned double buffer of ingest_acquire / _submit / process_ingested (ingest.h)
     IngestRing ext_ingest_;           // device twins of somebody else's pinned slots (ingest_wait / _upload / process_uploaded)
     std::vector<float> h_frame_, h_out_;
@@ -909,7 +903,7 @@ private:
     std::vector<uint32_t> aout_sel_;  // row r of a block is channel aout_sel_[r]
     struct Level { float gain = 100.f; bool mute = false; };  // Receiver::m_gain / m_mute defaults
     std::vector<Level> levels_;       // per channel (kept while the ring is closed)
-    EgressRow *d_aout_tab_ = nullptr; // [C] the selected rows' (g, mute, source row)
+    DevBuf<EgressRow> d_aout_tab_;    // [C] the selected rows' (g, mute, source row)
     bool aout_tab_dirty_ = false;
     int upload_audio_table();
     int queue_audio_block(hipStream_t s, uint64_t n);

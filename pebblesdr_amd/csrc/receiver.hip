@@ -87,13 +87,13 @@ int Receiver::create(const pebblegpu_config *cfg)
         else {
             if (int rc = resamp_.init(C, nf, rr, (uint32_t)(nd_max / nf))) return rc;
             rs_pitch = resamp_.max_out(nd_max);
-            PG_HIP(hipMalloc((void **)&d_audio_rs, sizeof(float2) * (size_t)rs_pitch * C));
+            PG_TRY(d_audio_rs.alloc((size_t)rs_pitch * C));
         }
     }
     if (bins) {
         if (int rc = spec_.init(S, nf, bins, tun_)) return rc;
         bins = spec_.bins;
-        PG_HIP(hipMalloc((void **)&d_spec, sizeof(float) * (size_t)(max_n / nf) * bins * S));
+        PG_TRY(d_spec.alloc((size_t)(max_n / nf) * bins * S));
         if (tun_.fuse_dec && spec_.dec_ready() && nf == 2048) { if (int rc = dec_.set_fuse_window(spec_.d_window, spec_.h_window)) return rc; }  // (opt-in) the decimator may run inside the transform's kernel
     }
     zoom_bins = cfg->hires_bins;
@@ -101,7 +101,7 @@ int Receiver::create(const pebblegpu_config *cfg)
         if (nd_max % nf != 0) return fail(PEBBLEGPU_E_UNSUPPORTED, "the zoomed spectrum needs whole frames at the demodulator rate");
         if (int rc = zoom_.init(C, nf, zoom_bins, tun_)) return rc;
         zoom_bins = zoom_.bins;
-        PG_HIP(hipMalloc((void **)&d_zoom, sizeof(float) * (size_t)(nd_max / nf) * zoom_bins * C));
+        PG_TRY(d_zoom.alloc((size_t)(nd_max / nf) * zoom_bins * C));
     }
     return 0;
 }
@@ -111,32 +111,19 @@ Receiver::~Receiver()
     (void)hipSetDevice(device);
     if (chain_stream_) (void)hipStreamSynchronize(chain_stream_);
     if (stream_) (void)hipStreamSynchronize(stream_);
-    osc_.release(); dec_.release(); ff_.release(); am_.release(); nfm_.release(); sam_.release(); wfmc_.release(); spec_.release(); zoom_.release();
+    // (what is released here holds events or host blocks; device memory goes with the members, behind this body: the streams have been waited for)
+    osc_.release();
+    dec_.release();
     for (hipEvent_t e : sync_ev_) if (e) (void)hipEventDestroy(e);
     ingest_.release();
     ext_ingest_.release();
     aout_.release();
     rec_.release();
     display_destroy();  // (closes an open display ring: waits for a reader that is inside _next)
-    if (d_aout_tab_) (void)hipFree(d_aout_tab_);
-    if (d_zoom) (void)hipFree(d_zoom);
     if (map_ev_) (void)hipEventDestroy(map_ev_);
-    agc_.release(); resamp_.release(); cond_.release(); anf_.release();
+    resamp_.release();
     morse_.release();
     tb_.release();
-    for (float2 *p : d_tap_) if (p) (void)hipFree(p);
-    if (d_audio_rs) (void)hipFree(d_audio_rs);
-    if (h_gate_) (void)hipHostFree(h_gate_);
-    if (d_squelch) (void)hipFree(d_squelch);
-    if (d_gate) (void)hipFree(d_gate);
-    if (d_raw_stage_) (void)hipFree(d_raw_stage_);
-    if (d_spec_carry) (void)hipFree(d_spec_carry);
-    if (d_sm_carry) (void)hipFree(d_sm_carry);
-    if (d_smeter) (void)hipFree(d_smeter);
-    if (d_sm_bins) (void)hipFree(d_sm_bins);
-    audio.release();
-    if (d_spec) (void)hipFree(d_spec);
-    if (d_stage_in_) (void)hipFree(d_stage_in_);
     for (auto &row : tm.ev)
         for (auto &e : row) if (e) (void)hipEventDestroy(e);
     if (chain_stream_) (void)hipStreamDestroy(chain_stream_);
@@ -257,8 +244,8 @@ int Receiver::set_spectrum_updates(int ups)
         if (bins) { if (int rc = spec_.init_list()) return rc; }
         if (zoom_bins) { if (int rc = zoom_.init_list()) return rc; }
         if (bins && !d_spec_carry) {
-            PG_HIP(hipMalloc((void **)&d_spec_carry, sizeof(float) * (size_t)bins * S));
-            PG_HIP(hipMalloc((void **)&d_sm_carry, sizeof(float4) * C));
+            PG_TRY(d_spec_carry.alloc((size_t)bins * S));
+            PG_TRY(d_sm_carry.alloc(C));
         }
         if (spec_ups_ == -1 && bins && last_spec_frames) {
             // so far every frame had a spectrum: the one the S-meter and the squelch go on reading is the last call's last
@@ -295,8 +282,8 @@ int Receiver::enable_smeter(bool on)
     PG_HIP(hipSetDevice(device));
     if (on && !d_smeter) {
         smeter_pitch = (long long)max_sf * (long long)(superframe / nf);
-        PG_HIP(hipMalloc((void **)&d_smeter, sizeof(float4) * (size_t)smeter_pitch * C));
-        PG_HIP(hipMalloc((void **)&d_sm_bins, sizeof(SmBins) * C));
+        PG_TRY(d_smeter.alloc((size_t)smeter_pitch * C));
+        PG_TRY(d_sm_bins.alloc(C));
         sm_dirty_ = true;
     }
     smeter_on = on;
@@ -346,8 +333,8 @@ int Receiver::set_squelch(uint32_t ch, double squelch_db)
         PG_HIP(hipSetDevice(device));
         if (squelch_.empty()) squelch_.assign(C, -120.f);
         if (!d_squelch) {
-            PG_HIP(hipMalloc((void **)&d_squelch, sizeof(float) * C));
-            PG_HIP(hipMalloc((void **)&d_gate, (size_t)C * max_sf));
+            PG_TRY(d_squelch.alloc(C));
+            PG_TRY(d_gate.alloc((size_t)C * max_sf));
         }
         squelch_[ch] = (float)squelch_db;
         bank_gate_ = false;
@@ -362,7 +349,7 @@ int Receiver::set_squelch(uint32_t ch, double squelch_db)
     touched_ = true;  // the next call joins its two pipelines before the change is applied
     if (squelch_db > -120.0 && !h_gate_) {
         PG_HIP(hipSetDevice(device));
-        PG_HIP(hipHostMalloc((void **)&h_gate_, sizeof(float4)));
+        PG_TRY(h_gate_.alloc(1));
     }
     squelch_db_ = squelch_db;
     return 0;
@@ -407,7 +394,7 @@ int Receiver::set_taps(uint32_t mask)
     const size_t max_n = (size_t)max_sf * superframe;
     for (int pt = 0; pt < kTapPoints; pt++) {
         if (!(mask >> pt & 1u)) continue;
-        if (!d_tap_[pt]) PG_HIP(hipMalloc((void **)&d_tap_[pt], sizeof(float2) * (pt == PEBBLEGPU_TAP_RAW_IQ ? (size_t)S * max_n : (size_t)C * (max_n / chain.total))));
+        if (!d_tap_[pt]) PG_TRY(d_tap_[pt].alloc(pt == PEBBLEGPU_TAP_RAW_IQ ? (size_t)S * max_n : (size_t)C * (max_n / chain.total)));
         if (!(taps_ >> pt & 1u)) tap_n_[pt] = 0;  // (nothing of this point yet)
     }
     taps_ = mask;
@@ -610,7 +597,7 @@ int Receiver::join_streams()
 // the staging buffer of raw and generated calls (allocated on first use)
 int Receiver::raw_stage(float2 **p)
 {
-    if (!d_raw_stage_) PG_HIP(hipMalloc((void **)&d_raw_stage_, sizeof(float2) * (size_t)S * max_sf * superframe));
+    if (!d_raw_stage_) PG_TRY(d_raw_stage_.alloc((size_t)S * max_sf * superframe));
     *p = d_raw_stage_;
     return 0;
 }
@@ -1235,7 +1222,7 @@ int Receiver::process_iq(const double *iq, uint16_t n, double *audio_out, uint32
     if (aout_.open || rec_.open || disp_open_)  // (this entry point returns its audio and its spectrum itself, and the host holds the frame it passes in)
         return fail(PEBBLEGPU_E_UNSUPPORTED, "the audio, recording and display rings follow the batched device path (pebblegpu_receiver_process) only: close them first");
     PG_HIP(hipSetDevice(device));
-    if (!d_stage_in_) PG_HIP(hipMalloc((void **)&d_stage_in_, sizeof(float2) * superframe));
+    if (!d_stage_in_) PG_TRY(d_stage_in_.alloc(superframe));
     h_frame_.resize((size_t)nf * 2);
     for (size_t i = 0; i < (size_t)nf * 2; i++) h_frame_[i] = (float)iq[i];
     float2 *dst = d_stage_in_ + acc_frames_ * nf;

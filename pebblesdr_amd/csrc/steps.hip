@@ -53,7 +53,7 @@ using pg::fail;
 struct pebblegpu_mixer : pg::StepBase {
     uint32_t n = 0;
     pg::OscBank osc;
-    float2 *d_in = nullptr, *d_out = nullptr;
+    pg::DevBuf<float2> d_in, d_out;
 };
 struct pebblegpu_decimator : pg::StepBase {
     uint32_t fs = 0, cap = 0;
@@ -61,7 +61,7 @@ struct pebblegpu_decimator : pg::StepBase {
     pg::OscBank osc;  // frequency 0: the oscillator is bypassed, the fused kernel only decimates
     pg::DecimCore dec;
     pg::Tuning tun;   // read at create, handed to dec.init() by every build_chain
-    float2 *d_in = nullptr;
+    pg::DevBuf<float2> d_in;
 };
 // CDownConvert (pebblelib/downconvert.cpp): quadrature-oscillator mixer + a cascade of decimate-by-2 stages
 struct pebblegpu_downconvert : pg::StepBase {
@@ -71,20 +71,18 @@ struct pebblegpu_downconvert : pg::StepBase {
     pg::OscBank osc;
     std::vector<int> stages;          // indices into the stage table
     std::vector<pg::HistBuf> bufs;    // bufs[j]: input of stage j (head-room = its look-back); bufs[nst]: the result
-    std::vector<float *> d_taps;      // [stage] the response it applies, oldest sample first
+    std::vector<pg::DevBuf<float>> d_taps;  // [stage] the response it applies, oldest sample first
     std::vector<int> ntaps;
-    float2 *d_in = nullptr;
+    pg::DevBuf<float2> d_in;
     void drop_chain()
     {
-        for (auto &b : bufs) b.release();
-        for (float *t : d_taps) if (t) (void)hipFree(t);
         bufs.clear(); d_taps.clear(); ntaps.clear(); stages.clear();
     }
 };
 struct pebblegpu_fastfir : pg::StepBase {
     pg::FastFirCore ff;
     pg::HistBuf in;
-    float2 *d_out = nullptr;
+    pg::DevBuf<float2> d_out;
     long long cap = 0;
     std::vector<double> pend;  // samples waiting for a whole block (m_InBufInPos - (FIR-1))
     double lo = -1.0, hi = 1.0, offset = 1.0, rate = 1.0;  // fastfir.cpp:141-144
@@ -95,25 +93,23 @@ struct pebblegpu_demod : pg::StepBase {
     pg::AmCore am;
     pg::PllCore nfm, sam;
     pg::WfmCore wfm;
-    float2 *d_in = nullptr, *d_out = nullptr;
+    pg::DevBuf<float2> d_in, d_out;
 };
 // the test bench's generator (NCO::genSweep / genNoise, MorseGen stations) on one stream of the caller's
 struct pebblegpu_siggen : pg::StepBase {
     pg::TestBenchCore tb;
     uint32_t noise_stream = 0;
-    float2 *d_buf = nullptr;
-    size_t cap = 0;
+    pg::DevBuf<float2> d_buf;  // (grows)
 };
 struct pebblegpu_spectrum : pg::StepBase {
     pg::SpectrumCore sp;
-    float2 *d_in = nullptr;
-    float *d_out = nullptr;
+    pg::DevBuf<float2> d_in;
+    pg::DevBuf<float> d_out;
     std::vector<float> hs;
     int overload = 0;  // m_isOverload: a member, rewritten by whole buffers only (fft.cpp:26,135-140)
     int path = 0;  // 0: no call yet; 1: the frame-length kernels; 2: the general kernel (their previous-frame amplitudes are laid out differently)
     double fs = 0;             // m_sampleRate (mapFFTToScreen's binsPerHz)
-    int32_t *d_px = nullptr;   // mapFFTToScreen's pixels
-    int32_t px_cap = 0;
+    pg::DevBuf<int32_t> d_px;  // mapFFTToScreen's pixels (grows)
 };
 
 extern "C" {
@@ -136,8 +132,8 @@ int pebblegpu_mixer_create(int device, uint32_t sample_rate, uint32_t buffer_siz
     m->n = buffer_size;
     int rc = m->open(device);
     if (!rc) rc = m->osc.init(1, (double)sample_rate);
-    if (!rc && hipMalloc((void **)&m->d_in, sizeof(float2) * buffer_size) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
-    if (!rc && hipMalloc((void **)&m->d_out, sizeof(float2) * buffer_size) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
+    if (!rc) rc = m->d_in.alloc(buffer_size);
+    if (!rc) rc = m->d_out.alloc(buffer_size);
     if (rc) { pebblegpu_mixer_destroy(m); return rc; }
     m->hd.resize((size_t)buffer_size * 2);
     m->osc.retune(0, 0.0);  // ctor: setFrequency(0), mixer.cpp:13
@@ -149,8 +145,6 @@ int pebblegpu_mixer_destroy(pebblegpu_mixer *m)
     if (!m) return 0;
     m->close_stream();
     m->osc.release();
-    if (m->d_in) (void)hipFree(m->d_in);
-    if (m->d_out) (void)hipFree(m->d_out);
     delete m;
     return 0;
 }
@@ -186,7 +180,7 @@ int pebblegpu_decimator_create(int device, uint32_t sample_rate, uint32_t buffer
     d->tun = pg::read_tuning();
     int rc = d->open(device);
     if (!rc) rc = d->osc.init(1, (double)sample_rate);
-    if (!rc && hipMalloc((void **)&d->d_in, sizeof(float2) * buffer_size) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
+    if (!rc) rc = d->d_in.alloc(buffer_size);
     if (rc) { pebblegpu_decimator_destroy(d); return rc; }
     d->osc.retune(0, 0.0);
     *out = d;
@@ -198,7 +192,6 @@ int pebblegpu_decimator_destroy(pebblegpu_decimator *d)
     d->close_stream();
     d->osc.release();
     d->dec.release();
-    if (d->d_in) (void)hipFree(d->d_in);
     delete d;
     return 0;
 }
@@ -257,7 +250,7 @@ int pebblegpu_downconvert_create(int device, uint32_t max_in_length, pebblegpu_d
     d->cap = max_in_length;
     int rc = d->open(device);
     if (!rc) rc = d->osc.init(1, d->in_rate);
-    if (!rc && hipMalloc((void **)&d->d_in, sizeof(float2) * max_in_length) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
+    if (!rc) rc = d->d_in.alloc(max_in_length);
     if (rc) { pebblegpu_downconvert_destroy(d); return rc; }
     d->osc.force_mix = true;       // no "frequency 0" exit: ProcessData always multiplies (downconvert.cpp:283-308)
     d->osc.retune(0, 0.0);         // m_Osc1 = (1, 0), m_NcoFreq = 0 (ctor)
@@ -269,8 +262,6 @@ int pebblegpu_downconvert_destroy(pebblegpu_downconvert *d)
     if (!d) return 0;
     d->close_stream();
     d->osc.release();
-    d->drop_chain();
-    if (d->d_in) (void)hipFree(d->d_in);
     delete d;
     return 0;
 }
@@ -312,15 +303,14 @@ int pebblegpu_downconvert_set_data_rate(pebblegpu_downconvert *d, double in_rate
                 const std::vector<double> h = pg::design::downconvert_stage_response(c.stages[j]);
                 look = (int)h.size() + 1;
                 std::vector<float> hf(h.begin(), h.end());
-                float *t = nullptr;
-                PG_HIP(hipMalloc((void **)&t, sizeof(float) * hf.size()));
-                d->d_taps.push_back(t);
+                pg::DevBuf<float> t;
+                PG_TRY(t.upload(hf.data(), hf.size()));
+                d->d_taps.push_back(std::move(t));
                 d->ntaps.push_back((int)hf.size());
-                PG_HIP(hipMemcpy(t, hf.data(), sizeof(float) * hf.size(), hipMemcpyHostToDevice));
             }
             pg::HistBuf b;
             if (int rc = b.alloc(1, look, len + 2)) return rc;
-            d->bufs.push_back(b);
+            d->bufs.push_back(std::move(b));
             len /= 2;
         }
         // the oscillator keeps its phasor; its increment follows the new input rate
@@ -407,7 +397,7 @@ int pebblegpu_fastfir_create(int device, uint32_t fft_size, uint32_t fir_size, p
         f->cap = 64 * f->ff.block_len();
         rc = f->in.alloc(1, (int)f->ff.taps - 1, f->cap);
     }
-    if (!rc && hipMalloc((void **)&f->d_out, sizeof(float2) * (size_t)f->cap) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
+    if (!rc) rc = f->d_out.alloc((size_t)f->cap);
     if (rc) { pebblegpu_fastfir_destroy(f); return rc; }
     *out = f;
     return 0;
@@ -416,9 +406,6 @@ int pebblegpu_fastfir_destroy(pebblegpu_fastfir *f)
 {
     if (!f) return 0;
     f->close_stream();
-    f->ff.release();
-    f->in.release();
-    if (f->d_out) (void)hipFree(f->d_out);
     delete f;
     return 0;
 }
@@ -482,8 +469,8 @@ int pebblegpu_demod_create(int device, uint32_t sample_rate, uint32_t wfm_sample
     }
     if (!rc && wfm_sample_rate) rc = d->wfm.init(1, (double)wfm_sample_rate, buffer_size, pg::read_tuning());
     d->wfm.stereo_block = 0;  // a processBlock call is one block
-    if (!rc && hipMalloc((void **)&d->d_in, sizeof(float2) * buffer_size) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
-    if (!rc && hipMalloc((void **)&d->d_out, sizeof(float2) * buffer_size) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
+    if (!rc) rc = d->d_in.alloc(buffer_size);
+    if (!rc) rc = d->d_out.alloc(buffer_size);
     if (rc) { pebblegpu_demod_destroy(d); return rc; }
     d->hd.resize((size_t)buffer_size * 2);
     *out = d;
@@ -493,12 +480,6 @@ int pebblegpu_demod_destroy(pebblegpu_demod *d)
 {
     if (!d) return 0;
     d->close_stream();
-    d->am.release();
-    d->nfm.release();
-    d->sam.release();
-    d->wfm.release();
-    if (d->d_in) (void)hipFree(d->d_in);
-    if (d->d_out) (void)hipFree(d->d_out);
     delete d;
     return 0;
 }
@@ -582,8 +563,8 @@ int pebblegpu_spectrum_create(int device, uint32_t fft_size, double sample_rate,
     s->fs = sample_rate;  // the bin width (fft.cpp:81) and mapFFTToScreen's binsPerHz (:424)
     int rc = s->open(device);
     if (!rc) rc = s->sp.init(1, samples_per_buffer, fft_size, pg::read_tuning());
-    if (!rc && hipMalloc((void **)&s->d_in, sizeof(float2) * samples_per_buffer) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
-    if (!rc && hipMalloc((void **)&s->d_out, sizeof(float) * s->sp.bins) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
+    if (!rc) rc = s->d_in.alloc(samples_per_buffer);
+    if (!rc) rc = s->d_out.alloc(s->sp.bins);
     if (rc) { pebblegpu_spectrum_destroy(s); return rc; }
     *out = s;
     return 0;
@@ -592,10 +573,6 @@ int pebblegpu_spectrum_destroy(pebblegpu_spectrum *s)
 {
     if (!s) return 0;
     s->close_stream();
-    s->sp.release();
-    if (s->d_in) (void)hipFree(s->d_in);
-    if (s->d_out) (void)hipFree(s->d_out);
-    if (s->d_px) (void)hipFree(s->d_px);
     delete s;
     return 0;
 }
@@ -644,14 +621,7 @@ int pebblegpu_spectrum_map_to_screen(pebblegpu_spectrum *s, const pebblegpu_scre
     if (int rc = pg::check_screen_map(map->y_pixels, map->x_pixels, map->max_db, map->min_db)) return rc;
     if (!s->path) return fail(PEBBLEGPU_E_INVALID, "no fftSpectrum call yet: there is no spectrum to map");
     PG_HIP(hipSetDevice(s->device));
-    if (map->x_pixels > s->px_cap) {
-        PG_HIP(hipStreamSynchronize(s->stream));
-        if (s->d_px) PG_HIP(hipFree(s->d_px));
-        s->d_px = nullptr;
-        s->px_cap = 0;
-        PG_HIP(hipMalloc((void **)&s->d_px, sizeof(int32_t) * (size_t)map->x_pixels));
-        s->px_cap = map->x_pixels;
-    }
+    PG_TRY(s->d_px.grow(s->stream, (size_t)map->x_pixels));
     const int32_t edges[2] = {map->start_freq, map->stop_freq};
     if (int rc = pg::run_screen_map(s->stream, s->d_out, (long long)s->sp.bins, (long long)s->sp.bins, 1, 1, (int32_t)s->sp.bins, s->fs, edges, false,
                                     map->y_pixels, map->x_pixels, map->max_db, map->min_db, s->d_px)) return rc;
@@ -702,7 +672,6 @@ int pebblegpu_siggen_destroy(pebblegpu_siggen *g)
     if (!g) return 0;
     g->close_stream();
     g->tb.release();
-    if (g->d_buf) (void)hipFree(g->d_buf);
     delete g;
     return 0;
 }
@@ -715,9 +684,8 @@ int pebblegpu_siggen_create(int device, double sample_rate, uint32_t frames_per_
     if (!g) return fail(PEBBLEGPU_E_INVALID, "out of host memory");
     int rc = g->open(device);
     if (!rc) rc = g->tb.init(sample_rate, 1);
-    if (!rc && hipMalloc((void **)&g->d_buf, sizeof(float2) * frames_per_buffer) != hipSuccess) rc = fail(PEBBLEGPU_E_HIP, "hipMalloc failed");
+    if (!rc) rc = g->d_buf.alloc(frames_per_buffer);
     if (rc) { pebblegpu_siggen_destroy(g); return rc; }
-    g->cap = frames_per_buffer;
     *out = g;
     return 0;
 }
@@ -762,14 +730,7 @@ int pebblegpu_siggen_generate(pebblegpu_siggen *g, double *iq, uint32_t n)
     if (n == 0) return fail(PEBBLEGPU_E_SIZE, "bad sample count");
     if (!g->tb.any()) return 0;  // every generator off: the frame stays as it is (testbench.cpp:522-523, 539-540)
     PG_HIP(hipSetDevice(g->device));
-    if (n > g->cap) {
-        PG_HIP(hipStreamSynchronize(g->stream));
-        PG_HIP(hipFree(g->d_buf));
-        g->d_buf = nullptr;
-        g->cap = 0;
-        PG_HIP(hipMalloc((void **)&g->d_buf, sizeof(float2) * n));
-        g->cap = n;
-    }
+    PG_TRY(g->d_buf.grow(g->stream, n));
     if (int rc = g->up(g->d_buf, iq, n)) return rc;
     if (int rc = g->tb.run(g->stream, g->d_buf, n, g->d_buf, n, n, 1, g->noise_stream)) return rc;
     return g->down(iq, g->d_buf, n);

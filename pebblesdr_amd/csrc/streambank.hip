@@ -17,12 +17,12 @@ struct pebblegpu_streambank {
     bool side_ok = true, side = false;
     pg::FastFirCore ff;
     pg::SpectrumCore sp;
-    float2 *d_tail = nullptr, *d_tail_alt = nullptr, *d_filt = nullptr;  // (the two overlap buffers swap after every band-pass call)
-    float *d_spec = nullptr;
+    pg::DevBuf<float2> d_tail, d_tail_alt, d_filt;  // (the two overlap buffers swap after every band-pass call)
+    pg::DevBuf<float> d_spec;
     uint64_t cap = 0, last_n = 0, last_frames = 0;
     hipEvent_t ev[5] = {};           // (ev[4]: behind the conditioners, where a side-by-side call forks)
     bool timed = false;
-    float2 *d_raw_stage = nullptr;   // raw calls of a geometry without converting loads: the normalised copy (allocated on first use)
+    pg::DevBuf<float2> d_raw_stage;  // raw calls of a geometry without converting loads: the normalised copy (allocated on first use)
     pg::IngestRing ingest;           // the pinned double buffer of pebblegpu_streambank_ingest_* (ingest.h)
     int last_fmt = -1;               // the last call's route, for pebblegpu_streambank_kernel_name: -1 float2 input, else the raw format
     bool last_staged = false, last_bp = false, last_sp = false;
@@ -36,14 +36,15 @@ struct pebblegpu_streambank {
     uint64_t spec_rows = 0;          // rows per stream of what d_spec holds (the last call that computed any): its last row is the latest spectrum
     // host egress (egress.h): the band-passed IQ of selected streams and the display rows of a call's spectra, one block per call each
     pg::EgressRing iq_ring, disp_ring;
-    uint32_t *d_iq_tab = nullptr;    // d_iq_tab[r] = the stream of block row r (written at open)
+    pg::DevBuf<uint32_t> d_iq_tab;   // d_iq_tab[r] = the stream of block row r (written at open)
     int iq_fmt = 0;
     pg::DisplayPack disp;            // format, selection table, plot geometry of the display ring
+    pg::DevBuf<uint32_t> d_disp_tab; // ... the table disp.d_tab looks at
     uint32_t disp_max_rows = 0;
     // the display ring's auto-scale (SpectrumWidget::recalcScale, kernels_display.h): host flags consumed when the next call is queued
     uint32_t scale_flags = 0, scale_live = 0;  // PEBBLEGPU_AUTO_SCALE_* as last set; those whose end a recalc has computed since
     bool scale_pending = false;      // m_scaleNeedsRecalc
-    pg::ScaleEntry *d_scale = nullptr;  // [n_streams] the ranges (allocated with the ring)
+    pg::DevBuf<pg::ScaleEntry> d_scale; // [n_streams] the ranges (allocated with the ring)
     uint64_t trailer_bytes = 0;      // per slot, behind the rows
     bool slot_scaled[pg::kEgressMaxSlots] = {};  // the slot's block carries a trailer
     // the S-meter and the squelch (kernels_strength.h): host state consumed when the next call is queued, like the auto-scale flags
@@ -52,16 +53,16 @@ struct pebblegpu_streambank {
     std::vector<float> squelch;          // per stream; -120 and below never closes
     uint32_t n_squelch = 0;              // thresholds above -120: while there are any the IQ ring packs through the gated instance
     bool win_dirty = true, sq_dirty = true;
-    pg::SmBins *d_win = nullptr;         // [n_streams] fdEstimate's windows
-    float *d_squelch = nullptr;          // [n_streams]
-    float4 *d_smeter = nullptr;          // [n_streams][max_frames]: one entry per row the last call computed
-    float4 *d_carry[2] = {};             // [n_streams] each: the last computed entry per stream.  A call that computes rows writes the other
+    pg::DevBuf<pg::SmBins> d_win;        // [n_streams] fdEstimate's windows
+    pg::DevBuf<float> d_squelch;         // [n_streams]
+    pg::DevBuf<float4> d_smeter;         // [n_streams][max_frames]: one entry per row the last call computed
+    pg::DevBuf<float4> d_carry[2];       // [n_streams] each: the last computed entry per stream.  A call that computes rows writes the other
     int carry_cur = 0;                   // one, so its own gate still reads what earlier calls left; then they swap
     bool have_row = false;               // d_carry[carry_cur] holds a row (computed since the S-meter went on)
     uint64_t sm_rows = 0;                // entries per stream the last call wrote
     // table uploads that never wait for earlier calls: pinned staging slots, each reused once the copy queued from it has completed
     static constexpr int kStage = 4;
-    void *h_stage[kStage] = {};
+    pg::PinnedBuf<unsigned char> h_stage[kStage];
     hipEvent_t stage_ev[kStage] = {};
     int stage_next = 0;
     // the input conditioners (kernels_condition.h): host flags consumed when the next call is queued; the setter touches no device state
@@ -74,14 +75,15 @@ struct pebblegpu_streambank {
     pg::ScanParams<1> cond_dc;           // DCRemoval's high-pass
     pg::CondAvg cond_mag{}, cond_cpx{};  // the blankers' averages
     double cond_m[4] = {};               // the high-pass's transition matrix on (w1, w1 - w2) to the power of a chunk
-    float2 *d_cond[2] = {};              // [n_streams][capacity] each; d_cond[1] IS d_raw_stage (allocated on first use, either way)
-    pg::CondPar *d_cond_par = nullptr;
-    pg::CondState *d_cond_state = nullptr;
-    double *d_cond_sum = nullptr, *d_cond_entry = nullptr;  // [n_streams][chunks][4]
-    unsigned *d_cond_map = nullptr;      // [n_streams][chunks]
-    int *d_cond_count = nullptr;         // [n_streams][chunks]
-    float2 *d_cond_prev = nullptr;       // [n_streams][2]
-    void *h_cond[kStage] = {};           // pinned staging of the parameter table, reused like h_stage
+    float2 *d_cond[2] = {};              // views, [n_streams][capacity] each: of d_cond0 and of d_raw_stage (allocated on first use, either way)
+    pg::DevBuf<float2> d_cond0;
+    pg::DevBuf<pg::CondPar> d_cond_par;
+    pg::DevBuf<pg::CondState> d_cond_state;
+    pg::DevBuf<double> d_cond_sum, d_cond_entry;  // [n_streams][chunks][4]
+    pg::DevBuf<unsigned> d_cond_map;     // [n_streams][chunks]
+    pg::DevBuf<int> d_cond_count;        // [n_streams][chunks]
+    pg::DevBuf<float2> d_cond_prev;      // [n_streams][2]
+    pg::PinnedBuf<pg::CondPar> h_cond[kStage];  // pinned staging of the parameter table, reused like h_stage
     hipEvent_t cond_ev[kStage] = {};
     int cond_next = 0;
     const float2 *last_cond = nullptr;   // the rows the last call's transforms read, if it conditioned any
@@ -115,7 +117,7 @@ static int sb_selection(const pebblegpu_streambank *sb, const uint32_t *streams,
 }
 
 // allocates the ring and the selection's table; on failure everything it made is freed again and the handle is as it was
-static int sb_open_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, uint32_t **d_tab, const std::vector<uint32_t> &sel, uint32_t n_slots, uint32_t bps,
+static int sb_open_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, pg::DevBuf<uint32_t> &d_tab, const std::vector<uint32_t> &sel, uint32_t n_slots, uint32_t bps,
                         uint64_t max_n, uint32_t fmt, uint64_t extra_bytes = 0)
 {
     const uint64_t slot = (uint64_t)sel.size() * pg::EgressRing::row_pitch(max_n, bps) + extra_bytes;
@@ -124,8 +126,7 @@ static int sb_open_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, uint32_t
                     (unsigned long long)kMaxRingBytes);
     PG_HIP(hipSetDevice(sb->cfg.device));
     auto body = [&]() -> int {
-        PG_HIP(hipMalloc((void **)d_tab, sizeof(uint32_t) * sel.size()));
-        PG_HIP(hipMemcpy(*d_tab, sel.data(), sizeof(uint32_t) * sel.size(), hipMemcpyHostToDevice));
+        PG_TRY(d_tab.upload(sel.data(), sel.size()));
         if (int rc = ring.open_ring(n_slots, (uint32_t)sel.size(), bps, max_n, fmt, extra_bytes)) return rc;
         for (uint32_t i = 0; i < n_slots; i++) PG_HIP(hipMemset(ring.slot[i].d, 0, ring.slot_bytes));  // (the padding of a row is never written)
         return 0;
@@ -134,20 +135,18 @@ static int sb_open_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, uint32_t
     const int rc = body();
     if (rc) {
         ring.release();
-        if (*d_tab) (void)hipFree(*d_tab);
-        *d_tab = nullptr;
+        d_tab.release();
     }
     return rc;
 }
 
-static int sb_close_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, uint32_t **d_tab)
+static int sb_close_ring(pebblegpu_streambank *sb, pg::EgressRing &ring, pg::DevBuf<uint32_t> &d_tab)
 {
     PG_HIP(hipSetDevice(sb->cfg.device));
     PG_HIP(hipStreamSynchronize(sb->stream));
     PG_HIP(hipStreamSynchronize(sb->stream2));
     ring.close_ring();
-    if (*d_tab) (void)hipFree(*d_tab);
-    *d_tab = nullptr;
+    d_tab.release();
     return 0;
 }
 
@@ -315,15 +314,15 @@ static int sb_condition(pebblegpu_streambank *sb, const float2 **in, bool owned,
         };
         avg(sb->cond_mag, 0.999, 0.001);
         avg(sb->cond_cpx, 0.75, 0.25);
-        if (!sb->d_cond_par) PG_HIP(hipMalloc((void **)&sb->d_cond_par, sizeof(pg::CondPar) * S));
-        if (!sb->d_cond_state) PG_HIP(hipMalloc((void **)&sb->d_cond_state, sizeof(pg::CondState) * S));
-        if (!sb->d_cond_sum) PG_HIP(hipMalloc((void **)&sb->d_cond_sum, sizeof(double) * 4 * ncmax * S));
-        if (!sb->d_cond_entry) PG_HIP(hipMalloc((void **)&sb->d_cond_entry, sizeof(double) * 4 * ncmax * S));
-        if (!sb->d_cond_map) PG_HIP(hipMalloc((void **)&sb->d_cond_map, sizeof(unsigned) * ncmax * S));
-        if (!sb->d_cond_count) PG_HIP(hipMalloc((void **)&sb->d_cond_count, sizeof(int) * ncmax * S));
-        if (!sb->d_cond_prev) PG_HIP(hipMalloc((void **)&sb->d_cond_prev, sizeof(float2) * 2 * S));
+        if (!sb->d_cond_par) PG_TRY(sb->d_cond_par.alloc(S));
+        if (!sb->d_cond_state) PG_TRY(sb->d_cond_state.alloc(S));
+        if (!sb->d_cond_sum) PG_TRY(sb->d_cond_sum.alloc(4 * ncmax * S));
+        if (!sb->d_cond_entry) PG_TRY(sb->d_cond_entry.alloc(4 * ncmax * S));
+        if (!sb->d_cond_map) PG_TRY(sb->d_cond_map.alloc(ncmax * S));
+        if (!sb->d_cond_count) PG_TRY(sb->d_cond_count.alloc(ncmax * S));
+        if (!sb->d_cond_prev) PG_TRY(sb->d_cond_prev.alloc((size_t)2 * S));
         for (int i = 0; i < pebblegpu_streambank::kStage; i++) {
-            if (!sb->h_cond[i]) PG_HIP(hipHostMalloc(&sb->h_cond[i], sizeof(pg::CondPar) * S, hipHostMallocDefault));
+            if (!sb->h_cond[i]) PG_TRY(sb->h_cond[i].alloc(S));
             if (!sb->cond_ev[i]) PG_HIP(hipEventCreateWithFlags(&sb->cond_ev[i], hipEventDisableTiming));
         }
     }
@@ -334,7 +333,7 @@ static int sb_condition(pebblegpu_streambank *sb, const float2 **in, bool owned,
         const int i = sb->cond_next;
         sb->cond_next = (i + 1) % pebblegpu_streambank::kStage;
         PG_HIP(hipEventSynchronize(sb->cond_ev[i]));
-        pg::CondPar *t = static_cast<pg::CondPar *>(sb->h_cond[i]);
+        pg::CondPar *t = sb->h_cond[i];
         sb->cond_mask = 0;
         for (uint32_t s = 0; s < S; s++) {
             const auto &h = sb->cond[s];
@@ -352,9 +351,9 @@ static int sb_condition(pebblegpu_streambank *sb, const float2 **in, bool owned,
     const int mask = sb->cond_mask;
     auto buffer = [&](int i) -> int {
         if (sb->d_cond[i]) return 0;
-        if (i == 1 && sb->d_raw_stage) { sb->d_cond[1] = sb->d_raw_stage; return 0; }
-        PG_HIP(hipMalloc((void **)&sb->d_cond[i], sizeof(float2) * (size_t)S * sb->cap));
-        if (i == 1) sb->d_raw_stage = sb->d_cond[1];
+        pg::DevBuf<float2> &own = i ? sb->d_raw_stage : sb->d_cond0;
+        if (!own) PG_TRY(own.alloc((size_t)S * sb->cap));
+        sb->d_cond[i] = own;
         return 0;
     };
     const long long N = (long long)n;
@@ -426,17 +425,8 @@ int pebblegpu_streambank_destroy(pebblegpu_streambank *sb)
         (void)hipStreamSynchronize(sb->stream);
         (void)hipStreamDestroy(sb->stream);
     }
-    sb->ff.release();
-    sb->sp.release();
     sb->ingest.release();
-    void *p[] = {sb->d_tail, sb->d_tail_alt, sb->d_filt, sb->d_spec, sb->d_raw_stage, sb->d_iq_tab, sb->disp.d_tab, sb->d_scale,
-                 sb->d_win, sb->d_squelch, sb->d_smeter, sb->d_carry[0], sb->d_carry[1],
-                 sb->d_cond[0], sb->d_cond_par, sb->d_cond_state, sb->d_cond_sum, sb->d_cond_entry, sb->d_cond_map, sb->d_cond_count,
-                 sb->d_cond_prev};  // (d_cond[1] is d_raw_stage)
-    for (void *q : p) if (q) (void)hipFree(q);
-    for (void *q : sb->h_stage) if (q) (void)hipHostFree(q);
     for (hipEvent_t e : sb->stage_ev) if (e) (void)hipEventDestroy(e);
-    for (void *q : sb->h_cond) if (q) (void)hipHostFree(q);
     for (hipEvent_t e : sb->cond_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sb->ev) if (e) (void)hipEventDestroy(e);
     delete sb;
@@ -473,12 +463,10 @@ int pebblegpu_streambank_create(const pebblegpu_streambank_config *cfg, pebblegp
         if (int r = sb->sp.init(S, cfg->frame, cfg->spectrum_bins, tun)) return r;
         if (cfg->frame % (uint64_t)sb->ff.block_len()) return fail(PEBBLEGPU_E_SIZE, "frame %u is not a multiple of the band-pass block %lld", cfg->frame, sb->ff.block_len());
         const size_t ov = sb->cfg.fastfir_taps - 1;
-        PG_HIP(hipMalloc((void **)&sb->d_tail, sizeof(float2) * ov * S));
-        PG_HIP(hipMemset(sb->d_tail, 0, sizeof(float2) * ov * S));  // m_pFFTOverlapBuf starts at zero, fastfir.cpp:104-105
-        PG_HIP(hipMalloc((void **)&sb->d_tail_alt, sizeof(float2) * ov * S));
-        PG_HIP(hipMemset(sb->d_tail_alt, 0, sizeof(float2) * ov * S));
-        PG_HIP(hipMalloc((void **)&sb->d_filt, sizeof(float2) * sb->cap * S));
-        PG_HIP(hipMalloc((void **)&sb->d_spec, sizeof(float) * (size_t)sb->sp.bins * cfg->max_frames * S));
+        PG_TRY(sb->d_tail.alloc_zero(ov * S));  // m_pFFTOverlapBuf starts at zero, fastfir.cpp:104-105
+        PG_TRY(sb->d_tail_alt.alloc_zero(ov * S));
+        PG_TRY(sb->d_filt.alloc(sb->cap * S));
+        PG_TRY(sb->d_spec.alloc((size_t)sb->sp.bins * cfg->max_frames * S));
         for (hipEvent_t &e : sb->ev) PG_HIP(hipEventCreate(&e));
         // CFastFIR's constructor state: lo -1, hi 1, offset 1, rate 1 -> an all-zero filter until the first setup
         return 0;
@@ -621,7 +609,7 @@ static int sb_run_raw(pebblegpu_streambank *sb, int fmt, int order, double gain,
     sb->last_staged = !sb_converts(sb, what) || (sb->n_cond && n);  // (the conditioners read and write float2 rows)
     if (!sb->last_staged || n == 0) return sb_run(sb, nullptr, &raw, n, what);
     const size_t S = sb->cfg.n_streams;
-    if (!sb->d_raw_stage) PG_HIP(hipMalloc((void **)&sb->d_raw_stage, sizeof(float2) * S * sb->cap));
+    if (!sb->d_raw_stage) PG_TRY(sb->d_raw_stage.alloc(S * sb->cap));
     sb->d_cond[1] = sb->d_raw_stage;
     // (the rows of d_raw are n pairs apart, so S * n pairs are one run; the side stream forks behind it, at the call's start event)
     if (int rc = pg::run_normalize_iq(fmt, order, 1.0, d_raw, (long long)(S * n), sb->d_raw_stage, sb->stream, false, &raw.scale)) return rc;
@@ -811,7 +799,7 @@ int pebblegpu_streambank_iq_out_open(pebblegpu_streambank *sb, int format, const
     if (sb->iq_ring.open) return fail(PEBBLEGPU_E_INVALID, "the IQ ring is already open");
     // (room behind the rows for the gate trailer, reserved whether or not the S-meter is on: a slot's size is fixed here)
     const uint64_t trailer = ((uint64_t)sel.size() * sb->cfg.max_frames * sizeof(pg::StreamGate) + 15) & ~(uint64_t)15;
-    if (int rc = sb_open_ring(sb, sb->iq_ring, &sb->d_iq_tab, sel, n_slots, pg::kAudioBytes[format], sb->cap, (uint32_t)format, trailer)) return rc;
+    if (int rc = sb_open_ring(sb, sb->iq_ring, sb->d_iq_tab, sel, n_slots, pg::kAudioBytes[format], sb->cap, (uint32_t)format, trailer)) return rc;
     sb->iq_fmt = format;
     sb->gate_bytes = trailer;
     for (bool &b : sb->slot_gated) b = false;
@@ -821,7 +809,7 @@ int pebblegpu_streambank_iq_out_close(pebblegpu_streambank *sb)
 {
     if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
     if (!sb->iq_ring.open) return fail(PEBBLEGPU_E_INVALID, "the IQ ring is not open");
-    return sb_close_ring(sb, sb->iq_ring, &sb->d_iq_tab);
+    return sb_close_ring(sb, sb->iq_ring, sb->d_iq_tab);
 }
 int pebblegpu_streambank_iq_out_next(pebblegpu_streambank *sb, int wait, pebblegpu_audio_block *b)
 {
@@ -884,10 +872,10 @@ int pebblegpu_streambank_display_open(pebblegpu_streambank *sb, int format, cons
     const uint64_t trailer = ((uint64_t)sel.size() * sizeof(pg::ScaleEntry) + 15) & ~(uint64_t)15;
     PG_HIP(hipSetDevice(sb->cfg.device));
     if (!sb->d_scale) {
-        PG_HIP(hipMalloc((void **)&sb->d_scale, sizeof(pg::ScaleEntry) * sb->cfg.n_streams));
-        PG_HIP(hipMemset(sb->d_scale, 0, sizeof(pg::ScaleEntry) * sb->cfg.n_streams));
+        PG_TRY(sb->d_scale.alloc_zero(sb->cfg.n_streams));
     }
-    if (int rc = sb_open_ring(sb, sb->disp_ring, &plan.d_tab, sel, n_slots, 4, (uint64_t)rows * (plan.row_pitch_bytes / 4), (uint32_t)format, trailer)) return rc;
+    if (int rc = sb_open_ring(sb, sb->disp_ring, sb->d_disp_tab, sel, n_slots, 4, (uint64_t)rows * (plan.row_pitch_bytes / 4), (uint32_t)format, trailer)) return rc;
+    plan.d_tab = sb->d_disp_tab;
     sb->disp = plan;
     sb->disp_max_rows = rows;
     sb->trailer_bytes = trailer;
@@ -899,7 +887,8 @@ int pebblegpu_streambank_display_close(pebblegpu_streambank *sb)
 {
     if (!sb) return fail(PEBBLEGPU_E_INVALID, "null argument");
     if (!sb->disp_ring.open) return fail(PEBBLEGPU_E_INVALID, "the display ring is not open");
-    return sb_close_ring(sb, sb->disp_ring, &sb->disp.d_tab);
+    sb->disp.d_tab = nullptr;
+    return sb_close_ring(sb, sb->disp_ring, sb->d_disp_tab);
 }
 int pebblegpu_streambank_display_next(pebblegpu_streambank *sb, int wait, pebblegpu_display_block *b)
 {
@@ -1047,13 +1036,13 @@ int pebblegpu_streambank_enable_signal_strength(pebblegpu_streambank *sb, int on
     if (!sb->d_smeter) {  // (kept until destroy; nothing here waits for queued calls)
         const size_t stage = std::max(sizeof(pg::SmBins), sizeof(float)) * S;
         for (int i = 0; i < pebblegpu_streambank::kStage; i++) {
-            if (!sb->h_stage[i]) PG_HIP(hipHostMalloc(&sb->h_stage[i], stage, hipHostMallocDefault));
+            if (!sb->h_stage[i]) PG_TRY(sb->h_stage[i].alloc(stage));
             if (!sb->stage_ev[i]) PG_HIP(hipEventCreateWithFlags(&sb->stage_ev[i], hipEventDisableTiming));
         }
-        if (!sb->d_win) PG_HIP(hipMalloc((void **)&sb->d_win, sizeof(pg::SmBins) * S));
-        if (!sb->d_squelch) PG_HIP(hipMalloc((void **)&sb->d_squelch, sizeof(float) * S));
-        for (float4 *&c : sb->d_carry) if (!c) PG_HIP(hipMalloc((void **)&c, sizeof(float4) * S));
-        PG_HIP(hipMalloc((void **)&sb->d_smeter, sizeof(float4) * (size_t)S * sb->cfg.max_frames));
+        if (!sb->d_win) PG_TRY(sb->d_win.alloc(S));
+        if (!sb->d_squelch) PG_TRY(sb->d_squelch.alloc(S));
+        for (pg::DevBuf<float4> &c : sb->d_carry) if (!c) PG_TRY(c.alloc(S));
+        PG_TRY(sb->d_smeter.alloc((size_t)S * sb->cfg.max_frames));
     }
     sb->sm_on = true;
     sb->win_dirty = sb->sq_dirty = true;

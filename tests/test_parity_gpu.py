@@ -1913,9 +1913,11 @@ def test_lifecycle_and_back_to_back_calls(gpu_lib, oracle_mod):
     oracle that saw the same sequence."""
     import pebblesdr_amd as P
     fs, n = 2048000, 2048
+    live = P.binding.live_bytes()
     for _ in range(30):
         b = P.ReceiverBank(fs, 4, True, False, 4096, max_superframes=4, audio_rate=11025)
         b.close()
+    assert P.binding.live_bytes() == live  # what the library holds, to the byte (pebblegpu_live_bytes)
     rx = P.ReceiverBank(fs, 1, True, False, 4096, max_superframes=1)
     ref = oracle_mod.Receiver(fs, n, 4096)
     sf = rx.superframe
