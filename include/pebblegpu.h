@@ -750,7 +750,8 @@ int pebblegpu_demod_destroy(pebblegpu_demod *d);
 int pebblegpu_demod_set_mode(pebblegpu_demod *d, int mode);          /* demod.cpp:241-257 */
 int pebblegpu_demod_set_bandwidth(pebblegpu_demod *d, double bw);    /* demod.cpp:230-239 */
 /* CPX *Demod::processBlock(CPX *in, int n), application/demod.h:33: *out = library buffer, or = in for the
- * pass-through modes (demod.cpp:127-138) */
+ * pass-through modes (demod.cpp:127-138).  The demodulating modes take calls of 80 samples or more (the depth of their FIRs' history);
+ * a shorter one is PEBBLEGPU_E_SIZE and leaves the stream where it was */
 int pebblegpu_demod_process(pebblegpu_demod *d, const double *in, int n, const double **out);
 /* dmFMS: getNextRdsGroupData as above, a processBlock call being one frame; and m_RdsData (the matched filter's output the bit
  * slicer reads, demod_wfm.cpp:309) of the last processBlock call: *n its length, at most cap values copied */

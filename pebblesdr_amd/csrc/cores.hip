@@ -1377,13 +1377,14 @@ int PllCore::set_list(hipStream_t s, const std::vector<int> &channels)
     }
     return 0;
 }
-int PllCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate)
+int PllCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate, int blk_len, int blk_frame)
 {
     if (list.empty()) return 0;
     if (n > tmp.cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
+    if (n < tmp.hist) return fail(PEBBLEGPU_E_SIZE, "PLL demod needs at least %d samples per call", tmp.hist);  // k_save_tail reads tmp[n - hist .. n)
     const unsigned nl = (unsigned)list.size();
     launch(k_pll_demod, dim3(cdiv(nl, 64)), dim3(64), s, in, in_pitch, tmp.data(), tmp.pitch, n, pp, d_state, (const int *)d_list,
-           (int)nl, gate);
+           (int)nl, gate, blk_frame > 0 ? blk_len : 0, blk_frame);
     launch(k_fir_dec, dim3(cdiv(n, 256), nl), dim3(256), s, (const float2 *)tmp.data(), tmp.pitch, out, out_pitch, n, 1, (const float *)d_taps_i,
            (const float *)d_taps_q, 0, (const int *)nullptr, ntaps, 1.0f, mode == 1 ? 1 : 0, (const int *)d_list, gate);
     // the listed channels' FIR history (a gated channel keeps its own)

@@ -448,7 +448,7 @@ static __global__ __launch_bounds__(256) void k_wfm_lmr_fir(const float2 *__rest
 // CFir that follows is k_fir_dec.
 static __global__ __launch_bounds__(64) void k_pll_demod(const float2 *__restrict__ in, long long in_pitch, float2 *__restrict__ out,
                                                          long long out_pitch, long long n, PllParams pp, PllState *__restrict__ st,
-                                                         const int *__restrict__ chan_list, int nlist, Gate gate)
+                                                         const int *__restrict__ chan_list, int nlist, Gate gate, int blk_len, int blk_frame)
 {
     const int li = blockIdx.x * 64 + threadIdx.x;
     if (li >= nlist) return;
@@ -459,6 +459,13 @@ static __global__ __launch_bounds__(64) void k_pll_demod(const float2 *__restric
     PllState s = st[c];
     const double kTwoPi = 6.28318530717958647692528676656, kPiD = 3.14159265358979323846;
     if (pp.mode == 0) {
+        // Demod_NFM wraps its phase at the end of every processBlock (demod_nfm.cpp:253), and the receiver hands it one frame of blk_frame
+        // demodulator-rate samples at a time (receiver.cpp:927-929, 987).  Wherever blk_len, the band-pass's block, divides blk_frame -- the
+        // reference's only case (1024 and 2048) -- the rule below wraps every blk_frame samples, as the reference does.  Where it does not,
+        // this library's band-pass releases whole blocks per frame and the wrap falls at the end of what each frame released: a behaviour of
+        // this library's alone, with no reference semantics.  A call starts on a block and a frame boundary (p counts from the call's
+        // start): a receiver's calls are whole super-frames.  blk_len 0: the call is one block
+        int to_blk = blk_len;
         for (long long i = 0; i < n; i++) {
             const double nco_sin = (double)sinf(s.phase), nco_cos = (double)cosf(s.phase);
             const float2 v = x[i];
@@ -471,6 +478,11 @@ static __global__ __launch_bounds__(64) void k_pll_demod(const float2 *__restric
             s.phase = (float)((double)s.phase + ((double)s.freq + (double)pp.alpha * phzerror));
             s.err_dc = (float)((1.0 - (double)pp.dc_alpha) * (double)s.err_dc + (double)pp.dc_alpha * (double)s.freq);
             y[i] = make_float2(__fmul_rn(__fsub_rn(s.freq, s.err_dc), pp.out_gain), 0.f);  // float arithmetic; CPX = real: imag 0
+            if (blk_len > 0 && --to_blk == 0) {
+                to_blk = blk_len;
+                const long long p = i + 1;  // a multiple of blk_len: released when a frame ends before the next block is full
+                if ((p + blk_frame - 1) / blk_frame * blk_frame < p + blk_len) s.phase = (float)fmod((double)s.phase, kTwoPi);
+            }
         }
         s.phase = (float)fmod((double)s.phase, kTwoPi);  // "keep radian counter bounded", once per block
     } else {

@@ -85,6 +85,8 @@ struct TailJob {
     int hist, pad_;
     float2 *dst;           // nullptr: the head-room in front of data
     long long dst_pitch;
+    const int *list;       // nullptr: every row of the launch; else rows list[0 .. n_list) only (the rest keep their head-room)
+    int n_list, pad2_;
 };
 constexpr int kMaxTailJobs = 12;
 // The oscillators' per-call fields can ride on the same launch: osc[c].phase0 += adv[c] (mod 1), n0 += adv_n (saturating at

@@ -282,11 +282,12 @@ struct AmCore {
     int set_bandwidth(hipStream_t s, uint32_t ch, double bw);   // Demod_AM::setBandwidth, demod_am.cpp:17-21
     int set_list(hipStream_t s, const std::vector<int> &am_channels);
     // in/out rows may be the same buffer (the scan reads `in`, the FIR writes `out`)
-    // defer_tail: run() leaves the refresh of tmp's head-room to the caller's tail launch (tail_jobs: every row, also those of channels
-    // that are not AM -- harmless; not for gated calls, whose closed channels keep their history)
+    // defer_tail: run() leaves the refresh of tmp's head-room to the caller's tail launch (tail_jobs: the rows of the AM list only, as
+    // k_save_tail -- a channel that left AM keeps the end of its last AM call there, like the idle Demod_AM's delay line, whatever the
+    // lengths of the calls it sits out; not for gated calls, whose closed channels keep their history)
     int run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate = Gate{nullptr, 0, 0}, bool defer_tail = false);
     long long deferred_n = 0;       // samples of the last run() whose tail refresh was left to the caller (0: none)
-    void tail_jobs(std::vector<TailJob> &jobs) const { if (!list.empty() && deferred_n > 0) jobs.push_back(TailJob{tmp.data(), tmp.pitch, deferred_n, tmp.hist, 0, nullptr, 0}); }
+    void tail_jobs(std::vector<TailJob> &jobs) const { if (!list.empty() && deferred_n > 0) jobs.push_back(TailJob{tmp.data(), tmp.pitch, deferred_n, tmp.hist, 0, nullptr, 0, d_list, (int)list.size(), 0}); }
 };
 
 // ---- Demod_NFM / Demod_SAM (PLL demodulators) ----
@@ -302,7 +303,10 @@ struct PllCore {
     std::vector<int> list;
     int init(uint32_t channels, double demod_rate, long long max_n, int which);
     int set_list(hipStream_t s, const std::vector<int> &channels);
-    int run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate = Gate{nullptr, 0, 0});
+    // blk_len, blk_frame: the band-pass releases whole blocks of blk_len per frame of blk_frame samples and Demod_NFM wraps its phase at the end
+    // of what each frame released (k_pll_demod); 0, 0: the call is one processBlock
+    int run(hipStream_t s, const float2 *in, long long in_pitch, float2 *out, long long out_pitch, long long n, Gate gate = Gate{nullptr, 0, 0},
+            int blk_len = 0, int blk_frame = 0);
 };
 
 // ---- Demod_WFM mono ----

@@ -919,7 +919,7 @@ int Receiver::tail_bank_gated(Call &c)
         if (int rc = agc_.run(cs, seg, audio.pitch, spf, gate)) return rc;
         if (int rc = am_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate, false)) return rc;
         if (sam_.C) { if (int rc = sam_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate)) return rc; }
-        if (nfm_.C) { if (int rc = nfm_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate)) return rc; }
+        if (nfm_.C) { if (int rc = nfm_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate, (int)ff_.block_len(), (int)nf)) return rc; }
     }
     if (int rc = run_gate_zero(cs, audio.data(), audio.pitch, spf, d_gate, (int)max_sf, C, k)) return rc;
     return clear_tune_only_rows(cs, audio.data(), audio.pitch, nd);
@@ -942,7 +942,7 @@ int Receiver::tail_narrow(Call &c)
     // (a two-stage call's tail launch carries the AM demodulator's history refresh: one launch fewer)
     if (int rc = am_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd, Gate{nullptr, 0, 0}, c.rt.bank_pipe)) return rc;
     if (sam_.C) { if (int rc = sam_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd)) return rc; }
-    if (nfm_.C) { if (int rc = nfm_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd)) return rc; }
+    if (nfm_.C) { if (int rc = nfm_.run(cs, audio.data(), audio.pitch, audio.data(), audio.pitch, nd, Gate{nullptr, 0, 0}, (int)ff_.block_len(), (int)nf)) return rc; }
     if (int rc = clear_tune_only_rows(cs, audio.data(), audio.pitch, nd)) return rc;
     return copy_tap(cs, PEBBLEGPU_TAP_POST_DEMOD, audio.data(), audio.pitch, nd, C);  // receiver.cpp:992, before the resampler
 }

@@ -5,7 +5,8 @@
 namespace pg {
 
 // All history tails of a call: buf[c][-hist + j] = buf[c][n - hist + j], j < hist, for job z and channel y (or into a separate
-// destination).  n may be shorter than hist (then part of the old history is kept, shifted), so a workgroup first reads every
+// destination).  A job with a channel list serves the listed rows only (workgroup y takes row list[y], the rest leave at once): the
+// rows of channels the call's kernels did not fill keep their head-room.  n may be shorter than hist (then part of the old history is kept, shifted), so a workgroup first reads every
 // value it will write.  Executed by ALL work-items of a workgroup (one barrier); the first 256 do the work; hist <= 256 * 32.
 // z == 0 also advances the oscillators when the job list carries an OscAdvance.
 __device__ __forceinline__ void save_tails_block(const TailJobs &jobs, int z, int y, int tid)
@@ -21,6 +22,10 @@ __device__ __forceinline__ void save_tails_block(const TailJobs &jobs, int z, in
     }
     if (z >= jobs.count) return;  // (an advance-only launch; uniform over the workgroup)
     const TailJob &tj = jobs.job[z];
+    if (tj.list != nullptr) {  // a job of listed rows: workgroup y serves row list[y] (uniform over the workgroup, in front of the barrier)
+        if (y >= tj.n_list) return;
+        y = tj.list[y];
+    }
     float2 *b = tj.data + (long long)y * tj.pitch;
     float2 keep[32];
     if (tid < 256) {
