@@ -232,9 +232,20 @@ int pebblegpu_set_agc(pebblegpu_receiver *rx, uint32_t channel, int agc_mode, in
 int pebblegpu_receiver_process(pebblegpu_receiver *rx, const void *d_iq, uint64_t n_samples);
 /* The same call fed with the device's own sample format (what ProducerConsumer hands normalizeIQ,
  * deviceinterfacebase.cpp:648-838): d_raw holds n_streams x n_samples raw IQ pairs, stream-major, in `format`
- * (pebblegpu_iq_format) and `iq_order`; they are scaled by the format's constant and `gain` into a library-owned float2
- * buffer on the library's stream (no host synchronisation) and processed as above.  Moves 2-4 bytes per sample over
- * PCIe/HBM on the way in instead of 8. */
+ * (pebblegpu_iq_format) and `iq_order`, scaled by the format's constant and `gain` (gain 0 is silence).  Results equal
+ * pebblegpu_receiver_process on the same samples converted on the host with the same constants, bit for bit, whichever way the call goes:
+ *   converted in the loads -- one stream, one channel beside the 8192-bin display transform, a first decimator stage hb11 x S (the
+ *     headline shape among them), no conditioner, generator, squelch value or per-kernel profiling on, and no oscillator inside its
+ *     amplitude transient (the first call of a handle and the call behind a retune are): the display transform and the first stage
+ *     read the raw pairs themselves and no float2 copy of the stream exists.  The recording ring and the RAW_IQ tap read the raw pairs too;
+ *   staged -- every other call: k_normalize_iq converts all streams into a library-owned float2 buffer on the library's stream (no host
+ *     synchronisation) and the call goes on from there.
+ * pebblegpu_receiver_kernel_name(rx, 6) says which it was.  d_raw must be aligned to PEBBLEGPU_RAW_ALIGN bytes on either route (the
+ * converting loads read 8, 16 and 32 bytes at a time), which every allocation and every whole super-frame inside one is.  Refused
+ * before anything is queued, leaving the handle usable: a null or misaligned d_raw, an unknown format or IQ order
+ * (PEBBLEGPU_E_INVALID); more samples than the capacity or not whole super-frames (PEBBLEGPU_E_SIZE).  pebblegpu_receiver_process_ingested
+ * and the multibank's raw calls make the same call per slot or shard (their buffers are allocations of the library's own) and refuse
+ * the same. */
 int pebblegpu_receiver_process_raw(pebblegpu_receiver *rx, int format, int iq_order, double gain, const void *d_raw, uint64_t n_samples);
 /* Host ingest through the library's own pinned buffers (the device plugins' producer side, e.g. the HackRF callback that fills
  * the producer/consumer ring, plugins/HackRFDevice/hackrfdevice.cpp:533-566, writes its raw samples straight into one): two slots,
@@ -332,7 +343,10 @@ int pebblegpu_receiver_map_zoom_spectrum(pebblegpu_receiver *rx, int32_t y_pixel
  * every call on one stream; set_profiling(rx, 1) does the same for as long as it is on. */
 int pebblegpu_receiver_last_ms(const pebblegpu_receiver *rx, int which, float *ms);
 /* name(s) of the kernel(s) behind group `which` (1..5) as the last process call ran them ("" when the group is empty): the
- * bench labels its per-kernel roofline lines with these */
+ * bench labels its per-kernel roofline lines with these.
+ * which = 6 is the input route of the last process call instead: "float2" (pebblegpu_receiver_process), "raw s8" / "raw u8" /
+ * "raw s16" / "raw f32" / "raw wav16" (a raw call whose first kernels converted that format in their own loads; the stream bank's
+ * tags), "k_normalize_iq" (a raw call staged through the conversion pass), "" before the first call.  A refused call leaves it alone. */
 const char *pebblegpu_receiver_kernel_name(const pebblegpu_receiver *rx, int which);
 /* which 0 and 1 are always available (two event records per call, three with a display transform; 1 reads 0 without one).  The per-kernel splits 2..5 need four more
  * records, each a ~5 us bubble in the stream, so they are recorded only after set_profiling(rx, 1). */
@@ -559,7 +573,9 @@ int pebblegpu_multibank_locate(const pebblegpu_multibank *mb, uint32_t channel, 
 /* Device-resident input: d_iq / d_raw is an array of n_shards device pointers; entry g is resident on shard g's device and holds what
  * that shard reads, as pebblegpu_receiver_process / _process_raw take it -- the whole stream for a shared stream (with {0, 0} both
  * entries may be the same pointer), the shard's rows [stream][time] for independent streams.  A host that keeps its samples on one
- * device distributes them itself.  The inputs are never modified and may be overwritten after pebblegpu_multibank_synchronize. */
+ * device distributes them itself.  The inputs are never modified and may be overwritten after pebblegpu_multibank_synchronize.
+ * Every d_raw entry must be aligned to PEBBLEGPU_RAW_ALIGN bytes, as for pebblegpu_receiver_process_raw; a misaligned one is refused
+ * (PEBBLEGPU_E_INVALID) before any shard is asked, so the multibank stays usable. */
 int pebblegpu_multibank_process(pebblegpu_multibank *mb, const void *const *d_iq, uint64_t n_samples);
 int pebblegpu_multibank_process_raw(pebblegpu_multibank *mb, int format, int iq_order, double gain,
                                     const void *const *d_raw, uint64_t n_samples);

@@ -907,8 +907,13 @@ class ReceiverBank:
         check(self.L, self.L.pebblegpu_receiver_process(self.h, C.c_void_p(dptr), int(n_samples)))
 
     def process_raw_device(self, dptr, n_samples, fmt, iq_order=0, gain=1.0):
-        """raw device-format IQ pairs (pebblegpu_iq_format) already on the device -> normalizeIQ + the full call"""
+        """raw device-format IQ pairs (pebblegpu_iq_format) already on the device, aligned to PEBBLEGPU_RAW_ALIGN (32) bytes: converted in the first
+        kernels' own loads where the call's shape allows it, through a normalizeIQ pass otherwise (input_route() says which)"""
         check(self.L, self.L.pebblegpu_receiver_process_raw(self.h, int(fmt), int(iq_order), float(gain), C.c_void_p(dptr), int(n_samples)))
+
+    def input_route(self):
+        """pebblegpu_receiver_kernel_name(rx, 6): "float2", "raw s8" .. "raw wav16" (converted in the loads), "k_normalize_iq" (staged)"""
+        return self.kernel_name(6)
 
     def ingest_buffer(self, slot, nbytes, dtype=np.int8):
         """the slot's pinned host buffer as a numpy array (valid until the slot is acquired again with a larger size)"""

@@ -290,6 +290,10 @@ int pebblegpu_multibank_process_raw(pebblegpu_multibank *mb, int format, int iq_
     if (!mb || !d_raw) return fail(PEBBLEGPU_E_INVALID, "null argument");
     for (uint32_t g = 0; g < mb->G; g++)
         if (!d_raw[g]) return fail(PEBBLEGPU_E_INVALID, "null input for shard %u", g);
+    // (the receivers refuse a misaligned pointer themselves; here, before any worker is asked, the refusal leaves every shard untouched)
+    for (uint32_t g = 0; g < mb->G; g++)
+        if (reinterpret_cast<uintptr_t>(d_raw[g]) % PEBBLEGPU_RAW_ALIGN)
+            return fail(PEBBLEGPU_E_INVALID, "d_raw of shard %u must be aligned to %d bytes", g, PEBBLEGPU_RAW_ALIGN);
     if (int rc = raw_checks(format, iq_order)) return rc;
     if (int rc = call_checks(mb, n_samples)) return rc;
     Job j;

@@ -2,6 +2,7 @@
 #pragma once
 #include <type_traits>
 #include "common.h"
+#include "raw_load.h"
 
 namespace pg {
 
@@ -153,15 +154,8 @@ struct RdsState {
     int pad_;
 };
 
-// A stream still in the device's own sample format (DeviceInterfaceBase::normalizeIQ, pebblelib/deviceinterfacebase.cpp:648-838, done
-// in the first loads of the kernels that take it instead of a separate pass): base == nullptr: the float2 pointer is the input.
-//   fmt 0 CPX8 int8 pairs, 1 CPXU8 (v - 128), 2 CPX16, 3 CPXFLOAT, 4 WAV PCM16; order 0 IQ, 1 QI, 2 I only, 3 Q only; scale includes the gain
-struct RawSrc {
-    const void *base;
-    int fmt, order;
-    float scale;
-    int pad_;
-};
+// A stream still in the device's own sample format (RawSrc), its scale and the loads that convert it: raw_load.h, which a plain C++
+// compiler accepts too
 
 // The raw sample format as a compile-time constant: f(std::integral_constant<int, F>) for the runtime fmt, so that one generic lambda
 // picks a kernel's instance per format (0..4: pebblegpu_iq_format; anything else takes 4's place).  with_sample_fmt also knows -1,
@@ -182,144 +176,6 @@ inline void with_sample_fmt(const RawSrc *raw, Fn &&f)
 {
     if (!raw) f(std::integral_constant<int, -1>{});
     else with_raw_fmt(raw->fmt, f);
-}
-
-// the format's constant folded into the gain (deviceinterfacebase.cpp:651,689,729; wavfile.cpp:299-300), rounded once to float
-inline float raw_scale(int fmt, double gain)
-{
-    double scale = gain;
-    if (fmt == 0 || fmt == 1) scale *= 1 / 128.0;
-    else if (fmt == 2) scale *= 1 / 32768.0;
-    else if (fmt == 4) scale *= 1 / 32767.0;
-    return (float)scale;
-}
-constexpr size_t kRawPairBytes[5] = {2, 2, 4, 8, 4};  // bytes per IQ pair: CPX8, CPXU8, CPX16, CPXFLOAT, WAV PCM16
-
-__device__ __forceinline__ float2 raw_load(const RawSrc &r, long long i)
-{
-    float a, b;
-    if (r.fmt == 0) {
-        const char2 v = reinterpret_cast<const char2 *>(r.base)[i];
-        a = (float)v.x; b = (float)v.y;
-    } else if (r.fmt == 1) {
-        const uchar2 v = reinterpret_cast<const uchar2 *>(r.base)[i];
-        a = (float)v.x - 128.0f; b = (float)v.y - 128.0f;
-    } else if (r.fmt == 2 || r.fmt == 4) {
-        const short2 v = reinterpret_cast<const short2 *>(r.base)[i];
-        a = (float)v.x; b = (float)v.y;
-    } else {
-        const float2 v = reinterpret_cast<const float2 *>(r.base)[i];
-        a = v.x; b = v.y;
-    }
-    a *= r.scale;
-    b *= r.scale;
-    return make_float2((r.order & 1) == 0 ? a : b, (r.order == 1 || r.order == 2) ? a : b);
-}
-
-// raw_load with the sample format a template constant, for kernels whose first use of a converted sample is an addition (the band-pass's
-// first butterfly): the product with the scale is rounded on its own (__fmul_rn is never contracted into a fused multiply-add), so
-// the sample is bit for bit what k_normalize_iq writes
-template <int FMT>
-__device__ __forceinline__ float2 raw_load1(const RawSrc &r, long long i)
-{
-    float a, b;
-    if (FMT == 0 || FMT == 1) {  // (the pair as ONE 2-byte load: char2 / uchar2 came out as two byte loads)
-        const unsigned w = reinterpret_cast<const unsigned short *>(r.base)[i];
-        a = FMT == 0 ? (float)((int)(w << 24) >> 24) : (float)(w & 0xFFu) - 128.0f;
-        b = FMT == 0 ? (float)((int)(w << 16) >> 24) : (float)(w >> 8) - 128.0f;
-    } else if (FMT == 2 || FMT == 4) {
-        const unsigned w = reinterpret_cast<const unsigned *>(r.base)[i];
-        a = (float)((int)(w << 16) >> 16);
-        b = (float)((int)w >> 16);
-    } else {
-        const float2 v = reinterpret_cast<const float2 *>(r.base)[i];
-        a = v.x; b = v.y;
-    }
-    a = __fmul_rn(a, r.scale);
-    b = __fmul_rn(b, r.scale);
-    return make_float2((r.order & 1) == 0 ? a : b, (r.order == 1 || r.order == 2) ? a : b);
-}
-
-// four consecutive samples i .. i + 3 (i a multiple of 4) in one or two wide loads: 8 bytes for the int8 formats, 16 for int16, 32 for float.
-// In two steps, so that a kernel can hold the words as they came (2, 4 or 8 registers) and convert where it uses the samples: a
-// conversion behind the load makes the compiler wait for the load there.
-template <int FMT>
-struct RawQuad {
-    uint4 a, b;  // 8-bit formats: a.x, a.y; 16-bit: a; float: a, b
-};
-template <int FMT>
-__device__ __forceinline__ void raw_fetch4(const RawSrc &r, long long i, RawQuad<FMT> &w)
-{
-    if (FMT == 0 || FMT == 1) {
-        const uint2 v = reinterpret_cast<const uint2 *>(r.base)[i >> 2];
-        w.a.x = v.x; w.a.y = v.y;
-    } else if (FMT == 2 || FMT == 4) {
-        w.a = reinterpret_cast<const uint4 *>(r.base)[i >> 2];
-    } else {
-        w.a = reinterpret_cast<const uint4 *>(r.base)[i >> 1];
-        w.b = reinterpret_cast<const uint4 *>(r.base)[(i >> 1) + 1];
-    }
-}
-template <int FMT>
-__device__ __forceinline__ void raw_convert4(const RawSrc &r, const RawQuad<FMT> &w, float2 (&o)[4])
-{
-    float v[8];
-    if (FMT == 0 || FMT == 1) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const unsigned word = k < 4 ? w.a.x : w.a.y;
-            const int sh = 8 * (k & 3);
-            v[k] = FMT == 0 ? (float)((int)(word << (24 - sh)) >> 24) : (float)((word >> sh) & 0xFFu) - 128.0f;
-        }
-    } else if (FMT == 2 || FMT == 4) {
-        const unsigned ww[4] = {w.a.x, w.a.y, w.a.z, w.a.w};
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = (float)((int)(ww[k >> 1] << (16 - 16 * (k & 1))) >> 16);
-    } else {
-        v[0] = __uint_as_float(w.a.x); v[1] = __uint_as_float(w.a.y); v[2] = __uint_as_float(w.a.z); v[3] = __uint_as_float(w.a.w);
-        v[4] = __uint_as_float(w.b.x); v[5] = __uint_as_float(w.b.y); v[6] = __uint_as_float(w.b.z); v[7] = __uint_as_float(w.b.w);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float a = v[2 * k] * r.scale, b = v[2 * k + 1] * r.scale;
-        o[k] = make_float2((r.order & 1) == 0 ? a : b, (r.order == 1 || r.order == 2) ? a : b);
-    }
-}
-template <int FMT>
-__device__ __forceinline__ void raw_load4(const RawSrc &r, long long i, float2 (&o)[4])
-{
-    RawQuad<FMT> w;
-    raw_fetch4<FMT>(r, i, w);
-    raw_convert4<FMT>(r, w, o);
-}
-
-template <int FMT>
-__device__ __forceinline__ void raw_load4_even(const RawSrc &r, long long i, float2 (&o)[4])
-{
-    float v[8];
-    if (FMT == 0 || FMT == 1) {
-        unsigned w[2];
-        __builtin_memcpy(w, reinterpret_cast<const unsigned char *>(r.base) + 2 * i, 8);
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const unsigned word = w[k >> 2];
-            const int sh = 8 * (k & 3);
-            v[k] = FMT == 0 ? (float)((int)(word << (24 - sh)) >> 24) : (float)((word >> sh) & 0xFFu) - 128.0f;
-        }
-    } else if (FMT == 2 || FMT == 4) {
-        unsigned w[4];
-        __builtin_memcpy(w, reinterpret_cast<const unsigned char *>(r.base) + 4 * i, 16);
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = (float)((int)(w[k >> 1] << (16 - 16 * (k & 1))) >> 16);
-    } else {
-        const float4 a = reinterpret_cast<const float4 *>(r.base)[i >> 1], b = reinterpret_cast<const float4 *>(r.base)[(i >> 1) + 1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float a = v[2 * k] * r.scale, b = v[2 * k + 1] * r.scale;
-        o[k] = make_float2((r.order & 1) == 0 ? a : b, (r.order == 1 || r.order == 2) ? a : b);
-    }
 }
 
 // Per-channel squelch gate of a bank (receiver.cpp:959-965 per channel): open[c * stride + j] != 0 <=> channel c's super-frame j of

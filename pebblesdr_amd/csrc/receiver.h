@@ -886,6 +886,8 @@ private:
     TestBenchCore tb_;
     bool last_tb_ = false;            // the last call ran the generator (kernel_name)
     bool last_tb_morse_ = false;      // ... with stations on: k_morsegen instead of k_testbench
+    int last_input_ = -2;             // the last call's input route (kernel_name(6)): -2 no call yet, -1 float2, 0..4 raw of that format
+                                      // converted in the kernels' loads, 5 raw staged through k_normalize_iq
     // taps: one buffer per enabled point (allocated when the point is first enabled), filled by a copy queued on the stream that has
     // just produced the signal; index = the point's number (PEBBLEGPU_TAP_*)
     static constexpr int kTapPoints = 17;

@@ -1061,6 +1061,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
     // them in (the same loader and scale as the conversion pass: the same values, and the recording needs no float2 copy of its own)
     c.rec_raw = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
     c.rec_from_raw = raw != nullptr && !tb_.any();
+    last_input_ = !raw ? -1 : c.rt.raw_fused ? (raw->fmt >= 0 && raw->fmt <= 4 ? raw->fmt : 4) : 5;
     if (int rc = join_and_apply(c)) return rc;
     if (int rc = stage_input(c)) return rc;
     if (int rc = start_call(c)) return rc;
@@ -1100,6 +1101,8 @@ int Receiver::process_raw(int fmt, int order, double gain, const void *d_raw, ui
     if (!d_raw || n == 0) return fail(PEBBLEGPU_E_INVALID, "null input or zero samples");
     if (fmt < 0 || fmt > 4 || order < 0 || order > 3) return fail(PEBBLEGPU_E_INVALID, "unknown sample format %d / IQ order %d", fmt, order);
     if (n > (uint64_t)max_sf * superframe) return fail(PEBBLEGPU_E_SIZE, "%llu samples exceed this object's capacity", (unsigned long long)n);
+    // (the converting loads read 8, 16 and 32 bytes at a time: raw_fetch4, raw_load4_even -- the stream bank's rule)
+    if (reinterpret_cast<uintptr_t>(d_raw) % PEBBLEGPU_RAW_ALIGN) return fail(PEBBLEGPU_E_INVALID, "d_raw must be aligned to %d bytes", PEBBLEGPU_RAW_ALIGN);
     const RawSrc raw{d_raw, fmt, order, raw_scale(fmt, gain), 0};
     return process(nullptr, n, bins != 0, true, &raw);
 }
@@ -1151,6 +1154,10 @@ const char *Receiver::kernel_name(int which) const
     case 3: return dec_.rest_name;
     case 4: return wfm ? "" : dec_.last_in_consumer ? "k_fastfir_t128 (mixing)" : ff_n == 2048 ? "k_fastfir_t128" : "k_fastfir";
     case 5: return wfm ? (wfmc_.fused ? "k_wfm_fir" : "k_iir_scan + k_discrim + k_fir_dec") : "k_anf/k_agc/k_iir_scan/k_pll_demod + k_fir_dec (listed channels only)";
+    case 6: {  // the input route of the last call; the format tags are the stream bank's
+        static const char *const kIn[8] = {"", "float2", "raw s8", "raw u8", "raw s16", "raw f32", "raw wav16", "k_normalize_iq"};
+        return kIn[last_input_ + 2];
+    }
     default: return "";
     }
 }

@@ -7,6 +7,7 @@ single product, and the band-pass's overlap carries converted samples.  One test
 import numpy as np
 import pytest
 
+from tests.raw_cases import FORMATS, GAIN, TAG, host_convert, make_raw  # noqa: F401  (the table module of the receiver's raw tests keeps them)
 from tests.signals import lcg_noise, tones
 
 pytestmark = pytest.mark.gpu
@@ -14,33 +15,6 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-5
 TOL_DB = 0.1
 N65 = 65536
-
-# pebblegpu_iq_format -> (numpy type of a component, offset, normaliser); deviceinterfacebase.cpp:651,689,729, wavfile.cpp:299-300
-FORMATS = {0: (np.int8, 0.0, 128.0), 1: (np.uint8, 128.0, 128.0), 2: (np.int16, 0.0, 32768.0), 3: (np.float32, 0.0, 1.0), 4: (np.int16, 0.0, 32767.0)}
-TAG = {0: "s8", 1: "u8", 2: "s16", 3: "f32", 4: "wav16"}
-# a gain per format; 0.5 where the normaliser is no power of two (the library forms gain * (1 / 32767.0) in double, the host
-# gain / 32767.0: equal for a power-of-two gain whatever the last bit of the reciprocal)
-GAIN = {0: 0.7, 1: 1.0, 2: 1.3, 3: 0.9, 4: 0.5}
-
-
-def make_raw(fmt, S, n, seed, fs=2.0e6):
-    """[S, n, 2] components of `fmt`: a few tones per stream plus noise, filling most of the format's range"""
-    dtype, off, norm = FORMATS[fmt]
-    rng = np.random.default_rng(seed)
-    sig = np.stack([tones(fs, n, [(0.4, 123456.7 * (c + 1)), (0.2, 20000.0 - 30000.0 * c), (0.1, 1700.0)]) for c in range(S)])
-    comp = np.stack([sig.real, sig.imag], axis=-1)
-    if dtype == np.float32:
-        return (comp + rng.uniform(-1e-3, 1e-3, comp.shape)).astype(np.float32)
-    return np.round(comp * (norm - 2) + off + rng.uniform(-1, 1, comp.shape)).astype(dtype)
-
-
-def host_convert(raw, fmt, order, gain):
-    """DeviceInterfaceBase::normalizeIQ on the host with the library's constants -> complex64 [..., n]"""
-    _, off, norm = FORMATS[fmt]
-    conv = (raw.astype(np.float32) - np.float32(off)) * np.float32(gain / norm)
-    i, q = conv[..., 0], conv[..., 1]
-    return {0: i + 1j * q, 1: q + 1j * i, 2: i + 1j * i, 3: q + 1j * q}[order].astype(np.complex64)
-
 
 def banks(P, S, frame, bins, F, n=2, fs=2.0e6):
     out = []
