@@ -3,6 +3,7 @@
 // to say which geometry each row of tests/bank_cases.py reaches.
 #pragma once
 #include <algorithm>
+#include "decim_route.h"
 
 namespace pg {
 
@@ -25,7 +26,7 @@ inline BankGeom bank_geometry(long long len_out, long long C, bool cic, int warm
     int waves = bank_waves;
     // (a receiver that runs two-stage calls keeps one wave per SIMD at every batch size: the previous call's band-pass needs the other
     // half of the register file beside it -- 0.2385 ms per configs[2] call of 32 super-frames against 0.2546, 0.875 against 0.905 at 128)
-    if (waves == 0) waves = (!has_fin2 && cdiv(len_out, 2 * std::max(1LL, 1024LL / g32)) >= 128) ? 2 : 1;
+    if (waves == 0) waves = (!has_fin2 && bank_long_call(len_out, C)) ? 2 : 1;
     if (waves > minw) waves = minw;  // (the instances with the longest halfbands need more than half a SIMD's registers)
     long long pairs_target = 1024LL * waves / g32;
     if (cic) pairs_target /= 2;  // (twelve pairs of lines per output instead of one window: the blocks are bound by what they fetch, and every chunk

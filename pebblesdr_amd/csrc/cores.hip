@@ -428,35 +428,28 @@ static size_t mixdec_lds_bytes(const FirTaps &t)
     return (size_t)(span + span / t.stride + 2) * sizeof(float2);
 }
 
-// ---- k_mix_dec_mfma's instantiations: fronts (4 pairs: hb11 x S; 12: a merged CIC3 in front of it) x the halfband triples the reference's ladder
-// puts behind them between 1 and 200 Msps (decimator.cpp:64-149) ----
+// ---- k_mix_dec_mfma's instantiations: one per entry of PG_BANK_DEC_INSTANCES (decim_route.h), in the list's order ----
 struct BankVariant {
-    int np, t1, t2, t3, hy, nstate, minw;
+    int np, t1, t2, t3;
     void *kern;
 };
 template <int NP, int T1, int T2, int T3, int MINW>
 static BankVariant bank_variant_of()
 {
-    using G = FusedDecGeom<T1, T2, T3>;
-    return BankVariant{NP, T1, T2, T3, G::HY, G::N1 + G::N2 + G::N3, MINW, (void *)k_mix_dec_mfma<NP, T1, T2, T3, 0, MINW>};
+    return BankVariant{NP, T1, T2, T3, (void *)k_mix_dec_mfma<NP, T1, T2, T3, 0, MINW>};
 }
 static const std::vector<BankVariant> &bank_variants()
 {
-    static const std::vector<BankVariant> v = {
-        bank_variant_of<4, 15, 19, 31, 2>(),  bank_variant_of<4, 15, 23, 43, 2>(),  bank_variant_of<4, 15, 23, 47, 2>(),  bank_variant_of<4, 15, 19, 35, 2>(),
-        bank_variant_of<4, 15, 27, 59, 2>(),  bank_variant_of<4, 19, 27, 59, 2>(),  // (227 / 231 registers since the main loop stopped copying its fetched samples: half a SIMD's file)
-        bank_variant_of<12, 15, 23, 47, 1>(), bank_variant_of<12, 15, 19, 35, 1>(), bank_variant_of<12, 15, 27, 59, 1>(),
-    };
+#define PG_X(NP, T1, T2, T3, MINW) bank_variant_of<NP, T1, T2, T3, MINW>(),
+    static const std::vector<BankVariant> v = {PG_BANK_DEC_INSTANCES(PG_X)};
+#undef PG_X
     return v;
 }
-bool bank_variant(int np, int t1, int t2, int t3, int *hy, int *nstate, int *minw)
+static void *bank_kernel(const DecimShape &s)
 {
     for (const BankVariant &b : bank_variants())
-        if (b.np == np && b.t1 == t1 && b.t2 == t2 && b.t3 == t3) {
-            *hy = b.hy; *nstate = b.nstate; *minw = b.minw;
-            return true;
-        }
-    return false;
+        if (b.np == s.bank_np && b.t1 == s.casc_ntaps[0] && b.t2 == s.casc_ntaps[1] && b.t3 == s.casc_ntaps[2]) return b.kern;
+    return nullptr;
 }
 
 template <int NP>
@@ -473,31 +466,29 @@ static int launch_bank(void *kern, unsigned n_wg, hipStream_t s, const float2 *d
 }
 
 // the call's decimator as one launch of k_mix_dec_mfma (the caller has checked the sizes)
-int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, bool had_state, const OscAdvance *oa, hipEvent_t done_event, DecimDone *done)
+int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, const OscAdvance *oa, hipEvent_t done_event, DecimDone *done)
 {
     const bool cic = fused_front;
-    const HistBuf &y0b = cic ? buf1 : buf0;
-    const int np = cic ? 12 : 4;
-    const BankVariant *bv = nullptr;
-    for (const BankVariant &b : bank_variants())
-        if (b.np == np && b.t1 == casc.ntaps[0] && b.t2 == casc.ntaps[1] && b.t3 == casc.ntaps[2]) bv = &b;
-    if (!bv) return fail(PEBBLEGPU_E_UNSUPPORTED, "no k_mix_dec_mfma instance for this chain");
+    const HistBuf &y0b = y0_buf();
+    void *kern = bank_kernel(*this);
+    if (!kern) return fail(PEBBLEGPU_E_UNSUPPORTED, "no k_mix_dec_mfma instance for this chain");
     const long long g32 = cdiv(C, 32);
-    const int warm = (bv->hy - 8) / 8;
+    const int warm = (fused_hy - 8) / 8;
+    const bool had_state = st.bank_state_valid;  // the previous call took this route: the halfbands' running sums are handed over
     // The first-stage outputs in front of the call's start (block 0 needs seven of them even with the running sums handed over; the whole
     // look-back without): from the stage-0 head-room when the previous call took another route, else straight from what the previous
     // launch staged (two staging buffers, written alternately: this launch's history waves write the other one)
-    const float2 *y0_hist = y0_pending ? (const float2 *)(d_y0stage2[y0_cur] + fused_hy) : (const float2 *)y0b.data();
-    const long long y0_hist_pitch = y0_pending ? (long long)fused_hy : y0b.pitch;
+    const float2 *y0_hist = st.y0_pending ? (const float2 *)(d_y0stage2[st.y0_cur] + fused_hy) : (const float2 *)y0b.data();
+    const long long y0_hist_pitch = st.y0_pending ? (long long)fused_hy : y0b.pitch;
     // the oscillators' advance rides on the launch when the caller handed it over (banks whose oscillators live on the device)
     const bool adv = tun.bank_osc_adv != 0 && oa != nullptr && oa->osc != nullptr && oa->osc_count == C;
     if (adv && !d_dyn[0]) {
         for (int i = 0; i < 2; i++) PG_TRY(d_dyn[i].alloc(C));
     }
-    if (osc.dyn_epoch != dyn_epoch_seen) dyn_valid = false;
-    dyn_epoch_seen = osc.dyn_epoch;
+    if (osc.dyn_epoch != st.dyn_epoch_seen) st.dyn_valid = false;
+    st.dyn_epoch_seen = osc.dyn_epoch;
     // waves per SIMD, outputs per chunk, chunk pairs and workgroups: bank_geom.h
-    const BankGeom geo = bank_geometry(len_out, C, cic, warm, bv->minw, fin2.base != nullptr, tun.bank_waves, tun.fused_l, tun.bank_hsplit);
+    const BankGeom geo = bank_geometry(len_out, C, cic, warm, bank_minw, fin2.base != nullptr, tun.bank_waves, tun.fused_l, tun.bank_hsplit);
     const long long L = geo.L;
     const int S0 = first.stride, Sfs = cic ? S0 * wide_stride : S0;  // input samples per first-stage (hb11) output
     const int hist_split = tun.bank_hsplit;
@@ -520,17 +511,17 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
         bp.gain = casc.gain;  // (the first stage's own gain is 1 in a chain of several stages)
         bp.hist_split = hist_split;
         bp.cic_s0 = cic ? S0 : 0;
-        bp.state_in = had_state ? d_bank_state[bank_state_parity] : nullptr;
-        bp.state_out = d_bank_state[bank_state_parity ^ 1];
+        bp.state_in = had_state ? d_bank_state[st.bank_state_parity] : nullptr;
+        bp.state_out = d_bank_state[st.bank_state_parity ^ 1];
         bp.clk = tun.bank_clk ? d_clk : nullptr;
-        bp.dyn_in = adv && dyn_valid ? d_dyn[dyn_parity] : nullptr;
-        bp.dyn_out = adv ? d_dyn[dyn_parity ^ 1] : nullptr;
+        bp.dyn_in = adv && st.dyn_valid ? d_dyn[st.dyn_parity] : nullptr;
+        bp.dyn_out = adv ? d_dyn[st.dyn_parity ^ 1] : nullptr;
         bp.osc_rw = adv ? oa->osc : nullptr;
         bp.adv = adv ? oa->adv : nullptr;
         bp.adv_n = adv ? oa->adv_n : 0;
     };
-    const float2 *xh = d_xhist[hist_parity];
-    float2 *xh_out = d_xhist[hist_parity ^ 1], *mixed = d_hist_mixed[hist_parity ^ 1];
+    const float2 *xh = d_xhist[st.hist_parity];
+    float2 *xh_out = d_xhist[st.hist_parity ^ 1], *mixed = d_hist_mixed[st.hist_parity ^ 1];
     if (!cic) {
         BankDecParams<4> bp;
         memset(&bp, 0, sizeof(bp));
@@ -545,7 +536,7 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
             bp.e[p] = (float)kE[p];
             bp.g[p] = p == 0 ? 0.5f * bank_taps.h[5] : bank_taps.h[5 + kE[p]];
         }
-        if (int rc = launch_bank<4>(bv->kern, n_wg, s, d_in, fin.data(), (const ChanOsc *)osc.d_osc, osc.inline_dyn, xh, xh_out, y0_hist, d_y0stage2[y0_cur ^ 1], mixed, bp, done_event)) return rc;
+        if (int rc = launch_bank<4>(kern, n_wg, s, d_in, fin.data(), (const ChanOsc *)osc.d_osc, osc.inline_dyn, xh, xh_out, y0_hist, d_y0stage2[st.y0_cur ^ 1], mixed, bp, done_event)) return rc;
     } else {
         // CIC3 at stride S0 in the reference's merged form (decimator.cpp:719-737: output k = .125 (od_k + ev_{k-1} + 3 (od_{k-1} + ev_k)) of the
         // sample pairs (ev, od)_P = x[S0 P], x[S0 P + 1]) under the hb11 at stride 16: relative to sample S j, pair q = -11 .. 0 carries
@@ -564,23 +555,19 @@ int DecimCore::run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, con
             bp.oa[2 * i + 1] = S0 * (-11 - q);  bp.ob[2 * i + 1] = S0 * q + 1;  bp.g[2 * i + 1] = (h(q + 10) + 3.f * h(q + 11)) * 0.125f;
         }
         for (int p = 0; p < 12; p++) bp.e[p] = 0.5f * (float)(bp.oa[p] - bp.ob[p]);
-        if (int rc = launch_bank<12>(bv->kern, n_wg, s, d_in, fin.data(), (const ChanOsc *)osc.d_osc, osc.inline_dyn, xh, xh_out, y0_hist, d_y0stage2[y0_cur ^ 1], mixed, bp, done_event)) return rc;
+        if (int rc = launch_bank<12>(kern, n_wg, s, d_in, fin.data(), (const ChanOsc *)osc.d_osc, osc.inline_dyn, xh, xh_out, y0_hist, d_y0stage2[st.y0_cur ^ 1], mixed, bp, done_event)) return rc;
     }
     done->done_recorded = done_event != nullptr;
     if (tun.bank_clk) { if (int rc = report_clk(s, n_wg, L)) return rc; }
-    hist_parity ^= 1;
-    bank_state_parity ^= 1;
-    bank_state_valid = true;
-    front_name = "k_mix_dec_mfma";
-    rest_name = "";
-    last_fused = true;
-    last_mfma = true;
-    y0_cur ^= 1;
-    y0_pending = true;
+    st.hist_parity ^= 1;
+    st.bank_state_parity ^= 1;
+    st.bank_state_valid = true;
+    st.y0_cur ^= 1;
+    st.y0_pending = true;
     // (with dyn_in the launch advanced the device blocks too; without, the caller's tail launch does and the next call finds dyn_out current)
-    done->osc_advanced = adv && dyn_valid;
-    if (adv) dyn_parity ^= 1;
-    dyn_valid = adv;
+    done->osc_advanced = adv && st.dyn_valid;
+    if (adv) st.dyn_parity ^= 1;
+    st.dyn_valid = adv;
     return 0;
 }
 
@@ -628,11 +615,11 @@ int DecimCore::report_clk(hipStream_t s, unsigned n_wg, long long L)
 // without the halfbands' running sums look for it.  Not needed between two such launches: queued only when a call wants it.
 int DecimCore::flush_y0(hipStream_t s)
 {
-    if (!y0_pending) return 0;
-    const HistBuf &y0b = fused_front ? buf1 : buf0;
+    if (!st.y0_pending) return 0;
+    const HistBuf &y0b = y0_buf();
     std::vector<TailJob> jobs;
-    jobs.push_back(TailJob{d_y0stage2[y0_cur], (long long)fused_hy, (long long)fused_hy, fused_hy, 0, y0b.base + (y0b.hist - fused_hy), y0b.pitch});
-    y0_pending = false;
+    jobs.push_back(TailJob{d_y0stage2[st.y0_cur], (long long)fused_hy, (long long)fused_hy, fused_hy, 0, y0b.base + (y0b.hist - fused_hy), y0b.pitch});
+    st.y0_pending = false;
     return run_save_tails(s, jobs, C, nullptr);
 }
 
@@ -641,115 +628,68 @@ int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in,
     release();
     tun = t;
     chain = c;
-    C = channels;
     const size_t ns = chain.stages.size();
-    if (ns == 0) {
+    if (ns > (size_t)kMaxCascade + 1) return fail(PEBBLEGPU_E_UNSUPPORTED, "decimation chain has %zu stages; at most %d are built", ns, kMaxCascade + 1);
+    DecimStageDesc sd[kMaxCascade + 1];
+    for (size_t k = 0; k < ns; k++) sd[k] = DecimStageDesc{chain.stages[k].ntaps, (int)chain.stages[k].stride};
+    DecimTuningFacts tf;
+    tf.no_fused_dec = tun.no_fused_dec;
+    tf.bank_dec = tun.bank_dec != 0;
+    static_cast<DecimShape &>(*this) = plan_decim_shape(sd, (int)ns, channels, tf);
+    if (total != (long long)chain.total) return fail(PEBBLEGPU_E_INVALID, "the chain's decimation %u is not the product of its strides %lld", chain.total, total);
+    memset(&first, 0, sizeof(first));
+    memset(&casc, 0, sizeof(casc));
+    first.stride = first_stride;
+    first.gain = ns <= 1 ? last_gain : 1.f;
+    if (zero_stage) {
         // "No decimation, just return" (decimator.cpp:155-160): the mixer alone, into the row the consumer reads (its look-back in front)
-        zero_stage = true;
-        memset(&first, 0, sizeof(first));
-        first.stride = 1;
-        first.gain = last_gain;
-        memset(&casc, 0, sizeof(casc));
         ovl_len = last_hist;
         return buf0.alloc((int)C, last_hist, max_in);
     }
-    if (ns - 1 > (size_t)kMaxCascade) return fail(PEBBLEGPU_E_UNSUPPORTED, "decimation chain has %zu stages; at most %d are built", ns, kMaxCascade + 1);
     const design::Stage &s0 = chain.stages[0];
-    memset(&first, 0, sizeof(first));
     first.ntaps = s0.ntaps;
-    first.stride = (int)s0.stride;
-    first.cic3 = s0.ntaps == 0;
-    first.gain = ns == 1 ? last_gain : 1.f;
+    first.cic3 = first_cic3;
     for (int p = 0; p < s0.ntaps; p++) first.h[p] = (float)design::halfband_taps(s0.design)[p];
     if (mixdec_lds_bytes(first) > 150 * 1024) return fail(PEBBLEGPU_E_UNSUPPORTED, "first-stage stride %u too wide for the LDS tile", s0.stride);
-    // banks of >= 16 channels behind an hb11 first stage mix in registers when their input is one shared stream
-    bank_front = !first.cic3 && first.ntaps == kFrontT1 && (C >= 16 || C == 1);
     memset(&bank_taps, 0, sizeof(bank_taps));
     bank_taps.stride = first.stride;
     for (int p = 0; p < kFrontT1 && p < first.ntaps; p++) bank_taps.h[p] = first.h[p];
-    // a wide second stage is peeled off the fused cascade (see receiver.h)
-    wide = ns >= 3 && chain.stages[1].stride >= 8 && chain.stages[1].ntaps > 0;
-    size_t kfirst = 1;
-    if (wide) {
+    if (wide) {  // a wide second stage is peeled off the fused cascade (see DecimShape)
         const design::Stage &w = chain.stages[1];
-        wide_taps = w.ntaps;
-        wide_stride = (int)w.stride;
         std::vector<float> wt(kMaxTaps, 0.f);
         for (int p = 0; p < w.ntaps; p++) wt[p] = (float)design::halfband_taps(w.design)[p];
         PG_TRY(d_wide_taps.upload(wt.data(), kMaxTaps));
-        kfirst = 2;
-        fused_front = first.cic3 != 0 && w.ntaps == kFrontT1;  // k_mix_cic_hb is built for the hb11 the ladder always picks here
         memset(&wide_fir, 0, sizeof(wide_fir));
         wide_fir.stride = (int)w.stride;
         for (int p = 0; p < w.ntaps && p < kFrontT1; p++) wide_fir.h[p] = wt[p];
     }
     // the fused later stages
-    memset(&casc, 0, sizeof(casc));
-    casc.nst = (int)(ns - kfirst);
+    casc.nst = nst;
     casc.gain = last_gain;
-    long long halo0 = 0, prod = 1, later = 1;
-    for (size_t k = kfirst; k < ns; k++) {
-        const design::Stage &st = chain.stages[k];
-        casc.ntaps[k - kfirst] = st.ntaps;
-        casc.stride[k - kfirst] = (int)st.stride;
-        for (int p = 0; p < st.ntaps; p++) casc.h[k - kfirst][p] = (float)design::halfband_taps(st.design)[p];
-        halo0 += (long long)(st.ntaps - 1) * prod;  // look-back of the whole cascade, in stage-0 output samples
-        prod *= st.stride;
-        later *= st.stride;
+    casc.outb = outb;
+    casc.lds_half = lds_half;
+    for (int k = 0; k < nst; k++) {
+        const design::Stage &stg = chain.stages[ns - nst + k];
+        casc.ntaps[k] = stg.ntaps;
+        casc.stride[k] = (int)stg.stride;
+        for (int p = 0; p < stg.ntaps; p++) casc.h[k][p] = (float)design::halfband_taps(stg.design)[p];
     }
-    if (casc.nst > 0) {
-        // largest power-of-two tile of final outputs whose two ping-pong buffers fit comfortably (<= 48 KiB)
-        const long long lds_cap = 48LL * 1024;
-        int outb = 256;
-        for (;; outb /= 2) {
-            long long c0 = outb, c1 = 0;
-            for (int k = casc.nst; k >= 1; k--) {
-                c1 = c0;
-                c0 = c0 * casc.stride[k - 1] + casc.ntaps[k - 1] - 1;
-            }
-            // c0 = stage-0 samples a tile reads, c1 = outputs of the first fused stage (the largest intermediate)
-            if ((c0 + c1) * (long long)sizeof(float2) <= lds_cap || outb == 1) {
-                casc.outb = outb;
-                casc.lds_half = (int)c0;
-                casc_lds_bytes = (size_t)(c0 + c1) * sizeof(float2);
-                break;
-            }
+    if (casc_lds_bytes > 150 * 1024) return fail(PEBBLEGPU_E_UNSUPPORTED, "decimation cascade does not fit LDS");
+    if (one_kernel()) {  // the histories of the one-kernel routes (DecimShape::fused_all, bank_mfma)
+        if (fused_all) {
+            fused_p = new FusedDecParams();
+            memset(fused_p, 0, sizeof(*fused_p));
+            fused_p->S = first.stride;
+            fused_p->n_chan = (int)C;
+            fused_p->hist_pitch = kMaxTaps;
+            fused_p->gain0 = first.gain;
+            fused_p->gain = casc.gain;
         }
-        if (casc_lds_bytes > 150 * 1024) return fail(PEBBLEGPU_E_UNSUPPORTED, "decimation cascade does not fit LDS");
-    }
-    // the whole decimator in one kernel for banks off one shared stream: k_mix_dec_mfma for every chain of the form [cic3 x S0,] hb11 x S,
-    // three halfbands at stride 2 whose tap counts are in its table (bank_variant); k_mix_dec_fused<15, 19, 31>, its predecessor, for
-    // hb11 x S, hb15, hb19, hb31 (PEBBLEGPU_BANK_DEC=0)
-    {
-        using FG = FusedDecGeom<15, 19, 31>;
-        const bool off = tun.no_fused_dec;
-        const bool three2 = casc.nst == 3 && casc.stride[0] == 2 && casc.stride[1] == 2 && casc.stride[2] == 2;
-        const bool hb_front = bank_front && C >= 16 && !wide && first.stride <= 16;
-        const bool cic_front = fused_front && C >= 16 && wide_stride == 16;
-        fused_all = hb_front && three2 && casc.ntaps[0] == 15 && casc.ntaps[1] == 19 && casc.ntaps[2] == 31 && !off;
-        bank_mfma = false;
-        if (three2 && (hb_front || cic_front) && !off && tun.bank_dec)
-            bank_mfma = bank_variant(cic_front ? 12 : 4, casc.ntaps[0], casc.ntaps[1], casc.ntaps[2], &fused_hy, &bank_nstate, &bank_minw);
-        if (fused_all && !bank_mfma) fused_hy = FG::HY;
-        if (fused_all || bank_mfma) {
-            if (halo0 < fused_hy) halo0 = fused_hy;  // the first-stage buffer's head-room doubles as these kernels' first-stage history
-            xh_depth = cic_front ? 512 : 16;         // raw samples in front of a call that its first windows reach (11 S0 + 1 with a CIC3 in front)
-            if (fused_all) {
-                fused_p = new FusedDecParams();
-                memset(fused_p, 0, sizeof(*fused_p));
-                fused_p->S = first.stride;
-                fused_p->n_chan = (int)C;
-                fused_p->hist_pitch = kMaxTaps;
-                fused_p->gain0 = first.gain;
-                fused_p->gain = casc.gain;
-            }
-            for (int i = 0; i < 2; i++) PG_TRY(d_xhist[i].alloc_zero(xh_depth));
-            for (int i = 0; i < 2; i++) PG_TRY(d_y0stage2[i].alloc_zero((size_t)fused_hy * C + 64));  // (64 entries of slack: the kernel requests a block ahead of what it uses)
-            d_y0stage = d_y0stage2[0];
-            if (bank_mfma) {
-                for (int i = 0; i < 2; i++) PG_TRY(d_bank_state[i].alloc_zero((size_t)bank_nstate * C));
-            }
-            bank_state_valid = false;
+        for (int i = 0; i < 2; i++) PG_TRY(d_xhist[i].alloc_zero(xh_depth));
+        for (int i = 0; i < 2; i++) PG_TRY(d_y0stage2[i].alloc_zero((size_t)fused_hy * C + 64));  // (64 entries of slack: the kernel requests a block ahead of what it uses)
+        d_y0stage = d_y0stage2[0];
+        if (bank_mfma) {
+            for (int i = 0; i < 2; i++) PG_TRY(d_bank_state[i].alloc_zero((size_t)bank_nstate * C));
         }
     }
     const long long len0 = max_in / s0.stride;
@@ -772,13 +712,13 @@ int DecimCore::init(uint32_t channels, const design::Chain &c, long long max_in,
     }
     return 0;
 }
+// everything init() derived and every field one call hands to the next go back to their defaults with the buffers
 void DecimCore::release()
 {
     delete fused_p;
     fused_p = nullptr;
-    zero_stage = false;
-    ovl_pending = last_in_consumer = false;
-    ovl_parity = 0;
+    static_cast<DecimShape &>(*this) = DecimShape{};
+    st = Carried{};
     d_y0stage = nullptr;
     for (int i = 0; i < 2; i++) {
         d_ovl[i].release();
@@ -824,8 +764,8 @@ int DecimCore::fill_dec_fuse(hipStream_t s, DecFuse *df, const OscBank &osc, lon
     memset(df, 0, sizeof(*df));
     df->y = fin.data();
     df->y0_tail = buf0.data() + (len0 - 256);
-    df->xtail = d_xtail_w[xtail_parity];
-    df->xtail_next = d_xtail_w[xtail_parity ^ 1];
+    df->xtail = d_xtail_w[st.xtail_parity];
+    df->xtail_next = d_xtail_w[st.xtail_parity ^ 1];
     const ChanOsc &o = osc.h_osc[0];
     df->phase0 = osc.inline_dyn.use ? osc.inline_dyn.d[0].phase0 : osc.ctl[0].phase0;
     df->inc = o.inc;
@@ -871,24 +811,147 @@ static __global__ __launch_bounds__(256) void k_window_tail(const float2 *__rest
     const float2 v = raw.base ? raw_load(raw, src) : in[src];
     out[i] = cscale(v, window[i]);
 }
+static RawSrc raw_or_none(const RawSrc *raw) { return raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0}; }
+// LDS of the kernels plan_channel_lanes() lays out: one transposing tile per wave unless a lane holds one channel's outputs only
+static size_t lanes_lds_bytes(const DecimRoute &r) { return r.cl_log2 ? 4 * (size_t)front_tile_slots(r.cl_log2, r.R) * sizeof(float2) : 0; }
+
+// Two workgroups of the general register front beside a kernel that computes a call's inner outputs (k_mix_hb11_lean, the display
+// transform): the first outputs, whose windows reach back into the mixed history, and the call's own mixed history
+int DecimCore::run_edges(const Launch &l, int R)
+{
+    const long long j_first = (10 + first.stride - 1) / first.stride;
+    launch(l.raw ? k_mix_hb11_bank<false, false, true> : k_mix_hb11_bank<false, false, false>, dim3(len0 / (4LL * R * 64) != 0 ? 2 : 1, 1), dim3(256), l.s, l.in, l.in_pitch,
+           (int)l.shared_input, buf0.data(), buf0.pitch, len0, (const ChanOsc *)l.osc.d_osc, (const float2 *)d_hist_mixed[st.hist_parity], d_hist_mixed[st.hist_parity ^ 1],
+           (int)kMaxTaps, (const float *)l.osc.d_amp, l.osc.a_inf, bank_taps, first.gain, l.osc.inline_dyn, 0, (int)C, R, j_first, raw_or_none(l.raw));
+    return 0;
+}
 int DecimCore::run_beside_spectrum(hipStream_t s, const float2 *d_in, long long in_pitch, bool shared_input, long long n, const OscBank &osc, const RawSrc *raw)
 {
     // (fill_dec_fuse has set the lengths.)  The general kernels keep the mixed samples of the call's end as their history: left by the
     // same two-workgroup launch that serves k_mix_hb11_lean, so the next call may take either route
-    const int R = 8;
-    const long long j_first = (10 + first.stride - 1) / first.stride;
-    const RawSrc rs = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
-    launch(raw ? k_mix_hb11_bank<false, false, true> : k_mix_hb11_bank<false, false, false>, dim3(len0 / (4LL * R * 64) != 0 ? 2 : 1, 1), dim3(256), s, d_in, in_pitch,
-           (int)shared_input, buf0.data(), buf0.pitch, len0, (const ChanOsc *)osc.d_osc, (const float2 *)d_hist_mixed[hist_parity], d_hist_mixed[hist_parity ^ 1],
-           (int)kMaxTaps, (const float *)osc.d_amp, osc.a_inf, bank_taps, first.gain, osc.inline_dyn, 0, (int)C, R, j_first, rs);
+    if (int rc = run_edges(Launch{s, d_in, in_pitch, shared_input, n, osc, raw}, 8)) return rc;
     PG_HIP(hipGetLastError());
-    hist_parity ^= 1;
-    xtail_parity ^= 1;  // the transform's last workgroup writes the next call's look-back
-    last_fused = false;
-    front_name = "k_spectrum_t128 (decimator inside)";
-    rest_name = "";
+    st.hist_parity ^= 1;
+    st.xtail_parity ^= 1;  // the transform's last workgroup writes the next call's look-back
+    st.last = DecimRoute{};
+    st.last.front = DecimFront::InSpectrum;
     return 0;
 }
+// An empty chain whose consumer mixes: nothing to launch, the consumer reads the stream.  Its block 0 looks back at the previous call's
+// mixed samples -- its own row, or the head-room a k_mixer call's tail job refreshed
+int DecimCore::run_in_consumer(const DecimRoute &r)
+{
+    if (!mix_in_consumer_ready()) return fail(PEBBLEGPU_E_INVALID, "the consumer's overlap rows were not enabled");
+    mix_tail.tail = r.ovl_from_row ? d_ovl[st.ovl_parity] : buf0.base + (buf0.hist - ovl_len);
+    mix_tail.tail_pitch = r.ovl_from_row ? (long long)ovl_len : buf0.pitch;
+    mix_tail.tail_out = d_ovl[st.ovl_parity ^ 1];
+    st.ovl_parity ^= 1;
+    return 0;
+}
+int DecimCore::run_mixer_only(const Launch &l, const DecimRoute &r)
+{
+    if (r.ovl_from_row) {  // the first k_mixer call behind calls that mixed in the band-pass: their overlap row becomes the head-room
+        std::vector<TailJob> jobs;
+        jobs.push_back(TailJob{d_ovl[st.ovl_parity], (long long)ovl_len, (long long)ovl_len, ovl_len, 0, buf0.base + (buf0.hist - ovl_len), buf0.pitch});
+        if (int rc = run_save_tails(l.s, jobs, C, nullptr)) return rc;
+    }
+    launch(k_mixer, dim3(r.grid_x, r.grid_y), dim3(256), l.s, l.in, l.in_pitch, (int)l.shared_input, buf0.data(), buf0.pitch, l.n, (const ChanOsc *)l.osc.d_osc,
+           (const float *)l.osc.d_amp, l.osc.a_inf, l.osc.inline_dyn);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+int DecimCore::run_fused(const Launch &l, const DecimRoute &r)
+{
+    long long L = tun.fused_l > 0 ? tun.fused_l : ((len_out * r.grid_y / 704 + 15) & ~15LL);  // ~700 four-wave workgroups (measured best on 256 CUs: 96 for configs[2]); every chunk pays a 21-block warm-up
+    if (L < 32) L = 32;
+    fused_p->n_out = len_out;
+    fused_p->out_pitch = fin.pitch;
+    fused_p->y0_pitch = buf0.pitch;
+    fused_p->L = (int)L;
+    fused_p->a_inf = l.osc.a_inf;
+    launch(k_mix_dec_fused<15, 19, 31>, dim3(cdiv(len_out, L), r.grid_y), dim3(256), l.s, l.in, fin.data(), (const ChanOsc *)l.osc.d_osc, l.osc.inline_dyn,
+           (const float2 *)d_xhist[st.hist_parity], d_xhist[st.hist_parity ^ 1], (const float2 *)buf0.data(), d_y0stage, d_hist_mixed[st.hist_parity ^ 1], *fused_p);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+int DecimCore::run_cic_hb(const Launch &l, const DecimRoute &r)
+{
+    auto kern = r.transient ? (r.uniform ? k_mix_cic_hb<true, true> : k_mix_cic_hb<true, false>) : (r.uniform ? k_mix_cic_hb<false, true> : k_mix_cic_hb<false, false>);
+    launch_lds(kern, dim3(r.grid_x, r.grid_y), dim3(256), lanes_lds_bytes(r), l.s, l.in, l.in_pitch, (int)l.shared_input, buf1.data(), buf1.pitch,
+               len1, (const ChanOsc *)l.osc.d_osc, (const float2 *)d_hist_mixed[st.hist_parity], d_hist_mixed[st.hist_parity ^ 1], (int)kMaxTaps,
+               (const float *)l.osc.d_amp, l.osc.a_inf, wide_fir, first.stride, 1.0f, l.osc.inline_dyn, r.cl_log2, (int)C, r.R);
+    return 0;
+}
+int DecimCore::run_lean(const Launch &l, const DecimRoute &r)
+{
+    const long long j_first = (10 + first.stride - 1) / first.stride;
+    auto lean = r.raw_fmt < 0 ? k_mix_hb11_lean<-1> : r.raw_fmt == 0 ? k_mix_hb11_lean<0> : r.raw_fmt == 1 ? k_mix_hb11_lean<1> : r.raw_fmt == 2 ? k_mix_hb11_lean<2>
+                             : r.raw_fmt == 3 ? k_mix_hb11_lean<3> : k_mix_hb11_lean<4>;
+    launch(lean, dim3(r.grid_x), dim3(256), l.s, l.in, buf0.data(), len0, (const ChanOsc *)l.osc.d_osc, l.osc.a_inf, bank_taps, first.gain, l.osc.inline_dyn, r.R,
+           r.edge_launch ? -j_first : j_first, raw_or_none(l.raw), (const float2 *)d_hist_mixed[st.hist_parity], d_hist_mixed[st.hist_parity ^ 1]);
+    return r.edge_launch ? run_edges(l, r.R) : 0;  // (A/B: the edges as a launch of their own)
+}
+int DecimCore::run_hb11_bank(const Launch &l, const DecimRoute &r)
+{
+    auto kern = r.transient ? (r.uniform ? k_mix_hb11_bank<true, true> : k_mix_hb11_bank<true, false>)
+                            : (r.uniform ? k_mix_hb11_bank<false, true> : k_mix_hb11_bank<false, false>);
+    launch_lds(kern, dim3(r.grid_x, r.grid_y), dim3(256), lanes_lds_bytes(r), l.s, l.in, l.in_pitch, (int)l.shared_input, buf0.data(),
+               buf0.pitch, len0, (const ChanOsc *)l.osc.d_osc, (const float2 *)d_hist_mixed[st.hist_parity], d_hist_mixed[st.hist_parity ^ 1], (int)kMaxTaps,
+               (const float *)l.osc.d_amp, l.osc.a_inf, bank_taps, first.gain, l.osc.inline_dyn, r.cl_log2, (int)C, r.R, -1LL, RawSrc{nullptr, 0, 0, 0.f, 0});
+    return 0;
+}
+int DecimCore::run_dec1(const Launch &l, const DecimRoute &r)
+{
+    size_t lds = mixdec_lds_bytes(first);
+    if (r.cg > 1 && lds < (size_t)r.cg * 258 * sizeof(float4)) lds = (size_t)r.cg * 258 * sizeof(float4);
+    launch_lds(k_mix_dec1, dim3(r.grid_x, r.grid_y), dim3(256), lds, l.s, l.in, l.in_pitch, (int)l.shared_input, buf0.data(),
+               buf0.pitch, len0, (const ChanOsc *)l.osc.d_osc, (const float2 *)d_hist_mixed[st.hist_parity], (int)kMaxTaps, (const float *)l.osc.d_amp,
+               l.osc.a_inf, first, d_hist_mixed[st.hist_parity ^ 1], l.osc.inline_dyn, r.cg, (int)C);  // its last block leaves the next call's mixed history
+    return 0;
+}
+// the stages behind a general front: the peeled wide stage from buf0 into buf1, the fused cascade into fin
+int DecimCore::run_rest(const Launch &l, const DecimRoute &r)
+{
+    if (r.fir_dec())
+        launch(k_fir_dec, dim3(cdiv(len1, 256), C), dim3(256), l.s, (const float2 *)buf0.data(), buf0.pitch, buf1.data(), buf1.pitch, len1, wide_stride,
+               (const float *)d_wide_taps, (const float *)nullptr, 0, (const int *)nullptr, wide_taps, 1.0f, 0, (const int *)nullptr, Gate{nullptr, 0, 0});
+    if (r.cascade()) {
+        const HistBuf &src = wide ? buf1 : buf0;
+        // (this ladder, not a conditional expression: the compiler emits the three in the order they are first named, and so does the
+        // order of the launchers in this file for every other instance -- reordering either moves the kernels inside the code object)
+        auto kern = k_cascade<0, 0, 0>;
+        if (r.cascade_inst == 1) kern = k_cascade<15, 23, 47>;
+        else if (r.cascade_inst == 2) kern = k_cascade<15, 19, 31>;
+        launch_lds(kern, dim3(r.tiles, C), dim3(256), casc_lds_bytes, l.s, (const float2 *)src.data(), src.pitch, fin.data(), fin.pitch, len_out, casc);
+    }
+    return 0;
+}
+int DecimCore::hand_over(const Launch &l)
+{
+    if (one_kernel() && l.shared_input && l.n >= xh_depth)  // the next call may take a one-kernel route: it wants this call's raw tail (hist_parity already flipped)
+        PG_HIP(hipMemcpyAsync(d_xhist[st.hist_parity], l.in + (l.n - xh_depth), sizeof(float2) * xh_depth, hipMemcpyDeviceToDevice, l.s));
+    if (fuse_window && l.n >= 2048 && shape_for_spectrum()) {  // the next call's decimator may run inside the display transform
+        launch(k_window_tail, dim3(8), dim3(256), l.s, l.in, l.n, fuse_window, d_xtail_w[st.xtail_parity ^ 1], raw_or_none(l.raw));
+        st.xtail_parity ^= 1;
+    }
+    return 0;
+}
+DecimCallFacts DecimCore::call_facts(const Launch &l, const DecimCall &call) const
+{
+    DecimCallFacts f;
+    f.n = l.n;
+    f.shared_input = l.shared_input;
+    f.transient = l.osc.any_transient();
+    f.lds_free = call.lds_free;
+    f.raw_fmt = l.raw ? l.raw->fmt : -1;
+    f.mix_in_consumer = call.mix_in_consumer;
+    f.in_aligned = (reinterpret_cast<uintptr_t>(l.in) & 7) == 0;
+    f.out_pitch = fin.pitch;
+    f.lean_edge_launch = tun.lean_edge_launch;
+    f.ovl_pending = st.ovl_pending;
+    return f;
+}
+// refusals, the route (decim_route.h), its launcher, what it hands to the next call
 int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool shared_input, long long n, const OscBank &osc,
                    hipEvent_t after_first, const RawSrc *raw, const OscAdvance *oa, DecimCall call, DecimDone *done)
 {
@@ -898,179 +961,54 @@ int DecimCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, bool s
     if (raw && !raw_ready(osc, call.lds_free)) return fail(PEBBLEGPU_E_INVALID, "raw-format input reached a decimator path that has no converting loads");
     if (n <= 0 || n % (long long)chain.total != 0)
         return fail(PEBBLEGPU_E_SIZE, "%lld samples is not a multiple of the decimation %u", n, chain.total);
-    len0 = n / first.stride;
-    if (zero_stage) {
-        if (n > buf0.cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
-        last_in_consumer = call.mix_in_consumer;
-        if (call.mix_in_consumer) {
-            if (!mix_in_consumer_ready()) return fail(PEBBLEGPU_E_INVALID, "the consumer's overlap rows were not enabled");
-            // nothing to launch: the consumer reads the stream.  Its block 0 looks back at the previous call's mixed samples -- its own
-            // row, or the head-room a k_mixer call's tail job refreshed
-            mix_tail.tail = ovl_pending ? d_ovl[ovl_parity] : buf0.base + (buf0.hist - ovl_len);
-            mix_tail.tail_pitch = ovl_pending ? (long long)ovl_len : buf0.pitch;
-            mix_tail.tail_out = d_ovl[ovl_parity ^ 1];
-            ovl_parity ^= 1;
-            ovl_pending = true;
-            len_out = n;
-            front_name = "k_fastfir_t128 (mixing)";
-            rest_name = "";
-            if (after_first) PG_HIP(hipEventRecord(after_first, s));
-            return 0;
-        }
-        if (ovl_pending) {  // the first k_mixer call behind calls that mixed in the band-pass: their overlap row becomes the head-room
-            std::vector<TailJob> jobs;
-            jobs.push_back(TailJob{d_ovl[ovl_parity], (long long)ovl_len, (long long)ovl_len, ovl_len, 0, buf0.base + (buf0.hist - ovl_len), buf0.pitch});
-            if (int rc = run_save_tails(s, jobs, C, nullptr)) return rc;
-            ovl_pending = false;
-        }
-        launch(k_mixer, dim3(cdiv(n, 1024), C), dim3(256), s, d_in, in_pitch, (int)shared_input, buf0.data(), buf0.pitch, n, (const ChanOsc *)osc.d_osc,
-               (const float *)osc.d_amp, osc.a_inf, osc.inline_dyn);
-        PG_HIP(hipGetLastError());
-        len_out = n;
-        front_name = "k_mixer";
-        rest_name = "";
-        if (after_first) PG_HIP(hipEventRecord(after_first, s));
-        return 0;
-    }
+    // (the buffer at the hb11's rate, or the only one: the first the call writes, and the one whose head-room the one-kernel routes keep)
+    if (n / ((long long)first.stride * (fused_front ? wide_stride : 1)) > y0_buf().cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
     // successive calls write successive output buffers (tail_job_out carries the consumer's look-back into the next one's head-room)
     if (fin3.base && call.rotate3) { std::swap(fin, fin2); std::swap(fin2, fin3); }  // (fin, fin2, fin3) <- (fin2, fin3, fin)
     else if (fin2.base) std::swap(fin, fin2);  // (either way the call writes what was fin2, whose head-room the last call's consumer filled)
-    const HistBuf *src = &buf0;
-    last_fused = false;
-    last_mfma = false;
-    const bool had_bank_state = bank_state_valid;
-    bank_state_valid = false;  // (set again below when this call takes the matrix-pipe route)
-    const bool had_dyn = dyn_valid;
-    dyn_valid = false;
-    if ((fused_all || bank_mfma) && shared_input && !osc.any_transient()) {
-        const HistBuf &y0b = fused_front ? buf1 : buf0;  // the first-stage (hb11) outputs' buffer of the other route: its head-room is the history
-        if (n / ((long long)first.stride * (fused_front ? wide_stride : 1)) > y0b.cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
-        len_out = n / (long long)chain.total;
-        const long long groups = cdiv(C, 64);
-        if (bank_mfma && (unsigned long long)n * 8 < 0xFFF00000ull && (unsigned long long)C * (unsigned long long)fin.pitch * 8 < 0xFFF00000ull &&
-            len_out >= 64 && (reinterpret_cast<uintptr_t>(d_in) & 7) == 0) {  // (its sample fetches and result stores carry 32-bit byte offsets)
-            dyn_valid = had_dyn;
-            if (int rc = run_bank_mfma(s, d_in, n, osc, had_bank_state, oa, call.done_event, done)) return rc;
-            if (after_first) PG_HIP(hipEventRecord(after_first, s));
-            return 0;
-        }
-      if (int rc = flush_y0(s)) return rc;
-      if (fused_all) {
-        long long L = tun.fused_l > 0 ? tun.fused_l : ((len_out * groups / 704 + 15) & ~15LL);  // ~700 four-wave workgroups (measured best on 256 CUs: 96 for configs[2]); every chunk pays a 21-block warm-up
-        if (L < 32) L = 32;
-        fused_p->n_out = len_out;
-        fused_p->out_pitch = fin.pitch;
-        fused_p->y0_pitch = buf0.pitch;
-        fused_p->L = (int)L;
-        fused_p->a_inf = osc.a_inf;
-        launch(k_mix_dec_fused<15, 19, 31>, dim3(cdiv(len_out, L), (unsigned)groups), dim3(256), s, d_in, fin.data(), (const ChanOsc *)osc.d_osc, osc.inline_dyn,
-               (const float2 *)d_xhist[hist_parity], d_xhist[hist_parity ^ 1], (const float2 *)buf0.data(), d_y0stage, d_hist_mixed[hist_parity ^ 1], *fused_p);
-        PG_HIP(hipGetLastError());
-        hist_parity ^= 1;
-        front_name = "k_mix_dec_fused";
-        rest_name = "";
-        last_fused = true;
-        if (after_first) PG_HIP(hipEventRecord(after_first, s));
-        return 0;
-      }
+    const Launch l{s, d_in, in_pitch, shared_input, n, osc, raw};
+    const DecimRoute r = plan_decim_route(*this, call_facts(l, call));
+    len0 = r.len0;
+    len1 = r.len1;
+    len_out = r.len_out;
+    if (r.front != DecimFront::BankMfma) {
+        // the running sums and the oscillator fields k_mix_dec_mfma hands from call to call end here; its staged first-stage history
+        // goes where every other route looks for it
+        st.bank_state_valid = st.dyn_valid = false;
+        if (int rc = flush_y0(s)) return rc;
     }
-    if (int rc = flush_y0(s)) return rc;
-    if (fused_front) {
-        len1 = len0 / wide_stride;
-        if (len1 > buf1.cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
-        int cl_log2 = 0;
-        while ((1u << cl_log2) < C && cl_log2 < 6) cl_log2++;  // channels across the lanes of a wave; the other lanes take further outputs
-        const int R = cl_log2 == 6 ? 16 : 8;                      // outputs per lane: a channel's R*OL outputs leave the wave as one row segment
-        const dim3 grid(cdiv(len1 + 1, 4LL * R * (64 >> cl_log2)), cdiv(C, 1u << cl_log2));
-        const bool uni = cl_log2 == 6 && shared_input;  // the lanes of a wave share one window: scalar loads
-        auto kern = osc.any_transient() ? (uni ? k_mix_cic_hb<true, true> : k_mix_cic_hb<true, false>) : (uni ? k_mix_cic_hb<false, true> : k_mix_cic_hb<false, false>);
-        launch_lds(kern, grid, dim3(256), cl_log2 ? 4 * (size_t)front_tile_slots(cl_log2, R) * sizeof(float2) : 0, s, d_in, in_pitch, (int)shared_input, buf1.data(), buf1.pitch,
-                   len1, (const ChanOsc *)osc.d_osc, (const float2 *)d_hist_mixed[hist_parity], d_hist_mixed[hist_parity ^ 1], (int)kMaxTaps,
-                   (const float *)osc.d_amp, osc.a_inf, wide_fir, first.stride, 1.0f, osc.inline_dyn, cl_log2, (int)C, R);
-        hist_parity ^= 1;
-        front_name = "k_mix_cic_hb";
-        if (after_first) PG_HIP(hipEventRecord(after_first, s));
-        len_out = len1;
-        src = &buf1;
-    } else {
-        if (len0 > buf0.cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
-        if (bank_front && C == 1 && call.lds_free && !osc.any_transient()) {
-            // beside the spectrum kernel: the lean one-channel kernel for every output inside the call, and the general one
-            // (a handful of lanes) for the first outputs, whose windows reach back into the mixed history, and the new history
-            const int R = 8;
-            const long long j_first = (10 + first.stride - 1) / first.stride;
-            const RawSrc rs = raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0};
-            auto lean = !raw ? k_mix_hb11_lean<-1> : rs.fmt == 0 ? k_mix_hb11_lean<0> : rs.fmt == 1 ? k_mix_hb11_lean<1> : rs.fmt == 2 ? k_mix_hb11_lean<2>
-                             : rs.fmt == 3 ? k_mix_hb11_lean<3> : k_mix_hb11_lean<4>;
-            const bool edge_launch = tun.lean_edge_launch;  // A/B: the edges as a launch of their own
-            launch(lean, dim3(cdiv(len0, 4LL * R * 64) + (edge_launch ? 0 : 1)), dim3(256), s, d_in, buf0.data(), len0, (const ChanOsc *)osc.d_osc,
-                   osc.a_inf, bank_taps, first.gain, osc.inline_dyn, R, edge_launch ? -j_first : j_first, rs, (const float2 *)d_hist_mixed[hist_parity],
-                   d_hist_mixed[hist_parity ^ 1]);
-            front_name = "k_mix_hb11_lean";
-            if (edge_launch)
-                launch(raw ? k_mix_hb11_bank<false, false, true> : k_mix_hb11_bank<false, false, false>, dim3(len0 / (4LL * R * 64) != 0 ? 2 : 1, 1), dim3(256), s, d_in, in_pitch,
-                       (int)shared_input, buf0.data(), buf0.pitch, len0, (const ChanOsc *)osc.d_osc, (const float2 *)d_hist_mixed[hist_parity], d_hist_mixed[hist_parity ^ 1],
-                       (int)kMaxTaps, (const float *)osc.d_amp, osc.a_inf, bank_taps, first.gain, osc.inline_dyn, 0, (int)C, R, j_first, rs);
-        } else if (bank_front && (C >= 16 ? shared_input : call.lds_free)) {
- // a bank off one shared stream: lanes = channels, windows in registers (k_mix_hb11_bank)
-            int cl_log2 = 0;
-            while ((1u << cl_log2) < C && cl_log2 < 6) cl_log2++;
-            const int R = cl_log2 == 6 ? 16 : 8;
-            const dim3 grid(cdiv(len0 + 1, 4LL * R * (64 >> cl_log2)), cdiv(C, 1u << cl_log2));
-            const bool uni = cl_log2 == 6;
-            auto kern = osc.any_transient() ? (uni ? k_mix_hb11_bank<true, true> : k_mix_hb11_bank<true, false>)
-                                            : (uni ? k_mix_hb11_bank<false, true> : k_mix_hb11_bank<false, false>);
-            launch_lds(kern, grid, dim3(256), cl_log2 ? 4 * (size_t)front_tile_slots(cl_log2, R) * sizeof(float2) : 0, s, d_in, in_pitch, (int)shared_input, buf0.data(),
-                       buf0.pitch, len0, (const ChanOsc *)osc.d_osc, (const float2 *)d_hist_mixed[hist_parity], d_hist_mixed[hist_parity ^ 1], (int)kMaxTaps,
-                       (const float *)osc.d_amp, osc.a_inf, bank_taps, first.gain, osc.inline_dyn, cl_log2, (int)C, R, -1LL, RawSrc{nullptr, 0, 0, 0.f, 0});
-            front_name = "k_mix_hb11_bank";
-        } else {
-        // merged CIC3 over a shared stream: one workgroup mixes a group of channels from one fetch of the sample pairs
-        const int cg = (first.cic3 && first.stride > 2 && shared_input) ? 8 : 1;
-        size_t lds = mixdec_lds_bytes(first);
-        if (cg > 1 && lds < (size_t)cg * 258 * sizeof(float4)) lds = (size_t)cg * 258 * sizeof(float4);
-        launch_lds(k_mix_dec1, dim3(cdiv(len0, 256), cdiv(C, cg)), dim3(256), lds, s, d_in, in_pitch, (int)shared_input, buf0.data(),
-                   buf0.pitch, len0, (const ChanOsc *)osc.d_osc, (const float2 *)d_hist_mixed[hist_parity], (int)kMaxTaps, (const float *)osc.d_amp,
-                   osc.a_inf, first, d_hist_mixed[hist_parity ^ 1], osc.inline_dyn, cg, (int)C);  // its last block leaves the next call's mixed history
-        front_name = "k_mix_dec1";
-        }
-        hist_parity ^= 1;
-        if (after_first) PG_HIP(hipEventRecord(after_first, s));
-        len_out = len0;
-        if (wide) {  // the peeled stride->=8 stage: every output reads its own taps-long window straight from buf0
-            len1 = len0 / wide_stride;
-            launch(k_fir_dec, dim3(cdiv(len1, 256), C), dim3(256), s, (const float2 *)buf0.data(), buf0.pitch, buf1.data(), buf1.pitch, len1, wide_stride,
-                   (const float *)d_wide_taps, (const float *)nullptr, 0, (const int *)nullptr, wide_taps, 1.0f, 0, (const int *)nullptr, Gate{nullptr, 0, 0});
-            src = &buf1;
-        }
+    int rc = 0;
+    switch (r.front) {
+    case DecimFront::InConsumer: rc = run_in_consumer(r); break;
+    case DecimFront::Mixer: rc = run_mixer_only(l, r); break;
+    case DecimFront::BankMfma: rc = run_bank_mfma(s, d_in, n, osc, oa, call.done_event, done); break;
+    case DecimFront::Fused: rc = run_fused(l, r); break;
+    case DecimFront::CicHb: rc = run_cic_hb(l, r); break;
+    case DecimFront::Lean: rc = run_lean(l, r); break;
+    case DecimFront::Hb11Bank: rc = run_hb11_bank(l, r); break;
+    case DecimFront::Dec1: rc = run_dec1(l, r); break;
+    case DecimFront::None: case DecimFront::InSpectrum: break;  // (never planned)
     }
-    rest_name = wide && !fused_front ? "k_fir_dec" : "";
-    if (casc.nst > 0) {
-        rest_name = wide && !fused_front ? "k_fir_dec + k_cascade" : "k_cascade";
-        len_out = n / (long long)chain.total;
-        const bool three2 = casc.nst == 3 && casc.stride[0] == 2 && casc.stride[1] == 2 && casc.stride[2] == 2;
-        auto kern = k_cascade<0, 0, 0>;
-        if (three2 && casc.ntaps[0] == 15 && casc.ntaps[1] == 23 && casc.ntaps[2] == 47) kern = k_cascade<15, 23, 47>;  // WFM from 20 Msps, narrow from 100 Msps
-        else if (three2 && casc.ntaps[0] == 15 && casc.ntaps[1] == 19 && casc.ntaps[2] == 31) kern = k_cascade<15, 19, 31>;  // narrow at 2.048 Msps
-        launch_lds(kern, dim3(cdiv(len_out, casc.outb), C), dim3(256), casc_lds_bytes, s, (const float2 *)src->data(), src->pitch, fin.data(),
-                   fin.pitch, len_out, casc);
+    if (rc) {
+        st.bank_state_valid = st.dyn_valid = false;
+        return rc;
     }
+    st.last = r;
+    st.ovl_pending = r.ovl_pending;
+    if (r.front == DecimFront::Fused || r.general()) st.hist_parity ^= 1;  // (k_mix_dec_mfma's launcher turns its own parities)
+    if (after_first) PG_HIP(hipEventRecord(after_first, s));
+    if (!r.general()) return 0;
+    if (int rc2 = run_rest(l, r)) return rc2;
     PG_HIP(hipGetLastError());
-    if ((fused_all || bank_mfma) && shared_input && n >= xh_depth)  // the next call may take a one-kernel route: it wants this call's raw tail (hist_parity already flipped)
-        PG_HIP(hipMemcpyAsync(d_xhist[hist_parity], d_in + (n - xh_depth), sizeof(float2) * xh_depth, hipMemcpyDeviceToDevice, s));
-    if (fuse_window && n >= 2048 && shape_for_spectrum()) {  // the next call's decimator may run inside the display transform
-        launch(k_window_tail, dim3(8), dim3(256), s, d_in, n, fuse_window, d_xtail_w[xtail_parity ^ 1], raw ? *raw : RawSrc{nullptr, 0, 0, 0.f, 0});
-        xtail_parity ^= 1;
-    }
-    return 0;
+    return hand_over(l);
 }
 void DecimCore::tail_jobs_dec(std::vector<TailJob> &jobs) const
 {
-    if (last_fused) {
+    if (st.last.one_kernel()) {
         // the call's last first-stage outputs (staged by the kernel) become the stage-0 head-room, as if the buffer had been written
         // (behind k_mix_dec_mfma only when a later call asks for them there: flush_y0)
-        const HistBuf &y0b = fused_front ? buf1 : buf0;
-        if (!last_mfma) jobs.push_back(TailJob{d_y0stage, (long long)fused_hy, (long long)fused_hy, fused_hy, 0, y0b.base + (y0b.hist - fused_hy), y0b.pitch});
+        const HistBuf &y0b = y0_buf();
+        if (st.last.front == DecimFront::Fused) jobs.push_back(TailJob{d_y0stage, (long long)fused_hy, (long long)fused_hy, fused_hy, 0, y0b.base + (y0b.hist - fused_hy), y0b.pitch});
         return;
     }
     if (!fused_front && buf0.hist > 0 && casc.nst > 0) jobs.push_back(TailJob{buf0.data(), buf0.pitch, len0, buf0.hist, 0, nullptr, 0});
@@ -1079,7 +1017,7 @@ void DecimCore::tail_jobs_dec(std::vector<TailJob> &jobs) const
 void DecimCore::tail_job_out(std::vector<TailJob> &jobs) const
 {
     if (casc.nst == 0) {  // a single stage (or none: the mixer's row): its buffer is the output
-        if (last_in_consumer) return;  // (the consumer mixed in its own loads and kept its overlap itself: buf0 was not written)
+        if (last_in_consumer()) return;  // (the consumer mixed in its own loads and kept its overlap itself: buf0 was not written)
         if (!fused_front && buf0.hist > 0) jobs.push_back(TailJob{buf0.data(), buf0.pitch, len0, buf0.hist, 0, nullptr, 0});
         return;
     }

@@ -68,16 +68,7 @@ struct FusedDecParams {
     float a_inf, gain0, gain; // oscillator amplitude, first-stage gain (1), gain on the final output
 };
 
-// HY: depth of the first-stage history a call leaves (and chunk 0 reads) = 8 * warm + 8
-template <int T1, int T2, int T3>
-struct FusedDecGeom {
-    static constexpr int halo = (T1 - 1) + 2 * (T2 - 1) + 4 * (T3 - 1);
-    static constexpr int warm = halo / 8;
-    static constexpr int HY = 8 * warm + 8;
-    // running sums per stage: pending outputs at a block's start plus the ones its inputs start
-    static constexpr int N1 = (T1 + 1) / 2 + 3, N2 = (T2 + 1) / 2 + 1, N3 = (T3 + 1) / 2;
-    static_assert(T1 % 4 == 3 && T2 % 4 == 3 && T3 % 4 == 3, "halfbands have 4k + 3 taps (odd centre)");
-};
+// (FusedDecGeom<T1, T2, T3>, the history depth HY and the running sums per stage: decim_route.h)
 
 // x_hist: [>= 16] raw input samples preceding the call (x[-16 .. -1]); xh_out receives the call's last 16.
 // y0_hist: data pointer of the stage-0 history rows: y0_hist[c * y0_pitch - HY .. -1] = previous call's last HY first-stage outputs.

@@ -2,6 +2,7 @@
 #pragma once
 #include <type_traits>
 #include "common.h"
+#include "decim_route.h"
 #include "raw_load.h"
 
 namespace pg {
@@ -30,11 +31,9 @@ struct FirTaps {
 };
 
 // the wide hb11 stage behind a merged CIC3, as kernel arguments of k_mix_cic_hb
-constexpr int kFrontT1 = 11;
 struct FrontTaps { float h[kFrontT1]; int stride; };
 
 // later decimation stages fused in one kernel (k_cascade): taps live in the kernel-argument segment
-constexpr int kMaxCascade = 6;
 struct CascadeParams {
     int nst, outb;            // fused stages, final outputs per workgroup
     int lds_half, pad_;       // float2 slots of the first ping-pong buffer

@@ -9,7 +9,8 @@
 //   SpectrumCore<- FFT::fftSpectrum            (pebblelib/fft.cpp)
 // Receiver composes them the way Receiver::processIQData does; the stand-alone steps (steps.hip) wrap one
 // core each behind the reference's per-class call shapes.  What one call asks of a core travels in that call's arguments
-// (DecimCall / DecimDone, AmCore::run's defer_tail); the route of a Receiver call is planned once, in call_route.h.
+// (DecimCall / DecimDone, AmCore::run's defer_tail); the route of a Receiver call is planned once, in call_route.h, and the kernels of
+// a DecimCore::run call in decim_route.h (both plain C++ that the CPU tier compiles).
 #pragma once
 #include <algorithm>
 #include <complex>
@@ -18,6 +19,7 @@
 #include "../../include/pebblegpu.h"
 #include "call_route.h"
 #include "common.h"
+#include "decim_route.h"
 #include "devmem.h"
 #include "design.h"
 #include "egress.h"
@@ -108,8 +110,6 @@ struct OscBank {
 };
 
 // ---- Mixer + Decimator ----
-bool bank_variant(int np, int t1, int t2, int t3, int *hy, int *nstate, int *minw);  // a k_mix_dec_mfma instance exists for this front and triple
-
 // what one DecimCore::run call is asked for, and what it reports back
 struct DecimCall {
     bool lds_free = false;            // the first kernel should leave LDS alone (it runs beside the display transform)
@@ -122,70 +122,41 @@ struct DecimDone {
     bool done_recorded = false;       // DecimCall::done_event was completed (else the caller records it)
 };
 
-struct DecimCore {
+// ---- shape: DecimShape (decim_route.h), what init derives from the chain -- C, zero_stage, bank_front, wide, fused_front, fused_all,
+// bank_mfma, fused_hy, xh_depth ... -- assigned whole by init() and release() ----
+struct DecimCore : DecimShape {
     design::Chain chain;
-    uint32_t C = 0;
+    Tuning tun;                      // the owner's switches (init)
+
+    // ---- buffers and tap values ----
     FirTaps first;                   // stage 0 (fused with the mixer)
     CascadeParams casc;              // stages 1.. (one fused kernel)
-    size_t casc_lds_bytes = 0;
     HistBuf buf0, fin;               // stage-0 output (head-room = look-back of its reader), final output (absent for 1-stage chains)
-    // A second stage with a stride >= 8 (merged halfbands at high input rates) would make the fused cascade's tiles mostly
-    // halo: it runs as its own strided FIR (k_fir_dec) from buf0 into buf1, and the fused rest reads buf1.
-    bool wide = false;
-    bool fused_front = false;        // merged CIC3 + wide halfband in one kernel (k_mix_cic_hb): nothing is written at the CIC rate
+    HistBuf buf1;                    // the wide stage's output (DecimShape::wide)
+    const HistBuf &y0_buf() const { return fused_front ? buf1 : buf0; }  // the first-stage (hb11) outputs' buffer: its head-room is the one-kernel routes' history
     FrontTaps wide_fir;              // the wide stage's taps as kernel arguments (fused_front)
-    bool bank_front = false;         // hb11 first stage in registers (k_mix_hb11_bank): a >= 16-channel bank off a shared stream, or one channel when asked
-    // An empty chain (no halfband design fits the rate: 48 kHz narrow, WFM below 500 kHz): run() is the stand-alone mixer (k_mixer) into
-    // buf0, which is then out() -- head-room = the consumer's look-back, refreshed by tail_job_out() like a single stage's.  No first
-    // stage means no register front, no raw-converting loads, no decimator inside the transform and no second output buffer.
-    bool zero_stage = false;
-    bool front_is_lds_free() const { return zero_stage || (C == 1 && (fused_front || bank_front)); }
-    // ... and its consumer may mix in its own loads (DecimCall::mix_in_consumer; k_fastfir_t128_mix): run() then launches nothing and
+    DevBuf<float> d_wide_taps;
+    FrontTaps bank_taps;
+    // An empty chain whose consumer may mix in its own loads (DecimCall::mix_in_consumer; k_fastfir_t128_mix): run() then launches nothing and
     // hands out where block 0's overlap of MIXED samples lies and where the consumer's last block leaves the next call's (mix_tail).
     // Hand-over between the two routes, in both directions, at the switch only: such a call behind a k_mixer call reads its overlap
     // straight from buf0's head-room (that call's tail job has refreshed it); a k_mixer call behind such a call first copies the
     // consumer's row into the head-room (ovl_pending).
-    struct MixTail { const float2 *tail = nullptr; long long tail_pitch = 0; float2 *tail_out = nullptr; };
-    MixTail mix_tail;                              // of the last run() with DecimCall::mix_in_consumer
     DevBuf<float2> d_ovl[2];                       // [C][ovl_len] the consumer's overlap rows, written by alternate calls
-    int ovl_len = 0, ovl_parity = 0;
-    bool ovl_pending = false;                      // d_ovl[ovl_parity] is newer than buf0's head-room
-    bool last_in_consumer = false;                 // the last run() left the mixing to the consumer: buf0 was not written
-    int enable_mix_in_consumer();                  // after init(), zero-stage only: allocates the rows (last_hist samples each)
-    bool mix_in_consumer_ready() const { return d_ovl[0].get() != nullptr; }
-    FrontTaps bank_taps;
-    // the whole decimator in one kernel (k_mix_dec_fused): a >= 16-channel bank off one shared stream whose chain is hb11 x S
-    // followed by hb15, hb19, hb31; calls inside an oscillator transient take the two-kernel route (both keep each other's history)
-    bool fused_all = false, last_fused = false;
-    struct FusedDecParams *fused_p = nullptr;   // host copy of the kernel's parameter block
-    DevBuf<float2> d_xhist[2];                  // [16] raw input tail of the previous call, ping-pong with hist_parity
+    int ovl_len = 0;
+    struct FusedDecParams *fused_p = nullptr;   // host copy of k_mix_dec_fused's parameter block
+    DevBuf<float2> d_xhist[2];                  // [xh_depth] raw input tail of the previous call, ping-pong with hist_parity
     float2 *d_y0stage = nullptr;                // a view of d_y0stage2[.]: [C][HY] the call's last first-stage outputs, copied into buf0's head-room by the tail refresh (k_mix_dec_fused: = d_y0stage2[0])
     DevBuf<float2> d_y0stage2[2];               // k_mix_dec_mfma stages them alternately and reads the previous launch's directly (y0_cur: the one written last)
-    int y0_cur = 0;
-    int fused_hy = 0;
-    // the same chain with its first stage on the matrix pipe, one wave per (32 channels, two chunks): k_mix_dec_mfma (kernels_bank_dec.h),
-    // the default route of such a bank; PEBBLEGPU_BANK_DEC=0 keeps the four-wave pipeline above
-    bool bank_mfma = false;
-    int bank_nstate = 0, bank_minw = 2;          // running sums per channel of the chain's instance; waves per SIMD it admits
-    int run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, bool had_state, const OscAdvance *oa, hipEvent_t done_event, DecimDone *done);
-    int xh_depth = 16;                           // samples of raw-input tail kept in d_xhist
-    DevBuf<float2> d_bank_state[2];                // [C][38] the halfbands' running sums where the last k_mix_dec_mfma call ended (ping-pong)
-    int bank_state_parity = 0;
-    bool bank_state_valid = false;               // the previous call took that route (else the next one warms up from the first-stage history)
-    int wide_taps = 0, wide_stride = 1;
-    DevBuf<float> d_wide_taps;
-    HistBuf buf1;
-    long long len1 = 0;
-    long long len0 = 0, len_out = 0; // lengths produced by the last run
-    const char *front_name = "";     // the kernel the last run() used for the mixer + first stage (bench / profiling labels)
-    const char *rest_name = "";      // ... and for the remaining stages
-    DevBuf<float2> d_hist_mixed[2];                // [C][kMaxTaps]: mixed-sample history of stage 0 (read one, write the other)
+    DevBuf<float2> d_bank_state[2];             // [C][38] the halfbands' running sums where the last k_mix_dec_mfma call ended (ping-pong)
+    DevBuf<OscDyn> d_dyn[2];                    // [C] the oscillators' per-call fields as k_mix_dec_mfma hands them from call to call (ping-pong)
+    DevBuf<float2> d_hist_mixed[2];             // [C][kMaxTaps]: mixed-sample history of stage 0 (read one, write the other)
+    DevBuf<unsigned long long> d_clk;           // Tuning::bank_clk: the waves' clock counts of the last k_mix_dec_mfma launch
     // One channel through hb11 x 8, hb15, hb23, hb47 beside an 8192-bin display transform: k_spectrum_t128<.., DEC> computes the whole
     // decimator from the frames it holds in LDS (DecFuse, kernels_spectrum.h).  Its look-back is the previous call's last frame, kept
     // WINDOWED (the transform's workgroups park windowed frames): written by that kernel, or by k_window_tail behind a call that took
     // the general kernels, so either route can follow the other.
     DevBuf<float2> d_xtail_w[2];                   // [2048] ping-pong
-    int xtail_parity = 0;
     const float *fuse_window = nullptr;            // a view of the display transform's window, SpectrumCore::d_window (set by the owner; nullptr: never fused)
     DevBuf<float2> d_c0tab;                        // [7][256] first-stage taps over that window times the oscillator's step per tap (DecFuse::c0tab)
     std::vector<float> h_r0;                       // ... the real part of it: h0[d] / w[n]
@@ -194,6 +165,44 @@ struct DecimCore {
     double c0_inc = 0;
     int c0_mix = 0;
     DevBuf<float2> d_ph_scratch;                   // DecFuse::ph_scratch (grows)
+    // Two output buffers, written by alternate calls, so that whatever reads a call's output (the band-pass) may run on another stream
+    // beside the NEXT call's decimator: the consumer's look-back (the head-room) is carried from the buffer just written into the other
+    // one's head-room.  tail_jobs() = tail_jobs_dec() (the decimator's own histories: its stream) + tail_job_out() (the consumer's stream)
+    HistBuf fin2, fin3;                      // fin: this call's; fin2: the next call's (its head-room filled by this call's consumer); fin3: a third, written by the call after that,
+                                             // so that a call's decimator waits for the consumer of the call THREE back (long over) instead of two (often still running)
+
+    // ---- what one call hands to the next: reset whole by release() ----
+    struct Carried {
+        int hist_parity = 0;           // d_xhist / d_hist_mixed: read [p], write [p ^ 1]
+        int y0_cur = 0;                // the d_y0stage2 written last
+        bool y0_pending = false;       // d_y0stage holds first-stage history the stage-0 head-room has not received yet (copied when a call needs it there)
+        int bank_state_parity = 0;
+        bool bank_state_valid = false; // the previous call took the k_mix_dec_mfma route (else the next one warms up from the first-stage history)
+        int dyn_parity = 0;
+        bool dyn_valid = false;        // d_dyn[dyn_parity] holds this call's fields (the previous call was such a launch and nothing was uploaded since)
+        uint64_t dyn_epoch_seen = 0;
+        int ovl_parity = 0;
+        bool ovl_pending = false;      // d_ovl[ovl_parity] is newer than buf0's head-room
+        int xtail_parity = 0;
+        DecimRoute last;               // the route of the last run() (run_beside_spectrum: DecimFront::InSpectrum)
+    } st;
+    bool last_in_consumer() const { return st.last.front == DecimFront::InConsumer; }  // the last run() left the mixing to the consumer: buf0 was not written
+    const char *front_name() const { return st.last.front_name(); }  // the kernel the last run() used for the mixer + first stage (bench / profiling labels)
+    const char *rest_name() const { return st.last.rest_name(); }    // ... and for the remaining stages
+
+    // ---- what the last call produced ----
+    long long len0 = 0, len1 = 0, len_out = 0;     // lengths produced by the last run
+    struct MixTail { const float2 *tail = nullptr; long long tail_pitch = 0; float2 *tail_out = nullptr; };
+    MixTail mix_tail;                              // of the last run() with DecimCall::mix_in_consumer
+
+    // ---- API ----
+    // last_hist: head-room of the final buffer (what the consumer looks back at); last_gain: folded into the final stage
+    int init(uint32_t channels, const design::Chain &c, long long max_in, int last_hist, float last_gain, const Tuning &t);
+    void release();
+    int enable_mix_in_consumer();                  // after init(), zero-stage only: allocates the consumer's overlap rows (last_hist samples each)
+    bool mix_in_consumer_ready() const { return d_ovl[0].get() != nullptr; }
+    int enable_double_out();                 // after init(); fails for a single-stage chain (its output is the first stage's buffer)
+    bool double_out() const { return fin2.base.get() != nullptr; }
     int set_fuse_window(const float *d_window, const std::vector<float> &w);  // the owner's display transform uses this window
     bool shape_for_spectrum() const;               // the chain is the one the kernel is built for
     bool fuse_shape() const { return shape_for_spectrum() && fuse_window; }  // ... and the owner's transform has handed over its window
@@ -203,42 +212,37 @@ struct DecimCore {
     int fill_dec_fuse(hipStream_t s, DecFuse *df, const OscBank &osc, long long n);
     // what is left for the chain's stream in such a call: the mixed-sample history for a later general call (two workgroups)
     int run_beside_spectrum(hipStream_t s, const float2 *d_in, long long in_pitch, bool shared_input, long long n, const OscBank &osc, const RawSrc *raw);
-    int hist_parity = 0;
-    // last_hist: head-room of the final buffer (what the consumer looks back at); last_gain: folded into the final stage
-    Tuning tun;                              // the owner's switches (init)
-    DevBuf<unsigned long long> d_clk;        // Tuning::bank_clk: the waves' clock counts of the last k_mix_dec_mfma launch
-    int report_clk(hipStream_t s, unsigned n_wg, long long L);  // waits for the launch, prints its clock counts on stderr
-    int init(uint32_t channels, const design::Chain &c, long long max_in, int last_hist, float last_gain, const Tuning &t);
-    void release();
+    // the first kernels this call would run read raw device-format samples themselves (DecimShape::raw_front)
+    bool raw_ready(const OscBank &osc, bool lds_free) const { return raw_front() && lds_free && !osc.any_transient(); }
+    // a call of this many input samples is "long": chunks of 128 outputs or more, where two output buffers do as well as three
+    bool long_call(long long n) const { return bank_long_call(n / (long long)chain.total, C); }
     // n must be a multiple of chain.total; any such n streams exactly (no minimum frame length)
     // oa (from OscBank::advance_job for this call, or nullptr): when the route's kernel can advance the oscillators itself it does, and
     // DecimDone::osc_advanced says so (the caller then leaves the advance out of its tail launch)
     int run(hipStream_t s, const float2 *d_in, long long in_pitch, bool shared_input, long long n, const OscBank &osc,
             hipEvent_t after_first = nullptr, const RawSrc *raw = nullptr, const OscAdvance *oa = nullptr, DecimCall call = DecimCall{}, DecimDone *done = nullptr);
-    bool last_mfma = false;                 // the last run() was a k_mix_dec_mfma launch
-    int flush_y0(hipStream_t s);
-    DevBuf<OscDyn> d_dyn[2];                // [C] the oscillators' per-call fields as k_mix_dec_mfma hands them from call to call (ping-pong)
-    int dyn_parity = 0;
-    bool dyn_valid = false;                 // d_dyn[dyn_parity] holds this call's fields (the previous call was such a launch and nothing was uploaded since)
-    uint64_t dyn_epoch_seen = 0;
-    bool y0_pending = false;                // d_y0stage holds first-stage history the stage-0 head-room has not received yet (copied when a call needs it there)
-    // the first kernels this call would run read raw device-format samples themselves (k_mix_hb11_lean + its edge launch)
-    bool raw_front() const { return bank_front && C == 1 && !(fused_all || bank_mfma); }  // those kernels exist for this chain
-    bool raw_ready(const OscBank &osc, bool lds_free) const { return raw_front() && lds_free && !osc.any_transient(); }
     void tail_jobs(std::vector<TailJob> &jobs) const;  // after run(): what must be refreshed before the next call
-    // Two output buffers, written by alternate calls, so that whatever reads a call's output (the band-pass) may run on another stream
-    // beside the NEXT call's decimator: the consumer's look-back (the head-room) is carried from the buffer just written into the other
-    // one's head-room.  tail_jobs() = tail_jobs_dec() (the decimator's own histories: its stream) + tail_job_out() (the consumer's stream)
-    // a call of this many input samples is "long": chunks of 128 outputs or more, where two output buffers do as well as three
-    bool long_call(long long n) const { const long long lo = n / (long long)chain.total; return (lo + 2 * std::max(1LL, 1024LL / ((C + 31) / 32)) - 1) / (2 * std::max(1LL, 1024LL / ((C + 31) / 32))) >= 128; }
-    HistBuf fin2, fin3;                      // fin: this call's; fin2: the next call's (its head-room filled by this call's consumer); fin3: a third, written by the call after that,
-                                             // so that a call's decimator waits for the consumer of the call THREE back (long over) instead of two (often still running)
-    int enable_double_out();                 // after init(); fails for a single-stage chain (its output is the first stage's buffer)
-    bool double_out() const { return fin2.base.get() != nullptr; }
     void tail_jobs_dec(std::vector<TailJob> &jobs) const;
     void tail_job_out(std::vector<TailJob> &jobs) const;
     const HistBuf &out() const { return casc.nst > 0 ? fin : buf0; }
     long long out_len() const { return len_out; }
+
+    // ---- run()'s steps: one launcher per route (DecimRoute, decim_route.h), the rest stages, the hand-overs ----
+    struct Launch { hipStream_t s; const float2 *in; long long in_pitch; bool shared_input; long long n; const OscBank &osc; const RawSrc *raw; };
+    DecimCallFacts call_facts(const Launch &l, const DecimCall &call) const;
+    int run_in_consumer(const DecimRoute &r);
+    int run_mixer_only(const Launch &l, const DecimRoute &r);
+    int run_bank_mfma(hipStream_t s, const float2 *d_in, long long n, const OscBank &osc, const OscAdvance *oa, hipEvent_t done_event, DecimDone *done);
+    int report_clk(hipStream_t s, unsigned n_wg, long long L);  // waits for the launch, prints its clock counts on stderr
+    int flush_y0(hipStream_t s);
+    int run_edges(const Launch &l, int R);  // the two-workgroup k_mix_hb11_bank launch: a call's first outputs and its mixed history
+    int run_fused(const Launch &l, const DecimRoute &r);
+    int run_cic_hb(const Launch &l, const DecimRoute &r);
+    int run_lean(const Launch &l, const DecimRoute &r);
+    int run_hb11_bank(const Launch &l, const DecimRoute &r);
+    int run_dec1(const Launch &l, const DecimRoute &r);
+    int run_rest(const Launch &l, const DecimRoute &r);
+    int hand_over(const Launch &l);  // what a general call leaves for a one-kernel call or a decimator inside the transform behind it
 };
 
 // ---- CFastFIR ----

@@ -1149,10 +1149,10 @@ const char *Receiver::kernel_name(int which) const
     switch (which) {
     case 1: return !bins ? "" : gated() ? (spec_.any ? "k_spectrum_list_any" : "k_spectrum_list_q128") : spec_.big ? "k_big256_cols + k_big256_rows" : spec_.per_q ? "k_spectrum_q128" : bins == 8192 ? (spec_.use_w64 ? "k_spectrum_w64" : spec_.last_fullc ? "k_spectrum_t128 (twiddles held)" : "k_spectrum_t128") : bins == 4096 ? "k_spectrum<2>" : "k_spectrum_1to1";
     case 2:
-        if (!last_tb_) return dec_.front_name;
-        return testbench_label(dec_.front_name, last_tb_morse_);
-    case 3: return dec_.rest_name;
-    case 4: return wfm ? "" : dec_.last_in_consumer ? "k_fastfir_t128 (mixing)" : ff_n == 2048 ? "k_fastfir_t128" : "k_fastfir";
+        if (!last_tb_) return dec_.front_name();
+        return testbench_label(dec_.front_name(), last_tb_morse_);
+    case 3: return dec_.rest_name();
+    case 4: return wfm ? "" : dec_.last_in_consumer() ? "k_fastfir_t128 (mixing)" : ff_n == 2048 ? "k_fastfir_t128" : "k_fastfir";
     case 5: return wfm ? (wfmc_.fused ? "k_wfm_fir" : "k_iir_scan + k_discrim + k_fir_dec") : "k_anf/k_agc/k_iir_scan/k_pll_demod + k_fir_dec (listed channels only)";
     case 6: {  // the input route of the last call; the format tags are the stream bank's
         static const char *const kIn[8] = {"", "float2", "raw s8", "raw u8", "raw s16", "raw f32", "raw wav16", "k_normalize_iq"};

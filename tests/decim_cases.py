@@ -1,7 +1,7 @@
 """The coverage statement for the general decimator routes (csrc/kernels_frontend.h: k_mix_dec1, k_mix_hb11_bank, k_mix_hb11_lean,
 k_mix_cic_hb, k_fir_dec as the peeled second stage, k_cascade): what DecimCore::run (csrc/cores.hip) launches when the call is not one
 k_mix_dec_mfma launch.  One table of rows, used by the CPU tier (tests/test_decimator_routes_host.py: every row's chain is the
-oracle's, its route is what route() -- DecimCore::init/run's rule restated below -- says, the union of the rows reaches what this
+oracle's, its route is what route() -- the rule of csrc/decim_route.h stated on its own below -- says, the union of the rows reaches what this
 statement claims, a plain fp64 model agrees with the oracle and nine deliberately wrong models cannot pass) and by the GPU tier
 (tests/test_decimator_routes_gpu.py: the same rows through P.ReceiverBank at the POST_MIXER tap, and the step rows through
 P.Decimator, against the oracle).  No row sets an environment switch, no kernel is launched directly.
@@ -87,7 +87,7 @@ CSRC = os.path.join(ROOT, "pebblesdr_amd", "csrc")
 
 
 # ------------------------------------------------------------------------------------------------
-# what the sources say: halfband taps (hb_taps.inc) and k_mix_dec_mfma's instances (cores.hip bank_variants())
+# what the sources say: halfband taps (hb_taps.inc) and k_mix_dec_mfma's instances (decim_route.h PG_BANK_DEC_INSTANCES)
 # ------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def halfband_taps():
@@ -102,16 +102,43 @@ def halfband_taps():
 
 
 @functools.lru_cache(maxsize=None)
+def bank_instances():
+    """{(NP, T1, T2, T3): MINW} of PG_BANK_DEC_INSTANCES in csrc/decim_route.h: the one list the planner looks a chain up in and
+    cores.hip instantiates k_mix_dec_mfma from.  The only reader of that list on the test side."""
+    text = open(os.path.join(CSRC, "decim_route.h")).read()
+    body = text[text.index("#define PG_BANK_DEC_INSTANCES(X)"):]
+    body = body[:body.index("\n\n")]
+    found = [tuple(int(v) for v in m) for m in re.findall(r"\bX\((\d+), (\d+), (\d+), (\d+), (\d+)\)", body)]
+    assert len(found) == len({f[:4] for f in found}) and body.count("X(") == len(found), body  # (every entry read, none twice)
+    return {f[:4]: f[4] for f in found}
+
+
 def bank_variants():
-    """{(NP, T1, T2, T3)} of bank_variants() in csrc/cores.hip"""
-    text = open(os.path.join(CSRC, "cores.hip")).read()
-    body = text[text.index("static const std::vector<BankVariant> &bank_variants()"):]
-    body = body[:body.index("return v;")]
-    return frozenset(tuple(int(v) for v in m.groups()) for m in re.finditer(r"bank_variant_of<(\d+), (\d+), (\d+), (\d+), \d+>\(\)", body))
+    """{(NP, T1, T2, T3)} of that list"""
+    return frozenset(bank_instances())
+
+
+_ladder = {}
+
+
+def ladder_rates():
+    """every rate 60 kHz .. 250 MHz in 0.1 % steps, the rows' rates and the round rates"""
+    return sorted({int(60000 * 1.001 ** k) for k in range(8340)} | {r.fs for r in ROWS} | {k * 100_000 for k in range(1, 2501)})
+
+
+def ladder_chains(oracle_mod):
+    """{chain: (first rate, bandwidth) that gives it} over ladder_rates() at both bandwidths (computed once per session)"""
+    if not _ladder:
+        for bw in (30000, 200000):
+            for fs in ladder_rates():
+                _ladder.setdefault(tuple(oracle_mod.Decimator(fs, bw).chain()), (fs, bw))
+    return _ladder
 
 
 # ------------------------------------------------------------------------------------------------
-# DecimCore::init / DecimCore::run restated (csrc/cores.hip), for a chain with at least one stage and the default tuning
+# The route of a DecimCore::run call, stated here on its own for a chain with at least one stage and the default tuning.  The library
+# plans it in csrc/decim_route.h (plan_decim_shape, plan_decim_route); tests/test_decim_route_host.py holds the two to each other over
+# the whole ladder, the GPU tier holds kernel_name() to this one.
 # ------------------------------------------------------------------------------------------------
 Route = namedtuple("Route", "front rest front_inst cl_log2 dec1_branch fir_dec cascade_inst nst outb tiles last_tile")
 

@@ -1,26 +1,23 @@
-"""CPU tier of the k_mix_dec_mfma coverage table (tests/bank_cases.py): every instance bank_variants() ships has a multi-group
+"""CPU tier of the k_mix_dec_mfma coverage table (tests/bank_cases.py): every instance the library's list ships has a multi-group
 row, every row reaches the instance and the chunk geometry it claims (bank_geometry() of csrc/bank_geom.h, compiled here with
 g++), the table as a whole covers the strides, chunk lengths and launch shapes it is there for, and the oracle puts every
 compared channel's peak into the bin the lane-mapping check of the GPU tier expects."""
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 from tests import bank_cases as B
+from tests import decim_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pebblesdr_amd", "csrc")
 
 
 def shipped_variants():
-    """{(NP, T1, T2, T3): MINW} out of bank_variants() in cores.hip"""
-    src = open(os.path.join(CSRC, "cores.hip")).read()
-    body = src[src.index("bank_variants()\n{"):]
-    body = body[:body.index("return v;")]
-    return {tuple(int(v) for v in m[:4]): int(m[4]) for m in re.findall(r"bank_variant_of<(\d+), (\d+), (\d+), (\d+), (\d+)>\(\)", body)}
+    """{(NP, T1, T2, T3): MINW} of the library's instance list (csrc/decim_route.h)"""
+    return dict(decim_cases.bank_instances())
 
 
 @pytest.fixture(scope="module")

@@ -1,6 +1,7 @@
 """CPU tier of the general decimator routes (tests/decim_cases.py): no device.
 
- - every row's chain is oracle.Decimator's and its route is what the restated DecimCore::init/run rule gives: the rows really sit on
+ - every row's chain is oracle.Decimator's and its route is what decim_cases.route() gives (tests/test_decim_route_host.py holds that
+   statement to the planner DecimCore::run reads, csrc/decim_route.h): the rows really sit on
    the kernels, channel-lane layouts and k_cascade instances the coverage statement claims,
  - a sweep of the ladder shows which branches no rate reaches; that list is asserted,
  - the plain fp64 model of mixer -> stages -> gain restore is the oracle at every row (100 times under the GPU bar),
@@ -98,13 +99,10 @@ def test_every_row_takes_the_route_it_is_there_for(oracle_mod, chains):
 def test_ladder_sweep_leaves_these_branches_dead(oracle_mod):
     """Every rate 60 kHz .. 250 MHz (0.1 % steps and the round rates) at both bandwidths, every bank size class, stream layout, call kind:
     the branches of DecimCore::run and k_mix_dec1 that never come up.  A change to the ladder that makes one live fails here."""
-    rates = sorted({int(60000 * 1.001 ** k) for k in range(8340)} | {r.fs for r in dc.ROWS} | {k * 100_000 for k in range(1, 2501)})
+    rates = dc.ladder_rates()
     assert rates[0] == 60000 and rates[-1] >= 249_000_000
     seen_dec1, seen_fir, seen_front, behind_cic, outbs, triples = set(), set(), set(), set(), set(), {4: set(), 12: set()}
-    chains = {}
-    for bw in (30000, 200000):
-        for fs in rates:
-            chains.setdefault(tuple(oracle_mod.Decimator(fs, bw).chain()), (fs, bw))
+    chains = dc.ladder_chains(oracle_mod)  # (both bandwidths at every rate)
     for ch in chains:
         if not ch:
             continue

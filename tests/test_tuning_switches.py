@@ -1,9 +1,11 @@
 """CPU tier: the library's environment switches have one reader (csrc/tuning.h), they are exactly the ones DESIGN.md's table lists,
-and the built library carries no k_mix_dec_mfma instance beyond the nine of bank_variants() (no timing instance: DBG is 0 in all)."""
+and the built library carries no k_mix_dec_mfma instance beyond the nine of its instance list (no timing instance: DBG is 0 in all)."""
 import os
 import re
 
 import pytest
+
+from tests import decim_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pebblesdr_amd", "csrc")
@@ -37,11 +39,7 @@ def test_switches_read_are_the_design_table():
 
 
 def test_only_the_bank_variants_are_built(lib_path):
-    src = open(os.path.join(CSRC, "cores.hip")).read()
-    body = src[src.index("bank_variants()\n{"):]
-    body = body[:body.index("return v;")]
-    want = {(np_, t1, t2, t3, 0, minw) for np_, t1, t2, t3, minw in
-            (tuple(int(v) for v in m) for m in re.findall(r"bank_variant_of<(\d+), (\d+), (\d+), (\d+), (\d+)>\(\)", body))}
+    want = {inst + (0, minw) for inst, minw in decim_cases.bank_instances().items()}
     assert len(want) == 9
     built = {tuple(int(v) for v in m) for m in MFMA.findall(open(lib_path, "rb").read())}
     assert built == want, (sorted(built - want), sorted(want - built))
