@@ -359,9 +359,21 @@ int pebblegpu_receiver_mean_ms(const pebblegpu_receiver *rx, int which, uint32_t
  * 0.7071, dcremoval.cpp:3-19); IQBALANCE: IQBalance::ProcessBlock with setGainFactor/setPhaseFactor values
  * (iqbalance.cpp:65-86); NB1/NB2: NoiseBlanker::ProcessBlock/ProcessBlock2 (noiseblanker.cpp:45-97; switching one on
  * resets its averages as setNbEnabled does).  These are serial-in-time algorithms: the library runs one lane per stream
- * (per frame for IQBALANCE), so they parallelise over banks of streams, not within one.  Batched device path only. */
+ * (per frame for IQBALANCE), so they parallelise over banks of streams, not within one.  Batched device path only.
+ * A blanker is reset on the off -> on TRANSITION of its flag only: a setter call with the flag already on (another gain, say) leaves its
+ * averages, NB1's spike count and delay line where the stream left them.  (The reference's setNbEnabled(true) resets whenever it is
+ * called; its UI calls it on a toggle.)  IQBALANCE is switched by its flag alone: iq_gain and iq_phase are applied as given, a negative
+ * gain included (the reference multiplies by it).  IQBalance restarts its adaptive terms every frames_per_buffer samples.
+ * PEBBLEGPU_E_INVALID, nothing changed and the handle usable afterwards: a NULL handle, a stream out of range, flags outside 0..15, a
+ * non-finite iq_gain or iq_phase.
+ *
+ * pebblegpu_receiver_conditioned(rx, &samples_per_stream, &pitch_samples): a device pointer to float2 [stream][pitch], the conditioned
+ * rows the LAST call's spectrum and mixer read; valid after pebblegpu_receiver_synchronize until the next call.  NULL and both outputs 0
+ * when the last call conditioned nothing: no flag set on any stream, a refused call, pebblegpu_process_iq.  It hands out what the call
+ * made anyway: no launch, copy or allocation of its own. */
 enum { PEBBLEGPU_COND_DC = 1, PEBBLEGPU_COND_IQBALANCE = 2, PEBBLEGPU_COND_NB1 = 4, PEBBLEGPU_COND_NB2 = 8 };
 int pebblegpu_set_conditioners(pebblegpu_receiver *rx, uint32_t stream, int flags, double iq_gain, double iq_phase);
+const void *pebblegpu_receiver_conditioned(const pebblegpu_receiver *rx, uint64_t *samples_per_stream, uint64_t *pitch_samples);
 /* NoiseFilter (ANF, 45-tap leaky LMS on a 64-sample delay, noisefilter.cpp:31-88) on a narrow channel, between the
  * band-pass and the AGC (receiver.cpp:974) */
 int pebblegpu_set_noise_filter(pebblegpu_receiver *rx, uint32_t channel, int on);

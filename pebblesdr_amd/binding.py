@@ -63,7 +63,7 @@ SYMBOLS = [
     "pebblegpu_streambank_display_set_auto_scale", "pebblegpu_streambank_display_rescale", "pebblegpu_streambank_display_scale",
     "pebblegpu_signal_strength_row", "pebblegpu_streambank_enable_signal_strength", "pebblegpu_streambank_signal_strength",
     "pebblegpu_streambank_set_squelch", "pebblegpu_streambank_iq_out_gate",
-    "pebblegpu_streambank_set_conditioners", "pebblegpu_streambank_conditioned",
+    "pebblegpu_streambank_set_conditioners", "pebblegpu_streambank_conditioned", "pebblegpu_receiver_conditioned",
 ]
 
 SPECTRUM_EVERY_FRAME = -1  # PEBBLEGPU_SPECTRUM_EVERY_FRAME
@@ -569,6 +569,8 @@ def _declare(L):
     L.pebblegpu_receiver_set_taps.argtypes = [vp, u32]
     L.pebblegpu_receiver_tap.restype = vp
     L.pebblegpu_receiver_tap.argtypes = [vp, i32, u64p, u64p, dp]
+    L.pebblegpu_receiver_conditioned.restype = vp
+    L.pebblegpu_receiver_conditioned.argtypes = [vp, u64p, u64p]
     L.pebblegpu_siggen_create.argtypes = [i32, dbl, u32, C.POINTER(vp)]
     L.pebblegpu_siggen_destroy.argtypes = [vp]
     L.pebblegpu_siggen_set_sweep.argtypes = [vp, swp]
@@ -876,6 +878,18 @@ class ReceiverBank:
 
     def set_conditioners(self, stream, flags, iq_gain=1.0, iq_phase=0.0):
         check(self.L, self.L.pebblegpu_set_conditioners(self.h, stream, int(flags), float(iq_gain), float(iq_phase)))
+
+    def conditioned(self):
+        """-> complex64 [streams, n]: the conditioned rows the last call's spectrum and mixer read, or None when it conditioned nothing"""
+        n, pitch = C.c_uint64(), C.c_uint64()
+        p = self.L.pebblegpu_receiver_conditioned(self.h, C.byref(n), C.byref(pitch))
+        if not p or not int(n.value):
+            return None
+        self.synchronize()
+        out = np.empty((self.n_streams, int(n.value)), dtype=np.complex64)
+        for r in range(self.n_streams):  # rows are pitched at the handle's capacity
+            check(self.L, self.L.pebblegpu_memcpy_d2h(self.device, out[r].ctypes.data_as(C.c_void_p), C.c_void_p(p + r * int(pitch.value) * 8), out[r].nbytes))
+        return out
 
     def set_noise_filter(self, ch, on=True):
         check(self.L, self.L.pebblegpu_set_noise_filter(self.h, ch, 1 if on else 0))

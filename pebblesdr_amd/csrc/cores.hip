@@ -1693,6 +1693,7 @@ int ConditionCore::init(uint32_t streams, uint32_t frame, double sample_rate, lo
 int ConditionCore::set(uint32_t stream, int flags, double gain, double phase)
 {
     if (stream >= S || flags < 0 || flags > 15) return fail(PEBBLEGPU_E_INVALID, "bad stream or conditioner flags");
+    if (!std::isfinite(gain) || !std::isfinite(phase)) return fail(PEBBLEGPU_E_INVALID, "the IQ gain and phase factors must be finite");
     Host &h = host[stream];
     if (!d_buf) {  // first use: the conditioned copy and the per-stream state
         PG_TRY(d_buf.alloc((size_t)cap * S));
@@ -1726,19 +1727,19 @@ int ConditionCore::apply(hipStream_t s)
     PG_HIP(hipStreamSynchronize(s));
     any = iq_any = nb_any = false;
     dc_list.clear();
-    std::vector<double2> iq(S);
+    std::vector<IqFactors> iq(S);
     for (uint32_t i = 0; i < S; i++) {
         const Host &h = host[i];
         if (h.flags) any = true;
         if (h.flags & 1) dc_list.push_back((int)i);
-        iq[i] = (h.flags & 2) ? make_double2(h.gain, h.phase) : make_double2(-1.0, 0.0);
+        iq[i] = IqFactors{h.gain, h.phase, (h.flags & 2) ? 1 : 0, 0};
         if (h.flags & 2) iq_any = true;
         if (h.flags & 12) nb_any = true;
         const int nbf = (h.flags >> 2) & 3;
         PG_HIP(hipMemcpy(&d_nb[i].flags, &nbf, sizeof(int), hipMemcpyHostToDevice));
     }
     if (!dc_list.empty()) PG_HIP(hipMemcpy(d_dc_list, dc_list.data(), sizeof(int) * dc_list.size(), hipMemcpyHostToDevice));
-    PG_HIP(hipMemcpy(d_iq, iq.data(), sizeof(double2) * S, hipMemcpyHostToDevice));
+    PG_HIP(hipMemcpy(d_iq, iq.data(), sizeof(IqFactors) * S, hipMemcpyHostToDevice));
     dirty = false;
     return 0;
 }
@@ -1754,7 +1755,7 @@ int ConditionCore::run(hipStream_t s, const float2 *d_in, long long in_pitch, lo
         launch(k_iir_scan<0, 1>, dim3(1, (unsigned)dc_list.size()), dim3(64), s, (const float2 *)d_buf, cap, d_buf, cap, n, dc, (const double *)d_dc_state,
                d_dc_state, (int)nsub, -1, (const int *)d_dc_list, Gate{nullptr, 0, 0});
     }
-    if (iq_any) launch(k_iq_balance, dim3(cdiv(n / nf, 64), S), dim3(64), s, d_buf, cap, (int)nf, n / nf, (const double2 *)d_iq);
+    if (iq_any) launch(k_iq_balance, dim3(cdiv(n / nf, 64), S), dim3(64), s, d_buf, cap, (int)nf, n / nf, (const IqFactors *)d_iq);
     if (nb_any) launch(k_noise_blank, dim3(cdiv(S, 64)), dim3(64), s, d_buf, cap, n, d_nb, (int)S);
     PG_HIP(hipGetLastError());
     *out = d_buf;

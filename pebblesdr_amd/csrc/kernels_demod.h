@@ -657,14 +657,16 @@ static __global__ __launch_bounds__(256) void k_resample(const float2 *__restric
 // ------------------------------------------------------------------------------------------------
 // IQBalance::ProcessBlock (application/iqbalance.cpp:65-86): the adaptive terms t1, t2 restart at zero every block,
 // so every (stream, frame) is independent: one lane each.  grid (ceil(frames/64), streams), block 64.
+// on / off is the stream's flag, never read out of the factors: a negative gain is applied as the reference applies it.
+struct IqFactors { double gain, phase; int on, pad_; };
 static __global__ __launch_bounds__(64) void k_iq_balance(float2 *__restrict__ buf, long long pitch, int nf, long long n_frames,
-                                                          const double2 *__restrict__ factors /* [stream] (gain, phase); gain < 0: off */)
+                                                          const IqFactors *__restrict__ factors /* [stream] */)
 {
     const long long f = (long long)blockIdx.x * 64 + threadIdx.x;
     const int s = blockIdx.y;
     if (f >= n_frames) return;
-    const double2 gp = factors[s];
-    if (gp.x < 0) return;
+    if (!factors[s].on) return;
+    const double2 gp = make_double2(factors[s].gain, factors[s].phase);
     float2 *x = buf + (long long)s * pitch + f * nf;
     double t1r = 0, t1i = 0, t2r = 0, t2i = 0;
     const float mu = 0.0025f;

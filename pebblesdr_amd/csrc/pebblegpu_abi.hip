@@ -192,6 +192,13 @@ const void *pebblegpu_receiver_tap(const pebblegpu_receiver *h, int point, uint6
     if (!h) return nullptr;
     return h->rx.tap(point, samples_per_row, pitch_samples, rate);
 }
+const void *pebblegpu_receiver_conditioned(const pebblegpu_receiver *h, uint64_t *samples_per_stream, uint64_t *pitch_samples)
+{
+    if (samples_per_stream) *samples_per_stream = 0;
+    if (pitch_samples) *pitch_samples = 0;
+    if (!h) return nullptr;
+    return h->rx.conditioned(samples_per_stream, pitch_samples);
+}
 int pebblegpu_set_demod_mode(pebblegpu_receiver *h, uint32_t channel, int mode)
 {
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");

@@ -481,7 +481,7 @@ struct ConditionCore {
     DevBuf<double> d_dc_state;        // [S][1][2][2]
     DevBuf<int> d_dc_list;
     std::vector<int> dc_list;
-    DevBuf<double2> d_iq;             // [S] (gain, phase), gain < 0: off
+    DevBuf<struct IqFactors> d_iq;    // [S] (gain, phase, on)
     DevBuf<struct NbState> d_nb;      // [S]
     ScanParams<1> dc;
     bool iq_any = false, nb_any = false;
@@ -712,6 +712,8 @@ public:
     int set_testbench_morse(const pebblegpu_morse_station *stations, uint32_t n_stations, int mix);
     int set_taps(uint32_t mask);
     const float2 *tap(int point, uint64_t *n_per_row, uint64_t *pitch, double *rate) const;
+    // the conditioned copy of the streams the last call read (ConditionCore::d_buf); NULL and zeros when that call conditioned nothing
+    const float2 *conditioned(uint64_t *n_per_stream, uint64_t *pitch) const;
     int process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool with_chain, const RawSrc *raw = nullptr);
     // spectrum_updated (may be null): whether this frame got a spectrum (always, without the update timer)
     int process_iq(const double *iq, uint16_t n, double *audio, uint32_t *n_audio, double *spectrum_db, uint32_t *spectrum_updated = nullptr);
@@ -888,6 +890,7 @@ private:
     AnfCore anf_;
     MorseCore morse_;
     TestBenchCore tb_;
+    uint64_t last_cond_n_ = 0;        // samples per stream the last call conditioned (0: it conditioned nothing, or was refused)
     bool last_tb_ = false;            // the last call ran the generator (kernel_name)
     bool last_tb_morse_ = false;      // ... with stations on: k_morsegen instead of k_testbench
     int last_input_ = -2;             // the last call's input route (kernel_name(6)): -2 no call yet, -1 float2, 0..4 raw of that format

@@ -420,6 +420,13 @@ int Receiver::copy_tap(hipStream_t s, int point, const float2 *src, long long sr
     return 0;
 }
 
+const float2 *Receiver::conditioned(uint64_t *n_per_stream, uint64_t *pitch) const
+{
+    if (n_per_stream) *n_per_stream = last_cond_n_;
+    if (pitch) *pitch = last_cond_n_ ? (uint64_t)cond_.cap : 0;
+    return last_cond_n_ ? (const float2 *)cond_.d_buf : nullptr;
+}
+
 int Receiver::set_conditioners(uint32_t stream, int flags, double iq_gain, double iq_phase)
 {
     std::lock_guard<std::mutex> g(mu_);
@@ -672,7 +679,9 @@ int Receiver::stage_input(Call &c)
     }
     c.tap_iq = c.d_iq;  // displayData(.., TB_RAW_IQ), receiver.cpp:803: before the conditioners
     // DCRemoval, IQBalance, NoiseBlanker 1/2 on the raw streams, ahead of the spectrum and the mixer (receiver.cpp:814-823)
-    return cond_.run(stream_, c.d_iq, c.in_pitch, (long long)c.n, &c.d_iq, &c.in_pitch);
+    if (int rc = cond_.run(stream_, c.d_iq, c.in_pitch, (long long)c.n, &c.d_iq, &c.in_pitch)) return rc;
+    if (cond_.any) last_cond_n_ = c.n;  // what pebblegpu_receiver_conditioned hands out
+    return 0;
 }
 
 // the call's timing slot, its start record, the fork, and the wait for the last reader of the output buffer it writes
@@ -1049,6 +1058,7 @@ int Receiver::process(const float2 *d_iq, uint64_t n, bool with_spectrum, bool w
 {
     std::lock_guard<std::mutex> g(mu_);
     PG_HIP(hipSetDevice(device));
+    last_cond_n_ = 0;
     if (int rc = refuse_call(d_iq, n, with_spectrum, with_chain, raw)) return rc;
     Call c;
     c.rt = plan_call_route(call_facts(n, with_spectrum, with_chain, raw != nullptr));
@@ -1219,6 +1229,7 @@ int Receiver::sync()
 // the reference stops returning early (receiver.cpp:922-931).
 int Receiver::process_iq(const double *iq, uint16_t n, double *audio_out, uint32_t *n_audio, double *spectrum_db, uint32_t *spectrum_updated)
 {
+    last_cond_n_ = 0;
     if (!iq || !n_audio) return fail(PEBBLEGPU_E_INVALID, "null argument");
     if (n != nf) return fail(PEBBLEGPU_E_SIZE, "process_iq takes frames of %u samples", nf);
     if (S != 1) return fail(PEBBLEGPU_E_UNSUPPORTED, "process_iq feeds one stream; this bank has %u", S);
