@@ -1153,7 +1153,9 @@ int pebblegpu_streambank_display_scale(pebblegpu_streambank *sb, uint64_t call_i
  *   over i in [noiseLow, min(noiseHigh, bins - 1)]: pwr = pow(10, dB_i / 10.0); lo <= i <= hi: total += pwr, peak = max; else noise += pwr
  *   peakDb = clip(powerTodB(peak)); avgDb = clip(powerTodB(total / bpBins)); floorDb = clip(powerTodB(noise / noiseBins));
  *   snrDb = bound(0, 10 log10(peak / noiseAvg), 120), 0 when either is 0.      powerTodB(0) = -120; clip bounds to -120..0
- * bpBins == 0 gives avgDb 0 (x / 0 = inf) and, with no noise bin, NaN floorDb and snrDb -- as the reference computes them.
+ * clip and bound are the reference's qBound(lo, v, hi) = qMax(lo, qMin(hi, v)), whose comparisons are all false for a NaN: a NaN comes out
+ * as the LOWER bound.  So bpBins == 0 with a bin in band gives avgDb 0 (x / 0 = inf); a window without a noise bin (0 / 0) floorDb -120 and
+ * snrDb 0; a window without any bin (the mixer's bin clamped to `bins`) (-120, -120, 0, -120).  No output is ever NaN or infinite.
  * pebblegpu_signal_strength_row is the host twin (no device): the reference's serial loop; out = (peakDb, avgDb, snrDb, floorDb).
  * PEBBLEGPU_E_INVALID for a NULL argument, 0 bins, or sample_rate < bins (the integer bin width would be 0).  The device
  * (k_stream_strength: one 256-lane workgroup per row, a fixed reduction order, no atomics -- the same bits on every run) adds in another

@@ -1559,7 +1559,14 @@ void po_anf_process(po_anf *a, const double *in, double *out, int n)
  * ---------------------------------------------------------------------------------------------- */
 static int po_qbound(int lo, int v, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 static double po_power_to_db(double p) { return p == 0 ? -120.0 : 10 * log10(p); } /* DB::minDb = -120 (db.cpp) */
-static double po_db_clip(double db) { return db < -120.0 ? -120.0 : (db > 0.0 ? 0.0 : db); }
+/* qBound(lo, v, hi) = qMax(lo, qMin(hi, v)) with Qt's comparisons, qMin(a, b) = a < b ? a : b and qMax(a, b) = a < b ? b : a:
+ * a NaN (0 / 0 of a window without a noise bin, or without any bin) comes out as the LOWER bound */
+static double po_qbound_d(double lo, double v, double hi)
+{
+    const double m = hi < v ? hi : v;
+    return lo < m ? m : lo;
+}
+static double po_db_clip(double db) { return po_qbound_d(-120.0, db, 0.0); }
 
 double po_fd_estimate(const double *spectrum, int bins, uint32_t rate, float bp_lo, float bp_hi, double mixer_freq, double *out)
 {
@@ -1591,7 +1598,7 @@ double po_fd_estimate(const double *spectrum, int bins, uint32_t rate, float bp_
     const double peak_db = po_db_clip(po_power_to_db(peak_pwr)), avg_db = po_db_clip(po_power_to_db(avg_pwr));
     const double floor_db = po_db_clip(po_power_to_db(noise_avg));
     double snr = (noise_avg == 0 || peak_pwr == 0) ? -120.0 : 10.0 * log10(peak_pwr / noise_avg);
-    snr = snr < 0.0 ? 0.0 : (snr > 120.0 ? 120.0 : snr);
+    snr = po_qbound_d(0.0, snr, 120.0);
     if (out) { out[0] = peak_db; out[1] = avg_db; out[2] = snr; out[3] = floor_db; }
     return avg_db;
 }

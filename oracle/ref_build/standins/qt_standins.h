@@ -30,7 +30,11 @@ typedef double qreal;
 #define slots
 #define emit
 
-template <typename T> inline const T &qMin(const T &a, const T &b) { return (b < a) ? b : a; }
+/* The order of the comparisons matters for NaN, where every comparison is false: Qt's published qglobal.h words them
+ * qMin(a, b) = (a < b) ? a : b, qMax(a, b) = (a < b) ? b : a, qBound(min, v, max) = qMax(min, qMin(max, v)), so that
+ * qBound of a NaN is the LOWER bound (SignalStrength::fdEstimate bounds 0 / 0 this way).  Written from that published
+ * wording as remembered, not checked against an installed Qt. */
+template <typename T> inline const T &qMin(const T &a, const T &b) { return (a < b) ? a : b; }
 template <typename T> inline const T &qMax(const T &a, const T &b) { return (a < b) ? b : a; }
 template <typename T> inline const T &qBound(const T &lo, const T &v, const T &hi) { return qMax(lo, qMin(hi, v)); }
 

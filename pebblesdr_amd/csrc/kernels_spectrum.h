@@ -1497,12 +1497,7 @@ static __global__ __launch_bounds__(64) void k_signal_strength(const float *__re
         nn += c2;
     }
     if (lane != 0) return;
-    auto p2db = [](double p) { return p == 0.0 ? -120.0 : 10.0 * log10(p); };
-    auto clip = [](double d) { return d < -120.0 ? -120.0 : (d > 0.0 ? 0.0 : d); };
-    const double avg = total / (double)b.bp_bins, navg = noise / (double)nn;
-    double snr = (navg == 0.0 || peak == 0.0) ? -120.0 : 10.0 * log10(peak / navg);
-    snr = snr < 0.0 ? 0.0 : (snr > 120.0 ? 120.0 : snr);
-    out[(long long)c * out_pitch + f] = make_float4((float)clip(p2db(peak)), (float)clip(p2db(avg)), (float)snr, (float)clip(p2db(navg)));
+    out[(long long)c * out_pitch + f] = strength_finish(total, peak, noise, nn, b.bp_bins);  // (params.h: a NaN ends as the lower bound)
 }
 
 }  // namespace pg

@@ -1,8 +1,8 @@
 // kernels_strength.h -- the stream bank's S-meter and squelch gate (streambank.hip): SignalStrength::fdEstimate
 // (application/signalstrength.cpp:287-380) per (stream, computed spectrum row), and the per-(stream, frame) decision
 // m_avgDb < m_squelchDb (application/receiver.cpp:959-965) that the IQ ring's packing kernel obeys.  The rule's windows are
-// strength_windows (params.h, shared with Receiver::apply_controls); its end -- power sums to four dB values -- is strength_finish, shared
-// by the kernel and the host twin (pebblegpu_signal_strength_row).
+// strength_windows (params.h, shared with Receiver::apply_controls); its end -- power sums to four dB values -- is strength_finish
+// (params.h), shared by this kernel, the receivers' k_signal_strength and the host twin (pebblegpu_signal_strength_row).
 #pragma once
 #include <cmath>
 #include "common.h"
@@ -11,25 +11,9 @@
 
 namespace pg {
 
-// fdEstimate behind its loop (signalstrength.cpp:355-380): total / peak over the band-pass bins, noise over the noise_bins bins either
-// side.  DB::powerTodB(0) = -120, DB::clip bounds to -120..0, snr to 0..120.  bp_bins == 0 with a bin in the window gives avg +inf -> 0 dB;
-// no noise bin gives 0 / 0: floor and snr are NaN, as the reference's are (every comparison with NaN is false, so no bound applies).
-__host__ __device__ inline float4 strength_finish(double total, double peak, double noise_total, int noise_bins, int bp_bins)
-{
-#pragma clang fp contract(off)
-    const double avg = total / (double)bp_bins, navg = noise_total / (double)noise_bins;
-    const double pk_db = peak == 0.0 ? -120.0 : 10.0 * log10(peak);
-    const double avg_db = avg == 0.0 ? -120.0 : 10.0 * log10(avg);
-    const double fl_db = navg == 0.0 ? -120.0 : 10.0 * log10(navg);
-    double snr = (navg == 0.0 || peak == 0.0) ? -120.0 : 10.0 * log10(peak / navg);
-    snr = snr < 0.0 ? 0.0 : (snr > 120.0 ? 120.0 : snr);
-    float4 o;
-    o.x = (float)(pk_db < -120.0 ? -120.0 : (pk_db > 0.0 ? 0.0 : pk_db));
-    o.y = (float)(avg_db < -120.0 ? -120.0 : (avg_db > 0.0 ? 0.0 : avg_db));
-    o.z = (float)snr;
-    o.w = (float)(fl_db < -120.0 ? -120.0 : (fl_db > 0.0 ? 0.0 : fl_db));
-    return o;
-}
+// (strength_finish stands in params.h beside strength_windows, so that the receivers' k_signal_strength ends through it as well: a
+// window without a noise bin, or without any bin, divides 0 by 0, and the NaN comes out as the reference's qBound gives it -- the
+// LOWER bound: -120 dB for peak, avg and floor, 0 for snr.  Nothing the S-meter reports is NaN.)
 
 // One 256-lane workgroup per (stream, computed row): grid = n_streams * n_rows, row = s * n_rows + j reads spec + s * stream_pitch + j * bins
 // and writes out[s * out_pitch + j]; the call's last row also goes to carry[s] (the row a later call's gate reads).  Only the aligned span

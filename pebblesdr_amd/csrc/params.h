@@ -1,5 +1,6 @@
 // params.h -- plain structs shared by the host objects and the kernels (passed by value or uploaded).
 #pragma once
+#include <cmath>
 #include <type_traits>
 #include "common.h"
 #include "decim_route.h"
@@ -204,6 +205,33 @@ inline SmBins strength_windows(uint32_t bins, uint32_t sample_rate, float bp_lo,
     b.nhi = qb(b.hi + b.bp_bins);
     b.stream = stream;
     return b;
+}
+
+// fdEstimate behind its loop (signalstrength.cpp:355-380): total / peak over the band-pass bins, noise over the noise_bins bins either
+// side.  DB::powerTodB(0) = -120, DB::clip bounds to -120..0, snr to 0..120.  bp_bins == 0 with a bin in the window gives avg +inf -> 0 dB;
+// no noise bin, or no bin at all, gives 0 / 0.  The reference bounds with qBound(lo, v, hi) = qMax(lo, qMin(hi, v)), where Qt words
+// qMin(a, b) = a < b ? a : b and qMax(a, b) = a < b ? b : a: every comparison with NaN is false, so a NaN comes out as the LOWER bound,
+// -120 dB for peak, avg and floor, 0 for snr (strength_bound keeps that order of comparisons).  One rule for the receivers' kernel
+// (k_signal_strength), the stream bank's (k_stream_strength) and the host twin (pebblegpu_signal_strength_row).
+__host__ __device__ inline double strength_bound(double lo, double v, double hi)
+{
+    const double m = hi < v ? hi : v;
+    return lo < m ? m : lo;
+}
+__host__ __device__ inline float4 strength_finish(double total, double peak, double noise_total, int noise_bins, int bp_bins)
+{
+#pragma clang fp contract(off)
+    const double avg = total / (double)bp_bins, navg = noise_total / (double)noise_bins;
+    const double pk_db = peak == 0.0 ? -120.0 : 10.0 * log10(peak);
+    const double avg_db = avg == 0.0 ? -120.0 : 10.0 * log10(avg);
+    const double fl_db = navg == 0.0 ? -120.0 : 10.0 * log10(navg);
+    const double snr = (navg == 0.0 || peak == 0.0) ? -120.0 : 10.0 * log10(peak / navg);
+    float4 o;
+    o.x = (float)strength_bound(-120.0, pk_db, 0.0);
+    o.y = (float)strength_bound(-120.0, avg_db, 0.0);
+    o.z = (float)strength_bound(0.0, snr, 120.0);
+    o.w = (float)strength_bound(-120.0, fl_db, 0.0);
+    return o;
 }
 
 // k_spectrum_t128<.., DEC = true>: the one-channel mixer + decimator hb11 x 8, hb15, hb23, hb47 (20 Msps -> 312.5 kHz; the halfbands'

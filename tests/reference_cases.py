@@ -453,6 +453,13 @@ def _build_cases():
     bands = [(-4000.0, 4000.0), (300.0, 3000.0)]
     C.append(Case("fdestimate", "fdestimate", [2048000, 2048, 2048000, 100000.0] + [v for b in bands for v in b], _fd_spectrum,
                   _fdestimate(2048000, 100000.0, bands)))
+    # ... and every window of tests/strength_cases.py: clipped at either end, bpBins == 0 with one bin and with none, no noise bin,
+    # truncating bin widths, a refused (inverted) band-pass.  Where fdEstimate divides 0 by 0 its qBound returns the lower bound
+    # (oracle/ref_build/standins/qt_standins.h words qMin as Qt does): every recorded value is finite
+    from tests import strength_cases as S
+    for name, rate, sbins, lo, hi, mixer, _ in S.ROWS:
+        C.append(Case("fdestimate_" + name, "fdestimate", [rate, 2048, rate, mixer, lo, hi], lambda name=name: S.row_spectrum(name),
+                      _fdestimate(rate, mixer, [(lo, hi)])))
     # the Morse modem's pebblelib classes at its four modem rates (no stage; 6000; 4687 of 4687.5; 7812 of 7812.5), both tones, the
     # tone moved to the other side on a running filter (Morse::setDemodMode): GoertzelOOK TH_PEAK, SampleClock, MovingAvgFilter(8)
     from tests import morse_ref as M

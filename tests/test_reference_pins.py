@@ -33,6 +33,11 @@ frame after an overloaded whole one (case spectrum_overload_then_short).  Fixed 
 pebblelib's c_j is {6.123233995736766e-17, 1} (cpx.h:158), so Goertzel's c_C and c_D have a modulus of exp(-6.1e-17 A (N - 1)), up to
 3e-14 under 1; the Morse restatement had {0, 1} and its powers came out 5e-14 off (cases morse_goertzel_*).  Fixed in the restatement and
 in MorseCore::init's coefficients; bit for bit since.
+fdEstimate divides 0 by 0 where a window has no noise bin or no bin at all, and bounds the NaN with qBound, which Qt words so that a NaN
+comes out as the LOWER bound (-120 dB; 0 for snr).  The oracle and the device let the NaN through, and the stand-in qMin, worded the
+other way round, returned the UPPER bound (cases fdestimate_* of tests/strength_cases.py: bp0_one_bin, bp0_no_bin, all_in_band,
+inverted).  Fixed in the stand-in, the oracle (po_db_clip, the snr bound) and the device's strength_finish; the 80 earlier pins did not
+move.  The wording of qMin / qMax / qBound is Qt's published qglobal.h as remembered, not checked against an installed Qt.
 """
 import os
 
@@ -90,6 +95,29 @@ def test_every_stage_of_the_table_has_a_case():
                       "iqbalance", "dcremoval", "fdestimate", "goertzel", "sampleclock", "movingavg"}
     assert all(c.bar <= R.MAX_BAR and c.bar_db <= R.MAX_BAR_DB for c in R.cases())
     assert all(os.path.getsize(c.fixture) < 16384 for c in R.cases())
+
+
+def test_every_recorded_signal_strength_is_finite(oracle_mod):
+    """fdEstimate's qBound turns 0 / 0 into its lower bound: no fixture, no oracle value and no value of the binary is NaN or inf, and
+    the rows whose class makes a value a bound hold exactly that bound"""
+    from tests import strength_cases as S
+    seen = 0
+    for case in R.cases():
+        if case.stage != "fdestimate":
+            continue
+        x = case.make_input()
+        sets = [[t for _, t in R.expand(np.load(case.fixture))], [v for _, v in case.oracle(oracle_mod, x)]]
+        if _have_binary():
+            sets.append(case.reference(x))
+        for records in sets:
+            for rec in records:
+                assert len(rec) == 5 and np.isfinite(rec).all(), (case.name, rec)
+                if case.name.startswith("fdestimate_"):
+                    for k, v in S.expected(S.row(case.name[len("fdestimate_"):])[6]).items():
+                        assert rec[k] == v, (case.name, k, rec)
+                    assert rec[4] == rec[1]
+        seen += 1
+    assert seen == 1 + len(S.ROWS)
 
 
 def test_chain_tables_of_the_reference_equal_the_recorded_ones(oracle_mod):

@@ -3,7 +3,8 @@ the IQ block's trailer, against the unchanged oracle.
 
 Shapes: 3 streams of 2048-sample frames at 2.048 Msps, at most 4 frames per call, 2048 and 8192 bins; 2 streams of 65536 / 65536 at
 200 Msps, 2 frames per call (the k_big256_* route).  Per stream one tone INSIDE the stream's band-pass whose amplitude doubles from frame
-to frame (6 dB), plus LCG noise at 1e-3; the band-passes are the windows of tests/test_streambank_smeter_host.py (all but the empty one).
+to frame (6 dB), plus LCG noise at 1e-3; the band-passes are the windows of tests/test_streambank_smeter_host.py; the empty one -- (100, 200):
+no noise bin -- has a test of its own, test_the_empty_window.
 
 Bounds.  The reduction alone -- every float4 against oracle.fd_estimate on the device's OWN dB row -- 1e-4 dB, the bound of
 test_parity_gpu.py::test_signal_strength_per_frame (b).  End to end -- against fd_estimate on the oracle's spectrum of the same frames --
@@ -149,6 +150,36 @@ def test_against_the_oracle(gpu_lib, oracle_mod, key):
         assert (r["gate"]["open"] == 1).all() and np.array_equal(r["gate"]["row"], np.tile(np.arange(r["n"], dtype=np.uint32), (len(sel), 1)))
         assert np.array_equal(bits(as_c64(r["block"])), bits(r["y"][sel]))
     assert float(sm[:, :, 0].max()) > -40.0 and float(np.ptp(sm[:, :, 1], axis=1).min()) > 15.0    # a real meter, not a constant
+
+
+def test_the_empty_window(gpu_lib, oracle_mod):
+    """(100, 200) at 2048 bins of 1000 Hz: bpBins == 0, one bin in band, no noise bin.  avg is x / 0 = +inf -> 0 dB, and the noise average
+    0 / 0, which the reference's qBound returns as its lower bound: snr 0, floor -120, nothing NaN.  An avg of 0 dB stays open at any
+    threshold up to 0; the stream next to it, (-5000, 5000) with a threshold of 50, closes"""
+    import pebblesdr_amd as P
+    fs, frame, bins, F = 2048000.0, 2048, 2048, 3
+    x = signal("2048")[:2, :F * frame]
+    sb = P.StreamBank(fs, 2, frame=frame, spectrum_bins=bins, max_frames=F)
+    try:
+        sb.set_bandpass(0, 100, 200)
+        sb.set_bandpass(1, -5000, 5000)
+        sb.enable_signal_strength(True)
+        sb.set_squelch(0, -1.0)
+        sb.set_squelch(1, 50.0)
+        sb.iq_out_open(P.AUDIO_F32, [0, 1], n_slots=2)
+        y, s = sb.process(x, 3)
+        sm = sb.signal_strength()
+        blk, gate = take(sb, 0)
+    finally:
+        sb.close()
+    assert sm.shape == (2, F, 4) and np.isfinite(sm).all()
+    for s_, (lo, hi) in enumerate([(100, 200), (-5000, 5000)]):
+        for f in range(F):
+            own = oracle_mod.fd_estimate(s[s_, f].astype(np.float64), int(fs), np.float32(lo), np.float32(hi), 0.0)
+            assert np.isfinite(own).all() and np.abs(sm[s_, f] - own).max() <= TOL_REDUCTION, (s_, f, sm[s_, f], own)
+    assert (sm[0, :, 1] == 0.0).all() and (sm[0, :, 2] == 0.0).all() and (sm[0, :, 3] == np.float32(-120.0)).all() and (sm[0, :, 0] < -20.0).all()
+    assert np.array_equal(bits(gate_values(gate)), bits(sm)) and (gate[0]["open"] == 1).all() and (gate[1]["open"] == 0).all()
+    assert np.array_equal(bits(as_c64(blk)[0]), bits(y[0])) and not blk[1].any()
 
 
 # 5

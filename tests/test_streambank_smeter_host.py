@@ -77,7 +77,9 @@ def test_binding_structure_matches_the_header(P, tmp_path):
 
 def test_host_twin_equals_the_oracle(P, oracle_mod):
     """The twin is the reference's serial loop in double over the same libm; it reports float (the header's float out[4], what the device
-    reports), so the oracle's doubles are narrowed the same way before the comparison: 1e-9 dB, NaN for NaN."""
+    reports), so the oracle's doubles are narrowed the same way before the comparison: 1e-9 dB.  The (100, 200) window has bpBins == 0 and
+    one bin in band: avg is x / 0 = +inf -> 0 dB, and the noise average 0 / 0, which the reference's qBound returns as its lower bound:
+    snr 0, floor -120 (tests/test_reference_pins.py, cases fdestimate_*).  Every output of every window is finite."""
     seen = 0
     for bins, rate, windows in CASES:
         row = db_row(bins, 1000 + bins)
@@ -87,14 +89,11 @@ def test_host_twin_equals_the_oracle(P, oracle_mod):
             name = "%d bins, (%g, %g)" % (bins, lo, hi)
             print(name, want, got)
             if (lo, hi) == (100, 200):
-                assert want[1] == 0.0 and np.isnan(want[2]) and np.isnan(want[3]), (name, want)
-            else:
-                assert np.isfinite(want).all(), (name, want)
+                assert want[1] == 0.0 and want[2] == 0.0 and want[3] == -120.0, (name, want)
+                assert got[1] == 0.0 and got[2] == 0.0 and got[3] == np.float32(-120.0), (name, got)
+            assert np.isfinite(want).all() and np.isfinite(got).all(), (name, want, got)
             for k in range(4):
-                if np.isnan(want[k]):
-                    assert np.isnan(got[k]), (name, k, got)
-                else:
-                    assert abs(float(got[k]) - float(np.float32(want[k]))) <= 1e-9, (name, k, got, want)
+                assert abs(float(got[k]) - float(np.float32(want[k]))) <= 1e-9, (name, k, got, want)
             seen += 1
     assert seen == 15
     # the peak bin inside the window: peakDb is the -30 dB bin, and avgDb follows it
@@ -103,12 +102,14 @@ def test_host_twin_equals_the_oracle(P, oracle_mod):
 
 
 def test_mixer_frequency_moves_the_window(P, oracle_mod):
+    """1.5 MHz clamps the mixer's bin to `bins`: the window is what is left of (-5000, 5000) under the upper edge; every value is finite"""
     row = db_row(2048, 5)
     for mixer in (-400000.0, 123456.0, 1.5e6):
         want = oracle_mod.fd_estimate(row.astype(np.float64), 2048000, -5000, 5000, mixer)
         got = P.signal_strength_row(row, 2048000, -5000, 5000, mixer)
+        assert np.isfinite(want).all() and np.isfinite(got).all(), (mixer, want, got)
         for k in range(4):
-            assert (np.isnan(want[k]) and np.isnan(got[k])) or abs(float(got[k]) - float(np.float32(want[k]))) <= 1e-9, (mixer, k, got, want)
+            assert abs(float(got[k]) - float(np.float32(want[k]))) <= 1e-9, (mixer, k, got, want)
 
 
 def test_refusals_without_a_device(P):
