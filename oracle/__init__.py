@@ -115,6 +115,9 @@ def lib():
         L.po_receiver_rds_polled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.po_fd_estimate.restype = C.c_double
         L.po_fd_estimate.argtypes = [_dp, C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_double, _dp]
+        L.po_map_fft_to_screen.restype = None
+        L.po_map_fft_to_screen.argtypes = [_dp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_int32)]
         L.po_agc_new.restype = C.c_void_p
         L.po_agc_new.argtypes = [C.c_double]
         L.po_agc_free.argtypes = [C.c_void_p]
@@ -519,6 +522,16 @@ def fd_estimate(spectrum_db, spectrum_rate, bp_lo, bp_hi, mixer_freq):
     out = np.empty(4, dtype=np.float64)
     lib().po_fd_estimate(_ptr(sp), len(sp), int(spectrum_rate), float(bp_lo), float(bp_hi), float(mixer_freq), _ptr(out))
     return out
+
+
+def map_fft_to_screen(db, fft_size, sample_rate, y_pixels, x_pixels, max_db, min_db, start_freq, stop_freq):
+    """FFT::mapFFTToScreen of one dB row (fft_size doubles) -> int32 [x_pixels]"""
+    row = np.ascontiguousarray(db, dtype=np.float64)
+    assert row.ndim == 1 and len(row) >= int(fft_size)
+    out = np.zeros(max(1, int(x_pixels)), dtype=np.int32)
+    lib().po_map_fft_to_screen(_ptr(row), int(fft_size), float(sample_rate), int(y_pixels), int(x_pixels), float(max_db), float(min_db),
+                               int(start_freq), int(stop_freq), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    return out[: int(x_pixels)]
 
 
 class _AnfS(C.Structure):

@@ -1603,6 +1603,65 @@ double po_fd_estimate(const double *spectrum, int bins, uint32_t rate, float bp_
     return avg_db;
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * FFT::mapFFTToScreen -- pebblelib/fft.cpp:411-534, pebblelib/db.h:72-82
+ * The reference's loop as written, every implicit conversion made explicit: qint32 * float and qint32 + float are float,
+ * powerdB and yPixel are qint32 (the double / float value truncates), yScaleFactor is a double quotient narrowed to float.
+ * A conversion whose value does not fit int32 is undefined in C; an x86-64 build gives INT_MIN (cvttss2si / cvttsd2si),
+ * which is written out here so that the oracle's answer does not depend on the compiler.  The int sums wrap as there.
+ * ---------------------------------------------------------------------------------------------- */
+static int32_t po_trunc_f(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (int32_t)f : INT32_MIN; }
+static int32_t po_trunc_d(double d) { return (d > -2147483649.0 && d < 2147483648.0) ? (int32_t)d : INT32_MIN; }
+
+void po_map_fft_to_screen(const double *in, int32_t fft_size, double sample_rate, int32_t y_pixels, int32_t x_pixels, double max_db,
+                          double min_db, int32_t start_freq, int32_t stop_freq, int32_t *out)
+{
+    const float bins_per_hz = (float)fft_size / (float)sample_rate;
+    int32_t bin_low = po_trunc_f((float)start_freq * bins_per_hz);
+    bin_low = (int32_t)((uint32_t)bin_low + (uint32_t)(fft_size / 2));
+    int32_t bin_high = po_trunc_f((float)stop_freq * bins_per_hz);
+    bin_high = (int32_t)((uint32_t)bin_high + (uint32_t)(fft_size / 2));
+    const int32_t bins_to_plot = (int32_t)((uint32_t)bin_high - (uint32_t)bin_low);
+    const float pixels_per_bin = (float)x_pixels / (float)bins_to_plot;
+    const float bins_per_pixel = (float)bins_to_plot / (float)x_pixels;
+    const double db_range = max_db - min_db;
+    const float y_scale = (float)(-y_pixels / db_range);
+    int32_t last = -1, power_db, bin, y;
+    if (bins_to_plot > x_pixels) {
+        for (int32_t i = 0; i < x_pixels; i++) {
+            bin = po_trunc_f((float)bin_low + ((float)i * bins_per_pixel));
+            if (bin < 0) {
+                power_db = -120; /* DB::minDb, without the maxdB offset */
+            } else if (bin >= fft_size) {
+                power_db = -120;
+            } else if (last > 0 && bin != last + 1) {
+                const int32_t skipped = bin - last;
+                double tmp = 0;
+                for (int j = 0; j < skipped; j++) tmp += pow(10, in[last + j] / 10.0); /* DB::dBToPower */
+                power_db = po_trunc_d(po_power_to_db(tmp / skipped) - max_db);
+            } else {
+                power_db = po_trunc_d(in[bin] - max_db);
+            }
+            last = bin;
+            y = po_trunc_f((y_scale * (float)power_db) - 1);
+            out[i] = y < 0 ? 0 : (y > y_pixels - 1 ? y_pixels - 1 : y); /* qBound(0, yPixel, yPixels - 1) */
+        }
+    } else {
+        for (int32_t i = 0; i < x_pixels; i++) {
+            bin = po_trunc_f((float)bin_low + ((float)i / pixels_per_bin));
+            if (bin < 0) {
+                power_db = -120;
+            } else if (bin >= fft_size) {
+                power_db = -120;
+            } else {
+                power_db = po_trunc_d(in[bin] - max_db);
+            }
+            y = po_trunc_f((y_scale * (float)power_db) - 1);
+            out[i] = y < 0 ? 0 : (y > y_pixels - 1 ? y_pixels - 1 : y);
+        }
+    }
+}
+
 struct po_receiver {
     uint32_t fs, n;
     int mode;

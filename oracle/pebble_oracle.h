@@ -221,6 +221,11 @@ void po_anf_process(po_anf *a, const double *in, double *out, int n);
  * open.  out[4] = peakDb, avgDb, snrDb, floorDb.  Returns avgDb.  Integer bin width (quint32 / int) as written. */
 double po_fd_estimate(const double *spectrum, int bins, uint32_t spectrum_rate, float bp_lo, float bp_hi, double mixer_freq, double *out);
 
+/* FFT::mapFFTToScreen (pebblelib/fft.cpp:411-534): one dB row of fft_size doubles -> x_pixels plot heights, serial, glibc pow / log10,
+ * the reference's order of additions.  Conversions that leave int32 give INT_MIN as on x86-64 (undefined in C: not pinned). */
+void po_map_fft_to_screen(const double *in, int32_t fft_size, double sample_rate, int32_t y_pixels, int32_t x_pixels, double max_db,
+                          double min_db, int32_t start_freq, int32_t stop_freq, int32_t *out);
+
 typedef struct po_receiver po_receiver;
 po_receiver *po_receiver_new(uint32_t fs, uint32_t frames_per_buffer, uint32_t spectrum_bins,
                              uint32_t fastfir_fft, uint32_t fastfir_taps);

@@ -215,6 +215,24 @@ static void st_spectrum()
     delete f;
 }
 
+/* mapscreen FFTSIZE FS Y X MAXDB MINDB START STOP: IN is one dB row of FFTSIZE real doubles; the FFT is made as in the spectrum stage
+ * (a buffer of FFTSIZE samples), then FFT::mapFFTToScreen of IN; one record, the X pixels */
+static void st_mapscreen()
+{
+    FFT *f = FFT::factory("ref_driver");
+    f->fftParams(quint32(arg(0)), 0, arg(1), int(arg(0)), WindowFunction::BLACKMANHARRIS);
+    if (g_in.size() != size_t(f->getFFTSize())) {
+        fprintf(stderr, "ref_driver: mapscreen wants %d values\n", f->getFFTSize());
+        exit(2);
+    }
+    int x = int(arg(3));
+    std::vector<qint32> px(x > 0 ? x : 1);
+    f->mapFFTToScreen(g_in.data(), qint32(arg(2)), qint32(x), arg(4), arg(5), qint32(arg(6)), qint32(arg(7)), px.data());
+    std::vector<double> out(px.begin(), px.begin() + (x > 0 ? x : 0));
+    rec(out.data(), out.size());
+    delete f;
+}
+
 /* agc FS N (MODE THRESHOLD)...: one block per pair, setAgcMode when the pair changes; one record per block */
 static void st_agc()
 {
@@ -355,7 +373,7 @@ int main(int argc, char **argv)
 {
     static const struct { const char *name; void (*fn)(); } stages[] = {
         {"mixer", st_mixer}, {"decimator", st_decimator}, {"downconvert", st_downconvert}, {"fastfir", st_fastfir},
-        {"fir", st_fir}, {"iir", st_iir}, {"resampler", st_resampler}, {"spectrum", st_spectrum}, {"agc", st_agc},
+        {"fir", st_fir}, {"iir", st_iir}, {"resampler", st_resampler}, {"spectrum", st_spectrum}, {"mapscreen", st_mapscreen}, {"agc", st_agc},
         {"nb", st_nb}, {"anf", st_anf}, {"iqbalance", st_iqbalance}, {"dcremoval", st_dcremoval}, {"fdestimate", st_fdestimate},
         {"goertzel", st_goertzel}, {"sampleclock", st_sampleclock}, {"movingavg", st_movingavg}};
     if (argc < 4) {

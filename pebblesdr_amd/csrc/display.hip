@@ -17,43 +17,7 @@ static void launch_map(hipStream_t s, const float *in, long long stream_pitch, l
     launch(k_screen_map<G>, dim3((unsigned)blocks), dim3(256), s, in, stream_pitch, frame_pitch, n_frames, n_items, geoms, sh, out);
 }
 
-// the lane group of a launch whose widest averaged pixel covers bpp bins (0: no averaged pixel)
-static int map_lane_group(float bpp)
-{
-    int G = 1;
-    while (G < 64 && (float)(2 * G) <= bpp) G *= 2;
-    return G;
-}
-
-// one chunk of run_screen_map: the geometries of streams s0 .. s0 + ns - 1 into g (per_stream; else the one geometry every stream uses)
-// and the lane group of the chunk's launch: the widest averaged pixel sizes it
-static int map_chunk_plan(int32_t fft_size, double sample_rate, const int32_t *edges, bool per_stream, int s0, int ns, int32_t x_pixels, MapGeom *g)
-{
-    const int n = per_stream ? ns : 1;
-    float bpp = 0.0f;
-    for (int k = 0; k < n; k++) {
-        const int32_t *e = edges + 2 * (per_stream ? s0 + k : 0);
-        g[k] = map_geom(fft_size, sample_rate, e[0], e[1], x_pixels);
-        if (g[k].bins_to_plot > x_pixels) bpp = std::max(bpp, g[k].bins_per_pixel);
-    }
-    return map_lane_group(bpp);
-}
-
-// what run_screen_map below does with each stream's rows, as a table: the receiver's display ring packs with it (k_display_panes)
-void map_row_plan(int32_t fft_size, double sample_rate, const int32_t *edges, bool per_stream, int n_streams, int32_t x_pixels, MapGeom *geoms, int *groups)
-{
-    const int chunk = per_stream ? kMapMaxGeom : n_streams;
-    for (int s0 = 0; s0 < n_streams; s0 += chunk) {
-        const int ns = std::min(chunk, n_streams - s0);
-        MapGeom g[kMapMaxGeom];
-        const int G = map_chunk_plan(fft_size, sample_rate, edges, per_stream, s0, ns, x_pixels, g);
-        for (int k = 0; k < ns; k++) {
-            geoms[s0 + k] = g[per_stream ? k : 0];
-            groups[s0 + k] = G;
-        }
-    }
-}
-
+// (the lane group of a launch and of each stream's rows: map_lane_group / map_chunk_plan / map_row_plan, screen_geom.h)
 int run_screen_map(hipStream_t s, const float *in, long long stream_pitch, long long frame_pitch, int n_streams, int n_frames, int32_t fft_size,
                    double sample_rate, const int32_t *edges, bool per_stream, int32_t y_pixels, int32_t x_pixels, double max_db, double min_db,
                    int32_t *out)

@@ -25,78 +25,20 @@
 #pragma once
 #include <climits>
 #include "common.h"
+#include "screen_geom.h"
 
 struct pebblegpu_screen_map;  // include/pebblegpu.h
 
 namespace pg {
 
-constexpr int kMapMaxGeom = 64;  // per-stream geometries carried in one launch's arguments (zoomed spectra with per-channel offsets)
 constexpr int kMinDb = -120;     // DB::minDb (pebblelib/db.cpp)
 
-__host__ __device__ inline int32_t x86_trunc(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (int32_t)f : INT32_MIN; }
-__host__ __device__ inline int32_t x86_trunc(double d) { return (d > -2147483649.0 && d < 2147483648.0) ? (int32_t)d : INT32_MIN; }
-
-// one (startFreq, stopFreq) against one transform size and rate
-struct MapGeom {
-    int32_t bin_low, bins_to_plot;
-    float pixels_per_bin, bins_per_pixel;
-};
+// x86_trunc, MapGeom, MapShared, map_geom, map_y_scale, map_bin, map_y and the lane-group plan (map_lane_group, map_chunk_plan,
+// map_row_plan): screen_geom.h, the part of the map a host evaluates too
 struct MapGeoms {
     int n;  // 1: every row uses g[0]; else row stream s (relative to the launch) uses g[s]
     MapGeom g[kMapMaxGeom];
 };
-struct MapShared {
-    int32_t fft_size, x_pixels, y_pixels;
-    float y_scale;
-    double max_db;
-};
-
-inline MapGeom map_geom(int32_t fft_size, double sample_rate, int32_t start_freq, int32_t stop_freq, int32_t x_pixels)
-{
-#pragma clang fp contract(off)
-    const float bins_per_hz = (float)fft_size / (float)sample_rate;
-    const int32_t lo = x86_trunc((float)start_freq * bins_per_hz), hi = x86_trunc((float)stop_freq * bins_per_hz);
-    MapGeom g;
-    g.bin_low = (int32_t)((uint32_t)lo + (uint32_t)(fft_size / 2));
-    const int32_t bin_high = (int32_t)((uint32_t)hi + (uint32_t)(fft_size / 2));
-    g.bins_to_plot = (int32_t)((uint32_t)bin_high - (uint32_t)g.bin_low);
-    g.pixels_per_bin = (float)x_pixels / (float)g.bins_to_plot;
-    g.bins_per_pixel = (float)g.bins_to_plot / (float)x_pixels;
-    return g;
-}
-
-// (a double division, correctly rounded on the device too: the packing kernels of a ring with auto-scale on call it per row and get the host's bits)
-__host__ __device__ inline float map_y_scale(int32_t y_pixels, double max_db, double min_db)
-{
-#pragma clang fp contract(off)
-    const double db_range = max_db - min_db;
-    return (float)(-y_pixels / db_range);
-}
-
-// the bin pixel i reads (fft.cpp:474 / :513)
-__host__ __device__ inline int32_t map_bin(const MapGeom &g, bool averaged, int32_t i)
-{
-#pragma clang fp contract(off)
-    const float fi = (float)i;
-    float off;
-    if (averaged) {
-        off = fi * g.bins_per_pixel;
-    } else {
-#ifdef __HIP_DEVICE_COMPILE__
-        off = __fdiv_rn(fi, g.pixels_per_bin);
-#else
-        off = fi / g.pixels_per_bin;
-#endif
-    }
-    return x86_trunc((float)g.bin_low + off);
-}
-
-__host__ __device__ inline int32_t map_y(float y_scale, int32_t power_db, int32_t y_pixels)
-{
-#pragma clang fp contract(off)
-    const int32_t y = x86_trunc(y_scale * (float)power_db - 1.0f);
-    return y < 0 ? 0 : (y > y_pixels - 1 ? y_pixels - 1 : y);  // qBound(0, y, yPixels - 1)
-}
 
 // powerdB of pixel i of the dB row x (fft.cpp:470-527), for the G lanes that own the pixel: every lane of the group calls it with the
 // same arguments and gets the same value.  Shared by k_screen_map and the display ring's packing kernel (k_display_map), so a block's
@@ -427,9 +369,6 @@ static __global__ __launch_bounds__(256) void k_display_panes(DisplayPaneArgs p0
     }
 }
 
-// the lane group run_screen_map gives each of n_streams rows: per chunk of kMapMaxGeom streams by the chunk's widest averaged pixel
-// (per_stream), one for all otherwise.  geoms / groups: n_streams entries each
-void map_row_plan(int32_t fft_size, double sample_rate, const int32_t *edges, bool per_stream, int n_streams, int32_t x_pixels, MapGeom *geoms, int *groups);
 // up to two panes in one launch on `s` (n_panes 1 or 2; a pane of 0 rows is left out, none left: no launch)
 // su / trailer_tab (auto-scale): the ranges' table and where the launch's first workgroup writes the trailer
 int run_display_panes(hipStream_t s, const DisplayPaneArgs *panes, int n_panes, const ScaleUse &su = ScaleUse{}, const DisplayRow *trailer_tab = nullptr);

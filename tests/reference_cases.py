@@ -257,6 +257,13 @@ def _fdestimate(rate, mixer, bands):
     return run
 
 
+def _mapscreen(r):
+    def run(O, db):
+        px = O.map_fft_to_screen(db, r.bins, r.fs, r.y, r.x, r.max_db, r.min_db, r.start, r.stop)
+        return [("x", px.astype(np.float64))]
+    return run
+
+
 # ---- the Morse restatement (tests/morse_ref.py): its Goertzel, TH_PEAK, clock and threshold-filter arithmetic.  Morse::stateMachine,
 # updateThresholds and findBestGoertzelN live in the Qt plugin, not in pebblelib: they stay pinned by hand (tests/test_morse_host.py)
 def _morse_goertzel(rate, n, freq, switch_at, freq2):
@@ -460,6 +467,13 @@ def _build_cases():
     for name, rate, sbins, lo, hi, mixer, _ in S.ROWS:
         C.append(Case("fdestimate_" + name, "fdestimate", [rate, 2048, rate, mixer, lo, hi], lambda name=name: S.row_spectrum(name),
                       _fdestimate(rate, mixer, [(lo, hi)])))
+    # FFT::mapFFTToScreen on every pinned row of tests/screen_cases.py (the rows whose float -> int conversions are all in range): one dB
+    # row of float32 values in, the pixels out; the driver and the oracle run the same libm in the same order, so the bar is 0
+    from tests import screen_cases as SC
+    for r in SC.ROWS:
+        if r.pinned:
+            C.append(Case("mapscreen_" + r.name, "mapscreen", [r.bins, r.fs, r.y, r.x, r.max_db, r.min_db, r.start, r.stop],
+                          lambda name=r.name: SC.row_input(name), _mapscreen(r)))
     # the Morse modem's pebblelib classes at its four modem rates (no stage; 6000; 4687 of 4687.5; 7812 of 7812.5), both tones, the
     # tone moved to the other side on a running filter (Morse::setDemodMode): GoertzelOOK TH_PEAK, SampleClock, MovingAvgFilter(8)
     from tests import morse_ref as M

@@ -16,7 +16,8 @@ selection, delay lines and short-frame fallback, and every serial fp64 stage who
 resampler, AGC, the blankers, ANF, IQBalance, DCRemoval, fdEstimate).  The Morse restatement (tests/morse_ref.py) is held to the
 pebblelib classes the modem is made of, driven the way morse.cpp:160-246 and :761-894 drive them: GoertzelOOK with TH_PEAK at the four
 modem rates of tests/morse_cases.py and both tones, the tone moved on a running filter (powers, decisions, peak averages, the count
-left in the block), SampleClock::uSecDelta, MovingAvgFilter(8).  The two primitives are cross-checked once each through
+left in the block), SampleClock::uSecDelta, MovingAvgFilter(8).  FFT::mapFFTToScreen is pinned on every row of tests/screen_cases.py whose
+float -> int conversions are all in range (cases mapscreen_*, one dB row in, the pixels out, exact).  The two primitives are cross-checked once each through
 reference code that does not use the stand-in: the decimator through HalfbandFilter::process (decimator.cpp:661-685) and the
 spectrum through the in-tree Ooura transform (magnitudes only: FastFIR is mirrored on that back end).
 
@@ -92,7 +93,7 @@ def test_reference_pin(oracle_mod, name):
 def test_every_stage_of_the_table_has_a_case():
     stages = {c.stage for c in R.cases()}
     assert stages == {"mixer", "decimator", "downconvert", "fastfir", "fir", "iir", "resampler", "spectrum", "agc", "nb", "anf",
-                      "iqbalance", "dcremoval", "fdestimate", "goertzel", "sampleclock", "movingavg"}
+                      "iqbalance", "dcremoval", "fdestimate", "goertzel", "sampleclock", "movingavg", "mapscreen"}
     assert all(c.bar <= R.MAX_BAR and c.bar_db <= R.MAX_BAR_DB for c in R.cases())
     assert all(os.path.getsize(c.fixture) < 16384 for c in R.cases())
 

@@ -1,7 +1,8 @@
 """CPU tier of the screen mapping (FFT::mapFFTToScreen, pebblelib/fft.cpp:411-534).
 
 The numpy restatement in tests/screen_map_ref.py is pinned on hand-worked answers for each quirk that decides an output, and
-against a pixel-by-pixel loop on random cases; the C++ adapter is shown to take SignalSpectrum's call sites as written
+against a pixel-by-pixel loop on random cases (tests/test_screen_cases_host.py holds both to the oracle's serial loop, which the
+mapscreen_* reference pins hold to the reference's compiled code); the C++ adapter is shown to take SignalSpectrum's call sites as written
 (application/signalspectrum.cpp:58-59, 111, 146) by compiling them against include/pebblegpu_steps.hpp and linking libpebblegpu.so."""
 import os
 import subprocess
