@@ -397,7 +397,7 @@ class DemodAM:
 
 class _NfmS(C.Structure):
     _fields_ = [("fs", C.c_double)] + [(n, C.c_float) for n in ("err_dc", "nco_freq", "nco_lo", "nco_hi", "phase", "alpha", "beta",
-                                                                "dc_alpha", "out_gain")] + [("lp", _FirS)]
+                                                                "dc_alpha", "out_gain")] + [("lp", _FirS), ("n_clamped", C.c_int)]
 
 
 class DemodNFM:

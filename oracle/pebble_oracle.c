@@ -623,7 +623,8 @@ void po_demod_am_process(po_demod_am *d, const double *in, double *out, int n) /
 }
 
 /* ------------------------------------------------------------------------------------------------
- * NFM demod (PLL) -- application/demod/demod_nfm.cpp.  parity unpinned: the reference offers no vector for it.
+ * NFM demod (PLL) -- application/demod/demod_nfm.cpp.  Pinned bit for bit to Demod_NFM::processBlockNCO compiled from the
+ * reference tree (tests/test_reference_pins.py, cases demod_nfm_*).
  * ---------------------------------------------------------------------------------------------- */
 void po_demod_nfm_init(po_demod_nfm *d, double fs) /* ctor :24-37, init :44-66 */
 {
@@ -646,10 +647,11 @@ void po_demod_nfm_process(po_demod_nfm *d, const double *in, double *out, int n)
         double ti = nco_cos * in[2 * i + 1] + nco_sin * in[2 * i];
         double phzerror = -atan2(ti, tr);
         d->nco_freq = (float)((double)d->nco_freq + ((double)d->beta * phzerror));
-        if (d->nco_freq > d->nco_hi) d->nco_freq = d->nco_hi;
-        else if (d->nco_freq < d->nco_lo) d->nco_freq = d->nco_lo;
+        if (d->nco_freq > d->nco_hi) { d->nco_freq = d->nco_hi; d->n_clamped++; }
+        else if (d->nco_freq < d->nco_lo) { d->nco_freq = d->nco_lo; d->n_clamped++; }
         d->phase = (float)((double)d->phase + ((double)d->nco_freq + (double)d->alpha * phzerror));
-        d->err_dc = (float)((1.0 - (double)d->dc_alpha) * (double)d->err_dc + (double)d->dc_alpha * (double)d->nco_freq);
+        /* :249: (1.0 - float) * float is a double product; float * float is a FLOAT product, rounded before the double sum */
+        d->err_dc = (float)((1.0 - (double)d->dc_alpha) * (double)d->err_dc + (double)(d->dc_alpha * d->nco_freq));
         float o = (d->nco_freq - d->err_dc) * d->out_gain; /* float arithmetic; CPX = real assigns imag 0 */
         out[2 * i] = (double)o;
         out[2 * i + 1] = 0.0;
@@ -659,7 +661,8 @@ void po_demod_nfm_process(po_demod_nfm *d, const double *in, double *out, int n)
 }
 
 /* ------------------------------------------------------------------------------------------------
- * SAM demod (PLL) -- application/demod/demod_sam.cpp.  parity unpinned: the reference offers no vector for it.
+ * SAM demod (PLL) -- application/demod/demod_sam.cpp.  Pinned bit for bit to Demod_SAM::processBlock compiled from the
+ * reference tree (tests/test_reference_pins.py, cases demod_sam_*).
  * ---------------------------------------------------------------------------------------------- */
 void po_demod_sam_init(po_demod_sam *d, double fs) /* ctor :5-32; sampleRate is quint32 there */
 {
@@ -1061,7 +1064,7 @@ static void po_rds_process(struct po_rds *r, int n, const double *cpx)
         r->sync = (double *)realloc(r->sync, (size_t)len * sizeof(double));
     }
     double *mag = r->sync, *data = r->data;
-    for (int i = 0; i < len; i++) { /* processRdsPll, :542-569 (fsincos there; sin and cos here) */
+    for (int i = 0; i < len; i++) { /* processRdsPll, :542-569 (x87 fsincos there; sin and cos here: bit for bit all the same on the pinned cases) */
         const double sn = sin(r->nco_phase), cs = cos(r->nco_phase);
         const double tr = cs * raw[2 * i] - sn * raw[2 * i + 1];
         const double ti = cs * raw[2 * i + 1] + sn * raw[2 * i];

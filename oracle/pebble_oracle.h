@@ -9,8 +9,10 @@
  * unmodified against stand-in Qt/vDSP headers into oracle/_ref/ref_driver (oracle/ref_build/), and
  * tests/test_reference_pins.py compares every time-domain stage below with them on the same fp64 input: mixer,
  * decimator, CDownConvert, FastFIR, CFir, CIir, resampler, spectrum, AGC, blankers, ANF, IQBalance, DCRemoval,
- * fdEstimate -- all bit for bit (DESIGN.md section 3 has the table).  Not pinned that way: the two vDSP primitives
- * (the stand-in is our code), FastFIR at 8192/4097 and the demodulators (demod.h needs a uic-generated header).
+ * fdEstimate, and the demodulators Demod_AM, Demod_SAM, Demod_NFM and Demod_WFM (mono, stereo with its pilot loop, the RDS
+ * branch up to the group queue) -- all bit for bit (DESIGN.md section 3 has the table).  Not pinned that way: the two vDSP
+ * primitives (the stand-in is our code), FastFIR at 8192/4097, CRdsDecode, and Demod::processBlock's dispatch itself (demod.cpp
+ * brings the GUI with it; the driver restates it by its call sequence).
  * The reference ships no tests and no golden vectors.
  * The oracle is also pinned by (1) the one worked known-answer table the reference holds
  * (pebblelib/fft.cpp:363-369, -10 dB tone -> spectrum peak per FFT size), (2) the outputs of
@@ -129,6 +131,7 @@ typedef struct {
     double fs;
     float err_dc, nco_freq, nco_lo, nco_hi, phase, alpha, beta, dc_alpha, out_gain;
     po_fir lp;
+    int n_clamped;      /* for the tests: samples whose nco_freq a clamp replaced */
 } po_demod_nfm;
 void po_demod_nfm_init(po_demod_nfm *d, double fs);
 void po_demod_nfm_process(po_demod_nfm *d, const double *in, double *out, int n);

@@ -43,12 +43,21 @@
 #include "goertzel.h"
 #include "movingavgfilter.h"
 #include "sampleclock.h"
+#include "demod_am.h"
+#include "demod_sam.h"
+#include "demod_nfm.h"
+#include "demod_wfm.h"
 #undef private
 #undef protected
 
 Global *global = nullptr;
 /* what moc would generate for the one signal the driven classes declare */
 void SignalStrength::newSignalStrength(double, double, double, double, double) {}
+/* The base class of the four demodulators lives in the application's demod.cpp, which brings the GUI with it.  The demodulators use
+ * nothing of it but its constructor and destructor; these two are this project's text, written from the declarations in demod.h (the
+ * destructor is the class's key function, so the vtable and the typeinfo come with it) */
+Demod::Demod(quint32 r, quint32 n) : ProcessStep(r, n) {}
+Demod::~Demod() {}
 
 static std::vector<double> g_in;
 static FILE *g_out;
@@ -369,13 +378,145 @@ static void st_movingavg()
     rec(out.data(), out.size());
 }
 
+/* The call scripts of the demodulator stages: the lengths from argument FIRST on (with STEP arguments per call); a call never exceeds
+ * the buffer size the class was constructed with, nor PHZBUF_SIZE for WFM */
+static int call_len(size_t i, quint32 n, size_t pos)
+{
+    int len = int(g_arg[i]);
+    if (len < 0 || quint32(len) > n || len > PHZBUF_SIZE || pos + size_t(len) > in_len()) {
+        fprintf(stderr, "ref_driver: call of %d samples at %zu (buffer %u, input %zu)\n", len, pos, n, in_len());
+        exit(2);
+    }
+    return len;
+}
+
+/* demod_am FS N (LEN BW)...: Demod::processBlock's dmAM (demod.cpp:104-107): setBandwidth where BW != 0, then processBlockFiltered;
+ * one record per call */
+static void st_demod_am()
+{
+    quint32 n = quint32(arg(1));
+    Demod_AM d(int(arg(0)), int(n));
+    std::vector<CPX> out(n);
+    size_t pos = 0;
+    for (size_t i = 2; i + 1 < g_arg.size(); i += 2) {
+        int len = call_len(i, n, pos);
+        if (g_arg[i + 1] != 0)
+            d.setBandwidth(g_arg[i + 1]);
+        d.processBlockFiltered(in_cpx() + pos, out.data(), len);
+        rec_cpx(out.data(), size_t(len));
+        pos += size_t(len);
+    }
+}
+
+/* demod_sam FS N LEN...: dmSAM (demod.cpp:108-110), Demod_SAM::processBlock; one record per call */
+static void st_demod_sam()
+{
+    quint32 n = quint32(arg(1));
+    Demod_SAM d(int(arg(0)), int(n));
+    std::vector<CPX> out(n);
+    size_t pos = 0;
+    for (size_t i = 2; i < g_arg.size(); i++) {
+        int len = call_len(i, n, pos);
+        d.processBlock(in_cpx() + pos, out.data(), len);
+        rec_cpx(out.data(), size_t(len));
+        pos += size_t(len);
+    }
+}
+
+/* demod_nfm FS N LEN...: dmFMN (demod.cpp:111-115), Demod_NFM::processBlockNCO; one record per call */
+static void st_demod_nfm()
+{
+    quint32 n = quint32(arg(1));
+    Demod_NFM d(int(arg(0)), int(n));
+    std::vector<CPX> out(n);
+    size_t pos = 0;
+    for (size_t i = 2; i < g_arg.size(); i++) {
+        int len = call_len(i, n, pos);
+        d.processBlockNCO(in_cpx() + pos, out.data(), len);
+        rec_cpx(out.data(), size_t(len));
+        pos += size_t(len);
+    }
+}
+
+/* Demod_WFM leaves m_RdsLastData (and its work arrays) uninitialised; it is constructed over zeroed memory here so that the first
+ * bit decision is defined */
+static Demod_WFM *new_wfm(int fs, int n)
+{
+    void *mem = calloc(1, sizeof(Demod_WFM));
+    return new (mem) Demod_WFM(fs, n);
+}
+static void delete_wfm(Demod_WFM *d)
+{
+    d->~Demod_WFM();
+    free(d);
+}
+
+/* demod_wfm_mono FS N LEN...: Demod::fmMono (demod.cpp:169-175), processDataMono, which filters its input in place; per call two
+ * records: the returned count, the output */
+static void st_demod_wfm_mono()
+{
+    quint32 n = quint32(arg(1));
+    Demod_WFM *d = new_wfm(int(arg(0)), int(n));
+    std::vector<CPX> out(n);
+    size_t pos = 0;
+    for (size_t i = 2; i < g_arg.size(); i++) {
+        int len = call_len(i, n, pos);
+        std::vector<CPX> work(in_cpx() + pos, in_cpx() + pos + len);
+        int k = d->processDataMono(len, work.data(), out.data());
+        rec1(k);
+        rec_cpx(out.data(), size_t(k));
+        pos += size_t(len);
+    }
+    delete_wfm(d);
+}
+
+/* demod_wfm_stereo FS N LEN...: Demod::fmStereo (demod.cpp:198-226): processDataStereo (its input buffer is its scratch), then
+ * getStereoLock, then ONE getNextRdsGroupData; per call four records: the returned count, the output, (changed, lock), (got, BlockA,
+ * BlockB, BlockC, BlockD).  After the last call the queue is drained into one more record, four words per group */
+static void st_demod_wfm_stereo()
+{
+    quint32 n = quint32(arg(1));
+    Demod_WFM *d = new_wfm(int(arg(0)), int(n));
+    std::vector<CPX> out(n);
+    size_t pos = 0;
+    for (size_t i = 2; i < g_arg.size(); i++) {
+        int len = call_len(i, n, pos);
+        std::vector<CPX> work(in_cpx() + pos, in_cpx() + pos + len);
+        int k = d->processDataStereo(len, work.data(), out.data());
+        rec1(k);
+        rec_cpx(out.data(), size_t(k));
+        int lock = 0;
+        int changed = d->getStereoLock(&lock);
+        double lk[2] = {double(changed), double(lock)};
+        rec(lk, 2);
+        tRDS_GROUPS g = {0, 0, 0, 0};
+        int got = d->getNextRdsGroupData(&g); /* 0 for an empty queue (the words stay 0) and for a group equal to the one before */
+        double gr[5] = {double(got), double(g.BlockA), double(g.BlockB), double(g.BlockC), double(g.BlockD)};
+        rec(gr, 5);
+        pos += size_t(len);
+    }
+    std::vector<double> rest;
+    while (d->m_RdsQHead != d->m_RdsQTail) {
+        tRDS_GROUPS g = {0, 0, 0, 0};
+        d->getNextRdsGroupData(&g);
+        rest.push_back(g.BlockA);
+        rest.push_back(g.BlockB);
+        rest.push_back(g.BlockC);
+        rest.push_back(g.BlockD);
+    }
+    rec(rest.data(), rest.size());
+    delete_wfm(d);
+}
+
 int main(int argc, char **argv)
 {
     static const struct { const char *name; void (*fn)(); } stages[] = {
         {"mixer", st_mixer}, {"decimator", st_decimator}, {"downconvert", st_downconvert}, {"fastfir", st_fastfir},
         {"fir", st_fir}, {"iir", st_iir}, {"resampler", st_resampler}, {"spectrum", st_spectrum}, {"mapscreen", st_mapscreen}, {"agc", st_agc},
         {"nb", st_nb}, {"anf", st_anf}, {"iqbalance", st_iqbalance}, {"dcremoval", st_dcremoval}, {"fdestimate", st_fdestimate},
-        {"goertzel", st_goertzel}, {"sampleclock", st_sampleclock}, {"movingavg", st_movingavg}};
+        {"goertzel", st_goertzel}, {"sampleclock", st_sampleclock}, {"movingavg", st_movingavg}, {"demod_am", st_demod_am},
+        {"demod_sam", st_demod_sam}, {"demod_nfm", st_demod_nfm}, {"demod_wfm_mono", st_demod_wfm_mono},
+        {"demod_wfm_stereo", st_demod_wfm_stereo}};
     if (argc < 4) {
         fprintf(stderr, "usage: ref_driver STAGE IN OUT [numbers...]\n");
         return 2;

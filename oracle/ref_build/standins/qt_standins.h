@@ -7,6 +7,7 @@
 #include <cassert>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -29,6 +30,7 @@ typedef double qreal;
 #define signals public
 #define slots
 #define emit
+#define Q_DECLARE_INTERFACE(a, b)
 
 /* The order of the comparisons matters for NaN, where every comparison is false: Qt's published qglobal.h words them
  * qMin(a, b) = (a < b) ? a : b, qMax(a, b) = (a < b) ? b : a, qBound(min, v, max) = qMax(min, qMin(max, v)), so that
@@ -84,6 +86,14 @@ public:
     QObject(QObject * = nullptr) {}
     virtual ~QObject() {}
 };
+/* swallows any value: the device interface passes its arguments and results through it, and no driven class reads one */
+class QVariant {
+public:
+    QVariant() {}
+    template <typename T> QVariant(const T &) {}
+};
+class QStringList {};
+class QWidget;
 class QSize {};
 class QMainWindow {};
 class QScreen {};

@@ -476,7 +476,8 @@ static __global__ __launch_bounds__(64) void k_pll_demod(const float2 *__restric
             if (s.freq > pp.hi) s.freq = pp.hi;
             else if (s.freq < pp.lo) s.freq = pp.lo;
             s.phase = (float)((double)s.phase + ((double)s.freq + (double)pp.alpha * phzerror));
-            s.err_dc = (float)((1.0 - (double)pp.dc_alpha) * (double)s.err_dc + (double)pp.dc_alpha * (double)s.freq);
+            // demod_nfm.cpp:249: (1.0 - float) * float is a double product, float * float a float product rounded before the double sum
+            s.err_dc = (float)((1.0 - (double)pp.dc_alpha) * (double)s.err_dc + (double)__fmul_rn(pp.dc_alpha, s.freq));
             y[i] = make_float2(__fmul_rn(__fsub_rn(s.freq, s.err_dc), pp.out_gain), 0.f);  // float arithmetic; CPX = real: imag 0
             if (blk_len > 0 && --to_blk == 0) {
                 to_blk = blk_len;

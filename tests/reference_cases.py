@@ -86,9 +86,14 @@ def record_error(kind, got, want):
 
 
 class Case:
-    def __init__(self, name, stage, args, make_input, oracle, bar=0.0, bar_db=0.0):
+    """view: what of the records a fixture is made of, [(kind, array)] -> [(kind, array)] (default: all of them, as they are).
+    meta: what the device tier (tests/test_demod_reference_gpu.py) needs to run the case: mode, rate, calls, why"""
+
+    def __init__(self, name, stage, args, make_input, oracle, bar=0.0, bar_db=0.0, view=None, meta=None):
         self.name, self.stage, self.args, self.make_input, self.oracle = name, stage, list(args), make_input, oracle
         self.bar, self.bar_db = bar, bar_db
+        self.view = view if view is not None else (lambda pairs: pairs)
+        self.meta = meta
         assert bar <= MAX_BAR and bar_db <= MAX_BAR_DB
 
     @property
@@ -331,6 +336,247 @@ def _clock_pairs(n):
     return pairs
 
 
+# ---- the demodulators (application/demod/): the driver calls the reference's classes the way Demod::processBlock, fmMono and fmStereo
+# do (demod.cpp:100-141, :169-226); every record is compared exactly.  A call script is a list of lengths, ragged on purpose
+DEMOD_CALLS = (2048, 2048, 1000, 81, 2048, 2048)   # the last call is whole, so that a fixture's tail lies inside it
+DEMOD_N = 2048                                       # the buffer size the classes are constructed with: no call is longer
+
+
+def _split(x, calls):
+    out, pos = [], 0
+    for ln in calls:
+        out.append(x[pos:pos + ln])
+        pos += ln
+    assert pos == len(x)
+    return out
+
+
+def am_fading(fs, n, seed):
+    """tests/demod_cases.am_input's recipe: a carrier fading from 0.5 to 0.1 with two modulating tones, turned in phase, plus noise"""
+    t = np.arange(n) / float(fs)
+    carrier = 0.096 + 0.4 * np.exp(-np.arange(n) / 2500.0)
+    return (carrier * (1 + 0.5 * np.cos(2 * np.pi * 1000 * t + 0.4) + 0.2 * np.cos(2 * np.pi * 3300 * t))) * np.exp(0.7j) + lcg_noise(n, seed, 1e-4)
+
+
+def _demod_am(fs, calls):
+    def run(O, x):
+        d = O.DemodAM(fs)
+        out = []
+        for blk, (_, bw) in zip(_split(x, [c[0] for c in calls]), calls):
+            if bw:
+                d.set_bandwidth(bw)
+            out.append(("v", _il(d.process(blk))))
+        return out
+    return run
+
+
+SAM_OFFSETS = {"lock": 30.0, "down": -40.0, "slip": 1500.0}
+SAM_KINDS = ("lock", "down", "slip", "clamp")
+
+
+def sam_carrier(fs, n, which):
+    """an AM-modulated carrier (800 Hz, depth 0.5) off tune by SAM_OFFSETS[which], plus noise.  "clamp": a stronger carrier (the loop's
+    gain follows the level, demod_sam.cpp:57) whose offset runs from 0 up to +1200 Hz within the first third and down to -1200 Hz by the
+    end, 25 kHz/s at most, which the 100 Hz loop follows: it is taken past pllLimit (1000 Hz) on either side"""
+    t = np.arange(n) / float(fs)
+    if which == "clamp":
+        u = np.arange(n) / float(n)
+        f = 1200.0 * np.where(u < 1 / 3.0, 3 * u, 1 - 3 * (u - 1 / 3.0))
+        return 0.8 * (1 + 0.3 * np.cos(2 * np.pi * 800 * t)) * np.exp(2j * np.pi * np.cumsum(f) / fs) + lcg_noise(n, 8, 1e-3)
+    return (0.3 * (1 + 0.5 * np.cos(2 * np.pi * 800 * t))) * np.exp(2j * np.pi * SAM_OFFSETS[which] * t) + lcg_noise(n, 8, 1e-3)
+
+
+def sam_trace(O, fs, x):
+    """(frequency, phase) of the oracle's loop behind every sample (a second instance, walked sample by sample)"""
+    d = O.DemodSAM(fs)
+    f, p = np.empty(len(x)), np.empty(len(x))
+    for i in range(len(x)):
+        d.process(x[i:i + 1])
+        f[i], p[i] = d.s.freq, d.s.phase
+    return f, p, float(d.s.lo), float(d.s.hi)
+
+
+def _demod_sam(fs, calls, which):
+    def run(O, x):
+        # the branch the input is there for was reached, read from the oracle's own loop state
+        f, p, lo, hi = sam_trace(O, fs, x)
+        jump = np.diff(p)
+        up, down = int((jump > np.pi).sum()), int((jump < -np.pi).sum())   # the second while added 2 pi / the first took 2 pi off
+        hz = f * fs / (2 * np.pi)
+        if which == "lock":       # the loop settles on the carrier (the NCO turns against it) and never touches a clamp
+            assert np.abs(hz[-2048:] + SAM_OFFSETS[which]).max() < 5.0 and f.min() > lo and f.max() < hi, (hz[-1], lo, hi)
+            assert up > down, (up, down)                                     # the phase runs below 0 again and again: demod_sam.cpp:73-74
+        elif which == "down":     # the other way round: the phase runs over 2 pi, demod_sam.cpp:71-72
+            assert np.abs(hz[-2048:] + SAM_OFFSETS[which]).max() < 5.0 and f.min() > lo and f.max() < hi, (hz[-1], lo, hi)
+            assert down > up, (up, down)
+        elif which == "slip":     # 1500 Hz off, beyond the limit: the 100 Hz loop never captures the carrier and never reaches a clamp;
+            # the phase is dragged round by the beat, wrapping many times
+            assert f.min() > lo and f.max() < hi, (f.min(), f.max(), lo, hi)
+            assert up + down >= 10, (up, down)
+        else:                     # both clamps engage (demod_sam.cpp:63-66): exactly the limit is what only their assignments leave
+            assert (f == lo).sum() >= 100 and (f == hi).sum() >= 100, (f.min(), f.max(), lo, hi)
+        d = O.DemodSAM(fs)
+        return [("v", _il(d.process(blk))) for blk in _split(x, calls)]
+    return run
+
+
+NFM_KINDS = ("tone", "clamp", "offset")
+
+
+NFM_CARRIER = {"tone": 0.0, "clamp": 16000.0, "offset": 700.0}
+
+
+def nfm_signal(fs, n, which):
+    """a 1 kHz tone at 3 kHz deviation on a carrier NFM_CARRIER[which] off tune, plus noise.  The static offset of "offset" carries the
+    tone as well: behind the loop's DC removal a bare carrier leaves nothing but the loop's own noise floor (6e-5 rad / sample RMS), on
+    which the reference algorithm fed single-precision samples misses itself by 1e-2 -- a relative error against that measures no kernel.
+    With the offset the float phase counts up to 140 .. 240 rad inside a call, where its last bit is 1.5e-5 rad: fed single-precision
+    samples the reference algorithm misses itself by 2e-7 to 5e-6 over the tail of these cases (by 1.1e-5 on one 8-sample snippet at
+    48 000), against 7e-8 without the offset"""
+    t = np.arange(n) / float(fs)
+    return 0.3 * np.exp(1j * (3.0 * np.sin(2 * np.pi * 1000 * t) + 2 * np.pi * NFM_CARRIER[which] * t)) + lcg_noise(n, 7, 1e-3)
+
+
+def _demod_nfm(fs, calls, which):
+    def run(O, x):
+        d = O.DemodNFM(fs)
+        out, ends = [], []
+        for blk in _split(x, calls):
+            out.append(("v", _il(d.process(blk))))
+            ends.append(float(d.s.err_dc))     # the loop's own running average of nco_freq (1 ms)
+        if which == "clamp" and fs / 2.0 > 16000.0 + 3000.0:
+            # the clamp (demod_nfm.cpp:242-245) replaced nco_freq on thousands of samples.  At 37 500 the carrier's swing passes half
+            # the rate, the loop never settles on it and no sample is clamped: the row is pinned all the same, without this assertion
+            assert d.s.n_clamped >= 1000, d.s.n_clamped
+        if which == "offset":     # at that average the phase passes 2 pi several times inside a 2048-sample call, between the per-call fmods (:253)
+            assert all(abs(f) * 2048 > 3 * 2 * np.pi for f in ends), ends
+        return out
+    return run
+
+
+WFM_MONO_CALLS = (2048, 2048, 1000)
+
+
+def wfm_fm(fs, n, seed):
+    """tests/demod_cases.wfm_input's recipe at full level: 1 kHz and 3.3 kHz tones, peak deviation min(75 kHz, rate / 4) * 1.3"""
+    t = np.arange(n) / float(fs)
+    f = min(75000.0, fs / 4.0) * (np.cos(2 * np.pi * 1000.0 * t + 0.9) + 0.3 * np.cos(2 * np.pi * 3300.0 * t + 0.2))
+    return 0.5 * np.exp(2j * np.pi * np.cumsum(f) / float(fs)) + lcg_noise(n, seed, 1e-4)
+
+
+def _demod_wfm_mono(fs, calls):
+    def run(O, x):
+        d = O.DemodWFM(float(fs))
+        out = []
+        for blk in _split(x, calls):
+            out += [("x", np.array([float(len(blk))])), ("v", _il(d.process(blk)))]
+        return out
+    return run
+
+
+def fm_stereo_mpx(fs, n, pilot_phase):
+    """the multiplex of tests/test_parity_gpu.py::test_wfm_stereo_mode_is_the_reference_from_the_first_block: 1 kHz left, 2.5 kHz right,
+    the pilot, the 38 kHz difference signal, on a 75 kHz-deviation carrier, plus that test's noise"""
+    t = np.arange(n) / float(fs)
+    left, right = 0.9 * np.sin(2 * np.pi * 1000 * t), 0.9 * np.sin(2 * np.pi * 2500 * t)
+    mpx = 0.45 * (left + right) + 0.1 * np.sin(2 * np.pi * 19000 * t + pilot_phase) \
+        + 0.45 * (left - right) * np.sin(2 * (2 * np.pi * 19000 * t + pilot_phase))
+    return 0.5 * np.exp(1j * 2 * np.pi * 75000 * np.cumsum(mpx) / fs) + lcg_noise(n, 9, 1e-4)
+
+
+# the RDS rows: tests/rds_signal.py's multiplex of the groups test_rds_groups_of_a_multiplex_through_the_restated_decoder sends, the
+# subcarrier 14 Hz low as there.  At 390 625 (24 414 Hz behind the chain) the decoder finds no block A at the default levels, as at
+# 384 000 (tests/rds_cases.A_LEVELS): that row carries the stronger subcarrier under quieter audio that row uses.  The lengths are the
+# shortest, in 2048-sample calls, at which the third group has been popped, and two calls more
+RDS_PIN_ROWS = {256000: (84, {}), 390625: (110, dict(rds_level=0.2, audio_level=0.1))}
+
+
+def rds_mpx(fs):
+    from tests import rds_signal as rs
+    calls, levels = RDS_PIN_ROWS[fs]
+    return rs.fm_multiplex(rs.make_groups(30), float(fs), 2048 * calls, subcarrier_offset_hz=-14.0, **levels)
+
+
+def _demod_wfm_stereo(fs, calls, rds):
+    def run(O, x):
+        d = O.DemodWFM(float(fs))
+        out, last, popped = [], True, []      # getStereoLock: m_LastPilotLocked starts as !m_PilotLocked, demod_wfm.cpp:122-123
+        for blk in _split(x, calls):
+            y, lock = d.process_stereo(blk)
+            g = d.next_rds_group()
+            out += [("x", np.array([float(len(blk))])), ("v", _il(y)), ("x", np.array([float(lock != last), float(lock)])),
+                    ("x", np.array([0.0] * 5 if g is None else [float(g[1])] + [float(v) for v in g[0]]))]
+            last = lock
+            if g is not None:
+                popped.append(g[0])
+        rest = []
+        while True:
+            g = d.next_rds_group()
+            if g is None:
+                break
+            rest += [float(v) for v in g[0]]
+        out.append(("x", np.array(rest)))
+        if rds:                   # at least three groups came through, a popped group's BlockA is there, and the queue was never cleared
+            assert len(popped) >= 3 and all(g[0] != 0 for g in popped), popped
+            assert len(rest) == 0
+        return out
+    return run
+
+
+HEAD = 256  # complex samples of the first call a head_view fixture keeps
+
+
+def head_view(pairs):
+    """The fixture of a case whose later output cannot be followed sample by sample (the SAM loop out of lock): every record, and then
+    the first HEAD samples of the first call once more, as the last record, which compress() keeps whole"""
+    return list(pairs) + [(pairs[0][0], pairs[0][1][:2 * HEAD])]
+
+
+def stereo_view(audio_every):
+    """The fixture of a demod_wfm_stereo case.  Its records are per call (count, output, (changed, lock), (got, four words)) and a drained
+    queue at the end; the fixture regroups them so that a hundred calls fit: the counts of all calls, the lock pairs of all calls, one
+    row (call, got, four words) per call that delivered a group, the drained queue -- each cut into records of at most 160 values,
+    which compress() keeps whole, the numbers of group and queue records in front of them -- and then the outputs of every audio_every-th call and of the last one"""
+    def chunks(kind, v, step):
+        v = np.asarray(v, dtype=np.float64)
+        return [(kind, v[i:i + step]) for i in range(0, max(len(v), 1), step)]
+
+    def view(pairs):
+        assert len(pairs) % 4 == 1
+        calls = len(pairs) // 4
+        rows = [[float(k)] + list(pairs[4 * k + 3][1]) for k in range(calls) if np.any(pairs[4 * k + 3][1] != 0)]
+        out = chunks("x", np.concatenate([pairs[4 * k][1] for k in range(calls)]), 160)
+        out += chunks("x", np.concatenate([pairs[4 * k + 2][1] for k in range(calls)]), 160)
+        grp, rest = chunks("x", np.array(rows).reshape(-1), 156), chunks("x", pairs[-1][1], 160)
+        out += [("x", np.array([float(len(grp)), float(len(rest))]))] + grp + rest
+        out += [pairs[4 * k + 1] for k in stereo_audio_calls(calls, audio_every)]
+        return out
+    return view
+
+
+def stereo_audio_calls(calls, audio_every):
+    return [k for k in range(calls) if k % audio_every == 0 or k == calls - 1]
+
+
+def stereo_fixture(case):
+    """the fixture of a demod_wfm_stereo case, taken apart again -> dict: counts [calls], locks [calls, 2], groups {call: (got, a, b, c,
+    d)}, rest [m, 4], audio {call: the kept tail, interleaved}"""
+    calls, every = len(case.meta["calls"]), case.meta["audio_every"]
+    recs = [t for _, t in expand(np.load(case.fixture))]
+    n160 = lambda m: max(1, -(-m // 160))
+    pos = 0
+    counts = np.concatenate(recs[pos:pos + n160(calls)]); pos += n160(calls)
+    locks = np.concatenate(recs[pos:pos + n160(2 * calls)]).reshape(-1, 2); pos += n160(2 * calls)
+    audio_calls = stereo_audio_calls(calls, every)
+    audio = dict(zip(audio_calls, recs[len(recs) - len(audio_calls):]))
+    ngrp, nrest = int(recs[pos][0]), int(recs[pos][1])
+    rows = np.concatenate(recs[pos + 1:pos + 1 + ngrp]).reshape(-1, 6)
+    rest = np.concatenate(recs[pos + 1 + ngrp:pos + 1 + ngrp + nrest]).reshape(-1, 4)
+    assert pos + 1 + ngrp + nrest + len(audio_calls) == len(recs)
+    assert len(counts) == calls and len(locks) == calls
+    return dict(counts=counts, locks=locks, groups={int(r[0]): tuple(int(v) for v in r[1:]) for r in rows}, rest=rest, audio=audio)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # the table of cases
 # ---------------------------------------------------------------------------------------------------------------
@@ -489,6 +735,62 @@ def _build_cases():
         C.append(Case("morse_clock_%d" % mrate, "sampleclock", [mrate] + [v for p in pairs for v in p], lambda: np.zeros(0),
                       _morse_clock(mrate, pairs)))
     C.append(Case("morse_threshold_filter", "movingavg", [8, 21], _sma_input, _morse_sma(21)))
+    C += _demod_rows()
+    return C
+
+
+def _demod_rows():
+    """the demodulators at the rates the library runs them: 64 000 (2.048 Msps receivers), 37 500 (2.4 Msps), 48 000 (no decimator)"""
+    C = []
+    N = DEMOD_N
+    # AM: setBandwidth before the first call and before the third (CFir::InitLPFilter clears the delay line)
+    am_calls = [(2048, 10000.0), (2048, 0.0), (1000, 6000.0), (81, 0.0), (2048, 0.0)]
+    for fs in (64000, 37500):
+        C.append(Case("demod_am_%d" % fs, "demod_am", [fs, N] + [v for c in am_calls for v in c],
+                      lambda fs=fs: am_fading(fs, sum(c[0] for c in am_calls), 90), _demod_am(fs, am_calls),
+                      meta=dict(mode="AM", rate=fs, calls=[c[0] for c in am_calls], bw=[c[1] for c in am_calls], why="")))
+    n = sum(DEMOD_CALLS)
+    for fs in (64000, 37500, 48000):
+        for which in SAM_KINDS:
+            # out of lock the float loop is chaotic: the oracle fed the same samples rounded to single precision, the device's input
+            # format, misses 1e-4 against itself within the first call ("slip": 1e-3 to 3e-3 over the first call, 0.7 to 2 over the
+            # tail) and, where the loop is driven along a clamp, in the later calls ("clamp": 1e-4 to 1.6e-3 over the tail).  Over the
+            # first 256 samples it stays at 2e-8.  Those are what the device tier compares of these cases, so their fixtures keep them
+            head = which in ("slip", "clamp")
+            C.append(Case("demod_sam_%s_%d" % (which, fs), "demod_sam", [fs, N] + list(DEMOD_CALLS),
+                          lambda fs=fs, which=which: sam_carrier(fs, n, which), _demod_sam(fs, DEMOD_CALLS, which),
+                          view=head_view if head else None,
+                          meta=dict(mode="SAM", rate=fs, calls=list(DEMOD_CALLS), which=which, head=head,
+                                    why="the first %d samples of the first call: behind them the loop's float trajectory cannot be "
+                                        "followed from single-precision input" % HEAD if head else "")))
+        for which in NFM_KINDS:
+            # 16 kHz off at 37 500: the carrier's swing passes half the rate and the loop never settles; like the SAM loop out of lock,
+            # the reference algorithm fed single-precision samples misses itself there (2.7e-5 over the tail, 1e-5 over the first call,
+            # 9e-7 over its first 256 samples), so the device tier compares that stretch
+            head = which == "clamp" and fs == 37500
+            C.append(Case("demod_nfm_%s_%d" % (which, fs), "demod_nfm", [fs, N] + list(DEMOD_CALLS),
+                          lambda fs=fs, which=which: nfm_signal(fs, n, which), _demod_nfm(fs, DEMOD_CALLS, which),
+                          view=head_view if head else None,
+                          meta=dict(mode="FMN", rate=fs, calls=list(DEMOD_CALLS), which=which, head=head,
+                                    why="the first %d samples of the first call: the loop is out of lock" % HEAD if head else "")))
+    # WFM mono: one row per path decision of the device's WfmCore::init (low-pass off; sequential; one kernel; longest responses)
+    for fs in (100000, 192000, 256000, 512000):
+        C.append(Case("demod_wfm_mono_%d" % fs, "demod_wfm_mono", [fs, N] + list(WFM_MONO_CALLS),
+                      lambda fs=fs: wfm_fm(fs, sum(WFM_MONO_CALLS), 70), _demod_wfm_mono(fs, WFM_MONO_CALLS),
+                      meta=dict(mode="FMM", rate=fs, calls=list(WFM_MONO_CALLS), why="")))
+    # WFM stereo: the lock sequence of the pilot loop itself, ten blocks
+    for fs in (256000, 312500):
+        for pp in (1.0, 2.5):
+            calls = [2048] * 10
+            C.append(Case("demod_wfm_stereo_%d_%s" % (fs, str(pp).replace(".", "p")), "demod_wfm_stereo", [fs, N] + calls,
+                          lambda fs=fs, pp=pp: fm_stereo_mpx(fs, 2048 * 10, pp), _demod_wfm_stereo(fs, calls, False), view=stereo_view(1),
+                          meta=dict(mode="FMS", rate=fs, calls=calls, audio_every=1, rds=False, why="")))
+    # the RDS branch up to the group queue; 390 625 is where the device's decimation goes from 8 to 16
+    for fs, (ncalls, _) in RDS_PIN_ROWS.items():
+        calls = [2048] * ncalls
+        C.append(Case("demod_wfm_rds_%d" % fs, "demod_wfm_stereo", [fs, N] + calls, lambda fs=fs: rds_mpx(fs),
+                      _demod_wfm_stereo(fs, calls, True), view=stereo_view(8),
+                      meta=dict(mode="FMS", rate=fs, calls=calls, audio_every=8, rds=True, why="")))
     return C
 
 

@@ -197,7 +197,7 @@ def test_cfir_and_ciir_match_scipy(oracle_mod):
 
 
 def test_nfm_pll_recovers_the_modulation(oracle_mod):
-    """parity unpinned: closed-form check of Demod_NFM -- a 1 kHz tone with 3 kHz deviation comes out as a 1 kHz sine of
+    """closed-form check of Demod_NFM (pinned to the reference's class since: tests/test_reference_pins.py, cases demod_nfm_*) -- a 1 kHz tone with 3 kHz deviation comes out as a 1 kHz sine of
     amplitude 2*pi*3000/fs (the PLL output is NCO frequency in rad/sample) within the 75-tap CFir's pass-band ripple."""
     fs, n = 64000, 16384
     t = np.arange(n) / fs
@@ -658,7 +658,7 @@ def test_rds_groups_of_a_multiplex_through_the_restated_decoder(oracle_mod, fsw)
     frequency limit with a constant lead; a subcarrier 14 Hz low stands nearly still in that loop and most groups come through, one
     on frequency turns at ~19 Hz through the detector and few do.  Pinned here: the groups the decoder queues are groups that were sent,
     in the order sent (the all-zero group marks a cleared queue; a miscorrected block now and then); getNextRdsGroupData pops them one per call and flags repeats.
-    parity unpinned beyond the tables above: the reference holds no recorded RDS output."""
+    The branch itself is pinned to Demod_WFM::processDataStereo since: tests/test_reference_pins.py, cases demod_wfm_rds_*."""
     O = oracle_mod
     from tests import rds_signal as rs
     ng = 30

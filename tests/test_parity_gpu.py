@@ -159,7 +159,7 @@ def test_am_demod_step(gpu_lib, oracle_mod):
 
 
 def test_nfm_pll_demod_step(gpu_lib, oracle_mod):
-    """Demod_NFM::processBlockNCO (2nd-order PLL, float loop state) + 75-tap CFir.  parity unpinned in the reference;
+    """Demod_NFM::processBlockNCO (2nd-order PLL, float loop state) + 75-tap CFir;
     checked against the oracle restatement, including a ragged final call."""
     import pebblesdr_amd as P
     n = 2048

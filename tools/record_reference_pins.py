@@ -3,7 +3,8 @@
     python tools/record_reference_pins.py
 
 Needs the binary (oracle.build_ref() with a reference tree).  Each fixture holds what tests/reference_cases.compress() keeps of the
-driver's output for one case: every record's length, the short records whole and the tails of the long ones.
+driver's output for one case (of the records the case's view selects): every record's length, the short records whole and the tails of
+the long ones.
 """
 import os
 import sys
@@ -20,7 +21,8 @@ def main():
         sys.exit("no reference binary and no reference tree to build it from")
     total = 0
     for c in R.cases():
-        np.save(c.fixture, R.compress(c.reference(c.make_input())))
+        kept = c.view([("", r) for r in c.reference(c.make_input())])   # the kinds play no part in what a fixture holds
+        np.save(c.fixture, R.compress([r for _, r in kept]))
         total += os.path.getsize(c.fixture)
     print("%d fixtures, %d bytes" % (len(R.cases()), total))
 
