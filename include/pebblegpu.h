@@ -164,8 +164,13 @@ int pebblegpu_set_bandpass(pebblegpu_receiver *rx, uint32_t channel, double lo_h
  * there (the lock average would need seconds of a quiet detector to come back).  The RDS branch of the same function (:296-357:
  * m_RdsDownConvert, the 2400 Hz low-pass, processRdsPll, the biphase matched filter, the bit-rate resonator and slicer,
  * processNewRdsBit's block synchroniser with its burst corrector) runs for every dmFMS channel, in double on the device; its groups are
- * read through pebblegpu_receiver_rds_groups.  Calls and frames of a dmFMS bank must be multiples of the RDS down-converter's
- * decimation (8 up to 312.5 kHz of demodulator rate, 16 from 390.625 kHz on) and at least as long as its widest stage.  Not reproduced: what the GUI makes of a group (rdsdecode.cpp). */
+ * read through pebblegpu_receiver_rds_groups.  The frame of a dmFMS bank (frames_per_buffer at the demodulator rate) must be a multiple
+ * of the RDS down-converter's decimation D (8 up to 312.5 kHz of demodulator rate, 16 from 384 kHz on) and leave every decimate-by-2
+ * stage j at least 2 (T_j - 1) samples (frame >> j; more than 18 for the fixed 11-tap stage): below that the reference's in-place
+ * DecBy2 keeps outputs where its history should be (see pebblegpu_downconvert_process) and a frame-by-frame receiver would not be the
+ * reference.  The shortest frames: 272 at 256 kHz (15, 19, 35 taps), 800 at 384 kHz (11, 15, 23, 51).  A handle whose frame does not
+ * fit REFUSES THE MODE CHANGE with PEBBLEGPU_E_SIZE and the rule in the text: the channel stays dmFMM, nothing is queued, nothing
+ * about the next call changes, and the handle goes on.  Not reproduced: what the GUI makes of a group (rdsdecode.cpp). */
 int pebblegpu_set_demod_mode(pebblegpu_receiver *rx, uint32_t channel, int mode);
 /* tRDS_GROUPS (application/demod/rbdsconstants.h) */
 typedef struct pebblegpu_rds_group { uint16_t block_a, block_b, block_c, block_d; } pebblegpu_rds_group;
@@ -753,7 +758,12 @@ int pebblegpu_downconvert_stages(const pebblegpu_downconvert *d, uint32_t *n_sta
 /* int ProcessData(int InLength, TYPECPX *pInData, TYPECPX *pOutData), downconvert.cpp:250-335: InLength a multiple of 2^stages;
  * returns the output count in *n_out.  The input is NOT modified (the reference mixes it in place).  Streams with exact history for
  * any such InLength: a call that leaves a stage fewer samples than it has taps is not skipped as the reference's "safety net" does
- * (:361-362, which returns stale samples). */
+ * (:361-362, which returns stale samples).  Exact history is also NOT the reference wherever a stage of T taps is left T <= n < 2 (T - 1)
+ * samples (n <= 18 for the fixed 11-tap stage): ProcessData runs its stages in place (:325) and DecBy2 copies its next history out of
+ * pInData after its outputs have overwritten the front of it (:389-390).  Measured against the reference's own class over six equal
+ * calls, from the second call on: 384 kHz / 8 kHz (11, 15, 23, 51 taps) in calls of 512: 7e-4 .. 3e-3 relative RMS, in calls of 1024
+ * bit for bit; 256 kHz / 8 kHz (15, 19, 35) in calls of 256: 2e-6 .. 1e-5, in calls of 512 bit for bit (tests/test_oracle_pins.py,
+ * tests/reference_cases.py DC_BOUNDARY). */
 int pebblegpu_downconvert_process(pebblegpu_downconvert *d, uint32_t in_length, const double *in, double *out, uint32_t *n_out);
 /* the same on device buffers (float2 in; *d_out: library-owned float2 row, valid until the next call); queues and returns */
 int pebblegpu_downconvert_process_device(pebblegpu_downconvert *d, const void *d_iq, uint32_t in_length, const void **d_out, uint32_t *n_out);
@@ -779,7 +789,12 @@ int pebblegpu_demod_set_mode(pebblegpu_demod *d, int mode);          /* demod.cp
 int pebblegpu_demod_set_bandwidth(pebblegpu_demod *d, double bw);    /* demod.cpp:230-239 */
 /* CPX *Demod::processBlock(CPX *in, int n), application/demod.h:33: *out = library buffer, or = in for the
  * pass-through modes (demod.cpp:127-138).  The demodulating modes take calls of 80 samples or more (the depth of their FIRs' history);
- * a shorter one is PEBBLEGPU_E_SIZE and leaves the stream where it was */
+ * a shorter one is PEBBLEGPU_E_SIZE and leaves the stream where it was.  dmFMS: a call is one block of processDataStereo and must be a
+ * multiple of the RDS down-converter's decimation that leaves every stage at least its taps (PEBBLEGPU_E_SIZE otherwise, before anything
+ * is queued).  Such calls stream with exact history; where they leave a stage fewer than 2 (T - 1) samples (calls of 512 and 768 at
+ * 384 kHz, of 144 .. 264 at 256 kHz) the reference's in-place history differs -- by 7e-4 .. 3e-3 of the RDS branch's input at 384 kHz in
+ * calls of 512, 2e-6 .. 1e-5 at 256 kHz in calls of 256 (see pebblegpu_downconvert_process) -- and a RECEIVER refuses the mode for
+ * such a frame (pebblegpu_set_demod_mode) */
 int pebblegpu_demod_process(pebblegpu_demod *d, const double *in, int n, const double **out);
 /* dmFMS: getNextRdsGroupData as above, a processBlock call being one frame; and m_RdsData (the matched filter's output the bit
  * slicer reads, demod_wfm.cpp:309) of the last processBlock call: *n its length, at most cap values copied */

@@ -1409,6 +1409,10 @@ int WfmCore::set_stereo(uint32_t ch, bool on)
         // the RDS members, initialised with the rest of setSampleRate (demod_wfm.cpp:187-191)
         if (tun.rds) { if (int rc = rds.init(C, rate, max_n_)) return rc; }
     }
+    // An owner with a fixed frame (a receiver: stereo_block = frames_per_buffer) is refused here, where nothing of a call is queued yet and
+    // the channel simply stays dmFMM; every call of such an owner is whole frames, so one frame passing is all calls passing.  The
+    // stand-alone step (stereo_block = 0: a call is a block) has no frame to ask about and is checked per call in run().
+    if (on && stereo_block > 0) { if (int rc = rds.check_frame(stereo_block, true)) return rc; }
     if (stereo[ch] != (unsigned char)on) stereo_dirty = true;
     stereo[ch] = on;
     return 0;
@@ -1445,7 +1449,10 @@ int WfmCore::run(hipStream_t s, const float2 *in, long long in_pitch, float2 *ou
         PG_HIP(hipStreamSynchronize(s));
         stereo_dirty = false;
     }
-    if (n_stereo) { if (int rc = rds.check(n, stereo_block)) return rc; }  // (before anything of the call is queued)
+    // Before anything of THIS object's call is queued: that protects pebblegpu_demod_process, whose call starts here.  A receiver has queued
+    // its mixer and decimator by now and would fail for good, which is why its frame is checked in set_stereo(); for it this is the last
+    // line of defence (a frame that passed there passes here: every call is whole frames within the capacity).
+    if (n_stereo) { if (int rc = rds.check(n, stereo_block)) return rc; }
     if (fused) {
         WfmFirParams wp;
         memset(&wp, 0, sizeof(wp));
@@ -1801,12 +1808,20 @@ int AnfCore::run(hipStream_t s, float2 *buf, long long pitch, long long n, Gate 
 // ------------------------------------------------------------------------------------------------
 // ResampCore
 // ------------------------------------------------------------------------------------------------
-int ResampCore::init(uint32_t channels, uint32_t frame, double rate, uint32_t frames_per_call)
+int ResampCore::init(uint32_t channels, const std::vector<uint32_t> &parts_per_superframe, double rate, uint32_t superframes_per_call)
 {
     C = channels;
-    nf = frame;
+    parts = parts_per_superframe;
+    period = 0;
+    nf = 0;
+    for (uint32_t p : parts) {
+        if (p < (uint32_t)kSincPeriods) return fail(PEBBLEGPU_E_SIZE, "resampler needs at least %d samples per frame", kSincPeriods);
+        period += p;
+        nf = nf ? std::min(nf, p) : p;
+    }
+    if (parts.empty()) return fail(PEBBLEGPU_E_INVALID, "resampler without a frame");
     dt = rate;
-    max_frames = frames_per_call;
+    max_frames = superframes_per_call * (uint32_t)parts.size();
     if (!(dt > 0) || dt > 1e6) return fail(PEBBLEGPU_E_INVALID, "bad resampling ratio");
     std::vector<float> t((size_t)kSincLength);
     for (int i = 0; i < kSincLength; i++) {  // fractresampler.cpp:104-118
@@ -1833,24 +1848,29 @@ void ResampCore::release()
 }
 int ResampCore::run(hipStream_t s, const float2 *in, long long in_pitch, long long n, float2 *out, long long out_pitch, long long *n_out)
 {
-    if (n % nf != 0 || n / nf > (long long)max_frames) return fail(PEBBLEGPU_E_SIZE, "resampler input %lld is not 1..%u frames of %u", n, max_frames, nf);
-    if (n < kSincPeriods) return fail(PEBBLEGPU_E_SIZE, "resampler needs at least %d samples per call", kSincPeriods);
-    const int F = (int)(n / nf);
+    if (n <= 0 || n % (long long)period != 0 || n / (long long)period * (long long)parts.size() > (long long)max_frames)
+        return fail(PEBBLEGPU_E_SIZE, "resampler input %lld is not 1..%zu super-frames of %llu", n, (size_t)max_frames / parts.size(), (unsigned long long)period);
+    const int F = (int)(n / (long long)period * (long long)parts.size());
     PG_HIP(hipEventSynchronize(h_done[pin]));  // the copy that last used this staging buffer has run
     ResampFrame *hf = h_frames[pin];
     // replay of the reference's time arithmetic, frame by frame (fractresampler.cpp:155-187)
     double t = float_time;
     int total = 0, max_per_frame = 0;
+    long long at = 0;
     for (int f = 0; f < F; f++) {
+        const int len = (int)parts[(size_t)f % parts.size()];
         hf[f].t_start = t;
         hf[f].out_offset = total;
+        hf[f].in_offset = (int)at;
+        hf[f].pad_ = 0;
+        at += len;
         int it = (int)t, cnt = 0;
-        while (it < (int)nf) {
+        while (it < len) {
             cnt++;
             t += dt;
             it = (int)t;
         }
-        t -= (double)nf;
+        t -= (double)len;
         hf[f].nout = cnt;
         total += cnt;
         if (cnt > max_per_frame) max_per_frame = cnt;
@@ -1863,7 +1883,7 @@ int ResampCore::run(hipStream_t s, const float2 *in, long long in_pitch, long lo
     pin ^= 1;
     if (total > 0) {
         const int sub = (int)cdiv(max_per_frame, 256);
-        launch(k_resample, dim3((unsigned)(F * sub), C), dim3(256), s, in, in_pitch, (const float2 *)d_hist[parity], out, out_pitch, (int)nf, sub, dt,
+        launch(k_resample, dim3((unsigned)(F * sub), C), dim3(256), s, in, in_pitch, (const float2 *)d_hist[parity], out, out_pitch, sub, dt,
                (const ResampFrame *)d_frames, (const float *)d_sinc);
         PG_HIP(hipGetLastError());
     }

@@ -461,10 +461,13 @@ static __global__ __launch_bounds__(64) void k_pll_demod(const float2 *__restric
     if (pp.mode == 0) {
         // Demod_NFM wraps its phase at the end of every processBlock (demod_nfm.cpp:253), and the receiver hands it one frame of blk_frame
         // demodulator-rate samples at a time (receiver.cpp:927-929, 987).  Wherever blk_len, the band-pass's block, divides blk_frame -- the
-        // reference's only case (1024 and 2048) -- the rule below wraps every blk_frame samples, as the reference does.  Where it does not,
-        // this library's band-pass releases whole blocks per frame and the wrap falls at the end of what each frame released: a behaviour of
-        // this library's alone, with no reference semantics.  A call starts on a block and a frame boundary (p counts from the call's
-        // start): a receiver's calls are whole super-frames.  blk_len 0: the call is one block
+        // stock sizes (1024 and 2048) -- the rule below wraps every blk_frame samples.  Where it does not, CFastFIR::ProcessData hands
+        // each frame the whole blocks that frame completed (none, one or several) and processBlock runs once on them, so the wrap falls at
+        // the end of what each frame released: block end p is a wrap when a frame ends in [p, p + blk_len).  That is the reference's rule
+        // too: a model of this partition from the oracle's parts is oracle.Receiver fed frame by frame, bit for bit, at frames of 300,
+        // 512, 1536, 3072 and 4096 and blocks of 1024, 1792 and 2048 (tests/test_receiver_frames_host.py, which also shows three other
+        // placements to differ).  A call starts on a block and a frame boundary (p counts from the call's start): a receiver's calls are
+        // whole super-frames.  blk_len 0: the call is one block
         int to_blk = blk_len;
         for (long long i = 0; i < n; i++) {
             const double nco_sin = (double)sinf(s.phase), nco_cos = (double)cosf(s.phase);
@@ -611,14 +614,15 @@ static __global__ __launch_bounds__(64) void k_agc(float2 *__restrict__ buf, lon
 // samples with a windowed sinc read from a 280 001-point table at floor((j - t) * 10000).  The output times t are the
 // reference's running fp64 sum (m_FloatTime += dt per output, -= InLength per frame); the host replays that sum per
 // call -- it also yields the output count without a device sync -- and hands each frame's start time to the kernel,
-// which re-adds dt in the same order, so every table index is the reference's own.
+// which re-adds dt in the same order, so every table index is the reference's own.  A "frame" here is what one frame of the
+// reference handed its resampler (ResampCore::parts): the frame itself, or the band-pass blocks it released, of any length.
 // grid (frames * sub_blocks, channels), block 256.
 // ------------------------------------------------------------------------------------------------
 constexpr int kSincPeriodPts = 10000, kSincPeriods = 28, kSincLength = kSincPeriods * kSincPeriodPts + 1;
-struct ResampFrame { double t_start; int out_offset, nout; };
+struct ResampFrame { double t_start; int out_offset, nout, in_offset, pad_; };  // in_offset: where the frame starts in the call's input
 
 static __global__ __launch_bounds__(256) void k_resample(const float2 *__restrict__ in, long long in_pitch, const float2 *__restrict__ hist,
-                                                         float2 *__restrict__ out, long long out_pitch, int nf, int sub_blocks, double dt,
+                                                         float2 *__restrict__ out, long long out_pitch, int sub_blocks, double dt,
                                                          const ResampFrame *__restrict__ frames, const float *__restrict__ sinc)
 {
     __shared__ double tk[256];
@@ -635,8 +639,8 @@ static __global__ __launch_bounds__(256) void k_resample(const float2 *__restric
     if (k >= fr.nout) return;
     const double t = tk[tid];
     const int it = (int)t;
-    // m_pInputBuf[j], j = it + i: [28 samples of history | this frame]; frame f of the call starts at in[f * nf]
-    const float2 *x = in + (long long)c * in_pitch + (long long)f * nf - kSincPeriods;
+    // m_pInputBuf[j], j = it + i: [28 samples of history | this frame]; frame f of the call starts at in[fr.in_offset]
+    const float2 *x = in + (long long)c * in_pitch + (long long)fr.in_offset - kSincPeriods;
     const float2 *h = hist + (long long)c * kSincPeriods;
     double ar = 0.0, ai = 0.0;
 #pragma unroll 4

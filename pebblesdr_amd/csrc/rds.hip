@@ -58,18 +58,36 @@ int RdsCore::init(uint32_t channels, double demod_rate, long long max_n)
     return 0;
 }
 
-int RdsCore::check(long long n, int block) const
+// The one statement of what a frame (the samples of one processDataStereo call of the reference) must be for the RDS down-converter.
+// streamed_history = false: what run() can stream with exact history -- a multiple of D, and in front of every stage at least that stage's
+// taps.  streamed_history = true: what is the reference as well.  CDownConvert::ProcessData runs its stages in place
+// (downconvert.cpp:325), and CHalfBandDecimateBy2::DecBy2 copies its next history out of pInData after the outputs have overwritten the
+// front half of it (:389-390): below 2 (T - 1) samples that history holds outputs.  The fixed 11-tap class reads pInData[16] for its
+// ninth output whatever the length and keeps the last ten inputs: the reference from 19 samples up.
+int RdsCore::check_frame(int block, bool reference_history) const
 {
     if (!on) return 0;
     const size_t nst = des.stages.size();
+    if (block <= 0 || block % D != 0)
+        return fail(PEBBLEGPU_E_SIZE, "dmFMS: calls and frames must be multiples of %d samples (the RDS down-converter's %zu decimate-by-2 stages)", D, nst);
+    for (size_t j = 0; j < nst; j++) {
+        const int len = block >> j, T = ntaps[j];
+        if (len < T)  // CHalfBandDecimateBy2's "safety net" (downconvert.cpp:361-362) would drop samples unfiltered
+            return fail(PEBBLEGPU_E_SIZE, "dmFMS: a frame of %d samples is shorter than the RDS down-converter's stage %zu needs", block, j);
+        if (reference_history && (des.stages[j] == 1 ? len <= 18 : len < 2 * (T - 1)))
+            return fail(PEBBLEGPU_E_SIZE, "dmFMS: a frame of %d samples leaves stage %zu of the RDS down-converter %d samples, fewer than twice its %d taps of history "
+                        "(the reference's in-place history is not the stream's there)", block, j, len, T - 1);
+    }
+    return 0;
+}
+
+int RdsCore::check(long long n, int block) const
+{
+    if (!on) return 0;
     if (block <= 0) block = (int)n;
     if (n > cap) return fail(PEBBLEGPU_E_SIZE, "%lld samples exceed this object's capacity", n);
-    if (n % D != 0 || block % D != 0)
-        return fail(PEBBLEGPU_E_SIZE, "dmFMS: calls and frames must be multiples of %d samples (the RDS down-converter's %zu decimate-by-2 stages)", D, nst);
-    for (size_t j = 0; j < nst; j++)
-        if ((block >> j) < ntaps[j])  // CHalfBandDecimateBy2's "safety net" (downconvert.cpp:361-362) would drop samples unfiltered
-            return fail(PEBBLEGPU_E_SIZE, "dmFMS: a frame of %d samples is shorter than the RDS down-converter's stage %zu needs", block, j);
-    return 0;
+    if (n % D != 0) return check_frame(0, false);  // (the multiple-of-D text)
+    return check_frame(block, false);
 }
 
 int RdsCore::run(hipStream_t s, const float2 *in, long long in_pitch, long long n, const double *d_hilb, const int *d_list, int n_list, int block)

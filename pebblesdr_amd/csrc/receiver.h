@@ -352,6 +352,9 @@ struct RdsCore {
     int init(uint32_t channels, double demod_rate, long long max_n);
     // queues the branch for the listed channels; block: demodulator-rate samples per processDataStereo call of the reference
     int check(long long n, int block) const;   // the sizes run() accepts (the owner asks before it queues anything of the call)
+    // the frame rule check() applies; reference_history: also refuse frames below which the reference's in-place history is not the stream's
+    // (what a receiver, whose frame is fixed at creation, asks when a channel is switched to dmFMS)
+    int check_frame(int block, bool reference_history) const;
     int run(hipStream_t s, const float2 *in, long long in_pitch, long long n, const double *d_hilb, const int *d_list, int n_list, int block);
     int collect(hipStream_t s, uint32_t ch);   // waits for the stream, replays the channel's new log entries
     int groups(hipStream_t s, uint32_t ch, RdsGroup *g, unsigned char *changed, uint32_t cap_out, uint32_t *n_out);
@@ -588,7 +591,14 @@ struct TestBenchCore {
 
 // ---- CFractResampler (complex), pebblelib/fractresampler.cpp ----
 struct ResampCore {
-    uint32_t C = 0, nf = 0;
+    uint32_t C = 0, nf = 0;                  // nf: the shortest part (max_out's bound on outputs lost to rounding per part)
+    // The reference resamples what each of its frames hands on, and takes the frame's length off its running time sum after each
+    // (fractresampler.cpp:186).  parts: those lengths over one super-frame, in order -- {nf} for a WFM receiver and wherever the band-pass's
+    // block divides the frame; the blocks each frame released otherwise (a frame that released none runs nothing).  The sum's rounding
+    // follows the partition: with a rational ratio such as 48000 / 11025 an output time lands on a whole sample every 147 outputs, and
+    // another partition delivers that output one call earlier or later.
+    std::vector<uint32_t> parts;
+    uint64_t period = 0;                     // their sum: the demodulator-rate samples of one super-frame
     double dt = 1.0, float_time = 0.0;     // Rate = input rate / output rate; m_FloatTime
     DevBuf<float> d_sinc;
     DevBuf<float2> d_hist[2];                // [C][28] last inputs of the previous call, ping-pong
@@ -597,10 +607,10 @@ struct ResampCore {
     hipEvent_t h_done[2] = {nullptr, nullptr};
     int parity = 0, pin = 0;
     uint32_t max_frames = 0;
-    int init(uint32_t channels, uint32_t frame, double rate, uint32_t frames_per_call);
+    int init(uint32_t channels, const std::vector<uint32_t> &parts_per_superframe, double rate, uint32_t superframes_per_call);
     void release();
     long long max_out(long long n) const { return (long long)((double)n / dt) + (long long)(n / (nf ? nf : 1)) + 8; }
-    // n: multiple of the frame; returns the output count of this call in *n_out (no device sync)
+    // n: whole super-frames; returns the output count of this call in *n_out (no device sync)
     int run(hipStream_t s, const float2 *in, long long in_pitch, long long n, float2 *out, long long out_pitch, long long *n_out);
 };
 

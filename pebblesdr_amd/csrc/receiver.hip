@@ -85,7 +85,19 @@ int Receiver::create(const pebblegpu_config *cfg)
         const double rr = ((double)demod_rate_int * 1.0) / ((double)audio_rate * 1.0);
         if (rr == 1.0) audio_rate = 0;  // copyCPX branch (receiver.cpp:1002-1003)
         else {
-            if (int rc = resamp_.init(C, nf, rr, (uint32_t)(nd_max / nf))) return rc;
+            // what each frame of the reference hands the resampler: the frame (WFM, receiver.cpp:901), or the blocks the band-pass released
+            // at its end (receiver.cpp:950, 994) -- floor((k + 1) nf / L) - floor(k nf / L) of them, the frame itself wherever L divides nf
+            std::vector<uint32_t> parts;
+            const uint64_t per_sf = superframe / chain.total;
+            if (wfm) parts.push_back(nf);
+            else {
+                const uint64_t L = (uint64_t)ff_.block_len();
+                for (uint64_t k = 0; k < per_sf / nf; k++) {
+                    const uint64_t r = ((k + 1) * nf) / L - (k * nf) / L;
+                    if (r) parts.push_back((uint32_t)(r * L));
+                }
+            }
+            if (int rc = resamp_.init(C, parts, rr, (uint32_t)(nd_max / (long long)per_sf))) return rc;
             rs_pitch = resamp_.max_out(nd_max);
             PG_TRY(d_audio_rs.alloc((size_t)rs_pitch * C));
         }
@@ -146,8 +158,10 @@ int Receiver::set_mode(uint32_t ch, int mode)
     if (wfm) {
         if (mode != PEBBLEGPU_DM_FMM && mode != PEBBLEGPU_DM_FMS) return fail(PEBBLEGPU_E_UNSUPPORTED, "a WFM bank demodulates FMM and FMS only");
         std::lock_guard<std::mutex> g(mu_);
-        touched_ = true;  // the next call joins its two pipelines before the change is applied
+        // refused (E_SIZE: the handle's frame against the RDS down-converter, RdsCore::check_frame): the channel stays as it was, nothing is
+        // marked touched and the handle goes on
         if (int rc = wfmc_.set_stereo(ch, mode == PEBBLEGPU_DM_FMS)) return rc;
+        touched_ = true;  // the next call joins its two pipelines before the change is applied
         ctl_[ch].mode = mode;
         return 0;
     } else if (mode == PEBBLEGPU_DM_FMM || mode == PEBBLEGPU_DM_FMS || mode < 0 || mode > PEBBLEGPU_DM_NONE) {

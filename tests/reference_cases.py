@@ -633,6 +633,27 @@ def _dc_input(fs, D, f0, n):
         + lcg_noise(n, 4, 1e-3)
 
 
+DC_BOUNDARY = ((384000.0, 1024), (256000.0, 512))     # chains 11, 15, 23, 51 and 15, 19, 35: 1024 >> 3 = 128 >= 100, 512 >> 2 = 128 >= 68
+DC_INPLACE = ((384000.0, 512), (256000.0, 256))       # 512 >> 3 = 64 < 100, 256 >> 2 = 64 < 68: every stage still sees its taps
+DC_RDS_BW, DC_RDS_F0, DC_EQUAL_CALLS = 8000.0, 57000.0, 6
+
+
+def _dc_equal_calls_case(dfs, ln, prefix="downconvert"):
+    """CDownConvert at the RDS branch's settings (SetDataRate(rate, 8000), 57 kHz) over six equal calls"""
+    calls = [(ln, DC_RDS_F0, 0.0)] * DC_EQUAL_CALLS
+    stages = {384000.0: 4, 256000.0: 3}[dfs]
+    return Case("%s_%d_%d_x%d" % (prefix, dfs, DC_RDS_BW, ln), "downconvert", [dfs, DC_RDS_BW, 0] + [v for c in calls for v in c],
+                lambda: _dc_input(dfs, 1 << stages, DC_RDS_F0, ln * DC_EQUAL_CALLS), _downconvert(dfs, DC_RDS_BW, False, calls))
+
+
+def inplace_cases():
+    """NOT in cases(): below 2 (T - 1) samples per stage the reference's in-place DecBy2 copies its next history out of samples its own
+    outputs have overwritten, and the oracle (exact history, what the device streams) is NOT the reference there.  The fixtures
+    tests/golden/refpin_inplace_*.npy hold the reference's outputs whole (32 outputs a call); tests/test_oracle_pins.py holds the oracle to
+    them on the first call and asserts that it differs from the second call on."""
+    return [_dc_equal_calls_case(dfs, ln, "inplace_downconvert") for dfs, ln in DC_INPLACE]
+
+
 def _build_cases():
     C = []
     fs, n = 2048000, 2048
@@ -654,6 +675,10 @@ def _build_cases():
         C.append(Case("downconvert_%d_%d" % (dfs, bw), "downconvert", [dfs, bw, int(simple)] + [v for c in calls for v in c],
                       lambda dfs=dfs, D=D, f0=f0, calls=calls: _dc_input(dfs, D, f0, sum(c[0] for c in calls)),
                       _downconvert(dfs, bw, simple, calls)))
+    # ... and the RDS down-converter's chains (bw 8000) at the shortest equal calls whose every stage sees 2 (T - 1) samples or more:
+    # from there up CHalfBandDecimateBy2's in-place history (downconvert.cpp:325, :389-390) is the stream's, and the oracle is bit for bit
+    for dfs, ln in DC_BOUNDARY:
+        C.append(_dc_equal_calls_case(dfs, ln))
     # CFastFIR 2048/1025 at 64 kHz: H and three blocks
     for lo, hi in ((300, 3000), (-5000, 5000), (-3000, -300), (1000, 1500)):
         C.append(Case("fastfir_%d_%d" % (lo, hi), "fastfir", [lo, hi, 0, 64000, 2048], lambda: _audio(64000, 3 * 2048, 31),

@@ -686,3 +686,32 @@ def test_rds_groups_of_a_multiplex_through_the_restated_decoder(oracle_mod, fsw)
         assert all(ch for _, ch in popped[:1])
         bits = d.rds_bits()
         assert abs(len(bits) - n / fsw * 1187.5) < 30   # the resonator delivers the bit clock (a peak more or less where the signal nulls)
+
+
+def test_downconvert_below_twice_a_stages_history_the_oracle_is_not_the_reference(oracle_mod):
+    """CDownConvert::ProcessData runs its decimate-by-2 stages in place (downconvert.cpp:325), and CHalfBandDecimateBy2::DecBy2 copies its
+    next history out of pInData after its outputs have overwritten the front of it (:389-390): with T <= InLength < 2 (T - 1) that
+    history holds outputs.  The oracle (po_ DecBy2: the exact last T - 1 inputs) and the device stream exact history there, as
+    pebblegpu.h promises for the stand-alone steps; a receiver refuses such frames for dmFMS (RdsCore::check_frame).  On the reference's
+    recorded outputs (tests/golden/refpin_inplace_*.npy: six equal calls of 512 at 384 000 and of 256 at 256 000, whole) the first call
+    is the oracle's -- its history is the zeros both start with -- and from the second call on the oracle differs by more than 1e-6
+    (measured on this input: 7.1e-4 .. 1.7e-3 at 384 000, 1.9e-6 .. 9.2e-6 at 256 000).  The day someone makes the oracle restate the in-place copy,
+    this test says so; tests/reference_cases.DC_BOUNDARY pins the shortest calls at which both are bit for bit."""
+    from tests import reference_cases as R
+    cases = R.inplace_cases()
+    assert [c.name for c in cases] == ["inplace_downconvert_384000_8000_x512", "inplace_downconvert_256000_8000_x256"]
+    for case in cases:
+        assert os.path.getsize(case.fixture) < 16384
+        want = R.expand(np.load(case.fixture))
+        x = case.make_input()
+        got = [np.asarray(v, dtype=np.float64) for _, v in case.oracle(oracle_mod, x)]
+        assert len(got) == len(want) == 1 + R.DC_EQUAL_CALLS
+        assert all(len(g) == n == len(t) for g, (n, t) in zip(got, want))            # the fixture holds every record whole
+        assert np.array_equal(got[0], want[0][1])                                    # the output rate
+        assert np.array_equal(got[1], want[1][1]), case.name                         # the first call
+        later = [R.record_error("v", g, t) for g, (_, t) in zip(got[2:], want[2:])]
+        print("%s: oracle against the reference's in-place history, calls 2..6: %s" % (case.name, " ".join("%.2e" % e for e in later)))
+        assert min(later) > 1e-6, (case.name, later)
+        if os.path.exists(R.BINARY):   # (and the fixture is what the binary gives today)
+            ref = case.reference(x)
+            assert all(np.array_equal(r, t) for r, (_, t) in zip(ref, want))

@@ -20,11 +20,12 @@ def main():
     if not oracle.build_ref():
         sys.exit("no reference binary and no reference tree to build it from")
     total = 0
-    for c in R.cases():
+    every = R.cases() + R.inplace_cases()   # (the second list: the reference where the oracle is NOT it, tests/test_oracle_pins.py)
+    for c in every:
         kept = c.view([("", r) for r in c.reference(c.make_input())])   # the kinds play no part in what a fixture holds
         np.save(c.fixture, R.compress([r for _, r in kept]))
         total += os.path.getsize(c.fixture)
-    print("%d fixtures, %d bytes" % (len(R.cases()), total))
+    print("%d fixtures, %d bytes" % (len(every), total))
 
 
 if __name__ == "__main__":
