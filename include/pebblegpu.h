@@ -938,6 +938,59 @@ int pebblegpu_receiver_record_release(pebblegpu_receiver *rx, uint64_t call_inde
 /* host twin: n IQ samples of interleaved float I, Q -> n PCM16 pairs */
 int pebblegpu_iq_record_convert(const float *iq, uint64_t n, int16_t *out);
 
+/* The modem hook ring: what a digital-modem plugin receives, for the host's own decoders (RTTY, PSK, WWV ...), without a synchronize.
+ * Source: the narrow branch's per-channel rows right behind NoiseFilter::ProcessBlock and before the Morse decoder and AGC::processBlock
+ * -- the block DigitalModemInterface::processBlock is handed at application/receiver.cpp:979-980, at the demodulator rate; exactly the
+ * values PEBBLEGPU_TAP_MODEM shows.  READ-ONLY, as the library's Morse modem is: a plugin that alters the stream
+ * (nextStep = processBlock(nextStep)) is out of scope; what the host does with a block never reaches the chain.
+ *
+ * One block per process call with the rows of the selected channels, every super-frame of the call one after the other
+ * (samples_per_channel = n_superframes * samples_per_superframe).  ABSENT PAIRS: the reference returns before the hook when the squelch
+ * is closed (receiver.cpp:962-965) and when the channel is dmNONE (:968-971), so a (channel, super-frame) that the bank's gate closed, or
+ * whose channel is dmNONE in that call, is absent: its samples in the block are zeros and its flag is 0.  TRAILER: one byte per (block
+ * row, super-frame of the call), present[r * n_superframes + j], 1 = present, padded to 16 bytes; the packing launch writes it at
+ * host + n_channels * pitch_bytes and it travels inside the block's one copy.  A one-channel receiver's closed call (the squelch's
+ * read-back gate, tune-only) gives a block with samples_per_channel == 0, n_superframes == 0 and present == NULL, like the audio ring.
+ * Formats: PEBBLEGPU_AUDIO_F32 -- the float2 rows verbatim, I then Q (no gain, no clip); PEBBLEGPU_AUDIO_S16 -- PCM16 pairs by the
+ * recording ring's rule (pebblegpu_iq_record_convert); PEBBLEGPU_AUDIO_S16_MONO is PEBBLEGPU_E_INVALID.
+ *
+ * The ring's rules are the audio ring's, word for word: ONE block per process call, call indices 0-based from open; A FULL RING DROPS
+ * AND COUNTS, IT NEVER STALLS OR REFUSES; n_slots 2..8; one reader, on any thread; pebblegpu_process_iq is refused while the ring is
+ * open; the shards of a multibank use their borrowed handles (pebblegpu_multibank_shard).  OPENING THE RING CHANGES NO CALL'S ROUTE AND
+ * NO KERNEL: pebblegpu_receiver_kernel_name reports the same strings, two-stage calls stay two-stage, and audio, Morse events, S-meter
+ * rows and spectra are bit for bit what they are without it; it adds one packing launch (k_modem_pack) and one event to a call, queued
+ * between the noise filter and the AGC, and nothing the rest of the call queues waits for the copy.  Unlike the MODEM tap the ring runs
+ * under a squelch threshold (a bank's per-channel gate included), with the Morse modem on, and with pebblegpu_set_spectrum_updates.
+ * Refusals, each leaving the handle as it was: PEBBLEGPU_E_UNSUPPORTED on a WFM receiver (the hook is on the narrow branch);
+ * PEBBLEGPU_E_INVALID for duplicate channels, channels out of range, an empty list, n_slots outside 2..8, a format other than the two
+ * above, a second open. */
+typedef struct {
+    uint32_t struct_size;            /* = sizeof(pebblegpu_modem_block), set by the caller */
+    uint32_t format;                 /* PEBBLEGPU_AUDIO_F32 or PEBBLEGPU_AUDIO_S16: I, Q pairs */
+    uint64_t call_index;             /* which process call since open */
+    const void *host;                /* pinned host memory: row r at host + r * pitch_bytes; NULL: no block (see _next) */
+    uint64_t samples_per_channel;    /* n_superframes * samples_per_superframe; may be 0 */
+    uint64_t pitch_bytes;            /* a multiple of 16 */
+    uint32_t n_channels;             /* rows: the selected channels */
+    uint32_t dropped_before;         /* blocks dropped between the previous queued block and this one */
+    uint32_t rate;                   /* samples per second of the rows: the demodulator rate */
+    uint32_t n_superframes;          /* super-frames of the call (0 in a block of 0 samples) */
+    uint64_t samples_per_superframe; /* per channel */
+    const uint8_t *present;          /* [n_channels][n_superframes], points into the slot behind the rows; NULL in a block of 0 samples */
+} pebblegpu_modem_block;
+/* channels: row r of every block is channel channels[r] -- a subset, in any order; NULL: all channels of the receiver, in order */
+int pebblegpu_receiver_modem_out_open(pebblegpu_receiver *rx, int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots);
+int pebblegpu_receiver_modem_out_close(pebblegpu_receiver *rx);   /* as pebblegpu_receiver_audio_out_close */
+int pebblegpu_receiver_modem_out_next(pebblegpu_receiver *rx, int wait, pebblegpu_modem_block *b);
+int pebblegpu_receiver_modem_out_release(pebblegpu_receiver *rx, uint64_t call_index);
+int pebblegpu_receiver_modem_out_dropped(const pebblegpu_receiver *rx, uint64_t *blocks);
+/* host twin of the packing kernel (no device): n IQ samples of interleaved float I, Q -> out in `format` (F32: copied; S16: the record twin) */
+int pebblegpu_modem_out_convert(int format, const float *iq, uint64_t n, void *out);
+/* a block's layout (no device), the function the producer and the reader use: the row pitch, and where the trailer of n_channels *
+ * n_superframes flags starts and how many bytes (a multiple of 16) it takes */
+int pebblegpu_modem_out_layout(int format, uint32_t n_channels, uint64_t samples_per_channel, uint32_t n_superframes, uint64_t *pitch_bytes,
+                               uint64_t *trailer_offset, uint64_t *trailer_bytes);
+
 /* ------------------------------------------------------------------------------------------------
  * Host egress for a stream bank: the band-passed IQ of selected streams and the display rows of the spectra a call computed, through
  * the same rings of pinned slots (above).  Without a ring the only way to a call's results is

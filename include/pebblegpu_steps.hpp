@@ -573,7 +573,7 @@ public:
     void processIQData(CPX *in, uint16_t numSamples)
     {
         if (!h) return;
-        if (tbSweep || tbNoise || tbMorse || tapMask) { processBatched(in, numSamples); return; }
+        if (tbSweep || tbNoise || tbMorse || tapMask || modemOpen) { processBatched(in, numSamples); return; }
         uint32_t na = 0;
         // (behind setUpdatesPerSec a frame the timer skips leaves `spectrum` as it is: the last computed one, as getUnprocessed() holds it)
         status = report("process_iq", pebblegpu_process_iq_updates(h, reinterpret_cast<const double *>(in), numSamples, reinterpret_cast<double *>(audio.data()), &na,
@@ -615,6 +615,32 @@ public:
         if (status == 0) status = report("memcpy_d2h", pebblegpu_memcpy_d2h(dev, outBuf, dPx, sizeof(int32_t) * (size_t)maxWidth));
         return false;
     }
+    // The modem hook ring (pebblegpu_receiver_modem_out_*): the frames m_iDigitalModem->processBlock receives (receiver.cpp:979-980), in
+    // pinned blocks a plugin's thread reads without a synchronize.  Read-only: what the plugin returns never reaches the chain.  While
+    // the ring is open processIQData runs on the library's batched device path (pebblegpu_process_iq is refused beside a ring): it
+    // collects a super-frame of frames and queues it as one call.  modemOutNext / modemOutRelease may be called from another thread;
+    // feedModemBlock (below) turns a block into the reference's processBlock calls.
+    int modemOutOpen(int format = PEBBLEGPU_AUDIO_F32, uint32_t nSlots = 4)
+    {
+        if (h) status = report("receiver_modem_out_open", pebblegpu_receiver_modem_out_open(h, format, nullptr, 0, nSlots));
+        if (h && status == 0) modemOpen = true;
+        return status;
+    }
+    int modemOutClose()
+    {
+        if (h) status = report("receiver_modem_out_close", pebblegpu_receiver_modem_out_close(h));
+        if (status == 0) modemOpen = false;
+        return status;
+    }
+    // b->host == nullptr: nothing queued (or, with wait false, not copied yet)
+    int modemOutNext(bool wait, pebblegpu_modem_block *b)
+    {
+        std::memset(b, 0, sizeof(*b));
+        b->struct_size = sizeof(*b);
+        return h ? report("receiver_modem_out_next", pebblegpu_receiver_modem_out_next(h, wait ? 1 : 0, b)) : PEBBLEGPU_E_INVALID;
+    }
+    int modemOutRelease(uint64_t callIndex) { return h ? report("receiver_modem_out_release", pebblegpu_receiver_modem_out_release(h, callIndex)) : PEBBLEGPU_E_INVALID; }
+    uint64_t modemOutDropped() { uint64_t d = 0; if (h) status = report("receiver_modem_out_dropped", pebblegpu_receiver_modem_out_dropped(h, &d)); return d; }
     uint32_t demodSampleRate() const { return demodRate; }
     int lastStatus() const { return status; }
 
@@ -668,7 +694,7 @@ private:
     }
     pebblegpu_receiver *h = nullptr;
     uint16_t n;
-    bool tbSweep = false, tbNoise = false, tbMorse = false;
+    bool tbSweep = false, tbNoise = false, tbMorse = false, modemOpen = false;
     uint32_t tapMask = 0;
     CB_DisplayData display;
     uint64_t superframe = 0;
@@ -686,6 +712,40 @@ private:
     void *dPx = nullptr;  // the mapped pixels on the device (mapFFTToScreen)
     size_t pxCap = 0;
 };
+
+// A modem block (pebblegpu_modem_block, from any receiver or shard handle) as the calls the reference would have made: one
+// processBlock(CPX *in)-shaped callback per demodulator frame (demodFrames samples: the receiver's frames_per_buffer over its
+// decimation, DigitalModemInterface::setSampleRate's second argument) of every PRESENT (block row, super-frame), a channel's frames
+// in stream order; absent pairs -- a closed squelch, dmNONE: the reference returned before the hook -- are skipped, not delivered as
+// zeros.  Samples arrive as the reference's CPX: the float rows widened, PCM16 rows divided by 32767.  Returns the number of callbacks
+// (0 as well for a frame length that does not divide the super-frame).
+typedef std::function<void(uint32_t row, CPX *in, uint32_t numSamples)> CB_ModemProcessBlock;
+inline uint64_t feedModemBlock(const pebblegpu_modem_block &b, uint32_t demodFrames, const CB_ModemProcessBlock &processBlock)
+{
+    if (!b.host || !b.present || !b.n_superframes || !demodFrames || b.samples_per_superframe % demodFrames || !processBlock) return 0;
+    std::vector<CPX> frame(demodFrames);
+    uint64_t calls = 0;
+    for (uint32_t r = 0; r < b.n_channels; r++) {
+        const char *row = static_cast<const char *>(b.host) + (size_t)r * b.pitch_bytes;
+        for (uint32_t j = 0; j < b.n_superframes; j++) {
+            if (!b.present[(size_t)r * b.n_superframes + j]) continue;
+            for (uint64_t at = j * b.samples_per_superframe; at < (j + 1) * b.samples_per_superframe; at += demodFrames) {
+                for (uint32_t i = 0; i < demodFrames; i++) {
+                    if (b.format == PEBBLEGPU_AUDIO_F32) {
+                        const float *p = reinterpret_cast<const float *>(row) + 2 * (at + i);
+                        frame[i] = CPX(p[0], p[1]);
+                    } else {
+                        const int16_t *p = reinterpret_cast<const int16_t *>(row) + 2 * (at + i);
+                        frame[i] = CPX(p[0] / 32767.0, p[1] / 32767.0);
+                    }
+                }
+                processBlock(r, frame.data(), demodFrames);
+                calls++;
+            }
+        }
+    }
+    return calls;
+}
 
 // A bank whose channels are sharded across devices, driven by this one process and one consumer thread (pebblegpu_multibank_*): the
 // shape a Qt host needs to use more than one GPU.  Channels are global; the control slots are routed to

@@ -52,6 +52,8 @@ SYMBOLS = [
     "pebblegpu_receiver_audio_out_release", "pebblegpu_receiver_audio_out_dropped", "pebblegpu_audio_out_convert",
     "pebblegpu_receiver_record_open", "pebblegpu_receiver_record_close", "pebblegpu_receiver_record_next", "pebblegpu_receiver_record_release",
     "pebblegpu_iq_record_convert",
+    "pebblegpu_receiver_modem_out_open", "pebblegpu_receiver_modem_out_close", "pebblegpu_receiver_modem_out_next",
+    "pebblegpu_receiver_modem_out_release", "pebblegpu_receiver_modem_out_dropped", "pebblegpu_modem_out_convert", "pebblegpu_modem_out_layout",
     "pebblegpu_streambank_iq_out_open", "pebblegpu_streambank_iq_out_close", "pebblegpu_streambank_iq_out_next", "pebblegpu_streambank_iq_out_release",
     "pebblegpu_streambank_iq_out_dropped",
     "pebblegpu_streambank_display_open", "pebblegpu_streambank_display_close", "pebblegpu_streambank_display_next",
@@ -276,6 +278,12 @@ def _block_array(b):
     return out[:, :, 0] if per == 1 else out
 
 
+class ModemBlock(C.Structure):
+    """pebblegpu_modem_block: the modem hook's rows of one call, with the trailer's presence flags"""
+    _fields_ = AudioBlock._fields_ + [("rate", C.c_uint32), ("n_superframes", C.c_uint32), ("samples_per_superframe", C.c_uint64),
+                                      ("present", C.POINTER(C.c_uint8))]
+
+
 DISPLAY_DB_F32, DISPLAY_PIXELS_I32, DISPLAY_WATERFALL_ARGB32 = range(3)  # pebblegpu_display_format
 _DISPLAY_DTYPE = {DISPLAY_DB_F32: np.float32, DISPLAY_PIXELS_I32: np.int32, DISPLAY_WATERFALL_ARGB32: np.uint32}
 
@@ -429,6 +437,26 @@ def iq_record_convert(iq, lib=None):
     out = np.zeros(iq.shape, dtype=np.int16)
     check(L, L.pebblegpu_iq_record_convert(iq.ctypes.data_as(C.c_void_p), iq.shape[0], out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def modem_out_convert(fmt, iq, lib=None):
+    """the host twin of the modem ring's packing kernel: float32 [n, 2] (or complex64 [n]) -> [n, 2] float32 (verbatim) or int16 (the record rule)"""
+    L = lib or load_library()
+    iq = np.ascontiguousarray(iq)
+    if np.iscomplexobj(iq):
+        iq = iq.astype(np.complex64).view(np.float32)
+    iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1, 2)
+    out = np.zeros(iq.shape, dtype=np.int16 if int(fmt) == AUDIO_S16 else np.float32)
+    check(L, L.pebblegpu_modem_out_convert(int(fmt), iq.ctypes.data_as(C.c_void_p), iq.shape[0], out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def modem_out_layout(fmt, n_channels, samples_per_channel, n_superframes, lib=None):
+    """-> (pitch_bytes, trailer_offset, trailer_bytes) of a modem block"""
+    L = lib or load_library()
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(L, L.pebblegpu_modem_out_layout(int(fmt), int(n_channels), int(samples_per_channel), int(n_superframes), C.byref(a), C.byref(b), C.byref(c)))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def library_path():
@@ -607,6 +635,13 @@ def _declare(L):
     L.pebblegpu_receiver_record_next.argtypes = [vp, i32, blk]
     L.pebblegpu_receiver_record_release.argtypes = [vp, u64]
     L.pebblegpu_iq_record_convert.argtypes = [vp, u64, vp]
+    L.pebblegpu_receiver_modem_out_open.argtypes = [vp, i32, u32p, u32, u32]
+    L.pebblegpu_receiver_modem_out_close.argtypes = [vp]
+    L.pebblegpu_receiver_modem_out_next.argtypes = [vp, i32, C.POINTER(ModemBlock)]
+    L.pebblegpu_receiver_modem_out_release.argtypes = [vp, u64]
+    L.pebblegpu_receiver_modem_out_dropped.argtypes = [vp, C.POINTER(u64)]
+    L.pebblegpu_modem_out_convert.argtypes = [i32, vp, u64, vp]
+    L.pebblegpu_modem_out_layout.argtypes = [i32, u32, u64, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     dblk = C.POINTER(DisplayBlock)
     L.pebblegpu_streambank_iq_out_open.argtypes = [vp, i32, u32p, u32, u32]
     L.pebblegpu_streambank_iq_out_close.argtypes = [vp]
@@ -993,6 +1028,40 @@ class ReceiverBank:
 
     def record_release(self, call_index):
         check(self.L, self.L.pebblegpu_receiver_record_release(self.h, int(call_index)))
+
+    # ---- host egress: the modem hook ring (the rows a digital-modem plugin receives, with presence flags) ----
+    def modem_out_open(self, fmt=AUDIO_F32, channels=None, n_slots=4):
+        """channels: row r of every block is channel channels[r] (None: all, in order)"""
+        if channels is None:
+            check(self.L, self.L.pebblegpu_receiver_modem_out_open(self.h, int(fmt), None, 0, int(n_slots)))
+        else:
+            arr = (C.c_uint32 * max(1, len(channels)))(*[int(c) for c in channels])
+            check(self.L, self.L.pebblegpu_receiver_modem_out_open(self.h, int(fmt), arr, len(channels), int(n_slots)))
+
+    def modem_out_close(self):
+        check(self.L, self.L.pebblegpu_receiver_modem_out_close(self.h))
+
+    def modem_out_next(self, wait=True):
+        """-> (call_index, dropped_before, copy of the rows [rows, samples, 2], present uint8 [rows, super-frames], rate) or None; the block stays
+        taken until modem_out_release(call_index)"""
+        b = ModemBlock()
+        b.struct_size = C.sizeof(ModemBlock)
+        check(self.L, self.L.pebblegpu_receiver_modem_out_next(self.h, 1 if wait else 0, C.byref(b)))
+        if not b.host:
+            return None
+        rows, k = int(b.n_channels), int(b.n_superframes)
+        present = np.zeros((rows, k), dtype=np.uint8)
+        if rows * k:
+            present = np.ctypeslib.as_array(b.present, shape=(rows * k,)).copy().reshape(rows, k)
+        return int(b.call_index), int(b.dropped_before), _block_array(b), present, int(b.rate)
+
+    def modem_out_release(self, call_index):
+        check(self.L, self.L.pebblegpu_receiver_modem_out_release(self.h, int(call_index)))
+
+    def modem_out_dropped(self):
+        n = C.c_uint64()
+        check(self.L, self.L.pebblegpu_receiver_modem_out_dropped(self.h, C.byref(n)))
+        return int(n.value)
 
     # ---- host egress: the display ring (one or two panes per block) ----
     def display_open(self, panes, n_slots=4):

@@ -1,12 +1,14 @@
 // egress.h -- host egress: ingest.h in the other direction.  A ring of pinned host slots that a small packing kernel, queued behind a
 // process call on the call's own stream, fills through a device staging twin and a copy stream; the host waits for ONE slot's
-// "copied" event, never for the device.  Two users in Receiver (egress.hip), two in the stream bank (streambank.hip: the band-passed IQ
-// of selected streams and the display rows of a call's spectra; the ring itself knows neither), and the receiver's display ring
-// (display.hip: one or two panes per slot, the ring's one "row" being the whole slot):
+// "copied" event, never for the device.  Three users in Receiver (egress.hip: audio, recording, and the modem hook ring below), two in
+// the stream bank (streambank.hip: the band-passed IQ of selected streams and the display rows of a call's spectra; the ring itself
+// knows neither), and the receiver's display ring (display.hip: one or two panes per slot, the ring's one "row" being the whole slot):
 //   the audio output stage -- Receiver::processAudioData -> Audio::SendToOutput(in, n, m_gain, m_mute), application/receiver.cpp:1029-1035;
 //                             the sample rule is pebblelib/audiopa.cpp:304-343 (the same clip in pebblelib/audioqt.cpp:169-211)
 //   IQ recording           -- if (m_isRecording) m_recordingFile.WriteSamples(nextStep, numSamples), application/receiver.cpp:800-801;
 //                             the conversion is pebblelib/wavfile.cpp:377-396
+//   the modem hook         -- if (m_iDigitalModem != NULL) nextStep = m_iDigitalModem->processBlock(nextStep), application/receiver.cpp:979-980:
+//                             the rows it receives, read-only, with a trailer of presence flags (k_modem_pack)
 // Per call: the packing kernel writes the next slot's twin on the stream where the call's last writer ran, an event is recorded
 // there, the copy stream waits for it, copies device -> pinned host and records the slot's event.  Nothing the next call queues waits
 // for that copy.  One block per process call, always (a call without audio yields a block of 0 samples); call indices count from
@@ -136,5 +138,26 @@ constexpr uint32_t kStreamGateCarried = 0xFFFFFFFEu, kStreamGateNone = 0xFFFFFFF
 int run_iq_pack(hipStream_t s, const float2 *iq, long long pitch, long long n, const uint32_t *d_tab, uint32_t rows, int format, void *dst, uint64_t dst_pitch,
                 const StreamGate *gate = nullptr, long long frame = 0);
 int check_egress_slots(uint32_t n_slots);
+
+// ---- the modem hook ring (Receiver::modem_out_*): the rows DigitalModemInterface::processBlock receives (receiver.cpp:979-980) ----
+// one selected row as k_modem_pack reads it: the channel's row of the narrow branch's buffer, bit 31 = the channel is in dmNONE this call
+constexpr uint32_t kModemRowTuneOnly = 0x80000000u;
+// a block's layout, one function for the producer, the reader and the host tier: row r at r * pitch, the trailer -- one byte per (row,
+// super-frame), [r * n_sf + j], 1 = present -- at rows * pitch, padded to 16 bytes
+struct ModemLayout { uint64_t pitch, trailer_off, trailer_bytes; };
+inline ModemLayout modem_layout(uint32_t bytes_per_sample, uint32_t rows, uint64_t samples, uint32_t n_sf)
+{
+    ModemLayout l;
+    l.pitch = EgressRing::row_pitch(samples, bytes_per_sample);
+    l.trailer_off = (uint64_t)rows * l.pitch;
+    l.trailer_bytes = ((uint64_t)rows * n_sf + 15) & ~(uint64_t)15;
+    return l;
+}
+// rows x n samples of the narrow branch's buffer behind the noise filter (row r at iq + (tab[r] & ~kModemRowTuneOnly) * pitch), n = n_sf
+// super-frames of spf samples -> dst [rows][dst_pitch bytes] in `format` (F32: the float2 rows verbatim; S16: iq_record_s16 pairs) and
+// the trailer at dst + rows * dst_pitch.  A (row, super-frame) is absent -- zeros, flag 0 -- where the row is tune-only or
+// gate[channel * gate_stride + j] == 0 (gate == nullptr: no gate)
+int run_modem_pack(hipStream_t s, const float2 *iq, long long pitch, long long spf, int n_sf, const uint32_t *d_tab, uint32_t rows, int format,
+                   const unsigned char *gate, int gate_stride, void *dst, uint64_t dst_pitch);
 
 }  // namespace pg

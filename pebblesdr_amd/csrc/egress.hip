@@ -156,6 +156,64 @@ static __global__ __launch_bounds__(256) void k_iq_pack_gated(const float2 *__re
     iq_pack_body<S16, true>(iq, pitch, n, tab, dst, dst_pitch, gate, frame);
 }
 
+// The modem hook ring: the rows DigitalModemInterface::processBlock receives (receiver.cpp:979-980), behind the noise filter and ahead of
+// the AGC, for the selected channels (row r of the block is channel tab[r] & ~kModemRowTuneOnly), and the block's trailer in the same
+// launch.  A (row, super-frame) the reference never hands to the hook -- the bank's gate closed it (receiver.cpp:962-965), or the channel
+// is in dmNONE (:968-971) -- is absent: zeros instead of the samples (0.0f pairs, which iq_record_s16 turns into 0 pairs) and flag 0 in
+// trailer[r * n_sf + j]; a present one goes through k_iq_pack's loads, conversions and stores.  Every lane moves 16 bytes per access:
+// F32 one 16-byte load and one 16-byte store of two samples (consecutive lanes, consecutive 16 bytes, both ways), S16 two 16-byte loads
+// and one 16-byte store of four.  Rows whose source is not 16-byte aligned, or whose super-frame is no multiple of the lane's samples, go
+// sample by sample.  The trailer (and its padding to 16 bytes) is written by the first workgroup of each row.
+template <bool S16>
+static __global__ __launch_bounds__(256) void k_modem_pack(const float2 *__restrict__ iq, long long pitch, int spf, int n_sf, const uint32_t *__restrict__ tab,
+                                                            const unsigned char *__restrict__ gate, int gate_stride, unsigned char *__restrict__ dst,
+                                                            unsigned long long dst_pitch)
+{
+    constexpr int SPL = S16 ? 4 : 2;  // samples per lane and step
+    const uint32_t e = tab[blockIdx.y], ch = e & ~kModemRowTuneOnly;
+    const bool tune_only = (e & kModemRowTuneOnly) != 0;
+    const unsigned n = (unsigned)spf * (unsigned)n_sf;  // (run_modem_pack: below 2^31)
+    const float2 *src = iq + (long long)ch * pitch;
+    unsigned char *out = dst + (unsigned long long)blockIdx.y * dst_pitch;
+    const unsigned char *g = gate ? gate + (long long)ch * gate_stride : nullptr;
+    const bool whole = !tune_only && !g;  // every super-frame of the row is present: no look-up per step
+    if (blockIdx.x == 0) {
+        unsigned char *trailer = dst + (unsigned long long)gridDim.y * dst_pitch;
+        for (int j = threadIdx.x; j < n_sf; j += 256) trailer[(unsigned long long)blockIdx.y * n_sf + j] = (!tune_only && (!g || g[j])) ? 1 : 0;
+        if (blockIdx.y == 0) {
+            const unsigned used = gridDim.y * (unsigned)n_sf, padded = (used + 15u) & ~15u;
+            for (unsigned i = used + threadIdx.x; i < padded; i += 256) trailer[i] = 0;
+        }
+    }
+    const bool vec = (reinterpret_cast<unsigned long long>(src) & 15ull) == 0 && spf % SPL == 0;  // (SPL samples, one super-frame; n % SPL == 0)
+    for (unsigned i0 = (blockIdx.x * 256u + threadIdx.x) * SPL; i0 < n; i0 += gridDim.x * 256u * SPL) {
+        if (vec) {
+            const bool present = whole || (!tune_only && g[i0 / (unsigned)spf]);
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+            if (present) {
+                a = reinterpret_cast<const float4 *>(src + i0)[0];
+                if (S16) b = reinterpret_cast<const float4 *>(src + i0)[1];
+            }
+            if (!S16) {
+                *reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(out) + i0) = a;
+            } else {
+                const short2 q0 = make_short2(iq_record_s16(a.x), iq_record_s16(a.y)), q1 = make_short2(iq_record_s16(a.z), iq_record_s16(a.w));
+                const short2 q2 = make_short2(iq_record_s16(b.x), iq_record_s16(b.y)), q3 = make_short2(iq_record_s16(b.z), iq_record_s16(b.w));
+                uint4 w;
+                memcpy(&w.x, &q0, 4); memcpy(&w.y, &q1, 4); memcpy(&w.z, &q2, 4); memcpy(&w.w, &q3, 4);
+                *reinterpret_cast<uint4 *>(reinterpret_cast<short2 *>(out) + i0) = w;
+            }
+        } else {
+            for (unsigned i = i0; i < n && i < i0 + SPL; i++) {
+                const bool present = whole || (!tune_only && g[i / (unsigned)spf]);
+                const float2 v = present ? src[i] : make_float2(0.f, 0.f);
+                if (!S16) reinterpret_cast<float2 *>(out)[i] = v;
+                else reinterpret_cast<short2 *>(out)[i] = make_short2(iq_record_s16(v.x), iq_record_s16(v.y));
+            }
+        }
+    }
+}
+
 static unsigned pack_blocks(long long n)
 {
     long long b = (n + 1023) / 1024;
@@ -201,6 +259,22 @@ int run_iq_pack(hipStream_t s, const float2 *iq, long long pitch, long long n, c
     } else {
         launch(k_iq_pack<true>, grid, dim3(256), s, iq, pitch, n, d_tab, o, (unsigned long long)dst_pitch);
     }
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+int run_modem_pack(hipStream_t s, const float2 *iq, long long pitch, long long spf, int n_sf, const uint32_t *d_tab, uint32_t rows, int format,
+                   const unsigned char *gate, int gate_stride, void *dst, uint64_t dst_pitch)
+{
+    if (spf <= 0 || n_sf <= 0 || rows == 0) return 0;
+    const long long n = spf * n_sf;
+    if (n >= (1LL << 31)) return fail(PEBBLEGPU_E_SIZE, "a modem block of %lld samples per row", n);
+    const int spl = format == PEBBLEGPU_AUDIO_F32 ? 2 : 4;
+    long long b = (n + 256 * spl - 1) / (256 * spl);
+    const dim3 grid((unsigned)(b > 1024 ? 1024 : b), rows);
+    unsigned char *o = (unsigned char *)dst;
+    if (format == PEBBLEGPU_AUDIO_F32) launch(k_modem_pack<false>, grid, dim3(256), s, iq, pitch, (int)spf, n_sf, d_tab, gate, gate_stride, o, (unsigned long long)dst_pitch);
+    else launch(k_modem_pack<true>, grid, dim3(256), s, iq, pitch, (int)spf, n_sf, d_tab, gate, gate_stride, o, (unsigned long long)dst_pitch);
     PG_HIP(hipGetLastError());
     return 0;
 }
@@ -456,6 +530,104 @@ int Receiver::audio_out_dropped(uint64_t *blocks)
     std::lock_guard<std::mutex> lk(aout_.mu);
     if (!aout_.open) return fail(PEBBLEGPU_E_INVALID, "the audio ring is not open");
     *blocks = aout_.dropped;
+    return 0;
+}
+
+// ---- the modem hook ring: what m_iDigitalModem->processBlock receives (receiver.cpp:979-980), for a host's own decoders ----
+int Receiver::modem_out_open(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots)
+{
+    if (wfm) return fail(PEBBLEGPU_E_UNSUPPORTED, "the digital-modem hook is on the narrow branch (receiver.cpp:977-980): a WFM receiver has none");
+    if (format != PEBBLEGPU_AUDIO_F32 && format != PEBBLEGPU_AUDIO_S16)
+        return fail(PEBBLEGPU_E_INVALID, "modem blocks are PEBBLEGPU_AUDIO_F32 or PEBBLEGPU_AUDIO_S16 (I, Q pairs), not format %d", format);
+    if (int rc = check_egress_slots(n_slots)) return rc;
+    if (channels && n_channels == 0) return fail(PEBBLEGPU_E_INVALID, "an empty channel list");
+    std::vector<uint32_t> sel;
+    if (!channels) {
+        for (uint32_t c = 0; c < C; c++) sel.push_back(c);
+    } else {
+        std::vector<char> seen(C, 0);
+        for (uint32_t i = 0; i < n_channels; i++) {
+            if (channels[i] >= C) return fail(PEBBLEGPU_E_INVALID, "channel %u out of range", channels[i]);
+            if (seen[channels[i]]) return fail(PEBBLEGPU_E_INVALID, "channel %u is listed twice", channels[i]);
+            seen[channels[i]] = 1;
+            sel.push_back(channels[i]);
+        }
+    }
+    std::lock_guard<std::mutex> g(mu_);
+    if (mout_.open) return fail(PEBBLEGPU_E_INVALID, "the modem ring is already open");
+    PG_HIP(hipSetDevice(device));
+    const uint64_t max_n = (uint64_t)max_sf * (superframe / chain.total);
+    if (!d_mout_tab_) PG_TRY(d_mout_tab_.alloc(C));
+    std::lock_guard<std::mutex> lk(mout_.mu);
+    const uint32_t bps = kAudioBytes[format];
+    if (int rc = mout_.open_ring(n_slots, (uint32_t)sel.size(), bps, max_n, (uint32_t)format, modem_layout(bps, (uint32_t)sel.size(), 0, max_sf).trailer_bytes)) {
+        mout_.release();
+        return rc;
+    }
+    mout_sel_ = sel;
+    mout_tab_dirty_ = true;
+    return 0;
+}
+
+int Receiver::modem_out_close()
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (!mout_.open) return fail(PEBBLEGPU_E_INVALID, "the modem ring is not open");
+    if (int rc = sync()) return rc;
+    mout_.close_ring();
+    return 0;
+}
+
+// the selection for the coming call: the rows and which of them sit the call out in dmNONE.  Rare (open, a mode change), and drained
+// like the audio ring's table: the packing kernel of an earlier call may still be reading it
+int Receiver::upload_modem_table()
+{
+    std::vector<uint32_t> tab(mout_sel_.size());
+    for (size_t r = 0; r < tab.size(); r++) tab[r] = mout_sel_[r] | (ctl_[mout_sel_[r]].mode == PEBBLEGPU_DM_NONE ? kModemRowTuneOnly : 0u);
+    PG_HIP(hipStreamSynchronize(stream_));
+    PG_HIP(hipStreamSynchronize(chain_stream_));
+    PG_HIP(hipMemcpy(d_mout_tab_, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice));
+    mout_tab_dirty_ = false;
+    return 0;
+}
+
+// behind the noise filter and ahead of the AGC (which works in place), on the chain's stream: one launch, one event; n_sf super-frames
+// of spf samples, gate = the bank's decisions of this call or nullptr; n_sf == 0 (a one-channel receiver's closed call): nothing
+int Receiver::queue_modem_block(hipStream_t s, long long spf, int n_sf, const unsigned char *gate)
+{
+    EgressSlot *g = mout_.begin();
+    if (!g) return 0;
+    g->aux = (uint32_t)n_sf;
+    if (n_sf <= 0 || spf <= 0) return mout_.commit(g, s, 0);
+    const ModemLayout l = modem_layout(mout_.bytes_per_sample, mout_.rows, (uint64_t)spf * n_sf, (uint32_t)n_sf);
+    if (int rc = run_modem_pack(s, audio.data(), audio.pitch, spf, n_sf, d_mout_tab_, mout_.rows, (int)mout_.format, gate, (int)max_sf, g->d, l.pitch)) return rc;
+    return mout_.commit(g, s, (uint64_t)spf * n_sf, l.trailer_bytes);
+}
+
+int Receiver::modem_out_next(int wait, pebblegpu_modem_block *b)
+{
+    EgressBlock e;
+    if (int rc = mout_.next(device, wait, &e)) return rc;
+    const uint32_t n_sf = e.host && e.samples ? e.aux : 0;
+    b->format = e.format;
+    b->call_index = e.call;
+    b->host = e.host;
+    b->samples_per_channel = e.host ? e.samples : 0;
+    b->pitch_bytes = e.host ? e.pitch_bytes : 0;
+    b->n_channels = e.rows;
+    b->dropped_before = e.host ? e.dropped_before : 0;
+    b->rate = demod_rate_int;
+    b->n_superframes = n_sf;
+    b->samples_per_superframe = n_sf ? e.samples / n_sf : 0;
+    b->present = n_sf ? (const uint8_t *)e.host + (uint64_t)e.rows * e.pitch_bytes : nullptr;
+    return 0;
+}
+int Receiver::modem_out_release(uint64_t call_index) { return mout_.finish(call_index); }
+int Receiver::modem_out_dropped(uint64_t *blocks)
+{
+    std::lock_guard<std::mutex> lk(mout_.mu);
+    if (!mout_.open) return fail(PEBBLEGPU_E_INVALID, "the modem ring is not open");
+    *blocks = mout_.dropped;
     return 0;
 }
 

@@ -530,5 +530,58 @@ int pebblegpu_iq_record_convert(const float *iq, uint64_t n, int16_t *out)
     for (uint64_t i = 0; i < 2 * n; i++) out[i] = pg::iq_record_s16(iq[i]);
     return 0;
 }
+// ---- the modem hook ring ----
+static int modem_format(int format)
+{
+    if (format != PEBBLEGPU_AUDIO_F32 && format != PEBBLEGPU_AUDIO_S16)
+        return fail(PEBBLEGPU_E_INVALID, "modem blocks are PEBBLEGPU_AUDIO_F32 or PEBBLEGPU_AUDIO_S16 (I, Q pairs), not format %d", format);
+    return 0;
+}
+int pebblegpu_receiver_modem_out_open(pebblegpu_receiver *h, int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.modem_out_open(format, channels, n_channels, n_slots);
+}
+int pebblegpu_receiver_modem_out_close(pebblegpu_receiver *h)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.modem_out_close();
+}
+int pebblegpu_receiver_modem_out_next(pebblegpu_receiver *h, int wait, pebblegpu_modem_block *b)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    if (!b) return fail(PEBBLEGPU_E_INVALID, "null pebblegpu_modem_block");
+    if (b->struct_size != sizeof(pebblegpu_modem_block)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_modem_block size mismatch (ABI %d)", PEBBLEGPU_ABI_VERSION);
+    return h->rx.modem_out_next(wait, b);
+}
+int pebblegpu_receiver_modem_out_release(pebblegpu_receiver *h, uint64_t call_index)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.modem_out_release(call_index);
+}
+int pebblegpu_receiver_modem_out_dropped(const pebblegpu_receiver *h, uint64_t *blocks)
+{
+    if (!h || !blocks) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    return const_cast<pebblegpu_receiver *>(h)->rx.modem_out_dropped(blocks);
+}
+int pebblegpu_modem_out_convert(int format, const float *iq, uint64_t n, void *out)
+{
+    if (int rc = modem_format(format)) return rc;
+    if (n && (!iq || !out)) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    if (format == PEBBLEGPU_AUDIO_S16) return pebblegpu_iq_record_convert(iq, n, (int16_t *)out);
+    if (n) memcpy(out, iq, sizeof(float) * 2 * n);  // the float2 rows verbatim (NaN payloads included)
+    return 0;
+}
+int pebblegpu_modem_out_layout(int format, uint32_t n_channels, uint64_t samples_per_channel, uint32_t n_superframes, uint64_t *pitch_bytes,
+                               uint64_t *trailer_offset, uint64_t *trailer_bytes)
+{
+    if (int rc = modem_format(format)) return rc;
+    if (!pitch_bytes || !trailer_offset || !trailer_bytes) return fail(PEBBLEGPU_E_INVALID, "null argument");
+    const pg::ModemLayout l = pg::modem_layout(pg::kAudioBytes[format], n_channels, samples_per_channel, n_superframes);
+    *pitch_bytes = l.pitch;
+    *trailer_offset = l.trailer_off;
+    *trailer_bytes = l.trailer_bytes;
+    return 0;
+}
 
 }  // extern "C"

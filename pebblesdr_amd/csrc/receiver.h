@@ -744,6 +744,13 @@ public:
     int record_close();
     int record_next(int wait, pebblegpu_audio_block *b);
     int record_release(uint64_t call_index);
+    // the modem hook ring: the rows m_iDigitalModem->processBlock receives (receiver.cpp:979-980) for a selection of channels, with a
+    // trailer that says which (row, super-frame) the reference would have handed to the hook at all
+    int modem_out_open(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots);
+    int modem_out_close();
+    int modem_out_next(int wait, pebblegpu_modem_block *b);
+    int modem_out_release(uint64_t call_index);
+    int modem_out_dropped(uint64_t *blocks);
     // the display ring (display.hip): the rows a call's display transforms computed, one or two panes per block, through the same slots
     int display_open(const pebblegpu_display_pane *panes, uint32_t n_panes, uint32_t n_slots);
     int display_close();
@@ -931,6 +938,12 @@ private:
     int upload_audio_table();
     int queue_audio_block(hipStream_t s, uint64_t n);
     int queue_record_block(hipStream_t s, const float2 *iq, const RawSrc *raw, uint64_t n);
+    EgressRing mout_;                 // the modem hook ring; closed: a call queues nothing for it
+    std::vector<uint32_t> mout_sel_;  // row r of a block is channel mout_sel_[r]
+    DevBuf<uint32_t> d_mout_tab_;     // [C] the selected rows: channel | kModemRowTuneOnly
+    bool mout_tab_dirty_ = false;
+    int upload_modem_table();
+    int queue_modem_block(hipStream_t s, long long spf, int n_sf, const unsigned char *gate);
     struct DisplayRing *disp_ = nullptr;  // allocated at the first open, kept until the receiver goes (a reader may hold it)
     bool disp_open_ = false;          // (under mu_: what a process call looks at)
     int upload_display_tables();

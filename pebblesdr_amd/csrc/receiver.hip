@@ -131,6 +131,7 @@ Receiver::~Receiver()
     ext_ingest_.release();
     aout_.release();
     rec_.release();
+    mout_.release();
     display_destroy();  // (closes an open display ring: waits for a reader that is inside _next)
     if (map_ev_) (void)hipEventDestroy(map_ev_);
     resamp_.release();
@@ -170,6 +171,7 @@ int Receiver::set_mode(uint32_t ch, int mode)
     std::lock_guard<std::mutex> g(mu_);
     touched_ = true;  // the next call joins its two pipelines before the change is applied
     if (ctl_[ch].mode != mode) am_list_dirty_ = true;
+    if (ctl_[ch].mode != mode) mout_tab_dirty_ = true;  // (the modem ring's table says which rows are in dmNONE)
     ctl_[ch].mode = mode;
     if (!wfm) {  // "Tune only mode": the reference returns before NoiseFilter and AGC (receiver.cpp:968-971): their states stay frozen
         agc_.set_muted(ch, mode == PEBBLEGPU_DM_NONE);
@@ -664,6 +666,7 @@ int Receiver::join_and_apply(Call &c)
     touched_ = false;
     if (int rc = cond_.apply(stream_)) return rc;
     if (aout_.open && aout_tab_dirty_) { if (int rc = upload_audio_table()) return rc; }
+    if (mout_.open && mout_tab_dirty_) { if (int rc = upload_modem_table()) return rc; }
     if (disp_open_) { if (int rc = upload_display_tables()) return rc; }  // (only after open or set_pane)
     return 0;
 }
@@ -905,6 +908,7 @@ int Receiver::tail_closed(Call &c)
 {
     last_audio_n = 0;
     if (profile_detail) { if (wfm) PG_HIP(hipEventRecord(c.ev[4], c.cs)); }
+    if (mout_.open) { if (int rc = queue_modem_block(c.cs, 0, 0, nullptr)) return rc; }  // the reference returned before the hook: a block of 0 samples
     for (int pt : {PEBBLEGPU_TAP_MODEM, PEBBLEGPU_TAP_POST_DEMOD}) {  // "Tune only mode" returns before both points: their rows read zero
         if (!(taps_ >> pt & 1u)) continue;
         PG_HIP(hipMemsetAsync(d_tap_[pt], 0, sizeof(float2) * (size_t)c.nd * C, c.cs));
@@ -935,10 +939,18 @@ int Receiver::tail_bank_gated(Call &c)
         }
         if (int rc = run_gate_eval_rows(cs, d_smeter, smeter_pitch, d_sm_carry, rows.data(), k, d_squelch, d_gate, (int)max_sf, C)) return rc;
     } else if (int rc = run_gate_eval(cs, d_smeter, smeter_pitch, (int)(superframe / nf), k, d_squelch, d_gate, (int)max_sf, C)) return rc;
+    // The modem ring reads every super-frame's rows between the noise filter and the AGC, which works in place.  With the ring open the
+    // noise filter's launches of all k super-frames are queued first (its state depends on nothing the AGC or a demodulator writes, and the
+    // segments are disjoint: the same launches on the same data), then ONE packing launch, then the rest per super-frame
+    const bool anf_first = mout_.open;
+    if (anf_first) {
+        for (int j = 0; j < k; j++) { if (int rc = anf_.run(cs, audio.data() + (long long)j * spf, audio.pitch, spf, Gate{d_gate, (int)max_sf, j})) return rc; }
+        if (int rc = queue_modem_block(cs, spf, k, d_gate)) return rc;
+    }
     for (int j = 0; j < k; j++) {
         const Gate gate{d_gate, (int)max_sf, j};
         float2 *seg = audio.data() + (long long)j * spf;
-        if (int rc = anf_.run(cs, seg, audio.pitch, spf, gate)) return rc;
+        if (!anf_first) { if (int rc = anf_.run(cs, seg, audio.pitch, spf, gate)) return rc; }
         if (int rc = agc_.run(cs, seg, audio.pitch, spf, gate)) return rc;
         if (int rc = am_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate, false)) return rc;
         if (sam_.C) { if (int rc = sam_.run(cs, seg, audio.pitch, seg, audio.pitch, spf, gate)) return rc; }
@@ -957,6 +969,10 @@ int Receiver::tail_narrow(Call &c)
     if (taps_ >> PEBBLEGPU_TAP_MODEM & 1u) {  // the frame m_iDigitalModem->processBlock receives (a dmNONE channel's call has returned before, :968-971)
         if (int rc = copy_tap(cs, PEBBLEGPU_TAP_MODEM, audio.data(), audio.pitch, nd, C)) return rc;
         if (int rc = clear_tune_only_rows(cs, d_tap_[PEBBLEGPU_TAP_MODEM], nd, nd)) return rc;
+    }
+    if (mout_.open) {  // the same rows, to the host's own modems: one launch per call
+        const int k = (int)(c.n / superframe);
+        if (int rc = queue_modem_block(cs, nd / k, k, nullptr)) return rc;
     }
     // m_iDigitalModem->processBlock, receiver.cpp:979-980: the Morse modem reads the rows before the AGC overwrites them
     if (morse_.any()) { if (int rc = morse_.run(cs, audio.data(), audio.pitch, nd)) return rc; }
@@ -1251,8 +1267,8 @@ int Receiver::process_iq(const double *iq, uint16_t n, double *audio_out, uint32
         return fail(PEBBLEGPU_E_UNSUPPORTED, "the input conditioners run on the batched device path (pebblegpu_receiver_process) only");
     if (tb_.any() || taps_)  // (here `iq` is a host CPX *: the host injects and displays itself)
         return fail(PEBBLEGPU_E_UNSUPPORTED, "the test bench's generator and taps run on the batched device path (pebblegpu_receiver_process) only");
-    if (aout_.open || rec_.open || disp_open_)  // (this entry point returns its audio and its spectrum itself, and the host holds the frame it passes in)
-        return fail(PEBBLEGPU_E_UNSUPPORTED, "the audio, recording and display rings follow the batched device path (pebblegpu_receiver_process) only: close them first");
+    if (aout_.open || rec_.open || mout_.open || disp_open_)  // (this entry point returns its audio and its spectrum itself, and the host holds the frame it passes in)
+        return fail(PEBBLEGPU_E_UNSUPPORTED, "the audio, recording, modem and display rings follow the batched device path (pebblegpu_receiver_process) only: close them first");
     PG_HIP(hipSetDevice(device));
     if (!d_stage_in_) PG_TRY(d_stage_in_.alloc(superframe));
     h_frame_.resize((size_t)nf * 2);
