@@ -984,6 +984,50 @@ int pebblegpu_receiver_modem_out_close(pebblegpu_receiver *rx);   /* as pebblegp
 int pebblegpu_receiver_modem_out_next(pebblegpu_receiver *rx, int wait, pebblegpu_modem_block *b);
 int pebblegpu_receiver_modem_out_release(pebblegpu_receiver *rx, uint64_t call_index);
 int pebblegpu_receiver_modem_out_dropped(const pebblegpu_receiver *rx, uint64_t *blocks);
+/* The modem hook ring AT A MODEM RATE: the same ring, opened with a modem bandwidth and a minimum rate, delivers every selected channel's
+ * rows already decimated on the device by the reference's own Decimator chain for those parameters --
+ * Decimator::buildDecimationChain(demodulator rate, max_bw, min_rate), pebblelib/decimator.cpp:64-149 (vDSP path, merged stages
+ * included), the first thing a modem plugin does with its block (Morse::setSampleRate, plugins/MorseDigitalModem/morse.cpp:174-193, and
+ * the head of its processBlock, :778-782).  At (1000 Hz, 8000 Hz) on a 64 kHz bank an eighth of the bytes cross the link and the host's
+ * modems start at their Goertzel, PLL or matched filter.  min_rate == 0: the reference's minDecimatedSampleRate (15000).
+ * THE STREAM of one selected channel is what ONE Decimator object, fresh when the ring is opened (all histories zero), produces when it
+ * is fed, in order, exactly the (channel, super-frame) pairs the ring delivers as present, and nothing else: over an ABSENT pair (a closed
+ * gate, dmNONE -- zeros and flag 0, as above), over a one-channel receiver's closed call (its block of 0 samples) and over a block the
+ * full ring DROPPED (dropped_before: it was never delivered) the channel's decimator state stands still, and the next present pair
+ * continues from the last delivered one.  Retunes, band-pass changes and mode changes other than to or from dmNONE reset nothing (the
+ * reference's modem is not told); close followed by open gives a fresh decimator.  THE BLOCK is pebblegpu_modem_block with the same
+ * trailer, layout and host twins: samples_per_superframe = demodulator samples per super-frame / D, rate = (uint32_t)(int) of the chain's
+ * achieved rate (the cast of morse.cpp:193: 39062.5 Hz with (1000, 8000) gives 4882), F32 rows the decimated float pairs, S16 rows
+ * pebblegpu_iq_record_convert of those same floats.  An EMPTY CHAIN (min_rate at or above the demodulator rate, or no design fits:
+ * decimator.cpp:155-160 copies) gives bit for bit the blocks of pebblegpu_receiver_modem_out_open.  _next, _release, _close and _dropped
+ * are the functions above; one modem ring of either kind is open at a time, and everything said above about the ring stays true: one
+ * block per call, a full ring drops and counts, read-only, no call's route and no other kernel changes.  One launch per call
+ * (k_modem_rate_pack, where k_modem_pack is queued otherwise) carries tiles of every (row, super-frame) through the whole chain in LDS;
+ * there is no per-stage state, only the last `lookback` delivered demodulator samples per row.
+ * pebblegpu_modem_rate_plan (no device): the chain, its rates and its look-back for a demodulator rate and a super-frame, with the
+ * refusals of the open, each of which leaves the handle as it was: PEBBLEGPU_E_UNSUPPORTED -- a WFM receiver (open only); a chain that
+ * contains a CIC3 stage, e.g. (64000, 100, 8000) -> [(cic3, 2), (hb11, 4)]: the merged CIC3's two-sample form is not built here; more
+ * than PEBBLEGPU_MODEM_RATE_MAX_STAGES stages; a chain whose smallest tile (4 outputs and the look-back) exceeds the kernel's 4096
+ * samples of LDS.  PEBBLEGPU_E_SIZE -- the super-frame's demodulator samples are no multiple of D; a stage would receive fewer inputs
+ * from one super-frame than it has taps (the reference drops samples unfiltered there, decimator.cpp:602-625); the look-back exceeds
+ * one super-frame.  PEBBLEGPU_E_INVALID -- max_bw == 0, and everything pebblegpu_receiver_modem_out_open refuses.  Not built: modem
+ * chains of the CDownConvert kind (SetDataRate, the WWV plugin's form), the hook on WFM, on the stream bank and on pebblegpu_process_iq,
+ * a per-channel (max_bw, min_rate). */
+#define PEBBLEGPU_MODEM_RATE_MAX_STAGES 16
+typedef struct {
+    uint32_t struct_size;            /* = sizeof(pebblegpu_modem_rate_info), set by the caller */
+    uint32_t rate_int;               /* (uint32_t)(int)rate: what the blocks report */
+    float rate;                      /* the chain's achieved rate (Decimator's float) */
+    uint32_t total_decimation;       /* D */
+    uint32_t n_stages;               /* 0: an empty chain, the plain ring */
+    uint32_t lookback;               /* H = sum_j (taps_j - 1) * prod_{i<j} stride_i, in demodulator samples */
+    uint64_t samples_per_superframe; /* of the blocks: the argument / D */
+    uint32_t taps[PEBBLEGPU_MODEM_RATE_MAX_STAGES];
+    uint32_t stride[PEBBLEGPU_MODEM_RATE_MAX_STAGES];   /* decimate-by of the stage, merged picks included */
+} pebblegpu_modem_rate_info;
+int pebblegpu_receiver_modem_out_open_rate(pebblegpu_receiver *rx, int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots,
+                                           uint32_t max_bw, uint32_t min_rate);
+int pebblegpu_modem_rate_plan(uint32_t demod_rate, uint64_t samples_per_superframe, uint32_t max_bw, uint32_t min_rate, pebblegpu_modem_rate_info *out);
 /* host twin of the packing kernel (no device): n IQ samples of interleaved float I, Q -> out in `format` (F32: copied; S16: the record twin) */
 int pebblegpu_modem_out_convert(int format, const float *iq, uint64_t n, void *out);
 /* a block's layout (no device), the function the producer and the reader use: the row pitch, and where the trailer of n_channels *

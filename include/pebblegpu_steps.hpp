@@ -626,6 +626,16 @@ public:
         if (h && status == 0) modemOpen = true;
         return status;
     }
+    // The same ring at a modem rate (pebblegpu_receiver_modem_out_open_rate): every row already through the reference's own Decimator
+    // chain for (maxBw, minRate) -- what Morse::setSampleRate builds (morse.cpp:174-193) and the plugin runs at the head of processBlock --
+    // on the device.  minRate 0: the reference's minDecimatedSampleRate.  The blocks report the modem's rate and its samples per
+    // super-frame; feedModemBlock then takes the MODEM's frame length (the demodulator frame over the chain's decimation).
+    int modemOutOpenRate(int format, uint32_t nSlots, uint32_t maxBw, uint32_t minRate)
+    {
+        if (h) status = report("receiver_modem_out_open_rate", pebblegpu_receiver_modem_out_open_rate(h, format, nullptr, 0, nSlots, maxBw, minRate));
+        if (h && status == 0) modemOpen = true;
+        return status;
+    }
     int modemOutClose()
     {
         if (h) status = report("receiver_modem_out_close", pebblegpu_receiver_modem_out_close(h));
@@ -718,7 +728,8 @@ private:
 // decimation, DigitalModemInterface::setSampleRate's second argument) of every PRESENT (block row, super-frame), a channel's frames
 // in stream order; absent pairs -- a closed squelch, dmNONE: the reference returned before the hook -- are skipped, not delivered as
 // zeros.  Samples arrive as the reference's CPX: the float rows widened, PCM16 rows divided by 32767.  Returns the number of callbacks
-// (0 as well for a frame length that does not divide the super-frame).
+// (0 as well for a frame length that does not divide the super-frame).  On a ring opened at a modem rate (modemOutOpenRate) the rows
+// are at the modem's rate and demodFrames is the MODEM's frame: the demodulator frame over the chain's total decimation.
 typedef std::function<void(uint32_t row, CPX *in, uint32_t numSamples)> CB_ModemProcessBlock;
 inline uint64_t feedModemBlock(const pebblegpu_modem_block &b, uint32_t demodFrames, const CB_ModemProcessBlock &processBlock)
 {

@@ -14,6 +14,7 @@ from .binding import (  # noqa: F401
     MorseStation, morse_station, morse_station_plan, morse_station_marks, MORSE_MAX_STATIONS,
     MultiBank, multibank_plan, MULTIBANK_MAX_SHARDS, MULTIBANK_SPECTRUM_SHARD0,
     AUDIO_F32, AUDIO_S16, AUDIO_S16_MONO, AudioBlock, audio_out_convert, iq_record_convert, ModemBlock, modem_out_convert, modem_out_layout,
+    ModemRateInfo, modem_rate_plan, MODEM_RATE_MAX_STAGES,
     DISPLAY_DB_F32, DISPLAY_PIXELS_I32, DISPLAY_WATERFALL_ARGB32, DisplayBlock, waterfall_colors,
     PANE_SPECTRUM, PANE_ZOOM, DisplayPane, display_pane,
     AUTO_SCALE_MAX, AUTO_SCALE_MIN, DisplayScale, DISPLAY_SCALE, auto_scale_row,
@@ -26,7 +27,7 @@ __all__ = [
     "PebbleGpuError", "load_library", "library_path", "ReceiverBank", "StreamBank", "DeviceBuffer", "ScreenMap", "screen_map",
     "Mixer", "Decimator", "DownConvert", "FastFIR", "Demod", "Spectrum", "Morse", "morse_token_to_dotdash",
     "SigGen", "Sweep", "sweep", "sweep_plan", "MorseStation", "morse_station", "morse_station_plan",
-    "MultiBank", "multibank_plan", "audio_out_convert", "iq_record_convert", "ModemBlock", "modem_out_convert", "modem_out_layout", "DisplayBlock", "waterfall_colors",
+    "MultiBank", "multibank_plan", "audio_out_convert", "iq_record_convert", "ModemBlock", "modem_out_convert", "modem_out_layout", "ModemRateInfo", "modem_rate_plan", "DisplayBlock", "waterfall_colors",
     "PANE_SPECTRUM", "PANE_ZOOM", "DisplayPane", "display_pane",
     "AUTO_SCALE_MAX", "AUTO_SCALE_MIN", "DisplayScale", "DISPLAY_SCALE", "auto_scale_row",
     "StreamGateEntry", "STREAM_GATE", "GATE_ROW_CARRIED", "GATE_ROW_NONE", "signal_strength_row",

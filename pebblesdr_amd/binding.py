@@ -54,6 +54,7 @@ SYMBOLS = [
     "pebblegpu_iq_record_convert",
     "pebblegpu_receiver_modem_out_open", "pebblegpu_receiver_modem_out_close", "pebblegpu_receiver_modem_out_next",
     "pebblegpu_receiver_modem_out_release", "pebblegpu_receiver_modem_out_dropped", "pebblegpu_modem_out_convert", "pebblegpu_modem_out_layout",
+    "pebblegpu_receiver_modem_out_open_rate", "pebblegpu_modem_rate_plan",
     "pebblegpu_streambank_iq_out_open", "pebblegpu_streambank_iq_out_close", "pebblegpu_streambank_iq_out_next", "pebblegpu_streambank_iq_out_release",
     "pebblegpu_streambank_iq_out_dropped",
     "pebblegpu_streambank_display_open", "pebblegpu_streambank_display_close", "pebblegpu_streambank_display_next",
@@ -284,6 +285,20 @@ class ModemBlock(C.Structure):
                                       ("present", C.POINTER(C.c_uint8))]
 
 
+MODEM_RATE_MAX_STAGES = 16
+
+
+class ModemRateInfo(C.Structure):
+    """pebblegpu_modem_rate_info: the chain of a modem ring at a modem rate"""
+    _fields_ = [("struct_size", C.c_uint32), ("rate_int", C.c_uint32), ("rate", C.c_float), ("total_decimation", C.c_uint32), ("n_stages", C.c_uint32),
+                ("lookback", C.c_uint32), ("samples_per_superframe", C.c_uint64), ("taps", C.c_uint32 * MODEM_RATE_MAX_STAGES),
+                ("stride", C.c_uint32 * MODEM_RATE_MAX_STAGES)]
+
+    def chain(self):
+        """[(taps, stride)], as oracle.Decimator.chain()"""
+        return [(int(self.taps[j]), int(self.stride[j])) for j in range(self.n_stages)]
+
+
 DISPLAY_DB_F32, DISPLAY_PIXELS_I32, DISPLAY_WATERFALL_ARGB32 = range(3)  # pebblegpu_display_format
 _DISPLAY_DTYPE = {DISPLAY_DB_F32: np.float32, DISPLAY_PIXELS_I32: np.int32, DISPLAY_WATERFALL_ARGB32: np.uint32}
 
@@ -457,6 +472,16 @@ def modem_out_layout(fmt, n_channels, samples_per_channel, n_superframes, lib=No
     a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     check(L, L.pebblegpu_modem_out_layout(int(fmt), int(n_channels), int(samples_per_channel), int(n_superframes), C.byref(a), C.byref(b), C.byref(c)))
     return int(a.value), int(b.value), int(c.value)
+
+
+def modem_rate_plan(demod_rate, samples_per_superframe, max_bw, min_rate=0, lib=None):
+    """-> ModemRateInfo for Decimator::buildDecimationChain(demod_rate, max_bw, min_rate) on super-frames of that many demodulator samples;
+    raises with the code a modem_out_open at that rate would"""
+    L = lib or load_library()
+    info = ModemRateInfo()
+    info.struct_size = C.sizeof(ModemRateInfo)
+    check(L, L.pebblegpu_modem_rate_plan(int(demod_rate), int(samples_per_superframe), int(max_bw), int(min_rate), C.byref(info)))
+    return info
 
 
 def library_path():
@@ -636,6 +661,8 @@ def _declare(L):
     L.pebblegpu_receiver_record_release.argtypes = [vp, u64]
     L.pebblegpu_iq_record_convert.argtypes = [vp, u64, vp]
     L.pebblegpu_receiver_modem_out_open.argtypes = [vp, i32, u32p, u32, u32]
+    L.pebblegpu_receiver_modem_out_open_rate.argtypes = [vp, i32, u32p, u32, u32, u32, u32]
+    L.pebblegpu_modem_rate_plan.argtypes = [u32, u64, u32, u32, C.POINTER(ModemRateInfo)]
     L.pebblegpu_receiver_modem_out_close.argtypes = [vp]
     L.pebblegpu_receiver_modem_out_next.argtypes = [vp, i32, C.POINTER(ModemBlock)]
     L.pebblegpu_receiver_modem_out_release.argtypes = [vp, u64]
@@ -1037,6 +1064,14 @@ class ReceiverBank:
         else:
             arr = (C.c_uint32 * max(1, len(channels)))(*[int(c) for c in channels])
             check(self.L, self.L.pebblegpu_receiver_modem_out_open(self.h, int(fmt), arr, len(channels), int(n_slots)))
+
+    def modem_out_open_rate(self, max_bw, min_rate=0, fmt=AUDIO_F32, channels=None, n_slots=4):
+        """the same ring with every row decimated on the device by Decimator::buildDecimationChain(demodulator rate, max_bw, min_rate)"""
+        if channels is None:
+            check(self.L, self.L.pebblegpu_receiver_modem_out_open_rate(self.h, int(fmt), None, 0, int(n_slots), int(max_bw), int(min_rate)))
+        else:
+            arr = (C.c_uint32 * max(1, len(channels)))(*[int(c) for c in channels])
+            check(self.L, self.L.pebblegpu_receiver_modem_out_open_rate(self.h, int(fmt), arr, len(channels), int(n_slots), int(max_bw), int(min_rate)))
 
     def modem_out_close(self):
         check(self.L, self.L.pebblegpu_receiver_modem_out_close(self.h))

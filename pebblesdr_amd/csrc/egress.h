@@ -8,7 +8,8 @@
 //   IQ recording           -- if (m_isRecording) m_recordingFile.WriteSamples(nextStep, numSamples), application/receiver.cpp:800-801;
 //                             the conversion is pebblelib/wavfile.cpp:377-396
 //   the modem hook         -- if (m_iDigitalModem != NULL) nextStep = m_iDigitalModem->processBlock(nextStep), application/receiver.cpp:979-980:
-//                             the rows it receives, read-only, with a trailer of presence flags (k_modem_pack)
+//                             the rows it receives, read-only, with a trailer of presence flags (k_modem_pack), or those rows through
+//                             a modem's own Decimator chain first (k_modem_rate_pack)
 // Per call: the packing kernel writes the next slot's twin on the stream where the call's last writer ran, an event is recorded
 // there, the copy stream waits for it, copies device -> pinned host and records the slot's event.  Nothing the next call queues waits
 // for that copy.  One block per process call, always (a call without audio yields a block of 0 samples); call indices count from
@@ -20,6 +21,7 @@
 #include <condition_variable>
 #include <mutex>
 #include "common.h"
+#include "design.h"
 #include "devmem.h"
 
 namespace pg {
@@ -159,5 +161,30 @@ inline ModemLayout modem_layout(uint32_t bytes_per_sample, uint32_t rows, uint64
 // gate[channel * gate_stride + j] == 0 (gate == nullptr: no gate)
 int run_modem_pack(hipStream_t s, const float2 *iq, long long pitch, long long spf, int n_sf, const uint32_t *d_tab, uint32_t rows, int format,
                    const unsigned char *gate, int gate_stride, void *dst, uint64_t dst_pitch);
+
+// ---- the same ring at a modem rate (Receiver::modem_out_open_rate): every selected row through the reference's own Decimator chain for
+// (demodulator rate, max_bw, min_rate) -- Decimator::buildDecimationChain, pebblelib/decimator.cpp:64-149, what Morse::setSampleRate builds
+// (morse.cpp:174-193) and runs at the head of processBlock -- before it crosses the link ----
+// The plan, one function for pebblegpu_modem_rate_plan and the open: the chain, its look-back H = sum_j (T_j - 1) prod_{i<j} stride_i in
+// demodulator samples (the raw samples in front of a segment from which every stage recomputes its own history), and the refusals
+struct ModemRatePlan {
+    design::Chain chain;
+    uint32_t rate_int = 0;   // (uint32_t)(int)chain.rate: int actualModemRate, morse.cpp:193
+    uint32_t lookback = 0;   // H
+    uint64_t out_spf = 0;    // samples per super-frame behind the chain
+    uint32_t tile = 0;       // modem-rate outputs one workgroup of k_modem_rate_pack carries (0: an empty chain, nothing to launch)
+    uint32_t lds_a = 0, lds_b = 0;  // float2 of the kernel's two LDS buffers
+};
+int modem_rate_plan(uint32_t demod_rate, uint64_t spf, uint32_t max_bw, uint32_t min_rate, ModemRatePlan *out);
+// what k_modem_rate_pack needs to know about the chain, by value
+struct ModemRateChain {
+    int n_stages, D, H, tile, lds_a, lds_b;
+    int taps[kMaxStages], stride[kMaxStages];
+};
+// rows x n_sf super-frames of spf samples -> dst rows of n_sf * spf / D samples in `format` and the trailer, as run_modem_pack; taps:
+// [stage][kMaxTaps] fp32; carry: [2][rows][H] float2, read at parity p and written at p ^ 1 (the caller flips p after every launch)
+int run_modem_rate_pack(hipStream_t s, const float2 *iq, long long pitch, long long spf, int n_sf, const uint32_t *d_tab, uint32_t rows, int format,
+                        const unsigned char *gate, int gate_stride, void *dst, uint64_t dst_pitch, const ModemRatePlan &plan, const float *d_taps,
+                        float2 *d_carry, int parity);
 
 }  // namespace pg

@@ -214,6 +214,140 @@ static __global__ __launch_bounds__(256) void k_modem_pack(const float2 *__restr
     }
 }
 
+// The same block at a modem rate: every present (row, super-frame) through the reference's Decimator chain for the ring's (max_bw,
+// min_rate) -- pebblelib/decimator.cpp, vDSP path, as design::build_chain merges it; stage by stage k_morse_fir's arithmetic,
+// out[o] = sum_p h[p] x[o stride - (T - 1) + p] with fmaf in tap order -- in ONE launch.  grid (tiles of modem-rate outputs, block rows,
+// super-frames of the call); a workgroup carries one tile of one (row, super-frame) through the whole cascade in LDS:
+//   load   tile * D + H demodulator samples: the tile's own and the H in front of them (16-byte loads where the row allows);
+//   stages ping-pong between two LDS buffers; in local indices stage j is out[q] = sum_p h[p] in[q stride_j + p], because the span starts
+//          exactly H = sum_j (T_j - 1) prod_{i<j} stride_i samples early and every stage's own look-back is the tail of that sum;
+//   store  16 bytes per lane (two float pairs, or four PCM16 pairs by iq_record_s16).
+// No per-stage state: a super-frame is a multiple of D, so recomputing every stage from the H raw samples in front of a segment IS the
+// streaming decimator.  Those H samples are the tail of the nearest present super-frame j' < j of this call, still in the audio rows
+// (the row's gate bytes say which), or, where there is none, the row's carry.  The carry is double-buffered by launch parity: every
+// workgroup reads carry_in; the workgroup that owns the last tile of the row's last present super-frame writes carry_out from that
+// super-frame's last H inputs; the first workgroup of a row without a present pair copies carry_in to carry_out.  The host flips the
+// parity per launch, a dropped block launches nothing: the state stands still over what was not delivered.  Absent pairs store zeros
+// and flag 0 and read nothing.  The first workgroup of each row writes the row's trailer flags, that of row 0 the trailer's padding.
+// LDS: [lds_a float2][lds_b float2][n_stages * kMaxTaps float] (modem_rate_plan sizes it: under 64 KiB)
+template <bool S16>
+static __global__ __launch_bounds__(256) void k_modem_rate_pack(const float2 *__restrict__ iq, long long pitch, int spf, int n_sf,
+                                                                 const uint32_t *__restrict__ tab, const unsigned char *__restrict__ gate, int gate_stride,
+                                                                 unsigned char *__restrict__ dst, unsigned long long dst_pitch, ModemRateChain c,
+                                                                 const float *__restrict__ taps, const float2 *__restrict__ carry_in,
+                                                                 float2 *__restrict__ carry_out)
+{
+    constexpr int SPL = S16 ? 4 : 2;  // samples per lane and 16-byte store
+    extern __shared__ float4 lds_rate[];
+    float2 *A = reinterpret_cast<float2 *>(lds_rate), *B = A + c.lds_a;
+    const int tid = threadIdx.x, r = blockIdx.y, j = blockIdx.z;
+    const uint32_t e = tab[r], chn = e & ~kModemRowTuneOnly;
+    const bool tune_only = (e & kModemRowTuneOnly) != 0;
+    const float2 *src = iq + (long long)chn * pitch;
+    const unsigned char *g = gate ? gate + (long long)chn * gate_stride : nullptr;
+    const int D = c.D, H = c.H, m = spf / D;  // m modem-rate samples per super-frame
+    const int o0 = (int)blockIdx.x * c.tile, tn = m - o0 < c.tile ? m - o0 : c.tile;
+    // the row's present super-frames (uniform over the workgroup): the nearest one in front of j, and whether one follows
+    int jprev = -1, any = 0, later = 0;
+    for (int q = 0; q < n_sf; q++) {
+        const int p = (!tune_only && (!g || g[q])) ? 1 : 0;
+        any |= p;
+        if (p && q < j) jprev = q;
+        if (p && q > j) later = 1;
+    }
+    const bool present = !tune_only && (!g || g[j]);
+    if (blockIdx.x == 0 && j == 0) {
+        unsigned char *trailer = dst + (unsigned long long)gridDim.y * dst_pitch;
+        for (int q = tid; q < n_sf; q += 256) trailer[(unsigned long long)r * n_sf + q] = (!tune_only && (!g || g[q])) ? 1 : 0;
+        if (r == 0) {
+            const unsigned used = gridDim.y * (unsigned)n_sf, padded = (used + 15u) & ~15u;
+            for (unsigned i = used + tid; i < padded; i += 256) trailer[i] = 0;
+        }
+        if (!any)  // nothing of this row is delivered in this call: its history stands still
+            for (int i = tid; i < H; i += 256) carry_out[(long long)r * H + i] = carry_in[(long long)r * H + i];
+    }
+    unsigned char *out = dst + (unsigned long long)r * dst_pitch;
+    const long long at = (long long)j * m + o0;  // the tile's first sample of the block row
+    const bool vec_out = m % SPL == 0 && c.tile % SPL == 0;  // (then o0, tn and `at` are multiples of SPL; block rows are 16-byte aligned)
+    if (!present) {
+        if (vec_out) {
+            for (int q = tid * SPL; q < tn; q += 256 * SPL) {
+                if (!S16) *reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(out) + at + q) = make_float4(0.f, 0.f, 0.f, 0.f);
+                else *reinterpret_cast<uint4 *>(reinterpret_cast<short2 *>(out) + at + q) = make_uint4(0u, 0u, 0u, 0u);
+            }
+        } else {
+            for (int q = tid; q < tn; q += 256) {
+                if (!S16) reinterpret_cast<float2 *>(out)[at + q] = make_float2(0.f, 0.f);
+                else reinterpret_cast<short2 *>(out)[at + q] = make_short2(0, 0);
+            }
+        }
+        return;
+    }
+    float *h = reinterpret_cast<float *>(B + c.lds_b);
+    for (int i = tid; i < c.n_stages * kMaxTaps; i += 256) h[i] = taps[i];
+    // the span: position p = o0 D - H + i of super-frame j, i in [0, tn D + H); p < 0 reaches into the look-back
+    const int n0 = tn * D + H, p0 = o0 * D - H;
+    const float2 *cur = src + (long long)j * spf;
+    const float2 *back = jprev >= 0 ? src + (long long)(jprev + 1) * spf : carry_in + (long long)r * H + H;  // back[p], p in [-H, 0)
+    // pairs of samples by one 16-byte load: the row, the super-frame, the span's start and the look-back are all even then
+    const bool vec_in = (reinterpret_cast<unsigned long long>(src) & 15ull) == 0 && ((spf | p0 | H | n0) & 1) == 0;
+    if (vec_in) {
+        for (int i = tid * 2; i < n0; i += 512) {
+            const int p = p0 + i;
+            *reinterpret_cast<float4 *>(A + i) = *reinterpret_cast<const float4 *>((p >= 0 ? cur : back) + p);
+        }
+    } else {
+        for (int i = tid; i < n0; i += 256) {
+            const int p = p0 + i;
+            A[i] = (p >= 0 ? cur : back)[p];
+        }
+    }
+    __syncthreads();
+    if (!later && o0 + tn == m)  // the row's last delivered samples: the next launch's look-back where it has no present pair in front
+        for (int i = tid; i < H; i += 256) carry_out[(long long)r * H + i] = A[n0 - H + i];
+    float2 *in = A, *res = B;
+    int n = n0;
+    for (int s = 0; s < c.n_stages; s++) {
+        const int T = c.taps[s], st = c.stride[s];
+        const int n_out = s == c.n_stages - 1 ? tn : (n - T) / st + 1;
+        const float *hs = h + s * kMaxTaps;
+        for (int q = tid; q < n_out; q += 256) {
+            const float2 *x = in + q * st;
+            float2 acc = make_float2(0.f, 0.f);
+            for (int p = 0; p < T; p++) {
+                const float2 v = x[p];
+                acc.x = fmaf(v.x, hs[p], acc.x);
+                acc.y = fmaf(v.y, hs[p], acc.y);
+            }
+            res[q] = acc;
+        }
+        __syncthreads();
+        float2 *t = in; in = res; res = t;
+        n = n_out;
+    }
+    if (vec_out) {
+        for (int q = tid * SPL; q < tn; q += 256 * SPL) {
+            const float4 a = *reinterpret_cast<const float4 *>(in + q);
+            if (!S16) {
+                *reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(out) + at + q) = a;
+            } else {
+                const float4 b = *reinterpret_cast<const float4 *>(in + q + 2);
+                const short2 q0 = make_short2(iq_record_s16(a.x), iq_record_s16(a.y)), q1 = make_short2(iq_record_s16(a.z), iq_record_s16(a.w));
+                const short2 q2 = make_short2(iq_record_s16(b.x), iq_record_s16(b.y)), q3 = make_short2(iq_record_s16(b.z), iq_record_s16(b.w));
+                uint4 w;
+                memcpy(&w.x, &q0, 4); memcpy(&w.y, &q1, 4); memcpy(&w.z, &q2, 4); memcpy(&w.w, &q3, 4);
+                *reinterpret_cast<uint4 *>(reinterpret_cast<short2 *>(out) + at + q) = w;
+            }
+        }
+    } else {
+        for (int q = tid; q < tn; q += 256) {
+            const float2 v = in[q];
+            if (!S16) reinterpret_cast<float2 *>(out)[at + q] = v;
+            else reinterpret_cast<short2 *>(out)[at + q] = make_short2(iq_record_s16(v.x), iq_record_s16(v.y));
+        }
+    }
+}
+
 static unsigned pack_blocks(long long n)
 {
     long long b = (n + 1023) / 1024;
@@ -275,6 +409,83 @@ int run_modem_pack(hipStream_t s, const float2 *iq, long long pitch, long long s
     unsigned char *o = (unsigned char *)dst;
     if (format == PEBBLEGPU_AUDIO_F32) launch(k_modem_pack<false>, grid, dim3(256), s, iq, pitch, (int)spf, n_sf, d_tab, gate, gate_stride, o, (unsigned long long)dst_pitch);
     else launch(k_modem_pack<true>, grid, dim3(256), s, iq, pitch, (int)spf, n_sf, d_tab, gate, gate_stride, o, (unsigned long long)dst_pitch);
+    PG_HIP(hipGetLastError());
+    return 0;
+}
+
+// the chain for (demod_rate, max_bw, min_rate) and what the ring at a modem rate refuses; spf: demodulator samples per super-frame
+int modem_rate_plan(uint32_t demod_rate, uint64_t spf, uint32_t max_bw, uint32_t min_rate, ModemRatePlan *out)
+{
+    if (max_bw == 0) return fail(PEBBLEGPU_E_INVALID, "a modem bandwidth of 0 Hz");
+    if (demod_rate == 0) return fail(PEBBLEGPU_E_INVALID, "a demodulator rate of 0");
+    ModemRatePlan p;
+    p.chain = design::build_chain(demod_rate, max_bw, min_rate);  // min_rate 0: minDecimatedSampleRate (15000), as buildDecimationChain
+    p.rate_int = (uint32_t)(int)p.chain.rate;
+    if (p.chain.stages.size() > (size_t)kMaxStages) return fail(PEBBLEGPU_E_UNSUPPORTED, "a modem chain of %zu stages; at most %d are built", p.chain.stages.size(), kMaxStages);
+    for (const design::Stage &st : p.chain.stages) {
+        if (st.ntaps == 0)
+            return fail(PEBBLEGPU_E_UNSUPPORTED, "the chain for (%u Hz, %u Hz) at %u samples/s contains a CIC3 stage (by %u): the merged CIC3's two-sample form is not built here",
+                        max_bw, min_rate, demod_rate, st.stride);
+        if (st.ntaps < 1 || st.ntaps > kMaxTaps) return fail(PEBBLEGPU_E_UNSUPPORTED, "a modem stage of %d taps", st.ntaps);
+    }
+    const uint64_t D = p.chain.total;
+    if (spf % D != 0) return fail(PEBBLEGPU_E_SIZE, "a super-frame of %llu demodulator samples is no multiple of the modem chain's decimation by %llu",
+                                  (unsigned long long)spf, (unsigned long long)D);
+    uint64_t len = spf, scale = 1, H = 0;
+    for (const design::Stage &st : p.chain.stages) {
+        if (len < (uint64_t)st.ntaps)  // Decimator::process's fallback for short frames (decimator.cpp:602-625) would drop samples unfiltered
+            return fail(PEBBLEGPU_E_SIZE, "a super-frame of %llu demodulator samples gives the modem chain's %d-tap stage %llu inputs", (unsigned long long)spf,
+                        st.ntaps, (unsigned long long)len);
+        H += (uint64_t)(st.ntaps - 1) * scale;
+        scale *= st.stride;
+        len /= st.stride;
+    }
+    if (H > spf) return fail(PEBBLEGPU_E_SIZE, "the modem chain looks back %llu demodulator samples, more than one super-frame of %llu", (unsigned long long)H,
+                             (unsigned long long)spf);
+    p.lookback = (uint32_t)H;
+    p.out_spf = spf / D;
+    if (!p.chain.stages.empty()) {
+        // the workgroup's tile: up to 256 outputs, fewer while the span tile * D + H would not fit 4096 samples of LDS
+        uint64_t tile = 256;
+        while (tile > 4 && tile / 2 >= p.out_spf) tile /= 2;
+        while (tile > 4 && tile * D + H > 4096) tile /= 2;
+        const uint64_t a = (tile * D + H + 1) & ~(uint64_t)1;
+        if (a > 4096) return fail(PEBBLEGPU_E_UNSUPPORTED, "a modem chain that decimates by %llu with a look-back of %llu samples exceeds the packing kernel's LDS tile",
+                                  (unsigned long long)D, (unsigned long long)H);
+        p.tile = (uint32_t)tile;
+        p.lds_a = (uint32_t)a;
+        p.lds_b = (uint32_t)(((a - p.chain.stages[0].ntaps) / p.chain.stages[0].stride + 2) & ~(uint64_t)1);
+    }
+    *out = p;
+    return 0;
+}
+
+int run_modem_rate_pack(hipStream_t s, const float2 *iq, long long pitch, long long spf, int n_sf, const uint32_t *d_tab, uint32_t rows, int format,
+                        const unsigned char *gate, int gate_stride, void *dst, uint64_t dst_pitch, const ModemRatePlan &plan, const float *d_taps,
+                        float2 *d_carry, int parity)
+{
+    if (spf <= 0 || n_sf <= 0 || rows == 0) return 0;
+    if ((uint64_t)spf != plan.out_spf * plan.chain.total || plan.tile == 0) return fail(PEBBLEGPU_E_SIZE, "a super-frame of %lld samples is not what the modem ring was opened for", spf);
+    if (spf * n_sf >= (1LL << 31)) return fail(PEBBLEGPU_E_SIZE, "a modem block of %lld samples per row", spf * n_sf);
+    ModemRateChain c;
+    memset(&c, 0, sizeof(c));
+    c.n_stages = (int)plan.chain.stages.size();
+    c.D = (int)plan.chain.total;
+    c.H = (int)plan.lookback;
+    c.tile = (int)plan.tile;
+    c.lds_a = (int)plan.lds_a;
+    c.lds_b = (int)plan.lds_b;
+    for (int j = 0; j < c.n_stages; j++) { c.taps[j] = plan.chain.stages[j].ntaps; c.stride[j] = (int)plan.chain.stages[j].stride; }
+    const size_t lds = sizeof(float2) * ((size_t)plan.lds_a + plan.lds_b) + sizeof(float) * (size_t)c.n_stages * kMaxTaps;
+    const dim3 grid((unsigned)((plan.out_spf + plan.tile - 1) / plan.tile), rows, (unsigned)n_sf);
+    const size_t half = (size_t)rows * plan.lookback;
+    const float2 *cin = d_carry + (parity ? half : 0);
+    float2 *cout = d_carry + (parity ? 0 : half);
+    unsigned char *o = (unsigned char *)dst;
+    if (format == PEBBLEGPU_AUDIO_F32)
+        launch_lds(k_modem_rate_pack<false>, grid, dim3(256), lds, s, iq, pitch, (int)spf, n_sf, d_tab, gate, gate_stride, o, (unsigned long long)dst_pitch, c, d_taps, cin, cout);
+    else
+        launch_lds(k_modem_rate_pack<true>, grid, dim3(256), lds, s, iq, pitch, (int)spf, n_sf, d_tab, gate, gate_stride, o, (unsigned long long)dst_pitch, c, d_taps, cin, cout);
     PG_HIP(hipGetLastError());
     return 0;
 }
@@ -536,6 +747,21 @@ int Receiver::audio_out_dropped(uint64_t *blocks)
 // ---- the modem hook ring: what m_iDigitalModem->processBlock receives (receiver.cpp:979-980), for a host's own decoders ----
 int Receiver::modem_out_open(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots)
 {
+    return modem_out_open_plan(format, channels, n_channels, n_slots, nullptr);
+}
+
+// the ring at a modem rate: the plan's refusals first (each leaves the handle as it was), then the plain ring's; an empty chain
+// (min_rate at or above the demodulator rate, or no design fits: decimator.cpp:155-160 copies) IS the plain ring
+int Receiver::modem_out_open_rate(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots, uint32_t max_bw, uint32_t min_rate)
+{
+    if (wfm) return fail(PEBBLEGPU_E_UNSUPPORTED, "the digital-modem hook is on the narrow branch (receiver.cpp:977-980): a WFM receiver has none");
+    ModemRatePlan plan;
+    if (int rc = modem_rate_plan(demod_rate_int, superframe / chain.total, max_bw, min_rate, &plan)) return rc;
+    return modem_out_open_plan(format, channels, n_channels, n_slots, plan.chain.stages.empty() ? nullptr : &plan);
+}
+
+int Receiver::modem_out_open_plan(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots, const ModemRatePlan *plan)
+{
     if (wfm) return fail(PEBBLEGPU_E_UNSUPPORTED, "the digital-modem hook is on the narrow branch (receiver.cpp:977-980): a WFM receiver has none");
     if (format != PEBBLEGPU_AUDIO_F32 && format != PEBBLEGPU_AUDIO_S16)
         return fail(PEBBLEGPU_E_INVALID, "modem blocks are PEBBLEGPU_AUDIO_F32 or PEBBLEGPU_AUDIO_S16 (I, Q pairs), not format %d", format);
@@ -556,14 +782,25 @@ int Receiver::modem_out_open(int format, const uint32_t *channels, uint32_t n_ch
     std::lock_guard<std::mutex> g(mu_);
     if (mout_.open) return fail(PEBBLEGPU_E_INVALID, "the modem ring is already open");
     PG_HIP(hipSetDevice(device));
-    const uint64_t max_n = (uint64_t)max_sf * (superframe / chain.total);
+    const uint64_t max_n = (uint64_t)max_sf * (plan ? plan->out_spf : superframe / chain.total);
     if (!d_mout_tab_) PG_TRY(d_mout_tab_.alloc(C));
+    if (plan) {  // the stages' taps as k_morse_fir takes them, and both halves of the carry at zero: a fresh Decimator's histories
+        std::vector<float> h((size_t)kMaxTaps * plan->chain.stages.size(), 0.f);
+        for (size_t j = 0; j < plan->chain.stages.size(); j++)
+            for (int p = 0; p < plan->chain.stages[j].ntaps; p++) h[j * kMaxTaps + p] = (float)design::halfband_taps(plan->chain.stages[j].design)[p];
+        PG_TRY(d_mrate_taps_.upload(h.data(), h.size()));
+        PG_TRY(d_mrate_carry_.alloc_zero((size_t)2 * sel.size() * std::max<uint32_t>(plan->lookback, 1u)));
+        PG_HIP(hipDeviceSynchronize());  // (the fill is over before a call's stream reads it)
+    }
     std::lock_guard<std::mutex> lk(mout_.mu);
     const uint32_t bps = kAudioBytes[format];
     if (int rc = mout_.open_ring(n_slots, (uint32_t)sel.size(), bps, max_n, (uint32_t)format, modem_layout(bps, (uint32_t)sel.size(), 0, max_sf).trailer_bytes)) {
         mout_.release();
         return rc;
     }
+    mrate_on_ = plan != nullptr;
+    if (plan) mrate_ = *plan;
+    mrate_parity_ = 0;
     mout_sel_ = sel;
     mout_tab_dirty_ = true;
     return 0;
@@ -575,6 +812,7 @@ int Receiver::modem_out_close()
     if (!mout_.open) return fail(PEBBLEGPU_E_INVALID, "the modem ring is not open");
     if (int rc = sync()) return rc;
     mout_.close_ring();
+    mrate_on_ = false;  // (the next open starts a fresh decimator: both halves of the carry at zero)
     return 0;
 }
 
@@ -599,6 +837,14 @@ int Receiver::queue_modem_block(hipStream_t s, long long spf, int n_sf, const un
     if (!g) return 0;
     g->aux = (uint32_t)n_sf;
     if (n_sf <= 0 || spf <= 0) return mout_.commit(g, s, 0);
+    if (mrate_on_) {  // at a modem rate: one launch through the whole chain; the carry's parity flips with every launch and with nothing else
+        const uint64_t m = mrate_.out_spf * (uint64_t)n_sf;
+        const ModemLayout l = modem_layout(mout_.bytes_per_sample, mout_.rows, m, (uint32_t)n_sf);
+        if (int rc = run_modem_rate_pack(s, audio.data(), audio.pitch, spf, n_sf, d_mout_tab_, mout_.rows, (int)mout_.format, gate, (int)max_sf, g->d, l.pitch, mrate_,
+                                         d_mrate_taps_, d_mrate_carry_, mrate_parity_)) return rc;
+        mrate_parity_ ^= 1;
+        return mout_.commit(g, s, m, l.trailer_bytes);
+    }
     const ModemLayout l = modem_layout(mout_.bytes_per_sample, mout_.rows, (uint64_t)spf * n_sf, (uint32_t)n_sf);
     if (int rc = run_modem_pack(s, audio.data(), audio.pitch, spf, n_sf, d_mout_tab_, mout_.rows, (int)mout_.format, gate, (int)max_sf, g->d, l.pitch)) return rc;
     return mout_.commit(g, s, (uint64_t)spf * n_sf, l.trailer_bytes);
@@ -616,7 +862,7 @@ int Receiver::modem_out_next(int wait, pebblegpu_modem_block *b)
     b->pitch_bytes = e.host ? e.pitch_bytes : 0;
     b->n_channels = e.rows;
     b->dropped_before = e.host ? e.dropped_before : 0;
-    b->rate = demod_rate_int;
+    b->rate = mrate_on_ ? mrate_.rate_int : demod_rate_int;
     b->n_superframes = n_sf;
     b->samples_per_superframe = n_sf ? e.samples / n_sf : 0;
     b->present = n_sf ? (const uint8_t *)e.host + (uint64_t)e.rows * e.pitch_bytes : nullptr;

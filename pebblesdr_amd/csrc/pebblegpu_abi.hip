@@ -542,6 +542,32 @@ int pebblegpu_receiver_modem_out_open(pebblegpu_receiver *h, int format, const u
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
     return h->rx.modem_out_open(format, channels, n_channels, n_slots);
 }
+int pebblegpu_receiver_modem_out_open_rate(pebblegpu_receiver *h, int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots, uint32_t max_bw,
+                                           uint32_t min_rate)
+{
+    if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");
+    return h->rx.modem_out_open_rate(format, channels, n_channels, n_slots, max_bw, min_rate);
+}
+int pebblegpu_modem_rate_plan(uint32_t demod_rate, uint64_t samples_per_superframe, uint32_t max_bw, uint32_t min_rate, pebblegpu_modem_rate_info *out)
+{
+    if (!out) return fail(PEBBLEGPU_E_INVALID, "null pebblegpu_modem_rate_info");
+    if (out->struct_size != sizeof(pebblegpu_modem_rate_info)) return fail(PEBBLEGPU_E_INVALID, "pebblegpu_modem_rate_info size mismatch (ABI %d)", PEBBLEGPU_ABI_VERSION);
+    pg::ModemRatePlan p;
+    if (int rc = pg::modem_rate_plan(demod_rate, samples_per_superframe, max_bw, min_rate, &p)) return rc;
+    memset(out, 0, sizeof(*out));
+    out->struct_size = sizeof(*out);
+    out->rate = p.chain.rate;
+    out->rate_int = p.rate_int;
+    out->total_decimation = p.chain.total;
+    out->n_stages = (uint32_t)p.chain.stages.size();
+    out->lookback = p.lookback;
+    out->samples_per_superframe = p.out_spf;
+    for (size_t j = 0; j < p.chain.stages.size(); j++) {
+        out->taps[j] = (uint32_t)p.chain.stages[j].ntaps;
+        out->stride[j] = p.chain.stages[j].stride;
+    }
+    return 0;
+}
 int pebblegpu_receiver_modem_out_close(pebblegpu_receiver *h)
 {
     if (!h) return fail(PEBBLEGPU_E_INVALID, "null handle");

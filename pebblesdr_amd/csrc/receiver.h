@@ -747,6 +747,8 @@ public:
     // the modem hook ring: the rows m_iDigitalModem->processBlock receives (receiver.cpp:979-980) for a selection of channels, with a
     // trailer that says which (row, super-frame) the reference would have handed to the hook at all
     int modem_out_open(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots);
+    // the same ring with every row through the reference's Decimator chain for (max_bw, min_rate) on the device (k_modem_rate_pack)
+    int modem_out_open_rate(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots, uint32_t max_bw, uint32_t min_rate);
     int modem_out_close();
     int modem_out_next(int wait, pebblegpu_modem_block *b);
     int modem_out_release(uint64_t call_index);
@@ -943,6 +945,12 @@ private:
     DevBuf<uint32_t> d_mout_tab_;     // [C] the selected rows: channel | kModemRowTuneOnly
     bool mout_tab_dirty_ = false;
     int upload_modem_table();
+    int modem_out_open_plan(int format, const uint32_t *channels, uint32_t n_channels, uint32_t n_slots, const ModemRatePlan *plan);
+    bool mrate_on_ = false;           // the open ring decimates (set under mout_.mu at open; a plain ring, or an empty chain: false)
+    ModemRatePlan mrate_;
+    DevBuf<float> d_mrate_taps_;      // [stage][kMaxTaps]
+    DevBuf<float2> d_mrate_carry_;    // [2][rows][H]: the last H delivered demodulator samples of every row, read at mrate_parity_
+    int mrate_parity_ = 0;
     int queue_modem_block(hipStream_t s, long long spf, int n_sf, const unsigned char *gate);
     struct DisplayRing *disp_ = nullptr;  // allocated at the first open, kept until the receiver goes (a reader may hold it)
     bool disp_open_ = false;          // (under mu_: what a process call looks at)
