@@ -1,5 +1,6 @@
 // egress.hip -- the egress ring (egress.h), its two packing kernels and the receiver's audio output stage and IQ recording.
 #include "receiver.h"
+#include "modem_rate_geom.h"
 
 namespace pg {
 
@@ -445,16 +446,13 @@ int modem_rate_plan(uint32_t demod_rate, uint64_t spf, uint32_t max_bw, uint32_t
     p.lookback = (uint32_t)H;
     p.out_spf = spf / D;
     if (!p.chain.stages.empty()) {
-        // the workgroup's tile: up to 256 outputs, fewer while the span tile * D + H would not fit 4096 samples of LDS
-        uint64_t tile = 256;
-        while (tile > 4 && tile / 2 >= p.out_spf) tile /= 2;
-        while (tile > 4 && tile * D + H > 4096) tile /= 2;
-        const uint64_t a = (tile * D + H + 1) & ~(uint64_t)1;
-        if (a > 4096) return fail(PEBBLEGPU_E_UNSUPPORTED, "a modem chain that decimates by %llu with a look-back of %llu samples exceeds the packing kernel's LDS tile",
-                                  (unsigned long long)D, (unsigned long long)H);
-        p.tile = (uint32_t)tile;
-        p.lds_a = (uint32_t)a;
-        p.lds_b = (uint32_t)(((a - p.chain.stages[0].ntaps) / p.chain.stages[0].stride + 2) & ~(uint64_t)1);
+        ModemRateGeom g;  // the workgroup's tile and its two LDS buffers: modem_rate_geom.h
+        if (!modem_rate_geometry(D, H, p.out_spf, p.chain.stages[0].ntaps, p.chain.stages[0].stride, &g))
+            return fail(PEBBLEGPU_E_UNSUPPORTED, "a modem chain that decimates by %llu with a look-back of %llu samples exceeds the packing kernel's LDS tile",
+                        (unsigned long long)D, (unsigned long long)H);
+        p.tile = g.tile;
+        p.lds_a = g.lds_a;
+        p.lds_b = g.lds_b;
     }
     *out = p;
     return 0;

@@ -7,7 +7,12 @@ samples, at most 6 channels -- but a 5-of-6 and a 70-of-70 selection for the tra
 The definition (include/pebblegpu.h): the stream of one selected channel is what ONE oracle.Decimator(demodulator rate, max_bw, min_rate)
 -- pinned to the reference's class -- produces when it is fed, in order, exactly the (channel, super-frame) pairs the ring delivers as
 present.  The input it is fed here are the present pairs of a TWIN bank's plain F32 ring rows: existing code, identical input, bit for bit
-the hook's rows.  The oracle is fed one pair (2048 samples) at a time: a longer frame overruns what it allocates.
+the hook's rows.  The oracle is fed one pair -- one whole super-frame -- at a time, whatever its length: its buffers grow with the
+frame (po_grow, oracle/pebble_oracle.c), and tests/test_modem_geom_host.py holds a super-frame of 5376 samples in one call to the same
+samples in pieces, exactly.  (An earlier version of this text said that a frame over 2048 overruns the oracle's allocation: it does not.)
+
+Other geometries -- ragged and halved tiles, D up to 128, four stages, spans that are mostly look-back, the sample-by-sample store --
+are the table of tests/modem_geom_cases.py, which reuses hold_row and the wrong models below on super-frames of other lengths.
 
 Bar per present pair: modem_out_cases.PAIR_BAR, the project's 1e-5 relative RMS; not taken from the code under test.  S16 rows against
 the host twin of a twin's F32 rows, the empty chain against the plain ring, and the same stream cut into other calls: exact.
@@ -48,7 +53,6 @@ def decimated(O, rate, bw, mn, pairs):
     dec = O.Decimator(rate, bw, mn)
     out = []
     for y in pairs:
-        assert len(y) <= 2048
         out.append(dec.process(np.asarray(y, dtype=np.complex128)))
     return out
 
