@@ -15,22 +15,70 @@
 //
 // LDS image: element i lives at lpad(i) = i + 4*(i>>5) (float2 units).  The 4-slot pad per 32
 // elements makes the stride-4 / stride-32 scatter of the early passes land on distinct banks
-// for ds_write_b64 (16-lane groups, 32 dword banks) while unit-stride gathers stay conflict-free.
+// for ds_write_b64 (16-lane groups, 32 dword banks) while unit-stride gathers stay conflict-free: as the pair reads the
+// compiler makes of plain loads (ds_read2_b64: the stores' rule) and as single ds_read_b64 (lds_gather_b64 below: two groups of 32
+// lanes over 64 banks), because 32 consecutive elements starting at a multiple of 32 lie in one unpadded run.  The other two
+// paddings break such a run (lpad4 after 16 elements): under the single-read rule its last slot wraps, a two-way conflict per group.
 #pragma once
 #include "common.h"
 
 namespace pg {
 
-__device__ __forceinline__ int lpad(int i) { return i + ((i >> 5) << 2); }
+__host__ __device__ constexpr int lpad(int i) { return i + ((i >> 5) << 2); }
 // The exchange after a leading radix-4 pass uses its own padding, one slot per 16: a work-item scatters 4 adjacent
 // elements there (lane stride 32 B), which the 4-per-32 pad leaves on half of the banks.
-__device__ __forceinline__ int lpad4(int i) { return i + (i >> 4); }
+__host__ __device__ constexpr int lpad4(int i) { return i + (i >> 4); }
 // ... and after the wave transform's leading radix-32 pass (32 adjacent elements per lane, lane stride 256 B) one slot
 // per 32: lane stride 33 slots = 66 dwords, 16 lanes cover the 32 banks.
-__device__ __forceinline__ int lpad1(int i) { return i + (i >> 5); }
+__host__ __device__ constexpr int lpad1(int i) { return i + (i >> 5); }
 enum { kPad4per32 = 0, kPad1per16 = 1, kPad1per32 = 2 };
-template <int A> __device__ __forceinline__ int lpad_sel(int i) { return A == kPad1per16 ? lpad4(i) : A == kPad1per32 ? lpad1(i) : lpad(i); }
+template <int A> __host__ __device__ constexpr int lpad_sel(int i) { return A == kPad1per16 ? lpad4(i) : A == kPad1per32 ? lpad1(i) : lpad(i); }
 template <int N> struct FftLds { static constexpr int kSlots = N + (N >> 5) * 4; };
+
+// ---- gather of N (a multiple of 8) float2 off one LDS address, as N single ds_read_b64 with immediate offsets ----
+// x[m] = p[OFF::at(m)], OFF::at constexpr, offsets up to 65535 bytes.  Written as instructions because the compiler merges two
+// 8-byte reads off one base into ds_read2_b64 / ds_read2st64_b64 wherever their distance allows: a pair is served in 16-lane
+// groups over 32 banks -- half the bytes per LDS clock of the single read's two 32-lane groups over 64 banks
+// (tools/ubench/isa_rates.hip measures both).  The reads are tied to their consumers by operands and waited for here: the
+// compiler's counters do not see them.  An LDS wait of the compiler's own that follows stays correct (LDS returns in order, so
+// more outstanding requests than it counted make its wait stricter, never weaker).
+template <int S> struct LdsStride { static constexpr int at(int m) { return S * m; } };
+__device__ __forceinline__ unsigned lds_addr(const void *p)
+{
+    return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
+}
+template <class OFF, int I0> __device__ __forceinline__ void lds_read8_b64(v2f_t *r, unsigned a)
+{
+    asm volatile("ds_read_b64 %0, %8 offset:%9\n\tds_read_b64 %1, %8 offset:%10\n\tds_read_b64 %2, %8 offset:%11\n\tds_read_b64 %3, %8 offset:%12\n\t"
+                 "ds_read_b64 %4, %8 offset:%13\n\tds_read_b64 %5, %8 offset:%14\n\tds_read_b64 %6, %8 offset:%15\n\tds_read_b64 %7, %8 offset:%16"
+                 : "=&v"(r[I0]), "=&v"(r[I0 + 1]), "=&v"(r[I0 + 2]), "=&v"(r[I0 + 3]), "=&v"(r[I0 + 4]), "=&v"(r[I0 + 5]), "=&v"(r[I0 + 6]), "=&v"(r[I0 + 7])
+                 : "v"(a), "n"(8 * OFF::at(I0)), "n"(8 * OFF::at(I0 + 1)), "n"(8 * OFF::at(I0 + 2)), "n"(8 * OFF::at(I0 + 3)), "n"(8 * OFF::at(I0 + 4)),
+                   "n"(8 * OFF::at(I0 + 5)), "n"(8 * OFF::at(I0 + 6)), "n"(8 * OFF::at(I0 + 7))
+                 : "memory");
+}
+template <int I0, bool WAIT> __device__ __forceinline__ void lds_tie8(v2f_t *r)
+{
+    if (WAIT)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[I0]), "+v"(r[I0 + 1]), "+v"(r[I0 + 2]), "+v"(r[I0 + 3]), "+v"(r[I0 + 4]), "+v"(r[I0 + 5]), "+v"(r[I0 + 6]), "+v"(r[I0 + 7])::"memory");
+    else
+        asm volatile("" : "+v"(r[I0]), "+v"(r[I0 + 1]), "+v"(r[I0 + 2]), "+v"(r[I0 + 3]), "+v"(r[I0 + 4]), "+v"(r[I0 + 5]), "+v"(r[I0 + 6]), "+v"(r[I0 + 7]));
+}
+template <int N, class OFF> __device__ __forceinline__ void lds_gather_b64(float2 (&x)[N], const float2 *p)
+{
+    static_assert(N % 8 == 0 && N <= 32 && 8 * OFF::at(N - 1) + 8 <= 65536, "blocks of eight reads, 16-bit byte offsets");
+    const unsigned a = lds_addr(p);
+    v2f_t r[N];
+    lds_read8_b64<OFF, 0>(r, a);
+    if (N > 8) lds_read8_b64<OFF, (N > 8 ? 8 : 0)>(r, a);
+    if (N > 16) lds_read8_b64<OFF, (N > 16 ? 16 : 0)>(r, a);
+    if (N > 24) lds_read8_b64<OFF, (N > 24 ? 24 : 0)>(r, a);
+    lds_tie8<0, true>(r);  // the one wait; the other blocks only take the dependence (asm volatile keeps them behind it)
+    if (N > 8) lds_tie8<(N > 8 ? 8 : 0), false>(r);
+    if (N > 16) lds_tie8<(N > 16 ? 16 : 0), false>(r);
+    if (N > 24) lds_tie8<(N > 24 ? 24 : 0), false>(r);
+#pragma unroll
+    for (int m = 0; m < N; m++) x[m] = make_float2(r[m].x, r[m].y);
+}
 
 // the pass plan (shared by the kernels and the host code that fills the twiddle table)
 __host__ __device__ constexpr int fft_passes(int n) { return n == 8192 ? 5 : 4; }

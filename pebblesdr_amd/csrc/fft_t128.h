@@ -13,6 +13,10 @@ namespace pg {
 constexpr int kTw128B = 0, kTw128C = 48, kTw128Count = 48 + 512;
 
 __host__ __device__ constexpr int perm16(int k) { return 4 * (k & 3) + (k >> 2); }
+// the exchange image between passes A and B (see fft2048_t128): 16 rows of 128 elements, 130 slots apart; 2078 slots of the image's 2304
+constexpr int kT128Pitch = 130;
+__host__ __device__ constexpr int t128_slot_ab(int e) { return kT128Pitch * (e & 15) + (e >> 4); }
+static_assert(t128_slot_ab(2047) < FftLds<2048>::kSlots, "the transposed image fits the padded one");
 
 // 16-point forward DFT in registers as 4 x 4 (n = 4*na + nb): DFT4 over na, twiddle W16^{nb*ka}, DFT4 over nb.
 // X[ka + 4*kb] is left in u[4*ka + kb], i.e. X[k] = u[perm16(k)].
@@ -59,15 +63,29 @@ __device__ __forceinline__ void tw128_fill_cx(Tw128Regs &w)
 
 // HELD (REGS, not FULLC): the first HELD of pass C's seven products w8 * w_i come from wr.cx[9 ..] (formed once by the caller) -- as many
 // as the caller's register budget allows
-template <class Sync, bool DO_LDS = true, bool DO_MATH = true, bool REGS = false, bool FULLC = false, int HELD = 0>
+// PAIR_READS (tools/ubench/fft_core.hip only): the gathers as plain loads, which the compiler merges into ds_read2 pairs, on the
+// A-to-B layout that suits pairs -- the form the single reads of lds_gather_b64 replaced, kept to be measured against.
+template <class Sync, bool DO_LDS = true, bool DO_MATH = true, bool REGS = false, bool FULLC = false, int HELD = 0, bool PAIR_READS = false>
 __device__ __forceinline__ void fft2048_t128(float2 (&x)[16], float2 *lds, const float2 *__restrict__ tw, int t, Sync sync, Tw128Regs wr = Tw128Regs())
 {
     // ---- pass A: radix 16, the 16 strided elements of a work-item are one butterfly; output k -> element 16 t + k ----
     if (DO_MATH) dft16(x);
+    // The image between A and B is transposed: element e = 16 t + k at slot t128_slot_ab(e) = 130 k + t.  Scatter (16-lane groups over 32
+    // banks): consecutive work-items, consecutive slots.  Gather of pass B as single reads (32-lane groups over 64 banks): the 32 elements
+    // t + 128 m of a group are k = 0 .. 15 of two adjacent work-items -- dword 260 k + 2 (0 | 1) + const, and 260 = 4 mod 64: every bank
+    // once.  Both stay one base register and immediate offsets (130 k slots in the scatter, 8 m in the gather).  The layout it
+    // replaced (lpad4: one pad slot per 16) served the same scatter but wrapped the gather's last slot onto a busy bank, a two-way
+    // conflict per group -- no additive pad serves both (tests/test_lds_exchange_banks_host.py enumerates this one).
     if (DO_LDS) {
-        float2 *wp = lds + lpad4(16 * t);  // one pad slot per 16: work-item stride 17 slots, 16 of them cover all banks
+        if (PAIR_READS) {
+            float2 *wp = lds + lpad4(16 * t);  // one pad slot per 16: work-item stride 17 slots, 16 of them cover all banks
 #pragma unroll
-        for (int k = 0; k < 16; k++) wp[k] = x[perm16(k)];
+            for (int k = 0; k < 16; k++) wp[k] = x[perm16(k)];
+        } else {
+            float2 *wp = lds + t;
+#pragma unroll
+            for (int k = 0; k < 16; k++) wp[kT128Pitch * k] = x[perm16(k)];
+        }
     }
     sync();
     // ---- pass B: radix 8, P = 16, two butterflies ----
@@ -77,9 +95,13 @@ __device__ __forceinline__ void fft2048_t128(float2 (&x)[16], float2 *lds, const
         if (REGS) { w1 = wr.b1; w2 = wr.b2; w4 = wr.b4; }
         else { w1 = tw[kTw128B + k]; w2 = tw[kTw128B + 16 + k]; w4 = tw[kTw128B + 32 + k]; }
         if (DO_LDS) {
-            const float2 *rp = lds + lpad4(t);  // lpad4(t + 128 m) = lpad4(t) + 136 m
+            if (PAIR_READS) {
+                const float2 *rp = lds + lpad4(t);  // lpad4(t + 128 m) = lpad4(t) + 136 m
 #pragma unroll
-            for (int m = 0; m < 16; m++) x[m] = rp[136 * m];
+                for (int m = 0; m < 16; m++) x[m] = rp[136 * m];
+            } else {
+                lds_gather_b64<16, LdsStride<8>>(x, lds + t128_slot_ab(t));  // t128_slot_ab(t + 128 m) = t128_slot_ab(t) + 8 m
+            }
         }
         sync();  // every gather done before anyone scatters into the same image
         const float2 w3 = cmul_pk(w1, w2), w5 = cmul_pk(w4, w1), w6 = cmul_pk(w4, w2), w7 = cmul_pk(w4, w3);
@@ -113,8 +135,12 @@ __device__ __forceinline__ void fft2048_t128(float2 (&x)[16], float2 *lds, const
         else { w1 = tw[kTw128C + t]; w2 = tw[kTw128C + 128 + t]; w4 = tw[kTw128C + 256 + t]; w8 = tw[kTw128C + 384 + t]; }
         if (DO_LDS) {
             const float2 *rp = lds + lpad(t);  // lpad(t + 128 m) = lpad(t) + 144 m
+            if (PAIR_READS) {
 #pragma unroll
-            for (int m = 0; m < 16; m++) x[m] = rp[144 * m];
+                for (int m = 0; m < 16; m++) x[m] = rp[144 * m];
+            } else {
+                lds_gather_b64<16, LdsStride<144>>(x, rp);
+            }
         }
         sync();  // the image may be overwritten (the caller parks its results there)
         if (!DO_MATH) return;

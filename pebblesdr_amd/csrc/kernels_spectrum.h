@@ -210,6 +210,10 @@ __global__ __launch_bounds__(256, 2) void k_spectrum(const float2 *__restrict__ 
 struct DecLds {
     float2 z0[14 + 256], z1[22 + 128], z2[2][46 + 64], xt[2][10];  // (z2 twice: hb47 runs a frame behind hb23, which is writing the next one)
 };
+// where a work-item's sixteen samples of the parked frame lie from its first (lds_gather_b64): sample t + 128 m in region m / 4
+template <int REGION, int RSTEP> struct FrameGatherOff {
+    static constexpr int at(int m) { return (m / 4) * REGION + (m % 4) * RSTEP; }
+};
 
 // FULLC: pass C's fifteen twiddles per work-item formed once and held (126 registers: four such waves fill a SIMD's register file --
 // for calls whose first decimator stage does not run beside this kernel, Receiver::process).
@@ -346,12 +350,9 @@ static __global__ __launch_bounds__(512 * HALVES, 2 * HALVES) void k_spectrum_t1
         if (!DEC) fetch_next();
         float2 v[E];
         if (xform) {
-            const float2 *gp = &lds[0][fslot(t)];
+            lds_gather_b64<E, FrameGatherOff<REGION, RSTEP>>(v, &lds[0][fslot(t)]);  // sample t + 128 m: region m / 4, slot (m % 4) RSTEP on
 #pragma unroll
-            for (int m = 0; m < E; m++) {
-                const float2 xv = gp[(m / 4) * REGION + (m % 4) * RSTEP];
-                v[m] = m == 0 ? xv : cmul(bq[m], xv);  // (bq[0] = 1)
-            }
+            for (int m = 1; m < E; m++) v[m] = cmul(bq[m], v[m]);  // (bq[0] = 1)
         }
         const bool dec_run = DEC && live;          // (f == -1 included: the look-back frame)
         const bool dec_emit = dec_run && it >= 0;  // outputs of the chain's own frames leave the kernel

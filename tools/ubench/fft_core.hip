@@ -1,5 +1,6 @@
 // DEVELOPER-ONLY micro-benchmark: throughput of the two-wave 2048-point transform (fft_t128.h) with nothing around it --
-// the whole transform, its LDS exchanges alone and its butterflies alone, at 8 / 4 / 2 workgroups of 128 per CU.
+// the whole transform, its LDS exchanges alone and its butterflies alone, at 8 / 4 / 2 workgroups of 128 per CU, and the first two
+// once more with the gathers as ds_read2 pairs instead of single ds_read_b64.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Ipebblesdr_amd/csrc tools/ubench/fft_core.hip -o gpurun_out/fft_core
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -7,7 +8,7 @@
 #include "fft_t128.h"
 using namespace pg;
 
-template <bool DO_LDS, bool DO_MATH>
+template <bool DO_LDS, bool DO_MATH, bool PAIR_READS = false>
 __global__ __launch_bounds__(128, 4) void k_core(const float2 *__restrict__ in, float2 *__restrict__ out, const float2 *__restrict__ tw128, int reps)
 {
     __shared__ float2 lds[FftLds<2048>::kSlots];
@@ -23,7 +24,7 @@ __global__ __launch_bounds__(128, 4) void k_core(const float2 *__restrict__ in, 
         int tt = t;
         asm volatile("" : "+v"(tt));
         auto sync = [] { __syncthreads(); };
-        fft2048_t128<decltype(sync), DO_LDS, DO_MATH>(v, lds, tw_lds, tt, sync);
+        fft2048_t128<decltype(sync), DO_LDS, DO_MATH, false, false, 0, PAIR_READS>(v, lds, tw_lds, tt, sync);
 #pragma unroll
         for (int m = 0; m < 16; m++) v[m] = cscale(v[m], 1.0f / 64.0f);
     }
@@ -56,7 +57,7 @@ int main()
             if (ms < best) best = ms;
         }
         const double ffts = (double)WG * reps;
-        printf("%-28s %d WG/CU: %.3f ms for %.0f transforms -> %.2f ns each chip-wide, %.0f CU-clk per transform at 2.1 GHz\n", name, per_cu, best, ffts, best * 1e6 / ffts,
+        printf("%-32s %d WG/CU: %.3f ms for %.0f transforms -> %.2f ns each chip-wide, %.0f CU-clk per transform at 2.1 GHz\n", name, per_cu, best, ffts, best * 1e6 / ffts,
                best * 1e-3 * 2.1e9 / (ffts / 256));
     };
     for (size_t pad : {(size_t)0, (size_t)20000, (size_t)60000}) {
@@ -64,6 +65,9 @@ int main()
         run(k_core<true, true>, "whole transform", pad, per_cu);
         run(k_core<true, false>, "LDS exchanges only", pad, per_cu);
         run(k_core<false, true>, "butterflies only", pad, per_cu);
+        // the same gathers as the compiler pairs them (ds_read2_b64 / ds_read2st64_b64): what the single reads are measured against
+        run(k_core<true, true, true>, "whole transform, pair reads", pad, per_cu);
+        run(k_core<true, false, true>, "LDS exchanges only, pair reads", pad, per_cu);
     }
     return 0;
 }

@@ -69,6 +69,40 @@ BODY(k_ds_write_b32, "ds_write_b32 %18, %8\nds_write_b32 %18, %9 offset:512\nds_
 BODY(k_ds_read_b32, "ds_read_b32 %8, %18\nds_read_b32 %9, %18 offset:512\nds_read_b32 %10, %18 offset:1024\nds_read_b32 %11, %18 offset:1536\nds_read_b32 %12, %18 offset:2048\nds_read_b32 %13, %18 offset:2560\nds_read_b32 %14, %18 offset:3072\nds_read_b32 %15, %18 offset:3584\n")
 
 
+// ---- pair reads against single reads, lane l at l * STRIDE bytes (unit stride in the access width: no bank conflict under either
+// banking rule), 4 instructions per line; the time is in-kernel like BODY's ----
+static __device__ float lo(float v) { return v; }
+static __device__ float lo(float __attribute__((ext_vector_type(2))) v) { return v.x; }
+static __device__ float lo(float __attribute__((ext_vector_type(4))) v) { return v.x; }
+#define BODYP(name, VT, STRIDE, asm_line)                                                                 \
+    __global__ void name(long long *out, float seed)                                                     \
+    {                                                                                                     \
+        VT a0, a1, a2, a3;                                                                                \
+        a0 = seed; a1 = a0 + 1.f; a2 = a0 + 2.f; a3 = a0 + 3.f;                                           \
+        __shared__ float lds[8192];                                                                       \
+        int addr = threadIdx.x * STRIDE;                                                                  \
+        lds[threadIdx.x] = seed;                                                                          \
+        __syncthreads();                                                                                  \
+        long long t0 = clock64();                                                                         \
+        for (int it = 0; it < 1024; it++) {                                                               \
+            asm volatile(REP16(asm_line) : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(addr));           \
+        }                                                                                                 \
+        asm volatile("s_waitcnt lgkmcnt(0)");                                                            \
+        long long t1 = clock64();                                                                         \
+        if (threadIdx.x % 64 == 0) out[blockIdx.x * 16 + threadIdx.x / 64] = t1 - t0;                     \
+        if (lo(a0) + lo(a1) + lo(a2) + lo(a3) == 12345.f) out[1000] = 1;                                  \
+    }
+typedef float v2f __attribute__((ext_vector_type(2)));
+// 16 bytes per lane and instruction as a pair of 8-byte reads 512 B apart (offsets in 8-byte units / in units of 64 * 8 bytes) ...
+BODYP(k_ds_read2_b64, v4f, 8, "ds_read2_b64 %0, %4 offset1:64\nds_read2_b64 %1, %4 offset0:128 offset1:192\nds_read2_b64 %2, %4 offset0:1 offset1:65\nds_read2_b64 %3, %4 offset0:129 offset1:193\n")
+BODYP(k_ds_read2st64_b64, v4f, 8, "ds_read2st64_b64 %0, %4 offset1:1\nds_read2st64_b64 %1, %4 offset0:2 offset1:3\nds_read2st64_b64 %2, %4 offset0:4 offset1:5\nds_read2st64_b64 %3, %4 offset0:6 offset1:7\n")
+// ... the same eight addresses as single reads, two per pair above (half the bytes per instruction) ...
+BODYP(k_ds_read_b64_x4, v2f, 8, "ds_read_b64 %0, %4\nds_read_b64 %1, %4 offset:512\nds_read_b64 %2, %4 offset:1024\nds_read_b64 %3, %4 offset:1536\n")
+// ... and 8 bytes per lane and instruction as a pair of 4-byte reads (offsets in dwords / in units of 64 dwords)
+BODYP(k_ds_read2_b32, v2f, 4, "ds_read2_b32 %0, %4 offset1:64\nds_read2_b32 %1, %4 offset0:128 offset1:192\nds_read2_b32 %2, %4 offset0:1 offset1:65\nds_read2_b32 %3, %4 offset0:129 offset1:193\n")
+BODYP(k_ds_read2st64_b32, v2f, 4, "ds_read2st64_b32 %0, %4 offset1:1\nds_read2st64_b32 %1, %4 offset0:2 offset1:3\nds_read2st64_b32 %2, %4 offset0:4 offset1:5\nds_read2st64_b32 %3, %4 offset0:6 offset1:7\n")
+BODYP(k_ds_read_b32_x4, float, 4, "ds_read_b32 %0, %4\nds_read_b32 %1, %4 offset:256\nds_read_b32 %2, %4 offset:512\nds_read_b32 %3, %4 offset:768\n")
+
 // overlap tests: 8 instructions per line again (2 LDS + 6 VALU, or 4 + 4)
 BODY(k_mix_w_fma, "ds_write_b64 %18, %0\nv_pk_fma_f32 %1, %1, %16, %17\nv_pk_fma_f32 %2, %2, %16, %17\nv_pk_fma_f32 %3, %3, %16, %17\nds_write_b64 %18, %4 offset:512\nv_pk_fma_f32 %5, %5, %16, %17\nv_pk_fma_f32 %6, %6, %16, %17\nv_pk_fma_f32 %7, %7, %16, %17\n")
 BODY(k_mix_r_fma, "ds_read_b64 %0, %18\nv_pk_fma_f32 %1, %1, %16, %17\nv_pk_fma_f32 %2, %2, %16, %17\nv_pk_fma_f32 %3, %3, %16, %17\nds_read_b64 %4, %18 offset:512\nv_pk_fma_f32 %5, %5, %16, %17\nv_pk_fma_f32 %6, %6, %16, %17\nv_pk_fma_f32 %7, %7, %16, %17\n")
@@ -95,7 +129,7 @@ template <class K> static void run(const char *name, K kernel, int waves_per_sim
     hipEventElapsedTime(&ms, e0, e1);
     std::vector<long long> h(16);
     hipMemcpy(h.data(), d, 8 * 16, hipMemcpyDeviceToHost);
-    printf("%-14s %d wave/SIMD: in-kernel %.2f ticks/instr/wave; wall %.1f us -> %.2f SIMD-clk per instr at %.2f GHz (incl. launch)\n", name,
+    printf("%-16s %d wave/SIMD: in-kernel %.2f ticks/instr/wave; wall %.1f us -> %.2f SIMD-clk per instr at %.2f GHz (incl. launch)\n", name,
            waves_per_simd, h[0] / n, ms * 1e3, ms * 1e-3 * g_ghz * 1e9 / (n * waves_per_simd), g_ghz);
 }
 
@@ -128,6 +162,14 @@ int main()
         run("ds_write2_b64", k_ds_write2_b64, w, d);
         run("ds_write_b128", k_ds_write_b128, w, d, 1024.0 * 16 * 4);
         run("ds_read_b128", k_ds_read_b128, w, d, 1024.0 * 16 * 4);
+        // pairs against singles over the same addresses: a pair moves what two singles move, so "no slower" means at most twice
+        // the single read's figure
+        run("ds_read_b64 x4", k_ds_read_b64_x4, w, d, 1024.0 * 16 * 4);
+        run("ds_read2_b64", k_ds_read2_b64, w, d, 1024.0 * 16 * 4);
+        run("ds_read2st64_b64", k_ds_read2st64_b64, w, d, 1024.0 * 16 * 4);
+        run("ds_read_b32 x4", k_ds_read_b32_x4, w, d, 1024.0 * 16 * 4);
+        run("ds_read2_b32", k_ds_read2_b32, w, d, 1024.0 * 16 * 4);
+        run("ds_read2st64_b32", k_ds_read2st64_b32, w, d, 1024.0 * 16 * 4);
     }
     return 0;
 }
