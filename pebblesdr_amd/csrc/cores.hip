@@ -922,7 +922,7 @@ int DecimCore::run_rest(const Launch &l, const DecimRoute &r)
         auto kern = k_cascade<0, 0, 0>;
         if (r.cascade_inst == 1) kern = k_cascade<15, 23, 47>;
         else if (r.cascade_inst == 2) kern = k_cascade<15, 19, 31>;
-        launch_lds(kern, dim3(r.tiles, C), dim3(256), casc_lds_bytes, l.s, (const float2 *)src.data(), src.pitch, fin.data(), fin.pitch, len_out, casc);
+        launch_lds(kern, dim3(r.tiles, C), dim3(256), r.cascade_inst ? casc_fixed_lds_bytes : casc_lds_bytes, l.s, (const float2 *)src.data(), src.pitch, fin.data(), fin.pitch, len_out, casc);
     }
     return 0;
 }

@@ -50,6 +50,39 @@ inline bool bank_long_call(long long len_out, long long C)
     return (len_out + per - 1) / per >= 128;
 }
 
+// ---- the tile of the fixed-tap k_cascade instances (three halfbands at stride 2: <15,23,47>, <15,19,31>).  A halfband output j reads
+// the even offsets 2j, 2j + 2, .. 2j + T - 1 of its input and the one odd centre 2j + (T-1)/2 (T = 4k + 3, so the centre is odd); a
+// work-item makes the outputs 2u and 2u + 1 from one window, which starts at input 4u.  The tile therefore lies in LDS as FOUR planes:
+// plane r holds the inputs i = r (mod 4) at i >> 2, unit stride.  Then
+//   - the window's (T+3)/2 even inputs 4u + 2k are reads of plane 0 (k even) or 2 (k odd) at u + (k >> 1): consecutive lanes, consecutive
+//     8-byte slots, one plane per instruction;
+//   - the two centres 4u + (T-1)/2 and 4u + 2 + (T-1)/2 are one read of plane 3 and one of plane 1 (or 1 and 3), again at unit stride;
+//   - a stage's output 2u (2u + 1) is the next stage's input of plane 0 or 2 (1 or 3) by the parity of u, at u >> 1: a group of 16
+//     lanes stores 8 consecutive slots of each of the two planes, and so does the tile load (lane v holds inputs 2v, 2v + 1).
+// The LDS unit serves an 8-byte store 16 lanes at a time over 32 four-byte banks (a single 8-byte read 32 lanes over 64, a pair read
+// like a store: tests/test_lds_exchange_banks_host.py): a group of stores is conflict-free when its 16 slots differ mod 16.  Planes 0
+// and 2 (and 1 and 3) therefore start 8 slots apart mod 16: the plane pitch is = 8 (mod 16), the planes lie in the order 0, 2, 1, 3.
+// The unit-stride reads are conflict-free under either read rule wherever the planes start.  One slot per plane beyond
+// ceil(count / 4) is slack: with an odd count of final outputs the last work-item's unused second window reaches one input past the
+// tile (read, never stored).
+// Two such buffers: A holds the tile (c0 inputs) and later the second stage's outputs (c2), B the first stage's (c1).  At the tile of
+// 256 final outputs every chain of the ladder stays under kCascadeFixedLdsCap = 32 KiB: five workgroups per CU's 160 KiB, as the three
+// contiguous runs of the generic form gave (tests/test_cascade_tiles_host.py walks all of this).
+constexpr int kCascadeFixedLdsCap = 32 * 1024;
+constexpr int cascade_plane_pitch(int count) { return (((count + 3) / 4 + 1 + 7) / 16) * 16 + 8; }
+constexpr int cascade_plane_base(int r, int pitch) { return (((r & 1) << 1) | ((r >> 1) & 1)) * pitch; }
+constexpr int cascade_plane_slot(int i, int pitch) { return cascade_plane_base(i & 3, pitch) + (i >> 2); }
+struct CascadeFixedTile { int c0, c1, c2, pitch_a, pitch_b, lds_bytes; };
+constexpr CascadeFixedTile cascade_fixed_tile(int outb, int t0, int t1, int t2)
+{
+    const int c2 = 2 * outb + t2 - 1, c1 = 2 * c2 + t1 - 1, c0 = 2 * c1 + t0 - 1;
+    const int pa = cascade_plane_pitch(c0), pb = cascade_plane_pitch(c1);
+    return {c0, c1, c2, pa, pb, 4 * (pa + pb) * 8};
+}
+// the tile of final outputs o0 .. starts at this input (relative to the call's first; what lies before 0 is the head-room); a ragged last
+// tile of n < outb outputs reads cascade_fixed_tile(n, ..).c0 inputs from there, which ends where the call's data ends
+constexpr long long cascade_fixed_first(long long o0, int t0, int t1, int t2) { return ((o0 * 2 - (t2 - 1)) * 2 - (t1 - 1)) * 2 - (t0 - 1); }
+
 // ---------------------------------------------------------------- the shape: what init derives from the chain
 struct DecimStageDesc { int ntaps, stride; };  // ntaps 0: the reference's merged CIC3
 struct DecimTuningFacts {
@@ -79,6 +112,7 @@ struct DecimShape {
     bool three2 = false;             // three of them, each at stride 2: the form the fixed-tap kernels are built for
     int outb = 0, lds_half = 0;      // final outputs per k_cascade tile, float2 slots of its first ping-pong buffer
     size_t casc_lds_bytes = 0;
+    size_t casc_fixed_lds_bytes = 0; // three2: the four-plane tile of the fixed-tap instances (cascade_fixed_tile)
     long long halo0 = 0;             // look-back of the whole cascade in its input's samples (the first-stage buffer's head-room)
     // the whole decimator in one kernel (k_mix_dec_fused): a >= 16-channel bank off one shared stream whose chain is hb11 x S
     // followed by hb15, hb19, hb31; calls inside an oscillator transient take the two-kernel route (both keep each other's history)
@@ -152,6 +186,7 @@ inline DecimShape plan_decim_shape(const DecimStageDesc *st, int n_stages, unsig
     // three halfbands at stride 2 whose tap counts are in its list; k_mix_dec_fused<15, 19, 31>, its predecessor, for
     // hb11 x S, hb15, hb19, hb31 (PEBBLEGPU_BANK_DEC=0)
     s.three2 = s.nst == 3 && s.casc_stride[0] == 2 && s.casc_stride[1] == 2 && s.casc_stride[2] == 2;
+    if (s.three2) s.casc_fixed_lds_bytes = (size_t)cascade_fixed_tile(s.outb, s.casc_ntaps[0], s.casc_ntaps[1], s.casc_ntaps[2]).lds_bytes;
     const bool hb_front = s.bank_front && C >= 16 && !s.wide && s.first_stride <= 16;
     const bool cic_front = s.fused_front && C >= 16 && s.wide_stride == 16;
     const int *T = s.casc_ntaps;

@@ -221,15 +221,95 @@ static __global__ __launch_bounds__(256) void k_mix_dec1(const float2 *__restric
 // the whole cascade: halo0 = sum_s (T_s - 1) * prod_{r<s} S_r.
 // grid (ceil(n_out/outb), C); dynamic LDS = (count_0 + count_1) float2.
 // F0, F1, F2 > 0: a chain of exactly three stride-2 stages with these tap counts (the one-channel WFM chain hb15, hb23, hb47 runs
-// behind the display transform on an idle GPU, so its length is the call's): the tap loops unroll and the taps come straight out
-// of the kernel arguments as scalars -- the generic form reads every tap from LDS next to every sample, and its three stages took
-// 13 of the kernel's 24 us.  F0 = 0: any chain.
+// behind the display transform on an idle GPU, so its length is the call's): cascade_fixed below.  F0 = 0: any chain.
+//
+// The fixed-tap form.  The tap loops unroll and the taps come straight out of the kernel arguments as scalars (the generic form reads
+// every tap from LDS next to every sample; no tap table is staged here).  The tile and both intermediates lie in LDS as four planes by
+// input index mod 4 (decim_route.h, cascade_fixed_tile): a work-item makes the outputs 2u and 2u + 1 of a stage from ONE window of
+// (T+3)/2 even inputs and two centres, every read and write at unit stride across the lanes -- T + 7 reads per two outputs where a
+// window per output took T + 3, each of those a two-way bank conflict (lanes 16 bytes apart).  Each output still starts from its centre
+// product and adds the taps p = 0, 2, .. in one fmaf chain, so the results are the per-output form's bit for bit.
+// cascade_fixed_tile(nfin, ..) and cascade_fixed_first are the generic form's cnt[] arithmetic: a ragged last tile loads cnt0 inputs from
+// `first`, which ends where the call's data ends.  Dynamic LDS = cascade_fixed_tile(outb, ..).lds_bytes (DecimShape::casc_fixed_lds_bytes).
+template <int F0, int F1, int F2>
+__device__ __forceinline__ void cascade_fixed(const float2 *__restrict__ in, long long in_pitch, float2 *__restrict__ out, long long out_pitch,
+                                              long long n_out, const CascadeParams &cp, float2 *buf)
+{
+    const int c = blockIdx.y, t = threadIdx.x;
+    const long long o0 = (long long)blockIdx.x * cp.outb;
+    const int nfin = (int)((n_out - o0) < cp.outb ? (n_out - o0) : cp.outb);
+    const CascadeFixedTile g = cascade_fixed_tile(cp.outb, F0, F1, F2), part = cascade_fixed_tile(nfin, F0, F1, F2);
+    const int cnt2 = part.c2, cnt1 = part.c1, cnt0 = part.c0;
+    const long long first = cascade_fixed_first(o0, F0, F1, F2);
+    const int QA = g.pitch_a, QB = g.pitch_b;
+    float2 *A = buf, *B = buf + 4 * QA;
+    const float2 *x = in + (long long)c * in_pitch + first;
+    // all of this tile's loads in flight together: batches of kBatch 16-byte lanes (`first`, the row pitch and cnt0 are all even, so the
+    // tile is a whole number of aligned sample pairs); lane v's pair 2v, 2v + 1 goes to planes 0 and 1 (v even) or 2 and 3 at v >> 1
+    {
+        constexpr int kBatch = 5;
+        const float4 *x4 = reinterpret_cast<const float4 *>(x);
+        const int n4 = cnt0 >> 1;
+        for (int jb = t; jb < n4; jb += 256 * kBatch) {
+            float4 v[kBatch];
+#pragma unroll
+            for (int k = 0; k < kBatch; k++) {
+                const int j = jb + 256 * k;
+                v[k] = j < n4 ? x4[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int k = 0; k < kBatch; k++) {
+                const int j = jb + 256 * k;
+                if (j < n4) {
+                    A[cascade_plane_slot(2 * j, QA)] = make_float2(v[k].x, v[k].y);
+                    A[cascade_plane_slot(2 * j + 1, QA)] = make_float2(v[k].z, v[k].w);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    auto stage = [&](auto tc, const int s, const float2 *src, const int qs, float2 *dst, const int qd, const int ns, const bool last) {
+        constexpr int TT = decltype(tc)::value, CC = (TT - 1) >> 1, NE = (TT + 3) >> 1;
+        static_assert(TT % 4 == 3, "halfbands have 4k + 3 taps (odd centre)");
+        for (int u = t; 2 * u < ns; u += 256) {
+            // the window of outputs 2u, 2u + 1: inputs 4u + 2k, and the centres 4u + CC, 4u + 2 + CC
+            float2 e[NE], m[2];
+#pragma unroll
+            for (int k = 0; k < NE; k++) e[k] = src[cascade_plane_base((2 * k) & 3, qs) + u + (k >> 1)];
+#pragma unroll
+            for (int r = 0; r < 2; r++) m[r] = src[cascade_plane_base((CC + 2 * r) & 3, qs) + u + ((CC + 2 * r) >> 2)];
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                float2 acc = cscale(m[r], cp.h[s][CC]);
+#pragma unroll
+                for (int p = 0; p < TT; p += 2) {
+                    const float h = cp.h[s][p];
+                    acc.x = fmaf(e[r + (p >> 1)].x, h, acc.x);
+                    acc.y = fmaf(e[r + (p >> 1)].y, h, acc.y);
+                }
+                const int j = 2 * u + r;
+                if (j < ns) {
+                    if (last) out[(long long)c * out_pitch + o0 + j] = cscale(acc, cp.gain);
+                    else dst[cascade_plane_slot(j, qd)] = acc;
+                }
+            }
+        }
+        if (!last) __syncthreads();
+    };
+    stage(std::integral_constant<int, F0>{}, 0, A, QA, B, QB, cnt1, false);
+    stage(std::integral_constant<int, F1>{}, 1, B, QB, A, QA, cnt2, false);
+    stage(std::integral_constant<int, F2>{}, 2, A, QA, nullptr, 0, nfin, true);
+}
+
 template <int F0, int F1, int F2>
 static __global__ __launch_bounds__(256) void k_cascade(const float2 *__restrict__ in, long long in_pitch,
                                                          float2 *__restrict__ out, long long out_pitch, long long n_out,
                                                          CascadeParams cp)
 {
     HIP_DYNAMIC_SHARED(float2, buf)
+    if constexpr (F0 > 0) {
+        cascade_fixed<F0, F1, F2>(in, in_pitch, out, out_pitch, n_out, cp, buf);
+    } else {
     __shared__ float ht[kMaxCascade][64];  // taps out of the kernel-argument segment
     const int c = blockIdx.y, t = threadIdx.x;
     for (int i = t; i < kMaxCascade * 64; i += 256) {
@@ -280,28 +360,6 @@ static __global__ __launch_bounds__(256) void k_cascade(const float2 *__restrict
             const int S = cp.stride[s], T = cp.ntaps[s], ns = cnt[s + 1];
             const bool last = s == cp.nst - 1;
             const int cc = (T - 1) >> 1;  // halfband: even taps + the odd centre
-            if (F0 > 0 && s < 3) {
-                constexpr int TF[3] = {F0 > 0 ? F0 : 3, F1 > 0 ? F1 : 3, F2 > 0 ? F2 : 3};
-                auto fixed = [&](auto tc) {
-                    constexpr int TT = decltype(tc)::value, CC = (TT - 1) >> 1;
-                    for (int j = t; j < ns; j += 256) {
-                        const float2 *w = src + j * 2;
-                        float2 acc = cscale(w[CC], cp.h[s][CC]);
-#pragma unroll
-                        for (int p = 0; p < TT; p += 2) {
-                            const float h = cp.h[s][p];
-                            const float2 m = w[p];
-                            acc.x = fmaf(m.x, h, acc.x);
-                            acc.y = fmaf(m.y, h, acc.y);
-                        }
-                        if (last) out[(long long)c * out_pitch + o0 + j] = cscale(acc, cp.gain);
-                        else dst[j] = acc;
-                    }
-                };
-                if (s == 0) fixed(std::integral_constant<int, TF[0]>{});
-                else if (s == 1) fixed(std::integral_constant<int, TF[1]>{});
-                else fixed(std::integral_constant<int, TF[2]>{});
-            } else
             for (int j = t; j < ns; j += 256) {
                 const float2 *w = src + j * S;
                 float2 acc = cscale(w[cc], ht[s][cc]);
@@ -319,6 +377,7 @@ static __global__ __launch_bounds__(256) void k_cascade(const float2 *__restrict
             src = dst;
             dst = tmp;
         }
+    }
     }
 }
 
