@@ -20,9 +20,11 @@ DEFAULT_REFERENCE = "/root/reference"
 ENV = "PEBBLE_REFERENCE_DIR"
 
 PEBBLELIB = ["cpx", "mixer", "decimator", "downconvert", "fastfir", "fft", "fftaccelerate", "fftooura", "fftcute", "windowfunction", "fir",
-             "iir", "fractresampler", "delayline", "perform", "db", "goertzel", "firfilter", "movingavgfilter", "sampleclock"]
+             "iir", "fractresampler", "delayline", "perform", "db", "goertzel", "firfilter", "movingavgfilter", "sampleclock", "fldigifilters"]
 APPLICATION = ["processstep", "agc", "noiseblanker", "noisefilter", "dcremoval", "iqbalance", "signalstrength"]
 DEMOD = ["demod_am", "demod_sam", "demod_nfm", "demod_wfm", "rdsdecode"]  # rdsdecode only because Demod has a CRdsDecode member
+# the Morse modem and the Morse sender: the decoder and the keyer proper, without the plugin shells that bring the GUI
+PLUGINS = [("MorseDigitalModem", "morse"), ("MorseDigitalModem", "morsecode"), ("MorseGenDevice", "morsegen")]
 FLAGS = ["-std=c++14", "-O2", "-ffp-contract=off", "-DPEBBLELIB_LIBRARY", "-DUSE_FFTACCELERATE", "-w"]
 
 
@@ -69,10 +71,12 @@ def build_ref(force=False):
     # forward/ holds the stand-ins named like a directory of standins/ ("QtCore") and comes first, so that the name finds the file;
     # the third path lies one level below the directory that holds fftw-3.3.4/, as the reference's fftw.h looks it up
     inc = ["-I" + os.path.join(STANDINS, "forward"), "-I" + STANDINS, "-I" + os.path.join(STANDINS, "QtCore"), "-I" + os.path.join(ref, "pebblelib"),
-           "-I" + os.path.join(ref, "application"), "-I" + os.path.join(ref, "application", "demod")]
+           "-I" + os.path.join(ref, "application"), "-I" + os.path.join(ref, "application", "demod"),
+           "-I" + os.path.join(ref, "plugins", "MorseDigitalModem"), "-I" + os.path.join(ref, "plugins", "MorseGenDevice")]
     jobs = [(n, os.path.join(ref, "pebblelib", n + ".cpp"), os.path.join(obj_dir, n + ".o"), inc) for n in PEBBLELIB]
     jobs += [(n, os.path.join(ref, "application", n + ".cpp"), os.path.join(obj_dir, n + ".o"), inc) for n in APPLICATION]
     jobs += [(n, os.path.join(ref, "application", "demod", n + ".cpp"), os.path.join(obj_dir, n + ".o"), inc) for n in DEMOD]
+    jobs += [(n, os.path.join(ref, "plugins", d, n + ".cpp"), os.path.join(obj_dir, n + ".o"), inc) for d, n in PLUGINS]
     jobs += [("Accelerate", os.path.join(STANDINS, "Accelerate", "Accelerate.cpp"), os.path.join(obj_dir, "Accelerate.o"), inc),
              ("ref_driver", os.path.join(HERE, "ref_driver.cpp"), os.path.join(obj_dir, "ref_driver.o"), inc)]
     with ThreadPoolExecutor(max_workers=8) as pool:

@@ -47,6 +47,8 @@
 #include "demod_sam.h"
 #include "demod_nfm.h"
 #include "demod_wfm.h"
+#include "morse.h"
+#include "morsegen.h"
 #undef private
 #undef protected
 
@@ -378,6 +380,112 @@ static void st_movingavg()
     rec(out.data(), out.size());
 }
 
+/* ---- the Morse modem plugin (plugins/MorseDigitalModem/morse.cpp, compiled as it is).  Its signals are plain member calls here (emit
+ * is empty, nothing is connected), and their bodies, which moc would generate, are this driver's observation points ---- */
+static struct {
+    quint32 samples; /* modem samples since the last setSampleRate: one testbench(CPX) per sample, morse.cpp:887 */
+    std::vector<double> powers, tones, events, stars;
+} g_morse;
+
+void Morse::testbench(int, CPX *buf, double, int)
+{
+    g_morse.samples++;
+    /* Goertzel::processSample leaves its count at 0 exactly where it returned a result (goertzel.cpp:253) */
+    if (m_goertzel->m_mainTone.m_nCount == 0) {
+        g_morse.powers.push_back(m_goertzel->m_mainTone.m_power); /* not m_testBenchValue's, which is times 100 */
+        g_morse.tones.push_back(buf->imag() != 0 ? 1 : 0);
+    }
+}
+void Morse::testbench(int, double *, double, int) {}
+bool Morse::addProfile(QString, int) { return true; }
+void Morse::removeProfile(quint16) {}
+/* outputString has appended to m_output; the dot-dash buffer is still whole (resetDotDashBuf follows, morse.cpp:1081-1083).  The sample
+ * under way has not been counted yet (stateMachine runs before testbench).  One event: sample, token, kind (0 character, 1 word
+ * space); stars: the numbers of the events for which the plugin printed '*' (a token that is no character) */
+void Morse::newOutput()
+{
+    bool word = m_output.s.size() >= 1 && m_output.s.back() == ' ' && m_dotDashBufIndex == 0;
+    g_morse.events.push_back(double(g_morse.samples + 1));
+    g_morse.events.push_back(word ? 0.0 : double(m_morseCode.tokenizeDotDash(m_dotDashBuf)));
+    g_morse.events.push_back(word ? 1.0 : 0.0);
+    if (!m_output.s.empty() && m_output.s.back() == '*')
+        g_morse.stars.push_back(double(g_morse.events.size() / 3 - 1));
+}
+
+static void morse_status(Morse *m, std::vector<double> &out)
+{
+    double v[10] = {double(m->m_wpmSpeedCurrent), double(m->m_aboveWpmRange), double(m->m_belowWpmRange), double(m->m_modemSampleRate),
+                    double(m->m_goertzelSamplesPerResult), double(m->m_usecDotDashThreshold), double(m->m_usecElementThreshold),
+                    double(m->m_usecCharThreshold), double(m->m_usecWordThreshold), double(m->m_usecShortestMark)};
+    out.insert(out.end(), v, v + 10);
+}
+
+/* morse RATE FRAME WPM0 OUTMODE (AT ACT)...: Morse(), setSampleRate(RATE, FRAME), then processBlock frame by frame.  Before the frame
+ * that starts at input sample AT: ACT 0 = setSampleRate(RATE, FRAME) again, otherwise setDemodMode(ACT) (8 dmCWL, 9 dmCWU); several
+ * pairs may name one AT and run in their order.  ACT < 0 takes a status and does nothing else.  OUTMODE is written to m_outputMode behind every
+ * setSampleRate (init sets CHAR_ONLY).
+ * The constructor leaves m_wpmSpeedCurrent, the two range limits and the state unset and setSampleRate reads them (morse.cpp:240,
+ * :671-684, :588): the object is built over zeroed memory, m_wpmSpeedCurrent is WPM0 and the limits are the class's own defaults,
+ * which init assigns a few lines after reading them -- what every later setSampleRate finds there.
+ * Records: decisions, events (3 values each), stars, statuses (10 values: one before every ACT <= 0 and one at the end), powers */
+static void st_morse()
+{
+    int rate = int(arg(0)), n = int(arg(1));
+    void *mem = calloc(1, sizeof(Morse));
+    Morse *m = new (mem) Morse();
+    m->m_wpmSpeedCurrent = int(arg(2));
+    m->m_wpmLimitLow = m->c_wpmLowDefault;
+    m->m_wpmLimitHigh = m->c_wpmHighDefault;
+    m->setSampleRate(rate, n);
+    m->m_outputMode = Morse::OUTPUT_MODE(int(arg(3)));
+    g_morse.samples = 0;
+    std::vector<double> status;
+    for (size_t f = 0; f * n + n <= in_len(); f++) {
+        for (size_t i = 4; i + 1 < g_arg.size(); i += 2) {
+            if (size_t(g_arg[i]) != f * n)
+                continue;
+            int act = int(g_arg[i + 1]);
+            if (act <= 0)
+                morse_status(m, status);
+            if (act == 0) {
+                m->setSampleRate(rate, n);
+                m->m_outputMode = Morse::OUTPUT_MODE(int(arg(3)));
+                g_morse.samples = 0;
+            } else if (act > 0)
+                m->setDemodMode(DeviceInterface::DemodMode(act));
+        }
+        m->processBlock(in_cpx() + f * n);
+    }
+    morse_status(m, status);
+    rec(g_morse.tones.data(), g_morse.tones.size());
+    rec(g_morse.events.data(), g_morse.events.size());
+    rec(g_morse.stars.data(), g_morse.stars.size());
+    rec(status.data(), status.size());
+    rec(g_morse.powers.data(), g_morse.powers.size());
+    /* the plugin's destructor frees what memalign gave and deletes the rest; the process ends here instead */
+}
+
+/* morsegen RATE FREQ DB WPM RISE N CHAR...: MorseGen(RATE), setParams(FREQ, DB, WPM, RISE), setTextOut(the CHARs, byte values), then
+ * nextOutputSample N times.  Records: (rise, fall, dot, dot buffer, dash, dash buffer, element, character, word) sample counts, then
+ * the N samples */
+static void st_morsegen()
+{
+    MorseGen g(arg(0));
+    g.setParams(arg(1), arg(2), quint32(arg(3)), quint32(arg(4)));
+    QString text;
+    for (size_t i = 6; i < g_arg.size(); i++)
+        text.s.push_back(char(int(g_arg[i])));
+    g.setTextOut(text);
+    double c[9] = {double(g.m_numSamplesRise), double(g.m_numSamplesFall), double(g.m_numSamplesDot), double(g.m_numSamplesDotBuf),
+                   double(g.m_numSamplesDash), double(g.m_numSamplesDashBuf), double(g.m_numSamplesElementBuf),
+                   double(g.m_numSamplesCharBuf), double(g.m_numSamplesWordBuf)};
+    rec(c, 9);
+    std::vector<CPX> out(size_t(arg(5)));
+    for (size_t i = 0; i < out.size(); i++)
+        out[i] = g.nextOutputSample();
+    rec_cpx(out.data(), out.size());
+}
+
 /* The call scripts of the demodulator stages: the lengths from argument FIRST on (with STEP arguments per call); a call never exceeds
  * the buffer size the class was constructed with, nor PHZBUF_SIZE for WFM */
 static int call_len(size_t i, quint32 n, size_t pos)
@@ -516,7 +624,7 @@ int main(int argc, char **argv)
         {"nb", st_nb}, {"anf", st_anf}, {"iqbalance", st_iqbalance}, {"dcremoval", st_dcremoval}, {"fdestimate", st_fdestimate},
         {"goertzel", st_goertzel}, {"sampleclock", st_sampleclock}, {"movingavg", st_movingavg}, {"demod_am", st_demod_am},
         {"demod_sam", st_demod_sam}, {"demod_nfm", st_demod_nfm}, {"demod_wfm_mono", st_demod_wfm_mono},
-        {"demod_wfm_stereo", st_demod_wfm_stereo}};
+        {"demod_wfm_stereo", st_demod_wfm_stereo}, {"morse", st_morse}, {"morsegen", st_morsegen}};
     if (argc < 4) {
         fprintf(stderr, "usage: ref_driver STAGE IN OUT [numbers...]\n");
         return 2;

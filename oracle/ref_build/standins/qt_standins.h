@@ -5,6 +5,8 @@
 #define PEBBLE_ORACLE_QT_STANDINS_H
 #include <algorithm>
 #include <cassert>
+#include <cstdarg>
+#include <cstdio>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -48,10 +50,61 @@ private:
     std::recursive_mutex m;
 };
 
+/* one byte of a QString: the plugins' texts are Latin-1 (a multi-byte display string of the Morse table is only ever copied whole) */
+class QChar {
+public:
+    QChar() : c(0) {}
+    QChar(char v) : c(v) {}
+    char toLatin1() const { return c; }
+private:
+    char c;
+};
+
 class QString {
 public:
     QString() {}
     QString(const char *t) : s(t ? t : "") {}
+    bool isEmpty() const { return s.empty(); }
+    int length() const { return int(s.size()); }
+    void clear() { s.clear(); }
+    QChar at(int i) const { return QChar(s[size_t(i)]); }
+    QChar operator[](int i) const { return at(i); }
+    QString &append(const QString &o) { s += o.s; return *this; }
+    QString toLower() const
+    {
+        QString r(*this);
+        for (char &c : r.s)
+            if (c >= 'A' && c <= 'Z')
+                c = char(c - 'A' + 'a');
+        return r;
+    }
+    /* replaces every occurrence of the lowest-numbered %N place marker */
+    QString arg(const QString &a) const
+    {
+        int low = 100;
+        for (size_t i = 0; i + 1 < s.size(); i++)
+            if (s[i] == '%' && s[i + 1] >= '1' && s[i + 1] <= '9')
+                low = std::min(low, s[i + 1] - '0');
+        QString r;
+        for (size_t i = 0; i < s.size(); i++)
+            if (i + 1 < s.size() && s[i] == '%' && s[i + 1] - '0' == low) {
+                r.s += a.s;
+                i++;
+            } else
+                r.s += s[i];
+        return r;
+    }
+    QString &sprintf(const char *fmt, ...)
+    {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        s = buf;
+        return *this;
+    }
+    static QString number(long long v) { return QString(std::to_string(v).c_str()); }
     std::string s;
 };
 
@@ -81,16 +134,23 @@ public:
     static bool setCurrent(const QString &) { return false; }
 };
 
+/* connections are never made: whoever wants a signal's effect defines the signal's body (ref_driver.cpp) */
+#define SIGNAL(x) #x
+#define SLOT(x) #x
+#define Q_PLUGIN_METADATA(x)
+#define Q_INTERFACES(x)
 class QObject {
 public:
     QObject(QObject * = nullptr) {}
     virtual ~QObject() {}
+    template <typename... A> static bool connect(const A &...) { return false; }
 };
 /* swallows any value: the device interface passes its arguments and results through it, and no driven class reads one */
 class QVariant {
 public:
     QVariant() {}
     template <typename T> QVariant(const T &) {}
+    int toInt() const { return 0; }
 };
 class QStringList {};
 class QWidget;

@@ -117,7 +117,7 @@ class MorseRef:
         if wpm < 5:
             wpm = 5
         self.wpm = wpm
-        self.update_thresholds(DOT_MAGIC // wpm, True)   # reads m_wpmLimitLow/High before they are set: 10 / 50 (unpinned)
+        self.update_thresholds(DOT_MAGIC // wpm, True)   # reads m_wpmLimitLow/High before they are set: 10 / 50 is what every setSampleRate but the first finds (pinned); at the first, a choice
         self.set_goertzel()                               # updateGoertzel(1000, findBestGoertzelN(10, 50))
         self.shortest = int(DOT_MAGIC / (WPM_HIGH * 1.10))  # setMinMaxMark, :375-381
         self.sma = None                                   # m_dotDashThresholdFilter->reset()

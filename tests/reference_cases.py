@@ -269,8 +269,9 @@ def _mapscreen(r):
     return run
 
 
-# ---- the Morse restatement (tests/morse_ref.py): its Goertzel, TH_PEAK, clock and threshold-filter arithmetic.  Morse::stateMachine,
-# updateThresholds and findBestGoertzelN live in the Qt plugin, not in pebblelib: they stay pinned by hand (tests/test_morse_host.py)
+# ---- the Morse restatement (tests/morse_ref.py): its Goertzel, TH_PEAK, clock and threshold-filter arithmetic against the pebblelib
+# classes; the decoder proper (Morse::init, updateThresholds, stateMachine, findBestGoertzelN, setSampleRate) against the plugin's own
+# morse.cpp, compiled unmodified into the driver (stage morse, further down)
 def _morse_goertzel(rate, n, freq, switch_at, freq2):
     def run(O, x):
         from tests import morse_ref as M
@@ -324,6 +325,131 @@ def _morse_keyed(rate, n, freq, switch_at, seed):
         t = (np.arange(len(env)) + start) / float(rate)
         out[start:start + len(env)] += 0.05 * env * np.exp(2j * np.pi * f * t)
     return out
+
+
+def morse_view(pairs):
+    """The fixture of a stage-morse case.  The driver's records are decisions, events (sample, token, kind), starred events, statuses,
+    powers.  The fixture keeps the decisions whole, 32 to a value; the events, stars and statuses whole, cut into records of at most
+    160 values with their count in front; and the powers last, of which compress() keeps the tail"""
+    (kt, tn), (ke, ev), (ks, stars), (kq, st), pw = pairs
+    bits = np.concatenate([np.asarray(tn, dtype=np.int64), np.zeros(-len(tn) % 32, dtype=np.int64)]).reshape(-1, 32)
+    out = [(kt, np.array([float(len(tn))]))]
+    out += _chunks(kt, (bits << np.arange(32)).sum(axis=1).astype(np.float64))
+    for k, v in ((ke, ev), (ks, stars), (kq, st)):
+        c = _chunks(k, v)
+        out += [(k, np.array([float(len(c))]))] + c
+    return out + [pw]
+
+
+def _chunks(kind, v, step=160):
+    v = np.asarray(v, dtype=np.float64)
+    return [(kind, v[i:i + step]) for i in range(0, max(len(v), 1), step)]
+
+
+def morse_fixture(case):
+    """a stage-morse fixture taken apart again -> dict: decisions [results], events [(sample, token, kind)], stars, statuses [k, 10],
+    powers (the kept tail), results (the count)"""
+    recs = [t for _, t in expand(np.load(case.fixture))]
+    nres, pos = int(recs[0][0]), 1
+    nb = max(1, -(-(-(-nres // 32)) // 160))
+    packed = np.concatenate(recs[pos:pos + nb]).astype(np.int64); pos += nb
+    tones = ((packed[:, None] >> np.arange(32)) & 1).reshape(-1)[:nres]
+    parts = []
+    for _ in range(3):
+        k = int(recs[pos][0])
+        parts.append(np.concatenate(recs[pos + 1:pos + 1 + k])); pos += 1 + k
+    assert pos + 1 == len(recs)
+    return dict(results=nres, decisions=tones.astype(bool).tolist(),
+                events=[tuple(int(v) for v in e) for e in parts[0].reshape(-1, 3)], stars=[int(v) for v in parts[1]],
+                statuses=parts[2].reshape(-1, 10).astype(np.int64).tolist(), powers=recs[-1])
+
+
+def _morse_records(name, ref, seen):
+    from tests import morse_hard_cases as H
+    return [("x", np.array(ref.tones, dtype=np.float64)), ("x", np.array(ref.events, dtype=np.float64).reshape(-1)),
+            ("x", np.array(H.stars_of(name, ref.events), dtype=np.float64)), ("x", np.array([s for _, s in seen], dtype=np.float64).reshape(-1)),
+            ("v", np.array(ref.powers))]
+
+
+def _morse_hard(name, rate, frame):
+    def run(O, x):
+        from tests import morse_hard_cases as H
+        ref = H.reference(name, rate, frame)
+        assert min(ref.margins) > H.MARGIN, (name, rate, frame, min(ref.margins))   # the condition of every row, at every geometry
+        return _morse_records(name, ref, ref.seen)
+    return run
+
+
+def _morse_stream(rate, frame):
+    """the stream of tests/morse_cases.py (TEST at -1000 Hz, CWU and MORSE at +1000 Hz), with the readings of a hard row's plan"""
+    def run(O, x):
+        from tests import morse_cases as MC, morse_hard_cases as H
+        ref = H.CountingRef(rate, frame)
+        seen = H.feed(ref, x, morse_stream_plan(rate, frame), frame)
+        assert min(ref.margins) > MC.MARGIN
+        return _morse_records("", ref, seen)
+    return run
+
+
+def morse_stream_plan(rate, frame):
+    n1 = -(-int(2.2 * rate) // frame) * frame          # tests/morse_cases.stream's two lengths
+    n = n1 + -(-int(4.6 * rate) // frame) * frame
+    return sorted([(n1, "cwu")] + [(((n // frame) * q // 4) * frame, "status") for q in (1, 2, 3)], key=lambda p: p[0])
+
+
+# the hard rows at the other forms of the modem's decimator: no stage, one stage, a fractional modem rate (7812 of 7812.5); every hard
+# row runs at 64 000 (the merged 11-tap stage).  The frame is morse_cases.frames()' third: the block phase moves a sample a call
+MORSE_HARD_ELSEWHERE = (("spike2", 8000), ("mode_rate_midchar", 12000), ("speed_15_35_15", 31250))
+
+
+# ---- the Morse sender (tests/morsegen_ref.py) against the reference's own MorseGen (stage morsegen): setParams, setTextOut, then
+# nextOutputSample n times.  n is one pass through the text, the rise of the mark it starts over with and 256 samples more, so that
+# a fixture's tail lies inside a mark
+MORSEGEN_FS, MORSEGEN_F, MORSEGEN_DB = 64000, 1000.0, -6.0
+# (wpm, ms rise, text): test_morsegen_host's mark-table rows and its pinned 25 WPM row; the last has samplesPerTcw = 1536 barely above
+# the rise of 1472 samples (a dot's steady part is 64 samples)
+MORSEGEN_ROWS = ((50, 5, "TEST "), (40, 0, "CQ DE K1ABC "), (13, 20, "E"), (25, 5, "PARIS "), (50, 23, "TEN "))
+
+
+def _morsegen_ref(wpm, ms_rise, text):
+    from tests import morsegen_ref as G
+    g = G.MorseGenRef(MORSEGEN_FS)
+    g.set_params(MORSEGEN_F, G.db_to_amplitude(MORSEGEN_DB), wpm, ms_rise)
+    g.set_text_out(G.text_tokens(text))
+    return g
+
+
+def morsegen_samples(wpm, ms_rise, text):
+    g = _morsegen_ref(wpm, ms_rise, text)
+    return g.lengths()[4] + g.rise + 256
+
+
+def _keyed_edges(il):
+    """the samples at which an interleaved stream starts or stops being zero"""
+    z = (il[0::2] != 0) | (il[1::2] != 0)
+    return np.flatnonzero(np.diff(np.concatenate([[False], z]).astype(np.int8))).astype(np.float64)
+
+
+def morsegen_view(pairs):
+    """counts, samples -> counts, the mark boundaries read off the samples (records of at most 160 values, their number in front),
+    samples"""
+    (kc, counts), (kv, x) = pairs
+    e = _chunks("x", _keyed_edges(x))
+    return [(kc, counts), ("x", np.array([float(len(e))]))] + e + [(kv, x)]
+
+
+def _morsegen(wpm, ms_rise, text, n):
+    def run(O, x):
+        g = _morsegen_ref(wpm, ms_rise, text)
+        y, key = g.generate(n)
+        # the restatement's own mark table says what the samples say (the last sample of a fall may come out as an exact zero)
+        edges = _keyed_edges(_il(y))
+        starts = [s for s, _ in g.mark_starts if s < n]
+        assert [int(v) for v in edges[0::2]] == starts, (edges[:8], starts[:4])
+        assert all(key[int(a)] and key[int(b) - 1] and b - a >= (g.n_dot_buf - 1) for a, b in zip(edges[0::2], edges[1::2]))
+        counts = [g.rise, g.fall, g.n_dot, g.n_dot_buf, g.n_dash, g.n_dash_buf, g.n_element, g.n_char, g.n_word]
+        return [("x", np.array(counts, dtype=np.float64)), ("v", _il(y))]
+    return run
 
 
 def _clock_pairs(n):
@@ -760,6 +886,20 @@ def _build_cases():
         C.append(Case("morse_clock_%d" % mrate, "sampleclock", [mrate] + [v for p in pairs for v in p], lambda: np.zeros(0),
                       _morse_clock(mrate, pairs)))
     C.append(Case("morse_threshold_filter", "movingavg", [8, 21], _sma_input, _morse_sma(21)))
+    # the plugin's decoder itself on the hard rows of tests/morse_hard_cases.py and on the stream of tests/morse_cases.py: decisions,
+    # events, starred events and statuses (estimate, range flags, modem rate, N, the five thresholds) exact, powers to MORSE_POWER_BAR
+    from tests import morse_cases as MC, morse_hard_cases as H
+    where = [(nm, H.RATE, H.FRAME) for nm in H.NAMES] + [(nm, r, MC.frames(r)[2]) for nm, r in MORSE_HARD_ELSEWHERE]
+    for nm, rate, frame in where:
+        C.append(Case("morse_hard_%s_%d" % (nm, rate), "morse", H.driver_args(rate, frame, H.plan(nm, rate, frame)[1]),
+                      lambda nm=nm, rate=rate, frame=frame: H.stream(nm, rate, frame)[0], _morse_hard(nm, rate, frame),
+                      bar=MORSE_POWER_BAR, view=morse_view, meta=dict(row=nm, rate=rate, frame=frame)))
+    for wpm, ms_rise, text in MORSEGEN_ROWS:
+        total = morsegen_samples(wpm, ms_rise, text)
+        C.append(Case("morsegen_%d_%d" % (wpm, ms_rise), "morsegen", [MORSEGEN_FS, MORSEGEN_F, MORSEGEN_DB, wpm, ms_rise, total] + [ord(c) for c in text],
+                      lambda: np.zeros(0), _morsegen(wpm, ms_rise, text, total), bar=MORSEGEN_BAR, view=morsegen_view))
+    C.append(Case("morse_stream_64000", "morse", H.driver_args(64000, 2048, morse_stream_plan(64000, 2048)),
+                  lambda: MC.stream(64000, 2048)[0], _morse_stream(64000, 2048), bar=MORSE_POWER_BAR, view=morse_view))
     C += _demod_rows()
     return C
 
@@ -840,6 +980,11 @@ def _fd_spectrum():
 OOURA_BAR_DB = 1.1e-9
 # The Goertzel powers and peak averages of the Morse restatement against the reference's GoertzelOOK: measured bit for bit as well
 MORSE_POWER_BAR = 0.0
+# The sender's samples, the restatement's serial sums against the reference's MorseGen: counts and mark boundaries exact; of the
+# samples 13 to 234 in 50 000 to 500 000 values differ, by one unit in the last place, at the same sample numbers whatever the rise
+# (so in cos / sin of the phase sum: the compiler pairs the reference's cos(acc), sin(acc) into one sincos call, whose last place is
+# not always cos's and sin's own).  Measured 3.4e-18 to 4.0e-18 relative RMS; the bar is ten times the largest
+MORSEGEN_BAR = 4e-17
 
 CASES = None
 

@@ -1,4 +1,5 @@
-"""CPU tier: the Morse modem restatement (tests/morse_ref.py) pinned by hand-worked answers."""
+"""CPU tier: the Morse modem restatement (tests/morse_ref.py) pinned by hand-worked answers.  The plugin's own compiled decoder holds it
+too, on clean and on hard keying: tests/test_reference_pins.py (cases morse_hard_*, morse_stream_64000), tests/test_morse_hard_host.py."""
 import numpy as np
 import pytest
 

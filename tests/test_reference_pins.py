@@ -37,9 +37,24 @@ the library runs: the float loop state of SAM and NFM sample for sample, the pil
 queue (groups word for word).  Their base class Demod is two lines of this project's own in the driver; a SAM or NFM case's oracle
 function asserts from the oracle's loop state that the branch its input is there for was reached.
 
+The Morse decoder proper (plugins/MorseDigitalModem/morse.cpp and morsecode.cpp, compiled unmodified against stand-in widgets; cases
+morse_hard_*, morse_stream_64000): Morse() + setSampleRate, then processBlock frame by frame, setDemodMode and setSampleRate again where
+a row says so.  The plugin's signals are plain member calls whose bodies the driver defines: testbench() gives the power and decision of
+every Goertzel result, newOutput() the sample and the dot-dash buffer of every output (the token, also where the plugin prints '*'),
+and the members give the estimate, the range flags, the modem rate, N and the five thresholds at every reading.  The restatement
+(init, updateThresholds, stateMachine, findBestGoertzelN, setSampleRate) is held to it on every row of tests/morse_hard_cases.py at
+64 000 / 2048 (the merged 11-tap stage), on one row each at 8000 (no stage), 12 000 (one stage) and 31 250 (modem rate 7812 of 7812.5),
+and on tests/morse_cases.py's stream: decisions, events, starred events and statuses exact, powers bit for bit (bar 0).  The constructor
+leaves m_wpmSpeedCurrent, the range limits and the state unset and setSampleRate reads them; the driver builds the object over zeroed
+memory and writes m_wpmSpeedCurrent = 20 and the class's default limits (10 / 50) into it: the first call is this project's choice, not
+the reference's doing; every later setSampleRate, which finds what the plugin left there, is pinned (row mode_rate_midchar).
+The Morse sender (plugins/MorseGenDevice/morsegen.cpp; cases morsegen_*): setParams, setTextOut, nextOutputSample at the speeds and rise
+times of tests/test_morsegen_host.py and with samplesPerTcw barely above the rise: sample counts and mark boundaries exact, samples to
+one unit in the last place (measured 4.0e-18 relative RMS: a handful of cos / sin values, see reference_cases.MORSEGEN_BAR).
+
 NOT PINNED: CRdsDecode; Demod::processBlock's dispatch itself (demod.cpp brings the GUI; the driver restates it by its call sequence);
-Morse::stateMachine, updateThresholds and findBestGoertzelN, which live in the Qt plugin (plugins/MorseDigitalModem), not
-in pebblelib: they stay pinned by hand-worked numbers (tests/test_morse_host.py); the two vDSP primitives themselves; CFastFIR at 8192/4097 (its sizes are #defines inside fastfir.cpp, so the
+the Morse plugin's panel code (setupDataUi, refreshOutput, the slider slots: compiled, never run) and its C_FIR_filter path
+(m_useGoertzel is true); the two vDSP primitives themselves; CFastFIR at 8192/4097 (its sizes are #defines inside fastfir.cpp, so the
 variant cannot be built from the unmodified source).
 
 FOUND BY THESE PINS: FFT::m_isOverload is a member that only whole buffers rewrite; the oracle returned 0 for a short
@@ -52,6 +67,7 @@ comes out as the LOWER bound (-120 dB; 0 for snr).  The oracle and the device le
 other way round, returned the UPPER bound (cases fdestimate_* of tests/strength_cases.py: bp0_one_bin, bp0_no_bin, all_in_band,
 inverted).  Fixed in the stand-in, the oracle (po_db_clip, the snr bound) and the device's strength_finish; the 80 earlier pins did not
 move.  The wording of qMin / qMax / qBound is Qt's published qglobal.h as remembered, not checked against an installed Qt.
+The Morse decoder and sender pins (above) found no defect: restatement, recorded reference and device agree on every row.
 Demod_NFM's DC average, m_pllFreqErrorDC = (1.0 - m_pllDcAlpha) * m_pllFreqErrorDC + m_pllDcAlpha * m_ncoFrequency (demod_nfm.cpp:249): the
 first product has a double factor and is a double product, the second multiplies two floats and is a FLOAT product, rounded before the sum.
 The oracle and k_pll_demod had a double product there: 1e-8 to 3e-7 of the output off the binary, first at sample 20 to 1734 (all nine
@@ -113,7 +129,7 @@ def test_every_stage_of_the_table_has_a_case():
     stages = {c.stage for c in R.cases()}
     assert stages == {"mixer", "decimator", "downconvert", "fastfir", "fir", "iir", "resampler", "spectrum", "agc", "nb", "anf",
                       "iqbalance", "dcremoval", "fdestimate", "goertzel", "sampleclock", "movingavg", "mapscreen", "demod_am", "demod_sam", "demod_nfm", "demod_wfm_mono",
-                      "demod_wfm_stereo"}
+                      "demod_wfm_stereo", "morse", "morsegen"}
     assert all(c.bar <= R.MAX_BAR and c.bar_db <= R.MAX_BAR_DB for c in R.cases())
     assert all(os.path.getsize(c.fixture) < 16384 for c in R.cases())
 
